@@ -19,10 +19,16 @@ synthesises only the rank's own range (no rank ever holds N codes).  Where every
 scaling, no collective) is timed after the headline run and reported beside it under "query_replicas";
 `--shard query` makes it the headline instead.
 
-The timed region of K steps is repeated --reps times (each bracketed by barrier + synchronize); `value` is the
-median repetition, min/max are reported.  Steps rotate over 4 distinct query batches.  Rank 0 prints ONE JSON
-line with `roofline` (binding resource of the scan kernel: LDS gather bandwidth; measured HBM beside it) and
-`cpu_baseline` (the oracle restatement of the reference, timed on this host).
+The timed region is exactly K = --steps steps, bracketed by barrier + synchronize; `ms_per_step` is its time / K.
+--reps R > 1 repeats the region R times (R x K timed steps) and `value` is the median repetition, min/max are
+reported.  Steps rotate over 4 distinct query batches.  Rank 0 prints ONE JSON line with `roofline` (binding
+resource of the scan kernel: LDS gather bandwidth; measured HBM beside it) and `cpu_baseline` (the oracle
+restatement of the reference, timed on this host).
+
+--dump-outputs DIR: after the timed region, rank 0 writes what the last timed step returned to its caller --
+DIR/ids.npy (float64, exact for int32 ids) and DIR/dists.npy (float32), [queries][topk] -- so that two builds
+run with the same arguments (same seeded inputs) can be compared output for output.  Above 64 MB a fixed,
+seeded sample of query rows is written, their indices in DIR/rows.npy.
 """
 import argparse
 import json
@@ -39,6 +45,27 @@ sys.path.insert(0, HERE)
 HBM_PEAK_GBPS = 8000.0      # MI355X_MICROARCH.md: 8 TB/s spec (6.3 TB/s measured streaming copy)
 LDS_PEAK_GBPS = 157286.4    # 256 CUs x 256 B/clk (ds_read_b128) x 2.4 GHz, MI355X_MICROARCH.md section LDS
 N_BATCHES = 4               # distinct query batches the steps rotate over
+DUMP_LIMIT_BYTES = 64_000_000  # --dump-outputs: at most this much in all, .npy headers included
+
+
+def dump_outputs(out_dir, ids, dists, seed=0):
+    """Writes one step's result lists (host arrays [nq][k]) as out_dir/ids.npy (float64) and dists.npy (float32).
+    Beyond DUMP_LIMIT_BYTES a seeded sample of rows (sorted indices in rows.npy, float64).  Returns a summary."""
+    os.makedirs(out_dir, exist_ok=True)
+    ids = np.asarray(ids).astype(np.float64)
+    dists = np.asarray(dists).astype(np.float32)
+    nq, k = ids.shape
+    rows = None
+    budget = DUMP_LIMIT_BYTES - 3 * 128                         # three files' .npy headers
+    if nq * k * 12 > budget:
+        keep = min(nq, budget // (k * 12 + 8))
+        rows = np.sort(np.random.default_rng(seed).choice(nq, keep, replace=False))
+        ids, dists = ids[rows], dists[rows]
+        np.save(os.path.join(out_dir, "rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(out_dir, "ids.npy"), ids)
+    np.save(os.path.join(out_dir, "dists.npy"), dists)
+    return {"dir": out_dir, "files": ["ids.npy", "dists.npy"] + ([] if rows is None else ["rows.npy"]),
+            "rows": int(len(ids)), "rows_sampled": rows is not None, "topk": int(k)}
 
 
 def pmc_traffic(args, world):
@@ -253,7 +280,8 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--reps", type=int, default=10, help="repetitions of the timed K-step region (median is the value)")
+    ap.add_argument("--reps", type=int, default=1,
+                    help="repetitions of the timed K-step region (median is the value); above 1 the run times reps x K steps")
     ap.add_argument("--n", "--codes", dest="n", type=int, default=1_000_000,
                     help="codes in the whole index (under torch.distributed.run use --codes: its parser takes --n for its own)")
     ap.add_argument("--queries", type=int, default=1000)
@@ -290,7 +318,11 @@ def main():
                     help="N > 1 index shards of an index every rank could hold whole: skip the query-replica run timed beside it")
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl",
                     help="gloo = rehearsal of the N > 1 path on a box with fewer GPUs than ranks (ranks share GPUs)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed step's ids / distances as DIR/ids.npy (float64) and DIR/dists.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0 or args.reps < 1:
+        ap.error("--steps and --reps must be >= 1, --warmup >= 0")
 
     import torch
     import torch.distributed as dist
@@ -448,9 +480,10 @@ def main():
             sync(index)
             t0 = time.perf_counter()
             for i in range(args.steps):
-                step(i, index)
+                last = step(i, index)
             sync(index)
             times.append(time.perf_counter() - t0)
+        state["last"] = last   # the last timed step's result lists (complete after sync)
         t = torch.tensor(times, dtype=torch.float64, device=torch.device("cpu") if cpu_coll else dev)
         if world > 1:
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -469,6 +502,9 @@ def main():
         if int(flag.item()) > 0:
             state["ordered"] = False
             times = timed()
+    dumped = None
+    if args.dump_outputs and rank == 0:   # before the legs below reuse the output buffers
+        dumped = dump_outputs(args.dump_outputs, state["last"][0].cpu().numpy(), state["last"][1].cpu().numpy())
     # Sustained rate: the same steps back to back for >= --sustain-seconds (the K-step regions above last a few
     # milliseconds: boost clocks; MI355X_MICROARCH.md 'DVFS give-back').  Same work per step, nothing skipped.
     sustained = None
@@ -718,6 +754,8 @@ def main():
             result["config"]["queries_per_decode_pass"] = per_pass
         if replicas:
             result["query_replicas"] = replicas
+        if dumped:
+            result["dumped_outputs"] = dumped
         if world == 1 and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(wl, args, batches_np[0])
             result["vs_cpu_baseline_1_thread"] = result["value"] / result["cpu_baseline"]["value"]

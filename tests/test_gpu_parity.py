@@ -540,6 +540,30 @@ def _run_bench(extra, nproc=2, timeout=900, env=None):
     return json.loads(r.stdout.strip().splitlines()[-1])
 
 
+def test_bench_one_gpu_times_steps_and_dumps_the_last_one(gpu, oracle, tmp_path):
+    """bench.py at N = 1: --steps K is the number of timed steps, and --dump-outputs writes the lists the last of them
+    returned (step K - 1 answers query batch (K - 1) % 4), checked against the oracle on the bench's own index."""
+    import json
+    import sys
+    from argparse import Namespace
+    import bench
+    n, nq, k, steps = 100_000, 64, 100, 7
+    out, index_dir = str(tmp_path / "out"), str(tmp_path / "index")
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--codes", str(n), "--queries", str(nq), "--topk", str(k),
+           "--steps", str(steps), "--warmup", "1", "--check", "2", "--no-cpu-baseline", "--no-hbm-leg", "--sustain-seconds", "0",
+           "--host-steps", "0", "--index-dir", index_dir, "--dump-outputs", out]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["steps"] == steps and line["repetitions"]["count"] == 1 and line["repetitions"]["steps_each"] == steps
+    assert line["ms_per_step"] > 0 and line["dumped_outputs"]["rows"] == nq and not line["dumped_outputs"]["rows_sampled"]
+    ids, dists = np.load(os.path.join(out, "ids.npy")), np.load(os.path.join(out, "dists.npy"))
+    assert ids.dtype == np.float64 and dists.dtype == np.float32 and ids.shape == dists.shape == (nq, k)
+    z = np.load(os.path.join(index_dir, "pipeline_n%d_m8_d128.npz" % n))
+    qs = bench.make_queries(Namespace(data="pipeline", queries=nq, dim=128), 101 + (steps - 1) % bench.N_BATCHES)
+    assert_parity(ids.astype(np.int64), dists, oracle_topk(oracle, z["payload"], n, z["codebook"], qs, k), n)
+
+
 @pytest.mark.parametrize("mode", ["index_stream_parts", "index_pipeline", "query"])
 def test_bench_two_ranks_rehearsal(gpu, built, mode):
     """bench.py's N > 1 paths end to end, 2 ranks on GPU 0 (gloo instead of RCCL, ranks share the GPU):
