@@ -66,6 +66,40 @@ int dev_alloc(T** p, size_t count) {
     return DPQ_OK;
 }
 
+// An owned device array: alloc() goes through dev_alloc's error path, the destructor frees it.  Reads as a T*.
+template <class T>
+class DevBuf {
+  public:
+    using value_type = T;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        if (this != &o) {
+            reset();
+            p_ = o.p_;
+            o.p_ = nullptr;
+        }
+        return *this;
+    }
+    ~DevBuf() { reset(); }
+    // frees what it holds, then allocates `count` elements (at least one); on failure it holds nothing
+    int alloc(size_t count) {
+        reset();
+        return dev_alloc(&p_, count);
+    }
+    void reset() {
+        if (p_) hipFree(p_);
+        p_ = nullptr;
+    }
+    T* get() const { return p_; }
+    operator T*() const { return p_; }
+
+  private:
+    T* p_ = nullptr;
+};
+
 struct EventPair {
     int kind;  // 0 lut, 1 scan, 2 select, 3 quantise, 4 per-batch decode, 5 bootstrap
     hipEvent_t a, b;
@@ -97,16 +131,25 @@ struct Tuning {
     int select_fast = 1;     // the last level as a bucket sort from one histogram pass (select_kernel)  [DPQ_SELECT_FAST=0: radix select + rank count / bitonic network]
     int64_t batch_tile_nodes = (int64_t)16 << 20;
     bool relabel = true, fuse_quantise = true, async_overlap = true, boot_fullsort = false, tighten = true, strands = true,
-         force_strands = false, strand1 = true;
-    int s1_debug = 0;  // developer experiments of strand1_kernel  [DPQ_S1_DEBUG]
-    // a lane's scan waits for the other lane's previous select: 0 = never (default), 1 = only for the second batch of a
-    // burst, 2 = every batch  [DPQ_LANE_GATE].  Measured (scripts/gpu_lane_gate.sh, same box, M q/s): 0: 6.24 / 6.48,
-    // 1: 6.46 / 6.30, 2: 5.89 -- the gate turns the lanes' lockstep (both bootstraps, then both scans, then both selects:
-    // profiles/r04_timeline_default.txt) into the staggered order (profiles/r04_timeline_lane_gate.txt: a step = scan +
-    // select beside the other lane's bootstrap + a 12 us event wait) and the step does not get shorter: kept as a knob.
-    int lane_gate = 0;
-    int s1_scatter = 0;  // ... its one level in the low-discrepancy strip order instead of storage order  [DPQ_S1_SCATTER=1]
-    bool dummy_ = false;  // strand1: one query per pass takes strand1_kernel  [DPQ_STRAND1=0: strand_kernel<1>]
+         force_strands = false;
+    bool strand1 = true;  // one query per pass takes strand1_kernel  [DPQ_OPT_NO_STRAND1, DPQ_STRAND1=0: strand_kernel<1>]
+    int s1_debug = 0;     // developer experiments of strand1_kernel  [DPQ_S1_DEBUG]
+};
+
+// The device buffers a batch works in (one per pipeline lane), sized for `slots` padded queries and `cap` candidates each.
+struct Workspace {
+    int slots = 0, cap = 0;
+    DevBuf<float> d_lut32;         // exact tables [query][8][256]
+    DevBuf<float> d_lut32r;        // the same, rows by the labels of the plain-code scratch (only with d_relabel)
+    DevBuf<float> d_lut_min;       // [query][8] minima (anchor of the filter quantisation)
+    DevBuf<uint4> d_qtab;          // [slot groups][128 KB] filter tables of the cascade level being scanned
+    DevBuf<uint32_t> d_cand_count;
+    DevBuf<uint32_t> d_overflow;   // [slots] overflow flags
+    DevBuf<uint32_t> d_tight;      // [slots][kTightWords] tightening counters of the level being scanned (strand1: its
+                                   // one slot's kS1HistWords, what one query group's rows hold)
+    DevBuf<uint64_t> d_cand_key, d_thr_key;  // candidate keys [slots][cap], threshold keys [slots]
+    DevBuf<uint64_t> d_scratch;    // [slots][cap] contiguous copy of a slot's keys when they exceed the select's LDS list
+    DevBuf<uint8_t> d_batch_raw;   // the shard's plain codes, decoded once per batch (batch_decode); kept when the rest grows
 };
 
 struct dpq_index {
@@ -119,39 +162,28 @@ struct dpq_index {
     dpq::DeviceImage img;
     // owned device memory of the image
     // strand image (dpq_format.h): the stream pass's own layout of the same nodes (M = 8, shards with a bootstrap)
-    uint64_t* d_st_ckpt = nullptr;
-    uint32_t* d_st_mask = nullptr;
-    uint16_t* d_st_depth = nullptr;
-    uint32_t *d_st_pbase = nullptr, *d_strip_order = nullptr;
-    uint32_t* d_strip_segs = nullptr;      // the segments of the strips, in strip visiting order (a level too small for the
+    DevBuf<uint64_t> d_st_ckpt;
+    DevBuf<uint32_t> d_st_mask;
+    DevBuf<uint16_t> d_st_depth;
+    DevBuf<uint32_t> d_st_pbase, d_strip_order;
+    DevBuf<uint32_t> d_strip_segs;         // the segments of the strips, in strip visiting order (a level too small for the
     std::vector<int64_t> strip_seg_off;    // strand pass runs the chunk-per-wavefront pass over ITS strips' segments)
-    uint8_t* d_st_delta = nullptr;
+    DevBuf<uint8_t> d_st_delta;
     int64_t strand_bytes = 0;
-    uint8_t *d_nib = nullptr, *d_par = nullptr, *d_carry = nullptr, *d_mask = nullptr, *d_delta = nullptr, *d_ckpt = nullptr,
-            *d_raw = nullptr;
+    DevBuf<uint8_t> d_nib, d_par, d_carry, d_mask, d_delta, d_ckpt, d_raw;
     bool plain = false;  // uncompressed comparator index (fp32-accumulate rule, no id quirk)
-    uint64_t* d_seg_off = nullptr;
+    DevBuf<uint64_t> d_seg_off;
     // threshold bootstrap: inverted multi-index over the shard's nodes (dpq::SoA::mi_*); boot = it is in use
-    uint32_t *d_mi_cell = nullptr, *d_mi_code = nullptr, *d_mi_id = nullptr;
+    DevBuf<uint32_t> d_mi_cell, d_mi_code, d_mi_id;
     bool boot = false;
     int boot_classes = 0;
-    unsigned long long* d_boot_stamps = nullptr;  // developer diagnostics (dpq_debug_boot_stamps)
-    unsigned long long* d_s1_stamps = nullptr;    // developer diagnostics (dpq_debug_strand1_stamps)
-    uint8_t* d_batch_raw = nullptr;  // active lane: the shard's plain codes, decoded once per batch (batch_decode)
+    DevBuf<unsigned long long> d_boot_stamps;  // developer diagnostics (dpq_debug_boot_stamps)
+    DevBuf<unsigned long long> d_s1_stamps;    // developer diagnostics (dpq_debug_strand1_stamps)
     int batch_decode = 0;            // dpq_open_opts.batch_decode
-    uint8_t* d_relabel = nullptr;    // [M][256] code value -> label in the plain-code scratch (bank-aware; NULL = code values)
-    uint8_t* d_nbr = nullptr;        // [8][256][256] centroid neighbour lists of the bootstrap's sub-spaces (dpq_set_codebook)
-    float* d_codebook = nullptr;
-    // workspace, sized for ws_slots padded queries and ws_cap candidates each
-    int ws_slots = 0, ws_cap = 0;
-    float* d_lut32 = nullptr;       // exact tables [query][8][256]
-    float* d_lut32r = nullptr;      // the same, rows by the labels of the plain-code scratch (only with d_relabel)
-    float* d_lut_min = nullptr;     // [query][8] minima (anchor of the filter quantisation)
-    uint4* d_qtab = nullptr;        // [slot groups][128 KB] filter tables of the cascade level being scanned
-    uint32_t *d_cand_count = nullptr, *d_overflow = nullptr;
-    uint64_t *d_cand_key = nullptr, *d_thr_key = nullptr;  // candidate keys [slots][ws_cap], threshold keys [slots]
-    unsigned long long* d_counters = nullptr;  // [2] scan statistics (dpq_profile.exact_checks / candidates)
-    uint64_t* d_scratch = nullptr;   // [slots][ws_cap] contiguous copy of a slot's keys when they exceed the select's LDS list
+    DevBuf<uint8_t> d_relabel;       // [M][256] code value -> label in the plain-code scratch (bank-aware; NULL = code values)
+    DevBuf<uint8_t> d_nbr;           // [8][256][256] centroid neighbour lists of the bootstrap's sub-spaces (dpq_set_codebook)
+    DevBuf<float> d_codebook;
+    DevBuf<unsigned long long> d_counters;  // [2] scan statistics (dpq_profile.exact_checks / candidates)
     uint32_t* h_overflow = nullptr;  // pinned
     // pinned + mapped words, one per batch in flight: set by select_kernel when any query of the batch overflowed
     static constexpr int kFlagSlots = 64;
@@ -171,9 +203,9 @@ struct dpq_index {
     // on copy_in (the lanes' batches wait for it), results come down on copy_out behind the batch's last kernel
     static constexpr int kHostSlots = 16;
     struct HostSlot {
-        float* d_q = nullptr;
-        int32_t* d_ids = nullptr;
-        float* d_d = nullptr;
+        DevBuf<float> d_q;
+        DevBuf<int32_t> d_ids;
+        DevBuf<float> d_d;
         size_t qf = 0, oe = 0;       // capacities (floats / elements)
         int32_t* h_ids = nullptr;    // the caller's buffers of the batch in flight
         float* h_d = nullptr;
@@ -187,44 +219,29 @@ struct dpq_index {
     uint64_t host_seq = 0;
     // Pipelined batches alternate between two LANES = two workspaces + two internal streams, so that a batch's
     // table build runs under the previous batch's scan (the scan fills every CU's LDS and half its wave slots:
-    // the LUT kernel needs neither) and its bootstrap next to the previous batch's select.  The d_* workspace
-    // fields above are the ACTIVE lane's; the other lane is parked here.
-    struct Lane {
-        float *d_lut32 = nullptr, *d_lut_min = nullptr, *d_lut32r = nullptr;
-        uint4* d_qtab = nullptr;
-        uint32_t *d_cand_count = nullptr, *d_overflow = nullptr;
-        uint64_t *d_cand_key = nullptr, *d_thr_key = nullptr, *d_scratch = nullptr;
-        uint8_t* d_batch_raw = nullptr;
-        int ws_slots = 0, ws_cap = 0;
-    };
-    Lane parked;                     // workspace of the lane that is not active
+    // the LUT kernel needs neither) and its bootstrap next to the previous batch's select.  Every batch works in
+    // the ACTIVE lane's workspace.
+    Workspace lane[2];
     int active_lane = 0;
+    Workspace& ws() { return lane[active_lane]; }
+    const Workspace& ws() const { return lane[active_lane]; }
     hipStream_t lane_stream[2] = {nullptr, nullptr};
     hipEvent_t lane_ready[2] = {nullptr, nullptr};   // recorded on the caller's stream: the batch's inputs are there
-    // recorded behind a laned batch's last select: the OTHER lane's next scan waits for it.  Without it the two lanes fall
-    // into lockstep (kernel-trace timeline, profiles/r04_timeline_*): both bootstraps side by side, then both scans one
-    // after the other -- the second scan's workgroups take every CU the first one frees, and the first batch's select
-    // (35 KB of LDS) starves until the second scan's tail: 2 scans + select + bootstrap per 2 steps.  With the wait a step is
-    // scan + max(select, the other lane's bootstrap).
-    hipEvent_t lane_select_done[2] = {nullptr, nullptr};
-    bool lane_select_recorded[2] = {false, false};
-    int run_lane = -1;               // >= 0 while run_batch enqueues a laned batch: its lane
-    bool gate_this_batch = false;    // the batch being enqueued is the second of a burst (one batch in flight, on the other lane)
     uint64_t async_seq = 0;
     hipStream_t ordered_stream[2] = {nullptr, nullptr};  // caller streams with stream-ordered batches: stream k <-> workspace k
     bool ordered_stream_set[2] = {false, false};
     int64_t finish_reruns = 0;       // batches dpq_finish had to answer again (a query overflowed its candidate buffers)
     std::vector<Pending> pending;
     // staging for the host-pointer entry point
-    float* d_q_stage = nullptr;
-    int32_t* d_ids_stage = nullptr;
-    float* d_dists_stage = nullptr;
+    DevBuf<float> d_q_stage;
+    DevBuf<int32_t> d_ids_stage;
+    DevBuf<float> d_dists_stage;
     size_t q_stage_floats = 0, out_stage_elems = 0;
     // cascade plan: visiting order of the segments, level bounds, decoded level 0
     int plan_top_k = -1, plan_cap = -1, plan_coarse = -1;
     std::vector<int> level_off, level_cnt;
-    uint32_t* d_order = nullptr;
-    uint32_t *d_l0_id = nullptr, *d_l0_code = nullptr;
+    DevBuf<uint32_t> d_order;
+    DevBuf<uint32_t> d_l0_id, d_l0_code;
     int l0_segments = 0;
     // profiling
     bool prof = false;
@@ -247,7 +264,8 @@ struct dpq_index {
         return e;
     }
     bool prof_failed = false;        // an event could not be created / recorded: dpq_profile_read reports it
-    // developer hooks (dpq_debug_scan_time mode 3): the last batch's bootstrap and first-level scan launches as they were
+    // developer hooks (dpq_debug_scan_time mode 3): the last batch's bootstrap and first-level scan launches as they were;
+    // they point into the active workspace, so switching lanes or growing the workspace clears them
     dpq::BootArgs dbg_ba{};
     dpq::ScanArgs dbg_sa{};
     int dbg_boot_slots = 0, dbg_groups = 0, dbg_splits = 0;
@@ -303,78 +321,43 @@ Tuning resolve_tuning(const dpq_open_opts& o) {
         t.force_strands = t.force_strands || v == 2;
         v = 1; geti("DPQ_STRAND1", &v); t.strand1 = t.strand1 && v != 0;
         geti("DPQ_S1_DEBUG", &t.s1_debug);
-        geti("DPQ_S1_SCATTER", &t.s1_scatter);
-        geti("DPQ_LANE_GATE", &t.lane_gate);
     }
     return t;
 }
 
-void switch_lane(dpq_index* x, int lane) {
+// Makes `lane`'s workspace the active one.
+void use_lane(dpq_index* x, int lane) {
     if (lane == x->active_lane) return;
     x->dbg_groups = x->dbg_boot_slots = 0;  // (dpq_debug_scan_time mode 3 replays launches of the ACTIVE workspace)
-    dpq_index::Lane cur;
-    cur.d_lut32 = x->d_lut32; cur.d_lut_min = x->d_lut_min; cur.d_qtab = x->d_qtab; cur.d_lut32r = x->d_lut32r;
-    cur.d_cand_count = x->d_cand_count; cur.d_overflow = x->d_overflow;
-    cur.d_cand_key = x->d_cand_key; cur.d_thr_key = x->d_thr_key; cur.d_scratch = x->d_scratch;
-    cur.ws_slots = x->ws_slots; cur.ws_cap = x->ws_cap; cur.d_batch_raw = x->d_batch_raw;
-    const dpq_index::Lane& o = x->parked;
-    x->d_lut32 = o.d_lut32; x->d_lut_min = o.d_lut_min; x->d_qtab = o.d_qtab; x->d_lut32r = o.d_lut32r;
-    x->d_cand_count = o.d_cand_count; x->d_overflow = o.d_overflow;
-    x->d_cand_key = o.d_cand_key; x->d_thr_key = o.d_thr_key; x->d_scratch = o.d_scratch;
-    x->ws_slots = o.ws_slots; x->ws_cap = o.ws_cap; x->d_batch_raw = o.d_batch_raw;
-    x->parked = cur;
     x->active_lane = lane;
 }
 
-void free_parked_lane(dpq_index* x) {
-    dpq_index::Lane& o = x->parked;
-    hipFree(o.d_lut32); hipFree(o.d_lut_min); hipFree(o.d_qtab); hipFree(o.d_cand_count); hipFree(o.d_overflow);
-    hipFree(o.d_lut32r);
-    hipFree(o.d_cand_key); hipFree(o.d_thr_key); hipFree(o.d_scratch); hipFree(o.d_batch_raw);
-    o = dpq_index::Lane();
-}
-
-void free_workspace(dpq_index* x) {
-    x->dbg_groups = x->dbg_boot_slots = 0;  // the recorded launch arguments point into what is freed here
-    hipFree(x->d_lut32);
-    hipFree(x->d_lut32r);
-    x->d_lut32r = nullptr;
-    hipFree(x->d_lut_min);
-    hipFree(x->d_qtab);
-    hipFree(x->d_cand_count);
-    hipFree(x->d_cand_key);
-    hipFree(x->d_scratch);
-    hipFree(x->d_overflow);
-    hipFree(x->d_thr_key);
-    x->d_lut32 = nullptr;
-    x->d_lut_min = nullptr;
-    x->d_qtab = nullptr;
-    x->d_cand_count = x->d_overflow = nullptr;
-    x->d_cand_key = x->d_thr_key = x->d_scratch = nullptr;
-    x->ws_slots = x->ws_cap = 0;
-}
-
+// Grows the active workspace to at least `slots` padded queries and `cap` candidates each (its plain-code scratch stays).
 int ensure_workspace(dpq_index* x, int slots, int cap) {
-    if (slots <= x->ws_slots && cap <= x->ws_cap) return DPQ_OK;
-    slots = std::max(slots, x->ws_slots);
-    cap = std::max(cap, x->ws_cap);
-    free_workspace(x);
+    Workspace& w = x->ws();
+    if (slots <= w.slots && cap <= w.cap) return DPQ_OK;
+    slots = std::max(slots, w.slots);
+    cap = std::max(cap, w.cap);
+    x->dbg_groups = x->dbg_boot_slots = 0;  // the recorded launch arguments point into what is freed here
+    DevBuf<uint8_t> batch_raw = std::move(w.d_batch_raw);
+    w = Workspace();  // the old buffers go before the new ones are allocated
+    w.d_batch_raw = std::move(batch_raw);
     int rc;
-    if ((rc = dev_alloc(&x->d_lut32, (size_t)slots * x->M * 256))) return rc;
-    if (x->d_relabel && (rc = dev_alloc(&x->d_lut32r, (size_t)slots * x->M * 256))) return rc;
-    if ((rc = dev_alloc(&x->d_lut_min, (size_t)slots * x->M * 4))) return rc;  // four partial minima per (query, m)
-    if ((rc = dev_alloc(&x->d_qtab, (size_t)(slots / dpq::queries_per_group(x->M) + 1) *
-                                        (dpq::qtab_bytes_per_group(x->M) / sizeof(uint4)))))
+    if ((rc = w.d_lut32.alloc((size_t)slots * x->M * 256))) return rc;
+    if (x->d_relabel && (rc = w.d_lut32r.alloc((size_t)slots * x->M * 256))) return rc;
+    if ((rc = w.d_lut_min.alloc((size_t)slots * x->M * 4))) return rc;  // four partial minima per (query, m)
+    if ((rc = w.d_qtab.alloc((size_t)(slots / dpq::queries_per_group(x->M) + 1) *
+                             (dpq::qtab_bytes_per_group(x->M) / sizeof(uint4)))))
         return rc;
-    if ((rc = dev_alloc(&x->d_cand_count, (size_t)slots * dpq::kRegionStride))) return rc;
-    if ((rc = dev_alloc(&x->d_cand_key, (size_t)slots * cap))) return rc;
-    if ((rc = dev_alloc(&x->d_scratch, (size_t)slots * cap))) return rc;
-    // [slots] overflow flags, then [slots][kTightWords] tightening counters of the level being scanned
-    if ((rc = dev_alloc(&x->d_overflow, (size_t)slots * (1 + dpq::kTightWords)))) return rc;
-    if ((rc = dev_alloc(&x->d_thr_key, (size_t)slots))) return rc;
+    if ((rc = w.d_cand_count.alloc((size_t)slots * dpq::kRegionStride))) return rc;
+    if ((rc = w.d_cand_key.alloc((size_t)slots * cap))) return rc;
+    if ((rc = w.d_scratch.alloc((size_t)slots * cap))) return rc;
+    if ((rc = w.d_overflow.alloc((size_t)slots))) return rc;
+    if ((rc = w.d_tight.alloc((size_t)slots * dpq::kTightWords))) return rc;
+    if ((rc = w.d_thr_key.alloc((size_t)slots))) return rc;
     if (!x->h_overflow) DPQ_HIP(hipHostMalloc(reinterpret_cast<void**>(&x->h_overflow), sizeof(uint32_t) * 4096));
     if (!x->d_counters) {
-        if ((rc = dev_alloc(&x->d_counters, 2))) return rc;
+        if ((rc = x->d_counters.alloc(2))) return rc;
         DPQ_HIP(hipMemset(x->d_counters, 0, 16));
     }
     if (!x->h_any) {
@@ -382,9 +365,20 @@ int ensure_workspace(dpq_index* x, int slots, int cap) {
                               hipHostMallocMapped));
         DPQ_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&x->d_any), x->h_any, 0));
     }
-    x->ws_slots = slots;
-    x->ws_cap = cap;
+    w.slots = slots;
+    w.cap = cap;
     return DPQ_OK;
+}
+
+// order[j] = j * P mod n with P ~ n / golden ratio and gcd(P, n) = 1: a low-discrepancy visiting order of 0 .. n - 1
+// (every prefix is a spread-out sample)
+std::vector<uint32_t> golden_order(int64_t n) {
+    std::vector<uint32_t> order((size_t)n);
+    int64_t P = std::max<int64_t>(1, (int64_t)((double)n * 0.6180339887498949));
+    auto gcd = [](int64_t a, int64_t b) { while (b) { int64_t t = a % b; a = b; b = t; } return a; };
+    while (gcd(P, n) != 1) ++P;
+    for (int64_t j = 0; j < n; ++j) order[(size_t)j] = (uint32_t)((j * P) % n);
+    return order;
 }
 
 int auto_cap(int top_k) { return std::max(4096, 32 * top_k); }
@@ -472,22 +466,15 @@ int ensure_plan(dpq_index* x, int top_k, int cap, int shape) {
         prev = bnd;
     }
     if (!x->d_order && nseg > 0) {
-        // order[j] = j * P mod nseg, P ~ nseg / golden ratio, gcd(P, nseg) = 1
-        std::vector<uint32_t> order((size_t)nseg);
-        int64_t P = std::max<int64_t>(1, (int64_t)((double)nseg * 0.6180339887498949));
-        auto gcd = [](int64_t a, int64_t b) { while (b) { int64_t t = a % b; a = b; b = t; } return a; };
-        while (gcd(P, nseg) != 1) ++P;
-        for (int64_t j = 0; j < nseg; ++j) order[(size_t)j] = (uint32_t)((j * P) % nseg);
-        int rc = dev_alloc(&x->d_order, (size_t)nseg);
+        const std::vector<uint32_t> order = golden_order(nseg);
+        int rc = x->d_order.alloc((size_t)nseg);
         if (rc) return rc;
         DPQ_HIP(hipMemcpy(x->d_order, order.data(), (size_t)nseg * sizeof(uint32_t), hipMemcpyHostToDevice));
     }
     if (!x->boot && nseg > 0 && x->l0_segments != (int)s0) {
-        hipFree(x->d_l0_id);
-        hipFree(x->d_l0_code);
-        x->d_l0_id = x->d_l0_code = nullptr;
-        int rc = dev_alloc(&x->d_l0_id, (size_t)(s0 * S));
-        if (!rc) rc = dev_alloc(&x->d_l0_code, (size_t)(s0 * S * (x->M / 4)));
+        x->d_l0_code.reset();
+        int rc = x->d_l0_id.alloc((size_t)(s0 * S));
+        if (!rc) rc = x->d_l0_code.alloc((size_t)(s0 * S * (x->M / 4)));
         if (rc) return rc;
         DPQ_HIP(dpq::launch_decode_segments(x->img, x->d_order, (int)s0, x->d_l0_id, x->d_l0_code, nullptr));
         DPQ_HIP(hipStreamSynchronize(nullptr));
@@ -545,8 +532,8 @@ bool use_batch_decode(const dpq_index* x, int n_groups) {
     return batch_decode_possible(x) && (x->batch_decode > 0 || n_groups >= 3);
 }
 int ensure_batch_raw(dpq_index* x) {
-    if (x->d_batch_raw) return DPQ_OK;
-    return dev_alloc(&x->d_batch_raw, (size_t)batch_raw_bytes(x));
+    if (x->ws().d_batch_raw) return DPQ_OK;
+    return x->ws().d_batch_raw.alloc((size_t)batch_raw_bytes(x));
 }
 
 int splits_for(int n_seg_pass, int n_groups) {
@@ -580,112 +567,145 @@ Regions regions_for(const dpq_index* x, int n_seg_pass, int n_groups, int top_k,
     return r;
 }
 
-// One sub-batch (nq <= kMaxBatchQueries) end to end on `stream`.
-// flag_slot 0: synchronous (waits, checks the overflow word, reruns what overflowed); > 0: enqueue only,
-// dpq_finish looks at the word later.
-int run_batch(dpq_index* x, const float* d_queries, int nq, int top_k, int32_t* d_ids, float* d_dists,
-              hipStream_t stream, int flag_slot = 0) {
-    const int QG = dpq::queries_per_group(x->M);
-    const int nqp = (nq + QG - 1) / QG * QG;
-    const int ngroups = nqp / QG;
-    const int cap = x->cap_auto ? auto_cap(top_k) : std::max(x->cap, top_k);
-    int rc;
+// What run_batch does with one sub-batch, decided up front from its size and the index.
+struct Batch {
+    int nq, top_k;
+    int nqp, ngroups;  // slots, padded to whole query groups
+    int cap;           // candidate capacity the plan is made for
     // In-scan tightening is live when the scan runs its plain-code instantiation with at most kTightSplits
     // workgroups per query group (8 groups or more): the plan then keeps one filter level also for a large top_k.
-    const bool tight_plan = x->tune.tighten && nq > x->tune.stream_max &&
-                            ngroups * dpq::kTightSplits >= dpq::kMaxSplits && (x->plain || use_batch_decode(x, ngroups));
-    // Which stream pass a batch of up to stream_max queries takes: the strand image (a lane per run of 64 nodes) has 64 x
-    // fewer, 64 x longer work items than the chunk-per-wavefront decode, so it wants a big shard (dpq::kStrandMinNodes).
-    // ONE query per pass runs strand1_kernel, which tightens its threshold while it runs: one level over the whole shard.
-    const bool direct = !x->plain && nq <= x->tune.stream_max;
-    const bool strands = direct && x->img.st_ckpt != nullptr && (x->tune.force_strands || x->img.n_local >= dpq::kStrandMinNodes);
-    const bool strand1 = strands && x->tune.strand1 && dpq::stream_queries_per_pass(x->M, nq) == 1;
-    const bool strand1_tight = strand1 && x->tune.tighten && x->tune.plan_ratios[0] == 0;
-    if ((rc = ensure_plan(x, top_k, cap, (nq <= x->tune.coarse_below ? 1 : 0) | (tight_plan ? 2 : 0) | (strand1_tight ? 4 : 0)))) return rc;
-    int64_t stride = top_k;
-    for (size_t l = 1; l < x->level_cnt.size(); ++l)
-        stride = std::max(stride, regions_for(x, x->level_cnt[l], ngroups, top_k, cap).stride);
-    // strand1_kernel: a region per workgroup (no global atomics on the candidates' way): room for top_k keys each, 64..256
-    const int s1_region_cap = std::min(std::max(64, top_k), 256);
-    if (strand1) stride = std::max<int64_t>(stride, (int64_t)top_k + (int64_t)dpq::kStrand1Regions * s1_region_cap);
-    if (stride > INT32_MAX) return fail(DPQ_ERR_NOMEM, "candidate buffer too large");
-    if ((rc = ensure_workspace(x, nqp, (int)stride))) return rc;
-    stride = x->ws_cap;
-
-    dpq::ScanArgs sa{};
-    sa.img = x->img;
-    sa.fp32_accum = x->plain ? 1 : 0;
+    bool tight_plan;
+    // One or two queries (the reference's own call shape), up to dpq_open_opts.stream_max_queries (-1 = never): one
+    // query per pass over the compressed image, every node evaluated against the exact table (stream_kernel) -- no
+    // filter tables, no 64-query group machinery.
+    bool direct;
+    // Which stream pass: the strand image (a lane per run of 64 nodes) has 64 x fewer, 64 x longer work items than the
+    // chunk-per-wavefront decode, so it wants a big shard (dpq::kStrandMinNodes).  ONE query per pass runs
+    // strand1_kernel, which tightens its threshold while it runs: one level over the whole shard.
+    bool strands, strand1, strand1_tight;
     // Where the decode happens (dpq_open_opts.batch_decode): a batch of several query groups decodes the shard
     // once into plain codes that every group's filter pass reads (through L2 / Infinity Cache at the headline
     // sizes) -- the scan kernel then runs its plain-code instantiation with the DTC distance rule; a batch of one or
     // two groups, or a shard whose plain codes exceed the scratch budget, decodes inside the scan, once per group.
     // Measured on 1 M codes x 1000 queries (16 groups): scan 0.166 -> 0.122 ms, step 0.212 -> 0.172 ms.
-    // One or two queries (the reference's own call shape): one query per pass over the compressed image, every node
-    // evaluated against the exact table (stream_kernel) -- no filter tables, no 64-query group machinery.
-    // dpq_open_opts.stream_max_queries: the batch size up to which this mode is used (-1 = never).
-    const bool scratch = !direct && use_batch_decode(x, ngroups);
-    if (scratch && (rc = ensure_batch_raw(x))) return rc;
-    const int64_t tile_segs = scratch ? batch_tile_segments(x) : 0;
-    // One tile covers the whole shard (the common case): it is decoded here, ahead of the table build, so that both
-    // run under the previous pipelined batch's scan (neither needs LDS; the bootstrap that follows has to wait for
-    // that scan's LDS anyway), and every level scans its slice of the shard-ordered scratch.  Otherwise each level
-    // decodes its own tiles in list order.
-    const bool one_tile = scratch && tile_segs >= x->img.n_segments;
-    if (one_tile) {
-        {
-            Timer t(x, stream, 4);
-            DPQ_HIP(dpq::launch_decode_list(x->img, nullptr, x->img.n_segments, x->d_relabel,
-                                            reinterpret_cast<uint32_t*>(x->d_batch_raw), stream));
-        }
-        sa.img.raw = x->d_batch_raw;
-    }
+    bool scratch;
+    int64_t tile_segs;  // segments per tile of the scratch
+    bool one_tile;      // one tile holds the shard: decoded once, ahead of the table build
     // the scratch holds relabelled codes (bank-aware labels): the filter tables of this batch are laid
     // out by label, the scan maps a surviving node's code back before the exact check
-    const bool labelled = scratch && x->d_relabel != nullptr;
+    bool labelled;
+    bool boot_tables;   // the bootstrap writes the first filter level's tables (DPQ_OPT_NO_FUSE_QUANTISE: quantise_kernel)
+    int plan_shape;     // ensure_plan's shape bits
+    int64_t stride;     // keys per slot of the candidate buffers (the workspace's cap; prepare_batch)
+};
+
+Batch batch_mode(const dpq_index* x, int nq, int top_k) {
+    Batch b{};
+    const int QG = dpq::queries_per_group(x->M);
+    b.nq = nq;
+    b.top_k = top_k;
+    b.nqp = (nq + QG - 1) / QG * QG;
+    b.ngroups = b.nqp / QG;
+    b.cap = x->cap_auto ? auto_cap(top_k) : std::max(x->cap, top_k);
+    b.tight_plan = x->tune.tighten && nq > x->tune.stream_max && b.ngroups * dpq::kTightSplits >= dpq::kMaxSplits &&
+                   (x->plain || use_batch_decode(x, b.ngroups));
+    b.direct = !x->plain && nq <= x->tune.stream_max;
+    b.strands = b.direct && x->img.st_ckpt != nullptr && (x->tune.force_strands || x->img.n_local >= dpq::kStrandMinNodes);
+    b.strand1 = b.strands && x->tune.strand1 && dpq::stream_queries_per_pass(x->M, nq) == 1;
+    b.strand1_tight = b.strand1 && x->tune.tighten && x->tune.plan_ratios[0] == 0;
+    b.scratch = !b.direct && use_batch_decode(x, b.ngroups);
+    b.tile_segs = b.scratch ? batch_tile_segments(x) : 0;
+    b.one_tile = b.scratch && b.tile_segs >= x->img.n_segments;
+    b.labelled = b.scratch && x->d_relabel.get() != nullptr;
+    b.boot_tables = x->boot && x->tune.fuse_quantise && !b.direct;
+    b.plan_shape = (nq <= x->tune.coarse_below ? 1 : 0) | (b.tight_plan ? 2 : 0) | (b.strand1_tight ? 4 : 0);
+    return b;
+}
+
+// The batch's plan and the active workspace, sized for it; sets b->stride.
+int prepare_batch(dpq_index* x, Batch* b) {
+    int rc;
+    if ((rc = ensure_plan(x, b->top_k, b->cap, b->plan_shape))) return rc;
+    int64_t stride = b->top_k;
+    for (size_t l = 1; l < x->level_cnt.size(); ++l)
+        stride = std::max(stride, regions_for(x, x->level_cnt[l], b->ngroups, b->top_k, b->cap).stride);
+    // strand1_kernel: a region per workgroup (no global atomics on the candidates' way): room for top_k keys each, 64..256
+    const int s1_region_cap = std::min(std::max(64, b->top_k), 256);
+    if (b->strand1) stride = std::max<int64_t>(stride, (int64_t)b->top_k + (int64_t)dpq::kStrand1Regions * s1_region_cap);
+    if (stride > INT32_MAX) return fail(DPQ_ERR_NOMEM, "candidate buffer too large");
+    if ((rc = ensure_workspace(x, b->nqp, (int)stride))) return rc;
+    b->stride = x->ws().cap;
+    if (b->scratch && (rc = ensure_batch_raw(x))) return rc;
+    return DPQ_OK;
+}
+
+// The exact tables of the batch; also clears the overflow flags and tightening counters of its slots.  One tile covers
+// the whole shard (the common case): it is decoded here, ahead of the table build, so that both run under the previous
+// pipelined batch's scan (neither needs LDS; the bootstrap that follows has to wait for that scan's LDS anyway), and
+// every level scans its slice of the shard-ordered scratch.  Otherwise each level decodes its own tiles in list order.
+int build_tables(dpq_index* x, const Batch& b, const float* d_queries, hipStream_t stream) {
+    Workspace& w = x->ws();
+    if (b.one_tile) {
+        Timer t(x, stream, 4);
+        DPQ_HIP(dpq::launch_decode_list(x->img, nullptr, x->img.n_segments, x->d_relabel,
+                                        reinterpret_cast<uint32_t*>(w.d_batch_raw.get()), stream));
+    }
     {
         Timer t(x, stream, 0);
-        // also clears the overflow flags of the nqp slots
         // batches that scan the plain-code scratch also get the tables in the scratch's label order
-        DPQ_HIP(dpq::launch_lut_build(x->d_codebook, d_queries, nq, nqp, x->M, x->K, x->Ds, x->d_lut32, x->d_lut_min,
-                                      nullptr, x->d_overflow, scratch ? x->d_relabel : nullptr, x->d_lut32r,
-                                      x->tune.tighten ? x->d_overflow + x->ws_slots : nullptr, stream));
+        DPQ_HIP(dpq::launch_lut_build(x->d_codebook, d_queries, b.nq, b.nqp, x->M, x->K, x->Ds, w.d_lut32, w.d_lut_min,
+                                      nullptr, w.d_overflow, b.scratch ? x->d_relabel.get() : nullptr, w.d_lut32r,
+                                      x->tune.tighten ? w.d_tight.get() : nullptr, stream));
     }
     if (x->prof) x->prof_acc.lut_launches++;
-    x->h_any[flag_slot] = 0;  // the slot is free: its previous batch has been finished
+    return DPQ_OK;
+}
 
-    sa.lut32 = labelled ? x->d_lut32r : x->d_lut32;
-    sa.lut_min = x->d_lut_min;
-    sa.thr_key = x->d_thr_key;
+// What every scan launch of the batch starts from.
+dpq::ScanArgs batch_scan_args(const dpq_index* x, const Batch& b) {
+    const Workspace& w = x->ws();
+    dpq::ScanArgs sa{};
+    sa.img = x->img;
+    if (b.one_tile) sa.img.raw = w.d_batch_raw;
+    sa.fp32_accum = x->plain ? 1 : 0;
+    sa.lut32 = b.labelled ? w.d_lut32r.get() : w.d_lut32.get();
+    sa.lut_min = w.d_lut_min;
+    sa.thr_key = w.d_thr_key;
     sa.slot_query = nullptr;
-    sa.n_queries = nq;
-    sa.cand_count = x->d_cand_count;
-    sa.cand_key = x->d_cand_key;
-    sa.cand_stride = stride;
-    sa.region_off = top_k;
-    sa.counters = x->prof && !x->prof_scan_only ? x->d_counters : nullptr;
-    sa.qtab = x->d_qtab;
-    // in-scan threshold tightening (plain-code scans of this batch; scan_kernel): histograms behind the overflow flags.
+    sa.n_queries = b.nq;
+    sa.cand_count = w.d_cand_count;
+    sa.cand_key = w.d_cand_key;
+    sa.cand_stride = b.stride;
+    sa.region_off = b.top_k;
+    sa.counters = x->prof && !x->prof_scan_only ? x->d_counters.get() : nullptr;
+    sa.qtab = w.d_qtab;
+    // in-scan threshold tightening (plain-code scans of this batch; scan_kernel): the workspace's tightening counters.
     // Measured (1 M codes x 1000 queries): top-100 +2 % queries/s (exact checks 3002 -> 1813 and candidates 802 -> 404 per
     // query, select 21 -> 16 us); top-300 +7 %, top-512 +22 %.  On top of the two short levels a large top_k used to get
     // it cost 2 % (M = 8) to 7 % (M = 16) -- but ONE level with the tightening beats those plans (top-1000 1.89 -> 2.27 M
     // q/s, M = 16 1.21 -> 1.27 M, top-2048 0.97 -> 1.19 M): ensure_plan gives top_k > 512 one level when the launch
     // tightens, and the tightening stays off only where such a top_k meets a plan of several levels (shards > 2 M codes).
-    sa.tight_hist = x->tune.tighten && (top_k <= 512 || x->level_cnt.size() <= 2) ? x->d_overflow + x->ws_slots : nullptr;
-    sa.tight_k = top_k;
+    sa.tight_hist = x->tune.tighten && (b.top_k <= 512 || x->level_cnt.size() <= 2) ? w.d_tight.get() : nullptr;
+    sa.tight_k = b.top_k;
+    return sa;
+}
 
+// What every select launch of the batch starts from.
+dpq::SelectArgs batch_select_args(const dpq_index* x, const Batch& b, int32_t* d_ids, float* d_dists, int flag_slot) {
+    const Workspace& w = x->ws();
     dpq::SelectArgs se{};
     se.threads = x->tune.select_threads;
     se.fast_final = x->tune.select_fast;
-    se.cand_count = x->d_cand_count;
-    se.cand_key = x->d_cand_key;
-    se.cand_stride = stride;
-    se.region_off = top_k;
-    se.scratch = x->d_scratch;
-    se.lut32 = x->d_lut32;
+    se.cand_count = w.d_cand_count;
+    se.cand_key = w.d_cand_key;
+    se.cand_stride = b.stride;
+    se.region_off = b.top_k;
+    se.scratch = w.d_scratch;
+    se.lut32 = w.d_lut32;
     se.slot_query = nullptr;
-    se.top_k = top_k;
-    se.thr_key = x->d_thr_key;
-    se.overflow = x->d_overflow;
+    se.top_k = b.top_k;
+    se.thr_key = w.d_thr_key;
+    se.overflow = w.d_overflow;
     se.any_overflow = x->d_any + flag_slot;
     se.out_ids = d_ids;
     se.out_dists = d_dists;
@@ -693,215 +713,194 @@ int run_batch(dpq_index* x, const float* d_queries, int nq, int top_k, int32_t* 
     se.fp32_accum = x->plain ? 1 : 0;
     se.keep_thr = x->boot ? 1 : 0;
     se.stamps = x->d_boot_stamps ? x->d_boot_stamps + (size_t)kMaxBatchQueries * 8 : nullptr;
+    return se;
+}
 
-    const int64_t S = (int64_t)dpq::kChunk * x->img.chunks_per_segment;
-    const size_t n_levels = x->img.n_segments > 0 ? x->level_cnt.size() : 0;
-    if (n_levels == 0) {  // empty shard: every row is padding
-        se.final_pass = 1;
-        DPQ_HIP(dpq::launch_select(se, x->M, nq, stream));
-        return DPQ_OK;
+// Level 0 with a multi-index: the nodes of the query's best cells, evaluated exactly -> first threshold.
+int boot_level(dpq_index* x, const Batch& b, hipStream_t stream) {
+    const Workspace& w = x->ws();
+    const int top_k = b.top_k;
+    const int cap_env = x->tune.boot_cap;
+    dpq::BootArgs ba{};
+    ba.cell_start = x->d_mi_cell;
+    const bool full_sort = x->tune.boot_fullsort;  // developer A/B
+    ba.nbr = full_sort ? nullptr : x->d_nbr.get();
+    ba.n_classes = x->boot_classes;
+    ba.mi_code = x->d_mi_code;
+    ba.mi_id = x->d_mi_id;
+    ba.lut32 = w.d_lut32;
+    ba.slot_query = nullptr;
+    ba.top_k = top_k;
+    // 4-byte keys: up to 6144 of them keep the block at 40 KB of LDS (four blocks per CU).  Measured at top-100,
+    // M = 8 (scripts/gpu_boot_ab.sh): 3072 / 4096 / 6144 nodes -> 727 / 559 / 404 candidates per query and the
+    // same step time within 1.5 % (what the scan saves the bootstrap spends); 3072 is the shortest critical path.
+    // M = 16 (a class sees 2 of 16 sub-spaces: weaker cells; a check costs 16 gathers): 3072 / 6144 / 8192 ->
+    // 3003 / 1373 / 1021 candidates, 1.77 / 1.99 / 2.00 M q/s (scripts/gpu_m16_boot.sh).  top_k > 256
+    // (scripts/gpu_boot_cap1000.sh, top-1000): 8192 / 12288 / 16384 -> M = 8 1.81 / 1.83 / 1.81, M = 16
+    // 1.05 / 1.10 / 1.00 M q/s.  Round 3, one level + in-scan tightening (scripts/gpu_boot_cap_large_k.sh),
+    // 4096 / 6144 / 8192 / 12288: top-512 3.11 / 3.27 / 3.25 / 3.16, top-1000 1.76 / 1.96 / 2.10 / 2.28,
+    // top-2048 0.74 / 0.97 / 1.06 / 1.20, M = 16 top-1000 1.04 / 1.17 / 1.22 / 1.27 M q/s.
+    // (5888, not 6144, keys where the block is meant to stay at four per CU: 39 KB is what four blocks per CU take --
+    // see select_list_keys; M = 16 holds 16 KB of tables and runs three per CU either way)
+    const int cap_auto = top_k <= 256 ? (x->M <= 8 ? 3072 : 6144) : (top_k <= 640 && x->M <= 8) ? 5888 : 12288;
+    ba.cap = std::max(std::min(cap_env > 0 ? cap_env : cap_auto, 16384), std::max(top_k, 2048));
+    ba.cap = (ba.cap + 63) / 64 * 64;
+    const int target_env = x->tune.boot_target;
+    // Cells are walked in rounds until `target` nodes are evaluated.  At top_k <= 256 two thirds of the key list are
+    // enough: the 1 % of the queries whose first round of cells brings fewer than `cap` nodes (sparse neighbourhoods:
+    // 9 of 1000 on the bench index) then stop there instead of walking a second round -- they were the launch's
+    // last blocks (dev_boot_stamps.py: span 25.4 -> 22.4 us), their thresholds come from >= 2048 nodes instead of
+    // 3072 and the scan's own tightening does the rest (exact checks and candidates per query unchanged).
+    const int target_auto = top_k <= 256 ? std::max(top_k, ba.cap * 2 / 3) : ba.cap;
+    ba.target = target_env > 0 ? std::min(ba.cap, std::max(target_env, top_k)) : target_auto;
+    ba.thr_key = w.d_thr_key;
+    ba.cand_count = w.d_cand_count;
+    ba.fp32_accum = x->plain ? 1 : 0;
+    ba.stamps = x->d_boot_stamps;
+    ba.variant = x->tune.boot_variant;
+    ba.n_queries = b.nq;
+    // DPQ_OPT_NO_FUSE_QUANTISE: the first level's tables from quantise_kernel, as for every later level
+    ba.qtab = b.boot_tables ? w.d_qtab.get() : nullptr;
+    ba.relabel = b.scratch ? x->d_relabel.get() : nullptr;
+    ba.lut_min = w.d_lut_min;
+    const int slots = b.boot_tables ? b.nqp : b.nq;
+    {
+        Timer t(x, stream, 5);
+        DPQ_HIP(dpq::launch_bootstrap(ba, x->M, slots, stream));
     }
-    bool boot_built_tables = false;
-    bool scan_gate_passed = false;
-    for (size_t l = 0; l < n_levels; ++l) {
-        const bool final_pass = l + 1 == n_levels;
-        if (l == 0 && x->boot) {
-            // level 0 with a multi-index: the nodes of the query's best cells, evaluated exactly -> first threshold
-            const int cap_env = x->tune.boot_cap;
-            dpq::BootArgs ba{};
-            ba.cell_start = x->d_mi_cell;
-            const bool full_sort = x->tune.boot_fullsort;  // developer A/B
-            ba.nbr = full_sort ? nullptr : x->d_nbr;
-            ba.n_classes = x->boot_classes;
-            ba.mi_code = x->d_mi_code;
-            ba.mi_id = x->d_mi_id;
-            ba.lut32 = x->d_lut32;
-            ba.slot_query = nullptr;
-            ba.top_k = top_k;
-            // 4-byte keys: up to 6144 of them keep the block at 40 KB of LDS (four blocks per CU).  Measured at top-100,
-            // M = 8 (scripts/gpu_boot_ab.sh): 3072 / 4096 / 6144 nodes -> 727 / 559 / 404 candidates per query and the
-            // same step time within 1.5 % (what the scan saves the bootstrap spends); 3072 is the shortest critical path.
-            // M = 16 (a class sees 2 of 16 sub-spaces: weaker cells; a check costs 16 gathers): 3072 / 6144 / 8192 ->
-            // 3003 / 1373 / 1021 candidates, 1.77 / 1.99 / 2.00 M q/s (scripts/gpu_m16_boot.sh).  top_k > 256
-            // (scripts/gpu_boot_cap1000.sh, top-1000): 8192 / 12288 / 16384 -> M = 8 1.81 / 1.83 / 1.81, M = 16
-            // 1.05 / 1.10 / 1.00 M q/s.  Round 3, one level + in-scan tightening (scripts/gpu_boot_cap_large_k.sh),
-            // 4096 / 6144 / 8192 / 12288: top-512 3.11 / 3.27 / 3.25 / 3.16, top-1000 1.76 / 1.96 / 2.10 / 2.28,
-            // top-2048 0.74 / 0.97 / 1.06 / 1.20, M = 16 top-1000 1.04 / 1.17 / 1.22 / 1.27 M q/s.
-            // (5888, not 6144, keys where the block is meant to stay at four per CU: 39 KB is what four blocks per CU take --
-            // see select_list_keys; M = 16 holds 16 KB of tables and runs three per CU either way)
-            const int cap_auto = top_k <= 256 ? (x->M <= 8 ? 3072 : 6144) : (top_k <= 640 && x->M <= 8) ? 5888 : 12288;
-            ba.cap = std::max(std::min(cap_env > 0 ? cap_env : cap_auto, 16384), std::max(top_k, 2048));
-            ba.cap = (ba.cap + 63) / 64 * 64;
-            const int target_env = x->tune.boot_target;
-            // Cells are walked in rounds until `target` nodes are evaluated.  At top_k <= 256 two thirds of the key list are
-            // enough: the 1 % of the queries whose first round of cells brings fewer than `cap` nodes (sparse neighbourhoods:
-            // 9 of 1000 on the bench index) then stop there instead of walking a second round -- they were the launch's
-            // last blocks (dev_boot_stamps.py: span 25.4 -> 22.4 us), their thresholds come from >= 2048 nodes instead of
-            // 3072 and the scan's own tightening does the rest (exact checks and candidates per query unchanged).
-            const int target_auto = top_k <= 256 ? std::max(top_k, ba.cap * 2 / 3) : ba.cap;
-            ba.target = target_env > 0 ? std::min(ba.cap, std::max(target_env, top_k)) : target_auto;
-            ba.thr_key = x->d_thr_key;
-            ba.cand_count = x->d_cand_count;
-            ba.fp32_accum = x->plain ? 1 : 0;
-            ba.stamps = x->d_boot_stamps;
-            ba.variant = x->tune.boot_variant;
-            ba.n_queries = nq;
-            // DPQ_OPT_NO_FUSE_QUANTISE: the first level's tables from quantise_kernel, as for every later level
-            const bool fuse = x->tune.fuse_quantise;
-            ba.qtab = fuse && !direct ? x->d_qtab : nullptr;
-            ba.relabel = scratch ? x->d_relabel : nullptr;
-            ba.lut_min = x->d_lut_min;
-            boot_built_tables = fuse && !direct;
-            {
-                Timer t(x, stream, 5);
-                DPQ_HIP(dpq::launch_bootstrap(ba, x->M, fuse && !direct ? nqp : nq, stream));
-            }
-            if (x->prof) x->prof_acc.bootstrap_launches++;
-            x->dbg_ba = ba;
-            x->dbg_boot_slots = fuse && !direct ? nqp : nq;
-            continue;
-        }
-        if (l == 0) {
-            // level 0: the pre-decoded, query-independent list; every query evaluates it exactly
-            se.shared_id = x->d_l0_id;
-            se.shared_code = x->d_l0_code;
-            se.shared_n = (int)(x->level_cnt[0] * S);
+    if (x->prof) x->prof_acc.bootstrap_launches++;
+    x->dbg_ba = ba;
+    x->dbg_boot_slots = slots;
+    return DPQ_OK;
+}
+
+// Level l >= 1 of a batch of the stream pass: every node of the level's segments (sa.seg_list / n_seg_pass), or of its
+// share of the strips, against each query's exact table; one region per slot behind the carried winners.
+int stream_level(dpq_index* x, const Batch& b, size_t l, const dpq::ScanArgs& sa, dpq::SelectArgs& se,
+                 hipStream_t stream) {
+    const Workspace& w = x->ws();
+    const int nq = b.nq, top_k = b.top_k;
+    dpq::ScanArgs st = sa;
+    st.tight_hist = nullptr;
+    // one region per slot behind the carried winners, filled through a global counter
+    st.region_cap = se.region_cap = (int32_t)std::min<int64_t>(b.stride - top_k, INT32_MAX);
+    se.n_regions = 2;
+    DPQ_HIP(hipMemset2DAsync(w.d_cand_count + 1, sizeof(uint32_t) * dpq::kRegionStride, 0, sizeof(uint32_t), (size_t)nq,
+                             stream));
+    // Which stream pass: the strand image (a lane per run of 64 nodes) has 64 x fewer, 64 x longer work items than
+    // the chunk-per-wavefront decode, so it wants a big shard.  Measured, us per call (strand / chunk), one query:
+    // 1 M codes 35 / 37 pipelined but 89 / 59 as a single synchronous call, 4 M 50 / 49, 12.5 M 72 / 97, 32 M
+    // 113 / 172, 125 M 343 / 619; four queries per pass: 1 M 55 / 47, 4 M 76 / 61, 12.5 M 103 / 121, 32 M
+    // 195 / 230, 125 M 609 / 841.  From 8 M codes.
+    if (!b.strands) {
+        Timer t(x, stream, 1);
+        DPQ_HIP(dpq::launch_stream(st, nq, stream));
+        if (x->prof) x->prof_acc.stream_launches++;
+    } else {
+        // the pass over the strand image: the level's share of the strips (every strip exactly once over the levels,
+        // like the segments; the bootstrap consumed none)
+        const bool one_level = x->level_cnt.size() == 2;
+        const int64_t nseg = x->img.n_segments, ns = x->img.n_strips;
+        const int64_t lo = (int64_t)x->level_off[l] * ns / nseg;
+        const int64_t hi = l + 1 == x->level_cnt.size() ? ns : ((int64_t)x->level_off[l] + x->level_cnt[l]) * ns / nseg;
+        Timer t(x, stream, 1);
+        if (b.strand1) {
+            // one level: the strips in storage order (a workgroup sweeps a contiguous share)
+            st.seg_list = one_level ? nullptr : x->d_strip_order + lo;
+            st.n_seg_pass = (int32_t)(hi - lo);
+            // the kernel's candidate histogram (kS1HistWords of the batch's one slot, cleared by the table build); one
+            // launch per batch reads it (a later level would count in other units)
+            st.tight_hist = b.strand1_tight && one_level && nq == 1 ? w.d_tight.get() : nullptr;
+            st.debug_pass = x->tune.s1_debug ? 16 + x->tune.s1_debug : 0;
+            st.stamps = x->d_s1_stamps;
+            // a region per workgroup, counts written by the kernel
+            st.region_cap = se.region_cap = (int32_t)((b.stride - top_k) / dpq::kStrand1Regions);
+            se.n_regions = 1 + dpq::strand1_workgroups(st.n_seg_pass);
+            DPQ_HIP(dpq::launch_strand1(st, nq, stream));
+            if (x->prof) x->prof_acc.strand1_launches++;
+        } else if (hi - lo < 1536 && x->d_strip_segs && !x->tune.force_strands) {
+            // A level of few strips (one strip per wavefront: the launch takes a strip's 64 dependent steps however
+            // few there are) goes through the chunk-per-wavefront pass over the same nodes: measured break-even at
+            // about 1500 strips (6 M nodes).
+            st.seg_list = x->d_strip_segs + x->strip_seg_off[(size_t)lo];
+            st.n_seg_pass = (int32_t)(x->strip_seg_off[(size_t)hi] - x->strip_seg_off[(size_t)lo]);
+            DPQ_HIP(dpq::launch_stream(st, nq, stream));
+            if (x->prof) x->prof_acc.stream_launches++;
         } else {
-            se.shared_id = nullptr;
-            se.shared_code = nullptr;
-            se.shared_n = 0;
-            // a laned batch's first scan lets the other lane's previous batch finish its select first (see lane_select_done)
-            if (x->run_lane >= 0 && !scan_gate_passed && (x->tune.lane_gate == 1 ? x->gate_this_batch : x->tune.lane_gate == 2)) {
-                const int other = x->run_lane ^ 1;
-                if (x->lane_select_recorded[other]) DPQ_HIP(hipStreamWaitEvent(stream, x->lane_select_done[other], 0));
-                scan_gate_passed = true;
-            }
-            // filter scan of the next slice of segments; appends behind the carried winners
-            sa.seg_list = x->d_order + x->level_off[l];
-            sa.n_seg_pass = x->level_cnt[l];
-            const Regions rg = regions_for(x, sa.n_seg_pass, ngroups, top_k, cap);
-            if (direct) {
-                // one region per slot behind the carried winners, filled through a global counter
-                sa.region_cap = se.region_cap = (int32_t)std::min<int64_t>(stride - top_k, INT32_MAX);
-                se.n_regions = 2;
-                DPQ_HIP(hipMemset2DAsync(x->d_cand_count + 1, sizeof(uint32_t) * dpq::kRegionStride, 0, sizeof(uint32_t),
-                                         (size_t)nq, stream));
-                // Which stream pass: the strand image (a lane per run of 64 nodes) has 64 x fewer, 64 x longer work items than
-                // the chunk-per-wavefront decode, so it wants a big shard.  Measured, us per call (strand / chunk), one query:
-                // 1 M codes 35 / 37 pipelined but 89 / 59 as a single synchronous call, 4 M 50 / 49, 12.5 M 72 / 97, 32 M
-                // 113 / 172, 125 M 343 / 619; four queries per pass: 1 M 55 / 47, 4 M 76 / 61, 12.5 M 103 / 121, 32 M
-                // 195 / 230, 125 M 609 / 841.  From 8 M codes.
-                if (strands) {
-                    // the pass over the strand image: the level's share of the strips (every strip exactly once over
-                    // the levels, like the segments; the bootstrap consumed none)
-                    const int64_t nseg = x->img.n_segments, ns = x->img.n_strips;
-                    const int64_t lo = (int64_t)x->level_off[l] * ns / nseg;
-                    const int64_t hi = final_pass ? ns : ((int64_t)x->level_off[l] + x->level_cnt[l]) * ns / nseg;
-                    dpq::ScanArgs st = sa;
-                    // strand1_kernel's candidate histogram: the first 256 words of the tightening counters (cleared by the
-                    // table build); one launch per batch reads it (a later level would count in other units)
-                    st.tight_hist = strand1_tight && x->level_cnt.size() == 2 ? x->d_overflow + x->ws_slots : nullptr;
-                    st.debug_pass = strand1 ? (x->tune.s1_debug ? 16 + x->tune.s1_debug : 0) : 3;
-                    st.stamps = strand1 ? x->d_s1_stamps : nullptr;
-                    Timer t(x, stream, 1);
-                    // A level of few strips (one strip per wavefront: the launch takes a strip's 64 dependent steps
-                    // however few there are) goes through the chunk-per-wavefront pass over the same nodes: measured
-                    // break-even at about 1500 strips (6 M nodes).
-                    if (hi - lo < 1536 && x->d_strip_segs && !x->tune.force_strands && !strand1) {
-                        st.seg_list = x->d_strip_segs + x->strip_seg_off[(size_t)lo];
-                        st.n_seg_pass = (int32_t)(x->strip_seg_off[(size_t)hi] - x->strip_seg_off[(size_t)lo]);
-                        DPQ_HIP(dpq::launch_stream(st, nq, stream));
-                        if (x->prof) x->prof_acc.stream_launches++;
-                    } else {
-                        st.seg_list = x->d_strip_order + lo;
-                        st.n_seg_pass = (int32_t)(hi - lo);
-                        if (strand1) {  // a region per workgroup, counts written by the kernel
-                            // one level: the strips in storage order (a workgroup sweeps a contiguous share)
-                            if (x->level_cnt.size() == 2 && !x->tune.s1_scatter) st.seg_list = nullptr;
-                            st.region_cap = se.region_cap = (int32_t)((stride - top_k) / dpq::kStrand1Regions);
-                            se.n_regions = 1 + dpq::strand1_workgroups(st.n_seg_pass);
-                        }
-                        DPQ_HIP(dpq::launch_strand(st, nq, stream));
-                        if (x->prof) (strand1 ? x->prof_acc.strand1_launches : x->prof_acc.strand_launches)++;
-                    }
-                } else {
-                    Timer t(x, stream, 1);
-                    sa.tight_hist = nullptr;
-                    DPQ_HIP(dpq::launch_stream(sa, nq, stream));
-                    if (x->prof) x->prof_acc.stream_launches++;
-                }
-                if (x->prof) {
-                    x->prof_acc.scan_launches++;
-                    x->prof_acc.scan_stream_bytes +=
-                        (int64_t)nq * (int64_t)((double)x->info.device_bytes * sa.n_seg_pass / std::max(1, x->img.n_segments));
-                }
-            } else {
-            sa.region_cap = se.region_cap = rg.region_cap;
-            se.n_regions = 1 + rg.splits;
-            if (!(boot_built_tables && l == 1)) {  // the bootstrap kernel wrote the first level's tables itself
-                Timer t(x, stream, 3);
-                DPQ_HIP(dpq::launch_quantise(sa, ngroups, stream));
-            }
-            if (scratch && !one_tile) {
-                // the level's list in tiles: decode a tile into the scratch (list order), scan it with all groups
-                const uint32_t* list = sa.seg_list;
-                const int total = sa.n_seg_pass;
-                for (int t0 = 0; t0 < total; t0 += (int)tile_segs) {
-                    const int cnt = std::min<int>((int)tile_segs, total - t0);
-                    {
-                        Timer t(x, stream, 4);
-                        DPQ_HIP(dpq::launch_decode_list(x->img, list + t0, cnt, x->d_relabel,
-                                                        reinterpret_cast<uint32_t*>(x->d_batch_raw), stream));
-                    }
-                    sa.img.raw = x->d_batch_raw;
-                    sa.raw_by_pos = 1;
-                    sa.append = t0 > 0 ? 1 : 0;
-                    sa.seg_list = list + t0;
-                    sa.n_seg_pass = cnt;
-                    {
-                        Timer t(x, stream, 1);
-                        DPQ_HIP(dpq::launch_scan(sa, ngroups, rg.splits, stream));
-                    }
-                    if (x->prof && t0 > 0) x->prof_acc.scan_launches++;
-                }
-                sa.img.raw = nullptr;
-                sa.raw_by_pos = sa.append = 0;
-                sa.seg_list = list;
-                sa.n_seg_pass = total;
-            } else {
-                Timer t(x, stream, 1);
-                DPQ_HIP(dpq::launch_scan(sa, ngroups, rg.splits, stream));
-                if (l == 1) {
-                    x->dbg_sa = sa;
-                    x->dbg_groups = ngroups;
-                    x->dbg_splits = rg.splits;
-                }
-            }
-            if (x->prof) {
-                x->prof_acc.scan_launches++;
-                x->prof_acc.scan_stream_bytes +=
-                    (int64_t)((double)x->info.device_bytes * sa.n_seg_pass / std::max(1, x->img.n_segments));
-            }
-            }
+            st.seg_list = x->d_strip_order + lo;
+            st.n_seg_pass = (int32_t)(hi - lo);
+            DPQ_HIP(dpq::launch_strand(st, nq, stream));
+            if (x->prof) x->prof_acc.strand_launches++;
         }
-        if (x->prof) x->prof_acc.scan_node_query_pairs += (int64_t)x->level_cnt[l] * S * nq;
-        se.final_pass = final_pass ? 1 : 0;
-        {
-            Timer t(x, stream, 2);
-            DPQ_HIP(dpq::launch_select(se, x->M, nq, stream));
-        }
-        if (x->prof) x->prof_acc.select_launches++;
     }
+    if (x->prof) {
+        x->prof_acc.scan_launches++;
+        x->prof_acc.scan_stream_bytes +=
+            (int64_t)nq * (int64_t)((double)x->info.device_bytes * sa.n_seg_pass / std::max(1, x->img.n_segments));
+    }
+    return DPQ_OK;
+}
 
-    // The only host synchronisation of the batch: did any query drop candidates
-    // at some level (buffer overflow)?  Then its list may miss entries.
-    if (flag_slot > 0) return DPQ_OK;  // asynchronous batch: dpq_finish checks the word
+// Filter level l >= 1 (sa.seg_list / n_seg_pass): its tables, then its scan by every query group -- in tiles of the
+// plain-code scratch (decode a tile in list order, scan it with all groups, next tile) where one tile does not hold the
+// shard.
+int filter_level(dpq_index* x, const Batch& b, size_t l, dpq::ScanArgs sa, dpq::SelectArgs& se, hipStream_t stream) {
+    const Workspace& w = x->ws();
+    const Regions rg = regions_for(x, sa.n_seg_pass, b.ngroups, b.top_k, b.cap);
+    sa.region_cap = se.region_cap = rg.region_cap;
+    se.n_regions = 1 + rg.splits;
+    if (!(b.boot_tables && l == 1)) {  // the bootstrap kernel wrote the first level's tables itself
+        Timer t(x, stream, 3);
+        DPQ_HIP(dpq::launch_quantise(sa, b.ngroups, stream));
+    }
+    if (b.scratch && !b.one_tile) {
+        for (int t0 = 0; t0 < sa.n_seg_pass; t0 += (int)b.tile_segs) {
+            const int cnt = std::min<int>((int)b.tile_segs, sa.n_seg_pass - t0);
+            {
+                Timer t(x, stream, 4);
+                DPQ_HIP(dpq::launch_decode_list(x->img, sa.seg_list + t0, cnt, x->d_relabel,
+                                                reinterpret_cast<uint32_t*>(w.d_batch_raw.get()), stream));
+            }
+            dpq::ScanArgs tile = sa;
+            tile.img.raw = w.d_batch_raw;
+            tile.raw_by_pos = 1;
+            tile.append = t0 > 0 ? 1 : 0;
+            tile.seg_list = sa.seg_list + t0;
+            tile.n_seg_pass = cnt;
+            {
+                Timer t(x, stream, 1);
+                DPQ_HIP(dpq::launch_scan(tile, b.ngroups, rg.splits, stream));
+            }
+            if (x->prof && t0 > 0) x->prof_acc.scan_launches++;
+        }
+    } else {
+        Timer t(x, stream, 1);
+        DPQ_HIP(dpq::launch_scan(sa, b.ngroups, rg.splits, stream));
+        if (l == 1) {
+            x->dbg_sa = sa;
+            x->dbg_groups = b.ngroups;
+            x->dbg_splits = rg.splits;
+        }
+    }
+    if (x->prof) {
+        x->prof_acc.scan_launches++;
+        x->prof_acc.scan_stream_bytes +=
+            (int64_t)((double)x->info.device_bytes * sa.n_seg_pass / std::max(1, x->img.n_segments));
+    }
+    return DPQ_OK;
+}
+
+// The only host synchronisation of a synchronous batch: did any query drop candidates at some level (buffer
+// overflow)?  Then its list may miss entries: those queries are answered again.  sa / se: the batch's last launches.
+int rerun_overflowed(dpq_index* x, const Batch& b, dpq::ScanArgs sa, dpq::SelectArgs se, hipStream_t stream) {
+    const Workspace& w = x->ws();
+    const int nq = b.nq, top_k = b.top_k;
     DPQ_HIP(hipStreamSynchronize(stream));
     if (*reinterpret_cast<volatile uint32_t*>(x->h_any) == 0) return DPQ_OK;
     std::vector<int> over;
     for (int base = 0; base < nq; base += 4096) {
         const int n = std::min(4096, nq - base);
-        DPQ_HIP(hipMemcpyAsync(x->h_overflow, x->d_overflow + base, sizeof(uint32_t) * n, hipMemcpyDeviceToHost,
+        DPQ_HIP(hipMemcpyAsync(x->h_overflow, w.d_overflow.get() + base, sizeof(uint32_t) * n, hipMemcpyDeviceToHost,
                                stream));
         DPQ_HIP(hipStreamSynchronize(stream));
         for (int i = 0; i < n; ++i)
@@ -913,11 +912,12 @@ int run_batch(dpq_index* x, const float* d_queries, int nq, int top_k, int32_t* 
     // k-th key of the incomplete list is still a valid upper bound (its entries
     // are real nodes) and it is tight, so the number of nodes under it is about
     // top_k; grow the buffer and repeat in the (pathological) case it is not.
+    const int QG = dpq::queries_per_group(x->M);
     const int slots2 = ((int)over.size() + QG - 1) / QG * QG;
     const int ng2 = slots2 / QG;
     std::vector<int32_t> slot_query((size_t)slots2, -1);
-    std::vector<uint64_t> h_key((size_t)nqp), k2((size_t)slots2, ~0ull);
-    DPQ_HIP(hipMemcpy(h_key.data(), x->d_thr_key, sizeof(uint64_t) * nqp, hipMemcpyDeviceToHost));
+    std::vector<uint64_t> h_key((size_t)b.nqp), k2((size_t)slots2, ~0ull);
+    DPQ_HIP(hipMemcpy(h_key.data(), w.d_thr_key, sizeof(uint64_t) * b.nqp, hipMemcpyDeviceToHost));
     for (size_t i = 0; i < over.size(); ++i) {
         slot_query[i] = over[i];
         k2[i] = h_key[(size_t)over[i]];
@@ -927,26 +927,19 @@ int run_batch(dpq_index* x, const float* d_queries, int nq, int top_k, int32_t* 
     int64_t rcap2 = std::max<int64_t>(2 * (int64_t)top_k, 1024);
     for (int attempt = 0;; ++attempt) {
         const int64_t stride2 = (int64_t)top_k + (int64_t)splits2 * rcap2;
-        int32_t* d_slot_query = nullptr;
-        uint32_t *c_count = nullptr, *c_over = nullptr;
-        uint64_t *c_keys = nullptr, *c_scratch = nullptr, *c_tk = nullptr;
-        uint4* c_qtab = nullptr;
-        auto cleanup = [&]() {
-            hipFree(d_slot_query); hipFree(c_count); hipFree(c_over); hipFree(c_keys); hipFree(c_scratch); hipFree(c_tk);
-            hipFree(c_qtab);
-        };
-        rc = stride2 > INT32_MAX ? fail(DPQ_ERR_NOMEM, "candidate buffer too large") : DPQ_OK;
-        if (!rc) rc = dev_alloc(&d_slot_query, (size_t)slots2);
-        if (!rc) rc = dev_alloc(&c_count, (size_t)slots2 * dpq::kRegionStride);
-        if (!rc) rc = dev_alloc(&c_over, (size_t)slots2);
-        if (!rc) rc = dev_alloc(&c_keys, (size_t)slots2 * stride2);
-        if (!rc) rc = dev_alloc(&c_scratch, (size_t)slots2 * stride2);
-        if (!rc) rc = dev_alloc(&c_tk, (size_t)slots2);
-        if (!rc) rc = dev_alloc(&c_qtab, (size_t)ng2 * (dpq::qtab_bytes_per_group(x->M) / sizeof(uint4)));
-        if (rc) {
-            cleanup();
-            return rc;
-        }
+        if (stride2 > INT32_MAX) return fail(DPQ_ERR_NOMEM, "candidate buffer too large");
+        DevBuf<int32_t> d_slot_query;
+        DevBuf<uint32_t> c_count, c_over;
+        DevBuf<uint64_t> c_keys, c_scratch, c_tk;
+        DevBuf<uint4> c_qtab;
+        int rc = d_slot_query.alloc((size_t)slots2);
+        if (!rc) rc = c_count.alloc((size_t)slots2 * dpq::kRegionStride);
+        if (!rc) rc = c_over.alloc((size_t)slots2);
+        if (!rc) rc = c_keys.alloc((size_t)slots2 * stride2);
+        if (!rc) rc = c_scratch.alloc((size_t)slots2 * stride2);
+        if (!rc) rc = c_tk.alloc((size_t)slots2);
+        if (!rc) rc = c_qtab.alloc((size_t)ng2 * (dpq::qtab_bytes_per_group(x->M) / sizeof(uint4)));
+        if (rc) return rc;
         hipError_t e = hipSuccess;
         auto chk = [&](hipError_t r) { if (e == hipSuccess) e = r; };
         chk(hipMemcpy(d_slot_query, slot_query.data(), sizeof(int32_t) * slots2, hipMemcpyHostToDevice));
@@ -956,9 +949,9 @@ int run_batch(dpq_index* x, const float* d_queries, int nq, int top_k, int32_t* 
         sa.seg_list = nullptr;
         sa.n_seg_pass = x->img.n_segments;
         sa.tight_hist = nullptr;  // the rerun starts from final thresholds
-        if (!one_tile) {  // a tiled scratch holds the last tile only: the rerun decodes inside the scan, code values as labels
+        if (!b.one_tile) {  // a tiled scratch holds the last tile only: the rerun decodes inside the scan, code values as labels
             sa.img.raw = x->img.raw;
-            sa.lut32 = x->d_lut32;
+            sa.lut32 = w.d_lut32;
         }
         sa.thr_key = c_tk;
         sa.slot_query = d_slot_query;
@@ -976,7 +969,6 @@ int run_batch(dpq_index* x, const float* d_queries, int nq, int top_k, int32_t* 
         uint32_t max_cnt = 0;
         for (uint32_t c : h_cnt) max_cnt = std::max(max_cnt, c);
         if (e == hipSuccess && (int64_t)max_cnt > rcap2 && attempt < 4) {
-            cleanup();
             rcap2 = (int64_t)max_cnt + 64;
             continue;
         }
@@ -996,13 +988,89 @@ int run_batch(dpq_index* x, const float* d_queries, int nq, int top_k, int32_t* 
         se.final_pass = 1;
         chk(dpq::launch_select(se, x->M, slots2, stream));
         chk(hipStreamSynchronize(stream));
-        cleanup();
         if (e != hipSuccess) return fail(DPQ_ERR_HIP, std::string("overflow rerun: ") + hipGetErrorString(e));
         if ((int64_t)max_cnt > rcap2) return fail(DPQ_ERR_NOMEM, "candidate overflow persisted after reruns");
         break;
     }
     if (x->prof) x->prof_acc.overflow_reruns += (int64_t)over.size();
     return DPQ_OK;
+}
+
+// One sub-batch (nq <= kMaxBatchQueries) end to end on `stream`.
+// flag_slot 0: synchronous (waits, checks the overflow word, reruns what overflowed); > 0: enqueue only,
+// dpq_finish looks at the word later.
+int run_batch(dpq_index* x, const float* d_queries, int nq, int top_k, int32_t* d_ids, float* d_dists,
+              hipStream_t stream, int flag_slot = 0) {
+    Batch b = batch_mode(x, nq, top_k);
+    int rc;
+    if ((rc = prepare_batch(x, &b))) return rc;
+    if ((rc = build_tables(x, b, d_queries, stream))) return rc;
+    x->h_any[flag_slot] = 0;  // the slot is free: its previous batch has been finished
+    dpq::ScanArgs sa = batch_scan_args(x, b);
+    dpq::SelectArgs se = batch_select_args(x, b, d_ids, d_dists, flag_slot);
+
+    const int64_t S = (int64_t)dpq::kChunk * x->img.chunks_per_segment;
+    const size_t n_levels = x->img.n_segments > 0 ? x->level_cnt.size() : 0;
+    if (n_levels == 0) {  // empty shard: every row is padding
+        se.final_pass = 1;
+        DPQ_HIP(dpq::launch_select(se, x->M, nq, stream));
+        return DPQ_OK;
+    }
+    for (size_t l = 0; l < n_levels; ++l) {
+        if (l == 0 && x->boot) {
+            if ((rc = boot_level(x, b, stream))) return rc;
+            continue;
+        }
+        if (l == 0) {
+            // level 0: the pre-decoded, query-independent list; every query evaluates it exactly
+            se.shared_id = x->d_l0_id;
+            se.shared_code = x->d_l0_code;
+            se.shared_n = (int)(x->level_cnt[0] * S);
+        } else {
+            se.shared_id = nullptr;
+            se.shared_code = nullptr;
+            se.shared_n = 0;
+            // the next slice of segments; its candidates go behind the carried winners
+            sa.seg_list = x->d_order + x->level_off[l];
+            sa.n_seg_pass = x->level_cnt[l];
+            if ((rc = b.direct ? stream_level(x, b, l, sa, se, stream) : filter_level(x, b, l, sa, se, stream))) return rc;
+        }
+        if (x->prof) x->prof_acc.scan_node_query_pairs += (int64_t)x->level_cnt[l] * S * nq;
+        se.final_pass = l + 1 == n_levels ? 1 : 0;
+        {
+            Timer t(x, stream, 2);
+            DPQ_HIP(dpq::launch_select(se, x->M, nq, stream));
+        }
+        if (x->prof) x->prof_acc.select_launches++;
+    }
+    if (flag_slot > 0) return DPQ_OK;  // asynchronous batch: dpq_finish checks the word
+    return rerun_overflowed(x, b, sa, se, stream);
+}
+
+// The full-index filter scan of the dpq_debug_scan_* hooks: nq slots of the active workspace with the thresholds and
+// tables the last batch left behind (at most DPQ_DEBUG_NSEG segments); *splits <= 0 becomes splits_for's.
+dpq::ScanArgs debug_scan_args(const dpq_index* x, int nq, int* splits) {
+    const Workspace& w = x->ws();
+    const int QG = dpq::queries_per_group(x->M);
+    dpq::ScanArgs sa{};
+    sa.img = x->img;
+    sa.fp32_accum = x->plain ? 1 : 0;
+    sa.lut32 = w.d_lut32;
+    sa.lut_min = w.d_lut_min;
+    sa.thr_key = w.d_thr_key;
+    sa.slot_query = nullptr;
+    sa.n_queries = nq;
+    sa.seg_list = nullptr;
+    sa.n_seg_pass = x->img.n_segments;
+    if (const char* e = getenv("DPQ_DEBUG_NSEG")) sa.n_seg_pass = std::min(x->img.n_segments, atoi(e));
+    if (*splits <= 0) *splits = splits_for(sa.n_seg_pass, (nq + QG - 1) / QG);
+    sa.cand_count = w.d_cand_count;
+    sa.cand_key = w.d_cand_key;
+    sa.cand_stride = w.cap;
+    sa.region_off = 0;
+    sa.region_cap = std::max(1, w.cap / *splits);
+    sa.qtab = w.d_qtab;
+    return sa;
 }
 
 int open_from_payload(const uint8_t* payload, int64_t n_bytes, int64_t n_codes, int M, int K,
@@ -1051,52 +1119,48 @@ int open_from_payload(const uint8_t* payload, int64_t n_bytes, int64_t n_codes, 
     x->cap = o.cand_capacity;
     x->batch_decode = o.batch_decode;
     x->tune = tune0;
-    auto up = [&](auto** dptr, const void* src, size_t bytes) -> int {
-        using T = std::remove_pointer_t<std::remove_pointer_t<decltype(dptr)>>;
-        int r = dev_alloc(dptr, (bytes + sizeof(T) - 1) / sizeof(T) + 64 / sizeof(T));
+    auto up = [&](auto& buf, const void* src, size_t bytes) -> int {
+        using T = typename std::remove_reference_t<decltype(buf)>::value_type;
+        int r = buf.alloc((bytes + sizeof(T) - 1) / sizeof(T) + 64 / sizeof(T));
         if (r) return r;
         if (bytes) {
-            hipError_t e = hipMemcpy(*dptr, src, bytes, hipMemcpyHostToDevice);
+            hipError_t e = hipMemcpy(buf, src, bytes, hipMemcpyHostToDevice);
             if (e != hipSuccess) return fail(DPQ_ERR_HIP, std::string("upload: ") + hipGetErrorString(e));
         }
         return DPQ_OK;
     };
-    rc = up(&x->d_nib, soa.nib.data(), soa.nib.size());
-    if (!rc) rc = up(&x->d_par, soa.par.data(), soa.par.size());
-    if (!rc) rc = up(&x->d_carry, soa.carry.data(), soa.carry.size());
-    if (!rc) rc = up(&x->d_mask, soa.mask.data(), soa.mask.size());
-    if (!rc) rc = up(&x->d_delta, soa.delta.data(), soa.delta.size());
-    if (!rc) rc = up(&x->d_seg_off, soa.seg_delta_off.data(), soa.seg_delta_off.size() * 8);
-    if (!rc) rc = up(&x->d_ckpt, soa.seg_ckpt.data(), soa.seg_ckpt.size());
+    rc = up(x->d_nib, soa.nib.data(), soa.nib.size());
+    if (!rc) rc = up(x->d_par, soa.par.data(), soa.par.size());
+    if (!rc) rc = up(x->d_carry, soa.carry.data(), soa.carry.size());
+    if (!rc) rc = up(x->d_mask, soa.mask.data(), soa.mask.size());
+    if (!rc) rc = up(x->d_delta, soa.delta.data(), soa.delta.size());
+    if (!rc) rc = up(x->d_seg_off, soa.seg_delta_off.data(), soa.seg_delta_off.size() * 8);
+    if (!rc) rc = up(x->d_ckpt, soa.seg_ckpt.data(), soa.seg_ckpt.size());
     if (o.global_offset != 0)
         for (uint32_t& id : soa.mi_id) id += (uint32_t)o.global_offset;
     if (!rc && soa.mi_stride > 0 && (int64_t)soa.mi_id.size() >= 16384) {
-        rc = up(&x->d_mi_cell, soa.mi_cell_start.data(), soa.mi_cell_start.size() * 4);
-        if (!rc) rc = up(&x->d_mi_code, soa.mi_code.data(), soa.mi_code.size() * 4);
-        if (!rc) rc = up(&x->d_mi_id, soa.mi_id.data(), soa.mi_id.size() * 4);
+        rc = up(x->d_mi_cell, soa.mi_cell_start.data(), soa.mi_cell_start.size() * 4);
+        if (!rc) rc = up(x->d_mi_code, soa.mi_code.data(), soa.mi_code.size() * 4);
+        if (!rc) rc = up(x->d_mi_id, soa.mi_id.data(), soa.mi_id.size() * 4);
         x->boot = !rc;
         x->boot_classes = soa.mi_classes;
     }
     if (!rc && x->tune.relabel && soa.relabel.size() == (size_t)M * 256) {
-        rc = up(&x->d_relabel, soa.relabel.data(), soa.relabel.size());
+        rc = up(x->d_relabel, soa.relabel.data(), soa.relabel.size());
     }
     if (!rc && x->boot && x->tune.strands && soa.n_strips > 0 && soa.n_strips < INT32_MAX) {
-        rc = up(&x->d_st_ckpt, soa.st_ckpt.data(), soa.st_ckpt.size() * 8);
-        if (!rc) rc = up(&x->d_st_mask, soa.st_mask.data(), soa.st_mask.size() * 4);
-        if (!rc) rc = up(&x->d_st_depth, soa.st_depth.data(), soa.st_depth.size() * 2);
+        rc = up(x->d_st_ckpt, soa.st_ckpt.data(), soa.st_ckpt.size() * 8);
+        if (!rc) rc = up(x->d_st_mask, soa.st_mask.data(), soa.st_mask.size() * 4);
+        if (!rc) rc = up(x->d_st_depth, soa.st_depth.data(), soa.st_depth.size() * 2);
         // (st_poff stays on the host: the kernel computes a lane's offset inside a phase as a wave prefix sum of the lanes'
         // byte counts; the array exists for the CPU-side checks of the image)
-        if (!rc) rc = up(&x->d_st_pbase, soa.st_pbase.data(), soa.st_pbase.size() * 4);
-        if (!rc) rc = up(&x->d_st_delta, soa.st_delta.data(), soa.st_delta.size());
+        if (!rc) rc = up(x->d_st_pbase, soa.st_pbase.data(), soa.st_pbase.size() * 4);
+        if (!rc) rc = up(x->d_st_delta, soa.st_delta.data(), soa.st_delta.size());
         if (!rc) {
             // strips are visited in a low-discrepancy order too (every prefix a spread sample of the shard)
             const int64_t ns = soa.n_strips;
-            std::vector<uint32_t> order((size_t)ns);
-            int64_t P = std::max<int64_t>(1, (int64_t)((double)ns * 0.6180339887498949));
-            auto gcd = [](int64_t a, int64_t b) { while (b) { int64_t t = a % b; a = b; b = t; } return a; };
-            while (gcd(P, ns) != 1) ++P;
-            for (int64_t j = 0; j < ns; ++j) order[(size_t)j] = (uint32_t)((j * P) % ns);
-            rc = up(&x->d_strip_order, order.data(), order.size() * 4);
+            const std::vector<uint32_t> order = golden_order(ns);
+            rc = up(x->d_strip_order, order.data(), order.size() * 4);
             const int64_t S = soa.nodes_per_segment();
             if (!rc && dpq::kStripNodes % S == 0) {
                 std::vector<uint32_t> segs;
@@ -1106,7 +1170,7 @@ int open_from_payload(const uint8_t* payload, int64_t n_bytes, int64_t n_codes, 
                     for (int64_t t = s0; t < std::min(s0 + dpq::kStripNodes / S, soa.n_segments); ++t) segs.push_back((uint32_t)t);
                     x->strip_seg_off[(size_t)j + 1] = (int64_t)segs.size();
                 }
-                rc = up(&x->d_strip_segs, segs.data(), segs.size() * 4);
+                rc = up(x->d_strip_segs, segs.data(), segs.size() * 4);
             }
         }
         if (!rc) {
@@ -1194,7 +1258,7 @@ int open_plain(const uint8_t* codes, int64_t n_codes, int M, int K, const dpq_op
     x->cap_auto = o.cand_capacity <= 0;
     x->cap = o.cand_capacity;
     const size_t padded = (size_t)(seg_hi - seg_lo) * S * M;
-    int rc = dev_alloc(&x->d_raw, padded + 64);
+    int rc = x->d_raw.alloc(padded + 64);
     if (!rc) {
         hipError_t e = hipMemset(x->d_raw, 0, padded + 64);
         if (e == hipSuccess && hi > lo)
@@ -1217,16 +1281,16 @@ int open_plain(const uint8_t* codes, int64_t n_codes, int M, int K, const dpq_op
                 cds.insert(cds.end(), codes + (size_t)i * M, codes + (size_t)(i + 1) * M);
             }
             dpq::build_multi_index(ids, cds, M, mi_stride, dpq::bootstrap_classes_for((int64_t)ids.size()), &mi);
-            auto upl = [&](uint32_t** d, const std::vector<uint32_t>& v) -> int {
-                int r = dev_alloc(d, v.size() + 16);
+            auto upl = [&](DevBuf<uint32_t>& d, const std::vector<uint32_t>& v) -> int {
+                int r = d.alloc(v.size() + 16);
                 if (r) return r;
-                if (!v.empty() && hipMemcpy(*d, v.data(), v.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
+                if (!v.empty() && hipMemcpy(d, v.data(), v.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
                     return fail(DPQ_ERR_HIP, "upload of the bootstrap multi-index failed");
                 return DPQ_OK;
             };
-            rc = upl(&x->d_mi_cell, mi.mi_cell_start);
-            if (!rc) rc = upl(&x->d_mi_code, mi.mi_code);
-            if (!rc) rc = upl(&x->d_mi_id, mi.mi_id);
+            rc = upl(x->d_mi_cell, mi.mi_cell_start);
+            if (!rc) rc = upl(x->d_mi_code, mi.mi_code);
+            if (!rc) rc = upl(x->d_mi_id, mi.mi_id);
             if (rc) {
                 dpq_close(x);
                 return rc;
@@ -1611,26 +1675,20 @@ int dpq_encode_pq(const float* vectors, int64_t n, int D, const float* codewords
     if (device < 0 || device >= ndev) return fail(DPQ_ERR_NO_DEVICE, "device ordinal out of range");
     if (n == 0) return DPQ_OK;
     DPQ_HIP(hipSetDevice(device));
-    float *d_v = nullptr, *d_c = nullptr;
-    uint8_t* d_o = nullptr;
+    DevBuf<float> d_v, d_c;
+    DevBuf<uint8_t> d_o;
     const int64_t tile = 1 << 20;  // vectors per upload
-    int rc = dev_alloc(&d_v, (size_t)std::min(n, tile) * D);
-    if (!rc) rc = dev_alloc(&d_c, (size_t)M * K * Ds);
-    if (!rc) rc = dev_alloc(&d_o, (size_t)std::min(n, tile) * M);
-    hipError_t e = hipSuccess;
-    if (!rc) {
-        e = hipMemcpy(d_c, codewords, (size_t)M * K * Ds * sizeof(float), hipMemcpyHostToDevice);
-        for (int64_t base = 0; base < n && e == hipSuccess; base += tile) {
-            const int64_t m = std::min(tile, n - base);
-            e = hipMemcpy(d_v, vectors + (size_t)base * D, (size_t)m * D * sizeof(float), hipMemcpyHostToDevice);
-            if (e == hipSuccess) e = dpq::launch_encode_pq(d_v, m, D, d_c, M, K, Ds, d_o, nullptr);
-            if (e == hipSuccess) e = hipMemcpy(codes_out + (size_t)base * M, d_o, (size_t)m * M, hipMemcpyDeviceToHost);
-        }
-    }
-    hipFree(d_v);
-    hipFree(d_c);
-    hipFree(d_o);
+    int rc = d_v.alloc((size_t)std::min(n, tile) * D);
+    if (!rc) rc = d_c.alloc((size_t)M * K * Ds);
+    if (!rc) rc = d_o.alloc((size_t)std::min(n, tile) * M);
     if (rc) return rc;
+    hipError_t e = hipMemcpy(d_c, codewords, (size_t)M * K * Ds * sizeof(float), hipMemcpyHostToDevice);
+    for (int64_t base = 0; base < n && e == hipSuccess; base += tile) {
+        const int64_t m = std::min(tile, n - base);
+        e = hipMemcpy(d_v, vectors + (size_t)base * D, (size_t)m * D * sizeof(float), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = dpq::launch_encode_pq(d_v, m, D, d_c, M, K, Ds, d_o, nullptr);
+        if (e == hipSuccess) e = hipMemcpy(codes_out + (size_t)base * M, d_o, (size_t)m * M, hipMemcpyDeviceToHost);
+    }
     if (e != hipSuccess) return fail(DPQ_ERR_HIP, std::string("dpq_encode_pq: ") + hipGetErrorString(e));
     return DPQ_OK;
     });
@@ -1683,10 +1741,8 @@ int dpq_set_codebook(dpq_index* x, const float* codewords, int Ds) {
     if (!x || !codewords || Ds < 1 || Ds > 4096) return fail(DPQ_ERR_ARG, "bad codebook argument");
     if (int rc = dpq_finish(x)) return rc;  // batches in flight still read the old codebook
     DPQ_HIP(hipSetDevice(x->device));
-    hipFree(x->d_codebook);
-    x->d_codebook = nullptr;
     const size_t n = (size_t)x->M * x->K * Ds;
-    int rc = dev_alloc(&x->d_codebook, n);
+    int rc = x->d_codebook.alloc(n);
     if (rc) return rc;
     DPQ_HIP(hipMemcpy(x->d_codebook, codewords, n * sizeof(float), hipMemcpyHostToDevice));
     x->Ds = Ds;
@@ -1715,9 +1771,7 @@ int dpq_set_codebook(dpq_index* x, const float* codewords, int Ds) {
                 for (int o = 0; o < 256; ++o) nbr[((size_t)sl * 256 + c) * 256 + o] = (uint8_t)row[(size_t)o].second;
             }
         }
-        hipFree(x->d_nbr);
-        x->d_nbr = nullptr;
-        rc = dev_alloc(&x->d_nbr, nbr.size());
+        rc = x->d_nbr.alloc(nbr.size());
         if (rc) return rc;
         DPQ_HIP(hipMemcpy(x->d_nbr, nbr.data(), nbr.size(), hipMemcpyHostToDevice));
     }
@@ -1747,55 +1801,17 @@ int dpq_close(dpq_index* x) {
         hipEventDestroy(ep.b);
     }
     for (auto e : x->ev_pool) hipEventDestroy(e);
-    free_workspace(x);
-    free_parked_lane(x);
     for (int l = 0; l < 2; ++l) {
         if (x->lane_stream[l]) hipStreamDestroy(x->lane_stream[l]);
         if (x->lane_ready[l]) hipEventDestroy(x->lane_ready[l]);
-        if (x->lane_select_done[l]) hipEventDestroy(x->lane_select_done[l]);
     }
-    hipFree(x->d_st_ckpt);
-    hipFree(x->d_st_mask);
-    hipFree(x->d_st_depth);
-    hipFree(x->d_st_pbase);
-    hipFree(x->d_st_delta);
-    hipFree(x->d_s1_stamps);
-    hipFree(x->d_strip_order);
-    hipFree(x->d_strip_segs);
-    hipFree(x->d_nib);
-    hipFree(x->d_par);
-    hipFree(x->d_carry);
-    hipFree(x->d_mask);
-    hipFree(x->d_delta);
-    hipFree(x->d_ckpt);
-    hipFree(x->d_raw);
-    hipFree(x->d_seg_off);
-    hipFree(x->d_boot_stamps);
-    hipFree(x->d_nbr);
-    hipFree(x->d_batch_raw);  // the active lane's plain-code scratch (the parked lane's goes with free_parked_lane)
-    hipFree(x->d_relabel);
-    hipFree(x->d_mi_cell);
-    hipFree(x->d_mi_code);
-    hipFree(x->d_mi_id);
-    hipFree(x->d_codebook);
-    hipFree(x->d_order);
-    hipFree(x->d_l0_id);
-    hipFree(x->d_l0_code);
-    hipFree(x->d_q_stage);
-    hipFree(x->d_ids_stage);
-    hipFree(x->d_dists_stage);
-    for (auto& hs : x->host_slots) {
-        hipFree(hs.d_q);
-        hipFree(hs.d_ids);
-        hipFree(hs.d_d);
+    for (auto& hs : x->host_slots)
         if (hs.kernels_done) hipEventDestroy(hs.kernels_done);
-    }
     if (x->copy_in) hipStreamDestroy(x->copy_in);
     if (x->copy_out) hipStreamDestroy(x->copy_out);
     if (x->h_overflow) hipHostFree(x->h_overflow);
     if (x->h_any) hipHostFree(x->h_any);
-    hipFree(x->d_counters);
-    delete x;
+    delete x;  // (the device buffers go with it)
     return DPQ_OK;
     });
 }
@@ -1942,7 +1958,7 @@ int enqueue_async(dpq_index* x, const float* d_queries, int nq, int top_k, int32
             x->ordered_stream[lane] = user;
             x->ordered_stream_set[lane] = true;
         }
-        switch_lane(x, lane);
+        use_lane(x, lane);
     }
     const int D = x->M * x->Ds;
     for (int base = 0; base < nq; base += kMaxBatchQueries) {
@@ -1958,21 +1974,13 @@ int enqueue_async(dpq_index* x, const float* d_queries, int nq, int top_k, int32
                 DPQ_HIP(hipStreamCreateWithFlags(&x->lane_stream[lane], hipStreamNonBlocking));
                 DPQ_HIP(hipEventCreateWithFlags(&x->lane_ready[lane], hipEventDisableTiming));
             }
-            switch_lane(x, lane);
+            use_lane(x, lane);
             stream = x->lane_stream[lane];
             DPQ_HIP(hipEventRecord(x->lane_ready[lane], user));
             DPQ_HIP(hipStreamWaitEvent(stream, x->lane_ready[lane], 0));
-            if (!x->lane_select_done[lane]) DPQ_HIP(hipEventCreateWithFlags(&x->lane_select_done[lane], hipEventDisableTiming));
-            x->run_lane = lane;
-            x->gate_this_batch = x->pending.size() == 1;
         }
         rc = run_batch(x, d_queries + (size_t)base * D, n, top_k, d_ids + (size_t)base * top_k,
                        d_dists + (size_t)base * top_k, stream, slot);
-        if (x->run_lane >= 0 && !rc) {
-            hipError_t e = hipEventRecord(x->lane_select_done[x->run_lane], stream);
-            x->lane_select_recorded[x->run_lane] = e == hipSuccess;
-        }
-        x->run_lane = -1;
         if (rc) return rc;
         x->pending.push_back({d_queries + (size_t)base * D, n, top_k, d_ids + (size_t)base * top_k,
                               d_dists + (size_t)base * top_k, stream, user, slot, host_slot});
@@ -1993,19 +2001,15 @@ int dpq_query_batch_device(dpq_index* x, const float* d_queries, int nq, int top
         int rc = dpq_finish(x);
         if (rc) return rc;
     }
-    if (!x || !d_queries || !d_ids || !d_dists || nq < 0) return fail(DPQ_ERR_ARG, "NULL argument or nq < 0");
-    if (!x->d_codebook) return fail(DPQ_ERR_STATE, "dpq_set_codebook has not been called");
-    if (top_k < 1 || top_k > dpq::kMaxTopK) return fail(DPQ_ERR_ARG, "top_k must be in 1..2048");
-    if ((int64_t)top_k > x->img.n_codes_total)
-        return fail(DPQ_ERR_TOPK, "top_k exceeds the number of codes in the index");
-    if (nq == 0) return DPQ_OK;
+    int rc = check_batch_args(x, d_queries, nq, top_k, d_ids, d_dists);
+    if (rc || nq == 0) return rc;
     DPQ_HIP(hipSetDevice(x->device));
     hipStream_t stream = reinterpret_cast<hipStream_t>(hip_stream);
     const int D = x->M * x->Ds;
     for (int base = 0; base < nq; base += kMaxBatchQueries) {
         const int n = std::min(kMaxBatchQueries, nq - base);
-        int rc = run_batch(x, d_queries + (size_t)base * D, n, top_k, d_ids + (size_t)base * top_k,
-                           d_dists + (size_t)base * top_k, stream);
+        rc = run_batch(x, d_queries + (size_t)base * D, n, top_k, d_ids + (size_t)base * top_k,
+                       d_dists + (size_t)base * top_k, stream);
         if (rc) return rc;
     }
     if (x->prof) {
@@ -2025,19 +2029,16 @@ int dpq_query_batch(dpq_index* x, const float* queries, int nq, int top_k, int32
     DPQ_HIP(hipSetDevice(x->device));
     const size_t qf = (size_t)nq * x->M * x->Ds, oe = (size_t)nq * top_k;
     if (qf > x->q_stage_floats) {
-        hipFree(x->d_q_stage);
-        x->d_q_stage = nullptr;
-        int rc = dev_alloc(&x->d_q_stage, qf);
+        x->q_stage_floats = 0;
+        int rc = x->d_q_stage.alloc(qf);
         if (rc) return rc;
         x->q_stage_floats = qf;
     }
     if (oe > x->out_stage_elems) {
-        hipFree(x->d_ids_stage);
-        hipFree(x->d_dists_stage);
-        x->d_ids_stage = nullptr;
-        x->d_dists_stage = nullptr;
-        int rc = dev_alloc(&x->d_ids_stage, oe);
-        if (!rc) rc = dev_alloc(&x->d_dists_stage, oe);
+        x->out_stage_elems = 0;
+        x->d_dists_stage.reset();
+        int rc = x->d_ids_stage.alloc(oe);
+        if (!rc) rc = x->d_dists_stage.alloc(oe);
         if (rc) return rc;
         x->out_stage_elems = oe;
     }
@@ -2057,7 +2058,6 @@ int dpq_query_batch(dpq_index* x, const float* queries, int nq, int top_k, int32
 // batch in which a query overflowed its candidate buffers.
 int dpq_query_batch_host_async(dpq_index* x, const float* queries, int nq, int top_k, int32_t* ids, float* dists) {
     return guarded([&]() -> int {
-    if (!x || !queries || !ids || !dists || nq < 0) return fail(DPQ_ERR_ARG, "NULL argument or nq < 0");
     int rc = check_batch_args(x, queries, nq, top_k, ids, dists);
     if (rc || nq == 0) return rc;
     DPQ_HIP(hipSetDevice(x->device));
@@ -2074,10 +2074,8 @@ int dpq_query_batch_host_async(dpq_index* x, const float* queries, int nq, int t
     dpq_index::HostSlot& hs = x->host_slots[slot];
     const size_t qf = (size_t)nq * x->M * x->Ds, oe = (size_t)nq * top_k;
     if (qf > hs.qf) {
-        hipFree(hs.d_q);
-        hs.d_q = nullptr;
         hs.qf = 0;
-        if ((rc = dev_alloc(&hs.d_q, qf))) return rc;
+        if ((rc = hs.d_q.alloc(qf))) return rc;
         hs.qf = qf;
     }
     // Page-locked result buffers (dpq_pin_host / hipHostRegister / hipHostMalloc) are mapped into the device's address
@@ -2088,20 +2086,17 @@ int dpq_query_batch_host_async(dpq_index* x, const float* queries, int nq, int t
     const bool direct = hipHostGetDevicePointer(&m_ids, ids, 0) == hipSuccess && hipHostGetDevicePointer(&m_d, dists, 0) == hipSuccess;
     if (!direct) (void)hipGetLastError();  // (an unregistered pointer is not an error of this call)
     if (!direct && oe > hs.oe) {
-        hipFree(hs.d_ids);
-        hipFree(hs.d_d);
-        hs.d_ids = nullptr;
-        hs.d_d = nullptr;
         hs.oe = 0;
-        if ((rc = dev_alloc(&hs.d_ids, oe)) || (rc = dev_alloc(&hs.d_d, oe))) return rc;
+        hs.d_d.reset();
+        if ((rc = hs.d_ids.alloc(oe)) || (rc = hs.d_d.alloc(oe))) return rc;
         hs.oe = oe;
     }
     if (!hs.kernels_done) DPQ_HIP(hipEventCreateWithFlags(&hs.kernels_done, hipEventDisableTiming));
     // (pageable caller memory makes this copy synchronous with the host; pinned memory -- dpq_pin_host -- lets it overlap)
     DPQ_HIP(hipMemcpyAsync(hs.d_q, queries, qf * sizeof(float), hipMemcpyHostToDevice, x->copy_in));
     const size_t first = x->pending.size();
-    int32_t* const out_ids = direct ? static_cast<int32_t*>(m_ids) : hs.d_ids;
-    float* const out_d = direct ? static_cast<float*>(m_d) : hs.d_d;
+    int32_t* const out_ids = direct ? static_cast<int32_t*>(m_ids) : hs.d_ids.get();
+    float* const out_d = direct ? static_cast<float*>(m_d) : hs.d_d.get();
     if ((rc = enqueue_async(x, hs.d_q, nq, top_k, out_ids, out_d, x->copy_in, true, slot))) return rc;
     // (enqueue_async may have settled older batches: the entries of this one are the pending tail)
     const size_t begin = std::min(first, x->pending.size());
@@ -2212,7 +2207,7 @@ int dpq_merge_topk_device_packed(const int32_t* d_packed, int n_lists, int nq, i
 int dpq_debug_scan_time(dpq_index* x, int nq, int pass_all, int reps, int splits, float* ms_out) {
     return guarded([&]() -> int {
     DPQ_DEV_ONLY();
-    if (!x || !ms_out || !x->d_lut32) return fail(DPQ_ERR_STATE, "run a query batch first");
+    if (!x || !ms_out || !x->ws().d_lut32) return fail(DPQ_ERR_STATE, "run a query batch first");
     DPQ_HIP(hipSetDevice(x->device));
     if (pass_all == 3) {
         // the last batch's first filter level exactly as it ran: its bootstrap again (thresholds + tables), then `reps`
@@ -2242,31 +2237,15 @@ int dpq_debug_scan_time(dpq_index* x, int nq, int pass_all, int reps, int splits
     }
     const int QG = dpq::queries_per_group(x->M);
     const int nqp = (nq + QG - 1) / QG * QG;
-    if (nqp > x->ws_slots) return fail(DPQ_ERR_ARG, "nq exceeds the workspace");
-    dpq::ScanArgs sa{};
-    sa.img = x->img;
-    sa.fp32_accum = x->plain ? 1 : 0;
-    sa.lut32 = x->d_lut32;
-    sa.lut_min = x->d_lut_min;
-    sa.thr_key = x->d_thr_key;
-    sa.slot_query = nullptr;
-    sa.n_queries = nq;
+    const Workspace& w = x->ws();
+    if (nqp > w.slots) return fail(DPQ_ERR_ARG, "nq exceeds the workspace");
+    dpq::ScanArgs sa = debug_scan_args(x, nq, &splits);
     sa.debug_pass = pass_all == 2 ? 0 : (pass_all ? 2 : 1);  // 2: the thresholds the last batch left behind
-    sa.seg_list = nullptr;
-    sa.n_seg_pass = x->img.n_segments;
     // what the last batch ran: its plain-code scratch, if it decoded the whole shard into one
-    if (!x->plain && x->d_batch_raw && batch_tile_segments(x) >= x->img.n_segments && !getenv("DPQ_DEBUG_FUSED")) {
-        sa.img.raw = x->d_batch_raw;
-        if (x->d_relabel) sa.lut32 = x->d_lut32r;
+    if (!x->plain && w.d_batch_raw && batch_tile_segments(x) >= x->img.n_segments && !getenv("DPQ_DEBUG_FUSED")) {
+        sa.img.raw = w.d_batch_raw;
+        if (x->d_relabel) sa.lut32 = w.d_lut32r;
     }
-    if (const char* e = getenv("DPQ_DEBUG_NSEG")) sa.n_seg_pass = std::min(x->img.n_segments, atoi(e));
-    if (splits <= 0) splits = splits_for(sa.n_seg_pass, nqp / QG);
-    sa.cand_count = x->d_cand_count;
-    sa.cand_key = x->d_cand_key;
-    sa.cand_stride = x->ws_cap;
-    sa.region_off = 0;
-    sa.region_cap = std::max(1, x->ws_cap / splits);
-    sa.qtab = x->d_qtab;
     hipEvent_t a, b;
     DPQ_HIP(hipEventCreate(&a));
     DPQ_HIP(hipEventCreate(&b));
@@ -2283,15 +2262,14 @@ int dpq_debug_scan_time(dpq_index* x, int nq, int pass_all, int reps, int splits
     hipEventDestroy(b);
     if (getenv("DPQ_DEBUG_WG_TIMES")) {  // when do the workgroups of one launch start and end?
         const int nwg = splits * (nqp / QG);
-        unsigned long long* d_t = nullptr;
-        int rc = dev_alloc(&d_t, (size_t)nwg * 2);
+        DevBuf<unsigned long long> d_t;
+        int rc = d_t.alloc((size_t)nwg * 2);
         if (rc) return rc;
         sa.wg_times = d_t;
         DPQ_HIP(dpq::launch_scan(sa, nqp / QG, splits, nullptr));
         DPQ_HIP(hipDeviceSynchronize());
         std::vector<unsigned long long> h((size_t)nwg * 2);
         DPQ_HIP(hipMemcpy(h.data(), d_t, h.size() * 8, hipMemcpyDeviceToHost));
-        hipFree(d_t);
         unsigned long long t0 = ~0ull, t1 = 0;
         for (int i = 0; i < nwg; ++i) t0 = std::min(t0, h[2 * (size_t)i]), t1 = std::max(t1, h[2 * (size_t)i + 1]);
         std::vector<double> st, en, life;
@@ -2318,33 +2296,18 @@ int dpq_debug_scan_time(dpq_index* x, int nq, int pass_all, int reps, int splits
 int dpq_debug_scan_stamps(dpq_index* x, int nq, int splits, unsigned long long* out, int n_out, float* ms_out) {
     return guarded([&]() -> int {
     DPQ_DEV_ONLY();
-    if (!x || !out || !x->d_lut32) return fail(DPQ_ERR_STATE, "run a query batch first");
+    if (!x || !out || !x->ws().d_lut32) return fail(DPQ_ERR_STATE, "run a query batch first");
     if (x->M != 8) return fail(DPQ_ERR_ARG, "the STAMPS build exists for M = 8");
     DPQ_HIP(hipSetDevice(x->device));
     const int QG = dpq::queries_per_group(x->M);
     const int nqp = (nq + QG - 1) / QG * QG;
-    if (nqp > x->ws_slots) return fail(DPQ_ERR_ARG, "nq exceeds the workspace");
+    if (nqp > x->ws().slots) return fail(DPQ_ERR_ARG, "nq exceeds the workspace");
     const int n = std::min(n_out, dpq::scan_stamp_count());
-    unsigned long long* d_st = nullptr;
-    int rc = dev_alloc(&d_st, (size_t)dpq::scan_stamp_count());
+    DevBuf<unsigned long long> d_st;
+    int rc = d_st.alloc((size_t)dpq::scan_stamp_count());
     if (rc) return rc;
     DPQ_HIP(hipMemset(d_st, 0, sizeof(unsigned long long) * dpq::scan_stamp_count()));
-    dpq::ScanArgs sa{};
-    sa.img = x->img;
-    sa.fp32_accum = x->plain ? 1 : 0;
-    sa.lut32 = x->d_lut32;
-    sa.lut_min = x->d_lut_min;
-    sa.thr_key = x->d_thr_key;
-    sa.n_queries = nq;
-    sa.n_seg_pass = x->img.n_segments;
-    if (const char* e = getenv("DPQ_DEBUG_NSEG")) sa.n_seg_pass = std::min(x->img.n_segments, atoi(e));
-    if (splits <= 0) splits = splits_for(sa.n_seg_pass, nqp / QG);
-    sa.cand_count = x->d_cand_count;
-    sa.cand_key = x->d_cand_key;
-    sa.cand_stride = x->ws_cap;
-    sa.region_off = 0;
-    sa.region_cap = std::max(1, x->ws_cap / splits);
-    sa.qtab = x->d_qtab;
+    dpq::ScanArgs sa = debug_scan_args(x, nq, &splits);
     sa.stamps = d_st;
     hipEvent_t a, b;
     DPQ_HIP(hipEventCreate(&a));
@@ -2360,7 +2323,6 @@ int dpq_debug_scan_stamps(dpq_index* x, int nq, int splits, unsigned long long* 
     DPQ_HIP(hipMemcpy(out, d_st, sizeof(unsigned long long) * n, hipMemcpyDeviceToHost));
     hipEventDestroy(a);
     hipEventDestroy(b);
-    hipFree(d_st);
     return DPQ_OK;
     });
 }
@@ -2375,7 +2337,7 @@ int dpq_debug_strand1_stamps(dpq_index* x, unsigned long long* out, int n_words)
     DPQ_HIP(hipSetDevice(x->device));
     const size_t total = (size_t)256 * 16 * 16;
     if (!x->d_s1_stamps) {
-        int rc = dev_alloc(&x->d_s1_stamps, total);
+        int rc = x->d_s1_stamps.alloc(total);
         if (rc) return rc;
         DPQ_HIP(hipMemset(x->d_s1_stamps, 0, total * 8));
         return DPQ_OK;
@@ -2396,7 +2358,7 @@ int dpq_debug_boot_stamps(dpq_index* x, int nq, double* out) {
     if (!x || !out) return fail(DPQ_ERR_ARG, "NULL argument");
     DPQ_HIP(hipSetDevice(x->device));
     if (!x->d_boot_stamps) {
-        int rc = dev_alloc(&x->d_boot_stamps, (size_t)kMaxBatchQueries * 16);
+        int rc = x->d_boot_stamps.alloc((size_t)kMaxBatchQueries * 16);
         if (rc) return rc;
         DPQ_HIP(hipMemset(x->d_boot_stamps, 0, sizeof(unsigned long long) * kMaxBatchQueries * 16));
         for (int i = 0; i < 8; ++i) out[i] = 0;
@@ -2455,22 +2417,23 @@ int dpq_debug_boot_stamps(dpq_index* x, int nq, double* out) {
 int dpq_debug_select_time(dpq_index* x, int nq, int top_k, int flags, int reps, float* ms_out) {
     return guarded([&]() -> int {
     DPQ_DEV_ONLY();
-    if (!x || !ms_out || !x->d_lut32 || !x->d_l0_id) return fail(DPQ_ERR_STATE, "run a query batch first");
+    if (!x || !ms_out || !x->ws().d_lut32 || !x->d_l0_id) return fail(DPQ_ERR_STATE, "run a query batch first");
     DPQ_HIP(hipSetDevice(x->device));
+    const Workspace& w = x->ws();
     dpq::SelectArgs se{};
     se.shared_id = x->d_l0_id;
     se.shared_code = x->d_l0_code;
     se.shared_n = x->l0_segments * dpq::kChunk * x->img.chunks_per_segment;
-    se.cand_count = x->d_cand_count;
-    se.cand_key = x->d_cand_key;
-    se.cand_stride = x->ws_cap;
+    se.cand_count = w.d_cand_count;
+    se.cand_key = w.d_cand_key;
+    se.cand_stride = w.cap;
     se.region_off = top_k;
-    se.scratch = x->d_scratch;
-    se.lut32 = x->d_lut32;
+    se.scratch = w.d_scratch;
+    se.lut32 = w.d_lut32;
     se.top_k = top_k;
     se.final_pass = 0;
-    se.thr_key = x->d_thr_key;
-    se.overflow = x->d_overflow;
+    se.thr_key = w.d_thr_key;
+    se.overflow = w.d_overflow;
     se.n_codes_total = x->img.n_codes_total;
     (void)flags;
     hipEvent_t a, b;

@@ -17,12 +17,17 @@ constexpr int kRegionStride = 1 + kMaxSplits;    // candidate-count words per sl
 constexpr int kLevel0Nodes = 3840;               // level-0 list: its select block (keys + exact tables) stays under 40 KB of LDS
 constexpr int kSortMax = 4096;  // candidate keys the select kernel holds in LDS; more -> radix select on the HBM list
 // queries per scan workgroup = what 128 KB of filter tables hold: 8-bit entries for M = 8, 16-bit for M = 16
-inline int queries_per_group(int M) { return M <= 8 ? 64 : 32; }
+constexpr int queries_per_group(int M) { return M <= 8 ? 64 : 32; }
 // In-scan threshold tightening: per slot and filter level a histogram of the candidates found so far, by how many
 // steps the level's cut could be lowered without losing them (scan_kernel).
 constexpr int kTightBuckets = 8;
 constexpr int kTightSplits = 32;                 // scan workgroups of a query group that can share their counts
 constexpr int kTightWords = kTightSplits * kTightBuckets / 4;  // u32 words per slot: [split][bucket] saturating bytes
+// strand1_kernel tightens its one slot through a histogram of kS1Replicas copies, kS1ReplicaWords words apart.  The
+// table build clears kTightWords per padded slot: one query group's worth must cover it.
+constexpr int kS1Replicas = 8, kS1ReplicaWords = 512;
+constexpr int kS1HistWords = kS1Replicas * kS1ReplicaWords;
+static_assert(queries_per_group(8) * kTightWords >= kS1HistWords, "strand1's histogram exceeds what one query group clears");
 
 // The SoA image of one shard in HBM (see DESIGN.md "Data layout").
 struct DeviceImage {
@@ -60,7 +65,8 @@ struct ScanArgs {
     const uint64_t* thr_key;    // [slots] threshold key of each slot (~0 = keep everything)
     const int32_t* slot_query;  // slot -> query of the batch, NULL = identity, -1 = unused slot (nothing passes)
     int32_t n_queries;          // slots >= n_queries are padding when slot_query == NULL
-    int32_t debug_pass;         // developer experiments: 0 normal, 1 nothing passes, 2 everything passes
+    int32_t debug_pass;         // developer experiments: 0 normal; scans: 1 nothing passes, 2 everything passes;
+                                // strand1_kernel: >= 16 (dpq_kernels.hip)
     unsigned long long* wg_times;  // developer diagnostics: [workgroups][2] start / end on the 100 MHz clock (NULL = off)
     int32_t raw_by_pos;         // img.raw is the per-batch scratch of THIS launch's list: entry s of seg_list at position s
     int32_t append;             // the launch continues a level: region counts start from cand_count instead of 0
@@ -153,7 +159,9 @@ hipError_t launch_stream(const ScanArgs& a, int n_slots, hipStream_t stream);
 hipError_t launch_strand(const ScanArgs& a, int n_slots, hipStream_t stream);
 int stream_queries_per_pass(int M, int n_slots);  // 1, 2, 4 or 8 (M = 16: at most 4)
 // One query per pass over the strand image (strand1_kernel): its workgroups, each with its own candidate region
-// (region 1 + w of the slot, a.region_cap keys, count published by the kernel).
+// (region 1 + w of the slot, a.region_cap keys, count published by the kernel).  a.tight_hist (kS1HistWords words,
+// zero at launch) only with one slot.
+hipError_t launch_strand1(const ScanArgs& a, int n_slots, hipStream_t stream);
 int strand1_workgroups(int n_strips);
 constexpr int kStrand1Regions = 256;
 hipError_t launch_quantise(const ScanArgs& a, int n_slot_groups, hipStream_t stream);

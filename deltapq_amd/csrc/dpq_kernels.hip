@@ -1792,10 +1792,9 @@ __global__ __launch_bounds__(kStrandThreads, Q >= 4 ? 2 : Q == 2 ? 3 : 4) void s
 #endif
 constexpr int kS1Threads = DPQ_S1_THREADS, kS1Waves = kS1Threads / 64;
 constexpr int kS1Buckets = 64;  // histogram words: bucket b = candidates under a cut of 4 b + 3 units
-// The global histogram (a.tight_hist, zero at launch) is kept in kS1Replicas copies 2 KB apart, a workgroup adds to copy
-// blockIdx % 8 and a look sums the copies: the few thousand adds of a launch's first microseconds otherwise queue up in
-// ONE memory channel, and every wavefront's in-order loads wait for the one that goes there.
-constexpr int kS1Replicas = 8, kS1ReplicaWords = 512;
+// The global histogram (a.tight_hist, zero at launch) is kept in kS1Replicas copies 2 KB apart (dpq_kernels.h), a
+// workgroup adds to copy blockIdx % 8 and a look sums the copies: the few thousand adds of a launch's first microseconds
+// otherwise queue up in ONE memory channel, and every wavefront's in-order loads wait for the one that goes there.
 static_assert((DPQ_S1_QT >> 2) < kS1Buckets && DPQ_S1_QT <= 253, "a lane per bucket; 8 entries of 255 must reject");
 
 struct S1Lds {
@@ -3446,7 +3445,9 @@ int strand1_workgroups(int n_strips) { return std::max(1, std::min(DPQ_S1_MAX_WG
 
 // One query per pass: the bound-table kernel.  One workgroup of 16 wavefronts per CU; strips go to the workgroups
 // first, so a short list still reaches every CU.
-static hipError_t launch_strand1(const ScanArgs& a, int n_slots, hipStream_t stream) {
+hipError_t launch_strand1(const ScanArgs& a, int n_slots, hipStream_t stream) {
+    if (a.n_seg_pass <= 0 || n_slots <= 0) return hipSuccess;
+    if (a.img.M != 8 || !a.img.st_ckpt || (a.tight_hist && n_slots != 1)) return hipErrorInvalidValue;
     static std::atomic<bool> done[64] = {};
     hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(&strand1_kernel), S1Lds::kBytes, done);
     if (e != hipSuccess) return e;
@@ -3459,7 +3460,7 @@ hipError_t launch_strand(const ScanArgs& a, int n_slots, hipStream_t stream) {
     if (a.n_seg_pass <= 0 || n_slots <= 0) return hipSuccess;
     if (a.img.M != 8 || !a.img.st_ckpt) return hipErrorInvalidValue;
     switch (stream_queries_per_pass(8, n_slots)) {
-        case 1: return a.debug_pass == 3 ? launch_strand_q<1>(a, n_slots, stream) : launch_strand1(a, n_slots, stream);  // (>= 16: strand1 experiments)
+        case 1: return launch_strand_q<1>(a, n_slots, stream);
         case 2: return launch_strand_q<2>(a, n_slots, stream);
         default: return launch_strand_q<4>(a, n_slots, stream);
     }
