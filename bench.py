@@ -21,9 +21,14 @@ scaling, no collective) is timed after the headline run and reported beside it u
 
 The timed region is exactly K = --steps steps, bracketed by barrier + synchronize; `ms_per_step` is its time / K.
 --reps R > 1 repeats the region R times (R x K timed steps) and `value` is the median repetition, min/max are
-reported.  Steps rotate over 4 distinct query batches.  Rank 0 prints ONE JSON line with `roofline` (binding
-resource of the scan kernel: LDS gather bandwidth; measured HBM beside it) and `cpu_baseline` (the oracle
-restatement of the reference, timed on this host).
+reported.  Steps rotate over 4 distinct query batches.  Rank 0 prints ONE JSON line.
+
+A plain run does only what that line's headline needs: it sets up, warms up, times the steps, writes --dump-outputs
+and prints `value`, `ms_per_step` and the repetitions.  --full adds everything else, each leg after the timed
+region as before: the oracle parity gates (--check), the sustained block, the host-to-host leg, `roofline` (binding
+resource of the scan kernel: LDS gather bandwidth; measured HBM beside it) and the per-kernel times from a
+profiled pass, the query-replica run of N > 1, `cpu_baseline` (the oracle restatement of the reference, timed on
+this host) and the HBM-regime leg.
 
 --dump-outputs DIR: after the timed region, rank 0 writes what the last timed step returned to its caller --
 DIR/ids.npy (float64, exact for int32 ids) and DIR/dists.npy (float32), [queries][topk] -- so that two builds
@@ -112,7 +117,7 @@ def hbm_leg():
     so that every call streams the compressed index from HBM (the stream pass).  A child process
     (its own 125 M-code index; this process keeps its workload), its bench line condensed."""
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__), "--codes", "125000000", "--data", "stream", "--queries", "1", "--steps", "10",
+    cmd = [sys.executable, os.path.abspath(__file__), "--full", "--codes", "125000000", "--data", "stream", "--queries", "1", "--steps", "10",
            "--warmup", "2", "--reps", "3", "--check", "4", "--min-check", "4", "--no-cpu-baseline", "--sustain-seconds", "0", "--host-steps", "0",
            "--no-hbm-leg"]
     try:
@@ -295,13 +300,18 @@ def main():
     ap.add_argument("--batch-decode", type=int, default=0,
                     help="dpq_open_opts.batch_decode: 0 auto (batches of >= 3 query groups decode once into a plain-code "
                          "scratch), 1 always, -1 never (decode inside the scan)")
-    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU time given to each leg of the oracle baseline")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--sustain-seconds", type=float, default=2.0, help="length of the sustained block after the timed regions (0 = skip)")
-    ap.add_argument("--host-steps", type=int, default=20, help="steps of the host-to-host leg through dpq_query_batch (N = 1; 0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: parity gates, sustained block, host-to-host leg, roofline and kernel times, "
+                         "query replicas, CPU baseline and HBM-regime leg (the options below marked --full tune these)")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="--full: CPU time given to each leg of the oracle baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the oracle baseline")
+    ap.add_argument("--sustain-seconds", type=float, default=2.0,
+                    help="--full: length of the sustained block after the timed regions (0 = skip)")
+    ap.add_argument("--host-steps", type=int, default=20,
+                    help="--full: steps of the host-to-host leg through dpq_query_batch (N = 1; 0 = skip)")
     ap.add_argument("--min-check", type=int, default=8,
-                    help="queries the parity gate verifies whatever its time budget (a 125 M-code oracle scan takes seconds per query)")
-    ap.add_argument("--check", type=int, default=64, help="queries verified against the oracle before timing (time-bounded)")
+                    help="--full: queries the parity gate verifies whatever its time budget (a 125 M-code oracle scan takes seconds per query)")
+    ap.add_argument("--check", type=int, default=64, help="--full: queries verified against the oracle before timing (time-bounded)")
     ap.add_argument("--shard", choices=["auto", "index", "query"], default="auto",
                     help="N > 1: 'index' (= auto) cuts the index into DFS ranges, every GPU answers the one batch on its "
                          "range, one all-gather + merge (strong scaling, the north-star decomposition); 'query' = every GPU "
@@ -313,9 +323,9 @@ def main():
                          "when present: profiled runs then hold the query path only")
     ap.add_argument("--build-only", action="store_true", help="with --index-dir: build + cache the index and exit")
     ap.add_argument("--no-hbm-leg", action="store_true",
-                    help="skip the HBM-regime leg of the default N = 1 run (one query per call on a 125 M-code index, in a child process)")
+                    help="--full: skip the HBM-regime leg of the default N = 1 run (one query per call on a 125 M-code index, in a child process)")
     ap.add_argument("--no-replicas", action="store_true",
-                    help="N > 1 index shards of an index every rank could hold whole: skip the query-replica run timed beside it")
+                    help="--full: N > 1 index shards of an index every rank could hold whole: skip the query-replica run timed beside it")
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl",
                     help="gloo = rehearsal of the N > 1 path on a box with fewer GPUs than ranks (ranks share GPUs)")
     ap.add_argument("--dump-outputs", default="", metavar="DIR",
@@ -435,10 +445,11 @@ def main():
             dist.barrier()
         torch.cuda.synchronize(dev)
 
-    # correctness gate before timing (rank 0, against the oracle)
+    # correctness gate before timing (--full: rank 0, against the oracle).  The gate's steps on the GPU run in every
+    # run: the timed region has always followed them (both lanes used once), whatever --warmup is.
     out_ids, out_dists = step(0)
     sync()
-    if nq == 1 and args.check > 1:
+    if args.full and nq == 1 and args.check > 1:
         # one query per call: the gate wants several queries through that very path -- one call each
         gate_q = np.concatenate([b[:1] for b in batches_np] + [make_queries(args, 900 + i)[:1] for i in range(max(0, args.check - N_BATCHES))])[:args.check]
         g_ids, g_d = [], []
@@ -449,7 +460,7 @@ def main():
     else:
         gate = None
     parity = 0
-    if rank == 0 and args.check > 0:
+    if args.full and rank == 0 and args.check > 0:
         if wl["whole"] and gate is not None:
             parity = parity_gate(args, wl, gate[0], gate[1], gate[2])
         elif wl["whole"]:
@@ -465,7 +476,7 @@ def main():
     if pipelined:
         o0, o1 = step(0), step(1)
         sync()
-        if rank == 0 and args.check > 0 and wl["whole"]:
+        if args.full and rank == 0 and args.check > 0 and wl["whole"]:
             for b, (oi, od) in enumerate((o0, o1)):
                 overlap_parity += parity_gate(args, wl, batches_np[b][:max(2, args.check // 8)], oi.cpu().numpy(), od.cpu().numpy(),
                                               budget_s=8.0)
@@ -508,7 +519,7 @@ def main():
     # Sustained rate: the same steps back to back for >= --sustain-seconds (the K-step regions above last a few
     # milliseconds: boost clocks; MI355X_MICROARCH.md 'DVFS give-back').  Same work per step, nothing skipped.
     sustained = None
-    if args.sustain_seconds > 0:
+    if args.full and args.sustain_seconds > 0:
         sync()
         n_done, t0 = 0, time.perf_counter()
         while True:
@@ -531,7 +542,7 @@ def main():
     # used for `value`.  Pipelined (dpq_query_batch_host_async: the copies of neighbouring batches beside a batch's
     # kernels, settled by dpq_finish every `steps` batches) and, beside it, one synchronous dpq_query_batch per batch.
     host_to_host = None
-    if world == 1 and args.host_steps > 0:
+    if args.full and world == 1 and args.host_steps > 0:
         hq = [api.pin_host(np.ascontiguousarray(b)) for b in batches_np]
         NH = 16   # batches in flight own their result buffers (dpq_query_batch_host_async: up to sixteen)
         h_out = [(api.pin_host(np.empty((nq, k), dtype=np.int32)), api.pin_host(np.empty((nq, k), dtype=np.float32))) for _ in range(NH)]
@@ -569,60 +580,52 @@ def main():
         for a in hq + [x for pair in h_out for x in pair]:
             api.unpin_host(a)
 
-    aux_steps = max(1, min(args.steps, 8))
-    idx.profile_enable(1)
-    idx.profile_reset()
-    for i in range(aux_steps):
-        idx.query_batch_torch(batches[i % N_BATCHES], k, ids, dists, wait=True)
-    torch.cuda.synchronize(dev)
-    prof = idx.profile_read()
-    prof_aux = prof
-    idx.profile_enable(0)
-    total_steps = aux_steps
+    if args.full:
+        aux_steps = max(1, min(args.steps, 8))
+        idx.profile_enable(1)
+        idx.profile_reset()
+        for i in range(aux_steps):
+            idx.query_batch_torch(batches[i % N_BATCHES], k, ids, dists, wait=True)
+        torch.cuda.synchronize(dev)
+        prof = idx.profile_read()
+        prof_aux = prof
+        idx.profile_enable(0)
+        total_steps = aux_steps
 
-    replicas = None
-    if sharded and not args.no_replicas and wl["whole"]:
-        ridx = open_index()
-        pipelined = True
-        rt = timed(ridx, reps=3)
-        pipelined = False
-        ridx.finish()
-        replicas = {"note": "same GPUs, every rank holds the whole index and answers its own %d-query batch; no collective" % nq,
-                    "value": world * nq * args.steps / float(np.median(rt)), "unit": "queries/s", "scaling": "weak",
-                    "ms_per_step": 1e3 * float(np.median(rt)) / args.steps}
-        ridx.close()
+        replicas = None
+        if sharded and not args.no_replicas and wl["whole"]:
+            ridx = open_index()
+            pipelined = True
+            rt = timed(ridx, reps=3)
+            pipelined = False
+            ridx.finish()
+            replicas = {"note": "same GPUs, every rank holds the whole index and answers its own %d-query batch; no collective" % nq,
+                        "value": world * nq * args.steps / float(np.median(rt)), "unit": "queries/s", "scaling": "weak",
+                        "ms_per_step": 1e3 * float(np.median(rt)) / args.steps}
+            ridx.close()
 
-    QG = 64 if args.m <= 8 else 32   # queries served by one decode pass (8-bit filter entries: 128 KB of LDS tables)
-    groups = (nq + QG - 1) // QG
-    S = 64 * info["chunks_per_segment"]
-    batch_decoded = prof_aux["decode_ms"] > 0.0
-    decode_ms_step = prof_aux["decode_ms"] / aux_steps
-    lds_bytes_step = float(info["n_segments"]) * S * groups * (4 if args.m <= 8 else 2) * args.m * 16   # NG * M * 16 B per node and group
-    stats = torch.tensor([prof["scan_ms"], float(prof["scan_launches"]), float(info["algorithmic_bytes"]),
-                          float(info["device_bytes"] + info["bootstrap_bytes"]), prof_aux["select_ms"], prof_aux["lut_ms"],
-                          prof_aux["quantise_ms"], lds_bytes_step, float(prof_aux["exact_checks"]), float(prof_aux["candidates"]),
-                          float(info["node_hi"] - info["node_lo"]), prof_aux["decode_ms"], float(info["strand_bytes"]),
-                          float(prof_aux["stream_launches"]), float(prof_aux["strand_launches"]), float(prof_aux["strand1_launches"])],
-                         dtype=torch.float64, device=torch.device("cpu") if cpu_coll else dev)
-    if world > 1:
-        all_stats = [torch.zeros_like(stats) for _ in range(world)]
-        dist.all_gather(all_stats, stats)
-        all_stats = torch.stack(all_stats).cpu().numpy()
-    else:
-        all_stats = stats.cpu().numpy()[None, :]
+        QG = 64 if args.m <= 8 else 32   # queries served by one decode pass (8-bit filter entries: 128 KB of LDS tables)
+        groups = (nq + QG - 1) // QG
+        S = 64 * info["chunks_per_segment"]
+        batch_decoded = prof_aux["decode_ms"] > 0.0
+        decode_ms_step = prof_aux["decode_ms"] / aux_steps
+        lds_bytes_step = float(info["n_segments"]) * S * groups * (4 if args.m <= 8 else 2) * args.m * 16   # NG * M * 16 B per node and group
+        stats = torch.tensor([prof["scan_ms"], float(prof["scan_launches"]), float(info["algorithmic_bytes"]),
+                              float(info["device_bytes"] + info["bootstrap_bytes"]), prof_aux["select_ms"], prof_aux["lut_ms"],
+                              prof_aux["quantise_ms"], lds_bytes_step, float(prof_aux["exact_checks"]), float(prof_aux["candidates"]),
+                              float(info["node_hi"] - info["node_lo"]), prof_aux["decode_ms"], float(info["strand_bytes"]),
+                              float(prof_aux["stream_launches"]), float(prof_aux["strand_launches"]), float(prof_aux["strand1_launches"])],
+                             dtype=torch.float64, device=torch.device("cpu") if cpu_coll else dev)
+        if world > 1:
+            all_stats = [torch.zeros_like(stats) for _ in range(world)]
+            dist.all_gather(all_stats, stats)
+            all_stats = torch.stack(all_stats).cpu().numpy()
+        else:
+            all_stats = stats.cpu().numpy()[None, :]
 
     if rank == 0:
         med = float(np.median(times))
-        scan_ms_step = float(all_stats[:, 0].max()) / total_steps          # slowest rank
-        launches_step = float(all_stats[0, 1]) / total_steps
-        alg_bytes_total = float(all_stats[:, 2].sum())     # index shards: n_bytes of the payload; replicas: world x n_bytes
-        lds_total = float(all_stats[:, 7].sum())
-        lds_gbps = lds_total / (scan_ms_step * 1e-3) / 1e9 if scan_ms_step > 0 else 0.0
-        traffic, pmc_launch_ms, pmc_name = pmc_traffic(args, world)
-        avg_launch_ms = scan_ms_step / launches_step if launches_step else None
-        prof_ms, prof_name = profile_launch_ms(args, world)
         global_q = (world if by_query else 1) * nq
-        bytes_per_code = float(all_stats[:, 2].sum()) / max(1.0, float(all_stats[:, 10].sum()))
         result = {
             "metric": "queries/sec, SIFT1M-shaped m=%d k=256 topk=%d" % (args.m, k),
             "value": global_q * args.steps / med,
@@ -636,132 +639,144 @@ def main():
             "vs_baseline": None,
             "dtype": "f64 sum of f32 table entries (u8 code decode; the reference's incremental f64 stack)",
             "data": "synthetic",
-            "config": {
-                "workload": "SIFT1M-shaped synthetic (%s): N=%d m=%d k=256 h=1 topk=%d, %d queries/step, %.2f B/code"
-                            % (wl["desc"], args.n, args.m, k, nq, bytes_per_code),
-                "n_codes": args.n, "queries_per_step": nq, "topk": k,
-                "n_bytes": int(alg_bytes_total if not by_query else alg_bytes_total / world),
-                "sharding": "one GPU, whole index" if world == 1 else
-                            ("query replicas x%d: every GPU holds the whole index and answers its own %d-query batch" % (world, nq)
-                             if by_query else "dfs-range index shards x%d, one %d-query batch, one all-gather + merge" % (world, nq)),
-                "global_queries_per_step": global_q,
-                "collectives": None if world == 1 else (backend_note or ("gloo (host tensors)" if cpu_coll else "RCCL (backend nccl)")),
-                "query_batches_rotated": N_BATCHES,
-                "step_pipelining": "two lanes (dpq_query_batch_device_async)" if pipelined or not sharded else
-                                   ("stream-ordered steps (dpq_query_batch_device_ordered) alternating between %d stream(s), no host round trip; "
-                                    "no batch had to be answered again" % n_step_streams
-                                    if state["ordered"] else "one synchronous call per step (a batch overflowed in the stream-ordered run)"),
-                "queries_per_decode_pass": (groups * QG if batch_decoded else QG),
-                "decode": ("once per batch (decode_list_kernel), tile by tile, into %d MB of plain codes that the %d query groups' "
-                           "filter passes read through L2 / Infinity Cache" % (info["batch_decode_mb"], groups)) if batch_decoded
-                          else "inside the scan kernel, once per %d-query group" % QG,
-                "threshold_bootstrap": "multi-index, stride %d, %.1f MB" % (info["bootstrap_stride"], info["bootstrap_bytes"] / 1e6)
-                                       if info["bootstrap_bytes"] else "off (spread-sample cascade)",
-            },
             "repetitions": {"count": int(len(times)), "steps_each": args.steps,
                             "ms_per_step_median": 1e3 * med / args.steps,
                             "ms_per_step_min": 1e3 * float(times.min()) / args.steps,
                             "ms_per_step_max": 1e3 * float(times.max()) / args.steps,
                             "value_min": global_q * args.steps / float(times.max()),
                             "value_max": global_q * args.steps / float(times.min())},
-            "roofline": {
-                "bound": "lds",
-                "kernel": "scan_kernel",
-                "achieved": lds_gbps,
-                "peak": LDS_PEAK_GBPS * world,
-                "unit": "GB/s",
-                "frac": lds_gbps / (LDS_PEAK_GBPS * world),
-                "traffic": traffic,
-                "traffic_source": None if traffic is None else "committed profile profiles/%s (rocprofv3 --pmc passes of this workload on another run), not measured in this run" % pmc_name,
-                "definition": "achieved = LDS bytes of the ADC table gathers the scan launches issue (per decoded node and "
-                              "%d-query group: M x %d ds_read_b128 = %d B, i.e. %d B per (code, query) pair, padding slots "
-                              "included) / scan-kernel time (HIP events on the launch stream); peak = 256 CUs x 256 B/clk x "
-                              "2.4 GHz.  The scan is a gather/lookup kernel bound by the LDS array (bank-conflict replays and the "
-                              "decode's ds_bpermute traffic come on top of the counted bytes), not by HBM: see `hbm`."
-                              % (QG, 4 if args.m <= 8 else 2, (4 if args.m <= 8 else 2) * args.m * 16, args.m),
-                "lds_gather_bytes_per_step": lds_total,
-                "hbm": None if traffic is None else {
-                    "achieved": traffic / ((pmc_launch_ms or avg_launch_ms) * 1e-3) / 1e9, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                    "frac": traffic / ((pmc_launch_ms or avg_launch_ms) * 1e-3) / 1e9 / HBM_PEAK_GBPS,
-                    "bytes_per_launch": traffic, "source": "profiles/%s: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in separate passes, "
-                                                           "2 x FETCH_SIZE + WRITE_SIZE (gfx950 correction)" % pmc_name},
-                "algorithmic_hbm": {
-                    "GBps": (nq * alg_bytes_total) / ((scan_ms_step + decode_ms_step) * 1e-3) / 1e9 if scan_ms_step > 0 else 0.0,
-                    "bytes_per_step": nq * alg_bytes_total,
-                    "note": "SURVEY.md 8(d) figure: queries x DTC payload bytes / (scan + per-batch decode) time.  Every decoded "
-                            "chunk serves %d queries, so this is reuse, not traffic: it is NOT a fraction of the HBM roof"
-                            % (groups * QG if batch_decoded else QG)},
-                "launches_per_step": launches_step,
-                "avg_launch_ms": avg_launch_ms,
-                # the same kernel in the committed rocprofv3 --kernel-trace --stats run of this workload (one lane, another box /
-                # another run): what `frac` is when recomputed from profiles/ alone
-                "from_profiles": None if not (prof_ms and launches_step) else {
-                    "avg_launch_ms_kernel_trace": prof_ms, "source": "profiles/%s" % prof_name,
-                    "frac": lds_total / launches_step / (prof_ms * 1e-3) / 1e9 / (LDS_PEAK_GBPS * world)},
-                "scan_ms_per_step": scan_ms_step,
-                "select_ms_per_step": float(all_stats[:, 4].max()) / aux_steps,
-                "lut_ms_per_step": float(all_stats[:, 5].max()) / aux_steps,
-                "quantise_ms_per_step": float(all_stats[:, 6].max()) / aux_steps,
-                "decode_ms_per_step": float(all_stats[:, 11].max()) / aux_steps,
-                "filter_survivors_per_query": float(all_stats[:, 8].sum()) / max(1, aux_steps * nq),
-                "candidates_per_query": float(all_stats[:, 9].sum()) / max(1, aux_steps * nq),
-                "event_note": "kernel times (scan, select incl. bootstrap, lut, quantise, per-batch decode) from %d synchronous steps run after the "
-                              "timed regions with HIP events around every kernel on the launch stream; the timed regions carry no "
-                              "events (pipelined batches overlap on two lanes there)" % aux_steps,
-            },
-            "parity_checked_queries": parity,
-            "parity_checked_queries_overlapped_steps": overlap_parity,
-            "sustained": sustained,
-            "host_to_host": host_to_host,
-            # SURVEY.md 8(d) "report alongside": whole-job rates of the timed regions (median repetition)
-            "rates": {"code_query_pairs_per_s": global_q * args.steps / med * float(all_stats[:, 10].sum()) / (1 if sharded or world == 1 else world),
-                      "raw_pq_equivalent_GBps": global_q * args.steps / med * float(all_stats[:, 10].sum()) / (1 if sharded or world == 1 else world) * args.m / 1e9,
-                      "note": "queries/s x codes each query is compared with (every code, exactly once); x M bytes = the bandwidth "
-                              "a plain PQ scan would need at one query per pass"},
-            "index": {"device_bytes_rank0": int(all_stats[0, 3] + all_stats[0, 12]), "strand_bytes_rank0": int(all_stats[0, 12]),
-                      "segments_rank0": info["n_segments"],
-                      "codes_rank0": int(all_stats[0, 10]), "gen_seconds": wl["gen_s"]},
         }
-        dev = os.environ.get("DPQ_DEV", "0") not in ("", "0")
-        stream_max = int(os.environ.get("DPQ_STREAM_MAX_QUERIES", "4")) if dev else 4   # the library's measured switch-over
-        if nq <= stream_max:
-            # up to four queries: the stream pass -- 1, 2 or 4 queries per pass over the compressed image, every decoded node
-            # against the queries' exact tables in LDS -- the mode in which the path is bound by the decode and by HBM,
-            # not by the filter tables' LDS gathers
-            r = result["roofline"]
-            per_pass = 1 if nq <= 1 else 2 if nq <= 2 else 4
-            passes = -(-nq // per_pass)
-            # which kernels the stream pass's launches were (dpq_profile counts them): named as they ran, all of them
-            # when a call's levels mix
-            ran = {"stream_kernel": float(all_stats[0, 13]) / aux_steps, "strand_kernel": float(all_stats[0, 14]) / aux_steps,
-                   "strand1_kernel": float(all_stats[0, 15]) / aux_steps}
-            names = [n for n, c in ran.items() if c > 0]
-            strands = any(n.startswith("strand") for n in names)
-            alg = (passes * alg_bytes_total) / (scan_ms_step * 1e-3) / 1e9 if scan_ms_step > 0 else 0.0
-            r.update({"bound": "hbm", "kernel": " + ".join(names) if names else "stream_kernel", "stream_pass_launches_per_step": ran,
-                      "achieved": alg, "peak": HBM_PEAK_GBPS * world,
-                      "frac": alg / (HBM_PEAK_GBPS * world),
-                      "definition": "stream pass, %d quer%s per pass, %d pass(es): achieved = passes x DTC payload bytes (SURVEY.md 8(d): every "
-                                    "pass streams the compressed index once) / kernel time of the pass's launches (HIP events on the launch "
-                                    "stream); peak = 8 TB/s HBM3E.  `hbm` holds the physical bytes of the counters where a matching PMC "
-                                    "summary is committed." % (per_pass, "y" if per_pass == 1 else "ies", passes),
-                      "queries_per_pass": per_pass, "passes": passes})
-            r.pop("lds_gather_bytes_per_step", None)
-            r["algorithmic_hbm"]["note"] = ("queries x DTC payload bytes / kernel time: with %d quer%s per pass this is %d x the bytes the "
-                                            "passes stream" % (per_pass, "y" if per_pass == 1 else "ies", per_pass))
-            result["config"]["decode"] = ("lane per run of 64 nodes over the strand image (%s)" % " + ".join(names) if strands else
-                                          "wavefront per 64-node chunk (stream_kernel)") + ", once per pass of %d quer%s" % (per_pass, "y" if per_pass == 1 else "ies")
-            result["config"]["queries_per_decode_pass"] = per_pass
-        if replicas:
-            result["query_replicas"] = replicas
         if dumped:
             result["dumped_outputs"] = dumped
-        if world == 1 and not args.no_cpu_baseline:
-            result["cpu_baseline"] = cpu_baseline(wl, args, batches_np[0])
-            result["vs_cpu_baseline_1_thread"] = result["value"] / result["cpu_baseline"]["value"]
-        default_workload = (args.n, args.queries, args.topk, args.m, args.data) == (1_000_000, 1000, 100, 8, "pipeline")
-        if world == 1 and default_workload and not args.no_hbm_leg:
-            result["hbm_regime"] = hbm_leg()
+        if args.full:
+            scan_ms_step = float(all_stats[:, 0].max()) / total_steps          # slowest rank
+            launches_step = float(all_stats[0, 1]) / total_steps
+            alg_bytes_total = float(all_stats[:, 2].sum())     # index shards: n_bytes of the payload; replicas: world x n_bytes
+            lds_total = float(all_stats[:, 7].sum())
+            lds_gbps = lds_total / (scan_ms_step * 1e-3) / 1e9 if scan_ms_step > 0 else 0.0
+            traffic, pmc_launch_ms, pmc_name = pmc_traffic(args, world)
+            avg_launch_ms = scan_ms_step / launches_step if launches_step else None
+            prof_ms, prof_name = profile_launch_ms(args, world)
+            bytes_per_code = float(all_stats[:, 2].sum()) / max(1.0, float(all_stats[:, 10].sum()))
+            result.update({
+                "config": {
+                    "workload": "SIFT1M-shaped synthetic (%s): N=%d m=%d k=256 h=1 topk=%d, %d queries/step, %.2f B/code"
+                                % (wl["desc"], args.n, args.m, k, nq, bytes_per_code),
+                    "n_codes": args.n, "queries_per_step": nq, "topk": k,
+                    "n_bytes": int(alg_bytes_total if not by_query else alg_bytes_total / world),
+                    "sharding": "one GPU, whole index" if world == 1 else
+                                ("query replicas x%d: every GPU holds the whole index and answers its own %d-query batch" % (world, nq)
+                                 if by_query else "dfs-range index shards x%d, one %d-query batch, one all-gather + merge" % (world, nq)),
+                    "global_queries_per_step": global_q,
+                    "collectives": None if world == 1 else (backend_note or ("gloo (host tensors)" if cpu_coll else "RCCL (backend nccl)")),
+                    "query_batches_rotated": N_BATCHES,
+                    "step_pipelining": "two lanes (dpq_query_batch_device_async)" if pipelined or not sharded else
+                                       ("stream-ordered steps (dpq_query_batch_device_ordered) alternating between %d stream(s), no host round trip; "
+                                        "no batch had to be answered again" % n_step_streams
+                                        if state["ordered"] else "one synchronous call per step (a batch overflowed in the stream-ordered run)"),
+                    "queries_per_decode_pass": (groups * QG if batch_decoded else QG),
+                    "decode": ("once per batch (decode_list_kernel), tile by tile, into %d MB of plain codes that the %d query groups' "
+                               "filter passes read through L2 / Infinity Cache" % (info["batch_decode_mb"], groups)) if batch_decoded
+                              else "inside the scan kernel, once per %d-query group" % QG,
+                    "threshold_bootstrap": "multi-index, stride %d, %.1f MB" % (info["bootstrap_stride"], info["bootstrap_bytes"] / 1e6)
+                                           if info["bootstrap_bytes"] else "off (spread-sample cascade)",
+                },
+                "roofline": {
+                    "bound": "lds",
+                    "kernel": "scan_kernel",
+                    "achieved": lds_gbps,
+                    "peak": LDS_PEAK_GBPS * world,
+                    "unit": "GB/s",
+                    "frac": lds_gbps / (LDS_PEAK_GBPS * world),
+                    "traffic": traffic,
+                    "traffic_source": None if traffic is None else "committed profile profiles/%s (rocprofv3 --pmc passes of this workload on another run), not measured in this run" % pmc_name,
+                    "definition": "achieved = LDS bytes of the ADC table gathers the scan launches issue (per decoded node and "
+                                  "%d-query group: M x %d ds_read_b128 = %d B, i.e. %d B per (code, query) pair, padding slots "
+                                  "included) / scan-kernel time (HIP events on the launch stream); peak = 256 CUs x 256 B/clk x "
+                                  "2.4 GHz.  The scan is a gather/lookup kernel bound by the LDS array (bank-conflict replays and the "
+                                  "decode's ds_bpermute traffic come on top of the counted bytes), not by HBM: see `hbm`."
+                                  % (QG, 4 if args.m <= 8 else 2, (4 if args.m <= 8 else 2) * args.m * 16, args.m),
+                    "lds_gather_bytes_per_step": lds_total,
+                    "hbm": None if traffic is None else {
+                        "achieved": traffic / ((pmc_launch_ms or avg_launch_ms) * 1e-3) / 1e9, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                        "frac": traffic / ((pmc_launch_ms or avg_launch_ms) * 1e-3) / 1e9 / HBM_PEAK_GBPS,
+                        "bytes_per_launch": traffic, "source": "profiles/%s: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in separate passes, "
+                                                               "2 x FETCH_SIZE + WRITE_SIZE (gfx950 correction)" % pmc_name},
+                    "algorithmic_hbm": {
+                        "GBps": (nq * alg_bytes_total) / ((scan_ms_step + decode_ms_step) * 1e-3) / 1e9 if scan_ms_step > 0 else 0.0,
+                        "bytes_per_step": nq * alg_bytes_total,
+                        "note": "SURVEY.md 8(d) figure: queries x DTC payload bytes / (scan + per-batch decode) time.  Every decoded "
+                                "chunk serves %d queries, so this is reuse, not traffic: it is NOT a fraction of the HBM roof"
+                                % (groups * QG if batch_decoded else QG)},
+                    "launches_per_step": launches_step,
+                    "avg_launch_ms": avg_launch_ms,
+                    # the same kernel in the committed rocprofv3 --kernel-trace --stats run of this workload (one lane, another box /
+                    # another run): what `frac` is when recomputed from profiles/ alone
+                    "from_profiles": None if not (prof_ms and launches_step) else {
+                        "avg_launch_ms_kernel_trace": prof_ms, "source": "profiles/%s" % prof_name,
+                        "frac": lds_total / launches_step / (prof_ms * 1e-3) / 1e9 / (LDS_PEAK_GBPS * world)},
+                    "scan_ms_per_step": scan_ms_step,
+                    "select_ms_per_step": float(all_stats[:, 4].max()) / aux_steps,
+                    "lut_ms_per_step": float(all_stats[:, 5].max()) / aux_steps,
+                    "quantise_ms_per_step": float(all_stats[:, 6].max()) / aux_steps,
+                    "decode_ms_per_step": float(all_stats[:, 11].max()) / aux_steps,
+                    "filter_survivors_per_query": float(all_stats[:, 8].sum()) / max(1, aux_steps * nq),
+                    "candidates_per_query": float(all_stats[:, 9].sum()) / max(1, aux_steps * nq),
+                    "event_note": "kernel times (scan, select incl. bootstrap, lut, quantise, per-batch decode) from %d synchronous steps run after the "
+                                  "timed regions with HIP events around every kernel on the launch stream; the timed regions carry no "
+                                  "events (pipelined batches overlap on two lanes there)" % aux_steps,
+                },
+                "parity_checked_queries": parity,
+                "parity_checked_queries_overlapped_steps": overlap_parity,
+                "sustained": sustained,
+                "host_to_host": host_to_host,
+                # SURVEY.md 8(d) "report alongside": whole-job rates of the timed regions (median repetition)
+                "rates": {"code_query_pairs_per_s": global_q * args.steps / med * float(all_stats[:, 10].sum()) / (1 if sharded or world == 1 else world),
+                          "raw_pq_equivalent_GBps": global_q * args.steps / med * float(all_stats[:, 10].sum()) / (1 if sharded or world == 1 else world) * args.m / 1e9,
+                          "note": "queries/s x codes each query is compared with (every code, exactly once); x M bytes = the bandwidth "
+                                  "a plain PQ scan would need at one query per pass"},
+                "index": {"device_bytes_rank0": int(all_stats[0, 3] + all_stats[0, 12]), "strand_bytes_rank0": int(all_stats[0, 12]),
+                          "segments_rank0": info["n_segments"],
+                          "codes_rank0": int(all_stats[0, 10]), "gen_seconds": wl["gen_s"]},
+            })
+            dev = os.environ.get("DPQ_DEV", "0") not in ("", "0")
+            stream_max = int(os.environ.get("DPQ_STREAM_MAX_QUERIES", "4")) if dev else 4   # the library's measured switch-over
+            if nq <= stream_max:
+                # up to four queries: the stream pass -- 1, 2 or 4 queries per pass over the compressed image, every decoded node
+                # against the queries' exact tables in LDS -- the mode in which the path is bound by the decode and by HBM,
+                # not by the filter tables' LDS gathers
+                r = result["roofline"]
+                per_pass = 1 if nq <= 1 else 2 if nq <= 2 else 4
+                passes = -(-nq // per_pass)
+                # which kernels the stream pass's launches were (dpq_profile counts them): named as they ran, all of them
+                # when a call's levels mix
+                ran = {"stream_kernel": float(all_stats[0, 13]) / aux_steps, "strand_kernel": float(all_stats[0, 14]) / aux_steps,
+                       "strand1_kernel": float(all_stats[0, 15]) / aux_steps}
+                names = [n for n, c in ran.items() if c > 0]
+                strands = any(n.startswith("strand") for n in names)
+                alg = (passes * alg_bytes_total) / (scan_ms_step * 1e-3) / 1e9 if scan_ms_step > 0 else 0.0
+                r.update({"bound": "hbm", "kernel": " + ".join(names) if names else "stream_kernel", "stream_pass_launches_per_step": ran,
+                          "achieved": alg, "peak": HBM_PEAK_GBPS * world,
+                          "frac": alg / (HBM_PEAK_GBPS * world),
+                          "definition": "stream pass, %d quer%s per pass, %d pass(es): achieved = passes x DTC payload bytes (SURVEY.md 8(d): every "
+                                        "pass streams the compressed index once) / kernel time of the pass's launches (HIP events on the launch "
+                                        "stream); peak = 8 TB/s HBM3E.  `hbm` holds the physical bytes of the counters where a matching PMC "
+                                        "summary is committed." % (per_pass, "y" if per_pass == 1 else "ies", passes),
+                          "queries_per_pass": per_pass, "passes": passes})
+                r.pop("lds_gather_bytes_per_step", None)
+                r["algorithmic_hbm"]["note"] = ("queries x DTC payload bytes / kernel time: with %d quer%s per pass this is %d x the bytes the "
+                                                "passes stream" % (per_pass, "y" if per_pass == 1 else "ies", per_pass))
+                result["config"]["decode"] = ("lane per run of 64 nodes over the strand image (%s)" % " + ".join(names) if strands else
+                                              "wavefront per 64-node chunk (stream_kernel)") + ", once per pass of %d quer%s" % (per_pass, "y" if per_pass == 1 else "ies")
+                result["config"]["queries_per_decode_pass"] = per_pass
+            if replicas:
+                result["query_replicas"] = replicas
+            if world == 1 and not args.no_cpu_baseline:
+                result["cpu_baseline"] = cpu_baseline(wl, args, batches_np[0])
+                result["vs_cpu_baseline_1_thread"] = result["value"] / result["cpu_baseline"]["value"]
+            default_workload = (args.n, args.queries, args.topk, args.m, args.data) == (1_000_000, 1000, 100, 8, "pipeline")
+            if world == 1 and default_workload and not args.no_hbm_leg:
+                result["hbm_regime"] = hbm_leg()
         print(json.dumps(result))
     idx.close()
     if world > 1:

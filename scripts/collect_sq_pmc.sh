@@ -1,4 +1,5 @@
 #!/bin/bash
+export RESULTS=${RESULTS:-results}   # where this script writes, relative to the repository root
 export DPQ_DEV=1   # developer switches of the library are read only with this set
 # Runs ON THE GPU BOX (via gpurun): SQ / LDS counters of the scan kernel on a bench.py workload,
 # one rocprofv3 --pmc pass per counter group (only --kernel-trace beside it, as the pool requires).
@@ -8,7 +9,7 @@ TAG=${1:-sq}; shift
 # per-kernel figures want one kernel at a time on the GPU: pipelined batches on one lane
 export DPQ_ASYNC_OVERLAP=${DPQ_ASYNC_OVERLAP:-0}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
-OUT=gpurun_out/$TAG
+OUT=$RESULTS/$TAG
 rm -rf "$OUT" && mkdir -p "$OUT"
 i=0
 for grp in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_SMEM SQ_INSTS_BRANCH" \
@@ -16,7 +17,7 @@ for grp in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SA
            "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_LDS_ADDR_CONFLICT SQ_LDS_CMD_FIFO_FULL SQ_LDS_DATA_FIFO_FULL SQ_INST_CYCLES_SALU SQ_THREAD_CYCLES_VALU SQ_INST_LEVEL_LDS" \
            "SQ_INSTS_LDS_LOAD SQ_INSTS_LDS_STORE SQ_INSTS_LDS_ATOMIC SQ_INSTS_LDS_LOAD_BANDWIDTH SQ_VMEM_TA_ADDR_FIFO_FULL SQ_VMEM_TA_CMD_FIFO_FULL SQ_INST_LEVEL_VMEM SQ_BUSY_CU_CYCLES"; do
   i=$((i+1))
-  timeout -k 10 300 rocprofv3 --kernel-trace --pmc $grp --output-format csv -d $OUT/p$i -- python bench.py --steps 3 --warmup 1 --reps 1 --no-cpu-baseline --check 0 --no-hbm-leg --sustain-seconds 0 --host-steps 0 "$@" > /dev/null 2> $OUT/p$i.err || echo "pass $i failed" >> $OUT/failed.txt
+  timeout -k 10 300 rocprofv3 --kernel-trace --pmc $grp --output-format csv -d $OUT/p$i -- python bench.py --full --steps 3 --warmup 1 --reps 1 --no-cpu-baseline --check 0 --no-hbm-leg --sustain-seconds 0 --host-steps 0 "$@" > /dev/null 2> $OUT/p$i.err || echo "pass $i failed" >> $OUT/failed.txt
 done
 for K in $(echo "${KERNEL:-scan_kernel}" | tr ',' ' '); do   # KERNEL: one kernel or a comma-separated list (a summary each)
 python - "$OUT" "$K" <<'PY'

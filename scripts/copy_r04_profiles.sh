@@ -1,7 +1,8 @@
 #!/bin/bash
-# gpurun_out/ (scratch) -> profiles/ (tracked): the round-4 evidence files produced by scripts/gpu_final_profiles_r04.sh
+# $RESULTS/ (scratch) -> profiles/ (tracked): the round-4 evidence files produced by scripts/gpu_final_profiles_r04.sh
+export RESULTS=${RESULTS:-results}   # where this script writes, relative to the repository root
 cd "$(dirname "$0")/.." || exit 1
-G=gpurun_out; P=profiles
+G=$RESULTS; P=profiles
 cp $G/r04final/r04_bench_line_default.json $P/ 2>/dev/null
 cp $G/r04_default/r04_default_kernel_stats.csv $P/r04_default_kernel_stats.csv 2>/dev/null
 cp $G/r04_default/r04_default_pmc_summary.json $P/r04_pmc_summary_default.json 2>/dev/null

@@ -90,5 +90,6 @@ with api.DeltaPQIndex.open_plain(codes_dfs) as idx:
     stamps(idx, "plain_dfs_order")
 with api.DeltaPQIndex.open_plain(codes) as idx:
     timed(idx, "plain_file_order")
-os.makedirs("gpurun_out", exist_ok=True)
-json.dump(out, open("gpurun_out/limiter_%s.json" % os.environ.get("TAG", "r02"), "w"), indent=1)
+results = os.environ.get("RESULTS", "results")
+os.makedirs(results, exist_ok=True)
+json.dump(out, open(os.path.join(results, "limiter_%s.json" % os.environ.get("TAG", "r02")), "w"), indent=1)

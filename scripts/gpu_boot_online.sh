@@ -1,9 +1,10 @@
 #!/bin/bash
 # round 4: bootstrap_kernel<M, 2> (histogram filled while the nodes are evaluated, no key list: LDS independent of the nodes
 # evaluated) against <M, 1> (key list + one histogram pass), over top_k; parity subset under variant 2 first
+export RESULTS=${RESULTS:-results}   # where this script writes, relative to the repository root
 set -o pipefail
 cd "$GRAFT_REPO_ROOT" || exit 1
-O=gpurun_out/booto; mkdir -p $O
+O=$RESULTS/booto; mkdir -p $O
 step() { echo "$(date +%T) $1" | tee -a $O/progress.txt; }
 export DPQ_DEV=1
 step "parity subset, variant 2"
@@ -14,7 +15,7 @@ timeout -k 10 300 python scripts/dev_boot_stamps.py 1 2 1 2 > $O/stamps.txt 2>&1
 grep -v "amdgpu.ids" $O/stamps.txt
 line() {  # tag, variant, bench args
   local tag=$1 bv=$2; shift 2
-  DPQ_BOOT_VARIANT=$bv timeout -k 10 400 python bench.py --index-dir /tmp/dpq_index_cache --no-cpu-baseline --reps ${REPS:-10} --no-hbm-leg --sustain-seconds 0 --host-steps 0 --no-replicas "$@" > $O/b.json 2> $O/b.err || { tail -5 $O/b.err; return 1; }
+  DPQ_BOOT_VARIANT=$bv timeout -k 10 400 python bench.py --full --index-dir /tmp/dpq_index_cache --no-cpu-baseline --reps ${REPS:-10} --no-hbm-leg --sustain-seconds 0 --host-steps 0 --no-replicas "$@" > $O/b.json 2> $O/b.err || { tail -5 $O/b.err; return 1; }
   python - <<PY | tee -a $O/ab.txt
 import json
 d=json.loads(open("$O/b.json").read().strip().splitlines()[-1])

@@ -1,9 +1,10 @@
 #!/bin/bash
 # round 4: the GPU builder's per-subset hash pre-filter (find_edges_gpu): identical trees (builder tests), and the 1 M x M = 16
 # index build under rocprofv3 --kernel-trace --stats (dispatches, GPU time), with the pre-filter and (PF0=1) without
+export RESULTS=${RESULTS:-results}   # where this script writes, relative to the repository root
 set -o pipefail
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
-O=gpurun_out/bpf; mkdir -p $O
+O=$RESULTS/bpf; mkdir -p $O
 step() { echo "$(date +%T) $1" | tee -a $O/progress.txt; }
 step "builder tests"
 timeout -k 10 600 python -m pytest tests/test_builder.py tests/test_hand_derived_builder.py -q -x -m gpu > $O/pytest_builder.log 2>&1 || { tail -30 $O/pytest_builder.log; exit 1; }

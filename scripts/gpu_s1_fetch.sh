@@ -1,7 +1,8 @@
 #!/bin/bash
 # HBM bytes fetched by one strand1_kernel launch (125 M codes): rocprofv3 --pmc FETCH_SIZE (x2: the gfx950 correction for wide reads)
+export RESULTS=${RESULTS:-results}   # where this script writes, relative to the repository root
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
-OUT=gpurun_out/s1_fetch; rm -rf $OUT; mkdir -p $OUT
+OUT=$RESULTS/s1_fetch; rm -rf $OUT; mkdir -p $OUT
 python scripts/dev_strand1.py --codes ${CODES:-125000000} --calls 2 > $OUT/warm.txt 2>&1
 timeout -k 10 400 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/p -- python scripts/dev_strand1.py --codes ${CODES:-125000000} --calls 4 > $OUT/p.out 2> $OUT/p.err
 python - "$OUT" <<'PY'

@@ -1,9 +1,10 @@
 #!/bin/bash
 # Vector-memory side counters of the one-query strand pass (TA / TD / TCP / address translation), one rocprofv3 --pmc pass per group.
 #   gpurun -- 'bash scripts/gpu_s1_mem_pmc.sh TAG [CODES]'
+export RESULTS=${RESULTS:-results}   # where this script writes, relative to the repository root
 TAG=${1:-s1_mem}; CODES=${2:-125000000}; KERNEL=strand1_kernel
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
-OUT=gpurun_out/$TAG
+OUT=$RESULTS/$TAG
 rm -rf "$OUT" && mkdir -p "$OUT"
 python scripts/dev_strand1.py --codes $CODES --calls 2 > $OUT/warm.txt 2>&1   # fills the payload cache
 i=0

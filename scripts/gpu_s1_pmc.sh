@@ -1,9 +1,10 @@
 #!/bin/bash
 # SQ / LDS counters of the one-query strand pass (scripts/dev_strand1.py workload), one rocprofv3 --pmc pass per group.
 #   gpurun -- 'bash scripts/gpu_s1_pmc.sh TAG [CODES] [FLAGS] [KERNEL]'
+export RESULTS=${RESULTS:-results}   # where this script writes, relative to the repository root
 TAG=${1:-s1_pmc}; CODES=${2:-32000000}; FLAGS=${3:-0}; KERNEL=${4:-strand1_kernel}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
-OUT=gpurun_out/$TAG
+OUT=$RESULTS/$TAG
 rm -rf "$OUT" && mkdir -p "$OUT"
 [ -n "$LIST" ] && rocprofv3 -L > $OUT/counters_list.txt 2>&1
 python scripts/dev_strand1.py --codes $CODES --calls 2 --flags $FLAGS > $OUT/warm.txt 2>&1   # fills the payload cache

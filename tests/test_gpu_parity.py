@@ -564,12 +564,30 @@ def test_bench_one_gpu_times_steps_and_dumps_the_last_one(gpu, oracle, tmp_path)
     assert_parity(ids.astype(np.int64), dists, oracle_topk(oracle, z["payload"], n, z["codebook"], qs, k), n)
 
 
+def test_bench_plain_run_prints_the_headline_only(gpu, built):
+    """bench.py without --full: the line holds the headline and the timed region's repetitions; none of the legs that
+    --full adds (parity gates, sustained block, host-to-host, roofline, CPU baseline, HBM regime) ran."""
+    import json
+    import sys
+    nq, steps = 64, 5
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--codes", "100000", "--queries", str(nq),
+           "--steps", str(steps), "--warmup", "1"]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert set(line) == {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                         "vs_baseline", "dtype", "data", "repetitions"}
+    assert line["steps"] == steps and line["warmup"] == 1 and line["unit"] == "queries/s" and line["higher_is_better"]
+    assert line["value"] > 0 and abs(line["value"] - nq * 1e3 / line["ms_per_step"]) <= 1e-9 * line["value"]
+    assert line["repetitions"]["count"] == 1 and line["repetitions"]["ms_per_step_median"] == line["ms_per_step"]
+
+
 @pytest.mark.parametrize("mode", ["index_stream_parts", "index_pipeline", "query"])
 def test_bench_two_ranks_rehearsal(gpu, built, mode):
     """bench.py's N > 1 paths end to end, 2 ranks on GPU 0 (gloo instead of RCCL, ranks share the GPU):
     index shards where every rank synthesises only its own DFS range (configs[3]/[4] scaled down; the default
     decomposition, strong scaling), index shards of a pipeline-built index, and query replicas (--shard query)."""
-    common = ["--backend", "gloo", "--queries", "100", "--steps", "3", "--warmup", "1", "--reps", "2", "--check", "3",
+    common = ["--full", "--backend", "gloo", "--queries", "100", "--steps", "3", "--warmup", "1", "--reps", "2", "--check", "3",
               "--no-cpu-baseline"]
     if mode == "index_stream_parts":
         line = _run_bench(common + ["--data", "stream", "--codes", "700001"])
@@ -601,7 +619,7 @@ def test_bench_two_gpus_over_rccl(gpu, built, mode):
     args = {"index_pipeline": ["--data", "pipeline", "--codes", "300000"],
             "index_stream_parts": ["--data", "stream", "--codes", "600000"],
             "query": ["--data", "pipeline", "--codes", "300000", "--shard", "query"]}[mode]
-    line = _run_bench(["--backend", "nccl"] + args + ["--queries", "200", "--steps", "3", "--warmup", "1", "--reps", "2",
+    line = _run_bench(["--full", "--backend", "nccl"] + args + ["--queries", "200", "--steps", "3", "--warmup", "1", "--reps", "2",
                                                       "--check", "8", "--no-cpu-baseline"])
     assert line["n_gpus"] == 2 and line["parity_checked_queries"] == 8 and line["value"] > 0
     assert line["scaling"] == ("weak" if mode == "query" else "strong")
@@ -638,7 +656,7 @@ def test_bench_survives_an_unusable_rccl(gpu, built):
     """The driver's N > 1 command line with the default backend where RCCL cannot work (two ranks on ONE device:
     ncclInvalidUsage): bench.py proves the collective layer with one all-reduce, falls back to gloo with host staging
     and says so on its line.  (With two devices visible RCCL works and the line says that.)"""
-    line = _run_bench(["--data", "pipeline", "--codes", "150000", "--queries", "100", "--steps", "3", "--warmup", "1", "--reps", "2",
+    line = _run_bench(["--full", "--data", "pipeline", "--codes", "150000", "--queries", "100", "--steps", "3", "--warmup", "1", "--reps", "2",
                        "--check", "4", "--no-cpu-baseline", "--no-replicas"], timeout=600, env={"DPQ_BENCH_SHARE_GPUS": "1"})
     import torch
     note = line["config"]["collectives"]
