@@ -102,6 +102,9 @@ SYMBOLS = [
     ("dpq_query_batch_host_async", ctypes.c_int, [_VP, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP]),
     ("dpq_pin_host", ctypes.c_int, [_VP, c_i64]),
     ("dpq_unpin_host", ctypes.c_int, [_VP]),
+    ("dpq_range_search", ctypes.c_int, [_VP, _VP, ctypes.c_int, _VP, P(_VP)]),
+    ("dpq_range_result_get", ctypes.c_int, [_VP, P(c_i32), P(_VP), P(_VP), P(_VP)]),
+    ("dpq_range_result_free", None, [_VP]),
     ("dpq_profile_enable", ctypes.c_int, [_VP, ctypes.c_int]),
     ("dpq_profile_reset", ctypes.c_int, [_VP]),
     ("dpq_profile_read", ctypes.c_int, [_VP, P(Profile)]),
@@ -111,6 +114,7 @@ SYMBOLS = [
     ("dpq_debug_boot_stamps", ctypes.c_int, [_VP, ctypes.c_int, P(ctypes.c_double)]),
     ("dpq_debug_select_time", ctypes.c_int, [_VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, P(ctypes.c_float)]),
     ("dpq_debug_strand1_stamps", ctypes.c_int, [_VP, _VP, ctypes.c_int]),
+    ("dpq_debug_range_keys", ctypes.c_int, [_VP, P(c_i64)]),
 ]
 
 _lib = None

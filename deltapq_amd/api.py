@@ -305,6 +305,32 @@ class DeltaPQIndex:
               "dpq_query_batch")
         return ids, dists
 
+    def range_search(self, queries, radius):
+        """Every code within `radius` of each query (dpq_range_search): d < radius, strictly.  `radius` is a scalar or one
+        value per query.  Returns (lims int64 [nq + 1], ids int32 [lims[-1]], dists float32 [lims[-1]]); query i owns
+        entries lims[i]:lims[i + 1], ascending by (distance, id)."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        nq = q.shape[0]
+        r = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, dtype=np.float32), (nq,)))
+        res = ctypes.c_void_p()
+        check(self._lib.dpq_range_search(self._h, _np_ptr(q), nq, _np_ptr(r), res), "dpq_range_search")
+        try:
+            n = _lib.c_i32()
+            pl, pi, pd = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+            check(self._lib.dpq_range_result_get(res, n, pl, pi, pd), "dpq_range_result_get")
+            lims = np.ctypeslib.as_array(ctypes.cast(pl, ctypes.POINTER(_lib.c_i64)), (n.value + 1,)).copy()
+            total = int(lims[-1])
+            ids = np.empty(total, dtype=np.int32)
+            dists = np.empty(total, dtype=np.float32)
+            if total:
+                ctypes.memmove(ids.ctypes.data, pi.value, total * 4)
+                ctypes.memmove(dists.ctypes.data, pd.value, total * 4)
+            return lims, ids, dists
+        finally:
+            self._lib.dpq_range_result_free(res)
+
     def query_batch_host_async(self, queries, top_k, ids, dists):
         """dpq_query_batch_host_async: host arrays in and out, enqueued only -- up to four batches in flight, queries up and
         results down beside the kernels.  `queries` (float32 [nq][D], C-contiguous), `ids` (int32 [nq][k]) and `dists`

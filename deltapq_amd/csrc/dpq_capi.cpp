@@ -11,6 +11,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <numeric>
 #include <stdexcept>
@@ -117,6 +118,14 @@ struct dpq_tree {
     dpq::Tree tree;
 };
 
+// dpq_range_search's answer: CSR lists in host memory, owned by the library until dpq_range_result_free.
+struct dpq_range_result {
+    int32_t nq = 0;
+    std::vector<int64_t> lims;  // [nq + 1]
+    std::vector<int32_t> ids;
+    std::vector<float> dists;
+};
+
 // Plan and tiling knobs of a handle: dpq_open_opts' fields with the defaults filled in (resolve_tuning).
 struct Tuning {
     // batches up to this size take stream_kernel (1, 2 or 4 queries per pass).  Measured at 125 M codes (ms per call,
@@ -134,6 +143,23 @@ struct Tuning {
          force_strands = false;
     bool strand1 = true;  // one query per pass takes strand1_kernel  [DPQ_OPT_NO_STRAND1, DPQ_STRAND1=0: strand_kernel<1>]
     int s1_debug = 0;     // developer experiments of strand1_kernel  [DPQ_S1_DEBUG]
+};
+
+// The device buffers of dpq_range_search beside the lanes' workspaces (which it uses for its tables only).  The slot
+// arrays hold one sub-batch; the candidate and output buffers grow to what a call needs.
+struct RangeWs {
+    DevBuf<int32_t> slot_query;    // [kMaxBatchQueries] slot -> query of the sub-batch
+    DevBuf<uint64_t> thr_key;      // [kMaxBatchQueries]
+    DevBuf<int64_t> out_off;       // [kMaxBatchQueries] where a slot's list goes in the output chunk
+    DevBuf<uint32_t> max_count;    // [kMaxBatchQueries]
+    DevBuf<int64_t> lims;          // [kMaxBatchQueries + 1]
+    DevBuf<uint32_t> cand_count;   // [kMaxBatchQueries][kRegionStride]
+    DevBuf<uint64_t> cand_key;     // [slots][splits * region_cap]
+    DevBuf<int32_t> out_ids;
+    DevBuf<float> out_dists;
+    DevBuf<uint64_t> scratch;      // [2 * out] HBM sort of lists beyond the emit kernel's LDS
+    size_t key_n = 0, out_n = 0, scratch_n = 0;
+    int64_t last_max_keys = 0;     // candidate keys the largest scan launch of the last call laid out (dpq_debug_range_keys)
 };
 
 // The device buffers a batch works in (one per pipeline lane), sized for `slots` padded queries and `cap` candidates each.
@@ -240,6 +266,7 @@ struct dpq_index {
     // cascade plan: visiting order of the segments, level bounds, decoded level 0
     int plan_top_k = -1, plan_cap = -1, plan_coarse = -1;
     std::vector<int> level_off, level_cnt;
+    RangeWs range;                   // dpq_range_search
     DevBuf<uint32_t> d_order;
     DevBuf<uint32_t> d_l0_id, d_l0_code;
     int l0_segments = 0;
@@ -381,6 +408,17 @@ std::vector<uint32_t> golden_order(int64_t n) {
     return order;
 }
 
+// x->d_order: the segments' low-discrepancy visiting order (the cascade's levels are slices of it)
+int ensure_order(dpq_index* x) {
+    const int64_t nseg = x->img.n_segments;
+    if (x->d_order || nseg <= 0) return DPQ_OK;
+    const std::vector<uint32_t> order = golden_order(nseg);
+    int rc = x->d_order.alloc((size_t)nseg);
+    if (rc) return rc;
+    DPQ_HIP(hipMemcpy(x->d_order, order.data(), (size_t)nseg * sizeof(uint32_t), hipMemcpyHostToDevice));
+    return DPQ_OK;
+}
+
 int auto_cap(int top_k) { return std::max(4096, 32 * top_k); }
 
 // Progressive cascade plan.  Segments are visited in a low-discrepancy order
@@ -465,12 +503,8 @@ int ensure_plan(dpq_index* x, int top_k, int cap, int shape) {
         x->level_cnt.push_back((int)(bnd - prev));
         prev = bnd;
     }
-    if (!x->d_order && nseg > 0) {
-        const std::vector<uint32_t> order = golden_order(nseg);
-        int rc = x->d_order.alloc((size_t)nseg);
-        if (rc) return rc;
-        DPQ_HIP(hipMemcpy(x->d_order, order.data(), (size_t)nseg * sizeof(uint32_t), hipMemcpyHostToDevice));
-    }
+    int rc0 = ensure_order(x);
+    if (rc0) return rc0;
     if (!x->boot && nseg > 0 && x->l0_segments != (int)s0) {
         x->d_l0_code.reset();
         int rc = x->d_l0_id.alloc((size_t)(s0 * S));
@@ -1045,6 +1079,308 @@ int run_batch(dpq_index* x, const float* d_queries, int nq, int top_k, int32_t* 
     }
     if (flag_slot > 0) return DPQ_OK;  // asynchronous batch: dpq_finish checks the word
     return rerun_overflowed(x, b, sa, se, stream);
+}
+
+// ---- range search (dpq_range_search) ------------------------------------------------------------------------------
+// One filter level over every segment at the caller's radius: no bootstrap, no tightening, no select.  The scan's
+// region counts are exact past region_cap, so range_count_kernel knows every list's length after the one scan; the
+// lists that did not fit their regions are scanned again with regions as large as their fullest one (segments go to
+// the scan's workgroups by list position, so the counts come out the same), and range_emit_kernel sorts each list
+// into the CSR output.  DESIGN.md 5.7.
+constexpr int64_t kRangeChunkKeys = (int64_t)1 << 26;  // keys (or results) a launch's buffers may hold: 512 MB of keys
+
+// The threshold key of radius r: the scan keeps key <= thr, so d < r is (dist bits << 32 | pos) <= (bits(r) << 32) - 1.
+// false: the list is empty (r <= 0).  +inf keeps every code.
+bool range_thr_key(float r, uint64_t* key) {
+    if (!(r > 0.0f)) return false;
+    if (std::isinf(r)) {
+        *key = ~0ull;
+        return true;
+    }
+    uint32_t bits;
+    std::memcpy(&bits, &r, sizeof bits);
+    *key = ((uint64_t)bits << 32) - 1ull;
+    return true;
+}
+
+template <class T>
+int grow(DevBuf<T>& buf, size_t* have, size_t want) {
+    if (want <= *have && buf) return DPQ_OK;
+    *have = 0;
+    int rc = buf.alloc(want);
+    if (!rc) *have = want;
+    return rc;
+}
+
+// The filter scan of one range launch: the slots' tables from their thresholds, then every segment -- in tiles of the
+// plain-code scratch where one tile does not hold the shard (as filter_level does).
+int range_scan(dpq_index* x, const Batch& b, dpq::ScanArgs sa, int n_groups, int splits, hipStream_t stream) {
+    const Workspace& w = x->ws();
+    DPQ_HIP(hipMemsetAsync(sa.cand_count, 0, sizeof(uint32_t) * (size_t)n_groups * dpq::queries_per_group(x->M) *
+                                                 dpq::kRegionStride, stream));
+    if (sa.n_seg_pass <= 0) return DPQ_OK;
+    {
+        Timer t(x, stream, 3);
+        DPQ_HIP(dpq::launch_quantise(sa, n_groups, stream));
+    }
+    if (b.scratch && !b.one_tile) {
+        for (int t0 = 0; t0 < sa.n_seg_pass; t0 += (int)b.tile_segs) {
+            const int cnt = std::min<int>((int)b.tile_segs, sa.n_seg_pass - t0);
+            {
+                Timer t(x, stream, 4);
+                DPQ_HIP(dpq::launch_decode_list(x->img, sa.seg_list + t0, cnt, x->d_relabel,
+                                                reinterpret_cast<uint32_t*>(w.d_batch_raw.get()), stream));
+            }
+            dpq::ScanArgs tile = sa;
+            tile.img.raw = w.d_batch_raw;
+            tile.raw_by_pos = 1;
+            tile.append = t0 > 0 ? 1 : 0;
+            tile.seg_list = sa.seg_list + t0;
+            tile.n_seg_pass = cnt;
+            Timer t(x, stream, 1);
+            DPQ_HIP(dpq::launch_scan(tile, n_groups, splits, stream));
+            if (x->prof) x->prof_acc.scan_launches++;
+        }
+    } else {
+        Timer t(x, stream, 1);
+        DPQ_HIP(dpq::launch_scan(sa, n_groups, splits, stream));
+        if (x->prof) x->prof_acc.scan_launches++;
+    }
+    return DPQ_OK;
+}
+
+// Writes the lists of the launch's slots `emit` (their queries in ascending order) from the candidate buffers of `ea`
+// into res at res_base + lims[query]: in chunks of at most kRangeChunkKeys results (a longer list is a chunk of its own).
+int range_emit(dpq_index* x, dpq::RangeEmitArgs ea, int n_slots, const std::vector<int>& emit,
+               const std::vector<int32_t>& slot_query, const std::vector<int64_t>& lims, int64_t res_base,
+               dpq_range_result* res, hipStream_t stream) {
+    RangeWs& R = x->range;
+    std::vector<int64_t> off((size_t)n_slots);
+    for (size_t i = 0; i < emit.size();) {
+        std::fill(off.begin(), off.end(), -1);
+        int64_t span = 0, max_n = 0;
+        bool contiguous = true;
+        size_t j = i;
+        for (; j < emit.size(); ++j) {
+            const int q = slot_query[(size_t)emit[j]];
+            const int64_t n = lims[(size_t)q + 1] - lims[(size_t)q];
+            if (j > i && span + n > kRangeChunkKeys) break;
+            if (j > i && lims[(size_t)slot_query[(size_t)emit[j - 1]] + 1] != lims[(size_t)q]) contiguous = false;
+            off[(size_t)emit[j]] = span;
+            span += n;
+            max_n = std::max(max_n, n);
+        }
+        if (span > 0) {
+            int rc;
+            if ((size_t)span > R.out_n) {
+                R.out_n = 0;
+                if ((rc = R.out_ids.alloc((size_t)span)) || (rc = R.out_dists.alloc((size_t)span))) return rc;
+                R.out_n = (size_t)span;
+            }
+            if (max_n > dpq::kRangeLdsKeys && (rc = grow(R.scratch, &R.scratch_n, 2 * (size_t)span))) return rc;
+            DPQ_HIP(hipMemcpyAsync(R.out_off, off.data(), sizeof(int64_t) * n_slots, hipMemcpyHostToDevice, stream));
+            ea.out_off = R.out_off;
+            ea.out_ids = R.out_ids;
+            ea.out_dists = R.out_dists;
+            ea.out_n = span;
+            ea.scratch = max_n > dpq::kRangeLdsKeys ? R.scratch.get() : nullptr;
+            int lk = 2;
+            while (lk < std::min<int64_t>(max_n, dpq::kRangeLdsKeys)) lk <<= 1;
+            ea.lds_keys = lk;
+            {
+                Timer t(x, stream, 2);
+                DPQ_HIP(dpq::launch_range_emit(ea, n_slots, stream));
+            }
+            const int64_t first = res_base + lims[(size_t)slot_query[(size_t)emit[i]]];
+            if (contiguous) {
+                DPQ_HIP(hipMemcpyAsync(res->ids.data() + first, R.out_ids, sizeof(int32_t) * span, hipMemcpyDeviceToHost, stream));
+                DPQ_HIP(hipMemcpyAsync(res->dists.data() + first, R.out_dists, sizeof(float) * span, hipMemcpyDeviceToHost,
+                                       stream));
+                DPQ_HIP(hipStreamSynchronize(stream));
+            } else {
+                std::vector<int32_t> h_ids((size_t)span);
+                std::vector<float> h_d((size_t)span);
+                DPQ_HIP(hipMemcpyAsync(h_ids.data(), R.out_ids, sizeof(int32_t) * span, hipMemcpyDeviceToHost, stream));
+                DPQ_HIP(hipMemcpyAsync(h_d.data(), R.out_dists, sizeof(float) * span, hipMemcpyDeviceToHost, stream));
+                DPQ_HIP(hipStreamSynchronize(stream));
+                for (size_t k = i; k < j; ++k) {
+                    const int q = slot_query[(size_t)emit[k]];
+                    const int64_t o = off[(size_t)emit[k]], n = lims[(size_t)q + 1] - lims[(size_t)q];
+                    std::copy(h_ids.begin() + o, h_ids.begin() + o + n, res->ids.begin() + res_base + lims[(size_t)q]);
+                    std::copy(h_d.begin() + o, h_d.begin() + o + n, res->dists.begin() + res_base + lims[(size_t)q]);
+                }
+            }
+        }
+        i = j;
+    }
+    return DPQ_OK;
+}
+
+// One sub-batch (nq <= kMaxBatchQueries) of dpq_range_search: d_queries on the device, radii on the host; appends its
+// lists to res (res->lims[base .. base + nq] are filled, base = the number of queries before it).
+int range_batch(dpq_index* x, const float* d_queries, int nq, const float* radii, int base, dpq_range_result* res,
+                hipStream_t stream) {
+    RangeWs& R = x->range;
+    const int QG = dpq::queries_per_group(x->M);
+    // the plain-code scratch as a top-k batch of this size would use it (tiles included); top_k only sizes what is unused here
+    Batch b = batch_mode(x, nq, 1);
+    std::vector<int32_t> slot_query;
+    std::vector<uint64_t> thr;
+    for (int q = 0; q < nq; ++q) {
+        uint64_t key;
+        if (!range_thr_key(radii[q], &key)) continue;
+        slot_query.push_back(q);
+        thr.push_back(key);
+    }
+    const int n_active = (int)slot_query.size();
+    const int slots = (n_active + QG - 1) / QG * QG, n_groups = slots / QG;
+    slot_query.resize((size_t)slots, -1);
+    thr.resize((size_t)slots, 0ull);
+    const int64_t res_base = res->lims[(size_t)base];
+    std::vector<int64_t> lims((size_t)nq + 1, 0);
+    if (n_active == 0) {
+        for (int q = 0; q <= nq; ++q) res->lims[(size_t)base + q] = res_base;
+        return DPQ_OK;
+    }
+    int rc;
+    if (!R.slot_query) {
+        if ((rc = R.slot_query.alloc(kMaxBatchQueries))) return rc;
+        if ((rc = R.thr_key.alloc(kMaxBatchQueries))) return rc;
+        if ((rc = R.out_off.alloc(kMaxBatchQueries))) return rc;
+        if ((rc = R.max_count.alloc(kMaxBatchQueries))) return rc;
+        if ((rc = R.lims.alloc(kMaxBatchQueries + 1))) return rc;
+        if ((rc = R.cand_count.alloc((size_t)kMaxBatchQueries * dpq::kRegionStride))) return rc;
+    }
+    // the tables (and the plain-code scratch) in the active lane's workspace, grown if need be; its plan stays as it is
+    if ((rc = ensure_workspace(x, b.nqp, std::max(1, x->ws().cap)))) return rc;
+    if (b.scratch && (rc = ensure_batch_raw(x))) return rc;
+    const bool tiled = b.scratch && !b.one_tile;
+    if (tiled && (rc = ensure_order(x))) return rc;
+    if ((rc = build_tables(x, b, d_queries, stream))) return rc;
+
+    // regions: splits_for's workgroups per query group, auto-sized as a top-k level's (or dpq_open_opts.cand_capacity)
+    const int nseg = x->img.n_segments;
+    const int splits = splits_for(nseg, n_groups);
+    const int region_cap = x->cap_auto ? std::max(256, 16384 / splits) : std::max(1, x->cap / splits);
+    const Workspace& w = x->ws();
+    dpq::ScanArgs sa{};
+    sa.img = x->img;
+    if (b.one_tile) sa.img.raw = w.d_batch_raw;
+    sa.fp32_accum = x->plain ? 1 : 0;
+    sa.lut32 = b.labelled ? w.d_lut32r.get() : w.d_lut32.get();
+    sa.lut_min = w.d_lut_min;
+    sa.thr_key = R.thr_key;
+    sa.slot_query = R.slot_query;
+    sa.n_queries = slots;
+    sa.seg_list = tiled ? x->d_order.get() : nullptr;
+    sa.n_seg_pass = nseg;
+    sa.cand_count = R.cand_count;
+    sa.region_off = 0;
+    sa.counters = x->prof && !x->prof_scan_only ? x->d_counters.get() : nullptr;
+    sa.qtab = w.d_qtab;
+    sa.tight_hist = nullptr;  // the radius is the final threshold
+
+    // n_live queries in slots [0, n_live), padded with unused slots to whole query groups.  Only the live slots get
+    // candidate regions: an unused slot's filter tables reject every node (quantise_kernel), so the scan never writes
+    // its region, and range_emit_kernel leaves it alone (out_off -1).
+    auto scan_and_count = [&](int n_live, int rcap, int64_t* lims_out, std::vector<uint32_t>* max_count) -> int {
+        const int n_slots = (n_live + QG - 1) / QG * QG, ng = n_slots / QG;
+        const int64_t stride = (int64_t)splits * rcap;
+        int rc2 = grow(R.cand_key, &R.key_n, (size_t)n_live * stride);
+        if (rc2) return rc2;
+        R.last_max_keys = std::max(R.last_max_keys, (int64_t)n_live * stride);
+        DPQ_HIP(hipMemcpyAsync(R.slot_query, slot_query.data(), sizeof(int32_t) * n_slots, hipMemcpyHostToDevice, stream));
+        DPQ_HIP(hipMemcpyAsync(R.thr_key, thr.data(), sizeof(uint64_t) * n_slots, hipMemcpyHostToDevice, stream));
+        sa.cand_key = R.cand_key;
+        sa.cand_stride = stride;
+        sa.region_cap = rcap;
+        if ((rc2 = range_scan(x, b, sa, ng, splits, stream))) return rc2;
+        dpq::RangeCountArgs ca{};
+        ca.slot_query = R.slot_query;
+        ca.cand_count = R.cand_count;
+        ca.n_slots = n_slots;
+        ca.n_regions = splits;
+        ca.n_queries = nq;
+        ca.max_count = R.max_count;
+        ca.lims = R.lims;
+        {
+            Timer t(x, stream, 2);
+            DPQ_HIP(dpq::launch_range_count(ca, stream));
+        }
+        max_count->resize((size_t)n_slots);
+        DPQ_HIP(hipMemcpyAsync(lims_out, R.lims, sizeof(int64_t) * (nq + 1), hipMemcpyDeviceToHost, stream));
+        DPQ_HIP(hipMemcpyAsync(max_count->data(), R.max_count, sizeof(uint32_t) * n_slots, hipMemcpyDeviceToHost, stream));
+        DPQ_HIP(hipStreamSynchronize(stream));  // the sizes of the lists
+        return DPQ_OK;
+    };
+    std::vector<uint32_t> max_count;
+    if ((rc = scan_and_count(n_active, region_cap, lims.data(), &max_count))) return rc;
+    for (int q = 0; q <= nq; ++q) res->lims[(size_t)base + q] = res_base + lims[(size_t)q];
+    const int64_t total = res_base + lims[(size_t)nq];
+    res->ids.resize((size_t)total);
+    res->dists.resize((size_t)total);
+
+    dpq::RangeEmitArgs ea{};
+    ea.cand_count = R.cand_count;
+    ea.cand_key = R.cand_key;
+    ea.cand_stride = (int64_t)splits * region_cap;
+    ea.region_off = 0;
+    ea.region_cap = region_cap;
+    ea.n_regions = splits;
+    ea.n_codes_total = x->plain ? -1 : x->img.n_codes_total;
+    std::vector<int> emit, over;
+    for (int s = 0; s < n_active; ++s) (max_count[(size_t)s] > (uint32_t)region_cap ? over : emit).push_back(s);
+    if ((rc = range_emit(x, ea, slots, emit, slot_query, lims, res_base, res, stream))) return rc;
+    if (over.empty()) return DPQ_OK;
+
+    // Lists that overflowed their regions: scanned again, as many at a time as kRangeChunkKeys of regions hold (at least
+    // one), with regions as large as the fullest of them: n2 x splits x that keys for n2 queries.  splits x the fullest
+    // region is about the list's length where its keys spread over the shard (a radius that admits most of it), and
+    // at most splits times it where they all sit in one workgroup's segments.
+    const std::vector<int32_t> q_of(slot_query.begin(), slot_query.begin() + n_active);
+    const std::vector<uint64_t> k_of(thr.begin(), thr.begin() + n_active);
+    const std::vector<uint32_t> need(max_count.begin(), max_count.begin() + n_active);
+    for (size_t i = 0; i < over.size();) {
+        size_t j = i;
+        uint32_t rcap = 0;
+        for (; j < over.size(); ++j) {
+            const uint32_t r2 = std::max(rcap, need[(size_t)over[j]]);
+            if (j > i && (int64_t)(j - i + 1) * splits * (int64_t)r2 > kRangeChunkKeys) break;
+            rcap = r2;
+        }
+        if ((int64_t)rcap * splits > INT32_MAX) return fail(DPQ_ERR_NOMEM, "range search: candidate regions too large");
+        const int n2 = (int)(j - i), slots2 = (n2 + QG - 1) / QG * QG;
+        std::fill(slot_query.begin(), slot_query.end(), -1);
+        for (int k = 0; k < n2; ++k) {
+            slot_query[(size_t)k] = q_of[(size_t)over[i + k]];
+            thr[(size_t)k] = k_of[(size_t)over[i + k]];
+        }
+        std::vector<int64_t> lims2((size_t)nq + 1);
+        if ((rc = scan_and_count(n2, (int)rcap, lims2.data(), &max_count))) return rc;
+        for (int k = 0; k < n2; ++k) {
+            const int q = slot_query[(size_t)k];
+            if (max_count[(size_t)k] > rcap || lims2[(size_t)q + 1] - lims2[(size_t)q] != lims[(size_t)q + 1] - lims[(size_t)q])
+                return fail(DPQ_ERR_STATE, "range search: the rerun of an overflowed query found a different count");
+        }
+        ea.cand_key = R.cand_key;
+        ea.cand_stride = (int64_t)splits * rcap;
+        ea.region_cap = (int)rcap;
+        std::vector<int> emit2((size_t)n2);
+        std::iota(emit2.begin(), emit2.end(), 0);
+        if ((rc = range_emit(x, ea, slots2, emit2, slot_query, lims, res_base, res, stream))) return rc;
+        if (x->prof) x->prof_acc.overflow_reruns += n2;
+        i = j;
+    }
+    return DPQ_OK;
+}
+
+// What a range call leaves allocated: the candidate and output buffers of an ordinary call stay for the next one.
+void range_trim(dpq_index* x) {
+    RangeWs& R = x->range;
+    if (R.key_n > ((size_t)40 << 20)) R.cand_key.reset(), R.key_n = 0;  // (a full sub-batch's regions: 32 M keys)
+    if (R.out_n > ((size_t)16 << 20)) R.out_ids.reset(), R.out_dists.reset(), R.out_n = 0;
+    R.scratch.reset();
+    R.scratch_n = 0;
 }
 
 // The full-index filter scan of the dpq_debug_scan_* hooks: nq slots of the active workspace with the thresholds and
@@ -2052,6 +2388,59 @@ int dpq_query_batch(dpq_index* x, const float* queries, int nq, int top_k, int32
     });
 }
 
+int dpq_range_search(dpq_index* x, const float* queries, int nq, const float* radii, dpq_range_result** out) {
+    return guarded([&]() -> int {
+    if (!out) return fail(DPQ_ERR_ARG, "out is NULL");
+    *out = nullptr;
+    if (!x || nq < 0 || (nq > 0 && (!queries || !radii))) return fail(DPQ_ERR_ARG, "NULL argument or nq < 0");
+    if (!x->d_codebook) return fail(DPQ_ERR_STATE, "dpq_set_codebook has not been called");
+    for (int q = 0; q < nq; ++q)
+        if (std::isnan(radii[q])) return fail(DPQ_ERR_ARG, "radius of query " + std::to_string(q) + " is NaN");
+    if (!x->pending.empty()) {  // keep the order of the batches on this index
+        int rc = dpq_finish(x);
+        if (rc) return rc;
+    }
+    x->range.last_max_keys = 0;
+    std::unique_ptr<dpq_range_result> res(new dpq_range_result());
+    res->nq = nq;
+    res->lims.assign((size_t)nq + 1, 0);
+    if (nq > 0) {
+        DPQ_HIP(hipSetDevice(x->device));
+        const size_t qf = (size_t)nq * x->M * x->Ds;
+        if (qf > x->q_stage_floats) {
+            x->q_stage_floats = 0;
+            int rc = x->d_q_stage.alloc(qf);
+            if (rc) return rc;
+            x->q_stage_floats = qf;
+        }
+        DPQ_HIP(hipMemcpy(x->d_q_stage, queries, qf * sizeof(float), hipMemcpyHostToDevice));
+        const int D = x->M * x->Ds;
+        int rc = DPQ_OK;
+        for (int base = 0; base < nq && !rc; base += kMaxBatchQueries) {
+            const int n = std::min(kMaxBatchQueries, nq - base);
+            rc = range_batch(x, x->d_q_stage + (size_t)base * D, n, radii + base, base, res.get(), nullptr);
+        }
+        range_trim(x);
+        if (rc) return rc;
+        if (x->prof) x->prof_acc.queries += nq;
+    }
+    *out = res.release();
+    return DPQ_OK;
+    });
+}
+
+int dpq_range_result_get(const dpq_range_result* r, int32_t* nq, const int64_t** lims, const int32_t** ids,
+                         const float** dists) {
+    if (!r || !nq || !lims || !ids || !dists) return fail(DPQ_ERR_ARG, "NULL argument");
+    *nq = r->nq;
+    *lims = r->lims.data();
+    *ids = r->ids.data();
+    *dists = r->dists.data();
+    return DPQ_OK;
+}
+
+void dpq_range_result_free(dpq_range_result* r) { delete r; }
+
 // The reference's interface is host vectors in, host results out (h:2805-2810), one call per query (main:328-339).  Pipelined:
 // the queries of batch i + 1 go up and the results of batch i - 1 come down (two copy streams) beside batch i's kernels
 // (the two lanes of dpq_query_batch_device_async); dpq_finish settles everything and answers again, synchronously, any
@@ -2414,6 +2803,13 @@ int dpq_debug_boot_stamps(dpq_index* x, int nq, double* out) {
 }
 
 // Developer hook: time the level-0 select (shared, query-independent candidate list).
+int dpq_debug_range_keys(dpq_index* x, int64_t* max_keys) {
+    DPQ_DEV_ONLY();
+    if (!x || !max_keys) return fail(DPQ_ERR_ARG, "NULL argument");
+    *max_keys = x->range.last_max_keys;
+    return DPQ_OK;
+}
+
 int dpq_debug_select_time(dpq_index* x, int nq, int top_k, int flags, int reps, float* ms_out) {
     return guarded([&]() -> int {
     DPQ_DEV_ONLY();

@@ -142,6 +142,34 @@ struct BootArgs {
     int32_t variant;               // bootstrap_kernel's V: 1 = round 4's kernel (one-pass threshold), 0 = round 3's, kept for A/B
 };
 
+// Range search (dpq_range_search): the filter scan at the caller's radii, then these two over its candidate regions.
+constexpr int kRangeMaxQueries = 2048;   // queries of one sub-batch (range_count_kernel holds their totals in LDS)
+constexpr int kRangeCountThreads = 1024;
+constexpr int kRangeEmitThreads = 256;
+constexpr int kRangeLdsKeys = 8192;      // longest list range_emit_kernel sorts in LDS (64 KB); longer ones: HBM scratch
+
+struct RangeCountArgs {
+    const int32_t* slot_query;   // [n_slots] slot -> query of the sub-batch, -1 = unused
+    const uint32_t* cand_count;  // [n_slots][kRegionStride]: region 1 + r holds the exact count of region r's keys
+    int32_t n_slots, n_regions, n_queries;
+    uint32_t* max_count;         // out [n_slots]: largest region count of the slot
+    int64_t* lims;               // out [n_queries + 1]: exclusive prefix of the per-query totals
+};
+
+struct RangeEmitArgs {
+    const int64_t* out_off;      // [slots] where the slot's list starts in out_ids / out_dists; -1 = nothing to write
+    const uint32_t* cand_count;  // as in ScanArgs (region r's count at [slot][1 + r])
+    const uint64_t* cand_key;
+    int64_t cand_stride;
+    int32_t region_off, region_cap, n_regions;
+    int32_t lds_keys;            // power of two <= kRangeLdsKeys: lists up to this long are sorted in LDS
+    int32_t* out_ids;            // [out_n]
+    float* out_dists;
+    int64_t out_n;
+    uint64_t* scratch;           // [2 * out_n] HBM sort of the longer lists (NULL: there are none)
+    int64_t n_codes_total;       // even-N id rule (report_id); odd (-1) for a plain index
+};
+
 // Builds the exact tables of queries [0, nq) and clears the candidate counters / overflow flags of
 // slots [0, n_slots) (either may be NULL).
 hipError_t launch_lut_build(const float* d_codebook, const float* d_queries, int nq, int n_slots, int M, int K, int Ds,
@@ -170,6 +198,9 @@ size_t qtab_bytes_per_group(int M);
 int scan_stamp_count();
 hipError_t launch_select(const SelectArgs& a, int M, int n_slots, hipStream_t stream);
 hipError_t launch_bootstrap(const BootArgs& a, int M, int n_slots, hipStream_t stream);
+// range_count_kernel: one block over a sub-batch's slots; range_emit_kernel: one block per slot
+hipError_t launch_range_count(const RangeCountArgs& a, hipStream_t stream);
+hipError_t launch_range_emit(const RangeEmitArgs& a, int n_slots, hipStream_t stream);
 // row_stride: elements between consecutive (list, query) rows of d_ids / d_dists (top_k, or 2 * top_k for the packed tensor)
 hipError_t launch_merge(const int32_t* d_ids, const float* d_dists, int n_lists, int nq, int top_k, int row_stride,
                         int32_t* d_out_ids, float* d_out_dists, hipStream_t stream);

@@ -46,6 +46,9 @@
 //                           (distance, id) key = next threshold, winners carried to the next
 //                           level; on the last level the sorted top-k.
 //   merge_kernel            8e: merge of per-shard partial top-k lists.
+//   range_count_kernel      range search: per-query totals of a scan's candidate regions and their prefix (CSR lims).
+//   range_emit_kernel       range search: a query's keys from its regions, sorted (LDS bitonic network, or a block-wide
+//                           radix sort in HBM for long lists), written as ids / distances at its CSR offset.
 //
 // Top-k strategy (replaces the sequential size-k max-heap, h:2851-2853,
 // 2909-2914): thresholds that are valid upper bounds of the final k-th key.
@@ -3254,6 +3257,174 @@ __global__ __launch_bounds__(kSelectThreads) void merge_kernel(const int32_t* __
 }
 
 // ---------------------------------------------------------------------------
+// Range search (dpq_range_search): one filter scan at the caller's radius leaves every key with d < r of a slot in the
+// regions of its candidate buffer (region counts exact, also past region_cap).  range_count_kernel turns the counts
+// into per-query totals and the CSR offsets; range_emit_kernel turns a slot's regions into its sorted list.
+// ---------------------------------------------------------------------------
+// One block per sub-batch (n_queries <= kRangeMaxQueries).  Per slot: total = sum of its region counts, max_count = the
+// largest (the host compares it with region_cap: a larger one means keys were dropped and the slot is scanned again with
+// regions that large).  lims[0 .. n_queries] = exclusive prefix of the per-query totals (a query without a slot: 0).
+__global__ __launch_bounds__(kRangeCountThreads) void range_count_kernel(const RangeCountArgs a) {
+    __shared__ int64_t s_tot[kRangeMaxQueries];
+    __shared__ int64_t s_part[2][kRangeCountThreads];
+    const int tid = threadIdx.x;
+    for (int q = tid; q < a.n_queries; q += kRangeCountThreads) s_tot[q] = 0;
+    __syncthreads();
+    for (int slot = tid; slot < a.n_slots; slot += kRangeCountThreads) {
+        const int q = a.slot_query[slot];
+        const uint32_t* cnt = a.cand_count + (size_t)slot * kRegionStride + 1;
+        int64_t tot = 0;
+        uint32_t mx = 0;
+        if (q >= 0)
+            for (int r0 = 0; r0 < a.n_regions; r0 += 8) {
+                uint32_t c[8];  // eight loads in flight before the first is summed (a slot has 8 regions at 16+ groups)
+#pragma unroll
+                for (int u = 0; u < 8; ++u) c[u] = r0 + u < a.n_regions ? cnt[r0 + u] : 0u;
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    tot += c[u];
+                    mx = max(mx, c[u]);
+                }
+            }
+        a.max_count[slot] = mx;
+        if (q >= 0 && q < a.n_queries) s_tot[q] = tot;
+    }
+    __syncthreads();
+    // each thread sums a contiguous run of queries, a Hillis-Steele scan over the runs, then the run's own prefix
+    const int per = (a.n_queries + kRangeCountThreads - 1) / kRangeCountThreads;
+    const int q0 = min(a.n_queries, tid * per), q1 = min(a.n_queries, q0 + per);
+    int64_t run = 0;
+    for (int q = q0; q < q1; ++q) run += s_tot[q];
+    int buf = 0;
+    s_part[0][tid] = run;
+    __syncthreads();
+    for (int off = 1; off < kRangeCountThreads; off <<= 1) {
+        const int64_t v = s_part[buf][tid] + (tid >= off ? s_part[buf][tid - off] : 0);
+        buf ^= 1;
+        s_part[buf][tid] = v;
+        __syncthreads();
+    }
+    int64_t acc = s_part[buf][tid] - run;  // exclusive prefix of this run
+    for (int q = q0; q < q1; ++q) {
+        a.lims[q] = acc;
+        acc += s_tot[q];
+    }
+    if (tid == kRangeCountThreads - 1) a.lims[a.n_queries] = s_part[buf][tid];
+}
+
+// Key i of a slot's list, regions laid side by side: off[r] = keys in regions before r (off[n_regions] = total).
+__device__ __forceinline__ uint64_t range_key_at(const RangeEmitArgs& a, const uint64_t* cand, const uint32_t* off, int64_t i) {
+    int lo = 0, hi = a.n_regions;  // the last region r with off[r] <= i
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if ((int64_t)off[mid] <= i) lo = mid; else hi = mid;
+    }
+    return cand[(size_t)a.region_off + (size_t)lo * a.region_cap + (size_t)(i - off[lo])];
+}
+
+// One block per slot of the launch: its keys, sorted ascending (distance bits, DFS position), as ids (report_id) and
+// distances at out_off[slot].  Up to lds_keys (<= kRangeLdsKeys) keys: a bitonic network in LDS.  Longer lists (rare: a radius that
+// admits tens of thousands of codes) are sorted in HBM, scratch[2 * out_off .. + 2 n): a stable LSD radix sort by
+// 4-bit digits, block-wide (ranks from wavefront ballots), skipping the digits every key shares.  A slot whose region
+// counts exceed region_cap (dropped keys) or whose list does not fit the output is left alone.
+__global__ __launch_bounds__(kRangeEmitThreads) void range_emit_kernel(const RangeEmitArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    uint64_t* s_key = reinterpret_cast<uint64_t*>(smem);  // [lds_keys]
+    __shared__ uint32_t s_off[kMaxSplits + 1];
+    __shared__ uint32_t s_hist[16], s_base[16];
+    __shared__ uint32_t s_wcnt[kRangeEmitThreads / 64][16];
+    __shared__ int s_bad;
+    const int slot = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t o = a.out_off[slot];
+    if (o < 0 || a.n_regions < 1 || a.n_regions > kMaxSplits) return;
+    const uint32_t* cnt = a.cand_count + (size_t)slot * kRegionStride + 1;
+    if (tid == 0) {
+        uint32_t s = 0;
+        int bad = 0;
+        for (int r = 0; r < a.n_regions; ++r) {
+            s_off[r] = s;
+            s += min(cnt[r], (uint32_t)a.region_cap);
+            bad |= cnt[r] > (uint32_t)a.region_cap;
+        }
+        s_off[a.n_regions] = s;
+        s_bad = bad || o + (int64_t)s > a.out_n;
+    }
+    __syncthreads();
+    if (s_bad) return;
+    const int64_t n = s_off[a.n_regions];
+    if (n == 0) return;
+    const uint64_t* cand = a.cand_key + (size_t)slot * a.cand_stride;
+    int32_t* out_ids = a.out_ids + o;
+    float* out_dists = a.out_dists + o;
+    const uint64_t* sorted = s_key;
+    if (n <= a.lds_keys) {
+        int p = 2;
+        while (p < n) p <<= 1;
+        for (int i = tid; i < p; i += kRangeEmitThreads) s_key[i] = i < n ? range_key_at(a, cand, s_off, i) : ~0ull;
+        __syncthreads();
+        block_bitonic_sort(s_key, p, tid, kRangeEmitThreads);  // (select_kernel's network)
+    } else {
+        if (!a.scratch) return;
+        uint64_t* src = a.scratch + 2 * o;
+        uint64_t* dst = src + n;
+        for (int64_t i = tid; i < n; i += kRangeEmitThreads) src[i] = range_key_at(a, cand, s_off, i);
+        __syncthreads();
+        for (int shift = 0; shift < 64; shift += 4) {
+            __syncthreads();  // (the previous digit's look at s_hist)
+            if (tid < 16) s_hist[tid] = 0;
+            __syncthreads();
+            for (int64_t i = tid; i < n; i += kRangeEmitThreads) atomicAdd(&s_hist[(src[i] >> shift) & 15u], 1u);
+            __syncthreads();
+            bool shared_digit = false;
+            for (int d = 0; d < 16; ++d) shared_digit |= s_hist[d] == (uint32_t)n;
+            if (shared_digit) continue;  // block-uniform: every key has this digit, the order stays
+            if (tid == 0) {
+                uint32_t s = 0;
+                for (int d = 0; d < 16; ++d) {
+                    s_base[d] = s;
+                    s += s_hist[d];
+                }
+            }
+            __syncthreads();
+            for (int64_t t0 = 0; t0 < n; t0 += kRangeEmitThreads) {
+                const int64_t i = t0 + tid;
+                const bool valid = i < n;
+                const uint64_t key = valid ? src[i] : 0ull;
+                const uint32_t dig = valid ? (uint32_t)(key >> shift) & 15u : 16u;
+                uint32_t rank = 0;
+                for (uint32_t d = 0; d < 16; ++d) {
+                    const uint64_t m = __ballot(dig == d);
+                    if (dig == d) rank = mbcnt64(m, 0u);
+                    if (lane == 0) s_wcnt[wave][d] = (uint32_t)__popcll(m);
+                }
+                __syncthreads();
+                if (tid < 16) {  // per digit: where each wavefront's keys of this tile go
+                    uint32_t s = s_base[tid];
+                    for (int w = 0; w < kRangeEmitThreads / 64; ++w) {
+                        const uint32_t c = s_wcnt[w][tid];
+                        s_wcnt[w][tid] = s;
+                        s += c;
+                    }
+                    s_base[tid] = s;
+                }
+                __syncthreads();
+                if (valid) dst[s_wcnt[wave][dig] + rank] = key;
+                __syncthreads();
+            }
+            uint64_t* t = src;
+            src = dst;
+            dst = t;
+        }
+        sorted = src;
+    }
+    for (int64_t i = tid; i < n; i += kRangeEmitThreads) {
+        const uint64_t key = sorted[i];
+        out_ids[i] = report_id((uint32_t)(key & 0xffffffffu), a.n_codes_total);
+        out_dists[i] = __uint_as_float((uint32_t)(key >> 32));
+    }
+}
+
+// ---------------------------------------------------------------------------
 // 8f row 2: PQ encoding, PQTree::EncodePlain (pq_tree.cpp:215-237): per
 // sub-space the nearest codeword in fp32 -- `diff = v - c; dist += diff * diff`
 // (separately rounded multiply and add), strict `<` so the first minimum wins.
@@ -3529,6 +3700,24 @@ hipError_t launch_select(const SelectArgs& a, int M, int n_slots, hipStream_t st
     if (M == 16) return threads >= 1024 ? launch_select_m<16, 1024>(a, n_slots, stream)
                       : threads >= 512 ? launch_select_m<16, 512>(a, n_slots, stream) : launch_select_m<16, 256>(a, n_slots, stream);
     return hipErrorInvalidValue;
+}
+
+hipError_t launch_range_count(const RangeCountArgs& a, hipStream_t stream) {
+    if (a.n_slots <= 0 && a.n_queries <= 0) return hipSuccess;
+    if (a.n_queries > kRangeMaxQueries || a.n_slots > kRangeMaxQueries || a.n_regions > kMaxSplits) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(range_count_kernel, dim3(1), dim3(kRangeCountThreads), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_range_emit(const RangeEmitArgs& a, int n_slots, hipStream_t stream) {
+    if (n_slots <= 0) return hipSuccess;
+    if (a.lds_keys < 2 || a.lds_keys > kRangeLdsKeys || (a.lds_keys & (a.lds_keys - 1)) || a.n_regions > kMaxSplits)
+        return hipErrorInvalidValue;
+    static std::atomic<bool> done[64] = {};
+    hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(&range_emit_kernel), (size_t)kRangeLdsKeys * 8, done);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(range_emit_kernel, dim3((unsigned)n_slots), dim3(kRangeEmitThreads), (size_t)a.lds_keys * 8, stream, a);
+    return hipGetLastError();
 }
 
 hipError_t launch_merge(const int32_t* d_ids, const float* d_dists, int n_lists, int nq, int top_k, int row_stride,

@@ -72,6 +72,31 @@ def gather_and_merge(ids, dists, group=None):
     return torch.from_numpy(mi), torch.from_numpy(md)
 
 
+def merge_range_host(parts):
+    """Combine the range_search results of the shard handles of one index: parts = [(lims, ids, dists), ...] with the
+    same queries.  Per query the parts' lists are concatenated and sorted by (distance, id), the order one handle over
+    the whole index gives.  Returns (lims int64 [nq + 1], ids int32, dists float32)."""
+    parts = list(parts)
+    if not parts:
+        raise ValueError("merge_range_host: no parts")
+    nq = len(parts[0][0]) - 1
+    q_all, i_all, d_all = [], [], []
+    for lims, ids, dists in parts:
+        lims = np.asarray(lims, dtype=np.int64)
+        if len(lims) != nq + 1:
+            raise ValueError("merge_range_host: the parts answer different numbers of queries")
+        q_all.append(np.repeat(np.arange(nq, dtype=np.int64), np.diff(lims)))
+        i_all.append(np.asarray(ids, dtype=np.int32)[:lims[-1]])
+        d_all.append(np.asarray(dists, dtype=np.float32)[:lims[-1]])
+    q = np.concatenate(q_all)
+    ids = np.concatenate(i_all)
+    dists = np.concatenate(d_all)
+    order = np.lexsort((ids, dists.view(np.uint32), q))   # distances are >= 0: their bit patterns sort as the values
+    lims = np.zeros(nq + 1, dtype=np.int64)
+    np.cumsum(np.bincount(q, minlength=nq), out=lims[1:])
+    return lims, ids[order], dists[order]
+
+
 def partial_topk_rows(all_ids, all_dists, k):
     """Helper for tests: the k best (distance, id) rows of arbitrary candidate
     arrays, padded with (-1, +inf) -- the shape a shard's partial list has."""

@@ -320,6 +320,29 @@ int dpq_finish(dpq_index* idx);
 int dpq_query_batch_host_async(dpq_index* idx, const float* queries, int nq, int top_k, int32_t* ids, float* dists);
 int dpq_pin_host(void* ptr, int64_t bytes);
 int dpq_unpin_host(void* ptr);
+/* ---- range search ---------------------------------------------------------
+ * Every code within a radius of each query (FAISS's range_search).  For query q the list holds every code whose
+ * distance d is STRICTLY below radii[q] (d < r, FAISS's L2 convention), d being exactly the distance dpq_query_batch
+ * reports, to the bit (the DTC fp64-sum rule; fp32 accumulation on a dpq_open_plain_* index).  Ids follow the top-k
+ * rules: DFS positions, global on shards and parts, the even-N id of the last node.  Within a list the entries are
+ * ascending by (distance, id).  A radius <= 0 gives an empty list, +inf every code of the handle; a NaN radius is
+ * DPQ_ERR_ARG.  With shard_count > 1 the lists are this shard's part of the answer (dpq_range_search on each shard,
+ * then concatenate per query and sort by (distance, id): deltapq_amd.dist.merge_range_host).
+ * The length of a list depends on the data, so the library owns the answer (host memory) until
+ * dpq_range_result_free.  Synchronous; pending asynchronous batches are finished first.  The plan, workspaces and
+ * results of later top-k calls are not affected.  Device memory: the call grows the active lane's table buffers like
+ * a top-k batch of its size and keeps buffers of its own for the next call, at most 320 MB of candidate keys (a
+ * 2048-query sub-batch's regions take 268 MB at the default cand_capacity) and 128 MB of output lists, until dpq_close; larger
+ * buffers a call needed (long lists, reruns of overflowed lists) are released before it returns. */
+typedef struct dpq_range_result dpq_range_result;
+/* queries[nq][M*Ds], radii[nq]: host memory. */
+int dpq_range_search(dpq_index* idx, const float* queries, int nq, const float* radii, dpq_range_result** out);
+/* Borrowed pointers, valid until dpq_range_result_free: lims[nq + 1] (lims[0] = 0), ids / dists [lims[nq]];
+ * query q owns entries [lims[q], lims[q + 1]). */
+int dpq_range_result_get(const dpq_range_result* r, int32_t* nq, const int64_t** lims, const int32_t** ids,
+                         const float** dists);
+void dpq_range_result_free(dpq_range_result* r);  /* NULL: nothing happens */
+
 /* Merge n_lists partial top-k lists per query (lists[l][nq][top_k]) into the
  * final top_k by (distance, id).  Host version for the single-process
  * multi-GPU CLI, device version for use after an RCCL all-gather. */
@@ -363,6 +386,8 @@ int dpq_debug_scan_stamps(dpq_index* idx, int nq, int splits, unsigned long long
 int dpq_debug_boot_stamps(dpq_index* idx, int nq, double* out);
 /* The level-0 select alone (shards without a bootstrap). */
 int dpq_debug_select_time(dpq_index* idx, int nq, int top_k, int flags, int reps, float* ms_out);
+/* Candidate keys the largest scan launch of the last dpq_range_search laid out (its live slots x regions). */
+int dpq_debug_range_keys(dpq_index* idx, int64_t* max_keys);
 /* Per-wavefront marks of strand1_kernel on the 100 MHz clock, [256][16][16] words (first call arms them). */
 int dpq_debug_strand1_stamps(dpq_index* idx, unsigned long long* out, int n_words);
 
