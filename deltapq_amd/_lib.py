@@ -105,6 +105,12 @@ SYMBOLS = [
     ("dpq_range_search", ctypes.c_int, [_VP, _VP, ctypes.c_int, _VP, P(_VP)]),
     ("dpq_range_result_get", ctypes.c_int, [_VP, P(c_i32), P(_VP), P(_VP), P(_VP)]),
     ("dpq_range_result_free", None, [_VP]),
+    ("dpq_filter_create", ctypes.c_int, [_VP, _VP, c_i64, P(_VP)]),
+    ("dpq_filter_free", None, [_VP]),
+    ("dpq_filter_count", ctypes.c_int, [_VP, P(c_i64)]),
+    ("dpq_query_batch_filtered", ctypes.c_int, [_VP, _VP, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP]),
+    ("dpq_query_batch_device_filtered", ctypes.c_int,
+     [_VP, _VP, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP]),
     ("dpq_profile_enable", ctypes.c_int, [_VP, ctypes.c_int]),
     ("dpq_profile_reset", ctypes.c_int, [_VP]),
     ("dpq_profile_read", ctypes.c_int, [_VP, P(Profile)]),

@@ -331,6 +331,37 @@ class DeltaPQIndex:
         finally:
             self._lib.dpq_range_result_free(res)
 
+    def query_batch_filtered(self, queries, top_k, id_filter):
+        """The top_k nearest codes among those `id_filter` (an IdFilter made on this index) allows
+        (dpq_query_batch_filtered).  Returns (ids int32 [nq][k], dists float32 [nq][k]); rows are padded with -1 / +inf
+        where fewer than top_k codes are allowed."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        nq = q.shape[0]
+        ids = np.empty((nq, top_k), dtype=np.int32)
+        dists = np.empty((nq, top_k), dtype=np.float32)
+        check(self._lib.dpq_query_batch_filtered(self._h, IdFilter._handle(id_filter), _np_ptr(q), nq, top_k, _np_ptr(ids),
+                                                 _np_ptr(dists)), "dpq_query_batch_filtered")
+        return ids, dists
+
+    def query_batch_filtered_torch(self, queries, top_k, id_filter, out_ids=None, out_dists=None):
+        """query_batch_filtered on device tensors, synchronous on torch's current stream
+        (dpq_query_batch_device_filtered)."""
+        import torch
+        assert queries.is_cuda and queries.dtype == torch.float32 and queries.is_contiguous()
+        nq = queries.shape[0]
+        if out_ids is None:
+            out_ids = torch.empty((nq, top_k), dtype=torch.int32, device=queries.device)
+        if out_dists is None:
+            out_dists = torch.empty((nq, top_k), dtype=torch.float32, device=queries.device)
+        stream = torch.cuda.current_stream(queries.device).cuda_stream
+        check(self._lib.dpq_query_batch_device_filtered(self._h, IdFilter._handle(id_filter), ctypes.c_void_p(queries.data_ptr()),
+                                                        nq, top_k, ctypes.c_void_p(out_ids.data_ptr()),
+                                                        ctypes.c_void_p(out_dists.data_ptr()), ctypes.c_void_p(stream)),
+              "dpq_query_batch_device_filtered")
+        return out_ids, out_dists
+
     def query_batch_host_async(self, queries, top_k, ids, dists):
         """dpq_query_batch_host_async: host arrays in and out, enqueued only -- up to four batches in flight, queries up and
         results down beside the kernels.  `queries` (float32 [nq][D], C-contiguous), `ids` (int32 [nq][k]) and `dists`
@@ -382,6 +413,88 @@ class DeltaPQIndex:
     def close(self):
         if self._h is not None:
             self._lib.dpq_close(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class IdFilter:
+    """A filter of DeltaPQIndex.query_batch_filtered (dpq_filter): the set of reported ids a search may return, uploaded
+    once to the index's device and used by any number of calls on that index.  Bit i of the bitmap is bit (i & 31) of
+    word i >> 5; ids at or beyond n_bits are not allowed."""
+
+    def __init__(self, index, words, n_bits):
+        self._lib = _lib.load()
+        self._h = None
+        w = np.ascontiguousarray(words, dtype=np.uint32)
+        if n_bits < 0 or w.size < (n_bits + 31) // 32:
+            raise ValueError("words must hold n_bits >= 0 bits")
+        h = ctypes.c_void_p()
+        check(self._lib.dpq_filter_create(index._h, _np_ptr(w) if w.size else None, int(n_bits), h), "dpq_filter_create")
+        self._h = h
+
+    @staticmethod
+    def pack_mask(mask):
+        """bool [n] -> (uint32 words [(n + 31) // 32], n): little-endian bits."""
+        m = np.ascontiguousarray(mask, dtype=bool).ravel()
+        n = m.size
+        b = np.packbits(m, bitorder="little")
+        b = np.concatenate([b, np.zeros((-b.size) % 4, dtype=np.uint8)])
+        return b.view("<u4").astype(np.uint32), n
+
+    @staticmethod
+    def pack_ids(ids, n_bits=None):
+        """allowed ids -> (words, n_bits); n_bits defaults to max(ids) + 1."""
+        a = np.asarray(ids, dtype=np.int64).ravel()
+        if n_bits is None:
+            n_bits = int(a.max()) + 1 if a.size else 0
+        if a.size and (a.min() < 0 or a.max() >= n_bits):
+            raise ValueError("ids must lie in [0, n_bits)")
+        m = np.zeros(n_bits, dtype=bool)
+        m[a] = True
+        return IdFilter.pack_mask(m)
+
+    @staticmethod
+    def unpack(words, n_bits):
+        """(words, n_bits) -> bool [n_bits]."""
+        w = np.ascontiguousarray(words, dtype=np.uint32).astype("<u4")
+        return np.unpackbits(w.view(np.uint8), bitorder="little")[:n_bits].astype(bool)
+
+    @classmethod
+    def from_mask(cls, index, mask):
+        """mask[i]: whether reported id i is allowed."""
+        return cls(index, *cls.pack_mask(mask))
+
+    @classmethod
+    def from_ids(cls, index, ids, n_bits=None):
+        return cls(index, *cls.pack_ids(ids, n_bits))
+
+    @staticmethod
+    def _handle(f):
+        if not isinstance(f, IdFilter):
+            raise TypeError("id_filter must be an IdFilter")
+        return f._h
+
+    @property
+    def n_allowed(self):
+        """Nodes of its index the filter allows."""
+        n = _lib.c_i64()
+        check(self._lib.dpq_filter_count(self._h, n), "dpq_filter_count")
+        return n.value
+
+    def close(self):
+        if self._h is not None:
+            self._lib.dpq_filter_free(self._h)
             self._h = None
 
     def __del__(self):

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -126,6 +127,23 @@ struct dpq_range_result {
     std::vector<float> dists;
 };
 
+// A filter of dpq_query_batch_*_filtered: the bitmap of the caller's reported ids, re-indexed by this handle's local
+// node positions (bit l = node id_base + l, the even-N rule applied) and uploaded once.
+struct dpq_filter {
+    uint64_t owner = 0;              // dpq_index::serial of the handle it was made for
+    DevBuf<uint32_t> bits;           // [n_segments x nodes per segment / 32] words
+    int64_t n_allowed = 0;           // local nodes it allows
+    mutable DevBuf<uint32_t> l0_id;  // the level-0 list with the nodes it does not allow as padding (run_batch)
+    mutable int l0_n = -1;           // entries of l0_id (-1: not made yet)
+};
+
+namespace {
+uint64_t next_index_serial() {
+    static std::atomic<uint64_t> next{1};
+    return next++;
+}
+}  // namespace
+
 // Plan and tiling knobs of a handle: dpq_open_opts' fields with the defaults filled in (resolve_tuning).
 struct Tuning {
     // batches up to this size take stream_kernel (1, 2 or 4 queries per pass).  Measured at 125 M codes (ms per call,
@@ -180,6 +198,7 @@ struct Workspace {
 
 struct dpq_index {
     Tuning tune;
+    const uint64_t serial = next_index_serial();  // unique per handle of the process (dpq_filter's owner)
     int device = 0;
     int M = 8, K = 256, Ds = 0;
     int cap = 0;
@@ -633,7 +652,9 @@ struct Batch {
     int64_t stride;     // keys per slot of the candidate buffers (the workspace's cap; prepare_batch)
 };
 
-Batch batch_mode(const dpq_index* x, int nq, int top_k) {
+// filtered: a batch of dpq_query_batch_*_filtered -- never the stream pass (its kernels take no bitmap): a batch of up to
+// stream_max_queries goes through the filter scan as one query group.
+Batch batch_mode(const dpq_index* x, int nq, int top_k, bool filtered = false) {
     Batch b{};
     const int QG = dpq::queries_per_group(x->M);
     b.nq = nq;
@@ -643,7 +664,7 @@ Batch batch_mode(const dpq_index* x, int nq, int top_k) {
     b.cap = x->cap_auto ? auto_cap(top_k) : std::max(x->cap, top_k);
     b.tight_plan = x->tune.tighten && nq > x->tune.stream_max && b.ngroups * dpq::kTightSplits >= dpq::kMaxSplits &&
                    (x->plain || use_batch_decode(x, b.ngroups));
-    b.direct = !x->plain && nq <= x->tune.stream_max;
+    b.direct = !x->plain && nq <= x->tune.stream_max && !filtered;
     b.strands = b.direct && x->img.st_ckpt != nullptr && (x->tune.force_strands || x->img.n_local >= dpq::kStrandMinNodes);
     b.strand1 = b.strands && x->tune.strand1 && dpq::stream_queries_per_pass(x->M, nq) == 1;
     b.strand1_tight = b.strand1 && x->tune.tighten && x->tune.plan_ratios[0] == 0;
@@ -751,7 +772,7 @@ dpq::SelectArgs batch_select_args(const dpq_index* x, const Batch& b, int32_t* d
 }
 
 // Level 0 with a multi-index: the nodes of the query's best cells, evaluated exactly -> first threshold.
-int boot_level(dpq_index* x, const Batch& b, hipStream_t stream) {
+int boot_level(dpq_index* x, const Batch& b, const dpq_filter* filt, hipStream_t stream) {
     const Workspace& w = x->ws();
     const int top_k = b.top_k;
     const int cap_env = x->tune.boot_cap;
@@ -797,12 +818,22 @@ int boot_level(dpq_index* x, const Batch& b, hipStream_t stream) {
     ba.qtab = b.boot_tables ? w.d_qtab.get() : nullptr;
     ba.relabel = b.scratch ? x->d_relabel.get() : nullptr;
     ba.lut_min = w.d_lut_min;
+    if (filt) {
+        // Filtered: the k-th key among allowed nodes, from at most 8 x cap evaluated nodes.  The bound keeps the launch
+        // within 8 x the unfiltered one's evaluations; a filter that allows 1/8 of the nodes or more still fills the key
+        // list, one that allows fewer gives a looser threshold (the k-th of fewer keys) or none (fewer than top_k keys:
+        // the first level then lets every allowed node through, which the select and the rerun handle).
+        ba.filter = filt->bits;
+        ba.id_base = x->img.id_base;
+        ba.eval_cap = 8 * ba.cap;
+    }
     const int slots = b.boot_tables ? b.nqp : b.nq;
     {
         Timer t(x, stream, 5);
         DPQ_HIP(dpq::launch_bootstrap(ba, x->M, slots, stream));
     }
     if (x->prof) x->prof_acc.bootstrap_launches++;
+    if (filt) return DPQ_OK;  // (the developer replay hooks keep unfiltered launches only: a filter may be freed)
     x->dbg_ba = ba;
     x->dbg_boot_slots = slots;
     return DPQ_OK;
@@ -910,7 +941,7 @@ int filter_level(dpq_index* x, const Batch& b, size_t l, dpq::ScanArgs sa, dpq::
     } else {
         Timer t(x, stream, 1);
         DPQ_HIP(dpq::launch_scan(sa, b.ngroups, rg.splits, stream));
-        if (l == 1) {
+        if (l == 1 && !sa.filter) {
             x->dbg_sa = sa;
             x->dbg_groups = b.ngroups;
             x->dbg_splits = rg.splits;
@@ -1033,14 +1064,28 @@ int rerun_overflowed(dpq_index* x, const Batch& b, dpq::ScanArgs sa, dpq::Select
 // One sub-batch (nq <= kMaxBatchQueries) end to end on `stream`.
 // flag_slot 0: synchronous (waits, checks the overflow word, reruns what overflowed); > 0: enqueue only,
 // dpq_finish looks at the word later.
+// filt (synchronous calls only): the batch of dpq_query_batch_*_filtered -- the bootstrap, the scans and level 0 see only
+// the nodes it allows.
 int run_batch(dpq_index* x, const float* d_queries, int nq, int top_k, int32_t* d_ids, float* d_dists,
-              hipStream_t stream, int flag_slot = 0) {
-    Batch b = batch_mode(x, nq, top_k);
+              hipStream_t stream, int flag_slot = 0, const dpq_filter* filt = nullptr) {
+    Batch b = batch_mode(x, nq, top_k, filt != nullptr);
     int rc;
     if ((rc = prepare_batch(x, &b))) return rc;
+    if (filt && !x->boot && x->img.n_segments > 0) {
+        // level 0 of this handle's plan, its nodes the filter does not allow turned into padding (once per filter: the
+        // list of a handle does not change)
+        const int n0 = (int)(x->level_cnt[0] * (int64_t)dpq::kChunk * x->img.chunks_per_segment);
+        if (filt->l0_n != n0) {
+            filt->l0_n = -1;
+            if ((rc = filt->l0_id.alloc((size_t)n0))) return rc;
+            DPQ_HIP(dpq::launch_filter_ids(x->d_l0_id, n0, filt->bits, x->img.id_base, filt->l0_id, stream));
+            filt->l0_n = n0;
+        }
+    }
     if ((rc = build_tables(x, b, d_queries, stream))) return rc;
     x->h_any[flag_slot] = 0;  // the slot is free: its previous batch has been finished
     dpq::ScanArgs sa = batch_scan_args(x, b);
+    sa.filter = filt ? filt->bits.get() : nullptr;
     dpq::SelectArgs se = batch_select_args(x, b, d_ids, d_dists, flag_slot);
 
     const int64_t S = (int64_t)dpq::kChunk * x->img.chunks_per_segment;
@@ -1052,12 +1097,12 @@ int run_batch(dpq_index* x, const float* d_queries, int nq, int top_k, int32_t* 
     }
     for (size_t l = 0; l < n_levels; ++l) {
         if (l == 0 && x->boot) {
-            if ((rc = boot_level(x, b, stream))) return rc;
+            if ((rc = boot_level(x, b, filt, stream))) return rc;
             continue;
         }
         if (l == 0) {
             // level 0: the pre-decoded, query-independent list; every query evaluates it exactly
-            se.shared_id = x->d_l0_id;
+            se.shared_id = filt ? filt->l0_id.get() : x->d_l0_id.get();
             se.shared_code = x->d_l0_code;
             se.shared_n = (int)(x->level_cnt[0] * S);
         } else {
@@ -2330,9 +2375,10 @@ int enqueue_async(dpq_index* x, const float* d_queries, int nq, int top_k, int32
 }
 }  // namespace
 
-int dpq_query_batch_device(dpq_index* x, const float* d_queries, int nq, int top_k, int32_t* d_ids, float* d_dists,
-                           void* hip_stream) {
-    return guarded([&]() -> int {
+namespace {
+// dpq_query_batch_device and its filtered twin (filt != NULL): synchronous on `hip_stream`.
+int query_device(dpq_index* x, const dpq_filter* filt, const float* d_queries, int nq, int top_k, int32_t* d_ids,
+                 float* d_dists, void* hip_stream) {
     if (x && !x->pending.empty()) {  // keep the order of the batches on this index
         int rc = dpq_finish(x);
         if (rc) return rc;
@@ -2345,7 +2391,7 @@ int dpq_query_batch_device(dpq_index* x, const float* d_queries, int nq, int top
     for (int base = 0; base < nq; base += kMaxBatchQueries) {
         const int n = std::min(kMaxBatchQueries, nq - base);
         rc = run_batch(x, d_queries + (size_t)base * D, n, top_k, d_ids + (size_t)base * top_k,
-                       d_dists + (size_t)base * top_k, stream);
+                       d_dists + (size_t)base * top_k, stream, 0, filt);
         if (rc) return rc;
     }
     if (x->prof) {
@@ -2353,11 +2399,10 @@ int dpq_query_batch_device(dpq_index* x, const float* d_queries, int nq, int top
         x->prof_acc.queries += nq;
     }
     return DPQ_OK;
-    });
 }
 
-int dpq_query_batch(dpq_index* x, const float* queries, int nq, int top_k, int32_t* ids, float* dists) {
-    return guarded([&]() -> int {
+// dpq_query_batch and its filtered twin: host buffers through the handle's staging buffers.
+int query_host(dpq_index* x, const dpq_filter* filt, const float* queries, int nq, int top_k, int32_t* ids, float* dists) {
     if (!x || !queries || !ids || !dists || nq < 0) return fail(DPQ_ERR_ARG, "NULL argument or nq < 0");
     if (!x->d_codebook) return fail(DPQ_ERR_STATE, "dpq_set_codebook has not been called");
     if (nq == 0) return DPQ_OK;
@@ -2379,12 +2424,98 @@ int dpq_query_batch(dpq_index* x, const float* queries, int nq, int top_k, int32
         x->out_stage_elems = oe;
     }
     DPQ_HIP(hipMemcpy(x->d_q_stage, queries, qf * sizeof(float), hipMemcpyHostToDevice));
-    int rc = dpq_query_batch_device(x, x->d_q_stage, nq, top_k, x->d_ids_stage, x->d_dists_stage, nullptr);
+    int rc = query_device(x, filt, x->d_q_stage, nq, top_k, x->d_ids_stage, x->d_dists_stage, nullptr);
     if (rc) return rc;
     DPQ_HIP(hipDeviceSynchronize());
     DPQ_HIP(hipMemcpy(ids, x->d_ids_stage, oe * sizeof(int32_t), hipMemcpyDeviceToHost));
     DPQ_HIP(hipMemcpy(dists, x->d_dists_stage, oe * sizeof(float), hipMemcpyDeviceToHost));
     return DPQ_OK;
+}
+
+int check_filter(const dpq_index* x, const dpq_filter* f) {
+    if (!x) return fail(DPQ_ERR_ARG, "NULL index");
+    if (!f) return fail(DPQ_ERR_ARG, "filter is NULL");
+    if (f->owner != x->serial) return fail(DPQ_ERR_ARG, "the filter was made for another index handle");
+    return DPQ_OK;
+}
+}  // namespace
+
+int dpq_query_batch_device(dpq_index* x, const float* d_queries, int nq, int top_k, int32_t* d_ids, float* d_dists,
+                           void* hip_stream) {
+    return guarded([&]() -> int { return query_device(x, nullptr, d_queries, nq, top_k, d_ids, d_dists, hip_stream); });
+}
+
+int dpq_query_batch(dpq_index* x, const float* queries, int nq, int top_k, int32_t* ids, float* dists) {
+    return guarded([&]() -> int { return query_host(x, nullptr, queries, nq, top_k, ids, dists); });
+}
+
+int dpq_filter_create(dpq_index* x, const uint32_t* words, int64_t n_bits, dpq_filter** out) {
+    return guarded([&]() -> int {
+    if (!out) return fail(DPQ_ERR_ARG, "out is NULL");
+    *out = nullptr;
+    if (!x || n_bits < 0 || (n_bits > 0 && !words)) return fail(DPQ_ERR_ARG, "NULL argument or n_bits < 0");
+    DPQ_HIP(hipSetDevice(x->device));
+    // Local bit l (node id_base + l) = the caller's bit of the id the handle reports for that node: id_base + l, or N
+    // for the last node of an even-N DTC index (report_id).  The bitmap covers every node of every segment (the scan
+    // reads whole segments' words); nodes past n_local stay 0.
+    const int64_t S = (int64_t)dpq::kChunk * x->img.chunks_per_segment;
+    const int64_t n_local = x->img.n_local, n_nodes = std::max<int64_t>(n_local, (int64_t)x->img.n_segments * S);
+    const int64_t n_words = std::max<int64_t>(1, (n_nodes + 31) / 32), user_words = (n_bits + 31) / 32;
+    const int64_t base = x->img.id_base;
+    auto user_bit = [&](int64_t r) -> uint32_t { return r < n_bits ? (words[r >> 5] >> (r & 31)) & 1u : 0u; };
+    std::vector<uint32_t> h((size_t)n_words, 0u);
+    int64_t allowed = 0;
+    for (int64_t w = 0; w < n_words && 32 * w < n_local; ++w) {
+        const int64_t g0 = base + 32 * w;  // global position of local bit 32 w
+        if (g0 >= n_bits) break;
+        const int64_t lo = g0 >> 5;
+        const int sh = (int)(g0 & 31);
+        uint32_t v = words[lo] >> sh;
+        if (sh && lo + 1 < user_words) v |= words[lo + 1] << (32 - sh);
+        const int64_t valid = std::min<int64_t>(32, std::min(n_bits - g0, n_local - 32 * w));
+        if (valid < 32) v &= (1u << valid) - 1u;
+        h[(size_t)w] = v;
+    }
+    const int64_t N = x->img.n_codes_total;
+    if (!x->plain && (N & 1) == 0 && N - 1 >= base && N - 1 < base + n_local) {  // the even-N rule
+        const int64_t l = N - 1 - base;
+        h[(size_t)(l >> 5)] = (h[(size_t)(l >> 5)] & ~(1u << (l & 31))) | (user_bit(N) << (l & 31));
+    }
+    for (uint32_t v : h) allowed += __builtin_popcount(v);
+    std::unique_ptr<dpq_filter> f(new dpq_filter());
+    f->owner = x->serial;
+    f->n_allowed = allowed;
+    int rc = f->bits.alloc((size_t)n_words);
+    if (rc) return rc;
+    DPQ_HIP(hipMemcpy(f->bits, h.data(), (size_t)n_words * sizeof(uint32_t), hipMemcpyHostToDevice));
+    *out = f.release();
+    return DPQ_OK;
+    });
+}
+
+void dpq_filter_free(dpq_filter* f) { delete f; }
+
+int dpq_filter_count(const dpq_filter* f, int64_t* n_allowed) {
+    if (!f || !n_allowed) return fail(DPQ_ERR_ARG, "NULL argument");
+    *n_allowed = f->n_allowed;
+    return DPQ_OK;
+}
+
+int dpq_query_batch_filtered(dpq_index* x, const dpq_filter* f, const float* queries, int nq, int top_k, int32_t* ids,
+                             float* dists) {
+    return guarded([&]() -> int {
+    int rc = check_filter(x, f);
+    if (rc) return rc;
+    return query_host(x, f, queries, nq, top_k, ids, dists);
+    });
+}
+
+int dpq_query_batch_device_filtered(dpq_index* x, const dpq_filter* f, const float* d_queries, int nq, int top_k,
+                                    int32_t* d_ids, float* d_dists, void* hip_stream) {
+    return guarded([&]() -> int {
+    int rc = check_filter(x, f);
+    if (rc) return rc;
+    return query_device(x, f, d_queries, nq, top_k, d_ids, d_dists, hip_stream);
     });
 }
 

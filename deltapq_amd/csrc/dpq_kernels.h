@@ -87,6 +87,11 @@ struct ScanArgs {
     // (lut_build_kernel / quantise_kernel clear them); tight_k = top_k.
     uint32_t* tight_hist;
     int32_t tight_k;
+    // Filtered search (dpq_query_batch_filtered; NULL = off): bit l of the bitmap (word l >> 5, bit l & 31) allows LOCAL
+    // node l (global DFS position id_base + l), [n_segments x nodes per segment] bits.  A node whose bit is clear never
+    // reaches the exact check, so it is neither a candidate nor counted by the in-scan tightening (scan_kernel's filtered
+    // instantiations; the stream / strand kernels take no bitmap).
+    const uint32_t* filter;
 };
 
 struct SelectArgs {
@@ -140,7 +145,18 @@ struct BootArgs {
     const float* lut_min;          // [query][M][4]
     unsigned long long* stamps;    // developer diagnostics (NULL in product calls): [slots][8] s_memtime marks
     int32_t variant;               // bootstrap_kernel's V: 1 = round 4's kernel (one-pass threshold), 0 = round 3's, kept for A/B
+    // Filtered search (NULL = off): the bitmap of ScanArgs::filter.  The filtered kernel loads each evaluated node's id,
+    // keeps the keys of allowed nodes only and walks cells until it holds `target` of them or has evaluated
+    // eval_cap nodes (variant 1 only).
+    const uint32_t* filter;
+    uint32_t id_base;              // global DFS position of local node 0 (mi_id - id_base = the bitmap's index)
+    int32_t eval_cap;
 };
+
+// The level-0 list of a filtered batch: ids[i] stays where its node is allowed by `filter` (local bitmap, as in ScanArgs),
+// else becomes 0xffffffff (a padding node: the select kernel gives it the ~0 key and does not count it).
+hipError_t launch_filter_ids(const uint32_t* ids, int n, const uint32_t* filter, uint32_t id_base, uint32_t* out,
+                             hipStream_t stream);
 
 // Range search (dpq_range_search): the filter scan at the caller's radii, then these two over its candidate regions.
 constexpr int kRangeMaxQueries = 2048;   // queries of one sub-batch (range_count_kernel holds their totals in LDS)

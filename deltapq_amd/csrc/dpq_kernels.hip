@@ -682,6 +682,9 @@ __global__ __launch_bounds__(256) void quantise_kernel(const ScanArgs a) {
 #endif
 
 // LDS map of the scan workgroup
+// Added to M in a template argument of scan_kernel / bootstrap_kernel: the instantiation of a filtered batch.
+constexpr int kFiltered = 0x1000;
+
 template <int M>
 struct ScanLds {
     using C = Cfg<M>;
@@ -715,8 +718,13 @@ enum { kStPrologue = 0, kStSegment, kStDecode, kStGather, kStFold, kStPush, kStR
 // Register budget: the plain-code instantiations at M = 8 stay within 96 VGPRs (second launch bound: five wavefronts per
 // SIMD), although a workgroup only ever brings four: the fifth slot's registers are what the NEXT pipelined batch's
 // table build and decode run in, under this scan (at 121 VGPRs the pipelined step was 18 us longer).
-template <int M, bool PLAIN, bool STAMPS, bool TIGHT>
-__global__ __launch_bounds__(kScanThreads, (PLAIN && !STAMPS && M <= 8) ? 5 : 4) void scan_kernel(const ScanArgs a) {
+// MF = M, or M | kFiltered: the instantiation of a filtered batch (ScanArgs::filter) -- a node whose bit is clear joins no
+// survivor mask (see the fold below).  (A flag inside M, not a template parameter of its own, keeps the names and the code
+// of the unfiltered instantiations what they were.)
+template <int MF, bool PLAIN, bool STAMPS, bool TIGHT>
+__global__ __launch_bounds__(kScanThreads, (PLAIN && !STAMPS && (MF & ~kFiltered) <= 8) ? 5 : 4) void scan_kernel(const ScanArgs a) {
+    constexpr int M = MF & ~kFiltered;
+    constexpr bool FILT = (MF & kFiltered) != 0;
     using C = Cfg<M>;
     constexpr int W = C::W, QG = C::QG, NG = C::NG, NA = C::NA, EB = C::AB, F = C::F, MD = C::MD, QCAP = C::QCAP;
     constexpr int TE = M * 256;  // table entries per query
@@ -1099,12 +1107,18 @@ __global__ __launch_bounds__(kScanThreads, (PLAIN && !STAMPS && M <= 8) ? 5 : 4)
         return n;
     };
     Chunk A, B, Cn;
+    // FILT: the bitmap word of the lane's node of chunk A / B / Cn, loaded with the chunk's stage 1 (a wavefront's 64 nodes
+    // are one or two words; a list covers whole segments, and the bitmap has their bits)
+    uint32_t fwA = 0, fwB = 0, fwC = 0;
+    auto filter_word = [&](const Chunk& k) -> uint32_t { return k.seg < 0 ? 0u : a.filter[(size_t)node_of(k) >> 5]; };
     A.seg = helper ? -1 : next_entry();  // the helper draws no segments: its scan loop below is empty
     A.pos = entry_pos;
     A.c = 0;
     stage1(A);
+    if constexpr (FILT) fwA = filter_word(A);
     B = successor(A);
     stage1(B);
+    if constexpr (FILT) fwB = filter_word(B);
     stage2(A);
     stamp(kStSegment);
     while (A.seg >= 0) {
@@ -1126,9 +1140,11 @@ __global__ __launch_bounds__(kScanThreads, (PLAIN && !STAMPS && M <= 8) ? 5 : 4)
 #pragma unroll
             for (int w = 0; w < W; ++w) asm volatile("" ::"v"(A.h_stk[w]), "v"(B.h_stk[w]));
         }
+        if constexpr (FILT) asm volatile("" ::"v"(fwA), "v"(fwB));
         Cn = successor(B);
         stage2(B);
         stage1(Cn);
+        if constexpr (FILT) fwC = filter_word(Cn);
         {
             const int64_t node = node_of(A);
             uint32_t code[W];
@@ -1258,7 +1274,11 @@ __global__ __launch_bounds__(kScanThreads, (PLAIN && !STAMPS && M <= 8) ? 5 : 4)
             // Fold the top bits of the NA accumulators into one pending mask per lane (bit = local slot):
             // shift-and-insert with one mask constant, accumulator j of a mask dword ends at bit j of
             // every field. ----
-            const bool valid = node < a.img.n_local;
+            // FILT: a node the caller's filter does not allow is no survivor of any slot -- it is never checked exactly,
+            // never a candidate and never counted by the tightening (whose cuts must stay upper bounds of the k-th
+            // key among ALLOWED nodes)
+            bool valid = node < a.img.n_local;
+            if constexpr (FILT) valid = valid && ((fwA >> ((uint32_t)node & 31u)) & 1u) != 0u;
             uint64_t pend = 0;
 #pragma unroll
             for (int h = 0; h < MD; ++h) {
@@ -1296,6 +1316,7 @@ __global__ __launch_bounds__(kScanThreads, (PLAIN && !STAMPS && M <= 8) ? 5 : 4)
         }
         A = B;
         B = Cn;
+        if constexpr (FILT) fwA = fwB, fwB = fwC;
     }
     while (rq_n > 0) refine(min(rq_n, 64));
     stamp(kStRefine);
@@ -2927,10 +2948,14 @@ constexpr int kBootBatch = 6;    // nodes a thread has in flight: cap / threads 
 // range fixed by the block's first batch of keys, so that no key is stored and the block's LDS stops growing with the nodes
 // it evaluates (top-1000: 65 KB = two blocks per CU -> 24.5 KB = four): top-100 22.5 -> 23.0 us and a looser bound,
 // top-1000 + 1 %, top-512 - 2 % (profiles/r04b_boot_online_histogram_ab.txt): the blocks per CU were not what bounds it.
-template <int M, int V>
+// MF = M, or M | kFiltered (V = 1 only): the bootstrap of a filtered batch (BootArgs::filter) -- only nodes the caller's
+// filter allows count, see the evaluation below.
+template <int MF, int V>
 // M = 8: four blocks per CU (40 KB of LDS each) = 8 wavefronts per SIMD: the register budget (SGPRs included:
 // 800 per SIMD) must allow it; M = 16: three blocks (48 KB)
-__global__ __launch_bounds__(kBootThreads, M <= 8 ? 8 : 6) void bootstrap_kernel(const BootArgs a) {
+__global__ __launch_bounds__(kBootThreads, (MF & ~kFiltered) <= 8 ? 8 : 6) void bootstrap_kernel(const BootArgs a) {
+    constexpr int M = MF & ~kFiltered;
+    constexpr bool FILT = (MF & kFiltered) != 0;
     constexpr int W = Cfg<M>::W;
     constexpr int TE = M * 256;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -3037,6 +3062,7 @@ __global__ __launch_bounds__(kBootThreads, M <= 8 ? 8 : 6) void bootstrap_kernel
     mark(1);
 
     int have = 0;  // keys so far (block-uniform)
+    int evaluated = 0;  // FILT: nodes evaluated so far (block-uniform)
     int rounds = 0;
     uint32_t key_lo = 0xffffffffu, key_hi = 0u;  // of the keys this thread wrote (V & 1)
     // Every class walks its 65536 cells in the order w = 0, 1, ...: shell t = floor(sqrt(w)) (= max of the two
@@ -3046,7 +3072,7 @@ __global__ __launch_bounds__(kBootThreads, M <= 8 ? 8 : 6) void bootstrap_kernel
     const int P = a.n_classes;  // 4 or 1
     const int p_shift = P == 4 ? 2 : 0;
     int w0 = 0;
-    while (w0 < 65536 && have < a.target) {
+    while (w0 < 65536 && have < a.target && (!FILT || evaluated < a.eval_cap)) {
         const int n_w = min(kBootCells >> p_shift, 65536 - w0);
         const int n_cells = n_w << p_shift;
         uint32_t cnt[kBootCellsPerThread], first[kBootCellsPerThread], mine = 0;
@@ -3100,6 +3126,65 @@ __global__ __launch_bounds__(kBootThreads, M <= 8 ? 8 : 6) void bootstrap_kernel
         // search -> entry loads -> distance together.  Only an UPPER BOUND of the k-th key has to leave this kernel,
         // so the distances are plain fp32 sums (relative error < 2^-21 against the exact fp64 sum) and the keys are
         // their 32 bits: no fp64 adds, no id loads, half the LDS per key; the bound is inflated below.
+        if constexpr (FILT) {
+            // Filtered: the threshold must be the k-th key of ALLOWED nodes, so every evaluated node's id is loaded and
+            // tested, and only allowed keys go to the list (compacted through an LDS counter).  The round's nodes are
+            // walked in steps of kBootThreads x kBootBatch until the list holds `cap` keys or eval_cap nodes have been
+            // evaluated over all rounds (a filter that allows few nodes would otherwise walk the whole multi-index).
+            __shared__ uint32_t s_kept;
+            if (tid == 0) s_kept = (uint32_t)have;
+            __syncthreads();
+            // At most the round's first 65535 nodes: `pre` holds the cells' node prefix clamped to 16 bits, so the search
+            // below finds a node's cell only for v < 65535 (the unfiltered walk takes <= cap <= 16384).  eval_cap may be up to
+            // 8 x 16384, and one cell of a concentrated multi-index can hold more than that: the rest of such a round is left
+            // out (any subset of real nodes gives a valid bound).
+            const int take = min(min((int)total, a.eval_cap - evaluated), 65535);
+            int v0 = 0;
+            for (; v0 < take; v0 += kBootThreads * kBootBatch) {
+                uint32_t e[kBootBatch], id[kBootBatch], code[kBootBatch][W];
+#pragma unroll
+                for (int r = 0; r < kBootBatch; ++r) {
+                    const int v = min(v0 + tid + r * kBootThreads, take - 1);
+                    int pos = 0;
+#pragma unroll
+                    for (int step = 512; step > 0; step >>= 1) pos += (uint32_t)pre[pos + step] <= (uint32_t)v ? step : 0;
+                    e[r] = cstart[pos] + ((uint32_t)v - pre[pos]);
+                }
+#pragma unroll
+                for (int r = 0; r < kBootBatch; ++r) {
+                    id[r] = a.mi_id[e[r]] - a.id_base;  // the multi-index holds this shard's nodes only
+#pragma unroll
+                    for (int w = 0; w < W; ++w) code[r][w] = a.mi_code[(size_t)e[r] * W + w];
+                }
+                uint32_t fw[kBootBatch];
+#pragma unroll
+                for (int r = 0; r < kBootBatch; ++r) fw[r] = a.filter[id[r] >> 5];
+#pragma unroll
+                for (int r = 0; r < kBootBatch; ++r) {
+                    const int v = v0 + tid + r * kBootThreads;
+                    float d = 0.0f;
+#pragma unroll
+                    for (int m = 0; m < M; ++m) d += T[m * 256 + ((code[r][m >> 2] >> (8 * (m & 3))) & 0xffu)];
+                    if (v < take && ((fw[r] >> (id[r] & 31u)) & 1u)) {
+                        const uint32_t slot_i = atomicAdd(&s_kept, 1u);
+                        if (slot_i < (uint32_t)a.cap) {
+                            keys[slot_i] = __float_as_uint(d);
+                            key_lo = min(key_lo, __float_as_uint(d));
+                            key_hi = max(key_hi, __float_as_uint(d));
+                        }
+                    }
+                }
+                __syncthreads();
+                const uint32_t kept = s_kept;  // block-uniform: read between two barriers
+                __syncthreads();
+                if (kept >= (uint32_t)a.cap) {
+                    v0 += kBootThreads * kBootBatch;
+                    break;
+                }
+            }
+            evaluated += min(v0, take);
+            have = (int)min(s_kept, (uint32_t)a.cap);
+        } else {
         const int take = min((int)total, a.cap - have);
         for (int v0 = 0; v0 < take; v0 += kBootThreads * kBootBatch) {
             uint32_t e[kBootBatch], code[kBootBatch][W];
@@ -3133,6 +3218,7 @@ __global__ __launch_bounds__(kBootThreads, M <= 8 ? 8 : 6) void bootstrap_kernel
             }
         }
         have += take;
+        }
         ++rounds;
         w0 += n_w;
         __syncthreads();  // pre / cstart / wave_sum are rewritten by the next round
@@ -3176,6 +3262,25 @@ __global__ __launch_bounds__(kBootThreads, M <= 8 ? 8 : 6) void bootstrap_kernel
     if (a.stamps && tid == 0) a.stamps[(size_t)slot * 8 + 7] = __builtin_amdgcn_s_memrealtime();
 }
 
+// The level-0 list of a filtered batch (launch_filter_ids).
+__global__ __launch_bounds__(256) void filter_ids_kernel(const uint32_t* __restrict__ ids, int n,
+                                                         const uint32_t* __restrict__ filter, uint32_t id_base,
+                                                         uint32_t* __restrict__ out) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t id = ids[i];
+    const uint32_t l = id - id_base;
+    out[i] = id != 0xffffffffu && ((filter[l >> 5] >> (l & 31u)) & 1u) ? id : 0xffffffffu;
+}
+
+hipError_t launch_filter_ids(const uint32_t* ids, int n, const uint32_t* filter, uint32_t id_base, uint32_t* out,
+                             hipStream_t stream) {
+    if (n <= 0) return hipSuccess;
+    if (!ids || !filter || !out) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(filter_ids_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, ids, n, filter, id_base, out);
+    return hipGetLastError();
+}
+
 size_t bootstrap_lds_bytes(int M, int cap) {
     return (size_t)cap * 4 + (size_t)M * 256 * 4 + (size_t)kBootCells * 4 + (1024 + 4) * 2 + 2 * kBootPairs * 256 + (264 + 2 + 8) * 4;
 }
@@ -3203,6 +3308,23 @@ hipError_t launch_bootstrap(const BootArgs& a, int M, int n_slots, hipStream_t s
     if (a.cap < a.top_k || a.cap < 2048 || a.cap > 16384 || !a.cell_start || (a.n_classes != 1 && a.n_classes != kBootPairs))
         return hipErrorInvalidValue;  // the rank sort borrows 8 KB of the key list
     const size_t lds = bootstrap_lds_bytes(M, a.cap);
+    if (a.filter) {
+        if (a.eval_cap < 1) return hipErrorInvalidValue;
+        if (M == 8) {
+            static std::atomic<bool> done[64] = {};
+            hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(&bootstrap_kernel<8 | kFiltered, 1>), 128 * 1024, done);
+            if (e != hipSuccess) return e;
+            hipLaunchKernelGGL((bootstrap_kernel<8 | kFiltered, 1>), dim3((unsigned)n_slots), dim3(kBootThreads), lds, stream, a);
+        } else if (M == 16) {
+            static std::atomic<bool> done[64] = {};
+            hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(&bootstrap_kernel<16 | kFiltered, 1>), 128 * 1024, done);
+            if (e != hipSuccess) return e;
+            hipLaunchKernelGGL((bootstrap_kernel<16 | kFiltered, 1>), dim3((unsigned)n_slots), dim3(kBootThreads), lds, stream, a);
+        } else {
+            return hipErrorInvalidValue;
+        }
+        return hipGetLastError();
+    }
     return (a.variant & 1) ? launch_bootstrap_variant<1>(a, M, n_slots, lds, stream)
                            : launch_bootstrap_variant<0>(a, M, n_slots, lds, stream);
 }
@@ -3552,6 +3674,17 @@ static hipError_t launch_scan_m(const ScanArgs& a, int n_slot_groups, int splits
     return hipGetLastError();
 }
 
+template <int M, bool PLAIN, bool TIGHT>
+static hipError_t launch_scan_filtered_m(const ScanArgs& a, int n_slot_groups, int splits, hipStream_t stream) {
+    static std::atomic<bool> done[64] = {};
+    hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(&scan_kernel<M | kFiltered, PLAIN, false, TIGHT>),
+                                      scan_lds_bytes(M), done);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((scan_kernel<M | kFiltered, PLAIN, false, TIGHT>), dim3((unsigned)splits, (unsigned)n_slot_groups),
+                       dim3(kScanThreads), scan_lds_bytes(M), stream, a);
+    return hipGetLastError();
+}
+
 // Q queries per pass (stream_kernel): ceil(n_slots / Q) passes over the launch's segment list; Q = the smallest of
 // 1, 2, 4 that covers the batch (eight per pass were measured too: 64 KB of tables leave 8-16 wavefronts per CU, and
 // the batched filter path answers eight queries in half the time).  The slots' region 1 counts must
@@ -3656,12 +3789,21 @@ hipError_t launch_scan(const ScanArgs& a, int n_slot_groups, int splits, hipStre
     if (!a.qtab) return hipErrorInvalidValue;
     const bool plain = a.img.raw != nullptr;
     if (a.stamps) {  // diagnostic instantiation (M = 8 only)
-        if (a.img.M != 8) return hipErrorInvalidValue;
+        if (a.img.M != 8 || a.filter) return hipErrorInvalidValue;
         return plain ? launch_scan_m<8, true, true>(a, n_slot_groups, splits, stream)
                      : launch_scan_m<8, false, true>(a, n_slot_groups, splits, stream);
     }
     // in-scan threshold tightening: plain-code instantiations only (the decode's registers leave no room for it)
     const bool tight = plain && a.tight_hist != nullptr && a.tight_k > 0 && a.debug_pass == 0 && splits <= kTightSplits;
+    if (a.filter) {
+        if (a.img.M == 8) return !plain ? launch_scan_filtered_m<8, false, false>(a, n_slot_groups, splits, stream)
+                                 : tight ? launch_scan_filtered_m<8, true, true>(a, n_slot_groups, splits, stream)
+                                         : launch_scan_filtered_m<8, true, false>(a, n_slot_groups, splits, stream);
+        if (a.img.M == 16) return !plain ? launch_scan_filtered_m<16, false, false>(a, n_slot_groups, splits, stream)
+                                  : tight ? launch_scan_filtered_m<16, true, true>(a, n_slot_groups, splits, stream)
+                                          : launch_scan_filtered_m<16, true, false>(a, n_slot_groups, splits, stream);
+        return hipErrorInvalidValue;
+    }
     if (a.img.M == 8) return !plain ? launch_scan_m<8, false, false>(a, n_slot_groups, splits, stream)
                              : tight ? launch_scan_m<8, true, false, true>(a, n_slot_groups, splits, stream)
                                      : launch_scan_m<8, true, false>(a, n_slot_groups, splits, stream);

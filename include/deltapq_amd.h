@@ -343,6 +343,36 @@ int dpq_range_result_get(const dpq_range_result* r, int32_t* nq, const int64_t**
                          const float** dists);
 void dpq_range_result_free(dpq_range_result* r);  /* NULL: nothing happens */
 
+/* ---- filtered top-k search ------------------------------------------------
+ * The k nearest codes among those an id bitmap allows (FAISS's IDSelector).  A filter is a bitmap over REPORTED ids:
+ * bit i is bit (i & 31) of words[i >> 5] (little-endian within a uint32_t), n_bits bits.  A code is eligible iff its
+ * reported id r -- exactly the id dpq_query_batch would report for it: global DFS positions on shards and parts
+ * (global_offset), position = id on a plain index, and the even-N rule (the last node of an even-N DTC index is
+ * reported as N, so bit N governs it and bit N - 1 governs nothing; N = num_codes under the same rule) -- satisfies
+ * r < n_bits and bit r is set.
+ * The result is the unfiltered algorithm applied to the eligible codes only: per query top_k entries ascending by
+ * (distance, id), distances bit-identical to what dpq_query_batch reports for the same code, rows padded with id -1 /
+ * +inf when fewer than top_k codes of the handle are eligible (none at all: an all-padding result, not an error).  One
+ * filter applies to every query of a call.  With shard_count > 1 each shard's result is its partial filtered top-k:
+ * dpq_merge_topk_* (deltapq_amd.dist) merge them unchanged, every rank building its filter from the same global bitmap.
+ * The calls are synchronous; pending asynchronous batches are finished first; the asynchronous, ordered and
+ * host-async pipelines have no filtered form.  A NULL filter or one made on another handle is DPQ_ERR_ARG.  Plans,
+ * workspaces and results of later unfiltered calls are not affected.  Device memory: the filter holds n_local / 8 bytes
+ * (rounded up to whole segments) plus, on handles without a bootstrap, a 15 KB copy of the level-0 id list. */
+typedef struct dpq_filter dpq_filter;
+/* words[(n_bits + 31) / 32], host memory, read during the call only.  Uploads to the index's device the part of the
+ * bitmap this handle can report (its [node_lo, node_hi) range, even-N rule applied), once.  n_bits >= 0. */
+int dpq_filter_create(dpq_index* idx, const uint32_t* words, int64_t n_bits, dpq_filter** out);
+void dpq_filter_free(dpq_filter* f);   /* NULL: nothing happens */
+/* Nodes of its handle the filter allows. */
+int dpq_filter_count(const dpq_filter* f, int64_t* n_allowed);
+/* Host buffers, synchronous (the contract of dpq_query_batch). */
+int dpq_query_batch_filtered(dpq_index* idx, const dpq_filter* f, const float* queries, int nq, int top_k,
+                             int32_t* ids, float* dists);
+/* Device buffers on hip_stream (the contract of dpq_query_batch_device). */
+int dpq_query_batch_device_filtered(dpq_index* idx, const dpq_filter* f, const float* d_queries, int nq, int top_k,
+                                    int32_t* d_ids, float* d_dists, void* hip_stream);
+
 /* Merge n_lists partial top-k lists per query (lists[l][nq][top_k]) into the
  * final top_k by (distance, id).  Host version for the single-process
  * multi-GPU CLI, device version for use after an RCCL all-gather. */
