@@ -51,6 +51,17 @@ class DtcStats(ctypes.Structure):
                 ("max_depth", c_i32), ("M", c_i32)]
 
 
+class TrainOpts(ctypes.Structure):
+    _fields_ = [("device", c_i32), ("max_iters", c_i32), ("seed", ctypes.c_uint64), ("use_initial", c_i32),
+                ("reserved", c_i32 * 3)]
+
+
+class TrainStats(ctypes.Structure):
+    _fields_ = [("iters_run", c_i32), ("converged", c_i32), ("reseeded", c_i64), ("distortion", ctypes.c_double * 64),
+                ("gpu_ms", ctypes.c_double), ("wall_ms", ctypes.c_double), ("rounds_ms", ctypes.c_double),
+                ("assign_ms", ctypes.c_double), ("update_ms", ctypes.c_double), ("repair_ms", ctypes.c_double)]
+
+
 # every symbol include/deltapq_amd.h declares: (name, restype, argtypes)
 _VP = ctypes.c_void_p
 SYMBOLS = [
@@ -82,6 +93,9 @@ SYMBOLS = [
     ("dpq_read_codes_plain_ex", ctypes.c_int, [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, P(c_i64), _VP, _VP]),
     ("dpq_encode_pq", ctypes.c_int,
      [_VP, c_i64, ctypes.c_int, _VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _VP]),
+    ("dpq_train_codebook", ctypes.c_int,
+     [_VP, c_i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, P(TrainOpts), _VP, P(TrainStats)]),
+    ("dpq_write_codewords", ctypes.c_int, [ctypes.c_char_p, _VP, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     ("dpq_open_plain_memory", ctypes.c_int, [_VP, c_i64, ctypes.c_int, ctypes.c_int, P(OpenOpts), P(_VP)]),
     ("dpq_open_plain_file", ctypes.c_int, [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, P(OpenOpts), P(_VP)]),
     ("dpq_open_file", ctypes.c_int, [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, P(OpenOpts), P(_VP)]),

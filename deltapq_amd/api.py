@@ -176,6 +176,35 @@ def encode_pq(vectors, codebook, device=0):
     return out
 
 
+def train_codebook(vectors, M=8, K=256, max_iters=25, seed=0, init=None, device=0):
+    """Codebook learning on the GPU (dpq_train_codebook; replaces PQ::Learn, pq.cpp:112-157, with this build's own
+    exact semantics -- no reference semantics (cv::kmeans)).  init: a start [M][K][Ds] instead of the seeded one.
+    Returns (codebook float32 [M][K][Ds], stats dict)."""
+    lib = _lib.load()
+    v = np.ascontiguousarray(vectors, dtype=np.float32)
+    assert v.ndim == 2
+    n, D = v.shape
+    Ds = -(-D // M) if M >= 1 else 1
+    opts = _lib.TrainOpts(device=device, max_iters=max_iters, seed=seed, use_initial=int(init is not None))
+    if init is None:
+        cb = np.zeros((max(M, 1), max(K, 1), Ds), dtype=np.float32)
+    else:
+        cb = np.array(init, dtype=np.float32, order="C")
+        assert cb.shape == (M, K, Ds), "init must be [M][K][ceil(D / M)]"
+    st = _lib.TrainStats()
+    check(lib.dpq_train_codebook(_np_ptr(v), n, D, M, K, opts, _np_ptr(cb), st), "dpq_train_codebook")
+    stats = {k: getattr(st, k) for k, _ in st._fields_ if k != "distortion"}
+    stats["distortion"] = [st.distortion[i] for i in range(st.iters_run)]
+    return cb, stats
+
+
+def write_codewords(path, codebook):
+    """PQ::WriteCodewords' format (pq.cpp:267-286) with nine significant digits: read_codewords gives the same bits."""
+    cb = np.ascontiguousarray(codebook, dtype=np.float32)
+    M, K, Ds = cb.shape
+    check(_lib.load().dpq_write_codewords(path.encode(), _np_ptr(cb), M, K, Ds), "dpq_write_codewords")
+
+
 def read_codes_plain(path, M):
     """PQTree::Read (pq_tree.cpp:1032-1081): uint8 [N][M]."""
     lib = _lib.load()

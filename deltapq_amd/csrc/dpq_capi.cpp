@@ -24,6 +24,7 @@
 #include "dpq_build.h"
 #include "dpq_format.h"
 #include "dpq_kernels.h"
+#include "dpq_train.h"
 
 namespace {
 
@@ -2071,6 +2072,83 @@ int dpq_encode_pq(const float* vectors, int64_t n, int D, const float* codewords
         if (e == hipSuccess) e = hipMemcpy(codes_out + (size_t)base * M, d_o, (size_t)m * M, hipMemcpyDeviceToHost);
     }
     if (e != hipSuccess) return fail(DPQ_ERR_HIP, std::string("dpq_encode_pq: ") + hipGetErrorString(e));
+    return DPQ_OK;
+    });
+}
+
+int dpq_train_codebook(const float* vectors, int64_t n, int D, int M, int K, const dpq_train_opts* opts, float* codewords,
+                       dpq_train_stats* stats) {
+    return guarded([&]() -> int {
+    const int device = opts ? opts->device : 0, max_iters = opts ? opts->max_iters : 25;
+    if (!vectors || !codewords) return fail(DPQ_ERR_ARG, "dpq_train_codebook: NULL argument");
+    if (D < 1 || M < 1 || M > 256) return fail(DPQ_ERR_ARG, "dpq_train_codebook: D < 1 or M outside 1..256");
+    if (K < 2 || K > 256) return fail(DPQ_ERR_ARG, "dpq_train_codebook: K outside 2..256 (one byte per label)");
+    if (n < K) return fail(DPQ_ERR_ARG, "dpq_train_codebook: fewer vectors than codewords (K > n)");
+    if (n * M >= ((int64_t)1 << 31)) return fail(DPQ_ERR_ARG, "dpq_train_codebook: n * M >= 2^31");
+    if (max_iters < 1 || max_iters > 64) return fail(DPQ_ERR_ARG, "dpq_train_codebook: max_iters outside 1..64");
+    const int Ds = (D + M - 1) / M;
+    const size_t lds = dpq::train_lds_bytes(K, Ds);
+    if (lds == 0 || lds > 160 * 1024)
+        return fail(DPQ_ERR_ARG, "dpq_train_codebook: a sub-space's codewords need more than 160 KB of LDS");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail(DPQ_ERR_NO_DEVICE, "no HIP device visible; this library has no CPU fallback");
+    if (device < 0 || device >= ndev) return fail(DPQ_ERR_NO_DEVICE, "device ordinal out of range");
+    DPQ_HIP(hipSetDevice(device));
+    if (!(opts && opts->use_initial)) {
+        // the seeded start (header comment): K rows without replacement, the same rows for every sub-space
+        std::vector<int64_t> p((size_t)n);
+        std::iota(p.begin(), p.end(), (int64_t)0);
+        uint64_t s = opts ? opts->seed : 0;
+        for (int i = 0; i < K; ++i) {
+            s += 0x9E3779B97F4A7C15ull;
+            uint64_t z = s;
+            z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+            z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+            z ^= z >> 31;
+            std::swap(p[(size_t)i], p[(size_t)i + (size_t)(z % (uint64_t)(n - i))]);
+            for (int m = 0; m < M; ++m)
+                for (int d = 0; d < Ds; ++d) {
+                    const int col = m * Ds + d;
+                    codewords[((size_t)m * K + i) * Ds + d] = col < D ? vectors[(size_t)p[(size_t)i] * D + col] : 0.0f;
+                }
+        }
+    }
+    dpq::TrainStats st;
+    std::string err;
+    int rc = dpq::train_codebook(vectors, n, D, M, K, Ds, max_iters, codewords, &st, &err);
+    if (rc) return fail(rc, "dpq_train_codebook: " + err);
+    if (stats) {
+        memset(stats, 0, sizeof *stats);
+        stats->iters_run = st.iters_run;
+        stats->converged = st.converged;
+        stats->reseeded = st.reseeded;
+        memcpy(stats->distortion, st.distortion, sizeof st.distortion);
+        stats->gpu_ms = st.gpu_ms;
+        stats->wall_ms = st.wall_ms;
+        stats->rounds_ms = st.rounds_ms;
+        stats->assign_ms = st.assign_ms;
+        stats->update_ms = st.update_ms;
+        stats->repair_ms = st.repair_ms;
+    }
+    return DPQ_OK;
+    });
+}
+
+int dpq_write_codewords(const char* path, const float* codewords, int M, int K, int Ds) {
+    return guarded([&]() -> int {
+    if (!path || !codewords || M < 1 || K < 1 || Ds < 1) return fail(DPQ_ERR_ARG, "bad argument to dpq_write_codewords");
+    FILE* f = fopen(path, "w");
+    if (!f) return fail(DPQ_ERR_IO, std::string("cannot open ") + path);
+    fprintf(f, "%d,%d,%d\n", M, K, Ds);  // pq.cpp:273
+    for (int m = 0; m < M; ++m) {
+        fprintf(f, "%d:\n", m);
+        for (int k = 0; k < K; ++k) {
+            for (int d = 0; d < Ds; ++d) fprintf(f, "%.9g,", (double)codewords[((size_t)m * K + k) * Ds + d]);
+            fprintf(f, "\n");
+        }
+    }
+    if (fclose(f) != 0) return fail(DPQ_ERR_IO, std::string("short write on ") + path);
     return DPQ_OK;
     });
 }

@@ -19,7 +19,8 @@
 // only prints top-1 under -debug); -task pqscan is the reference's uncompressed
 // comparator (main:496-556); -task encode is the encode step of the reference's
 // other binary, pqtree (main.cpp:314-425), so that base vectors -> codes ->
-// index -> query runs from this one tool.
+// index -> query runs from this one tool; -task learn is its learn step
+// (main.cpp:243-277) with this build's own k-means (dpq_train_codebook).
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -67,6 +68,39 @@ int main(int argc, char* argv[]) {
     }
     (void)diff_argument; (void)method; (void)queryset;
 
+    if (task == "learn") {
+        // The other binary's `pqtree -task learn` (main.cpp:243-277): learn.{ext} -> M{M}K{K}codewords.txt.  The
+        // reference shuffles the file's vectors before it takes -N of them (main.cpp:262) and trains with cv::kmeans;
+        // here -N takes the first N vectors as they are and dpq_train_codebook trains with its own stated rules.
+        if (PQ_M <= 0 || PQ_K <= 0 || dataset.empty()) {
+            std::cout << "usage: deltapq -dataset DIR -task learn -m M -k K [-N TRAIN_SIZE] [-ext fvecs|bvecs]" << std::endl;
+            return 2;
+        }
+        const std::string learn_path = dataset + "/learn." + ext;  // main.cpp:251
+        int64_t n_file = 0;
+        int32_t D = 0;
+        int rc = dpq_read_vecs(learn_path.c_str(), ext == "bvecs", &n_file, &D, nullptr, 0);
+        if (rc) return die("ReadTopN", rc);
+        int64_t n = n_file;
+        if (N != -1 && N < n) n = N;
+        std::vector<float> learn((size_t)n * D);
+        rc = dpq_read_vecs(learn_path.c_str(), ext == "bvecs", &n_file, &D, learn.data(), n);
+        if (rc) return die("ReadTopN", rc);
+        const int Ds = (D + PQ_M - 1) / PQ_M;
+        std::vector<float> codewords((size_t)PQ_M * PQ_K * Ds);
+        dpq_train_stats st;
+        rc = dpq_train_codebook(learn.data(), n, D, PQ_M, PQ_K, nullptr, codewords.data(), &st);
+        if (rc) return die("learn", rc);
+        for (int r = 0; r < st.iters_run; ++r) std::cout << "round " << r + 1 << " distortion " << st.distortion[r] << std::endl;
+        const std::string cw_path =
+            dataset + "/M" + std::to_string(PQ_M) + "K" + std::to_string(PQ_K) + "codewords.txt";  // main.cpp:273-275
+        rc = dpq_write_codewords(cw_path.c_str(), codewords.data(), PQ_M, PQ_K, Ds);
+        if (rc) return die("PQ::WriteCodewords", rc);
+        std::cout << "learned M = " << PQ_M << " K = " << PQ_K << " Ds = " << Ds << " from " << n << " vectors in " << st.iters_run
+                  << " rounds" << (st.converged ? " (converged)" : "") << ", " << st.reseeded << " empty clusters reseeded, "
+                  << st.wall_ms / 1000 << " [sec] -> " << cw_path << std::endl;
+        return 0;
+    }
     if (task == "encode") {
         // The other binary's `pqtree -task encode` (main.cpp:314-425): base.{ext} -> PQ codes (nearest
         // codeword per sub-space, PQTree::EncodePlain pq_tree.cpp:215-237) -> codes.bin.plain.M{M}K{K}N{N}.
@@ -173,7 +207,7 @@ int main(int argc, char* argv[]) {
         task = "query";
     }
     if (task != "query" && task != "query_im" && !pqscan) {
-        std::cout << "deltapq (MI355X build): -task query, query_im, pqscan, approx_tree and encode are implemented (batch_query = "
+        std::cout << "deltapq (MI355X build): -task query, query_im, pqscan, approx_tree, encode and learn are implemented (batch_query = "
                      "alias of query); got '" << task
                   << "'" << std::endl;
         return 2;

@@ -28,6 +28,8 @@
  *     ascending (h:2977-2982)                     dists[nq][top_k] float, ascending
  *   decoder[256] argument (main:312-325)        gone (popcount / byte permute on GPU)
  *   PQ::ReadCodewords (pq.cpp:288-312)          dpq_read_codewords
+ *   PQ::Learn (pq.cpp:112-157, cv::kmeans)      dpq_train_codebook (own semantics)
+ *   PQ::WriteCodewords (pq.cpp:267-286)         dpq_write_codewords
  *   ReadTopN(query.{fvecs,bvecs})               dpq_read_vecs
  *     (utils.cpp:14-110)
  *
@@ -265,6 +267,61 @@ int dpq_read_codes_plain_ex(const char* path, int M, int K, int with_id, int64_t
  * (PQTree::EncodePlain pq_tree.cpp:215-237; host buffers in/out). */
 int dpq_encode_pq(const float* vectors, int64_t n, int D, const float* codewords, int M, int K, int Ds, int device,
                   uint8_t* codes_out);
+
+/* ---- codebook learning -----------------------------------------------------
+ * Replaces PQ::Learn (pq.cpp:112-157): Lloyd's k-means per sub-space on the GPU, output float [M][K][Ds] with
+ * Ds = ceil(D / M), the layout dpq_set_codebook and dpq_encode_pq take.  NO REFERENCE SEMANTICS (cv::kmeans): the
+ * reference calls cv::kmeans with KMEANS_PP_CENTERS and three random restarts after a parallel random shuffle
+ * (main.cpp:262), which cannot be reproduced; the rules below are this build's own, restated on the CPU in
+ * tests/_kmeans_restatement.py and met by the GPU bit for bit.  Each sub-space is trained on its own; short vectors
+ * are zero padded as dpq_encode_pq pads them (pq.cpp:114-123).
+ *   Start   use_initial != 0: the caller's codewords.  Otherwise K rows drawn without replacement on the host, the
+ *           same rows for every sub-space: p = 0 .. n-1, s = seed; for i = 0 .. K-1: s += 0x9E3779B97F4A7C15,
+ *           z = s, z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9, z = (z ^ z >> 27) * 0x94D049BB133111EB, z ^= z >> 31
+ *           (splitmix64, mod 2^64), j = i + z % (n - i), swap p[i], p[j]; codeword i = vector p[i].
+ *   Assign  dpq_encode_pq's arithmetic: per codeword `diff = v - c; dist += diff * diff` in fp32, subtract, multiply
+ *           and add rounded separately, dimensions in order, strict `<` (the lowest k wins a tie).  The labels of a
+ *           round are dpq_encode_pq(vectors, the codebook entering that round).
+ *   Stop    a sub-space stops right after an assignment (not the first) that changes no label and leaves no cluster
+ *           empty: its codebook already is the mean of those labels.  It is not touched again.  Otherwise after
+ *           max_iters rounds.
+ *   Update  cluster with members: per dimension the fp64 sum, starting from +0.0, of the members' fp32 values in
+ *           ascending vector index, one add after the other, divided in fp64 by (double)count, rounded once to fp32.
+ *   Empty   with E empty clusters after an assignment, the sub-space's vectors are ranked by (winning distance
+ *           descending, vector index ascending); the j-th empty cluster in ascending k takes the j-th ranked vector's
+ *           sub-vector.  The donor stays in its old cluster's mean of this round.
+ *   Distortion  per round the fp64 sum over vectors and sub-spaces of the winning fp32 distances (a stopped
+ *           sub-space contributes its last assignment's); the order of that sum is not part of the contract.
+ * The same input gives the same bytes, run to run.  opts == NULL: device 0, 25 rounds, seed 0.  DPQ_ERR_ARG, before
+ * any device call: a NULL pointer, D < 1, M < 1 or > 256, K outside 2..256, K > n, n * M >= 2^31, max_iters
+ * outside 1..64, a sub-space whose codewords need more than 160 KB of LDS (Ds > 160, or K * Ds close to 40960).
+ * Without a GPU: DPQ_ERR_NO_DEVICE.  Device memory: about 4 * n * M * (Ds rounded up to 4..160) + 16 * n * M bytes. */
+typedef struct dpq_train_opts {
+    int32_t device;
+    int32_t max_iters;   /* 1..64 */
+    uint64_t seed;       /* of the seeded start */
+    int32_t use_initial; /* != 0: `codewords` holds the start on entry */
+    int32_t reserved[3]; /* 0 */
+} dpq_train_opts;
+
+typedef struct dpq_train_stats {
+    int32_t iters_run;     /* rounds run = entries of distortion[] */
+    int32_t converged;     /* 1: every sub-space stopped by the rule */
+    int64_t reseeded;      /* empty clusters repaired, all rounds and sub-spaces */
+    double distortion[64]; /* per round */
+    double gpu_ms;         /* assign_ms + update_ms + repair_ms (device events) */
+    double wall_ms;        /* the whole call, upload included */
+    double rounds_ms;      /* host clock around the rounds; minus gpu_ms = the host round trips */
+    double assign_ms, update_ms, repair_ms; /* update_ms: label sort + means */
+} dpq_train_stats;
+
+/* codewords: float [M][K][Ds], in (use_initial) and out.  stats may be NULL. */
+int dpq_train_codebook(const float* vectors, int64_t n, int D, int M, int K, const dpq_train_opts* opts, float* codewords,
+                       dpq_train_stats* stats);
+/* PQ::WriteCodewords' text format (pq.cpp:267-286) with nine significant digits, so that dpq_read_codewords and the
+ * reference's `ifs >> float` (pq.cpp:288-312) read back the same bits; the reference's own default precision (six
+ * digits) loses them. */
+int dpq_write_codewords(const char* path, const float* codewords, int M, int K, int Ds);
 
 /* Plain (uncompressed) PQ index for the comparator scan `-task pqscan` (h:2590-2678): raw codes[n][M],
  * distance accumulated in **fp32** in ascending m (h:2658-2662), ids = positions in the code file (no
