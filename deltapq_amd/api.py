@@ -539,6 +539,133 @@ class IdFilter:
         self.close()
 
 
+class FlatIndex:
+    """Raw fp32 vectors [n][D] on one GPU (dpq_flat): exact squared L2 distances with the reference's brute-force
+    arithmetic -- ground truth over all of them (search), or over a candidate list per query (rerank)."""
+
+    def __init__(self, vectors, device=0, id_offset=0):
+        self._lib = _lib.load()
+        self._h = None
+        v = np.ascontiguousarray(vectors, dtype=np.float32)
+        if v.ndim != 2:
+            raise ValueError("vectors must be [n][D]")
+        self.n, self.D, self.id_offset = int(v.shape[0]), int(v.shape[1]), int(id_offset)
+        h = ctypes.c_void_p()
+        check(self._lib.dpq_flat_open(_np_ptr(v), self.n, self.D, device, id_offset, ctypes.byref(h)), "dpq_flat_open")
+        self._h = h
+
+    def _queries(self, queries):
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim != 2 or q.shape[1] != self.D:
+            raise ValueError("queries must be [nq][%d]" % self.D)
+        return q
+
+    def search(self, queries, top_k):
+        """Exact top_k over all vectors -> ids int32 [nq][top_k], dists float32 [nq][top_k] by (distance, id)."""
+        q = self._queries(queries)
+        ids = np.empty((q.shape[0], top_k), dtype=np.int32)
+        dists = np.empty((q.shape[0], top_k), dtype=np.float32)
+        check(self._lib.dpq_flat_search(self._h, _np_ptr(q), q.shape[0], top_k, _np_ptr(ids), _np_ptr(dists)),
+              "dpq_flat_search")
+        return ids, dists
+
+    def set_id_map(self, vec_id):
+        """DFS position -> row of this handle (DeltaTree.vec_id): rerank candidates are then DFS positions."""
+        m = np.ascontiguousarray(vec_id, dtype=np.uint32)
+        check(self._lib.dpq_flat_set_id_map(self._h, _np_ptr(m), m.size), "dpq_flat_set_id_map")
+
+    def rerank(self, queries, cand_ids, top_k):
+        """Exact distances of cand_ids[nq][n_cand] only (negative = padding), the best top_k of them."""
+        q = self._queries(queries)
+        c = np.ascontiguousarray(cand_ids, dtype=np.int32)
+        if c.ndim != 2 or c.shape[0] != q.shape[0]:
+            raise ValueError("cand_ids must be [nq][n_cand]")
+        ids = np.empty((q.shape[0], top_k), dtype=np.int32)
+        dists = np.empty((q.shape[0], top_k), dtype=np.float32)
+        check(self._lib.dpq_flat_rerank(self._h, _np_ptr(q), q.shape[0], _np_ptr(c), c.shape[1], top_k, _np_ptr(ids),
+                                        _np_ptr(dists)), "dpq_flat_rerank")
+        return ids, dists
+
+    def rerank_torch(self, queries, cand_ids, top_k, out_ids=None, out_dists=None):
+        """rerank on device tensors, on torch's current stream (dpq_flat_rerank_device); the results are complete on return."""
+        import torch
+        assert queries.is_cuda and queries.dtype == torch.float32 and queries.is_contiguous() and queries.shape[1] == self.D
+        assert cand_ids.is_cuda and cand_ids.dtype == torch.int32 and cand_ids.is_contiguous()
+        assert cand_ids.shape[0] == queries.shape[0]
+        nq = queries.shape[0]
+        if out_ids is None:
+            out_ids = torch.empty((nq, top_k), dtype=torch.int32, device=queries.device)
+        if out_dists is None:
+            out_dists = torch.empty((nq, top_k), dtype=torch.float32, device=queries.device)
+        stream = torch.cuda.current_stream(queries.device).cuda_stream
+        check(self._lib.dpq_flat_rerank_device(self._h, ctypes.c_void_p(queries.data_ptr()), nq,
+                                               ctypes.c_void_p(cand_ids.data_ptr()), cand_ids.shape[1], top_k,
+                                               ctypes.c_void_p(out_ids.data_ptr()), ctypes.c_void_p(out_dists.data_ptr()),
+                                               ctypes.c_void_p(stream)), "dpq_flat_rerank_device")
+        return out_ids, out_dists
+
+    def close(self):
+        if self._h is not None:
+            self._lib.dpq_flat_close(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def read_vecs_range(path, first, count, ext="fvecs"):
+    """Vectors [first, first + count) of an .fvecs/.bvecs file -> float32 [count][D]."""
+    lib = _lib.load()
+    D = _lib.c_i32()
+    check(lib.dpq_read_vecs_range(path.encode(), int(ext == "bvecs"), first, count, D, None), "dpq_read_vecs_range")
+    out = np.empty((count, D.value), dtype=np.float32)
+    check(lib.dpq_read_vecs_range(path.encode(), int(ext == "bvecs"), first, count, D, _np_ptr(out)), "dpq_read_vecs_range")
+    return out
+
+
+def write_groundtruth(path, ids, dists):
+    """The reference's ground-truth text file (pqbase.cpp:294-312), distances with nine digits (bit-exact on read)."""
+    ids = np.ascontiguousarray(ids, dtype=np.int32)
+    dists = np.ascontiguousarray(dists, dtype=np.float32)
+    assert ids.ndim == 2 and ids.shape == dists.shape
+    check(_lib.load().dpq_write_groundtruth(path.encode(), _np_ptr(ids), _np_ptr(dists), ids.shape[0], ids.shape[1]),
+          "dpq_write_groundtruth")
+
+
+def read_groundtruth(path):
+    """-> ids int32 [nq][top_k], dists float32 [nq][top_k] (pqbase.cpp:313-332)."""
+    lib = _lib.load()
+    nq, k = _lib.c_i32(), _lib.c_i32()
+    check(lib.dpq_read_groundtruth(path.encode(), nq, k, None, None), "dpq_read_groundtruth")
+    ids = np.empty((nq.value, k.value), dtype=np.int32)
+    dists = np.empty((nq.value, k.value), dtype=np.float32)
+    check(lib.dpq_read_groundtruth(path.encode(), nq, k, _np_ptr(ids), _np_ptr(dists)), "dpq_read_groundtruth")
+    return ids, dists
+
+
+def recall(found, truth, k=None, R=None):
+    """Mean over queries of |found[q][:R] & truth[q][:k]| / k, negative ids ignored (dpq_recall).  R = k (the default:
+    k = truth's width, R = k) is the reference's measure (main.cpp:783-796); k = 1 gives 1-recall@R."""
+    found = np.ascontiguousarray(found, dtype=np.int32)
+    truth = np.ascontiguousarray(truth, dtype=np.int32)
+    assert found.ndim == 2 and truth.ndim == 2 and found.shape[0] == truth.shape[0]
+    k = truth.shape[1] if k is None else k
+    R = min(k, found.shape[1]) if R is None else R
+    out = ctypes.c_double()
+    check(_lib.load().dpq_recall(_np_ptr(found), found.shape[1], R, _np_ptr(truth), truth.shape[1], k, found.shape[0], out),
+          "dpq_recall")
+    return out.value
+
+
 def pin_host(arr):
     """Page-lock a numpy array's memory (hipHostRegister through the library): host-to-host batches then overlap their copies."""
     check(_lib.load().dpq_pin_host(_np_ptr(arr), arr.nbytes), "dpq_pin_host")

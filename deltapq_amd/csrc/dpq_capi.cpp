@@ -22,6 +22,7 @@
 
 #include "../../include/deltapq_amd.h"
 #include "dpq_build.h"
+#include "dpq_flat.h"
 #include "dpq_format.h"
 #include "dpq_kernels.h"
 #include "dpq_train.h"
@@ -136,6 +137,23 @@ struct dpq_filter {
     int64_t n_allowed = 0;           // local nodes it allows
     mutable DevBuf<uint32_t> l0_id;  // the level-0 list with the nodes it does not allow as padding (run_batch)
     mutable int l0_n = -1;           // entries of l0_id (-1: not made yet)
+};
+
+// Raw fp32 vectors resident on one GPU (exact search, dpq_flat.hip).  Rows are stored padded to Dp floats.
+struct dpq_flat {
+    int device = 0;
+    int64_t n = 0, id_offset = 0;
+    int D = 0, Dp = 0;
+    DevBuf<float> base;           // [n][Dp]
+    DevBuf<uint32_t> map;         // DFS position -> row (dpq_flat_set_id_map)
+    std::vector<uint32_t> h_map;  // its host copy: dpq_flat_rerank checks candidates on the host
+    // workspaces, grown on demand and kept until dpq_flat_close
+    DevBuf<uint64_t> keys;
+    DevBuf<dpq::FlatQueryState> state;
+    DevBuf<float> d_q, d_dists;
+    DevBuf<int32_t> d_ids, d_cand;
+    DevBuf<uint32_t> flag;
+    size_t keys_n = 0, state_n = 0, q_n = 0, out_n = 0, cand_n = 0;
 };
 
 namespace {
@@ -2149,6 +2167,321 @@ int dpq_write_codewords(const char* path, const float* codewords, int M, int K, 
         }
     }
     if (fclose(f) != 0) return fail(DPQ_ERR_IO, std::string("short write on ") + path);
+    return DPQ_OK;
+    });
+}
+
+// ---- exact search over raw vectors (dpq_flat.hip) ---------------------------------------------------------------
+
+}  // extern "C"
+
+namespace {
+
+template <class B>
+int grow(B& buf, size_t* have, size_t want) {
+    if (want <= *have) return DPQ_OK;
+    *have = 0;
+    int rc = buf.alloc(want);
+    if (!rc) *have = want;
+    return rc;
+}
+
+// Candidates of dpq_flat_rerank*, all device pointers; ends with one flag word read back.
+int flat_rerank_on_device(dpq_flat* f, const float* d_queries, int nq, const int32_t* d_cand, int n_cand, int top_k,
+                          int32_t* d_ids, float* d_dists, hipStream_t stream) {
+    const size_t n_pad = dpq::flat_rerank_keys(n_cand);
+    const int per = (int)std::max<size_t>(1, std::min<size_t>((size_t)nq, ((size_t)64 << 20) / (n_pad * sizeof(uint64_t))));
+    int rc = grow(f->keys, &f->keys_n, (size_t)per * n_pad);
+    if (rc) return rc;
+    if (!f->flag.get() && (rc = f->flag.alloc(1))) return rc;
+    DPQ_HIP(hipMemsetAsync(f->flag, 0, sizeof(uint32_t), stream));
+    for (int q0 = 0; q0 < nq; q0 += per) {
+        const int m = std::min(per, nq - q0);
+        DPQ_HIP(dpq::launch_flat_rerank(f->base, f->n, f->D, f->Dp, d_queries + (size_t)q0 * f->D, m,
+                                        d_cand + (size_t)q0 * n_cand, n_cand, top_k, f->id_offset,
+                                        f->h_map.empty() ? nullptr : f->map.get(), (int64_t)f->h_map.size(), f->keys,
+                                        f->flag, d_ids + (size_t)q0 * top_k, d_dists + (size_t)q0 * top_k, stream));
+    }
+    uint32_t bad = 0;
+    DPQ_HIP(hipMemcpyAsync(&bad, f->flag, sizeof bad, hipMemcpyDeviceToHost, stream));
+    DPQ_HIP(hipStreamSynchronize(stream));
+    if (bad) return fail(DPQ_ERR_ARG, "dpq_flat_rerank: a candidate names no row of this handle");
+    return DPQ_OK;
+}
+
+int flat_rerank_args(const dpq_flat* f, const void* queries, int nq, const void* cand, int n_cand, int top_k,
+                     const void* ids, const void* dists) {
+    if (!f || !queries || !cand || !ids || !dists || nq < 0) return fail(DPQ_ERR_ARG, "dpq_flat_rerank: NULL argument or nq < 0");
+    if (top_k < 1 || top_k > n_cand || n_cand > dpq::kFlatMaxTopK)
+        return fail(DPQ_ERR_ARG, "dpq_flat_rerank: needs 1 <= top_k <= n_cand <= 16384");
+    return DPQ_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dpq_flat_open(const float* vectors, int64_t n, int D, int device, int64_t id_offset, dpq_flat** out) {
+    return guarded([&]() -> int {
+    if (out) *out = nullptr;
+    if (!vectors || !out) return fail(DPQ_ERR_ARG, "dpq_flat_open: NULL argument");
+    if (n < 1) return fail(DPQ_ERR_ARG, "dpq_flat_open: n < 1");
+    if (D < 1 || D > dpq::kFlatMaxD) return fail(DPQ_ERR_ARG, "dpq_flat_open: D outside 1..2048");
+    if (id_offset < 0 || n + id_offset >= ((int64_t)1 << 31))
+        return fail(DPQ_ERR_ARG, "dpq_flat_open: id_offset < 0 or n + id_offset >= 2^31 (ids are int32)");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail(DPQ_ERR_NO_DEVICE, "no HIP device visible; this library has no CPU fallback");
+    if (device < 0 || device >= ndev) return fail(DPQ_ERR_NO_DEVICE, "device ordinal out of range");
+    DPQ_HIP(hipSetDevice(device));
+    std::unique_ptr<dpq_flat> f(new dpq_flat);
+    f->device = device;
+    f->n = n;
+    f->id_offset = id_offset;
+    f->D = D;
+    f->Dp = dpq::flat_padded_d(D);
+    int rc = f->base.alloc((size_t)n * f->Dp);
+    if (rc) return fail(rc, "dpq_flat_open: the vectors do not fit into device memory (" + g_last_error + ")");
+    if (f->Dp == D) {
+        DPQ_HIP(hipMemcpy(f->base, vectors, (size_t)n * D * sizeof(float), hipMemcpyHostToDevice));
+    } else {
+        const int64_t tile = 1 << 18;  // rows per upload; padded on the device
+        DevBuf<float> tmp;
+        if ((rc = tmp.alloc((size_t)std::min(n, tile) * D))) return rc;
+        for (int64_t r0 = 0; r0 < n; r0 += tile) {
+            const int64_t m = std::min(tile, n - r0);
+            DPQ_HIP(hipMemcpy(tmp, vectors + (size_t)r0 * D, (size_t)m * D * sizeof(float), hipMemcpyHostToDevice));
+            DPQ_HIP(dpq::launch_flat_pad_rows(tmp, m, D, f->Dp, f->base.get() + (size_t)r0 * f->Dp, nullptr));
+            DPQ_HIP(hipDeviceSynchronize());
+        }
+    }
+    *out = f.release();
+    return DPQ_OK;
+    });
+}
+
+int dpq_flat_close(dpq_flat* f) {
+    return guarded([&]() -> int {
+    if (!f) return DPQ_OK;
+    hipSetDevice(f->device);
+    delete f;
+    return DPQ_OK;
+    });
+}
+
+int dpq_flat_search(dpq_flat* f, const float* queries, int nq, int top_k, int32_t* ids, float* dists) {
+    return guarded([&]() -> int {
+    if (!f || !queries || !ids || !dists || nq < 0) return fail(DPQ_ERR_ARG, "dpq_flat_search: NULL argument or nq < 0");
+    if (top_k < 1 || top_k > DPQ_FLAT_MAX_TOPK) return fail(DPQ_ERR_ARG, "dpq_flat_search: top_k outside 1..DPQ_FLAT_MAX_TOPK");
+    if (top_k > f->n) return fail(DPQ_ERR_TOPK, "dpq_flat_search: top_k exceeds the number of vectors");
+    if (nq == 0) return DPQ_OK;
+    DPQ_HIP(hipSetDevice(f->device));
+    const int D = f->D, Dp = f->Dp;
+    const int qb = std::min(nq, dpq::flat_query_batch(top_k));
+    int rc = grow(f->keys, &f->keys_n, (size_t)qb * dpq::flat_key_capacity(top_k));
+    if (!rc) rc = grow(f->state, &f->state_n, (size_t)qb);
+    if (!rc) rc = grow(f->d_q, &f->q_n, (size_t)qb * Dp);
+    if (!rc && f->out_n < (size_t)qb * top_k) {
+        f->out_n = 0;
+        rc = f->d_ids.alloc((size_t)qb * top_k);
+        if (!rc) rc = f->d_dists.alloc((size_t)qb * top_k);
+        if (!rc) f->out_n = (size_t)qb * top_k;
+    }
+    if (rc) return rc;
+    std::vector<float> padded;
+    std::vector<dpq::FlatQueryState> st((size_t)qb);
+    for (int q0 = 0; q0 < nq; q0 += qb) {
+        const int m = std::min(qb, nq - q0);
+        const float* src = queries + (size_t)q0 * D;
+        if (Dp != D) {
+            padded.assign((size_t)m * Dp, 0.0f);
+            for (int q = 0; q < m; ++q) memcpy(&padded[(size_t)q * Dp], src + (size_t)q * D, (size_t)D * sizeof(float));
+            src = padded.data();
+        }
+        DPQ_HIP(hipMemcpy(f->d_q, src, (size_t)m * Dp * sizeof(float), hipMemcpyHostToDevice));
+        DPQ_HIP(dpq::launch_flat_search(f->base, f->n, Dp, f->d_q, m, top_k, f->id_offset, f->keys, f->state, f->d_ids,
+                                        f->d_dists, nullptr));
+        DPQ_HIP(hipMemcpy(ids + (size_t)q0 * top_k, f->d_ids, (size_t)m * top_k * sizeof(int32_t), hipMemcpyDeviceToHost));
+        DPQ_HIP(hipMemcpy(dists + (size_t)q0 * top_k, f->d_dists, (size_t)m * top_k * sizeof(float), hipMemcpyDeviceToHost));
+        DPQ_HIP(hipMemcpy(st.data(), f->state, (size_t)m * sizeof(dpq::FlatQueryState), hipMemcpyDeviceToHost));
+        for (int q = 0; q < m; ++q)
+            if (st[(size_t)q].overflow || st[(size_t)q].count != (uint32_t)top_k)
+                return fail(DPQ_ERR_STATE, "dpq_flat_search: internal error: a key buffer overflowed");
+    }
+    return DPQ_OK;
+    });
+}
+
+int dpq_flat_set_id_map(dpq_flat* f, const uint32_t* map, int64_t n_map) {
+    return guarded([&]() -> int {
+    if (!f || !map || n_map < 1 || n_map >= ((int64_t)1 << 31)) return fail(DPQ_ERR_ARG, "dpq_flat_set_id_map: bad argument");
+    for (int64_t i = 0; i < n_map; ++i)
+        if ((int64_t)map[i] >= f->n) return fail(DPQ_ERR_ARG, "dpq_flat_set_id_map: an entry names no row of this handle");
+    DPQ_HIP(hipSetDevice(f->device));
+    DevBuf<uint32_t> d;
+    int rc = d.alloc((size_t)n_map);
+    if (rc) return rc;
+    DPQ_HIP(hipMemcpy(d, map, (size_t)n_map * sizeof(uint32_t), hipMemcpyHostToDevice));
+    f->map = std::move(d);
+    f->h_map.assign(map, map + n_map);
+    return DPQ_OK;
+    });
+}
+
+int dpq_flat_rerank_device(dpq_flat* f, const float* d_queries, int nq, const int32_t* d_cand_ids, int n_cand, int top_k,
+                           int32_t* d_ids, float* d_dists, void* hip_stream) {
+    return guarded([&]() -> int {
+    int rc = flat_rerank_args(f, d_queries, nq, d_cand_ids, n_cand, top_k, d_ids, d_dists);
+    if (rc || nq == 0) return rc;
+    DPQ_HIP(hipSetDevice(f->device));
+    return flat_rerank_on_device(f, d_queries, nq, d_cand_ids, n_cand, top_k, d_ids, d_dists, (hipStream_t)hip_stream);
+    });
+}
+
+int dpq_flat_rerank(dpq_flat* f, const float* queries, int nq, const int32_t* cand_ids, int n_cand, int top_k, int32_t* ids,
+                    float* dists) {
+    return guarded([&]() -> int {
+    int rc = flat_rerank_args(f, queries, nq, cand_ids, n_cand, top_k, ids, dists);
+    if (rc || nq == 0) return rc;
+    const int64_t n_map = (int64_t)f->h_map.size();
+    for (size_t i = 0; i < (size_t)nq * n_cand; ++i) {
+        const int64_t c = cand_ids[i];
+        if (c < 0) continue;
+        bool ok;
+        if (n_map)
+            ok = c < n_map || (c == n_map && (n_map & 1) == 0);
+        else
+            ok = c - f->id_offset >= 0 && c - f->id_offset < f->n;
+        if (!ok) return fail(DPQ_ERR_ARG, "dpq_flat_rerank: a candidate names no row of this handle");
+    }
+    DPQ_HIP(hipSetDevice(f->device));
+    rc = grow(f->d_q, &f->q_n, (size_t)nq * f->D);
+    if (!rc) rc = grow(f->d_cand, &f->cand_n, (size_t)nq * n_cand);
+    if (!rc && f->out_n < (size_t)nq * top_k) {
+        f->out_n = 0;
+        rc = f->d_ids.alloc((size_t)nq * top_k);
+        if (!rc) rc = f->d_dists.alloc((size_t)nq * top_k);
+        if (!rc) f->out_n = (size_t)nq * top_k;
+    }
+    if (rc) return rc;
+    DPQ_HIP(hipMemcpy(f->d_q, queries, (size_t)nq * f->D * sizeof(float), hipMemcpyHostToDevice));
+    DPQ_HIP(hipMemcpy(f->d_cand, cand_ids, (size_t)nq * n_cand * sizeof(int32_t), hipMemcpyHostToDevice));
+    rc = flat_rerank_on_device(f, f->d_q, nq, f->d_cand, n_cand, top_k, f->d_ids, f->d_dists, nullptr);
+    if (rc) return rc;
+    DPQ_HIP(hipMemcpy(ids, f->d_ids, (size_t)nq * top_k * sizeof(int32_t), hipMemcpyDeviceToHost));
+    DPQ_HIP(hipMemcpy(dists, f->d_dists, (size_t)nq * top_k * sizeof(float), hipMemcpyDeviceToHost));
+    return DPQ_OK;
+    });
+}
+
+int dpq_read_vecs_range(const char* path, int is_bvecs, int64_t first, int64_t count, int32_t* D, float* out) {
+    return guarded([&]() -> int {
+    if (!path || !D || first < 0 || count < 0) return fail(DPQ_ERR_ARG, "bad argument to dpq_read_vecs_range");
+    FILE* fp = fopen(path, "rb");
+    if (!fp) return fail(DPQ_ERR_IO, std::string("cannot open ") + path);
+    std::unique_ptr<FILE, int (*)(FILE*)> closer(fp, fclose);
+    int32_t d = 0;
+    if (fread(&d, sizeof d, 1, fp) != 1 || d < 1 || d > (1 << 20)) return fail(DPQ_ERR_IO, std::string("no vector header in ") + path);
+    const int64_t rec = 4 + (int64_t)d * (is_bvecs ? 1 : 4);
+    if (fseeko(fp, 0, SEEK_END) != 0) return fail(DPQ_ERR_IO, std::string("cannot seek in ") + path);
+    const int64_t n_file = (int64_t)ftello(fp) / rec;
+    if (first + count > n_file)
+        return fail(DPQ_ERR_IO, std::string(path) + " holds " + std::to_string(n_file) + " vectors, asked for [" +
+                                    std::to_string(first) + ", " + std::to_string(first + count) + ")");
+    *D = d;
+    if (!out || count == 0) return DPQ_OK;
+    if (fseeko(fp, (off_t)(first * rec), SEEK_SET) != 0) return fail(DPQ_ERR_IO, std::string("cannot seek in ") + path);
+    const int64_t chunk = std::max<int64_t>(1, ((int64_t)8 << 20) / rec);  // records per read
+    std::vector<uint8_t> raw((size_t)(std::min(chunk, count) * rec));
+    for (int64_t r0 = 0; r0 < count; r0 += chunk) {
+        const int64_t m = std::min(chunk, count - r0);
+        if (fread(raw.data(), (size_t)rec, (size_t)m, fp) != (size_t)m) return fail(DPQ_ERR_IO, std::string("short read on ") + path);
+        for (int64_t r = 0; r < m; ++r) {
+            const uint8_t* p = raw.data() + (size_t)(r * rec);
+            int32_t dd;
+            memcpy(&dd, p, 4);
+            if (dd != d) return fail(DPQ_ERR_IO, std::string("a record of another dimension in ") + path);
+            float* o = out + (size_t)(r0 + r) * d;
+            if (is_bvecs)
+                for (int j = 0; j < d; ++j) o[j] = (float)p[4 + j];
+            else
+                memcpy(o, p + 4, (size_t)d * 4);
+        }
+    }
+    return DPQ_OK;
+    });
+}
+
+int dpq_write_groundtruth(const char* path, const int32_t* ids, const float* dists, int nq, int top_k) {
+    return guarded([&]() -> int {
+    if (!path || !ids || !dists || nq < 0 || top_k < 1) return fail(DPQ_ERR_ARG, "bad argument to dpq_write_groundtruth");
+    FILE* fp = fopen(path, "w");
+    if (!fp) return fail(DPQ_ERR_IO, std::string("cannot open ") + path);
+    fprintf(fp, "%d,%d\n", nq, top_k);  // pqbase.cpp:300
+    for (int q = 0; q < nq; ++q) {
+        for (int r = 0; r < top_k; ++r)
+            fprintf(fp, "%d,%.9g,", ids[(size_t)q * top_k + r], (double)dists[(size_t)q * top_k + r]);  // pqbase.cpp:308
+        fprintf(fp, "\n");
+    }
+    if (fclose(fp) != 0) return fail(DPQ_ERR_IO, std::string("short write on ") + path);
+    return DPQ_OK;
+    });
+}
+
+int dpq_read_groundtruth(const char* path, int32_t* nq, int32_t* top_k, int32_t* ids, float* dists) {
+    return guarded([&]() -> int {
+    if (!path || !nq || !top_k || (ids == nullptr) != (dists == nullptr)) return fail(DPQ_ERR_ARG, "bad argument to dpq_read_groundtruth");
+    FILE* fp = fopen(path, "rb");
+    if (!fp) return fail(DPQ_ERR_IO, std::string("cannot open ") + path);
+    std::unique_ptr<FILE, int (*)(FILE*)> closer(fp, fclose);
+    int a = 0, b = 0;
+    if (fscanf(fp, "%d ,%d", &a, &b) != 2 || a < 0 || b < 1) return fail(DPQ_ERR_IO, std::string("no `nq,top_k` line in ") + path);
+    *nq = a;
+    *top_k = b;
+    if (!ids) return DPQ_OK;
+    std::string text;
+    char blk[1 << 16];
+    size_t got;
+    while ((got = fread(blk, 1, sizeof blk, fp)) > 0) text.append(blk, got);
+    const char* p = text.c_str();
+    for (size_t i = 0; i < (size_t)a * b; ++i) {  // pqbase.cpp:328: id, distance, each followed by one separator
+        char* e = nullptr;
+        const long long id = strtoll(p, &e, 10);
+        if (e == p || *e != ',') return fail(DPQ_ERR_IO, std::string("malformed entry in ") + path);
+        p = e + 1;
+        const float d = strtof(p, &e);
+        if (e == p || *e != ',') return fail(DPQ_ERR_IO, std::string("malformed entry in ") + path);
+        p = e + 1;
+        ids[i] = (int32_t)id;
+        dists[i] = d;
+    }
+    return DPQ_OK;
+    });
+}
+
+int dpq_recall(const int32_t* found, int found_stride, int R, const int32_t* truth, int truth_stride, int k, int nq,
+               double* recall) {
+    return guarded([&]() -> int {
+    if (!found || !truth || !recall || R < 1 || k < 1 || nq < 1 || found_stride < R || truth_stride < k)
+        return fail(DPQ_ERR_ARG, "bad argument to dpq_recall");
+    int64_t hits = 0;
+    std::vector<int32_t> t;
+    for (int q = 0; q < nq; ++q) {
+        t.assign(truth + (size_t)q * truth_stride, truth + (size_t)q * truth_stride + k);
+        std::sort(t.begin(), t.end());
+        t.erase(std::unique(t.begin(), t.end()), t.end());
+        while (!t.empty() && t.front() < 0) t.erase(t.begin());  // padding
+        std::vector<char> hit(t.size(), 0);
+        for (int r = 0; r < R; ++r) {
+            const int32_t id = found[(size_t)q * found_stride + r];
+            if (id < 0) continue;
+            const size_t at = (size_t)(std::lower_bound(t.begin(), t.end(), id) - t.begin());
+            if (at == t.size() || t[at] != id || hit[at]) continue;  // an id found twice counts once
+            hit[at] = 1;
+            ++hits;
+        }
+    }
+    *recall = (double)hits / ((double)nq * k);
     return DPQ_OK;
     });
 }

@@ -20,8 +20,14 @@
 // comparator (main:496-556); -task encode is the encode step of the reference's
 // other binary, pqtree (main.cpp:314-425), so that base vectors -> codes ->
 // index -> query runs from this one tool; -task learn is its learn step
-// (main.cpp:243-277) with this build's own k-means (dpq_train_codebook).
+// (main.cpp:243-277) with this build's own k-means (dpq_train_codebook); -task groundtruth and -task recall are
+// its brute-force ground truth (main.cpp:569-669) and recall measure (main.cpp:727-803) over raw vectors, the
+// latter with an optional exact re-rank of the PQ answer (-rerank R).
+#include <sys/stat.h>
+
+#include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -45,7 +51,8 @@ static int die(const char* where, int rc) {
 int main(int argc, char* argv[]) {
     std::string dataset, queryset, task = "approx_tree", ext = "fvecs", out_path;
     int query_size = -1, top_k = 1, diff_argument = 1, debug = 0, max_height_folds = 1, method = 1;
-    int PQ_M = 0, PQ_K = 0, gpus = 1;
+    int PQ_M = 0, PQ_K = 0, gpus = 1, gt_topk = -1, rerank = 0;
+    bool topk_given = false;
     long long N = -1;
     for (int i = 0; i < argc; i++) {  // main:26-70: hand-rolled scan, no validation
         std::string arg = argv[i];
@@ -53,7 +60,9 @@ int main(int argc, char* argv[]) {
         if (arg == "-dataset") dataset = nx;
         if (arg == "-queryset") queryset = nx;
         if (arg == "-task") task = nx;
-        if (arg == "-topk") top_k = atoi(nx);
+        if (arg == "-topk") top_k = atoi(nx), topk_given = true;
+        if (arg == "-gt_topk") gt_topk = atoi(nx);
+        if (arg == "-rerank") rerank = atoi(nx);
         if (arg == "-N") N = atoll(nx);
         if (arg == "-diff") diff_argument = atoi(nx);
         if (arg == "-query_size") query_size = atoi(nx);
@@ -195,6 +204,223 @@ int main(int argc, char* argv[]) {
         std::cout << "WARNING: Just built an index. no query processed." << std::endl;                 // main:140
         return 0;
     }
+    if (task == "groundtruth") {
+        // The other binary's `pqtree -task groundtruth` (main.cpp:569-669): brute force over base.{ext}, streamed in
+        // parts; every part is a dpq_flat handle with its own id offset, the partial lists meet in dpq_merge_topk_host.
+        if (dataset.empty() || !topk_given || top_k < 1 || query_size < 1) {
+            std::cout << "usage: deltapq -dataset DIR -task groundtruth -topk K -query_size Q [-N N] [-ext fvecs|bvecs]" << std::endl;
+            return 2;
+        }
+        const bool bvecs = ext == "bvecs";
+        const std::string q_path = dataset + "/query." + ext, base_path = dataset + "/base." + ext;
+        int64_t nq_file = 0, n_file = 0;
+        int32_t D = 0, Db = 0;
+        int rc = dpq_read_vecs(q_path.c_str(), bvecs, &nq_file, &D, nullptr, 0);
+        if (rc) return die("ReadTopN", rc);
+        if (query_size > nq_file) {
+            std::cout << "-query_size " << query_size << " exceeds the " << nq_file << " available queries" << std::endl;
+            return 1;
+        }
+        const int nq = query_size;
+        std::vector<float> queries((size_t)nq * D);
+        rc = dpq_read_vecs(q_path.c_str(), bvecs, &nq_file, &D, queries.data(), nq);
+        if (rc) return die("ReadTopN", rc);
+        rc = dpq_read_vecs(base_path.c_str(), bvecs, &n_file, &Db, nullptr, 0);
+        if (rc) return die("ItrReader", rc);
+        if (Db != D) {
+            std::cout << "query dimension " << D << " != base dimension " << Db << std::endl;
+            return 1;
+        }
+        int64_t n = n_file;
+        if (N != -1 && N < n) n = N;
+        if (top_k > n || top_k > DPQ_FLAT_MAX_TOPK) {
+            std::cout << "-topk " << top_k << " outside 1.." << std::min<int64_t>(n, DPQ_FLAT_MAX_TOPK) << std::endl;
+            return 1;
+        }
+        if (dpq_device_count() < 1) {
+            std::cout << "no GPU visible: this build has no CPU search path" << std::endl;
+            return 1;
+        }
+        int64_t part_rows = std::max<int64_t>(1, ((int64_t)1 << 29) / D);  // at most 2 GB of floats per part
+        if (const char* dev = getenv("DPQ_DEV"))
+            if (atoi(dev) != 0)
+                if (const char* e = getenv("DPQ_GT_PART_ROWS")) part_rows = std::max<int64_t>(1, atoll(e));  // developer knob
+        const size_t list = (size_t)nq * top_k;
+        std::vector<int32_t> two_ids(2 * list, -1), out_ids(list);  // [0] the answer so far, [1] the part's
+        std::vector<float> two_dists(2 * list, INFINITY), out_dists(list);
+        std::vector<float> part;
+        std::vector<int32_t> p_ids;
+        std::vector<float> p_dists;
+        const double t0 = Elapsed();
+        int n_parts = 0;
+        for (int64_t r0 = 0; r0 < n; r0 += part_rows, ++n_parts) {
+            const int64_t rows = std::min(part_rows, n - r0);
+            part.resize((size_t)rows * D);
+            rc = dpq_read_vecs_range(base_path.c_str(), bvecs, r0, rows, &Db, part.data());
+            if (rc) return die("ItrReader", rc);
+            dpq_flat* f = nullptr;
+            rc = dpq_flat_open(part.data(), rows, D, 0, r0, &f);
+            if (rc) return die("dpq_flat_open", rc);
+            const int kk = (int)std::min<int64_t>(top_k, rows);  // a short last part gives a short list, padded
+            p_ids.resize((size_t)nq * kk);
+            p_dists.resize((size_t)nq * kk);
+            rc = dpq_flat_search(f, queries.data(), nq, kk, p_ids.data(), p_dists.data());
+            if (rc) return die("dpq_flat_search", rc);
+            dpq_flat_close(f);
+            for (int q = 0; q < nq; ++q)
+                for (int r = 0; r < top_k; ++r) {
+                    two_ids[list + (size_t)q * top_k + r] = r < kk ? p_ids[(size_t)q * kk + r] : -1;
+                    two_dists[list + (size_t)q * top_k + r] = r < kk ? p_dists[(size_t)q * kk + r] : INFINITY;
+                }
+            rc = dpq_merge_topk_host(two_ids.data(), two_dists.data(), 2, nq, top_k, out_ids.data(), out_dists.data());
+            if (rc) return die("dpq_merge_topk_host", rc);
+            std::copy(out_ids.begin(), out_ids.end(), two_ids.begin());
+            std::copy(out_dists.begin(), out_dists.end(), two_dists.begin());
+        }
+        const double elapsed = Elapsed() - t0;
+        std::cout << n << " base vectors in " << n_parts << " part(s)" << std::endl;
+        std::cout << elapsed / (double)nq * 1000 << " [msec/query] " << std::endl;
+        const std::string gt_dir = dataset + "/groundtruth";
+        mkdir(gt_dir.c_str(), 0777);  // (exists already: fine)
+        const std::string gt_path = gt_dir + "/N" + std::to_string(n) + "Top" + std::to_string(top_k) + ".txt";  // main.cpp:663-667
+        rc = dpq_write_groundtruth(gt_path.c_str(), out_ids.data(), out_dists.data(), nq, top_k);
+        if (rc) return die("write_groundtruth", rc);
+        std::cout << gt_path << std::endl;
+        return 0;
+    }
+    if (task == "recall") {
+        // The other binary's `pqtree -task recall` (main.cpp:727-803) over this engine's answer: DTC query, DFS
+        // positions -> vector ids (QNode.vec_id), against groundtruth/N{N}Top{G}.txt; -rerank R re-scores the PQ top-R
+        // against base.{ext} (main.cpp:898-939) and reports the recall of that answer too.
+        if (PQ_M <= 0 || PQ_K <= 0 || dataset.empty() || N < 1 || !topk_given || top_k < 1 || query_size < 1) {
+            std::cout << "usage: deltapq -dataset DIR -task recall -m M -k K -N N -query_size Q -topk K [-gt_topk G] [-rerank R]"
+                         " [-ext fvecs|bvecs]" << std::endl;
+            return 2;
+        }
+        if (gt_topk < 0) gt_topk = top_k;
+        if (gt_topk < top_k) {
+            std::cout << "-gt_topk " << gt_topk << " is below -topk " << top_k << std::endl;
+            return 1;
+        }
+        if (rerank != 0 && (rerank < top_k || rerank > 2048)) {
+            std::cout << "-rerank " << rerank << " outside " << top_k << "..2048" << std::endl;
+            return 1;
+        }
+        const bool bvecs = ext == "bvecs";
+        const std::string cw_path = dataset + "/M" + std::to_string(PQ_M) + "K" + std::to_string(PQ_K) + "codewords.txt";
+        int32_t cM = 0, cK = 0, cDs = 0;
+        int rc = dpq_read_codewords(cw_path.c_str(), &cM, &cK, &cDs, nullptr);
+        if (rc) return die("ReadCodewords", rc);
+        std::vector<float> codewords((size_t)cM * cK * cDs);
+        rc = dpq_read_codewords(cw_path.c_str(), &cM, &cK, &cDs, codewords.data());
+        if (rc) return die("ReadCodewords", rc);
+        if (cM != PQ_M || cK != PQ_K) {
+            std::cout << "codewords file is M=" << cM << " K=" << cK << std::endl;
+            return 1;
+        }
+        const std::string q_path = dataset + "/query." + ext;
+        int64_t nq_file = 0;
+        int32_t D = 0;
+        rc = dpq_read_vecs(q_path.c_str(), bvecs, &nq_file, &D, nullptr, 0);
+        if (rc) return die("ReadTopN", rc);
+        if (query_size > nq_file) {
+            std::cout << "-query_size " << query_size << " exceeds the " << nq_file << " available queries" << std::endl;
+            return 1;
+        }
+        const int nq = query_size;
+        std::vector<float> queries((size_t)nq * D);
+        rc = dpq_read_vecs(q_path.c_str(), bvecs, &nq_file, &D, queries.data(), nq);
+        if (rc) return die("ReadTopN", rc);
+        if (D != PQ_M * cDs) {
+            std::cout << "query dimension " << D << " != M*Ds = " << PQ_M * cDs << std::endl;
+            return 1;
+        }
+        const std::string gt_path = dataset + "/groundtruth/N" + std::to_string(N) + "Top" + std::to_string(gt_topk) + ".txt";
+        int32_t g_nq = 0, g_k = 0;
+        rc = dpq_read_groundtruth(gt_path.c_str(), &g_nq, &g_k, nullptr, nullptr);
+        if (rc) return die("read_groundtruth", rc);
+        if (g_nq < nq || g_k < top_k) {
+            std::cout << gt_path << " holds " << g_nq << " x " << g_k << ", needed " << nq << " x " << top_k << std::endl;
+            return 1;
+        }
+        std::vector<int32_t> truth((size_t)g_nq * g_k);
+        std::vector<float> truth_d((size_t)g_nq * g_k);
+        rc = dpq_read_groundtruth(gt_path.c_str(), &g_nq, &g_k, truth.data(), truth_d.data());
+        if (rc) return die("read_groundtruth", rc);
+        std::vector<uint32_t> vec_id((size_t)N);
+        const std::string nodes_path = dataset + "/M" + std::to_string(PQ_M) + "K" + std::to_string(PQ_K) +
+                                       "_Approx_TreeNodesDFS_N" + std::to_string(N);
+        rc = dpq_read_qnode_ids(nodes_path.c_str(), N, vec_id.data());
+        if (rc) return die("read TreeNodesDFS", rc);
+        if (dpq_device_count() < 1) {
+            std::cout << "no GPU visible: this build has no CPU query path" << std::endl;
+            return 1;
+        }
+        char fname[4096];
+        rc = dpq_dtc_file_name(dataset.c_str(), PQ_M, PQ_K, N, fname, sizeof fname);
+        if (rc) return die("file name", rc);
+        dpq_index* idx = nullptr;
+        dpq_open_opts o;
+        memset(&o, 0, sizeof o);
+        rc = dpq_open_file(fname, PQ_M, PQ_K, &o, &idx);
+        if (rc) return die("dpq_open_file", rc);
+        rc = dpq_set_codebook(idx, codewords.data(), cDs);
+        if (rc) return die("dpq_set_codebook", rc);
+        const int R = rerank ? rerank : top_k;
+        std::vector<int32_t> pos((size_t)nq * R), found((size_t)nq * R);
+        std::vector<float> pq_d((size_t)nq * R);
+        const double t0 = Elapsed();
+        for (int q0 = 0; q0 < nq; q0 += 1024) {
+            const int m = std::min(1024, nq - q0);
+            rc = dpq_query_batch(idx, queries.data() + (size_t)q0 * D, m, R, pos.data() + (size_t)q0 * R, pq_d.data() + (size_t)q0 * R);
+            if (rc) return die("dpq_query_batch", rc);
+        }
+        std::cout << (Elapsed() - t0) / (double)nq * 1000 << " [msec/query] " << std::endl;
+        dpq_close(idx);
+        for (size_t i = 0; i < found.size(); ++i) {
+            int64_t p = pos[i];
+            if (p == N && N % 2 == 0) p = N - 1;  // the even-N id of the last DFS node (h:2949, 2970)
+            found[i] = p < 0 || p >= N ? -1 : (int32_t)vec_id[(size_t)p];
+        }
+        double rec = 0;
+        rc = dpq_recall(found.data(), R, top_k, truth.data(), g_k, top_k, nq, &rec);
+        if (rc) return die("dpq_recall", rc);
+        char line[128];
+        snprintf(line, sizeof line, "recall@%d = %.6f", top_k, rec);
+        std::cout << line << std::endl;
+        if (rerank) {
+            std::vector<float> base((size_t)N * D);
+            int32_t Db = 0;
+            rc = dpq_read_vecs_range((dataset + "/base." + ext).c_str(), bvecs, 0, N, &Db, nullptr);
+            if (!rc && Db != D) {
+                std::cout << "query dimension " << D << " != base dimension " << Db << std::endl;
+                return 1;
+            }
+            if (!rc) rc = dpq_read_vecs_range((dataset + "/base." + ext).c_str(), bvecs, 0, N, &Db, base.data());
+            if (rc) return die("ItrReader", rc);
+            dpq_flat* f = nullptr;
+            rc = dpq_flat_open(base.data(), N, D, 0, 0, &f);
+            if (rc == DPQ_ERR_NOMEM) {
+                std::cout << "-rerank: base." << ext << " (" << N << " x " << D << ") does not fit into device memory" << std::endl;
+                return 1;
+            }
+            if (rc) return die("dpq_flat_open", rc);
+            rc = dpq_flat_set_id_map(f, vec_id.data(), N);
+            if (rc) return die("dpq_flat_set_id_map", rc);
+            std::vector<int32_t> r_ids((size_t)nq * top_k);
+            std::vector<float> r_d((size_t)nq * top_k);
+            const double t1 = Elapsed();
+            rc = dpq_flat_rerank(f, queries.data(), nq, pos.data(), R, top_k, r_ids.data(), r_d.data());
+            if (rc) return die("dpq_flat_rerank", rc);
+            std::cout << "re-rank " << (Elapsed() - t1) / (double)nq * 1000 << " [msec/query] " << std::endl;
+            dpq_flat_close(f);
+            rc = dpq_recall(r_ids.data(), top_k, top_k, truth.data(), g_k, top_k, nq, &rec);
+            if (rc) return die("dpq_recall", rc);
+            snprintf(line, sizeof line, "reranked recall@%d = %.6f", top_k, rec);
+            std::cout << line << std::endl;
+        }
+        return 0;
+    }
     const bool pqscan = task == "pqscan";  // main:496-556: uncompressed comparator over codes.bin.plain
     // -task batch_query (main:351-420) is accepted as an alias of -task query: the engine behind `query`
     // already decodes every chunk once for a whole batch of queries, with the -task query arithmetic and ids
@@ -207,7 +433,7 @@ int main(int argc, char* argv[]) {
         task = "query";
     }
     if (task != "query" && task != "query_im" && !pqscan) {
-        std::cout << "deltapq (MI355X build): -task query, query_im, pqscan, approx_tree, encode and learn are implemented (batch_query = "
+        std::cout << "deltapq (MI355X build): -task query, query_im, pqscan, approx_tree, encode, learn, groundtruth and recall are implemented (batch_query = "
                      "alias of query); got '" << task
                   << "'" << std::endl;
         return 2;

@@ -1,0 +1,391 @@
+// dpq_flat.hip -- exact L2 distances between fp32 queries and fp32 base vectors on gfx950.
+//
+// The arithmetic (include/deltapq_amd.h, "exact search"): per dimension, in ascending order, t = v[d] - q[d] and
+// s = t * t in fp32, each rounded on its own (the build passes -ffp-contract=off), then acc += (double)s on an fp64
+// accumulator that starts at +0.0; the reported distance is (float)acc.  One lane owns one distance from the first
+// dimension to the last, so the order of the sum is the reference's (main.cpp:150-156) and the bits are too.
+//
+//   flat_dist_kernel      a workgroup takes 64 queries x 64 vectors; both tiles go through LDS in slices of 32
+//                         dimensions, transposed so that a lane reads its four queries and four vectors as two
+//                         16-byte LDS loads; 16 fp64 accumulators per lane.  Distances at or below the query's
+//                         threshold are appended as keys (distance bits << 32 | id) to the query's buffer.
+//   flat_select_kernel    when a buffer is filling up: radix select of the top_k-th key, compaction in place, the
+//                         threshold lowered to that key.
+//   flat_sort_emit_kernel bitonic sort of a query's keys in LDS, duplicates dropped, ids and distances written.
+//   flat_rerank_kernel    a lane per candidate; a wavefront fetches its 64 rows with 16-byte loads into LDS, 32
+//                         dimensions at a time, and every lane then walks its own row in order.
+#include "dpq_flat.h"
+
+#include <algorithm>
+#include <atomic>
+
+namespace dpq {
+namespace {
+
+constexpr int TQ = 64, TV = 64;  // queries and vectors of a workgroup's tile
+constexpr int DC = 32;           // dimensions staged at a time
+constexpr int LD = TV + 4;       // LDS row stride in floats (16-byte aligned; spreads the transposed writes)
+constexpr uint64_t kNoKey = ~0ull;
+constexpr int kSelThreads = 1024;
+
+__device__ __forceinline__ uint64_t make_key(double acc, uint32_t id) {
+    return ((uint64_t)__float_as_uint((float)acc) << 32) | id;
+}
+
+__global__ void flat_init_state_kernel(FlatQueryState* state, int nq) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q < nq) {
+        state[q].count = 0;
+        state[q].overflow = 0;
+        state[q].thr = kNoKey;
+    }
+}
+
+__global__ void flat_pad_rows_kernel(const float* in, int64_t rows, int D, int Dp, float* out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= rows * Dp) return;
+    const int64_t r = i / Dp;
+    const int d = (int)(i - r * Dp);
+    out[i] = d < D ? in[r * D + d] : 0.0f;
+}
+
+// grid (vector tiles of the stripe, query tiles), 256 threads: thread (tx, ty) owns queries ty*4.. x vectors tx*4..
+__global__ __launch_bounds__(256) void flat_dist_kernel(const float* __restrict__ base, int64_t row0, int rows, int Dp,
+                                                        const float* __restrict__ queries, int nq, int64_t id_offset,
+                                                        uint64_t* __restrict__ keys, int cap, FlatQueryState* state) {
+    __shared__ float qs[DC][LD];
+    __shared__ float vs[DC][LD];
+    __shared__ uint32_t cnt[TQ];
+    __shared__ uint32_t pos0[TQ];
+    __shared__ uint64_t thr[TQ];
+    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+    const int v0 = blockIdx.x * TV, q0 = blockIdx.y * TQ;
+    const int sr = tid >> 3, sj = (tid & 7) * 4;  // staging: row sr (and sr + 32), dimensions sj .. sj + 3 of the slice
+
+    double acc[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = 0.0;
+
+    for (int d0 = 0; d0 < Dp; d0 += DC) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int r = sr + 32 * h, d = d0 + sj;
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f), q = v;
+            if (v0 + r < rows && d < Dp) v = *reinterpret_cast<const float4*>(base + (size_t)(row0 + v0 + r) * Dp + d);
+            if (q0 + r < nq && d < Dp) q = *reinterpret_cast<const float4*>(queries + (size_t)(q0 + r) * Dp + d);
+            vs[sj + 0][r] = v.x; vs[sj + 1][r] = v.y; vs[sj + 2][r] = v.z; vs[sj + 3][r] = v.w;
+            qs[sj + 0][r] = q.x; qs[sj + 1][r] = q.y; qs[sj + 2][r] = q.z; qs[sj + 3][r] = q.w;
+        }
+        __syncthreads();
+        const int dc = min(DC, Dp - d0);
+#pragma unroll 4
+        for (int d = 0; d < dc; ++d) {
+            const float4 q4 = *reinterpret_cast<const float4*>(&qs[d][ty * 4]);
+            const float4 v4 = *reinterpret_cast<const float4*>(&vs[d][tx * 4]);
+            const float qa[4] = {q4.x, q4.y, q4.z, q4.w}, va[4] = {v4.x, v4.y, v4.z, v4.w};
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const float t = va[j] - qa[i];
+                    const float s = t * t;
+                    acc[i][j] += (double)s;
+                }
+        }
+        __syncthreads();
+    }
+
+    if (tid < TQ) {
+        cnt[tid] = 0;
+        thr[tid] = q0 + tid < nq ? state[q0 + tid].thr : 0;
+    }
+    __syncthreads();
+    uint64_t key[4][4];
+    uint32_t slot[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int ql = ty * 4 + i, v = v0 + tx * 4 + j;
+            key[i][j] = make_key(acc[i][j], (uint32_t)(id_offset + row0 + v));
+            const bool pass = q0 + ql < nq && v < rows && key[i][j] <= thr[ql];
+            slot[i][j] = pass ? atomicAdd(&cnt[ql], 1u) : 0xffffffffu;
+        }
+    __syncthreads();
+    if (tid < TQ && cnt[tid]) pos0[tid] = atomicAdd(&state[q0 + tid].count, cnt[tid]);
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (slot[i][j] == 0xffffffffu) continue;
+            const int ql = ty * 4 + i;
+            const uint32_t pos = pos0[ql] + slot[i][j];
+            if (pos < (uint32_t)cap)
+                keys[(size_t)(q0 + ql) * cap + pos] = key[i][j];
+            else
+                state[q0 + ql].overflow = 1;
+        }
+}
+
+// exclusive prefix sum over the 1024 threads of a workgroup; *total = the sum.  wsum: 16 words of LDS.
+__device__ __forceinline__ uint32_t block_scan_1024(uint32_t v, uint32_t* wsum, uint32_t* total) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    uint32_t inc = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t t = __shfl_up(inc, o);
+        if (lane >= o) inc += t;
+    }
+    if (lane == 63) wsum[w] = inc;
+    __syncthreads();
+    uint32_t woff = 0, tot = 0;
+    for (int k = 0; k < 16; ++k) {
+        const uint32_t s = wsum[k];
+        if (k < w) woff += s;
+        tot += s;
+    }
+    __syncthreads();
+    *total = tot;
+    return woff + inc - v;
+}
+
+// One workgroup per query.  With more than `limit` (>= top_k) keys in the buffer: keep the top_k smallest, in place,
+// and lower the threshold to the top_k-th.  Keys of one query are distinct (distinct ids), so "<= the k-th" is k keys.
+__global__ __launch_bounds__(kSelThreads) void flat_select_kernel(uint64_t* keys, int cap, FlatQueryState* state, int top_k,
+                                                                  uint32_t limit) {
+    __shared__ uint32_t hist[256];
+    __shared__ uint32_t wsum[16];
+    __shared__ uint64_t s_prefix;
+    __shared__ uint32_t s_rem;
+    const int q = blockIdx.x, tid = threadIdx.x;
+    uint64_t* buf = keys + (size_t)q * cap;
+    const uint32_t cnt = min(state[q].count, (uint32_t)cap);
+    if (cnt <= limit) return;
+    uint64_t prefix = 0, mask = 0;
+    uint32_t rem = (uint32_t)top_k;  // rank, from 1, of the wanted key among those that match the prefix
+    for (int shift = 56; shift >= 0; shift -= 8) {
+        if (tid < 256) hist[tid] = 0;
+        __syncthreads();
+        for (uint32_t i = tid; i < cnt; i += kSelThreads) {
+            const uint64_t k = buf[i];
+            if ((k & mask) == prefix) atomicAdd(&hist[(uint32_t)(k >> shift) & 255u], 1u);
+        }
+        __syncthreads();
+        if (tid == 0) {
+            uint32_t cum = 0;
+            for (int b = 0; b < 256; ++b) {
+                if (cum + hist[b] >= rem) {
+                    s_prefix = prefix | ((uint64_t)b << shift);
+                    s_rem = rem - cum;
+                    break;
+                }
+                cum += hist[b];
+            }
+        }
+        __syncthreads();
+        prefix = s_prefix;
+        rem = s_rem;
+        mask |= 0xffull << shift;
+        __syncthreads();
+    }
+    const uint64_t kth = prefix;
+    uint32_t out = 0;
+    for (uint32_t b = 0; b < cnt; b += kSelThreads) {
+        // a round reads [b, b + 1024) before the barrier inside the scan and writes below b + 1024 after it
+        const uint32_t i = b + tid;
+        const uint64_t k = i < cnt ? buf[i] : kNoKey;
+        const uint32_t keep = i < cnt && k <= kth;
+        uint32_t total;
+        const uint32_t off = block_scan_1024(keep, wsum, &total);
+        if (keep) buf[out + off] = k;
+        out += total;
+    }
+    if (tid == 0) {
+        state[q].count = out;  // == top_k
+        state[q].thr = kth;
+    }
+}
+
+// One workgroup per query: sort its keys (n_keys of them, or state[q].count) in LDS, drop repeats, write the first
+// top_k as (id, distance); rows are padded with -1 / +inf.  kNoKey entries are padding.  n_pad: a power of two.
+__global__ __launch_bounds__(kSelThreads) void flat_sort_emit_kernel(const uint64_t* __restrict__ keys, size_t stride,
+                                                                     const FlatQueryState* state, int n_keys, int n_pad,
+                                                                     int top_k, int32_t* __restrict__ ids,
+                                                                     float* __restrict__ dists) {
+    extern __shared__ uint64_t sk[];
+    __shared__ uint32_t wsum[16];
+    const int q = blockIdx.x, tid = threadIdx.x;
+    const int cnt = state ? (int)min(state[q].count, (uint32_t)n_keys) : n_keys;
+    for (int i = tid; i < n_pad; i += kSelThreads) sk[i] = i < cnt ? keys[(size_t)q * stride + i] : kNoKey;
+    __syncthreads();
+    for (int k = 2; k <= n_pad; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int i = tid; i < n_pad; i += kSelThreads) {
+                const int x = i ^ j;
+                if (x > i) {
+                    const uint64_t a = sk[i], b = sk[x];
+                    if ((a > b) == ((i & k) == 0)) {
+                        sk[i] = b;
+                        sk[x] = a;
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    const int per = (n_pad + kSelThreads - 1) / kSelThreads;
+    const int lo = min(n_pad, tid * per), hi = min(n_pad, lo + per);
+    uint32_t u = 0;
+    for (int i = lo; i < hi; ++i) u += sk[i] != kNoKey && (i == 0 || sk[i] != sk[i - 1]);
+    uint32_t total;
+    uint32_t pos = block_scan_1024(u, wsum, &total);
+    for (int i = lo; i < hi; ++i)
+        if (sk[i] != kNoKey && (i == 0 || sk[i] != sk[i - 1])) {
+            if (pos < (uint32_t)top_k) {
+                ids[(size_t)q * top_k + pos] = (int32_t)(uint32_t)(sk[i] & 0xffffffffu);
+                dists[(size_t)q * top_k + pos] = __uint_as_float((uint32_t)(sk[i] >> 32));
+            }
+            ++pos;
+        }
+    for (int r = (int)total + tid; r < top_k; r += kSelThreads) {
+        ids[(size_t)q * top_k + r] = -1;
+        dists[(size_t)q * top_k + r] = __uint_as_float(0x7f800000u);
+    }
+}
+
+// grid (candidate groups of 256, queries), 256 threads: lane = candidate.
+__global__ __launch_bounds__(256) void flat_rerank_kernel(const float* __restrict__ base, int64_t n, int D, int Dp,
+                                                          const float* __restrict__ queries,
+                                                          const int32_t* __restrict__ cand, int n_cand, int n_pad,
+                                                          int64_t id_offset, const uint32_t* __restrict__ map,
+                                                          int64_t n_map, uint64_t* __restrict__ keys, uint32_t* flag) {
+    __shared__ float qv[kFlatMaxD];
+    __shared__ float tile[4][64][DC + 1];
+    const int q = blockIdx.y, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    for (int d = tid; d < Dp; d += 256) qv[d] = d < D ? queries[(size_t)q * D + d] : 0.0f;
+    const int ci = blockIdx.x * 256 + tid;
+    int row = -1;
+    if (ci < n_cand) {
+        const int32_t c = cand[(size_t)q * n_cand + ci];
+        if (c >= 0) {  // a negative candidate is padding
+            if (map) {
+                int64_t p = c;
+                if ((n_map & 1) == 0 && p == n_map) p = n_map - 1;  // the even-N id of the last DFS node
+                if (p < n_map && (int64_t)map[p] < n) row = (int)map[p];
+            } else {
+                const int64_t r = (int64_t)c - id_offset;
+                if (r >= 0 && r < n) row = (int)r;
+            }
+            if (row < 0) *flag = 1;  // names no row
+        }
+    }
+    __syncthreads();
+    double acc = 0.0;
+    const int lj = (lane & 7) * 4;
+    for (int d0 = 0; d0 < Dp; d0 += DC) {
+#pragma unroll
+        for (int it = 0; it < 8; ++it) {
+            const int cc = it * 8 + (lane >> 3);
+            const int rr = __shfl(row, cc);
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (rr >= 0 && d0 + lj < Dp) v = *reinterpret_cast<const float4*>(base + (size_t)rr * Dp + d0 + lj);
+            tile[w][cc][lj + 0] = v.x; tile[w][cc][lj + 1] = v.y; tile[w][cc][lj + 2] = v.z; tile[w][cc][lj + 3] = v.w;
+        }
+        __syncthreads();
+        const int dc = min(DC, Dp - d0);
+#pragma unroll 8
+        for (int d = 0; d < dc; ++d) {
+            const float t = tile[w][lane][d] - qv[d0 + d];
+            const float s = t * t;
+            acc += (double)s;
+        }
+        __syncthreads();
+    }
+    if (ci < n_pad)
+        keys[(size_t)q * n_pad + ci] = row >= 0 ? make_key(acc, (uint32_t)((int64_t)row + id_offset)) : kNoKey;
+}
+
+int pow2_at_least(int v) {
+    int p = 1;
+    while (p < v) p <<= 1;
+    return p;
+}
+
+// hipFuncSetAttribute is per device
+hipError_t ensure_sort_lds() {
+    static std::atomic<bool> done[64];
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    if (dev < 0 || dev >= 64 || !done[dev].load(std::memory_order_acquire)) {
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(flat_sort_emit_kernel),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, kFlatMaxTopK * (int)sizeof(uint64_t));
+        if (e != hipSuccess) return e;
+        if (dev >= 0 && dev < 64) done[dev].store(true, std::memory_order_release);
+    }
+    return hipSuccess;
+}
+
+}  // namespace
+
+int flat_key_capacity(int top_k) { return std::max(8192, pow2_at_least(4 * top_k)); }
+
+int flat_query_batch(int top_k) { return (int)(((size_t)64 << 20) / ((size_t)flat_key_capacity(top_k) * sizeof(uint64_t))); }
+
+size_t flat_rerank_keys(int n_cand) { return (size_t)pow2_at_least(n_cand); }
+
+hipError_t launch_flat_pad_rows(const float* d_in, int64_t rows, int D, int Dp, float* d_out, hipStream_t stream) {
+    const int64_t total = rows * Dp;
+    if (total <= 0) return hipSuccess;
+    flat_pad_rows_kernel<<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream>>>(d_in, rows, D, Dp, d_out);
+    return hipGetLastError();
+}
+
+hipError_t launch_flat_search(const float* d_base, int64_t n, int Dp, const float* d_queries, int nq, int top_k,
+                              int64_t id_offset, uint64_t* d_keys, FlatQueryState* d_state, int32_t* d_ids, float* d_dists,
+                              hipStream_t stream) {
+    if (nq <= 0) return hipSuccess;
+    hipError_t e = ensure_sort_lds();
+    if (e != hipSuccess) return e;
+    const int cap = flat_key_capacity(top_k);
+    // A stripe appends at most cap / 2 keys to a buffer, and a buffer enters a stripe with at most cap / 2: the select
+    // between two stripes cuts every buffer above cap / 4 (>= top_k) down to top_k.  The first stripe, with no
+    // threshold yet, is the prefix the first thresholds come from.
+    const int64_t stripe = cap / 2;
+    const uint32_t limit = (uint32_t)std::max(top_k, cap / 4);
+    flat_init_state_kernel<<<dim3((nq + 255) / 256), dim3(256), 0, stream>>>(d_state, nq);
+    for (int64_t r0 = 0; r0 < n; r0 += stripe) {
+        const int rows = (int)std::min<int64_t>(stripe, n - r0);
+        if (r0 > 0) flat_select_kernel<<<dim3(nq), dim3(kSelThreads), 0, stream>>>(d_keys, cap, d_state, top_k, limit);
+        flat_dist_kernel<<<dim3((rows + TV - 1) / TV, (nq + TQ - 1) / TQ), dim3(256), 0, stream>>>(
+            d_base, r0, rows, Dp, d_queries, nq, id_offset, d_keys, cap, d_state);
+    }
+    flat_select_kernel<<<dim3(nq), dim3(kSelThreads), 0, stream>>>(d_keys, cap, d_state, top_k, (uint32_t)top_k);
+    const int n_pad = pow2_at_least(top_k);
+    flat_sort_emit_kernel<<<dim3(nq), dim3(kSelThreads), (size_t)n_pad * sizeof(uint64_t), stream>>>(
+        d_keys, (size_t)cap, d_state, top_k, n_pad, top_k, d_ids, d_dists);
+    return hipGetLastError();
+}
+
+hipError_t launch_flat_rerank(const float* d_base, int64_t n, int D, int Dp, const float* d_queries, int nq,
+                              const int32_t* d_cand, int n_cand, int top_k, int64_t id_offset, const uint32_t* d_map,
+                              int64_t n_map, uint64_t* d_keys, uint32_t* d_flag, int32_t* d_ids, float* d_dists,
+                              hipStream_t stream) {
+    if (nq <= 0) return hipSuccess;
+    hipError_t e = ensure_sort_lds();
+    if (e != hipSuccess) return e;
+    const int n_pad = pow2_at_least(n_cand);
+    for (int q0 = 0; q0 < nq; q0 += 65535) {  // the grid's y extent
+        const int m = std::min(65535, nq - q0);
+        flat_rerank_kernel<<<dim3((n_pad + 255) / 256, m), dim3(256), 0, stream>>>(
+            d_base, n, D, Dp, d_queries + (size_t)q0 * D, d_cand + (size_t)q0 * n_cand, n_cand, n_pad, id_offset, d_map,
+            n_map, d_keys + (size_t)q0 * n_pad, d_flag);
+    }
+    flat_sort_emit_kernel<<<dim3(nq), dim3(kSelThreads), (size_t)n_pad * sizeof(uint64_t), stream>>>(
+        d_keys, (size_t)n_pad, nullptr, n_pad, n_pad, top_k, d_ids, d_dists);
+    return hipGetLastError();
+}
+
+}  // namespace dpq

@@ -32,6 +32,9 @@
  *   PQ::WriteCodewords (pq.cpp:267-286)         dpq_write_codewords
  *   ReadTopN(query.{fvecs,bvecs})               dpq_read_vecs
  *     (utils.cpp:14-110)
+ *   brute force over base.{ext}                 dpq_flat_open / dpq_flat_search (exact L2,
+ *     (main.cpp:107-166, 569-669)                 the reference's bits), dpq_flat_rerank
+ *   recall (main.cpp:727-803)                   dpq_recall, dpq_read/write_groundtruth
  *
  * Conventions: plain pointers and sizes only; the caller owns every host
  * buffer it passes, the library owns device memory.  Every function returns a
@@ -454,6 +457,69 @@ int dpq_merge_topk_device_packed(const int32_t* d_packed, int n_lists, int nq, i
 int dpq_query_batch_device_ordered(dpq_index* idx, const float* d_queries, int nq, int top_k, int32_t* d_ids,
                                    float* d_dists, void* hip_stream);
 int dpq_finish_count(dpq_index* idx, int32_t* rerun_batches);
+
+/* ---- exact search over raw vectors: ground truth, recall, re-ranking --------
+ * Every distance above is a PQ approximation.  A dpq_flat holds the raw fp32 vectors [n][D] on one GPU and gives true
+ * squared L2 distances: over all of them (ground truth, the reference's `pqtree -task groundtruth`, main.cpp:569-669)
+ * or over a candidate list per query (re-ranking a PQ answer, main.cpp:898-939).
+ * The arithmetic is the reference's brute force (main.cpp:150-156), met bit for bit.  For a base vector v and a query
+ * q, both fp32 [D], acc is an fp64 value starting at +0.0; for d = 0 .. D-1 in ascending order:
+ *     t = v[d] - q[d]      in fp32, rounded;
+ *     s = t * t            in fp32, rounded on its own (no fused multiply-add);
+ *     acc += (double)s     one add after the other.
+ * The reported distance is (float)acc, round to nearest even (the reference keeps pair<float, uint>); it is the SQUARED
+ * distance, as in the reference's file.  Results are ordered by (distance, id) ascending and at the k-th boundary the
+ * lowest ids win -- the engine's rule above; the reference's heap order among exact ties is not reproduced.  Ids are
+ * row numbers plus the handle's id_offset, int32.  Behaviour for non-finite inputs (NaN, infinities, or values whose
+ * squared difference overflows) is unspecified.  tests/_exact_restatement.py restates these rules in numpy.
+ * A handle is bound to one GPU and is used from one thread at a time.  Device memory: 4 * n * (D rounded up to a
+ * multiple of 4) bytes, plus workspaces of at most about 200 MB kept until dpq_flat_close. */
+typedef struct dpq_flat dpq_flat;
+#define DPQ_FLAT_MAX_TOPK 16384 /* the reference's README runs groundtruth with -topk 10000 */
+
+/* vectors[n][D], host memory, copied to GPU `device`.  DPQ_ERR_ARG before any device call: a NULL pointer, n < 1, D
+ * outside 1..2048, id_offset < 0, n + id_offset >= 2^31.  Without a GPU: DPQ_ERR_NO_DEVICE.  Vectors that do not fit
+ * into device memory: DPQ_ERR_NOMEM -- search a larger base part by part, each part a handle with its own id_offset,
+ * and merge the answers with dpq_merge_topk_host. */
+int dpq_flat_open(const float* vectors, int64_t n, int D, int device, int64_t id_offset, dpq_flat** out);
+int dpq_flat_close(dpq_flat* f);
+/* Exact top_k of every query over all n vectors.  Host buffers, synchronous; queries[nq][D]; ids[nq][top_k],
+ * dists[nq][top_k] ascending by (distance, id).  top_k outside 1..DPQ_FLAT_MAX_TOPK: DPQ_ERR_ARG; top_k > n:
+ * DPQ_ERR_TOPK; nq == 0: DPQ_OK. */
+int dpq_flat_search(dpq_flat* f, const float* queries, int nq, int top_k, int32_t* ids, float* dists);
+/* map[n_map]: DFS position -> row of this handle (QNode.vec_id, dpq_tree_array 0 / dpq_read_qnode_ids), uploaded once.
+ * With a map set, the candidates of dpq_flat_rerank* are DFS positions as dpq_query_batch reports them.  An entry
+ * >= n is DPQ_ERR_ARG. */
+int dpq_flat_set_id_map(dpq_flat* f, const uint32_t* map, int64_t n_map);
+/* Exact distances of the given candidates only, the best top_k of them: cand_ids[nq][n_cand], 1 <= top_k <= n_cand <=
+ * 16384.  A negative candidate is padding and is skipped.  Without a map a candidate is an id of this handle (row = id
+ * - id_offset) and the same id is reported back.  With a map a candidate c is a DFS position: the row is map[c], the
+ * reported id map[c] + id_offset, and for an even n_map the candidate n_map means position n_map - 1 (the even-N rule
+ * above).  A candidate that names no row is DPQ_ERR_ARG (the host variant checks on the host before any device work;
+ * the device variant reads one flag word back at its end, and its outputs are then unspecified).  A row named twice by
+ * one query counts once.  Output ascending by (exact distance, reported id), rows padded with id -1 / +inf when fewer
+ * than top_k candidates are valid. */
+int dpq_flat_rerank(dpq_flat* f, const float* queries, int nq, const int32_t* cand_ids, int n_cand, int top_k,
+                    int32_t* ids, float* dists);
+/* Same with device pointers on the handle's GPU, enqueued on `hip_stream` (NULL = default stream); returns after the
+ * flag word has come back, i.e. with the results complete. */
+int dpq_flat_rerank_device(dpq_flat* f, const float* d_queries, int nq, const int32_t* d_cand_ids, int n_cand, int top_k,
+                           int32_t* d_ids, float* d_dists, void* hip_stream);
+
+/* Host only.  Vectors [first, first + count) of an .fvecs / .bvecs file (the streaming read of main.cpp:607-640);
+ * out[count][D] may be NULL to learn D.  A range past the end of the file: DPQ_ERR_IO. */
+int dpq_read_vecs_range(const char* path, int is_bvecs, int64_t first, int64_t count, int32_t* D, float* out);
+/* The reference's ground-truth text file (PQBase::write_groundtruth / read_groundtruth, pqbase.cpp:294-332): a first
+ * line `nq,top_k`, then one line per query of `id,dist,` pairs.  Distances are written with nine significant digits so
+ * that they read back to the same bits (the reference's six digits lose them).  Read with ids == dists == NULL to
+ * learn the shape. */
+int dpq_write_groundtruth(const char* path, const int32_t* ids, const float* dists, int nq, int top_k);
+int dpq_read_groundtruth(const char* path, int32_t* nq, int32_t* top_k, int32_t* ids, float* dists);
+/* recall = (1 / (nq * k)) * sum over q of |found[q][0..R) intersected with truth[q][0..k)|, negative ids ignored, an id
+ * counted once.  found[nq][found_stride], truth[nq][truth_stride].  R = k is the reference's measure
+ * (main.cpp:783-796); k = 1 gives 1-recall@R. */
+int dpq_recall(const int32_t* found, int found_stride, int R, const int32_t* truth, int truth_stride, int k, int nq,
+               double* recall);
 
 /* ---- measurement -------------------------------------------------------- */
 int dpq_profile_enable(dpq_index* idx, int on);  /* 0 off, 1 every kernel, 2 scan launches only (less event overhead) */
