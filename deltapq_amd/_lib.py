@@ -79,6 +79,7 @@ SYMBOLS = [
     ("dpq_soa_array", ctypes.c_int, [_VP, ctypes.c_int, P(_VP), P(c_i64)]),
     ("dpq_soa_free", None, [_VP]),
     ("dpq_dtc_encode", ctypes.c_int, [_VP, _VP, _VP, _VP, c_i64, ctypes.c_int, _VP, P(c_i64)]),
+    ("dpq_dtc_decode", ctypes.c_int, [_VP, c_i64, c_i64, ctypes.c_int, c_i64, c_i64, _VP]),
     ("dpq_tree_build", ctypes.c_int, [_VP, c_i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, _VP, ctypes.c_int, P(_VP)]),
     ("dpq_tree_build_gpu", ctypes.c_int,
      [_VP, c_i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, _VP, ctypes.c_int, ctypes.c_int, P(_VP)]),
@@ -125,6 +126,11 @@ SYMBOLS = [
     ("dpq_query_batch_filtered", ctypes.c_int, [_VP, _VP, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP]),
     ("dpq_query_batch_device_filtered", ctypes.c_int,
      [_VP, _VP, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP]),
+    ("dpq_get_codes", ctypes.c_int, [_VP, _VP, c_i64, _VP]),
+    ("dpq_get_codes_device", ctypes.c_int, [_VP, _VP, c_i64, _VP, _VP]),
+    ("dpq_reconstruct", ctypes.c_int, [_VP, _VP, c_i64, _VP]),
+    ("dpq_reconstruct_device", ctypes.c_int, [_VP, _VP, c_i64, _VP, _VP]),
+    ("dpq_decode_range", ctypes.c_int, [_VP, c_i64, c_i64, _VP]),
     ("dpq_flat_open", ctypes.c_int, [_VP, c_i64, ctypes.c_int, ctypes.c_int, c_i64, P(_VP)]),
     ("dpq_flat_close", ctypes.c_int, [_VP]),
     ("dpq_flat_search", ctypes.c_int, [_VP, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP]),

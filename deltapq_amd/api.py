@@ -74,6 +74,18 @@ def dtc_encode(root, depths, masks, deltas, M=8):
     return out
 
 
+def dtc_decode(payload, n_codes, M=8, first=0, count=None):
+    """The inverse of dtc_encode (dpq_dtc_decode): codes [first, first + count) of a DTC payload in DFS order,
+    uint8 [count][M].  count=None: everything from `first` on.  Positions, not reported ids."""
+    lib = _lib.load()
+    pl = np.ascontiguousarray(payload, dtype=np.uint8)
+    if count is None:
+        count = n_codes - first
+    out = np.empty((max(int(count), 0), M), dtype=np.uint8)
+    check(lib.dpq_dtc_decode(_np_ptr(pl), pl.size, n_codes, M, first, count, _np_ptr(out)), "dpq_dtc_decode")
+    return out
+
+
 class HostSoA:
     """The transcoded structure-of-arrays image, built on the host (no GPU)."""
 
@@ -390,6 +402,69 @@ class DeltaPQIndex:
                                                         ctypes.c_void_p(out_dists.data_ptr()), ctypes.c_void_p(stream)),
               "dpq_query_batch_device_filtered")
         return out_ids, out_dists
+
+    def _lookup_ids(self, ids):
+        return np.ascontiguousarray(np.asarray(ids, dtype=np.int32).reshape(-1))
+
+    def get_codes(self, ids):
+        """The codes of reported ids (dpq_get_codes), uint8 [n][M].  An id is what a search reports; a negative id is
+        padding and gives a zero row; an id that names no node of this handle raises DpqError (DPQ_ERR_ARG)."""
+        i = self._lookup_ids(ids)
+        out = np.empty((i.size, self.info()["M"]), dtype=np.uint8)
+        check(self._lib.dpq_get_codes(self._h, _np_ptr(i), i.size, _np_ptr(out)), "dpq_get_codes")
+        return out
+
+    def reconstruct(self, ids):
+        """The codebook's approximation of reported ids (dpq_reconstruct), float32 [n][M * Ds]: row i is the
+        concatenation of codebook[m, code_i[m]].  A negative id gives a row of NaNs."""
+        i = self._lookup_ids(ids)
+        inf = self.info()
+        out = np.empty((i.size, inf["M"] * inf["Ds"]), dtype=np.float32)
+        check(self._lib.dpq_reconstruct(self._h, _np_ptr(i), i.size, _np_ptr(out)), "dpq_reconstruct")
+        return out
+
+    def decode_range(self, first=None, count=None):
+        """The handle's codes for POSITIONS [first, first + count) in DFS order (dpq_decode_range), uint8 [count][M];
+        by default everything the handle holds, info()["node_lo"] .. info()["node_hi"]."""
+        inf = self.info()
+        if first is None:
+            first = inf["node_lo"]
+        if count is None:
+            count = inf["node_hi"] - first
+        out = np.empty((max(int(count), 0), inf["M"]), dtype=np.uint8)
+        check(self._lib.dpq_decode_range(self._h, first, count, _np_ptr(out)), "dpq_decode_range")
+        return out
+
+    def get_codes_torch(self, ids, out=None):
+        """get_codes on device tensors, synchronous on torch's current stream (dpq_get_codes_device): `ids` int32 [n]
+        on the index's GPU; returns uint8 [n][M] there."""
+        import torch
+        assert ids.is_cuda and ids.dtype == torch.int32 and ids.is_contiguous()
+        n = ids.numel()
+        if out is None:
+            out = torch.empty((n, self.info()["M"]), dtype=torch.uint8, device=ids.device)
+        if n == 0:                      # (an empty tensor has no storage: nothing to hand to the library)
+            return out
+        stream = torch.cuda.current_stream(ids.device).cuda_stream
+        check(self._lib.dpq_get_codes_device(self._h, ctypes.c_void_p(ids.data_ptr()), n, ctypes.c_void_p(out.data_ptr()),
+                                             ctypes.c_void_p(stream)), "dpq_get_codes_device")
+        return out
+
+    def reconstruct_torch(self, ids, out=None):
+        """reconstruct on device tensors, synchronous on torch's current stream (dpq_reconstruct_device): returns
+        float32 [n][M * Ds] on the index's GPU."""
+        import torch
+        assert ids.is_cuda and ids.dtype == torch.int32 and ids.is_contiguous()
+        n = ids.numel()
+        if out is None:
+            inf = self.info()
+            out = torch.empty((n, inf["M"] * inf["Ds"]), dtype=torch.float32, device=ids.device)
+        if n == 0:
+            return out
+        stream = torch.cuda.current_stream(ids.device).cuda_stream
+        check(self._lib.dpq_reconstruct_device(self._h, ctypes.c_void_p(ids.data_ptr()), n, ctypes.c_void_p(out.data_ptr()),
+                                               ctypes.c_void_p(stream)), "dpq_reconstruct_device")
+        return out
 
     def query_batch_host_async(self, queries, top_k, ids, dists):
         """dpq_query_batch_host_async: host arrays in and out, enqueued only -- up to four batches in flight, queries up and

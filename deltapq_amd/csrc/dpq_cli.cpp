@@ -22,7 +22,8 @@
 // index -> query runs from this one tool; -task learn is its learn step
 // (main.cpp:243-277) with this build's own k-means (dpq_train_codebook); -task groundtruth and -task recall are
 // its brute-force ground truth (main.cpp:569-669) and recall measure (main.cpp:727-803) over raw vectors, the
-// latter with an optional exact re-rank of the PQ answer (-rerank R).
+// latter with an optional exact re-rank of the PQ answer (-rerank R); -task decompress (no counterpart in the
+// reference) decodes the DTC index on the GPU back into the codes.bin.plain record layout.
 #include <sys/stat.h>
 
 #include <algorithm>
@@ -49,7 +50,7 @@ static int die(const char* where, int rc) {
 }
 
 int main(int argc, char* argv[]) {
-    std::string dataset, queryset, task = "approx_tree", ext = "fvecs", out_path;
+    std::string dataset, queryset, task = "approx_tree", ext = "fvecs", out_path, order = "dfs";
     int query_size = -1, top_k = 1, diff_argument = 1, debug = 0, max_height_folds = 1, method = 1;
     int PQ_M = 0, PQ_K = 0, gpus = 1, gt_topk = -1, rerank = 0;
     bool topk_given = false;
@@ -74,6 +75,7 @@ int main(int argc, char* argv[]) {
         if (arg == "-method") method = atoi(nx);
         if (arg == "-gpus") gpus = atoi(nx);
         if (arg == "-out") out_path = nx;
+        if (arg == "-order") order = nx;
     }
     (void)diff_argument; (void)method; (void)queryset;
 
@@ -202,6 +204,59 @@ int main(int argc, char* argv[]) {
         std::cout << "==========================BUILD DELTATREE INDEX IN " << (Elapsed() - t0) << " [sec] "
                   << "==========================" << std::endl << std::endl;                           // main:136-137
         std::cout << "WARNING: Just built an index. no query processed." << std::endl;                 // main:140
+        return 0;
+    }
+    if (task == "decompress") {
+        // No counterpart in the reference (it never reads a code back out of its index): the DTC index decoded on the
+        // GPU (dpq_decode_range over everything) into the codes.bin.plain record layout, in DFS order or -- through the
+        // TreeNodesDFS file's vec_ids -- in the order of the encoder's file.
+        if (PQ_M <= 0 || PQ_K <= 0 || dataset.empty() || N < 0 || (order != "dfs" && order != "file")) {
+            std::cout << "usage: deltapq -dataset DIR -task decompress -m M -k K -N N [-order dfs|file]" << std::endl;
+            return 2;
+        }
+        char path[4096];
+        int rc = dpq_dtc_file_name(dataset.c_str(), PQ_M, PQ_K, N, path, sizeof path);
+        if (rc) return die("dpq_dtc_file_name", rc);
+        const double t0 = Elapsed();
+        dpq_index* idx = nullptr;
+        rc = dpq_open_file(path, PQ_M, PQ_K, nullptr, &idx);
+        if (rc) return die("dpq_open_file", rc);
+        dpq_info inf;
+        dpq_get_info(idx, &inf);
+        const int64_t n = inf.node_hi - inf.node_lo;
+        std::vector<uint8_t> codes((size_t)n * PQ_M);
+        rc = dpq_decode_range(idx, inf.node_lo, n, codes.data());
+        dpq_close(idx);
+        if (rc) return die("dpq_decode_range", rc);
+        if (order == "file") {
+            if (PQ_M > 8) {
+                std::cout << "-order file needs the TreeNodesDFS file, which exists for M <= 8 only" << std::endl;
+                return 1;
+            }
+            const std::string nodes_path = dataset + "/M" + std::to_string(PQ_M) + "K" + std::to_string(PQ_K) +
+                                           "_Approx_TreeNodesDFS_N" + std::to_string(N);
+            std::vector<uint32_t> vec_id((size_t)n);
+            rc = dpq_read_qnode_ids(nodes_path.c_str(), n, vec_id.data());
+            if (rc) return die("dpq_read_qnode_ids", rc);
+            std::vector<uint8_t> by_file((size_t)n * PQ_M);
+            std::vector<bool> seen((size_t)n, false);
+            for (int64_t p = 0; p < n; ++p) {
+                const uint32_t v = vec_id[(size_t)p];
+                if (v >= (uint64_t)n || seen[v]) {
+                    std::cout << nodes_path << ": vec_ids are not a permutation of 0.." << n - 1 << std::endl;
+                    return 1;
+                }
+                seen[v] = true;
+                memcpy(&by_file[(size_t)v * PQ_M], &codes[(size_t)p * PQ_M], (size_t)PQ_M);
+            }
+            codes.swap(by_file);
+        }
+        const std::string out = dataset + "/codes.bin.decoded.M" + std::to_string(PQ_M) + "K" + std::to_string(PQ_K) + "N" +
+                                std::to_string(N);
+        rc = dpq_write_codes_plain(out.c_str(), codes.data(), n, PQ_M);
+        if (rc) return die("PQTree::Write", rc);
+        std::cout << "decoded " << n << " codes (" << order << " order) in " << (Elapsed() - t0) << " [sec] -> " << out
+                  << std::endl;
         return 0;
     }
     if (task == "groundtruth") {
@@ -433,7 +488,7 @@ int main(int argc, char* argv[]) {
         task = "query";
     }
     if (task != "query" && task != "query_im" && !pqscan) {
-        std::cout << "deltapq (MI355X build): -task query, query_im, pqscan, approx_tree, encode, learn, groundtruth and recall are implemented (batch_query = "
+        std::cout << "deltapq (MI355X build): -task query, query_im, pqscan, approx_tree, encode, learn, decompress, groundtruth and recall are implemented (batch_query = "
                      "alias of query); got '" << task
                   << "'" << std::endl;
         return 2;

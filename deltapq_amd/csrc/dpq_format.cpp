@@ -493,6 +493,41 @@ int encode(const uint8_t* root_code, const uint8_t* depths, const uint16_t* mask
     return DPQ_OK;
 }
 
+// The inverse of encode(): the stack machine of the reference scan (h:2888, 2896-2900) over the whole stream, rows
+// [first, first + count) kept.  The stream is validated first, so a refused stream leaves codes_out untouched.
+int decode_codes(const uint8_t* payload, int64_t n_bytes, int64_t n_codes, int M, int64_t first, int64_t count,
+                 uint8_t* codes_out, std::string* err) {
+    int rc = validate(payload, n_bytes, n_codes, M, nullptr, err);
+    if (rc) return rc;
+    if (first < 0 || count < 0 || first > n_codes || count > n_codes - first) {
+        if (err) *err = "[first, first + count) outside the payload's codes";
+        return DPQ_ERR_ARG;
+    }
+    if (count == 0) return DPQ_OK;
+    if (!codes_out) {
+        if (err) *err = "codes_out is NULL";
+        return DPQ_ERR_ARG;
+    }
+    std::vector<uint8_t> stack((size_t)levels_for(M) * M, 0);
+    DtcWalker w(payload, n_bytes, n_codes, M);
+    NodeRec r;
+    while (w.pos() < first + count) {
+        const int64_t i = w.pos();
+        rc = w.next(&r);
+        if (rc) {
+            if (err) *err = w.error();
+            return rc;
+        }
+        uint8_t* cur = &stack[(size_t)r.depth * M];
+        if (r.depth > 0) memcpy(cur, &stack[(size_t)(r.depth - 1) * M], (size_t)M);
+        int j = 0;
+        for (int m = 0; m < M; m++)
+            if (r.mask & (1u << m)) cur[m] = r.deltas[j++];
+        if (i >= first) memcpy(codes_out + (size_t)(i - first) * M, cur, (size_t)M);
+    }
+    return DPQ_OK;
+}
+
 // ---------------------------------------------------------------------------
 // loaders
 // ---------------------------------------------------------------------------

@@ -149,6 +149,9 @@ inline int bootstrap_stride_for(int64_t n_local) {
 inline int bootstrap_classes_for(int64_t n_sampled) { return n_sampled >= 4 * 65536 ? kBootPairs : 1; }
 int encode(const uint8_t* root_code, const uint8_t* depths, const uint16_t* masks, const uint8_t* deltas,
            int64_t n_codes, int M, uint8_t* out, int64_t* n_bytes, std::string* err);
+// Codes [first, first + count) of a payload in DFS order, codes_out[count][M] (dpq_dtc_decode).
+int decode_codes(const uint8_t* payload, int64_t n_bytes, int64_t n_codes, int M, int64_t first, int64_t count,
+                 uint8_t* codes_out, std::string* err);
 
 // loaders (a10)
 int read_file(const std::string& path, std::vector<uint8_t>* out, std::string* err);

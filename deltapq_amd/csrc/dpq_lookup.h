@@ -1,0 +1,38 @@
+// dpq_lookup.h -- launch interface of the code lookup kernels (dpq_lookup.hip): the codes, or the codebook's
+// approximate vectors, of a list of reported ids.
+#pragma once
+#include "dpq_kernels.h"
+
+namespace dpq {
+
+// Requests one launch takes (a wavefront per request, four to a workgroup); the entry points cut longer lists.
+constexpr int64_t kLookupSlice = (int64_t)1 << 20;
+
+// The grouped path (dpq_capi.cpp lookup_begin): a call that names the handle's segments often enough decodes every
+// segment ONCE (decode_list_kernel, no relabelling) into a scratch image and serves all its requests from it as from a
+// plain index.  Taken from kLookupGroupedPerSegment requests per segment of the handle, on handles whose decoded
+// image fits kLookupGroupedMaxBytes.  The switch-over is read off profiles/lookup_bench_index.txt (1 M codes, 7813
+// segments; ms per synchronous call, per-request / grouped): 1000 ids (0.13 per segment) 0.036 / 0.040, 100 000 ids
+// (12.8 per segment) 0.075 / 0.044, 1 M ids 0.42 / 0.056, 10 M ids 3.80 / 0.19; reconstruction 0.036 / 0.041, 0.089 /
+// 0.067, 0.56 / 0.34, 5.3 / 3.1.  12 per segment is the smallest measured ratio at which the grouped path wins.
+// The byte bound is a memory bound, not a measured one: the largest transient scratch a call may allocate.
+constexpr int64_t kLookupGroupedPerSegment = 12;
+constexpr int64_t kLookupGroupedMaxBytes = (int64_t)256 << 20;
+
+struct LookupArgs {
+    DeviceImage img;
+    const int32_t* ids;      // [n] reported ids: < 0 = padding
+    int64_t n;
+    int32_t even_rule;       // 1: DTC index (for even n_codes_total the id N names position N - 1 and N - 1 nothing)
+    uint8_t* out_codes;      // [n][M], any alignment (lookup of codes)
+    float* out_vecs;         // [n][M * Ds] (reconstruction)
+    const float* codebook;   // [M][K][Ds]
+    int32_t Ds;
+    uint32_t* flag;          // set to 1 by every request whose id >= 0 names no node of the image
+};
+
+// One of out_codes / out_vecs (with codebook and Ds) is set.  A padding request gives M zero bytes / M * Ds quiet NaNs;
+// so does a request the flag word reports, and a code byte >= K has no codeword: its Ds floats are NaN.
+hipError_t launch_lookup(const LookupArgs& a, hipStream_t stream);
+
+}  // namespace dpq

@@ -1,0 +1,165 @@
+// dpq_lookup.hip -- code lookup on an opened index (dpq_get_codes / dpq_reconstruct): random access into the
+// delta tree.  Every segment is decodable on its own from its checkpoint, so a request costs the decode of the
+// chunks of ITS segment up to its own -- at most chunks_per_segment wavefront steps -- never a walk from the root.
+//
+//   lookup_kernel<M, RECON>   one wavefront per request, four per workgroup, no LDS.  The request's reported id
+//                             becomes (segment, chunk, lane); the wavefront starts from the segment's checkpoint,
+//                             steps the chunks up to the requested one (the scan's own WaveDecoder) and takes the
+//                             owning lane's code.  RECON = false: lanes 0 .. M-1 store the code's bytes.
+//                             RECON = true: the gather of the codewords is fused in, all 64 lanes write the
+//                             M * Ds floats of the row as consecutive dwords (any Ds).
+//                             With img.raw set (a plain index, or the grouped path's decoded image) it reads the row
+//                             instead of decoding.
+//   gather_codes_kernel<M>    codes from img.raw, a THREAD per request: the row gather of a plain index and the
+//                             second half of the grouped path (dpq_capi.cpp decodes every segment of the handle once
+//                             with decode_list_kernel, then all requests are served from that image).
+#include "dpq_lookup.h"
+
+#include "dpq_wave_decoder.h"
+
+namespace dpq {
+
+template <int M, bool RECON>
+__global__ __launch_bounds__(256) void lookup_kernel(const LookupArgs a) {
+    constexpr int W = Cfg<M>::W;
+    const int lane = threadIdx.x & 63;
+    const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= a.n) return;  // (a whole wavefront)
+    // everything that steers the wavefront is made wave-uniform: the decode below runs ballots and lane exchanges
+    const int32_t id = __builtin_amdgcn_readfirstlane(a.ids[i]);
+    bool have = id >= 0;
+    int64_t local = 0;
+    if (have) {
+        int64_t pos = id;
+        const int64_t N = a.img.n_codes_total;
+        if (a.even_rule && (N & 1) == 0) {  // report_id's inverse: N names the last node, N - 1 nothing
+            if (pos == N)
+                pos = N - 1;
+            else if (pos == N - 1)
+                pos = -1;
+        }
+        local = pos - (int64_t)a.img.id_base;
+        if (pos < 0 || local < 0 || local >= a.img.n_local) {
+            have = false;
+            if (lane == 0) *a.flag = 1u;
+        }
+    }
+    uint32_t code[W];
+#pragma unroll
+    for (int w = 0; w < W; ++w) code[w] = 0;
+    if (have) {
+        if (a.img.raw) {
+#pragma unroll
+            for (int w = 0; w < W; ++w) code[w] = reinterpret_cast<const uint32_t*>(a.img.raw)[(size_t)local * W + w];
+        } else {
+            const int cps = a.img.chunks_per_segment;
+            const int64_t S = (int64_t)64 * cps;
+            const int64_t seg = local / S;
+            const int r = (int)(local - seg * S);
+            const int chunk = r >> 6, owner = r & 63;
+            WaveDecoder<M> dec;
+            dec.begin_segment(a.img, (uint32_t)seg, lane);
+            uint32_t cur[W];
+            for (int c = 0; c <= chunk; ++c) dec.step(a.img, (seg * cps + c) * 64 + lane, lane, c < chunk, cur);
+#pragma unroll
+            for (int w = 0; w < W; ++w) code[w] = bperm(owner, cur[w]);
+        }
+    }
+    if constexpr (!RECON) {
+        if (lane < M) {
+            uint32_t v = code[0];
+#pragma unroll
+            for (int w = 1; w < W; ++w)
+                if ((lane >> 2) == w) v = code[w];
+            a.out_codes[(size_t)i * M + lane] = (uint8_t)(v >> (8 * (lane & 3)));
+        }
+    } else {
+        const int Ds = a.Ds, D = M * Ds, K = a.img.K;
+        float* __restrict__ row = a.out_vecs + (size_t)i * D;
+        for (int e = lane; e < D; e += 64) {
+            const int m = e / Ds, d = e - m * Ds;
+            uint32_t v = code[0];
+#pragma unroll
+            for (int w = 1; w < W; ++w)
+                if ((m >> 2) == w) v = code[w];
+            const int c = (int)((v >> (8 * (m & 3))) & 0xffu);
+            float f = __uint_as_float(0x7FC00000u);
+            if (have && c < K) f = a.codebook[((size_t)m * K + c) * Ds + d];
+            row[e] = f;
+        }
+    }
+}
+
+// Codes of the requests from img.raw: one thread per request.  ALIGNED: out_codes is 4-byte aligned (dword stores).
+template <int M, bool ALIGNED>
+__global__ __launch_bounds__(256) void gather_codes_kernel(const LookupArgs a) {
+    constexpr int W = Cfg<M>::W;
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.n) return;
+    const int32_t id = a.ids[i];
+    bool have = id >= 0;
+    int64_t local = 0;
+    if (have) {
+        int64_t pos = id;
+        const int64_t N = a.img.n_codes_total;
+        if (a.even_rule && (N & 1) == 0) {
+            if (pos == N)
+                pos = N - 1;
+            else if (pos == N - 1)
+                pos = -1;
+        }
+        local = pos - (int64_t)a.img.id_base;
+        if (pos < 0 || local < 0 || local >= a.img.n_local) {
+            have = false;
+            *a.flag = 1u;
+        }
+    }
+    uint32_t code[W];
+#pragma unroll
+    for (int w = 0; w < W; ++w) code[w] = have ? reinterpret_cast<const uint32_t*>(a.img.raw)[(size_t)local * W + w] : 0u;
+    if constexpr (ALIGNED) {
+#pragma unroll
+        for (int w = 0; w < W; ++w) reinterpret_cast<uint32_t*>(a.out_codes)[(size_t)i * W + w] = code[w];
+    } else {
+#pragma unroll
+        for (int b = 0; b < M; ++b) a.out_codes[(size_t)i * M + b] = (uint8_t)(code[b >> 2] >> (8 * (b & 3)));
+    }
+}
+
+hipError_t launch_lookup(const LookupArgs& a, hipStream_t stream) {
+    if (a.n <= 0) return hipSuccess;
+    if (a.n > kLookupSlice || (a.img.M != 8 && a.img.M != 16) || !a.ids || !a.flag) return hipErrorInvalidValue;
+    const bool recon = a.out_vecs != nullptr;
+    if (recon ? (!a.codebook || a.Ds < 1) : !a.out_codes) return hipErrorInvalidValue;
+    if (!recon && a.img.raw) {  // plain rows: a thread per request
+        const dim3 grid((unsigned)((a.n + 255) / 256)), block(256);
+        const bool al = (reinterpret_cast<uintptr_t>(a.out_codes) & 3u) == 0;
+        if (a.img.M == 8) {
+            if (al)
+                hipLaunchKernelGGL((gather_codes_kernel<8, true>), grid, block, 0, stream, a);
+            else
+                hipLaunchKernelGGL((gather_codes_kernel<8, false>), grid, block, 0, stream, a);
+        } else {
+            if (al)
+                hipLaunchKernelGGL((gather_codes_kernel<16, true>), grid, block, 0, stream, a);
+            else
+                hipLaunchKernelGGL((gather_codes_kernel<16, false>), grid, block, 0, stream, a);
+        }
+        return hipGetLastError();
+    }
+    const dim3 grid((unsigned)((a.n + 3) / 4)), block(256);
+    if (a.img.M == 8) {
+        if (recon)
+            hipLaunchKernelGGL((lookup_kernel<8, true>), grid, block, 0, stream, a);
+        else
+            hipLaunchKernelGGL((lookup_kernel<8, false>), grid, block, 0, stream, a);
+    } else {
+        if (recon)
+            hipLaunchKernelGGL((lookup_kernel<16, true>), grid, block, 0, stream, a);
+        else
+            hipLaunchKernelGGL((lookup_kernel<16, false>), grid, block, 0, stream, a);
+    }
+    return hipGetLastError();
+}
+
+}  // namespace dpq

@@ -35,6 +35,8 @@
  *   brute force over base.{ext}                 dpq_flat_open / dpq_flat_search (exact L2,
  *     (main.cpp:107-166, 569-669)                 the reference's bits), dpq_flat_rerank
  *   recall (main.cpp:727-803)                   dpq_recall, dpq_read/write_groundtruth
+ *   (none: the reference never reads a code     dpq_get_codes / dpq_reconstruct / dpq_decode_range,
+ *     back out of its index)                      dpq_dtc_decode (FAISS's sa_decode / reconstruct_batch)
  *
  * Conventions: plain pointers and sizes only; the caller owns every host
  * buffer it passes, the library owns device memory.  Every function returns a
@@ -233,6 +235,12 @@ void dpq_soa_free(dpq_soa* soa);
  * order, ascending position.  Call with out == NULL to get n_bytes. */
 int dpq_dtc_encode(const uint8_t* root_code, const uint8_t* depths, const uint16_t* masks, const uint8_t* deltas,
                    int64_t n_codes, int M, uint8_t* out, int64_t* n_bytes);
+/* The inverse of dpq_dtc_encode: codes [first, first + count) of a DTC payload in DFS order, codes_out[count][M].
+ * Positions, not reported ids: no even-N rule here.  M <= 8 and this build's M = 16 extension.  A stream
+ * dpq_dtc_validate refuses: DPQ_ERR_FORMAT; first < 0, count < 0 or first + count > n_codes: DPQ_ERR_ARG; count == 0:
+ * DPQ_OK (codes_out may then be NULL). */
+int dpq_dtc_decode(const uint8_t* payload, int64_t n_bytes, int64_t n_codes, int M, int64_t first, int64_t count,
+                   uint8_t* codes_out);
 
 /* ---- callers either side of the path -------------- */
 /* DeltaTree construction, `deltapq -task approx_tree` with -method 1 (create_approx_tree h:970-1065:
@@ -432,6 +440,43 @@ int dpq_query_batch_filtered(dpq_index* idx, const dpq_filter* f, const float* q
 /* Device buffers on hip_stream (the contract of dpq_query_batch_device). */
 int dpq_query_batch_device_filtered(dpq_index* idx, const dpq_filter* f, const float* d_queries, int nq, int top_k,
                                     int32_t* d_ids, float* d_dists, void* hip_stream);
+
+/* ---- code lookup ------------------------------------------------------------
+ * The codes an opened index holds, or their codebook vectors, for any reported ids (FAISS's sa_decode / reconstruct /
+ * reconstruct_batch), decoded on the GPU from the very image the searches scan.  Every segment is decodable on its own
+ * from its checkpoint, so a request costs the decode of at most one segment, not a walk from the root.
+ * Ids: an id names a node exactly as a search result does -- global DFS positions on shards (shard_rank / shard_count)
+ * and parts (global_offset), position = id on a dpq_open_plain_* index, and the even-N rule: the last node of an even-N
+ * DTC index is named by N and N - 1 names nothing (N = num_codes under the same rule when a prefix is opened).
+ * dpq_decode_range counts POSITIONS [first, first + count) inside the handle's [node_lo, node_hi), without the even-N
+ * renaming: row i of codes_out is position first + i.
+ * A non-negative id that names no node OF THIS HANDLE -- outside [node_lo, node_hi), beyond the opened prefix, the N - 1
+ * hole -- is DPQ_ERR_ARG: the host variants check on the host before any device work; the device variants raise one flag
+ * word that is read back at the end of the call, and their outputs are then unspecified.  Gathering across shards is
+ * the caller's business (split the ids by dpq_info.node_lo / node_hi).  A NEGATIVE id is padding, so a padded top-k row
+ * can be passed straight in: its code row is M zero bytes, its reconstructed row M * Ds quiet NaNs (0x7FC00000).  The
+ * same id given twice yields two equal rows; the order of `ids` is kept.  n == 0 is DPQ_OK.
+ * Reconstructed vectors: vectors_out[i][m * Ds + d] = codewords[m][code[m]][d], the very floats dpq_set_codebook
+ * received, in the layout of queries[nq][M * Ds]; a code byte >= K has no codeword and gives Ds quiet NaNs.  Without a
+ * codebook dpq_reconstruct* is DPQ_ERR_STATE; dpq_get_codes* and dpq_decode_range need none.
+ * The calls are synchronous (the device variants return once the flag word is back, with the rows complete); pending
+ * asynchronous batches are finished first.  Plans, workspaces and results of later searches are not affected.  Large n
+ * is processed in slices of 1 Mi ids (2^20; reconstructed rows to the host: at most 64 MB of them per slice).
+ * n == 0 needs no buffers (NULL is accepted); otherwise a NULL pointer is DPQ_ERR_ARG.
+ * A call (or slice) of 16 or more ids per segment of a DTC handle whose decoded codes fit 256 MB takes the grouped path:
+ * every segment is decoded once into a scratch image and all its requests are served from it (same results).
+ * Device memory, kept until dpq_close: the host variants' staging of one slice (4 MB of ids, M MB of codes, 64 MB of
+ * rows) and a scratch of up to one 4 Mi-node tile of decoded codes (M * 4 MB) shared by dpq_decode_range and the grouped
+ * path; the device variants keep the flag word and that scratch only.  A grouped call on a larger handle allocates its
+ * image (at most 256 MB) and releases it before it returns. */
+/* ids[n]: reported ids, exactly what dpq_query_batch reports.  Host buffers. */
+int dpq_get_codes(dpq_index* idx, const int32_t* ids, int64_t n, uint8_t* codes_out /* [n][M] */);
+/* Device buffers on the handle's GPU, enqueued on hip_stream (NULL = default stream). */
+int dpq_get_codes_device(dpq_index* idx, const int32_t* d_ids, int64_t n, uint8_t* d_codes, void* hip_stream);
+int dpq_reconstruct(dpq_index* idx, const int32_t* ids, int64_t n, float* vectors_out /* [n][M*Ds] */);
+int dpq_reconstruct_device(dpq_index* idx, const int32_t* d_ids, int64_t n, float* d_vectors, void* hip_stream);
+/* The handle's codes for positions [first, first + count) in DFS order: the bulk path, host out. */
+int dpq_decode_range(dpq_index* idx, int64_t first, int64_t count, uint8_t* codes_out /* [count][M] */);
 
 /* Merge n_lists partial top-k lists per query (lists[l][nq][top_k]) into the
  * final top_k by (distance, id).  Host version for the single-process
