@@ -137,7 +137,12 @@ SYMBOLS = [
     ("dpq_flat_set_id_map", ctypes.c_int, [_VP, _VP, c_i64]),
     ("dpq_flat_rerank", ctypes.c_int, [_VP, _VP, ctypes.c_int, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP]),
     ("dpq_flat_rerank_device", ctypes.c_int, [_VP, _VP, ctypes.c_int, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP]),
+    ("dpq_flat_open_u8", ctypes.c_int, [_VP, c_i64, ctypes.c_int, ctypes.c_int, c_i64, P(_VP)]),
+    ("dpq_flat_search_u8", ctypes.c_int, [_VP, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP]),
+    ("dpq_flat_rerank_u8", ctypes.c_int, [_VP, _VP, ctypes.c_int, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP]),
+    ("dpq_flat_rerank_u8_device", ctypes.c_int, [_VP, _VP, ctypes.c_int, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP]),
     ("dpq_read_vecs_range", ctypes.c_int, [ctypes.c_char_p, ctypes.c_int, c_i64, c_i64, P(c_i32), _VP]),
+    ("dpq_read_bvecs_range", ctypes.c_int, [ctypes.c_char_p, c_i64, c_i64, P(c_i32), _VP]),
     ("dpq_write_groundtruth", ctypes.c_int, [ctypes.c_char_p, _VP, _VP, ctypes.c_int, ctypes.c_int]),
     ("dpq_read_groundtruth", ctypes.c_int, [ctypes.c_char_p, P(c_i32), P(c_i32), _VP, _VP]),
     ("dpq_recall", ctypes.c_int,

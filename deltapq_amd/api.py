@@ -697,6 +697,98 @@ class FlatIndex:
         self.close()
 
 
+class FlatIndexU8:
+    """Byte vectors [n][D] on one GPU (dpq_flat_open_u8): FlatIndex's answers -- the same ids and the same distance bits as
+    on the bytes widened to fp32 -- from the int8 matrix cores, at a quarter of the device memory.  Takes uint8 arrays and
+    tensors only; anything else is a TypeError rather than a conversion."""
+
+    def __init__(self, vectors, device=0, id_offset=0):
+        self._h = None
+        v = self._bytes(vectors, "vectors")
+        if v.ndim != 2:
+            raise ValueError("vectors must be [n][D]")
+        self._lib = _lib.load()
+        self.n, self.D, self.id_offset = int(v.shape[0]), int(v.shape[1]), int(id_offset)
+        h = ctypes.c_void_p()
+        check(self._lib.dpq_flat_open_u8(_np_ptr(v), self.n, self.D, device, id_offset, ctypes.byref(h)), "dpq_flat_open_u8")
+        self._h = h
+
+    @staticmethod
+    def _bytes(a, what):
+        if not isinstance(a, np.ndarray) or a.dtype != np.uint8:
+            raise TypeError("%s must be a uint8 array (FlatIndex takes fp32)" % what)
+        return np.ascontiguousarray(a)
+
+    def _queries(self, queries):
+        q = self._bytes(queries, "queries")
+        if q.ndim != 2 or q.shape[1] != self.D:
+            raise ValueError("queries must be [nq][%d]" % self.D)
+        return q
+
+    def search(self, queries, top_k):
+        """Exact top_k over all vectors -> ids int32 [nq][top_k], dists float32 [nq][top_k] by (distance, id)."""
+        q = self._queries(queries)
+        ids = np.empty((q.shape[0], top_k), dtype=np.int32)
+        dists = np.empty((q.shape[0], top_k), dtype=np.float32)
+        check(self._lib.dpq_flat_search_u8(self._h, _np_ptr(q), q.shape[0], top_k, _np_ptr(ids), _np_ptr(dists)),
+              "dpq_flat_search_u8")
+        return ids, dists
+
+    def set_id_map(self, vec_id):
+        """DFS position -> row of this handle (DeltaTree.vec_id): rerank candidates are then DFS positions."""
+        m = np.ascontiguousarray(vec_id, dtype=np.uint32)
+        check(self._lib.dpq_flat_set_id_map(self._h, _np_ptr(m), m.size), "dpq_flat_set_id_map")
+
+    def rerank(self, queries, cand_ids, top_k):
+        """Exact distances of cand_ids[nq][n_cand] only (negative = padding), the best top_k of them."""
+        q = self._queries(queries)
+        c = np.ascontiguousarray(cand_ids, dtype=np.int32)
+        if c.ndim != 2 or c.shape[0] != q.shape[0]:
+            raise ValueError("cand_ids must be [nq][n_cand]")
+        ids = np.empty((q.shape[0], top_k), dtype=np.int32)
+        dists = np.empty((q.shape[0], top_k), dtype=np.float32)
+        check(self._lib.dpq_flat_rerank_u8(self._h, _np_ptr(q), q.shape[0], _np_ptr(c), c.shape[1], top_k, _np_ptr(ids),
+                                           _np_ptr(dists)), "dpq_flat_rerank_u8")
+        return ids, dists
+
+    def rerank_torch(self, queries, cand_ids, top_k, out_ids=None, out_dists=None):
+        """rerank on device tensors, on torch's current stream (dpq_flat_rerank_u8_device); complete on return."""
+        import torch
+        if not isinstance(queries, torch.Tensor) or queries.dtype != torch.uint8:
+            raise TypeError("queries must be a uint8 tensor (FlatIndex takes fp32)")
+        assert queries.is_cuda and queries.is_contiguous() and queries.shape[1] == self.D
+        assert cand_ids.is_cuda and cand_ids.dtype == torch.int32 and cand_ids.is_contiguous()
+        assert cand_ids.shape[0] == queries.shape[0]
+        nq = queries.shape[0]
+        if out_ids is None:
+            out_ids = torch.empty((nq, top_k), dtype=torch.int32, device=queries.device)
+        if out_dists is None:
+            out_dists = torch.empty((nq, top_k), dtype=torch.float32, device=queries.device)
+        stream = torch.cuda.current_stream(queries.device).cuda_stream
+        check(self._lib.dpq_flat_rerank_u8_device(self._h, ctypes.c_void_p(queries.data_ptr()), nq,
+                                                  ctypes.c_void_p(cand_ids.data_ptr()), cand_ids.shape[1], top_k,
+                                                  ctypes.c_void_p(out_ids.data_ptr()), ctypes.c_void_p(out_dists.data_ptr()),
+                                                  ctypes.c_void_p(stream)), "dpq_flat_rerank_u8_device")
+        return out_ids, out_dists
+
+    def close(self):
+        if self._h is not None:
+            self._lib.dpq_flat_close(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 def read_vecs_range(path, first, count, ext="fvecs"):
     """Vectors [first, first + count) of an .fvecs/.bvecs file -> float32 [count][D]."""
     lib = _lib.load()
@@ -704,6 +796,16 @@ def read_vecs_range(path, first, count, ext="fvecs"):
     check(lib.dpq_read_vecs_range(path.encode(), int(ext == "bvecs"), first, count, D, None), "dpq_read_vecs_range")
     out = np.empty((count, D.value), dtype=np.float32)
     check(lib.dpq_read_vecs_range(path.encode(), int(ext == "bvecs"), first, count, D, _np_ptr(out)), "dpq_read_vecs_range")
+    return out
+
+
+def read_bvecs_range(path, first, count):
+    """Vectors [first, first + count) of a .bvecs file -> uint8 [count][D], the bytes as they are."""
+    lib = _lib.load()
+    D = _lib.c_i32()
+    check(lib.dpq_read_bvecs_range(path.encode(), first, count, D, None), "dpq_read_bvecs_range")
+    out = np.empty((count, D.value), dtype=np.uint8)
+    check(lib.dpq_read_bvecs_range(path.encode(), first, count, D, _np_ptr(out)), "dpq_read_bvecs_range")
     return out
 
 

@@ -140,12 +140,16 @@ struct dpq_filter {
     mutable int l0_n = -1;           // entries of l0_id (-1: not made yet)
 };
 
-// Raw fp32 vectors resident on one GPU (exact search, dpq_flat.hip).  Rows are stored padded to Dp floats.
+// Raw vectors resident on one GPU (exact search).  An fp32 handle (dpq_flat.hip) stores rows padded to Dp floats; a byte
+// handle (dpq_flat_u8.hip) stores them biased to int8 and padded to Dp bytes, with an int32 norm per row.
 struct dpq_flat {
     int device = 0;
     int64_t n = 0, id_offset = 0;
     int D = 0, Dp = 0;
+    bool u8 = false;              // opened by dpq_flat_open_u8
     DevBuf<float> base;           // [n][Dp]
+    DevBuf<int8_t> base8;         // [n][Dp] (byte handle)
+    DevBuf<int32_t> norm8;        // [n rounded up to 4]
     DevBuf<uint32_t> map;         // DFS position -> row (dpq_flat_set_id_map)
     std::vector<uint32_t> h_map;  // its host copy: dpq_flat_rerank checks candidates on the host
     // workspaces, grown on demand and kept until dpq_flat_close
@@ -154,7 +158,10 @@ struct dpq_flat {
     DevBuf<float> d_q, d_dists;
     DevBuf<int32_t> d_ids, d_cand;
     DevBuf<uint32_t> flag;
-    size_t keys_n = 0, state_n = 0, q_n = 0, out_n = 0, cand_n = 0;
+    DevBuf<uint8_t> q_raw;        // a byte handle's queries as given, biased and padded into q8, their norms in qnorm
+    DevBuf<int8_t> q8;
+    DevBuf<int32_t> qnorm;
+    size_t keys_n = 0, state_n = 0, q_n = 0, out_n = 0, cand_n = 0, q_raw_n = 0, q8_n = 0, qnorm_n = 0;
 };
 
 namespace {
@@ -2185,7 +2192,7 @@ int dpq_write_codewords(const char* path, const float* codewords, int M, int K, 
     });
 }
 
-// ---- exact search over raw vectors (dpq_flat.hip) ---------------------------------------------------------------
+// ---- exact search over raw vectors (dpq_flat.hip, dpq_flat_u8.hip) ----------------------------------------------
 
 }  // extern "C"
 
@@ -2201,8 +2208,9 @@ int grow(B& buf, size_t* have, size_t want) {
 }
 
 // Candidates of dpq_flat_rerank*, all device pointers; ends with one flag word read back.
-int flat_rerank_on_device(dpq_flat* f, const float* d_queries, int nq, const int32_t* d_cand, int n_cand, int top_k,
-                          int32_t* d_ids, float* d_dists, hipStream_t stream) {
+template <class Q>
+int flat_rerank_on_device(const char* fn, dpq_flat* f, const Q* d_queries, int nq, const int32_t* d_cand, int n_cand,
+                          int top_k, int32_t* d_ids, float* d_dists, hipStream_t stream) {
     const size_t n_pad = dpq::flat_rerank_keys(n_cand);
     const int per = (int)std::max<size_t>(1, std::min<size_t>((size_t)nq, ((size_t)64 << 20) / (n_pad * sizeof(uint64_t))));
     int rc = grow(f->keys, &f->keys_n, (size_t)per * n_pad);
@@ -2211,24 +2219,73 @@ int flat_rerank_on_device(dpq_flat* f, const float* d_queries, int nq, const int
     DPQ_HIP(hipMemsetAsync(f->flag, 0, sizeof(uint32_t), stream));
     for (int q0 = 0; q0 < nq; q0 += per) {
         const int m = std::min(per, nq - q0);
-        DPQ_HIP(dpq::launch_flat_rerank(f->base, f->n, f->D, f->Dp, d_queries + (size_t)q0 * f->D, m,
-                                        d_cand + (size_t)q0 * n_cand, n_cand, top_k, f->id_offset,
-                                        f->h_map.empty() ? nullptr : f->map.get(), (int64_t)f->h_map.size(), f->keys,
-                                        f->flag, d_ids + (size_t)q0 * top_k, d_dists + (size_t)q0 * top_k, stream));
+        const uint32_t* map = f->h_map.empty() ? nullptr : f->map.get();
+        if constexpr (std::is_same<Q, uint8_t>::value)
+            DPQ_HIP(dpq::launch_flat_rerank_u8(f->base8, f->n, f->D, f->Dp, d_queries + (size_t)q0 * f->D, m,
+                                               d_cand + (size_t)q0 * n_cand, n_cand, top_k, f->id_offset, map,
+                                               (int64_t)f->h_map.size(), f->keys, f->flag, d_ids + (size_t)q0 * top_k,
+                                               d_dists + (size_t)q0 * top_k, stream));
+        else
+            DPQ_HIP(dpq::launch_flat_rerank(f->base, f->n, f->D, f->Dp, d_queries + (size_t)q0 * f->D, m,
+                                            d_cand + (size_t)q0 * n_cand, n_cand, top_k, f->id_offset, map,
+                                            (int64_t)f->h_map.size(), f->keys, f->flag, d_ids + (size_t)q0 * top_k,
+                                            d_dists + (size_t)q0 * top_k, stream));
     }
     uint32_t bad = 0;
     DPQ_HIP(hipMemcpyAsync(&bad, f->flag, sizeof bad, hipMemcpyDeviceToHost, stream));
     DPQ_HIP(hipStreamSynchronize(stream));
-    if (bad) return fail(DPQ_ERR_ARG, "dpq_flat_rerank: a candidate names no row of this handle");
+    if (bad) return fail(DPQ_ERR_ARG, std::string(fn) + ": a candidate names no row of this handle");
     return DPQ_OK;
 }
 
-int flat_rerank_args(const dpq_flat* f, const void* queries, int nq, const void* cand, int n_cand, int top_k,
-                     const void* ids, const void* dists) {
-    if (!f || !queries || !cand || !ids || !dists || nq < 0) return fail(DPQ_ERR_ARG, "dpq_flat_rerank: NULL argument or nq < 0");
+// A handle takes the calls of its own kind only: the fp32 functions an fp32 handle, the _u8 functions a byte handle.
+int flat_kind(const dpq_flat* f, bool u8, const char* fn, const char* other) {
+    if (f->u8 == u8) return DPQ_OK;
+    return fail(DPQ_ERR_ARG, std::string(fn) + (u8 ? ": the handle holds fp32 vectors (dpq_flat_open); call "
+                                                   : ": the handle holds byte vectors (dpq_flat_open_u8); call ") + other);
+}
+
+int flat_rerank_args(const char* fn, const char* other, const dpq_flat* f, bool u8, const void* queries, int nq,
+                     const void* cand, int n_cand, int top_k, const void* ids, const void* dists) {
+    if (!f || !queries || !cand || !ids || !dists || nq < 0) return fail(DPQ_ERR_ARG, std::string(fn) + ": NULL argument or nq < 0");
+    if (int rc = flat_kind(f, u8, fn, other)) return rc;
     if (top_k < 1 || top_k > n_cand || n_cand > dpq::kFlatMaxTopK)
-        return fail(DPQ_ERR_ARG, "dpq_flat_rerank: needs 1 <= top_k <= n_cand <= 16384");
+        return fail(DPQ_ERR_ARG, std::string(fn) + ": needs 1 <= top_k <= n_cand <= 16384");
     return DPQ_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+}  // extern "C"
+
+namespace {
+
+// The checks of dpq_flat_open / dpq_flat_open_u8: the arguments before any device call, then the device.
+int flat_open_args(const char* fn, const void* vectors, int64_t n, int D, int device, int64_t id_offset, dpq_flat** out) {
+    const std::string who(fn);
+    if (out) *out = nullptr;
+    if (!vectors || !out) return fail(DPQ_ERR_ARG, who + ": NULL argument");
+    if (n < 1) return fail(DPQ_ERR_ARG, who + ": n < 1");
+    if (D < 1 || D > dpq::kFlatMaxD) return fail(DPQ_ERR_ARG, who + ": D outside 1..2048");
+    if (id_offset < 0 || n + id_offset >= ((int64_t)1 << 31))
+        return fail(DPQ_ERR_ARG, who + ": id_offset < 0 or n + id_offset >= 2^31 (ids are int32)");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail(DPQ_ERR_NO_DEVICE, "no HIP device visible; this library has no CPU fallback");
+    if (device < 0 || device >= ndev) return fail(DPQ_ERR_NO_DEVICE, "device ordinal out of range");
+    DPQ_HIP(hipSetDevice(device));
+    return DPQ_OK;
+}
+
+int grow_outputs(dpq_flat* f, size_t want) {
+    if (f->out_n >= want) return DPQ_OK;
+    f->out_n = 0;
+    int rc = f->d_ids.alloc(want);
+    if (!rc) rc = f->d_dists.alloc(want);
+    if (!rc) f->out_n = want;
+    return rc;
 }
 
 }  // namespace
@@ -2237,17 +2294,7 @@ extern "C" {
 
 int dpq_flat_open(const float* vectors, int64_t n, int D, int device, int64_t id_offset, dpq_flat** out) {
     return guarded([&]() -> int {
-    if (out) *out = nullptr;
-    if (!vectors || !out) return fail(DPQ_ERR_ARG, "dpq_flat_open: NULL argument");
-    if (n < 1) return fail(DPQ_ERR_ARG, "dpq_flat_open: n < 1");
-    if (D < 1 || D > dpq::kFlatMaxD) return fail(DPQ_ERR_ARG, "dpq_flat_open: D outside 1..2048");
-    if (id_offset < 0 || n + id_offset >= ((int64_t)1 << 31))
-        return fail(DPQ_ERR_ARG, "dpq_flat_open: id_offset < 0 or n + id_offset >= 2^31 (ids are int32)");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(DPQ_ERR_NO_DEVICE, "no HIP device visible; this library has no CPU fallback");
-    if (device < 0 || device >= ndev) return fail(DPQ_ERR_NO_DEVICE, "device ordinal out of range");
-    DPQ_HIP(hipSetDevice(device));
+    if (int rc = flat_open_args("dpq_flat_open", vectors, n, D, device, id_offset, out)) return rc;
     std::unique_ptr<dpq_flat> f(new dpq_flat);
     f->device = device;
     f->n = n;
@@ -2274,6 +2321,36 @@ int dpq_flat_open(const float* vectors, int64_t n, int D, int device, int64_t id
     });
 }
 
+int dpq_flat_open_u8(const uint8_t* vectors, int64_t n, int D, int device, int64_t id_offset, dpq_flat** out) {
+    return guarded([&]() -> int {
+    if (int rc = flat_open_args("dpq_flat_open_u8", vectors, n, D, device, id_offset, out)) return rc;
+    std::unique_ptr<dpq_flat> f(new dpq_flat);
+    f->device = device;
+    f->n = n;
+    f->id_offset = id_offset;
+    f->D = D;
+    f->Dp = dpq::flat_u8_padded_d(D);
+    f->u8 = true;
+    int rc = f->base8.alloc((size_t)n * f->Dp);
+    if (!rc) rc = f->norm8.alloc((size_t)((n + 3) & ~(int64_t)3));
+    if (rc) return fail(rc, "dpq_flat_open_u8: the vectors do not fit into device memory (" + g_last_error + ")");
+    // the norm array's padding is read by the last stripe's 16-byte loads (and masked afterwards): keep it defined
+    DPQ_HIP(hipMemset(f->norm8.get() + ((n - 1) & ~(int64_t)3), 0, 4 * sizeof(int32_t)));
+    const int64_t tile = std::max<int64_t>(1, ((int64_t)128 << 20) / D);  // rows per upload (128 MB); biased on the device
+    DevBuf<uint8_t> tmp;
+    if ((rc = tmp.alloc((size_t)std::min(n, tile) * D))) return rc;
+    for (int64_t r0 = 0; r0 < n; r0 += tile) {
+        const int64_t m = std::min(tile, n - r0);
+        DPQ_HIP(hipMemcpy(tmp, vectors + (size_t)r0 * D, (size_t)m * D, hipMemcpyHostToDevice));
+        DPQ_HIP(dpq::launch_flat_u8_prepare(tmp, m, D, f->Dp, f->base8.get() + (size_t)r0 * f->Dp, f->norm8.get() + r0,
+                                            nullptr));
+        DPQ_HIP(hipDeviceSynchronize());
+    }
+    *out = f.release();
+    return DPQ_OK;
+    });
+}
+
 int dpq_flat_close(dpq_flat* f) {
     return guarded([&]() -> int {
     if (!f) return DPQ_OK;
@@ -2287,6 +2364,7 @@ int dpq_flat_search(dpq_flat* f, const float* queries, int nq, int top_k, int32_
     return guarded([&]() -> int {
     if (!f || !queries || !ids || !dists || nq < 0) return fail(DPQ_ERR_ARG, "dpq_flat_search: NULL argument or nq < 0");
     if (top_k < 1 || top_k > DPQ_FLAT_MAX_TOPK) return fail(DPQ_ERR_ARG, "dpq_flat_search: top_k outside 1..DPQ_FLAT_MAX_TOPK");
+    if (int rc = flat_kind(f, false, "dpq_flat_search", "dpq_flat_search_u8")) return rc;
     if (top_k > f->n) return fail(DPQ_ERR_TOPK, "dpq_flat_search: top_k exceeds the number of vectors");
     if (nq == 0) return DPQ_OK;
     DPQ_HIP(hipSetDevice(f->device));
@@ -2326,6 +2404,42 @@ int dpq_flat_search(dpq_flat* f, const float* queries, int nq, int top_k, int32_
     });
 }
 
+int dpq_flat_search_u8(dpq_flat* f, const uint8_t* queries, int nq, int top_k, int32_t* ids, float* dists) {
+    return guarded([&]() -> int {
+    if (!f || !queries || !ids || !dists || nq < 0) return fail(DPQ_ERR_ARG, "dpq_flat_search_u8: NULL argument or nq < 0");
+    if (top_k < 1 || top_k > DPQ_FLAT_MAX_TOPK)
+        return fail(DPQ_ERR_ARG, "dpq_flat_search_u8: top_k outside 1..DPQ_FLAT_MAX_TOPK");
+    if (int rc = flat_kind(f, true, "dpq_flat_search_u8", "dpq_flat_search")) return rc;
+    if (top_k > f->n) return fail(DPQ_ERR_TOPK, "dpq_flat_search_u8: top_k exceeds the number of vectors");
+    if (nq == 0) return DPQ_OK;
+    DPQ_HIP(hipSetDevice(f->device));
+    const int D = f->D, Dp = f->Dp;
+    const int qb = std::min(nq, dpq::flat_query_batch(top_k));
+    int rc = grow(f->keys, &f->keys_n, (size_t)qb * dpq::flat_key_capacity(top_k));
+    if (!rc) rc = grow(f->state, &f->state_n, (size_t)qb);
+    if (!rc) rc = grow(f->q_raw, &f->q_raw_n, (size_t)qb * D);
+    if (!rc) rc = grow(f->q8, &f->q8_n, (size_t)qb * Dp);
+    if (!rc) rc = grow(f->qnorm, &f->qnorm_n, (size_t)qb);
+    if (!rc) rc = grow_outputs(f, (size_t)qb * top_k);
+    if (rc) return rc;
+    std::vector<dpq::FlatQueryState> st((size_t)qb);
+    for (int q0 = 0; q0 < nq; q0 += qb) {
+        const int m = std::min(qb, nq - q0);
+        DPQ_HIP(hipMemcpy(f->q_raw, queries + (size_t)q0 * D, (size_t)m * D, hipMemcpyHostToDevice));
+        DPQ_HIP(dpq::launch_flat_u8_prepare(f->q_raw, m, D, Dp, f->q8, f->qnorm, nullptr));
+        DPQ_HIP(dpq::launch_flat_search_u8(f->base8, f->norm8, f->n, Dp, f->q8, f->qnorm, m, top_k, f->id_offset, f->keys,
+                                           f->state, f->d_ids, f->d_dists, nullptr));
+        DPQ_HIP(hipMemcpy(ids + (size_t)q0 * top_k, f->d_ids, (size_t)m * top_k * sizeof(int32_t), hipMemcpyDeviceToHost));
+        DPQ_HIP(hipMemcpy(dists + (size_t)q0 * top_k, f->d_dists, (size_t)m * top_k * sizeof(float), hipMemcpyDeviceToHost));
+        DPQ_HIP(hipMemcpy(st.data(), f->state, (size_t)m * sizeof(dpq::FlatQueryState), hipMemcpyDeviceToHost));
+        for (int q = 0; q < m; ++q)
+            if (st[(size_t)q].overflow || st[(size_t)q].count != (uint32_t)top_k)
+                return fail(DPQ_ERR_STATE, "dpq_flat_search_u8: internal error: a key buffer overflowed");
+    }
+    return DPQ_OK;
+    });
+}
+
 int dpq_flat_set_id_map(dpq_flat* f, const uint32_t* map, int64_t n_map) {
     return guarded([&]() -> int {
     if (!f || !map || n_map < 1 || n_map >= ((int64_t)1 << 31)) return fail(DPQ_ERR_ARG, "dpq_flat_set_id_map: bad argument");
@@ -2342,20 +2456,28 @@ int dpq_flat_set_id_map(dpq_flat* f, const uint32_t* map, int64_t n_map) {
     });
 }
 
-int dpq_flat_rerank_device(dpq_flat* f, const float* d_queries, int nq, const int32_t* d_cand_ids, int n_cand, int top_k,
-                           int32_t* d_ids, float* d_dists, void* hip_stream) {
-    return guarded([&]() -> int {
-    int rc = flat_rerank_args(f, d_queries, nq, d_cand_ids, n_cand, top_k, d_ids, d_dists);
+}  // extern "C"
+
+namespace {
+
+// dpq_flat_rerank_device / _u8_device: Q is float or uint8_t, the handle of the same kind.
+template <class Q>
+int flat_rerank_device_call(const char* fn, const char* other, dpq_flat* f, const Q* d_queries, int nq,
+                            const int32_t* d_cand_ids, int n_cand, int top_k, int32_t* d_ids, float* d_dists,
+                            void* hip_stream) {
+    int rc = flat_rerank_args(fn, other, f, std::is_same<Q, uint8_t>::value, d_queries, nq, d_cand_ids, n_cand, top_k, d_ids,
+                              d_dists);
     if (rc || nq == 0) return rc;
     DPQ_HIP(hipSetDevice(f->device));
-    return flat_rerank_on_device(f, d_queries, nq, d_cand_ids, n_cand, top_k, d_ids, d_dists, (hipStream_t)hip_stream);
-    });
+    return flat_rerank_on_device(fn, f, d_queries, nq, d_cand_ids, n_cand, top_k, d_ids, d_dists, (hipStream_t)hip_stream);
 }
 
-int dpq_flat_rerank(dpq_flat* f, const float* queries, int nq, const int32_t* cand_ids, int n_cand, int top_k, int32_t* ids,
-                    float* dists) {
-    return guarded([&]() -> int {
-    int rc = flat_rerank_args(f, queries, nq, cand_ids, n_cand, top_k, ids, dists);
+// dpq_flat_rerank / _u8: the candidates are checked on the host, then queries and candidates go up and the answer down.
+template <class Q>
+int flat_rerank_host_call(const char* fn, const char* other, dpq_flat* f, const Q* queries, int nq,
+                          const int32_t* cand_ids, int n_cand, int top_k, int32_t* ids, float* dists) {
+    constexpr bool u8 = std::is_same<Q, uint8_t>::value;
+    int rc = flat_rerank_args(fn, other, f, u8, queries, nq, cand_ids, n_cand, top_k, ids, dists);
     if (rc || nq == 0) return rc;
     const int64_t n_map = (int64_t)f->h_map.size();
     for (size_t i = 0; i < (size_t)nq * n_cand; ++i) {
@@ -2366,31 +2488,72 @@ int dpq_flat_rerank(dpq_flat* f, const float* queries, int nq, const int32_t* ca
             ok = c < n_map || (c == n_map && (n_map & 1) == 0);
         else
             ok = c - f->id_offset >= 0 && c - f->id_offset < f->n;
-        if (!ok) return fail(DPQ_ERR_ARG, "dpq_flat_rerank: a candidate names no row of this handle");
+        if (!ok) return fail(DPQ_ERR_ARG, std::string(fn) + ": a candidate names no row of this handle");
     }
     DPQ_HIP(hipSetDevice(f->device));
-    rc = grow(f->d_q, &f->q_n, (size_t)nq * f->D);
-    if (!rc) rc = grow(f->d_cand, &f->cand_n, (size_t)nq * n_cand);
-    if (!rc && f->out_n < (size_t)nq * top_k) {
-        f->out_n = 0;
-        rc = f->d_ids.alloc((size_t)nq * top_k);
-        if (!rc) rc = f->d_dists.alloc((size_t)nq * top_k);
-        if (!rc) f->out_n = (size_t)nq * top_k;
+    Q* d_q;
+    if constexpr (u8) {
+        rc = grow(f->q_raw, &f->q_raw_n, (size_t)nq * f->D);
+        d_q = f->q_raw;
+    } else {
+        rc = grow(f->d_q, &f->q_n, (size_t)nq * f->D);
+        d_q = f->d_q;
     }
+    if (!rc) rc = grow(f->d_cand, &f->cand_n, (size_t)nq * n_cand);
+    if (!rc) rc = grow_outputs(f, (size_t)nq * top_k);
     if (rc) return rc;
-    DPQ_HIP(hipMemcpy(f->d_q, queries, (size_t)nq * f->D * sizeof(float), hipMemcpyHostToDevice));
+    DPQ_HIP(hipMemcpy(d_q, queries, (size_t)nq * f->D * sizeof(Q), hipMemcpyHostToDevice));
     DPQ_HIP(hipMemcpy(f->d_cand, cand_ids, (size_t)nq * n_cand * sizeof(int32_t), hipMemcpyHostToDevice));
-    rc = flat_rerank_on_device(f, f->d_q, nq, f->d_cand, n_cand, top_k, f->d_ids, f->d_dists, nullptr);
+    rc = flat_rerank_on_device(fn, f, d_q, nq, f->d_cand, n_cand, top_k, f->d_ids, f->d_dists, nullptr);
     if (rc) return rc;
     DPQ_HIP(hipMemcpy(ids, f->d_ids, (size_t)nq * top_k * sizeof(int32_t), hipMemcpyDeviceToHost));
     DPQ_HIP(hipMemcpy(dists, f->d_dists, (size_t)nq * top_k * sizeof(float), hipMemcpyDeviceToHost));
     return DPQ_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dpq_flat_rerank_device(dpq_flat* f, const float* d_queries, int nq, const int32_t* d_cand_ids, int n_cand, int top_k,
+                           int32_t* d_ids, float* d_dists, void* hip_stream) {
+    return guarded([&]() -> int {
+    return flat_rerank_device_call("dpq_flat_rerank", "dpq_flat_rerank_u8_device", f, d_queries, nq, d_cand_ids, n_cand,
+                                   top_k, d_ids, d_dists, hip_stream);
     });
 }
 
-int dpq_read_vecs_range(const char* path, int is_bvecs, int64_t first, int64_t count, int32_t* D, float* out) {
+int dpq_flat_rerank(dpq_flat* f, const float* queries, int nq, const int32_t* cand_ids, int n_cand, int top_k, int32_t* ids,
+                    float* dists) {
     return guarded([&]() -> int {
-    if (!path || !D || first < 0 || count < 0) return fail(DPQ_ERR_ARG, "bad argument to dpq_read_vecs_range");
+    return flat_rerank_host_call("dpq_flat_rerank", "dpq_flat_rerank_u8", f, queries, nq, cand_ids, n_cand, top_k, ids, dists);
+    });
+}
+
+int dpq_flat_rerank_u8_device(dpq_flat* f, const uint8_t* d_queries, int nq, const int32_t* d_cand_ids, int n_cand,
+                              int top_k, int32_t* d_ids, float* d_dists, void* hip_stream) {
+    return guarded([&]() -> int {
+    return flat_rerank_device_call("dpq_flat_rerank_u8_device", "dpq_flat_rerank_device", f, d_queries, nq, d_cand_ids,
+                                   n_cand, top_k, d_ids, d_dists, hip_stream);
+    });
+}
+
+int dpq_flat_rerank_u8(dpq_flat* f, const uint8_t* queries, int nq, const int32_t* cand_ids, int n_cand, int top_k,
+                       int32_t* ids, float* dists) {
+    return guarded([&]() -> int {
+    return flat_rerank_host_call("dpq_flat_rerank_u8", "dpq_flat_rerank", f, queries, nq, cand_ids, n_cand, top_k, ids, dists);
+    });
+}
+
+}  // extern "C"
+
+namespace {
+
+// Records [first, first + count) of an .fvecs / .bvecs file into out[count][D]: T = float widens bytes, T = uint8_t
+// (bvecs only) keeps them.
+template <class T>
+int read_vecs_range(const char* fn, const char* path, bool is_bvecs, int64_t first, int64_t count, int32_t* D, T* out) {
+    if (!path || !D || first < 0 || count < 0) return fail(DPQ_ERR_ARG, std::string("bad argument to ") + fn);
     FILE* fp = fopen(path, "rb");
     if (!fp) return fail(DPQ_ERR_IO, std::string("cannot open ") + path);
     std::unique_ptr<FILE, int (*)(FILE*)> closer(fp, fclose);
@@ -2415,15 +2578,26 @@ int dpq_read_vecs_range(const char* path, int is_bvecs, int64_t first, int64_t c
             int32_t dd;
             memcpy(&dd, p, 4);
             if (dd != d) return fail(DPQ_ERR_IO, std::string("a record of another dimension in ") + path);
-            float* o = out + (size_t)(r0 + r) * d;
+            T* o = out + (size_t)(r0 + r) * d;
             if (is_bvecs)
-                for (int j = 0; j < d; ++j) o[j] = (float)p[4 + j];
+                for (int j = 0; j < d; ++j) o[j] = (T)p[4 + j];
             else
                 memcpy(o, p + 4, (size_t)d * 4);
         }
     }
     return DPQ_OK;
-    });
+}
+
+}  // namespace
+
+extern "C" {
+
+int dpq_read_vecs_range(const char* path, int is_bvecs, int64_t first, int64_t count, int32_t* D, float* out) {
+    return guarded([&]() -> int { return read_vecs_range("dpq_read_vecs_range", path, is_bvecs != 0, first, count, D, out); });
+}
+
+int dpq_read_bvecs_range(const char* path, int64_t first, int64_t count, int32_t* D, uint8_t* out) {
+    return guarded([&]() -> int { return read_vecs_range("dpq_read_bvecs_range", path, true, first, count, D, out); });
 }
 
 int dpq_write_groundtruth(const char* path, const int32_t* ids, const float* dists, int nq, int top_k) {

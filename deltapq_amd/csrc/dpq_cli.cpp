@@ -262,6 +262,7 @@ int main(int argc, char* argv[]) {
     if (task == "groundtruth") {
         // The other binary's `pqtree -task groundtruth` (main.cpp:569-669): brute force over base.{ext}, streamed in
         // parts; every part is a dpq_flat handle with its own id offset, the partial lists meet in dpq_merge_topk_host.
+        // With -ext bvecs the bytes stay bytes (dpq_flat_open_u8 / dpq_flat_search_u8): the same bits, the same file.
         if (dataset.empty() || !topk_given || top_k < 1 || query_size < 1) {
             std::cout << "usage: deltapq -dataset DIR -task groundtruth -topk K -query_size Q [-N N] [-ext fvecs|bvecs]" << std::endl;
             return 2;
@@ -277,8 +278,15 @@ int main(int argc, char* argv[]) {
             return 1;
         }
         const int nq = query_size;
-        std::vector<float> queries((size_t)nq * D);
-        rc = dpq_read_vecs(q_path.c_str(), bvecs, &nq_file, &D, queries.data(), nq);
+        std::vector<float> queries;    // -ext fvecs
+        std::vector<uint8_t> queries8;  // -ext bvecs: the bytes stay bytes
+        if (bvecs) {
+            queries8.resize((size_t)nq * D);
+            rc = dpq_read_bvecs_range(q_path.c_str(), 0, nq, &D, queries8.data());
+        } else {
+            queries.resize((size_t)nq * D);
+            rc = dpq_read_vecs(q_path.c_str(), bvecs, &nq_file, &D, queries.data(), nq);
+        }
         if (rc) return die("ReadTopN", rc);
         rc = dpq_read_vecs(base_path.c_str(), bvecs, &n_file, &Db, nullptr, 0);
         if (rc) return die("ItrReader", rc);
@@ -296,7 +304,9 @@ int main(int argc, char* argv[]) {
             std::cout << "no GPU visible: this build has no CPU search path" << std::endl;
             return 1;
         }
-        int64_t part_rows = std::max<int64_t>(1, ((int64_t)1 << 29) / D);  // at most 2 GB of floats per part
+        // at most 2 GB per part: of floats, or with -ext bvecs of bytes (a byte handle, four times as many rows)
+        int64_t part_rows = std::max<int64_t>(1, ((int64_t)1 << (bvecs ? 31 : 29)) / D);
+        std::vector<uint8_t> part8;
         if (const char* dev = getenv("DPQ_DEV"))
             if (atoi(dev) != 0)
                 if (const char* e = getenv("DPQ_GT_PART_ROWS")) part_rows = std::max<int64_t>(1, atoll(e));  // developer knob
@@ -310,17 +320,25 @@ int main(int argc, char* argv[]) {
         int n_parts = 0;
         for (int64_t r0 = 0; r0 < n; r0 += part_rows, ++n_parts) {
             const int64_t rows = std::min(part_rows, n - r0);
-            part.resize((size_t)rows * D);
-            rc = dpq_read_vecs_range(base_path.c_str(), bvecs, r0, rows, &Db, part.data());
-            if (rc) return die("ItrReader", rc);
             dpq_flat* f = nullptr;
-            rc = dpq_flat_open(part.data(), rows, D, 0, r0, &f);
-            if (rc) return die("dpq_flat_open", rc);
+            if (bvecs) {
+                part8.resize((size_t)rows * D);
+                rc = dpq_read_bvecs_range(base_path.c_str(), r0, rows, &Db, part8.data());
+                if (rc) return die("ItrReader", rc);
+                rc = dpq_flat_open_u8(part8.data(), rows, D, 0, r0, &f);
+            } else {
+                part.resize((size_t)rows * D);
+                rc = dpq_read_vecs_range(base_path.c_str(), bvecs, r0, rows, &Db, part.data());
+                if (rc) return die("ItrReader", rc);
+                rc = dpq_flat_open(part.data(), rows, D, 0, r0, &f);
+            }
+            if (rc) return die(bvecs ? "dpq_flat_open_u8" : "dpq_flat_open", rc);
             const int kk = (int)std::min<int64_t>(top_k, rows);  // a short last part gives a short list, padded
             p_ids.resize((size_t)nq * kk);
             p_dists.resize((size_t)nq * kk);
-            rc = dpq_flat_search(f, queries.data(), nq, kk, p_ids.data(), p_dists.data());
-            if (rc) return die("dpq_flat_search", rc);
+            rc = bvecs ? dpq_flat_search_u8(f, queries8.data(), nq, kk, p_ids.data(), p_dists.data())
+                       : dpq_flat_search(f, queries.data(), nq, kk, p_ids.data(), p_dists.data());
+            if (rc) return die(bvecs ? "dpq_flat_search_u8" : "dpq_flat_search", rc);
             dpq_flat_close(f);
             for (int q = 0; q < nq; ++q)
                 for (int r = 0; r < top_k; ++r) {
@@ -444,29 +462,42 @@ int main(int argc, char* argv[]) {
         snprintf(line, sizeof line, "recall@%d = %.6f", top_k, rec);
         std::cout << line << std::endl;
         if (rerank) {
-            std::vector<float> base((size_t)N * D);
+            const std::string base_path = dataset + "/base." + ext;
             int32_t Db = 0;
-            rc = dpq_read_vecs_range((dataset + "/base." + ext).c_str(), bvecs, 0, N, &Db, nullptr);
+            rc = dpq_read_vecs_range(base_path.c_str(), bvecs, 0, N, &Db, nullptr);
             if (!rc && Db != D) {
                 std::cout << "query dimension " << D << " != base dimension " << Db << std::endl;
                 return 1;
             }
-            if (!rc) rc = dpq_read_vecs_range((dataset + "/base." + ext).c_str(), bvecs, 0, N, &Db, base.data());
             if (rc) return die("ItrReader", rc);
             dpq_flat* f = nullptr;
-            rc = dpq_flat_open(base.data(), N, D, 0, 0, &f);
+            std::vector<uint8_t> queries8;
+            if (bvecs) {  // bytes stay bytes: a byte handle and the _u8 calls, the same bits
+                std::vector<uint8_t> base8((size_t)N * D);
+                queries8.resize((size_t)nq * D);
+                rc = dpq_read_bvecs_range(base_path.c_str(), 0, N, &Db, base8.data());
+                if (!rc) rc = dpq_read_bvecs_range(q_path.c_str(), 0, nq, &Db, queries8.data());
+                if (rc) return die("ItrReader", rc);
+                rc = dpq_flat_open_u8(base8.data(), N, D, 0, 0, &f);
+            } else {
+                std::vector<float> base((size_t)N * D);
+                rc = dpq_read_vecs_range(base_path.c_str(), bvecs, 0, N, &Db, base.data());
+                if (rc) return die("ItrReader", rc);
+                rc = dpq_flat_open(base.data(), N, D, 0, 0, &f);
+            }
             if (rc == DPQ_ERR_NOMEM) {
                 std::cout << "-rerank: base." << ext << " (" << N << " x " << D << ") does not fit into device memory" << std::endl;
                 return 1;
             }
-            if (rc) return die("dpq_flat_open", rc);
+            if (rc) return die(bvecs ? "dpq_flat_open_u8" : "dpq_flat_open", rc);
             rc = dpq_flat_set_id_map(f, vec_id.data(), N);
             if (rc) return die("dpq_flat_set_id_map", rc);
             std::vector<int32_t> r_ids((size_t)nq * top_k);
             std::vector<float> r_d((size_t)nq * top_k);
             const double t1 = Elapsed();
-            rc = dpq_flat_rerank(f, queries.data(), nq, pos.data(), R, top_k, r_ids.data(), r_d.data());
-            if (rc) return die("dpq_flat_rerank", rc);
+            rc = bvecs ? dpq_flat_rerank_u8(f, queries8.data(), nq, pos.data(), R, top_k, r_ids.data(), r_d.data())
+                       : dpq_flat_rerank(f, queries.data(), nq, pos.data(), R, top_k, r_ids.data(), r_d.data());
+            if (rc) return die(bvecs ? "dpq_flat_rerank_u8" : "dpq_flat_rerank", rc);
             std::cout << "re-rank " << (Elapsed() - t1) / (double)nq * 1000 << " [msec/query] " << std::endl;
             dpq_flat_close(f);
             rc = dpq_recall(r_ids.data(), top_k, top_k, truth.data(), g_k, top_k, nq, &rec);

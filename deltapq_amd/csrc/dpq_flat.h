@@ -1,6 +1,6 @@
-// dpq_flat.h -- exact L2 search over raw fp32 vectors on the GPU (dpq_flat.hip): ground truth over a whole base,
-// re-ranking over a candidate list per query.  The arithmetic is the reference's brute force (main.cpp:150-156),
-// restated in include/deltapq_amd.h and DESIGN.md 5.10.
+// dpq_flat.h -- exact L2 search over raw vectors on the GPU: fp32 (dpq_flat.hip) and bytes on the int8 matrix cores
+// (dpq_flat_u8.hip); ground truth over a whole base, re-ranking over a candidate list per query.  The arithmetic is
+// the reference's brute force (main.cpp:150-156), restated in include/deltapq_amd.h and DESIGN.md 5.10.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -45,5 +45,34 @@ size_t flat_rerank_keys(int n_cand);  // keys per query launch_flat_rerank needs
 
 // [rows][D] -> [rows][Dp] with zero padding, on the device.
 hipError_t launch_flat_pad_rows(const float* d_in, int64_t rows, int D, int Dp, float* d_out, hipStream_t stream);
+
+// The stages of a search that do not depend on how distances are formed, for dpq_flat_u8.hip: the kernels of
+// launch_flat_search / launch_flat_rerank, launched one at a time.
+hipError_t launch_flat_init_state(FlatQueryState* d_state, int nq, hipStream_t stream);
+// Every buffer above `limit` (>= top_k) keys is cut down to its top_k smallest and its threshold lowered.
+hipError_t launch_flat_select(uint64_t* d_keys, int cap, FlatQueryState* d_state, int nq, int top_k, uint32_t limit,
+                              hipStream_t stream);
+// Sorts n_keys keys per query (d_state[q].count of them when d_state is given), drops repeats, writes top_k.
+hipError_t launch_flat_sort_emit(const uint64_t* d_keys, size_t stride, const FlatQueryState* d_state, int nq, int n_keys,
+                                 int top_k, int32_t* d_ids, float* d_dists, hipStream_t stream);
+
+// ---- byte vectors on the int8 matrix cores (dpq_flat_u8.hip) -------------------------------------------------------
+// Rows are stored as x ^ 0x80 (int8), padded with int8 zeros to the K step of v_mfma_i32_32x32x32_i8, with an int32
+// norm per row; the norm array of a base is allocated rounded up to four rows (16-byte loads in the epilogue).
+constexpr int kFlatU8KStep = 32;
+inline int flat_u8_padded_d(int D) { return (D + kFlatU8KStep - 1) & ~(kFlatU8KStep - 1); }
+
+// bytes [rows][D] -> biased int8 [rows][Dp] and norms [rows], on the device.
+hipError_t launch_flat_u8_prepare(const uint8_t* d_in, int64_t rows, int D, int Dp, int8_t* d_out, int32_t* d_norms,
+                                  hipStream_t stream);
+// launch_flat_search over prepared bytes: d_base [n][Dp] with d_vnorm, d_queries [nq][Dp] with d_qnorm.
+hipError_t launch_flat_search_u8(const int8_t* d_base, const int32_t* d_vnorm, int64_t n, int Dp, const int8_t* d_queries,
+                                 const int32_t* d_qnorm, int nq, int top_k, int64_t id_offset, uint64_t* d_keys,
+                                 FlatQueryState* d_state, int32_t* d_ids, float* d_dists, hipStream_t stream);
+// launch_flat_rerank over a prepared base; d_queries are the caller's bytes [nq][D], unpadded.
+hipError_t launch_flat_rerank_u8(const int8_t* d_base, int64_t n, int D, int Dp, const uint8_t* d_queries, int nq,
+                                 const int32_t* d_cand, int n_cand, int top_k, int64_t id_offset, const uint32_t* d_map,
+                                 int64_t n_map, uint64_t* d_keys, uint32_t* d_flag, int32_t* d_ids, float* d_dists,
+                                 hipStream_t stream);
 
 }  // namespace dpq

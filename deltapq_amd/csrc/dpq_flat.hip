@@ -388,4 +388,25 @@ hipError_t launch_flat_rerank(const float* d_base, int64_t n, int D, int Dp, con
     return hipGetLastError();
 }
 
+hipError_t launch_flat_init_state(FlatQueryState* d_state, int nq, hipStream_t stream) {
+    flat_init_state_kernel<<<dim3((nq + 255) / 256), dim3(256), 0, stream>>>(d_state, nq);
+    return hipGetLastError();
+}
+
+hipError_t launch_flat_select(uint64_t* d_keys, int cap, FlatQueryState* d_state, int nq, int top_k, uint32_t limit,
+                              hipStream_t stream) {
+    flat_select_kernel<<<dim3(nq), dim3(kSelThreads), 0, stream>>>(d_keys, cap, d_state, top_k, limit);
+    return hipGetLastError();
+}
+
+hipError_t launch_flat_sort_emit(const uint64_t* d_keys, size_t stride, const FlatQueryState* d_state, int nq, int n_keys,
+                                 int top_k, int32_t* d_ids, float* d_dists, hipStream_t stream) {
+    hipError_t e = ensure_sort_lds();
+    if (e != hipSuccess) return e;
+    const int n_pad = pow2_at_least(n_keys);
+    flat_sort_emit_kernel<<<dim3(nq), dim3(kSelThreads), (size_t)n_pad * sizeof(uint64_t), stream>>>(
+        d_keys, stride, d_state, n_keys, n_pad, top_k, d_ids, d_dists);
+    return hipGetLastError();
+}
+
 }  // namespace dpq

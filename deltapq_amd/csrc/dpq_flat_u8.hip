@@ -1,0 +1,306 @@
+// dpq_flat_u8.hip -- exact L2 distances between byte queries and byte base vectors on the int8 matrix cores of gfx950
+// (DESIGN.md 5.10.1).
+//
+// With v, q in {0..255}^D and D <= 2048 every intermediate of the fp32 path's arithmetic (dpq_flat.hip) is an exactly
+// representable integer: |t| <= 255, s <= 65025, acc <= 2048 * 65025 < 2^31.  The reported distance is therefore
+// (float)(int32)sum (v[d] - q[d])^2, round to nearest even, whatever the order of the sum -- the same bits as
+// flat_dist_kernel gives on the widened data.
+//
+// The MFMA operands are signed bytes, so a value x is stored as x ^ 0x80 (x - 128 as int8), rows padded with int8 zeros
+// to a multiple of 32 bytes, with the int32 norm |v'|^2 beside them.  Differences are unchanged by the bias:
+//     |v - q|^2 = |v'|^2 + |q'|^2 - 2 v'.q'      all in int32, |v'.q'| <= 2048 * 128^2 = 2^25.
+// An int8 zero adds nothing to a dot product or a norm, so padding is invisible.
+//
+//   flat_u8_bias_rows_kernel   bytes [rows][D] -> biased int8 [rows][Dp], padded
+//   flat_u8_norms_kernel       a lane per row: its int32 norm
+//   flat_dist_u8_kernel        a workgroup takes 64 queries x 256 vectors, a wavefront 64 x 64 as 2 x 2 tiles of
+//                              v_mfma_i32_32x32x32_i8 (A = vectors, B = queries); a lane's operand of a K step is 16
+//                              contiguous bytes of one row, loaded straight from global memory.  The epilogue forms the
+//                              int32 distances and appends keys under flat_dist_kernel's threshold / counter protocol.
+//   flat_rerank_u8_kernel      a lane per candidate; a wavefront fetches its 64 rows with 16-byte loads into LDS, 128
+//                              bytes of a row at a time, and every lane then sums its own row in int32.
+// State, selection and the final sort are dpq_flat.hip's kernels, unchanged.
+#include "dpq_flat.h"
+
+#include <algorithm>
+
+namespace dpq {
+namespace {
+
+using i32x4 = __attribute__((ext_vector_type(4))) int;
+using i32x16 = __attribute__((ext_vector_type(16))) int;
+
+constexpr int UQ = 64;    // queries of a workgroup's tile
+constexpr int UV = 256;   // vectors of a workgroup's tile: 64 per wavefront
+constexpr int KS = 32;    // bytes of a row one MFMA consumes (kFlatU8KStep)
+constexpr int RC = 128;   // bytes of a row the re-rank stages at a time
+constexpr uint64_t kNoKey = ~0ull;
+
+static_assert(KS == kFlatU8KStep, "rows are padded to the K step of the MFMA");
+
+__device__ __forceinline__ uint64_t make_key_i32(int dist, uint32_t id) {
+    return ((uint64_t)__float_as_uint(__int2float_rn(dist)) << 32) | id;
+}
+
+// one thread per four output bytes (Dp is a multiple of four)
+__global__ void flat_u8_bias_rows_kernel(const uint8_t* __restrict__ in, int64_t rows, int D, int Dp,
+                                         int8_t* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int wpr = Dp >> 2;
+    if (i >= rows * wpr) return;
+    const int64_t r = i / wpr;
+    const int d = (int)(i - r * wpr) * 4;
+    uint32_t w = 0;
+#pragma unroll
+    for (int b = 0; b < 4; ++b)
+        if (d + b < D) w |= (uint32_t)(in[r * D + d + b] ^ 0x80u) << (8 * b);
+    *reinterpret_cast<uint32_t*>(out + r * Dp + d) = w;
+}
+
+__device__ __forceinline__ int sq_sum4(uint32_t a) {
+    int s = 0;
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+        const int x = (int)(int8_t)(a >> (8 * b));
+        s += x * x;
+    }
+    return s;
+}
+
+__global__ void flat_u8_norms_kernel(const int8_t* __restrict__ rows8, int64_t rows, int Dp, int32_t* __restrict__ norms) {
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= rows) return;
+    int s = 0;
+    for (int d = 0; d < Dp; d += 16) {
+        const uint4 v = *reinterpret_cast<const uint4*>(rows8 + r * Dp + d);
+        s += sq_sum4(v.x) + sq_sum4(v.y) + sq_sum4(v.z) + sq_sum4(v.w);
+    }
+    norms[r] = s;
+}
+
+// grid (vector tiles of the stripe, query tiles), 256 threads.  Wavefront w owns vectors v0 .. v0 + 63 of the tile and
+// all 64 queries.  acc[i][j] is the 32 x 32 tile of vectors 32 i .. x queries 32 j ..: register e of lane l holds
+// vector 32 i + (e & 3) + 8 (e >> 2) + 4 (l >> 5) against query 32 j + (l & 31)  (the C/D map of the 32x32 shapes).
+__global__ __launch_bounds__(256) void flat_dist_u8_kernel(const int8_t* __restrict__ base, const int32_t* __restrict__ vnorm,
+                                                           int64_t row0, int rows, int Dp,
+                                                           const int8_t* __restrict__ queries,
+                                                           const int32_t* __restrict__ qnorm, int nq, int64_t id_offset,
+                                                           uint64_t* __restrict__ keys, int cap, FlatQueryState* state) {
+    __shared__ uint32_t cnt[UQ];
+    __shared__ uint32_t pos0[UQ];
+    __shared__ uint64_t thr[UQ];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r = lane & 31, h = lane >> 5;
+    const int v0 = blockIdx.x * UV + w * 64, q0 = blockIdx.y * UQ;
+    if (tid < UQ) {
+        cnt[tid] = 0;
+        thr[tid] = q0 + tid < nq ? state[q0 + tid].thr : 0;
+    }
+
+    // lane l feeds row (l & 31) of a tile with bytes 16 (l >> 5) .. + 15 of the K step, on both sides
+    const int8_t* ap[2];
+    const int8_t* bp[2];
+    bool aok[2], bok[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int v = v0 + 32 * i + r, q = q0 + 32 * i + r;
+        aok[i] = v < rows;
+        bok[i] = q < nq;
+        ap[i] = base + (size_t)(row0 + (aok[i] ? v : 0)) * Dp + 16 * h;
+        bp[i] = queries + (size_t)(bok[i] ? q : 0) * Dp + 16 * h;
+    }
+    i32x16 acc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0;
+
+    const i32x4 zero = {0, 0, 0, 0};
+    for (int k0 = 0; k0 < Dp; k0 += KS) {
+        i32x4 a[2], b[2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            a[i] = aok[i] ? *reinterpret_cast<const i32x4*>(ap[i] + k0) : zero;
+            b[i] = bok[i] ? *reinterpret_cast<const i32x4*>(bp[i] + k0) : zero;
+        }
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[i], b[j], acc[i][j], 0, 0, 0);
+    }
+    __syncthreads();
+
+    // dot products -> the fp32 bit patterns of the distances, in place.  A distance is a non-negative integer, so its
+    // bits order as unsigned integers and key <= thr is (bits, id) <= (thr >> 32, thr & 0xffffffff).
+    uint32_t thi[2], tlo[2];
+    bool qok[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int ql = 32 * j + r;
+        qok[j] = q0 + ql < nq;
+        thi[j] = (uint32_t)(thr[ql] >> 32);
+        tlo[j] = (uint32_t)thr[ql];
+        const int qn = qok[j] ? qnorm[q0 + ql] : 0;
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int vg = v0 + 32 * i + 8 * g + 4 * h;  // four vectors in a row: registers 4 g .. 4 g + 3
+                i32x4 vn = zero;
+                if (vg < rows) vn = *reinterpret_cast<const i32x4*>(vnorm + row0 + vg);  // vnorm is padded to four rows
+#pragma unroll
+                for (int c = 0; c < 4; ++c)
+                    acc[i][j][4 * g + c] = __float_as_int(__int2float_rn(vn[c] + qn - 2 * acc[i][j][4 * g + c]));
+            }
+    }
+    const uint32_t id0 = (uint32_t)(id_offset + row0);
+    auto passes = [&](int i, int j, int e, int v) {
+        const uint32_t b = (uint32_t)acc[i][j][e];
+        return v < rows && (b < thi[j] || (b == thi[j] && id0 + (uint32_t)v <= tlo[j]));
+    };
+
+    // first pass: how many of a lane's 32 vectors per query pass, and where its run starts in the query's block
+    uint32_t run[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        uint32_t np = 0;
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) np += passes(i, j, e, v0 + 32 * i + (e & 3) + 8 * (e >> 2) + 4 * h);
+        if (!qok[j]) np = 0;
+        run[j] = np ? atomicAdd(&cnt[32 * j + r], np) : 0u;
+    }
+    __syncthreads();
+    if (tid < UQ && cnt[tid]) pos0[tid] = atomicAdd(&state[q0 + tid].count, cnt[tid]);
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int ql = 32 * j + r;
+        if (!qok[j] || !cnt[ql]) continue;
+        uint32_t pos = pos0[ql] + run[j];
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int v = v0 + 32 * i + (e & 3) + 8 * (e >> 2) + 4 * h;
+                if (passes(i, j, e, v)) {
+                    if (pos < (uint32_t)cap)
+                        keys[(size_t)(q0 + ql) * cap + pos] = ((uint64_t)(uint32_t)acc[i][j][e] << 32) | (id0 + (uint32_t)v);
+                    else
+                        state[q0 + ql].overflow = 1;
+                    ++pos;
+                }
+            }
+    }
+}
+
+__device__ __forceinline__ int sq_diff4(uint32_t a, uint32_t b) {
+    int s = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int d = (int)(int8_t)(a >> (8 * k)) - (int)(int8_t)(b >> (8 * k));
+        s += d * d;
+    }
+    return s;
+}
+
+// grid (candidate groups of 256, queries), 256 threads: lane = candidate.  queries: the caller's bytes [nq][D].
+__global__ __launch_bounds__(256) void flat_rerank_u8_kernel(const int8_t* __restrict__ base, int64_t n, int D, int Dp,
+                                                             const uint8_t* __restrict__ queries,
+                                                             const int32_t* __restrict__ cand, int n_cand, int n_pad,
+                                                             int64_t id_offset, const uint32_t* __restrict__ map,
+                                                             int64_t n_map, uint64_t* __restrict__ keys, uint32_t* flag) {
+    __shared__ __align__(16) int8_t qv[kFlatMaxD];
+    __shared__ __align__(16) int8_t tile[4][64][RC + 16];
+    const int q = blockIdx.y, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    for (int d = tid; d < Dp; d += 256) qv[d] = d < D ? (int8_t)(queries[(size_t)q * D + d] ^ 0x80u) : (int8_t)0;
+    const int ci = blockIdx.x * 256 + tid;
+    int row = -1;
+    if (ci < n_cand) {
+        const int32_t c = cand[(size_t)q * n_cand + ci];
+        if (c >= 0) {  // a negative candidate is padding
+            if (map) {
+                int64_t p = c;
+                if ((n_map & 1) == 0 && p == n_map) p = n_map - 1;  // the even-N id of the last DFS node
+                if (p < n_map && (int64_t)map[p] < n) row = (int)map[p];
+            } else {
+                const int64_t rr = (int64_t)c - id_offset;
+                if (rr >= 0 && rr < n) row = (int)rr;
+            }
+            if (row < 0) *flag = 1;  // names no row
+        }
+    }
+    __syncthreads();
+    int acc = 0;
+    const int lj = (lane & 7) * 16;
+    for (int d0 = 0; d0 < Dp; d0 += RC) {
+#pragma unroll
+        for (int it = 0; it < 8; ++it) {
+            const int cc = it * 8 + (lane >> 3);
+            const int rr = __shfl(row, cc);
+            uint4 v = make_uint4(0u, 0u, 0u, 0u);
+            if (rr >= 0 && d0 + lj < Dp) v = *reinterpret_cast<const uint4*>(base + (size_t)rr * Dp + d0 + lj);
+            *reinterpret_cast<uint4*>(&tile[w][cc][lj]) = v;
+        }
+        __syncthreads();
+        const int dc = min(RC, Dp - d0);
+        for (int d = 0; d < dc; d += 16) {
+            const uint4 v = *reinterpret_cast<const uint4*>(&tile[w][lane][d]);
+            const uint4 u = *reinterpret_cast<const uint4*>(&qv[d0 + d]);
+            acc += sq_diff4(v.x, u.x) + sq_diff4(v.y, u.y) + sq_diff4(v.z, u.z) + sq_diff4(v.w, u.w);
+        }
+        __syncthreads();
+    }
+    if (ci < n_pad)
+        keys[(size_t)q * n_pad + ci] = row >= 0 ? make_key_i32(acc, (uint32_t)((int64_t)row + id_offset)) : kNoKey;
+}
+
+}  // namespace
+
+hipError_t launch_flat_u8_prepare(const uint8_t* d_in, int64_t rows, int D, int Dp, int8_t* d_out, int32_t* d_norms,
+                                  hipStream_t stream) {
+    if (rows <= 0) return hipSuccess;
+    const int64_t words = rows * (Dp >> 2);
+    flat_u8_bias_rows_kernel<<<dim3((unsigned)((words + 255) / 256)), dim3(256), 0, stream>>>(d_in, rows, D, Dp, d_out);
+    flat_u8_norms_kernel<<<dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, stream>>>(d_out, rows, Dp, d_norms);
+    return hipGetLastError();
+}
+
+hipError_t launch_flat_search_u8(const int8_t* d_base, const int32_t* d_vnorm, int64_t n, int Dp, const int8_t* d_queries,
+                                 const int32_t* d_qnorm, int nq, int top_k, int64_t id_offset, uint64_t* d_keys,
+                                 FlatQueryState* d_state, int32_t* d_ids, float* d_dists, hipStream_t stream) {
+    if (nq <= 0) return hipSuccess;
+    // the stripes, the limit and the selection between them: launch_flat_search's, with the distance stage replaced
+    const int cap = flat_key_capacity(top_k);
+    const int64_t stripe = cap / 2;
+    const uint32_t limit = (uint32_t)std::max(top_k, cap / 4);
+    hipError_t e = launch_flat_init_state(d_state, nq, stream);
+    if (e != hipSuccess) return e;
+    for (int64_t r0 = 0; r0 < n; r0 += stripe) {
+        const int rows = (int)std::min<int64_t>(stripe, n - r0);
+        if (r0 > 0 && (e = launch_flat_select(d_keys, cap, d_state, nq, top_k, limit, stream)) != hipSuccess) return e;
+        flat_dist_u8_kernel<<<dim3((rows + UV - 1) / UV, (nq + UQ - 1) / UQ), dim3(256), 0, stream>>>(
+            d_base, d_vnorm, r0, rows, Dp, d_queries, d_qnorm, nq, id_offset, d_keys, cap, d_state);
+    }
+    if ((e = launch_flat_select(d_keys, cap, d_state, nq, top_k, (uint32_t)top_k, stream)) != hipSuccess) return e;
+    return launch_flat_sort_emit(d_keys, (size_t)cap, d_state, nq, top_k, top_k, d_ids, d_dists, stream);
+}
+
+hipError_t launch_flat_rerank_u8(const int8_t* d_base, int64_t n, int D, int Dp, const uint8_t* d_queries, int nq,
+                                 const int32_t* d_cand, int n_cand, int top_k, int64_t id_offset, const uint32_t* d_map,
+                                 int64_t n_map, uint64_t* d_keys, uint32_t* d_flag, int32_t* d_ids, float* d_dists,
+                                 hipStream_t stream) {
+    if (nq <= 0) return hipSuccess;
+    const int n_pad = (int)flat_rerank_keys(n_cand);
+    for (int q0 = 0; q0 < nq; q0 += 65535) {  // the grid's y extent
+        const int m = std::min(65535, nq - q0);
+        flat_rerank_u8_kernel<<<dim3((n_pad + 255) / 256, m), dim3(256), 0, stream>>>(
+            d_base, n, D, Dp, d_queries + (size_t)q0 * D, d_cand + (size_t)q0 * n_cand, n_cand, n_pad, id_offset, d_map,
+            n_map, d_keys + (size_t)q0 * n_pad, d_flag);
+    }
+    return launch_flat_sort_emit(d_keys, (size_t)n_pad, nullptr, nq, n_pad, top_k, d_ids, d_dists, stream);
+}
+
+}  // namespace dpq

@@ -32,7 +32,7 @@
  *   PQ::WriteCodewords (pq.cpp:267-286)         dpq_write_codewords
  *   ReadTopN(query.{fvecs,bvecs})               dpq_read_vecs
  *     (utils.cpp:14-110)
- *   brute force over base.{ext}                 dpq_flat_open / dpq_flat_search (exact L2,
+ *   brute force over base.{ext}                 dpq_flat_open[_u8] / dpq_flat_search[_u8] (exact L2,
  *     (main.cpp:107-166, 569-669)                 the reference's bits), dpq_flat_rerank
  *   recall (main.cpp:727-803)                   dpq_recall, dpq_read/write_groundtruth
  *   (none: the reference never reads a code     dpq_get_codes / dpq_reconstruct / dpq_decode_range,
@@ -551,9 +551,36 @@ int dpq_flat_rerank(dpq_flat* f, const float* queries, int nq, const int32_t* ca
 int dpq_flat_rerank_device(dpq_flat* f, const float* d_queries, int nq, const int32_t* d_cand_ids, int n_cand, int top_k,
                            int32_t* d_ids, float* d_dists, void* hip_stream);
 
+/* Byte vectors (.bvecs data: SIFT1B and its kin, queries included) on the int8 matrix cores.  The contract is that of
+ * the fp32 functions of the same name applied to the bytes widened to fp32: squared L2 reported as fp32, keys
+ * `distance bits << 32 | id` ordered by (distance, id), the lowest ids winning at the k-th boundary; id_offset, the
+ * DPQ_ERR_TOPK rule, nq == 0, the top_k limits, padding with -1 / +inf, a row named twice counting once, the flag word of
+ * the device variant and the id map with its even-n_map rule all carry over.  dpq_flat_set_id_map, dpq_flat_close and
+ * dpq_merge_topk_host work on a byte handle unchanged.
+ * Why the bits are the same: with v, q in {0..255}^D and D <= 2048 every intermediate of the arithmetic above is an
+ * exactly representable integer -- |t| <= 255, s <= 65025, acc <= 2048 * 65025 = 133 171 200 < 2^31 -- so acc equals the
+ * int32 value sum (v[d] - q[d])^2 whatever the order of the sum, and the reported distance is (float)(int32) of it, round
+ * to nearest even: the bits of dpq_flat_search on the widened data and of the reference (main.cpp:150-156 after
+ * ReadTopN's widening).  Two different integer distances above 2^24 can round to the same float; they are then ordered
+ * by id, because the key is built from the float's bits and not from the integer.
+ * Handle kinds do not mix: a _u8 call on a handle of dpq_flat_open, or dpq_flat_search / dpq_flat_rerank* on a handle of
+ * dpq_flat_open_u8, is DPQ_ERR_ARG with a message that names the other function.
+ * Device memory: n * (D rounded up to a multiple of 32, the K step of v_mfma_i32_32x32x32_i8) bytes of biased vectors
+ * plus 4 * n bytes of int32 norms, plus the same workspaces; while dpq_flat_open_u8 runs, an upload buffer of at most
+ * 128 MB on top of that, freed before it returns.  dpq_flat_open_u8 checks its arguments as dpq_flat_open
+ * does, before any device call. */
+int dpq_flat_open_u8(const uint8_t* vectors, int64_t n, int D, int device, int64_t id_offset, dpq_flat** out);
+int dpq_flat_search_u8(dpq_flat* f, const uint8_t* queries, int nq, int top_k, int32_t* ids, float* dists);
+int dpq_flat_rerank_u8(dpq_flat* f, const uint8_t* queries, int nq, const int32_t* cand_ids, int n_cand, int top_k,
+                       int32_t* ids, float* dists);
+int dpq_flat_rerank_u8_device(dpq_flat* f, const uint8_t* d_queries, int nq, const int32_t* d_cand_ids, int n_cand,
+                              int top_k, int32_t* d_ids, float* d_dists, void* hip_stream);
+
 /* Host only.  Vectors [first, first + count) of an .fvecs / .bvecs file (the streaming read of main.cpp:607-640);
  * out[count][D] may be NULL to learn D.  A range past the end of the file: DPQ_ERR_IO. */
 int dpq_read_vecs_range(const char* path, int is_bvecs, int64_t first, int64_t count, int32_t* D, float* out);
+/* The same over a .bvecs file with the bytes kept as they are (for dpq_flat_open_u8); the same errors. */
+int dpq_read_bvecs_range(const char* path, int64_t first, int64_t count, int32_t* D, uint8_t* out);
 /* The reference's ground-truth text file (PQBase::write_groundtruth / read_groundtruth, pqbase.cpp:294-332): a first
  * line `nq,top_k`, then one line per query of `id,dist,` pairs.  Distances are written with nine significant digits so
  * that they read back to the same bits (the reference's six digits lose them).  Read with ids == dists == NULL to
