@@ -141,6 +141,17 @@ SYMBOLS = [
     ("dpq_flat_search_u8", ctypes.c_int, [_VP, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP]),
     ("dpq_flat_rerank_u8", ctypes.c_int, [_VP, _VP, ctypes.c_int, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP]),
     ("dpq_flat_rerank_u8_device", ctypes.c_int, [_VP, _VP, ctypes.c_int, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP]),
+    ("dpq_flat_filter_create", ctypes.c_int, [_VP, _VP, c_i64, P(_VP)]),
+    ("dpq_flat_filter_free", None, [_VP]),
+    ("dpq_flat_filter_count", ctypes.c_int, [_VP, P(c_i64)]),
+    ("dpq_flat_search_filtered", ctypes.c_int, [_VP, _VP, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP]),
+    ("dpq_flat_search_filtered_u8", ctypes.c_int, [_VP, _VP, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP]),
+    ("dpq_flat_range_search", ctypes.c_int, [_VP, _VP, _VP, ctypes.c_int, _VP, P(_VP)]),
+    ("dpq_flat_range_search_u8", ctypes.c_int, [_VP, _VP, _VP, ctypes.c_int, _VP, P(_VP)]),
+    ("dpq_range_recall", ctypes.c_int, [ctypes.c_int, _VP, _VP, _VP, _VP, P(ctypes.c_double), P(ctypes.c_double)]),
+    ("dpq_bitmap_to_dfs", ctypes.c_int, [_VP, c_i64, _VP, c_i64, _VP]),
+    ("dpq_write_bitmap", ctypes.c_int, [ctypes.c_char_p, _VP, c_i64]),
+    ("dpq_read_bitmap", ctypes.c_int, [ctypes.c_char_p, P(c_i64), _VP]),
     ("dpq_read_vecs_range", ctypes.c_int, [ctypes.c_char_p, ctypes.c_int, c_i64, c_i64, P(c_i32), _VP]),
     ("dpq_read_bvecs_range", ctypes.c_int, [ctypes.c_char_p, c_i64, c_i64, P(c_i32), _VP]),
     ("dpq_write_groundtruth", ctypes.c_int, [ctypes.c_char_p, _VP, _VP, ctypes.c_int, ctypes.c_int]),

@@ -614,6 +614,103 @@ class IdFilter:
         self.close()
 
 
+class FlatIdFilter:
+    """A filter of FlatIndex / FlatIndexU8 .search_filtered and .range_search (dpq_flat_filter): the set of reported ids
+    (row + id_offset) a search may return, compacted once on the index's device into a list of eligible rows.  The bitmap
+    convention is IdFilter's; ids at or beyond n_bits are not allowed."""
+
+    pack_mask = staticmethod(IdFilter.pack_mask)
+    pack_ids = staticmethod(IdFilter.pack_ids)
+    unpack = staticmethod(IdFilter.unpack)
+
+    def __init__(self, flat_index, words, n_bits):
+        self._lib = _lib.load()
+        self._h = None
+        w = np.ascontiguousarray(words, dtype=np.uint32)
+        if n_bits < 0 or w.size < (n_bits + 31) // 32:
+            raise ValueError("words must hold n_bits >= 0 bits")
+        h = ctypes.c_void_p()
+        check(self._lib.dpq_flat_filter_create(flat_index._h, _np_ptr(w) if w.size else None, int(n_bits), h),
+              "dpq_flat_filter_create")
+        self._h = h
+
+    @classmethod
+    def from_mask(cls, flat_index, mask):
+        """mask[i]: whether reported id i is allowed."""
+        return cls(flat_index, *cls.pack_mask(mask))
+
+    @classmethod
+    def from_ids(cls, flat_index, ids, n_bits=None):
+        return cls(flat_index, *cls.pack_ids(ids, n_bits))
+
+    @staticmethod
+    def _handle(f, optional=False):
+        if f is None and optional:
+            return None
+        if not isinstance(f, FlatIdFilter):
+            raise TypeError("id_filter must be a FlatIdFilter")
+        return f._h
+
+    @property
+    def n_allowed(self):
+        """Rows of its index the filter allows."""
+        n = _lib.c_i64()
+        check(self._lib.dpq_flat_filter_count(self._h, n), "dpq_flat_filter_count")
+        return n.value
+
+    def close(self):
+        if self._h is not None:
+            self._lib.dpq_flat_filter_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def _range_result(lib, res):
+    """A dpq_range_result -> (lims int64 [nq + 1], ids int32, dists float32), copied; the result is freed."""
+    try:
+        n = _lib.c_i32()
+        pl, pi, pd = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+        check(lib.dpq_range_result_get(res, n, pl, pi, pd), "dpq_range_result_get")
+        lims = np.ctypeslib.as_array(ctypes.cast(pl, ctypes.POINTER(_lib.c_i64)), (n.value + 1,)).copy()
+        total = int(lims[-1])
+        ids = np.empty(total, dtype=np.int32)
+        dists = np.empty(total, dtype=np.float32)
+        if total:
+            ctypes.memmove(ids.ctypes.data, pi.value, total * 4)
+            ctypes.memmove(dists.ctypes.data, pd.value, total * 4)
+        return lims, ids, dists
+    finally:
+        lib.dpq_range_result_free(res)
+
+
+def _flat_search_filtered(index, fn, name, queries, top_k, id_filter):
+    q = index._queries(queries)
+    ids = np.empty((q.shape[0], top_k), dtype=np.int32)
+    dists = np.empty((q.shape[0], top_k), dtype=np.float32)
+    check(fn(index._h, FlatIdFilter._handle(id_filter), _np_ptr(q), q.shape[0], top_k, _np_ptr(ids), _np_ptr(dists)), name)
+    return ids, dists
+
+
+def _flat_range_search(index, fn, name, queries, radius, id_filter):
+    q = index._queries(queries)
+    nq = q.shape[0]
+    r = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, dtype=np.float32), (nq,)))
+    res = ctypes.c_void_p()
+    check(fn(index._h, FlatIdFilter._handle(id_filter, optional=True), _np_ptr(q), nq, _np_ptr(r), res), name)
+    return _range_result(index._lib, res)
+
+
 class FlatIndex:
     """Raw fp32 vectors [n][D] on one GPU (dpq_flat): exact squared L2 distances with the reference's brute-force
     arithmetic -- ground truth over all of them (search), or over a candidate list per query (rerank)."""
@@ -643,6 +740,19 @@ class FlatIndex:
         check(self._lib.dpq_flat_search(self._h, _np_ptr(q), q.shape[0], top_k, _np_ptr(ids), _np_ptr(dists)),
               "dpq_flat_search")
         return ids, dists
+
+    def search_filtered(self, queries, top_k, id_filter):
+        """Exact top_k over the rows `id_filter` (a FlatIdFilter made on this index) allows; rows are padded with -1 / +inf
+        where fewer than top_k rows are allowed (dpq_flat_search_filtered)."""
+        return _flat_search_filtered(self, self._lib.dpq_flat_search_filtered, "dpq_flat_search_filtered", queries, top_k,
+                                     id_filter)
+
+    def range_search(self, queries, radius, id_filter=None):
+        """Every (allowed) row with exact distance d < radius, strictly (dpq_flat_range_search).  `radius` is a scalar or
+        one value per query.  Returns (lims int64 [nq + 1], ids int32, dists float32) as DeltaPQIndex.range_search does;
+        query i owns entries lims[i]:lims[i + 1], ascending by (distance, id)."""
+        return _flat_range_search(self, self._lib.dpq_flat_range_search, "dpq_flat_range_search", queries, radius,
+                                  id_filter)
 
     def set_id_map(self, vec_id):
         """DFS position -> row of this handle (DeltaTree.vec_id): rerank candidates are then DFS positions."""
@@ -733,6 +843,19 @@ class FlatIndexU8:
         check(self._lib.dpq_flat_search_u8(self._h, _np_ptr(q), q.shape[0], top_k, _np_ptr(ids), _np_ptr(dists)),
               "dpq_flat_search_u8")
         return ids, dists
+
+    def search_filtered(self, queries, top_k, id_filter):
+        """Exact top_k over the rows `id_filter` (a FlatIdFilter made on this index) allows; rows are padded with -1 / +inf
+        where fewer than top_k rows are allowed (dpq_flat_search_filtered_u8)."""
+        return _flat_search_filtered(self, self._lib.dpq_flat_search_filtered_u8, "dpq_flat_search_filtered_u8", queries, top_k,
+                                     id_filter)
+
+    def range_search(self, queries, radius, id_filter=None):
+        """Every (allowed) row with exact distance d < radius, strictly (dpq_flat_range_search_u8).  `radius` is a scalar or
+        one value per query.  Returns (lims int64 [nq + 1], ids int32, dists float32) as DeltaPQIndex.range_search does;
+        query i owns entries lims[i]:lims[i + 1], ascending by (distance, id)."""
+        return _flat_range_search(self, self._lib.dpq_flat_range_search_u8, "dpq_flat_range_search_u8", queries, radius,
+                                  id_filter)
 
     def set_id_map(self, vec_id):
         """DFS position -> row of this handle (DeltaTree.vec_id): rerank candidates are then DFS positions."""
@@ -841,6 +964,52 @@ def recall(found, truth, k=None, R=None):
     check(_lib.load().dpq_recall(_np_ptr(found), found.shape[1], R, _np_ptr(truth), truth.shape[1], k, found.shape[0], out),
           "dpq_recall")
     return out.value
+
+
+def range_recall(found, truth):
+    """(recall, precision) of a range answer against the truth, both (lims, ids[, dists]) over the same queries and in the
+    same id space, summed over the queries (dpq_range_recall); a zero denominator gives 1.0."""
+    fl = np.ascontiguousarray(found[0], dtype=np.int64)
+    fi = np.ascontiguousarray(found[1], dtype=np.int32)
+    tl = np.ascontiguousarray(truth[0], dtype=np.int64)
+    ti = np.ascontiguousarray(truth[1], dtype=np.int32)
+    if fl.ndim != 1 or fl.shape != tl.shape or fl.size < 1 or fi.size < fl[-1] or ti.size < tl[-1]:
+        raise ValueError("found and truth must be (lims [nq + 1], ids [lims[-1]]) over the same queries")
+    rec, prec = ctypes.c_double(), ctypes.c_double()
+    check(_lib.load().dpq_range_recall(fl.size - 1, _np_ptr(fl), _np_ptr(fi) if fi.size else None, _np_ptr(tl),
+                                       _np_ptr(ti) if ti.size else None, rec, prec), "dpq_range_recall")
+    return rec.value, prec.value
+
+
+def bitmap_to_dfs(words, n_bits, vec_id):
+    """A bitmap over original vector ids -> (words, n_bits) of the bitmap IdFilter takes for the DTC index whose DFS
+    position p holds vector vec_id[p] (dpq_bitmap_to_dfs; the even-N rule applied)."""
+    w = np.ascontiguousarray(words, dtype=np.uint32)
+    v = np.ascontiguousarray(vec_id, dtype=np.uint32)
+    if n_bits < 0 or w.size < (n_bits + 31) // 32:
+        raise ValueError("words must hold n_bits >= 0 bits")
+    out = np.zeros((v.size + 1 + 31) // 32, dtype=np.uint32)
+    check(_lib.load().dpq_bitmap_to_dfs(_np_ptr(w) if w.size else None, int(n_bits), _np_ptr(v), v.size, _np_ptr(out)),
+          "dpq_bitmap_to_dfs")
+    return out, v.size + 1
+
+
+def write_bitmap(path, words, n_bits):
+    """A bitmap file: int64 n_bits, then (n_bits + 31) // 32 little-endian uint32 words (dpq_write_bitmap)."""
+    w = np.ascontiguousarray(words, dtype=np.uint32)
+    if n_bits < 0 or w.size < (n_bits + 31) // 32:
+        raise ValueError("words must hold n_bits >= 0 bits")
+    check(_lib.load().dpq_write_bitmap(path.encode(), _np_ptr(w) if w.size else None, int(n_bits)), "dpq_write_bitmap")
+
+
+def read_bitmap(path):
+    """-> (words uint32 [(n_bits + 31) // 32], n_bits) (dpq_read_bitmap)."""
+    lib = _lib.load()
+    n = _lib.c_i64()
+    check(lib.dpq_read_bitmap(path.encode(), n, None), "dpq_read_bitmap")
+    words = np.zeros((n.value + 31) // 32, dtype=np.uint32)
+    check(lib.dpq_read_bitmap(path.encode(), n, _np_ptr(words) if words.size else None), "dpq_read_bitmap")
+    return words, n.value
 
 
 def pin_host(arr):

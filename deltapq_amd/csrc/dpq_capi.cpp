@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <iterator>
 #include <memory>
 #include <new>
 #include <numeric>
@@ -140,6 +141,11 @@ struct dpq_filter {
     mutable int l0_n = -1;           // entries of l0_id (-1: not made yet)
 };
 
+inline uint64_t next_flat_serial() {
+    static std::atomic<uint64_t> next{1};
+    return next++;
+}
+
 // Raw vectors resident on one GPU (exact search).  An fp32 handle (dpq_flat.hip) stores rows padded to Dp floats; a byte
 // handle (dpq_flat_u8.hip) stores them biased to int8 and padded to Dp bytes, with an int32 norm per row.
 struct dpq_flat {
@@ -162,6 +168,19 @@ struct dpq_flat {
     DevBuf<int8_t> q8;
     DevBuf<int32_t> qnorm;
     size_t keys_n = 0, state_n = 0, q_n = 0, out_n = 0, cand_n = 0, q_raw_n = 0, q8_n = 0, qnorm_n = 0;
+    // filtered and range search
+    const uint64_t serial = next_flat_serial();  // what a dpq_flat_filter remembers of the handle it was made for
+    DevBuf<uint64_t> r_thr, r_pool, r_sorted;    // radius keys of a query batch; the lists of a sub-batch, unsorted / sorted
+    DevBuf<int64_t> r_offs;                      // [queries of a sub-batch + 1] list starts in the pool
+    size_t r_thr_n = 0, r_pool_n = 0, r_sorted_n = 0, r_offs_n = 0;
+};
+
+// A filter of dpq_flat_search_filtered* / dpq_flat_range_search*: the ascending list of the handle's eligible rows.
+struct dpq_flat_filter {
+    uint64_t owner = 0;      // dpq_flat::serial
+    int device = 0;
+    DevBuf<uint32_t> list;   // [n_allowed]
+    int64_t n_allowed = 0;
 };
 
 namespace {
@@ -2452,6 +2471,385 @@ int dpq_flat_set_id_map(dpq_flat* f, const uint32_t* map, int64_t n_map) {
     DPQ_HIP(hipMemcpy(d, map, (size_t)n_map * sizeof(uint32_t), hipMemcpyHostToDevice));
     f->map = std::move(d);
     f->h_map.assign(map, map + n_map);
+    return DPQ_OK;
+    });
+}
+
+}  // extern "C"
+
+// ---- exact filtered and range search (dpq_flat_filter.hip) -----------------------------------------------------------
+namespace {
+
+constexpr int64_t kFlatRangePoolKeys = (int64_t)1 << 19;  // keys of a range sub-batch's lists: 4 MB, and as much sorted
+constexpr int kFlatRangeQueries = 1024;                   // queries whose lists one pass counts
+
+// 32 bits of the caller's bitmap from bit `start` on; bits at or beyond n_bits read as 0.
+uint32_t bitmap_bits32(const uint32_t* words, int64_t n_bits, int64_t start) {
+    if (start >= n_bits) return 0;
+    const int64_t lo = start >> 5, n_words = (n_bits + 31) / 32;
+    const int sh = (int)(start & 31);
+    uint32_t v = words[lo] >> sh;
+    if (sh && lo + 1 < n_words) v |= words[lo + 1] << (32 - sh);
+    const int64_t valid = n_bits - start;
+    if (valid < 32) v &= (1u << valid) - 1u;
+    return v;
+}
+
+// After the arguments that need no handle, before the handle is read.
+int flat_device_present(const std::string& who) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail(DPQ_ERR_NO_DEVICE, who + ": no HIP device visible; this library has no CPU fallback");
+    return DPQ_OK;
+}
+
+int flat_filter_owner(const dpq_flat* f, const dpq_flat_filter* ff, const std::string& who) {
+    if (ff->owner == f->serial) return DPQ_OK;
+    return fail(DPQ_ERR_ARG, who + ": the filter was made for another handle");
+}
+
+// Uploads m queries as the distance kernels read them: fp32 rows padded to Dp, or bytes biased and padded with norms.
+template <class Q>
+int flat_stage_queries(dpq_flat* f, const Q* src, int m, std::vector<float>* padded) {
+    const int D = f->D, Dp = f->Dp;
+    if constexpr (std::is_same<Q, uint8_t>::value) {
+        DPQ_HIP(hipMemcpy(f->q_raw, src, (size_t)m * D, hipMemcpyHostToDevice));
+        DPQ_HIP(dpq::launch_flat_u8_prepare(f->q_raw, m, D, Dp, f->q8, f->qnorm, nullptr));
+    } else {
+        if (Dp != D) {
+            padded->assign((size_t)m * Dp, 0.0f);
+            for (int q = 0; q < m; ++q) memcpy(&(*padded)[(size_t)q * Dp], src + (size_t)q * D, (size_t)D * sizeof(float));
+            src = padded->data();
+        }
+        DPQ_HIP(hipMemcpy(f->d_q, src, (size_t)m * Dp * sizeof(float), hipMemcpyHostToDevice));
+    }
+    return DPQ_OK;
+}
+
+template <class Q>
+int flat_grow_queries(dpq_flat* f, size_t qb) {
+    if constexpr (std::is_same<Q, uint8_t>::value) {
+        int rc = grow(f->q_raw, &f->q_raw_n, qb * f->D);
+        if (!rc) rc = grow(f->q8, &f->q8_n, qb * f->Dp);
+        if (!rc) rc = grow(f->qnorm, &f->qnorm_n, qb);
+        return rc;
+    } else {
+        return grow(f->d_q, &f->q_n, qb * f->Dp);
+    }
+}
+
+// dpq_flat_search_filtered / _u8: Q is float or uint8_t, the handle of the same kind.
+template <class Q>
+int flat_search_filtered_call(const char* fn, const char* other, dpq_flat* f, const dpq_flat_filter* ff, const Q* queries,
+                              int nq, int top_k, int32_t* ids, float* dists) {
+    constexpr bool u8 = std::is_same<Q, uint8_t>::value;
+    const std::string who(fn);
+    if (!f || !ff || !queries || !ids || !dists || nq < 0)
+        return fail(DPQ_ERR_ARG, who + ": NULL argument (the filter included) or nq < 0");
+    if (top_k < 1 || top_k > DPQ_FLAT_MAX_TOPK) return fail(DPQ_ERR_ARG, who + ": top_k outside 1..DPQ_FLAT_MAX_TOPK");
+    if (int rc = flat_device_present(who)) return rc;
+    if (int rc = flat_kind(f, u8, fn, other)) return rc;
+    if (int rc = flat_filter_owner(f, ff, who)) return rc;
+    if (nq == 0) return DPQ_OK;
+    DPQ_HIP(hipSetDevice(f->device));
+    const int qb = std::min(nq, dpq::flat_query_batch(top_k));
+    int rc = grow(f->keys, &f->keys_n, (size_t)qb * dpq::flat_key_capacity(top_k));
+    if (!rc) rc = grow(f->state, &f->state_n, (size_t)qb);
+    if (!rc) rc = flat_grow_queries<Q>(f, (size_t)qb);
+    if (!rc) rc = grow_outputs(f, (size_t)qb * top_k);
+    if (rc) return rc;
+    const uint32_t expect = (uint32_t)std::min<int64_t>(top_k, ff->n_allowed);
+    std::vector<float> padded;
+    std::vector<dpq::FlatQueryState> st((size_t)qb);
+    for (int q0 = 0; q0 < nq; q0 += qb) {
+        const int m = std::min(qb, nq - q0);
+        if ((rc = flat_stage_queries(f, queries + (size_t)q0 * f->D, m, &padded))) return rc;
+        if constexpr (u8)
+            DPQ_HIP(dpq::launch_flat_search_list_u8(f->base8, f->norm8, ff->list, ff->n_allowed, f->Dp, f->q8, f->qnorm, m, top_k,
+                                                    f->id_offset, f->keys, f->state, f->d_ids, f->d_dists, nullptr));
+        else
+            DPQ_HIP(dpq::launch_flat_search_list(f->base, ff->list, ff->n_allowed, f->Dp, f->d_q, m, top_k, f->id_offset, f->keys,
+                                                 f->state, f->d_ids, f->d_dists, nullptr));
+        DPQ_HIP(hipMemcpy(ids + (size_t)q0 * top_k, f->d_ids, (size_t)m * top_k * sizeof(int32_t), hipMemcpyDeviceToHost));
+        DPQ_HIP(hipMemcpy(dists + (size_t)q0 * top_k, f->d_dists, (size_t)m * top_k * sizeof(float), hipMemcpyDeviceToHost));
+        DPQ_HIP(hipMemcpy(st.data(), f->state, (size_t)m * sizeof(dpq::FlatQueryState), hipMemcpyDeviceToHost));
+        for (int q = 0; q < m; ++q)
+            if (st[(size_t)q].overflow || st[(size_t)q].count != expect)
+                return fail(DPQ_ERR_STATE, who + ": internal error: a key buffer overflowed");
+    }
+    return DPQ_OK;
+}
+
+// One distance pass of a range search over queries [a, a + m) of the staged batch: counting (pool NULL) or emitting.
+template <class Q>
+int flat_range_pass(dpq_flat* f, const dpq_flat_filter* ff, int a, int m, uint64_t* pool) {
+    const uint32_t* list = ff ? ff->list.get() : nullptr;
+    const int64_t n_entries = ff ? ff->n_allowed : f->n;
+    DPQ_HIP(dpq::launch_flat_range_state(f->state.get() + a, f->r_thr.get() + a, m, nullptr));
+    if constexpr (std::is_same<Q, uint8_t>::value)
+        DPQ_HIP(dpq::launch_flat_range_pass_u8(f->base8, f->norm8, list, n_entries, f->Dp, f->q8.get() + (size_t)a * f->Dp,
+                                               f->qnorm.get() + a, m, f->id_offset, pool, f->r_offs, f->state.get() + a,
+                                               nullptr));
+    else
+        DPQ_HIP(dpq::launch_flat_range_pass(f->base, list, n_entries, f->Dp, f->d_q.get() + (size_t)a * f->Dp, m, f->id_offset,
+                                            pool, f->r_offs, f->state.get() + a, nullptr));
+    return DPQ_OK;
+}
+
+// dpq_flat_range_search / _u8.  Count, then emit: a pass over a batch of queries counts every list, the host lays the
+// lists out, and sub-batches of at most kFlatRangePoolKeys keys (or one longer list) are formed again into the pool,
+// sorted there and brought down.
+template <class Q>
+int flat_range_call(const char* fn, const char* other, dpq_flat* f, const dpq_flat_filter* ff, const Q* queries, int nq,
+                    const float* radii, dpq_range_result** out) {
+    constexpr bool u8 = std::is_same<Q, uint8_t>::value;
+    const std::string who(fn);
+    if (!out) return fail(DPQ_ERR_ARG, who + ": out is NULL");
+    *out = nullptr;
+    if (!f || nq < 0 || (nq > 0 && (!queries || !radii))) return fail(DPQ_ERR_ARG, who + ": NULL argument or nq < 0");
+    for (int q = 0; q < nq; ++q)
+        if (std::isnan(radii[q])) return fail(DPQ_ERR_ARG, who + ": radius of query " + std::to_string(q) + " is NaN");
+    if (int rc = flat_device_present(who)) return rc;
+    if (int rc = flat_kind(f, u8, fn, other)) return rc;
+    if (ff)
+        if (int rc = flat_filter_owner(f, ff, who)) return rc;
+    std::unique_ptr<dpq_range_result> res(new dpq_range_result());
+    res->nq = nq;
+    res->lims.assign((size_t)nq + 1, 0);
+    if (nq == 0) {
+        *out = res.release();
+        return DPQ_OK;
+    }
+    DPQ_HIP(hipSetDevice(f->device));
+    const int qb = std::min(nq, kFlatRangeQueries);
+    int rc = grow(f->state, &f->state_n, (size_t)qb);
+    if (!rc) rc = flat_grow_queries<Q>(f, (size_t)qb);
+    if (!rc) rc = grow(f->r_thr, &f->r_thr_n, (size_t)qb);
+    if (!rc) rc = grow(f->r_offs, &f->r_offs_n, (size_t)qb + 1);
+    if (rc) return rc;
+    std::vector<float> padded;
+    std::vector<dpq::FlatQueryState> st((size_t)qb);
+    std::vector<uint64_t> thr((size_t)qb), sorted;
+    std::vector<int64_t> offs;
+    for (int q0 = 0; q0 < nq && !rc; q0 += qb) {
+        const int m = std::min(qb, nq - q0);
+        if ((rc = flat_stage_queries(f, queries + (size_t)q0 * f->D, m, &padded))) break;
+        for (int q = 0; q < m; ++q) {  // d < r on non-negative floats is bits(d) < bits(r); key 0 lets nothing pass
+            const float r = radii[q0 + q];
+            uint32_t bits = 0;
+            if (r > 0.0f) memcpy(&bits, &r, sizeof bits);
+            thr[(size_t)q] = (uint64_t)bits << 32;
+        }
+        DPQ_HIP(hipMemcpy(f->r_thr, thr.data(), (size_t)m * sizeof(uint64_t), hipMemcpyHostToDevice));
+        if ((rc = flat_range_pass<Q>(f, ff, 0, m, nullptr))) break;
+        DPQ_HIP(hipMemcpy(st.data(), f->state, (size_t)m * sizeof(dpq::FlatQueryState), hipMemcpyDeviceToHost));
+        for (int q = 0; q < m; ++q) res->lims[(size_t)q0 + q + 1] = res->lims[(size_t)q0 + q] + st[(size_t)q].count;
+        res->ids.resize((size_t)res->lims[(size_t)q0 + m]);
+        res->dists.resize((size_t)res->lims[(size_t)q0 + m]);
+        for (int a = 0; a < m && !rc;) {
+            int b = a;
+            int64_t sum = 0;
+            while (b < m && (b == a || sum + st[(size_t)b].count <= kFlatRangePoolKeys)) sum += st[(size_t)b++].count;
+            if (sum > 0) {
+                offs.assign(1, 0);
+                for (int q = a; q < b; ++q) offs.push_back(offs.back() + st[(size_t)q].count);
+                if ((rc = grow(f->r_pool, &f->r_pool_n, (size_t)std::max(sum, kFlatRangePoolKeys)))) break;
+                if ((rc = grow(f->r_sorted, &f->r_sorted_n, f->r_pool_n))) break;
+                DPQ_HIP(hipMemcpy(f->r_offs, offs.data(), offs.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+                if ((rc = flat_range_pass<Q>(f, ff, a, b - a, f->r_pool))) break;
+                size_t tb = 0;
+                DPQ_HIP(dpq::flat_range_sort(nullptr, &tb, f->r_pool, f->r_sorted, sum, b - a, f->r_offs, nullptr));
+                DevBuf<uint8_t> temp;  // the segmented sort's workspace
+                if ((rc = temp.alloc(tb))) break;
+                DPQ_HIP(dpq::flat_range_sort(temp, &tb, f->r_pool, f->r_sorted, sum, b - a, f->r_offs, nullptr));
+                sorted.resize((size_t)sum);
+                DPQ_HIP(hipMemcpy(sorted.data(), f->r_sorted, (size_t)sum * sizeof(uint64_t), hipMemcpyDeviceToHost));
+                std::vector<dpq::FlatQueryState> st2((size_t)(b - a));
+                DPQ_HIP(hipMemcpy(st2.data(), f->state.get() + a, st2.size() * sizeof(dpq::FlatQueryState), hipMemcpyDeviceToHost));
+                for (int q = a; q < b; ++q)
+                    if (st2[(size_t)(q - a)].overflow || st2[(size_t)(q - a)].count != st[(size_t)q].count)
+                        rc = fail(DPQ_ERR_STATE, who + ": internal error: the two passes disagree on the length of a list");
+                if (rc) break;
+                const size_t at = (size_t)res->lims[(size_t)q0 + a];
+                for (size_t i = 0; i < (size_t)sum; ++i) {
+                    const uint32_t bits = (uint32_t)(sorted[i] >> 32);
+                    res->ids[at + i] = (int32_t)(uint32_t)sorted[i];
+                    memcpy(&res->dists[at + i], &bits, sizeof bits);
+                }
+            }
+            a = b;
+        }
+    }
+    if (f->r_pool_n > (size_t)kFlatRangePoolKeys) {  // a list longer than the pool: give the larger buffers back
+        f->r_pool.reset();
+        f->r_sorted.reset();
+        f->r_pool_n = f->r_sorted_n = 0;
+    }
+    if (rc) return rc;
+    *out = res.release();
+    return DPQ_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dpq_flat_filter_create(dpq_flat* f, const uint32_t* words, int64_t n_bits, dpq_flat_filter** out) {
+    return guarded([&]() -> int {
+    const std::string who("dpq_flat_filter_create");
+    if (!out) return fail(DPQ_ERR_ARG, who + ": out is NULL");
+    *out = nullptr;
+    if (!f || n_bits < 0 || (n_bits > 0 && !words)) return fail(DPQ_ERR_ARG, who + ": NULL argument or n_bits < 0");
+    if (int rc = flat_device_present(who)) return rc;
+    DPQ_HIP(hipSetDevice(f->device));
+    // bit b of local word w = row 32 w + b = the caller's bit of the reported id row + id_offset
+    const int64_t n_words = (f->n + 31) / 32;
+    std::vector<uint32_t> h((size_t)n_words);
+    for (int64_t w = 0; w < n_words; ++w) {
+        uint32_t v = bitmap_bits32(words, n_bits, f->id_offset + 32 * w);
+        if (f->n - 32 * w < 32) v &= (1u << (f->n - 32 * w)) - 1u;
+        h[(size_t)w] = v;
+    }
+    std::unique_ptr<dpq_flat_filter> ff(new dpq_flat_filter());
+    ff->owner = f->serial;
+    ff->device = f->device;
+    DevBuf<uint32_t> d_words, d_cnt, d_off, d_flag;
+    int rc = d_words.alloc((size_t)n_words);
+    if (!rc) rc = d_cnt.alloc((size_t)n_words);
+    if (!rc) rc = d_off.alloc((size_t)n_words);
+    if (!rc) rc = d_flag.alloc(1);
+    if (rc) return rc;
+    DPQ_HIP(hipMemcpy(d_words, h.data(), (size_t)n_words * sizeof(uint32_t), hipMemcpyHostToDevice));
+    DPQ_HIP(hipMemset(d_flag, 0, sizeof(uint32_t)));
+    DPQ_HIP(dpq::flat_filter_count(d_words, n_words, d_cnt, d_off, &ff->n_allowed, nullptr));
+    if (ff->n_allowed < 0 || ff->n_allowed > f->n) return fail(DPQ_ERR_STATE, who + ": internal error: bad row count");
+    if ((rc = ff->list.alloc((size_t)ff->n_allowed))) return rc;
+    DPQ_HIP(dpq::launch_flat_filter_emit(d_words, n_words, d_off, ff->list, ff->n_allowed, d_flag, nullptr));
+    uint32_t bad = 0;
+    DPQ_HIP(hipMemcpy(&bad, d_flag, sizeof bad, hipMemcpyDeviceToHost));
+    if (bad) return fail(DPQ_ERR_STATE, who + ": internal error: the row list overflowed");
+    *out = ff.release();
+    return DPQ_OK;
+    });
+}
+
+void dpq_flat_filter_free(dpq_flat_filter* ff) {
+    if (!ff) return;
+    hipSetDevice(ff->device);
+    delete ff;
+}
+
+int dpq_flat_filter_count(const dpq_flat_filter* ff, int64_t* n_allowed) {
+    if (!ff || !n_allowed) return fail(DPQ_ERR_ARG, "dpq_flat_filter_count: NULL argument");
+    *n_allowed = ff->n_allowed;
+    return DPQ_OK;
+}
+
+int dpq_flat_search_filtered(dpq_flat* f, const dpq_flat_filter* ff, const float* queries, int nq, int top_k, int32_t* ids,
+                             float* dists) {
+    return guarded([&]() -> int {
+    return flat_search_filtered_call("dpq_flat_search_filtered", "dpq_flat_search_filtered_u8", f, ff, queries, nq, top_k, ids,
+                                     dists);
+    });
+}
+
+int dpq_flat_search_filtered_u8(dpq_flat* f, const dpq_flat_filter* ff, const uint8_t* queries, int nq, int top_k,
+                                int32_t* ids, float* dists) {
+    return guarded([&]() -> int {
+    return flat_search_filtered_call("dpq_flat_search_filtered_u8", "dpq_flat_search_filtered", f, ff, queries, nq, top_k, ids,
+                                     dists);
+    });
+}
+
+int dpq_flat_range_search(dpq_flat* f, const dpq_flat_filter* ff, const float* queries, int nq, const float* radii,
+                          dpq_range_result** out) {
+    return guarded([&]() -> int {
+    return flat_range_call("dpq_flat_range_search", "dpq_flat_range_search_u8", f, ff, queries, nq, radii, out);
+    });
+}
+
+int dpq_flat_range_search_u8(dpq_flat* f, const dpq_flat_filter* ff, const uint8_t* queries, int nq, const float* radii,
+                             dpq_range_result** out) {
+    return guarded([&]() -> int {
+    return flat_range_call("dpq_flat_range_search_u8", "dpq_flat_range_search", f, ff, queries, nq, radii, out);
+    });
+}
+
+int dpq_range_recall(int nq, const int64_t* found_lims, const int32_t* found_ids, const int64_t* truth_lims,
+                     const int32_t* truth_ids, double* recall, double* precision) {
+    return guarded([&]() -> int {
+    if (nq < 0 || !found_lims || !truth_lims || (found_lims[nq] > found_lims[0] && !found_ids) ||
+        (truth_lims[nq] > truth_lims[0] && !truth_ids))
+        return fail(DPQ_ERR_ARG, "bad argument to dpq_range_recall");
+    int64_t hits = 0, n_found = 0, n_truth = 0;
+    std::vector<int32_t> a, b, both;
+    auto ids_of = [](const int64_t* lims, const int32_t* ids, int q, std::vector<int32_t>* v) {
+        v->clear();
+        for (int64_t i = lims[q]; i < lims[q + 1]; ++i)
+            if (ids[i] >= 0) v->push_back(ids[i]);  // negative ids are ignored
+        std::sort(v->begin(), v->end());
+        v->erase(std::unique(v->begin(), v->end()), v->end());  // an id counts once per query
+    };
+    for (int q = 0; q < nq; ++q) {
+        if (found_lims[q + 1] < found_lims[q] || truth_lims[q + 1] < truth_lims[q])
+            return fail(DPQ_ERR_ARG, "dpq_range_recall: lims must not descend");
+        ids_of(found_lims, found_ids, q, &a);
+        ids_of(truth_lims, truth_ids, q, &b);
+        both.clear();
+        std::set_intersection(a.begin(), a.end(), b.begin(), b.end(), std::back_inserter(both));
+        hits += (int64_t)both.size();
+        n_found += (int64_t)a.size();
+        n_truth += (int64_t)b.size();
+    }
+    if (recall) *recall = n_truth ? (double)hits / (double)n_truth : 1.0;
+    if (precision) *precision = n_found ? (double)hits / (double)n_found : 1.0;
+    return DPQ_OK;
+    });
+}
+
+int dpq_bitmap_to_dfs(const uint32_t* words, int64_t n_bits, const uint32_t* vec_id, int64_t n_codes, uint32_t* words_out) {
+    return guarded([&]() -> int {
+    if (n_bits < 0 || (n_bits > 0 && !words) || !vec_id || n_codes < 1 || !words_out)
+        return fail(DPQ_ERR_ARG, "bad argument to dpq_bitmap_to_dfs");
+    std::fill(words_out, words_out + (n_codes + 1 + 31) / 32, 0u);
+    for (int64_t p = 0; p < n_codes; ++p) {
+        const int64_t v = vec_id[p];
+        if (v >= n_bits || !((words[v >> 5] >> (v & 31)) & 1u)) continue;
+        const int64_t r = ((n_codes & 1) == 0 && p == n_codes - 1) ? n_codes : p;  // the even-N id of the last DFS node
+        words_out[r >> 5] |= 1u << (r & 31);
+    }
+    return DPQ_OK;
+    });
+}
+
+int dpq_write_bitmap(const char* path, const uint32_t* words, int64_t n_bits) {
+    return guarded([&]() -> int {
+    if (!path || n_bits < 0 || (n_bits > 0 && !words)) return fail(DPQ_ERR_ARG, "bad argument to dpq_write_bitmap");
+    FILE* fp = fopen(path, "wb");
+    if (!fp) return fail(DPQ_ERR_IO, std::string("cannot open ") + path);
+    const size_t n_words = (size_t)((n_bits + 31) / 32);
+    const bool ok = fwrite(&n_bits, sizeof n_bits, 1, fp) == 1 && (n_words == 0 || fwrite(words, sizeof(uint32_t), n_words, fp) == n_words);
+    if (fclose(fp) != 0 || !ok) return fail(DPQ_ERR_IO, std::string("short write on ") + path);
+    return DPQ_OK;
+    });
+}
+
+int dpq_read_bitmap(const char* path, int64_t* n_bits, uint32_t* words) {
+    return guarded([&]() -> int {
+    if (!path || !n_bits) return fail(DPQ_ERR_ARG, "bad argument to dpq_read_bitmap");
+    FILE* fp = fopen(path, "rb");
+    if (!fp) return fail(DPQ_ERR_IO, std::string("cannot open ") + path);
+    std::unique_ptr<FILE, int (*)(FILE*)> closer(fp, fclose);
+    int64_t nb = 0;
+    if (fread(&nb, sizeof nb, 1, fp) != 1 || nb < 0) return fail(DPQ_ERR_IO, std::string("no bitmap header in ") + path);
+    const int64_t n_words = (nb + 31) / 32;
+    if (fseeko(fp, 0, SEEK_END) != 0) return fail(DPQ_ERR_IO, std::string("cannot seek in ") + path);
+    if ((int64_t)ftello(fp) < 8 + 4 * n_words)
+        return fail(DPQ_ERR_IO, std::string(path) + " is shorter than its " + std::to_string(nb) + " bits");
+    *n_bits = nb;
+    if (!words || n_words == 0) return DPQ_OK;
+    if (fseeko(fp, 8, SEEK_SET) != 0 || fread(words, sizeof(uint32_t), (size_t)n_words, fp) != (size_t)n_words)
+        return fail(DPQ_ERR_IO, std::string("short read on ") + path);
     return DPQ_OK;
     });
 }

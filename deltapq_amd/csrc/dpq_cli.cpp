@@ -49,8 +49,16 @@ static int die(const char* where, int rc) {
     return 1;
 }
 
+// -filter FILE: a bitmap over original vector ids (dpq_write_bitmap's format).
+static int read_filter(const std::string& path, std::vector<uint32_t>* words, int64_t* n_bits) {
+    int rc = dpq_read_bitmap(path.c_str(), n_bits, nullptr);
+    if (rc) return rc;
+    words->assign((size_t)((*n_bits + 31) / 32) + 1, 0u);
+    return dpq_read_bitmap(path.c_str(), n_bits, words->data());
+}
+
 int main(int argc, char* argv[]) {
-    std::string dataset, queryset, task = "approx_tree", ext = "fvecs", out_path, order = "dfs";
+    std::string dataset, queryset, task = "approx_tree", ext = "fvecs", out_path, order = "dfs", filter_path;
     int query_size = -1, top_k = 1, diff_argument = 1, debug = 0, max_height_folds = 1, method = 1;
     int PQ_M = 0, PQ_K = 0, gpus = 1, gt_topk = -1, rerank = 0;
     bool topk_given = false;
@@ -64,6 +72,7 @@ int main(int argc, char* argv[]) {
         if (arg == "-topk") top_k = atoi(nx), topk_given = true;
         if (arg == "-gt_topk") gt_topk = atoi(nx);
         if (arg == "-rerank") rerank = atoi(nx);
+        if (arg == "-filter") filter_path = nx;
         if (arg == "-N") N = atoll(nx);
         if (arg == "-diff") diff_argument = atoi(nx);
         if (arg == "-query_size") query_size = atoi(nx);
@@ -264,14 +273,20 @@ int main(int argc, char* argv[]) {
         // parts; every part is a dpq_flat handle with its own id offset, the partial lists meet in dpq_merge_topk_host.
         // With -ext bvecs the bytes stay bytes (dpq_flat_open_u8 / dpq_flat_search_u8): the same bits, the same file.
         if (dataset.empty() || !topk_given || top_k < 1 || query_size < 1) {
-            std::cout << "usage: deltapq -dataset DIR -task groundtruth -topk K -query_size Q [-N N] [-ext fvecs|bvecs]" << std::endl;
+            std::cout << "usage: deltapq -dataset DIR -task groundtruth -topk K -query_size Q [-N N] [-ext fvecs|bvecs] [-filter FILE]" << std::endl;
             return 2;
         }
         const bool bvecs = ext == "bvecs";
         const std::string q_path = dataset + "/query." + ext, base_path = dataset + "/base." + ext;
         int64_t nq_file = 0, n_file = 0;
         int32_t D = 0, Db = 0;
-        int rc = dpq_read_vecs(q_path.c_str(), bvecs, &nq_file, &D, nullptr, 0);
+        int rc = DPQ_OK;
+        // -filter FILE: the exact top-k among the vectors the bitmap allows, one filter per part from the same bitmap
+        const bool filtered = !filter_path.empty();
+        std::vector<uint32_t> f_words;
+        int64_t f_bits = 0;
+        if (filtered && (rc = read_filter(filter_path, &f_words, &f_bits))) return die("dpq_read_bitmap", rc);
+        rc = dpq_read_vecs(q_path.c_str(), bvecs, &nq_file, &D, nullptr, 0);
         if (rc) return die("ReadTopN", rc);
         if (query_size > nq_file) {
             std::cout << "-query_size " << query_size << " exceeds the " << nq_file << " available queries" << std::endl;
@@ -333,12 +348,23 @@ int main(int argc, char* argv[]) {
                 rc = dpq_flat_open(part.data(), rows, D, 0, r0, &f);
             }
             if (rc) return die(bvecs ? "dpq_flat_open_u8" : "dpq_flat_open", rc);
-            const int kk = (int)std::min<int64_t>(top_k, rows);  // a short last part gives a short list, padded
+            // a short last part gives a short list, padded; a filtered search pads its own rows
+            const int kk = filtered ? top_k : (int)std::min<int64_t>(top_k, rows);
             p_ids.resize((size_t)nq * kk);
             p_dists.resize((size_t)nq * kk);
-            rc = bvecs ? dpq_flat_search_u8(f, queries8.data(), nq, kk, p_ids.data(), p_dists.data())
-                       : dpq_flat_search(f, queries.data(), nq, kk, p_ids.data(), p_dists.data());
-            if (rc) return die(bvecs ? "dpq_flat_search_u8" : "dpq_flat_search", rc);
+            if (filtered) {
+                dpq_flat_filter* ff = nullptr;
+                rc = dpq_flat_filter_create(f, f_words.data(), f_bits, &ff);
+                if (rc) return die("dpq_flat_filter_create", rc);
+                rc = bvecs ? dpq_flat_search_filtered_u8(f, ff, queries8.data(), nq, kk, p_ids.data(), p_dists.data())
+                           : dpq_flat_search_filtered(f, ff, queries.data(), nq, kk, p_ids.data(), p_dists.data());
+                if (rc) return die(bvecs ? "dpq_flat_search_filtered_u8" : "dpq_flat_search_filtered", rc);
+                dpq_flat_filter_free(ff);
+            } else {
+                rc = bvecs ? dpq_flat_search_u8(f, queries8.data(), nq, kk, p_ids.data(), p_dists.data())
+                           : dpq_flat_search(f, queries.data(), nq, kk, p_ids.data(), p_dists.data());
+                if (rc) return die(bvecs ? "dpq_flat_search_u8" : "dpq_flat_search", rc);
+            }
             dpq_flat_close(f);
             for (int q = 0; q < nq; ++q)
                 for (int r = 0; r < top_k; ++r) {
@@ -355,7 +381,8 @@ int main(int argc, char* argv[]) {
         std::cout << elapsed / (double)nq * 1000 << " [msec/query] " << std::endl;
         const std::string gt_dir = dataset + "/groundtruth";
         mkdir(gt_dir.c_str(), 0777);  // (exists already: fine)
-        const std::string gt_path = gt_dir + "/N" + std::to_string(n) + "Top" + std::to_string(top_k) + ".txt";  // main.cpp:663-667
+        const std::string gt_path = gt_dir + "/N" + std::to_string(n) + "Top" + std::to_string(top_k) +
+                                    (filtered ? ".filtered.txt" : ".txt");  // main.cpp:663-667
         rc = dpq_write_groundtruth(gt_path.c_str(), out_ids.data(), out_dists.data(), nq, top_k);
         if (rc) return die("write_groundtruth", rc);
         std::cout << gt_path << std::endl;
@@ -367,7 +394,7 @@ int main(int argc, char* argv[]) {
         // against base.{ext} (main.cpp:898-939) and reports the recall of that answer too.
         if (PQ_M <= 0 || PQ_K <= 0 || dataset.empty() || N < 1 || !topk_given || top_k < 1 || query_size < 1) {
             std::cout << "usage: deltapq -dataset DIR -task recall -m M -k K -N N -query_size Q -topk K [-gt_topk G] [-rerank R]"
-                         " [-ext fvecs|bvecs]" << std::endl;
+                         " [-ext fvecs|bvecs] [-filter FILE]" << std::endl;
             return 2;
         }
         if (gt_topk < 0) gt_topk = top_k;
@@ -377,6 +404,12 @@ int main(int argc, char* argv[]) {
         }
         if (rerank != 0 && (rerank < top_k || rerank > 2048)) {
             std::cout << "-rerank " << rerank << " outside " << top_k << "..2048" << std::endl;
+            return 1;
+        }
+        // -filter FILE: dpq_query_batch_filtered under the bitmap translated to DFS positions, against the .filtered.txt truth
+        const bool filtered = !filter_path.empty();
+        if (filtered && rerank) {
+            std::cout << "-rerank cannot be combined with -filter: there is no filtered re-rank" << std::endl;
             return 1;
         }
         const bool bvecs = ext == "bvecs";
@@ -408,7 +441,8 @@ int main(int argc, char* argv[]) {
             std::cout << "query dimension " << D << " != M*Ds = " << PQ_M * cDs << std::endl;
             return 1;
         }
-        const std::string gt_path = dataset + "/groundtruth/N" + std::to_string(N) + "Top" + std::to_string(gt_topk) + ".txt";
+        const std::string gt_path = dataset + "/groundtruth/N" + std::to_string(N) + "Top" + std::to_string(gt_topk) +
+                                    (filtered ? ".filtered.txt" : ".txt");
         int32_t g_nq = 0, g_k = 0;
         rc = dpq_read_groundtruth(gt_path.c_str(), &g_nq, &g_k, nullptr, nullptr);
         if (rc) return die("read_groundtruth", rc);
@@ -442,13 +476,27 @@ int main(int argc, char* argv[]) {
         const int R = rerank ? rerank : top_k;
         std::vector<int32_t> pos((size_t)nq * R), found((size_t)nq * R);
         std::vector<float> pq_d((size_t)nq * R);
+        dpq_filter* filt = nullptr;
+        if (filtered) {
+            std::vector<uint32_t> f_words, dfs_words((size_t)((N + 1 + 31) / 32));
+            int64_t f_bits = 0;
+            rc = read_filter(filter_path, &f_words, &f_bits);
+            if (rc) return die("dpq_read_bitmap", rc);
+            rc = dpq_bitmap_to_dfs(f_words.data(), f_bits, vec_id.data(), N, dfs_words.data());
+            if (rc) return die("dpq_bitmap_to_dfs", rc);
+            rc = dpq_filter_create(idx, dfs_words.data(), N + 1, &filt);
+            if (rc) return die("dpq_filter_create", rc);
+        }
         const double t0 = Elapsed();
         for (int q0 = 0; q0 < nq; q0 += 1024) {
             const int m = std::min(1024, nq - q0);
-            rc = dpq_query_batch(idx, queries.data() + (size_t)q0 * D, m, R, pos.data() + (size_t)q0 * R, pq_d.data() + (size_t)q0 * R);
-            if (rc) return die("dpq_query_batch", rc);
+            const float* qp = queries.data() + (size_t)q0 * D;
+            rc = filtered ? dpq_query_batch_filtered(idx, filt, qp, m, R, pos.data() + (size_t)q0 * R, pq_d.data() + (size_t)q0 * R)
+                          : dpq_query_batch(idx, qp, m, R, pos.data() + (size_t)q0 * R, pq_d.data() + (size_t)q0 * R);
+            if (rc) return die(filtered ? "dpq_query_batch_filtered" : "dpq_query_batch", rc);
         }
         std::cout << (Elapsed() - t0) / (double)nq * 1000 << " [msec/query] " << std::endl;
+        dpq_filter_free(filt);
         dpq_close(idx);
         for (size_t i = 0; i < found.size(); ++i) {
             int64_t p = pos[i];
@@ -459,7 +507,7 @@ int main(int argc, char* argv[]) {
         rc = dpq_recall(found.data(), R, top_k, truth.data(), g_k, top_k, nq, &rec);
         if (rc) return die("dpq_recall", rc);
         char line[128];
-        snprintf(line, sizeof line, "recall@%d = %.6f", top_k, rec);
+        snprintf(line, sizeof line, filtered ? "filtered recall@%d = %.6f" : "recall@%d = %.6f", top_k, rec);
         std::cout << line << std::endl;
         if (rerank) {
             const std::string base_path = dataset + "/base." + ext;

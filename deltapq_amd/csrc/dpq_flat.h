@@ -75,4 +75,36 @@ hipError_t launch_flat_rerank_u8(const int8_t* d_base, int64_t n, int D, int Dp,
                                  int64_t n_map, uint64_t* d_keys, uint32_t* d_flag, int32_t* d_ids, float* d_dists,
                                  hipStream_t stream);
 
+// ---- filtered and range search (dpq_flat_filter.hip) ----------------------------------------------------------------
+// A filter is the ascending list of a handle's eligible rows.  d_words [n_words]: bit b of word w = row 32 w + b.
+// flat_filter_count fills d_cnt / d_off [n_words] (popcounts and their exclusive prefix sum) and waits for n_allowed;
+// launch_flat_filter_emit then writes d_list [cap] (*d_flag is set if an entry would fall outside it).
+hipError_t flat_filter_count(const uint32_t* d_words, int64_t n_words, uint32_t* d_cnt, uint32_t* d_off, int64_t* n_allowed,
+                             hipStream_t stream);
+hipError_t launch_flat_filter_emit(const uint32_t* d_words, int64_t n_words, const uint32_t* d_off, uint32_t* d_list,
+                                   int64_t cap, uint32_t* d_flag, hipStream_t stream);
+// launch_flat_search / launch_flat_search_u8 over the rows d_list [n_list] names (n_list may be below top_k, or zero:
+// rows are padded with -1 / +inf).  Buffers as there.
+hipError_t launch_flat_search_list(const float* d_base, const uint32_t* d_list, int64_t n_list, int Dp, const float* d_queries,
+                                   int nq, int top_k, int64_t id_offset, uint64_t* d_keys, FlatQueryState* d_state,
+                                   int32_t* d_ids, float* d_dists, hipStream_t stream);
+hipError_t launch_flat_search_list_u8(const int8_t* d_base, const int32_t* d_vnorm, const uint32_t* d_list, int64_t n_list,
+                                      int Dp, const int8_t* d_queries, const int32_t* d_qnorm, int nq, int top_k,
+                                      int64_t id_offset, uint64_t* d_keys, FlatQueryState* d_state, int32_t* d_ids,
+                                      float* d_dists, hipStream_t stream);
+// Range search, count then emit.  launch_flat_range_state: count = overflow = 0, thr = d_thr[q] (distance bits of the
+// radius << 32; 0 passes nothing).  A pass forms the distances of nq queries to n_entries rows (those of d_list, or all
+// when it is NULL) and, for keys below thr, counts them (d_pool NULL) or appends them to the query's list
+// d_pool[d_offs[q] .. d_offs[q + 1]).  flat_range_sort: hipcub's two-call protocol (d_temp NULL: *temp_bytes only); sorts
+// every list of the pool by key into d_out.
+hipError_t launch_flat_range_state(FlatQueryState* d_state, const uint64_t* d_thr, int nq, hipStream_t stream);
+hipError_t launch_flat_range_pass(const float* d_base, const uint32_t* d_list, int64_t n_entries, int Dp,
+                                  const float* d_queries, int nq, int64_t id_offset, uint64_t* d_pool, const int64_t* d_offs,
+                                  FlatQueryState* d_state, hipStream_t stream);
+hipError_t launch_flat_range_pass_u8(const int8_t* d_base, const int32_t* d_vnorm, const uint32_t* d_list, int64_t n_entries,
+                                     int Dp, const int8_t* d_queries, const int32_t* d_qnorm, int nq, int64_t id_offset,
+                                     uint64_t* d_pool, const int64_t* d_offs, FlatQueryState* d_state, hipStream_t stream);
+hipError_t flat_range_sort(void* d_temp, size_t* temp_bytes, const uint64_t* d_in, uint64_t* d_out, int64_t n_keys,
+                           int n_lists, const int64_t* d_offs, hipStream_t stream);
+
 }  // namespace dpq

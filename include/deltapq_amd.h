@@ -37,6 +37,9 @@
  *   recall (main.cpp:727-803)                   dpq_recall, dpq_read/write_groundtruth
  *   (none: the reference never reads a code     dpq_get_codes / dpq_reconstruct / dpq_decode_range,
  *     back out of its index)                      dpq_dtc_decode (FAISS's sa_decode / reconstruct_batch)
+ *   (none: FAISS's IndexFlat::search with an    dpq_flat_filter_create / dpq_flat_search_filtered[_u8]
+ *     IDSelector)
+ *   (none: FAISS's IndexFlat::range_search)     dpq_flat_range_search[_u8], dpq_range_recall
  *
  * Conventions: plain pointers and sizes only; the caller owns every host
  * buffer it passes, the library owns device memory.  Every function returns a
@@ -575,6 +578,69 @@ int dpq_flat_rerank_u8(dpq_flat* f, const uint8_t* queries, int nq, const int32_
                        int32_t* ids, float* dists);
 int dpq_flat_rerank_u8_device(dpq_flat* f, const uint8_t* d_queries, int nq, const int32_t* d_cand_ids, int n_cand,
                               int top_k, int32_t* d_ids, float* d_dists, void* hip_stream);
+
+/* ---- exact filtered and range search ------------------------------------------
+ * The two other kinds of search the PQ index offers (dpq_query_batch_filtered, dpq_range_search), answered exactly over
+ * the raw vectors of a dpq_flat: their ground truth.  FAISS's IndexFlat::search with an IDSelector, and
+ * IndexFlat::range_search; the reference has neither.
+ * Filter: the bitmap convention of dpq_filter -- bit i is bit (i & 31) of words[i >> 5], n_bits bits -- over the handle's
+ * REPORTED ids, row + id_offset: row r is eligible iff r + id_offset < n_bits and that bit is set.  n_bits >= 0, and
+ * n_bits == 0 allows nothing.  A base searched in parts builds each part's filter from the same global bitmap, and
+ * dpq_merge_topk_host merges the partial lists unchanged.  The id map of dpq_flat_set_id_map plays no part in it.  A
+ * filter works on the handle it was made for, fp32 or byte; one made on another handle is DPQ_ERR_ARG.  A NULL filter
+ * is DPQ_ERR_ARG in the _filtered calls and means "every row of the handle" in the range calls.  On the device a filter
+ * is the ascending list of its eligible rows (4 bytes each), so a search costs what the eligible rows cost.
+ * Filtered top-k: the contract of dpq_flat_search[_u8] applied to the eligible rows only -- top_k entries ascending by
+ * (distance, id), the distance bits those of dpq_flat_search, the lowest ids winning at the k-th boundary -- with rows
+ * padded with id -1 / +inf when fewer than top_k rows are eligible (none at all: an all-padding answer, not an error;
+ * there is no DPQ_ERR_TOPK here).  top_k outside 1..DPQ_FLAT_MAX_TOPK is DPQ_ERR_ARG; nq == 0 is DPQ_OK.
+ * Range search: for query q every eligible row whose reported fp32 distance d satisfies d < radii[q], STRICTLY (the rule
+ * of dpq_range_search); d is the squared L2 with the bits of dpq_flat_search, on a byte handle (float)(int32) of the
+ * integer sum.  Within a list the entries ascend by (distance, id).  A radius <= 0 gives an empty list, +inf every
+ * eligible row; a NaN radius is DPQ_ERR_ARG, checked before any device work.  The answer is a dpq_range_result, the type
+ * dpq_range_search returns: dpq_range_result_get / dpq_range_result_free serve both.  A failed host allocation for the
+ * lists is DPQ_ERR_NOMEM.
+ * Handle kinds do not mix: a _u8 call on an fp32 handle or the reverse is DPQ_ERR_ARG with a message that names the other
+ * function.  Order of the checks: the arguments that need no handle (NULL pointers, nq < 0, top_k, n_bits, NaN radii),
+ * then the device (none visible: DPQ_ERR_NO_DEVICE), then the handle (its kind, the filter's owner).  Host buffers,
+ * synchronous, one thread per handle at a time.
+ * Device memory of a range call: it counts every list in one pass over the distances and forms them a second time to
+ * write them (no list is ever cut short, no rerun), 1024 queries at a time, in sub-batches of queries whose lists
+ * together hold at most 2^19 entries: 4 MB of keys and as much again sorted, kept until dpq_flat_close, plus the
+ * segmented sort's workspace.  A single list longer than that makes a sub-batch of its own with buffers of 16 bytes per
+ * entry (at most 16 * n), released before the call returns. */
+typedef struct dpq_flat_filter dpq_flat_filter;
+/* words[(n_bits + 31) / 32], host memory, read during the call only.  Uploads the handle's slice of the bitmap and
+ * compacts it on the device into the row list (popcount, prefix sum, emit). */
+int dpq_flat_filter_create(dpq_flat* f, const uint32_t* words, int64_t n_bits, dpq_flat_filter** out);
+void dpq_flat_filter_free(dpq_flat_filter* ff);  /* NULL: nothing happens */
+/* Rows of its handle the filter allows. */
+int dpq_flat_filter_count(const dpq_flat_filter* ff, int64_t* n_allowed);
+int dpq_flat_search_filtered(dpq_flat* f, const dpq_flat_filter* ff, const float* queries, int nq, int top_k, int32_t* ids,
+                             float* dists);
+int dpq_flat_search_filtered_u8(dpq_flat* f, const dpq_flat_filter* ff, const uint8_t* queries, int nq, int top_k,
+                                int32_t* ids, float* dists);
+/* ff may be NULL: every row of the handle is eligible.  queries[nq][D], radii[nq]: host memory. */
+int dpq_flat_range_search(dpq_flat* f, const dpq_flat_filter* ff, const float* queries, int nq, const float* radii,
+                          dpq_range_result** out);
+int dpq_flat_range_search_u8(dpq_flat* f, const dpq_flat_filter* ff, const uint8_t* queries, int nq, const float* radii,
+                             dpq_range_result** out);
+
+/* Host only.  Two range answers in lims / ids form over the same nq queries and in the same id space (mapping ids is the
+ * caller's job), summed over the queries: recall = |found & truth| / |truth|, precision = |found & truth| / |found|; a
+ * zero denominator gives 1.0.  An id counts once per query; negative ids are ignored.  Either output may be NULL. */
+int dpq_range_recall(int nq, const int64_t* found_lims, const int32_t* found_ids, const int64_t* truth_lims,
+                     const int32_t* truth_ids, double* recall, double* precision);
+/* Host only.  A bitmap over ORIGINAL vector ids -> the bitmap dpq_filter_create takes for the DTC index built from those
+ * vectors.  vec_id[n_codes]: DFS position -> vector id (dpq_tree_array(.., 0) or dpq_read_qnode_ids).  For position p
+ * with reported id r, bit r of the output is bit vec_id[p] of the input, or 0 when vec_id[p] >= n_bits; r = p, except that
+ * the last node of an even n_codes is reported as n_codes (bit n_codes - 1 then stays 0). */
+int dpq_bitmap_to_dfs(const uint32_t* words, int64_t n_bits, const uint32_t* vec_id, int64_t n_codes,
+                      uint32_t* words_out /* [(n_codes + 1 + 31) / 32] */);
+/* Host only.  A bitmap file: int64 n_bits, then (n_bits + 31) / 32 little-endian uint32 words.  Read with words == NULL to
+ * learn n_bits.  A file shorter than its header says: DPQ_ERR_IO. */
+int dpq_write_bitmap(const char* path, const uint32_t* words, int64_t n_bits);
+int dpq_read_bitmap(const char* path, int64_t* n_bits, uint32_t* words);
 
 /* Host only.  Vectors [first, first + count) of an .fvecs / .bvecs file (the streaming read of main.cpp:607-640);
  * out[count][D] may be NULL to learn D.  A range past the end of the file: DPQ_ERR_IO. */
