@@ -53,7 +53,7 @@ class DtcStats(ctypes.Structure):
 
 class TrainOpts(ctypes.Structure):
     _fields_ = [("device", c_i32), ("max_iters", c_i32), ("seed", ctypes.c_uint64), ("use_initial", c_i32),
-                ("reserved", c_i32 * 3)]
+                ("init", c_i32), ("restarts", c_i32), ("reserved", c_i32 * 1)]
 
 
 class TrainStats(ctypes.Structure):
@@ -96,6 +96,10 @@ SYMBOLS = [
      [_VP, c_i64, ctypes.c_int, _VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _VP]),
     ("dpq_train_codebook", ctypes.c_int,
      [_VP, c_i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, P(TrainOpts), _VP, P(TrainStats)]),
+    ("dpq_kmeanspp_seed", ctypes.c_int,
+     [_VP, c_i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.c_int, _VP, _VP]),
+    ("dpq_train_potential", ctypes.c_int,
+     [_VP, c_i64, ctypes.c_int, _VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _VP]),
     ("dpq_write_codewords", ctypes.c_int, [ctypes.c_char_p, _VP, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     ("dpq_open_plain_memory", ctypes.c_int, [_VP, c_i64, ctypes.c_int, ctypes.c_int, P(OpenOpts), P(_VP)]),
     ("dpq_open_plain_file", ctypes.c_int, [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, P(OpenOpts), P(_VP)]),

@@ -188,16 +188,24 @@ def encode_pq(vectors, codebook, device=0):
     return out
 
 
-def train_codebook(vectors, M=8, K=256, max_iters=25, seed=0, init=None, device=0):
+_TRAIN_STARTS = {"rows": 0, "kmeans++": 1}
+
+
+def train_codebook(vectors, M=8, K=256, max_iters=25, seed=0, init=None, device=0, start="rows", restarts=1):
     """Codebook learning on the GPU (dpq_train_codebook; replaces PQ::Learn, pq.cpp:112-157, with this build's own
     exact semantics -- no reference semantics (cv::kmeans)).  init: a start [M][K][Ds] instead of the seeded one.
-    Returns (codebook float32 [M][K][Ds], stats dict)."""
+    start: "rows" (K random rows, the same for every sub-space) or "kmeans++" (per sub-space, on the GPU).
+    restarts: that many independent runs with seed, seed + 1, ...; every sub-space keeps the run with the lowest
+    potential.  Returns (codebook float32 [M][K][Ds], stats dict)."""
+    if start not in _TRAIN_STARTS:
+        raise ValueError('start must be "rows" or "kmeans++"')
     lib = _lib.load()
     v = np.ascontiguousarray(vectors, dtype=np.float32)
     assert v.ndim == 2
     n, D = v.shape
     Ds = -(-D // M) if M >= 1 else 1
-    opts = _lib.TrainOpts(device=device, max_iters=max_iters, seed=seed, use_initial=int(init is not None))
+    opts = _lib.TrainOpts(device=device, max_iters=max_iters, seed=seed, use_initial=int(init is not None),
+                          init=_TRAIN_STARTS[start], restarts=restarts)
     if init is None:
         cb = np.zeros((max(M, 1), max(K, 1), Ds), dtype=np.float32)
     else:
@@ -208,6 +216,32 @@ def train_codebook(vectors, M=8, K=256, max_iters=25, seed=0, init=None, device=
     stats = {k: getattr(st, k) for k, _ in st._fields_ if k != "distortion"}
     stats["distortion"] = [st.distortion[i] for i in range(st.iters_run)]
     return cb, stats
+
+
+def kmeanspp_seed(vectors, M=8, K=256, seed=0, device=0):
+    """The k-means++ start alone (dpq_kmeanspp_seed): (codebook float32 [M][K][Ds], potential float64 [M])."""
+    lib = _lib.load()
+    v = np.ascontiguousarray(vectors, dtype=np.float32)
+    assert v.ndim == 2
+    n, D = v.shape
+    cb = np.zeros((max(M, 1), max(K, 1), -(-D // M) if M >= 1 else 1), dtype=np.float32)
+    pot = np.zeros(max(M, 1), dtype=np.float64)
+    check(lib.dpq_kmeanspp_seed(_np_ptr(v), n, D, M, K, seed, device, _np_ptr(cb), _np_ptr(pot)), "dpq_kmeanspp_seed")
+    return cb, pot
+
+
+def train_potential(vectors, codebook, device=0):
+    """The leaf-ordered potential of a codebook per sub-space (dpq_train_potential): float64 [M], the sum of the
+    winning distances in the order the header states, so two codebooks compare reproducibly."""
+    lib = _lib.load()
+    v = np.ascontiguousarray(vectors, dtype=np.float32)
+    cb = np.ascontiguousarray(codebook, dtype=np.float32)
+    assert v.ndim == 2 and cb.ndim == 3
+    M, K, Ds = cb.shape
+    pot = np.zeros(M, dtype=np.float64)
+    check(lib.dpq_train_potential(_np_ptr(v), v.shape[0], v.shape[1], _np_ptr(cb), M, K, Ds, device, _np_ptr(pot)),
+          "dpq_train_potential")
+    return pot
 
 
 def write_codewords(path, codebook):

@@ -8,6 +8,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -2134,62 +2135,156 @@ int dpq_encode_pq(const float* vectors, int64_t n, int D, const float* codewords
     });
 }
 
-int dpq_train_codebook(const float* vectors, int64_t n, int D, int M, int K, const dpq_train_opts* opts, float* codewords,
-                       dpq_train_stats* stats) {
-    return guarded([&]() -> int {
-    const int device = opts ? opts->device : 0, max_iters = opts ? opts->max_iters : 25;
-    if (!vectors || !codewords) return fail(DPQ_ERR_ARG, "dpq_train_codebook: NULL argument");
-    if (D < 1 || M < 1 || M > 256) return fail(DPQ_ERR_ARG, "dpq_train_codebook: D < 1 or M outside 1..256");
-    if (K < 2 || K > 256) return fail(DPQ_ERR_ARG, "dpq_train_codebook: K outside 2..256 (one byte per label)");
-    if (n < K) return fail(DPQ_ERR_ARG, "dpq_train_codebook: fewer vectors than codewords (K > n)");
-    if (n * M >= ((int64_t)1 << 31)) return fail(DPQ_ERR_ARG, "dpq_train_codebook: n * M >= 2^31");
-    if (max_iters < 1 || max_iters > 64) return fail(DPQ_ERR_ARG, "dpq_train_codebook: max_iters outside 1..64");
-    const int Ds = (D + M - 1) / M;
-    const size_t lds = dpq::train_lds_bytes(K, Ds);
+// The argument checks dpq_train_codebook, dpq_kmeanspp_seed and dpq_train_potential share; 0 or a failed status.
+static int train_check_shape(const char* who, int64_t n, int D, int M, int K) {
+    const std::string w = std::string(who) + ": ";
+    if (D < 1 || M < 1 || M > 256) return fail(DPQ_ERR_ARG, w + "D < 1 or M outside 1..256");
+    if (K < 2 || K > 256) return fail(DPQ_ERR_ARG, w + "K outside 2..256 (one byte per label)");
+    if (n < K) return fail(DPQ_ERR_ARG, w + "fewer vectors than codewords (K > n)");
+    if (n * M >= ((int64_t)1 << 31)) return fail(DPQ_ERR_ARG, w + "n * M >= 2^31");
+    const size_t lds = dpq::train_lds_bytes(K, (D + M - 1) / M);
     if (lds == 0 || lds > 160 * 1024)
-        return fail(DPQ_ERR_ARG, "dpq_train_codebook: a sub-space's codewords need more than 160 KB of LDS");
+        return fail(DPQ_ERR_ARG, w + "a sub-space's codewords need more than 160 KB of LDS");
+    return DPQ_OK;
+}
+
+static int train_select_device(int device) {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail(DPQ_ERR_NO_DEVICE, "no HIP device visible; this library has no CPU fallback");
     if (device < 0 || device >= ndev) return fail(DPQ_ERR_NO_DEVICE, "device ordinal out of range");
     DPQ_HIP(hipSetDevice(device));
-    if (!(opts && opts->use_initial)) {
-        // the seeded start (header comment): K rows without replacement, the same rows for every sub-space
-        std::vector<int64_t> p((size_t)n);
-        std::iota(p.begin(), p.end(), (int64_t)0);
-        uint64_t s = opts ? opts->seed : 0;
-        for (int i = 0; i < K; ++i) {
-            s += 0x9E3779B97F4A7C15ull;
-            uint64_t z = s;
-            z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-            z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-            z ^= z >> 31;
-            std::swap(p[(size_t)i], p[(size_t)i + (size_t)(z % (uint64_t)(n - i))]);
-            for (int m = 0; m < M; ++m)
-                for (int d = 0; d < Ds; ++d) {
-                    const int col = m * Ds + d;
-                    codewords[((size_t)m * K + i) * Ds + d] = col < D ? vectors[(size_t)p[(size_t)i] * D + col] : 0.0f;
-                }
-        }
+    return DPQ_OK;
+}
+
+// the random-rows start (header comment): K rows without replacement, the same rows for every sub-space
+static void train_rows_start(const float* vectors, int64_t n, int D, int M, int K, int Ds, uint64_t seed, float* codewords) {
+    std::vector<int64_t> p((size_t)n);
+    std::iota(p.begin(), p.end(), (int64_t)0);
+    uint64_t s = seed;
+    for (int i = 0; i < K; ++i) {
+        s += 0x9E3779B97F4A7C15ull;
+        uint64_t z = s;
+        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+        z ^= z >> 31;
+        std::swap(p[(size_t)i], p[(size_t)i + (size_t)(z % (uint64_t)(n - i))]);
+        for (int m = 0; m < M; ++m)
+            for (int d = 0; d < Ds; ++d) {
+                const int col = m * Ds + d;
+                codewords[((size_t)m * K + i) * Ds + d] = col < D ? vectors[(size_t)p[(size_t)i] * D + col] : 0.0f;
+            }
     }
-    dpq::TrainStats st;
+}
+
+int dpq_train_codebook(const float* vectors, int64_t n, int D, int M, int K, const dpq_train_opts* opts, float* codewords,
+                       dpq_train_stats* stats) {
+    return guarded([&]() -> int {
+    const int device = opts ? opts->device : 0, max_iters = opts ? opts->max_iters : 25;
+    const int init = opts ? opts->init : 0, restarts = opts ? opts->restarts : 0;
+    const bool use_initial = opts && opts->use_initial;
+    const uint64_t seed = opts ? opts->seed : 0;
+    if (!vectors || !codewords) return fail(DPQ_ERR_ARG, "dpq_train_codebook: NULL argument");
+    if (max_iters < 1 || max_iters > 64) return fail(DPQ_ERR_ARG, "dpq_train_codebook: max_iters outside 1..64");
+    if (init < 0 || init > 1) return fail(DPQ_ERR_ARG, "dpq_train_codebook: init outside 0..1");
+    if (restarts < 0 || restarts > 16) return fail(DPQ_ERR_ARG, "dpq_train_codebook: restarts outside 0..16");
+    if (init == 1 && use_initial)
+        return fail(DPQ_ERR_ARG, "dpq_train_codebook: init = 1 (k-means++) together with use_initial");
+    int rc = train_check_shape("dpq_train_codebook", n, D, M, K);
+    if (rc) return rc;
+    const int Ds = (D + M - 1) / M;
+    if ((rc = train_select_device(device))) return rc;
+    const auto wall0 = std::chrono::steady_clock::now();
+    const int runs = std::max(1, restarts);
+    const size_t sub_floats = (size_t)K * Ds;  // one sub-space's codewords
     std::string err;
-    int rc = dpq::train_codebook(vectors, n, D, M, K, Ds, max_iters, codewords, &st, &err);
-    if (rc) return fail(rc, "dpq_train_codebook: " + err);
+    dpq::Trainer trainer;
+    if ((rc = trainer.open(vectors, n, D, M, K, Ds, &err))) return fail(rc, "dpq_train_codebook: " + err);
+    std::vector<float> start, run_cb;   // restarts: the caller's start is kept, `codewords` collects the winners
+    std::vector<double> pot((size_t)M), best((size_t)M);
+    if (runs > 1) {
+        run_cb.resize((size_t)M * sub_floats);
+        if (use_initial) start.assign(codewords, codewords + (size_t)M * sub_floats);
+    }
+    dpq::TrainStats sum;
+    sum.converged = 1;
+    for (int r = 0; r < runs; ++r) {
+        float* cb = runs > 1 ? run_cb.data() : codewords;
+        if (init == 1) {
+            rc = trainer.seed_kmeanspp(seed + (uint64_t)r, nullptr, nullptr, &err);
+        } else {
+            if (!use_initial) train_rows_start(vectors, n, D, M, K, Ds, seed + (uint64_t)r, cb);
+            rc = trainer.set_codebook(use_initial && runs > 1 ? start.data() : cb, &err);
+        }
+        dpq::TrainStats st;
+        if (!rc) rc = trainer.lloyd(max_iters, &st, &err);
+        if (!rc) rc = trainer.get_codebook(cb, &err);
+        if (!rc && runs > 1) rc = trainer.potential(pot.data(), &err);
+        if (rc) return fail(rc, "dpq_train_codebook: " + err);
+        if (runs > 1)
+            for (int m = 0; m < M; ++m)
+                if (r == 0 || pot[(size_t)m] < best[(size_t)m]) {  // strict: a tie stays with the lower r
+                    best[(size_t)m] = pot[(size_t)m];
+                    memcpy(codewords + (size_t)m * sub_floats, cb + (size_t)m * sub_floats, sub_floats * sizeof(float));
+                }
+        if (r == 0) memcpy(sum.distortion, st.distortion, sizeof st.distortion);
+        sum.iters_run = std::max(sum.iters_run, st.iters_run);
+        sum.converged = sum.converged && st.converged;
+        sum.reseeded += st.reseeded;
+        sum.gpu_ms += st.gpu_ms;
+        sum.rounds_ms += st.rounds_ms;
+        sum.assign_ms += st.assign_ms;
+        sum.update_ms += st.update_ms;
+        sum.repair_ms += st.repair_ms;
+    }
+    sum.wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
     if (stats) {
         memset(stats, 0, sizeof *stats);
-        stats->iters_run = st.iters_run;
-        stats->converged = st.converged;
-        stats->reseeded = st.reseeded;
-        memcpy(stats->distortion, st.distortion, sizeof st.distortion);
-        stats->gpu_ms = st.gpu_ms;
-        stats->wall_ms = st.wall_ms;
-        stats->rounds_ms = st.rounds_ms;
-        stats->assign_ms = st.assign_ms;
-        stats->update_ms = st.update_ms;
-        stats->repair_ms = st.repair_ms;
+        stats->iters_run = sum.iters_run;
+        stats->converged = sum.converged;
+        stats->reseeded = sum.reseeded;
+        memcpy(stats->distortion, sum.distortion, sizeof sum.distortion);
+        stats->gpu_ms = sum.gpu_ms;
+        stats->wall_ms = sum.wall_ms;
+        stats->rounds_ms = sum.rounds_ms;
+        stats->assign_ms = sum.assign_ms;
+        stats->update_ms = sum.update_ms;
+        stats->repair_ms = sum.repair_ms;
     }
     return DPQ_OK;
+    });
+}
+
+int dpq_kmeanspp_seed(const float* vectors, int64_t n, int D, int M, int K, uint64_t seed, int device, float* codewords_out,
+                      double* potential_out) {
+    return guarded([&]() -> int {
+    if (!vectors || !codewords_out) return fail(DPQ_ERR_ARG, "dpq_kmeanspp_seed: NULL argument");
+    int rc = train_check_shape("dpq_kmeanspp_seed", n, D, M, K);
+    if (rc) return rc;
+    if ((rc = train_select_device(device))) return rc;
+    std::string err;
+    dpq::Trainer trainer;
+    rc = trainer.open(vectors, n, D, M, K, (D + M - 1) / M, &err);
+    if (!rc) rc = trainer.seed_kmeanspp(seed, potential_out, nullptr, &err);
+    if (!rc) rc = trainer.get_codebook(codewords_out, &err);
+    return rc ? fail(rc, "dpq_kmeanspp_seed: " + err) : DPQ_OK;
+    });
+}
+
+int dpq_train_potential(const float* vectors, int64_t n, int D, const float* codewords, int M, int K, int Ds, int device,
+                        double* potential_out) {
+    return guarded([&]() -> int {
+    if (!vectors || !codewords || !potential_out) return fail(DPQ_ERR_ARG, "dpq_train_potential: NULL argument");
+    int rc = train_check_shape("dpq_train_potential", n, D, M, K);
+    if (rc) return rc;
+    if (Ds != (D + M - 1) / M) return fail(DPQ_ERR_ARG, "dpq_train_potential: Ds is not ceil(D / M)");
+    if ((rc = train_select_device(device))) return rc;
+    std::string err;
+    dpq::Trainer trainer;
+    rc = trainer.open(vectors, n, D, M, K, Ds, &err);
+    if (!rc) rc = trainer.set_codebook(codewords, &err);
+    if (!rc) rc = trainer.potential(potential_out, &err);
+    return rc ? fail(rc, "dpq_train_potential: " + err) : DPQ_OK;
     });
 }
 

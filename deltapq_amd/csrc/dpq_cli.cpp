@@ -58,11 +58,13 @@ static int read_filter(const std::string& path, std::vector<uint32_t>* words, in
 }
 
 int main(int argc, char* argv[]) {
-    std::string dataset, queryset, task = "approx_tree", ext = "fvecs", out_path, order = "dfs", filter_path;
+    std::string dataset, queryset, task = "approx_tree", ext = "fvecs", out_path, order = "dfs", filter_path, init = "rows";
     int query_size = -1, top_k = 1, diff_argument = 1, debug = 0, max_height_folds = 1, method = 1;
     int PQ_M = 0, PQ_K = 0, gpus = 1, gt_topk = -1, rerank = 0;
     bool topk_given = false;
     long long N = -1;
+    int restarts = 1;
+    unsigned long long seed = 0;
     for (int i = 0; i < argc; i++) {  // main:26-70: hand-rolled scan, no validation
         std::string arg = argv[i];
         const char* nx = i + 1 < argc ? argv[i + 1] : "";
@@ -85,6 +87,9 @@ int main(int argc, char* argv[]) {
         if (arg == "-gpus") gpus = atoi(nx);
         if (arg == "-out") out_path = nx;
         if (arg == "-order") order = nx;
+        if (arg == "-init") init = nx;
+        if (arg == "-restarts") restarts = atoi(nx);
+        if (arg == "-seed") seed = strtoull(nx, nullptr, 10);
     }
     (void)diff_argument; (void)method; (void)queryset;
 
@@ -92,8 +97,10 @@ int main(int argc, char* argv[]) {
         // The other binary's `pqtree -task learn` (main.cpp:243-277): learn.{ext} -> M{M}K{K}codewords.txt.  The
         // reference shuffles the file's vectors before it takes -N of them (main.cpp:262) and trains with cv::kmeans;
         // here -N takes the first N vectors as they are and dpq_train_codebook trains with its own stated rules.
-        if (PQ_M <= 0 || PQ_K <= 0 || dataset.empty()) {
-            std::cout << "usage: deltapq -dataset DIR -task learn -m M -k K [-N TRAIN_SIZE] [-ext fvecs|bvecs]" << std::endl;
+        // -init rows|pp: K random rows or k-means++; -restarts R: the best of R runs per sub-space; -seed S.
+        if (PQ_M <= 0 || PQ_K <= 0 || dataset.empty() || (init != "rows" && init != "pp")) {
+            std::cout << "usage: deltapq -dataset DIR -task learn -m M -k K [-N TRAIN_SIZE] [-ext fvecs|bvecs] [-init rows|pp] "
+                         "[-restarts R] [-seed S]" << std::endl;
             return 2;
         }
         const std::string learn_path = dataset + "/learn." + ext;  // main.cpp:251
@@ -109,7 +116,12 @@ int main(int argc, char* argv[]) {
         const int Ds = (D + PQ_M - 1) / PQ_M;
         std::vector<float> codewords((size_t)PQ_M * PQ_K * Ds);
         dpq_train_stats st;
-        rc = dpq_train_codebook(learn.data(), n, D, PQ_M, PQ_K, nullptr, codewords.data(), &st);
+        dpq_train_opts topts = {};
+        topts.max_iters = 25;
+        topts.seed = seed;
+        topts.init = init == "pp" ? 1 : 0;
+        topts.restarts = restarts;
+        rc = dpq_train_codebook(learn.data(), n, D, PQ_M, PQ_K, &topts, codewords.data(), &st);
         if (rc) return die("learn", rc);
         for (int r = 0; r < st.iters_run; ++r) std::cout << "round " << r + 1 << " distortion " << st.distortion[r] << std::endl;
         const std::string cw_path =

@@ -25,9 +25,29 @@ int train_padded_ds(int Ds);
 // 0 when train_padded_ds(Ds) is.
 size_t train_lds_bytes(int K, int Ds);
 
-// Runs on the current device.  codewords [M][K][Ds]: the start on entry, the trained codebook on return.
-// Returns a dpq_status; *err gets the detail.
-int train_codebook(const float* vectors, int64_t n, int D, int M, int K, int Ds, int max_iters, float* codewords,
-                   TrainStats* stats, std::string* err);
+// One training problem on the current device: the vectors as the split image sub[m][n][DsP] and every work array,
+// uploaded once and shared by the start, the Lloyd rounds, the potential and any number of restarts.  Every member
+// returns a dpq_status; *err gets the detail.  codewords are host arrays [M][K][Ds].
+class Trainer {
+public:
+    Trainer();
+    ~Trainer();
+    Trainer(const Trainer&) = delete;
+    Trainer& operator=(const Trainer&) = delete;
+
+    int open(const float* vectors, int64_t n, int D, int M, int K, int Ds, std::string* err);
+    int set_codebook(const float* codewords, std::string* err);
+    int get_codebook(float* codewords, std::string* err);
+    // The k-means++ start of `seed` into the device codebook.  potential: double [M] or NULL; ms: device time or NULL.
+    int seed_kmeanspp(uint64_t seed, double* potential, double* ms, std::string* err);
+    // Lloyd's rounds from the device codebook.  stats->wall_ms stays 0: the caller owns the whole call's clock.
+    int lloyd(int max_iters, TrainStats* stats, std::string* err);
+    // The leaf-ordered potential, double [M], of the device codebook: one more assignment, then the ordered sums.
+    int potential(double* out, std::string* err);
+
+private:
+    struct Impl;
+    Impl* p_;
+};
 
 }  // namespace dpq

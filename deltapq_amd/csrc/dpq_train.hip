@@ -2,8 +2,9 @@
 //
 // Replaces PQ::Learn (pq.cpp:112-157), which hands each sub-space to cv::kmeans.  NO REFERENCE SEMANTICS
 // (cv::kmeans): OpenCV's k-means++ start, its three restarts and the parallel shuffle before it
-// (main.cpp:262) are not reproducible, so this file defines Lloyd's algorithm with exact, stated arithmetic
-//  and tests/_kmeans_restatement.py restates it on the CPU bit for bit.
+// (main.cpp:262) are not reproducible, so this file defines Lloyd's algorithm, a k-means++ start and a restart
+// rule with exact, stated arithmetic; tests/_kmeans_restatement.py and
+// tests/_kmeanspp_restatement.py restate them on the CPU bit for bit.
 //
 // One round, all sub-spaces at once (a sub-space that has stopped is skipped by every kernel):
 //   train_assign_kernel   label + winning distance per (vector, sub-space), label histogram, changed count,
@@ -13,6 +14,9 @@
 //   hipcub radix sort     (sub-space, label) keys, stable: member lists in ascending vector index
 //   train_update_kernel   one thread per (sub-space, cluster, dimension): the ordered fp64 sum and the mean
 //   train_repair_kernel   one block per sub-space with empty clusters: top-E by (distance desc, index asc)
+// The start is the caller's codebook, K rows drawn on the host, or k-means++ per sub-space on the device
+// (train_pp_update_kernel + train_pp_choose_kernel per centre); train_leaf_sum_kernel and the choose kernel's
+// chain give the leaf-ordered potential by which restarts are compared.
 // The vectors stay on the device for the whole run as sub[m][n][DsP]: one sub-space's sub-vectors
 // contiguous and zero padded to the kernel's width, so that a thread's sub-vector is a few 16-byte loads.
 #include <hip/hip_runtime.h>
@@ -36,6 +40,8 @@ namespace {
 constexpr int kAssignThreads = 256;
 constexpr int kRepairThreads = 1024;
 constexpr int kMaxK = 256;  // one byte per label; counts / offsets rows are kMaxK wide
+constexpr int kLeaf = 256;  // vectors per leaf of the ordered sums: part of the contract (deltapq_amd.h)
+constexpr int kChunk = 1024;  // leaf sums train_pp_choose_kernel holds in LDS at a time
 
 struct RoundRec {  // what the host reads per round and sub-space
     int32_t changed, empty;
@@ -280,6 +286,224 @@ __global__ __launch_bounds__(kRepairThreads) void train_repair_kernel(const floa
     }
 }
 
+// ---- k-means++ start and the leaf-ordered potential (include/deltapq_amd.h) -----------------------
+// A leaf is kLeaf consecutive vectors.  Every sum here is ordered by contract: the leaf sum S_l is one lane's chain
+// of fp64 adds over the leaf's fp32 weights in ascending index, the running totals T_l are one lane's chain over
+// the leaves.  No floating point atomics.  One step of the seeding is train_pp_update_kernel followed by
+// train_pp_choose_kernel, all sub-spaces in each launch; the steps are queued back to back and the chosen index
+// never leaves the device.
+
+// Lane 0's ordered chain over a leaf's weights in LDS (16-byte aligned): the adds are one after the other by
+// contract, so the next eight values are read while the current eight are added.
+__device__ __forceinline__ double leaf_chain(const float* wl, int cnt) {
+    const float4* w4 = reinterpret_cast<const float4*>(wl);
+    const int groups = cnt >> 3;
+    double s = 0.0;
+    float4 a = {}, b = {};
+    if (groups) {
+        a = w4[0];
+        b = w4[1];
+    }
+    for (int g = 0; g < groups; ++g) {
+        float4 na = a, nb = b;
+        if (g + 1 < groups) {
+            na = w4[2 * g + 2];
+            nb = w4[2 * g + 3];
+        }
+        s = __dadd_rn(s, (double)a.x);
+        s = __dadd_rn(s, (double)a.y);
+        s = __dadd_rn(s, (double)a.z);
+        s = __dadd_rn(s, (double)a.w);
+        s = __dadd_rn(s, (double)b.x);
+        s = __dadd_rn(s, (double)b.y);
+        s = __dadd_rn(s, (double)b.z);
+        s = __dadd_rn(s, (double)b.w);
+        a = na;
+        b = nb;
+    }
+    for (int t = groups << 3; t < cnt; ++t) s = __dadd_rn(s, (double)wl[t]);
+    return s;
+}
+
+// grid = (leaves, M), step j: the distance of every sub-vector to centre j = sub-vector chosen[m][j] in
+// train_assign_kernel's arithmetic, w = (d < w ? d : w) (step 0: w = d), and the leaf's ordered fp64 sum.  The
+// leaf-0 block also files the centre in the codebook.  Dynamic LDS: DsP floats of centre, kLeaf floats of weights.
+__global__ __launch_bounds__(kLeaf) void train_pp_update_kernel(const float* __restrict__ sub, int64_t n, int K, int DsP,
+                                                                 int j, const int32_t* __restrict__ chosen,
+                                                                 float* __restrict__ w, double* __restrict__ S,
+                                                                 float* __restrict__ cb) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int Q = DsP / 4;
+    float4* c4 = reinterpret_cast<float4*>(smem);      // [Q]
+    float* wl = reinterpret_cast<float*>(c4 + Q);      // [kLeaf]
+    const int m = blockIdx.y, tid = threadIdx.x;
+    const int64_t leaf = blockIdx.x;
+    const int64_t c = chosen[m * K + j];
+    if (tid < Q) {
+        const float4 t = reinterpret_cast<const float4*>(sub + ((size_t)m * n + c) * DsP)[tid];
+        c4[tid] = t;
+        if (leaf == 0) reinterpret_cast<float4*>(cb + ((size_t)m * K + j) * DsP)[tid] = t;
+    }
+    __syncthreads();
+    const int64_t i = leaf * kLeaf + tid;
+    if (i < n) {
+        const float4* p = reinterpret_cast<const float4*>(sub + ((size_t)m * n + i) * DsP);
+        float d = 0.0f;
+        for (int q = 0; q < Q; ++q) {
+            const float4 x = p[q], y = c4[q];
+            float diff = __fsub_rn(x.x, y.x);
+            d = __fadd_rn(d, __fmul_rn(diff, diff));
+            diff = __fsub_rn(x.y, y.y);
+            d = __fadd_rn(d, __fmul_rn(diff, diff));
+            diff = __fsub_rn(x.z, y.z);
+            d = __fadd_rn(d, __fmul_rn(diff, diff));
+            diff = __fsub_rn(x.w, y.w);
+            d = __fadd_rn(d, __fmul_rn(diff, diff));
+        }
+        const size_t e = (size_t)m * n + i;
+        if (j > 0) {
+            const float old = w[e];
+            d = d < old ? d : old;
+        }
+        w[e] = d;
+        wl[tid] = d;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        const int cnt = (int)(n - leaf * kLeaf < kLeaf ? n - leaf * kLeaf : kLeaf);
+        S[(size_t)m * gridDim.x + leaf] = leaf_chain(wl, cnt);
+    }
+}
+
+// grid = (leaves, M): the ordered leaf sums of any weights [M][n] (the potential of a codebook sums the winning
+// distances train_assign_kernel left).
+__global__ __launch_bounds__(kLeaf) void train_leaf_sum_kernel(const float* __restrict__ w, int64_t n,
+                                                                double* __restrict__ S) {
+    __shared__ __attribute__((aligned(16))) float wl[kLeaf];
+    const int m = blockIdx.y, tid = threadIdx.x;
+    const int64_t leaf = blockIdx.x, i = leaf * kLeaf + tid;
+    if (i < n) wl[tid] = w[(size_t)m * n + i];
+    __syncthreads();
+    if (tid == 0) {
+        const int cnt = (int)(n - leaf * kLeaf < kLeaf ? n - leaf * kLeaf : kLeaf);
+        S[(size_t)m * gridDim.x + leaf] = leaf_chain(wl, cnt);
+    }
+}
+
+// One block per sub-space.  Lane 0 chains the running totals T over the leaf sums, kChunk leaves at a time through
+// LDS, and the block keeps them.  j < 0: the total is the potential, nothing else.  Otherwise centre j is drawn
+// with z = zs[m][j]: total == 0 takes the smallest index that is no centre yet; else r = u * total, the first leaf
+// with T_l > r (none: the last with S_l > 0), and in it the first i whose running sum exceeds r - T_{l-1} (none:
+// the last with w_i > 0).  The searches over the leaves are minima and maxima of indices, the same in any order.
+__global__ __launch_bounds__(kLeaf) void train_pp_choose_kernel(const float* __restrict__ w, int64_t n, int L, int K, int j,
+                                                                 const uint64_t* __restrict__ zs,
+                                                                 const double* __restrict__ S, double* __restrict__ T,
+                                                                 int32_t* __restrict__ chosen,
+                                                                 double* __restrict__ potential) {
+    __shared__ __attribute__((aligned(16))) double chunk[kChunk];
+    __shared__ float wl[kLeaf];
+    __shared__ int taken[kLeaf];
+    __shared__ double s_total;
+    __shared__ int s_first, s_last;
+    const int m = blockIdx.x, tid = threadIdx.x;
+    const double* Sm = S + (size_t)m * L;
+    double* Tm = T + (size_t)m * L;
+    double run = 0.0;  // lane 0's
+    for (int base = 0; base < L; base += kChunk) {
+        const int cnt = L - base < kChunk ? L - base : kChunk;
+        for (int i = tid; i < cnt; i += kLeaf) chunk[i] = Sm[base + i];
+        __syncthreads();
+        if (tid == 0) {
+            // T_0 = +0.0 + S_0 = S_0: a leaf sum is never -0.0.  Eight sums at a time, the next eight in flight.
+            double2* c2 = reinterpret_cast<double2*>(chunk);
+            const int groups = cnt >> 3;
+            double2 v[4] = {}, nv[4] = {};
+            if (groups)
+                for (int q = 0; q < 4; ++q) v[q] = c2[q];
+            for (int g = 0; g < groups; ++g) {
+                if (g + 1 < groups)
+                    for (int q = 0; q < 4; ++q) nv[q] = c2[4 * g + 4 + q];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    run = __dadd_rn(run, v[q].x);
+                    v[q].x = run;
+                    run = __dadd_rn(run, v[q].y);
+                    v[q].y = run;
+                    c2[4 * g + q] = v[q];
+                }
+#pragma unroll
+                for (int q = 0; q < 4; ++q) v[q] = nv[q];
+            }
+            for (int i = groups << 3; i < cnt; ++i) {
+                run = __dadd_rn(run, chunk[i]);
+                chunk[i] = run;
+            }
+        }
+        __syncthreads();
+        for (int i = tid; i < cnt; i += kLeaf) Tm[base + i] = chunk[i];
+        __syncthreads();
+    }
+    if (tid == 0) {
+        s_total = run;
+        s_first = 0x7fffffff;
+        s_last = -1;
+    }
+    taken[tid] = 0;
+    __syncthreads();  // also makes the block's own T stores visible to all of its lanes
+    const double total = s_total;
+    if (j < 0) {
+        if (tid == 0) potential[m] = total;
+        return;
+    }
+    int32_t* mine = chosen + m * K;
+    int leaf = -1;
+    double r = 0.0;
+    if (total != 0.0) {
+        const double u = __dmul_rn((double)(zs[m * K + j] >> 11), 0x1p-53);
+        r = __dmul_rn(u, total);
+        int first = 0x7fffffff, last = -1;
+        for (int l = tid; l < L; l += kLeaf) {
+            if (Tm[l] > r && l < first) first = l;
+            if (Sm[l] > 0.0) last = l;  // ascending l: the lane's largest
+        }
+        if (first != 0x7fffffff) atomicMin(&s_first, first);
+        if (last >= 0) atomicMax(&s_last, last);
+        __syncthreads();
+        leaf = s_first != 0x7fffffff ? s_first : s_last;  // total > 0: some S_l > 0
+    }
+    if (leaf < 0) {
+        // total == 0 (or a NaN total, which has no leaf either: the same rule keeps every index in range).
+        // j centres so far, so one of the indices 0 .. j is free (j < K <= n)
+        if (tid < j && mine[tid] >= 0 && mine[tid] <= j) taken[mine[tid]] = 1;
+        __syncthreads();
+        if (tid == 0) {
+            int pick = 0;
+            while (pick < j && taken[pick]) ++pick;
+            mine[j] = pick;
+        }
+        return;
+    }
+    const int64_t at = (int64_t)leaf * kLeaf;
+    const int cnt = (int)(n - at < kLeaf ? n - at : kLeaf);
+    if (tid < cnt) wl[tid] = w[(size_t)m * n + at + tid];
+    __syncthreads();
+    if (tid == 0) {
+        const double rp = __dsub_rn(r, leaf ? Tm[leaf - 1] : 0.0);
+        double t = 0.0;
+        int pick = -1, positive = -1;
+        for (int i = 0; i < cnt; ++i) {
+            t = __dadd_rn(t, (double)wl[i]);
+            if (wl[i] > 0.0f) positive = i;
+            if (t > rp) {
+                pick = i;
+                break;
+            }
+        }
+        if (pick < 0) pick = positive >= 0 ? positive : 0;  // S_leaf > 0: a positive weight exists
+        mine[j] = (int32_t)(at + pick);
+    }
+}
+
 // hipFuncSetAttribute is per device
 hipError_t ensure_lds(const void* fn, std::atomic<bool>* done) {
     int dev = 0;
@@ -377,64 +601,180 @@ size_t train_lds_bytes(int K, int Ds) {
         }                                                                              \
     } while (0)
 
-int train_codebook(const float* vectors, int64_t n, int D, int M, int K, int Ds, int max_iters, float* codewords,
-                   TrainStats* st, std::string* err) {
-    const auto wall0 = std::chrono::steady_clock::now();
-    const int DsP = train_padded_ds(Ds);
-    const size_t lds = train_lds_bytes(K, Ds);
-    const int64_t total = n * M;
-    const int V = assign_vectors_per_thread(DsP);
-    const int n_blocks = (int)((n + kAssignThreads * V - 1) / (kAssignThreads * V));
-
-    Dev<float> d_sub, d_tile, d_cb, d_dist;
+struct Trainer::Impl {
+    int64_t n = 0, total = 0;
+    int D = 0, M = 0, K = 0, Ds = 0, DsP = 0, V = 0, n_blocks = 0, n_leaves = 0, key_bits = 8;
+    size_t lds = 0, temp_bytes = 0;
+    Dev<float> d_sub, d_cb, d_dist;
     Dev<uint16_t> d_keys, d_keys_sorted;
     Dev<uint32_t> d_iota, d_members, d_counts, d_changed, d_offsets;
-    Dev<int32_t> d_active;
-    Dev<double> d_partial;
+    Dev<int32_t> d_active, d_chosen;
+    Dev<double> d_partial, d_leaf_sums, d_leaf_totals, d_potential;
+    Dev<uint64_t> d_zs;
     Dev<RoundRec> d_rec;
     Dev<unsigned char> d_temp;
+
+    AssignArgs assign_args() const {
+        return {d_sub, n, d_cb, M, K, d_active, d_keys, d_dist, d_counts, d_changed, d_partial};
+    }
+    int activate_all(std::string* err) {
+        std::vector<int32_t> act((size_t)M, 1);
+        TR_HIP(hipMemcpy(d_active, act.data(), act.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        return DPQ_OK;
+    }
+};
+
+Trainer::Trainer() : p_(new Impl) {}
+Trainer::~Trainer() { delete p_; }
+
+int Trainer::open(const float* vectors, int64_t n, int D, int M, int K, int Ds, std::string* err) {
+    Impl& s = *p_;
+    s.n = n, s.D = D, s.M = M, s.K = K, s.Ds = Ds;
+    s.DsP = train_padded_ds(Ds);
+    s.lds = train_lds_bytes(K, Ds);
+    s.total = n * M;
+    s.V = assign_vectors_per_thread(s.DsP);
+    s.n_blocks = (int)((n + kAssignThreads * s.V - 1) / (kAssignThreads * s.V));
+    s.n_leaves = (int)((n + kLeaf - 1) / kLeaf);
+    const int64_t total = s.total;
+    const int DsP = s.DsP;
+
+    Dev<float> d_tile;
     const int64_t tile = std::min<int64_t>(n, 1 << 18);  // vectors per upload
-    TR_HIP(d_sub.alloc((size_t)total * DsP));
+    TR_HIP(s.d_sub.alloc((size_t)total * DsP));
     TR_HIP(d_tile.alloc((size_t)tile * D));
-    TR_HIP(d_cb.alloc((size_t)M * K * DsP));
-    TR_HIP(d_dist.alloc((size_t)total));
-    TR_HIP(d_keys.alloc((size_t)total));
-    TR_HIP(d_keys_sorted.alloc((size_t)total));
-    TR_HIP(d_iota.alloc((size_t)total));
-    TR_HIP(d_members.alloc((size_t)total));
-    TR_HIP(d_counts.alloc((size_t)M * kMaxK));
-    TR_HIP(d_changed.alloc((size_t)M));
-    TR_HIP(d_offsets.alloc((size_t)M * kMaxK));
-    TR_HIP(d_active.alloc((size_t)M));
-    TR_HIP(d_partial.alloc((size_t)M * n_blocks));
-    TR_HIP(d_rec.alloc((size_t)M));
-    int key_bits = 8;
-    while ((1 << key_bits) < M * 256) ++key_bits;
-    size_t temp_bytes = 0;
-    TR_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, temp_bytes, d_keys.p, d_keys_sorted.p, d_iota.p, d_members.p,
-                                              (int)total, 0, key_bits, nullptr));
-    TR_HIP(d_temp.alloc(temp_bytes));
+    TR_HIP(s.d_cb.alloc((size_t)M * K * DsP));
+    TR_HIP(s.d_dist.alloc((size_t)total));
+    TR_HIP(s.d_keys.alloc((size_t)total));
+    TR_HIP(s.d_keys_sorted.alloc((size_t)total));
+    TR_HIP(s.d_iota.alloc((size_t)total));
+    TR_HIP(s.d_members.alloc((size_t)total));
+    TR_HIP(s.d_counts.alloc((size_t)M * kMaxK));
+    TR_HIP(s.d_changed.alloc((size_t)M));
+    TR_HIP(s.d_offsets.alloc((size_t)M * kMaxK));
+    TR_HIP(s.d_active.alloc((size_t)M));
+    TR_HIP(s.d_partial.alloc((size_t)M * s.n_blocks));
+    TR_HIP(s.d_rec.alloc((size_t)M));
+    TR_HIP(s.d_leaf_sums.alloc((size_t)M * s.n_leaves));
+    TR_HIP(s.d_leaf_totals.alloc((size_t)M * s.n_leaves));
+    TR_HIP(s.d_potential.alloc((size_t)M));
+    TR_HIP(s.d_chosen.alloc((size_t)M * K));
+    TR_HIP(s.d_zs.alloc((size_t)M * K));
+    while ((1 << s.key_bits) < M * 256) ++s.key_bits;
+    TR_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, s.temp_bytes, s.d_keys.p, s.d_keys_sorted.p, s.d_iota.p,
+                                              s.d_members.p, (int)total, 0, s.key_bits, nullptr));
+    TR_HIP(s.d_temp.alloc(s.temp_bytes));
 
     for (int64_t base = 0; base < n; base += tile) {
         const int64_t cnt = std::min(tile, n - base);
         TR_HIP(hipMemcpy(d_tile, vectors + (size_t)base * D, (size_t)cnt * D * sizeof(float), hipMemcpyHostToDevice));
         const int64_t work = cnt * M * DsP;
         hipLaunchKernelGGL(train_split_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, nullptr, d_tile.p, base,
-                           cnt, n, D, M, Ds, DsP, d_sub.p);
+                           cnt, n, D, M, Ds, DsP, s.d_sub.p);
         TR_HIP(hipGetLastError());
     }
-    hipLaunchKernelGGL(train_iota_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, nullptr, d_iota.p, n, total);
+    hipLaunchKernelGGL(train_iota_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, nullptr, s.d_iota.p, n, total);
     TR_HIP(hipGetLastError());
-    {
-        std::vector<float> cbp((size_t)M * K * DsP, 0.0f);
-        for (size_t r = 0; r < (size_t)M * K; ++r)
-            for (int d = 0; d < Ds; ++d) cbp[r * DsP + d] = codewords[r * Ds + d];
-        TR_HIP(hipMemcpy(d_cb, cbp.data(), cbp.size() * sizeof(float), hipMemcpyHostToDevice));
-        std::vector<int32_t> act((size_t)M, 1);
-        TR_HIP(hipMemcpy(d_active, act.data(), act.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    TR_HIP(hipDeviceSynchronize());  // d_tile goes out of scope
+    return DPQ_OK;
+}
+
+int Trainer::set_codebook(const float* codewords, std::string* err) {
+    Impl& s = *p_;
+    std::vector<float> cbp((size_t)s.M * s.K * s.DsP, 0.0f);
+    for (size_t r = 0; r < (size_t)s.M * s.K; ++r)
+        for (int d = 0; d < s.Ds; ++d) cbp[r * s.DsP + d] = codewords[r * s.Ds + d];
+    TR_HIP(hipMemcpy(s.d_cb, cbp.data(), cbp.size() * sizeof(float), hipMemcpyHostToDevice));
+    return DPQ_OK;
+}
+
+int Trainer::get_codebook(float* codewords, std::string* err) {
+    Impl& s = *p_;
+    std::vector<float> cbp((size_t)s.M * s.K * s.DsP);
+    TR_HIP(hipMemcpy(cbp.data(), s.d_cb, cbp.size() * sizeof(float), hipMemcpyDeviceToHost));
+    for (size_t r = 0; r < (size_t)s.M * s.K; ++r)
+        for (int d = 0; d < s.Ds; ++d) codewords[r * s.Ds + d] = cbp[r * s.DsP + d];
+    return DPQ_OK;
+}
+
+int Trainer::seed_kmeanspp(uint64_t seed, double* potential, double* ms, std::string* err) {
+    Impl& s = *p_;
+    const int M = s.M, K = s.K;
+    // every draw of every sub-space, from the host: s = seed + m * 0xD6E8FEB86659FD93, splitmix64 from there
+    std::vector<uint64_t> zs((size_t)M * K);
+    std::vector<int32_t> chosen((size_t)M * K, 0);
+    for (int m = 0; m < M; ++m) {
+        uint64_t st = seed + (uint64_t)m * 0xD6E8FEB86659FD93ull;
+        for (int j = 0; j < K; ++j) {
+            st += 0x9E3779B97F4A7C15ull;
+            uint64_t z = st;
+            z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+            z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+            z ^= z >> 31;
+            zs[(size_t)m * K + j] = z;
+        }
+        chosen[(size_t)m * K] = (int32_t)(zs[(size_t)m * K] % (uint64_t)s.n);  // centre 0
     }
-    TR_HIP(hipMemset(d_keys, 0xff, (size_t)total * sizeof(uint16_t)));
-    TR_HIP(hipMemset(d_rec, 0, (size_t)M * sizeof(RoundRec)));
+    TR_HIP(hipMemcpy(s.d_zs, zs.data(), zs.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+    TR_HIP(hipMemcpy(s.d_chosen, chosen.data(), chosen.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    Events events;
+    events.ev.resize(2);
+    for (hipEvent_t& e : events.ev) TR_HIP(hipEventCreate(&e));
+    TR_HIP(hipEventRecord(events.ev[0], nullptr));
+    const dim3 leaves((unsigned)s.n_leaves, (unsigned)M);
+    const size_t lds = (size_t)s.DsP * sizeof(float) + kLeaf * sizeof(float);
+    for (int j = 0; j < K; ++j) {
+        if (j > 0) {
+            hipLaunchKernelGGL(train_pp_choose_kernel, dim3((unsigned)M), dim3(kLeaf), 0, nullptr, s.d_dist.p, s.n, s.n_leaves,
+                               K, j, s.d_zs.p, s.d_leaf_sums.p, s.d_leaf_totals.p, s.d_chosen.p, s.d_potential.p);
+            TR_HIP(hipGetLastError());
+        }
+        hipLaunchKernelGGL(train_pp_update_kernel, leaves, dim3(kLeaf), lds, nullptr, s.d_sub.p, s.n, K, s.DsP, j,
+                           s.d_chosen.p, s.d_dist.p, s.d_leaf_sums.p, s.d_cb.p);
+        TR_HIP(hipGetLastError());
+    }
+    if (potential) {
+        hipLaunchKernelGGL(train_pp_choose_kernel, dim3((unsigned)M), dim3(kLeaf), 0, nullptr, s.d_dist.p, s.n, s.n_leaves, K,
+                           -1, s.d_zs.p, s.d_leaf_sums.p, s.d_leaf_totals.p, s.d_chosen.p, s.d_potential.p);
+        TR_HIP(hipGetLastError());
+    }
+    TR_HIP(hipEventRecord(events.ev[1], nullptr));
+    TR_HIP(hipDeviceSynchronize());
+    if (potential) TR_HIP(hipMemcpy(potential, s.d_potential, (size_t)M * sizeof(double), hipMemcpyDeviceToHost));
+    if (ms) {
+        float f = 0.f;
+        TR_HIP(hipEventElapsedTime(&f, events.ev[0], events.ev[1]));
+        *ms = f;
+    }
+    return DPQ_OK;
+}
+
+int Trainer::potential(double* out, std::string* err) {
+    Impl& s = *p_;
+    const int M = s.M;
+    int rc = s.activate_all(err);
+    if (rc) return rc;
+    TR_HIP(hipMemsetAsync(s.d_counts, 0, (size_t)M * kMaxK * sizeof(uint32_t), nullptr));
+    TR_HIP(hipMemsetAsync(s.d_changed, 0, (size_t)M * sizeof(uint32_t), nullptr));
+    TR_HIP(launch_assign(s.assign_args(), s.DsP, s.lds));
+    hipLaunchKernelGGL(train_leaf_sum_kernel, dim3((unsigned)s.n_leaves, (unsigned)M), dim3(kLeaf), 0, nullptr, s.d_dist.p,
+                       s.n, s.d_leaf_sums.p);
+    TR_HIP(hipGetLastError());
+    hipLaunchKernelGGL(train_pp_choose_kernel, dim3((unsigned)M), dim3(kLeaf), 0, nullptr, s.d_dist.p, s.n, s.n_leaves, s.K, -1,
+                       s.d_zs.p, s.d_leaf_sums.p, s.d_leaf_totals.p, s.d_chosen.p, s.d_potential.p);
+    TR_HIP(hipGetLastError());
+    TR_HIP(hipMemcpy(out, s.d_potential, (size_t)M * sizeof(double), hipMemcpyDeviceToHost));
+    return DPQ_OK;
+}
+
+int Trainer::lloyd(int max_iters, TrainStats* st, std::string* err) {
+    Impl& s = *p_;
+    const int64_t n = s.n, total = s.total;
+    const int M = s.M, K = s.K, DsP = s.DsP, n_blocks = s.n_blocks;
+    int rc = s.activate_all(err);
+    if (rc) return rc;
+    TR_HIP(hipMemset(s.d_keys, 0xff, (size_t)total * sizeof(uint16_t)));
+    TR_HIP(hipMemset(s.d_rec, 0, (size_t)M * sizeof(RoundRec)));
 
     Events events;
     events.ev.resize((size_t)max_iters * 5);
@@ -442,21 +782,21 @@ int train_codebook(const float* vectors, int64_t n, int D, int M, int K, int Ds,
     std::vector<int> ran((size_t)max_iters, 0);  // 1: assignment only, 2: the update ran, 3: the repair too
     std::vector<RoundRec> rec((size_t)M);
     std::vector<char> active((size_t)M, 1);
-    const AssignArgs aa = {d_sub, n, d_cb, M, K, d_active, d_keys, d_dist, d_counts, d_changed, d_partial};
+    const AssignArgs aa = s.assign_args();
     *st = TrainStats();
     TR_HIP(hipDeviceSynchronize());
     const auto rounds0 = std::chrono::steady_clock::now();
     for (int r = 0; r < max_iters; ++r) {
         hipEvent_t* ev = &events.ev[(size_t)r * 5];
         TR_HIP(hipEventRecord(ev[0], nullptr));
-        TR_HIP(hipMemsetAsync(d_counts, 0, (size_t)M * kMaxK * sizeof(uint32_t), nullptr));
-        TR_HIP(hipMemsetAsync(d_changed, 0, (size_t)M * sizeof(uint32_t), nullptr));
-        TR_HIP(launch_assign(aa, DsP, lds));
-        hipLaunchKernelGGL(train_stats_kernel, dim3((unsigned)M), dim3(kMaxK), 0, nullptr, n, K, n_blocks, r, d_active.p,
-                           d_counts.p, d_changed.p, d_partial.p, d_offsets.p, d_rec.p);
+        TR_HIP(hipMemsetAsync(s.d_counts, 0, (size_t)M * kMaxK * sizeof(uint32_t), nullptr));
+        TR_HIP(hipMemsetAsync(s.d_changed, 0, (size_t)M * sizeof(uint32_t), nullptr));
+        TR_HIP(launch_assign(aa, DsP, s.lds));
+        hipLaunchKernelGGL(train_stats_kernel, dim3((unsigned)M), dim3(kMaxK), 0, nullptr, n, K, n_blocks, r, s.d_active.p,
+                           s.d_counts.p, s.d_changed.p, s.d_partial.p, s.d_offsets.p, s.d_rec.p);
         TR_HIP(hipGetLastError());
         TR_HIP(hipEventRecord(ev[1], nullptr));
-        TR_HIP(hipMemcpy(rec.data(), d_rec, (size_t)M * sizeof(RoundRec), hipMemcpyDeviceToHost));  // the round's only sync
+        TR_HIP(hipMemcpy(rec.data(), s.d_rec, (size_t)M * sizeof(RoundRec), hipMemcpyDeviceToHost));  // the round's only sync
         st->iters_run = r + 1;
         ran[(size_t)r] = 1;
         double distortion = 0.0;
@@ -478,17 +818,17 @@ int train_codebook(const float* vectors, int64_t n, int D, int M, int K, int Ds,
             break;
         }
         TR_HIP(hipEventRecord(ev[2], nullptr));  // between ev[1] and ev[2] the device waits for the host
-        TR_HIP(hipcub::DeviceRadixSort::SortPairs(d_temp.p, temp_bytes, d_keys.p, d_keys_sorted.p, d_iota.p, d_members.p,
-                                                  (int)total, 0, key_bits, nullptr));
+        TR_HIP(hipcub::DeviceRadixSort::SortPairs(s.d_temp.p, s.temp_bytes, s.d_keys.p, s.d_keys_sorted.p, s.d_iota.p,
+                                                  s.d_members.p, (int)total, 0, s.key_bits, nullptr));
         const int64_t chains = (int64_t)M * K * DsP;
-        hipLaunchKernelGGL(train_update_kernel, dim3((unsigned)((chains + 255) / 256)), dim3(256), 0, nullptr, d_sub.p, n, M,
-                           K, DsP, d_active.p, d_counts.p, d_offsets.p, d_members.p, d_cb.p);
+        hipLaunchKernelGGL(train_update_kernel, dim3((unsigned)((chains + 255) / 256)), dim3(256), 0, nullptr, s.d_sub.p, n, M,
+                           K, DsP, s.d_active.p, s.d_counts.p, s.d_offsets.p, s.d_members.p, s.d_cb.p);
         TR_HIP(hipGetLastError());
         TR_HIP(hipEventRecord(ev[3], nullptr));
         ran[(size_t)r] = 2;
         if (n_empty > 0) {
-            hipLaunchKernelGGL(train_repair_kernel, dim3((unsigned)M), dim3(kRepairThreads), 0, nullptr, d_sub.p, n, K, DsP,
-                               d_active.p, d_counts.p, d_dist.p, d_cb.p);
+            hipLaunchKernelGGL(train_repair_kernel, dim3((unsigned)M), dim3(kRepairThreads), 0, nullptr, s.d_sub.p, n, K, DsP,
+                               s.d_active.p, s.d_counts.p, s.d_dist.p, s.d_cb.p);
             TR_HIP(hipGetLastError());
             TR_HIP(hipEventRecord(ev[4], nullptr));
             ran[(size_t)r] = 3;
@@ -497,12 +837,6 @@ int train_codebook(const float* vectors, int64_t n, int D, int M, int K, int Ds,
     }
     TR_HIP(hipDeviceSynchronize());
     st->rounds_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - rounds0).count();
-    {
-        std::vector<float> cbp((size_t)M * K * DsP);
-        TR_HIP(hipMemcpy(cbp.data(), d_cb, cbp.size() * sizeof(float), hipMemcpyDeviceToHost));
-        for (size_t r = 0; r < (size_t)M * K; ++r)
-            for (int d = 0; d < Ds; ++d) codewords[r * Ds + d] = cbp[r * DsP + d];
-    }
     for (int r = 0; r < st->iters_run; ++r) {
         hipEvent_t* ev = &events.ev[(size_t)r * 5];
         float ms = 0.f;
@@ -518,7 +852,6 @@ int train_codebook(const float* vectors, int64_t n, int D, int M, int K, int Ds,
         }
     }
     st->gpu_ms = st->assign_ms + st->update_ms + st->repair_ms;
-    st->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
     return DPQ_OK;
 }
 

@@ -28,7 +28,7 @@
  *     ascending (h:2977-2982)                     dists[nq][top_k] float, ascending
  *   decoder[256] argument (main:312-325)        gone (popcount / byte permute on GPU)
  *   PQ::ReadCodewords (pq.cpp:288-312)          dpq_read_codewords
- *   PQ::Learn (pq.cpp:112-157, cv::kmeans)      dpq_train_codebook (own semantics)
+ *   PQ::Learn (pq.cpp:112-157, cv::kmeans)      dpq_train_codebook (own semantics; k-means++ start and restarts too)
  *   PQ::WriteCodewords (pq.cpp:267-286)         dpq_write_codewords
  *   ReadTopN(query.{fvecs,bvecs})               dpq_read_vecs
  *     (utils.cpp:14-110)
@@ -289,10 +289,29 @@ int dpq_encode_pq(const float* vectors, int64_t n, int D, const float* codewords
  * (main.cpp:262), which cannot be reproduced; the rules below are this build's own, restated on the CPU in
  * tests/_kmeans_restatement.py and met by the GPU bit for bit.  Each sub-space is trained on its own; short vectors
  * are zero padded as dpq_encode_pq pads them (pq.cpp:114-123).
- *   Start   use_initial != 0: the caller's codewords.  Otherwise K rows drawn without replacement on the host, the
- *           same rows for every sub-space: p = 0 .. n-1, s = seed; for i = 0 .. K-1: s += 0x9E3779B97F4A7C15,
+ *   Start   use_initial != 0: the caller's codewords.  Otherwise, init == 0: K rows drawn without replacement on the
+ *           host, the same rows for every sub-space: p = 0 .. n-1, s = seed; for i = 0 .. K-1: s += 0x9E3779B97F4A7C15,
  *           z = s, z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9, z = (z ^ z >> 27) * 0x94D049BB133111EB, z ^= z >> 31
  *           (splitmix64, mod 2^64), j = i + z % (n - i), swap p[i], p[j]; codeword i = vector p[i].
+ *           init == 1: k-means++ on the GPU, every sub-space m on its own (what dpq_kmeanspp_seed returns).  RNG state
+ *           s = seed + m * 0xD6E8FEB86659FD93 (mod 2^64); next(): s += 0x9E3779B97F4A7C15, then the finaliser above
+ *           gives z.  Centre 0 is sub-vector next() % n, and w_i is the Assign distance of sub-vector i to it.  Then for
+ *           j = 1 .. K-1, with z = next():
+ *             leaves   a leaf is 256 consecutive vectors (the last may be short); S_l is the fp64 sum, from +0.0, of
+ *                      (double)w_i in ascending i, one add after the other; T_0 = S_0, T_l = T_{l-1} + S_l, one fp64
+ *                      add after the other; total is the last T.
+ *             total == 0   the smallest index that is not yet a centre of this sub-space is chosen.
+ *             otherwise    u = (double)(z >> 11) * 2^-53, r = u * total (one fp64 multiply); the leaf is the first l
+ *                      with T_l > r, or, if there is none, the last l with S_l > 0; r' = r - (l ? T_{l-1} : 0.0); walk
+ *                      the leaf in ascending i with t = +0.0, t += (double)w_i: the first i with t > r' is chosen,
+ *                      or, if there is none, the leaf's last i with w_i > 0.
+ *             update   centre j is sub-vector i; then every w_i = (d < w_i ? d : w_i), d the Assign distance to it.
+ *   Potential  of a sub-space for given weights: `total` by the leaf rule above.  The seeding's potential is that of
+ *           its final w; a codebook's (dpq_train_potential) that of the winning distances of one Assign.
+ *   Restarts  restarts R > 1: run r = 0 .. R-1 is a complete, independent run (start and rounds) with seed + r
+ *           (mod 2^64).  Every sub-space on its own keeps the run whose FINAL codebook has the lowest potential, a
+ *           tie going to the lowest r.  Stats: the millisecond fields and `reseeded` sum over the runs, iters_run is
+ *           the largest, converged is 1 only if every run converged, distortion[] is run 0's trace.
  *   Assign  dpq_encode_pq's arithmetic: per codeword `diff = v - c; dist += diff * diff` in fp32, subtract, multiply
  *           and add rounded separately, dimensions in order, strict `<` (the lowest k wins a tie).  The labels of a
  *           round are dpq_encode_pq(vectors, the codebook entering that round).
@@ -308,14 +327,17 @@ int dpq_encode_pq(const float* vectors, int64_t n, int D, const float* codewords
  *           sub-space contributes its last assignment's); the order of that sum is not part of the contract.
  * The same input gives the same bytes, run to run.  opts == NULL: device 0, 25 rounds, seed 0.  DPQ_ERR_ARG, before
  * any device call: a NULL pointer, D < 1, M < 1 or > 256, K outside 2..256, K > n, n * M >= 2^31, max_iters
- * outside 1..64, a sub-space whose codewords need more than 160 KB of LDS (Ds > 160, or K * Ds close to 40960).
+ * outside 1..64, init outside 0..1, restarts outside 0..16, init == 1 together with use_initial != 0, a sub-space
+ * whose codewords need more than 160 KB of LDS (Ds > 160, or K * Ds close to 40960).
  * Without a GPU: DPQ_ERR_NO_DEVICE.  Device memory: about 4 * n * M * (Ds rounded up to 4..160) + 16 * n * M bytes. */
 typedef struct dpq_train_opts {
     int32_t device;
     int32_t max_iters;   /* 1..64 */
     uint64_t seed;       /* of the seeded start */
     int32_t use_initial; /* != 0: `codewords` holds the start on entry */
-    int32_t reserved[3]; /* 0 */
+    int32_t init;        /* the start without use_initial: 0 random rows, 1 k-means++ */
+    int32_t restarts;    /* 0..16 runs, the best per sub-space kept; 0 and 1: one run */
+    int32_t reserved[1]; /* 0 */
 } dpq_train_opts;
 
 typedef struct dpq_train_stats {
@@ -332,6 +354,15 @@ typedef struct dpq_train_stats {
 /* codewords: float [M][K][Ds], in (use_initial) and out.  stats may be NULL. */
 int dpq_train_codebook(const float* vectors, int64_t n, int D, int M, int K, const dpq_train_opts* opts, float* codewords,
                        dpq_train_stats* stats);
+/* The k-means++ start alone (Start, init == 1): codewords_out float [M][K][Ds], Ds = ceil(D / M); potential_out
+ * double [M], the potential of the final weights, may be NULL.  dpq_train_codebook with init = 1 equals
+ * dpq_train_codebook with use_initial = 1 on this output, byte for byte.  Argument checks as dpq_train_codebook's. */
+int dpq_kmeanspp_seed(const float* vectors, int64_t n, int D, int M, int K, uint64_t seed, int device, float* codewords_out,
+                      double* potential_out);
+/* The leaf-ordered potential (Potential above) of any codebook [M][K][Ds], Ds = ceil(D / M): potential_out double [M].
+ * The restart rule compares runs by it; the same inputs give the same bits.  Argument checks as dpq_train_codebook's. */
+int dpq_train_potential(const float* vectors, int64_t n, int D, const float* codewords, int M, int K, int Ds, int device,
+                        double* potential_out);
 /* PQ::WriteCodewords' text format (pq.cpp:267-286) with nine significant digits, so that dpq_read_codewords and the
  * reference's `ifs >> float` (pq.cpp:288-312) read back the same bits; the reference's own default precision (six
  * digits) loses them. */
