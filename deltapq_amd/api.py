@@ -1069,14 +1069,29 @@ def merge_topk_host(ids, dists):
     return oi, od
 
 
-def merge_topk_torch(ids, dists):
-    """Device merge after an all-gather: ids/dists [n_lists][nq][k] cuda tensors."""
+def _merge_out(out, nq, k, device):
+    """The [nq][k] int32 / float32 result tensors of a device merge: fresh ones, or the caller's `out` pair."""
+    import torch
+    if out is None:
+        return (torch.empty((nq, k), dtype=torch.int32, device=device),
+                torch.empty((nq, k), dtype=torch.float32, device=device))
+    oi, od = out
+    assert oi.shape == (nq, k) and od.shape == (nq, k) and oi.dtype == torch.int32 and od.dtype == torch.float32
+    assert oi.device == device and od.device == device and oi.is_contiguous() and od.is_contiguous()
+    return oi, od
+
+
+def merge_topk_torch(ids, dists, out=None):
+    """Device merge after an all-gather: ids/dists [n_lists][nq][k] cuda tensors.  Every list ascending by (distance
+    bits, id) with its padding rows (id < 0) last; repeated keys are kept (include/deltapq_amd.h).  `out`: an
+    (ids, dists) pair of [nq][k] tensors to write into."""
     import torch
     lib = _lib.load()
     assert ids.is_cuda and ids.is_contiguous() and dists.is_contiguous()
     n_lists, nq, k = ids.shape
-    oi = torch.empty((nq, k), dtype=torch.int32, device=ids.device)
-    od = torch.empty((nq, k), dtype=torch.float32, device=ids.device)
+    oi, od = _merge_out(out, nq, k, ids.device)
+    if nq == 0:
+        return oi, od       # an empty tensor has no address to pass
     stream = torch.cuda.current_stream(ids.device).cuda_stream
     check(lib.dpq_merge_topk_device(ctypes.c_void_p(ids.data_ptr()), ctypes.c_void_p(dists.data_ptr()), n_lists, nq,
                                     k, ctypes.c_void_p(oi.data_ptr()), ctypes.c_void_p(od.data_ptr()),
@@ -1084,14 +1099,16 @@ def merge_topk_torch(ids, dists):
     return oi, od
 
 
-def merge_topk_packed_torch(gathered, k):
-    """Device merge straight from the all-gathered tensor [n_lists][nq][2k] int32 (ids | distance bits)."""
+def merge_topk_packed_torch(gathered, k, out=None):
+    """Device merge straight from the all-gathered tensor [n_lists][nq][2k] int32 (ids | distance bits); the contract
+    and `out` of merge_topk_torch."""
     import torch
     lib = _lib.load()
     assert gathered.is_cuda and gathered.is_contiguous() and gathered.dtype == torch.int32 and gathered.shape[2] == 2 * k
     n_lists, nq = gathered.shape[0], gathered.shape[1]
-    oi = torch.empty((nq, k), dtype=torch.int32, device=gathered.device)
-    od = torch.empty((nq, k), dtype=torch.float32, device=gathered.device)
+    oi, od = _merge_out(out, nq, k, gathered.device)
+    if nq == 0:
+        return oi, od
     stream = torch.cuda.current_stream(gathered.device).cuda_stream
     check(lib.dpq_merge_topk_device_packed(ctypes.c_void_p(gathered.data_ptr()), n_lists, nq, k, ctypes.c_void_p(oi.data_ptr()),
                                            ctypes.c_void_p(od.data_ptr()), gathered.device.index or 0, ctypes.c_void_p(stream)),

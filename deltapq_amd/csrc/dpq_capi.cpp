@@ -4008,6 +4008,7 @@ int dpq_merge_topk_device(const int32_t* d_ids, const float* d_dists, int n_list
     if (!d_ids || !d_dists || !d_out_ids || !d_out_dists || n_lists < 1 || nq < 0 || top_k < 1)
         return fail(DPQ_ERR_ARG, "bad merge argument");
     if ((int64_t)n_lists * top_k > 16384) return fail(DPQ_ERR_ARG, "n_lists * top_k exceeds 16384");
+    if (nq == 0) return DPQ_OK;  // nothing to merge: no device is touched
     DPQ_HIP(hipSetDevice(device));
     DPQ_HIP(dpq::launch_merge(d_ids, d_dists, n_lists, nq, top_k, top_k, d_out_ids, d_out_dists,
                               reinterpret_cast<hipStream_t>(hip_stream)));
@@ -4021,6 +4022,7 @@ int dpq_merge_topk_device_packed(const int32_t* d_packed, int n_lists, int nq, i
     if (!d_packed || !d_out_ids || !d_out_dists || n_lists < 1 || nq < 0 || top_k < 1)
         return fail(DPQ_ERR_ARG, "bad merge argument");
     if ((int64_t)n_lists * top_k > 16384) return fail(DPQ_ERR_ARG, "n_lists * top_k exceeds 16384");
+    if (nq == 0) return DPQ_OK;  // nothing to merge: no device is touched
     DPQ_HIP(hipSetDevice(device));
     DPQ_HIP(dpq::launch_merge(d_packed, reinterpret_cast<const float*>(d_packed + top_k), n_lists, nq, top_k, 2 * top_k,
                               d_out_ids, d_out_dists, reinterpret_cast<hipStream_t>(hip_stream)));

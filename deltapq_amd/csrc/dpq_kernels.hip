@@ -3074,9 +3074,16 @@ hipError_t launch_bootstrap(const BootArgs& a, int M, int n_slots, hipStream_t s
 
 // ---------------------------------------------------------------------------
 // 8e: merge of n_lists partial top-k lists per query.  grid = nq.
-// Every partial list arrives sorted (ascending (distance bits, id) keys, padding rows last) and the lists are
-// disjoint (shards), so a key's place in the merged list is the number of smaller keys: its position in its own
-// list plus, per other list, a binary search.  One barrier; a bitonic sort of n_lists * k keys took 55 of them.
+// Contract: every partial list arrives sorted, ascending by (distance bits, id) with its padding rows (id < 0, any
+// distance) last; an unsorted list is a precondition violation here (dpq_merge_topk_host sorts and tolerates it).
+// The merge is a stable multiway merge: a key's place is its position in its own list plus, per earlier list, the
+// number of keys <= it (upper bound) and, per later list, the number of keys < it (lower bound).  Ranks are unique
+// for any sorted input, so a key that occurs in two lists (a prefix handle and the whole index, a rank gathered
+// twice, replica answers) or twice in one list is KEPT as often as it occurs, as the host's sort of the
+// concatenation keeps it; nothing is deduplicated.  (Counting strictly smaller keys in every other list gave both
+// copies one rank: a row lost and a padding row inside the merged list.)  A valid key is never ~0 (id <= 2^31 - 1),
+// so key + 1 cannot wrap and padding is counted by neither bound.
+// One barrier; a bitonic sort of n_lists * k keys took 55 of them.
 // List l, query q, rank r: ids[((l * nq + q) * row_stride) + r], dists likewise -- row_stride = top_k for two
 // separate arrays, 2 * top_k for the packed [n_lists][nq][2k] tensor of the all-gather (dists = ids + top_k).
 // ---------------------------------------------------------------------------
@@ -3104,16 +3111,18 @@ __global__ __launch_bounds__(kSelectThreads) void merge_kernel(const int32_t* __
         if (key == ~0ull) continue;
         const int own = i / top_k;
         int rank = i % top_k;
-        for (int l = 0; l < n_lists && rank < top_k; ++l) {
-            if (l == own) continue;
+        // first position of list l whose key is not below `bound` (padding = ~0 sorts last)
+        auto lower = [&](int l, uint64_t bound) {
             const uint64_t* lst = v + (size_t)l * top_k;
-            int lo = 0, hi = top_k;  // first position whose key is not below `key` (padding = ~0 sorts last)
+            int lo = 0, hi = top_k;
             while (lo < hi) {
                 const int mid = (lo + hi) >> 1;
-                if (lst[mid] < key) lo = mid + 1; else hi = mid;
+                if (lst[mid] < bound) lo = mid + 1; else hi = mid;
             }
-            rank += lo;
-        }
+            return lo;
+        };
+        for (int l = 0; l < own && rank < top_k; ++l) rank += lower(l, key + 1);             // earlier lists: keys <= key
+        for (int l = own + 1; l < n_lists && rank < top_k; ++l) rank += lower(l, key);       // later lists: keys < key
         if (rank < top_k) {
             out_ids[(size_t)q * top_k + rank] = (int32_t)(key & 0xffffffffu);
             out_dists[(size_t)q * top_k + rank] = __uint_as_float((uint32_t)(key >> 32));

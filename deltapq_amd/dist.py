@@ -42,6 +42,8 @@ def gather_and_merge(ids, dists, group=None):
     partial result with GLOBAL DFS positions (padding rows: id -1, dist +inf).
     CUDA tensors take the device path (RCCL all-gather + dpq_merge_topk_device),
     CPU tensors the host path (gloo all-gather + dpq_merge_topk_host).
+    Both paths answer alike, to the bit: a row that several ranks report (replica answers) is kept as often as it
+    occurs.  The lists must be ascending by (distance bits, id) with their padding last, as query calls deliver them.
     Returns (ids, dists) of the merged top-k on every rank."""
     import torch
     import torch.distributed as dist

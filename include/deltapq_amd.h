@@ -514,7 +514,18 @@ int dpq_decode_range(dpq_index* idx, int64_t first, int64_t count, uint8_t* code
 
 /* Merge n_lists partial top-k lists per query (lists[l][nq][top_k]) into the
  * final top_k by (distance, id).  Host version for the single-process
- * multi-GPU CLI, device version for use after an RCCL all-gather. */
+ * multi-GPU CLI, device version for use after an RCCL all-gather.
+ * Contract, the same for all three calls unless said otherwise:
+ *  - A row with id < 0 is padding, whatever its id and distance.  The answer holds the top_k smallest valid rows by
+ *    (distance bit pattern as uint32, id), then rows of id -1 / +inf.  A valid row of distance +inf precedes them.
+ *  - Each list must be ascending by (distance bits, id) with its padding rows last -- what every query call of this
+ *    library delivers.  An unsorted list is a precondition violation for the two device calls (the answer is then
+ *    unspecified, within the output's bounds); the host call sorts and tolerates it.
+ *  - Repeated keys are kept, not merged away: a (distance, id) row that occurs in two lists (a prefix handle and the
+ *    whole index, a rank gathered twice, replica answers) or twice in one list occurs as often in the answer, as far
+ *    as top_k reaches.  Host and device calls answer alike, to the bit.
+ *  - DPQ_ERR_ARG before any device call: a NULL pointer, n_lists < 1, top_k < 1, nq < 0; for the device calls also
+ *    n_lists * top_k > 16384 (a query's keys are merged in 128 KB of LDS).  nq == 0: DPQ_OK, nothing is touched. */
 int dpq_merge_topk_host(const int32_t* ids, const float* dists, int n_lists, int nq, int top_k, int32_t* out_ids,
                         float* out_dists);
 int dpq_merge_topk_device(const int32_t* d_ids, const float* d_dists, int n_lists, int nq, int top_k,

@@ -53,6 +53,23 @@ def test_merge_range_host_hand_built():
     assert _keyed(*merge_range_host([b])) == _keyed(*b)
     l0, i0, d0 = merge_range_host([(np.array([0]), np.array([], np.int32), np.array([], f))] * 2)
     assert l0.tolist() == [0] and len(i0) == 0 and len(d0) == 0
+    # every part empty for every one of three queries
+    nothing = (np.array([0, 0, 0, 0]), np.array([], np.int32), np.array([], f))
+    l3, i3, d3 = merge_range_host([nothing, nothing, nothing])
+    assert l3.tolist() == [0, 0, 0, 0] and l3.dtype == np.int64 and len(i3) == 0 and len(d3) == 0
+    assert i3.dtype == np.int32 and d3.dtype == np.float32
+    assert _keyed(*merge_range_host([nothing, b, nothing])) == _keyed(*b)
+    # id / distance arrays longer than lims[-1] (a buffer with room to spare): the tail is not part of the answer
+    a_long = (a[0], np.array([7, 9, 1, 0], np.int32), np.array([1.0, 2.5, 0.0, 0.25], f))
+    b_long = (b[0], np.concatenate((b[1], np.array([2], np.int32))), np.concatenate((b[2], np.array([0.125], f))))
+    assert _keyed(*merge_range_host([a_long, b_long])) == _keyed(lims, ids, dists)
+    # parts that answer different numbers of queries, and no parts at all
+    with pytest.raises(ValueError):
+        merge_range_host([a, (np.array([0, 2, 4]), b[1], b[2])])
+    with pytest.raises(ValueError):
+        merge_range_host([(np.array([0, 2, 4]), b[1], b[2]), a])
+    with pytest.raises(ValueError):
+        merge_range_host([])
 
 
 # ---- GPU ------------------------------------------------------------------------------------------------------------
