@@ -130,6 +130,17 @@ SYMBOLS = [
     ("dpq_query_batch_filtered", ctypes.c_int, [_VP, _VP, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP]),
     ("dpq_query_batch_device_filtered", ctypes.c_int,
      [_VP, _VP, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP]),
+    ("dpq_filter_create_device", ctypes.c_int, [_VP, _VP, c_i64, _VP, P(_VP)]),
+    ("dpq_filter_create_ids", ctypes.c_int, [_VP, _VP, c_i64, ctypes.c_int, P(_VP)]),
+    ("dpq_filter_create_ids_device", ctypes.c_int, [_VP, _VP, c_i64, ctypes.c_int, _VP, P(_VP)]),
+    ("dpq_filter_create_range", ctypes.c_int, [_VP, c_i64, c_i64, P(_VP)]),
+    ("dpq_set_vec_ids", ctypes.c_int, [_VP, _VP, c_i64]),
+    ("dpq_filter_create_vec", ctypes.c_int, [_VP, _VP, c_i64, P(_VP)]),
+    ("dpq_filter_create_vec_device", ctypes.c_int, [_VP, _VP, c_i64, _VP, P(_VP)]),
+    ("dpq_filter_combine", ctypes.c_int, [_VP, ctypes.c_int, _VP, _VP, P(_VP)]),
+    ("dpq_filter_to_bitmap", ctypes.c_int, [_VP, _VP, c_i64]),
+    ("dpq_bitmap_from_mask_device", ctypes.c_int, [_VP, c_i64, _VP, ctypes.c_int, _VP]),
+    ("dpq_bitmap_from_ids_device", ctypes.c_int, [_VP, c_i64, c_i64, _VP, ctypes.c_int, _VP]),
     ("dpq_get_codes", ctypes.c_int, [_VP, _VP, c_i64, _VP]),
     ("dpq_get_codes_device", ctypes.c_int, [_VP, _VP, c_i64, _VP, _VP]),
     ("dpq_reconstruct", ctypes.c_int, [_VP, _VP, c_i64, _VP]),

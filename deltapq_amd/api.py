@@ -437,6 +437,14 @@ class DeltaPQIndex:
               "dpq_query_batch_device_filtered")
         return out_ids, out_dists
 
+    def set_vec_ids(self, vec_id):
+        """The original vector id of every node this handle holds (dpq_set_vec_ids): `vec_id` is the handle's local
+        slice, uint32 [node_hi - node_lo], of the builder's DFS position -> vector id array.  Kept on the device for
+        IdFilter.from_vec_* only; searches keep reporting DFS positions."""
+        v = np.ascontiguousarray(vec_id, dtype=np.uint32).ravel()
+        check(self._lib.dpq_set_vec_ids(self._h, _np_ptr(v) if v.size else None, v.size), "dpq_set_vec_ids")
+        return self
+
     def _lookup_ids(self, ids):
         return np.ascontiguousarray(np.asarray(ids, dtype=np.int32).reshape(-1))
 
@@ -580,6 +588,23 @@ class IdFilter:
         h = ctypes.c_void_p()
         check(self._lib.dpq_filter_create(index._h, _np_ptr(w) if w.size else None, int(n_bits), h), "dpq_filter_create")
         self._h = h
+        self._index = index
+
+    @classmethod
+    def _wrap(cls, index, handle):
+        """An IdFilter around a dpq_filter the library has already made on `index`."""
+        f = cls.__new__(cls)
+        f._lib = index._lib
+        f._h = handle
+        f._index = index
+        return f
+
+    @classmethod
+    def _create(cls, index, name, *args):
+        """One of the dpq_filter_create_* constructors: fn(index, *args, &out)."""
+        h = ctypes.c_void_p()
+        check(getattr(index._lib, name)(index._h, *args, h), name)
+        return cls._wrap(index, h)
 
     @staticmethod
     def pack_mask(mask):
@@ -614,8 +639,122 @@ class IdFilter:
         return cls(index, *cls.pack_mask(mask))
 
     @classmethod
-    def from_ids(cls, index, ids, n_bits=None):
-        return cls(index, *cls.pack_ids(ids, n_bits))
+    def from_ids(cls, index, ids, n_bits=None, invert=False):
+        """The listed reported ids (invert=True: every code of the index except them).  With `n_bits` the list is packed
+        into a bitmap on the host (ids must lie in [0, n_bits)); without, or with invert, it goes to the GPU as it is
+        (dpq_filter_create_ids): negative ids are padding, ids of other shards are skipped."""
+        if not invert and n_bits is not None:
+            return cls(index, *cls.pack_ids(ids, n_bits))
+        if n_bits is not None:
+            raise ValueError("a deny-list takes no n_bits: it allows every code of the index but the listed ones")
+        a = np.ascontiguousarray(np.asarray(ids, dtype=np.int32).ravel())
+        return cls._create(index, "dpq_filter_create_ids", _np_ptr(a) if a.size else None, a.size, int(bool(invert)))
+
+    @classmethod
+    def from_range(cls, index, lo, hi):
+        """Reported ids in [lo, hi) (dpq_filter_create_range)."""
+        return cls._create(index, "dpq_filter_create_range", int(lo), int(hi))
+
+    @classmethod
+    def from_vec_mask(cls, index, mask):
+        """mask[v]: whether ORIGINAL vector id v is allowed (dpq_filter_create_vec; index.set_vec_ids first)."""
+        w, n = cls.pack_mask(mask)
+        return cls._create(index, "dpq_filter_create_vec", _np_ptr(w) if w.size else None, n)
+
+    @classmethod
+    def from_vec_ids(cls, index, ids, n_bits=None):
+        """The listed ORIGINAL vector ids (index.set_vec_ids first)."""
+        w, n = cls.pack_ids(ids, n_bits)
+        return cls._create(index, "dpq_filter_create_vec", _np_ptr(w) if w.size else None, n)
+
+    # -- torch forms: CUDA tensors on the index's GPU, torch's current stream; nothing but the count goes to the host
+
+    @staticmethod
+    def _torch_words(index, n_bits, fill, *args):
+        """A device bitmap of n_bits bits, packed by one of the dpq_bitmap_from_*_device helpers: (tensor, pointer, stream)."""
+        import torch
+        dev = args[0].device
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        words = torch.empty(((n_bits + 31) // 32,), dtype=torch.int32, device=dev)
+        ptrs = [ctypes.c_void_p(t.data_ptr()) if t.numel() else None for t in args]
+        wp = ctypes.c_void_p(words.data_ptr()) if words.numel() else None
+        if fill == "mask":
+            check(index._lib.dpq_bitmap_from_mask_device(ptrs[0], args[0].numel(), wp, dev.index or 0, stream),
+                  "dpq_bitmap_from_mask_device")
+        else:
+            check(index._lib.dpq_bitmap_from_ids_device(ptrs[0], args[0].numel(), n_bits, wp, dev.index or 0, stream),
+                  "dpq_bitmap_from_ids_device")
+        return words, wp, stream
+
+    @staticmethod
+    def _torch_arg(t, dtype):
+        assert t.is_cuda and t.dtype == dtype and t.is_contiguous()
+        return t.reshape(-1)
+
+    @classmethod
+    def from_mask_torch(cls, index, mask):
+        """from_mask for a bool CUDA tensor over reported ids."""
+        import torch
+        m = cls._torch_arg(mask, torch.bool)
+        words, wp, stream = cls._torch_words(index, m.numel(), "mask", m)
+        return cls._create(index, "dpq_filter_create_device", wp, m.numel(), stream)
+
+    @classmethod
+    def from_ids_torch(cls, index, ids, invert=False):
+        """from_ids for an int32 CUDA tensor of reported ids (dpq_filter_create_ids_device)."""
+        import torch
+        i = cls._torch_arg(ids, torch.int32)
+        stream = ctypes.c_void_p(torch.cuda.current_stream(i.device).cuda_stream)
+        return cls._create(index, "dpq_filter_create_ids_device", ctypes.c_void_p(i.data_ptr()) if i.numel() else None,
+                           i.numel(), int(bool(invert)), stream)
+
+    @classmethod
+    def from_vec_mask_torch(cls, index, mask):
+        """from_vec_mask for a bool CUDA tensor over ORIGINAL vector ids."""
+        import torch
+        m = cls._torch_arg(mask, torch.bool)
+        words, wp, stream = cls._torch_words(index, m.numel(), "mask", m)
+        return cls._create(index, "dpq_filter_create_vec_device", wp, m.numel(), stream)
+
+    @classmethod
+    def from_vec_ids_torch(cls, index, ids, n_bits):
+        """from_vec_ids for an int32 CUDA tensor of ORIGINAL vector ids below n_bits (ids outside [0, n_bits) are skipped)."""
+        import torch
+        i = cls._torch_arg(ids, torch.int32)
+        words, wp, stream = cls._torch_words(index, int(n_bits), "ids", i)
+        return cls._create(index, "dpq_filter_create_vec_device", wp, int(n_bits), stream)
+
+    # -- algebra and read-back
+
+    def _combine(self, op, other):
+        if other is not None and not isinstance(other, IdFilter):
+            return NotImplemented
+        return IdFilter._create(self._index, "dpq_filter_combine", op, self._h, None if other is None else other._h)
+
+    def __and__(self, other):
+        return self._combine(0, other)
+
+    def __or__(self, other):
+        return self._combine(1, other)
+
+    def __sub__(self, other):
+        """The codes this filter allows and `other` does not."""
+        return self._combine(2, other)
+
+    def __xor__(self, other):
+        return self._combine(3, other)
+
+    def __invert__(self):
+        """Every code of the index this filter does not allow."""
+        return self._combine(4, None)
+
+    def to_mask(self, n_bits):
+        """bool [n_bits] over reported ids: whether the filter allows the code its index reports under that id
+        (dpq_filter_to_bitmap); ids that name no code of the index are False."""
+        n_bits = int(n_bits)
+        w = np.zeros((n_bits + 31) // 32, dtype=np.uint32)
+        check(self._lib.dpq_filter_to_bitmap(self._h, _np_ptr(w) if w.size else None, n_bits), "dpq_filter_to_bitmap")
+        return IdFilter.unpack(w, n_bits)
 
     @staticmethod
     def _handle(f):

@@ -475,6 +475,60 @@ int dpq_query_batch_filtered(dpq_index* idx, const dpq_filter* f, const float* q
 int dpq_query_batch_device_filtered(dpq_index* idx, const dpq_filter* f, const float* d_queries, int nq, int top_k,
                                     int32_t* d_ids, float* d_dists, void* hip_stream);
 
+/* ---- filter construction on the device ------------------------------------------
+ * Every other way of making a dpq_filter, with the work in HIP kernels on the handle's GPU (dpq_filter.hip) instead of
+ * dpq_filter_create's host pass: from a bitmap over reported ids that already lives on the GPU, from an id list (allow-
+ * or deny-list), from an id range, from a bitmap over ORIGINAL vector ids through a resident position -> vector-id map,
+ * and from other filters (AND / OR / AND-NOT / XOR / NOT); plus the read-back of a filter and two packing helpers.
+ * Same result: a filter from any constructor is indistinguishable from the one dpq_filter_create makes from the
+ * equivalent host bitmap -- the same bits, the same dpq_filter_count, the same owner check; it serves both filtered query
+ * calls on shards, parts, prefixes, plain handles and at M = 16.  Ids are REPORTED ids under the rules of the section
+ * above (global positions, the even-N rule: id N names the last node of an even-N DTC index and N - 1 names nothing).
+ * An id or bit that names no node of THIS handle is skipped, never an error: every shard builds from the same global
+ * list.  A negative id is padding.  Duplicates are harmless.
+ * Synchronous: a constructor enqueues its kernels on hip_stream (NULL = the default stream; the host forms use the
+ * default stream) and returns once the count of allowed nodes has been read back -- that one small read-back is the
+ * call's only host round trip (the convention of dpq_get_codes_device).  On return the filter is complete and usable on
+ * any stream.  Inputs must be complete on hip_stream's order; pending asynchronous batches are finished first.
+ * Arguments are checked before any device call; DPQ_ERR_ARG: NULL out (*out is cleared wherever out is given), NULL
+ * index, n_bits < 0, n < 0, a NULL pointer with a non-zero size, lo > hi, an unknown op, b given with DPQ_FILTER_NOT or
+ * missing otherwise, a filter of another handle, dpq_set_vec_ids with n != node_hi - node_lo.  n == 0 and n_bits == 0
+ * are legal and give empty filters (full ones with invert).  A _vec constructor before dpq_set_vec_ids: DPQ_ERR_STATE.
+ * Device memory: a filter costs what dpq_filter_create's costs; the vector-id map 4 bytes per node of the handle until
+ * dpq_close; the host forms' temporary uploads are freed before they return. */
+#define DPQ_FILTER_AND 0     /* a & b */
+#define DPQ_FILTER_OR 1      /* a | b */
+#define DPQ_FILTER_ANDNOT 2  /* a & ~b */
+#define DPQ_FILTER_XOR 3     /* a ^ b */
+#define DPQ_FILTER_NOT 4     /* every node of the handle a does not allow; b must be NULL */
+/* d_words[(n_bits + 31) / 32]: a bitmap over reported ids on the handle's GPU (dpq_filter_create's, without the upload). */
+int dpq_filter_create_device(dpq_index* idx, const uint32_t* d_words, int64_t n_bits, void* hip_stream, dpq_filter** out);
+/* An id list: invert == 0 allows exactly the listed ids, != 0 every node of the handle except them.  ids[n]: host. */
+int dpq_filter_create_ids(dpq_index* idx, const int32_t* ids, int64_t n, int invert, dpq_filter** out);
+int dpq_filter_create_ids_device(dpq_index* idx, const int32_t* d_ids, int64_t n, int invert, void* hip_stream,
+                                 dpq_filter** out);
+/* Reported ids in [lo, hi). */
+int dpq_filter_create_range(dpq_index* idx, int64_t lo, int64_t hi, dpq_filter** out);
+/* vec_id[n], host: the original vector id of local node l (position node_lo + l), n == node_hi - node_lo -- the handle's
+ * slice of dpq_tree_array(.., 0) / dpq_read_qnode_ids.  Uploaded once and kept until dpq_close or the next call.  Only the
+ * _vec constructors use it: searches keep reporting DFS positions. */
+int dpq_set_vec_ids(dpq_index* idx, const uint32_t* vec_id, int64_t n);
+/* A bitmap over ORIGINAL vector ids: node l is allowed iff vec_id[l] < n_bits and bit vec_id[l] is set -- what
+ * dpq_bitmap_to_dfs followed by dpq_filter_create gives, without the host pass.  words: host; d_words: the handle's GPU. */
+int dpq_filter_create_vec(dpq_index* idx, const uint32_t* words, int64_t n_bits, dpq_filter** out);
+int dpq_filter_create_vec_device(dpq_index* idx, const uint32_t* d_words, int64_t n_bits, void* hip_stream, dpq_filter** out);
+/* op: DPQ_FILTER_*; a and b filters of idx.  The operands are left as they are. */
+int dpq_filter_combine(dpq_index* idx, int op, const dpq_filter* a, const dpq_filter* b, dpq_filter** out);
+/* The filter back as a bitmap over reported ids: bit r = 1 iff the filter allows the node its handle reports as r; bits
+ * that name no node of the handle are 0.  words_out[(n_bits + 31) / 32]: host.  Works after dpq_close of the handle. */
+int dpq_filter_to_bitmap(const dpq_filter* f, uint32_t* words_out, int64_t n_bits);
+/* Helpers for any id space: a device bitmap of (n_bits + 31) / 32 words from a device byte mask (d_mask[n], non-zero =
+ * set, n_bits = n, the tail word zero-padded) or a device id list (cleared first; ids outside [0, n_bits) are skipped).
+ * Enqueued on hip_stream of GPU `device` and NOT waited for: a constructor called on the same stream sees the result. */
+int dpq_bitmap_from_mask_device(const uint8_t* d_mask, int64_t n, uint32_t* d_words_out, int device, void* hip_stream);
+int dpq_bitmap_from_ids_device(const int32_t* d_ids, int64_t n, int64_t n_bits, uint32_t* d_words_out, int device,
+                               void* hip_stream);
+
 /* ---- code lookup ------------------------------------------------------------
  * The codes an opened index holds, or their codebook vectors, for any reported ids (FAISS's sa_decode / reconstruct /
  * reconstruct_batch), decoded on the GPU from the very image the searches scan.  Every segment is decodable on its own
