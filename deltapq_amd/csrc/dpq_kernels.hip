@@ -309,8 +309,13 @@ __device__ __forceinline__ FilterScale filter_scale(uint64_t key, const float* _
     const double R = taup - B;
     r.B = B;
     if (key != ~0ull && R > 0.0 && R < 1e300) {  // else: no threshold yet (or degenerate), keep everything
-        r.s32 = (float)((double)C::QT / R * (1.0 - 0x1p-20));
-        r.bias = C::R == 1 ? (uint32_t)C::BIAS : 0u;  // R = 2: the accumulators carry it
+        const float s = (float)((double)C::QT / R * (1.0 - 0x1p-20));
+        // R below QT / FLT_MAX (distances under 2^-120): the scale is +inf in fp32 and every field would be NaN, which
+        // the fminf of filter_field turns into SAT -- a filter that rejects every node.  No scale, like no threshold.
+        if (s <= FLT_MAX) {
+            r.s32 = s;
+            r.bias = C::R == 1 ? (uint32_t)C::BIAS : 0u;  // R = 2: the accumulators carry it
+        }
     }
     return r;
 }
@@ -1656,6 +1661,7 @@ __global__ __launch_bounds__(kS1Threads) void strand1_kernel(const ScanArgs a) {
         const double R = taup - B;
         fs.B = B;
         if (thr != ~0ull && R > 0.0 && R < 1e300) fs.s32 = (float)((double)QT / R * (1.0 - 0x1p-20));  // else: everything passes the bound
+        if (!(fs.s32 <= FLT_MAX)) fs.s32 = 0.0f;  // (+inf: R below QT / FLT_MAX, see filter_scale)
     }
     const float sc = fs.s32, bdn = __double2float_rd(fs.B);
     // developer experiments (a.debug_pass >= 16, never in a query call): bit 0 nothing is checked exactly, bit 1 no looks
@@ -1679,7 +1685,9 @@ __global__ __launch_bounds__(kS1Threads) void strand1_kernel(const ScanArgs a) {
                 // as the scan's filter_field: half a unit off first, so whichever way v_cvt_pk_u8_f32 rounds the byte is
                 // <= floor((T - min) s): the entry stays a lower bound; it clamps to [0, 255] (inf of centroids beyond K: 255)
                 const float of = filter_offset<M>(fs, min_m[m], 1);
-                const float fv = fminf(__fmaf_rn(T32[m * 256 + tid], sc, of), 255.0f);
+                // (no scale: every entry 0 -- fma(+inf, 0, of) would be NaN and saturate, and an entry of 255 is above
+                // the cut whatever the threshold: a +inf entry of a real code must not reject where nothing is to reject)
+                const float fv = sc != 0.0f ? fminf(__fmaf_rn(T32[m * 256 + tid], sc, of), 255.0f) : 0.0f;
                 if (m < 4)
                     lo = __builtin_amdgcn_cvt_pk_u8_f32(fv, (uint32_t)m, lo);
                 else

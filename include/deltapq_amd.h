@@ -55,7 +55,9 @@
  *     bit-identical to the reference's incremental fp64 stack (h:2889-2907);
  *   - for even N the last DFS node is reported with id N, not N-1 (h:2949, 2970);
  *   - equal-distance results are ordered by ascending id (the reference emits
- *     them in libstdc++ heap order); at the k-th boundary the lowest ids win.
+ *     them in libstdc++ heap order); at the k-th boundary the lowest ids win;
+ *   - NaN inputs (codebook or queries) are out of scope; a distance of +inf (an entry or a sum that overflows fp32)
+ *     is an ordinary value, ordered by its bit pattern like any other: real ids at +inf precede padding.
  */
 #ifndef DELTAPQ_AMD_H
 #define DELTAPQ_AMD_H

@@ -260,11 +260,12 @@ def expected_topk(all_d, mask, k, base=0, N_total=None, node_lo=None, node_hi=No
 
 
 def expected_range(all_d, r, base=0, N_total=None, node_lo=None, node_hi=None):
-    """(ids int32, dists) of one query's range list on that handle: d < r strictly, by (distance bits, id)."""
+    """(ids int32, dists) of one query's range list on that handle: d < r strictly, by (distance bits, id); r = +inf:
+    every code of the handle, those at +inf included (include/deltapq_amd.h, range search)."""
     N_total = len(all_d) if N_total is None else N_total
     lo = 0 if node_lo is None else int(node_lo) - base
     hi = len(all_d) if node_hi is None else int(node_hi) - base
-    pos = lo + np.flatnonzero(all_d[lo:hi] < np.float32(r))
+    pos = lo + (np.arange(hi - lo) if np.isposinf(r) else np.flatnonzero(all_d[lo:hi] < np.float32(r)))
     pos = pos[np.lexsort((pos, all_d[pos].view(np.uint32)))]
     return reported_ids(pos, base, N_total).astype(np.int32), all_d[pos]
 
