@@ -62,6 +62,11 @@ class TrainStats(ctypes.Structure):
                 ("assign_ms", ctypes.c_double), ("update_ms", ctypes.c_double), ("repair_ms", ctypes.c_double)]
 
 
+class RefineOpts(ctypes.Structure):
+    _fields_ = [("M2", c_i32), ("K2", c_i32), ("train_n", c_i64), ("max_iters", c_i32), ("init", c_i32),
+                ("restarts", c_i32), ("reserved", c_i32), ("seed", ctypes.c_uint64)]
+
+
 # every symbol include/deltapq_amd.h declares: (name, restype, argtypes)
 _VP = ctypes.c_void_p
 SYMBOLS = [
@@ -173,6 +178,16 @@ SYMBOLS = [
     ("dpq_read_groundtruth", ctypes.c_int, [ctypes.c_char_p, P(c_i32), P(c_i32), _VP, _VP]),
     ("dpq_recall", ctypes.c_int,
      [_VP, ctypes.c_int, ctypes.c_int, _VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, P(ctypes.c_double)]),
+    ("dpq_residuals", ctypes.c_int, [_VP, _VP, c_i64, _VP, ctypes.c_int, _VP]),
+    ("dpq_refine_create", ctypes.c_int, [_VP, _VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, _VP, c_i64, P(_VP)]),
+    ("dpq_refine_free", None, [_VP]),
+    ("dpq_refine_get", ctypes.c_int, [_VP, P(c_i32), P(c_i32), P(c_i32), P(c_i64), _VP, _VP]),
+    ("dpq_refine_build", ctypes.c_int, [_VP, _VP, c_i64, ctypes.c_int, _VP, P(RefineOpts), P(_VP)]),
+    ("dpq_refine_reconstruct", ctypes.c_int, [_VP, _VP, c_i64, _VP]),
+    ("dpq_refine_rerank", ctypes.c_int, [_VP, _VP, ctypes.c_int, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP]),
+    ("dpq_refine_rerank_device", ctypes.c_int, [_VP, _VP, ctypes.c_int, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP]),
+    ("dpq_query_batch_refined", ctypes.c_int,
+     [_VP, _VP, _VP, _VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, _VP, _VP]),
     ("dpq_profile_enable", ctypes.c_int, [_VP, ctypes.c_int]),
     ("dpq_profile_reset", ctypes.c_int, [_VP]),
     ("dpq_profile_read", ctypes.c_int, [_VP, P(Profile)]),

@@ -1085,6 +1085,150 @@ class FlatIndexU8:
         self.close()
 
 
+class RefineLevel:
+    """A second PQ level over the residuals of an index's nodes (dpq_refine): M2 more bytes per node, and a PQ
+    shortlist is re-ranked by the distance to the two-level reconstruction -- no raw vectors on the GPU.  Made on one
+    DeltaPQIndex (after set_codebook) and closed before it."""
+
+    def __init__(self, index, handle):
+        self._lib = _lib.load()
+        self.index = index
+        self._h = handle
+        m2, k2, ds2, n = _lib.c_i32(), _lib.c_i32(), _lib.c_i32(), _lib.c_i64()
+        check(self._lib.dpq_refine_get(self._h, m2, k2, ds2, n, None, None), "dpq_refine_get")
+        self.M2, self.K2, self.Ds2, self.n_local = m2.value, k2.value, ds2.value, n.value
+        inf = index.info()
+        self.D1 = inf["M"] * inf["Ds"]
+
+    @classmethod
+    def build(cls, index, vectors, vec_id=None, M2=0, K2=0, train_n=0, max_iters=0, seed=0, start="rows", restarts=0):
+        """Trains and encodes a level from raw vectors [n_rows][D] (dpq_refine_build).  The row of the handle's local
+        node l is vectors[vec_id[l]] (DeltaTree.vec_id's slice for the handle), or vectors[l] without a map."""
+        if start not in _TRAIN_STARTS:
+            raise ValueError('start must be "rows" or "kmeans++"')
+        lib = _lib.load()
+        v = np.ascontiguousarray(vectors, dtype=np.float32)
+        if v.ndim != 2:
+            raise ValueError("vectors must be [n_rows][D]")
+        vid = None if vec_id is None else np.ascontiguousarray(vec_id, dtype=np.uint32).ravel()
+        if vid is not None and vid.size != index.info()["node_hi"] - index.info()["node_lo"]:
+            raise ValueError("vec_id must hold one entry per node of the handle")
+        opts = _lib.RefineOpts(M2=M2, K2=K2, train_n=train_n, max_iters=max_iters, init=_TRAIN_STARTS[start],
+                               restarts=restarts, seed=seed)
+        h = ctypes.c_void_p()
+        check(lib.dpq_refine_build(index._h, _np_ptr(v), v.shape[0], v.shape[1], None if vid is None else _np_ptr(vid), opts,
+                                   ctypes.byref(h)), "dpq_refine_build")
+        return cls(index, h)
+
+    @classmethod
+    def from_arrays(cls, index, codewords2, codes2):
+        """Uploads a ready-made level (dpq_refine_create): codewords2 float32 [M2][K2][Ds2], codes2 uint8 [n_local][M2]."""
+        lib = _lib.load()
+        cw = np.ascontiguousarray(codewords2, dtype=np.float32)
+        c = np.ascontiguousarray(codes2, dtype=np.uint8)
+        if cw.ndim != 3 or c.ndim != 2 or c.shape[1] != cw.shape[0]:
+            raise ValueError("codewords2 must be [M2][K2][Ds2] and codes2 [n_local][M2]")
+        h = ctypes.c_void_p()
+        check(lib.dpq_refine_create(index._h, _np_ptr(cw), cw.shape[0], cw.shape[1], cw.shape[2], _np_ptr(c), c.shape[0],
+                                    ctypes.byref(h)), "dpq_refine_create")
+        return cls(index, h)
+
+    def arrays(self):
+        """(codewords2 float32 [M2][K2][Ds2], codes2 uint8 [n_local][M2]) read back (dpq_refine_get)."""
+        cw = np.empty((self.M2, self.K2, self.Ds2), dtype=np.float32)
+        c = np.empty((self.n_local, self.M2), dtype=np.uint8)
+        check(self._lib.dpq_refine_get(self._h, None, None, None, None, _np_ptr(cw), _np_ptr(c)), "dpq_refine_get")
+        return cw, c
+
+    @staticmethod
+    def residuals(index, ids, vectors):
+        """Row i: vectors[i] (zero padded to M * Ds) minus the level-1 reconstruction of the node ids[i] names
+        (dpq_residuals), float32 [n][M * Ds]; a negative id gives NaNs."""
+        lib = _lib.load()
+        i = np.ascontiguousarray(np.asarray(ids, dtype=np.int32).reshape(-1))
+        v = np.ascontiguousarray(vectors, dtype=np.float32)
+        if v.ndim != 2 or v.shape[0] != i.size:
+            raise ValueError("vectors must be [len(ids)][D]")
+        inf = index.info()
+        out = np.empty((i.size, inf["M"] * inf["Ds"]), dtype=np.float32)
+        check(lib.dpq_residuals(index._h, _np_ptr(i), i.size, _np_ptr(v), v.shape[1], _np_ptr(out)), "dpq_residuals")
+        return out
+
+    def reconstruct(self, ids):
+        """The two-level reconstruction of reported ids (dpq_refine_reconstruct), float32 [n][M * Ds]; a negative id gives
+        a row of NaNs."""
+        i = np.ascontiguousarray(np.asarray(ids, dtype=np.int32).reshape(-1))
+        out = np.empty((i.size, self.D1), dtype=np.float32)
+        check(self._lib.dpq_refine_reconstruct(self._h, _np_ptr(i), i.size, _np_ptr(out)), "dpq_refine_reconstruct")
+        return out
+
+    def _queries(self, queries):
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim != 2 or q.shape[1] != self.D1:
+            raise ValueError("queries must be [nq][%d]" % self.D1)
+        return q
+
+    def rerank(self, queries, cand_ids, top_k):
+        """Refined distances of cand_ids[nq][n_cand] only (negative = padding), the best top_k of them
+        (dpq_refine_rerank)."""
+        q = self._queries(queries)
+        c = np.ascontiguousarray(cand_ids, dtype=np.int32)
+        if c.ndim != 2 or c.shape[0] != q.shape[0]:
+            raise ValueError("cand_ids must be [nq][n_cand]")
+        ids = np.empty((q.shape[0], top_k), dtype=np.int32)
+        dists = np.empty((q.shape[0], top_k), dtype=np.float32)
+        check(self._lib.dpq_refine_rerank(self._h, _np_ptr(q), q.shape[0], _np_ptr(c), c.shape[1], top_k, _np_ptr(ids),
+                                          _np_ptr(dists)), "dpq_refine_rerank")
+        return ids, dists
+
+    def rerank_torch(self, queries, cand_ids, top_k, out_ids=None, out_dists=None):
+        """rerank on device tensors, on torch's current stream (dpq_refine_rerank_device); the results are complete on
+        return."""
+        import torch
+        assert queries.is_cuda and queries.dtype == torch.float32 and queries.is_contiguous() and queries.shape[1] == self.D1
+        assert cand_ids.is_cuda and cand_ids.dtype == torch.int32 and cand_ids.is_contiguous()
+        assert cand_ids.shape[0] == queries.shape[0]
+        nq = queries.shape[0]
+        if out_ids is None:
+            out_ids = torch.empty((nq, top_k), dtype=torch.int32, device=queries.device)
+        if out_dists is None:
+            out_dists = torch.empty((nq, top_k), dtype=torch.float32, device=queries.device)
+        stream = torch.cuda.current_stream(queries.device).cuda_stream
+        check(self._lib.dpq_refine_rerank_device(self._h, ctypes.c_void_p(queries.data_ptr()), nq,
+                                                 ctypes.c_void_p(cand_ids.data_ptr()), cand_ids.shape[1], top_k,
+                                                 ctypes.c_void_p(out_ids.data_ptr()), ctypes.c_void_p(out_dists.data_ptr()),
+                                                 ctypes.c_void_p(stream)), "dpq_refine_rerank_device")
+        return out_ids, out_dists
+
+    def query_batch_refined(self, queries, n_cand, top_k, id_filter=None):
+        """The PQ top-n_cand of the index (among those `id_filter` allows, when given) refined to top_k, without a host
+        round trip in between (dpq_query_batch_refined)."""
+        q = self._queries(queries)
+        ids = np.empty((q.shape[0], top_k), dtype=np.int32)
+        dists = np.empty((q.shape[0], top_k), dtype=np.float32)
+        f = None if id_filter is None else IdFilter._handle(id_filter)
+        check(self._lib.dpq_query_batch_refined(self.index._h, self._h, f, _np_ptr(q), q.shape[0], n_cand, top_k,
+                                                _np_ptr(ids), _np_ptr(dists)), "dpq_query_batch_refined")
+        return ids, dists
+
+    def close(self):
+        if self._h is not None:
+            self._lib.dpq_refine_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 def read_vecs_range(path, first, count, ext="fvecs"):
     """Vectors [first, first + count) of an .fvecs/.bvecs file -> float32 [count][D]."""
     lib = _lib.load()

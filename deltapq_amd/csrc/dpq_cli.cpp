@@ -65,6 +65,8 @@ int main(int argc, char* argv[]) {
     long long N = -1;
     int restarts = 1;
     unsigned long long seed = 0;
+    int refine_m2 = 0, refine_k2 = 0, refine_r = 0;
+    long long train_size = 0;
     for (int i = 0; i < argc; i++) {  // main:26-70: hand-rolled scan, no validation
         std::string arg = argv[i];
         const char* nx = i + 1 < argc ? argv[i + 1] : "";
@@ -90,6 +92,10 @@ int main(int argc, char* argv[]) {
         if (arg == "-init") init = nx;
         if (arg == "-restarts") restarts = atoi(nx);
         if (arg == "-seed") seed = strtoull(nx, nullptr, 10);
+        if (arg == "-m2") refine_m2 = atoi(nx);
+        if (arg == "-k2") refine_k2 = atoi(nx);
+        if (arg == "-refine") refine_r = atoi(nx);
+        if (arg == "-train_size") train_size = atoll(nx);
     }
     (void)diff_argument; (void)method; (void)queryset;
 
@@ -400,13 +406,98 @@ int main(int argc, char* argv[]) {
         std::cout << gt_path << std::endl;
         return 0;
     }
+    if (task == "refine") {
+        // A second PQ level over the residuals of the index's nodes (dpq_refine_build): base.{ext}, the DTC index, its
+        // codewords and the TreeNodesDFS file (DFS position -> vector id, written for M <= 8 only) ->
+        // M{M}K{K}_refine_M{M2}K{K2}codewords.txt and codes.bin.refine.M{M}K{K}M{M2}K{K2}N{N}.
+        if (PQ_M <= 0 || PQ_K <= 0 || dataset.empty() || N < 1) {
+            std::cout << "usage: deltapq -dataset DIR -task refine -m M -k K -N N [-m2 M2] [-k2 K2] [-train_size T] [-seed S]"
+                         " [-ext fvecs|bvecs]   (M <= 8: the TreeNodesDFS file supplies the vector ids)" << std::endl;
+            return 2;
+        }
+        if (PQ_M > 8) {
+            std::cout << "-task refine needs M <= 8: there is no TreeNodesDFS file (vector ids) at M = " << PQ_M << std::endl;
+            return 1;
+        }
+        const bool bvecs = ext == "bvecs";
+        const std::string cw_path = dataset + "/M" + std::to_string(PQ_M) + "K" + std::to_string(PQ_K) + "codewords.txt";
+        int32_t cM = 0, cK = 0, cDs = 0;
+        int rc = dpq_read_codewords(cw_path.c_str(), &cM, &cK, &cDs, nullptr);
+        if (rc) return die("ReadCodewords", rc);
+        std::vector<float> codewords((size_t)cM * cK * cDs);
+        rc = dpq_read_codewords(cw_path.c_str(), &cM, &cK, &cDs, codewords.data());
+        if (rc) return die("ReadCodewords", rc);
+        if (cM != PQ_M || cK != PQ_K) {
+            std::cout << "codewords file is M=" << cM << " K=" << cK << std::endl;
+            return 1;
+        }
+        const std::string base_path = dataset + "/base." + ext;
+        int32_t D = 0;
+        rc = dpq_read_vecs_range(base_path.c_str(), bvecs, 0, N, &D, nullptr);
+        if (rc) return die("ItrReader", rc);
+        std::vector<float> base((size_t)N * D);
+        rc = dpq_read_vecs_range(base_path.c_str(), bvecs, 0, N, &D, base.data());
+        if (rc) return die("ItrReader", rc);
+        std::vector<uint32_t> vec_id((size_t)N);
+        const std::string nodes_path = dataset + "/M" + std::to_string(PQ_M) + "K" + std::to_string(PQ_K) +
+                                       "_Approx_TreeNodesDFS_N" + std::to_string(N);
+        rc = dpq_read_qnode_ids(nodes_path.c_str(), N, vec_id.data());
+        if (rc) return die("read TreeNodesDFS", rc);
+        if (dpq_device_count() < 1) {
+            std::cout << "no GPU visible: this build has no CPU path" << std::endl;
+            return 1;
+        }
+        char fname[4096];
+        rc = dpq_dtc_file_name(dataset.c_str(), PQ_M, PQ_K, N, fname, sizeof fname);
+        if (rc) return die("file name", rc);
+        dpq_index* idx = nullptr;
+        dpq_open_opts o;
+        memset(&o, 0, sizeof o);
+        rc = dpq_open_file(fname, PQ_M, PQ_K, &o, &idx);
+        if (rc) return die("dpq_open_file", rc);
+        rc = dpq_set_codebook(idx, codewords.data(), cDs);
+        if (rc) return die("dpq_set_codebook", rc);
+        dpq_refine_opts ro;
+        memset(&ro, 0, sizeof ro);
+        ro.M2 = refine_m2;
+        ro.K2 = refine_k2;
+        ro.train_n = train_size;
+        ro.seed = seed;
+        dpq_refine* lvl = nullptr;
+        const double t0 = Elapsed();
+        rc = dpq_refine_build(idx, base.data(), N, D, vec_id.data(), &ro, &lvl);
+        if (rc) return die("dpq_refine_build", rc);
+        const double elapsed = Elapsed() - t0;
+        int32_t M2 = 0, K2 = 0, Ds2 = 0;
+        int64_t n_local = 0;
+        rc = dpq_refine_get(lvl, &M2, &K2, &Ds2, &n_local, nullptr, nullptr);
+        if (rc) return die("dpq_refine_get", rc);
+        std::vector<float> cw2((size_t)M2 * K2 * Ds2);
+        std::vector<uint8_t> codes2((size_t)n_local * M2);
+        rc = dpq_refine_get(lvl, nullptr, nullptr, nullptr, nullptr, cw2.data(), codes2.data());
+        if (rc) return die("dpq_refine_get", rc);
+        dpq_refine_free(lvl);
+        dpq_close(idx);
+        const std::string tag = "M" + std::to_string(PQ_M) + "K" + std::to_string(PQ_K);
+        const std::string tag2 = "M" + std::to_string(M2) + "K" + std::to_string(K2);
+        const std::string cw2_path = dataset + "/" + tag + "_refine_" + tag2 + "codewords.txt";
+        const std::string codes2_path = dataset + "/codes.bin.refine." + tag + tag2 + "N" + std::to_string(N);
+        rc = dpq_write_codewords(cw2_path.c_str(), cw2.data(), M2, K2, Ds2);
+        if (rc) return die("PQ::WriteCodewords", rc);
+        rc = dpq_write_codes_plain(codes2_path.c_str(), codes2.data(), n_local, M2);
+        if (rc) return die("PQTree::Write", rc);
+        std::cout << "refine level M2 = " << M2 << " K2 = " << K2 << " Ds2 = " << Ds2 << " over " << n_local << " nodes in "
+                  << elapsed << " [sec] -> " << cw2_path << ", " << codes2_path << std::endl;
+        return 0;
+    }
     if (task == "recall") {
         // The other binary's `pqtree -task recall` (main.cpp:727-803) over this engine's answer: DTC query, DFS
         // positions -> vector ids (QNode.vec_id), against groundtruth/N{N}Top{G}.txt; -rerank R re-scores the PQ top-R
         // against base.{ext} (main.cpp:898-939) and reports the recall of that answer too.
         if (PQ_M <= 0 || PQ_K <= 0 || dataset.empty() || N < 1 || !topk_given || top_k < 1 || query_size < 1) {
             std::cout << "usage: deltapq -dataset DIR -task recall -m M -k K -N N -query_size Q -topk K [-gt_topk G] [-rerank R]"
-                         " [-ext fvecs|bvecs] [-filter FILE]" << std::endl;
+                         " [-ext fvecs|bvecs] [-filter FILE] [-refine R [-m2 M2] [-k2 K2]]   (-refine: the level of -task refine,"
+                         " M <= 8)" << std::endl;
             return 2;
         }
         if (gt_topk < 0) gt_topk = top_k;
@@ -422,6 +513,10 @@ int main(int argc, char* argv[]) {
         const bool filtered = !filter_path.empty();
         if (filtered && rerank) {
             std::cout << "-rerank cannot be combined with -filter: there is no filtered re-rank" << std::endl;
+            return 1;
+        }
+        if (refine_r != 0 && (refine_r < top_k || refine_r > 2048 || filtered || PQ_M > 8)) {
+            std::cout << "-refine " << refine_r << " outside " << top_k << "..2048, or combined with -filter, or M > 8" << std::endl;
             return 1;
         }
         const bool bvecs = ext == "bvecs";
@@ -509,6 +604,36 @@ int main(int argc, char* argv[]) {
         }
         std::cout << (Elapsed() - t0) / (double)nq * 1000 << " [msec/query] " << std::endl;
         dpq_filter_free(filt);
+        std::vector<int32_t> ref_pos;
+        if (refine_r) {  // the level -task refine wrote: the PQ top-R refined to top_k on the device
+            const int M2 = refine_m2 ? refine_m2 : PQ_M, K2 = refine_k2 ? refine_k2 : 256;
+            const std::string tag = "M" + std::to_string(PQ_M) + "K" + std::to_string(PQ_K);
+            const std::string tag2 = "M" + std::to_string(M2) + "K" + std::to_string(K2);
+            const std::string cw2_path = dataset + "/" + tag + "_refine_" + tag2 + "codewords.txt";
+            const std::string codes2_path = dataset + "/codes.bin.refine." + tag + tag2 + "N" + std::to_string(N);
+            int32_t rM = 0, rK = 0, rDs = 0;
+            rc = dpq_read_codewords(cw2_path.c_str(), &rM, &rK, &rDs, nullptr);
+            if (rc) return die("ReadCodewords (refine)", rc);
+            std::vector<float> cw2((size_t)rM * rK * rDs);
+            rc = dpq_read_codewords(cw2_path.c_str(), &rM, &rK, &rDs, cw2.data());
+            if (rc) return die("ReadCodewords (refine)", rc);
+            int64_t n2 = 0;
+            rc = dpq_read_codes_plain(codes2_path.c_str(), rM, &n2, nullptr);
+            if (rc) return die("PQTree::Read (refine)", rc);
+            std::vector<uint8_t> codes2((size_t)n2 * rM);
+            rc = dpq_read_codes_plain(codes2_path.c_str(), rM, &n2, codes2.data());
+            if (rc) return die("PQTree::Read (refine)", rc);
+            dpq_refine* lvl = nullptr;
+            rc = dpq_refine_create(idx, cw2.data(), rM, rK, rDs, codes2.data(), n2, &lvl);
+            if (rc) return die("dpq_refine_create", rc);
+            ref_pos.resize((size_t)nq * top_k);
+            std::vector<float> ref_d((size_t)nq * top_k);
+            const double t1 = Elapsed();
+            rc = dpq_query_batch_refined(idx, lvl, nullptr, queries.data(), nq, refine_r, top_k, ref_pos.data(), ref_d.data());
+            if (rc) return die("dpq_query_batch_refined", rc);
+            std::cout << "refined query " << (Elapsed() - t1) / (double)nq * 1000 << " [msec/query] " << std::endl;
+            dpq_refine_free(lvl);
+        }
         dpq_close(idx);
         for (size_t i = 0; i < found.size(); ++i) {
             int64_t p = pos[i];
@@ -521,6 +646,19 @@ int main(int argc, char* argv[]) {
         char line[128];
         snprintf(line, sizeof line, filtered ? "filtered recall@%d = %.6f" : "recall@%d = %.6f", top_k, rec);
         std::cout << line << std::endl;
+        if (refine_r) {
+            std::vector<int32_t> ref_found(ref_pos.size());
+            for (size_t i = 0; i < ref_found.size(); ++i) {
+                int64_t p = ref_pos[i];
+                if (p == N && N % 2 == 0) p = N - 1;
+                ref_found[i] = p < 0 || p >= N ? -1 : (int32_t)vec_id[(size_t)p];
+            }
+            double ref_rec = 0;
+            rc = dpq_recall(ref_found.data(), top_k, top_k, truth.data(), g_k, top_k, nq, &ref_rec);
+            if (rc) return die("dpq_recall", rc);
+            snprintf(line, sizeof line, "refine: recall@%d PQ %.6f -> top-%d refined %.6f", top_k, rec, refine_r, ref_rec);
+            std::cout << line << std::endl;
+        }
         if (rerank) {
             const std::string base_path = dataset + "/base." + ext;
             int32_t Db = 0;

@@ -40,6 +40,8 @@
  *   (none: FAISS's IndexFlat::search with an    dpq_flat_filter_create / dpq_flat_search_filtered[_u8]
  *     IDSelector)
  *   (none: FAISS's IndexFlat::range_search)     dpq_flat_range_search[_u8], dpq_range_recall
+ *   (none: FAISS's IndexRefine over two PQ      dpq_refine_build / dpq_refine_rerank / dpq_query_batch_refined
+ *     indexes; ADC+R)                             (a second PQ level over the residuals re-ranks a shortlist)
  *
  * Conventions: plain pointers and sizes only; the caller owns every host
  * buffer it passes, the library owns device memory.  Every function returns a
@@ -756,6 +758,93 @@ int dpq_read_groundtruth(const char* path, int32_t* nq, int32_t* top_k, int32_t*
  * (main.cpp:783-796); k = 1 gives 1-recall@R. */
 int dpq_recall(const int32_t* found, int found_stride, int R, const int32_t* truth, int truth_stride, int k, int nq,
                double* recall);
+
+/* ---- residual re-ranking: a second PQ level refines a shortlist ---------------
+ * Every answer of dpq_query_batch is a coarse PQ approximation, and dpq_flat_rerank needs the raw vectors on the GPU
+ * (512 B per SIFT vector against 8 B of code).  A dpq_refine is a second product quantizer over the RESIDUALS of the
+ * handle's nodes against their level-1 reconstruction (Jegou, Tavenard, Douze, Amsaleg, "Searching in one billion
+ * vectors: re-rank with source coding", ICASSP 2011; FAISS's IndexRefine over two PQ indexes): M2 more bytes per
+ * node, and a shortlist is re-ranked by the distance to the two-level reconstruction.
+ * Definitions.  The handle has M, K, Ds (dpq_set_codebook) and D1 = M * Ds, the width of its queries.  A level has M2,
+ * K2 and Ds2 = ceil(D1 / M2), codewords2 [M2][K2][Ds2] and one code c2[M2] per node of the handle.  For node p with
+ * level-1 code c1 and j = 0 .. D1-1:
+ *     a[j] = codewords1[j / Ds][c1[j / Ds]][j % Ds]     the very floats dpq_set_codebook received; the level keeps its
+ *                                                       own device copy taken when it is made: a later
+ *                                                       dpq_set_codebook does not change a level;
+ *     r[j] = v[j] - a[j]                                the residual: one fp32 subtraction, rounded; v is the node's
+ *                                                       raw vector [D], zero padded to D1; ceil(D / M) must be Ds;
+ *     c2   = dpq_encode_pq(r, D = D1, codewords2, M2, K2, Ds2)   with its padding of r to M2 * Ds2 and its
+ *                                                       first-minimum rule;
+ *     b[j] = codewords2[j / Ds2][c2[j / Ds2]][j % Ds2];
+ *     x[j] = a[j] + b[j]                                the reconstruction: one fp32 add, rounded.
+ * The refined distance of a query q [D1] to the node is the exact search's arithmetic (above) over the row x: for j
+ * ascending t = x[j] - q[j] in fp32, s = t * t in fp32 rounded on its own, acc += (double)s from +0.0; the result is
+ * (float)acc.  No fused multiply-add, no distance split across lanes, no |q-a|^2 - 2 (q-a).b + |b|^2 shortcut.
+ * tests/_refine_restatement.py restates these rules in numpy; the GPU meets them bit for bit.
+ * Results follow dpq_flat_rerank's rules: keys `distance bits << 32 | reported id` ascending; the reported id is the
+ * candidate id itself; a negative candidate is padding; a node named twice by one query counts once; rows are padded
+ * with -1 / +inf; 1 <= top_k <= n_cand <= 16384.  A non-negative candidate or id that names no node of the handle --
+ * by the code lookup's id rules: global positions on shards and parts, prefixes, plain handles, the even-N rule -- is
+ * DPQ_ERR_ARG: the host forms check on the host before any device work, the device form raises a flag word that is
+ * read back at the end (its outputs are then unspecified).
+ * DPQ_ERR_ARG for a level's shape: M2 outside 1..64, K2 outside 2..256, Ds2 != ceil(D1 / M2), (M2 - 1) * Ds2 >= D1 (a
+ * sub-space without a real dimension).  A level made on another handle is DPQ_ERR_ARG.  Before dpq_set_codebook:
+ * DPQ_ERR_STATE.  Argument checks that need no device come first.  All entry points are synchronous and finish
+ * pending asynchronous batches first.  A level must be freed before the dpq_close of its handle.  Handles of M = 8 and
+ * M = 16 (what the code lookup decodes).
+ * Shards: every shard has its own level over its own nodes; the partial refined lists merge with dpq_merge_topk_*
+ * unchanged.  The merged answer re-ranks the UNION of the shards' shortlists (n_cand candidates per shard), which can
+ * only add candidates over a single handle's shortlist of n_cand.
+ * Device memory: M2 bytes per node of the handle plus the two codebooks, until dpq_refine_free; workspaces of one
+ * slice of 2^20 candidates (M MB of level-1 codes, 16 MB of keys) kept with the level; dpq_refine_build adds one
+ * slice's rows and residuals (at most 128 MB each) while it runs. */
+typedef struct dpq_refine dpq_refine;
+typedef struct dpq_refine_opts {
+    int32_t M2;        /* 0 = M */
+    int32_t K2;        /* 0 = 256 */
+    int64_t train_n;   /* residuals the codebook is trained on; 0 = min(n_local, 256 * K2) */
+    int32_t max_iters; /* 0 = 25; then dpq_train_opts' meaning */
+    int32_t init, restarts;
+    int32_t reserved;  /* 0 */
+    uint64_t seed;
+} dpq_refine_opts;
+/* Row i of out[n][D1] is the residual of the node ids[i] names against vectors[i] (vectors[n][D]); a negative id gives
+ * D1 quiet NaNs.  Host buffers. */
+int dpq_residuals(dpq_index* idx, const int32_t* ids, int64_t n, const float* vectors, int D, float* out);
+/* Uploads a ready-made level: codewords2 [M2][K2][Ds2], codes2[n_local][M2], row l for position node_lo + l; n_local
+ * must be the handle's node count; a code byte >= K2 is DPQ_ERR_ARG.  With dpq_refine_get, dpq_write_codewords and
+ * dpq_write_codes_plain this is how a level is saved and loaded again. */
+int dpq_refine_create(dpq_index* idx, const float* codewords2, int M2, int K2, int Ds2, const uint8_t* codes2,
+                      int64_t n_local, dpq_refine** out);
+void dpq_refine_free(dpq_refine* r);  /* NULL: nothing happens */
+/* The shape, and with non-NULL pointers the codewords [M2][K2][Ds2] and codes [n_local][M2] back (host). */
+int dpq_refine_get(const dpq_refine* r, int32_t* M2, int32_t* K2, int32_t* Ds2, int64_t* n_local, float* codewords2,
+                   uint8_t* codes2);
+/* Trains and encodes a level from raw vectors [n_rows][D] (host).  The row of local node l is vectors[vec_id[l]]
+ * (vec_id [n_local], an entry >= n_rows is DPQ_ERR_ARG), or vectors[l] when vec_id is NULL (then n_rows = n_local).
+ * opts NULL = all defaults.  By definition the composition of public calls, byte for byte: the sample positions
+ * l_i = floor(i * n_local / train_n), i = 0 .. train_n - 1; dpq_residuals of the sample; dpq_train_codebook(those,
+ * train_n, D1, M2, K2, the options, the handle's device); then for every node dpq_residuals and dpq_encode_pq; then
+ * dpq_refine_create.  It streams the nodes in slices of at most 2^20 (host gather into staging, upload, residual and
+ * encode on the device), so device memory stays bounded whatever n_local. */
+int dpq_refine_build(dpq_index* idx, const float* vectors, int64_t n_rows, int D, const uint32_t* vec_id,
+                     const dpq_refine_opts* opts, dpq_refine** out);
+/* x rows [n][D1] of reported ids, with dpq_reconstruct's padding rule (a negative id: D1 quiet NaNs).  Host buffers. */
+int dpq_refine_reconstruct(dpq_refine* r, const int32_t* ids, int64_t n, float* out);
+/* queries[nq][D1], cand_ids[nq][n_cand] -> ids / dists [nq][top_k].  Host buffers.  Candidates are processed in slices
+ * of at most 2^20, so the level-1 code scratch stays at M MB. */
+int dpq_refine_rerank(dpq_refine* r, const float* queries, int nq, const int32_t* cand_ids, int n_cand, int top_k,
+                      int32_t* ids, float* dists);
+/* Device pointers on the handle's GPU, enqueued on `hip_stream` (NULL = default stream); returns after the flag word
+ * has come back, i.e. with the results complete (dpq_flat_rerank_device's conventions). */
+int dpq_refine_rerank_device(dpq_refine* r, const float* d_queries, int nq, const int32_t* d_cand_ids, int n_cand,
+                             int top_k, int32_t* d_ids, float* d_dists, void* hip_stream);
+/* The PQ top-n_cand on the device (dpq_query_batch_device, or _device_filtered when filter is not NULL), then the
+ * refined re-rank of those lists, with no host round trip in between.  By definition dpq_query_batch[_filtered] with
+ * top_k = n_cand followed by dpq_refine_rerank; n_cand is bound by both (<= 2048), and n_cand above the handle's codes
+ * is DPQ_ERR_TOPK.  Host buffers. */
+int dpq_query_batch_refined(dpq_index* idx, dpq_refine* r, const dpq_filter* filter, const float* queries, int nq,
+                            int n_cand, int top_k, int32_t* ids, float* dists);
 
 /* ---- measurement -------------------------------------------------------- */
 int dpq_profile_enable(dpq_index* idx, int on);  /* 0 off, 1 every kernel, 2 scan launches only (less event overhead) */
