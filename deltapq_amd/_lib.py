@@ -67,6 +67,20 @@ class RefineOpts(ctypes.Structure):
                 ("restarts", c_i32), ("reserved", c_i32), ("seed", ctypes.c_uint64)]
 
 
+class OpqOpts(ctypes.Structure):
+    _fields_ = [("device", c_i32), ("outer_iters", c_i32), ("init_iters", c_i32), ("inner_iters", c_i32),
+                ("seed", ctypes.c_uint64), ("init", c_i32), ("restarts", c_i32), ("use_initial_rotation", c_i32),
+                ("reserved", c_i32 * 1)]
+
+
+class OpqStats(ctypes.Structure):
+    _fields_ = [("outer_run", c_i32), ("best_t", c_i32), ("degenerate", c_i32), ("reserved", c_i32),
+                ("objective", ctypes.c_double * 65), ("rotation_residual", ctypes.c_double * 64),
+                ("gpu_ms", ctypes.c_double), ("wall_ms", ctypes.c_double), ("rounds_ms", ctypes.c_double),
+                ("assign_ms", ctypes.c_double), ("update_ms", ctypes.c_double), ("repair_ms", ctypes.c_double),
+                ("rotate_ms", ctypes.c_double), ("cross_ms", ctypes.c_double), ("procrustes_ms", ctypes.c_double)]
+
+
 # every symbol include/deltapq_amd.h declares: (name, restype, argtypes)
 _VP = ctypes.c_void_p
 SYMBOLS = [
@@ -188,6 +202,15 @@ SYMBOLS = [
     ("dpq_refine_rerank_device", ctypes.c_int, [_VP, _VP, ctypes.c_int, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP]),
     ("dpq_query_batch_refined", ctypes.c_int,
      [_VP, _VP, _VP, _VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, _VP, _VP]),
+    ("dpq_rotate", ctypes.c_int, [_VP, c_i64, ctypes.c_int, _VP, ctypes.c_int, _VP]),
+    ("dpq_rotate_device", ctypes.c_int, [_VP, c_i64, ctypes.c_int, _VP, _VP, _VP]),
+    ("dpq_cross_covariance", ctypes.c_int,
+     [_VP, c_i64, ctypes.c_int, _VP, _VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _VP]),
+    ("dpq_procrustes", ctypes.c_int, [_VP, ctypes.c_int, _VP, P(c_i32)]),
+    ("dpq_opq_train", ctypes.c_int,
+     [_VP, c_i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, P(OpqOpts), _VP, _VP, P(OpqStats)]),
+    ("dpq_write_rotation", ctypes.c_int, [ctypes.c_char_p, _VP, ctypes.c_int]),
+    ("dpq_read_rotation", ctypes.c_int, [ctypes.c_char_p, P(c_i32), _VP]),
     ("dpq_profile_enable", ctypes.c_int, [_VP, ctypes.c_int]),
     ("dpq_profile_reset", ctypes.c_int, [_VP]),
     ("dpq_profile_read", ctypes.c_int, [_VP, P(Profile)]),

@@ -251,6 +251,112 @@ def write_codewords(path, codebook):
     check(_lib.load().dpq_write_codewords(path.encode(), _np_ptr(cb), M, K, Ds), "dpq_write_codewords")
 
 
+def rotate(vectors, rotation, device=0):
+    """out = vectors . rotation on the GPU (dpq_rotate): fp64 accumulation over d ascending, rounded once to float32.
+    Host arrays; returns float32 [n][D]."""
+    v = np.ascontiguousarray(vectors, dtype=np.float32)
+    if v.ndim == 1:
+        v = v[None, :]
+    r = np.ascontiguousarray(rotation, dtype=np.float32)
+    assert v.ndim == 2 and r.shape == (v.shape[1], v.shape[1]), "rotation must be [D][D]"
+    out = np.empty_like(v)
+    check(_lib.load().dpq_rotate(_np_ptr(v), v.shape[0], v.shape[1], _np_ptr(r), device, _np_ptr(out)), "dpq_rotate")
+    return out
+
+
+def rotate_torch(vectors, rotation, out=None):
+    """rotate on device tensors (dpq_rotate_device): enqueued on torch's current stream, no host round trip.  `out`
+    must not be `vectors`."""
+    import torch
+    assert vectors.is_cuda and vectors.dtype == torch.float32 and vectors.is_contiguous() and vectors.dim() == 2
+    assert rotation.is_cuda and rotation.dtype == torch.float32 and rotation.is_contiguous()
+    n, D = vectors.shape
+    assert tuple(rotation.shape) == (D, D), "rotation must be [D][D]"
+    if out is None:
+        out = torch.empty_like(vectors)
+    if n == 0:
+        return out
+    with torch.cuda.device(vectors.device):
+        stream = torch.cuda.current_stream(vectors.device).cuda_stream
+        check(_lib.load().dpq_rotate_device(ctypes.c_void_p(vectors.data_ptr()), n, D, ctypes.c_void_p(rotation.data_ptr()),
+                                            ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(stream)), "dpq_rotate_device")
+    return out
+
+
+def cross_covariance(vectors, codes, codebook, device=0):
+    """C = X^T Y in fp64, leaf-ordered (dpq_cross_covariance): Y is the reconstruction of `codes` under `codebook`,
+    gathered on the GPU.  Returns float64 [D][D]."""
+    v = np.ascontiguousarray(vectors, dtype=np.float32)
+    c = np.ascontiguousarray(codes, dtype=np.uint8)
+    cb = np.ascontiguousarray(codebook, dtype=np.float32)
+    assert v.ndim == 2 and c.ndim == 2 and cb.ndim == 3 and c.shape == (v.shape[0], cb.shape[0])
+    M, K, Ds = cb.shape
+    out = np.zeros((v.shape[1], v.shape[1]), dtype=np.float64)
+    check(_lib.load().dpq_cross_covariance(_np_ptr(v), v.shape[0], v.shape[1], _np_ptr(c), _np_ptr(cb), M, K, Ds, device,
+                                           _np_ptr(out)), "dpq_cross_covariance")
+    return out
+
+
+def procrustes(C):
+    """The orthogonal polar factor U V^T of C = U S V^T (dpq_procrustes; host, fp64, one-sided Jacobi).  Returns
+    (R float64 [D][D], degenerate bool); R is all zeros when degenerate."""
+    c = np.ascontiguousarray(C, dtype=np.float64)
+    assert c.ndim == 2 and c.shape[0] == c.shape[1]
+    out = np.zeros_like(c)
+    deg = _lib.c_i32(0)
+    check(_lib.load().dpq_procrustes(_np_ptr(c), c.shape[0], _np_ptr(out), deg), "dpq_procrustes")
+    return out, bool(deg.value)
+
+
+def train_opq(vectors, M=8, K=256, outer_iters=8, init_iters=25, inner_iters=4, seed=0, start="rows", restarts=1,
+              rotation=None, device=0):
+    """OPQ on the GPU (dpq_opq_train): an orthogonal rotation learned together with the codebooks of the rotated space.
+    rotation: a start [D][D] instead of the identity.  Returns (rotation float32 [D][D], codebook float32 [M][K][D / M],
+    stats dict); the pair is the outer step with the lowest objective."""
+    if start not in _TRAIN_STARTS:
+        raise ValueError('start must be "rows" or "kmeans++"')
+    lib = _lib.load()
+    v = np.ascontiguousarray(vectors, dtype=np.float32)
+    assert v.ndim == 2
+    n, D = v.shape
+    opts = _lib.OpqOpts(device=device, outer_iters=outer_iters, init_iters=init_iters, inner_iters=inner_iters, seed=seed,
+                        init=_TRAIN_STARTS[start], restarts=restarts, use_initial_rotation=int(rotation is not None))
+    if rotation is None:
+        rot = np.zeros((D, D), dtype=np.float32)
+    else:
+        rot = np.array(rotation, dtype=np.float32, order="C")
+        assert rot.shape == (D, D), "rotation must be [D][D]"
+    cb = np.zeros((max(M, 1), max(K, 1), max(D // M, 1) if M >= 1 else 1), dtype=np.float32)
+    st = _lib.OpqStats()
+    check(lib.dpq_opq_train(_np_ptr(v), n, D, M, K, opts, _np_ptr(rot), _np_ptr(cb), st), "dpq_opq_train")
+    stats = {k: getattr(st, k) for k, _ in st._fields_ if k not in ("objective", "rotation_residual", "reserved")}
+    stats["objective"] = [st.objective[i] for i in range(st.outer_run + 1)]
+    stats["rotation_residual"] = [st.rotation_residual[i] for i in range(st.outer_run)]
+    return rot, cb, stats
+
+
+def write_rotation(path, rotation):
+    """The rotation file (dpq_write_rotation): .fvecs layout, D rows of D floats."""
+    r = np.ascontiguousarray(rotation, dtype=np.float32)
+    assert r.ndim == 2 and r.shape[0] == r.shape[1]
+    check(_lib.load().dpq_write_rotation(path.encode(), _np_ptr(r), r.shape[0]), "dpq_write_rotation")
+
+
+def read_rotation(path):
+    """float32 [D][D] of a rotation file (dpq_read_rotation); a truncated or non-square file raises DpqError."""
+    lib = _lib.load()
+    D = _lib.c_i32()
+    check(lib.dpq_read_rotation(path.encode(), D, None), "dpq_read_rotation")
+    out = np.empty((D.value, D.value), dtype=np.float32)
+    check(lib.dpq_read_rotation(path.encode(), D, _np_ptr(out)), "dpq_read_rotation")
+    return out
+
+
+def rotation_file_name(dataset_dir, M, K):
+    import os
+    return os.path.join(dataset_dir, "M%dK%drotation.fvecs" % (M, K))
+
+
 def read_codes_plain(path, M):
     """PQTree::Read (pq_tree.cpp:1032-1081): uint8 [N][M]."""
     lib = _lib.load()
@@ -572,6 +678,56 @@ class DeltaPQIndex:
 
     def __exit__(self, *exc):
         self.close()
+
+
+class RotatedIndex:
+    """An index over codes of ROTATED vectors (OPQ) that takes raw queries: every search rotates its queries on the
+    index's GPU (dpq_rotate_device, into a buffer this object owns) and then calls the unchanged method of the index
+    it wraps.  The rotation stays on the device.  Everything else (info, get_codes, ...) passes through."""
+
+    def __init__(self, index, rotation):
+        import torch
+        r = np.ascontiguousarray(rotation, dtype=np.float32)
+        assert r.ndim == 2 and r.shape[0] == r.shape[1], "rotation must be [D][D]"
+        self.index = index
+        self._device = torch.device("cuda", index.info()["device"])
+        self._rot = torch.from_numpy(r).to(self._device)
+        self._buf = None
+
+    def _rotated(self, queries):
+        """Device tensor [nq][D] of the rotated queries; valid until the next call."""
+        import torch
+        if isinstance(queries, torch.Tensor):
+            q = queries
+            assert q.is_cuda and q.dtype == torch.float32 and q.is_contiguous()
+        else:
+            h = np.ascontiguousarray(queries, dtype=np.float32)
+            if h.ndim == 1:
+                h = h[None, :]
+            q = torch.from_numpy(h).to(self._device)
+        if self._buf is None or self._buf.shape[0] < q.shape[0]:
+            self._buf = torch.empty((q.shape[0], self._rot.shape[0]), dtype=torch.float32, device=self._device)
+        return rotate_torch(q, self._rot, out=self._buf[:q.shape[0]])
+
+    def _rotated_host(self, queries):
+        return self._rotated(queries).cpu().numpy()
+
+    def query_batch(self, queries, top_k):
+        return self.index.query_batch(self._rotated_host(queries), top_k)
+
+    def query_batch_filtered(self, queries, top_k, id_filter):
+        return self.index.query_batch_filtered(self._rotated_host(queries), top_k, id_filter)
+
+    def range_search(self, queries, radius):
+        return self.index.range_search(self._rotated_host(queries), radius)
+
+    def query_batch_torch(self, queries, top_k, **kw):
+        return self.index.query_batch_torch(self._rotated(queries), top_k, **kw)
+
+    def __getattr__(self, name):
+        if name == "index":      # (not set yet: __init__ failed early)
+            raise AttributeError(name)
+        return getattr(self.index, name)
 
 
 class IdFilter:

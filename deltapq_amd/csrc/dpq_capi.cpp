@@ -29,6 +29,8 @@
 #include "dpq_format.h"
 #include "dpq_kernels.h"
 #include "dpq_lookup.h"
+#include "dpq_opq.h"
+#include "dpq_procrustes.h"
 #include "dpq_refine.h"
 #include "dpq_train.h"
 
@@ -5060,6 +5062,258 @@ int dpq_query_batch_refined(dpq_index* x, dpq_refine* r, const dpq_filter* filte
     if (rc) return rc;
     DPQ_HIP(hipMemcpy(ids, r->d_ids, (size_t)nq * top_k * sizeof(int32_t), hipMemcpyDeviceToHost));
     DPQ_HIP(hipMemcpy(dists, r->d_dists, (size_t)nq * top_k * sizeof(float), hipMemcpyDeviceToHost));
+    return DPQ_OK;
+    });
+}
+
+// ---- OPQ: rotation, cross-covariance, Procrustes, the training loop (dpq_opq.hip, dpq_procrustes.cpp) ----------------
+
+static int opq_check_dim(const std::string& who, int D) {
+    if (D < 1 || D > dpq::kOpqMaxD) return fail(DPQ_ERR_ARG, who + ": D outside 1..1024");
+    return DPQ_OK;
+}
+
+int dpq_rotate_device(const float* d_vectors, int64_t n, int D, const float* d_R, float* d_out, void* hip_stream) {
+    return guarded([&]() -> int {
+    const std::string who = "dpq_rotate_device";
+    if (!d_vectors || !d_R || !d_out) return fail(DPQ_ERR_ARG, who + ": NULL argument");
+    if (n < 0) return fail(DPQ_ERR_ARG, who + ": n < 0");
+    if (int rc = opq_check_dim(who, D)) return rc;
+    if (d_out == d_vectors) return fail(DPQ_ERR_ARG, who + ": out must not alias vectors");
+    if (int rc = flat_device_present(who)) return rc;
+    const hipError_t e = dpq::launch_opq_rotate(d_vectors, n, D, d_R, d_out, (hipStream_t)hip_stream);
+    if (e != hipSuccess) return fail(DPQ_ERR_HIP, who + ": " + hipGetErrorString(e));
+    return DPQ_OK;
+    });
+}
+
+int dpq_rotate(const float* vectors, int64_t n, int D, const float* R, int device, float* out) {
+    return guarded([&]() -> int {
+    const std::string who = "dpq_rotate";
+    if (!vectors || !R || !out) return fail(DPQ_ERR_ARG, who + ": NULL argument");
+    if (n < 0) return fail(DPQ_ERR_ARG, who + ": n < 0");
+    if (int rc = opq_check_dim(who, D)) return rc;
+    if (out == vectors) return fail(DPQ_ERR_ARG, who + ": out must not alias vectors");
+    if (int rc = train_select_device(device)) return rc;
+    if (n == 0) return DPQ_OK;
+    const int64_t tile = std::min(n, dpq::kOpqSlice);
+    DevBuf<float> d_x, d_r, d_o;
+    int rc = d_x.alloc((size_t)tile * D);
+    if (!rc) rc = d_o.alloc((size_t)tile * D);
+    if (!rc) rc = d_r.alloc((size_t)D * D);
+    if (rc) return rc;
+    hipError_t e = hipMemcpy(d_r, R, (size_t)D * D * sizeof(float), hipMemcpyHostToDevice);
+    for (int64_t base = 0; base < n && e == hipSuccess; base += tile) {
+        const int64_t m = std::min(tile, n - base);
+        e = hipMemcpy(d_x, vectors + (size_t)base * D, (size_t)m * D * sizeof(float), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = dpq::launch_opq_rotate(d_x, m, D, d_r, d_o, nullptr);
+        if (e == hipSuccess) e = hipMemcpy(out + (size_t)base * D, d_o, (size_t)m * D * sizeof(float), hipMemcpyDeviceToHost);
+    }
+    if (e != hipSuccess) return fail(DPQ_ERR_HIP, who + ": " + hipGetErrorString(e));
+    return DPQ_OK;
+    });
+}
+
+int dpq_cross_covariance(const float* vectors, int64_t n, int D, const uint8_t* codes, const float* codewords, int M, int K,
+                         int Ds, int device, double* C_out) {
+    return guarded([&]() -> int {
+    const std::string who = "dpq_cross_covariance";
+    if (!vectors || !codes || !codewords || !C_out) return fail(DPQ_ERR_ARG, who + ": NULL argument");
+    if (n < 1) return fail(DPQ_ERR_ARG, who + ": n < 1");
+    if (int rc = opq_check_dim(who, D)) return rc;
+    if (M < 1 || M > 256 || K < 1 || K > 256 || Ds < 1) return fail(DPQ_ERR_ARG, who + ": M or K outside 1..256, or Ds < 1");
+    if ((int64_t)M * Ds != D) return fail(DPQ_ERR_ARG, who + ": D is not M * Ds");
+    if (K < 256)
+        for (int64_t i = 0; i < n * M; ++i)
+            if (codes[i] >= K) return fail(DPQ_ERR_ARG, who + ": a code byte is >= K");
+    if (int rc = train_select_device(device)) return rc;
+    const int64_t leaves = (n + dpq::kOpqLeaf - 1) / dpq::kOpqLeaf;
+    DevBuf<float> d_x, d_cw;
+    DevBuf<uint8_t> d_codes;
+    DevBuf<double> d_S, d_C;
+    int rc = d_x.alloc((size_t)n * D);
+    if (!rc) rc = d_codes.alloc((size_t)n * M);
+    if (!rc) rc = d_cw.alloc((size_t)M * K * Ds);
+    if (!rc) rc = d_S.alloc((size_t)std::min(leaves, dpq::opq_cross_leaves_per_pass(D)) * D * D);
+    if (!rc) rc = d_C.alloc((size_t)D * D);
+    if (rc) return rc;
+    DPQ_HIP(hipMemcpy(d_x, vectors, (size_t)n * D * sizeof(float), hipMemcpyHostToDevice));
+    DPQ_HIP(hipMemcpy(d_codes, codes, (size_t)n * M, hipMemcpyHostToDevice));
+    DPQ_HIP(hipMemcpy(d_cw, codewords, (size_t)M * K * Ds * sizeof(float), hipMemcpyHostToDevice));
+    DPQ_HIP(dpq::launch_opq_cross(d_x, n, D, d_codes, d_cw, M, K, Ds, d_S, d_C, nullptr));
+    DPQ_HIP(hipMemcpy(C_out, d_C, (size_t)D * D * sizeof(double), hipMemcpyDeviceToHost));
+    return DPQ_OK;
+    });
+}
+
+int dpq_procrustes(const double* C, int D, double* R_out, int32_t* degenerate) {
+    return guarded([&]() -> int {
+    const std::string who = "dpq_procrustes";
+    if (!C || !R_out || !degenerate) return fail(DPQ_ERR_ARG, who + ": NULL argument");
+    if (int rc = opq_check_dim(who, D)) return rc;
+    if (C == R_out) return fail(DPQ_ERR_ARG, who + ": R_out must not alias C");
+    int deg = 1;
+    dpq::procrustes(C, D, R_out, &deg, nullptr);
+    *degenerate = deg;
+    return DPQ_OK;
+    });
+}
+
+int dpq_write_rotation(const char* path, const float* R, int D) {
+    return guarded([&]() -> int {
+    const std::string who = "dpq_write_rotation";
+    if (!path || !R) return fail(DPQ_ERR_ARG, who + ": NULL argument");
+    if (int rc = opq_check_dim(who, D)) return rc;
+    FILE* f = fopen(path, "wb");
+    if (!f) return fail(DPQ_ERR_IO, std::string("cannot open ") + path);
+    const int32_t d32 = D;
+    bool ok = true;
+    for (int i = 0; i < D && ok; ++i)
+        ok = fwrite(&d32, 4, 1, f) == 1 && fwrite(R + (size_t)i * D, sizeof(float), (size_t)D, f) == (size_t)D;
+    if (fclose(f) != 0 || !ok) return fail(DPQ_ERR_IO, std::string("short write on ") + path);
+    return DPQ_OK;
+    });
+}
+
+int dpq_read_rotation(const char* path, int32_t* D, float* out) {
+    return guarded([&]() -> int {
+    const std::string who = "dpq_read_rotation";
+    if (!path || !D) return fail(DPQ_ERR_ARG, who + ": NULL argument");
+    FILE* f = fopen(path, "rb");
+    if (!f) return fail(DPQ_ERR_IO, std::string("cannot open ") + path);
+    int rc = DPQ_OK;
+    int32_t d32 = 0;
+    if (fread(&d32, 4, 1, f) != 1 || d32 < 1 || d32 > dpq::kOpqMaxD) {
+        rc = fail(DPQ_ERR_FORMAT, std::string(path) + ": not a rotation file (first dimension word outside 1..1024)");
+    } else {
+        fseek(f, 0, SEEK_END);
+        const long size = ftell(f);
+        if (size != (long)d32 * (4 + 4 * (long)d32))
+            rc = fail(DPQ_ERR_FORMAT, std::string(path) + ": not a square matrix of D rows (file size is not D * (4 + 4 D))");
+    }
+    if (!rc) {
+        *D = d32;
+        fseek(f, 0, SEEK_SET);
+        std::vector<float> row((size_t)d32);
+        for (int i = 0; i < d32 && !rc; ++i) {
+            int32_t h = 0;
+            if (fread(&h, 4, 1, f) != 1 || fread(row.data(), sizeof(float), (size_t)d32, f) != (size_t)d32)
+                rc = fail(DPQ_ERR_IO, std::string("short read on ") + path);
+            else if (h != d32)
+                rc = fail(DPQ_ERR_FORMAT, std::string(path) + ": a row's dimension word differs from the first");
+            else if (out)
+                memcpy(out + (size_t)i * d32, row.data(), (size_t)d32 * sizeof(float));
+        }
+    }
+    fclose(f);
+    return rc;
+    });
+}
+
+int dpq_opq_train(const float* vectors, int64_t n, int D, int M, int K, const dpq_opq_opts* opts, float* rotation,
+                  float* codewords, dpq_opq_stats* stats) {
+    return guarded([&]() -> int {
+    const std::string who = "dpq_opq_train";
+    const int device = opts ? opts->device : 0, outer = opts ? opts->outer_iters : 8;
+    const int init_iters = opts ? opts->init_iters : 25, inner_iters = opts ? opts->inner_iters : 4;
+    const int init = opts ? opts->init : 0, restarts = opts ? opts->restarts : 0;
+    const uint64_t seed = opts ? opts->seed : 0;
+    const bool use_rot = opts && opts->use_initial_rotation;
+    if (!vectors || !rotation || !codewords) return fail(DPQ_ERR_ARG, who + ": NULL argument");
+    if (int rc = opq_check_dim(who, D)) return rc;
+    if (M < 1 || D % M != 0) return fail(DPQ_ERR_ARG, who + ": D is not a multiple of M (pad the vectors and say so)");
+    if (outer < 0 || outer > 64) return fail(DPQ_ERR_ARG, who + ": outer_iters outside 0..64");
+    if (init_iters < 1 || init_iters > 64) return fail(DPQ_ERR_ARG, who + ": init_iters outside 1..64");
+    if (inner_iters < 1 || inner_iters > 64) return fail(DPQ_ERR_ARG, who + ": inner_iters outside 1..64");
+    if (init < 0 || init > 1) return fail(DPQ_ERR_ARG, who + ": init outside 0..1");
+    if (restarts < 0 || restarts > 16) return fail(DPQ_ERR_ARG, who + ": restarts outside 0..16");
+    if (int rc = train_check_shape("dpq_opq_train", n, D, M, K)) return rc;
+    if (int rc = train_select_device(device)) return rc;
+    using clock = std::chrono::steady_clock;
+    auto ms_since = [](clock::time_point t0) { return std::chrono::duration<double, std::milli>(clock::now() - t0).count(); };
+    const auto wall0 = clock::now();
+    const int Ds = D / M;
+    const size_t rot_n = (size_t)D * D, cb_n = (size_t)M * K * Ds;
+    dpq_opq_stats st{};
+    std::vector<float> R(rot_n, 0.0f), cb(cb_n), xr((size_t)n * D);
+    std::vector<double> pot((size_t)M), C(rot_n), R64(rot_n);
+    std::vector<uint8_t> codes((size_t)n * M);
+    if (use_rot)
+        memcpy(R.data(), rotation, rot_n * sizeof(float));
+    else
+        for (int i = 0; i < D; ++i) R[(size_t)i * D + i] = 1.0f;
+
+    auto add_train = [&](const dpq_train_stats& t) {
+        st.gpu_ms += t.gpu_ms;
+        st.rounds_ms += t.rounds_ms;
+        st.assign_ms += t.assign_ms;
+        st.update_ms += t.update_ms;
+        st.repair_ms += t.repair_ms;
+    };
+    auto rotate_now = [&]() -> int {
+        const auto t0 = clock::now();
+        const int rc = dpq_rotate(vectors, n, D, R.data(), device, xr.data());
+        st.rotate_ms += ms_since(t0);
+        return rc;
+    };
+    auto objective_now = [&](double* obj) -> int {
+        if (int rc = dpq_train_potential(xr.data(), n, D, cb.data(), M, K, Ds, device, pot.data())) return rc;
+        double s = 0.0;
+        for (int m = 0; m < M; ++m) s = s + pot[(size_t)m];
+        *obj = s;
+        return DPQ_OK;
+    };
+    double best = 0.0;
+    auto keep_if_best = [&](int t) {
+        if (t == 0 || st.objective[t] < best) {  // strict: a tie stays with the lower t
+            best = st.objective[t];
+            st.best_t = t;
+            memcpy(rotation, R.data(), rot_n * sizeof(float));
+            memcpy(codewords, cb.data(), cb_n * sizeof(float));
+        }
+    };
+
+    // t = 0 (the caller's rotation was copied above: `rotation` is free to collect the best pair from here on)
+    if (int rc = rotate_now()) return rc;
+    dpq_train_opts to{};
+    to.device = device;
+    to.max_iters = init_iters;
+    to.seed = seed;
+    to.init = init;
+    to.restarts = restarts;
+    dpq_train_stats ts{};
+    if (int rc = dpq_train_codebook(xr.data(), n, D, M, K, &to, cb.data(), &ts)) return rc;
+    add_train(ts);
+    if (int rc = objective_now(&st.objective[0])) return rc;
+    keep_if_best(0);
+
+    for (int t = 1; t <= outer; ++t) {
+        if (int rc = dpq_encode_pq(xr.data(), n, D, cb.data(), M, K, Ds, device, codes.data())) return rc;
+        auto t0 = clock::now();
+        if (int rc = dpq_cross_covariance(vectors, n, D, codes.data(), cb.data(), M, K, Ds, device, C.data())) return rc;
+        st.cross_ms += ms_since(t0);
+        t0 = clock::now();
+        int32_t deg = 0;
+        if (int rc = dpq_procrustes(C.data(), D, R64.data(), &deg)) return rc;
+        if (deg)
+            ++st.degenerate;
+        else
+            for (size_t e = 0; e < rot_n; ++e) R[e] = (float)R64[e];
+        st.rotation_residual[t - 1] = dpq::orthogonality_residual(R.data(), D);
+        st.procrustes_ms += ms_since(t0);
+        if (int rc = rotate_now()) return rc;
+        dpq_train_opts ti{};
+        ti.device = device;
+        ti.max_iters = inner_iters;
+        ti.use_initial = 1;
+        if (int rc = dpq_train_codebook(xr.data(), n, D, M, K, &ti, cb.data(), &ts)) return rc;
+        add_train(ts);
+        if (int rc = objective_now(&st.objective[t])) return rc;
+        keep_if_best(t);
+        st.outer_run = t;
+    }
+    st.wall_ms = ms_since(wall0);
+    if (stats) *stats = st;
     return DPQ_OK;
     });
 }

@@ -57,6 +57,30 @@ static int read_filter(const std::string& path, std::vector<uint32_t>* words, in
     return dpq_read_bitmap(path.c_str(), n_bits, words->data());
 }
 
+// -opq: the rows are replaced by rows . R on GPU 0 (dpq_rotate), R from M{M}K{K}rotation.fvecs beside the codewords.
+// A missing or unreadable file is an error that names the file.
+static int rotate_rows(const std::string& dataset, int M, int K, std::vector<float>* rows, int64_t n, int D) {
+    const std::string path = dataset + "/M" + std::to_string(M) + "K" + std::to_string(K) + "rotation.fvecs";
+    int32_t rD = 0;
+    int rc = dpq_read_rotation(path.c_str(), &rD, nullptr);
+    if (rc) {
+        std::cout << "-opq: cannot read the rotation file " << path << " (written by -task learn -opq T): " << dpq_strerror(rc)
+                  << ": " << dpq_last_error() << std::endl;
+        return 1;
+    }
+    if (rD != D) {
+        std::cout << "-opq: " << path << " is " << rD << " x " << rD << " but the vectors have " << D << " dimensions" << std::endl;
+        return 1;
+    }
+    std::vector<float> R((size_t)D * D), out((size_t)n * D);
+    rc = dpq_read_rotation(path.c_str(), &rD, R.data());
+    if (rc) return die("dpq_read_rotation", rc);
+    rc = dpq_rotate(rows->data(), n, D, R.data(), 0, out.data());
+    if (rc) return die("dpq_rotate", rc);
+    rows->swap(out);
+    return 0;
+}
+
 int main(int argc, char* argv[]) {
     std::string dataset, queryset, task = "approx_tree", ext = "fvecs", out_path, order = "dfs", filter_path, init = "rows";
     int query_size = -1, top_k = 1, diff_argument = 1, debug = 0, max_height_folds = 1, method = 1;
@@ -67,6 +91,8 @@ int main(int argc, char* argv[]) {
     unsigned long long seed = 0;
     int refine_m2 = 0, refine_k2 = 0, refine_r = 0;
     long long train_size = 0;
+    bool opq = false;
+    int opq_outer = 0, opq_init_iters = 25, opq_inner_iters = 4;
     for (int i = 0; i < argc; i++) {  // main:26-70: hand-rolled scan, no validation
         std::string arg = argv[i];
         const char* nx = i + 1 < argc ? argv[i + 1] : "";
@@ -96,8 +122,16 @@ int main(int argc, char* argv[]) {
         if (arg == "-k2") refine_k2 = atoi(nx);
         if (arg == "-refine") refine_r = atoi(nx);
         if (arg == "-train_size") train_size = atoll(nx);
+        if (arg == "-opq") opq = true, opq_outer = atoi(nx);  // learn: -opq T outer steps; elsewhere a bare flag
+        if (arg == "-opq_init_iters") opq_init_iters = atoi(nx);
+        if (arg == "-opq_inner_iters") opq_inner_iters = atoi(nx);
     }
     (void)diff_argument; (void)method; (void)queryset;
+    if (opq && (task == "refine" || (task == "recall" && refine_r != 0))) {
+        std::cout << "usage: -opq cannot be combined with -task refine or -refine R: a refine level over rotated codes is out of "
+                     "scope" << std::endl;
+        return 2;
+    }
 
     if (task == "learn") {
         // The other binary's `pqtree -task learn` (main.cpp:243-277): learn.{ext} -> M{M}K{K}codewords.txt.  The
@@ -106,7 +140,7 @@ int main(int argc, char* argv[]) {
         // -init rows|pp: K random rows or k-means++; -restarts R: the best of R runs per sub-space; -seed S.
         if (PQ_M <= 0 || PQ_K <= 0 || dataset.empty() || (init != "rows" && init != "pp")) {
             std::cout << "usage: deltapq -dataset DIR -task learn -m M -k K [-N TRAIN_SIZE] [-ext fvecs|bvecs] [-init rows|pp] "
-                         "[-restarts R] [-seed S]" << std::endl;
+                         "[-restarts R] [-seed S] [-opq T [-opq_init_iters A] [-opq_inner_iters B]]" << std::endl;
             return 2;
         }
         const std::string learn_path = dataset + "/learn." + ext;  // main.cpp:251
@@ -121,6 +155,34 @@ int main(int argc, char* argv[]) {
         if (rc) return die("ReadTopN", rc);
         const int Ds = (D + PQ_M - 1) / PQ_M;
         std::vector<float> codewords((size_t)PQ_M * PQ_K * Ds);
+        const std::string cw_path =
+            dataset + "/M" + std::to_string(PQ_M) + "K" + std::to_string(PQ_K) + "codewords.txt";  // main.cpp:273-275
+        if (opq) {
+            // -opq T: OPQ (dpq_opq_train): T outer steps around the trainer; the codebook is that of the rotated space and
+            // the rotation goes to M{M}K{K}rotation.fvecs beside it
+            std::vector<float> rotation((size_t)D * D);
+            dpq_opq_opts oo = {};
+            oo.outer_iters = opq_outer;
+            oo.init_iters = opq_init_iters;
+            oo.inner_iters = opq_inner_iters;
+            oo.seed = seed;
+            oo.init = init == "pp" ? 1 : 0;
+            oo.restarts = restarts;
+            dpq_opq_stats os;
+            rc = dpq_opq_train(learn.data(), n, D, PQ_M, PQ_K, &oo, rotation.data(), codewords.data(), &os);
+            if (rc) return die("learn -opq", rc);
+            for (int t = 0; t <= os.outer_run; ++t) std::cout << "outer step " << t << " objective " << os.objective[t] << std::endl;
+            const std::string rot_path =
+                dataset + "/M" + std::to_string(PQ_M) + "K" + std::to_string(PQ_K) + "rotation.fvecs";
+            rc = dpq_write_codewords(cw_path.c_str(), codewords.data(), PQ_M, PQ_K, Ds);
+            if (rc) return die("PQ::WriteCodewords", rc);
+            rc = dpq_write_rotation(rot_path.c_str(), rotation.data(), D);
+            if (rc) return die("dpq_write_rotation", rc);
+            std::cout << "learned OPQ M = " << PQ_M << " K = " << PQ_K << " Ds = " << Ds << " from " << n << " vectors: step "
+                      << os.best_t << " of " << os.outer_run << " kept, " << os.degenerate << " degenerate, " << os.wall_ms / 1000
+                      << " [sec] -> " << cw_path << ", " << rot_path << std::endl;
+            return 0;
+        }
         dpq_train_stats st;
         dpq_train_opts topts = {};
         topts.max_iters = 25;
@@ -130,8 +192,6 @@ int main(int argc, char* argv[]) {
         rc = dpq_train_codebook(learn.data(), n, D, PQ_M, PQ_K, &topts, codewords.data(), &st);
         if (rc) return die("learn", rc);
         for (int r = 0; r < st.iters_run; ++r) std::cout << "round " << r + 1 << " distortion " << st.distortion[r] << std::endl;
-        const std::string cw_path =
-            dataset + "/M" + std::to_string(PQ_M) + "K" + std::to_string(PQ_K) + "codewords.txt";  // main.cpp:273-275
         rc = dpq_write_codewords(cw_path.c_str(), codewords.data(), PQ_M, PQ_K, Ds);
         if (rc) return die("PQ::WriteCodewords", rc);
         std::cout << "learned M = " << PQ_M << " K = " << PQ_K << " Ds = " << Ds << " from " << n << " vectors in " << st.iters_run
@@ -143,7 +203,7 @@ int main(int argc, char* argv[]) {
         // The other binary's `pqtree -task encode` (main.cpp:314-425): base.{ext} -> PQ codes (nearest
         // codeword per sub-space, PQTree::EncodePlain pq_tree.cpp:215-237) -> codes.bin.plain.M{M}K{K}N{N}.
         if (PQ_M <= 0 || PQ_K <= 0 || dataset.empty()) {
-            std::cout << "usage: deltapq -dataset DIR -task encode -m M -k K [-N N] [-ext fvecs|bvecs]" << std::endl;
+            std::cout << "usage: deltapq -dataset DIR -task encode -m M -k K [-N N] [-ext fvecs|bvecs] [-opq]" << std::endl;
             return 2;
         }
         const std::string cw_path =
@@ -168,6 +228,7 @@ int main(int argc, char* argv[]) {
         std::vector<float> base((size_t)n * D);
         rc = dpq_read_vecs(base_path.c_str(), ext == "bvecs", &n_file, &D, base.data(), n);
         if (rc) return die("ItrReader", rc);
+        if (opq && rotate_rows(dataset, PQ_M, PQ_K, &base, n, D)) return 1;  // the codes are those of the rotated vectors
         const double t0 = Elapsed();
         std::vector<uint8_t> codes((size_t)n * PQ_M);
         rc = dpq_encode_pq(base.data(), n, D, codewords.data(), PQ_M, PQ_K, cDs, 0, codes.data());
@@ -496,7 +557,7 @@ int main(int argc, char* argv[]) {
         // against base.{ext} (main.cpp:898-939) and reports the recall of that answer too.
         if (PQ_M <= 0 || PQ_K <= 0 || dataset.empty() || N < 1 || !topk_given || top_k < 1 || query_size < 1) {
             std::cout << "usage: deltapq -dataset DIR -task recall -m M -k K -N N -query_size Q -topk K [-gt_topk G] [-rerank R]"
-                         " [-ext fvecs|bvecs] [-filter FILE] [-refine R [-m2 M2] [-k2 K2]]   (-refine: the level of -task refine,"
+                         " [-ext fvecs|bvecs] [-filter FILE] [-opq] [-refine R [-m2 M2] [-k2 K2]]   (-refine: the level of -task refine,"
                          " M <= 8)" << std::endl;
             return 2;
         }
@@ -548,6 +609,13 @@ int main(int argc, char* argv[]) {
             std::cout << "query dimension " << D << " != M*Ds = " << PQ_M * cDs << std::endl;
             return 1;
         }
+        // -opq: the PQ query sees rotated queries; ground truth and the exact re-rank keep the raw ones
+        std::vector<float> pq_queries_store;
+        if (opq) {
+            pq_queries_store = queries;
+            if (rotate_rows(dataset, PQ_M, PQ_K, &pq_queries_store, nq, D)) return 1;
+        }
+        const std::vector<float>& pq_queries = opq ? pq_queries_store : queries;
         const std::string gt_path = dataset + "/groundtruth/N" + std::to_string(N) + "Top" + std::to_string(gt_topk) +
                                     (filtered ? ".filtered.txt" : ".txt");
         int32_t g_nq = 0, g_k = 0;
@@ -597,7 +665,7 @@ int main(int argc, char* argv[]) {
         const double t0 = Elapsed();
         for (int q0 = 0; q0 < nq; q0 += 1024) {
             const int m = std::min(1024, nq - q0);
-            const float* qp = queries.data() + (size_t)q0 * D;
+            const float* qp = pq_queries.data() + (size_t)q0 * D;
             rc = filtered ? dpq_query_batch_filtered(idx, filt, qp, m, R, pos.data() + (size_t)q0 * R, pq_d.data() + (size_t)q0 * R)
                           : dpq_query_batch(idx, qp, m, R, pos.data() + (size_t)q0 * R, pq_d.data() + (size_t)q0 * R);
             if (rc) return die(filtered ? "dpq_query_batch_filtered" : "dpq_query_batch", rc);
@@ -724,7 +792,7 @@ int main(int argc, char* argv[]) {
     }
     if (PQ_M <= 0 || PQ_K <= 0 || dataset.empty()) {
         std::cout << "usage: deltapq -dataset DIR -task query -m M -k K -N N -query_size Q -topk K [-ext fvecs|bvecs]"
-                     " [-debug] [-gpus G] [-out FILE]" << std::endl;
+                     " [-debug] [-gpus G] [-out FILE] [-opq]" << std::endl;
         return 2;
     }
 
@@ -809,6 +877,7 @@ int main(int argc, char* argv[]) {
         std::cout << "no GPU visible: this build has no CPU query path" << std::endl;
         return 1;
     }
+    if (opq && rotate_rows(dataset, PQ_M, PQ_K, &queries, nq, D)) return 1;  // the index holds codes of rotated vectors
     if (gpus < 1) gpus = 1;
     if (gpus > ndev) {
         std::cout << "-gpus " << gpus << " but only " << ndev << " device(s) visible" << std::endl;

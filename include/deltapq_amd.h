@@ -846,6 +846,100 @@ int dpq_refine_rerank_device(dpq_refine* r, const float* d_queries, int nq, cons
 int dpq_query_batch_refined(dpq_index* idx, dpq_refine* r, const dpq_filter* filter, const float* queries, int nq,
                             int n_cand, int top_k, int32_t* ids, float* dists);
 
+/* ---- OPQ: a learned rotation in front of the product quantizer -----------------
+ * Non-parametric Optimized Product Quantization (Ge, He, Ke, Sun, CVPR 2013): an orthogonal R is learned together with
+ * the codebooks; vectors and queries are rotated (x . R) before they are encoded or looked up.  The index, the scans,
+ * the filters and the refine level are untouched: they hold codes of rotated vectors.  L2 distances do not see R, so
+ * exact search, ground truth and the exact re-rank keep the raw vectors.  NO REFERENCE SEMANTICS: the rules are this
+ * build's own, restated in tests/_opq_restatement.py and met by the GPU bit for bit.
+ *   Rotation   R is float [D][D], row-major, out = x . R.  out[i][j]: acc = +0.0 in fp64; for d = 0 .. D-1 ascending
+ *           acc = acc + (double)x[i][d] * (double)R[d][j]; out[i][j] = (float)acc.  The product of two fp32 values is
+ *           exact in fp64 (48 significant bits, exponent in range), so a fused multiply-add and a separate multiply and
+ *           add give the same bits; the kernel uses v_fma_f64.  Not allowed: fp32 accumulation, another dimension
+ *           order, a sum split across lanes.  1 <= D <= 1024.  out must not alias x (the same pointer: DPQ_ERR_ARG).
+ *           +inf from an overflowing final conversion is an ordinary value; NaN inputs are out of scope.
+ *   Cross-covariance   C[d][j] = sum over i of (double)x[i][d] * (double)y[i][j], double [D][D], where
+ *           y[i][j] = codewords[j / Ds][codes[i][j / Ds]][j % Ds] is the reconstruction (never materialised on the
+ *           host) and D = M * Ds.  Order, the trainer's leaf rule with a leaf of 1024 consecutive rows (the last may be
+ *           short): S_l is the fp64 sum, from +0.0, over the leaf's rows in ascending i, one add after the other;
+ *           T_0 = S_0, T_l = T_{l-1} + S_l; C = the last T.  No floating-point atomics.  A code byte >= K: DPQ_ERR_ARG.
+ *           Device memory: the inputs, plus at most 256 MiB of leaf sums (leaves are taken in passes of
+ *           max(1, 256 MiB / (8 D^2)), at most 65535, the chain running on through the passes).
+ *   Procrustes   dpq_procrustes returns, in fp64 on the host, the orthogonal polar factor U . V^T of C = U . S . V^T
+ *           by one-sided (Hestenes) Jacobi.  The library is built with -ffp-contract=off: every multiply and add below
+ *           is rounded on its own.
+ *             scale    A = C * 2^-e, e the binary exponent that brings the largest |C[i][j]| into [0.5, 1) (exact).
+ *                      V = the identity.
+ *             sweep    pairs (p, q), p < q, cyclic: p = 0 .. D-2 ascending, inside it q = p+1 .. D-1 ascending.
+ *                      alpha = sum_i A[i][p]^2, beta = sum_i A[i][q]^2, gamma = sum_i A[i][p] * A[i][q]: column sums in
+ *                      ascending row order from +0.0, of the columns as they are at that moment.  The pair is skipped
+ *                      when gamma * gamma <= (D * 2^-104) * alpha * beta.  Otherwise zeta = (beta - alpha) / (2 * gamma),
+ *                      t = (zeta >= 0 ? 1 : -1) / (|zeta| + sqrt(1 + zeta * zeta)), c = 1 / sqrt(1 + t * t), s = c * t,
+ *                      and for every row i of A and of V: (a, b) = (M[i][p], M[i][q]); M[i][p] = c * a - s * b;
+ *                      M[i][q] = s * a + c * b.
+ *             stop     after a sweep without a rotation, or after 64 sweeps.
+ *             answer   sigma_j = sqrt(sum_i A[i][j]^2); U[i][j] = A[i][j] / sigma_j; R[i][k] = the sum over j
+ *                      ascending, from +0.0, of U[i][j] * V[k][j].
+ *           *degenerate = 1 and R_out untouched when the smallest sigma is at or below D * 2^-52 times the largest, or
+ *           an entry of C (or a sigma) is not finite: the polar factor is not unique there.  The same input gives the
+ *           same bytes.  Needs no device.
+ *   Training   dpq_opq_train is BY DEFINITION this composition of the public calls, byte for byte.  D % M == 0 (else
+ *           DPQ_ERR_ARG: zero padding makes C singular; a caller pads the vectors and says so), Ds = D / M.
+ *             t = 0    R_0 = the identity, or the caller's matrix (use_initial_rotation); X^ = dpq_rotate(X, R_0);
+ *                      cb_0 = dpq_train_codebook(X^; max_iters = init_iters, seed, init, restarts);
+ *                      obj_0 = the sum over m ascending, in fp64 from +0.0, of dpq_train_potential(X^, cb_0)[m].
+ *             t = 1 .. outer_iters   codes = dpq_encode_pq(X^, cb_{t-1}); C = dpq_cross_covariance(X -- not X^ --,
+ *                      codes, cb_{t-1}); R64 = dpq_procrustes(C); R_t = (float)R64 entry by entry, or R_{t-1} when
+ *                      degenerate (counted in the stats); X^ = dpq_rotate(X, R_t); cb_t = dpq_train_codebook(X^;
+ *                      use_initial = cb_{t-1}, max_iters = inner_iters, init = 0, restarts = 0); obj_t as above.
+ *           Returned: the pair (R_t, cb_t) with the lowest obj_t, a tie going to the lowest t.  So outer_iters = 0 with
+ *           the identity returns dpq_train_codebook's bytes, and the result is never worse than its own start by its
+ *           own measure.  opts == NULL: device 0, 8 outer steps, 25 first rounds, 4 inner rounds, seed 0, random rows.
+ * DPQ_ERR_ARG before any device call: a NULL pointer, D outside 1..1024, n < 0 (n < 1 for the cross-covariance),
+ * D != M * Ds, D % M != 0, outer_iters outside 0..64, init_iters or inner_iters outside 1..64, and what
+ * dpq_train_codebook refuses.  Without a GPU: DPQ_ERR_NO_DEVICE, except dpq_procrustes, dpq_write_rotation and
+ * dpq_read_rotation, which need none. */
+typedef struct dpq_opq_opts {
+    int32_t device;
+    int32_t outer_iters;          /* 0..64 */
+    int32_t init_iters;           /* 1..64: rounds of the first training */
+    int32_t inner_iters;          /* 1..64: rounds of every later one */
+    uint64_t seed;                /* seed, init, restarts: handed to the first dpq_train_codebook */
+    int32_t init;
+    int32_t restarts;
+    int32_t use_initial_rotation; /* != 0: `rotation` holds R_0 on entry */
+    int32_t reserved[1];          /* 0 */
+} dpq_opq_opts;
+
+typedef struct dpq_opq_stats {
+    int32_t outer_run;             /* outer steps run */
+    int32_t best_t;                /* the step whose pair was returned */
+    int32_t degenerate;            /* steps whose Procrustes solve was degenerate (the rotation was kept) */
+    int32_t reserved;
+    double objective[65];          /* obj_t, t = 0 .. outer_run */
+    double rotation_residual[64];  /* max |R_t^T R_t - I|, t = 1 .. outer_run at [t - 1]; fp64 on the host */
+    double gpu_ms, wall_ms, rounds_ms, assign_ms, update_ms, repair_ms; /* the trainer's, summed; wall_ms: this call */
+    double rotate_ms, cross_ms, procrustes_ms; /* host clock around those calls (transfers included) */
+} dpq_opq_stats;
+
+/* Host buffers; slices of at most 2^20 rows, so device memory stays bounded whatever n. */
+int dpq_rotate(const float* vectors, int64_t n, int D, const float* R, int device, float* out);
+/* Device pointers on the current device; enqueued on `hip_stream` (NULL = default stream) and nothing else: no host
+ * round trip, no allocation, no synchronisation.  The call a query loop puts in front of dpq_query_batch_device*. */
+int dpq_rotate_device(const float* d_vectors, int64_t n, int D, const float* d_R, float* d_out, void* hip_stream);
+/* Host buffers: vectors float [n][D], codes uint8 [n][M], codewords float [M][K][Ds]; C_out double [D][D]. */
+int dpq_cross_covariance(const float* vectors, int64_t n, int D, const uint8_t* codes, const float* codewords, int M, int K,
+                         int Ds, int device, double* C_out);
+int dpq_procrustes(const double* C, int D, double* R_out, int32_t* degenerate);
+/* rotation: float [D][D], in (use_initial_rotation) and out; codewords: float [M][K][D / M] out; stats may be NULL. */
+int dpq_opq_train(const float* vectors, int64_t n, int D, int M, int K, const dpq_opq_opts* opts, float* rotation,
+                  float* codewords, dpq_opq_stats* stats);
+/* The rotation file: the .fvecs layout, D rows of (int32 D, D floats), so dpq_read_vecs reads it too.  By convention
+ * M{M}K{K}rotation.fvecs beside M{M}K{K}codewords.txt.  dpq_read_rotation: out == NULL only reports *D; a file that is
+ * truncated, not square or above D = 1024 is DPQ_ERR_FORMAT. */
+int dpq_write_rotation(const char* path, const float* R, int D);
+int dpq_read_rotation(const char* path, int32_t* D, float* out);
+
 /* ---- measurement -------------------------------------------------------- */
 int dpq_profile_enable(dpq_index* idx, int on);  /* 0 off, 1 every kernel, 2 scan launches only (less event overhead) */
 int dpq_profile_reset(dpq_index* idx);
