@@ -2323,15 +2323,6 @@ int dpq_write_codewords(const char* path, const float* codewords, int M, int K, 
 
 namespace {
 
-template <class B>
-int grow(B& buf, size_t* have, size_t want) {
-    if (want <= *have) return DPQ_OK;
-    *have = 0;
-    int rc = buf.alloc(want);
-    if (!rc) *have = want;
-    return rc;
-}
-
 // Candidates of dpq_flat_rerank*, all device pointers; ends with one flag word read back.
 template <class Q>
 int flat_rerank_on_device(const char* fn, dpq_flat* f, const Q* d_queries, int nq, const int32_t* d_cand, int n_cand,
@@ -2379,14 +2370,6 @@ int flat_rerank_args(const char* fn, const char* other, const dpq_flat* f, bool 
     return DPQ_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-}  // extern "C"
-
-namespace {
-
 // The checks of dpq_flat_open / dpq_flat_open_u8: the arguments before any device call, then the device.
 int flat_open_args(const char* fn, const void* vectors, int64_t n, int D, int device, int64_t id_offset, dpq_flat** out) {
     const std::string who(fn);
@@ -2411,6 +2394,79 @@ int grow_outputs(dpq_flat* f, size_t want) {
     if (!rc) rc = f->d_dists.alloc(want);
     if (!rc) f->out_n = want;
     return rc;
+}
+
+// Uploads m queries as the distance kernels read them: fp32 rows padded to Dp, or bytes biased and padded with norms.
+template <class Q>
+int flat_stage_queries(dpq_flat* f, const Q* src, int m, std::vector<float>* padded) {
+    const int D = f->D, Dp = f->Dp;
+    if constexpr (std::is_same<Q, uint8_t>::value) {
+        DPQ_HIP(hipMemcpy(f->q_raw, src, (size_t)m * D, hipMemcpyHostToDevice));
+        DPQ_HIP(dpq::launch_flat_u8_prepare(f->q_raw, m, D, Dp, f->q8, f->qnorm, nullptr));
+    } else {
+        if (Dp != D) {
+            padded->assign((size_t)m * Dp, 0.0f);
+            for (int q = 0; q < m; ++q) memcpy(&(*padded)[(size_t)q * Dp], src + (size_t)q * D, (size_t)D * sizeof(float));
+            src = padded->data();
+        }
+        DPQ_HIP(hipMemcpy(f->d_q, src, (size_t)m * Dp * sizeof(float), hipMemcpyHostToDevice));
+    }
+    return DPQ_OK;
+}
+
+template <class Q>
+int flat_grow_queries(dpq_flat* f, size_t qb) {
+    if constexpr (std::is_same<Q, uint8_t>::value) {
+        int rc = grow(f->q_raw, &f->q_raw_n, qb * f->D);
+        if (!rc) rc = grow(f->q8, &f->q8_n, qb * f->Dp);
+        if (!rc) rc = grow(f->qnorm, &f->qnorm_n, qb);
+        return rc;
+    } else {
+        return grow(f->d_q, &f->q_n, qb * f->Dp);
+    }
+}
+
+// The handle's rows, all of them or those a filter lists, and queries [a, a + m) of the staged batch, as the launchers
+// of dpq_flat.h take them.
+dpq::FlatBase flat_base(const dpq_flat* f, const dpq_flat_filter* ff) {
+    return {f->base, f->base8, f->norm8, f->Dp, f->id_offset, ff != nullptr, ff ? ff->list.get() : nullptr,
+            ff ? ff->n_allowed : f->n};
+}
+
+dpq::FlatQueries flat_queries(const dpq_flat* f, int a, int m) {
+    if (f->u8) return {nullptr, f->q8.get() + (size_t)a * f->Dp, f->qnorm.get() + a, m};
+    return {f->d_q.get() + (size_t)a * f->Dp, nullptr, nullptr, m};
+}
+
+// What dpq_flat_search[_u8] and dpq_flat_search_filtered[_u8] share once their arguments are checked: the buffers, the
+// batches of staged queries, the copies down and the check of every query's state.  ff NULL: all rows, top_k <= n.
+template <class Q>
+int flat_search_run(const std::string& who, dpq_flat* f, const dpq_flat_filter* ff, const Q* queries, int nq, int top_k,
+                    int32_t* ids, float* dists) {
+    if (nq == 0) return DPQ_OK;
+    DPQ_HIP(hipSetDevice(f->device));
+    const int qb = std::min(nq, dpq::flat_query_batch(top_k));
+    int rc = grow(f->keys, &f->keys_n, (size_t)qb * dpq::flat_key_capacity(top_k));
+    if (!rc) rc = grow(f->state, &f->state_n, (size_t)qb);
+    if (!rc) rc = flat_grow_queries<Q>(f, (size_t)qb);
+    if (!rc) rc = grow_outputs(f, (size_t)qb * top_k);
+    if (rc) return rc;
+    const dpq::FlatBase base = flat_base(f, ff);
+    const uint32_t expect = (uint32_t)std::min<int64_t>(top_k, base.n_entries);
+    std::vector<float> padded;
+    std::vector<dpq::FlatQueryState> st((size_t)qb);
+    for (int q0 = 0; q0 < nq; q0 += qb) {
+        const int m = std::min(qb, nq - q0);
+        if ((rc = flat_stage_queries(f, queries + (size_t)q0 * f->D, m, &padded))) return rc;
+        DPQ_HIP(dpq::launch_flat_search(base, flat_queries(f, 0, m), top_k, f->keys, f->state, f->d_ids, f->d_dists, nullptr));
+        DPQ_HIP(hipMemcpy(ids + (size_t)q0 * top_k, f->d_ids, (size_t)m * top_k * sizeof(int32_t), hipMemcpyDeviceToHost));
+        DPQ_HIP(hipMemcpy(dists + (size_t)q0 * top_k, f->d_dists, (size_t)m * top_k * sizeof(float), hipMemcpyDeviceToHost));
+        DPQ_HIP(hipMemcpy(st.data(), f->state, (size_t)m * sizeof(dpq::FlatQueryState), hipMemcpyDeviceToHost));
+        for (int q = 0; q < m; ++q)
+            if (st[(size_t)q].overflow || st[(size_t)q].count != expect)
+                return fail(DPQ_ERR_STATE, who + ": internal error: a key buffer overflowed");
+    }
+    return DPQ_OK;
 }
 
 }  // namespace
@@ -2491,41 +2547,7 @@ int dpq_flat_search(dpq_flat* f, const float* queries, int nq, int top_k, int32_
     if (top_k < 1 || top_k > DPQ_FLAT_MAX_TOPK) return fail(DPQ_ERR_ARG, "dpq_flat_search: top_k outside 1..DPQ_FLAT_MAX_TOPK");
     if (int rc = flat_kind(f, false, "dpq_flat_search", "dpq_flat_search_u8")) return rc;
     if (top_k > f->n) return fail(DPQ_ERR_TOPK, "dpq_flat_search: top_k exceeds the number of vectors");
-    if (nq == 0) return DPQ_OK;
-    DPQ_HIP(hipSetDevice(f->device));
-    const int D = f->D, Dp = f->Dp;
-    const int qb = std::min(nq, dpq::flat_query_batch(top_k));
-    int rc = grow(f->keys, &f->keys_n, (size_t)qb * dpq::flat_key_capacity(top_k));
-    if (!rc) rc = grow(f->state, &f->state_n, (size_t)qb);
-    if (!rc) rc = grow(f->d_q, &f->q_n, (size_t)qb * Dp);
-    if (!rc && f->out_n < (size_t)qb * top_k) {
-        f->out_n = 0;
-        rc = f->d_ids.alloc((size_t)qb * top_k);
-        if (!rc) rc = f->d_dists.alloc((size_t)qb * top_k);
-        if (!rc) f->out_n = (size_t)qb * top_k;
-    }
-    if (rc) return rc;
-    std::vector<float> padded;
-    std::vector<dpq::FlatQueryState> st((size_t)qb);
-    for (int q0 = 0; q0 < nq; q0 += qb) {
-        const int m = std::min(qb, nq - q0);
-        const float* src = queries + (size_t)q0 * D;
-        if (Dp != D) {
-            padded.assign((size_t)m * Dp, 0.0f);
-            for (int q = 0; q < m; ++q) memcpy(&padded[(size_t)q * Dp], src + (size_t)q * D, (size_t)D * sizeof(float));
-            src = padded.data();
-        }
-        DPQ_HIP(hipMemcpy(f->d_q, src, (size_t)m * Dp * sizeof(float), hipMemcpyHostToDevice));
-        DPQ_HIP(dpq::launch_flat_search(f->base, f->n, Dp, f->d_q, m, top_k, f->id_offset, f->keys, f->state, f->d_ids,
-                                        f->d_dists, nullptr));
-        DPQ_HIP(hipMemcpy(ids + (size_t)q0 * top_k, f->d_ids, (size_t)m * top_k * sizeof(int32_t), hipMemcpyDeviceToHost));
-        DPQ_HIP(hipMemcpy(dists + (size_t)q0 * top_k, f->d_dists, (size_t)m * top_k * sizeof(float), hipMemcpyDeviceToHost));
-        DPQ_HIP(hipMemcpy(st.data(), f->state, (size_t)m * sizeof(dpq::FlatQueryState), hipMemcpyDeviceToHost));
-        for (int q = 0; q < m; ++q)
-            if (st[(size_t)q].overflow || st[(size_t)q].count != (uint32_t)top_k)
-                return fail(DPQ_ERR_STATE, "dpq_flat_search: internal error: a key buffer overflowed");
-    }
-    return DPQ_OK;
+    return flat_search_run("dpq_flat_search", f, nullptr, queries, nq, top_k, ids, dists);
     });
 }
 
@@ -2536,32 +2558,7 @@ int dpq_flat_search_u8(dpq_flat* f, const uint8_t* queries, int nq, int top_k, i
         return fail(DPQ_ERR_ARG, "dpq_flat_search_u8: top_k outside 1..DPQ_FLAT_MAX_TOPK");
     if (int rc = flat_kind(f, true, "dpq_flat_search_u8", "dpq_flat_search")) return rc;
     if (top_k > f->n) return fail(DPQ_ERR_TOPK, "dpq_flat_search_u8: top_k exceeds the number of vectors");
-    if (nq == 0) return DPQ_OK;
-    DPQ_HIP(hipSetDevice(f->device));
-    const int D = f->D, Dp = f->Dp;
-    const int qb = std::min(nq, dpq::flat_query_batch(top_k));
-    int rc = grow(f->keys, &f->keys_n, (size_t)qb * dpq::flat_key_capacity(top_k));
-    if (!rc) rc = grow(f->state, &f->state_n, (size_t)qb);
-    if (!rc) rc = grow(f->q_raw, &f->q_raw_n, (size_t)qb * D);
-    if (!rc) rc = grow(f->q8, &f->q8_n, (size_t)qb * Dp);
-    if (!rc) rc = grow(f->qnorm, &f->qnorm_n, (size_t)qb);
-    if (!rc) rc = grow_outputs(f, (size_t)qb * top_k);
-    if (rc) return rc;
-    std::vector<dpq::FlatQueryState> st((size_t)qb);
-    for (int q0 = 0; q0 < nq; q0 += qb) {
-        const int m = std::min(qb, nq - q0);
-        DPQ_HIP(hipMemcpy(f->q_raw, queries + (size_t)q0 * D, (size_t)m * D, hipMemcpyHostToDevice));
-        DPQ_HIP(dpq::launch_flat_u8_prepare(f->q_raw, m, D, Dp, f->q8, f->qnorm, nullptr));
-        DPQ_HIP(dpq::launch_flat_search_u8(f->base8, f->norm8, f->n, Dp, f->q8, f->qnorm, m, top_k, f->id_offset, f->keys,
-                                           f->state, f->d_ids, f->d_dists, nullptr));
-        DPQ_HIP(hipMemcpy(ids + (size_t)q0 * top_k, f->d_ids, (size_t)m * top_k * sizeof(int32_t), hipMemcpyDeviceToHost));
-        DPQ_HIP(hipMemcpy(dists + (size_t)q0 * top_k, f->d_dists, (size_t)m * top_k * sizeof(float), hipMemcpyDeviceToHost));
-        DPQ_HIP(hipMemcpy(st.data(), f->state, (size_t)m * sizeof(dpq::FlatQueryState), hipMemcpyDeviceToHost));
-        for (int q = 0; q < m; ++q)
-            if (st[(size_t)q].overflow || st[(size_t)q].count != (uint32_t)top_k)
-                return fail(DPQ_ERR_STATE, "dpq_flat_search_u8: internal error: a key buffer overflowed");
-    }
-    return DPQ_OK;
+    return flat_search_run("dpq_flat_search_u8", f, nullptr, queries, nq, top_k, ids, dists);
     });
 }
 
@@ -2614,36 +2611,6 @@ int flat_filter_owner(const dpq_flat* f, const dpq_flat_filter* ff, const std::s
     return fail(DPQ_ERR_ARG, who + ": the filter was made for another handle");
 }
 
-// Uploads m queries as the distance kernels read them: fp32 rows padded to Dp, or bytes biased and padded with norms.
-template <class Q>
-int flat_stage_queries(dpq_flat* f, const Q* src, int m, std::vector<float>* padded) {
-    const int D = f->D, Dp = f->Dp;
-    if constexpr (std::is_same<Q, uint8_t>::value) {
-        DPQ_HIP(hipMemcpy(f->q_raw, src, (size_t)m * D, hipMemcpyHostToDevice));
-        DPQ_HIP(dpq::launch_flat_u8_prepare(f->q_raw, m, D, Dp, f->q8, f->qnorm, nullptr));
-    } else {
-        if (Dp != D) {
-            padded->assign((size_t)m * Dp, 0.0f);
-            for (int q = 0; q < m; ++q) memcpy(&(*padded)[(size_t)q * Dp], src + (size_t)q * D, (size_t)D * sizeof(float));
-            src = padded->data();
-        }
-        DPQ_HIP(hipMemcpy(f->d_q, src, (size_t)m * Dp * sizeof(float), hipMemcpyHostToDevice));
-    }
-    return DPQ_OK;
-}
-
-template <class Q>
-int flat_grow_queries(dpq_flat* f, size_t qb) {
-    if constexpr (std::is_same<Q, uint8_t>::value) {
-        int rc = grow(f->q_raw, &f->q_raw_n, qb * f->D);
-        if (!rc) rc = grow(f->q8, &f->q8_n, qb * f->Dp);
-        if (!rc) rc = grow(f->qnorm, &f->qnorm_n, qb);
-        return rc;
-    } else {
-        return grow(f->d_q, &f->q_n, qb * f->Dp);
-    }
-}
-
 // dpq_flat_search_filtered / _u8: Q is float or uint8_t, the handle of the same kind.
 template <class Q>
 int flat_search_filtered_call(const char* fn, const char* other, dpq_flat* f, const dpq_flat_filter* ff, const Q* queries,
@@ -2656,49 +2623,14 @@ int flat_search_filtered_call(const char* fn, const char* other, dpq_flat* f, co
     if (int rc = flat_device_present(who)) return rc;
     if (int rc = flat_kind(f, u8, fn, other)) return rc;
     if (int rc = flat_filter_owner(f, ff, who)) return rc;
-    if (nq == 0) return DPQ_OK;
-    DPQ_HIP(hipSetDevice(f->device));
-    const int qb = std::min(nq, dpq::flat_query_batch(top_k));
-    int rc = grow(f->keys, &f->keys_n, (size_t)qb * dpq::flat_key_capacity(top_k));
-    if (!rc) rc = grow(f->state, &f->state_n, (size_t)qb);
-    if (!rc) rc = flat_grow_queries<Q>(f, (size_t)qb);
-    if (!rc) rc = grow_outputs(f, (size_t)qb * top_k);
-    if (rc) return rc;
-    const uint32_t expect = (uint32_t)std::min<int64_t>(top_k, ff->n_allowed);
-    std::vector<float> padded;
-    std::vector<dpq::FlatQueryState> st((size_t)qb);
-    for (int q0 = 0; q0 < nq; q0 += qb) {
-        const int m = std::min(qb, nq - q0);
-        if ((rc = flat_stage_queries(f, queries + (size_t)q0 * f->D, m, &padded))) return rc;
-        if constexpr (u8)
-            DPQ_HIP(dpq::launch_flat_search_list_u8(f->base8, f->norm8, ff->list, ff->n_allowed, f->Dp, f->q8, f->qnorm, m, top_k,
-                                                    f->id_offset, f->keys, f->state, f->d_ids, f->d_dists, nullptr));
-        else
-            DPQ_HIP(dpq::launch_flat_search_list(f->base, ff->list, ff->n_allowed, f->Dp, f->d_q, m, top_k, f->id_offset, f->keys,
-                                                 f->state, f->d_ids, f->d_dists, nullptr));
-        DPQ_HIP(hipMemcpy(ids + (size_t)q0 * top_k, f->d_ids, (size_t)m * top_k * sizeof(int32_t), hipMemcpyDeviceToHost));
-        DPQ_HIP(hipMemcpy(dists + (size_t)q0 * top_k, f->d_dists, (size_t)m * top_k * sizeof(float), hipMemcpyDeviceToHost));
-        DPQ_HIP(hipMemcpy(st.data(), f->state, (size_t)m * sizeof(dpq::FlatQueryState), hipMemcpyDeviceToHost));
-        for (int q = 0; q < m; ++q)
-            if (st[(size_t)q].overflow || st[(size_t)q].count != expect)
-                return fail(DPQ_ERR_STATE, who + ": internal error: a key buffer overflowed");
-    }
-    return DPQ_OK;
+    return flat_search_run(who, f, ff, queries, nq, top_k, ids, dists);
 }
 
 // One distance pass of a range search over queries [a, a + m) of the staged batch: counting (pool NULL) or emitting.
-template <class Q>
 int flat_range_pass(dpq_flat* f, const dpq_flat_filter* ff, int a, int m, uint64_t* pool) {
-    const uint32_t* list = ff ? ff->list.get() : nullptr;
-    const int64_t n_entries = ff ? ff->n_allowed : f->n;
-    DPQ_HIP(dpq::launch_flat_range_state(f->state.get() + a, f->r_thr.get() + a, m, nullptr));
-    if constexpr (std::is_same<Q, uint8_t>::value)
-        DPQ_HIP(dpq::launch_flat_range_pass_u8(f->base8, f->norm8, list, n_entries, f->Dp, f->q8.get() + (size_t)a * f->Dp,
-                                               f->qnorm.get() + a, m, f->id_offset, pool, f->r_offs, f->state.get() + a,
-                                               nullptr));
-    else
-        DPQ_HIP(dpq::launch_flat_range_pass(f->base, list, n_entries, f->Dp, f->d_q.get() + (size_t)a * f->Dp, m, f->id_offset,
-                                            pool, f->r_offs, f->state.get() + a, nullptr));
+    dpq::FlatQueryState* state = f->state.get() + a;
+    DPQ_HIP(dpq::launch_flat_range_state(state, f->r_thr.get() + a, m, nullptr));
+    DPQ_HIP(dpq::launch_flat_range_pass(flat_base(f, ff), flat_queries(f, a, m), pool, f->r_offs, state, nullptr));
     return DPQ_OK;
 }
 
@@ -2747,7 +2679,7 @@ int flat_range_call(const char* fn, const char* other, dpq_flat* f, const dpq_fl
             thr[(size_t)q] = (uint64_t)bits << 32;
         }
         DPQ_HIP(hipMemcpy(f->r_thr, thr.data(), (size_t)m * sizeof(uint64_t), hipMemcpyHostToDevice));
-        if ((rc = flat_range_pass<Q>(f, ff, 0, m, nullptr))) break;
+        if ((rc = flat_range_pass(f, ff, 0, m, nullptr))) break;
         DPQ_HIP(hipMemcpy(st.data(), f->state, (size_t)m * sizeof(dpq::FlatQueryState), hipMemcpyDeviceToHost));
         for (int q = 0; q < m; ++q) res->lims[(size_t)q0 + q + 1] = res->lims[(size_t)q0 + q] + st[(size_t)q].count;
         res->ids.resize((size_t)res->lims[(size_t)q0 + m]);
@@ -2762,7 +2694,7 @@ int flat_range_call(const char* fn, const char* other, dpq_flat* f, const dpq_fl
                 if ((rc = grow(f->r_pool, &f->r_pool_n, (size_t)std::max(sum, kFlatRangePoolKeys)))) break;
                 if ((rc = grow(f->r_sorted, &f->r_sorted_n, f->r_pool_n))) break;
                 DPQ_HIP(hipMemcpy(f->r_offs, offs.data(), offs.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-                if ((rc = flat_range_pass<Q>(f, ff, a, b - a, f->r_pool))) break;
+                if ((rc = flat_range_pass(f, ff, a, b - a, f->r_pool))) break;
                 size_t tb = 0;
                 DPQ_HIP(dpq::flat_range_sort(nullptr, &tb, f->r_pool, f->r_sorted, sum, b - a, f->r_offs, nullptr));
                 DevBuf<uint8_t> temp;  // the segmented sort's workspace

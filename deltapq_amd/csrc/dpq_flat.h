@@ -1,6 +1,9 @@
 // dpq_flat.h -- exact L2 search over raw vectors on the GPU: fp32 (dpq_flat.hip) and bytes on the int8 matrix cores
-// (dpq_flat_u8.hip); ground truth over a whole base, re-ranking over a candidate list per query.  The arithmetic is
-// the reference's brute force (main.cpp:150-156), restated in include/deltapq_amd.h and DESIGN.md 5.10.
+// (dpq_flat_u8.hip); top-k over a whole base or over the rows a filter lists, range search, re-ranking over a candidate
+// list per query.  The arithmetic is the reference's brute force (main.cpp:150-156), restated in include/deltapq_amd.h
+// and DESIGN.md 5.10.  Each element type has one distance kernel template <LIST, MODE> in its own file; one stripe
+// driver (launch_flat_search) and one range pass (launch_flat_range_pass) serve both types, with and without a filter.
+// What the kernels of the two files share -- the modes, the key sink, the padding key -- is defined here, once.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -27,12 +30,51 @@ int flat_key_capacity(int top_k);
 // Queries one search pass takes (their key buffers together stay within 64 MB).
 int flat_query_batch(int top_k);
 
-// Exact top_k of nq (<= flat_query_batch(top_k)) queries over n rows, all device pointers.  d_base [n][Dp],
-// d_queries [nq][Dp] (padded rows), d_keys [nq][flat_key_capacity(top_k)], d_state [nq].  Reported id = row + id_offset.
-// Enqueues on `stream`; d_state[q].overflow must be read back afterwards.
-hipError_t launch_flat_search(const float* d_base, int64_t n, int Dp, const float* d_queries, int nq, int top_k,
-                              int64_t id_offset, uint64_t* d_keys, FlatQueryState* d_state, int32_t* d_ids, float* d_dists,
-                              hipStream_t stream);
+// ---- what a search or a range pass runs over ---------------------------------------------------------------------------
+// A prepared base: fp32 rows [n][Dp] padded with zeros (f32), or biased int8 rows [n][Dp] with their int32 norms (i8,
+// norm; see "byte vectors" below) -- exactly one of f32 / i8 is set.  The entries a pass visits are rows
+// 0 .. n_entries - 1, or, with `filtered`, rows list[0 .. n_entries - 1] (ascending).  `filtered`, not the list pointer,
+// says which: an empty filter has n_entries == 0 and may have a NULL list.  Reported id = row + id_offset.
+struct FlatBase {
+    const float* f32;
+    const int8_t* i8;
+    const int32_t* norm;
+    int Dp;
+    int64_t id_offset;
+    bool filtered;
+    const uint32_t* list;
+    int64_t n_entries;
+};
+// Prepared queries of the base's kind: [nq][Dp] padded rows, with norms for bytes.
+struct FlatQueries {
+    const float* f32;
+    const int8_t* i8;
+    const int32_t* norm;
+    int nq;
+};
+
+// What a distance kernel does with a key (its MODE): at or below the query's threshold it is appended to the query's
+// buffer keys[q][cap]; below the radius key it is counted; below the radius key it is appended to the query's list
+// keys[offs[q] .. offs[q + 1]).
+enum { kFlatTopK = 0, kFlatCount = 1, kFlatEmit = 2 };
+constexpr uint64_t kFlatNoKey = ~0ull;  // padding in a key buffer; the threshold that lets every key pass
+
+// Where the keys of query q go and how many fit.
+template <int MODE>
+__device__ __forceinline__ uint64_t* flat_sink_of(uint64_t* keys, int cap, const int64_t* offs, int q, uint32_t* room) {
+    if (MODE == kFlatEmit) {
+        *room = (uint32_t)(offs[q + 1] - offs[q]);
+        return keys + offs[q];
+    }
+    *room = (uint32_t)cap;
+    return keys + (size_t)q * cap;
+}
+
+// Exact top_k of q.nq (<= flat_query_batch(top_k)) queries over the base's entries, all device pointers.
+// d_keys [nq][flat_key_capacity(top_k)], d_state [nq].  Fewer than top_k entries (a filter): rows are padded with
+// -1 / +inf.  Enqueues on `stream`; d_state[q].overflow and .count must be read back afterwards.
+hipError_t launch_flat_search(const FlatBase& b, const FlatQueries& q, int top_k, uint64_t* d_keys, FlatQueryState* d_state,
+                              int32_t* d_ids, float* d_dists, hipStream_t stream);
 
 // Exact distances of cand[nq][n_cand] only, best top_k by (distance, reported id).  d_map (may be NULL) [n_map]: a
 // candidate is a DFS position, row = map[c], with the even-N rule; without it row = c - id_offset.  d_queries [nq][D]
@@ -46,13 +88,8 @@ size_t flat_rerank_keys(int n_cand);  // keys per query launch_flat_rerank needs
 // [rows][D] -> [rows][Dp] with zero padding, on the device.
 hipError_t launch_flat_pad_rows(const float* d_in, int64_t rows, int D, int Dp, float* d_out, hipStream_t stream);
 
-// The stages of a search that do not depend on how distances are formed, for dpq_flat_u8.hip: the kernels of
-// launch_flat_search / launch_flat_rerank, launched one at a time.
-hipError_t launch_flat_init_state(FlatQueryState* d_state, int nq, hipStream_t stream);
-// Every buffer above `limit` (>= top_k) keys is cut down to its top_k smallest and its threshold lowered.
-hipError_t launch_flat_select(uint64_t* d_keys, int cap, FlatQueryState* d_state, int nq, int top_k, uint32_t limit,
-                              hipStream_t stream);
-// Sorts n_keys keys per query (d_state[q].count of them when d_state is given), drops repeats, writes top_k.
+// The last stage of a search or a re-rank, for dpq_flat_u8.hip: sorts n_keys keys per query (d_state[q].count of them
+// when d_state is given), drops repeats, writes top_k.
 hipError_t launch_flat_sort_emit(const uint64_t* d_keys, size_t stride, const FlatQueryState* d_state, int nq, int n_keys,
                                  int top_k, int32_t* d_ids, float* d_dists, hipStream_t stream);
 
@@ -65,17 +102,17 @@ inline int flat_u8_padded_d(int D) { return (D + kFlatU8KStep - 1) & ~(kFlatU8KS
 // bytes [rows][D] -> biased int8 [rows][Dp] and norms [rows], on the device.
 hipError_t launch_flat_u8_prepare(const uint8_t* d_in, int64_t rows, int D, int Dp, int8_t* d_out, int32_t* d_norms,
                                   hipStream_t stream);
-// launch_flat_search over prepared bytes: d_base [n][Dp] with d_vnorm, d_queries [nq][Dp] with d_qnorm.
-hipError_t launch_flat_search_u8(const int8_t* d_base, const int32_t* d_vnorm, int64_t n, int Dp, const int8_t* d_queries,
-                                 const int32_t* d_qnorm, int nq, int top_k, int64_t id_offset, uint64_t* d_keys,
-                                 FlatQueryState* d_state, int32_t* d_ids, float* d_dists, hipStream_t stream);
+// The distance stage of launch_flat_search / launch_flat_range_pass on a byte base: one launch of the byte kernel's
+// (b.filtered, mode) instantiation over entries e0 .. e0 + rows - 1.  keys / cap / offs: the mode's sink, as above.
+hipError_t launch_flat_dist_u8(int mode, const FlatBase& b, int64_t e0, int rows, const FlatQueries& q, uint64_t* keys,
+                               int cap, const int64_t* offs, FlatQueryState* state, hipStream_t stream);
 // launch_flat_rerank over a prepared base; d_queries are the caller's bytes [nq][D], unpadded.
 hipError_t launch_flat_rerank_u8(const int8_t* d_base, int64_t n, int D, int Dp, const uint8_t* d_queries, int nq,
                                  const int32_t* d_cand, int n_cand, int top_k, int64_t id_offset, const uint32_t* d_map,
                                  int64_t n_map, uint64_t* d_keys, uint32_t* d_flag, int32_t* d_ids, float* d_dists,
                                  hipStream_t stream);
 
-// ---- filtered and range search (dpq_flat_filter.hip) ----------------------------------------------------------------
+// ---- filters and range search (dpq_flat_filter.hip: the row list, the range state, the sort; no distance code) -----
 // A filter is the ascending list of a handle's eligible rows.  d_words [n_words]: bit b of word w = row 32 w + b.
 // flat_filter_count fills d_cnt / d_off [n_words] (popcounts and their exclusive prefix sum) and waits for n_allowed;
 // launch_flat_filter_emit then writes d_list [cap] (*d_flag is set if an entry would fall outside it).
@@ -83,27 +120,14 @@ hipError_t flat_filter_count(const uint32_t* d_words, int64_t n_words, uint32_t*
                              hipStream_t stream);
 hipError_t launch_flat_filter_emit(const uint32_t* d_words, int64_t n_words, const uint32_t* d_off, uint32_t* d_list,
                                    int64_t cap, uint32_t* d_flag, hipStream_t stream);
-// launch_flat_search / launch_flat_search_u8 over the rows d_list [n_list] names (n_list may be below top_k, or zero:
-// rows are padded with -1 / +inf).  Buffers as there.
-hipError_t launch_flat_search_list(const float* d_base, const uint32_t* d_list, int64_t n_list, int Dp, const float* d_queries,
-                                   int nq, int top_k, int64_t id_offset, uint64_t* d_keys, FlatQueryState* d_state,
-                                   int32_t* d_ids, float* d_dists, hipStream_t stream);
-hipError_t launch_flat_search_list_u8(const int8_t* d_base, const int32_t* d_vnorm, const uint32_t* d_list, int64_t n_list,
-                                      int Dp, const int8_t* d_queries, const int32_t* d_qnorm, int nq, int top_k,
-                                      int64_t id_offset, uint64_t* d_keys, FlatQueryState* d_state, int32_t* d_ids,
-                                      float* d_dists, hipStream_t stream);
 // Range search, count then emit.  launch_flat_range_state: count = overflow = 0, thr = d_thr[q] (distance bits of the
-// radius << 32; 0 passes nothing).  A pass forms the distances of nq queries to n_entries rows (those of d_list, or all
-// when it is NULL) and, for keys below thr, counts them (d_pool NULL) or appends them to the query's list
-// d_pool[d_offs[q] .. d_offs[q + 1]).  flat_range_sort: hipcub's two-call protocol (d_temp NULL: *temp_bytes only); sorts
-// every list of the pool by key into d_out.
+// radius << 32; 0 passes nothing).  launch_flat_range_pass (dpq_flat.hip, beside the distance kernels) forms the distances
+// of the queries to every entry of the base in one launch and, for keys below thr, counts them (d_pool NULL) or appends
+// them to the query's list d_pool[d_offs[q] .. d_offs[q + 1]).  flat_range_sort: hipcub's two-call protocol (d_temp NULL:
+// *temp_bytes only); sorts every list of the pool by key into d_out.
 hipError_t launch_flat_range_state(FlatQueryState* d_state, const uint64_t* d_thr, int nq, hipStream_t stream);
-hipError_t launch_flat_range_pass(const float* d_base, const uint32_t* d_list, int64_t n_entries, int Dp,
-                                  const float* d_queries, int nq, int64_t id_offset, uint64_t* d_pool, const int64_t* d_offs,
+hipError_t launch_flat_range_pass(const FlatBase& b, const FlatQueries& q, uint64_t* d_pool, const int64_t* d_offs,
                                   FlatQueryState* d_state, hipStream_t stream);
-hipError_t launch_flat_range_pass_u8(const int8_t* d_base, const int32_t* d_vnorm, const uint32_t* d_list, int64_t n_entries,
-                                     int Dp, const int8_t* d_queries, const int32_t* d_qnorm, int nq, int64_t id_offset,
-                                     uint64_t* d_pool, const int64_t* d_offs, FlatQueryState* d_state, hipStream_t stream);
 hipError_t flat_range_sort(void* d_temp, size_t* temp_bytes, const uint64_t* d_in, uint64_t* d_out, int64_t n_keys,
                            int n_lists, const int64_t* d_offs, hipStream_t stream);
 

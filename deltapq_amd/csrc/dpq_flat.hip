@@ -5,15 +5,27 @@
 // accumulator that starts at +0.0; the reported distance is (float)acc.  One lane owns one distance from the first
 // dimension to the last, so the order of the sum is the reference's (main.cpp:150-156) and the bits are too.
 //
-//   flat_dist_kernel      a workgroup takes 64 queries x 64 vectors; both tiles go through LDS in slices of 32
-//                         dimensions, transposed so that a lane reads its four queries and four vectors as two
-//                         16-byte LDS loads; 16 fp64 accumulators per lane.  Distances at or below the query's
-//                         threshold are appended as keys (distance bits << 32 | id) to the query's buffer.
+//   flat_dist_kernel<LIST, MODE>
+//                         the one fp32 distance kernel, for every search.  A workgroup takes 64 queries x 64 entries of
+//                         a stripe; both tiles go through LDS in slices of 32 dimensions, transposed so that a lane
+//                         reads its four queries and four vectors as two 16-byte LDS loads; 16 fp64 accumulators per
+//                         lane.  LIST: entry e is row l0 + e (false: every row, or a range search without a filter), or
+//                         row list[l0 + e] (true: a filter's row list), the tile's row numbers staged in LDS.  MODE,
+//                         what becomes of a key (distance bits << 32 | id):
+//                           kFlatTopK   key <= the query's threshold: appended to the query's buffer
+//                           kFlatCount  key <  the radius key: counted
+//                           kFlatEmit   key <  the radius key: appended to the query's list in the pool, whose length
+//                                       the count pass gave
+//                         Every append checks its position against the capacity of its buffer and raises
+//                         FlatQueryState::overflow instead of storing outside it.
 //   flat_select_kernel    when a buffer is filling up: radix select of the top_k-th key, compaction in place, the
 //                         threshold lowered to that key.
 //   flat_sort_emit_kernel bitonic sort of a query's keys in LDS, duplicates dropped, ids and distances written.
 //   flat_rerank_kernel    a lane per candidate; a wavefront fetches its 64 rows with 16-byte loads into LDS, 32
 //                         dimensions at a time, and every lane then walks its own row in order.
+// launch_flat_search is the one stripe driver (state, then per stripe a select and a distance launch, then the last
+// select and the sort) and launch_flat_range_pass the one range pass, for both element types, with and without a list;
+// the byte kernel of dpq_flat_u8.hip comes in through launch_flat_dist_u8.
 #include "dpq_flat.h"
 
 #include <algorithm>
@@ -25,7 +37,6 @@ namespace {
 constexpr int TQ = 64, TV = 64;  // queries and vectors of a workgroup's tile
 constexpr int DC = 32;           // dimensions staged at a time
 constexpr int LD = TV + 4;       // LDS row stride in floats (16-byte aligned; spreads the transposed writes)
-constexpr uint64_t kNoKey = ~0ull;
 constexpr int kSelThreads = 1024;
 
 __device__ __forceinline__ uint64_t make_key(double acc, uint32_t id) {
@@ -37,7 +48,7 @@ __global__ void flat_init_state_kernel(FlatQueryState* state, int nq) {
     if (q < nq) {
         state[q].count = 0;
         state[q].overflow = 0;
-        state[q].thr = kNoKey;
+        state[q].thr = kFlatNoKey;
     }
 }
 
@@ -49,18 +60,33 @@ __global__ void flat_pad_rows_kernel(const float* in, int64_t rows, int D, int D
     out[i] = d < D ? in[r * D + d] : 0.0f;
 }
 
-// grid (vector tiles of the stripe, query tiles), 256 threads: thread (tx, ty) owns queries ty*4.. x vectors tx*4..
-__global__ __launch_bounds__(256) void flat_dist_kernel(const float* __restrict__ base, int64_t row0, int rows, int Dp,
-                                                        const float* __restrict__ queries, int nq, int64_t id_offset,
-                                                        uint64_t* __restrict__ keys, int cap, FlatQueryState* state) {
+// grid (tiles of the stripe's `rows` entries, query tiles), 256 threads: thread (tx, ty) owns queries ty*4.. x entries
+// tx*4.. of the tile.  Entry e of the stripe is row l0 + e, computed where it is needed (LIST false: no row numbers in
+// LDS, no barrier before the first slice), or row list[l0 + e], staged once per tile in lrow.  Every instantiation is
+// the straight-line kernel of its case; nothing is picked at run time.
+template <bool LIST, int MODE>
+__global__ __launch_bounds__(256) void flat_dist_kernel(const float* __restrict__ base, const uint32_t* __restrict__ list,
+                                                        int64_t l0, int rows, int Dp, const float* __restrict__ queries,
+                                                        int nq, int64_t id_offset, uint64_t* __restrict__ keys, int cap,
+                                                        const int64_t* __restrict__ offs, FlatQueryState* state) {
     __shared__ float qs[DC][LD];
     __shared__ float vs[DC][LD];
+    __shared__ uint32_t lrow[TV];  // LIST only
     __shared__ uint32_t cnt[TQ];
     __shared__ uint32_t pos0[TQ];
     __shared__ uint64_t thr[TQ];
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
     const int v0 = blockIdx.x * TV, q0 = blockIdx.y * TQ;
     const int sr = tid >> 3, sj = (tid & 7) * 4;  // staging: row sr (and sr + 32), dimensions sj .. sj + 3 of the slice
+    if constexpr (LIST) {
+        if (tid < TV) lrow[tid] = v0 + tid < rows ? list[l0 + v0 + tid] : 0;  // past the stripe: row 0, masked below
+        __syncthreads();
+    }
+    // the row of tile entry e; only called for, or masked to, e with v0 + e < rows
+    auto row_of = [&](int e) -> int64_t {
+        if constexpr (LIST) return lrow[e];
+        else return l0 + (v0 + e);
+    };
 
     double acc[4][4];
 #pragma unroll
@@ -73,7 +99,7 @@ __global__ __launch_bounds__(256) void flat_dist_kernel(const float* __restrict_
         for (int h = 0; h < 2; ++h) {
             const int r = sr + 32 * h, d = d0 + sj;
             float4 v = make_float4(0.f, 0.f, 0.f, 0.f), q = v;
-            if (v0 + r < rows && d < Dp) v = *reinterpret_cast<const float4*>(base + (size_t)(row0 + v0 + r) * Dp + d);
+            if (v0 + r < rows && d < Dp) v = *reinterpret_cast<const float4*>(base + (size_t)row_of(r) * Dp + d);
             if (q0 + r < nq && d < Dp) q = *reinterpret_cast<const float4*>(queries + (size_t)(q0 + r) * Dp + d);
             vs[sj + 0][r] = v.x; vs[sj + 1][r] = v.y; vs[sj + 2][r] = v.z; vs[sj + 3][r] = v.w;
             qs[sj + 0][r] = q.x; qs[sj + 1][r] = q.y; qs[sj + 2][r] = q.z; qs[sj + 3][r] = q.w;
@@ -108,13 +134,15 @@ __global__ __launch_bounds__(256) void flat_dist_kernel(const float* __restrict_
     for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const int ql = ty * 4 + i, v = v0 + tx * 4 + j;
-            key[i][j] = make_key(acc[i][j], (uint32_t)(id_offset + row0 + v));
-            const bool pass = q0 + ql < nq && v < rows && key[i][j] <= thr[ql];
+            const int ql = ty * 4 + i, vl = tx * 4 + j;
+            key[i][j] = make_key(acc[i][j], (uint32_t)(id_offset + row_of(vl)));
+            const bool below = MODE == kFlatTopK ? key[i][j] <= thr[ql] : key[i][j] < thr[ql];
+            const bool pass = q0 + ql < nq && v0 + vl < rows && below;
             slot[i][j] = pass ? atomicAdd(&cnt[ql], 1u) : 0xffffffffu;
         }
     __syncthreads();
     if (tid < TQ && cnt[tid]) pos0[tid] = atomicAdd(&state[q0 + tid].count, cnt[tid]);
+    if (MODE == kFlatCount) return;
     __syncthreads();
 #pragma unroll
     for (int i = 0; i < 4; ++i)
@@ -123,8 +151,10 @@ __global__ __launch_bounds__(256) void flat_dist_kernel(const float* __restrict_
             if (slot[i][j] == 0xffffffffu) continue;
             const int ql = ty * 4 + i;
             const uint32_t pos = pos0[ql] + slot[i][j];
-            if (pos < (uint32_t)cap)
-                keys[(size_t)(q0 + ql) * cap + pos] = key[i][j];
+            uint32_t room;
+            uint64_t* out = flat_sink_of<MODE>(keys, cap, offs, q0 + ql, &room);
+            if (pos < room)
+                out[pos] = key[i][j];
             else
                 state[q0 + ql].overflow = 1;
         }
@@ -196,7 +226,7 @@ __global__ __launch_bounds__(kSelThreads) void flat_select_kernel(uint64_t* keys
     for (uint32_t b = 0; b < cnt; b += kSelThreads) {
         // a round reads [b, b + 1024) before the barrier inside the scan and writes below b + 1024 after it
         const uint32_t i = b + tid;
-        const uint64_t k = i < cnt ? buf[i] : kNoKey;
+        const uint64_t k = i < cnt ? buf[i] : kFlatNoKey;
         const uint32_t keep = i < cnt && k <= kth;
         uint32_t total;
         const uint32_t off = block_scan_1024(keep, wsum, &total);
@@ -210,7 +240,7 @@ __global__ __launch_bounds__(kSelThreads) void flat_select_kernel(uint64_t* keys
 }
 
 // One workgroup per query: sort its keys (n_keys of them, or state[q].count) in LDS, drop repeats, write the first
-// top_k as (id, distance); rows are padded with -1 / +inf.  kNoKey entries are padding.  n_pad: a power of two.
+// top_k as (id, distance); rows are padded with -1 / +inf.  kFlatNoKey entries are padding.  n_pad: a power of two.
 __global__ __launch_bounds__(kSelThreads) void flat_sort_emit_kernel(const uint64_t* __restrict__ keys, size_t stride,
                                                                      const FlatQueryState* state, int n_keys, int n_pad,
                                                                      int top_k, int32_t* __restrict__ ids,
@@ -219,7 +249,7 @@ __global__ __launch_bounds__(kSelThreads) void flat_sort_emit_kernel(const uint6
     __shared__ uint32_t wsum[16];
     const int q = blockIdx.x, tid = threadIdx.x;
     const int cnt = state ? (int)min(state[q].count, (uint32_t)n_keys) : n_keys;
-    for (int i = tid; i < n_pad; i += kSelThreads) sk[i] = i < cnt ? keys[(size_t)q * stride + i] : kNoKey;
+    for (int i = tid; i < n_pad; i += kSelThreads) sk[i] = i < cnt ? keys[(size_t)q * stride + i] : kFlatNoKey;
     __syncthreads();
     for (int k = 2; k <= n_pad; k <<= 1)
         for (int j = k >> 1; j > 0; j >>= 1) {
@@ -238,11 +268,11 @@ __global__ __launch_bounds__(kSelThreads) void flat_sort_emit_kernel(const uint6
     const int per = (n_pad + kSelThreads - 1) / kSelThreads;
     const int lo = min(n_pad, tid * per), hi = min(n_pad, lo + per);
     uint32_t u = 0;
-    for (int i = lo; i < hi; ++i) u += sk[i] != kNoKey && (i == 0 || sk[i] != sk[i - 1]);
+    for (int i = lo; i < hi; ++i) u += sk[i] != kFlatNoKey && (i == 0 || sk[i] != sk[i - 1]);
     uint32_t total;
     uint32_t pos = block_scan_1024(u, wsum, &total);
     for (int i = lo; i < hi; ++i)
-        if (sk[i] != kNoKey && (i == 0 || sk[i] != sk[i - 1])) {
+        if (sk[i] != kFlatNoKey && (i == 0 || sk[i] != sk[i - 1])) {
             if (pos < (uint32_t)top_k) {
                 ids[(size_t)q * top_k + pos] = (int32_t)(uint32_t)(sk[i] & 0xffffffffu);
                 dists[(size_t)q * top_k + pos] = __uint_as_float((uint32_t)(sk[i] >> 32));
@@ -304,7 +334,7 @@ __global__ __launch_bounds__(256) void flat_rerank_kernel(const float* __restric
         __syncthreads();
     }
     if (ci < n_pad)
-        keys[(size_t)q * n_pad + ci] = row >= 0 ? make_key(acc, (uint32_t)((int64_t)row + id_offset)) : kNoKey;
+        keys[(size_t)q * n_pad + ci] = row >= 0 ? make_key(acc, (uint32_t)((int64_t)row + id_offset)) : kFlatNoKey;
 }
 
 int pow2_at_least(int v) {
@@ -343,30 +373,61 @@ hipError_t launch_flat_pad_rows(const float* d_in, int64_t rows, int D, int Dp, 
     return hipGetLastError();
 }
 
-hipError_t launch_flat_search(const float* d_base, int64_t n, int Dp, const float* d_queries, int nq, int top_k,
-                              int64_t id_offset, uint64_t* d_keys, FlatQueryState* d_state, int32_t* d_ids, float* d_dists,
-                              hipStream_t stream) {
+namespace {
+
+template <bool LIST, int MODE>
+void dist_fp32(const FlatBase& b, int64_t e0, int rows, const FlatQueries& q, uint64_t* keys, int cap, const int64_t* offs,
+               FlatQueryState* state, hipStream_t stream) {
+    flat_dist_kernel<LIST, MODE><<<dim3((rows + TV - 1) / TV, (q.nq + TQ - 1) / TQ), dim3(256), 0, stream>>>(
+        b.f32, b.list, e0, rows, b.Dp, q.f32, q.nq, b.id_offset, keys, cap, offs, state);
+}
+
+// One distance launch over entries e0 .. e0 + rows - 1 of the base, by element type, row source and mode.
+hipError_t launch_flat_dist(int mode, const FlatBase& b, int64_t e0, int rows, const FlatQueries& q, uint64_t* keys, int cap,
+                            const int64_t* offs, FlatQueryState* state, hipStream_t stream) {
+    if (b.i8) return launch_flat_dist_u8(mode, b, e0, rows, q, keys, cap, offs, state, stream);
+    auto* launch = b.filtered ? (mode == kFlatTopK    ? dist_fp32<true, kFlatTopK>
+                                 : mode == kFlatCount ? dist_fp32<true, kFlatCount>
+                                                      : dist_fp32<true, kFlatEmit>)
+                              : (mode == kFlatTopK    ? dist_fp32<false, kFlatTopK>
+                                 : mode == kFlatCount ? dist_fp32<false, kFlatCount>
+                                                      : dist_fp32<false, kFlatEmit>);
+    launch(b, e0, rows, q, keys, cap, offs, state, stream);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_flat_search(const FlatBase& b, const FlatQueries& q, int top_k, uint64_t* d_keys, FlatQueryState* d_state,
+                              int32_t* d_ids, float* d_dists, hipStream_t stream) {
+    const int nq = q.nq;
     if (nq <= 0) return hipSuccess;
     hipError_t e = ensure_sort_lds();
     if (e != hipSuccess) return e;
     const int cap = flat_key_capacity(top_k);
     // A stripe appends at most cap / 2 keys to a buffer, and a buffer enters a stripe with at most cap / 2: the select
     // between two stripes cuts every buffer above cap / 4 (>= top_k) down to top_k.  The first stripe, with no
-    // threshold yet, is the prefix the first thresholds come from.
+    // threshold yet, is the prefix the first thresholds come from.  A stripe is cap / 2 entries: rows, or list entries.
     const int64_t stripe = cap / 2;
     const uint32_t limit = (uint32_t)std::max(top_k, cap / 4);
     flat_init_state_kernel<<<dim3((nq + 255) / 256), dim3(256), 0, stream>>>(d_state, nq);
-    for (int64_t r0 = 0; r0 < n; r0 += stripe) {
-        const int rows = (int)std::min<int64_t>(stripe, n - r0);
-        if (r0 > 0) flat_select_kernel<<<dim3(nq), dim3(kSelThreads), 0, stream>>>(d_keys, cap, d_state, top_k, limit);
-        flat_dist_kernel<<<dim3((rows + TV - 1) / TV, (nq + TQ - 1) / TQ), dim3(256), 0, stream>>>(
-            d_base, r0, rows, Dp, d_queries, nq, id_offset, d_keys, cap, d_state);
+    for (int64_t e0 = 0; e0 < b.n_entries; e0 += stripe) {
+        const int rows = (int)std::min<int64_t>(stripe, b.n_entries - e0);
+        if (e0 > 0) flat_select_kernel<<<dim3(nq), dim3(kSelThreads), 0, stream>>>(d_keys, cap, d_state, top_k, limit);
+        if ((e = launch_flat_dist(kFlatTopK, b, e0, rows, q, d_keys, cap, nullptr, d_state, stream)) != hipSuccess) return e;
     }
     flat_select_kernel<<<dim3(nq), dim3(kSelThreads), 0, stream>>>(d_keys, cap, d_state, top_k, (uint32_t)top_k);
     const int n_pad = pow2_at_least(top_k);
     flat_sort_emit_kernel<<<dim3(nq), dim3(kSelThreads), (size_t)n_pad * sizeof(uint64_t), stream>>>(
         d_keys, (size_t)cap, d_state, top_k, n_pad, top_k, d_ids, d_dists);
     return hipGetLastError();
+}
+
+hipError_t launch_flat_range_pass(const FlatBase& b, const FlatQueries& q, uint64_t* d_pool, const int64_t* d_offs,
+                                  FlatQueryState* d_state, hipStream_t stream) {
+    if (q.nq <= 0 || b.n_entries <= 0) return hipSuccess;
+    return launch_flat_dist(d_pool ? kFlatEmit : kFlatCount, b, 0, (int)b.n_entries, q, d_pool, 0, d_pool ? d_offs : nullptr,
+                            d_state, stream);
 }
 
 hipError_t launch_flat_rerank(const float* d_base, int64_t n, int D, int Dp, const float* d_queries, int nq,
@@ -385,17 +446,6 @@ hipError_t launch_flat_rerank(const float* d_base, int64_t n, int D, int Dp, con
     }
     flat_sort_emit_kernel<<<dim3(nq), dim3(kSelThreads), (size_t)n_pad * sizeof(uint64_t), stream>>>(
         d_keys, (size_t)n_pad, nullptr, n_pad, n_pad, top_k, d_ids, d_dists);
-    return hipGetLastError();
-}
-
-hipError_t launch_flat_init_state(FlatQueryState* d_state, int nq, hipStream_t stream) {
-    flat_init_state_kernel<<<dim3((nq + 255) / 256), dim3(256), 0, stream>>>(d_state, nq);
-    return hipGetLastError();
-}
-
-hipError_t launch_flat_select(uint64_t* d_keys, int cap, FlatQueryState* d_state, int nq, int top_k, uint32_t limit,
-                              hipStream_t stream) {
-    flat_select_kernel<<<dim3(nq), dim3(kSelThreads), 0, stream>>>(d_keys, cap, d_state, top_k, limit);
     return hipGetLastError();
 }
 

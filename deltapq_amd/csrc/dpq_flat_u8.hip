@@ -13,13 +13,16 @@
 //
 //   flat_u8_bias_rows_kernel   bytes [rows][D] -> biased int8 [rows][Dp], padded
 //   flat_u8_norms_kernel       a lane per row: its int32 norm
-//   flat_dist_u8_kernel        a workgroup takes 64 queries x 256 vectors, a wavefront 64 x 64 as 2 x 2 tiles of
-//                              v_mfma_i32_32x32x32_i8 (A = vectors, B = queries); a lane's operand of a K step is 16
-//                              contiguous bytes of one row, loaded straight from global memory.  The epilogue forms the
-//                              int32 distances and appends keys under flat_dist_kernel's threshold / counter protocol.
+//   flat_dist_u8_kernel<LIST, MODE>
+//                              the one byte distance kernel, for every search.  A workgroup takes 64 queries x 256
+//                              entries of a stripe, a wavefront 64 x 64 as 2 x 2 tiles of v_mfma_i32_32x32x32_i8 (A =
+//                              vectors, B = queries); a lane's operand of a K step is 16 contiguous bytes of one row,
+//                              loaded straight from global memory.  The epilogue forms the int32 distances and treats
+//                              the keys as flat_dist_kernel<LIST, MODE> does: the same row sources (LIST), the same
+//                              modes and threshold / counter protocol (dpq_flat.hip's header).
 //   flat_rerank_u8_kernel      a lane per candidate; a wavefront fetches its 64 rows with 16-byte loads into LDS, 128
 //                              bytes of a row at a time, and every lane then sums its own row in int32.
-// State, selection and the final sort are dpq_flat.hip's kernels, unchanged.
+// State, selection, the final sort and the stripe driver are dpq_flat.hip's; launch_flat_dist_u8 is the one way in.
 #include "dpq_flat.h"
 
 #include <algorithm>
@@ -34,7 +37,6 @@ constexpr int UQ = 64;    // queries of a workgroup's tile
 constexpr int UV = 256;   // vectors of a workgroup's tile: 64 per wavefront
 constexpr int KS = 32;    // bytes of a row one MFMA consumes (kFlatU8KStep)
 constexpr int RC = 128;   // bytes of a row the re-rank stages at a time
-constexpr uint64_t kNoKey = ~0ull;
 
 static_assert(KS == kFlatU8KStep, "rows are padded to the K step of the MFMA");
 
@@ -78,23 +80,43 @@ __global__ void flat_u8_norms_kernel(const int8_t* __restrict__ rows8, int64_t r
     norms[r] = s;
 }
 
-// grid (vector tiles of the stripe, query tiles), 256 threads.  Wavefront w owns vectors v0 .. v0 + 63 of the tile and
-// all 64 queries.  acc[i][j] is the 32 x 32 tile of vectors 32 i .. x queries 32 j ..: register e of lane l holds
-// vector 32 i + (e & 3) + 8 (e >> 2) + 4 (l >> 5) against query 32 j + (l & 31)  (the C/D map of the 32x32 shapes).
+// grid (tiles of the stripe's `rows` entries, query tiles), 256 threads.  Wavefront w owns entries 64 w .. 64 w + 63 of
+// the workgroup's 256 and all 64 queries.  acc[i][j] is the 32 x 32 tile of the wavefront's entries 32 i .. x queries
+// 32 j ..: register e of lane l holds entry 32 i + (e & 3) + 8 (e >> 2) + 4 (l >> 5) against query 32 j + (l & 31)  (the
+// C/D map of the 32x32 shapes).  Entry e of the stripe is row l0 + e, computed where it is needed (LIST false: no row
+// numbers in LDS, no barrier before the MFMA loop, the norms of four adjacent registers one 16-byte load), or row
+// list[l0 + e], staged once per tile in lrow, every norm fetched by its row number.  Every instantiation is the
+// straight-line kernel of its case; nothing is picked at run time.
+template <bool LIST, int MODE>
 __global__ __launch_bounds__(256) void flat_dist_u8_kernel(const int8_t* __restrict__ base, const int32_t* __restrict__ vnorm,
-                                                           int64_t row0, int rows, int Dp,
+                                                           const uint32_t* __restrict__ list, int64_t l0, int rows, int Dp,
                                                            const int8_t* __restrict__ queries,
                                                            const int32_t* __restrict__ qnorm, int nq, int64_t id_offset,
-                                                           uint64_t* __restrict__ keys, int cap, FlatQueryState* state) {
+                                                           uint64_t* __restrict__ keys, int cap,
+                                                           const int64_t* __restrict__ offs, FlatQueryState* state) {
+    __shared__ uint32_t lrow[UV];  // LIST only
     __shared__ uint32_t cnt[UQ];
     __shared__ uint32_t pos0[UQ];
     __shared__ uint64_t thr[UQ];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r = lane & 31, h = lane >> 5;
-    const int v0 = blockIdx.x * UV + w * 64, q0 = blockIdx.y * UQ;
+    const int b0 = blockIdx.x * UV, q0 = blockIdx.y * UQ;  // b0: the tile's first entry in the stripe
+    // Below, an entry goes by the index v that finds its row: its place in the tile under LIST (lrow[v]), its place in
+    // the stripe otherwise (row l0 + v).  v0: the wavefront's first entry.  inside(v): the stripe has that entry.
+    const int v0 = (LIST ? 0 : b0) + w * 64;
+    auto inside = [&](int v) { return (LIST ? b0 + v : v) < rows; };
+    if constexpr (LIST) {
+        lrow[tid] = b0 + tid < rows ? list[l0 + b0 + tid] : 0;  // past the stripe: row 0, masked below
+    }
     if (tid < UQ) {
         cnt[tid] = 0;
         thr[tid] = q0 + tid < nq ? state[q0 + tid].thr : 0;
     }
+    if constexpr (LIST) __syncthreads();
+    // the row of entry v; past the stripe it is clamped to a row that exists, and the entry masked below
+    auto row_of = [&](int v) -> int64_t {
+        if constexpr (LIST) return lrow[v];
+        else return l0 + (inside(v) ? v : 0);
+    };
 
     // lane l feeds row (l & 31) of a tile with bytes 16 (l >> 5) .. + 15 of the K step, on both sides
     const int8_t* ap[2];
@@ -103,9 +125,9 @@ __global__ __launch_bounds__(256) void flat_dist_u8_kernel(const int8_t* __restr
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         const int v = v0 + 32 * i + r, q = q0 + 32 * i + r;
-        aok[i] = v < rows;
+        aok[i] = inside(v);
         bok[i] = q < nq;
-        ap[i] = base + (size_t)(row0 + (aok[i] ? v : 0)) * Dp + 16 * h;
+        ap[i] = base + (size_t)row_of(v) * Dp + 16 * h;
         bp[i] = queries + (size_t)(bok[i] ? q : 0) * Dp + 16 * h;
     }
     i32x16 acc[2][2];
@@ -129,7 +151,7 @@ __global__ __launch_bounds__(256) void flat_dist_u8_kernel(const int8_t* __restr
 #pragma unroll
             for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[i], b[j], acc[i][j], 0, 0, 0);
     }
-    __syncthreads();
+    if constexpr (!LIST) __syncthreads();  // cnt and thr
 
     // dot products -> the fp32 bit patterns of the distances, in place.  A distance is a non-negative integer, so its
     // bits order as unsigned integers and key <= thr is (bits, id) <= (thr >> 32, thr & 0xffffffff).
@@ -146,21 +168,33 @@ __global__ __launch_bounds__(256) void flat_dist_u8_kernel(const int8_t* __restr
         for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                const int vg = v0 + 32 * i + 8 * g + 4 * h;  // four vectors in a row: registers 4 g .. 4 g + 3
+                const int vg = v0 + 32 * i + 8 * g + 4 * h;  // four entries in a row: registers 4 g .. 4 g + 3
+                // Their norms: one 16-byte load where the rows are adjacent (vnorm is padded to four rows), else a load
+                // per row right before its conversion -- fetching the four first costs 4 % of a filtered search.
                 i32x4 vn = zero;
-                if (vg < rows) vn = *reinterpret_cast<const i32x4*>(vnorm + row0 + vg);  // vnorm is padded to four rows
+                if constexpr (!LIST)
+                    if (inside(vg)) vn = *reinterpret_cast<const i32x4*>(vnorm + l0 + vg);
 #pragma unroll
-                for (int c = 0; c < 4; ++c)
+                for (int c = 0; c < 4; ++c) {
+                    if constexpr (LIST) vn[c] = vnorm[row_of(vg + c)];
                     acc[i][j][4 * g + c] = __float_as_int(__int2float_rn(vn[c] + qn - 2 * acc[i][j][4 * g + c]));
+                }
             }
     }
-    const uint32_t id0 = (uint32_t)(id_offset + row0);
+    // the reported id of entry v
+    const uint32_t id0 = LIST ? (uint32_t)id_offset : (uint32_t)(id_offset + l0);
+    auto id_of = [&](int v) -> uint32_t {
+        if constexpr (LIST) return id0 + lrow[v];
+        else return id0 + (uint32_t)v;
+    };
     auto passes = [&](int i, int j, int e, int v) {
         const uint32_t b = (uint32_t)acc[i][j][e];
-        return v < rows && (b < thi[j] || (b == thi[j] && id0 + (uint32_t)v <= tlo[j]));
+        if (!inside(v)) return false;
+        if (MODE != kFlatTopK) return b < thi[j];  // the radius key's id half is zero
+        return b < thi[j] || (b == thi[j] && id_of(v) <= tlo[j]);
     };
 
-    // first pass: how many of a lane's 32 vectors per query pass, and where its run starts in the query's block
+    // first pass: how many of a lane's 32 entries per query pass, and where its run starts in the query's block
     uint32_t run[2];
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
@@ -174,20 +208,23 @@ __global__ __launch_bounds__(256) void flat_dist_u8_kernel(const int8_t* __restr
     }
     __syncthreads();
     if (tid < UQ && cnt[tid]) pos0[tid] = atomicAdd(&state[q0 + tid].count, cnt[tid]);
+    if (MODE == kFlatCount) return;
     __syncthreads();
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const int ql = 32 * j + r;
         if (!qok[j] || !cnt[ql]) continue;
         uint32_t pos = pos0[ql] + run[j];
+        uint32_t room;
+        uint64_t* out = flat_sink_of<MODE>(keys, cap, offs, q0 + ql, &room);
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
                 const int v = v0 + 32 * i + (e & 3) + 8 * (e >> 2) + 4 * h;
                 if (passes(i, j, e, v)) {
-                    if (pos < (uint32_t)cap)
-                        keys[(size_t)(q0 + ql) * cap + pos] = ((uint64_t)(uint32_t)acc[i][j][e] << 32) | (id0 + (uint32_t)v);
+                    if (pos < room)
+                        out[pos] = ((uint64_t)(uint32_t)acc[i][j][e] << 32) | id_of(v);
                     else
                         state[q0 + ql].overflow = 1;
                     ++pos;
@@ -254,7 +291,7 @@ __global__ __launch_bounds__(256) void flat_rerank_u8_kernel(const int8_t* __res
         __syncthreads();
     }
     if (ci < n_pad)
-        keys[(size_t)q * n_pad + ci] = row >= 0 ? make_key_i32(acc, (uint32_t)((int64_t)row + id_offset)) : kNoKey;
+        keys[(size_t)q * n_pad + ci] = row >= 0 ? make_key_i32(acc, (uint32_t)((int64_t)row + id_offset)) : kFlatNoKey;
 }
 
 }  // namespace
@@ -268,24 +305,27 @@ hipError_t launch_flat_u8_prepare(const uint8_t* d_in, int64_t rows, int D, int 
     return hipGetLastError();
 }
 
-hipError_t launch_flat_search_u8(const int8_t* d_base, const int32_t* d_vnorm, int64_t n, int Dp, const int8_t* d_queries,
-                                 const int32_t* d_qnorm, int nq, int top_k, int64_t id_offset, uint64_t* d_keys,
-                                 FlatQueryState* d_state, int32_t* d_ids, float* d_dists, hipStream_t stream) {
-    if (nq <= 0) return hipSuccess;
-    // the stripes, the limit and the selection between them: launch_flat_search's, with the distance stage replaced
-    const int cap = flat_key_capacity(top_k);
-    const int64_t stripe = cap / 2;
-    const uint32_t limit = (uint32_t)std::max(top_k, cap / 4);
-    hipError_t e = launch_flat_init_state(d_state, nq, stream);
-    if (e != hipSuccess) return e;
-    for (int64_t r0 = 0; r0 < n; r0 += stripe) {
-        const int rows = (int)std::min<int64_t>(stripe, n - r0);
-        if (r0 > 0 && (e = launch_flat_select(d_keys, cap, d_state, nq, top_k, limit, stream)) != hipSuccess) return e;
-        flat_dist_u8_kernel<<<dim3((rows + UV - 1) / UV, (nq + UQ - 1) / UQ), dim3(256), 0, stream>>>(
-            d_base, d_vnorm, r0, rows, Dp, d_queries, d_qnorm, nq, id_offset, d_keys, cap, d_state);
-    }
-    if ((e = launch_flat_select(d_keys, cap, d_state, nq, top_k, (uint32_t)top_k, stream)) != hipSuccess) return e;
-    return launch_flat_sort_emit(d_keys, (size_t)cap, d_state, nq, top_k, top_k, d_ids, d_dists, stream);
+namespace {
+
+template <bool LIST, int MODE>
+void dist_u8(const FlatBase& b, int64_t e0, int rows, const FlatQueries& q, uint64_t* keys, int cap, const int64_t* offs,
+             FlatQueryState* state, hipStream_t stream) {
+    flat_dist_u8_kernel<LIST, MODE><<<dim3((rows + UV - 1) / UV, (q.nq + UQ - 1) / UQ), dim3(256), 0, stream>>>(
+        b.i8, b.norm, b.list, e0, rows, b.Dp, q.i8, q.norm, q.nq, b.id_offset, keys, cap, offs, state);
+}
+
+}  // namespace
+
+hipError_t launch_flat_dist_u8(int mode, const FlatBase& b, int64_t e0, int rows, const FlatQueries& q, uint64_t* keys,
+                               int cap, const int64_t* offs, FlatQueryState* state, hipStream_t stream) {
+    auto* launch = b.filtered ? (mode == kFlatTopK    ? dist_u8<true, kFlatTopK>
+                                 : mode == kFlatCount ? dist_u8<true, kFlatCount>
+                                                      : dist_u8<true, kFlatEmit>)
+                              : (mode == kFlatTopK    ? dist_u8<false, kFlatTopK>
+                                 : mode == kFlatCount ? dist_u8<false, kFlatCount>
+                                                      : dist_u8<false, kFlatEmit>);
+    launch(b, e0, rows, q, keys, cap, offs, state, stream);
+    return hipGetLastError();
 }
 
 hipError_t launch_flat_rerank_u8(const int8_t* d_base, int64_t n, int D, int Dp, const uint8_t* d_queries, int nq,

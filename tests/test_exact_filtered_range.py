@@ -382,6 +382,13 @@ def test_gpu_all_ones_filter_equals_the_unfiltered_search(gpu):
             for k in (1, 100, 3000):
                 a, c = f.search(q, k), f.search_filtered(q, k, ff)
                 assert a[0].tobytes() == c[0].tobytes() and a[1].tobytes() == c[1].tobytes(), (cls.__name__, k)
+            # range search: the direct-row kernels (no filter) against the list kernels (the all-ones filter)
+            for radius in (np.inf, f.search(q, 10)[1][:, 9].copy()):
+                a, c = f.range_search(q, radius), f.range_search(q, radius, ff)
+                assert len(a) == 3 and len(c) == 3
+                for x, y, what in zip(a, c, ("lims", "ids", "dists")):
+                    assert x.dtype == y.dtype and x.tobytes() == y.tobytes(), (cls.__name__, what)
+            assert a[0][-1] > 0  # the last radius, every query's 10th distance, lets rows in
 
 
 @pytest.mark.gpu
