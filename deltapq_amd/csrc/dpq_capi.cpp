@@ -260,7 +260,8 @@ struct Workspace {
                                    // one slot's kS1HistWords, what one query group's rows hold)
     DevBuf<uint64_t> d_cand_key, d_thr_key;  // candidate keys [slots][cap], threshold keys [slots]
     DevBuf<uint64_t> d_scratch;    // [slots][cap] contiguous copy of a slot's keys when they exceed the select's LDS list
-    DevBuf<uint8_t> d_batch_raw;   // the shard's plain codes, decoded once per batch (batch_decode); kept when the rest grows
+    DevBuf<uint8_t> d_batch_raw;   // tiled plain-code scratch (a shard larger than one tile): the tile being scanned, decoded
+                                   // per batch; kept when the rest grows.  A one-tile shard: dpq_index::d_plain_image
 };
 
 struct dpq_index {
@@ -293,6 +294,15 @@ struct dpq_index {
     DevBuf<unsigned long long> d_s1_stamps;    // developer diagnostics (dpq_debug_strand1_stamps)
     int batch_decode = 0;            // dpq_open_opts.batch_decode
     DevBuf<uint8_t> d_relabel;       // [M][256] code value -> label in the plain-code scratch (bank-aware; NULL = code values)
+    // The plain-code image of a shard that one tile holds (batch_tile_segments): every node's (relabelled) codes in
+    // shard order, shared by both lanes and every entry point.  It is decoded ONCE per handle, by the first batch that
+    // scans it, on that batch's stream (ensure_plain_image).  Nothing invalidates it: its only inputs are the device
+    // image and d_relabel, both fixed at dpq_open_*; dpq_set_codebook changes tables, never codes.
+    DevBuf<uint8_t> d_plain_image;
+    hipEvent_t image_done = nullptr;     // recorded behind the decode
+    hipStream_t image_stream = nullptr;  // the stream the decode was enqueued on
+    int image_state = 0;                 // 0: not decoded; 1: enqueued, batches on other streams wait for image_done;
+                                         // 2: the host has seen image_done complete, nothing waits any more
     DevBuf<uint8_t> d_nbr;           // [8][256][256] centroid neighbour lists of the bootstrap's sub-spaces (dpq_set_codebook)
     DevBuf<float> d_codebook;
     DevBuf<unsigned long long> d_counters;  // [2] scan statistics (dpq_profile.exact_checks / candidates)
@@ -638,8 +648,7 @@ struct Timer {
     }
 };
 
-// plain-code scratch of a shard (per pipeline lane), and whether a batch of n_groups query groups uses it
-// Plain-code scratch of a batch (per pipeline lane): one TILE of a filter level's segment list at a time -- decode the
+// Plain-code scratch of a batch (per pipeline lane; a shard of one tile: the handle's resident image instead): one TILE of a filter level's segment list at a time -- decode the
 // tile, scan it with every query group, next tile -- so the scratch stays Infinity-Cache-sized whatever the shard
 // (16 M nodes = 128 MB at M = 8; the 1 M-code headline and a 12.5 M-code shard are one tile, a 125 M-code shard's
 // last level eight).  dpq_open_opts.batch_tile_nodes overrides; dpq_open_opts.batch_decode >= 2 = tile of that many segments.
@@ -655,9 +664,42 @@ bool batch_decode_possible(const dpq_index* x) { return !x->plain && x->batch_de
 bool use_batch_decode(const dpq_index* x, int n_groups) {
     return batch_decode_possible(x) && (x->batch_decode > 0 || n_groups >= 3);
 }
+// one tile holds the shard: its batches scan the handle's resident image, not a workspace's tile scratch
+bool one_tile_shard(const dpq_index* x) { return batch_tile_segments(x) >= x->img.n_segments; }
 int ensure_batch_raw(dpq_index* x) {
+    if (one_tile_shard(x)) return DPQ_OK;  // (ensure_plain_image allocates with the decode)
     if (x->ws().d_batch_raw) return DPQ_OK;
     return x->ws().d_batch_raw.alloc((size_t)batch_raw_bytes(x));
+}
+
+// The resident plain-code image, valid for what is enqueued on `stream` after this call.  The first call decodes it on
+// `stream` (timed as decode) and records image_done behind the decode; until the host has seen that event complete, a
+// batch on another stream (the other lane, a caller's ordered stream, range search) waits for it.
+int ensure_plain_image(dpq_index* x, hipStream_t stream) {
+    if (x->image_state == 2) return DPQ_OK;
+    if (x->image_state == 1) {
+        const hipError_t q = hipEventQuery(x->image_done);
+        if (q == hipSuccess) {
+            x->image_state = 2;
+            return DPQ_OK;
+        }
+        if (q != hipErrorNotReady) DPQ_HIP(q);
+        (void)hipGetLastError();  // ("not ready" is no error of this call: the launches' own checks must not see it)
+        if (stream != x->image_stream) DPQ_HIP(hipStreamWaitEvent(stream, x->image_done, 0));
+        return DPQ_OK;
+    }
+    int rc;
+    if (!x->d_plain_image && (rc = x->d_plain_image.alloc((size_t)batch_raw_bytes(x)))) return rc;
+    if (!x->image_done) DPQ_HIP(hipEventCreateWithFlags(&x->image_done, hipEventDisableTiming));
+    {
+        Timer t(x, stream, 4);
+        DPQ_HIP(dpq::launch_decode_list(x->img, nullptr, x->img.n_segments, x->d_relabel,
+                                        reinterpret_cast<uint32_t*>(x->d_plain_image.get()), stream));
+    }
+    DPQ_HIP(hipEventRecord(x->image_done, stream));
+    x->image_stream = stream;
+    x->image_state = 1;
+    return DPQ_OK;
 }
 
 int splits_for(int n_seg_pass, int n_groups) {
@@ -766,16 +808,13 @@ int prepare_batch(dpq_index* x, Batch* b) {
 }
 
 // The exact tables of the batch; also clears the overflow flags and tightening counters of its slots.  One tile covers
-// the whole shard (the common case): it is decoded here, ahead of the table build, so that both run under the previous
-// pipelined batch's scan (neither needs LDS; the bootstrap that follows has to wait for that scan's LDS anyway), and
-// every level scans its slice of the shard-ordered scratch.  Otherwise each level decodes its own tiles in list order.
+// the whole shard (the common case): the handle's resident plain-code image serves every batch (decoded by the first
+// one, ahead of its table build) and every level scans its slice of it.  Otherwise each level decodes its own tiles
+// in list order.
 int build_tables(dpq_index* x, const Batch& b, const float* d_queries, hipStream_t stream) {
     Workspace& w = x->ws();
-    if (b.one_tile) {
-        Timer t(x, stream, 4);
-        DPQ_HIP(dpq::launch_decode_list(x->img, nullptr, x->img.n_segments, x->d_relabel,
-                                        reinterpret_cast<uint32_t*>(w.d_batch_raw.get()), stream));
-    }
+    int rc;
+    if (b.one_tile && (rc = ensure_plain_image(x, stream))) return rc;
     {
         Timer t(x, stream, 0);
         // batches that scan the plain-code scratch also get the tables in the scratch's label order
@@ -792,7 +831,7 @@ dpq::ScanArgs batch_scan_args(const dpq_index* x, const Batch& b) {
     const Workspace& w = x->ws();
     dpq::ScanArgs sa{};
     sa.img = x->img;
-    if (b.one_tile) sa.img.raw = w.d_batch_raw;
+    if (b.one_tile) sa.img.raw = x->d_plain_image;
     sa.fp32_accum = x->plain ? 1 : 0;
     sa.lut32 = b.labelled ? w.d_lut32r.get() : w.d_lut32.get();
     sa.lut_min = w.d_lut_min;
@@ -1381,7 +1420,7 @@ int range_batch(dpq_index* x, const float* d_queries, int nq, const float* radii
     const Workspace& w = x->ws();
     dpq::ScanArgs sa{};
     sa.img = x->img;
-    if (b.one_tile) sa.img.raw = w.d_batch_raw;
+    if (b.one_tile) sa.img.raw = x->d_plain_image;
     sa.fp32_accum = x->plain ? 1 : 0;
     sa.lut32 = b.labelled ? w.d_lut32r.get() : w.d_lut32.get();
     sa.lut_min = w.d_lut_min;
@@ -3223,6 +3262,7 @@ int dpq_close(dpq_index* x) {
     }
     for (auto& hs : x->host_slots)
         if (hs.kernels_done) hipEventDestroy(hs.kernels_done);
+    if (x->image_done) hipEventDestroy(x->image_done);
     if (x->copy_in) hipStreamDestroy(x->copy_in);
     if (x->copy_out) hipStreamDestroy(x->copy_out);
     if (x->h_overflow) hipHostFree(x->h_overflow);
@@ -4257,8 +4297,12 @@ int dpq_debug_scan_time(dpq_index* x, int nq, int pass_all, int reps, int splits
     dpq::ScanArgs sa = debug_scan_args(x, nq, &splits);
     sa.debug_pass = pass_all == 2 ? 0 : (pass_all ? 2 : 1);  // 2: the thresholds the last batch left behind
     // what the last batch ran: its plain-code scratch, if it decoded the whole shard into one
-    if (!x->plain && w.d_batch_raw && batch_tile_segments(x) >= x->img.n_segments && !getenv("DPQ_DEBUG_FUSED")) {
-        sa.img.raw = w.d_batch_raw;
+    if (!x->plain && x->image_state != 0 && !getenv("DPQ_DEBUG_FUSED")) {
+        if (x->image_state == 1) {  // (this replay runs on the null stream: the image must be there)
+            DPQ_HIP(hipEventSynchronize(x->image_done));
+            x->image_state = 2;
+        }
+        sa.img.raw = x->d_plain_image;
         if (x->d_relabel) sa.lut32 = w.d_lut32r;
     }
     hipEvent_t a, b;

@@ -167,8 +167,10 @@ typedef struct dpq_info {
     int32_t cand_capacity;
     int64_t bootstrap_bytes;   /* HBM bytes of the threshold-bootstrap multi-index (0 = not in use) */
     int32_t bootstrap_stride;  /* every bootstrap_stride-th node is in it */
-    int32_t batch_decode_mb;   /* MB of plain-code scratch (one tile, per pipeline lane) a batch decodes into; 0 = this
-                                * handle always decodes inside the scan */
+    int32_t batch_decode_mb;   /* MB of plain codes one tile holds.  A shard of one tile keeps ONE such image per handle,
+                                * decoded once by the first batch that scans it and shared by both pipeline lanes; a
+                                * larger shard decodes tile by tile, per batch, into a scratch per pipeline lane.
+                                * 0 = this handle always decodes inside the scan */
     int64_t strand_bytes;      /* HBM bytes of the strand image (the stream pass's own layout of the same nodes, resident
                                 * beside the SoA image on shards from 8 M codes); 0 = not built */
 } dpq_info;
