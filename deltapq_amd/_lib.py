@@ -211,6 +211,14 @@ SYMBOLS = [
      [_VP, c_i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, P(OpqOpts), _VP, _VP, P(OpqStats)]),
     ("dpq_write_rotation", ctypes.c_int, [ctypes.c_char_p, _VP, ctypes.c_int]),
     ("dpq_read_rotation", ctypes.c_int, [ctypes.c_char_p, P(c_i32), _VP]),
+    ("dpq_query_batch_tables", ctypes.c_int, [_VP, _VP, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP]),
+    ("dpq_query_batch_device_tables", ctypes.c_int, [_VP, _VP, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP]),
+    ("dpq_range_search_tables", ctypes.c_int, [_VP, _VP, ctypes.c_int, _VP, P(_VP)]),
+    ("dpq_ip_tables", ctypes.c_int, [_VP, _VP, ctypes.c_int, _VP, _VP]),
+    ("dpq_ip_tables_device", ctypes.c_int, [_VP, _VP, ctypes.c_int, _VP, _VP, _VP]),
+    ("dpq_query_batch_ip", ctypes.c_int, [_VP, _VP, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP, _VP]),
+    ("dpq_query_batch_device_ip", ctypes.c_int, [_VP, _VP, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP, _VP, _VP]),
+    ("dpq_ip_scores", ctypes.c_int, [_VP, _VP, _VP, ctypes.c_int, ctypes.c_int, _VP]),
     ("dpq_profile_enable", ctypes.c_int, [_VP, ctypes.c_int]),
     ("dpq_profile_reset", ctypes.c_int, [_VP]),
     ("dpq_profile_read", ctypes.c_int, [_VP, P(Profile)]),

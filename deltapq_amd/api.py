@@ -543,6 +543,128 @@ class DeltaPQIndex:
               "dpq_query_batch_device_filtered")
         return out_ids, out_dists
 
+    # ---- search by distance tables, and inner product (include/deltapq_amd.h) ----
+
+    def _tables(self, tables):
+        """float32 [nq][M][K], C-contiguous, of one table [M][K] or a batch of them."""
+        info = self.info()
+        t = np.ascontiguousarray(tables, dtype=np.float32)
+        if t.ndim == 2:
+            t = t[None]
+        assert t.ndim == 3 and t.shape[1:] == (info["M"], info["K"]), "tables must be [nq][M][K] of this index"
+        return t
+
+    def query_batch_tables(self, tables, top_k, id_filter=None):
+        """query_batch[_filtered] with the caller's distance tables [nq][M][K] standing where the L2 tables of the
+        queries stand (dpq_query_batch_tables); needs no codebook.  Entries: finite >= 0 or +inf."""
+        t = self._tables(tables)
+        nq = t.shape[0]
+        ids = np.empty((nq, top_k), dtype=np.int32)
+        dists = np.empty((nq, top_k), dtype=np.float32)
+        f = IdFilter._handle(id_filter) if id_filter is not None else None
+        check(self._lib.dpq_query_batch_tables(self._h, f, _np_ptr(t), nq, top_k, _np_ptr(ids), _np_ptr(dists)),
+              "dpq_query_batch_tables")
+        return ids, dists
+
+    def query_batch_tables_torch(self, tables, top_k, id_filter=None, out_ids=None, out_dists=None):
+        """query_batch_tables on device tensors ([nq][M][K] float32, contiguous), synchronous on torch's current stream
+        (dpq_query_batch_device_tables)."""
+        import torch
+        assert tables.is_cuda and tables.dtype == torch.float32 and tables.is_contiguous() and tables.dim() == 3
+        nq = tables.shape[0]
+        if out_ids is None:
+            out_ids = torch.empty((nq, top_k), dtype=torch.int32, device=tables.device)
+        if out_dists is None:
+            out_dists = torch.empty((nq, top_k), dtype=torch.float32, device=tables.device)
+        stream = torch.cuda.current_stream(tables.device).cuda_stream
+        f = IdFilter._handle(id_filter) if id_filter is not None else None
+        check(self._lib.dpq_query_batch_device_tables(self._h, f, ctypes.c_void_p(tables.data_ptr()), nq, top_k,
+                                                      ctypes.c_void_p(out_ids.data_ptr()),
+                                                      ctypes.c_void_p(out_dists.data_ptr()), ctypes.c_void_p(stream)),
+              "dpq_query_batch_device_tables")
+        return out_ids, out_dists
+
+    def range_search_tables(self, tables, radius, id_filter=None):
+        """range_search with the caller's distance tables (dpq_range_search_tables).  Range search takes no filter:
+        id_filter must be None."""
+        if id_filter is not None:
+            raise ValueError("range_search_tables takes no id_filter (dpq_range_search has no filtered form)")
+        t = self._tables(tables)
+        nq = t.shape[0]
+        r = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, dtype=np.float32), (nq,)))
+        res = ctypes.c_void_p()
+        check(self._lib.dpq_range_search_tables(self._h, _np_ptr(t), nq, _np_ptr(r), res), "dpq_range_search_tables")
+        return _range_result(self._lib, res)
+
+    def ip_tables(self, queries, id_filter=None):
+        """(tables float32 [nq][M][K], bias float32 [nq]) of the inner-product rule (dpq_ip_tables): the tables
+        query_batch_tables takes, gaps to each sub-space's best centroid.  A filter has no part in them: id_filter must
+        be None."""
+        if id_filter is not None:
+            raise ValueError("ip_tables takes no id_filter: the tables depend on the queries and the codebook only")
+        q =np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        info = self.info()
+        nq = q.shape[0]
+        tables = np.empty((nq, info["M"], info["K"]), dtype=np.float32)
+        bias = np.empty(nq, dtype=np.float32)
+        check(self._lib.dpq_ip_tables(self._h, _np_ptr(q), nq, _np_ptr(tables), _np_ptr(bias)), "dpq_ip_tables")
+        return tables, bias
+
+    def ip_tables_torch(self, queries, out_tables=None, out_bias=None):
+        """ip_tables on device tensors, enqueued on torch's current stream and nothing else (dpq_ip_tables_device)."""
+        import torch
+        assert queries.is_cuda and queries.dtype == torch.float32 and queries.is_contiguous()
+        info = self.info()
+        nq = queries.shape[0]
+        if out_tables is None:
+            out_tables = torch.empty((nq, info["M"], info["K"]), dtype=torch.float32, device=queries.device)
+        if out_bias is None:
+            out_bias = torch.empty((nq,), dtype=torch.float32, device=queries.device)
+        stream = torch.cuda.current_stream(queries.device).cuda_stream
+        check(self._lib.dpq_ip_tables_device(self._h, ctypes.c_void_p(queries.data_ptr()), nq,
+                                             ctypes.c_void_p(out_tables.data_ptr()), ctypes.c_void_p(out_bias.data_ptr()),
+                                             ctypes.c_void_p(stream)), "dpq_ip_tables_device")
+        return out_tables, out_bias
+
+    def query_batch_ip(self, queries, top_k, id_filter=None):
+        """The top_k codes of the largest approximate inner product with each query (dpq_query_batch_ip).  Returns
+        (ids int32 [nq][k], scores float32 [nq][k] descending, gaps float32 [nq][k], bias float32 [nq]); padding rows
+        are -1 / -inf / +inf."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        nq = q.shape[0]
+        ids = np.empty((nq, top_k), dtype=np.int32)
+        scores = np.empty((nq, top_k), dtype=np.float32)
+        gaps = np.empty((nq, top_k), dtype=np.float32)
+        bias = np.empty(nq, dtype=np.float32)
+        f = IdFilter._handle(id_filter) if id_filter is not None else None
+        check(self._lib.dpq_query_batch_ip(self._h, f, _np_ptr(q), nq, top_k, _np_ptr(ids), _np_ptr(scores), _np_ptr(gaps),
+                                           _np_ptr(bias)), "dpq_query_batch_ip")
+        return ids, scores, gaps, bias
+
+    def query_batch_ip_torch(self, queries, top_k, id_filter=None, out_ids=None, out_scores=None, out_gaps=None,
+                             out_bias=None):
+        """query_batch_ip on device tensors, synchronous on torch's current stream (dpq_query_batch_device_ip).  Returns
+        (ids, scores); gaps and bias are written where out_gaps / out_bias are given."""
+        import torch
+        assert queries.is_cuda and queries.dtype == torch.float32 and queries.is_contiguous()
+        nq = queries.shape[0]
+        if out_ids is None:
+            out_ids = torch.empty((nq, top_k), dtype=torch.int32, device=queries.device)
+        if out_scores is None:
+            out_scores = torch.empty((nq, top_k), dtype=torch.float32, device=queries.device)
+        stream = torch.cuda.current_stream(queries.device).cuda_stream
+        f = IdFilter._handle(id_filter) if id_filter is not None else None
+        opt = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        check(self._lib.dpq_query_batch_device_ip(self._h, f, ctypes.c_void_p(queries.data_ptr()), nq, top_k,
+                                                  ctypes.c_void_p(out_ids.data_ptr()), ctypes.c_void_p(out_scores.data_ptr()),
+                                                  opt(out_gaps), opt(out_bias), ctypes.c_void_p(stream)),
+              "dpq_query_batch_device_ip")
+        return out_ids, out_scores
+
     def set_vec_ids(self, vec_id):
         """The original vector id of every node this handle holds (dpq_set_vec_ids): `vec_id` is the handle's local
         slice, uint32 [node_hi - node_lo], of the builder's DFS position -> vector id array.  Kept on the device for
@@ -723,6 +845,10 @@ class RotatedIndex:
 
     def query_batch_torch(self, queries, top_k, **kw):
         return self.index.query_batch_torch(self._rotated(queries), top_k, **kw)
+
+    def query_batch_ip(self, queries, top_k, id_filter=None):
+        """An orthogonal rotation leaves inner products alone: rotate the queries, then the index's own call."""
+        return self.index.query_batch_ip(self._rotated_host(queries), top_k, id_filter=id_filter)
 
     def __getattr__(self, name):
         if name == "index":      # (not set yet: __init__ failed early)
@@ -1506,6 +1632,19 @@ def merge_topk_host(ids, dists):
     check(lib.dpq_merge_topk_host(_np_ptr(ids), _np_ptr(dists), n_lists, nq, k, _np_ptr(oi), _np_ptr(od)),
           "dpq_merge_topk_host")
     return oi, od
+
+
+def ip_scores(bias, gaps, ids):
+    """float32 [nq][k] inner-product scores of (merged) gaps: (float)((double)bias[q] - (double)gap), -inf for a padding
+    row (dpq_ip_scores; host only, no device)."""
+    lib = _lib.load()
+    g = np.ascontiguousarray(gaps, dtype=np.float32)
+    i = np.ascontiguousarray(ids, dtype=np.int32)
+    b = np.ascontiguousarray(bias, dtype=np.float32).ravel()
+    assert g.ndim == 2 and i.shape == g.shape and b.shape == (g.shape[0],)
+    out = np.empty(g.shape, dtype=np.float32)
+    check(lib.dpq_ip_scores(_np_ptr(b), _np_ptr(g), _np_ptr(i), g.shape[0], g.shape[1], _np_ptr(out)), "dpq_ip_scores")
+    return out
 
 
 def _merge_out(out, nq, k, device):

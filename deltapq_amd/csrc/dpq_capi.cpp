@@ -1,6 +1,6 @@
 // dpq_capi.cpp -- the core of the C-ABI of include/deltapq_amd.h: the error slot, index lifetime, the
 // threshold-cascade driver around the scan/select kernels, range search, profiling and the developer hooks.  The
-// other entry points live by feature in dpq_capi_{io,train,flat,lookup,filter,refine}.cpp; dpq_capi_internal.h is
+// other entry points live by feature in dpq_capi_{io,train,flat,lookup,filter,refine,tables}.cpp; dpq_capi_internal.h is
 // what they share.
 // Compiled with hipcc (HIP runtime calls only; kernels live in dpq_kernels.hip).
 //
@@ -433,16 +433,21 @@ int prepare_batch(dpq_index* x, Batch* b) {
 // the whole shard (the common case): the handle's resident plain-code image serves every batch (decoded by the first
 // one, ahead of its table build) and every level scans its slice of it.  Otherwise each level decodes its own tiles
 // in list order.
-int build_tables(dpq_index* x, const Batch& b, const float* d_queries, hipStream_t stream) {
+int build_tables(dpq_index* x, const Batch& b, const TableSource& src, hipStream_t stream) {
     Workspace& w = x->ws();
     int rc;
     if (b.one_tile && (rc = ensure_plain_image(x, stream))) return rc;
     {
         Timer t(x, stream, 0);
         // batches that scan the plain-code scratch also get the tables in the scratch's label order
-        DPQ_HIP(dpq::launch_lut_build(x->d_codebook, d_queries, b.nq, b.nqp, x->M, x->K, x->Ds, w.d_lut32, w.d_lut_min,
-                                      nullptr, w.d_overflow, b.scratch ? x->d_relabel.get() : nullptr, w.d_lut32r,
-                                      x->tune.tighten ? w.d_tight.get() : nullptr, stream));
+        const uint8_t* relabel = b.scratch ? x->d_relabel.get() : nullptr;
+        uint32_t* tight = x->tune.tighten ? w.d_tight.get() : nullptr;
+        if (src.d_tables)  // the caller's tables (dpq_query_batch_tables): the same workspace state, entries validated
+            DPQ_HIP(dpq::launch_tables_ingest(src.d_tables, b.nq, b.nqp, x->M, x->K, w.d_lut32, w.d_lut_min, w.d_overflow,
+                                              relabel, w.d_lut32r, tight, src.d_bad, stream));
+        else
+            DPQ_HIP(dpq::launch_lut_build(x->d_codebook, src.d_queries, b.nq, b.nqp, x->M, x->K, x->Ds, w.d_lut32,
+                                          w.d_lut_min, nullptr, w.d_overflow, relabel, w.d_lut32r, tight, stream));
     }
     if (x->prof) x->prof_acc.lut_launches++;
     return DPQ_OK;
@@ -798,7 +803,7 @@ int rerun_overflowed(dpq_index* x, const Batch& b, dpq::ScanArgs sa, dpq::Select
 // dpq_finish looks at the word later.
 // filt (synchronous calls only): the batch of dpq_query_batch_*_filtered -- the bootstrap, the scans and level 0 see only
 // the nodes it allows.
-int run_batch(dpq_index* x, const float* d_queries, int nq, int top_k, int32_t* d_ids, float* d_dists,
+int run_batch(dpq_index* x, const TableSource& src, int nq, int top_k, int32_t* d_ids, float* d_dists,
               hipStream_t stream, int flag_slot = 0, const dpq_filter* filt = nullptr) {
     Batch b = batch_mode(x, nq, top_k, filt != nullptr);
     int rc;
@@ -814,7 +819,7 @@ int run_batch(dpq_index* x, const float* d_queries, int nq, int top_k, int32_t* 
             filt->l0_n = n0;
         }
     }
-    if ((rc = build_tables(x, b, d_queries, stream))) return rc;
+    if ((rc = build_tables(x, b, src, stream))) return rc;
     x->h_any[flag_slot] = 0;  // the slot is free: its previous batch has been finished
     dpq::ScanArgs sa = batch_scan_args(x, b);
     sa.filter = filt ? filt->bits.get() : nullptr;
@@ -984,9 +989,9 @@ int range_emit(dpq_index* x, dpq::RangeEmitArgs ea, int n_slots, const std::vect
     return DPQ_OK;
 }
 
-// One sub-batch (nq <= kMaxBatchQueries) of dpq_range_search: d_queries on the device, radii on the host; appends its
-// lists to res (res->lims[base .. base + nq] are filled, base = the number of queries before it).
-int range_batch(dpq_index* x, const float* d_queries, int nq, const float* radii, int base, dpq_range_result* res,
+// One sub-batch (nq <= kMaxBatchQueries) of dpq_range_search: queries or tables on the device, radii on the host; appends
+// its lists to res (res->lims[base .. base + nq] are filled, base = the number of queries before it).
+int range_batch(dpq_index* x, const TableSource& src, int nq, const float* radii, int base, dpq_range_result* res,
                 hipStream_t stream) {
     RangeWs& R = x->range;
     const int QG = dpq::queries_per_group(x->M);
@@ -1024,7 +1029,7 @@ int range_batch(dpq_index* x, const float* d_queries, int nq, const float* radii
     if (b.scratch && (rc = ensure_batch_raw(x))) return rc;
     const bool tiled = b.scratch && !b.one_tile;
     if (tiled && (rc = ensure_order(x))) return rc;
-    if ((rc = build_tables(x, b, d_queries, stream))) return rc;
+    if ((rc = build_tables(x, b, src, stream))) return rc;
 
     // regions: splits_for's workgroups per query group, auto-sized as a top-k level's (or dpq_open_opts.cand_capacity)
     const int nseg = x->img.n_segments;
@@ -1608,6 +1613,7 @@ int dpq_close(dpq_index* x) {
     if (x->copy_out) hipStreamDestroy(x->copy_out);
     if (x->h_overflow) hipHostFree(x->h_overflow);
     if (x->h_any) hipHostFree(x->h_any);
+    if (x->h_tables_bad) hipHostFree(x->h_tables_bad);
     delete x;  // (the device buffers go with it)
     return DPQ_OK;
     });
@@ -1657,7 +1663,7 @@ int dpq_finish(dpq_index* x) {
         if (*reinterpret_cast<volatile uint32_t*>(x->h_any + p.flag_slot) == 0) continue;
         // a query of this batch dropped candidates: answer the batch again, synchronously (it reruns what overflows)
         x->finish_reruns++;
-        int rc = run_batch(x, p.d_queries, p.nq, p.top_k, p.d_ids, p.d_dists, p.stream);
+        int rc = run_batch(x, TableSource{p.d_queries}, p.nq, p.top_k, p.d_ids, p.d_dists, p.stream);
         if (p.host_slot >= 0) x->host_slots[p.host_slot].redo = true;  // its results went down before this
         if (rc && !first_rc) {
             first_rc = rc;
@@ -1776,7 +1782,7 @@ int enqueue_async(dpq_index* x, const float* d_queries, int nq, int top_k, int32
             DPQ_HIP(hipEventRecord(x->lane_ready[lane], user));
             DPQ_HIP(hipStreamWaitEvent(stream, x->lane_ready[lane], 0));
         }
-        rc = run_batch(x, d_queries + (size_t)base * D, n, top_k, d_ids + (size_t)base * top_k,
+        rc = run_batch(x, TableSource{d_queries + (size_t)base * D}, n, top_k, d_ids + (size_t)base * top_k,
                        d_dists + (size_t)base * top_k, stream, slot);
         if (rc) return rc;
         x->pending.push_back({d_queries + (size_t)base * D, n, top_k, d_ids + (size_t)base * top_k,
@@ -1802,19 +1808,53 @@ int query_device(dpq_index* x, const dpq_filter* filt, const float* d_queries, i
     }
     int rc = check_batch_args(x, d_queries, nq, top_k, d_ids, d_dists);
     if (rc || nq == 0) return rc;
+    return query_device_src(x, filt, TableSource{d_queries}, nq, top_k, d_ids, d_dists, hip_stream);
+}
+
+namespace {
+// The source of the sub-batch of n queries from query `base` on: device pointers advanced; tables in host memory go up
+// into the handle's staging buffer (the batch before it has been answered: every caller is synchronous).
+int sub_source(dpq_index* x, const TableSource& src, int base, int n, TableSource* s) {
+    const size_t q_floats = (size_t)x->M * x->Ds, t_floats = (size_t)x->M * x->K;
+    *s = src;
+    if (s->d_queries) s->d_queries += (size_t)base * q_floats;
+    if (s->d_tables) s->d_tables += (size_t)base * t_floats;
+    if (src.h_tables) {
+        DPQ_HIP(hipMemcpy(x->d_tab_stage, src.h_tables + (size_t)base * t_floats, (size_t)n * t_floats * sizeof(float),
+                          hipMemcpyHostToDevice));
+        s->d_tables = x->d_tab_stage;
+    }
+    return DPQ_OK;
+}
+}  // namespace
+
+int query_device_src(dpq_index* x, const dpq_filter* filt, const TableSource& src, int nq, int top_k, int32_t* d_ids,
+                     float* d_dists, void* hip_stream) {
     DPQ_HIP(hipSetDevice(x->device));
     hipStream_t stream = reinterpret_cast<hipStream_t>(hip_stream);
-    const int D = x->M * x->Ds;
     for (int base = 0; base < nq; base += kMaxBatchQueries) {
         const int n = std::min(kMaxBatchQueries, nq - base);
-        rc = run_batch(x, d_queries + (size_t)base * D, n, top_k, d_ids + (size_t)base * top_k,
-                       d_dists + (size_t)base * top_k, stream, 0, filt);
+        TableSource s;
+        int rc = sub_source(x, src, base, n, &s);
+        if (rc) return rc;
+        rc = run_batch(x, s, n, top_k, d_ids + (size_t)base * top_k, d_dists + (size_t)base * top_k, stream, 0, filt);
         if (rc) return rc;
     }
     if (x->prof) {
         x->prof_acc.query_batches++;
         x->prof_acc.queries += nq;
     }
+    return DPQ_OK;
+}
+
+int ensure_out_stage(dpq_index* x, size_t oe) {
+    if (oe <= x->out_stage_elems) return DPQ_OK;
+    x->out_stage_elems = 0;
+    x->d_dists_stage.reset();
+    int rc = x->d_ids_stage.alloc(oe);
+    if (!rc) rc = x->d_dists_stage.alloc(oe);
+    if (rc) return rc;
+    x->out_stage_elems = oe;
     return DPQ_OK;
 }
 
@@ -1833,14 +1873,7 @@ int query_host(dpq_index* x, const dpq_filter* filt, const float* queries, int n
         if (rc) return rc;
         x->q_stage_floats = qf;
     }
-    if (oe > x->out_stage_elems) {
-        x->out_stage_elems = 0;
-        x->d_dists_stage.reset();
-        int rc = x->d_ids_stage.alloc(oe);
-        if (!rc) rc = x->d_dists_stage.alloc(oe);
-        if (rc) return rc;
-        x->out_stage_elems = oe;
-    }
+    if (int rc = ensure_out_stage(x, oe)) return rc;
     DPQ_HIP(hipMemcpy(x->d_q_stage, queries, qf * sizeof(float), hipMemcpyHostToDevice));
     int rc = query_device(x, filt, x->d_q_stage, nq, top_k, x->d_ids_stage, x->d_dists_stage, nullptr);
     if (rc) return rc;
@@ -1899,10 +1932,6 @@ int dpq_range_search(dpq_index* x, const float* queries, int nq, const float* ra
         int rc = dpq_finish(x);
         if (rc) return rc;
     }
-    x->range.last_max_keys = 0;
-    std::unique_ptr<dpq_range_result> res(new dpq_range_result());
-    res->nq = nq;
-    res->lims.assign((size_t)nq + 1, 0);
     if (nq > 0) {
         DPQ_HIP(hipSetDevice(x->device));
         const size_t qf = (size_t)nq * x->M * x->Ds;
@@ -1913,11 +1942,26 @@ int dpq_range_search(dpq_index* x, const float* queries, int nq, const float* ra
             x->q_stage_floats = qf;
         }
         DPQ_HIP(hipMemcpy(x->d_q_stage, queries, qf * sizeof(float), hipMemcpyHostToDevice));
-        const int D = x->M * x->Ds;
+    }
+    return range_search_src(x, TableSource{x->d_q_stage}, nq, radii, out);
+    });
+}
+
+}  // extern "C"
+
+int range_search_src(dpq_index* x, const TableSource& src, int nq, const float* radii, dpq_range_result** out) {
+    x->range.last_max_keys = 0;
+    std::unique_ptr<dpq_range_result> res(new dpq_range_result());
+    res->nq = nq;
+    res->lims.assign((size_t)nq + 1, 0);
+    if (nq > 0) {
+        DPQ_HIP(hipSetDevice(x->device));
         int rc = DPQ_OK;
         for (int base = 0; base < nq && !rc; base += kMaxBatchQueries) {
             const int n = std::min(kMaxBatchQueries, nq - base);
-            rc = range_batch(x, x->d_q_stage + (size_t)base * D, n, radii + base, base, res.get(), nullptr);
+            TableSource s;
+            if ((rc = sub_source(x, src, base, n, &s))) break;
+            rc = range_batch(x, s, n, radii + base, base, res.get(), nullptr);
         }
         range_trim(x);
         if (rc) return rc;
@@ -1925,8 +1969,9 @@ int dpq_range_search(dpq_index* x, const float* queries, int nq, const float* ra
     }
     *out = res.release();
     return DPQ_OK;
-    });
 }
+
+extern "C" {
 
 int dpq_range_result_get(const dpq_range_result* r, int32_t* nq, const int64_t** lims, const int32_t** ids,
                          const float** dists) {

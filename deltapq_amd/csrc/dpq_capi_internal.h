@@ -30,6 +30,7 @@
 #include "dpq_opq.h"
 #include "dpq_procrustes.h"
 #include "dpq_refine.h"
+#include "dpq_tables.h"
 #include "dpq_train.h"
 
 // Nothing declared here is part of the library's interface: all of it stays out of the dynamic symbol table.
@@ -236,6 +237,15 @@ struct LookupWs {
     size_t ids_n = 0, codes_n = 0, vecs_n = 0, tile_n = 0, tile_segs_n = 0;
 };
 
+// Where a batch's exact tables come from: queries against the handle's codebook (lut_build_kernel), or the caller's own
+// tables[nq][M][K] (tables_ingest_kernel), which raises *d_bad when an entry is not a distance.
+struct TableSource {
+    const float* d_queries = nullptr;
+    const float* d_tables = nullptr;
+    uint32_t* d_bad = nullptr;
+    const float* h_tables = nullptr;  // host forms: tables in host memory, staged one sub-batch at a time (d_tab_stage)
+};
+
 // The device buffers a batch works in (one per pipeline lane), sized for `slots` padded queries and `cap` candidates each.
 struct Workspace {
     int slots = 0, cap = 0;
@@ -356,6 +366,12 @@ struct dpq_index {
     DevBuf<uint32_t> d_vec_id;       // [n_local] local node -> original vector id (dpq_set_vec_ids; the _vec filter constructors)
     bool vec_ids_set = false;
     DevBuf<unsigned long long> d_filter_count;  // [1] the set bits of the filter being built (dpq_filter_create_* on the device)
+    // search by tables and inner-product search (dpq_capi_tables.cpp), kept until dpq_close
+    uint32_t* h_tables_bad = nullptr;    // pinned + mapped word tables_ingest_kernel raises; d_tables_bad: its device address
+    uint32_t* d_tables_bad = nullptr;
+    DevBuf<float> d_tab_stage;           // [one sub-batch][M][K] tables of the host forms / of the inner-product forms
+    DevBuf<float> d_ip_bias, d_ip_gaps;  // [nq], [nq][top_k] where the caller of an inner-product form passes none
+    size_t tab_stage_n = 0, ip_bias_n = 0, ip_gaps_n = 0;
     DevBuf<uint32_t> d_order;
     DevBuf<uint32_t> d_l0_id, d_l0_code;
     int l0_segments = 0;
@@ -407,6 +423,12 @@ int check_batch_args(dpq_index* x, const float* d_queries, int nq, int top_k, in
 int query_device(dpq_index* x, const dpq_filter* filt, const float* d_queries, int nq, int top_k, int32_t* d_ids,
                  float* d_dists, void* hip_stream);                                                             // dpq_capi.cpp
 int check_filter(const dpq_index* x, const dpq_filter* f);                                                      // dpq_capi.cpp
+// query_device / dpq_range_search behind their argument checks, for either table source (src's pointers name the first
+// query; sub-batches advance them); the caller has finished the pending batches
+int query_device_src(dpq_index* x, const dpq_filter* filt, const TableSource& src, int nq, int top_k, int32_t* d_ids,
+                     float* d_dists, void* hip_stream);                                                         // dpq_capi.cpp
+int range_search_src(dpq_index* x, const TableSource& src, int nq, const float* radii, dpq_range_result** out);  // dpq_capi.cpp
+int ensure_out_stage(dpq_index* x, size_t elems);  // d_ids_stage / d_dists_stage                                  dpq_capi.cpp
 int flat_device_present(const std::string& who);                                                                // dpq_capi_flat.cpp
 bool lookup_id_ok(const dpq_index* x, int64_t id);                                                              // dpq_capi_lookup.cpp
 int lookup_on_device(dpq_index* x, const int32_t* d_ids, int64_t n, uint8_t* d_codes, float* d_vecs, hipStream_t stream,

@@ -28,6 +28,9 @@ constexpr int kTightWords = kTightSplits * kTightBuckets / 4;  // u32 words per 
 constexpr int kS1Replicas = 8, kS1ReplicaWords = 512;
 constexpr int kS1HistWords = kS1Replicas * kS1ReplicaWords;
 static_assert(queries_per_group(8) * kTightWords >= kS1HistWords, "strand1's histogram exceeds what one query group clears");
+// The table build (lut_build_kernel; tables_ingest_kernel of dpq_tables.hip leaves the same state)
+constexpr int kLutQueries = 8;
+constexpr int kLutMinParts = 4;  // per (query, m): one partial minimum per wavefront of the 256-thread block
 
 // The SoA image of one shard in HBM (see DESIGN.md "Data layout").
 struct DeviceImage {

@@ -97,9 +97,6 @@ __device__ __forceinline__ uint64_t make_key(float d, uint32_t id) {
 // quantisation.  Also clears the per-slot candidate counters and overflow
 // flags of the batch (saves two fill launches per batch).
 // ---------------------------------------------------------------------------
-constexpr int kLutQueries = 8;
-constexpr int kLutMinParts = 4;  // per (query, m): one partial minimum per wavefront of the 256-thread block
-
 __device__ __forceinline__ float lut_min_of(const float* __restrict__ lut_min, size_t q, int M, int m) {
     const float4 p = *reinterpret_cast<const float4*>(lut_min + (q * M + m) * kLutMinParts);
     return fminf(fminf(p.x, p.y), fminf(p.z, p.w));

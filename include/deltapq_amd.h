@@ -42,6 +42,10 @@
  *   (none: FAISS's IndexFlat::range_search)     dpq_flat_range_search[_u8], dpq_range_recall
  *   (none: FAISS's IndexRefine over two PQ      dpq_refine_build / dpq_refine_rerank / dpq_query_batch_refined
  *     indexes; ADC+R)                             (a second PQ level over the residuals re-ranks a shortlist)
+ *   (none: FAISS's METRIC_INNER_PRODUCT over    dpq_query_batch_ip / dpq_ip_tables / dpq_ip_scores
+ *     PQ codes)
+ *   (none: a caller's own distance tables:      dpq_query_batch_tables / dpq_range_search_tables
+ *     weights, masks, residual queries)
  *
  * Conventions: plain pointers and sizes only; the caller owns every host
  * buffer it passes, the library owns device memory.  Every function returns a
@@ -941,6 +945,69 @@ int dpq_opq_train(const float* vectors, int64_t n, int D, int M, int K, const dp
  * truncated, not square or above D = 1024 is DPQ_ERR_FORMAT. */
 int dpq_write_rotation(const char* path, const float* R, int D);
 int dpq_read_rotation(const char* path, int32_t* D, float* out);
+
+/* ---- search by distance tables, and inner product -------------------------------
+ * Every search above builds, per query, M tables T[m][k] = |q_m - c[m][k]|^2 and from there on reads nothing but
+ * those tables.  These calls take the tables from the caller instead: tables[nq][M][K], fp32, row-major, M and K the
+ * handle's.
+ *   Relation to the query forms   The answer is what dpq_query_batch[_filtered] / dpq_range_search give, with
+ *           tables[q][m][k] standing where the L2 rule's T[m][k] of query q stands: the distance of a code is the
+ *           fp64 sum of its M fp32 entries rounded once to fp32 (a dpq_open_plain_* handle: fp32 accumulation in
+ *           ascending m), results are ordered by (distance bits, id), and ids, padding, shards, parts, prefixes, the
+ *           even-N id, DPQ_ERR_TOPK and the sub-batches of 2048 queries are those of the query forms.
+ *   No codebook   The calls work before dpq_set_codebook.  A handle with a codebook uses its centroid neighbour lists
+ *           as they are: they only decide which cells the threshold bootstrap walks first; every threshold comes
+ *           from nodes evaluated with the caller's tables, so the answer does not depend on them.
+ *   Entries   A finite value >= 0 or +inf is an ordinary value; -0.0 is read as +0.0.  A negative entry, -inf or a NaN
+ *           is DPQ_ERR_ARG: the host forms check every entry on the host before any device work; the device form
+ *           raises one flag word that comes back with the call's closing synchronisation, and its outputs are then
+ *           unspecified.  No kernel behind the ingest ever sees such an entry (it reads +inf in its place).
+ *   Exact tables   Call a query's table exact when its finite non-zero entries are whole multiples of one power of two
+ *           2^g and its per-sub-space maxima add up to less than 2^53 * 2^g.  Every fp64 sum of M entries is then exact
+ *           in any order and the answer is defined to the bit on every scan path.  For other tables a distance is the
+ *           fp32 rounding of an fp64 sum of the entries in an order the scan path chooses (what L2 tables get too).
+ *           Sufficient: at M = 8, finite non-zero fp32 entries within a factor 2^26 of each other; 2^25 at M = 16.
+ *   Calling conventions   Synchronous; pending asynchronous batches are finished first; plans, workspaces and results
+ *           of later calls are unaffected.  The host forms stage one sub-batch of tables on the device, at most
+ *           2048 * M * K * 4 bytes, kept until dpq_close.  filter may be NULL.  The asynchronous, ordered, host-async
+ *           and refined pipelines have no tables form. */
+int dpq_query_batch_tables(dpq_index* idx, const dpq_filter* filter, const float* tables, int nq, int top_k,
+                           int32_t* ids, float* dists);
+/* Device pointers on the handle's GPU, on `hip_stream` (NULL = default stream); returns with the results complete. */
+int dpq_query_batch_device_tables(dpq_index* idx, const dpq_filter* filter, const float* d_tables, int nq, int top_k,
+                                  int32_t* d_ids, float* d_dists, void* hip_stream);
+int dpq_range_search_tables(dpq_index* idx, const float* tables, int nq, const float* radii, dpq_range_result** out);
+
+/* Inner-product search (FAISS's METRIC_INNER_PRODUCT over PQ codes) on top of the table search.  NO REFERENCE
+ * SEMANTICS: the rules are this build's own, restated in tests/_tables_restatement.py and met by the GPU bit for bit.
+ * With the handle's M, K, Ds, its codebook c and a query q[M * Ds]:
+ *   Dot product   p[m][k] = (float)acc: acc = +0.0 in fp64; for d = 0 .. Ds-1 ascending
+ *           acc = acc + (double)q[m * Ds + d] * (double)c[m][k][d] (the product of two fp32 values is exact in fp64, so a
+ *           fused multiply-add gives the same bits: the rotation rule of the OPQ section).
+ *   Maximum   top[m] = the largest p[m][k] over k < K.
+ *   Table entry   e[m][k] = top[m] - p[m][k], one fp32 subtraction: >= +0, and +0 at every maximum.
+ *   Bias   B = (float) of the fp64 sum from +0.0, m ascending, of (double)top[m].
+ *   Gap   g of a code = dpq_query_batch_tables' distance under the table e.  Results are ordered by (g bits, id): by
+ *           descending approximate inner product, the lowest ids first among equals.
+ *   Score   s = (float)((double)B - (double)g).  A padding row is id -1, gap +inf, score -inf.
+ *   Inputs   finite queries and codewords with finite dot products; anything else is out of scope (the search forms
+ *           return DPQ_ERR_ARG where a NaN reaches a table).
+ * B depends on the query and the codebook only: shards merge their (ids, gaps) with dpq_merge_topk_* unchanged and
+ * convert once with dpq_ip_scores.  s is the usual ADC inner product sum_m <q_m, c_m> to within the roundings named; an
+ * orthogonal OPQ rotation leaves it alone (rotate the queries first).  The search forms keep one sub-batch of tables
+ * (the buffer of the table forms, at most 2048 * M * K * 4 bytes) and, where the caller passes none, their gaps and
+ * biases with the handle until dpq_close. */
+/* Needs dpq_set_codebook (else DPQ_ERR_STATE).  tables_out[nq][M][K], bias_out[nq]. */
+int dpq_ip_tables(dpq_index* idx, const float* queries, int nq, float* tables_out, float* bias_out);
+/* Enqueue only: no allocation, no synchronisation (dpq_rotate_device's convention). */
+int dpq_ip_tables_device(dpq_index* idx, const float* d_queries, int nq, float* d_tables, float* d_bias, void* hip_stream);
+/* scores[nq][top_k] descending; gaps_out [nq][top_k] and bias_out [nq] may be NULL.  filter may be NULL. */
+int dpq_query_batch_ip(dpq_index* idx, const dpq_filter* filter, const float* queries, int nq, int top_k, int32_t* ids,
+                       float* scores, float* gaps_out, float* bias_out);
+int dpq_query_batch_device_ip(dpq_index* idx, const dpq_filter* filter, const float* d_queries, int nq, int top_k,
+                              int32_t* d_ids, float* d_scores, float* d_gaps, float* d_bias, void* hip_stream);
+/* Host only, no device: scores from merged gaps (shards).  A negative id gives -inf. */
+int dpq_ip_scores(const float* bias, const float* gaps, const int32_t* ids, int nq, int top_k, float* scores_out);
 
 /* ---- measurement -------------------------------------------------------- */
 int dpq_profile_enable(dpq_index* idx, int on);  /* 0 off, 1 every kernel, 2 scan launches only (less event overhead) */
