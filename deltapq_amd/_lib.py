@@ -229,6 +229,8 @@ SYMBOLS = [
     ("dpq_debug_select_time", ctypes.c_int, [_VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, P(ctypes.c_float)]),
     ("dpq_debug_strand1_stamps", ctypes.c_int, [_VP, _VP, ctypes.c_int]),
     ("dpq_debug_range_keys", ctypes.c_int, [_VP, P(c_i64)]),
+    ("dpq_debug_filter_tables", ctypes.c_int, [_VP, ctypes.c_int, _VP, c_i64]),
+    ("dpq_debug_relabel", ctypes.c_int, [_VP, _VP, ctypes.c_int]),
 ]
 
 _lib = None

@@ -95,6 +95,7 @@ int ensure_workspace(dpq_index* x, int slots, int cap) {
     if ((rc = w.d_lut32.alloc((size_t)slots * x->M * 256))) return rc;
     if (x->d_relabel && (rc = w.d_lut32r.alloc((size_t)slots * x->M * 256))) return rc;
     if ((rc = w.d_lut_min.alloc((size_t)slots * x->M * 4))) return rc;  // four partial minima per (query, m)
+    if ((rc = w.d_lut_stat.alloc((size_t)slots * x->M))) return rc;
     if ((rc = w.d_qtab.alloc((size_t)(slots / dpq::queries_per_group(x->M) + 1) *
                              (dpq::qtab_bytes_per_group(x->M) / sizeof(uint4)))))
         return rc;
@@ -104,6 +105,7 @@ int ensure_workspace(dpq_index* x, int slots, int cap) {
     if ((rc = w.d_overflow.alloc((size_t)slots))) return rc;
     if ((rc = w.d_tight.alloc((size_t)slots * dpq::kTightWords))) return rc;
     if ((rc = w.d_thr_key.alloc((size_t)slots))) return rc;
+    if ((rc = w.d_dbg_thr.alloc((size_t)slots))) return rc;
     if (!x->h_overflow) DPQ_HIP(hipHostMalloc(reinterpret_cast<void**>(&x->h_overflow), sizeof(uint32_t) * 4096));
     if (!x->d_counters) {
         if ((rc = x->d_counters.alloc(2))) return rc;
@@ -433,7 +435,7 @@ int prepare_batch(dpq_index* x, Batch* b) {
 // the whole shard (the common case): the handle's resident plain-code image serves every batch (decoded by the first
 // one, ahead of its table build) and every level scans its slice of it.  Otherwise each level decodes its own tiles
 // in list order.
-int build_tables(dpq_index* x, const Batch& b, const TableSource& src, hipStream_t stream) {
+int build_tables(dpq_index* x, const Batch& b, const TableSource& src, hipStream_t stream, bool row_stats = true) {
     Workspace& w = x->ws();
     int rc;
     if (b.one_tile && (rc = ensure_plain_image(x, stream))) return rc;
@@ -448,6 +450,9 @@ int build_tables(dpq_index* x, const Batch& b, const TableSource& src, hipStream
         else
             DPQ_HIP(dpq::launch_lut_build(x->d_codebook, src.d_queries, b.nq, b.nqp, x->M, x->K, x->Ds, w.d_lut32,
                                           w.d_lut_min, nullptr, w.d_overflow, relabel, w.d_lut32r, tight, stream));
+        // the rows' order statistics the filter's saturations are split by (M = 8): behind the tables, under the other
+        // lane's scan like them.  row_stats false: a batch of the stream pass, which builds no filter tables
+        if (row_stats) DPQ_HIP(dpq::launch_row_stats(w.d_lut32, b.nq, x->M, w.d_lut_stat, stream));
     }
     if (x->prof) x->prof_acc.lut_launches++;
     return DPQ_OK;
@@ -462,6 +467,7 @@ dpq::ScanArgs batch_scan_args(const dpq_index* x, const Batch& b) {
     sa.fp32_accum = x->plain ? 1 : 0;
     sa.lut32 = b.labelled ? w.d_lut32r.get() : w.d_lut32.get();
     sa.lut_min = w.d_lut_min;
+    sa.lut_stat = w.d_lut_stat;
     sa.thr_key = w.d_thr_key;
     sa.slot_query = nullptr;
     sa.n_queries = b.nq;
@@ -555,6 +561,7 @@ int boot_level(dpq_index* x, const Batch& b, const dpq_filter* filt, hipStream_t
     ba.qtab = b.boot_tables ? w.d_qtab.get() : nullptr;
     ba.relabel = b.scratch ? x->d_relabel.get() : nullptr;
     ba.lut_min = w.d_lut_min;
+    ba.lut_stat = w.d_lut_stat;
     if (filt) {
         // Filtered: the k-th key among allowed nodes, from at most 8 x cap evaluated nodes.  The bound keeps the launch
         // within 8 x the unfiltered one's evaluations; a filter that allows 1/8 of the nodes or more still fills the key
@@ -647,7 +654,18 @@ int stream_level(dpq_index* x, const Batch& b, size_t l, const dpq::ScanArgs& sa
 // plain-code scratch (decode a tile in list order, scan it with all groups, next tile) where one tile does not hold the
 // shard.
 int filter_level(dpq_index* x, const Batch& b, size_t l, dpq::ScanArgs sa, dpq::SelectArgs& se, hipStream_t stream) {
-    const Workspace& w = x->ws();
+    Workspace& w = x->ws();
+    if (l == 1) {
+        // developer hook dpq_debug_filter_tables (DPQ_DEV=1 only): the thresholds the first level's tables are built from,
+        // before the selects lower them
+        w.dbg_qtab_groups = b.ngroups;
+        w.dbg_qtab_nq = 0;
+        if (dev_mode()) {
+            DPQ_HIP(hipMemcpyAsync(w.d_dbg_thr.get(), sa.thr_key, sizeof(uint64_t) * (size_t)b.nqp, hipMemcpyDeviceToDevice, stream));
+            w.dbg_qtab_nq = b.nq;
+        }
+    }
+    w.dbg_qtab_levels++;
     const Regions rg = regions_for(x, sa.n_seg_pass, b.ngroups, b.top_k, b.cap);
     sa.region_cap = se.region_cap = rg.region_cap;
     se.n_regions = 1 + rg.splits;
@@ -763,6 +781,8 @@ int rerun_overflowed(dpq_index* x, const Batch& b, dpq::ScanArgs sa, dpq::Select
         sa.cand_stride = stride2;
         sa.region_cap = (int32_t)rcap2;
         sa.qtab = c_qtab;
+        if (b.direct && attempt == 0)  // a batch of the stream pass left no row statistics for the filter tables
+            chk(dpq::launch_row_stats(w.d_lut32, b.nq, x->M, w.d_lut_stat, stream));
         chk(dpq::launch_quantise(sa, ng2, stream));
         chk(dpq::launch_scan(sa, ng2, splits2, stream));
         std::vector<uint32_t> h_cnt((size_t)slots2 * dpq::kRegionStride, 0);
@@ -819,7 +839,8 @@ int run_batch(dpq_index* x, const TableSource& src, int nq, int top_k, int32_t* 
             filt->l0_n = n0;
         }
     }
-    if ((rc = build_tables(x, b, src, stream))) return rc;
+    if ((rc = build_tables(x, b, src, stream, !b.direct))) return rc;
+    x->ws().dbg_qtab_levels = 0;
     x->h_any[flag_slot] = 0;  // the slot is free: its previous batch has been finished
     dpq::ScanArgs sa = batch_scan_args(x, b);
     sa.filter = filt ? filt->bits.get() : nullptr;
@@ -888,7 +909,8 @@ bool range_thr_key(float r, uint64_t* key) {
 // The filter scan of one range launch: the slots' tables from their thresholds, then every segment -- in tiles of the
 // plain-code scratch where one tile does not hold the shard (as filter_level does).
 int range_scan(dpq_index* x, const Batch& b, dpq::ScanArgs sa, int n_groups, int splits, hipStream_t stream) {
-    const Workspace& w = x->ws();
+    Workspace& w = x->ws();
+    w.dbg_qtab_levels = 0;  // (not a batch's first filter level: dpq_debug_filter_tables)
     DPQ_HIP(hipMemsetAsync(sa.cand_count, 0, sizeof(uint32_t) * (size_t)n_groups * dpq::queries_per_group(x->M) *
                                                  dpq::kRegionStride, stream));
     if (sa.n_seg_pass <= 0) return DPQ_OK;
@@ -1042,6 +1064,7 @@ int range_batch(dpq_index* x, const TableSource& src, int nq, const float* radii
     sa.fp32_accum = x->plain ? 1 : 0;
     sa.lut32 = b.labelled ? w.d_lut32r.get() : w.d_lut32.get();
     sa.lut_min = w.d_lut_min;
+    sa.lut_stat = w.d_lut_stat;
     sa.thr_key = R.thr_key;
     sa.slot_query = R.slot_query;
     sa.n_queries = slots;
@@ -1166,6 +1189,7 @@ dpq::ScanArgs debug_scan_args(const dpq_index* x, int nq, int* splits) {
     sa.fp32_accum = x->plain ? 1 : 0;
     sa.lut32 = w.d_lut32;
     sa.lut_min = w.d_lut_min;
+    sa.lut_stat = w.d_lut_stat;
     sa.thr_key = w.d_thr_key;
     sa.slot_query = nullptr;
     sa.n_queries = nq;
@@ -2318,7 +2342,57 @@ int dpq_debug_boot_stamps(dpq_index* x, int nq, double* out) {
     });
 }
 
-// Developer hook: time the level-0 select (shared, query-independent candidate list).
+// Developer hook: the first filter level's tables of the last batch answered on `lane`, as the scan copies them into
+// LDS ([group][g][m][code] x 16 B), followed at M = 8 by one 16-byte record per slot (8 saturation bytes, the u64
+// threshold key the fields were built from) -- recomputed here by saturation_debug_kernel from the thresholds the
+// batch saved before its first level (a batch run with DPQ_DEV=1).  Waits for the device.
+int dpq_debug_filter_tables(dpq_index* x, int lane, void* out, int64_t bytes) {
+    return guarded([&]() -> int {
+    DPQ_DEV_ONLY();
+    if (!x || !out || lane < 0 || lane > 1) return fail(DPQ_ERR_ARG, "bad argument");
+    const Workspace& w = x->lane[lane];
+    if (!w.d_qtab || w.dbg_qtab_groups <= 0 || w.dbg_qtab_levels != 1)
+        return fail(DPQ_ERR_STATE, "the lane's last batch did not leave one filter level's tables");
+    const int slots = w.dbg_qtab_groups * dpq::queries_per_group(x->M);
+    const size_t tables = (size_t)w.dbg_qtab_groups * dpq::qtab_bytes_per_group(x->M);
+    const size_t records = x->M == 8 ? (size_t)slots * 16 : 0;
+    if (records && w.dbg_qtab_nq <= 0) return fail(DPQ_ERR_STATE, "the batch did not run with DPQ_DEV=1: no thresholds saved");
+    if (bytes < (int64_t)(tables + records)) return fail(DPQ_ERR_ARG, "the buffer is smaller than the tables");
+    DPQ_HIP(hipSetDevice(x->device));
+    DPQ_HIP(hipDeviceSynchronize());
+    DPQ_HIP(hipMemcpy(out, w.d_qtab.get(), tables, hipMemcpyDeviceToHost));
+    if (records) {
+        DevBuf<unsigned char> d_rec;
+        int rc;
+        if ((rc = d_rec.alloc(records))) return rc;
+        dpq::ScanArgs sa{};
+        sa.img.M = x->M;
+        sa.lut_min = w.d_lut_min;
+        sa.lut_stat = w.d_lut_stat;
+        sa.thr_key = w.d_dbg_thr;
+        sa.n_queries = w.dbg_qtab_nq;
+        DPQ_HIP(dpq::launch_saturation_debug(sa, slots, d_rec, nullptr));
+        DPQ_HIP(hipMemcpy(static_cast<char*>(out) + tables, d_rec.get(), records, hipMemcpyDeviceToHost));
+    }
+    return DPQ_OK;
+    });
+}
+
+// Developer hook: the code value -> label map of the plain-code scratch ([M][256] bytes; the rows of a scratch batch's
+// filter tables stand in label order).  DPQ_ERR_STATE: the handle has none (labels are code values).
+int dpq_debug_relabel(dpq_index* x, unsigned char* out, int bytes) {
+    return guarded([&]() -> int {
+    DPQ_DEV_ONLY();
+    if (!x || !out || bytes < x->M * 256) return fail(DPQ_ERR_ARG, "bad argument");
+    if (!x->d_relabel) return fail(DPQ_ERR_STATE, "the handle has no label map");
+    DPQ_HIP(hipSetDevice(x->device));
+    DPQ_HIP(hipDeviceSynchronize());
+    DPQ_HIP(hipMemcpy(out, x->d_relabel.get(), (size_t)x->M * 256, hipMemcpyDeviceToHost));
+    return DPQ_OK;
+    });
+}
+
+// Developer hook: candidate keys the largest scan launch of the last dpq_range_search laid out.
 int dpq_debug_range_keys(dpq_index* x, int64_t* max_keys) {
     DPQ_DEV_ONLY();
     if (!x || !max_keys) return fail(DPQ_ERR_ARG, "NULL argument");

@@ -252,6 +252,7 @@ struct Workspace {
     DevBuf<float> d_lut32;         // exact tables [query][8][256]
     DevBuf<float> d_lut32r;        // the same, rows by the labels of the plain-code scratch (only with d_relabel)
     DevBuf<float> d_lut_min;       // [query][8] minima (anchor of the filter quantisation)
+    DevBuf<float> d_lut_stat;      // [query][8] the 32nd largest entry of every row (M = 8: the split of the filter's saturations)
     DevBuf<uint4> d_qtab;          // [slot groups][128 KB] filter tables of the cascade level being scanned
     DevBuf<uint32_t> d_cand_count;
     DevBuf<uint32_t> d_overflow;   // [slots] overflow flags
@@ -261,6 +262,11 @@ struct Workspace {
     DevBuf<uint64_t> d_scratch;    // [slots][cap] contiguous copy of a slot's keys when they exceed the select's LDS list
     DevBuf<uint8_t> d_batch_raw;   // tiled plain-code scratch (a shard larger than one tile): the tile being scanned, decoded
                                    // per batch; kept when the rest grows.  A one-tile shard: dpq_index::d_plain_image
+    // dpq_debug_filter_tables: the query groups of the last batch's first filter level and how many filter levels have
+    // written d_qtab since that batch began (1: the first level's tables are still there)
+    int dbg_qtab_groups = 0, dbg_qtab_levels = 0;
+    int dbg_qtab_nq = 0;             // > 0: d_dbg_thr holds that batch's thresholds as its first level's tables saw them
+    DevBuf<uint64_t> d_dbg_thr;      // [slots] (written only in a process started with DPQ_DEV=1)
 };
 
 struct dpq_index {

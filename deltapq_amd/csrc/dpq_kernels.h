@@ -95,6 +95,9 @@ struct ScanArgs {
     // reaches the exact check, so it is neither a candidate nor counted by the in-scan tightening (scan_kernel's filtered
     // instantiations; the stream / strand kernels take no bitmap).
     const uint32_t* filter;
+    // M = 8: [query][M] the 32nd largest entry of every row of the exact tables (launch_row_stats): what launch_quantise
+    // splits a slot's saturation budget by.  The scans do not read it.
+    const float* lut_stat;
 };
 
 struct SelectArgs {
@@ -154,6 +157,7 @@ struct BootArgs {
     const uint32_t* filter;
     uint32_t id_base;              // global DFS position of local node 0 (mi_id - id_base = the bitmap's index)
     int32_t eval_cap;
+    const float* lut_stat;         // [query][M] as in ScanArgs (with qtab, M = 8)
 };
 
 // The level-0 list of a filtered batch: ids[i] stays where its node is allowed by `filter` (local bitmap, as in ScanArgs),
@@ -212,8 +216,14 @@ hipError_t launch_strand1(const ScanArgs& a, int n_slots, hipStream_t stream);
 int strand1_workgroups(int n_strips);
 constexpr int kStrand1Regions = 256;
 hipError_t launch_quantise(const ScanArgs& a, int n_slot_groups, hipStream_t stream);
+// M = 8: the 32nd largest entry of every row of queries [0, nq)'s exact tables -> d_lut_stat[nq][M], behind the table build
+// (other M: nothing).
+hipError_t launch_row_stats(const float* d_lut32, int nq, int M, float* d_lut_stat, hipStream_t stream);
 hipError_t launch_scan(const ScanArgs& a, int n_slot_groups, int splits, hipStream_t stream);
 size_t qtab_bytes_per_group(int M);
+// Developer hook (M = 8): d_out[slot] = (8 saturation bytes, u64 key) as a table builder would give slots [0, n_slots) of `a`
+// at a.thr_key (a.lut_min, a.lut_stat, a.slot_query / n_queries as in launch_quantise); n_slots a multiple of 8.
+hipError_t launch_saturation_debug(const ScanArgs& a, int n_slots, unsigned char* d_out, hipStream_t stream);
 int scan_stamp_count();
 hipError_t launch_select(const SelectArgs& a, int M, int n_slots, hipStream_t stream);
 hipError_t launch_bootstrap(const BootArgs& a, int M, int n_slots, hipStream_t stream);

@@ -331,21 +331,111 @@ __device__ __forceinline__ float filter_offset(const FilterScale& fs, float min_
     return sf;
 }
 
+// `clamp`: the saturation of the entry's sub-space plus the bias of m = 0 (sat_of + bias_m).
 template <int M>
-__device__ __forceinline__ uint32_t filter_field(float tv, float sc, float of, uint32_t bias_m) {
-    using C = Cfg<M>;
+__device__ __forceinline__ uint32_t filter_field(float tv, float sc, float of, uint32_t clamp) {
     // v_cvt_pk_u8_f32: float -> u8 clamped to [0, 255].  Half a unit is taken off first (in `of`), so whichever
     // way the conversion rounds, the byte is <= floor(value): the entry stays a lower bound (negative -> 0;
-    // inf/NaN of centroids beyond K -> SAT by the min).
-    const float fv = fminf(__fmaf_rn(tv, sc, of), (float)C::SAT + (float)bias_m);
+    // inf/NaN of centroids beyond K -> the saturation by the min).
+    const float fv = fminf(__fmaf_rn(tv, sc, of), (float)clamp);
     return __builtin_amdgcn_cvt_pk_u8_f32(fv, 0u, 0u);
 }
 
+// ---------------------------------------------------------------------------
+// Saturation per (slot, sub-space), M = 8 (byte accumulators).  Only the clamp of filter_field sees a saturation, and
+// min(x, SAT_m) is a lower bound of x whatever SAT_m is, so the SAT_BUDGET units a byte field leaves (Cfg) may be
+// split among a slot's sub-spaces in any way -- and a query's rows do not spread alike: a row whose far centroids lie
+// 40 units out is clipped by a uniform 23, a row that ends at 15 wastes 8 of them.  The rule, from the query's tables
+// and threshold alone (both table builders compute it; the scan never sees it):
+//   stat_m = the kSatRank-th largest of x_m[k] = trunc(clamp(fma(T[m][k], s32, off_m), 0, QT + 1)) over the row's 256
+//            entries (off_m: filter_offset without a bias; +inf of centroids beyond K counts as QT + 1).  x is
+//            monotone in T, so this is x of the kSatRank-th largest ENTRY of the row, which does not depend on the
+//            threshold: row_stat_kernel finds it once per batch behind the table build (off the step's critical path),
+//            and a table builder only scales eight numbers
+//   SAT_m  = SAT_BUDGET * stat_m / sum of the stats, no row above QT + 1 (an entry above QT rejects alone): what
+//            a capped row leaves is split again among the others, rows without a statistic share what is left evenly,
+//            and the units the integer divisions drop go one each to the first rows below the cap.
+// No scale (no threshold yet) or every statistic 0: the uniform split Cfg::SAT.  Integers throughout: the same
+// tables and threshold give the same eight values in whichever kernel computes them.
+// (Order statistic, not water-filling on tail counts: the CPU simulation has them within 0.5 % of each other,
+// scripts/sim_filter_saturation.py, and tail counts depend on the threshold: a histogram per row inside the bootstrap.)
+// ---------------------------------------------------------------------------
+constexpr int kSatRank = 32;
+
+// The kSatRank-th largest entry of every row of the batch's exact tables: grid = queries, block = M wavefronts,
+// wavefront m takes row m (four entries per lane) and searches the value bit by bit, counting with ballots.  Entries
+// are >= 0 or +inf (lut_build_kernel / tables_ingest_kernel), so their bit patterns order like the values.  (The sign bit
+// is masked off.  That entries are not negative is an assumption about the QUALITY of the split only: whatever this
+// kernel writes, both builders read the same numbers and any split of the budget is a valid lower bound.)
+template <int M>
+__global__ __launch_bounds__(64 * M) void row_stat_kernel(const float* __restrict__ lut32, float* __restrict__ lut_stat) {
+    const int q = blockIdx.x, m = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const float* row = lut32 + ((size_t)q * M + m) * 256;
+    uint32_t x[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) x[j] = __float_as_uint(row[lane + 64 * j]) & 0x7fffffffu;
+    uint32_t r = 0;  // the largest c with at least kSatRank entries >= c
+    for (int b = 30; b >= 0; --b) {
+        const uint32_t c = r | (1u << b);
+        int n = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) n += __popcll(__ballot(x[j] >= c));
+        if (n >= kSatRank) r = c;
+    }
+    if (lane == 0) lut_stat[(size_t)q * M + m] = __uint_as_float(r);
+}
+
+// stat_m from the row's kSatRank-th largest entry (sc != 0)
+template <int M>
+__device__ __forceinline__ uint32_t filter_row_stat(float entry, float sc, float of) {
+    return (uint32_t)fmaxf(fminf(__fmaf_rn(entry, sc, of), (float)Cfg<M>::SAT_CAP), 0.0f);
+}
+
+// The eight saturations of a slot by eight neighbouring lanes, lane m of the group = sub-space m with its statistic
+// (no scale: pass 0 everywhere).  Every lane of the wavefront must be here (shuffles, a ballot); returns the lane's
+// saturation.
+template <int M>
+__device__ __forceinline__ int filter_saturations(uint32_t stat_m, int lane) {
+    using C = Cfg<M>;
+    static_assert(M == 8, "groups of eight lanes");
+    constexpr int CAP = C::SAT_CAP;
+    auto sum8 = [](int v) {  // over the lane's group of eight, by DPP (no LDS round trips: the bootstrap's first wavefront waits on this)
+        v += __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xf, 0xf, true);   // quad_perm [1, 0, 3, 2]
+        v += __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xf, 0xf, true);   // quad_perm [2, 3, 0, 1]
+        v += __builtin_amdgcn_update_dpp(0, v, 0x141, 0xf, 0xf, true);  // row_half_mirror: the other quad's sum
+        return v;
+    };
+    const int stat = (int)stat_m;
+    const bool uniform = sum8(stat) == 0;  // every statistic 0
+    bool open = true;                      // rows whose saturation is not settled yet
+    int sat = 0, rem = C::SAT_BUDGET, num = 0, den = 1;
+    for (int it = 0; it < M && __ballot(open) != 0; ++it) {  // (every pass settles a row of every open group)
+        const int S = sum8(open ? stat : 0), n = sum8(open ? 1 : 0);
+        const bool capped = open && S > 0 && rem * stat >= CAP * S;  // its share reaches the cap
+        const int nc = sum8(capped ? 1 : 0);
+        if (open && S == 0) {  // (the whole group) rows with fewer than kSatRank entries above zero: what is left, evenly
+            num = rem, den = n, open = false;
+        } else if (open && nc == 0) {  // (the whole group) nobody reaches the cap: proportional shares
+            num = rem * stat, den = S, open = false;
+        } else if (capped) {
+            sat = CAP, open = false;
+        }
+        rem -= CAP * nc;  // >= 0: the capped rows' shares were each >= CAP
+    }
+    if (sat != CAP) sat = min(num / den, CAP);
+    const int left = C::SAT_BUDGET - sum8(sat);
+    const bool below = sat < CAP;
+    const uint32_t mine = (uint32_t)(__ballot(below) >> (lane & 56)) & ((1u << (lane & 7)) - 1u);  // rows below the cap in front
+    if (below && (int)__popc(mine) < left) ++sat;
+    return uniform ? C::SAT : sat;
+}
+
 // One slot's fields of its group's filter tables, written byte by byte (16 bytes apart):
-// T = the slot's exact tables (NULL: an unused slot, its entries reject).
+// T = the slot's exact tables (NULL: an unused slot, its entries reject).  clamp_m: saturation (+ bias at m = 0) per sub-space.
 template <int M>
 __device__ __forceinline__ void write_filter_fields(uint4* qtab, int slot, const float* T, float sc, const float* of_m,
-                                                    uint32_t bias, const uint8_t* __restrict__ relabel, int tid, int nthreads) {
+                                                    const uint32_t* clamp_m, const uint8_t* __restrict__ relabel, int tid,
+                                                    int nthreads) {
     using C = Cfg<M>;
     constexpr int F = C::F, AB = C::AB, R = C::R, QG = C::QG, NG = C::NG, J = C::J;
     const int group = slot / QG, ls = slot % QG;
@@ -355,10 +445,22 @@ __device__ __forceinline__ void write_filter_fields(uint4* qtab, int slot, const
     unsigned char* base = reinterpret_cast<unsigned char*>(qtab + ((size_t)group * NG + g) * M * 256) + c * 4 + tb;
     for (int e = tid; e < M * 256; e += nthreads) {
         const int m = e >> 8;
-        const uint32_t v = T ? filter_field<M>(T[e], sc, of_m[m], m == 0 ? bias : 0u) : C::reject_entry(m);
+        const uint32_t v = T ? filter_field<M>(T[e], sc, of_m[m], clamp_m[m]) : C::reject_entry(m);
         const int row = relabel ? (m << 8) + relabel[e] : e;  // the label this code value carries in the scratch
         base[(size_t)row * 16] = (unsigned char)v;
     }
+}
+
+// The threshold key a level's tables of `slot` are built from, and its query (-1: an unused slot).
+__device__ __forceinline__ int table_slot_query(const ScanArgs& a, int slot, uint64_t* key) {
+    int qq = a.slot_query ? a.slot_query[slot] : (slot < a.n_queries ? slot : -1);
+    *key = ~0ull;
+    if (qq >= 0 && a.debug_pass != 1) {
+        if (a.debug_pass != 2) *key = a.thr_key[slot];
+    } else {
+        qq = -1;
+    }
+    return qq;
 }
 
 template <int M>
@@ -369,31 +471,43 @@ __global__ __launch_bounds__(256) void quantise_kernel(const ScanArgs a) {
     constexpr int NS = 16;  // slots served by one 16-byte entry: byte tb of dword c
     __shared__ float s_scale[NS], s_off[NS];
     __shared__ int32_t s_row[NS];
-    __shared__ uint32_t s_bias[NS];
+    __shared__ uint32_t s_bias[NS];  // the clamp of the slot's entries of this sub-space: saturation (+ bias at m = 0)
     const int g = blockIdx.x / M, m = blockIdx.x % M, group = blockIdx.y, k = threadIdx.x;
     if (blockIdx.x == 0 && a.tight_hist)  // this level's tightening histograms of the group's slots (scan_kernel)
         for (int i = k; i < QG * kTightWords; i += 256) a.tight_hist[(size_t)group * QG * kTightWords + i] = 0;
     if (k < NS) {
         const int ls = C::slot_of_table(g, k >> 2, k & 3);
         const int slot = group * QG + ls;
-        int qq = a.slot_query ? a.slot_query[slot] : (slot < a.n_queries ? slot : -1);
+        uint64_t key;
+        const int qq = table_slot_query(a, slot, &key);
         FilterScale fs{0.0f, 0u, 0.0};
         float mn_m = 0.0f;
-        if (qq >= 0 && a.debug_pass != 1) {
-            uint64_t key = ~0ull;
-            if (a.debug_pass != 2) key = a.thr_key[slot];
+        if (qq >= 0) {
             fs = filter_scale<M>(key, a.lut_min, (size_t)qq);
             mn_m = lut_min_of(a.lut_min, (size_t)qq, M, m);
-        } else {
-            qq = -1;
         }
-        const float s32 = fs.s32;
-        const uint32_t bias = fs.bias;
-        const float of = filter_offset<M>(fs, mn_m, m);
-        s_scale[k] = s32;
-        s_off[k] = of;
-        s_bias[k] = m == 0 ? bias : 0u;
+        s_scale[k] = fs.s32;
+        s_off[k] = filter_offset<M>(fs, mn_m, m);
+        s_bias[k] = (uint32_t)C::SAT + (m == 0 ? fs.bias : 0u);  // (R = 1: the slot's own saturation, below)
         s_row[k] = qq >= 0 ? qq * TE + m * 256 : -1;
+    }
+    if constexpr (C::R == 1) {
+        // The saturations of the block's sixteen slots: eight lanes per slot, lane = sub-space, from the slot's scale
+        // above.  The lane of this block's sub-space sets the clamp.
+        __syncthreads();
+        if (k < NS * M) {
+            const int i = k / M, sub = k % M;
+            const int row = s_row[i];
+            const float sc = s_scale[i];
+            uint32_t st = 0;
+            if (row >= 0 && sc != 0.0f) {
+                const size_t qq = (size_t)(row / TE);
+                const FilterScale fs{sc, 0u, 0.0};
+                st = filter_row_stat<M>(a.lut_stat[qq * M + sub], sc, filter_offset<M>(fs, lut_min_of(a.lut_min, qq, M, sub), 1));
+            }
+            const uint32_t sat = (uint32_t)filter_saturations<M>(st, k & 63);
+            if (sub == m) s_bias[i] = sat + s_bias[i] - (uint32_t)C::SAT;
+        }
     }
     __syncthreads();
     uint32_t out[4] = {0, 0, 0, 0};
@@ -409,12 +523,32 @@ __global__ __launch_bounds__(256) void quantise_kernel(const ScanArgs a) {
             // v_cvt_pk_u8_f32: float -> u8 clamped to [0, 255], written into byte tb of the dword.  Half a
             // unit is taken off first, so whichever way the conversion rounds, the byte is <= floor(value):
             // the entry stays a lower bound (negative -> 0; inf/NaN of centroids beyond K -> SAT by the min).
-            const float fv = fminf(__fmaf_rn(tv, sc, of), (float)C::SAT + (float)bias);  // `of` holds the shift here
+            const float fv = fminf(__fmaf_rn(tv, sc, of), (float)bias);  // `of` holds the shift here, `bias` the clamp
             out[c] = row < 0 ? out[c] | (C::reject_entry(m) << (8 * tb))  // unused slot: rejects everything
                              : __builtin_amdgcn_cvt_pk_u8_f32(fv, (uint32_t)tb, out[c]);
         }
     }
     a.qtab[((size_t)group * NG * M + blockIdx.x) * 256 + k] = make_uint4(out[0], out[1], out[2], out[3]);
+}
+
+// Developer hook (dpq_debug_filter_tables; never launched by a query call): the saturations a table builder gives the
+// slots of `a` at the thresholds a.thr_key, with those keys: out[slot] = (8 saturation bytes, u64 key).
+// grid = slots / 8, block = one wavefront: eight lanes per slot.
+template <int M>
+__global__ __launch_bounds__(64) void saturation_debug_kernel(const ScanArgs a, unsigned char* __restrict__ out) {
+    const int lane = threadIdx.x, sub = lane % M, slot = blockIdx.x * (64 / M) + lane / M;
+    uint64_t key;
+    const int qq = table_slot_query(a, slot, &key);
+    uint32_t st = 0;
+    if (qq >= 0) {
+        const FilterScale fs = filter_scale<M>(key, a.lut_min, (size_t)qq);
+        if (fs.s32 != 0.0f)
+            st = filter_row_stat<M>(a.lut_stat[(size_t)qq * M + sub], fs.s32,
+                                    filter_offset<M>(fs, lut_min_of(a.lut_min, (size_t)qq, M, sub), 1));
+    }
+    const int sat = filter_saturations<M>(st, lane);
+    out[(size_t)slot * 16 + sub] = (unsigned char)sat;
+    if (sub == 0) *reinterpret_cast<uint64_t*>(out + (size_t)slot * 16 + 8) = key;
 }
 
 // Read window of the scan's ADC gathers at M = 8 (ds_read_b128 in flight before the first pair is summed; 0 = leave
@@ -2719,7 +2853,7 @@ __global__ __launch_bounds__(kBootThreads, (MF & ~kFiltered) <= 8 ? 8 : 6) void 
     const int slot = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int q = a.slot_query ? a.slot_query[slot] : (slot < a.n_queries ? slot : -1);
     if (q < 0) {  // padding slot of the last query group: its filter-table fields reject everything
-        if (a.qtab) write_filter_fields<M>(a.qtab, slot, nullptr, 0.0f, nullptr, 0u, nullptr, tid, kBootThreads);
+        if (a.qtab) write_filter_fields<M>(a.qtab, slot, nullptr, 0.0f, nullptr, nullptr, nullptr, tid, kBootThreads);
         return;
     }
     if (a.stamps && tid == 0) a.stamps[(size_t)slot * 8 + 6] = __builtin_amdgcn_s_memrealtime();  // 100 MHz, chip-wide
@@ -2995,17 +3129,28 @@ __global__ __launch_bounds__(kBootThreads, (MF & ~kFiltered) <= 8 ? 8 : 6) void 
         // quantise launch between bootstrap and scan: it sat on the critical path of a pipelined batch).
         __shared__ float s_of[M];
         __shared__ float s_scale;
-        __shared__ uint32_t s_bias;
-        if (tid < M) {
+        __shared__ uint32_t s_clamp[M];  // saturation (+ bias at m = 0) of the slot's sub-spaces
+        if (wave == 0) {  // lane & (M - 1) = sub-space (the wavefront's groups of M lanes all do the same)
+            const int m = lane & (M - 1);
             const FilterScale fs = filter_scale<M>(kth, a.lut_min, (size_t)q);
-            s_of[tid] = filter_offset<M>(fs, lut_min_of(a.lut_min, (size_t)q, M, tid), tid);
-            if (tid == 0) {
-                s_scale = fs.s32;
-                s_bias = fs.bias;
+            const float mn = lut_min_of(a.lut_min, (size_t)q, M, m);
+            uint32_t sat = (uint32_t)Cfg<M>::SAT;
+            if constexpr (Cfg<M>::R == 1) {
+                // the slot's saturations from the rows' kSatRank-th largest entries (row_stat_kernel)
+                uint32_t st = 0;
+                if (fs.s32 != 0.0f) st = filter_row_stat<M>(a.lut_stat[(size_t)q * M + m], fs.s32, filter_offset<M>(fs, mn, 1));
+                sat = (uint32_t)filter_saturations<M>(st, lane);
+            }
+            if (lane < M) {
+                s_of[lane] = filter_offset<M>(fs, mn, lane);
+                s_clamp[lane] = sat + (lane == 0 ? fs.bias : 0u);
+                if (lane == 0) s_scale = fs.s32;
             }
         }
         __syncthreads();
-        write_filter_fields<M>(a.qtab, slot, T, s_scale, s_of, s_bias, a.relabel, tid, kBootThreads);
+        // (no record of the saturations and the key here, as quantise_kernel leaves one for dpq_debug_filter_tables: a
+        // 16-byte store in this epilogue made the compiler serialise the evaluation loop's table gathers, + 2.5 us a block)
+        write_filter_fields<M>(a.qtab, slot, T, s_scale, s_of, s_clamp, a.relabel, tid, kBootThreads);
     }
     if (a.stamps && tid == 0) a.stamps[(size_t)slot * 8 + 7] = __builtin_amdgcn_s_memrealtime();
 }
@@ -3530,9 +3675,11 @@ hipError_t launch_strand(const ScanArgs& a, int n_slots, hipStream_t stream) {
 hipError_t launch_quantise(const ScanArgs& a, int n_slot_groups, hipStream_t stream) {
     if (n_slot_groups <= 0) return hipSuccess;
     if (!a.qtab) return hipErrorInvalidValue;
-    if (a.img.M == 8)
+    if (a.img.M == 8) {
+        if (!a.lut_stat) return hipErrorInvalidValue;
         hipLaunchKernelGGL(quantise_kernel<8>, dim3((unsigned)(Cfg<8>::NG * 8), (unsigned)n_slot_groups), dim3(256), 0,
                            stream, a);
+    }
     else if (a.img.M == 16)
         hipLaunchKernelGGL(quantise_kernel<16>, dim3((unsigned)(Cfg<16>::NG * 16), (unsigned)n_slot_groups), dim3(256),
                            0, stream, a);
@@ -3570,7 +3717,19 @@ hipError_t launch_scan(const ScanArgs& a, int n_slot_groups, int splits, hipStre
     return hipErrorInvalidValue;
 }
 
+hipError_t launch_row_stats(const float* d_lut32, int nq, int M, float* d_lut_stat, hipStream_t stream) {
+    if (nq <= 0 || M != 8) return hipSuccess;  // (M = 16 keeps one saturation for every entry)
+    if (!d_lut32 || !d_lut_stat) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(row_stat_kernel<8>, dim3((unsigned)nq), dim3(64 * 8), 0, stream, d_lut32, d_lut_stat);
+    return hipGetLastError();
+}
+
 size_t qtab_bytes_per_group(int M) { return M <= 8 ? ScanLds<8>::kTables : ScanLds<16>::kTables; }
+hipError_t launch_saturation_debug(const ScanArgs& a, int n_slots, unsigned char* d_out, hipStream_t stream) {
+    if (a.img.M != 8 || n_slots <= 0 || n_slots % 8 || !a.lut_stat || !d_out) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(saturation_debug_kernel<8>, dim3((unsigned)(n_slots / 8)), dim3(64), 0, stream, a, d_out);
+    return hipGetLastError();
+}
 int scan_stamp_count() { return kStCount; }
 
 template <int M, int THREADS>

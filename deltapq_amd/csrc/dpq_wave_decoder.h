@@ -63,12 +63,24 @@ struct Cfg {
     // than a longer range reaches, as at M = 16) free a unit of saturation: 64/23 with XU 1 against 64/22 with XU 2 on the
     // GPU (scripts/gpu_xu8.sh): exact checks per query 1676 against 1810 at top-100 (candidates 400 / 401), 12 514 against
     // 13 344 at top-1000; scan launch 0.1148 / 0.1178 ms and 0.284 / 0.298 ms.
+    // Saturation per (slot, sub-space) (filter_saturations, dpq_kernels.hip): the saturations of a slot
+    // share SAT_BUDGET = 122 + QT - XMAX XU + 1 units (210 at QT 88), split by the spread of the query's eight table
+    // rows; the uniform split SAT_BUDGET / M (26 at QT 88; the sweeps above ran with one SAT for all, 23 at QT 64) is
+    // the fallback of a slot without a scale.  With saturation no longer what a finer resolution costs, QT re-swept on
+    // the GPU (profiles/filter_sat_sweep.txt; exact checks / candidates per query, scan ms per step, at top-100 and
+    // top-1000; uniform 64/23: 1707 / 408, 0.1212 and 12 667 / 3779, 0.3060):
+    // 64: 1514 / 410, 0.1196 and 11 909 / 3788, 0.2930;  72: 1416 / 422, 0.1181 and 11 099 / 3938, 0.2778;
+    // 80: 1366 / 435, 0.1181 and 10 664 / 4107, 0.2701;  88: 1358 / 450, 0.1177 and 10 468 / 4280, 0.2655.
+    // That sweep ran on an intermediate build whose bootstrap epilogue was 3 us longer than the one kept; checks,
+    // candidates and scan times do not depend on the epilogue, step times do.  The headline (top-100) steps do not
+    // tell the four values apart on either build, so the choice of 88 rests on top-1000 alone: fewest checks and
+    // shortest step there (this build against the parent: 0.344 against 0.375 ms, profiles/filter_sat_ab.txt).
+    // Candidates rise because seven tightening steps of one unit reach 8 % of the span at QT 88 where they reached
+    // 11 % at QT 64.
 #ifndef DPQ_QT8
-#define DPQ_QT8 64
-#define DPQ_SAT8 23
+#define DPQ_QT8 88
 #endif
     static constexpr int QT = M <= 8 ? DPQ_QT8 : DPQ_QT16;   // filter units that span (tau - sum of minima)
-    static constexpr int SAT = M <= 8 ? DPQ_SAT8 : DPQ_SAT16; // entry saturation
     // In-scan tightening: a slot's cut can be lowered by e * XU filter units, e = 1 .. XMAX, while a scan launch runs
     // (the additive term of its accumulator field grows by as much): the field sums need that much headroom.
     static constexpr int XMAX = kTightBuckets - 1;
@@ -84,7 +96,13 @@ struct Cfg {
     // R = 2: the accumulator fields start from it.
     static constexpr int BIAS = (1 << (AB - 1)) - 1 - (QT + 1);
     static constexpr int FIELD_MAX = (1 << EB) - 1;
-    static_assert(BIAS >= 0 && M * SAT + BIAS + XMAX * XU < (1 << AB), "a field sum must not carry into its neighbour");
+    // R = 1: what the M saturations of a slot may sum to (a byte field holds sum of SAT_m + BIAS + XMAX XU <= 255);
+    // SAT: the uniform split, used where a slot has no scale.  R = 2: every entry saturates at DPQ_SAT16.
+    static constexpr int SAT_BUDGET = R == 1 ? FIELD_MAX - BIAS - XMAX * XU : M * DPQ_SAT16;
+    static constexpr int SAT = SAT_BUDGET / M;
+    static constexpr int SAT_CAP = QT + 1;  // an entry above QT rejects alone: a larger saturation is wasted
+    static_assert(BIAS >= 0 && SAT_BUDGET + BIAS + XMAX * XU < (1 << AB), "a field sum must not carry into its neighbour");
+    static_assert(R != 1 || (SAT_BUDGET >= M && SAT_CAP <= 127 && M * SAT <= SAT_BUDGET), "saturations are 7-bit, one unit each at least");
     static_assert(XMAX * XU < QT, "cuts stay above zero");
     static constexpr int PRE = R == 1 ? M : DPQ_PRE16;  // entries summed as bytes before they are widened
     static_assert(R == 1 || (PRE * SAT <= FIELD_MAX && M * SAT > QT + 1 && M % PRE == 0), "byte sums of PRE entries; all-SAT rejects");

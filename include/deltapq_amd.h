@@ -1031,6 +1031,14 @@ int dpq_debug_select_time(dpq_index* idx, int nq, int top_k, int flags, int reps
 int dpq_debug_range_keys(dpq_index* idx, int64_t* max_keys);
 /* Per-wavefront marks of strand1_kernel on the 100 MHz clock, [256][16][16] words (first call arms them). */
 int dpq_debug_strand1_stamps(dpq_index* idx, unsigned long long* out, int n_words);
+/* The first filter level's tables of the last batch answered on `lane` (0 or 1), in the scan's LDS layout
+ * ([query group][g][m][code] x 16 bytes), followed at M = 8 by one 16-byte record per slot: the eight saturation bytes a
+ * table builder gives the slot and the u64 threshold key its fields were built from (recomputed by the hook; the batch
+ * itself must have run with DPQ_DEV=1).  DPQ_ERR_STATE unless that batch ran exactly one filter level. */
+int dpq_debug_filter_tables(dpq_index* idx, int lane, void* out, int64_t bytes);
+/* The code value -> label map [M][256] of the plain-code scratch, in whose label order the rows of a scratch batch's
+ * filter tables stand.  DPQ_ERR_STATE: the handle has none (labels are code values). */
+int dpq_debug_relabel(dpq_index* idx, unsigned char* out, int bytes);
 
 #ifdef __cplusplus
 }
