@@ -1168,7 +1168,8 @@ def _flat_range_search(index, fn, name, queries, radius, id_filter):
 
 class FlatIndex:
     """Raw fp32 vectors [n][D] on one GPU (dpq_flat): exact squared L2 distances with the reference's brute-force
-    arithmetic -- ground truth over all of them (search), or over a candidate list per query (rerank)."""
+    arithmetic -- ground truth over all of them (search), or over a candidate list per query (rerank).  The *_ip methods
+    are the same searches by exact inner product: scores instead of distances, best (largest) first."""
 
     def __init__(self, vectors, device=0, id_offset=0):
         self._lib = _lib.load()
@@ -1187,14 +1188,33 @@ class FlatIndex:
             raise ValueError("queries must be [nq][%d]" % self.D)
         return q
 
-    def search(self, queries, top_k):
-        """Exact top_k over all vectors -> ids int32 [nq][top_k], dists float32 [nq][top_k] by (distance, id)."""
+    def _search(self, name, queries, top_k):
         q = self._queries(queries)
         ids = np.empty((q.shape[0], top_k), dtype=np.int32)
         dists = np.empty((q.shape[0], top_k), dtype=np.float32)
-        check(self._lib.dpq_flat_search(self._h, _np_ptr(q), q.shape[0], top_k, _np_ptr(ids), _np_ptr(dists)),
-              "dpq_flat_search")
+        check(getattr(self._lib, name)(self._h, _np_ptr(q), q.shape[0], top_k, _np_ptr(ids), _np_ptr(dists)), name)
         return ids, dists
+
+    def search(self, queries, top_k):
+        """Exact top_k over all vectors -> ids int32 [nq][top_k], dists float32 [nq][top_k] by (distance, id)."""
+        return self._search("dpq_flat_search", queries, top_k)
+
+    def search_ip(self, queries, top_k):
+        """Exact top_k by inner product -> ids int32 [nq][top_k], scores float32 [nq][top_k] by (score descending, id)
+        (dpq_flat_search_ip)."""
+        return self._search("dpq_flat_search_ip", queries, top_k)
+
+    def search_filtered_ip(self, queries, top_k, id_filter):
+        """search_ip over the rows `id_filter` allows; rows are padded with -1 / -inf (dpq_flat_search_filtered_ip)."""
+        return _flat_search_filtered(self, self._lib.dpq_flat_search_filtered_ip, "dpq_flat_search_filtered_ip", queries,
+                                     top_k, id_filter)
+
+    def range_search_ip(self, queries, threshold, id_filter=None):
+        """Every (allowed) row with exact score s > threshold, strictly (dpq_flat_range_search_ip).  `threshold` is a
+        scalar or one value per query.  Returns (lims int64 [nq + 1], ids int32, scores float32); query i owns entries
+        lims[i]:lims[i + 1], by (score descending, id)."""
+        return _flat_range_search(self, self._lib.dpq_flat_range_search_ip, "dpq_flat_range_search_ip", queries,
+                                  threshold, id_filter)
 
     def search_filtered(self, queries, top_k, id_filter):
         """Exact top_k over the rows `id_filter` (a FlatIdFilter made on this index) allows; rows are padded with -1 / +inf
@@ -1214,20 +1234,35 @@ class FlatIndex:
         m = np.ascontiguousarray(vec_id, dtype=np.uint32)
         check(self._lib.dpq_flat_set_id_map(self._h, _np_ptr(m), m.size), "dpq_flat_set_id_map")
 
-    def rerank(self, queries, cand_ids, top_k):
-        """Exact distances of cand_ids[nq][n_cand] only (negative = padding), the best top_k of them."""
+    def _rerank(self, name, queries, cand_ids, top_k):
         q = self._queries(queries)
         c = np.ascontiguousarray(cand_ids, dtype=np.int32)
         if c.ndim != 2 or c.shape[0] != q.shape[0]:
             raise ValueError("cand_ids must be [nq][n_cand]")
         ids = np.empty((q.shape[0], top_k), dtype=np.int32)
         dists = np.empty((q.shape[0], top_k), dtype=np.float32)
-        check(self._lib.dpq_flat_rerank(self._h, _np_ptr(q), q.shape[0], _np_ptr(c), c.shape[1], top_k, _np_ptr(ids),
-                                        _np_ptr(dists)), "dpq_flat_rerank")
+        check(getattr(self._lib, name)(self._h, _np_ptr(q), q.shape[0], _np_ptr(c), c.shape[1], top_k, _np_ptr(ids),
+                                       _np_ptr(dists)), name)
         return ids, dists
+
+    def rerank(self, queries, cand_ids, top_k):
+        """Exact distances of cand_ids[nq][n_cand] only (negative = padding), the best top_k of them."""
+        return self._rerank("dpq_flat_rerank", queries, cand_ids, top_k)
+
+    def rerank_ip(self, queries, cand_ids, top_k):
+        """Exact inner-product scores of cand_ids[nq][n_cand] only (negative = padding), the best top_k of them by (score
+        descending, id); rows are padded with -1 / -inf (dpq_flat_rerank_ip)."""
+        return self._rerank("dpq_flat_rerank_ip", queries, cand_ids, top_k)
 
     def rerank_torch(self, queries, cand_ids, top_k, out_ids=None, out_dists=None):
         """rerank on device tensors, on torch's current stream (dpq_flat_rerank_device); the results are complete on return."""
+        return self._rerank_torch("dpq_flat_rerank_device", queries, cand_ids, top_k, out_ids, out_dists)
+
+    def rerank_ip_torch(self, queries, cand_ids, top_k, out_ids=None, out_scores=None):
+        """rerank_ip on device tensors, on torch's current stream (dpq_flat_rerank_ip_device); complete on return."""
+        return self._rerank_torch("dpq_flat_rerank_ip_device", queries, cand_ids, top_k, out_ids, out_scores)
+
+    def _rerank_torch(self, name, queries, cand_ids, top_k, out_ids, out_dists):
         import torch
         assert queries.is_cuda and queries.dtype == torch.float32 and queries.is_contiguous() and queries.shape[1] == self.D
         assert cand_ids.is_cuda and cand_ids.dtype == torch.int32 and cand_ids.is_contiguous()
@@ -1238,10 +1273,10 @@ class FlatIndex:
         if out_dists is None:
             out_dists = torch.empty((nq, top_k), dtype=torch.float32, device=queries.device)
         stream = torch.cuda.current_stream(queries.device).cuda_stream
-        check(self._lib.dpq_flat_rerank_device(self._h, ctypes.c_void_p(queries.data_ptr()), nq,
-                                               ctypes.c_void_p(cand_ids.data_ptr()), cand_ids.shape[1], top_k,
-                                               ctypes.c_void_p(out_ids.data_ptr()), ctypes.c_void_p(out_dists.data_ptr()),
-                                               ctypes.c_void_p(stream)), "dpq_flat_rerank_device")
+        check(getattr(self._lib, name)(self._h, ctypes.c_void_p(queries.data_ptr()), nq,
+                                       ctypes.c_void_p(cand_ids.data_ptr()), cand_ids.shape[1], top_k,
+                                       ctypes.c_void_p(out_ids.data_ptr()), ctypes.c_void_p(out_dists.data_ptr()),
+                                       ctypes.c_void_p(stream)), name)
         return out_ids, out_dists
 
     def close(self):
@@ -1631,6 +1666,20 @@ def merge_topk_host(ids, dists):
     od = np.empty((nq, k), dtype=np.float32)
     check(lib.dpq_merge_topk_host(_np_ptr(ids), _np_ptr(dists), n_lists, nq, k, _np_ptr(oi), _np_ptr(od)),
           "dpq_merge_topk_host")
+    return oi, od
+
+
+def merge_topk_ip_host(ids, scores):
+    """ids/scores [n_lists][nq][k] -> merged [nq][k] by (score descending, id); padding is -1 / -inf
+    (dpq_merge_topk_ip_host; host only, no device)."""
+    lib = _lib.load()
+    ids = np.ascontiguousarray(ids, dtype=np.int32)
+    scores = np.ascontiguousarray(scores, dtype=np.float32)
+    n_lists, nq, k = ids.shape
+    oi = np.empty((nq, k), dtype=np.int32)
+    od = np.empty((nq, k), dtype=np.float32)
+    check(lib.dpq_merge_topk_ip_host(_np_ptr(ids), _np_ptr(scores), n_lists, nq, k, _np_ptr(oi), _np_ptr(od)),
+          "dpq_merge_topk_ip_host")
     return oi, od
 
 

@@ -7,8 +7,8 @@ namespace {
 
 // Candidates of dpq_flat_rerank*, all device pointers; ends with one flag word read back.
 template <class Q>
-int flat_rerank_on_device(const char* fn, dpq_flat* f, const Q* d_queries, int nq, const int32_t* d_cand, int n_cand,
-                          int top_k, int32_t* d_ids, float* d_dists, hipStream_t stream) {
+int flat_rerank_on_device(const char* fn, int metric, dpq_flat* f, const Q* d_queries, int nq, const int32_t* d_cand,
+                          int n_cand, int top_k, int32_t* d_ids, float* d_dists, hipStream_t stream) {
     const size_t n_pad = dpq::flat_rerank_keys(n_cand);
     const int per = (int)std::max<size_t>(1, std::min<size_t>((size_t)nq, ((size_t)64 << 20) / (n_pad * sizeof(uint64_t))));
     int rc = grow(f->keys, &f->keys_n, (size_t)per * n_pad);
@@ -24,7 +24,7 @@ int flat_rerank_on_device(const char* fn, dpq_flat* f, const Q* d_queries, int n
                                                (int64_t)f->h_map.size(), f->keys, f->flag, d_ids + (size_t)q0 * top_k,
                                                d_dists + (size_t)q0 * top_k, stream));
         else
-            DPQ_HIP(dpq::launch_flat_rerank(f->base, f->n, f->D, f->Dp, d_queries + (size_t)q0 * f->D, m,
+            DPQ_HIP(dpq::launch_flat_rerank(metric, f->base, f->n, f->D, f->Dp, d_queries + (size_t)q0 * f->D, m,
                                             d_cand + (size_t)q0 * n_cand, n_cand, top_k, f->id_offset, map,
                                             (int64_t)f->h_map.size(), f->keys, f->flag, d_ids + (size_t)q0 * top_k,
                                             d_dists + (size_t)q0 * top_k, stream));
@@ -37,8 +37,12 @@ int flat_rerank_on_device(const char* fn, dpq_flat* f, const Q* d_queries, int n
 }
 
 // A handle takes the calls of its own kind only: the fp32 functions an fp32 handle, the _u8 functions a byte handle.
+// The _ip functions (other == NULL) have no byte counterpart.
 int flat_kind(const dpq_flat* f, bool u8, const char* fn, const char* other) {
     if (f->u8 == u8) return DPQ_OK;
+    if (!other)
+        return fail(DPQ_ERR_ARG, std::string(fn) + ": the handle holds byte vectors (dpq_flat_open_u8), which have no "
+                                                   "inner-product search; open the vectors as fp32 with dpq_flat_open");
     return fail(DPQ_ERR_ARG, std::string(fn) + (u8 ? ": the handle holds fp32 vectors (dpq_flat_open); call "
                                                    : ": the handle holds byte vectors (dpq_flat_open_u8); call ") + other);
 }
@@ -110,9 +114,9 @@ int flat_grow_queries(dpq_flat* f, size_t qb) {
 
 // The handle's rows, all of them or those a filter lists, and queries [a, a + m) of the staged batch, as the launchers
 // of dpq_flat.h take them.
-dpq::FlatBase flat_base(const dpq_flat* f, const dpq_flat_filter* ff) {
+dpq::FlatBase flat_base(const dpq_flat* f, const dpq_flat_filter* ff, int metric) {
     return {f->base, f->base8, f->norm8, f->Dp, f->id_offset, ff != nullptr, ff ? ff->list.get() : nullptr,
-            ff ? ff->n_allowed : f->n};
+            ff ? ff->n_allowed : f->n, metric};
 }
 
 dpq::FlatQueries flat_queries(const dpq_flat* f, int a, int m) {
@@ -122,9 +126,10 @@ dpq::FlatQueries flat_queries(const dpq_flat* f, int a, int m) {
 
 // What dpq_flat_search[_u8] and dpq_flat_search_filtered[_u8] share once their arguments are checked: the buffers, the
 // batches of staged queries, the copies down and the check of every query's state.  ff NULL: all rows, top_k <= n.
+// metric: dpq::kFlatL2, or dpq::kFlatIP (fp32 handles; dists then holds scores).
 template <class Q>
-int flat_search_run(const std::string& who, dpq_flat* f, const dpq_flat_filter* ff, const Q* queries, int nq, int top_k,
-                    int32_t* ids, float* dists) {
+int flat_search_run(const std::string& who, int metric, dpq_flat* f, const dpq_flat_filter* ff, const Q* queries, int nq,
+                    int top_k, int32_t* ids, float* dists) {
     if (nq == 0) return DPQ_OK;
     DPQ_HIP(hipSetDevice(f->device));
     const int qb = std::min(nq, dpq::flat_query_batch(top_k));
@@ -133,7 +138,7 @@ int flat_search_run(const std::string& who, dpq_flat* f, const dpq_flat_filter* 
     if (!rc) rc = flat_grow_queries<Q>(f, (size_t)qb);
     if (!rc) rc = grow_outputs(f, (size_t)qb * top_k);
     if (rc) return rc;
-    const dpq::FlatBase base = flat_base(f, ff);
+    const dpq::FlatBase base = flat_base(f, ff, metric);
     const uint32_t expect = (uint32_t)std::min<int64_t>(top_k, base.n_entries);
     std::vector<float> padded;
     std::vector<dpq::FlatQueryState> st((size_t)qb);
@@ -229,7 +234,18 @@ int dpq_flat_search(dpq_flat* f, const float* queries, int nq, int top_k, int32_
     if (top_k < 1 || top_k > DPQ_FLAT_MAX_TOPK) return fail(DPQ_ERR_ARG, "dpq_flat_search: top_k outside 1..DPQ_FLAT_MAX_TOPK");
     if (int rc = flat_kind(f, false, "dpq_flat_search", "dpq_flat_search_u8")) return rc;
     if (top_k > f->n) return fail(DPQ_ERR_TOPK, "dpq_flat_search: top_k exceeds the number of vectors");
-    return flat_search_run("dpq_flat_search", f, nullptr, queries, nq, top_k, ids, dists);
+    return flat_search_run("dpq_flat_search", dpq::kFlatL2, f, nullptr, queries, nq, top_k, ids, dists);
+    });
+}
+
+int dpq_flat_search_ip(dpq_flat* f, const float* queries, int nq, int top_k, int32_t* ids, float* scores) {
+    return guarded([&]() -> int {
+    if (!f || !queries || !ids || !scores || nq < 0) return fail(DPQ_ERR_ARG, "dpq_flat_search_ip: NULL argument or nq < 0");
+    if (top_k < 1 || top_k > DPQ_FLAT_MAX_TOPK)
+        return fail(DPQ_ERR_ARG, "dpq_flat_search_ip: top_k outside 1..DPQ_FLAT_MAX_TOPK");
+    if (int rc = flat_kind(f, false, "dpq_flat_search_ip", nullptr)) return rc;
+    if (top_k > f->n) return fail(DPQ_ERR_TOPK, "dpq_flat_search_ip: top_k exceeds the number of vectors");
+    return flat_search_run("dpq_flat_search_ip", dpq::kFlatIP, f, nullptr, queries, nq, top_k, ids, scores);
     });
 }
 
@@ -240,7 +256,7 @@ int dpq_flat_search_u8(dpq_flat* f, const uint8_t* queries, int nq, int top_k, i
         return fail(DPQ_ERR_ARG, "dpq_flat_search_u8: top_k outside 1..DPQ_FLAT_MAX_TOPK");
     if (int rc = flat_kind(f, true, "dpq_flat_search_u8", "dpq_flat_search")) return rc;
     if (top_k > f->n) return fail(DPQ_ERR_TOPK, "dpq_flat_search_u8: top_k exceeds the number of vectors");
-    return flat_search_run("dpq_flat_search_u8", f, nullptr, queries, nq, top_k, ids, dists);
+    return flat_search_run("dpq_flat_search_u8", dpq::kFlatL2, f, nullptr, queries, nq, top_k, ids, dists);
     });
 }
 
@@ -297,9 +313,9 @@ int flat_filter_owner(const dpq_flat* f, const dpq_flat_filter* ff, const std::s
     return fail(DPQ_ERR_ARG, who + ": the filter was made for another handle");
 }
 
-// dpq_flat_search_filtered / _u8: Q is float or uint8_t, the handle of the same kind.
+// dpq_flat_search_filtered / _u8 / _ip: Q is float or uint8_t, the handle of the same kind.
 template <class Q>
-int flat_search_filtered_call(const char* fn, const char* other, dpq_flat* f, const dpq_flat_filter* ff, const Q* queries,
+int flat_search_filtered_call(const char* fn, const char* other, int metric, dpq_flat* f, const dpq_flat_filter* ff, const Q* queries,
                               int nq, int top_k, int32_t* ids, float* dists) {
     constexpr bool u8 = std::is_same<Q, uint8_t>::value;
     const std::string who(fn);
@@ -309,22 +325,22 @@ int flat_search_filtered_call(const char* fn, const char* other, dpq_flat* f, co
     if (int rc = flat_device_present(who)) return rc;
     if (int rc = flat_kind(f, u8, fn, other)) return rc;
     if (int rc = flat_filter_owner(f, ff, who)) return rc;
-    return flat_search_run(who, f, ff, queries, nq, top_k, ids, dists);
+    return flat_search_run(who, metric, f, ff, queries, nq, top_k, ids, dists);
 }
 
 // One distance pass of a range search over queries [a, a + m) of the staged batch: counting (pool NULL) or emitting.
-int flat_range_pass(dpq_flat* f, const dpq_flat_filter* ff, int a, int m, uint64_t* pool) {
+int flat_range_pass(dpq_flat* f, const dpq_flat_filter* ff, int metric, int a, int m, uint64_t* pool) {
     dpq::FlatQueryState* state = f->state.get() + a;
     DPQ_HIP(dpq::launch_flat_range_state(state, f->r_thr.get() + a, m, nullptr));
-    DPQ_HIP(dpq::launch_flat_range_pass(flat_base(f, ff), flat_queries(f, a, m), pool, f->r_offs, state, nullptr));
+    DPQ_HIP(dpq::launch_flat_range_pass(flat_base(f, ff, metric), flat_queries(f, a, m), pool, f->r_offs, state, nullptr));
     return DPQ_OK;
 }
 
-// dpq_flat_range_search / _u8.  Count, then emit: a pass over a batch of queries counts every list, the host lays the
+// dpq_flat_range_search / _u8 / _ip (radii are then score thresholds: a row is kept when its score is above).  Count, then emit: a pass over a batch of queries counts every list, the host lays the
 // lists out, and sub-batches of at most kFlatRangePoolKeys keys (or one longer list) are formed again into the pool,
 // sorted there and brought down.
 template <class Q>
-int flat_range_call(const char* fn, const char* other, dpq_flat* f, const dpq_flat_filter* ff, const Q* queries, int nq,
+int flat_range_call(const char* fn, const char* other, int metric, dpq_flat* f, const dpq_flat_filter* ff, const Q* queries, int nq,
                     const float* radii, dpq_range_result** out) {
     constexpr bool u8 = std::is_same<Q, uint8_t>::value;
     const std::string who(fn);
@@ -332,7 +348,9 @@ int flat_range_call(const char* fn, const char* other, dpq_flat* f, const dpq_fl
     *out = nullptr;
     if (!f || nq < 0 || (nq > 0 && (!queries || !radii))) return fail(DPQ_ERR_ARG, who + ": NULL argument or nq < 0");
     for (int q = 0; q < nq; ++q)
-        if (std::isnan(radii[q])) return fail(DPQ_ERR_ARG, who + ": radius of query " + std::to_string(q) + " is NaN");
+        if (std::isnan(radii[q]))
+            return fail(DPQ_ERR_ARG, who + (metric == dpq::kFlatIP ? ": threshold of query " : ": radius of query ") +
+                                         std::to_string(q) + " is NaN");
     if (int rc = flat_device_present(who)) return rc;
     if (int rc = flat_kind(f, u8, fn, other)) return rc;
     if (ff)
@@ -361,11 +379,16 @@ int flat_range_call(const char* fn, const char* other, dpq_flat* f, const dpq_fl
         for (int q = 0; q < m; ++q) {  // d < r on non-negative floats is bits(d) < bits(r); key 0 lets nothing pass
             const float r = radii[q0 + q];
             uint32_t bits = 0;
-            if (r > 0.0f) memcpy(&bits, &r, sizeof bits);
+            if (metric == dpq::kFlatIP) {  // s > r is word(s) < word(r): the map descends, and -0.0 is read as +0.0
+                memcpy(&bits, &r, sizeof bits);
+                bits = dpq::flat_ip_word(bits);
+            } else if (r > 0.0f) {
+                memcpy(&bits, &r, sizeof bits);
+            }
             thr[(size_t)q] = (uint64_t)bits << 32;
         }
         DPQ_HIP(hipMemcpy(f->r_thr, thr.data(), (size_t)m * sizeof(uint64_t), hipMemcpyHostToDevice));
-        if ((rc = flat_range_pass(f, ff, 0, m, nullptr))) break;
+        if ((rc = flat_range_pass(f, ff, metric, 0, m, nullptr))) break;
         DPQ_HIP(hipMemcpy(st.data(), f->state, (size_t)m * sizeof(dpq::FlatQueryState), hipMemcpyDeviceToHost));
         for (int q = 0; q < m; ++q) res->lims[(size_t)q0 + q + 1] = res->lims[(size_t)q0 + q] + st[(size_t)q].count;
         res->ids.resize((size_t)res->lims[(size_t)q0 + m]);
@@ -380,7 +403,7 @@ int flat_range_call(const char* fn, const char* other, dpq_flat* f, const dpq_fl
                 if ((rc = grow(f->r_pool, &f->r_pool_n, (size_t)std::max(sum, kFlatRangePoolKeys)))) break;
                 if ((rc = grow(f->r_sorted, &f->r_sorted_n, f->r_pool_n))) break;
                 DPQ_HIP(hipMemcpy(f->r_offs, offs.data(), offs.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-                if ((rc = flat_range_pass(f, ff, a, b - a, f->r_pool))) break;
+                if ((rc = flat_range_pass(f, ff, metric, a, b - a, f->r_pool))) break;
                 size_t tb = 0;
                 DPQ_HIP(dpq::flat_range_sort(nullptr, &tb, f->r_pool, f->r_sorted, sum, b - a, f->r_offs, nullptr));
                 DevBuf<uint8_t> temp;  // the segmented sort's workspace
@@ -396,7 +419,8 @@ int flat_range_call(const char* fn, const char* other, dpq_flat* f, const dpq_fl
                 if (rc) break;
                 const size_t at = (size_t)res->lims[(size_t)q0 + a];
                 for (size_t i = 0; i < (size_t)sum; ++i) {
-                    const uint32_t bits = (uint32_t)(sorted[i] >> 32);
+                    uint32_t bits = (uint32_t)(sorted[i] >> 32);
+                    if (metric == dpq::kFlatIP) bits = dpq::flat_ip_word(bits);
                     res->ids[at + i] = (int32_t)(uint32_t)sorted[i];
                     memcpy(&res->dists[at + i], &bits, sizeof bits);
                 }
@@ -472,7 +496,7 @@ int dpq_flat_filter_count(const dpq_flat_filter* ff, int64_t* n_allowed) {
 int dpq_flat_search_filtered(dpq_flat* f, const dpq_flat_filter* ff, const float* queries, int nq, int top_k, int32_t* ids,
                              float* dists) {
     return guarded([&]() -> int {
-    return flat_search_filtered_call("dpq_flat_search_filtered", "dpq_flat_search_filtered_u8", f, ff, queries, nq, top_k, ids,
+    return flat_search_filtered_call("dpq_flat_search_filtered", "dpq_flat_search_filtered_u8", dpq::kFlatL2, f, ff, queries, nq, top_k, ids,
                                      dists);
     });
 }
@@ -480,7 +504,7 @@ int dpq_flat_search_filtered(dpq_flat* f, const dpq_flat_filter* ff, const float
 int dpq_flat_search_filtered_u8(dpq_flat* f, const dpq_flat_filter* ff, const uint8_t* queries, int nq, int top_k,
                                 int32_t* ids, float* dists) {
     return guarded([&]() -> int {
-    return flat_search_filtered_call("dpq_flat_search_filtered_u8", "dpq_flat_search_filtered", f, ff, queries, nq, top_k, ids,
+    return flat_search_filtered_call("dpq_flat_search_filtered_u8", "dpq_flat_search_filtered", dpq::kFlatL2, f, ff, queries, nq, top_k, ids,
                                      dists);
     });
 }
@@ -488,14 +512,29 @@ int dpq_flat_search_filtered_u8(dpq_flat* f, const dpq_flat_filter* ff, const ui
 int dpq_flat_range_search(dpq_flat* f, const dpq_flat_filter* ff, const float* queries, int nq, const float* radii,
                           dpq_range_result** out) {
     return guarded([&]() -> int {
-    return flat_range_call("dpq_flat_range_search", "dpq_flat_range_search_u8", f, ff, queries, nq, radii, out);
+    return flat_range_call("dpq_flat_range_search", "dpq_flat_range_search_u8", dpq::kFlatL2, f, ff, queries, nq, radii, out);
     });
 }
 
 int dpq_flat_range_search_u8(dpq_flat* f, const dpq_flat_filter* ff, const uint8_t* queries, int nq, const float* radii,
                              dpq_range_result** out) {
     return guarded([&]() -> int {
-    return flat_range_call("dpq_flat_range_search_u8", "dpq_flat_range_search", f, ff, queries, nq, radii, out);
+    return flat_range_call("dpq_flat_range_search_u8", "dpq_flat_range_search", dpq::kFlatL2, f, ff, queries, nq, radii, out);
+    });
+}
+
+int dpq_flat_search_filtered_ip(dpq_flat* f, const dpq_flat_filter* ff, const float* queries, int nq, int top_k, int32_t* ids,
+                                float* scores) {
+    return guarded([&]() -> int {
+    return flat_search_filtered_call("dpq_flat_search_filtered_ip", nullptr, dpq::kFlatIP, f, ff, queries, nq, top_k, ids,
+                                     scores);
+    });
+}
+
+int dpq_flat_range_search_ip(dpq_flat* f, const dpq_flat_filter* ff, const float* queries, int nq, const float* thresholds,
+                             dpq_range_result** out) {
+    return guarded([&]() -> int {
+    return flat_range_call("dpq_flat_range_search_ip", nullptr, dpq::kFlatIP, f, ff, queries, nq, thresholds, out);
     });
 }
 
@@ -503,21 +542,21 @@ int dpq_flat_range_search_u8(dpq_flat* f, const dpq_flat_filter* ff, const uint8
 
 namespace {
 
-// dpq_flat_rerank_device / _u8_device: Q is float or uint8_t, the handle of the same kind.
+// dpq_flat_rerank_device / _u8_device / _ip_device: Q is float or uint8_t, the handle of the same kind.
 template <class Q>
-int flat_rerank_device_call(const char* fn, const char* other, dpq_flat* f, const Q* d_queries, int nq,
+int flat_rerank_device_call(const char* fn, const char* other, int metric, dpq_flat* f, const Q* d_queries, int nq,
                             const int32_t* d_cand_ids, int n_cand, int top_k, int32_t* d_ids, float* d_dists,
                             void* hip_stream) {
     int rc = flat_rerank_args(fn, other, f, std::is_same<Q, uint8_t>::value, d_queries, nq, d_cand_ids, n_cand, top_k, d_ids,
                               d_dists);
     if (rc || nq == 0) return rc;
     DPQ_HIP(hipSetDevice(f->device));
-    return flat_rerank_on_device(fn, f, d_queries, nq, d_cand_ids, n_cand, top_k, d_ids, d_dists, (hipStream_t)hip_stream);
+    return flat_rerank_on_device(fn, metric, f, d_queries, nq, d_cand_ids, n_cand, top_k, d_ids, d_dists, (hipStream_t)hip_stream);
 }
 
-// dpq_flat_rerank / _u8: the candidates are checked on the host, then queries and candidates go up and the answer down.
+// dpq_flat_rerank / _u8 / _ip: the candidates are checked on the host, then queries and candidates go up and the answer down.
 template <class Q>
-int flat_rerank_host_call(const char* fn, const char* other, dpq_flat* f, const Q* queries, int nq,
+int flat_rerank_host_call(const char* fn, const char* other, int metric, dpq_flat* f, const Q* queries, int nq,
                           const int32_t* cand_ids, int n_cand, int top_k, int32_t* ids, float* dists) {
     constexpr bool u8 = std::is_same<Q, uint8_t>::value;
     int rc = flat_rerank_args(fn, other, f, u8, queries, nq, cand_ids, n_cand, top_k, ids, dists);
@@ -547,7 +586,7 @@ int flat_rerank_host_call(const char* fn, const char* other, dpq_flat* f, const 
     if (rc) return rc;
     DPQ_HIP(hipMemcpy(d_q, queries, (size_t)nq * f->D * sizeof(Q), hipMemcpyHostToDevice));
     DPQ_HIP(hipMemcpy(f->d_cand, cand_ids, (size_t)nq * n_cand * sizeof(int32_t), hipMemcpyHostToDevice));
-    rc = flat_rerank_on_device(fn, f, d_q, nq, f->d_cand, n_cand, top_k, f->d_ids, f->d_dists, nullptr);
+    rc = flat_rerank_on_device(fn, metric, f, d_q, nq, f->d_cand, n_cand, top_k, f->d_ids, f->d_dists, nullptr);
     if (rc) return rc;
     DPQ_HIP(hipMemcpy(ids, f->d_ids, (size_t)nq * top_k * sizeof(int32_t), hipMemcpyDeviceToHost));
     DPQ_HIP(hipMemcpy(dists, f->d_dists, (size_t)nq * top_k * sizeof(float), hipMemcpyDeviceToHost));
@@ -561,7 +600,7 @@ extern "C" {
 int dpq_flat_rerank_device(dpq_flat* f, const float* d_queries, int nq, const int32_t* d_cand_ids, int n_cand, int top_k,
                            int32_t* d_ids, float* d_dists, void* hip_stream) {
     return guarded([&]() -> int {
-    return flat_rerank_device_call("dpq_flat_rerank", "dpq_flat_rerank_u8_device", f, d_queries, nq, d_cand_ids, n_cand,
+    return flat_rerank_device_call("dpq_flat_rerank", "dpq_flat_rerank_u8_device", dpq::kFlatL2, f, d_queries, nq, d_cand_ids, n_cand,
                                    top_k, d_ids, d_dists, hip_stream);
     });
 }
@@ -569,14 +608,14 @@ int dpq_flat_rerank_device(dpq_flat* f, const float* d_queries, int nq, const in
 int dpq_flat_rerank(dpq_flat* f, const float* queries, int nq, const int32_t* cand_ids, int n_cand, int top_k, int32_t* ids,
                     float* dists) {
     return guarded([&]() -> int {
-    return flat_rerank_host_call("dpq_flat_rerank", "dpq_flat_rerank_u8", f, queries, nq, cand_ids, n_cand, top_k, ids, dists);
+    return flat_rerank_host_call("dpq_flat_rerank", "dpq_flat_rerank_u8", dpq::kFlatL2, f, queries, nq, cand_ids, n_cand, top_k, ids, dists);
     });
 }
 
 int dpq_flat_rerank_u8_device(dpq_flat* f, const uint8_t* d_queries, int nq, const int32_t* d_cand_ids, int n_cand,
                               int top_k, int32_t* d_ids, float* d_dists, void* hip_stream) {
     return guarded([&]() -> int {
-    return flat_rerank_device_call("dpq_flat_rerank_u8_device", "dpq_flat_rerank_device", f, d_queries, nq, d_cand_ids,
+    return flat_rerank_device_call("dpq_flat_rerank_u8_device", "dpq_flat_rerank_device", dpq::kFlatL2, f, d_queries, nq, d_cand_ids,
                                    n_cand, top_k, d_ids, d_dists, hip_stream);
     });
 }
@@ -584,7 +623,58 @@ int dpq_flat_rerank_u8_device(dpq_flat* f, const uint8_t* d_queries, int nq, con
 int dpq_flat_rerank_u8(dpq_flat* f, const uint8_t* queries, int nq, const int32_t* cand_ids, int n_cand, int top_k,
                        int32_t* ids, float* dists) {
     return guarded([&]() -> int {
-    return flat_rerank_host_call("dpq_flat_rerank_u8", "dpq_flat_rerank", f, queries, nq, cand_ids, n_cand, top_k, ids, dists);
+    return flat_rerank_host_call("dpq_flat_rerank_u8", "dpq_flat_rerank", dpq::kFlatL2, f, queries, nq, cand_ids, n_cand, top_k,
+                                 ids, dists);
+    });
+}
+
+int dpq_flat_rerank_ip(dpq_flat* f, const float* queries, int nq, const int32_t* cand_ids, int n_cand, int top_k, int32_t* ids,
+                       float* scores) {
+    return guarded([&]() -> int {
+    return flat_rerank_host_call("dpq_flat_rerank_ip", nullptr, dpq::kFlatIP, f, queries, nq, cand_ids, n_cand, top_k, ids,
+                                 scores);
+    });
+}
+
+int dpq_flat_rerank_ip_device(dpq_flat* f, const float* d_queries, int nq, const int32_t* d_cand_ids, int n_cand, int top_k,
+                              int32_t* d_ids, float* d_scores, void* hip_stream) {
+    return guarded([&]() -> int {
+    return flat_rerank_device_call("dpq_flat_rerank_ip_device", nullptr, dpq::kFlatIP, f, d_queries, nq, d_cand_ids, n_cand,
+                                   top_k, d_ids, d_scores, hip_stream);
+    });
+}
+
+int dpq_merge_topk_ip_host(const int32_t* ids, const float* scores, int n_lists, int nq, int top_k, int32_t* out_ids,
+                           float* out_scores) {
+    return guarded([&]() -> int {
+    if (!ids || !scores || !out_ids || !out_scores || n_lists < 1 || nq < 0 || top_k < 1)
+        return fail(DPQ_ERR_ARG, "dpq_merge_topk_ip_host: NULL argument, n_lists < 1, nq < 0 or top_k < 1");
+    std::vector<uint64_t> keys;
+    for (int q = 0; q < nq; ++q) {
+        keys.clear();
+        for (int l = 0; l < n_lists; ++l)
+            for (int r = 0; r < top_k; ++r) {
+                const size_t o = ((size_t)l * nq + q) * top_k + r;
+                if (ids[o] < 0) continue;
+                uint32_t bits;
+                memcpy(&bits, &scores[o], 4);
+                keys.push_back(((uint64_t)dpq::flat_ip_word(bits) << 32) | (uint32_t)ids[o]);
+            }
+        const size_t kk = std::min((size_t)top_k, keys.size());
+        std::partial_sort(keys.begin(), keys.begin() + kk, keys.end());
+        for (int r = 0; r < top_k; ++r) {
+            const size_t o = (size_t)q * top_k + r;
+            if ((size_t)r < kk) {
+                out_ids[o] = (int32_t)(keys[r] & 0xffffffffu);
+                const uint32_t bits = dpq::flat_ip_word((uint32_t)(keys[r] >> 32));
+                memcpy(&out_scores[o], &bits, 4);
+            } else {
+                out_ids[o] = -1;
+                out_scores[o] = -INFINITY;
+            }
+        }
+    }
+    return DPQ_OK;
     });
 }
 

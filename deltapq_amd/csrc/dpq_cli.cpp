@@ -23,7 +23,9 @@
 // (main.cpp:243-277) with this build's own k-means (dpq_train_codebook); -task groundtruth and -task recall are
 // its brute-force ground truth (main.cpp:569-669) and recall measure (main.cpp:727-803) over raw vectors, the
 // latter with an optional exact re-rank of the PQ answer (-rerank R); -task decompress (no counterpart in the
-// reference) decodes the DTC index on the GPU back into the codes.bin.plain record layout.
+// reference) decodes the DTC index on the GPU back into the codes.bin.plain record layout.  -metric l2|ip (default l2)
+// switches groundtruth and recall to the inner product: dpq_flat_search_ip and its kin for the truth and the re-rank,
+// dpq_query_batch_ip for the PQ answer; the truth file is then groundtruth/N{N}Top{k}.ip.txt.
 #include <sys/stat.h>
 
 #include <algorithm>
@@ -83,6 +85,7 @@ static int rotate_rows(const std::string& dataset, int M, int K, std::vector<flo
 
 int main(int argc, char* argv[]) {
     std::string dataset, queryset, task = "approx_tree", ext = "fvecs", out_path, order = "dfs", filter_path, init = "rows";
+    std::string metric = "l2";
     int query_size = -1, top_k = 1, diff_argument = 1, debug = 0, max_height_folds = 1, method = 1;
     int PQ_M = 0, PQ_K = 0, gpus = 1, gt_topk = -1, rerank = 0;
     bool topk_given = false;
@@ -103,6 +106,7 @@ int main(int argc, char* argv[]) {
         if (arg == "-gt_topk") gt_topk = atoi(nx);
         if (arg == "-rerank") rerank = atoi(nx);
         if (arg == "-filter") filter_path = nx;
+        if (arg == "-metric") metric = nx;
         if (arg == "-N") N = atoll(nx);
         if (arg == "-diff") diff_argument = atoi(nx);
         if (arg == "-query_size") query_size = atoi(nx);
@@ -130,6 +134,13 @@ int main(int argc, char* argv[]) {
     if (opq && (task == "refine" || (task == "recall" && refine_r != 0))) {
         std::cout << "usage: -opq cannot be combined with -task refine or -refine R: a refine level over rotated codes is out of "
                      "scope" << std::endl;
+        return 2;
+    }
+
+    const bool ip = metric == "ip";
+    if ((!ip && metric != "l2") || (ip && (refine_r != 0 || gpus > 1 || (task != "groundtruth" && task != "recall")))) {
+        std::cout << "usage: -metric l2|ip (default l2); -metric ip serves -task groundtruth and -task recall [-rerank R] "
+                     "[-filter FILE] [-opq], and cannot be combined with -refine R or -gpus above 1" << std::endl;
         return 2;
     }
 
@@ -352,10 +363,12 @@ int main(int argc, char* argv[]) {
         // parts; every part is a dpq_flat handle with its own id offset, the partial lists meet in dpq_merge_topk_host.
         // With -ext bvecs the bytes stay bytes (dpq_flat_open_u8 / dpq_flat_search_u8): the same bits, the same file.
         if (dataset.empty() || !topk_given || top_k < 1 || query_size < 1) {
-            std::cout << "usage: deltapq -dataset DIR -task groundtruth -topk K -query_size Q [-N N] [-ext fvecs|bvecs] [-filter FILE]" << std::endl;
+            std::cout << "usage: deltapq -dataset DIR -task groundtruth -topk K -query_size Q [-N N] [-ext fvecs|bvecs] [-filter FILE]"
+                         " [-metric l2|ip]" << std::endl;
             return 2;
         }
-        const bool bvecs = ext == "bvecs";
+        // -metric ip: exact inner products (dpq_flat_search_ip); a .bvecs base is widened to fp32, there is no byte kernel
+        const bool file_bvecs = ext == "bvecs", bvecs = file_bvecs && !ip;
         const std::string q_path = dataset + "/query." + ext, base_path = dataset + "/base." + ext;
         int64_t nq_file = 0, n_file = 0;
         int32_t D = 0, Db = 0;
@@ -365,7 +378,7 @@ int main(int argc, char* argv[]) {
         std::vector<uint32_t> f_words;
         int64_t f_bits = 0;
         if (filtered && (rc = read_filter(filter_path, &f_words, &f_bits))) return die("dpq_read_bitmap", rc);
-        rc = dpq_read_vecs(q_path.c_str(), bvecs, &nq_file, &D, nullptr, 0);
+        rc = dpq_read_vecs(q_path.c_str(), file_bvecs, &nq_file, &D, nullptr, 0);
         if (rc) return die("ReadTopN", rc);
         if (query_size > nq_file) {
             std::cout << "-query_size " << query_size << " exceeds the " << nq_file << " available queries" << std::endl;
@@ -379,10 +392,10 @@ int main(int argc, char* argv[]) {
             rc = dpq_read_bvecs_range(q_path.c_str(), 0, nq, &D, queries8.data());
         } else {
             queries.resize((size_t)nq * D);
-            rc = dpq_read_vecs(q_path.c_str(), bvecs, &nq_file, &D, queries.data(), nq);
+            rc = dpq_read_vecs(q_path.c_str(), file_bvecs, &nq_file, &D, queries.data(), nq);
         }
         if (rc) return die("ReadTopN", rc);
-        rc = dpq_read_vecs(base_path.c_str(), bvecs, &n_file, &Db, nullptr, 0);
+        rc = dpq_read_vecs(base_path.c_str(), file_bvecs, &n_file, &Db, nullptr, 0);
         if (rc) return die("ItrReader", rc);
         if (Db != D) {
             std::cout << "query dimension " << D << " != base dimension " << Db << std::endl;
@@ -406,7 +419,8 @@ int main(int argc, char* argv[]) {
                 if (const char* e = getenv("DPQ_GT_PART_ROWS")) part_rows = std::max<int64_t>(1, atoll(e));  // developer knob
         const size_t list = (size_t)nq * top_k;
         std::vector<int32_t> two_ids(2 * list, -1), out_ids(list);  // [0] the answer so far, [1] the part's
-        std::vector<float> two_dists(2 * list, INFINITY), out_dists(list);
+        const float pad = ip ? -INFINITY : INFINITY;
+        std::vector<float> two_dists(2 * list, pad), out_dists(list);
         std::vector<float> part;
         std::vector<int32_t> p_ids;
         std::vector<float> p_dists;
@@ -422,7 +436,7 @@ int main(int argc, char* argv[]) {
                 rc = dpq_flat_open_u8(part8.data(), rows, D, 0, r0, &f);
             } else {
                 part.resize((size_t)rows * D);
-                rc = dpq_read_vecs_range(base_path.c_str(), bvecs, r0, rows, &Db, part.data());
+                rc = dpq_read_vecs_range(base_path.c_str(), file_bvecs, r0, rows, &Db, part.data());
                 if (rc) return die("ItrReader", rc);
                 rc = dpq_flat_open(part.data(), rows, D, 0, r0, &f);
             }
@@ -436,22 +450,25 @@ int main(int argc, char* argv[]) {
                 rc = dpq_flat_filter_create(f, f_words.data(), f_bits, &ff);
                 if (rc) return die("dpq_flat_filter_create", rc);
                 rc = bvecs ? dpq_flat_search_filtered_u8(f, ff, queries8.data(), nq, kk, p_ids.data(), p_dists.data())
+                     : ip  ? dpq_flat_search_filtered_ip(f, ff, queries.data(), nq, kk, p_ids.data(), p_dists.data())
                            : dpq_flat_search_filtered(f, ff, queries.data(), nq, kk, p_ids.data(), p_dists.data());
-                if (rc) return die(bvecs ? "dpq_flat_search_filtered_u8" : "dpq_flat_search_filtered", rc);
+                if (rc) return die(bvecs ? "dpq_flat_search_filtered_u8" : ip ? "dpq_flat_search_filtered_ip" : "dpq_flat_search_filtered", rc);
                 dpq_flat_filter_free(ff);
             } else {
                 rc = bvecs ? dpq_flat_search_u8(f, queries8.data(), nq, kk, p_ids.data(), p_dists.data())
+                     : ip  ? dpq_flat_search_ip(f, queries.data(), nq, kk, p_ids.data(), p_dists.data())
                            : dpq_flat_search(f, queries.data(), nq, kk, p_ids.data(), p_dists.data());
-                if (rc) return die(bvecs ? "dpq_flat_search_u8" : "dpq_flat_search", rc);
+                if (rc) return die(bvecs ? "dpq_flat_search_u8" : ip ? "dpq_flat_search_ip" : "dpq_flat_search", rc);
             }
             dpq_flat_close(f);
             for (int q = 0; q < nq; ++q)
                 for (int r = 0; r < top_k; ++r) {
                     two_ids[list + (size_t)q * top_k + r] = r < kk ? p_ids[(size_t)q * kk + r] : -1;
-                    two_dists[list + (size_t)q * top_k + r] = r < kk ? p_dists[(size_t)q * kk + r] : INFINITY;
+                    two_dists[list + (size_t)q * top_k + r] = r < kk ? p_dists[(size_t)q * kk + r] : pad;
                 }
-            rc = dpq_merge_topk_host(two_ids.data(), two_dists.data(), 2, nq, top_k, out_ids.data(), out_dists.data());
-            if (rc) return die("dpq_merge_topk_host", rc);
+            rc = ip ? dpq_merge_topk_ip_host(two_ids.data(), two_dists.data(), 2, nq, top_k, out_ids.data(), out_dists.data())
+                    : dpq_merge_topk_host(two_ids.data(), two_dists.data(), 2, nq, top_k, out_ids.data(), out_dists.data());
+            if (rc) return die(ip ? "dpq_merge_topk_ip_host" : "dpq_merge_topk_host", rc);
             std::copy(out_ids.begin(), out_ids.end(), two_ids.begin());
             std::copy(out_dists.begin(), out_dists.end(), two_dists.begin());
         }
@@ -461,7 +478,7 @@ int main(int argc, char* argv[]) {
         const std::string gt_dir = dataset + "/groundtruth";
         mkdir(gt_dir.c_str(), 0777);  // (exists already: fine)
         const std::string gt_path = gt_dir + "/N" + std::to_string(n) + "Top" + std::to_string(top_k) +
-                                    (filtered ? ".filtered.txt" : ".txt");  // main.cpp:663-667
+                                    (ip ? ".ip" : "") + (filtered ? ".filtered.txt" : ".txt");  // main.cpp:663-667
         rc = dpq_write_groundtruth(gt_path.c_str(), out_ids.data(), out_dists.data(), nq, top_k);
         if (rc) return die("write_groundtruth", rc);
         std::cout << gt_path << std::endl;
@@ -557,8 +574,8 @@ int main(int argc, char* argv[]) {
         // against base.{ext} (main.cpp:898-939) and reports the recall of that answer too.
         if (PQ_M <= 0 || PQ_K <= 0 || dataset.empty() || N < 1 || !topk_given || top_k < 1 || query_size < 1) {
             std::cout << "usage: deltapq -dataset DIR -task recall -m M -k K -N N -query_size Q -topk K [-gt_topk G] [-rerank R]"
-                         " [-ext fvecs|bvecs] [-filter FILE] [-opq] [-refine R [-m2 M2] [-k2 K2]]   (-refine: the level of -task refine,"
-                         " M <= 8)" << std::endl;
+                         " [-ext fvecs|bvecs] [-filter FILE] [-opq] [-refine R [-m2 M2] [-k2 K2]] [-metric l2|ip]   (-refine: the level of"
+                         " -task refine, M <= 8; -metric ip: dpq_query_batch_ip against the .ip.txt truth, not with -refine)" << std::endl;
             return 2;
         }
         if (gt_topk < 0) gt_topk = top_k;
@@ -617,7 +634,7 @@ int main(int argc, char* argv[]) {
         }
         const std::vector<float>& pq_queries = opq ? pq_queries_store : queries;
         const std::string gt_path = dataset + "/groundtruth/N" + std::to_string(N) + "Top" + std::to_string(gt_topk) +
-                                    (filtered ? ".filtered.txt" : ".txt");
+                                    (ip ? ".ip" : "") + (filtered ? ".filtered.txt" : ".txt");
         int32_t g_nq = 0, g_k = 0;
         rc = dpq_read_groundtruth(gt_path.c_str(), &g_nq, &g_k, nullptr, nullptr);
         if (rc) return die("read_groundtruth", rc);
@@ -666,9 +683,12 @@ int main(int argc, char* argv[]) {
         for (int q0 = 0; q0 < nq; q0 += 1024) {
             const int m = std::min(1024, nq - q0);
             const float* qp = pq_queries.data() + (size_t)q0 * D;
-            rc = filtered ? dpq_query_batch_filtered(idx, filt, qp, m, R, pos.data() + (size_t)q0 * R, pq_d.data() + (size_t)q0 * R)
-                          : dpq_query_batch(idx, qp, m, R, pos.data() + (size_t)q0 * R, pq_d.data() + (size_t)q0 * R);
-            if (rc) return die(filtered ? "dpq_query_batch_filtered" : "dpq_query_batch", rc);
+            int32_t* ids_at = pos.data() + (size_t)q0 * R;
+            float* d_at = pq_d.data() + (size_t)q0 * R;
+            rc = ip         ? dpq_query_batch_ip(idx, filt, qp, m, R, ids_at, d_at, nullptr, nullptr)  // filt may be NULL
+                 : filtered ? dpq_query_batch_filtered(idx, filt, qp, m, R, ids_at, d_at)
+                            : dpq_query_batch(idx, qp, m, R, ids_at, d_at);
+            if (rc) return die(ip ? "dpq_query_batch_ip" : filtered ? "dpq_query_batch_filtered" : "dpq_query_batch", rc);
         }
         std::cout << (Elapsed() - t0) / (double)nq * 1000 << " [msec/query] " << std::endl;
         dpq_filter_free(filt);
@@ -738,7 +758,7 @@ int main(int argc, char* argv[]) {
             if (rc) return die("ItrReader", rc);
             dpq_flat* f = nullptr;
             std::vector<uint8_t> queries8;
-            if (bvecs) {  // bytes stay bytes: a byte handle and the _u8 calls, the same bits
+            if (bvecs && !ip) {  // bytes stay bytes: a byte handle and the _u8 calls, the same bits
                 std::vector<uint8_t> base8((size_t)N * D);
                 queries8.resize((size_t)nq * D);
                 rc = dpq_read_bvecs_range(base_path.c_str(), 0, N, &Db, base8.data());
@@ -755,15 +775,16 @@ int main(int argc, char* argv[]) {
                 std::cout << "-rerank: base." << ext << " (" << N << " x " << D << ") does not fit into device memory" << std::endl;
                 return 1;
             }
-            if (rc) return die(bvecs ? "dpq_flat_open_u8" : "dpq_flat_open", rc);
+            if (rc) return die(bvecs && !ip ? "dpq_flat_open_u8" : "dpq_flat_open", rc);
             rc = dpq_flat_set_id_map(f, vec_id.data(), N);
             if (rc) return die("dpq_flat_set_id_map", rc);
             std::vector<int32_t> r_ids((size_t)nq * top_k);
             std::vector<float> r_d((size_t)nq * top_k);
             const double t1 = Elapsed();
-            rc = bvecs ? dpq_flat_rerank_u8(f, queries8.data(), nq, pos.data(), R, top_k, r_ids.data(), r_d.data())
-                       : dpq_flat_rerank(f, queries.data(), nq, pos.data(), R, top_k, r_ids.data(), r_d.data());
-            if (rc) return die(bvecs ? "dpq_flat_rerank_u8" : "dpq_flat_rerank", rc);
+            rc = ip      ? dpq_flat_rerank_ip(f, queries.data(), nq, pos.data(), R, top_k, r_ids.data(), r_d.data())
+                 : bvecs ? dpq_flat_rerank_u8(f, queries8.data(), nq, pos.data(), R, top_k, r_ids.data(), r_d.data())
+                         : dpq_flat_rerank(f, queries.data(), nq, pos.data(), R, top_k, r_ids.data(), r_d.data());
+            if (rc) return die(ip ? "dpq_flat_rerank_ip" : bvecs ? "dpq_flat_rerank_u8" : "dpq_flat_rerank", rc);
             std::cout << "re-rank " << (Elapsed() - t1) / (double)nq * 1000 << " [msec/query] " << std::endl;
             dpq_flat_close(f);
             rc = dpq_recall(r_ids.data(), top_k, top_k, truth.data(), g_k, top_k, nq, &rec);

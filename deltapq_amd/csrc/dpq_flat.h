@@ -1,9 +1,11 @@
-// dpq_flat.h -- exact L2 search over raw vectors on the GPU: fp32 (dpq_flat.hip) and bytes on the int8 matrix cores
-// (dpq_flat_u8.hip); top-k over a whole base or over the rows a filter lists, range search, re-ranking over a candidate
+// dpq_flat.h -- exact search over raw vectors on the GPU, by squared L2 or (fp32 only) by inner product: fp32
+// (dpq_flat.hip) and bytes on the int8 matrix cores (dpq_flat_u8.hip); top-k over a whole base or over the rows a filter lists, range search, re-ranking over a candidate
 // list per query.  The arithmetic is the reference's brute force (main.cpp:150-156), restated in include/deltapq_amd.h
 // and DESIGN.md 5.10.  Each element type has one distance kernel template <LIST, MODE> in its own file; one stripe
 // driver (launch_flat_search) and one range pass (launch_flat_range_pass) serve both types, with and without a filter.
 // What the kernels of the two files share -- the modes, the key sink, the padding key -- is defined here, once.
+// The metric is a compile-time parameter of the fp32 kernels beside <LIST, MODE>; it reaches them through
+// FlatBase::metric and the metric argument of launch_flat_rerank, so the drivers stay one of each kind.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -14,6 +16,17 @@ namespace dpq {
 
 constexpr int kFlatMaxTopK = 16384;  // DPQ_FLAT_MAX_TOPK, and the most candidates a re-rank takes per query
 constexpr int kFlatMaxD = 2048;
+
+// The metric of an fp32 kernel.  kFlatL2: the key's high word is the bits of the (non-negative) distance.  kFlatIP:
+// the score's bits mapped so that ascending keys are descending scores (flat_ip_word below); a byte base is L2 only.
+enum { kFlatL2 = 0, kFlatIP = 1 };
+// Score bits <-> high word of an inner-product key; the map is its own inverse.  -0.0 is read as +0.0 first.  A
+// non-negative score u becomes ~u & 0x7fffffff (larger scores, smaller words), a negative one keeps its bits (sign set,
+// larger magnitudes later): +inf 0x007fffff < 1.0 < +0.0 0x7fffffff < -1e-40 < -1.0 < -inf 0xff800000 < kFlatNoKey's.
+__host__ __device__ inline uint32_t flat_ip_word(uint32_t u) {
+    if (u == 0x80000000u) u = 0;
+    return (u & 0x80000000u) ? u : (~u & 0x7fffffffu);
+}
 
 // Per-query selection state of a search.  overflow: an append fell outside the key buffer (the launcher's striping
 // rules that out; a set word is reported as an internal error instead of a wrong answer).
@@ -44,6 +57,7 @@ struct FlatBase {
     bool filtered;
     const uint32_t* list;
     int64_t n_entries;
+    int metric = kFlatL2;  // kFlatIP: fp32 only
 };
 // Prepared queries of the base's kind: [nq][Dp] padded rows, with norms for bytes.
 struct FlatQueries {
@@ -72,14 +86,15 @@ __device__ __forceinline__ uint64_t* flat_sink_of(uint64_t* keys, int cap, const
 
 // Exact top_k of q.nq (<= flat_query_batch(top_k)) queries over the base's entries, all device pointers.
 // d_keys [nq][flat_key_capacity(top_k)], d_state [nq].  Fewer than top_k entries (a filter): rows are padded with
-// -1 / +inf.  Enqueues on `stream`; d_state[q].overflow and .count must be read back afterwards.
+// -1 / +inf (kFlatIP: -1 / -inf, and d_dists holds scores, descending).  Enqueues on `stream`; d_state[q].overflow and .count must be read back afterwards.
 hipError_t launch_flat_search(const FlatBase& b, const FlatQueries& q, int top_k, uint64_t* d_keys, FlatQueryState* d_state,
                               int32_t* d_ids, float* d_dists, hipStream_t stream);
 
 // Exact distances of cand[nq][n_cand] only, best top_k by (distance, reported id).  d_map (may be NULL) [n_map]: a
 // candidate is a DFS position, row = map[c], with the even-N rule; without it row = c - id_offset.  d_queries [nq][D]
 // unpadded.  d_keys [nq][n_cand rounded up to a power of two].  *d_flag is set when a candidate names no row.
-hipError_t launch_flat_rerank(const float* d_base, int64_t n, int D, int Dp, const float* d_queries, int nq,
+// metric kFlatIP: exact scores, best top_k by (score descending, reported id).
+hipError_t launch_flat_rerank(int metric, const float* d_base, int64_t n, int D, int Dp, const float* d_queries, int nq,
                               const int32_t* d_cand, int n_cand, int top_k, int64_t id_offset, const uint32_t* d_map,
                               int64_t n_map, uint64_t* d_keys, uint32_t* d_flag, int32_t* d_ids, float* d_dists,
                               hipStream_t stream);

@@ -1,17 +1,21 @@
-// dpq_flat.hip -- exact L2 distances between fp32 queries and fp32 base vectors on gfx950.
+// dpq_flat.hip -- exact L2 distances, or inner products, between fp32 queries and fp32 base vectors on gfx950
+// (DESIGN.md 5.10, 5.10.3).
 //
 // The arithmetic (include/deltapq_amd.h, "exact search"): per dimension, in ascending order, t = v[d] - q[d] and
 // s = t * t in fp32, each rounded on its own (the build passes -ffp-contract=off), then acc += (double)s on an fp64
 // accumulator that starts at +0.0; the reported distance is (float)acc.  One lane owns one distance from the first
 // dimension to the last, so the order of the sum is the reference's (main.cpp:150-156) and the bits are too.
+// METRIC = kFlatIP ("exact inner-product search"): acc = acc + (double)v[d] * (double)q[d] instead, one rounding per
+// step, and the score's bits go through flat_ip_word into the key, so that ascending keys are descending scores; the
+// kernels below are otherwise the same source.
 //
-//   flat_dist_kernel<LIST, MODE>
+//   flat_dist_kernel<LIST, MODE, METRIC>
 //                         the one fp32 distance kernel, for every search.  A workgroup takes 64 queries x 64 entries of
 //                         a stripe; both tiles go through LDS in slices of 32 dimensions, transposed so that a lane
 //                         reads its four queries and four vectors as two 16-byte LDS loads; 16 fp64 accumulators per
 //                         lane.  LIST: entry e is row l0 + e (false: every row, or a range search without a filter), or
 //                         row list[l0 + e] (true: a filter's row list), the tile's row numbers staged in LDS.  MODE,
-//                         what becomes of a key (distance bits << 32 | id):
+//                         what becomes of a key (distance bits, or the score's key word, << 32 | id):
 //                           kFlatTopK   key <= the query's threshold: appended to the query's buffer
 //                           kFlatCount  key <  the radius key: counted
 //                           kFlatEmit   key <  the radius key: appended to the query's list in the pool, whose length
@@ -20,8 +24,10 @@
 //                         FlatQueryState::overflow instead of storing outside it.
 //   flat_select_kernel    when a buffer is filling up: radix select of the top_k-th key, compaction in place, the
 //                         threshold lowered to that key.
-//   flat_sort_emit_kernel bitonic sort of a query's keys in LDS, duplicates dropped, ids and distances written.
-//   flat_rerank_kernel    a lane per candidate; a wavefront fetches its 64 rows with 16-byte loads into LDS, 32
+//   flat_sort_emit_kernel<METRIC>
+//                         bitonic sort of a query's keys in LDS, duplicates dropped, ids and distances (scores) written.
+//   flat_rerank_kernel<METRIC>
+//                         a lane per candidate; a wavefront fetches its 64 rows with 16-byte loads into LDS, 32
 //                         dimensions at a time, and every lane then walks its own row in order.
 // launch_flat_search is the one stripe driver (state, then per stripe a select and a distance launch, then the last
 // select and the sort) and launch_flat_range_pass the one range pass, for both element types, with and without a list;
@@ -39,8 +45,24 @@ constexpr int DC = 32;           // dimensions staged at a time
 constexpr int LD = TV + 4;       // LDS row stride in floats (16-byte aligned; spreads the transposed writes)
 constexpr int kSelThreads = 1024;
 
+template <int METRIC>
 __device__ __forceinline__ uint64_t make_key(double acc, uint32_t id) {
-    return ((uint64_t)__float_as_uint((float)acc) << 32) | id;
+    const uint32_t u = __float_as_uint((float)acc);
+    return ((uint64_t)(METRIC == kFlatIP ? flat_ip_word(u) : u) << 32) | id;
+}
+
+// One dimension of one (vector, query) pair on the lane's fp64 accumulator.  L2: the difference and its square each
+// rounded in fp32, then widened.  Inner product: both values widened first, so the product is exact and the step is one
+// rounding, fused or not.
+template <int METRIC>
+__device__ __forceinline__ void accumulate(double& acc, float v, float q) {
+    if constexpr (METRIC == kFlatIP) {
+        acc = fma((double)v, (double)q, acc);
+    } else {
+        const float t = v - q;
+        const float s = t * t;
+        acc += (double)s;
+    }
 }
 
 __global__ void flat_init_state_kernel(FlatQueryState* state, int nq) {
@@ -64,7 +86,7 @@ __global__ void flat_pad_rows_kernel(const float* in, int64_t rows, int D, int D
 // tx*4.. of the tile.  Entry e of the stripe is row l0 + e, computed where it is needed (LIST false: no row numbers in
 // LDS, no barrier before the first slice), or row list[l0 + e], staged once per tile in lrow.  Every instantiation is
 // the straight-line kernel of its case; nothing is picked at run time.
-template <bool LIST, int MODE>
+template <bool LIST, int MODE, int METRIC>
 __global__ __launch_bounds__(256) void flat_dist_kernel(const float* __restrict__ base, const uint32_t* __restrict__ list,
                                                         int64_t l0, int rows, int Dp, const float* __restrict__ queries,
                                                         int nq, int64_t id_offset, uint64_t* __restrict__ keys, int cap,
@@ -114,11 +136,7 @@ __global__ __launch_bounds__(256) void flat_dist_kernel(const float* __restrict_
 #pragma unroll
             for (int i = 0; i < 4; ++i)
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float t = va[j] - qa[i];
-                    const float s = t * t;
-                    acc[i][j] += (double)s;
-                }
+                for (int j = 0; j < 4; ++j) accumulate<METRIC>(acc[i][j], va[j], qa[i]);
         }
         __syncthreads();
     }
@@ -135,7 +153,7 @@ __global__ __launch_bounds__(256) void flat_dist_kernel(const float* __restrict_
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int ql = ty * 4 + i, vl = tx * 4 + j;
-            key[i][j] = make_key(acc[i][j], (uint32_t)(id_offset + row_of(vl)));
+            key[i][j] = make_key<METRIC>(acc[i][j], (uint32_t)(id_offset + row_of(vl)));
             const bool below = MODE == kFlatTopK ? key[i][j] <= thr[ql] : key[i][j] < thr[ql];
             const bool pass = q0 + ql < nq && v0 + vl < rows && below;
             slot[i][j] = pass ? atomicAdd(&cnt[ql], 1u) : 0xffffffffu;
@@ -241,6 +259,8 @@ __global__ __launch_bounds__(kSelThreads) void flat_select_kernel(uint64_t* keys
 
 // One workgroup per query: sort its keys (n_keys of them, or state[q].count) in LDS, drop repeats, write the first
 // top_k as (id, distance); rows are padded with -1 / +inf.  kFlatNoKey entries are padding.  n_pad: a power of two.
+// kFlatIP: the key's high word is unmade into the score's bits, and the padding is -1 / -inf.
+template <int METRIC>
 __global__ __launch_bounds__(kSelThreads) void flat_sort_emit_kernel(const uint64_t* __restrict__ keys, size_t stride,
                                                                      const FlatQueryState* state, int n_keys, int n_pad,
                                                                      int top_k, int32_t* __restrict__ ids,
@@ -275,17 +295,19 @@ __global__ __launch_bounds__(kSelThreads) void flat_sort_emit_kernel(const uint6
         if (sk[i] != kFlatNoKey && (i == 0 || sk[i] != sk[i - 1])) {
             if (pos < (uint32_t)top_k) {
                 ids[(size_t)q * top_k + pos] = (int32_t)(uint32_t)(sk[i] & 0xffffffffu);
-                dists[(size_t)q * top_k + pos] = __uint_as_float((uint32_t)(sk[i] >> 32));
+                const uint32_t w = (uint32_t)(sk[i] >> 32);
+                dists[(size_t)q * top_k + pos] = __uint_as_float(METRIC == kFlatIP ? flat_ip_word(w) : w);
             }
             ++pos;
         }
     for (int r = (int)total + tid; r < top_k; r += kSelThreads) {
         ids[(size_t)q * top_k + r] = -1;
-        dists[(size_t)q * top_k + r] = __uint_as_float(0x7f800000u);
+        dists[(size_t)q * top_k + r] = __uint_as_float(METRIC == kFlatIP ? 0xff800000u : 0x7f800000u);
     }
 }
 
 // grid (candidate groups of 256, queries), 256 threads: lane = candidate.
+template <int METRIC>
 __global__ __launch_bounds__(256) void flat_rerank_kernel(const float* __restrict__ base, int64_t n, int D, int Dp,
                                                           const float* __restrict__ queries,
                                                           const int32_t* __restrict__ cand, int n_cand, int n_pad,
@@ -326,15 +348,11 @@ __global__ __launch_bounds__(256) void flat_rerank_kernel(const float* __restric
         __syncthreads();
         const int dc = min(DC, Dp - d0);
 #pragma unroll 8
-        for (int d = 0; d < dc; ++d) {
-            const float t = tile[w][lane][d] - qv[d0 + d];
-            const float s = t * t;
-            acc += (double)s;
-        }
+        for (int d = 0; d < dc; ++d) accumulate<METRIC>(acc, tile[w][lane][d], qv[d0 + d]);
         __syncthreads();
     }
     if (ci < n_pad)
-        keys[(size_t)q * n_pad + ci] = row >= 0 ? make_key(acc, (uint32_t)((int64_t)row + id_offset)) : kFlatNoKey;
+        keys[(size_t)q * n_pad + ci] = row >= 0 ? make_key<METRIC>(acc, (uint32_t)((int64_t)row + id_offset)) : kFlatNoKey;
 }
 
 int pow2_at_least(int v) {
@@ -350,9 +368,11 @@ hipError_t ensure_sort_lds() {
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
     if (dev < 0 || dev >= 64 || !done[dev].load(std::memory_order_acquire)) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(flat_sort_emit_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, kFlatMaxTopK * (int)sizeof(uint64_t));
-        if (e != hipSuccess) return e;
+        for (const void* fn : {reinterpret_cast<const void*>(flat_sort_emit_kernel<kFlatL2>),
+                               reinterpret_cast<const void*>(flat_sort_emit_kernel<kFlatIP>)}) {
+            e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kFlatMaxTopK * (int)sizeof(uint64_t));
+            if (e != hipSuccess) return e;
+        }
         if (dev >= 0 && dev < 64) done[dev].store(true, std::memory_order_release);
     }
     return hipSuccess;
@@ -375,23 +395,36 @@ hipError_t launch_flat_pad_rows(const float* d_in, int64_t rows, int D, int Dp, 
 
 namespace {
 
-template <bool LIST, int MODE>
+template <bool LIST, int MODE, int METRIC>
 void dist_fp32(const FlatBase& b, int64_t e0, int rows, const FlatQueries& q, uint64_t* keys, int cap, const int64_t* offs,
                FlatQueryState* state, hipStream_t stream) {
-    flat_dist_kernel<LIST, MODE><<<dim3((rows + TV - 1) / TV, (q.nq + TQ - 1) / TQ), dim3(256), 0, stream>>>(
+    flat_dist_kernel<LIST, MODE, METRIC><<<dim3((rows + TV - 1) / TV, (q.nq + TQ - 1) / TQ), dim3(256), 0, stream>>>(
         b.f32, b.list, e0, rows, b.Dp, q.f32, q.nq, b.id_offset, keys, cap, offs, state);
 }
 
-// One distance launch over entries e0 .. e0 + rows - 1 of the base, by element type, row source and mode.
+template <int METRIC>
+auto* pick_dist_fp32(bool filtered, int mode) {
+    return filtered ? (mode == kFlatTopK    ? dist_fp32<true, kFlatTopK, METRIC>
+                       : mode == kFlatCount ? dist_fp32<true, kFlatCount, METRIC>
+                                            : dist_fp32<true, kFlatEmit, METRIC>)
+                    : (mode == kFlatTopK    ? dist_fp32<false, kFlatTopK, METRIC>
+                       : mode == kFlatCount ? dist_fp32<false, kFlatCount, METRIC>
+                                            : dist_fp32<false, kFlatEmit, METRIC>);
+}
+
+// The sort stage of a search or a re-rank, by metric.
+void sort_emit(int metric, const uint64_t* d_keys, size_t stride, const FlatQueryState* d_state, int nq, int n_keys,
+               int n_pad, int top_k, int32_t* d_ids, float* d_dists, hipStream_t stream) {
+    auto* kernel = metric == kFlatIP ? flat_sort_emit_kernel<kFlatIP> : flat_sort_emit_kernel<kFlatL2>;
+    kernel<<<dim3(nq), dim3(kSelThreads), (size_t)n_pad * sizeof(uint64_t), stream>>>(d_keys, stride, d_state, n_keys, n_pad,
+                                                                                     top_k, d_ids, d_dists);
+}
+
+// One distance launch over entries e0 .. e0 + rows - 1 of the base, by element type, metric, row source and mode.
 hipError_t launch_flat_dist(int mode, const FlatBase& b, int64_t e0, int rows, const FlatQueries& q, uint64_t* keys, int cap,
                             const int64_t* offs, FlatQueryState* state, hipStream_t stream) {
     if (b.i8) return launch_flat_dist_u8(mode, b, e0, rows, q, keys, cap, offs, state, stream);
-    auto* launch = b.filtered ? (mode == kFlatTopK    ? dist_fp32<true, kFlatTopK>
-                                 : mode == kFlatCount ? dist_fp32<true, kFlatCount>
-                                                      : dist_fp32<true, kFlatEmit>)
-                              : (mode == kFlatTopK    ? dist_fp32<false, kFlatTopK>
-                                 : mode == kFlatCount ? dist_fp32<false, kFlatCount>
-                                                      : dist_fp32<false, kFlatEmit>);
+    auto* launch = b.metric == kFlatIP ? pick_dist_fp32<kFlatIP>(b.filtered, mode) : pick_dist_fp32<kFlatL2>(b.filtered, mode);
     launch(b, e0, rows, q, keys, cap, offs, state, stream);
     return hipGetLastError();
 }
@@ -418,8 +451,7 @@ hipError_t launch_flat_search(const FlatBase& b, const FlatQueries& q, int top_k
     }
     flat_select_kernel<<<dim3(nq), dim3(kSelThreads), 0, stream>>>(d_keys, cap, d_state, top_k, (uint32_t)top_k);
     const int n_pad = pow2_at_least(top_k);
-    flat_sort_emit_kernel<<<dim3(nq), dim3(kSelThreads), (size_t)n_pad * sizeof(uint64_t), stream>>>(
-        d_keys, (size_t)cap, d_state, top_k, n_pad, top_k, d_ids, d_dists);
+    sort_emit(b.metric, d_keys, (size_t)cap, d_state, nq, top_k, n_pad, top_k, d_ids, d_dists, stream);
     return hipGetLastError();
 }
 
@@ -430,7 +462,7 @@ hipError_t launch_flat_range_pass(const FlatBase& b, const FlatQueries& q, uint6
                             d_state, stream);
 }
 
-hipError_t launch_flat_rerank(const float* d_base, int64_t n, int D, int Dp, const float* d_queries, int nq,
+hipError_t launch_flat_rerank(int metric, const float* d_base, int64_t n, int D, int Dp, const float* d_queries, int nq,
                               const int32_t* d_cand, int n_cand, int top_k, int64_t id_offset, const uint32_t* d_map,
                               int64_t n_map, uint64_t* d_keys, uint32_t* d_flag, int32_t* d_ids, float* d_dists,
                               hipStream_t stream) {
@@ -440,12 +472,12 @@ hipError_t launch_flat_rerank(const float* d_base, int64_t n, int D, int Dp, con
     const int n_pad = pow2_at_least(n_cand);
     for (int q0 = 0; q0 < nq; q0 += 65535) {  // the grid's y extent
         const int m = std::min(65535, nq - q0);
-        flat_rerank_kernel<<<dim3((n_pad + 255) / 256, m), dim3(256), 0, stream>>>(
+        auto* kernel = metric == kFlatIP ? flat_rerank_kernel<kFlatIP> : flat_rerank_kernel<kFlatL2>;
+        kernel<<<dim3((n_pad + 255) / 256, m), dim3(256), 0, stream>>>(
             d_base, n, D, Dp, d_queries + (size_t)q0 * D, d_cand + (size_t)q0 * n_cand, n_cand, n_pad, id_offset, d_map,
             n_map, d_keys + (size_t)q0 * n_pad, d_flag);
     }
-    flat_sort_emit_kernel<<<dim3(nq), dim3(kSelThreads), (size_t)n_pad * sizeof(uint64_t), stream>>>(
-        d_keys, (size_t)n_pad, nullptr, n_pad, n_pad, top_k, d_ids, d_dists);
+    sort_emit(metric, d_keys, (size_t)n_pad, nullptr, nq, n_pad, n_pad, top_k, d_ids, d_dists, stream);
     return hipGetLastError();
 }
 
@@ -454,8 +486,7 @@ hipError_t launch_flat_sort_emit(const uint64_t* d_keys, size_t stride, const Fl
     hipError_t e = ensure_sort_lds();
     if (e != hipSuccess) return e;
     const int n_pad = pow2_at_least(n_keys);
-    flat_sort_emit_kernel<<<dim3(nq), dim3(kSelThreads), (size_t)n_pad * sizeof(uint64_t), stream>>>(
-        d_keys, stride, d_state, n_keys, n_pad, top_k, d_ids, d_dists);
+    sort_emit(kFlatL2, d_keys, stride, d_state, nq, n_keys, n_pad, top_k, d_ids, d_dists, stream);
     return hipGetLastError();
 }
 

@@ -46,6 +46,9 @@
  *     PQ codes)
  *   (none: a caller's own distance tables:      dpq_query_batch_tables / dpq_range_search_tables
  *     weights, masks, residual queries)
+ *   (none: FAISS's IndexFlatIP: search, an      dpq_flat_search_ip / dpq_flat_search_filtered_ip /
+ *     IDSelector, range_search; re-ranking by     dpq_flat_range_search_ip / dpq_flat_rerank_ip[_device],
+ *     inner product)                              dpq_merge_topk_ip_host
  *
  * Conventions: plain pointers and sizes only; the caller owns every host
  * buffer it passes, the library owns device memory.  Every function returns a
@@ -764,6 +767,55 @@ int dpq_read_groundtruth(const char* path, int32_t* nq, int32_t* top_k, int32_t*
  * (main.cpp:783-796); k = 1 gives 1-recall@R. */
 int dpq_recall(const int32_t* found, int found_stride, int R, const int32_t* truth, int truth_stride, int k, int nq,
                double* recall);
+
+/* ---- exact inner-product search over raw vectors -------------------------------
+ * The exact counterpart of dpq_query_batch_ip: every kind of exact search above, by inner product instead of squared L2,
+ * on an fp32 handle of dpq_flat_open.  FAISS's IndexFlatIP; the reference has no inner product.
+ * The arithmetic, met bit for bit.  For a base vector v and a query q, both fp32 [D], acc is an fp64 value starting at
+ * +0.0; for d = 0 .. D-1 in ascending order:
+ *     acc = acc + (double)v[d] * (double)q[d].
+ * The product of two fp32 values is exact in fp64, so each step is one rounding and a fused multiply-add or a multiply
+ * followed by an add give the same bits: the rule does not depend on -ffp-contract.  The score is s = (float)acc, round
+ * to nearest even.  A score of -0.0 is reported and ordered as +0.0 (a tiny negative acc rounds to -0.0; acc itself is
+ * never -0.0).  This is the rule of dpq_ip_tables' p[m][k]; one lane owns one score from the first dimension to the
+ * last.  tests/_exact_ip_restatement.py restates these rules in numpy.
+ * Order: (score descending, id ascending); at the k-th boundary the lowest ids win.  The selection is that of
+ * dpq_flat_search, on keys `hi << 32 | id` with, u being the bits of the normalised score,
+ *     hi = (u & 0x80000000) ? u : (~u & 0x7fffffff),
+ * so that ascending keys are descending scores (+inf, 3.5, 1.0, 1e-40, 0.0, -1e-40, -1.0, -inf map to ascending hi), and
+ * the all-ones padding key has the high word of a negative NaN and collides with no score.  Padding rows are id -1 with
+ * score -inf.  Non-finite inputs, and scores that overflow fp32, are unspecified.
+ * What carries over from the L2 function of the same shape: dpq_flat_search_ip -- the argument checks, DPQ_ERR_TOPK, nq
+ * == 0 and id_offset of dpq_flat_search; dpq_flat_search_filtered_ip -- the filter, the padding and the all-padding
+ * answer of an empty filter of dpq_flat_search_filtered; dpq_flat_rerank_ip[_device] -- candidates, negative candidates
+ * as padding, the id map with its even-n_map rule, a row named twice counting once and the flag word of
+ * dpq_flat_rerank[_device]; the order of the checks of each.
+ * Range: the list of query q holds every eligible row with s > thresholds[q], STRICTLY (FAISS's inner-product
+ * convention); the `dists` array of the dpq_range_result holds the scores, and a list is ordered by (score descending, id
+ * ascending).  A threshold of -inf keeps every row, +inf none, -0.0 is read as +0.0; a NaN threshold is DPQ_ERR_ARG,
+ * checked before any device work.
+ * Byte handles are out of scope: an _ip call on a handle of dpq_flat_open_u8 is DPQ_ERR_ARG with a message that says so.
+ * The byte kernel gets its L2 from sum (v - q)^2 = |v|^2 + |q|^2 - 2 v.q on biased int8 rows; the inner product of the
+ * UNBIASED bytes needs, beside the int8 dot product, the per-row sum of the bytes -- an array the open call does not
+ * compute today.  Widen such data to fp32 (dpq_read_vecs_range does) and use dpq_flat_open. */
+int dpq_flat_search_ip(dpq_flat* f, const float* queries, int nq, int top_k, int32_t* ids, float* scores);
+int dpq_flat_search_filtered_ip(dpq_flat* f, const dpq_flat_filter* ff, const float* queries, int nq, int top_k, int32_t* ids,
+                                float* scores);
+/* ff may be NULL: every row of the handle is eligible.  queries[nq][D], thresholds[nq]: host memory. */
+int dpq_flat_range_search_ip(dpq_flat* f, const dpq_flat_filter* ff, const float* queries, int nq, const float* thresholds,
+                             dpq_range_result** out);
+int dpq_flat_rerank_ip(dpq_flat* f, const float* queries, int nq, const int32_t* cand_ids, int n_cand, int top_k, int32_t* ids,
+                       float* scores);
+int dpq_flat_rerank_ip_device(dpq_flat* f, const float* d_queries, int nq, const int32_t* d_cand_ids, int n_cand, int top_k,
+                              int32_t* d_ids, float* d_scores, void* hip_stream);
+/* Host only: dpq_merge_topk_host for lists of scores.  ids / scores [n_lists][nq][top_k]; the answer is the best top_k of
+ * a query's n_lists * top_k rows by (score descending, id ascending).  A row with id < 0 is padding; repeated rows are
+ * kept; missing rows are padded with -1 / -inf; -0.0 is reported as +0.0.  A base searched part by part, each part a
+ * handle with its own id_offset, merges its dpq_flat_search_ip answers here (dpq_merge_topk_host orders by distance bits,
+ * which puts every negative score last and the positive ones upside down).  DPQ_ERR_ARG: a NULL pointer, n_lists < 1,
+ * top_k < 1, nq < 0. */
+int dpq_merge_topk_ip_host(const int32_t* ids, const float* scores, int n_lists, int nq, int top_k, int32_t* out_ids,
+                           float* out_scores);
 
 /* ---- residual re-ranking: a second PQ level refines a shortlist ---------------
  * Every answer of dpq_query_batch is a coarse PQ approximation, and dpq_flat_rerank needs the raw vectors on the GPU
