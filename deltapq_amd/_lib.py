@@ -188,6 +188,10 @@ SYMBOLS = [
     ("dpq_flat_rerank_ip", ctypes.c_int, [_VP, _VP, ctypes.c_int, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP]),
     ("dpq_flat_rerank_ip_device", ctypes.c_int, [_VP, _VP, ctypes.c_int, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP]),
     ("dpq_merge_topk_ip_host", ctypes.c_int, [_VP, _VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, _VP, _VP]),
+    ("dpq_half_from_float", ctypes.c_int, [_VP, c_i64, ctypes.c_int, _VP]),
+    ("dpq_half_to_float", ctypes.c_int, [_VP, c_i64, ctypes.c_int, _VP]),
+    ("dpq_flat_open_half", ctypes.c_int, [_VP, c_i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_i64, P(_VP)]),
+    ("dpq_flat_open_narrowed", ctypes.c_int, [_VP, c_i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_i64, P(_VP)]),
     ("dpq_range_recall", ctypes.c_int, [ctypes.c_int, _VP, _VP, _VP, _VP, P(ctypes.c_double), P(ctypes.c_double)]),
     ("dpq_bitmap_to_dfs", ctypes.c_int, [_VP, c_i64, _VP, c_i64, _VP]),
     ("dpq_write_bitmap", ctypes.c_int, [ctypes.c_char_p, _VP, c_i64]),

@@ -1297,6 +1297,76 @@ class FlatIndex:
         self.close()
 
 
+HALF_FORMATS = {"f16": 1, "bf16": 2}   # DPQ_HALF_F16, DPQ_HALF_BF16
+
+
+def _half_format(fmt):
+    if fmt not in HALF_FORMATS:
+        raise ValueError("fmt must be 'f16' or 'bf16'")
+    return HALF_FORMATS[fmt]
+
+
+def half_from_float(a, fmt):
+    """float32 array -> uint16 array of the same shape: the bits of the values narrowed to fp16 ('f16') or bf16 ('bf16'),
+    round to nearest, ties to even (dpq_half_from_float; host only)."""
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    out = np.empty(a.shape, dtype=np.uint16)
+    check(_lib.load().dpq_half_from_float(_np_ptr(a), a.size, _half_format(fmt), _np_ptr(out)), "dpq_half_from_float")
+    return out
+
+
+def half_to_float(a, fmt):
+    """uint16 bits (or a np.float16 array with fmt 'f16') -> the float32 values they stand for, exactly
+    (dpq_half_to_float; host only)."""
+    a = np.asarray(a)
+    if a.dtype == np.float16 and fmt == "f16":
+        a = a.view(np.uint16)
+    if a.dtype != np.uint16:
+        raise TypeError("half_to_float takes uint16 bits (or float16 with fmt 'f16')")
+    a = np.ascontiguousarray(a)
+    out = np.empty(a.shape, dtype=np.float32)
+    check(_lib.load().dpq_half_to_float(_np_ptr(a), a.size, _half_format(fmt), _np_ptr(out)), "dpq_half_to_float")
+    return out
+
+
+class FlatIndexHalf(FlatIndex):
+    """fp16 or bf16 vectors [n][D] on one GPU, at half the device memory of FlatIndex: every method of FlatIndex, with
+    fp32 queries, and bit for bit FlatIndex's answers over the rows widened to fp32 (half_to_float).  `vectors` is a
+    float32 array (narrowed on the GPU, dpq_flat_open_narrowed), or 16-bit data kept as it is (dpq_flat_open_half): a
+    np.float16 array (fmt 'f16'), a np.uint16 array of raw bits, or a CPU torch tensor of dtype float16 / bfloat16
+    matching fmt."""
+
+    def __init__(self, vectors, fmt="f16", device=0, id_offset=0):
+        self._lib = _lib.load()
+        self._h = None
+        self.fmt = fmt
+        code = _half_format(fmt)
+        if not isinstance(vectors, np.ndarray) and hasattr(vectors, "is_cuda"):       # a torch tensor
+            import torch
+            want = {"f16": torch.float16, "bf16": torch.bfloat16}[fmt]
+            if vectors.is_cuda or vectors.dtype != want:
+                raise TypeError("a tensor must live on the CPU and have dtype %s for fmt '%s'" % (want, fmt))
+            vectors = vectors.contiguous().view(torch.int16).numpy().view(np.uint16)
+        v = np.asarray(vectors)
+        if v.dtype == np.float16:
+            if fmt != "f16":
+                raise TypeError("a float16 array needs fmt 'f16'")
+            v = v.view(np.uint16)
+        if v.dtype == np.uint16:
+            name = "dpq_flat_open_half"
+        elif v.dtype == np.float32:
+            name = "dpq_flat_open_narrowed"
+        else:
+            raise TypeError("vectors must be float32, float16 or uint16 bits (got %s)" % v.dtype)
+        v = np.ascontiguousarray(v)
+        if v.ndim != 2:
+            raise ValueError("vectors must be [n][D]")
+        self.n, self.D, self.id_offset = int(v.shape[0]), int(v.shape[1]), int(id_offset)
+        h = ctypes.c_void_p()
+        check(getattr(self._lib, name)(_np_ptr(v), self.n, self.D, code, device, id_offset, ctypes.byref(h)), name)
+        self._h = h
+
+
 class FlatIndexU8:
     """Byte vectors [n][D] on one GPU (dpq_flat_open_u8): FlatIndex's answers -- the same ids and the same distance bits as
     on the bytes widened to fp32 -- from the int8 matrix cores, at a quarter of the device memory.  Takes uint8 arrays and

@@ -23,6 +23,11 @@ int flat_rerank_on_device(const char* fn, int metric, dpq_flat* f, const Q* d_qu
                                                d_cand + (size_t)q0 * n_cand, n_cand, top_k, f->id_offset, map,
                                                (int64_t)f->h_map.size(), f->keys, f->flag, d_ids + (size_t)q0 * top_k,
                                                d_dists + (size_t)q0 * top_k, stream));
+        else if (f->half)
+            DPQ_HIP(dpq::launch_flat_rerank_half(metric, f->half, f->base16, f->n, f->D, f->Dp, d_queries + (size_t)q0 * f->D, m,
+                                                 d_cand + (size_t)q0 * n_cand, n_cand, top_k, f->id_offset, map,
+                                                 (int64_t)f->h_map.size(), f->keys, f->flag, d_ids + (size_t)q0 * top_k,
+                                                 d_dists + (size_t)q0 * top_k, stream));
         else
             DPQ_HIP(dpq::launch_flat_rerank(metric, f->base, f->n, f->D, f->Dp, d_queries + (size_t)q0 * f->D, m,
                                             d_cand + (size_t)q0 * n_cand, n_cand, top_k, f->id_offset, map,
@@ -36,10 +41,13 @@ int flat_rerank_on_device(const char* fn, int metric, dpq_flat* f, const Q* d_qu
     return DPQ_OK;
 }
 
-// A handle takes the calls of its own kind only: the fp32 functions an fp32 handle, the _u8 functions a byte handle.
-// The _ip functions (other == NULL) have no byte counterpart.
+// A handle takes the calls of its own kind only: the fp32-query functions an fp32 or a half handle, the _u8 functions a
+// byte handle.  The _ip functions (other == NULL) have no byte counterpart.
 int flat_kind(const dpq_flat* f, bool u8, const char* fn, const char* other) {
     if (f->u8 == u8) return DPQ_OK;
+    if (f->half)
+        return fail(DPQ_ERR_ARG, std::string(fn) + ": the handle holds half-precision vectors (dpq_flat_open_half, "
+                                                   "dpq_flat_open_narrowed), searched with fp32 queries; call " + other);
     if (!other)
         return fail(DPQ_ERR_ARG, std::string(fn) + ": the handle holds byte vectors (dpq_flat_open_u8), which have no "
                                                    "inner-product search; open the vectors as fp32 with dpq_flat_open");
@@ -56,8 +64,10 @@ int flat_rerank_args(const char* fn, const char* other, const dpq_flat* f, bool 
     return DPQ_OK;
 }
 
-// The checks of dpq_flat_open / dpq_flat_open_u8: the arguments before any device call, then the device.
-int flat_open_args(const char* fn, const void* vectors, int64_t n, int D, int device, int64_t id_offset, dpq_flat** out) {
+// The checks of every dpq_flat_open*: the arguments (the half format too, where there is one) before any device call,
+// then the device.
+int flat_open_args(const char* fn, const void* vectors, int64_t n, int D, int device, int64_t id_offset, dpq_flat** out,
+                   const int* half_format = nullptr) {
     const std::string who(fn);
     if (out) *out = nullptr;
     if (!vectors || !out) return fail(DPQ_ERR_ARG, who + ": NULL argument");
@@ -65,11 +75,51 @@ int flat_open_args(const char* fn, const void* vectors, int64_t n, int D, int de
     if (D < 1 || D > dpq::kFlatMaxD) return fail(DPQ_ERR_ARG, who + ": D outside 1..2048");
     if (id_offset < 0 || n + id_offset >= ((int64_t)1 << 31))
         return fail(DPQ_ERR_ARG, who + ": id_offset < 0 or n + id_offset >= 2^31 (ids are int32)");
+    if (half_format && *half_format != DPQ_HALF_F16 && *half_format != DPQ_HALF_BF16)
+        return fail(DPQ_ERR_ARG, who + ": format is neither DPQ_HALF_F16 nor DPQ_HALF_BF16");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail(DPQ_ERR_NO_DEVICE, "no HIP device visible; this library has no CPU fallback");
     if (device < 0 || device >= ndev) return fail(DPQ_ERR_NO_DEVICE, "device ordinal out of range");
     DPQ_HIP(hipSetDevice(device));
+    return DPQ_OK;
+}
+
+// dpq_flat_open_half (h16 given) and dpq_flat_open_narrowed (f32 given): the rows go up in slices of at most 128 MB and
+// are padded, or narrowed and padded, on the device.
+int flat_open_16(const char* fn, const uint16_t* h16, const float* f32, int64_t n, int D, int format, int device,
+                 int64_t id_offset, dpq_flat** out) {
+    if (int rc = flat_open_args(fn, h16 ? (const void*)h16 : (const void*)f32, n, D, device, id_offset, out, &format)) return rc;
+    std::unique_ptr<dpq_flat> f(new dpq_flat);
+    f->device = device;
+    f->n = n;
+    f->id_offset = id_offset;
+    f->D = D;
+    f->Dp = dpq::flat_half_padded_d(D);
+    f->half = format;
+    int rc = f->base16.alloc((size_t)n * f->Dp);
+    if (rc) return fail(rc, std::string(fn) + ": the vectors do not fit into device memory (" + dpq_last_error() + ")");
+    if (h16 && f->Dp == D) {
+        DPQ_HIP(hipMemcpy(f->base16, h16, (size_t)n * D * sizeof(uint16_t), hipMemcpyHostToDevice));
+    } else {
+        const size_t elem = h16 ? sizeof(uint16_t) : sizeof(float);
+        const int64_t tile = std::max<int64_t>(1, ((int64_t)128 << 20) / ((int64_t)D * (int64_t)elem));  // rows per upload
+        DevBuf<uint8_t> tmp;
+        if ((rc = tmp.alloc((size_t)std::min(n, tile) * D * elem))) return rc;
+        for (int64_t r0 = 0; r0 < n; r0 += tile) {
+            const int64_t m = std::min(tile, n - r0);
+            uint16_t* dst = f->base16.get() + (size_t)r0 * f->Dp;
+            if (h16) {
+                DPQ_HIP(hipMemcpy(tmp, h16 + (size_t)r0 * D, (size_t)m * D * elem, hipMemcpyHostToDevice));
+                DPQ_HIP(dpq::launch_flat_half_prepare(reinterpret_cast<const uint16_t*>(tmp.get()), m, D, f->Dp, dst, nullptr));
+            } else {
+                DPQ_HIP(hipMemcpy(tmp, f32 + (size_t)r0 * D, (size_t)m * D * elem, hipMemcpyHostToDevice));
+                DPQ_HIP(dpq::launch_flat_half_narrow(reinterpret_cast<const float*>(tmp.get()), m, D, f->Dp, format, dst, nullptr));
+            }
+            DPQ_HIP(hipDeviceSynchronize());
+        }
+    }
+    *out = f.release();
     return DPQ_OK;
 }
 
@@ -116,7 +166,7 @@ int flat_grow_queries(dpq_flat* f, size_t qb) {
 // of dpq_flat.h take them.
 dpq::FlatBase flat_base(const dpq_flat* f, const dpq_flat_filter* ff, int metric) {
     return {f->base, f->base8, f->norm8, f->Dp, f->id_offset, ff != nullptr, ff ? ff->list.get() : nullptr,
-            ff ? ff->n_allowed : f->n, metric};
+            ff ? ff->n_allowed : f->n, metric, f->base16, f->half};
 }
 
 dpq::FlatQueries flat_queries(const dpq_flat* f, int a, int m) {
@@ -219,6 +269,41 @@ int dpq_flat_open_u8(const uint8_t* vectors, int64_t n, int D, int device, int64
     });
 }
 
+int dpq_half_from_float(const float* in, int64_t count, int format, uint16_t* out) {
+    return guarded([&]() -> int {
+    if (count < 0 || (count > 0 && (!in || !out))) return fail(DPQ_ERR_ARG, "dpq_half_from_float: NULL argument or count < 0");
+    if (format != DPQ_HALF_F16 && format != DPQ_HALF_BF16)
+        return fail(DPQ_ERR_ARG, "dpq_half_from_float: format is neither DPQ_HALF_F16 nor DPQ_HALF_BF16");
+    for (int64_t i = 0; i < count; ++i) {
+        uint32_t u;
+        memcpy(&u, in + i, sizeof u);
+        out[i] = dpq::flat_half_narrow(u, format);
+    }
+    return DPQ_OK;
+    });
+}
+
+int dpq_half_to_float(const uint16_t* in, int64_t count, int format, float* out) {
+    return guarded([&]() -> int {
+    if (count < 0 || (count > 0 && (!in || !out))) return fail(DPQ_ERR_ARG, "dpq_half_to_float: NULL argument or count < 0");
+    if (format != DPQ_HALF_F16 && format != DPQ_HALF_BF16)
+        return fail(DPQ_ERR_ARG, "dpq_half_to_float: format is neither DPQ_HALF_F16 nor DPQ_HALF_BF16");
+    for (int64_t i = 0; i < count; ++i) {
+        const uint32_t u = dpq::flat_half_widen(in[i], format);
+        memcpy(out + i, &u, sizeof u);
+    }
+    return DPQ_OK;
+    });
+}
+
+int dpq_flat_open_half(const uint16_t* vectors, int64_t n, int D, int format, int device, int64_t id_offset, dpq_flat** out) {
+    return guarded([&]() -> int { return flat_open_16("dpq_flat_open_half", vectors, nullptr, n, D, format, device, id_offset, out); });
+}
+
+int dpq_flat_open_narrowed(const float* vectors, int64_t n, int D, int format, int device, int64_t id_offset, dpq_flat** out) {
+    return guarded([&]() -> int { return flat_open_16("dpq_flat_open_narrowed", nullptr, vectors, n, D, format, device, id_offset, out); });
+}
+
 int dpq_flat_close(dpq_flat* f) {
     return guarded([&]() -> int {
     if (!f) return DPQ_OK;
@@ -313,7 +398,7 @@ int flat_filter_owner(const dpq_flat* f, const dpq_flat_filter* ff, const std::s
     return fail(DPQ_ERR_ARG, who + ": the filter was made for another handle");
 }
 
-// dpq_flat_search_filtered / _u8 / _ip: Q is float or uint8_t, the handle of the same kind.
+// dpq_flat_search_filtered / _u8 / _ip: Q is float (an fp32 or a half handle) or uint8_t (a byte handle).
 template <class Q>
 int flat_search_filtered_call(const char* fn, const char* other, int metric, dpq_flat* f, const dpq_flat_filter* ff, const Q* queries,
                               int nq, int top_k, int32_t* ids, float* dists) {

@@ -157,7 +157,9 @@ struct dpq_flat {
     int64_t n = 0, id_offset = 0;
     int D = 0, Dp = 0;
     bool u8 = false;              // opened by dpq_flat_open_u8
+    int half = 0;                 // opened by dpq_flat_open_half / _narrowed: DPQ_HALF_F16 or DPQ_HALF_BF16
     DevBuf<float> base;           // [n][Dp]
+    DevBuf<uint16_t> base16;      // [n][Dp] (half handle)
     DevBuf<int8_t> base8;         // [n][Dp] (byte handle)
     DevBuf<int32_t> norm8;        // [n rounded up to 4]
     DevBuf<uint32_t> map;         // DFS position -> row (dpq_flat_set_id_map)

@@ -25,7 +25,8 @@
 // latter with an optional exact re-rank of the PQ answer (-rerank R); -task decompress (no counterpart in the
 // reference) decodes the DTC index on the GPU back into the codes.bin.plain record layout.  -metric l2|ip (default l2)
 // switches groundtruth and recall to the inner product: dpq_flat_search_ip and its kin for the truth and the re-rank,
-// dpq_query_batch_ip for the PQ answer; the truth file is then groundtruth/N{N}Top{k}.ip.txt.
+// dpq_query_batch_ip for the PQ answer; the truth file is then groundtruth/N{N}Top{k}.ip.txt.  -store f16|bf16 runs
+// recall's re-rank a second time from the base narrowed to that format (dpq_flat_open_narrowed).
 #include <sys/stat.h>
 
 #include <algorithm>
@@ -85,7 +86,7 @@ static int rotate_rows(const std::string& dataset, int M, int K, std::vector<flo
 
 int main(int argc, char* argv[]) {
     std::string dataset, queryset, task = "approx_tree", ext = "fvecs", out_path, order = "dfs", filter_path, init = "rows";
-    std::string metric = "l2";
+    std::string metric = "l2", store;
     int query_size = -1, top_k = 1, diff_argument = 1, debug = 0, max_height_folds = 1, method = 1;
     int PQ_M = 0, PQ_K = 0, gpus = 1, gt_topk = -1, rerank = 0;
     bool topk_given = false;
@@ -107,6 +108,7 @@ int main(int argc, char* argv[]) {
         if (arg == "-rerank") rerank = atoi(nx);
         if (arg == "-filter") filter_path = nx;
         if (arg == "-metric") metric = nx;
+        if (arg == "-store") store = nx;
         if (arg == "-N") N = atoll(nx);
         if (arg == "-diff") diff_argument = atoi(nx);
         if (arg == "-query_size") query_size = atoi(nx);
@@ -141,6 +143,13 @@ int main(int argc, char* argv[]) {
     if ((!ip && metric != "l2") || (ip && (refine_r != 0 || gpus > 1 || (task != "groundtruth" && task != "recall")))) {
         std::cout << "usage: -metric l2|ip (default l2); -metric ip serves -task groundtruth and -task recall [-rerank R] "
                      "[-filter FILE] [-opq], and cannot be combined with -refine R or -gpus above 1" << std::endl;
+        return 2;
+    }
+
+    if (!store.empty() && ((store != "f16" && store != "bf16") || task != "recall" || rerank == 0)) {
+        std::cout << "usage: -store f16|bf16 serves -task recall with -rerank R (also with -metric ip): the re-rank is run a "
+                     "second time from the base narrowed to that format (dpq_flat_open_narrowed) and its recall printed beside "
+                     "the fp32 line" << std::endl;
         return 2;
     }
 
@@ -574,8 +583,9 @@ int main(int argc, char* argv[]) {
         // against base.{ext} (main.cpp:898-939) and reports the recall of that answer too.
         if (PQ_M <= 0 || PQ_K <= 0 || dataset.empty() || N < 1 || !topk_given || top_k < 1 || query_size < 1) {
             std::cout << "usage: deltapq -dataset DIR -task recall -m M -k K -N N -query_size Q -topk K [-gt_topk G] [-rerank R]"
-                         " [-ext fvecs|bvecs] [-filter FILE] [-opq] [-refine R [-m2 M2] [-k2 K2]] [-metric l2|ip]   (-refine: the level of"
-                         " -task refine, M <= 8; -metric ip: dpq_query_batch_ip against the .ip.txt truth, not with -refine)" << std::endl;
+                         " [-store f16|bf16] [-ext fvecs|bvecs] [-filter FILE] [-opq] [-refine R [-m2 M2] [-k2 K2]] [-metric l2|ip]   (-refine: the"
+                         " level of -task refine, M <= 8; -metric ip: dpq_query_batch_ip against the .ip.txt truth, not with -refine;"
+                         " -store: the re-rank once more from the base narrowed to fp16 / bf16)" << std::endl;
             return 2;
         }
         if (gt_topk < 0) gt_topk = top_k;
@@ -791,6 +801,26 @@ int main(int argc, char* argv[]) {
             if (rc) return die("dpq_recall", rc);
             snprintf(line, sizeof line, "reranked recall@%d = %.6f", top_k, rec);
             std::cout << line << std::endl;
+            if (!store.empty()) {  // the same re-rank from the base narrowed to 16 bits per value; the truth stays fp32
+                std::vector<float> base((size_t)N * D);
+                rc = dpq_read_vecs_range(base_path.c_str(), bvecs, 0, N, &Db, base.data());
+                if (rc) return die("ItrReader", rc);
+                const float* q32 = queries.data();  // fp32, a .bvecs file widened
+                rc = dpq_flat_open_narrowed(base.data(), N, D, store == "f16" ? DPQ_HALF_F16 : DPQ_HALF_BF16, 0, 0, &f);
+                if (rc) return die("dpq_flat_open_narrowed", rc);
+                rc = dpq_flat_set_id_map(f, vec_id.data(), N);
+                if (rc) return die("dpq_flat_set_id_map", rc);
+                const double t2 = Elapsed();
+                rc = ip ? dpq_flat_rerank_ip(f, q32, nq, pos.data(), R, top_k, r_ids.data(), r_d.data())
+                        : dpq_flat_rerank(f, q32, nq, pos.data(), R, top_k, r_ids.data(), r_d.data());
+                if (rc) return die(ip ? "dpq_flat_rerank_ip" : "dpq_flat_rerank", rc);
+                std::cout << "re-rank (" << store << " store) " << (Elapsed() - t2) / (double)nq * 1000 << " [msec/query] " << std::endl;
+                dpq_flat_close(f);
+                rc = dpq_recall(r_ids.data(), top_k, top_k, truth.data(), g_k, top_k, nq, &rec);
+                if (rc) return die("dpq_recall", rc);
+                snprintf(line, sizeof line, "reranked recall@%d (%s store) = %.6f", top_k, store.c_str(), rec);
+                std::cout << line << std::endl;
+            }
         }
         return 0;
     }

@@ -1,10 +1,12 @@
-// dpq_flat.h -- exact search over raw vectors on the GPU, by squared L2 or (fp32 only) by inner product: fp32
-// (dpq_flat.hip) and bytes on the int8 matrix cores (dpq_flat_u8.hip); top-k over a whole base or over the rows a filter lists, range search, re-ranking over a candidate
+// dpq_flat.h -- exact search over raw vectors on the GPU, by squared L2 or (not on bytes) by inner product: fp32
+// (dpq_flat.hip), fp16 / bf16 widened exactly to fp32 (dpq_flat_half.hip) and bytes on the int8 matrix cores
+// (dpq_flat_u8.hip); top-k over a whole base or over the rows a filter lists, range search, re-ranking over a candidate
 // list per query.  The arithmetic is the reference's brute force (main.cpp:150-156), restated in include/deltapq_amd.h
 // and DESIGN.md 5.10.  Each element type has one distance kernel template <LIST, MODE> in its own file; one stripe
-// driver (launch_flat_search) and one range pass (launch_flat_range_pass) serve both types, with and without a filter.
-// What the kernels of the two files share -- the modes, the key sink, the padding key -- is defined here, once.
-// The metric is a compile-time parameter of the fp32 kernels beside <LIST, MODE>; it reaches them through
+// driver (launch_flat_search) and one range pass (launch_flat_range_pass) serve every type, with and without a filter.
+// What the kernels of the three files share -- the modes, the key sink, the padding key, and for the fp32-query kernels
+// the step of the sum and the key -- is defined here, once.
+// The metric is a compile-time parameter of the fp32 and half kernels beside <LIST, MODE>; it reaches them through
 // FlatBase::metric and the metric argument of launch_flat_rerank, so the drivers stay one of each kind.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -27,6 +29,29 @@ __host__ __device__ inline uint32_t flat_ip_word(uint32_t u) {
     if (u == 0x80000000u) u = 0;
     return (u & 0x80000000u) ? u : (~u & 0x7fffffffu);
 }
+
+#ifdef __HIPCC__
+// The key of an fp32-query kernel: the accumulator rounded to fp32, its bits (kFlatIP: their key word) above the id.
+template <int METRIC>
+__device__ __forceinline__ uint64_t make_key(double acc, uint32_t id) {
+    const uint32_t u = __float_as_uint((float)acc);
+    return ((uint64_t)(METRIC == kFlatIP ? flat_ip_word(u) : u) << 32) | id;
+}
+
+// One dimension of one (vector, query) pair on the lane's fp64 accumulator.  L2: the difference and its square each
+// rounded in fp32, then widened.  Inner product: both values widened first, so the product is exact and the step is one
+// rounding, fused or not.
+template <int METRIC>
+__device__ __forceinline__ void accumulate(double& acc, float v, float q) {
+    if constexpr (METRIC == kFlatIP) {
+        acc = fma((double)v, (double)q, acc);
+    } else {
+        const float t = v - q;
+        const float s = t * t;
+        acc += (double)s;
+    }
+}
+#endif
 
 // Per-query selection state of a search.  overflow: an append fell outside the key buffer (the launcher's striping
 // rules that out; a set word is reported as an internal error instead of a wrong answer).
@@ -57,7 +82,9 @@ struct FlatBase {
     bool filtered;
     const uint32_t* list;
     int64_t n_entries;
-    int metric = kFlatL2;  // kFlatIP: fp32 only
+    int metric = kFlatL2;  // kFlatIP: fp32 and half only
+    const uint16_t* h16 = nullptr;  // a half base (dpq_flat_half.hip): 16-bit rows [n][Dp], Dp a multiple of 8; f32 and
+    int half_format = 0;            // i8 are then NULL.  kFlatF16 or kFlatBF16.  Its queries are fp32, padded to its Dp.
 };
 // Prepared queries of the base's kind: [nq][Dp] padded rows, with norms for bytes.
 struct FlatQueries {
@@ -103,10 +130,10 @@ size_t flat_rerank_keys(int n_cand);  // keys per query launch_flat_rerank needs
 // [rows][D] -> [rows][Dp] with zero padding, on the device.
 hipError_t launch_flat_pad_rows(const float* d_in, int64_t rows, int D, int Dp, float* d_out, hipStream_t stream);
 
-// The last stage of a search or a re-rank, for dpq_flat_u8.hip: sorts n_keys keys per query (d_state[q].count of them
+// The last stage of a search or a re-rank, for the other files: sorts n_keys keys per query (d_state[q].count of them
 // when d_state is given), drops repeats, writes top_k.
 hipError_t launch_flat_sort_emit(const uint64_t* d_keys, size_t stride, const FlatQueryState* d_state, int nq, int n_keys,
-                                 int top_k, int32_t* d_ids, float* d_dists, hipStream_t stream);
+                                 int top_k, int32_t* d_ids, float* d_dists, hipStream_t stream, int metric = kFlatL2);
 
 // ---- byte vectors on the int8 matrix cores (dpq_flat_u8.hip) -------------------------------------------------------
 // Rows are stored as x ^ 0x80 (int8), padded with int8 zeros to the K step of v_mfma_i32_32x32x32_i8, with an int32
@@ -126,6 +153,59 @@ hipError_t launch_flat_rerank_u8(const int8_t* d_base, int64_t n, int D, int Dp,
                                  const int32_t* d_cand, int n_cand, int top_k, int64_t id_offset, const uint32_t* d_map,
                                  int64_t n_map, uint64_t* d_keys, uint32_t* d_flag, int32_t* d_ids, float* d_dists,
                                  hipStream_t stream);
+
+// ---- half-precision vectors, fp16 and bf16 (dpq_flat_half.hip) -------------------------------------------------------
+// Rows are stored as they are given, 16 bits per value, padded with zeros to a multiple of eight values (16-byte loads).
+// The kernels widen a value to fp32, which is exact, and from there on are the fp32 kernels: an answer over a half base
+// is, bit for bit, the answer of the fp32 code over the widened rows.  Queries are fp32 throughout.
+enum { kFlatF16 = 1, kFlatBF16 = 2 };  // DPQ_HALF_F16, DPQ_HALF_BF16
+inline int flat_half_padded_d(int D) { return (D + 7) & ~7; }
+
+// fp32 bits -> 16 bits, round to nearest, ties to even, in integer arithmetic: the same bits on the host and on the
+// device, whatever the denormal mode.  fp16 underflows gradually and overflows to infinity from 65520 on; NaNs are out
+// of scope (they stay NaNs).
+__host__ __device__ inline uint16_t flat_half_narrow(uint32_t u, int format) {
+    if (format == kFlatBF16) return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+    const uint32_t sign = (u >> 16) & 0x8000u, a = u & 0x7fffffffu;
+    if (a > 0x7f800000u) return (uint16_t)(sign | 0x7e00u);
+    if (a >= 0x477ff000u) return (uint16_t)(sign | 0x7c00u);  // 65520 and above
+    if (a >= 0x38800000u) {                                   // 2^-14 and above: a normal half
+        const uint32_t r = a - 0x38000000u;
+        return (uint16_t)(sign | ((r + 0xfffu + ((r >> 13) & 1u)) >> 13));
+    }
+    if (a < 0x33000000u) return (uint16_t)sign;               // below 2^-25: zero
+    const uint32_t shift = 126u - (a >> 23), m = (a & 0x7fffffu) | 0x800000u;  // the half is m * 2^-shift, 14 <= shift <= 24
+    uint32_t h = m >> shift;
+    const uint32_t rem = m & ((1u << shift) - 1u), mid = 1u << (shift - 1);
+    if (rem > mid || (rem == mid && (h & 1u))) ++h;
+    return (uint16_t)(sign | h);
+}
+// 16 bits -> the bits of the fp32 value they stand for, exactly.
+__host__ __device__ inline uint32_t flat_half_widen(uint16_t h, int format) {
+    if (format == kFlatBF16) return (uint32_t)h << 16;
+    const uint32_t sign = (uint32_t)(h & 0x8000u) << 16, e = (h >> 10) & 31u;
+    uint32_t m = h & 0x3ffu;
+    if (e == 31u) return sign | 0x7f800000u | (m << 13);
+    if (e) return sign | ((e + 112u) << 23) | (m << 13);
+    if (!m) return sign;
+    uint32_t s = 0;
+    while (!(m & 0x400u)) m <<= 1, ++s;
+    return sign | ((113u - s) << 23) | ((m & 0x3ffu) << 13);
+}
+
+// 16-bit rows [rows][D] -> [rows][Dp] with zero padding; fp32 rows [rows][D] -> narrowed, padded 16-bit rows.
+hipError_t launch_flat_half_prepare(const uint16_t* d_in, int64_t rows, int D, int Dp, uint16_t* d_out, hipStream_t stream);
+hipError_t launch_flat_half_narrow(const float* d_in, int64_t rows, int D, int Dp, int format, uint16_t* d_out,
+                                   hipStream_t stream);
+// The distance stage of launch_flat_search / launch_flat_range_pass on a half base (b.h16, b.half_format, b.metric): one
+// launch of the half kernel's instantiation over entries e0 .. e0 + rows - 1.  keys / cap / offs: the mode's sink.
+hipError_t launch_flat_dist_half(int mode, const FlatBase& b, int64_t e0, int rows, const FlatQueries& q, uint64_t* keys,
+                                 int cap, const int64_t* offs, FlatQueryState* state, hipStream_t stream);
+// launch_flat_rerank over a half base; d_queries are the caller's fp32 [nq][D], unpadded.
+hipError_t launch_flat_rerank_half(int metric, int format, const uint16_t* d_base, int64_t n, int D, int Dp,
+                                   const float* d_queries, int nq, const int32_t* d_cand, int n_cand, int top_k,
+                                   int64_t id_offset, const uint32_t* d_map, int64_t n_map, uint64_t* d_keys, uint32_t* d_flag,
+                                   int32_t* d_ids, float* d_dists, hipStream_t stream);
 
 // ---- filters and range search (dpq_flat_filter.hip: the row list, the range state, the sort; no distance code) -----
 // A filter is the ascending list of a handle's eligible rows.  d_words [n_words]: bit b of word w = row 32 w + b.

@@ -30,8 +30,9 @@
 //                         a lane per candidate; a wavefront fetches its 64 rows with 16-byte loads into LDS, 32
 //                         dimensions at a time, and every lane then walks its own row in order.
 // launch_flat_search is the one stripe driver (state, then per stripe a select and a distance launch, then the last
-// select and the sort) and launch_flat_range_pass the one range pass, for both element types, with and without a list;
-// the byte kernel of dpq_flat_u8.hip comes in through launch_flat_dist_u8.
+// select and the sort) and launch_flat_range_pass the one range pass, for every element type, with and without a list;
+// the byte kernel of dpq_flat_u8.hip comes in through launch_flat_dist_u8, the half kernel of dpq_flat_half.hip through
+// launch_flat_dist_half.  make_key<METRIC> and accumulate<METRIC> live in dpq_flat.h, shared with the half kernels.
 #include "dpq_flat.h"
 
 #include <algorithm>
@@ -44,26 +45,6 @@ constexpr int TQ = 64, TV = 64;  // queries and vectors of a workgroup's tile
 constexpr int DC = 32;           // dimensions staged at a time
 constexpr int LD = TV + 4;       // LDS row stride in floats (16-byte aligned; spreads the transposed writes)
 constexpr int kSelThreads = 1024;
-
-template <int METRIC>
-__device__ __forceinline__ uint64_t make_key(double acc, uint32_t id) {
-    const uint32_t u = __float_as_uint((float)acc);
-    return ((uint64_t)(METRIC == kFlatIP ? flat_ip_word(u) : u) << 32) | id;
-}
-
-// One dimension of one (vector, query) pair on the lane's fp64 accumulator.  L2: the difference and its square each
-// rounded in fp32, then widened.  Inner product: both values widened first, so the product is exact and the step is one
-// rounding, fused or not.
-template <int METRIC>
-__device__ __forceinline__ void accumulate(double& acc, float v, float q) {
-    if constexpr (METRIC == kFlatIP) {
-        acc = fma((double)v, (double)q, acc);
-    } else {
-        const float t = v - q;
-        const float s = t * t;
-        acc += (double)s;
-    }
-}
 
 __global__ void flat_init_state_kernel(FlatQueryState* state, int nq) {
     const int q = blockIdx.x * blockDim.x + threadIdx.x;
@@ -424,6 +405,7 @@ void sort_emit(int metric, const uint64_t* d_keys, size_t stride, const FlatQuer
 hipError_t launch_flat_dist(int mode, const FlatBase& b, int64_t e0, int rows, const FlatQueries& q, uint64_t* keys, int cap,
                             const int64_t* offs, FlatQueryState* state, hipStream_t stream) {
     if (b.i8) return launch_flat_dist_u8(mode, b, e0, rows, q, keys, cap, offs, state, stream);
+    if (b.h16) return launch_flat_dist_half(mode, b, e0, rows, q, keys, cap, offs, state, stream);
     auto* launch = b.metric == kFlatIP ? pick_dist_fp32<kFlatIP>(b.filtered, mode) : pick_dist_fp32<kFlatL2>(b.filtered, mode);
     launch(b, e0, rows, q, keys, cap, offs, state, stream);
     return hipGetLastError();
@@ -482,11 +464,11 @@ hipError_t launch_flat_rerank(int metric, const float* d_base, int64_t n, int D,
 }
 
 hipError_t launch_flat_sort_emit(const uint64_t* d_keys, size_t stride, const FlatQueryState* d_state, int nq, int n_keys,
-                                 int top_k, int32_t* d_ids, float* d_dists, hipStream_t stream) {
+                                 int top_k, int32_t* d_ids, float* d_dists, hipStream_t stream, int metric) {
     hipError_t e = ensure_sort_lds();
     if (e != hipSuccess) return e;
     const int n_pad = pow2_at_least(n_keys);
-    sort_emit(kFlatL2, d_keys, stride, d_state, nq, n_keys, n_pad, top_k, d_ids, d_dists, stream);
+    sort_emit(metric, d_keys, stride, d_state, nq, n_keys, n_pad, top_k, d_ids, d_dists, stream);
     return hipGetLastError();
 }
 

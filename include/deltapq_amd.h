@@ -49,6 +49,9 @@
  *   (none: FAISS's IndexFlatIP: search, an      dpq_flat_search_ip / dpq_flat_search_filtered_ip /
  *     IDSelector, range_search; re-ranking by     dpq_flat_range_search_ip / dpq_flat_rerank_ip[_device],
  *     inner product)                              dpq_merge_topk_ip_host
+ *   (none: FAISS's IndexScalarQuantizer fp16 /  dpq_flat_open_half / dpq_flat_open_narrowed, then every fp32-query
+ *     bf16 under IndexFlat's calls, and           dpq_flat_* call; dpq_half_from_float / dpq_half_to_float
+ *     IndexRefineFlat over it)
  *
  * Conventions: plain pointers and sizes only; the caller owns every host
  * buffer it passes, the library owns device memory.  Every function returns a
@@ -816,6 +819,45 @@ int dpq_flat_rerank_ip_device(dpq_flat* f, const float* d_queries, int nq, const
  * top_k < 1, nq < 0. */
 int dpq_merge_topk_ip_host(const int32_t* ids, const float* scores, int n_lists, int nq, int top_k, int32_t* out_ids,
                            float* out_scores);
+
+/* ---- exact search over half-precision vectors: fp16 and bf16 storage -------------
+ * Embeddings are stored as fp16 or bf16.  A half handle keeps such rows on the GPU as they are, 16 bits per value, at
+ * half the device memory, half the upload and half the bytes a re-rank gathers of an fp32 handle over the same rows.
+ * FAISS's IndexScalarQuantizer(QT_fp16 / QT_bf16) under IndexFlat's calls, and IndexRefineFlat over it.
+ * There are no new search calls.  Every fp32-query call above takes an fp32 handle or a half handle: dpq_flat_search,
+ * dpq_flat_search_ip, dpq_flat_search_filtered, dpq_flat_search_filtered_ip, dpq_flat_range_search,
+ * dpq_flat_range_search_ip, dpq_flat_rerank, dpq_flat_rerank_device, dpq_flat_rerank_ip, dpq_flat_rerank_ip_device,
+ * dpq_flat_filter_create, dpq_flat_filter_count, dpq_flat_set_id_map, dpq_flat_close.  Queries stay fp32 and are never
+ * narrowed.  A _u8 call on a half handle is DPQ_ERR_ARG with a message that names the fp32 function.
+ * The contract.  Widening fp16 or bf16 to fp32 is exact, so there is no tolerance: any call above on a half handle gives
+ * ids, float bits and lims equal, bit for bit, to the same call on a dpq_flat_open handle over dpq_half_to_float(vectors).
+ * The L2 rule (fp32 subtract, fp32 square, fp64 accumulate in ascending d), the inner-product rule (fp64 accumulate of
+ * exact products, -0.0 reported as +0.0), the key order and the padding rows, DPQ_ERR_TOPK, the id map with its
+ * even-n_map rule, the flag word of the device forms and the order of the argument checks all carry over unchanged.
+ * Narrowing (dpq_half_from_float on the host, dpq_flat_open_narrowed on the device: the same bits): round to nearest,
+ * ties to even.  bf16: with u the fp32 bits, (u + 0x7fff + ((u >> 16) & 1)) >> 16.  fp16: the IEEE conversion with
+ * gradual underflow -- 2^-24 gives 0x0001, 2^-25 gives 0x0000, 2^-25 * (1 + 2^-20) gives 0x0001, 65519.99 gives 0x7bff,
+ * 65520 gives 0x7c00.  -0.0 keeps its sign.  NaN inputs are out of scope.  A value that narrows to an infinity is stored
+ * as one; searches over it fall under the exact search's "non-finite: unspecified" clause.  Subnormal halves are kept,
+ * never flushed, when they are widened.  tests/_half_restatement.py restates both rules and the widening in numpy.
+ * Device memory: 2 * n * (D rounded up to a multiple of 8) bytes, plus the workspaces of an fp32 handle; while
+ * dpq_flat_open_narrowed runs (and dpq_flat_open_half with D not a multiple of 8), an upload buffer of at most 128 MB on
+ * top of that, freed before it returns. */
+#define DPQ_HALF_F16  1   /* IEEE binary16 */
+#define DPQ_HALF_BF16 2   /* bfloat16: the upper 16 bits of a binary32 */
+/* Host only, no device.  in[count] -> out[count]; count == 0 is DPQ_OK.  DPQ_ERR_ARG: a NULL pointer with count > 0,
+ * count < 0, format outside {DPQ_HALF_F16, DPQ_HALF_BF16}. */
+int dpq_half_from_float(const float* in, int64_t count, int format, uint16_t* out);
+int dpq_half_to_float(const uint16_t* in, int64_t count, int format, float* out);
+/* vectors[n][D], host memory, 16-bit values of `format`, uploaded as they are.  The arguments are checked as
+ * dpq_flat_open checks them, before any device call; format outside {1, 2} is DPQ_ERR_ARG; no visible device is
+ * DPQ_ERR_NO_DEVICE. */
+int dpq_flat_open_half(const uint16_t* vectors /* [n][D], host */, int64_t n, int D, int format, int device,
+                       int64_t id_offset, dpq_flat** out);
+/* The same handle from fp32 rows (an .fvecs base, or what dpq_read_vecs_range returns), narrowed on the GPU in upload
+ * slices of at most 128 MB: indistinguishable from dpq_flat_open_half over dpq_half_from_float of the same rows. */
+int dpq_flat_open_narrowed(const float* vectors /* [n][D], host */, int64_t n, int D, int format, int device,
+                           int64_t id_offset, dpq_flat** out);
 
 /* ---- residual re-ranking: a second PQ level refines a shortlist ---------------
  * Every answer of dpq_query_batch is a coarse PQ approximation, and dpq_flat_rerank needs the raw vectors on the GPU

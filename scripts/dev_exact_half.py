@@ -1,0 +1,143 @@
+#!/usr/bin/env python
+"""Measurements of the exact search over fp16 / bf16 vectors beside the fp32 handle, in one run, on
+the bench-shaped vectors; prints one JSON line and writes it to `--out`.
+
+  open     the three ways to a handle: dpq_flat_open (fp32), dpq_flat_open_half (16-bit rows as they are) and
+           dpq_flat_open_narrowed (fp32 rows narrowed on the GPU), the latter two for both formats; the device bytes of
+           each handle's rows
+  search   exact top-`--topk` of `--nq` queries over all `--n` vectors by L2 and by inner product on the fp32, the f16 and
+           the bf16 handle; whether each half answer equals the fp32 handle's over the widened rows, bit for bit; and, on
+           the vectors times `--scale` (no longer exact in 16 bits), recall@topk of the half handles' searches against
+           the fp32 handle's
+  rerank   the index of DESIGN.md 5.14 (synth.kmeans_codebook, six rounds), its PQ top-`--rerank` by L2 and by inner
+           product, the exact re-rank of those answers to top-`--topk` on device tensors on each of the three handles, and
+           recall@topk of every re-ranked answer against the fp32 handle's exact search
+Every timing is `--reps` calls after a warm-up call, median and min - max on the host clock around the call.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from deltapq_amd import api, synth  # noqa: E402
+
+
+def spread(vals):
+    return dict(median=statistics.median(vals), min=min(vals), max=max(vals))
+
+
+def timed(fn, reps):
+    fn()  # warm-up: workspaces, code objects
+    ms = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        out = fn()
+        ms.append((time.perf_counter() - t0) * 1e3)
+    return out, ms
+
+
+def same(a, b):
+    return bool(np.array_equal(a[0], b[0]) and np.array_equal(a[1].view(np.uint32), b[1].view(np.uint32)))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=1_000_000)
+    ap.add_argument("--dim", type=int, default=128)
+    ap.add_argument("--nq", type=int, default=1000)
+    ap.add_argument("--topk", type=int, default=100)
+    ap.add_argument("--rerank", type=int, default=1000)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--scale", type=float, default=0.37)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "exact_half_line.json"))
+    args = ap.parse_args()
+    if api.device_count() < 1:
+        raise SystemExit("needs a GPU: there is no CPU path to time")
+    import torch
+    base = synth.make_clustered_vectors(args.n, args.dim, seed=100, n_clusters=20000, spread=12.0, centre_seed=7)
+    qs = synth.make_clustered_vectors(args.nq, args.dim, seed=1, n_clusters=20000, spread=12.0, centre_seed=7)
+    out = dict(n=args.n, dim=args.dim, nq=args.nq, top_k=args.topk, rerank=args.rerank, reps=args.reps)
+    stored = {fmt: api.half_from_float(base, fmt) for fmt in ("f16", "bf16")}
+
+    def opened(make):
+        make().close()
+        ms = []
+        for _ in range(args.reps):
+            t0 = time.perf_counter()
+            h = make()
+            ms.append((time.perf_counter() - t0) * 1e3)
+            h.close()
+        return spread(ms)
+    out["open_fp32_ms"] = opened(lambda: api.FlatIndex(base))
+    for fmt in ("f16", "bf16"):
+        out["open_half_%s_ms" % fmt] = opened(lambda: api.FlatIndexHalf(stored[fmt], fmt))
+        out["open_narrowed_%s_ms" % fmt] = opened(lambda: api.FlatIndexHalf(base, fmt))
+    out["device_bytes"] = dict(fp32=4 * args.n * ((args.dim + 3) // 4 * 4), half=2 * args.n * ((args.dim + 7) // 8 * 8))
+
+    handles = {"fp32": api.FlatIndex(base), "f16": api.FlatIndexHalf(base, "f16"), "bf16": api.FlatIndexHalf(base, "bf16")}
+    wide = {fmt: api.FlatIndex(api.half_to_float(stored[fmt], fmt)) for fmt in ("f16", "bf16")}
+    truth = {}
+    for name, h in handles.items():
+        res_l2, ms = timed(lambda: h.search(qs, args.topk), args.reps)
+        out["search_l2_%s_call_ms" % name] = spread(ms)
+        res_ip, ms = timed(lambda: h.search_ip(qs, args.topk), args.reps)
+        out["search_ip_%s_call_ms" % name] = spread(ms)
+        if name == "fp32":
+            truth = {"l2": res_l2, "ip": res_ip}
+        else:
+            out["search_%s_equals_fp32_over_widened" % name] = same(res_l2, wide[name].search(qs, args.topk)) and \
+                same(res_ip, wide[name].search_ip(qs, args.topk))
+            out["search_l2_%s_recall_at_%d" % (name, args.topk)] = api.recall(res_l2[0], truth["l2"][0], k=args.topk, R=args.topk)
+            out["search_ip_%s_recall_at_%d" % (name, args.topk)] = api.recall(res_ip[0], truth["ip"][0], k=args.topk, R=args.topk)
+    for w in wide.values():
+        w.close()
+    # The bench vectors are integers below 256, which both formats hold exactly: the recalls above are 1 by construction.
+    # Scaled by `--scale` they are not, and the same searches show what the narrowing costs.
+    sb, sq = base * np.float32(args.scale), qs * np.float32(args.scale)
+    with api.FlatIndex(sb) as f:
+        s_truth = {"l2": f.search(sq, args.topk)[0], "ip": f.search_ip(sq, args.topk)[0]}
+    for fmt in ("f16", "bf16"):
+        out["scaled_values_changed_by_%s" % fmt] = float((api.half_to_float(api.half_from_float(sb, fmt), fmt) != sb).mean())
+        with api.FlatIndexHalf(sb, fmt) as h:
+            out["scaled_search_l2_%s_recall_at_%d" % (fmt, args.topk)] = api.recall(h.search(sq, args.topk)[0], s_truth["l2"],
+                                                                                    k=args.topk, R=args.topk)
+            out["scaled_search_ip_%s_recall_at_%d" % (fmt, args.topk)] = api.recall(h.search_ip(sq, args.topk)[0], s_truth["ip"],
+                                                                                    k=args.topk, R=args.topk)
+    del sb
+
+    cb = synth.kmeans_codebook(base, 8, 256, iters=6, seed=102)
+    codes = api.encode_pq(base, cb, device=0)
+    tree = api.DeltaTree(codes, codebook=cb, device=0)
+    with api.DeltaPQIndex.open_memory(tree.payload(), args.n, 8, 256, device=0) as idx:
+        idx.set_codebook(cb)
+        pos = {"l2": idx.query_batch(qs, args.rerank)[0], "ip": idx.query_batch_ip(qs, args.rerank)[0]}
+    d_q = torch.from_numpy(qs).cuda()
+    for name, h in handles.items():
+        h.set_id_map(tree.vec_id)
+        for metric, call in (("l2", h.rerank_torch), ("ip", h.rerank_ip_torch)):
+            d_c = torch.from_numpy(pos[metric]).cuda()
+
+            def on_device():
+                r = call(d_q, d_c, args.topk)
+                torch.cuda.synchronize()
+                return r
+            (ti, _), ms = timed(on_device, args.reps)
+            out["rerank_%s_%s_device_call_ms" % (metric, name)] = spread(ms)
+            out["reranked_%s_%s_recall_at_%d" % (metric, name, args.topk)] = api.recall(ti.cpu().numpy(), truth[metric][0],
+                                                                                        k=args.topk, R=args.topk)
+        h.close()
+    tree.close()
+    line = json.dumps(out)
+    print(line)
+    with open(args.out, "w") as f:
+        f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
