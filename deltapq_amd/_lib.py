@@ -188,6 +188,19 @@ SYMBOLS = [
     ("dpq_flat_rerank_ip", ctypes.c_int, [_VP, _VP, ctypes.c_int, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP]),
     ("dpq_flat_rerank_ip_device", ctypes.c_int, [_VP, _VP, ctypes.c_int, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP]),
     ("dpq_merge_topk_ip_host", ctypes.c_int, [_VP, _VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, _VP, _VP]),
+    ("dpq_flat_open_i8", ctypes.c_int, [_VP, c_i64, ctypes.c_int, ctypes.c_int, c_i64, P(_VP)]),
+] + [
+    # the byte forms of the inner-product calls (u8 handles) and every call of an i8 handle: the argument lists of the
+    # fp32 call of the same shape
+    ("dpq_flat_%s%s%s" % (shape, suffix, tail), ctypes.c_int, args)
+    for suffix in ("_ip_u8", "_i8", "_ip_i8")
+    for shape, tail, args in (
+        ("search", "", [_VP, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP]),
+        ("search_filtered", "", [_VP, _VP, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP]),
+        ("range_search", "", [_VP, _VP, _VP, ctypes.c_int, _VP, P(_VP)]),
+        ("rerank", "", [_VP, _VP, ctypes.c_int, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP]),
+        ("rerank", "_device", [_VP, _VP, ctypes.c_int, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP]))
+] + [
     ("dpq_half_from_float", ctypes.c_int, [_VP, c_i64, ctypes.c_int, _VP]),
     ("dpq_half_to_float", ctypes.c_int, [_VP, c_i64, ctypes.c_int, _VP]),
     ("dpq_flat_open_half", ctypes.c_int, [_VP, c_i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_i64, P(_VP)]),

@@ -1070,7 +1070,7 @@ class IdFilter:
 
 
 class FlatIdFilter:
-    """A filter of FlatIndex / FlatIndexU8 .search_filtered and .range_search (dpq_flat_filter): the set of reported ids
+    """A filter of FlatIndex / FlatIndexU8 / FlatIndexI8 .search_filtered and .range_search (dpq_flat_filter): the set of reported ids
     (row + id_offset) a search may return, compacted once on the index's device into a list of eligible rows.  The bitmap
     convention is IdFilter's; ids at or beyond n_bits are not allowed."""
 
@@ -1369,8 +1369,11 @@ class FlatIndexHalf(FlatIndex):
 
 class FlatIndexU8:
     """Byte vectors [n][D] on one GPU (dpq_flat_open_u8): FlatIndex's answers -- the same ids and the same distance bits as
-    on the bytes widened to fp32 -- from the int8 matrix cores, at a quarter of the device memory.  Takes uint8 arrays and
-    tensors only; anything else is a TypeError rather than a conversion."""
+    on the bytes widened to fp32 -- from the int8 matrix cores, at a quarter of the device memory.  The *_ip methods are
+    the same searches by exact inner product of the bytes (dpq_flat_*_ip_u8): FlatIndex's *_ip answers over the widened
+    rows.  Takes uint8 arrays and tensors only; anything else is a TypeError rather than a conversion."""
+
+    _dtype, _open, _l2, _ip = np.uint8, "dpq_flat_open_u8", "_u8", "_ip_u8"
 
     def __init__(self, vectors, device=0, id_offset=0):
         self._h = None
@@ -1380,13 +1383,13 @@ class FlatIndexU8:
         self._lib = _lib.load()
         self.n, self.D, self.id_offset = int(v.shape[0]), int(v.shape[1]), int(id_offset)
         h = ctypes.c_void_p()
-        check(self._lib.dpq_flat_open_u8(_np_ptr(v), self.n, self.D, device, id_offset, ctypes.byref(h)), "dpq_flat_open_u8")
+        check(getattr(self._lib, self._open)(_np_ptr(v), self.n, self.D, device, id_offset, ctypes.byref(h)), self._open)
         self._h = h
 
-    @staticmethod
-    def _bytes(a, what):
-        if not isinstance(a, np.ndarray) or a.dtype != np.uint8:
-            raise TypeError("%s must be a uint8 array (FlatIndex takes fp32)" % what)
+    @classmethod
+    def _bytes(cls, a, what):
+        if not isinstance(a, np.ndarray) or a.dtype != cls._dtype:
+            raise TypeError("%s must be a %s array (FlatIndex takes fp32)" % (what, np.dtype(cls._dtype).name))
         return np.ascontiguousarray(a)
 
     def _queries(self, queries):
@@ -1395,50 +1398,76 @@ class FlatIndexU8:
             raise ValueError("queries must be [nq][%d]" % self.D)
         return q
 
-    def search(self, queries, top_k):
-        """Exact top_k over all vectors -> ids int32 [nq][top_k], dists float32 [nq][top_k] by (distance, id)."""
+    def _search(self, name, queries, top_k):
         q = self._queries(queries)
         ids = np.empty((q.shape[0], top_k), dtype=np.int32)
         dists = np.empty((q.shape[0], top_k), dtype=np.float32)
-        check(self._lib.dpq_flat_search_u8(self._h, _np_ptr(q), q.shape[0], top_k, _np_ptr(ids), _np_ptr(dists)),
-              "dpq_flat_search_u8")
+        check(getattr(self._lib, name)(self._h, _np_ptr(q), q.shape[0], top_k, _np_ptr(ids), _np_ptr(dists)), name)
         return ids, dists
+
+    def search(self, queries, top_k):
+        """Exact top_k over all vectors -> ids int32 [nq][top_k], dists float32 [nq][top_k] by (distance, id)."""
+        return self._search("dpq_flat_search" + self._l2, queries, top_k)
+
+    def search_ip(self, queries, top_k):
+        """Exact top_k by inner product -> ids int32 [nq][top_k], scores float32 [nq][top_k] by (score descending, id)."""
+        return self._search("dpq_flat_search" + self._ip, queries, top_k)
+
+    def _search_filtered(self, name, queries, top_k, id_filter):
+        return _flat_search_filtered(self, getattr(self._lib, name), name, queries, top_k, id_filter)
 
     def search_filtered(self, queries, top_k, id_filter):
         """Exact top_k over the rows `id_filter` (a FlatIdFilter made on this index) allows; rows are padded with -1 / +inf
         where fewer than top_k rows are allowed (dpq_flat_search_filtered_u8)."""
-        return _flat_search_filtered(self, self._lib.dpq_flat_search_filtered_u8, "dpq_flat_search_filtered_u8", queries, top_k,
-                                     id_filter)
+        return self._search_filtered("dpq_flat_search_filtered" + self._l2, queries, top_k, id_filter)
+
+    def search_filtered_ip(self, queries, top_k, id_filter):
+        """search_ip over the rows `id_filter` allows; rows are padded with -1 / -inf."""
+        return self._search_filtered("dpq_flat_search_filtered" + self._ip, queries, top_k, id_filter)
+
+    def _range_search(self, name, queries, radius, id_filter):
+        return _flat_range_search(self, getattr(self._lib, name), name, queries, radius, id_filter)
 
     def range_search(self, queries, radius, id_filter=None):
         """Every (allowed) row with exact distance d < radius, strictly (dpq_flat_range_search_u8).  `radius` is a scalar or
         one value per query.  Returns (lims int64 [nq + 1], ids int32, dists float32) as DeltaPQIndex.range_search does;
         query i owns entries lims[i]:lims[i + 1], ascending by (distance, id)."""
-        return _flat_range_search(self, self._lib.dpq_flat_range_search_u8, "dpq_flat_range_search_u8", queries, radius,
-                                  id_filter)
+        return self._range_search("dpq_flat_range_search" + self._l2, queries, radius, id_filter)
+
+    def range_search_ip(self, queries, threshold, id_filter=None):
+        """Every (allowed) row with exact score s > threshold, strictly; lists by (score descending, id)."""
+        return self._range_search("dpq_flat_range_search" + self._ip, queries, threshold, id_filter)
 
     def set_id_map(self, vec_id):
         """DFS position -> row of this handle (DeltaTree.vec_id): rerank candidates are then DFS positions."""
         m = np.ascontiguousarray(vec_id, dtype=np.uint32)
         check(self._lib.dpq_flat_set_id_map(self._h, _np_ptr(m), m.size), "dpq_flat_set_id_map")
 
-    def rerank(self, queries, cand_ids, top_k):
-        """Exact distances of cand_ids[nq][n_cand] only (negative = padding), the best top_k of them."""
+    def _rerank(self, name, queries, cand_ids, top_k):
         q = self._queries(queries)
         c = np.ascontiguousarray(cand_ids, dtype=np.int32)
         if c.ndim != 2 or c.shape[0] != q.shape[0]:
             raise ValueError("cand_ids must be [nq][n_cand]")
         ids = np.empty((q.shape[0], top_k), dtype=np.int32)
         dists = np.empty((q.shape[0], top_k), dtype=np.float32)
-        check(self._lib.dpq_flat_rerank_u8(self._h, _np_ptr(q), q.shape[0], _np_ptr(c), c.shape[1], top_k, _np_ptr(ids),
-                                           _np_ptr(dists)), "dpq_flat_rerank_u8")
+        check(getattr(self._lib, name)(self._h, _np_ptr(q), q.shape[0], _np_ptr(c), c.shape[1], top_k, _np_ptr(ids),
+                                       _np_ptr(dists)), name)
         return ids, dists
 
-    def rerank_torch(self, queries, cand_ids, top_k, out_ids=None, out_dists=None):
-        """rerank on device tensors, on torch's current stream (dpq_flat_rerank_u8_device); complete on return."""
+    def rerank(self, queries, cand_ids, top_k):
+        """Exact distances of cand_ids[nq][n_cand] only (negative = padding), the best top_k of them."""
+        return self._rerank("dpq_flat_rerank" + self._l2, queries, cand_ids, top_k)
+
+    def rerank_ip(self, queries, cand_ids, top_k):
+        """Exact inner-product scores of cand_ids[nq][n_cand] only (negative = padding), the best top_k of them by (score
+        descending, id); rows are padded with -1 / -inf."""
+        return self._rerank("dpq_flat_rerank" + self._ip, queries, cand_ids, top_k)
+
+    def _rerank_torch(self, name, queries, cand_ids, top_k, out_ids, out_dists):
         import torch
-        if not isinstance(queries, torch.Tensor) or queries.dtype != torch.uint8:
-            raise TypeError("queries must be a uint8 tensor (FlatIndex takes fp32)")
+        want = getattr(torch, np.dtype(self._dtype).name)
+        if not isinstance(queries, torch.Tensor) or queries.dtype != want:
+            raise TypeError("queries must be a %s tensor (FlatIndex takes fp32)" % np.dtype(self._dtype).name)
         assert queries.is_cuda and queries.is_contiguous() and queries.shape[1] == self.D
         assert cand_ids.is_cuda and cand_ids.dtype == torch.int32 and cand_ids.is_contiguous()
         assert cand_ids.shape[0] == queries.shape[0]
@@ -1448,11 +1477,19 @@ class FlatIndexU8:
         if out_dists is None:
             out_dists = torch.empty((nq, top_k), dtype=torch.float32, device=queries.device)
         stream = torch.cuda.current_stream(queries.device).cuda_stream
-        check(self._lib.dpq_flat_rerank_u8_device(self._h, ctypes.c_void_p(queries.data_ptr()), nq,
-                                                  ctypes.c_void_p(cand_ids.data_ptr()), cand_ids.shape[1], top_k,
-                                                  ctypes.c_void_p(out_ids.data_ptr()), ctypes.c_void_p(out_dists.data_ptr()),
-                                                  ctypes.c_void_p(stream)), "dpq_flat_rerank_u8_device")
+        check(getattr(self._lib, name)(self._h, ctypes.c_void_p(queries.data_ptr()), nq,
+                                       ctypes.c_void_p(cand_ids.data_ptr()), cand_ids.shape[1], top_k,
+                                       ctypes.c_void_p(out_ids.data_ptr()), ctypes.c_void_p(out_dists.data_ptr()),
+                                       ctypes.c_void_p(stream)), name)
         return out_ids, out_dists
+
+    def rerank_torch(self, queries, cand_ids, top_k, out_ids=None, out_dists=None):
+        """rerank on device tensors, on torch's current stream (dpq_flat_rerank_u8_device); complete on return."""
+        return self._rerank_torch("dpq_flat_rerank%s_device" % self._l2, queries, cand_ids, top_k, out_ids, out_dists)
+
+    def rerank_ip_torch(self, queries, cand_ids, top_k, out_ids=None, out_scores=None):
+        """rerank_ip on device tensors, on torch's current stream; complete on return."""
+        return self._rerank_torch("dpq_flat_rerank%s_device" % self._ip, queries, cand_ids, top_k, out_ids, out_scores)
 
     def close(self):
         if self._h is not None:
@@ -1470,6 +1507,20 @@ class FlatIndexU8:
 
     def __exit__(self, *exc):
         self.close()
+
+
+class FlatIndexI8(FlatIndexU8):
+    """Signed byte vectors [n][D] on one GPU (dpq_flat_open_i8): int8 embeddings as they are, searched with int8 queries by
+    squared L2 or by inner product (dpq_flat_*_i8, dpq_flat_*_ip_i8) -- every method of FlatIndexU8, and bit for bit
+    FlatIndex's answers over the rows widened to fp32.  Takes C-contiguous int8 arrays and int8 tensors only."""
+
+    _dtype, _open, _l2, _ip = np.int8, "dpq_flat_open_i8", "_i8", "_ip_i8"
+
+    @classmethod
+    def _bytes(cls, a, what):
+        if not isinstance(a, np.ndarray) or a.dtype != np.int8 or not a.flags.c_contiguous:
+            raise TypeError("%s must be a C-contiguous int8 array (FlatIndexU8 takes uint8, FlatIndex fp32)" % what)
+        return a
 
 
 class RefineLevel:

@@ -5,6 +5,26 @@
 
 namespace {
 
+// The kind of handle a call with queries of type Q takes: float -- an fp32 or a half handle, uint8_t -- a handle of
+// dpq_flat_open_u8, int8_t -- a handle of dpq_flat_open_i8.
+template <class Q> constexpr int kind_of = kFlatKindF32;
+template <> constexpr int kind_of<uint8_t> = kFlatKindU8;
+template <> constexpr int kind_of<int8_t> = kFlatKindI8;
+
+// A search call's name: its shape ("dpq_flat_search", "dpq_flat_rerank", ...), its metric, the kind of handle it takes,
+// the device form.  The same pieces name the call of the same shape for any other kind of handle.
+struct FlatCall {
+    const char* stem;
+    int metric;
+    int kind;
+    bool device = false;
+    std::string name(int k) const {
+        return std::string(stem) + (metric == dpq::kFlatIP ? "_ip" : "") + (k == kFlatKindU8 ? "_u8" : k == kFlatKindI8 ? "_i8" : "") +
+               (device ? "_device" : "");
+    }
+    std::string name() const { return name(kind); }
+};
+
 // Candidates of dpq_flat_rerank*, all device pointers; ends with one flag word read back.
 template <class Q>
 int flat_rerank_on_device(const char* fn, int metric, dpq_flat* f, const Q* d_queries, int nq, const int32_t* d_cand,
@@ -18,8 +38,9 @@ int flat_rerank_on_device(const char* fn, int metric, dpq_flat* f, const Q* d_qu
     for (int q0 = 0; q0 < nq; q0 += per) {
         const int m = std::min(per, nq - q0);
         const uint32_t* map = f->h_map.empty() ? nullptr : f->map.get();
-        if constexpr (std::is_same<Q, uint8_t>::value)
-            DPQ_HIP(dpq::launch_flat_rerank_u8(f->base8, f->n, f->D, f->Dp, d_queries + (size_t)q0 * f->D, m,
+        if constexpr (kind_of<Q> != kFlatKindF32)
+            DPQ_HIP(dpq::launch_flat_rerank_u8(metric, kind_of<Q> == kFlatKindI8, f->base8, f->n, f->D, f->Dp,
+                                               reinterpret_cast<const uint8_t*>(d_queries) + (size_t)q0 * f->D, m,
                                                d_cand + (size_t)q0 * n_cand, n_cand, top_k, f->id_offset, map,
                                                (int64_t)f->h_map.size(), f->keys, f->flag, d_ids + (size_t)q0 * top_k,
                                                d_dists + (size_t)q0 * top_k, stream));
@@ -42,25 +63,29 @@ int flat_rerank_on_device(const char* fn, int metric, dpq_flat* f, const Q* d_qu
 }
 
 // A handle takes the calls of its own kind only: the fp32-query functions an fp32 or a half handle, the _u8 functions a
-// byte handle.  The _ip functions (other == NULL) have no byte counterpart.
-int flat_kind(const dpq_flat* f, bool u8, const char* fn, const char* other) {
-    if (f->u8 == u8) return DPQ_OK;
+// handle of dpq_flat_open_u8, the _i8 functions one of dpq_flat_open_i8.  The message names the call of the same shape
+// that the handle does take.
+int flat_kind(const dpq_flat* f, const FlatCall& c) {
+    if (f->kind == c.kind) return DPQ_OK;
+    const std::string fn = c.name(), right = c.name(f->kind);
     if (f->half)
-        return fail(DPQ_ERR_ARG, std::string(fn) + ": the handle holds half-precision vectors (dpq_flat_open_half, "
-                                                   "dpq_flat_open_narrowed), searched with fp32 queries; call " + other);
-    if (!other)
-        return fail(DPQ_ERR_ARG, std::string(fn) + ": the handle holds byte vectors (dpq_flat_open_u8), which have no "
-                                                   "inner-product search; open the vectors as fp32 with dpq_flat_open");
-    return fail(DPQ_ERR_ARG, std::string(fn) + (u8 ? ": the handle holds fp32 vectors (dpq_flat_open); call "
-                                                   : ": the handle holds byte vectors (dpq_flat_open_u8); call ") + other);
+        return fail(DPQ_ERR_ARG, fn + ": the handle holds half-precision vectors (dpq_flat_open_half, "
+                                      "dpq_flat_open_narrowed), searched with fp32 queries; call " + right);
+    if (f->kind == kFlatKindF32) return fail(DPQ_ERR_ARG, fn + ": the handle holds fp32 vectors (dpq_flat_open); call " + right);
+    if (f->kind == kFlatKindI8)
+        return fail(DPQ_ERR_ARG, fn + ": the handle holds signed byte vectors (dpq_flat_open_i8); call " + right);
+    if (c.kind == kFlatKindF32 && c.metric == dpq::kFlatIP)
+        return fail(DPQ_ERR_ARG, fn + ": the handle holds byte vectors (dpq_flat_open_u8), which have no inner-product search "
+                                      "with fp32 queries; call " + right);
+    return fail(DPQ_ERR_ARG, fn + ": the handle holds byte vectors (dpq_flat_open_u8); call " + right);
 }
 
-int flat_rerank_args(const char* fn, const char* other, const dpq_flat* f, bool u8, const void* queries, int nq,
-                     const void* cand, int n_cand, int top_k, const void* ids, const void* dists) {
-    if (!f || !queries || !cand || !ids || !dists || nq < 0) return fail(DPQ_ERR_ARG, std::string(fn) + ": NULL argument or nq < 0");
-    if (int rc = flat_kind(f, u8, fn, other)) return rc;
+int flat_rerank_args(const FlatCall& c, const dpq_flat* f, const void* queries, int nq, const void* cand, int n_cand,
+                     int top_k, const void* ids, const void* dists) {
+    if (!f || !queries || !cand || !ids || !dists || nq < 0) return fail(DPQ_ERR_ARG, c.name() + ": NULL argument or nq < 0");
+    if (int rc = flat_kind(f, c)) return rc;
     if (top_k < 1 || top_k > n_cand || n_cand > dpq::kFlatMaxTopK)
-        return fail(DPQ_ERR_ARG, std::string(fn) + ": needs 1 <= top_k <= n_cand <= 16384");
+        return fail(DPQ_ERR_ARG, c.name() + ": needs 1 <= top_k <= n_cand <= 16384");
     return DPQ_OK;
 }
 
@@ -123,6 +148,37 @@ int flat_open_16(const char* fn, const uint16_t* h16, const float* f32, int64_t 
     return DPQ_OK;
 }
 
+// dpq_flat_open_u8 and dpq_flat_open_i8 (vectors then holds int8 values): the rows go up in slices of at most 128 MB and
+// are padded, and biased when unsigned, on the device.
+int flat_open_bytes(const char* fn, int kind, const uint8_t* vectors, int64_t n, int D, int device, int64_t id_offset,
+                    dpq_flat** out) {
+    if (int rc = flat_open_args(fn, vectors, n, D, device, id_offset, out)) return rc;
+    std::unique_ptr<dpq_flat> f(new dpq_flat);
+    f->device = device;
+    f->n = n;
+    f->id_offset = id_offset;
+    f->D = D;
+    f->Dp = dpq::flat_u8_padded_d(D);
+    f->kind = kind;
+    int rc = f->base8.alloc((size_t)n * f->Dp);
+    if (!rc) rc = f->norm8.alloc((size_t)((n + 3) & ~(int64_t)3));
+    if (rc) return fail(rc, std::string(fn) + ": the vectors do not fit into device memory (" + dpq_last_error() + ")");
+    // the norm array's padding is read by the last stripe's 16-byte loads (and masked afterwards): keep it defined
+    DPQ_HIP(hipMemset(f->norm8.get() + ((n - 1) & ~(int64_t)3), 0, 4 * sizeof(int32_t)));
+    const int64_t tile = std::max<int64_t>(1, ((int64_t)128 << 20) / D);  // rows per upload (128 MB); biased on the device
+    DevBuf<uint8_t> tmp;
+    if ((rc = tmp.alloc((size_t)std::min(n, tile) * D))) return rc;
+    for (int64_t r0 = 0; r0 < n; r0 += tile) {
+        const int64_t m = std::min(tile, n - r0);
+        DPQ_HIP(hipMemcpy(tmp, vectors + (size_t)r0 * D, (size_t)m * D, hipMemcpyHostToDevice));
+        DPQ_HIP(dpq::launch_flat_u8_prepare(tmp, m, D, f->Dp, f->base8.get() + (size_t)r0 * f->Dp, f->norm8.get() + r0,
+                                            nullptr, kind == kFlatKindI8));
+        DPQ_HIP(hipDeviceSynchronize());
+    }
+    *out = f.release();
+    return DPQ_OK;
+}
+
 int grow_outputs(dpq_flat* f, size_t want) {
     if (f->out_n >= want) return DPQ_OK;
     f->out_n = 0;
@@ -132,13 +188,16 @@ int grow_outputs(dpq_flat* f, size_t want) {
     return rc;
 }
 
-// Uploads m queries as the distance kernels read them: fp32 rows padded to Dp, or bytes biased and padded with norms.
+// Uploads m queries as the distance kernels read them: fp32 rows padded to Dp, or bytes (biased, on a u8 handle) padded
+// with norms -- and, for the inner product on a u8 handle, with the queries' correction terms.
 template <class Q>
-int flat_stage_queries(dpq_flat* f, const Q* src, int m, std::vector<float>* padded) {
+int flat_stage_queries(dpq_flat* f, int metric, const Q* src, int m, std::vector<float>* padded) {
     const int D = f->D, Dp = f->Dp;
-    if constexpr (std::is_same<Q, uint8_t>::value) {
+    if constexpr (kind_of<Q> != kFlatKindF32) {
         DPQ_HIP(hipMemcpy(f->q_raw, src, (size_t)m * D, hipMemcpyHostToDevice));
-        DPQ_HIP(dpq::launch_flat_u8_prepare(f->q_raw, m, D, Dp, f->q8, f->qnorm, nullptr));
+        DPQ_HIP(dpq::launch_flat_u8_prepare(f->q_raw, m, D, Dp, f->q8, f->qnorm, nullptr, kind_of<Q> == kFlatKindI8));
+        if (kind_of<Q> == kFlatKindU8 && metric == dpq::kFlatIP)
+            DPQ_HIP(dpq::launch_flat_u8_sums(f->q8, m, Dp, 0, f->qsum, nullptr));
     } else {
         if (Dp != D) {
             padded->assign((size_t)m * Dp, 0.0f);
@@ -150,12 +209,26 @@ int flat_stage_queries(dpq_flat* f, const Q* src, int m, std::vector<float>* pad
     return DPQ_OK;
 }
 
+// The query buffers of a search or a range call.  The first inner-product call on a u8 handle also makes the rows'
+// correction terms, in one pass over the stored rows: 4 * n bytes, kept until dpq_flat_close.
 template <class Q>
-int flat_grow_queries(dpq_flat* f, size_t qb) {
-    if constexpr (std::is_same<Q, uint8_t>::value) {
+int flat_grow_queries(dpq_flat* f, int metric, size_t qb) {
+    if constexpr (kind_of<Q> != kFlatKindF32) {
         int rc = grow(f->q_raw, &f->q_raw_n, qb * f->D);
         if (!rc) rc = grow(f->q8, &f->q8_n, qb * f->Dp);
         if (!rc) rc = grow(f->qnorm, &f->qnorm_n, qb);
+        if (kind_of<Q> == kFlatKindU8 && metric == dpq::kFlatIP) {
+            if (!rc) rc = grow(f->qsum, &f->qsum_n, qb);
+            if (!rc && !f->rsum8.get()) {
+                DevBuf<int32_t> sums;
+                if ((rc = sums.alloc((size_t)((f->n + 3) & ~(int64_t)3)))) return rc;
+                // the padding is read by the last stripe's 16-byte loads (and masked afterwards): keep it defined
+                DPQ_HIP(hipMemset(sums.get() + ((f->n - 1) & ~(int64_t)3), 0, 4 * sizeof(int32_t)));
+                DPQ_HIP(dpq::launch_flat_u8_sums(f->base8, f->n, f->Dp, 16384 * f->D, sums, nullptr));
+                DPQ_HIP(hipDeviceSynchronize());
+                f->rsum8 = std::move(sums);
+            }
+        }
         return rc;
     } else {
         return grow(f->d_q, &f->q_n, qb * f->Dp);
@@ -166,17 +239,18 @@ int flat_grow_queries(dpq_flat* f, size_t qb) {
 // of dpq_flat.h take them.
 dpq::FlatBase flat_base(const dpq_flat* f, const dpq_flat_filter* ff, int metric) {
     return {f->base, f->base8, f->norm8, f->Dp, f->id_offset, ff != nullptr, ff ? ff->list.get() : nullptr,
-            ff ? ff->n_allowed : f->n, metric, f->base16, f->half};
+            ff ? ff->n_allowed : f->n, metric, f->base16, f->half, f->kind == kFlatKindI8, f->rsum8};
 }
 
 dpq::FlatQueries flat_queries(const dpq_flat* f, int a, int m) {
-    if (f->u8) return {nullptr, f->q8.get() + (size_t)a * f->Dp, f->qnorm.get() + a, m};
+    if (f->kind != kFlatKindF32)
+        return {nullptr, f->q8.get() + (size_t)a * f->Dp, f->qnorm.get() + a, m, f->qsum.get() ? f->qsum.get() + a : nullptr};
     return {f->d_q.get() + (size_t)a * f->Dp, nullptr, nullptr, m};
 }
 
 // What dpq_flat_search[_u8] and dpq_flat_search_filtered[_u8] share once their arguments are checked: the buffers, the
 // batches of staged queries, the copies down and the check of every query's state.  ff NULL: all rows, top_k <= n.
-// metric: dpq::kFlatL2, or dpq::kFlatIP (fp32 handles; dists then holds scores).
+// metric: dpq::kFlatL2, or dpq::kFlatIP (dists then holds scores).
 template <class Q>
 int flat_search_run(const std::string& who, int metric, dpq_flat* f, const dpq_flat_filter* ff, const Q* queries, int nq,
                     int top_k, int32_t* ids, float* dists) {
@@ -185,7 +259,7 @@ int flat_search_run(const std::string& who, int metric, dpq_flat* f, const dpq_f
     const int qb = std::min(nq, dpq::flat_query_batch(top_k));
     int rc = grow(f->keys, &f->keys_n, (size_t)qb * dpq::flat_key_capacity(top_k));
     if (!rc) rc = grow(f->state, &f->state_n, (size_t)qb);
-    if (!rc) rc = flat_grow_queries<Q>(f, (size_t)qb);
+    if (!rc) rc = flat_grow_queries<Q>(f, metric, (size_t)qb);
     if (!rc) rc = grow_outputs(f, (size_t)qb * top_k);
     if (rc) return rc;
     const dpq::FlatBase base = flat_base(f, ff, metric);
@@ -194,7 +268,7 @@ int flat_search_run(const std::string& who, int metric, dpq_flat* f, const dpq_f
     std::vector<dpq::FlatQueryState> st((size_t)qb);
     for (int q0 = 0; q0 < nq; q0 += qb) {
         const int m = std::min(qb, nq - q0);
-        if ((rc = flat_stage_queries(f, queries + (size_t)q0 * f->D, m, &padded))) return rc;
+        if ((rc = flat_stage_queries(f, metric, queries + (size_t)q0 * f->D, m, &padded))) return rc;
         DPQ_HIP(dpq::launch_flat_search(base, flat_queries(f, 0, m), top_k, f->keys, f->state, f->d_ids, f->d_dists, nullptr));
         DPQ_HIP(hipMemcpy(ids + (size_t)q0 * top_k, f->d_ids, (size_t)m * top_k * sizeof(int32_t), hipMemcpyDeviceToHost));
         DPQ_HIP(hipMemcpy(dists + (size_t)q0 * top_k, f->d_dists, (size_t)m * top_k * sizeof(float), hipMemcpyDeviceToHost));
@@ -204,6 +278,17 @@ int flat_search_run(const std::string& who, int metric, dpq_flat* f, const dpq_f
                 return fail(DPQ_ERR_STATE, who + ": internal error: a key buffer overflowed");
     }
     return DPQ_OK;
+}
+
+// dpq_flat_search and its _ip / _u8 / _i8 forms: Q is the query type of the call's kind.
+template <class Q>
+int flat_search_call(const FlatCall& c, dpq_flat* f, const Q* queries, int nq, int top_k, int32_t* ids, float* dists) {
+    const std::string who = c.name();
+    if (!f || !queries || !ids || !dists || nq < 0) return fail(DPQ_ERR_ARG, who + ": NULL argument or nq < 0");
+    if (top_k < 1 || top_k > DPQ_FLAT_MAX_TOPK) return fail(DPQ_ERR_ARG, who + ": top_k outside 1..DPQ_FLAT_MAX_TOPK");
+    if (int rc = flat_kind(f, c)) return rc;
+    if (top_k > f->n) return fail(DPQ_ERR_TOPK, who + ": top_k exceeds the number of vectors");
+    return flat_search_run(who, c.metric, f, nullptr, queries, nq, top_k, ids, dists);
 }
 
 }  // namespace
@@ -240,32 +325,13 @@ int dpq_flat_open(const float* vectors, int64_t n, int D, int device, int64_t id
 }
 
 int dpq_flat_open_u8(const uint8_t* vectors, int64_t n, int D, int device, int64_t id_offset, dpq_flat** out) {
+    return guarded([&]() -> int { return flat_open_bytes("dpq_flat_open_u8", kFlatKindU8, vectors, n, D, device, id_offset, out); });
+}
+
+int dpq_flat_open_i8(const int8_t* vectors, int64_t n, int D, int device, int64_t id_offset, dpq_flat** out) {
     return guarded([&]() -> int {
-    if (int rc = flat_open_args("dpq_flat_open_u8", vectors, n, D, device, id_offset, out)) return rc;
-    std::unique_ptr<dpq_flat> f(new dpq_flat);
-    f->device = device;
-    f->n = n;
-    f->id_offset = id_offset;
-    f->D = D;
-    f->Dp = dpq::flat_u8_padded_d(D);
-    f->u8 = true;
-    int rc = f->base8.alloc((size_t)n * f->Dp);
-    if (!rc) rc = f->norm8.alloc((size_t)((n + 3) & ~(int64_t)3));
-    if (rc) return fail(rc, std::string("dpq_flat_open_u8: the vectors do not fit into device memory (") + dpq_last_error() + ")");
-    // the norm array's padding is read by the last stripe's 16-byte loads (and masked afterwards): keep it defined
-    DPQ_HIP(hipMemset(f->norm8.get() + ((n - 1) & ~(int64_t)3), 0, 4 * sizeof(int32_t)));
-    const int64_t tile = std::max<int64_t>(1, ((int64_t)128 << 20) / D);  // rows per upload (128 MB); biased on the device
-    DevBuf<uint8_t> tmp;
-    if ((rc = tmp.alloc((size_t)std::min(n, tile) * D))) return rc;
-    for (int64_t r0 = 0; r0 < n; r0 += tile) {
-        const int64_t m = std::min(tile, n - r0);
-        DPQ_HIP(hipMemcpy(tmp, vectors + (size_t)r0 * D, (size_t)m * D, hipMemcpyHostToDevice));
-        DPQ_HIP(dpq::launch_flat_u8_prepare(tmp, m, D, f->Dp, f->base8.get() + (size_t)r0 * f->Dp, f->norm8.get() + r0,
-                                            nullptr));
-        DPQ_HIP(hipDeviceSynchronize());
-    }
-    *out = f.release();
-    return DPQ_OK;
+    return flat_open_bytes("dpq_flat_open_i8", kFlatKindI8, reinterpret_cast<const uint8_t*>(vectors), n, D, device, id_offset,
+                           out);
     });
 }
 
@@ -315,33 +381,37 @@ int dpq_flat_close(dpq_flat* f) {
 
 int dpq_flat_search(dpq_flat* f, const float* queries, int nq, int top_k, int32_t* ids, float* dists) {
     return guarded([&]() -> int {
-    if (!f || !queries || !ids || !dists || nq < 0) return fail(DPQ_ERR_ARG, "dpq_flat_search: NULL argument or nq < 0");
-    if (top_k < 1 || top_k > DPQ_FLAT_MAX_TOPK) return fail(DPQ_ERR_ARG, "dpq_flat_search: top_k outside 1..DPQ_FLAT_MAX_TOPK");
-    if (int rc = flat_kind(f, false, "dpq_flat_search", "dpq_flat_search_u8")) return rc;
-    if (top_k > f->n) return fail(DPQ_ERR_TOPK, "dpq_flat_search: top_k exceeds the number of vectors");
-    return flat_search_run("dpq_flat_search", dpq::kFlatL2, f, nullptr, queries, nq, top_k, ids, dists);
+    return flat_search_call({"dpq_flat_search", dpq::kFlatL2, kFlatKindF32}, f, queries, nq, top_k, ids, dists);
     });
 }
 
 int dpq_flat_search_ip(dpq_flat* f, const float* queries, int nq, int top_k, int32_t* ids, float* scores) {
     return guarded([&]() -> int {
-    if (!f || !queries || !ids || !scores || nq < 0) return fail(DPQ_ERR_ARG, "dpq_flat_search_ip: NULL argument or nq < 0");
-    if (top_k < 1 || top_k > DPQ_FLAT_MAX_TOPK)
-        return fail(DPQ_ERR_ARG, "dpq_flat_search_ip: top_k outside 1..DPQ_FLAT_MAX_TOPK");
-    if (int rc = flat_kind(f, false, "dpq_flat_search_ip", nullptr)) return rc;
-    if (top_k > f->n) return fail(DPQ_ERR_TOPK, "dpq_flat_search_ip: top_k exceeds the number of vectors");
-    return flat_search_run("dpq_flat_search_ip", dpq::kFlatIP, f, nullptr, queries, nq, top_k, ids, scores);
+    return flat_search_call({"dpq_flat_search", dpq::kFlatIP, kFlatKindF32}, f, queries, nq, top_k, ids, scores);
     });
 }
 
 int dpq_flat_search_u8(dpq_flat* f, const uint8_t* queries, int nq, int top_k, int32_t* ids, float* dists) {
     return guarded([&]() -> int {
-    if (!f || !queries || !ids || !dists || nq < 0) return fail(DPQ_ERR_ARG, "dpq_flat_search_u8: NULL argument or nq < 0");
-    if (top_k < 1 || top_k > DPQ_FLAT_MAX_TOPK)
-        return fail(DPQ_ERR_ARG, "dpq_flat_search_u8: top_k outside 1..DPQ_FLAT_MAX_TOPK");
-    if (int rc = flat_kind(f, true, "dpq_flat_search_u8", "dpq_flat_search")) return rc;
-    if (top_k > f->n) return fail(DPQ_ERR_TOPK, "dpq_flat_search_u8: top_k exceeds the number of vectors");
-    return flat_search_run("dpq_flat_search_u8", dpq::kFlatL2, f, nullptr, queries, nq, top_k, ids, dists);
+    return flat_search_call({"dpq_flat_search", dpq::kFlatL2, kFlatKindU8}, f, queries, nq, top_k, ids, dists);
+    });
+}
+
+int dpq_flat_search_ip_u8(dpq_flat* f, const uint8_t* queries, int nq, int top_k, int32_t* ids, float* scores) {
+    return guarded([&]() -> int {
+    return flat_search_call({"dpq_flat_search", dpq::kFlatIP, kFlatKindU8}, f, queries, nq, top_k, ids, scores);
+    });
+}
+
+int dpq_flat_search_i8(dpq_flat* f, const int8_t* queries, int nq, int top_k, int32_t* ids, float* dists) {
+    return guarded([&]() -> int {
+    return flat_search_call({"dpq_flat_search", dpq::kFlatL2, kFlatKindI8}, f, queries, nq, top_k, ids, dists);
+    });
+}
+
+int dpq_flat_search_ip_i8(dpq_flat* f, const int8_t* queries, int nq, int top_k, int32_t* ids, float* scores) {
+    return guarded([&]() -> int {
+    return flat_search_call({"dpq_flat_search", dpq::kFlatIP, kFlatKindI8}, f, queries, nq, top_k, ids, scores);
     });
 }
 
@@ -398,19 +468,18 @@ int flat_filter_owner(const dpq_flat* f, const dpq_flat_filter* ff, const std::s
     return fail(DPQ_ERR_ARG, who + ": the filter was made for another handle");
 }
 
-// dpq_flat_search_filtered / _u8 / _ip: Q is float (an fp32 or a half handle) or uint8_t (a byte handle).
+// dpq_flat_search_filtered and its _ip / _u8 / _i8 forms: Q is the query type of the call's kind.
 template <class Q>
-int flat_search_filtered_call(const char* fn, const char* other, int metric, dpq_flat* f, const dpq_flat_filter* ff, const Q* queries,
-                              int nq, int top_k, int32_t* ids, float* dists) {
-    constexpr bool u8 = std::is_same<Q, uint8_t>::value;
-    const std::string who(fn);
+int flat_search_filtered_call(const FlatCall& c, dpq_flat* f, const dpq_flat_filter* ff, const Q* queries, int nq, int top_k,
+                              int32_t* ids, float* dists) {
+    const std::string who = c.name();
     if (!f || !ff || !queries || !ids || !dists || nq < 0)
         return fail(DPQ_ERR_ARG, who + ": NULL argument (the filter included) or nq < 0");
     if (top_k < 1 || top_k > DPQ_FLAT_MAX_TOPK) return fail(DPQ_ERR_ARG, who + ": top_k outside 1..DPQ_FLAT_MAX_TOPK");
     if (int rc = flat_device_present(who)) return rc;
-    if (int rc = flat_kind(f, u8, fn, other)) return rc;
+    if (int rc = flat_kind(f, c)) return rc;
     if (int rc = flat_filter_owner(f, ff, who)) return rc;
-    return flat_search_run(who, metric, f, ff, queries, nq, top_k, ids, dists);
+    return flat_search_run(who, c.metric, f, ff, queries, nq, top_k, ids, dists);
 }
 
 // One distance pass of a range search over queries [a, a + m) of the staged batch: counting (pool NULL) or emitting.
@@ -421,14 +490,15 @@ int flat_range_pass(dpq_flat* f, const dpq_flat_filter* ff, int metric, int a, i
     return DPQ_OK;
 }
 
-// dpq_flat_range_search / _u8 / _ip (radii are then score thresholds: a row is kept when its score is above).  Count, then emit: a pass over a batch of queries counts every list, the host lays the
-// lists out, and sub-batches of at most kFlatRangePoolKeys keys (or one longer list) are formed again into the pool,
+// dpq_flat_range_search and its _ip / _u8 / _i8 forms (_ip: radii are score thresholds, a row is kept when its score is
+// above).  Count, then emit: a pass over a batch of queries counts every list, the host lays the lists out, and
+// sub-batches of at most kFlatRangePoolKeys keys (or one longer list) are formed again into the pool,
 // sorted there and brought down.
 template <class Q>
-int flat_range_call(const char* fn, const char* other, int metric, dpq_flat* f, const dpq_flat_filter* ff, const Q* queries, int nq,
-                    const float* radii, dpq_range_result** out) {
-    constexpr bool u8 = std::is_same<Q, uint8_t>::value;
-    const std::string who(fn);
+int flat_range_call(const FlatCall& c, dpq_flat* f, const dpq_flat_filter* ff, const Q* queries, int nq, const float* radii,
+                    dpq_range_result** out) {
+    const int metric = c.metric;
+    const std::string who = c.name();
     if (!out) return fail(DPQ_ERR_ARG, who + ": out is NULL");
     *out = nullptr;
     if (!f || nq < 0 || (nq > 0 && (!queries || !radii))) return fail(DPQ_ERR_ARG, who + ": NULL argument or nq < 0");
@@ -437,7 +507,7 @@ int flat_range_call(const char* fn, const char* other, int metric, dpq_flat* f, 
             return fail(DPQ_ERR_ARG, who + (metric == dpq::kFlatIP ? ": threshold of query " : ": radius of query ") +
                                          std::to_string(q) + " is NaN");
     if (int rc = flat_device_present(who)) return rc;
-    if (int rc = flat_kind(f, u8, fn, other)) return rc;
+    if (int rc = flat_kind(f, c)) return rc;
     if (ff)
         if (int rc = flat_filter_owner(f, ff, who)) return rc;
     std::unique_ptr<dpq_range_result> res(new dpq_range_result());
@@ -450,7 +520,7 @@ int flat_range_call(const char* fn, const char* other, int metric, dpq_flat* f, 
     DPQ_HIP(hipSetDevice(f->device));
     const int qb = std::min(nq, kFlatRangeQueries);
     int rc = grow(f->state, &f->state_n, (size_t)qb);
-    if (!rc) rc = flat_grow_queries<Q>(f, (size_t)qb);
+    if (!rc) rc = flat_grow_queries<Q>(f, metric, (size_t)qb);
     if (!rc) rc = grow(f->r_thr, &f->r_thr_n, (size_t)qb);
     if (!rc) rc = grow(f->r_offs, &f->r_offs_n, (size_t)qb + 1);
     if (rc) return rc;
@@ -460,7 +530,7 @@ int flat_range_call(const char* fn, const char* other, int metric, dpq_flat* f, 
     std::vector<int64_t> offs;
     for (int q0 = 0; q0 < nq && !rc; q0 += qb) {
         const int m = std::min(qb, nq - q0);
-        if ((rc = flat_stage_queries(f, queries + (size_t)q0 * f->D, m, &padded))) break;
+        if ((rc = flat_stage_queries(f, metric, queries + (size_t)q0 * f->D, m, &padded))) break;
         for (int q = 0; q < m; ++q) {  // d < r on non-negative floats is bits(d) < bits(r); key 0 lets nothing pass
             const float r = radii[q0 + q];
             uint32_t bits = 0;
@@ -581,45 +651,84 @@ int dpq_flat_filter_count(const dpq_flat_filter* ff, int64_t* n_allowed) {
 int dpq_flat_search_filtered(dpq_flat* f, const dpq_flat_filter* ff, const float* queries, int nq, int top_k, int32_t* ids,
                              float* dists) {
     return guarded([&]() -> int {
-    return flat_search_filtered_call("dpq_flat_search_filtered", "dpq_flat_search_filtered_u8", dpq::kFlatL2, f, ff, queries, nq, top_k, ids,
-                                     dists);
+    return flat_search_filtered_call({"dpq_flat_search_filtered", dpq::kFlatL2, kFlatKindF32}, f, ff, queries, nq, top_k, ids, dists);
     });
 }
 
-int dpq_flat_search_filtered_u8(dpq_flat* f, const dpq_flat_filter* ff, const uint8_t* queries, int nq, int top_k,
-                                int32_t* ids, float* dists) {
+int dpq_flat_search_filtered_u8(dpq_flat* f, const dpq_flat_filter* ff, const uint8_t* queries, int nq, int top_k, int32_t* ids,
+                                float* dists) {
     return guarded([&]() -> int {
-    return flat_search_filtered_call("dpq_flat_search_filtered_u8", "dpq_flat_search_filtered", dpq::kFlatL2, f, ff, queries, nq, top_k, ids,
-                                     dists);
+    return flat_search_filtered_call({"dpq_flat_search_filtered", dpq::kFlatL2, kFlatKindU8}, f, ff, queries, nq, top_k, ids, dists);
     });
 }
 
-int dpq_flat_range_search(dpq_flat* f, const dpq_flat_filter* ff, const float* queries, int nq, const float* radii,
-                          dpq_range_result** out) {
+int dpq_flat_search_filtered_i8(dpq_flat* f, const dpq_flat_filter* ff, const int8_t* queries, int nq, int top_k, int32_t* ids,
+                                float* dists) {
     return guarded([&]() -> int {
-    return flat_range_call("dpq_flat_range_search", "dpq_flat_range_search_u8", dpq::kFlatL2, f, ff, queries, nq, radii, out);
-    });
-}
-
-int dpq_flat_range_search_u8(dpq_flat* f, const dpq_flat_filter* ff, const uint8_t* queries, int nq, const float* radii,
-                             dpq_range_result** out) {
-    return guarded([&]() -> int {
-    return flat_range_call("dpq_flat_range_search_u8", "dpq_flat_range_search", dpq::kFlatL2, f, ff, queries, nq, radii, out);
+    return flat_search_filtered_call({"dpq_flat_search_filtered", dpq::kFlatL2, kFlatKindI8}, f, ff, queries, nq, top_k, ids, dists);
     });
 }
 
 int dpq_flat_search_filtered_ip(dpq_flat* f, const dpq_flat_filter* ff, const float* queries, int nq, int top_k, int32_t* ids,
                                 float* scores) {
     return guarded([&]() -> int {
-    return flat_search_filtered_call("dpq_flat_search_filtered_ip", nullptr, dpq::kFlatIP, f, ff, queries, nq, top_k, ids,
-                                     scores);
+    return flat_search_filtered_call({"dpq_flat_search_filtered", dpq::kFlatIP, kFlatKindF32}, f, ff, queries, nq, top_k, ids, scores);
+    });
+}
+
+int dpq_flat_search_filtered_ip_u8(dpq_flat* f, const dpq_flat_filter* ff, const uint8_t* queries, int nq, int top_k, int32_t* ids,
+                                   float* scores) {
+    return guarded([&]() -> int {
+    return flat_search_filtered_call({"dpq_flat_search_filtered", dpq::kFlatIP, kFlatKindU8}, f, ff, queries, nq, top_k, ids, scores);
+    });
+}
+
+int dpq_flat_search_filtered_ip_i8(dpq_flat* f, const dpq_flat_filter* ff, const int8_t* queries, int nq, int top_k, int32_t* ids,
+                                   float* scores) {
+    return guarded([&]() -> int {
+    return flat_search_filtered_call({"dpq_flat_search_filtered", dpq::kFlatIP, kFlatKindI8}, f, ff, queries, nq, top_k, ids, scores);
+    });
+}
+
+int dpq_flat_range_search(dpq_flat* f, const dpq_flat_filter* ff, const float* queries, int nq, const float* radii,
+                          dpq_range_result** out) {
+    return guarded([&]() -> int {
+    return flat_range_call({"dpq_flat_range_search", dpq::kFlatL2, kFlatKindF32}, f, ff, queries, nq, radii, out);
+    });
+}
+
+int dpq_flat_range_search_u8(dpq_flat* f, const dpq_flat_filter* ff, const uint8_t* queries, int nq, const float* radii,
+                             dpq_range_result** out) {
+    return guarded([&]() -> int {
+    return flat_range_call({"dpq_flat_range_search", dpq::kFlatL2, kFlatKindU8}, f, ff, queries, nq, radii, out);
+    });
+}
+
+int dpq_flat_range_search_i8(dpq_flat* f, const dpq_flat_filter* ff, const int8_t* queries, int nq, const float* radii,
+                             dpq_range_result** out) {
+    return guarded([&]() -> int {
+    return flat_range_call({"dpq_flat_range_search", dpq::kFlatL2, kFlatKindI8}, f, ff, queries, nq, radii, out);
     });
 }
 
 int dpq_flat_range_search_ip(dpq_flat* f, const dpq_flat_filter* ff, const float* queries, int nq, const float* thresholds,
                              dpq_range_result** out) {
     return guarded([&]() -> int {
-    return flat_range_call("dpq_flat_range_search_ip", nullptr, dpq::kFlatIP, f, ff, queries, nq, thresholds, out);
+    return flat_range_call({"dpq_flat_range_search", dpq::kFlatIP, kFlatKindF32}, f, ff, queries, nq, thresholds, out);
+    });
+}
+
+int dpq_flat_range_search_ip_u8(dpq_flat* f, const dpq_flat_filter* ff, const uint8_t* queries, int nq, const float* thresholds,
+                                dpq_range_result** out) {
+    return guarded([&]() -> int {
+    return flat_range_call({"dpq_flat_range_search", dpq::kFlatIP, kFlatKindU8}, f, ff, queries, nq, thresholds, out);
+    });
+}
+
+int dpq_flat_range_search_ip_i8(dpq_flat* f, const dpq_flat_filter* ff, const int8_t* queries, int nq, const float* thresholds,
+                                dpq_range_result** out) {
+    return guarded([&]() -> int {
+    return flat_range_call({"dpq_flat_range_search", dpq::kFlatIP, kFlatKindI8}, f, ff, queries, nq, thresholds, out);
     });
 }
 
@@ -627,24 +736,26 @@ int dpq_flat_range_search_ip(dpq_flat* f, const dpq_flat_filter* ff, const float
 
 namespace {
 
-// dpq_flat_rerank_device / _u8_device / _ip_device: Q is float or uint8_t, the handle of the same kind.
+// dpq_flat_rerank_device and its _ip / _u8 / _i8 forms: Q is the query type of the call's kind.
 template <class Q>
-int flat_rerank_device_call(const char* fn, const char* other, int metric, dpq_flat* f, const Q* d_queries, int nq,
-                            const int32_t* d_cand_ids, int n_cand, int top_k, int32_t* d_ids, float* d_dists,
-                            void* hip_stream) {
-    int rc = flat_rerank_args(fn, other, f, std::is_same<Q, uint8_t>::value, d_queries, nq, d_cand_ids, n_cand, top_k, d_ids,
-                              d_dists);
+int flat_rerank_device_call(const FlatCall& c, dpq_flat* f, const Q* d_queries, int nq, const int32_t* d_cand_ids, int n_cand,
+                            int top_k, int32_t* d_ids, float* d_dists, void* hip_stream) {
+    int rc = flat_rerank_args(c, f, d_queries, nq, d_cand_ids, n_cand, top_k, d_ids, d_dists);
     if (rc || nq == 0) return rc;
     DPQ_HIP(hipSetDevice(f->device));
-    return flat_rerank_on_device(fn, metric, f, d_queries, nq, d_cand_ids, n_cand, top_k, d_ids, d_dists, (hipStream_t)hip_stream);
+    return flat_rerank_on_device(c.name().c_str(), c.metric, f, d_queries, nq, d_cand_ids, n_cand, top_k, d_ids, d_dists,
+                                 (hipStream_t)hip_stream);
 }
 
-// dpq_flat_rerank / _u8 / _ip: the candidates are checked on the host, then queries and candidates go up and the answer down.
+// dpq_flat_rerank and its _ip / _u8 / _i8 forms: the candidates are checked on the host, then queries and candidates go
+// up and the answer down.
 template <class Q>
-int flat_rerank_host_call(const char* fn, const char* other, int metric, dpq_flat* f, const Q* queries, int nq,
-                          const int32_t* cand_ids, int n_cand, int top_k, int32_t* ids, float* dists) {
-    constexpr bool u8 = std::is_same<Q, uint8_t>::value;
-    int rc = flat_rerank_args(fn, other, f, u8, queries, nq, cand_ids, n_cand, top_k, ids, dists);
+int flat_rerank_host_call(const FlatCall& c, dpq_flat* f, const Q* queries, int nq, const int32_t* cand_ids, int n_cand,
+                          int top_k, int32_t* ids, float* dists) {
+    constexpr bool bytes = kind_of<Q> != kFlatKindF32;
+    const std::string who = c.name();
+    const char* fn = who.c_str();
+    int rc = flat_rerank_args(c, f, queries, nq, cand_ids, n_cand, top_k, ids, dists);
     if (rc || nq == 0) return rc;
     const int64_t n_map = (int64_t)f->h_map.size();
     for (size_t i = 0; i < (size_t)nq * n_cand; ++i) {
@@ -659,9 +770,9 @@ int flat_rerank_host_call(const char* fn, const char* other, int metric, dpq_fla
     }
     DPQ_HIP(hipSetDevice(f->device));
     Q* d_q;
-    if constexpr (u8) {
+    if constexpr (bytes) {
         rc = grow(f->q_raw, &f->q_raw_n, (size_t)nq * f->D);
-        d_q = f->q_raw;
+        d_q = reinterpret_cast<Q*>(f->q_raw.get());
     } else {
         rc = grow(f->d_q, &f->q_n, (size_t)nq * f->D);
         d_q = f->d_q;
@@ -671,7 +782,7 @@ int flat_rerank_host_call(const char* fn, const char* other, int metric, dpq_fla
     if (rc) return rc;
     DPQ_HIP(hipMemcpy(d_q, queries, (size_t)nq * f->D * sizeof(Q), hipMemcpyHostToDevice));
     DPQ_HIP(hipMemcpy(f->d_cand, cand_ids, (size_t)nq * n_cand * sizeof(int32_t), hipMemcpyHostToDevice));
-    rc = flat_rerank_on_device(fn, metric, f, d_q, nq, f->d_cand, n_cand, top_k, f->d_ids, f->d_dists, nullptr);
+    rc = flat_rerank_on_device(fn, c.metric, f, d_q, nq, f->d_cand, n_cand, top_k, f->d_ids, f->d_dists, nullptr);
     if (rc) return rc;
     DPQ_HIP(hipMemcpy(ids, f->d_ids, (size_t)nq * top_k * sizeof(int32_t), hipMemcpyDeviceToHost));
     DPQ_HIP(hipMemcpy(dists, f->d_dists, (size_t)nq * top_k * sizeof(float), hipMemcpyDeviceToHost));
@@ -682,50 +793,93 @@ int flat_rerank_host_call(const char* fn, const char* other, int metric, dpq_fla
 
 extern "C" {
 
-int dpq_flat_rerank_device(dpq_flat* f, const float* d_queries, int nq, const int32_t* d_cand_ids, int n_cand, int top_k,
-                           int32_t* d_ids, float* d_dists, void* hip_stream) {
+int dpq_flat_rerank(dpq_flat* f, const float* queries, int nq, const int32_t* cand_ids, int n_cand, int top_k,
+                    int32_t* ids, float* dists) {
     return guarded([&]() -> int {
-    return flat_rerank_device_call("dpq_flat_rerank", "dpq_flat_rerank_u8_device", dpq::kFlatL2, f, d_queries, nq, d_cand_ids, n_cand,
-                                   top_k, d_ids, d_dists, hip_stream);
+    return flat_rerank_host_call({"dpq_flat_rerank", dpq::kFlatL2, kFlatKindF32}, f, queries, nq, cand_ids, n_cand, top_k, ids, dists);
     });
 }
 
-int dpq_flat_rerank(dpq_flat* f, const float* queries, int nq, const int32_t* cand_ids, int n_cand, int top_k, int32_t* ids,
-                    float* dists) {
+int dpq_flat_rerank_device(dpq_flat* f, const float* d_queries, int nq, const int32_t* d_cand_ids, int n_cand,
+                           int top_k, int32_t* d_ids, float* d_dists, void* hip_stream) {
     return guarded([&]() -> int {
-    return flat_rerank_host_call("dpq_flat_rerank", "dpq_flat_rerank_u8", dpq::kFlatL2, f, queries, nq, cand_ids, n_cand, top_k, ids, dists);
-    });
-}
-
-int dpq_flat_rerank_u8_device(dpq_flat* f, const uint8_t* d_queries, int nq, const int32_t* d_cand_ids, int n_cand,
-                              int top_k, int32_t* d_ids, float* d_dists, void* hip_stream) {
-    return guarded([&]() -> int {
-    return flat_rerank_device_call("dpq_flat_rerank_u8_device", "dpq_flat_rerank_device", dpq::kFlatL2, f, d_queries, nq, d_cand_ids,
-                                   n_cand, top_k, d_ids, d_dists, hip_stream);
+    return flat_rerank_device_call({"dpq_flat_rerank", dpq::kFlatL2, kFlatKindF32, true}, f, d_queries, nq, d_cand_ids, n_cand, top_k, d_ids,
+                                   d_dists, hip_stream);
     });
 }
 
 int dpq_flat_rerank_u8(dpq_flat* f, const uint8_t* queries, int nq, const int32_t* cand_ids, int n_cand, int top_k,
                        int32_t* ids, float* dists) {
     return guarded([&]() -> int {
-    return flat_rerank_host_call("dpq_flat_rerank_u8", "dpq_flat_rerank", dpq::kFlatL2, f, queries, nq, cand_ids, n_cand, top_k,
-                                 ids, dists);
+    return flat_rerank_host_call({"dpq_flat_rerank", dpq::kFlatL2, kFlatKindU8}, f, queries, nq, cand_ids, n_cand, top_k, ids, dists);
     });
 }
 
-int dpq_flat_rerank_ip(dpq_flat* f, const float* queries, int nq, const int32_t* cand_ids, int n_cand, int top_k, int32_t* ids,
-                       float* scores) {
+int dpq_flat_rerank_u8_device(dpq_flat* f, const uint8_t* d_queries, int nq, const int32_t* d_cand_ids, int n_cand,
+                              int top_k, int32_t* d_ids, float* d_dists, void* hip_stream) {
     return guarded([&]() -> int {
-    return flat_rerank_host_call("dpq_flat_rerank_ip", nullptr, dpq::kFlatIP, f, queries, nq, cand_ids, n_cand, top_k, ids,
-                                 scores);
+    return flat_rerank_device_call({"dpq_flat_rerank", dpq::kFlatL2, kFlatKindU8, true}, f, d_queries, nq, d_cand_ids, n_cand, top_k, d_ids,
+                                   d_dists, hip_stream);
     });
 }
 
-int dpq_flat_rerank_ip_device(dpq_flat* f, const float* d_queries, int nq, const int32_t* d_cand_ids, int n_cand, int top_k,
-                              int32_t* d_ids, float* d_scores, void* hip_stream) {
+int dpq_flat_rerank_i8(dpq_flat* f, const int8_t* queries, int nq, const int32_t* cand_ids, int n_cand, int top_k,
+                       int32_t* ids, float* dists) {
     return guarded([&]() -> int {
-    return flat_rerank_device_call("dpq_flat_rerank_ip_device", nullptr, dpq::kFlatIP, f, d_queries, nq, d_cand_ids, n_cand,
-                                   top_k, d_ids, d_scores, hip_stream);
+    return flat_rerank_host_call({"dpq_flat_rerank", dpq::kFlatL2, kFlatKindI8}, f, queries, nq, cand_ids, n_cand, top_k, ids, dists);
+    });
+}
+
+int dpq_flat_rerank_i8_device(dpq_flat* f, const int8_t* d_queries, int nq, const int32_t* d_cand_ids, int n_cand,
+                              int top_k, int32_t* d_ids, float* d_dists, void* hip_stream) {
+    return guarded([&]() -> int {
+    return flat_rerank_device_call({"dpq_flat_rerank", dpq::kFlatL2, kFlatKindI8, true}, f, d_queries, nq, d_cand_ids, n_cand, top_k, d_ids,
+                                   d_dists, hip_stream);
+    });
+}
+
+int dpq_flat_rerank_ip(dpq_flat* f, const float* queries, int nq, const int32_t* cand_ids, int n_cand, int top_k,
+                       int32_t* ids, float* scores) {
+    return guarded([&]() -> int {
+    return flat_rerank_host_call({"dpq_flat_rerank", dpq::kFlatIP, kFlatKindF32}, f, queries, nq, cand_ids, n_cand, top_k, ids, scores);
+    });
+}
+
+int dpq_flat_rerank_ip_device(dpq_flat* f, const float* d_queries, int nq, const int32_t* d_cand_ids, int n_cand,
+                              int top_k, int32_t* d_ids, float* d_scores, void* hip_stream) {
+    return guarded([&]() -> int {
+    return flat_rerank_device_call({"dpq_flat_rerank", dpq::kFlatIP, kFlatKindF32, true}, f, d_queries, nq, d_cand_ids, n_cand, top_k, d_ids,
+                                   d_scores, hip_stream);
+    });
+}
+
+int dpq_flat_rerank_ip_u8(dpq_flat* f, const uint8_t* queries, int nq, const int32_t* cand_ids, int n_cand, int top_k,
+                          int32_t* ids, float* scores) {
+    return guarded([&]() -> int {
+    return flat_rerank_host_call({"dpq_flat_rerank", dpq::kFlatIP, kFlatKindU8}, f, queries, nq, cand_ids, n_cand, top_k, ids, scores);
+    });
+}
+
+int dpq_flat_rerank_ip_u8_device(dpq_flat* f, const uint8_t* d_queries, int nq, const int32_t* d_cand_ids, int n_cand,
+                                 int top_k, int32_t* d_ids, float* d_scores, void* hip_stream) {
+    return guarded([&]() -> int {
+    return flat_rerank_device_call({"dpq_flat_rerank", dpq::kFlatIP, kFlatKindU8, true}, f, d_queries, nq, d_cand_ids, n_cand, top_k, d_ids,
+                                   d_scores, hip_stream);
+    });
+}
+
+int dpq_flat_rerank_ip_i8(dpq_flat* f, const int8_t* queries, int nq, const int32_t* cand_ids, int n_cand, int top_k,
+                          int32_t* ids, float* scores) {
+    return guarded([&]() -> int {
+    return flat_rerank_host_call({"dpq_flat_rerank", dpq::kFlatIP, kFlatKindI8}, f, queries, nq, cand_ids, n_cand, top_k, ids, scores);
+    });
+}
+
+int dpq_flat_rerank_ip_i8_device(dpq_flat* f, const int8_t* d_queries, int nq, const int32_t* d_cand_ids, int n_cand,
+                                 int top_k, int32_t* d_ids, float* d_scores, void* hip_stream) {
+    return guarded([&]() -> int {
+    return flat_rerank_device_call({"dpq_flat_rerank", dpq::kFlatIP, kFlatKindI8, true}, f, d_queries, nq, d_cand_ids, n_cand, top_k, d_ids,
+                                   d_scores, hip_stream);
     });
 }
 

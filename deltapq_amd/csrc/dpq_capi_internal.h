@@ -152,16 +152,20 @@ inline uint64_t next_flat_serial() {
 
 // Raw vectors resident on one GPU (exact search).  An fp32 handle (dpq_flat.hip) stores rows padded to Dp floats; a byte
 // handle (dpq_flat_u8.hip) stores them biased to int8 and padded to Dp bytes, with an int32 norm per row.
+enum { kFlatKindF32 = 0, kFlatKindU8 = 1, kFlatKindI8 = 2 };  // dpq_flat::kind; a half handle is kFlatKindF32 with `half` set
+
 struct dpq_flat {
     int device = 0;
     int64_t n = 0, id_offset = 0;
     int D = 0, Dp = 0;
-    bool u8 = false;              // opened by dpq_flat_open_u8
+    int kind = kFlatKindF32;      // what the open call stored: fp32 or half rows, bytes (dpq_flat_open_u8), int8 (_i8)
     int half = 0;                 // opened by dpq_flat_open_half / _narrowed: DPQ_HALF_F16 or DPQ_HALF_BF16
     DevBuf<float> base;           // [n][Dp]
     DevBuf<uint16_t> base16;      // [n][Dp] (half handle)
     DevBuf<int8_t> base8;         // [n][Dp] (byte handle)
     DevBuf<int32_t> norm8;        // [n rounded up to 4]
+    DevBuf<int32_t> rsum8;        // [n rounded up to 4] a u8 handle's row terms of the inner product: made by its first
+                                  // inner-product search or range call, kept until dpq_flat_close
     DevBuf<uint32_t> map;         // DFS position -> row (dpq_flat_set_id_map)
     std::vector<uint32_t> h_map;  // its host copy: dpq_flat_rerank checks candidates on the host
     // workspaces, grown on demand and kept until dpq_flat_close
@@ -170,10 +174,10 @@ struct dpq_flat {
     DevBuf<float> d_q, d_dists;
     DevBuf<int32_t> d_ids, d_cand;
     DevBuf<uint32_t> flag;
-    DevBuf<uint8_t> q_raw;        // a byte handle's queries as given, biased and padded into q8, their norms in qnorm
-    DevBuf<int8_t> q8;
-    DevBuf<int32_t> qnorm;
-    size_t keys_n = 0, state_n = 0, q_n = 0, out_n = 0, cand_n = 0, q_raw_n = 0, q8_n = 0, qnorm_n = 0;
+    DevBuf<uint8_t> q_raw;        // a byte handle's queries as given, biased (u8) and padded into q8, their norms in qnorm,
+    DevBuf<int8_t> q8;            // their terms of the inner product (u8) in qsum
+    DevBuf<int32_t> qnorm, qsum;
+    size_t keys_n = 0, state_n = 0, q_n = 0, out_n = 0, cand_n = 0, q_raw_n = 0, q8_n = 0, qnorm_n = 0, qsum_n = 0;
     // filtered and range search
     const uint64_t serial = next_flat_serial();  // what a dpq_flat_filter remembers of the handle it was made for
     DevBuf<uint64_t> r_thr, r_pool, r_sorted;    // radius keys of a query batch; the lists of a sub-batch, unsorted / sorted

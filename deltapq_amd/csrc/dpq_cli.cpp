@@ -370,14 +370,14 @@ int main(int argc, char* argv[]) {
     if (task == "groundtruth") {
         // The other binary's `pqtree -task groundtruth` (main.cpp:569-669): brute force over base.{ext}, streamed in
         // parts; every part is a dpq_flat handle with its own id offset, the partial lists meet in dpq_merge_topk_host.
-        // With -ext bvecs the bytes stay bytes (dpq_flat_open_u8 / dpq_flat_search_u8): the same bits, the same file.
+        // With -ext bvecs the bytes stay bytes (dpq_flat_open_u8 / dpq_flat_search[_ip]_u8): the same bits, the same file.
         if (dataset.empty() || !topk_given || top_k < 1 || query_size < 1) {
             std::cout << "usage: deltapq -dataset DIR -task groundtruth -topk K -query_size Q [-N N] [-ext fvecs|bvecs] [-filter FILE]"
                          " [-metric l2|ip]" << std::endl;
             return 2;
         }
-        // -metric ip: exact inner products (dpq_flat_search_ip); a .bvecs base is widened to fp32, there is no byte kernel
-        const bool file_bvecs = ext == "bvecs", bvecs = file_bvecs && !ip;
+        // -metric ip: exact inner products (dpq_flat_search_ip; over a .bvecs base dpq_flat_search_ip_u8, the bytes kept)
+        const bool file_bvecs = ext == "bvecs", bvecs = file_bvecs;
         const std::string q_path = dataset + "/query." + ext, base_path = dataset + "/base." + ext;
         int64_t nq_file = 0, n_file = 0;
         int32_t D = 0, Db = 0;
@@ -458,16 +458,23 @@ int main(int argc, char* argv[]) {
                 dpq_flat_filter* ff = nullptr;
                 rc = dpq_flat_filter_create(f, f_words.data(), f_bits, &ff);
                 if (rc) return die("dpq_flat_filter_create", rc);
-                rc = bvecs ? dpq_flat_search_filtered_u8(f, ff, queries8.data(), nq, kk, p_ids.data(), p_dists.data())
+                rc = bvecs ? (ip ? dpq_flat_search_filtered_ip_u8(f, ff, queries8.data(), nq, kk, p_ids.data(), p_dists.data())
+                                 : dpq_flat_search_filtered_u8(f, ff, queries8.data(), nq, kk, p_ids.data(), p_dists.data()))
                      : ip  ? dpq_flat_search_filtered_ip(f, ff, queries.data(), nq, kk, p_ids.data(), p_dists.data())
                            : dpq_flat_search_filtered(f, ff, queries.data(), nq, kk, p_ids.data(), p_dists.data());
-                if (rc) return die(bvecs ? "dpq_flat_search_filtered_u8" : ip ? "dpq_flat_search_filtered_ip" : "dpq_flat_search_filtered", rc);
+                if (rc)
+                    return die(bvecs ? (ip ? "dpq_flat_search_filtered_ip_u8" : "dpq_flat_search_filtered_u8")
+                               : ip  ? "dpq_flat_search_filtered_ip"
+                                     : "dpq_flat_search_filtered", rc);
                 dpq_flat_filter_free(ff);
             } else {
-                rc = bvecs ? dpq_flat_search_u8(f, queries8.data(), nq, kk, p_ids.data(), p_dists.data())
+                rc = bvecs ? (ip ? dpq_flat_search_ip_u8(f, queries8.data(), nq, kk, p_ids.data(), p_dists.data())
+                                 : dpq_flat_search_u8(f, queries8.data(), nq, kk, p_ids.data(), p_dists.data()))
                      : ip  ? dpq_flat_search_ip(f, queries.data(), nq, kk, p_ids.data(), p_dists.data())
                            : dpq_flat_search(f, queries.data(), nq, kk, p_ids.data(), p_dists.data());
-                if (rc) return die(bvecs ? "dpq_flat_search_u8" : ip ? "dpq_flat_search_ip" : "dpq_flat_search", rc);
+                if (rc)
+                    return die(bvecs ? (ip ? "dpq_flat_search_ip_u8" : "dpq_flat_search_u8") : ip ? "dpq_flat_search_ip" : "dpq_flat_search",
+                               rc);
             }
             dpq_flat_close(f);
             for (int q = 0; q < nq; ++q)
@@ -768,7 +775,7 @@ int main(int argc, char* argv[]) {
             if (rc) return die("ItrReader", rc);
             dpq_flat* f = nullptr;
             std::vector<uint8_t> queries8;
-            if (bvecs && !ip) {  // bytes stay bytes: a byte handle and the _u8 calls, the same bits
+            if (bvecs) {  // bytes stay bytes: a byte handle and the _u8 / _ip_u8 calls, the same bits
                 std::vector<uint8_t> base8((size_t)N * D);
                 queries8.resize((size_t)nq * D);
                 rc = dpq_read_bvecs_range(base_path.c_str(), 0, N, &Db, base8.data());
@@ -785,16 +792,18 @@ int main(int argc, char* argv[]) {
                 std::cout << "-rerank: base." << ext << " (" << N << " x " << D << ") does not fit into device memory" << std::endl;
                 return 1;
             }
-            if (rc) return die(bvecs && !ip ? "dpq_flat_open_u8" : "dpq_flat_open", rc);
+            if (rc) return die(bvecs ? "dpq_flat_open_u8" : "dpq_flat_open", rc);
             rc = dpq_flat_set_id_map(f, vec_id.data(), N);
             if (rc) return die("dpq_flat_set_id_map", rc);
             std::vector<int32_t> r_ids((size_t)nq * top_k);
             std::vector<float> r_d((size_t)nq * top_k);
             const double t1 = Elapsed();
-            rc = ip      ? dpq_flat_rerank_ip(f, queries.data(), nq, pos.data(), R, top_k, r_ids.data(), r_d.data())
-                 : bvecs ? dpq_flat_rerank_u8(f, queries8.data(), nq, pos.data(), R, top_k, r_ids.data(), r_d.data())
-                         : dpq_flat_rerank(f, queries.data(), nq, pos.data(), R, top_k, r_ids.data(), r_d.data());
-            if (rc) return die(ip ? "dpq_flat_rerank_ip" : bvecs ? "dpq_flat_rerank_u8" : "dpq_flat_rerank", rc);
+            rc = bvecs ? (ip ? dpq_flat_rerank_ip_u8(f, queries8.data(), nq, pos.data(), R, top_k, r_ids.data(), r_d.data())
+                             : dpq_flat_rerank_u8(f, queries8.data(), nq, pos.data(), R, top_k, r_ids.data(), r_d.data()))
+                 : ip  ? dpq_flat_rerank_ip(f, queries.data(), nq, pos.data(), R, top_k, r_ids.data(), r_d.data())
+                       : dpq_flat_rerank(f, queries.data(), nq, pos.data(), R, top_k, r_ids.data(), r_d.data());
+            if (rc)
+                return die(bvecs ? (ip ? "dpq_flat_rerank_ip_u8" : "dpq_flat_rerank_u8") : ip ? "dpq_flat_rerank_ip" : "dpq_flat_rerank", rc);
             std::cout << "re-rank " << (Elapsed() - t1) / (double)nq * 1000 << " [msec/query] " << std::endl;
             dpq_flat_close(f);
             rc = dpq_recall(r_ids.data(), top_k, top_k, truth.data(), g_k, top_k, nq, &rec);

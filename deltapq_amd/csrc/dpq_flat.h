@@ -1,13 +1,14 @@
-// dpq_flat.h -- exact search over raw vectors on the GPU, by squared L2 or (not on bytes) by inner product: fp32
-// (dpq_flat.hip), fp16 / bf16 widened exactly to fp32 (dpq_flat_half.hip) and bytes on the int8 matrix cores
+// dpq_flat.h -- exact search over raw vectors on the GPU, by squared L2 or by inner product: fp32 (dpq_flat.hip),
+// fp16 / bf16 widened exactly to fp32 (dpq_flat_half.hip) and bytes, unsigned or signed, on the int8 matrix cores
 // (dpq_flat_u8.hip); top-k over a whole base or over the rows a filter lists, range search, re-ranking over a candidate
 // list per query.  The arithmetic is the reference's brute force (main.cpp:150-156), restated in include/deltapq_amd.h
 // and DESIGN.md 5.10.  Each element type has one distance kernel template <LIST, MODE> in its own file; one stripe
 // driver (launch_flat_search) and one range pass (launch_flat_range_pass) serve every type, with and without a filter.
 // What the kernels of the three files share -- the modes, the key sink, the padding key, and for the fp32-query kernels
 // the step of the sum and the key -- is defined here, once.
-// The metric is a compile-time parameter of the fp32 and half kernels beside <LIST, MODE>; it reaches them through
-// FlatBase::metric and the metric argument of launch_flat_rerank, so the drivers stay one of each kind.
+// The metric is a compile-time parameter of every distance kernel beside <LIST, MODE>; it reaches them through
+// FlatBase::metric and the metric argument of launch_flat_rerank*, so the drivers stay one of each kind.  The byte
+// kernels take the signedness of the rows the same way (FlatBase::i8_signed).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -19,8 +20,8 @@ namespace dpq {
 constexpr int kFlatMaxTopK = 16384;  // DPQ_FLAT_MAX_TOPK, and the most candidates a re-rank takes per query
 constexpr int kFlatMaxD = 2048;
 
-// The metric of an fp32 kernel.  kFlatL2: the key's high word is the bits of the (non-negative) distance.  kFlatIP:
-// the score's bits mapped so that ascending keys are descending scores (flat_ip_word below); a byte base is L2 only.
+// The metric of a kernel.  kFlatL2: the key's high word is the bits of the (non-negative) distance.  kFlatIP: the
+// score's bits mapped so that ascending keys are descending scores (flat_ip_word below).
 enum { kFlatL2 = 0, kFlatIP = 1 };
 // Score bits <-> high word of an inner-product key; the map is its own inverse.  -0.0 is read as +0.0 first.  A
 // non-negative score u becomes ~u & 0x7fffffff (larger scores, smaller words), a negative one keeps its bits (sign set,
@@ -82,16 +83,20 @@ struct FlatBase {
     bool filtered;
     const uint32_t* list;
     int64_t n_entries;
-    int metric = kFlatL2;  // kFlatIP: fp32 and half only
+    int metric = kFlatL2;
     const uint16_t* h16 = nullptr;  // a half base (dpq_flat_half.hip): 16-bit rows [n][Dp], Dp a multiple of 8; f32 and
     int half_format = 0;            // i8 are then NULL.  kFlatF16 or kFlatBF16.  Its queries are fp32, padded to its Dp.
+    bool i8_signed = false;         // a byte base: the rows are the caller's int8 values, not bytes biased by 128
+    const int32_t* rsum = nullptr;  // an unsigned byte base under kFlatIP: the rows' correction terms, padded as norm is
 };
-// Prepared queries of the base's kind: [nq][Dp] padded rows, with norms for bytes.
+// Prepared queries of the base's kind: [nq][Dp] padded rows, with norms for bytes (and, for the inner product over an
+// unsigned byte base, the queries' correction terms).
 struct FlatQueries {
     const float* f32;
     const int8_t* i8;
     const int32_t* norm;
     int nq;
+    const int32_t* sum = nullptr;
 };
 
 // What a distance kernel does with a key (its MODE): at or below the query's threshold it is appended to the query's
@@ -136,23 +141,28 @@ hipError_t launch_flat_sort_emit(const uint64_t* d_keys, size_t stride, const Fl
                                  int top_k, int32_t* d_ids, float* d_dists, hipStream_t stream, int metric = kFlatL2);
 
 // ---- byte vectors on the int8 matrix cores (dpq_flat_u8.hip) -------------------------------------------------------
-// Rows are stored as x ^ 0x80 (int8), padded with int8 zeros to the K step of v_mfma_i32_32x32x32_i8, with an int32
-// norm per row; the norm array of a base is allocated rounded up to four rows (16-byte loads in the epilogue).
+// Unsigned rows (0..255) are stored as x ^ 0x80 (int8), signed rows (-128..127) as they are; both padded with int8 zeros
+// to the K step of v_mfma_i32_32x32x32_i8, with an int32 norm per row; the norm array of a base is allocated rounded up
+// to four rows (16-byte loads in the epilogue).  The inner product over unsigned rows adds a term per row and a term per
+// query to the int8 dot product (dpq_flat_u8.hip's header); the rows' terms are padded as the norms are.
 constexpr int kFlatU8KStep = 32;
 inline int flat_u8_padded_d(int D) { return (D + kFlatU8KStep - 1) & ~(kFlatU8KStep - 1); }
 
-// bytes [rows][D] -> biased int8 [rows][Dp] and norms [rows], on the device.
+// bytes [rows][D] -> int8 [rows][Dp] (biased unless is_signed: d_in then holds int8 values) and norms [rows], on the device.
 hipError_t launch_flat_u8_prepare(const uint8_t* d_in, int64_t rows, int D, int Dp, int8_t* d_out, int32_t* d_norms,
-                                  hipStream_t stream);
+                                  hipStream_t stream, bool is_signed = false);
+// d_sums[r] = 128 * (the sum of prepared row r) + add: the rows' terms with add = 16384 * D, the queries' with add = 0.
+hipError_t launch_flat_u8_sums(const int8_t* d_rows8, int64_t rows, int Dp, int add, int32_t* d_sums, hipStream_t stream);
 // The distance stage of launch_flat_search / launch_flat_range_pass on a byte base: one launch of the byte kernel's
-// (b.filtered, mode) instantiation over entries e0 .. e0 + rows - 1.  keys / cap / offs: the mode's sink, as above.
+// (b.filtered, mode, b.metric, b.i8_signed) instantiation over entries e0 .. e0 + rows - 1.  keys / cap / offs: the mode's
+// sink, as above.  kFlatIP on an unsigned base needs b.rsum and q.sum.
 hipError_t launch_flat_dist_u8(int mode, const FlatBase& b, int64_t e0, int rows, const FlatQueries& q, uint64_t* keys,
                                int cap, const int64_t* offs, FlatQueryState* state, hipStream_t stream);
-// launch_flat_rerank over a prepared base; d_queries are the caller's bytes [nq][D], unpadded.
-hipError_t launch_flat_rerank_u8(const int8_t* d_base, int64_t n, int D, int Dp, const uint8_t* d_queries, int nq,
-                                 const int32_t* d_cand, int n_cand, int top_k, int64_t id_offset, const uint32_t* d_map,
-                                 int64_t n_map, uint64_t* d_keys, uint32_t* d_flag, int32_t* d_ids, float* d_dists,
-                                 hipStream_t stream);
+// launch_flat_rerank over a prepared base; d_queries are the caller's bytes [nq][D] (int8 values when is_signed), unpadded.
+hipError_t launch_flat_rerank_u8(int metric, bool is_signed, const int8_t* d_base, int64_t n, int D, int Dp,
+                                 const uint8_t* d_queries, int nq, const int32_t* d_cand, int n_cand, int top_k,
+                                 int64_t id_offset, const uint32_t* d_map, int64_t n_map, uint64_t* d_keys, uint32_t* d_flag,
+                                 int32_t* d_ids, float* d_dists, hipStream_t stream);
 
 // ---- half-precision vectors, fp16 and bf16 (dpq_flat_half.hip) -------------------------------------------------------
 // Rows are stored as they are given, 16 bits per value, padded with zeros to a multiple of eight values (16-byte loads).

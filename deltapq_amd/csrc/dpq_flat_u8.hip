@@ -1,5 +1,5 @@
-// dpq_flat_u8.hip -- exact L2 distances between byte queries and byte base vectors on the int8 matrix cores of gfx950
-// (DESIGN.md 5.10.1).
+// dpq_flat_u8.hip -- exact L2 distances and inner products between byte queries and byte base vectors, unsigned
+// (0..255) or signed (-128..127), on the int8 matrix cores of gfx950.
 //
 // With v, q in {0..255}^D and D <= 2048 every intermediate of the fp32 path's arithmetic (dpq_flat.hip) is an exactly
 // representable integer: |t| <= 255, s <= 65025, acc <= 2048 * 65025 < 2^31.  The reported distance is therefore
@@ -10,17 +10,30 @@
 // to a multiple of 32 bytes, with the int32 norm |v'|^2 beside them.  Differences are unchanged by the bias:
 //     |v - q|^2 = |v'|^2 + |q'|^2 - 2 v'.q'      all in int32, |v'.q'| <= 2048 * 128^2 = 2^25.
 // An int8 zero adds nothing to a dot product or a norm, so padding is invisible.
+// A signed base (dpq_flat_open_i8) stores its rows as they are; its L2 is the same identity and the same kernel.
 //
-//   flat_u8_bias_rows_kernel   bytes [rows][D] -> biased int8 [rows][Dp], padded
+// Inner product (kFlatIP): the score is (float)(int32)S, its key word flat_ip_word of the bits.  Signed rows: S = v.q,
+// the int8 dot product itself, |S| <= 2048 * 128^2 = 2^25.  Unsigned rows, v = v' + 128 and q = q' + 128:
+//     S = v'.q' + rs[row] + qs[query],   rs = 128 sum v' + 16384 D (= 128 sum v, 0 .. 2048 * 32640 < 2^26),
+//                                        qs = 128 sum q'           (within +-2^25),
+// all in int32 (S <= 2048 * 65025 < 2^31).  The padding adds nothing to either sum.  The kernel takes rs / qs in the
+// place of the norms; flat_u8_sums_kernel makes them.
+//
+//   flat_u8_bias_rows_kernel<BIAS>
+//                              bytes [rows][D] -> int8 [rows][Dp], biased (unsigned data) or as they are, padded
 //   flat_u8_norms_kernel       a lane per row: its int32 norm
-//   flat_dist_u8_kernel<LIST, MODE>
+//   flat_u8_sums_kernel        a lane per row: 128 * the sum of its int8 values + a constant (rs, qs above)
+//   flat_dist_u8_kernel<LIST, MODE, METRIC, CORR>
 //                              the one byte distance kernel, for every search.  A workgroup takes 64 queries x 256
 //                              entries of a stripe, a wavefront 64 x 64 as 2 x 2 tiles of v_mfma_i32_32x32x32_i8 (A =
 //                              vectors, B = queries); a lane's operand of a K step is 16 contiguous bytes of one row,
 //                              loaded straight from global memory.  The epilogue forms the int32 distances and treats
 //                              the keys as flat_dist_kernel<LIST, MODE> does: the same row sources (LIST), the same
-//                              modes and threshold / counter protocol (dpq_flat.hip's header).
-//   flat_rerank_u8_kernel      a lane per candidate; a wavefront fetches its 64 rows with 16-byte loads into LDS, 128
+//                              modes and threshold / counter protocol (dpq_flat.hip's header).  kFlatIP: the epilogue
+//                              forms the scores instead, with (CORR, unsigned rows) or without (signed rows) the two
+//                              correction terms, and the keys' high words are flat_ip_word of their bits.
+//   flat_rerank_u8_kernel<METRIC, SIGNED>
+//                              a lane per candidate; a wavefront fetches its 64 rows with 16-byte loads into LDS, 128
 //                              bytes of a row at a time, and every lane then sums its own row in int32.
 // State, selection, the final sort and the stripe driver are dpq_flat.hip's; launch_flat_dist_u8 is the one way in.
 #include "dpq_flat.h"
@@ -40,11 +53,15 @@ constexpr int RC = 128;   // bytes of a row the re-rank stages at a time
 
 static_assert(KS == kFlatU8KStep, "rows are padded to the K step of the MFMA");
 
-__device__ __forceinline__ uint64_t make_key_i32(int dist, uint32_t id) {
-    return ((uint64_t)__float_as_uint(__int2float_rn(dist)) << 32) | id;
+// The high word of a key: the fp32 bits of the integer distance, or the key word of the integer score's.
+template <int METRIC>
+__device__ __forceinline__ uint32_t key_word_i32(int x) {
+    const uint32_t u = __float_as_uint(__int2float_rn(x));
+    return METRIC == kFlatIP ? flat_ip_word(u) : u;
 }
 
 // one thread per four output bytes (Dp is a multiple of four)
+template <bool BIAS>
 __global__ void flat_u8_bias_rows_kernel(const uint8_t* __restrict__ in, int64_t rows, int D, int Dp,
                                          int8_t* __restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -55,7 +72,7 @@ __global__ void flat_u8_bias_rows_kernel(const uint8_t* __restrict__ in, int64_t
     uint32_t w = 0;
 #pragma unroll
     for (int b = 0; b < 4; ++b)
-        if (d + b < D) w |= (uint32_t)(in[r * D + d + b] ^ 0x80u) << (8 * b);
+        if (d + b < D) w |= (uint32_t)(in[r * D + d + b] ^ (BIAS ? 0x80u : 0u)) << (8 * b);
     *reinterpret_cast<uint32_t*>(out + r * Dp + d) = w;
 }
 
@@ -80,6 +97,25 @@ __global__ void flat_u8_norms_kernel(const int8_t* __restrict__ rows8, int64_t r
     norms[r] = s;
 }
 
+__device__ __forceinline__ int sum4(uint32_t a) {
+    int s = 0;
+#pragma unroll
+    for (int b = 0; b < 4; ++b) s += (int)(int8_t)(a >> (8 * b));
+    return s;
+}
+
+// sums[r] = 128 * (the sum of row r's int8 values) + add: the correction terms of the unsigned inner product
+__global__ void flat_u8_sums_kernel(const int8_t* __restrict__ rows8, int64_t rows, int Dp, int add, int32_t* __restrict__ sums) {
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= rows) return;
+    int s = 0;
+    for (int d = 0; d < Dp; d += 16) {
+        const uint4 v = *reinterpret_cast<const uint4*>(rows8 + r * Dp + d);
+        s += sum4(v.x) + sum4(v.y) + sum4(v.z) + sum4(v.w);
+    }
+    sums[r] = 128 * s + add;
+}
+
 // grid (tiles of the stripe's `rows` entries, query tiles), 256 threads.  Wavefront w owns entries 64 w .. 64 w + 63 of
 // the workgroup's 256 and all 64 queries.  acc[i][j] is the 32 x 32 tile of the wavefront's entries 32 i .. x queries
 // 32 j ..: register e of lane l holds entry 32 i + (e & 3) + 8 (e >> 2) + 4 (l >> 5) against query 32 j + (l & 31)  (the
@@ -87,7 +123,9 @@ __global__ void flat_u8_norms_kernel(const int8_t* __restrict__ rows8, int64_t r
 // numbers in LDS, no barrier before the MFMA loop, the norms of four adjacent registers one 16-byte load), or row
 // list[l0 + e], staged once per tile in lrow, every norm fetched by its row number.  Every instantiation is the
 // straight-line kernel of its case; nothing is picked at run time.
-template <bool LIST, int MODE>
+// kFlatIP: vnorm / qnorm are the correction terms rs / qs of an unsigned base (CORR), or are not read at all (a signed
+// base); the MFMA loop is the same.  kFlatL2 has no CORR = false form.
+template <bool LIST, int MODE, int METRIC, bool CORR>
 __global__ __launch_bounds__(256) void flat_dist_u8_kernel(const int8_t* __restrict__ base, const int32_t* __restrict__ vnorm,
                                                            const uint32_t* __restrict__ list, int64_t l0, int rows, int Dp,
                                                            const int8_t* __restrict__ queries,
@@ -154,7 +192,9 @@ __global__ __launch_bounds__(256) void flat_dist_u8_kernel(const int8_t* __restr
     if constexpr (!LIST) __syncthreads();  // cnt and thr
 
     // dot products -> the fp32 bit patterns of the distances, in place.  A distance is a non-negative integer, so its
-    // bits order as unsigned integers and key <= thr is (bits, id) <= (thr >> 32, thr & 0xffffffff).
+    // bits order as unsigned integers and key <= thr is (bits, id) <= (thr >> 32, thr & 0xffffffff).  kFlatIP: the key
+    // words of the scores, which order as unsigned integers by construction.
+    static_assert(METRIC == kFlatIP || CORR, "the L2 epilogue always reads the norms");
     uint32_t thi[2], tlo[2];
     bool qok[2];
 #pragma unroll
@@ -163,7 +203,8 @@ __global__ __launch_bounds__(256) void flat_dist_u8_kernel(const int8_t* __restr
         qok[j] = q0 + ql < nq;
         thi[j] = (uint32_t)(thr[ql] >> 32);
         tlo[j] = (uint32_t)thr[ql];
-        const int qn = qok[j] ? qnorm[q0 + ql] : 0;
+        int qn = 0;
+        if constexpr (CORR) qn = qok[j] ? qnorm[q0 + ql] : 0;
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -172,12 +213,17 @@ __global__ __launch_bounds__(256) void flat_dist_u8_kernel(const int8_t* __restr
                 // Their norms: one 16-byte load where the rows are adjacent (vnorm is padded to four rows), else a load
                 // per row right before its conversion -- fetching the four first costs 4 % of a filtered search.
                 i32x4 vn = zero;
-                if constexpr (!LIST)
+                if constexpr (!LIST && CORR)
                     if (inside(vg)) vn = *reinterpret_cast<const i32x4*>(vnorm + l0 + vg);
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
-                    if constexpr (LIST) vn[c] = vnorm[row_of(vg + c)];
-                    acc[i][j][4 * g + c] = __float_as_int(__int2float_rn(vn[c] + qn - 2 * acc[i][j][4 * g + c]));
+                    if constexpr (LIST && CORR) vn[c] = vnorm[row_of(vg + c)];
+                    if constexpr (METRIC == kFlatL2)
+                        acc[i][j][4 * g + c] = __float_as_int(__int2float_rn(vn[c] + qn - 2 * acc[i][j][4 * g + c]));
+                    else if constexpr (CORR)
+                        acc[i][j][4 * g + c] = (int)key_word_i32<kFlatIP>(acc[i][j][4 * g + c] + vn[c] + qn);
+                    else
+                        acc[i][j][4 * g + c] = (int)key_word_i32<kFlatIP>(acc[i][j][4 * g + c]);
                 }
             }
     }
@@ -243,7 +289,33 @@ __device__ __forceinline__ int sq_diff4(uint32_t a, uint32_t b) {
     return s;
 }
 
-// grid (candidate groups of 256, queries), 256 threads: lane = candidate.  queries: the caller's bytes [nq][D].
+// kFlatIP over signed rows: the int8 products as they are.
+__device__ __forceinline__ int dot4(uint32_t a, uint32_t b) {
+    int s = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) s += (int)(int8_t)(a >> (8 * k)) * (int)(int8_t)(b >> (8 * k));
+    return s;
+}
+
+// kFlatIP over unsigned rows stored biased: (v' + 128)(q' + 128), the products of the bytes themselves.
+__device__ __forceinline__ int dot4_biased(uint32_t a, uint32_t b) {
+    int s = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) s += ((int)(int8_t)(a >> (8 * k)) + 128) * ((int)(int8_t)(b >> (8 * k)) + 128);
+    return s;
+}
+
+template <int METRIC, bool SIGNED>
+__device__ __forceinline__ int pair4(uint32_t a, uint32_t b) {
+    if constexpr (METRIC == kFlatL2) return sq_diff4(a, b);
+    else if constexpr (SIGNED) return dot4(a, b);
+    else return dot4_biased(a, b);
+}
+
+// grid (candidate groups of 256, queries), 256 threads: lane = candidate.  queries: the caller's bytes [nq][D], read as
+// int8 when SIGNED.  The query is staged as the rows are stored; its padding is an int8 zero, except for the unsigned
+// inner product, where a padded row byte stands for 128 and the query's padding must stand for 0: the int8 -128.
+template <int METRIC, bool SIGNED>
 __global__ __launch_bounds__(256) void flat_rerank_u8_kernel(const int8_t* __restrict__ base, int64_t n, int D, int Dp,
                                                              const uint8_t* __restrict__ queries,
                                                              const int32_t* __restrict__ cand, int n_cand, int n_pad,
@@ -252,7 +324,9 @@ __global__ __launch_bounds__(256) void flat_rerank_u8_kernel(const int8_t* __res
     __shared__ __align__(16) int8_t qv[kFlatMaxD];
     __shared__ __align__(16) int8_t tile[4][64][RC + 16];
     const int q = blockIdx.y, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    for (int d = tid; d < Dp; d += 256) qv[d] = d < D ? (int8_t)(queries[(size_t)q * D + d] ^ 0x80u) : (int8_t)0;
+    constexpr uint32_t flip = SIGNED ? 0u : 0x80u;
+    constexpr int8_t qpad = (METRIC == kFlatIP && !SIGNED) ? (int8_t)-128 : (int8_t)0;
+    for (int d = tid; d < Dp; d += 256) qv[d] = d < D ? (int8_t)(queries[(size_t)q * D + d] ^ flip) : qpad;
     const int ci = blockIdx.x * 256 + tid;
     int row = -1;
     if (ci < n_cand) {
@@ -286,61 +360,83 @@ __global__ __launch_bounds__(256) void flat_rerank_u8_kernel(const int8_t* __res
         for (int d = 0; d < dc; d += 16) {
             const uint4 v = *reinterpret_cast<const uint4*>(&tile[w][lane][d]);
             const uint4 u = *reinterpret_cast<const uint4*>(&qv[d0 + d]);
-            acc += sq_diff4(v.x, u.x) + sq_diff4(v.y, u.y) + sq_diff4(v.z, u.z) + sq_diff4(v.w, u.w);
+            acc += pair4<METRIC, SIGNED>(v.x, u.x) + pair4<METRIC, SIGNED>(v.y, u.y) + pair4<METRIC, SIGNED>(v.z, u.z) +
+                   pair4<METRIC, SIGNED>(v.w, u.w);
         }
         __syncthreads();
     }
     if (ci < n_pad)
-        keys[(size_t)q * n_pad + ci] = row >= 0 ? make_key_i32(acc, (uint32_t)((int64_t)row + id_offset)) : kFlatNoKey;
+        keys[(size_t)q * n_pad + ci] =
+            row >= 0 ? ((uint64_t)key_word_i32<METRIC>(acc) << 32) | (uint32_t)((int64_t)row + id_offset) : kFlatNoKey;
 }
 
 }  // namespace
 
 hipError_t launch_flat_u8_prepare(const uint8_t* d_in, int64_t rows, int D, int Dp, int8_t* d_out, int32_t* d_norms,
-                                  hipStream_t stream) {
+                                  hipStream_t stream, bool is_signed) {
     if (rows <= 0) return hipSuccess;
     const int64_t words = rows * (Dp >> 2);
-    flat_u8_bias_rows_kernel<<<dim3((unsigned)((words + 255) / 256)), dim3(256), 0, stream>>>(d_in, rows, D, Dp, d_out);
+    auto* pad = is_signed ? flat_u8_bias_rows_kernel<false> : flat_u8_bias_rows_kernel<true>;
+    pad<<<dim3((unsigned)((words + 255) / 256)), dim3(256), 0, stream>>>(d_in, rows, D, Dp, d_out);
     flat_u8_norms_kernel<<<dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, stream>>>(d_out, rows, Dp, d_norms);
+    return hipGetLastError();
+}
+
+hipError_t launch_flat_u8_sums(const int8_t* d_rows8, int64_t rows, int Dp, int add, int32_t* d_sums, hipStream_t stream) {
+    if (rows <= 0) return hipSuccess;
+    flat_u8_sums_kernel<<<dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, stream>>>(d_rows8, rows, Dp, add, d_sums);
     return hipGetLastError();
 }
 
 namespace {
 
-template <bool LIST, int MODE>
+// b's per-row and q's per-query terms of the epilogue: the norms (L2), the correction sums (inner product, unsigned
+// rows), or nothing (inner product, signed rows).
+template <bool LIST, int MODE, int METRIC, bool CORR>
 void dist_u8(const FlatBase& b, int64_t e0, int rows, const FlatQueries& q, uint64_t* keys, int cap, const int64_t* offs,
              FlatQueryState* state, hipStream_t stream) {
-    flat_dist_u8_kernel<LIST, MODE><<<dim3((rows + UV - 1) / UV, (q.nq + UQ - 1) / UQ), dim3(256), 0, stream>>>(
-        b.i8, b.norm, b.list, e0, rows, b.Dp, q.i8, q.norm, q.nq, b.id_offset, keys, cap, offs, state);
+    const int32_t* vterm = METRIC == kFlatL2 ? b.norm : CORR ? b.rsum : nullptr;
+    const int32_t* qterm = METRIC == kFlatL2 ? q.norm : CORR ? q.sum : nullptr;
+    flat_dist_u8_kernel<LIST, MODE, METRIC, CORR><<<dim3((rows + UV - 1) / UV, (q.nq + UQ - 1) / UQ), dim3(256), 0, stream>>>(
+        b.i8, vterm, b.list, e0, rows, b.Dp, q.i8, qterm, q.nq, b.id_offset, keys, cap, offs, state);
+}
+
+template <int METRIC, bool CORR>
+auto pick_dist_u8(bool filtered, int mode) {
+    return filtered ? (mode == kFlatTopK    ? dist_u8<true, kFlatTopK, METRIC, CORR>
+                       : mode == kFlatCount ? dist_u8<true, kFlatCount, METRIC, CORR>
+                                            : dist_u8<true, kFlatEmit, METRIC, CORR>)
+                    : (mode == kFlatTopK    ? dist_u8<false, kFlatTopK, METRIC, CORR>
+                       : mode == kFlatCount ? dist_u8<false, kFlatCount, METRIC, CORR>
+                                            : dist_u8<false, kFlatEmit, METRIC, CORR>);
 }
 
 }  // namespace
 
 hipError_t launch_flat_dist_u8(int mode, const FlatBase& b, int64_t e0, int rows, const FlatQueries& q, uint64_t* keys,
                                int cap, const int64_t* offs, FlatQueryState* state, hipStream_t stream) {
-    auto* launch = b.filtered ? (mode == kFlatTopK    ? dist_u8<true, kFlatTopK>
-                                 : mode == kFlatCount ? dist_u8<true, kFlatCount>
-                                                      : dist_u8<true, kFlatEmit>)
-                              : (mode == kFlatTopK    ? dist_u8<false, kFlatTopK>
-                                 : mode == kFlatCount ? dist_u8<false, kFlatCount>
-                                                      : dist_u8<false, kFlatEmit>);
+    auto* launch = b.metric != kFlatIP ? pick_dist_u8<kFlatL2, true>(b.filtered, mode)
+                   : b.i8_signed       ? pick_dist_u8<kFlatIP, false>(b.filtered, mode)
+                                       : pick_dist_u8<kFlatIP, true>(b.filtered, mode);
     launch(b, e0, rows, q, keys, cap, offs, state, stream);
     return hipGetLastError();
 }
 
-hipError_t launch_flat_rerank_u8(const int8_t* d_base, int64_t n, int D, int Dp, const uint8_t* d_queries, int nq,
-                                 const int32_t* d_cand, int n_cand, int top_k, int64_t id_offset, const uint32_t* d_map,
-                                 int64_t n_map, uint64_t* d_keys, uint32_t* d_flag, int32_t* d_ids, float* d_dists,
-                                 hipStream_t stream) {
+hipError_t launch_flat_rerank_u8(int metric, bool is_signed, const int8_t* d_base, int64_t n, int D, int Dp,
+                                 const uint8_t* d_queries, int nq, const int32_t* d_cand, int n_cand, int top_k,
+                                 int64_t id_offset, const uint32_t* d_map, int64_t n_map, uint64_t* d_keys, uint32_t* d_flag,
+                                 int32_t* d_ids, float* d_dists, hipStream_t stream) {
     if (nq <= 0) return hipSuccess;
     const int n_pad = (int)flat_rerank_keys(n_cand);
+    auto* kernel = metric == kFlatIP ? (is_signed ? flat_rerank_u8_kernel<kFlatIP, true> : flat_rerank_u8_kernel<kFlatIP, false>)
+                                     : (is_signed ? flat_rerank_u8_kernel<kFlatL2, true> : flat_rerank_u8_kernel<kFlatL2, false>);
     for (int q0 = 0; q0 < nq; q0 += 65535) {  // the grid's y extent
         const int m = std::min(65535, nq - q0);
-        flat_rerank_u8_kernel<<<dim3((n_pad + 255) / 256, m), dim3(256), 0, stream>>>(
+        kernel<<<dim3((n_pad + 255) / 256, m), dim3(256), 0, stream>>>(
             d_base, n, D, Dp, d_queries + (size_t)q0 * D, d_cand + (size_t)q0 * n_cand, n_cand, n_pad, id_offset, d_map,
             n_map, d_keys + (size_t)q0 * n_pad, d_flag);
     }
-    return launch_flat_sort_emit(d_keys, (size_t)n_pad, nullptr, nq, n_pad, top_k, d_ids, d_dists, stream);
+    return launch_flat_sort_emit(d_keys, (size_t)n_pad, nullptr, nq, n_pad, top_k, d_ids, d_dists, stream, metric);
 }
 
 }  // namespace dpq

@@ -49,6 +49,8 @@
  *   (none: FAISS's IndexFlatIP: search, an      dpq_flat_search_ip / dpq_flat_search_filtered_ip /
  *     IDSelector, range_search; re-ranking by     dpq_flat_range_search_ip / dpq_flat_rerank_ip[_device],
  *     inner product)                              dpq_merge_topk_ip_host
+ *   (none: IndexFlatIP over bytes; FAISS's      dpq_flat_*_ip_u8 on a dpq_flat_open_u8 handle; dpq_flat_open_i8 and
+ *     ScalarQuantizer QT_8bit_direct_signed)      dpq_flat_*_i8 / dpq_flat_*_ip_i8 (signed int8 rows, both metrics)
  *   (none: FAISS's IndexScalarQuantizer fp16 /  dpq_flat_open_half / dpq_flat_open_narrowed, then every fp32-query
  *     bf16 under IndexFlat's calls, and           dpq_flat_* call; dpq_half_from_float / dpq_half_to_float
  *     IndexRefineFlat over it)
@@ -797,10 +799,8 @@ int dpq_recall(const int32_t* found, int found_stride, int R, const int32_t* tru
  * convention); the `dists` array of the dpq_range_result holds the scores, and a list is ordered by (score descending, id
  * ascending).  A threshold of -inf keeps every row, +inf none, -0.0 is read as +0.0; a NaN threshold is DPQ_ERR_ARG,
  * checked before any device work.
- * Byte handles are out of scope: an _ip call on a handle of dpq_flat_open_u8 is DPQ_ERR_ARG with a message that says so.
- * The byte kernel gets its L2 from sum (v - q)^2 = |v|^2 + |q|^2 - 2 v.q on biased int8 rows; the inner product of the
- * UNBIASED bytes needs, beside the int8 dot product, the per-row sum of the bytes -- an array the open call does not
- * compute today.  Widen such data to fp32 (dpq_read_vecs_range does) and use dpq_flat_open. */
+ * Byte handles take byte queries: an fp32-query _ip call on a handle of dpq_flat_open_u8 is DPQ_ERR_ARG with a message
+ * that names the _ip_u8 call ("exact inner product over byte vectors" below). */
 int dpq_flat_search_ip(dpq_flat* f, const float* queries, int nq, int top_k, int32_t* ids, float* scores);
 int dpq_flat_search_filtered_ip(dpq_flat* f, const dpq_flat_filter* ff, const float* queries, int nq, int top_k, int32_t* ids,
                                 float* scores);
@@ -819,6 +819,65 @@ int dpq_flat_rerank_ip_device(dpq_flat* f, const float* d_queries, int nq, const
  * top_k < 1, nq < 0. */
 int dpq_merge_topk_ip_host(const int32_t* ids, const float* scores, int n_lists, int nq, int top_k, int32_t* out_ids,
                            float* out_scores);
+
+/* ---- exact inner product over byte vectors; signed int8 storage -------------------
+ * The last two cells of the table of kinds x metrics: inner product on a handle of dpq_flat_open_u8, and a handle kind
+ * for signed bytes -- embeddings quantised to int8 and scored by dot product -- with both metrics.  Both run on the int8
+ * matrix cores (v_mfma_i32_32x32x32_i8) over rows of one byte per value.  Every answer is an integer below 2^31 in
+ * magnitude, so the contract is once more "the bits of the fp32 call over the rows widened to fp32", with no tolerance.
+ * Unsigned bytes, inner product (the _ip_u8 calls; const uint8_t* queries).  v, q in {0..255}^D, D <= 2048:
+ * S = sum v[d] * q[d] is an integer, 0 <= S <= 2048 * 65025 = 133 171 200 < 2^31, and the score is (float)(int32)S, round
+ * to nearest even.  These are the bits of dpq_flat_search_ip over the widened rows: its fp64 accumulator holds S exactly,
+ * whatever the order.  Order, key word and padding (-1 / -inf) are those of the fp32 inner-product calls above; range
+ * search keeps s > threshold, strictly, with -0.0 read as +0.0 and a NaN threshold refused first.  Two different
+ * integers above 2^24 that round to the same float are ordered by id: the key is built from the float's bits.
+ * The stored rows are v' = v - 128 and the staged queries q' = q - 128, so the kernel forms
+ *     S = v'.q' + rs[row] + qs[query],   rs = 128 sum v' + 16384 D,   qs = 128 sum q',
+ * in int32: |v'.q'| <= 2^25, 0 <= rs < 2^26, |qs| <= 2^25.  The rows' terms rs are made by the FIRST inner-product search
+ * or range call on the handle, in one pass over the stored rows, and cost 4 * n bytes of device memory from then until
+ * dpq_flat_close; dpq_flat_open_u8 and the L2 calls keep their device memory and their behaviour.  The re-rank forms
+ * the products of the bytes themselves and needs no such array.
+ * Signed bytes (dpq_flat_open_i8 and the _i8 calls; const int8_t* vectors and queries).  v, q in {-128..127}^D.
+ * L2: sum (v[d] - q[d])^2 <= 2048 * 255^2 < 2^31, reported as (float)(int32): the bits of dpq_flat_search over the
+ * widened rows.  Inner product: |S| <= 2048 * 128^2 = 2^25, reported as (float)(int32)S -- the int8 dot product itself,
+ * with no correction term; negative scores take the sign branch of the key word, an integer 0 is +0.0.  Device memory:
+ * that of dpq_flat_open_u8.
+ * What carries over unchanged from the call of the same shape (dpq_flat_search_u8 for dpq_flat_search_i8,
+ * dpq_flat_search_ip for dpq_flat_search_ip_u8, and so on): every argument check and its order (arguments, then
+ * device, then handle), DPQ_ERR_TOPK, nq == 0, id_offset, the padding rows, filters (dpq_flat_filter_create and
+ * dpq_flat_filter_count work on an i8 handle), dpq_flat_set_id_map with the even-n_map rule, negative candidates as
+ * padding, a row named twice counting once, the flag word of the device forms, dpq_flat_close, dpq_merge_topk_host (L2)
+ * and dpq_merge_topk_ip_host (scores).
+ * Handle kinds do not mix: fp32 (and half), u8 and i8 handles each take the calls of their own kind; any other is
+ * DPQ_ERR_ARG with a message that names the function to call instead.  fp32 queries against byte rows are out of scope. */
+int dpq_flat_open_i8(const int8_t* vectors, int64_t n, int D, int device, int64_t id_offset, dpq_flat** out);
+int dpq_flat_search_ip_u8(dpq_flat* f, const uint8_t* queries, int nq, int top_k, int32_t* ids, float* scores);
+int dpq_flat_search_filtered_ip_u8(dpq_flat* f, const dpq_flat_filter* ff, const uint8_t* queries, int nq, int top_k,
+                                   int32_t* ids, float* scores);
+int dpq_flat_range_search_ip_u8(dpq_flat* f, const dpq_flat_filter* ff, const uint8_t* queries, int nq,
+                                const float* thresholds, dpq_range_result** out);
+int dpq_flat_rerank_ip_u8(dpq_flat* f, const uint8_t* queries, int nq, const int32_t* cand_ids, int n_cand, int top_k,
+                          int32_t* ids, float* scores);
+int dpq_flat_rerank_ip_u8_device(dpq_flat* f, const uint8_t* d_queries, int nq, const int32_t* d_cand_ids, int n_cand,
+                                 int top_k, int32_t* d_ids, float* d_scores, void* hip_stream);
+int dpq_flat_search_i8(dpq_flat* f, const int8_t* queries, int nq, int top_k, int32_t* ids, float* dists);
+int dpq_flat_search_filtered_i8(dpq_flat* f, const dpq_flat_filter* ff, const int8_t* queries, int nq, int top_k,
+                                int32_t* ids, float* dists);
+int dpq_flat_range_search_i8(dpq_flat* f, const dpq_flat_filter* ff, const int8_t* queries, int nq, const float* radii,
+                             dpq_range_result** out);
+int dpq_flat_rerank_i8(dpq_flat* f, const int8_t* queries, int nq, const int32_t* cand_ids, int n_cand, int top_k,
+                       int32_t* ids, float* dists);
+int dpq_flat_rerank_i8_device(dpq_flat* f, const int8_t* d_queries, int nq, const int32_t* d_cand_ids, int n_cand,
+                              int top_k, int32_t* d_ids, float* d_dists, void* hip_stream);
+int dpq_flat_search_ip_i8(dpq_flat* f, const int8_t* queries, int nq, int top_k, int32_t* ids, float* scores);
+int dpq_flat_search_filtered_ip_i8(dpq_flat* f, const dpq_flat_filter* ff, const int8_t* queries, int nq, int top_k,
+                                   int32_t* ids, float* scores);
+int dpq_flat_range_search_ip_i8(dpq_flat* f, const dpq_flat_filter* ff, const int8_t* queries, int nq,
+                                const float* thresholds, dpq_range_result** out);
+int dpq_flat_rerank_ip_i8(dpq_flat* f, const int8_t* queries, int nq, const int32_t* cand_ids, int n_cand, int top_k,
+                          int32_t* ids, float* scores);
+int dpq_flat_rerank_ip_i8_device(dpq_flat* f, const int8_t* d_queries, int nq, const int32_t* d_cand_ids, int n_cand,
+                                 int top_k, int32_t* d_ids, float* d_scores, void* hip_stream);
 
 /* ---- exact search over half-precision vectors: fp16 and bf16 storage -------------
  * Embeddings are stored as fp16 or bf16.  A half handle keeps such rows on the GPU as they are, 16 bits per value, at
