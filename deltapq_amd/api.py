@@ -1149,85 +1149,66 @@ def _range_result(lib, res):
         lib.dpq_range_result_free(res)
 
 
-def _flat_search_filtered(index, fn, name, queries, top_k, id_filter):
-    q = index._queries(queries)
-    ids = np.empty((q.shape[0], top_k), dtype=np.int32)
-    dists = np.empty((q.shape[0], top_k), dtype=np.float32)
-    check(fn(index._h, FlatIdFilter._handle(id_filter), _np_ptr(q), q.shape[0], top_k, _np_ptr(ids), _np_ptr(dists)), name)
-    return ids, dists
+class _FlatIndexBase:
+    """The methods of every flat index.  A subclass opens the handle (self._lib, self._h, self.n, self.D, self.id_offset),
+    says what it takes as queries (_queries for arrays, _check_tensor for tensors) and names its C entry points by the
+    suffixes _l2 / _ip: dpq_flat_search + suffix, dpq_flat_rerank + suffix + _device, and so on."""
 
-
-def _flat_range_search(index, fn, name, queries, radius, id_filter):
-    q = index._queries(queries)
-    nq = q.shape[0]
-    r = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, dtype=np.float32), (nq,)))
-    res = ctypes.c_void_p()
-    check(fn(index._h, FlatIdFilter._handle(id_filter, optional=True), _np_ptr(q), nq, _np_ptr(r), res), name)
-    return _range_result(index._lib, res)
-
-
-class FlatIndex:
-    """Raw fp32 vectors [n][D] on one GPU (dpq_flat): exact squared L2 distances with the reference's brute-force
-    arithmetic -- ground truth over all of them (search), or over a candidate list per query (rerank).  The *_ip methods
-    are the same searches by exact inner product: scores instead of distances, best (largest) first."""
-
-    def __init__(self, vectors, device=0, id_offset=0):
-        self._lib = _lib.load()
-        self._h = None
-        v = np.ascontiguousarray(vectors, dtype=np.float32)
-        if v.ndim != 2:
-            raise ValueError("vectors must be [n][D]")
-        self.n, self.D, self.id_offset = int(v.shape[0]), int(v.shape[1]), int(id_offset)
-        h = ctypes.c_void_p()
-        check(self._lib.dpq_flat_open(_np_ptr(v), self.n, self.D, device, id_offset, ctypes.byref(h)), "dpq_flat_open")
-        self._h = h
+    _l2, _ip = "", "_ip"
 
     def _queries(self, queries):
-        q = np.ascontiguousarray(queries, dtype=np.float32)
+        q = self._as_queries(queries)
         if q.ndim != 2 or q.shape[1] != self.D:
             raise ValueError("queries must be [nq][%d]" % self.D)
         return q
 
-    def _search(self, name, queries, top_k):
+    def _search(self, name, queries, top_k, *id_filter):
+        """dpq_flat_search*, or, given an id_filter, dpq_flat_search_filtered*."""
         q = self._queries(queries)
         ids = np.empty((q.shape[0], top_k), dtype=np.int32)
         dists = np.empty((q.shape[0], top_k), dtype=np.float32)
-        check(getattr(self._lib, name)(self._h, _np_ptr(q), q.shape[0], top_k, _np_ptr(ids), _np_ptr(dists)), name)
+        filt = [FlatIdFilter._handle(f) for f in id_filter]
+        check(getattr(self._lib, name)(self._h, *filt, _np_ptr(q), q.shape[0], top_k, _np_ptr(ids), _np_ptr(dists)), name)
         return ids, dists
 
     def search(self, queries, top_k):
         """Exact top_k over all vectors -> ids int32 [nq][top_k], dists float32 [nq][top_k] by (distance, id)."""
-        return self._search("dpq_flat_search", queries, top_k)
+        return self._search("dpq_flat_search" + self._l2, queries, top_k)
 
     def search_ip(self, queries, top_k):
         """Exact top_k by inner product -> ids int32 [nq][top_k], scores float32 [nq][top_k] by (score descending, id)
-        (dpq_flat_search_ip)."""
-        return self._search("dpq_flat_search_ip", queries, top_k)
-
-    def search_filtered_ip(self, queries, top_k, id_filter):
-        """search_ip over the rows `id_filter` allows; rows are padded with -1 / -inf (dpq_flat_search_filtered_ip)."""
-        return _flat_search_filtered(self, self._lib.dpq_flat_search_filtered_ip, "dpq_flat_search_filtered_ip", queries,
-                                     top_k, id_filter)
-
-    def range_search_ip(self, queries, threshold, id_filter=None):
-        """Every (allowed) row with exact score s > threshold, strictly (dpq_flat_range_search_ip).  `threshold` is a
-        scalar or one value per query.  Returns (lims int64 [nq + 1], ids int32, scores float32); query i owns entries
-        lims[i]:lims[i + 1], by (score descending, id)."""
-        return _flat_range_search(self, self._lib.dpq_flat_range_search_ip, "dpq_flat_range_search_ip", queries,
-                                  threshold, id_filter)
+        (dpq_flat_search_ip*)."""
+        return self._search("dpq_flat_search" + self._ip, queries, top_k)
 
     def search_filtered(self, queries, top_k, id_filter):
         """Exact top_k over the rows `id_filter` (a FlatIdFilter made on this index) allows; rows are padded with -1 / +inf
-        where fewer than top_k rows are allowed (dpq_flat_search_filtered)."""
-        return _flat_search_filtered(self, self._lib.dpq_flat_search_filtered, "dpq_flat_search_filtered", queries, top_k,
-                                     id_filter)
+        where fewer than top_k rows are allowed (dpq_flat_search_filtered*)."""
+        return self._search("dpq_flat_search_filtered" + self._l2, queries, top_k, id_filter)
+
+    def search_filtered_ip(self, queries, top_k, id_filter):
+        """search_ip over the rows `id_filter` allows; rows are padded with -1 / -inf (dpq_flat_search_filtered_ip*)."""
+        return self._search("dpq_flat_search_filtered" + self._ip, queries, top_k, id_filter)
+
+    def _range_search(self, name, queries, radius, id_filter):
+        q = self._queries(queries)
+        nq = q.shape[0]
+        r = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, dtype=np.float32), (nq,)))
+        res = ctypes.c_void_p()
+        check(getattr(self._lib, name)(self._h, FlatIdFilter._handle(id_filter, optional=True), _np_ptr(q), nq, _np_ptr(r),
+                                       res), name)
+        return _range_result(self._lib, res)
 
     def range_search(self, queries, radius, id_filter=None):
-        """Every (allowed) row with exact distance d < radius, strictly (dpq_flat_range_search).  `radius` is a scalar or
+        """Every (allowed) row with exact distance d < radius, strictly (dpq_flat_range_search*).  `radius` is a scalar or
         one value per query.  Returns (lims int64 [nq + 1], ids int32, dists float32) as DeltaPQIndex.range_search does;
         query i owns entries lims[i]:lims[i + 1], ascending by (distance, id)."""
-        return _flat_range_search(self, self._lib.dpq_flat_range_search, "dpq_flat_range_search", queries, radius,
-                                  id_filter)
+        return self._range_search("dpq_flat_range_search" + self._l2, queries, radius, id_filter)
+
+    def range_search_ip(self, queries, threshold, id_filter=None):
+        """Every (allowed) row with exact score s > threshold, strictly (dpq_flat_range_search_ip*).  `threshold` is a
+        scalar or one value per query.  Returns (lims int64 [nq + 1], ids int32, scores float32); query i owns entries
+        lims[i]:lims[i + 1], by (score descending, id)."""
+        return self._range_search("dpq_flat_range_search" + self._ip, queries, threshold, id_filter)
 
     def set_id_map(self, vec_id):
         """DFS position -> row of this handle (DeltaTree.vec_id): rerank candidates are then DFS positions."""
@@ -1247,24 +1228,17 @@ class FlatIndex:
 
     def rerank(self, queries, cand_ids, top_k):
         """Exact distances of cand_ids[nq][n_cand] only (negative = padding), the best top_k of them."""
-        return self._rerank("dpq_flat_rerank", queries, cand_ids, top_k)
+        return self._rerank("dpq_flat_rerank" + self._l2, queries, cand_ids, top_k)
 
     def rerank_ip(self, queries, cand_ids, top_k):
         """Exact inner-product scores of cand_ids[nq][n_cand] only (negative = padding), the best top_k of them by (score
-        descending, id); rows are padded with -1 / -inf (dpq_flat_rerank_ip)."""
-        return self._rerank("dpq_flat_rerank_ip", queries, cand_ids, top_k)
-
-    def rerank_torch(self, queries, cand_ids, top_k, out_ids=None, out_dists=None):
-        """rerank on device tensors, on torch's current stream (dpq_flat_rerank_device); the results are complete on return."""
-        return self._rerank_torch("dpq_flat_rerank_device", queries, cand_ids, top_k, out_ids, out_dists)
-
-    def rerank_ip_torch(self, queries, cand_ids, top_k, out_ids=None, out_scores=None):
-        """rerank_ip on device tensors, on torch's current stream (dpq_flat_rerank_ip_device); complete on return."""
-        return self._rerank_torch("dpq_flat_rerank_ip_device", queries, cand_ids, top_k, out_ids, out_scores)
+        descending, id); rows are padded with -1 / -inf (dpq_flat_rerank_ip*)."""
+        return self._rerank("dpq_flat_rerank" + self._ip, queries, cand_ids, top_k)
 
     def _rerank_torch(self, name, queries, cand_ids, top_k, out_ids, out_dists):
         import torch
-        assert queries.is_cuda and queries.dtype == torch.float32 and queries.is_contiguous() and queries.shape[1] == self.D
+        self._check_tensor(queries)
+        assert queries.is_cuda and queries.is_contiguous() and queries.shape[1] == self.D
         assert cand_ids.is_cuda and cand_ids.dtype == torch.int32 and cand_ids.is_contiguous()
         assert cand_ids.shape[0] == queries.shape[0]
         nq = queries.shape[0]
@@ -1278,6 +1252,15 @@ class FlatIndex:
                                        ctypes.c_void_p(out_ids.data_ptr()), ctypes.c_void_p(out_dists.data_ptr()),
                                        ctypes.c_void_p(stream)), name)
         return out_ids, out_dists
+
+    def rerank_torch(self, queries, cand_ids, top_k, out_ids=None, out_dists=None):
+        """rerank on device tensors, on torch's current stream (dpq_flat_rerank*_device); the results are complete on
+        return."""
+        return self._rerank_torch("dpq_flat_rerank%s_device" % self._l2, queries, cand_ids, top_k, out_ids, out_dists)
+
+    def rerank_ip_torch(self, queries, cand_ids, top_k, out_ids=None, out_scores=None):
+        """rerank_ip on device tensors, on torch's current stream (dpq_flat_rerank_ip*_device); complete on return."""
+        return self._rerank_torch("dpq_flat_rerank%s_device" % self._ip, queries, cand_ids, top_k, out_ids, out_scores)
 
     def close(self):
         if self._h is not None:
@@ -1295,6 +1278,32 @@ class FlatIndex:
 
     def __exit__(self, *exc):
         self.close()
+
+
+class FlatIndex(_FlatIndexBase):
+    """Raw fp32 vectors [n][D] on one GPU (dpq_flat): exact squared L2 distances with the reference's brute-force
+    arithmetic -- ground truth over all of them (search), or over a candidate list per query (rerank).  The *_ip methods
+    are the same searches by exact inner product: scores instead of distances, best (largest) first."""
+
+    def __init__(self, vectors, device=0, id_offset=0):
+        self._lib = _lib.load()
+        self._h = None
+        v = np.ascontiguousarray(vectors, dtype=np.float32)
+        if v.ndim != 2:
+            raise ValueError("vectors must be [n][D]")
+        self.n, self.D, self.id_offset = int(v.shape[0]), int(v.shape[1]), int(id_offset)
+        h = ctypes.c_void_p()
+        check(self._lib.dpq_flat_open(_np_ptr(v), self.n, self.D, device, id_offset, ctypes.byref(h)), "dpq_flat_open")
+        self._h = h
+
+    @staticmethod
+    def _as_queries(queries):
+        return np.ascontiguousarray(queries, dtype=np.float32)
+
+    @staticmethod
+    def _check_tensor(queries):
+        import torch
+        assert queries.dtype == torch.float32
 
 
 HALF_FORMATS = {"f16": 1, "bf16": 2}   # DPQ_HALF_F16, DPQ_HALF_BF16
@@ -1367,7 +1376,7 @@ class FlatIndexHalf(FlatIndex):
         self._h = h
 
 
-class FlatIndexU8:
+class FlatIndexU8(_FlatIndexBase):
     """Byte vectors [n][D] on one GPU (dpq_flat_open_u8): FlatIndex's answers -- the same ids and the same distance bits as
     on the bytes widened to fp32 -- from the int8 matrix cores, at a quarter of the device memory.  The *_ip methods are
     the same searches by exact inner product of the bytes (dpq_flat_*_ip_u8): FlatIndex's *_ip answers over the widened
@@ -1392,121 +1401,14 @@ class FlatIndexU8:
             raise TypeError("%s must be a %s array (FlatIndex takes fp32)" % (what, np.dtype(cls._dtype).name))
         return np.ascontiguousarray(a)
 
-    def _queries(self, queries):
-        q = self._bytes(queries, "queries")
-        if q.ndim != 2 or q.shape[1] != self.D:
-            raise ValueError("queries must be [nq][%d]" % self.D)
-        return q
+    def _as_queries(self, queries):
+        return self._bytes(queries, "queries")
 
-    def _search(self, name, queries, top_k):
-        q = self._queries(queries)
-        ids = np.empty((q.shape[0], top_k), dtype=np.int32)
-        dists = np.empty((q.shape[0], top_k), dtype=np.float32)
-        check(getattr(self._lib, name)(self._h, _np_ptr(q), q.shape[0], top_k, _np_ptr(ids), _np_ptr(dists)), name)
-        return ids, dists
-
-    def search(self, queries, top_k):
-        """Exact top_k over all vectors -> ids int32 [nq][top_k], dists float32 [nq][top_k] by (distance, id)."""
-        return self._search("dpq_flat_search" + self._l2, queries, top_k)
-
-    def search_ip(self, queries, top_k):
-        """Exact top_k by inner product -> ids int32 [nq][top_k], scores float32 [nq][top_k] by (score descending, id)."""
-        return self._search("dpq_flat_search" + self._ip, queries, top_k)
-
-    def _search_filtered(self, name, queries, top_k, id_filter):
-        return _flat_search_filtered(self, getattr(self._lib, name), name, queries, top_k, id_filter)
-
-    def search_filtered(self, queries, top_k, id_filter):
-        """Exact top_k over the rows `id_filter` (a FlatIdFilter made on this index) allows; rows are padded with -1 / +inf
-        where fewer than top_k rows are allowed (dpq_flat_search_filtered_u8)."""
-        return self._search_filtered("dpq_flat_search_filtered" + self._l2, queries, top_k, id_filter)
-
-    def search_filtered_ip(self, queries, top_k, id_filter):
-        """search_ip over the rows `id_filter` allows; rows are padded with -1 / -inf."""
-        return self._search_filtered("dpq_flat_search_filtered" + self._ip, queries, top_k, id_filter)
-
-    def _range_search(self, name, queries, radius, id_filter):
-        return _flat_range_search(self, getattr(self._lib, name), name, queries, radius, id_filter)
-
-    def range_search(self, queries, radius, id_filter=None):
-        """Every (allowed) row with exact distance d < radius, strictly (dpq_flat_range_search_u8).  `radius` is a scalar or
-        one value per query.  Returns (lims int64 [nq + 1], ids int32, dists float32) as DeltaPQIndex.range_search does;
-        query i owns entries lims[i]:lims[i + 1], ascending by (distance, id)."""
-        return self._range_search("dpq_flat_range_search" + self._l2, queries, radius, id_filter)
-
-    def range_search_ip(self, queries, threshold, id_filter=None):
-        """Every (allowed) row with exact score s > threshold, strictly; lists by (score descending, id)."""
-        return self._range_search("dpq_flat_range_search" + self._ip, queries, threshold, id_filter)
-
-    def set_id_map(self, vec_id):
-        """DFS position -> row of this handle (DeltaTree.vec_id): rerank candidates are then DFS positions."""
-        m = np.ascontiguousarray(vec_id, dtype=np.uint32)
-        check(self._lib.dpq_flat_set_id_map(self._h, _np_ptr(m), m.size), "dpq_flat_set_id_map")
-
-    def _rerank(self, name, queries, cand_ids, top_k):
-        q = self._queries(queries)
-        c = np.ascontiguousarray(cand_ids, dtype=np.int32)
-        if c.ndim != 2 or c.shape[0] != q.shape[0]:
-            raise ValueError("cand_ids must be [nq][n_cand]")
-        ids = np.empty((q.shape[0], top_k), dtype=np.int32)
-        dists = np.empty((q.shape[0], top_k), dtype=np.float32)
-        check(getattr(self._lib, name)(self._h, _np_ptr(q), q.shape[0], _np_ptr(c), c.shape[1], top_k, _np_ptr(ids),
-                                       _np_ptr(dists)), name)
-        return ids, dists
-
-    def rerank(self, queries, cand_ids, top_k):
-        """Exact distances of cand_ids[nq][n_cand] only (negative = padding), the best top_k of them."""
-        return self._rerank("dpq_flat_rerank" + self._l2, queries, cand_ids, top_k)
-
-    def rerank_ip(self, queries, cand_ids, top_k):
-        """Exact inner-product scores of cand_ids[nq][n_cand] only (negative = padding), the best top_k of them by (score
-        descending, id); rows are padded with -1 / -inf."""
-        return self._rerank("dpq_flat_rerank" + self._ip, queries, cand_ids, top_k)
-
-    def _rerank_torch(self, name, queries, cand_ids, top_k, out_ids, out_dists):
+    def _check_tensor(self, queries):
         import torch
         want = getattr(torch, np.dtype(self._dtype).name)
         if not isinstance(queries, torch.Tensor) or queries.dtype != want:
             raise TypeError("queries must be a %s tensor (FlatIndex takes fp32)" % np.dtype(self._dtype).name)
-        assert queries.is_cuda and queries.is_contiguous() and queries.shape[1] == self.D
-        assert cand_ids.is_cuda and cand_ids.dtype == torch.int32 and cand_ids.is_contiguous()
-        assert cand_ids.shape[0] == queries.shape[0]
-        nq = queries.shape[0]
-        if out_ids is None:
-            out_ids = torch.empty((nq, top_k), dtype=torch.int32, device=queries.device)
-        if out_dists is None:
-            out_dists = torch.empty((nq, top_k), dtype=torch.float32, device=queries.device)
-        stream = torch.cuda.current_stream(queries.device).cuda_stream
-        check(getattr(self._lib, name)(self._h, ctypes.c_void_p(queries.data_ptr()), nq,
-                                       ctypes.c_void_p(cand_ids.data_ptr()), cand_ids.shape[1], top_k,
-                                       ctypes.c_void_p(out_ids.data_ptr()), ctypes.c_void_p(out_dists.data_ptr()),
-                                       ctypes.c_void_p(stream)), name)
-        return out_ids, out_dists
-
-    def rerank_torch(self, queries, cand_ids, top_k, out_ids=None, out_dists=None):
-        """rerank on device tensors, on torch's current stream (dpq_flat_rerank_u8_device); complete on return."""
-        return self._rerank_torch("dpq_flat_rerank%s_device" % self._l2, queries, cand_ids, top_k, out_ids, out_dists)
-
-    def rerank_ip_torch(self, queries, cand_ids, top_k, out_ids=None, out_scores=None):
-        """rerank_ip on device tensors, on torch's current stream; complete on return."""
-        return self._rerank_torch("dpq_flat_rerank%s_device" % self._ip, queries, cand_ids, top_k, out_ids, out_scores)
-
-    def close(self):
-        if self._h is not None:
-            self._lib.dpq_flat_close(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
 
 class FlatIndexI8(FlatIndexU8):

@@ -1,29 +1,47 @@
 // dpq_capi_flat.cpp -- the exact-search entry points of include/deltapq_amd.h: dpq_flat_* and dpq_flat_filter_*.
 #include "dpq_capi_internal.h"
 
-// ---- exact search over raw vectors (dpq_flat.hip, dpq_flat_u8.hip) ----------------------------------------------
+// ---- exact search over raw vectors (dpq_flat.hip, dpq_flat_u8.hip) ---------------------------------------------------
 
 namespace {
 
-// The kind of handle a call with queries of type Q takes: float -- an fp32 or a half handle, uint8_t -- a handle of
-// dpq_flat_open_u8, int8_t -- a handle of dpq_flat_open_i8.
-template <class Q> constexpr int kind_of = kFlatKindF32;
-template <> constexpr int kind_of<uint8_t> = kFlatKindU8;
-template <> constexpr int kind_of<int8_t> = kFlatKindI8;
+// The format of queries of type Q.  A call takes the handles whose rows go with it (dpq::flat_query_format): float -- an
+// fp32 or a half handle, uint8_t -- a handle of dpq_flat_open_u8, int8_t -- a handle of dpq_flat_open_i8.
+template <class Q> constexpr int format_of = dpq::kFlatF32;
+template <> constexpr int format_of<uint8_t> = dpq::kFlatU8;
+template <> constexpr int format_of<int8_t> = dpq::kFlatI8;
 
-// A search call's name: its shape ("dpq_flat_search", "dpq_flat_rerank", ...), its metric, the kind of handle it takes,
-// the device form.  The same pieces name the call of the same shape for any other kind of handle.
+// A search call's name: its shape ("dpq_flat_search", "dpq_flat_rerank", ...), its metric, the format of its queries
+// (`kind`), the device form.  The same pieces name the call of the same shape for queries of any other format.
 struct FlatCall {
     const char* stem;
     int metric;
     int kind;
     bool device = false;
     std::string name(int k) const {
-        return std::string(stem) + (metric == dpq::kFlatIP ? "_ip" : "") + (k == kFlatKindU8 ? "_u8" : k == kFlatKindI8 ? "_i8" : "") +
+        return std::string(stem) + (metric == dpq::kFlatIP ? "_ip" : "") + (k == dpq::kFlatU8 ? "_u8" : k == dpq::kFlatI8 ? "_i8" : "") +
                (device ? "_device" : "");
     }
     std::string name() const { return name(kind); }
 };
+
+// The handle's rows, all of them or those a filter lists, as the launchers of dpq_flat.h take them.
+dpq::FlatBase flat_base(const dpq_flat* f, const dpq_flat_filter* ff, int metric) {
+    dpq::FlatBase b;
+    b.format = f->format;
+    b.rows = f->rows.get();
+    b.n = f->n;
+    b.D = f->D;
+    b.Dp = f->Dp;
+    b.id_offset = f->id_offset;
+    b.metric = metric;
+    b.norm = f->norm8;
+    b.rsum = f->rsum8;
+    b.filtered = ff != nullptr;
+    b.list = ff ? ff->list.get() : nullptr;
+    b.n_entries = ff ? ff->n_allowed : f->n;
+    return b;
+}
 
 // Candidates of dpq_flat_rerank*, all device pointers; ends with one flag word read back.
 template <class Q>
@@ -35,25 +53,21 @@ int flat_rerank_on_device(const char* fn, int metric, dpq_flat* f, const Q* d_qu
     if (rc) return rc;
     if (!f->flag.get() && (rc = f->flag.alloc(1))) return rc;
     DPQ_HIP(hipMemsetAsync(f->flag, 0, sizeof(uint32_t), stream));
+    const dpq::FlatBase base = flat_base(f, nullptr, metric);
+    dpq::FlatRerank r;
+    r.n_cand = n_cand;
+    r.top_k = top_k;
+    r.map = f->h_map.empty() ? nullptr : f->map.get();
+    r.n_map = (int64_t)f->h_map.size();
+    r.keys = f->keys;
+    r.flag = f->flag;
     for (int q0 = 0; q0 < nq; q0 += per) {
-        const int m = std::min(per, nq - q0);
-        const uint32_t* map = f->h_map.empty() ? nullptr : f->map.get();
-        if constexpr (kind_of<Q> != kFlatKindF32)
-            DPQ_HIP(dpq::launch_flat_rerank_u8(metric, kind_of<Q> == kFlatKindI8, f->base8, f->n, f->D, f->Dp,
-                                               reinterpret_cast<const uint8_t*>(d_queries) + (size_t)q0 * f->D, m,
-                                               d_cand + (size_t)q0 * n_cand, n_cand, top_k, f->id_offset, map,
-                                               (int64_t)f->h_map.size(), f->keys, f->flag, d_ids + (size_t)q0 * top_k,
-                                               d_dists + (size_t)q0 * top_k, stream));
-        else if (f->half)
-            DPQ_HIP(dpq::launch_flat_rerank_half(metric, f->half, f->base16, f->n, f->D, f->Dp, d_queries + (size_t)q0 * f->D, m,
-                                                 d_cand + (size_t)q0 * n_cand, n_cand, top_k, f->id_offset, map,
-                                                 (int64_t)f->h_map.size(), f->keys, f->flag, d_ids + (size_t)q0 * top_k,
-                                                 d_dists + (size_t)q0 * top_k, stream));
-        else
-            DPQ_HIP(dpq::launch_flat_rerank(metric, f->base, f->n, f->D, f->Dp, d_queries + (size_t)q0 * f->D, m,
-                                            d_cand + (size_t)q0 * n_cand, n_cand, top_k, f->id_offset, map,
-                                            (int64_t)f->h_map.size(), f->keys, f->flag, d_ids + (size_t)q0 * top_k,
-                                            d_dists + (size_t)q0 * top_k, stream));
+        r.queries = d_queries + (size_t)q0 * f->D;
+        r.nq = std::min(per, nq - q0);
+        r.cand = d_cand + (size_t)q0 * n_cand;
+        r.ids = d_ids + (size_t)q0 * top_k;
+        r.dists = d_dists + (size_t)q0 * top_k;
+        DPQ_HIP(dpq::launch_flat_rerank(base, r, stream));
     }
     uint32_t bad = 0;
     DPQ_HIP(hipMemcpyAsync(&bad, f->flag, sizeof bad, hipMemcpyDeviceToHost, stream));
@@ -66,15 +80,19 @@ int flat_rerank_on_device(const char* fn, int metric, dpq_flat* f, const Q* d_qu
 // handle of dpq_flat_open_u8, the _i8 functions one of dpq_flat_open_i8.  The message names the call of the same shape
 // that the handle does take.
 int flat_kind(const dpq_flat* f, const FlatCall& c) {
-    if (f->kind == c.kind) return DPQ_OK;
-    const std::string fn = c.name(), right = c.name(f->kind);
-    if (f->half)
-        return fail(DPQ_ERR_ARG, fn + ": the handle holds half-precision vectors (dpq_flat_open_half, "
-                                      "dpq_flat_open_narrowed), searched with fp32 queries; call " + right);
-    if (f->kind == kFlatKindF32) return fail(DPQ_ERR_ARG, fn + ": the handle holds fp32 vectors (dpq_flat_open); call " + right);
-    if (f->kind == kFlatKindI8)
-        return fail(DPQ_ERR_ARG, fn + ": the handle holds signed byte vectors (dpq_flat_open_i8); call " + right);
-    if (c.kind == kFlatKindF32 && c.metric == dpq::kFlatIP)
+    const int kind = dpq::flat_query_format(f->format);
+    if (kind == c.kind) return DPQ_OK;
+    const std::string fn = c.name(), right = c.name(kind);
+    switch (f->format) {
+        case dpq::kFlatF16:
+        case dpq::kFlatBF16:
+            return fail(DPQ_ERR_ARG, fn + ": the handle holds half-precision vectors (dpq_flat_open_half, "
+                                          "dpq_flat_open_narrowed), searched with fp32 queries; call " + right);
+        case dpq::kFlatF32: return fail(DPQ_ERR_ARG, fn + ": the handle holds fp32 vectors (dpq_flat_open); call " + right);
+        case dpq::kFlatI8:
+            return fail(DPQ_ERR_ARG, fn + ": the handle holds signed byte vectors (dpq_flat_open_i8); call " + right);
+    }
+    if (c.kind == dpq::kFlatF32 && c.metric == dpq::kFlatIP)
         return fail(DPQ_ERR_ARG, fn + ": the handle holds byte vectors (dpq_flat_open_u8), which have no inner-product search "
                                       "with fp32 queries; call " + right);
     return fail(DPQ_ERR_ARG, fn + ": the handle holds byte vectors (dpq_flat_open_u8); call " + right);
@@ -110,70 +128,54 @@ int flat_open_args(const char* fn, const void* vectors, int64_t n, int D, int de
     return DPQ_OK;
 }
 
-// dpq_flat_open_half (h16 given) and dpq_flat_open_narrowed (f32 given): the rows go up in slices of at most 128 MB and
-// are padded, or narrowed and padded, on the device.
-int flat_open_16(const char* fn, const uint16_t* h16, const float* f32, int64_t n, int D, int format, int device,
-                 int64_t id_offset, dpq_flat** out) {
-    if (int rc = flat_open_args(fn, h16 ? (const void*)h16 : (const void*)f32, n, D, device, id_offset, out, &format)) return rc;
+// Every dpq_flat_open*: n rows of D values, fp32 (from_fp32: dpq_flat_open, and dpq_flat_open_narrowed, which narrows
+// them) or already of `format`, become the handle's rows of `format`.  callers_format: `format` is an argument of the
+// call and is checked with the others.  The rows go up in slices of at most 128 MB through one staging buffer and are
+// padded (narrowed, biased) by the format's prepare kernel on the device; fp32 and 16-bit rows that need no padding go
+// straight to their place.
+int flat_open(const char* fn, int format, bool from_fp32, bool callers_format, const void* vectors, int64_t n, int D,
+              int device, int64_t id_offset, dpq_flat** out) {
+    if (int rc = flat_open_args(fn, vectors, n, D, device, id_offset, out, callers_format ? &format : nullptr)) return rc;
+    const bool bytes = dpq::flat_query_format(format) != dpq::kFlatF32;
+    const size_t elem = bytes ? 1 : format == dpq::kFlatF32 ? sizeof(float) : sizeof(uint16_t);  // of a stored value
+    const size_t in_elem = from_fp32 ? sizeof(float) : elem;                                     // of a value as given
     std::unique_ptr<dpq_flat> f(new dpq_flat);
     f->device = device;
     f->n = n;
     f->id_offset = id_offset;
     f->D = D;
-    f->Dp = dpq::flat_half_padded_d(D);
-    f->half = format;
-    int rc = f->base16.alloc((size_t)n * f->Dp);
-    if (rc) return fail(rc, std::string(fn) + ": the vectors do not fit into device memory (" + dpq_last_error() + ")");
-    if (h16 && f->Dp == D) {
-        DPQ_HIP(hipMemcpy(f->base16, h16, (size_t)n * D * sizeof(uint16_t), hipMemcpyHostToDevice));
-    } else {
-        const size_t elem = h16 ? sizeof(uint16_t) : sizeof(float);
-        const int64_t tile = std::max<int64_t>(1, ((int64_t)128 << 20) / ((int64_t)D * (int64_t)elem));  // rows per upload
-        DevBuf<uint8_t> tmp;
-        if ((rc = tmp.alloc((size_t)std::min(n, tile) * D * elem))) return rc;
-        for (int64_t r0 = 0; r0 < n; r0 += tile) {
-            const int64_t m = std::min(tile, n - r0);
-            uint16_t* dst = f->base16.get() + (size_t)r0 * f->Dp;
-            if (h16) {
-                DPQ_HIP(hipMemcpy(tmp, h16 + (size_t)r0 * D, (size_t)m * D * elem, hipMemcpyHostToDevice));
-                DPQ_HIP(dpq::launch_flat_half_prepare(reinterpret_cast<const uint16_t*>(tmp.get()), m, D, f->Dp, dst, nullptr));
-            } else {
-                DPQ_HIP(hipMemcpy(tmp, f32 + (size_t)r0 * D, (size_t)m * D * elem, hipMemcpyHostToDevice));
-                DPQ_HIP(dpq::launch_flat_half_narrow(reinterpret_cast<const float*>(tmp.get()), m, D, f->Dp, format, dst, nullptr));
-            }
-            DPQ_HIP(hipDeviceSynchronize());
-        }
-    }
-    *out = f.release();
-    return DPQ_OK;
-}
-
-// dpq_flat_open_u8 and dpq_flat_open_i8 (vectors then holds int8 values): the rows go up in slices of at most 128 MB and
-// are padded, and biased when unsigned, on the device.
-int flat_open_bytes(const char* fn, int kind, const uint8_t* vectors, int64_t n, int D, int device, int64_t id_offset,
-                    dpq_flat** out) {
-    if (int rc = flat_open_args(fn, vectors, n, D, device, id_offset, out)) return rc;
-    std::unique_ptr<dpq_flat> f(new dpq_flat);
-    f->device = device;
-    f->n = n;
-    f->id_offset = id_offset;
-    f->D = D;
-    f->Dp = dpq::flat_u8_padded_d(D);
-    f->kind = kind;
-    int rc = f->base8.alloc((size_t)n * f->Dp);
-    if (!rc) rc = f->norm8.alloc((size_t)((n + 3) & ~(int64_t)3));
+    f->Dp = bytes ? dpq::flat_u8_padded_d(D) : format == dpq::kFlatF32 ? dpq::flat_padded_d(D) : dpq::flat_half_padded_d(D);
+    f->format = format;
+    int rc = f->rows.alloc((size_t)n * f->Dp * elem);
+    if (!rc && bytes) rc = f->norm8.alloc((size_t)((n + 3) & ~(int64_t)3));
     if (rc) return fail(rc, std::string(fn) + ": the vectors do not fit into device memory (" + dpq_last_error() + ")");
     // the norm array's padding is read by the last stripe's 16-byte loads (and masked afterwards): keep it defined
-    DPQ_HIP(hipMemset(f->norm8.get() + ((n - 1) & ~(int64_t)3), 0, 4 * sizeof(int32_t)));
-    const int64_t tile = std::max<int64_t>(1, ((int64_t)128 << 20) / D);  // rows per upload (128 MB); biased on the device
-    DevBuf<uint8_t> tmp;
-    if ((rc = tmp.alloc((size_t)std::min(n, tile) * D))) return rc;
-    for (int64_t r0 = 0; r0 < n; r0 += tile) {
-        const int64_t m = std::min(tile, n - r0);
-        DPQ_HIP(hipMemcpy(tmp, vectors + (size_t)r0 * D, (size_t)m * D, hipMemcpyHostToDevice));
-        DPQ_HIP(dpq::launch_flat_u8_prepare(tmp, m, D, f->Dp, f->base8.get() + (size_t)r0 * f->Dp, f->norm8.get() + r0,
-                                            nullptr, kind == kFlatKindI8));
-        DPQ_HIP(hipDeviceSynchronize());
+    if (bytes) DPQ_HIP(hipMemset(f->norm8.get() + ((n - 1) & ~(int64_t)3), 0, 4 * sizeof(int32_t)));
+    if (!bytes && in_elem == elem && f->Dp == D) {
+        DPQ_HIP(hipMemcpy(f->rows, vectors, (size_t)n * D * elem, hipMemcpyHostToDevice));
+    } else {
+        const int64_t tile = std::max<int64_t>(1, ((int64_t)128 << 20) / ((int64_t)D * (int64_t)in_elem));  // rows per upload
+        DevBuf<uint8_t> tmp;
+        if ((rc = tmp.alloc((size_t)std::min(n, tile) * D * in_elem))) return rc;
+        for (int64_t r0 = 0; r0 < n; r0 += tile) {
+            const int64_t m = std::min(tile, n - r0);
+            const void* src = tmp.get();
+            void* dst = f->rows.get() + (size_t)r0 * f->Dp * elem;
+            DPQ_HIP(hipMemcpy(tmp, static_cast<const uint8_t*>(vectors) + (size_t)r0 * D * in_elem, (size_t)m * D * in_elem,
+                              hipMemcpyHostToDevice));
+            if (bytes)
+                DPQ_HIP(dpq::launch_flat_u8_prepare(tmp, m, D, f->Dp, static_cast<int8_t*>(dst), f->norm8.get() + r0, nullptr,
+                                                    format == dpq::kFlatI8));
+            else if (format == dpq::kFlatF32)
+                DPQ_HIP(dpq::launch_flat_pad_rows(static_cast<const float*>(src), m, D, f->Dp, static_cast<float*>(dst), nullptr));
+            else if (from_fp32)
+                DPQ_HIP(dpq::launch_flat_half_narrow(static_cast<const float*>(src), m, D, f->Dp, format,
+                                                     static_cast<uint16_t*>(dst), nullptr));
+            else
+                DPQ_HIP(dpq::launch_flat_half_prepare(static_cast<const uint16_t*>(src), m, D, f->Dp, static_cast<uint16_t*>(dst),
+                                                      nullptr));
+            DPQ_HIP(hipDeviceSynchronize());
+        }
     }
     *out = f.release();
     return DPQ_OK;
@@ -193,10 +195,10 @@ int grow_outputs(dpq_flat* f, size_t want) {
 template <class Q>
 int flat_stage_queries(dpq_flat* f, int metric, const Q* src, int m, std::vector<float>* padded) {
     const int D = f->D, Dp = f->Dp;
-    if constexpr (kind_of<Q> != kFlatKindF32) {
+    if constexpr (format_of<Q> != dpq::kFlatF32) {
         DPQ_HIP(hipMemcpy(f->q_raw, src, (size_t)m * D, hipMemcpyHostToDevice));
-        DPQ_HIP(dpq::launch_flat_u8_prepare(f->q_raw, m, D, Dp, f->q8, f->qnorm, nullptr, kind_of<Q> == kFlatKindI8));
-        if (kind_of<Q> == kFlatKindU8 && metric == dpq::kFlatIP)
+        DPQ_HIP(dpq::launch_flat_u8_prepare(f->q_raw, m, D, Dp, f->q8, f->qnorm, nullptr, format_of<Q> == dpq::kFlatI8));
+        if (format_of<Q> == dpq::kFlatU8 && metric == dpq::kFlatIP)
             DPQ_HIP(dpq::launch_flat_u8_sums(f->q8, m, Dp, 0, f->qsum, nullptr));
     } else {
         if (Dp != D) {
@@ -213,18 +215,18 @@ int flat_stage_queries(dpq_flat* f, int metric, const Q* src, int m, std::vector
 // correction terms, in one pass over the stored rows: 4 * n bytes, kept until dpq_flat_close.
 template <class Q>
 int flat_grow_queries(dpq_flat* f, int metric, size_t qb) {
-    if constexpr (kind_of<Q> != kFlatKindF32) {
+    if constexpr (format_of<Q> != dpq::kFlatF32) {
         int rc = grow(f->q_raw, &f->q_raw_n, qb * f->D);
         if (!rc) rc = grow(f->q8, &f->q8_n, qb * f->Dp);
         if (!rc) rc = grow(f->qnorm, &f->qnorm_n, qb);
-        if (kind_of<Q> == kFlatKindU8 && metric == dpq::kFlatIP) {
+        if (format_of<Q> == dpq::kFlatU8 && metric == dpq::kFlatIP) {
             if (!rc) rc = grow(f->qsum, &f->qsum_n, qb);
             if (!rc && !f->rsum8.get()) {
                 DevBuf<int32_t> sums;
                 if ((rc = sums.alloc((size_t)((f->n + 3) & ~(int64_t)3)))) return rc;
                 // the padding is read by the last stripe's 16-byte loads (and masked afterwards): keep it defined
                 DPQ_HIP(hipMemset(sums.get() + ((f->n - 1) & ~(int64_t)3), 0, 4 * sizeof(int32_t)));
-                DPQ_HIP(dpq::launch_flat_u8_sums(f->base8, f->n, f->Dp, 16384 * f->D, sums, nullptr));
+                DPQ_HIP(dpq::launch_flat_u8_sums(reinterpret_cast<const int8_t*>(f->rows.get()), f->n, f->Dp, 16384 * f->D, sums, nullptr));
                 DPQ_HIP(hipDeviceSynchronize());
                 f->rsum8 = std::move(sums);
             }
@@ -235,15 +237,9 @@ int flat_grow_queries(dpq_flat* f, int metric, size_t qb) {
     }
 }
 
-// The handle's rows, all of them or those a filter lists, and queries [a, a + m) of the staged batch, as the launchers
-// of dpq_flat.h take them.
-dpq::FlatBase flat_base(const dpq_flat* f, const dpq_flat_filter* ff, int metric) {
-    return {f->base, f->base8, f->norm8, f->Dp, f->id_offset, ff != nullptr, ff ? ff->list.get() : nullptr,
-            ff ? ff->n_allowed : f->n, metric, f->base16, f->half, f->kind == kFlatKindI8, f->rsum8};
-}
-
+// Queries [a, a + m) of the staged batch, as the launchers of dpq_flat.h take them.
 dpq::FlatQueries flat_queries(const dpq_flat* f, int a, int m) {
-    if (f->kind != kFlatKindF32)
+    if (dpq::flat_query_format(f->format) != dpq::kFlatF32)
         return {nullptr, f->q8.get() + (size_t)a * f->Dp, f->qnorm.get() + a, m, f->qsum.get() ? f->qsum.get() + a : nullptr};
     return {f->d_q.get() + (size_t)a * f->Dp, nullptr, nullptr, m};
 }
@@ -297,41 +293,19 @@ extern "C" {
 
 int dpq_flat_open(const float* vectors, int64_t n, int D, int device, int64_t id_offset, dpq_flat** out) {
     return guarded([&]() -> int {
-    if (int rc = flat_open_args("dpq_flat_open", vectors, n, D, device, id_offset, out)) return rc;
-    std::unique_ptr<dpq_flat> f(new dpq_flat);
-    f->device = device;
-    f->n = n;
-    f->id_offset = id_offset;
-    f->D = D;
-    f->Dp = dpq::flat_padded_d(D);
-    int rc = f->base.alloc((size_t)n * f->Dp);
-    if (rc) return fail(rc, std::string("dpq_flat_open: the vectors do not fit into device memory (") + dpq_last_error() + ")");
-    if (f->Dp == D) {
-        DPQ_HIP(hipMemcpy(f->base, vectors, (size_t)n * D * sizeof(float), hipMemcpyHostToDevice));
-    } else {
-        const int64_t tile = 1 << 18;  // rows per upload; padded on the device
-        DevBuf<float> tmp;
-        if ((rc = tmp.alloc((size_t)std::min(n, tile) * D))) return rc;
-        for (int64_t r0 = 0; r0 < n; r0 += tile) {
-            const int64_t m = std::min(tile, n - r0);
-            DPQ_HIP(hipMemcpy(tmp, vectors + (size_t)r0 * D, (size_t)m * D * sizeof(float), hipMemcpyHostToDevice));
-            DPQ_HIP(dpq::launch_flat_pad_rows(tmp, m, D, f->Dp, f->base.get() + (size_t)r0 * f->Dp, nullptr));
-            DPQ_HIP(hipDeviceSynchronize());
-        }
-    }
-    *out = f.release();
-    return DPQ_OK;
+    return flat_open("dpq_flat_open", dpq::kFlatF32, true, false, vectors, n, D, device, id_offset, out);
     });
 }
 
 int dpq_flat_open_u8(const uint8_t* vectors, int64_t n, int D, int device, int64_t id_offset, dpq_flat** out) {
-    return guarded([&]() -> int { return flat_open_bytes("dpq_flat_open_u8", kFlatKindU8, vectors, n, D, device, id_offset, out); });
+    return guarded([&]() -> int {
+    return flat_open("dpq_flat_open_u8", dpq::kFlatU8, false, false, vectors, n, D, device, id_offset, out);
+    });
 }
 
 int dpq_flat_open_i8(const int8_t* vectors, int64_t n, int D, int device, int64_t id_offset, dpq_flat** out) {
     return guarded([&]() -> int {
-    return flat_open_bytes("dpq_flat_open_i8", kFlatKindI8, reinterpret_cast<const uint8_t*>(vectors), n, D, device, id_offset,
-                           out);
+    return flat_open("dpq_flat_open_i8", dpq::kFlatI8, false, false, vectors, n, D, device, id_offset, out);
     });
 }
 
@@ -363,11 +337,15 @@ int dpq_half_to_float(const uint16_t* in, int64_t count, int format, float* out)
 }
 
 int dpq_flat_open_half(const uint16_t* vectors, int64_t n, int D, int format, int device, int64_t id_offset, dpq_flat** out) {
-    return guarded([&]() -> int { return flat_open_16("dpq_flat_open_half", vectors, nullptr, n, D, format, device, id_offset, out); });
+    return guarded([&]() -> int {
+    return flat_open("dpq_flat_open_half", format, false, true, vectors, n, D, device, id_offset, out);
+    });
 }
 
 int dpq_flat_open_narrowed(const float* vectors, int64_t n, int D, int format, int device, int64_t id_offset, dpq_flat** out) {
-    return guarded([&]() -> int { return flat_open_16("dpq_flat_open_narrowed", nullptr, vectors, n, D, format, device, id_offset, out); });
+    return guarded([&]() -> int {
+    return flat_open("dpq_flat_open_narrowed", format, true, true, vectors, n, D, device, id_offset, out);
+    });
 }
 
 int dpq_flat_close(dpq_flat* f) {
@@ -381,37 +359,37 @@ int dpq_flat_close(dpq_flat* f) {
 
 int dpq_flat_search(dpq_flat* f, const float* queries, int nq, int top_k, int32_t* ids, float* dists) {
     return guarded([&]() -> int {
-    return flat_search_call({"dpq_flat_search", dpq::kFlatL2, kFlatKindF32}, f, queries, nq, top_k, ids, dists);
+    return flat_search_call({"dpq_flat_search", dpq::kFlatL2, dpq::kFlatF32}, f, queries, nq, top_k, ids, dists);
     });
 }
 
 int dpq_flat_search_ip(dpq_flat* f, const float* queries, int nq, int top_k, int32_t* ids, float* scores) {
     return guarded([&]() -> int {
-    return flat_search_call({"dpq_flat_search", dpq::kFlatIP, kFlatKindF32}, f, queries, nq, top_k, ids, scores);
+    return flat_search_call({"dpq_flat_search", dpq::kFlatIP, dpq::kFlatF32}, f, queries, nq, top_k, ids, scores);
     });
 }
 
 int dpq_flat_search_u8(dpq_flat* f, const uint8_t* queries, int nq, int top_k, int32_t* ids, float* dists) {
     return guarded([&]() -> int {
-    return flat_search_call({"dpq_flat_search", dpq::kFlatL2, kFlatKindU8}, f, queries, nq, top_k, ids, dists);
+    return flat_search_call({"dpq_flat_search", dpq::kFlatL2, dpq::kFlatU8}, f, queries, nq, top_k, ids, dists);
     });
 }
 
 int dpq_flat_search_ip_u8(dpq_flat* f, const uint8_t* queries, int nq, int top_k, int32_t* ids, float* scores) {
     return guarded([&]() -> int {
-    return flat_search_call({"dpq_flat_search", dpq::kFlatIP, kFlatKindU8}, f, queries, nq, top_k, ids, scores);
+    return flat_search_call({"dpq_flat_search", dpq::kFlatIP, dpq::kFlatU8}, f, queries, nq, top_k, ids, scores);
     });
 }
 
 int dpq_flat_search_i8(dpq_flat* f, const int8_t* queries, int nq, int top_k, int32_t* ids, float* dists) {
     return guarded([&]() -> int {
-    return flat_search_call({"dpq_flat_search", dpq::kFlatL2, kFlatKindI8}, f, queries, nq, top_k, ids, dists);
+    return flat_search_call({"dpq_flat_search", dpq::kFlatL2, dpq::kFlatI8}, f, queries, nq, top_k, ids, dists);
     });
 }
 
 int dpq_flat_search_ip_i8(dpq_flat* f, const int8_t* queries, int nq, int top_k, int32_t* ids, float* scores) {
     return guarded([&]() -> int {
-    return flat_search_call({"dpq_flat_search", dpq::kFlatIP, kFlatKindI8}, f, queries, nq, top_k, ids, scores);
+    return flat_search_call({"dpq_flat_search", dpq::kFlatIP, dpq::kFlatI8}, f, queries, nq, top_k, ids, scores);
     });
 }
 
@@ -651,84 +629,84 @@ int dpq_flat_filter_count(const dpq_flat_filter* ff, int64_t* n_allowed) {
 int dpq_flat_search_filtered(dpq_flat* f, const dpq_flat_filter* ff, const float* queries, int nq, int top_k, int32_t* ids,
                              float* dists) {
     return guarded([&]() -> int {
-    return flat_search_filtered_call({"dpq_flat_search_filtered", dpq::kFlatL2, kFlatKindF32}, f, ff, queries, nq, top_k, ids, dists);
+    return flat_search_filtered_call({"dpq_flat_search_filtered", dpq::kFlatL2, dpq::kFlatF32}, f, ff, queries, nq, top_k, ids, dists);
     });
 }
 
 int dpq_flat_search_filtered_u8(dpq_flat* f, const dpq_flat_filter* ff, const uint8_t* queries, int nq, int top_k, int32_t* ids,
                                 float* dists) {
     return guarded([&]() -> int {
-    return flat_search_filtered_call({"dpq_flat_search_filtered", dpq::kFlatL2, kFlatKindU8}, f, ff, queries, nq, top_k, ids, dists);
+    return flat_search_filtered_call({"dpq_flat_search_filtered", dpq::kFlatL2, dpq::kFlatU8}, f, ff, queries, nq, top_k, ids, dists);
     });
 }
 
 int dpq_flat_search_filtered_i8(dpq_flat* f, const dpq_flat_filter* ff, const int8_t* queries, int nq, int top_k, int32_t* ids,
                                 float* dists) {
     return guarded([&]() -> int {
-    return flat_search_filtered_call({"dpq_flat_search_filtered", dpq::kFlatL2, kFlatKindI8}, f, ff, queries, nq, top_k, ids, dists);
+    return flat_search_filtered_call({"dpq_flat_search_filtered", dpq::kFlatL2, dpq::kFlatI8}, f, ff, queries, nq, top_k, ids, dists);
     });
 }
 
 int dpq_flat_search_filtered_ip(dpq_flat* f, const dpq_flat_filter* ff, const float* queries, int nq, int top_k, int32_t* ids,
                                 float* scores) {
     return guarded([&]() -> int {
-    return flat_search_filtered_call({"dpq_flat_search_filtered", dpq::kFlatIP, kFlatKindF32}, f, ff, queries, nq, top_k, ids, scores);
+    return flat_search_filtered_call({"dpq_flat_search_filtered", dpq::kFlatIP, dpq::kFlatF32}, f, ff, queries, nq, top_k, ids, scores);
     });
 }
 
 int dpq_flat_search_filtered_ip_u8(dpq_flat* f, const dpq_flat_filter* ff, const uint8_t* queries, int nq, int top_k, int32_t* ids,
                                    float* scores) {
     return guarded([&]() -> int {
-    return flat_search_filtered_call({"dpq_flat_search_filtered", dpq::kFlatIP, kFlatKindU8}, f, ff, queries, nq, top_k, ids, scores);
+    return flat_search_filtered_call({"dpq_flat_search_filtered", dpq::kFlatIP, dpq::kFlatU8}, f, ff, queries, nq, top_k, ids, scores);
     });
 }
 
 int dpq_flat_search_filtered_ip_i8(dpq_flat* f, const dpq_flat_filter* ff, const int8_t* queries, int nq, int top_k, int32_t* ids,
                                    float* scores) {
     return guarded([&]() -> int {
-    return flat_search_filtered_call({"dpq_flat_search_filtered", dpq::kFlatIP, kFlatKindI8}, f, ff, queries, nq, top_k, ids, scores);
+    return flat_search_filtered_call({"dpq_flat_search_filtered", dpq::kFlatIP, dpq::kFlatI8}, f, ff, queries, nq, top_k, ids, scores);
     });
 }
 
 int dpq_flat_range_search(dpq_flat* f, const dpq_flat_filter* ff, const float* queries, int nq, const float* radii,
                           dpq_range_result** out) {
     return guarded([&]() -> int {
-    return flat_range_call({"dpq_flat_range_search", dpq::kFlatL2, kFlatKindF32}, f, ff, queries, nq, radii, out);
+    return flat_range_call({"dpq_flat_range_search", dpq::kFlatL2, dpq::kFlatF32}, f, ff, queries, nq, radii, out);
     });
 }
 
 int dpq_flat_range_search_u8(dpq_flat* f, const dpq_flat_filter* ff, const uint8_t* queries, int nq, const float* radii,
                              dpq_range_result** out) {
     return guarded([&]() -> int {
-    return flat_range_call({"dpq_flat_range_search", dpq::kFlatL2, kFlatKindU8}, f, ff, queries, nq, radii, out);
+    return flat_range_call({"dpq_flat_range_search", dpq::kFlatL2, dpq::kFlatU8}, f, ff, queries, nq, radii, out);
     });
 }
 
 int dpq_flat_range_search_i8(dpq_flat* f, const dpq_flat_filter* ff, const int8_t* queries, int nq, const float* radii,
                              dpq_range_result** out) {
     return guarded([&]() -> int {
-    return flat_range_call({"dpq_flat_range_search", dpq::kFlatL2, kFlatKindI8}, f, ff, queries, nq, radii, out);
+    return flat_range_call({"dpq_flat_range_search", dpq::kFlatL2, dpq::kFlatI8}, f, ff, queries, nq, radii, out);
     });
 }
 
 int dpq_flat_range_search_ip(dpq_flat* f, const dpq_flat_filter* ff, const float* queries, int nq, const float* thresholds,
                              dpq_range_result** out) {
     return guarded([&]() -> int {
-    return flat_range_call({"dpq_flat_range_search", dpq::kFlatIP, kFlatKindF32}, f, ff, queries, nq, thresholds, out);
+    return flat_range_call({"dpq_flat_range_search", dpq::kFlatIP, dpq::kFlatF32}, f, ff, queries, nq, thresholds, out);
     });
 }
 
 int dpq_flat_range_search_ip_u8(dpq_flat* f, const dpq_flat_filter* ff, const uint8_t* queries, int nq, const float* thresholds,
                                 dpq_range_result** out) {
     return guarded([&]() -> int {
-    return flat_range_call({"dpq_flat_range_search", dpq::kFlatIP, kFlatKindU8}, f, ff, queries, nq, thresholds, out);
+    return flat_range_call({"dpq_flat_range_search", dpq::kFlatIP, dpq::kFlatU8}, f, ff, queries, nq, thresholds, out);
     });
 }
 
 int dpq_flat_range_search_ip_i8(dpq_flat* f, const dpq_flat_filter* ff, const int8_t* queries, int nq, const float* thresholds,
                                 dpq_range_result** out) {
     return guarded([&]() -> int {
-    return flat_range_call({"dpq_flat_range_search", dpq::kFlatIP, kFlatKindI8}, f, ff, queries, nq, thresholds, out);
+    return flat_range_call({"dpq_flat_range_search", dpq::kFlatIP, dpq::kFlatI8}, f, ff, queries, nq, thresholds, out);
     });
 }
 
@@ -752,7 +730,7 @@ int flat_rerank_device_call(const FlatCall& c, dpq_flat* f, const Q* d_queries, 
 template <class Q>
 int flat_rerank_host_call(const FlatCall& c, dpq_flat* f, const Q* queries, int nq, const int32_t* cand_ids, int n_cand,
                           int top_k, int32_t* ids, float* dists) {
-    constexpr bool bytes = kind_of<Q> != kFlatKindF32;
+    constexpr bool bytes = format_of<Q> != dpq::kFlatF32;
     const std::string who = c.name();
     const char* fn = who.c_str();
     int rc = flat_rerank_args(c, f, queries, nq, cand_ids, n_cand, top_k, ids, dists);
@@ -796,14 +774,14 @@ extern "C" {
 int dpq_flat_rerank(dpq_flat* f, const float* queries, int nq, const int32_t* cand_ids, int n_cand, int top_k,
                     int32_t* ids, float* dists) {
     return guarded([&]() -> int {
-    return flat_rerank_host_call({"dpq_flat_rerank", dpq::kFlatL2, kFlatKindF32}, f, queries, nq, cand_ids, n_cand, top_k, ids, dists);
+    return flat_rerank_host_call({"dpq_flat_rerank", dpq::kFlatL2, dpq::kFlatF32}, f, queries, nq, cand_ids, n_cand, top_k, ids, dists);
     });
 }
 
 int dpq_flat_rerank_device(dpq_flat* f, const float* d_queries, int nq, const int32_t* d_cand_ids, int n_cand,
                            int top_k, int32_t* d_ids, float* d_dists, void* hip_stream) {
     return guarded([&]() -> int {
-    return flat_rerank_device_call({"dpq_flat_rerank", dpq::kFlatL2, kFlatKindF32, true}, f, d_queries, nq, d_cand_ids, n_cand, top_k, d_ids,
+    return flat_rerank_device_call({"dpq_flat_rerank", dpq::kFlatL2, dpq::kFlatF32, true}, f, d_queries, nq, d_cand_ids, n_cand, top_k, d_ids,
                                    d_dists, hip_stream);
     });
 }
@@ -811,14 +789,14 @@ int dpq_flat_rerank_device(dpq_flat* f, const float* d_queries, int nq, const in
 int dpq_flat_rerank_u8(dpq_flat* f, const uint8_t* queries, int nq, const int32_t* cand_ids, int n_cand, int top_k,
                        int32_t* ids, float* dists) {
     return guarded([&]() -> int {
-    return flat_rerank_host_call({"dpq_flat_rerank", dpq::kFlatL2, kFlatKindU8}, f, queries, nq, cand_ids, n_cand, top_k, ids, dists);
+    return flat_rerank_host_call({"dpq_flat_rerank", dpq::kFlatL2, dpq::kFlatU8}, f, queries, nq, cand_ids, n_cand, top_k, ids, dists);
     });
 }
 
 int dpq_flat_rerank_u8_device(dpq_flat* f, const uint8_t* d_queries, int nq, const int32_t* d_cand_ids, int n_cand,
                               int top_k, int32_t* d_ids, float* d_dists, void* hip_stream) {
     return guarded([&]() -> int {
-    return flat_rerank_device_call({"dpq_flat_rerank", dpq::kFlatL2, kFlatKindU8, true}, f, d_queries, nq, d_cand_ids, n_cand, top_k, d_ids,
+    return flat_rerank_device_call({"dpq_flat_rerank", dpq::kFlatL2, dpq::kFlatU8, true}, f, d_queries, nq, d_cand_ids, n_cand, top_k, d_ids,
                                    d_dists, hip_stream);
     });
 }
@@ -826,14 +804,14 @@ int dpq_flat_rerank_u8_device(dpq_flat* f, const uint8_t* d_queries, int nq, con
 int dpq_flat_rerank_i8(dpq_flat* f, const int8_t* queries, int nq, const int32_t* cand_ids, int n_cand, int top_k,
                        int32_t* ids, float* dists) {
     return guarded([&]() -> int {
-    return flat_rerank_host_call({"dpq_flat_rerank", dpq::kFlatL2, kFlatKindI8}, f, queries, nq, cand_ids, n_cand, top_k, ids, dists);
+    return flat_rerank_host_call({"dpq_flat_rerank", dpq::kFlatL2, dpq::kFlatI8}, f, queries, nq, cand_ids, n_cand, top_k, ids, dists);
     });
 }
 
 int dpq_flat_rerank_i8_device(dpq_flat* f, const int8_t* d_queries, int nq, const int32_t* d_cand_ids, int n_cand,
                               int top_k, int32_t* d_ids, float* d_dists, void* hip_stream) {
     return guarded([&]() -> int {
-    return flat_rerank_device_call({"dpq_flat_rerank", dpq::kFlatL2, kFlatKindI8, true}, f, d_queries, nq, d_cand_ids, n_cand, top_k, d_ids,
+    return flat_rerank_device_call({"dpq_flat_rerank", dpq::kFlatL2, dpq::kFlatI8, true}, f, d_queries, nq, d_cand_ids, n_cand, top_k, d_ids,
                                    d_dists, hip_stream);
     });
 }
@@ -841,14 +819,14 @@ int dpq_flat_rerank_i8_device(dpq_flat* f, const int8_t* d_queries, int nq, cons
 int dpq_flat_rerank_ip(dpq_flat* f, const float* queries, int nq, const int32_t* cand_ids, int n_cand, int top_k,
                        int32_t* ids, float* scores) {
     return guarded([&]() -> int {
-    return flat_rerank_host_call({"dpq_flat_rerank", dpq::kFlatIP, kFlatKindF32}, f, queries, nq, cand_ids, n_cand, top_k, ids, scores);
+    return flat_rerank_host_call({"dpq_flat_rerank", dpq::kFlatIP, dpq::kFlatF32}, f, queries, nq, cand_ids, n_cand, top_k, ids, scores);
     });
 }
 
 int dpq_flat_rerank_ip_device(dpq_flat* f, const float* d_queries, int nq, const int32_t* d_cand_ids, int n_cand,
                               int top_k, int32_t* d_ids, float* d_scores, void* hip_stream) {
     return guarded([&]() -> int {
-    return flat_rerank_device_call({"dpq_flat_rerank", dpq::kFlatIP, kFlatKindF32, true}, f, d_queries, nq, d_cand_ids, n_cand, top_k, d_ids,
+    return flat_rerank_device_call({"dpq_flat_rerank", dpq::kFlatIP, dpq::kFlatF32, true}, f, d_queries, nq, d_cand_ids, n_cand, top_k, d_ids,
                                    d_scores, hip_stream);
     });
 }
@@ -856,14 +834,14 @@ int dpq_flat_rerank_ip_device(dpq_flat* f, const float* d_queries, int nq, const
 int dpq_flat_rerank_ip_u8(dpq_flat* f, const uint8_t* queries, int nq, const int32_t* cand_ids, int n_cand, int top_k,
                           int32_t* ids, float* scores) {
     return guarded([&]() -> int {
-    return flat_rerank_host_call({"dpq_flat_rerank", dpq::kFlatIP, kFlatKindU8}, f, queries, nq, cand_ids, n_cand, top_k, ids, scores);
+    return flat_rerank_host_call({"dpq_flat_rerank", dpq::kFlatIP, dpq::kFlatU8}, f, queries, nq, cand_ids, n_cand, top_k, ids, scores);
     });
 }
 
 int dpq_flat_rerank_ip_u8_device(dpq_flat* f, const uint8_t* d_queries, int nq, const int32_t* d_cand_ids, int n_cand,
                                  int top_k, int32_t* d_ids, float* d_scores, void* hip_stream) {
     return guarded([&]() -> int {
-    return flat_rerank_device_call({"dpq_flat_rerank", dpq::kFlatIP, kFlatKindU8, true}, f, d_queries, nq, d_cand_ids, n_cand, top_k, d_ids,
+    return flat_rerank_device_call({"dpq_flat_rerank", dpq::kFlatIP, dpq::kFlatU8, true}, f, d_queries, nq, d_cand_ids, n_cand, top_k, d_ids,
                                    d_scores, hip_stream);
     });
 }
@@ -871,14 +849,14 @@ int dpq_flat_rerank_ip_u8_device(dpq_flat* f, const uint8_t* d_queries, int nq, 
 int dpq_flat_rerank_ip_i8(dpq_flat* f, const int8_t* queries, int nq, const int32_t* cand_ids, int n_cand, int top_k,
                           int32_t* ids, float* scores) {
     return guarded([&]() -> int {
-    return flat_rerank_host_call({"dpq_flat_rerank", dpq::kFlatIP, kFlatKindI8}, f, queries, nq, cand_ids, n_cand, top_k, ids, scores);
+    return flat_rerank_host_call({"dpq_flat_rerank", dpq::kFlatIP, dpq::kFlatI8}, f, queries, nq, cand_ids, n_cand, top_k, ids, scores);
     });
 }
 
 int dpq_flat_rerank_ip_i8_device(dpq_flat* f, const int8_t* d_queries, int nq, const int32_t* d_cand_ids, int n_cand,
                                  int top_k, int32_t* d_ids, float* d_scores, void* hip_stream) {
     return guarded([&]() -> int {
-    return flat_rerank_device_call({"dpq_flat_rerank", dpq::kFlatIP, kFlatKindI8, true}, f, d_queries, nq, d_cand_ids, n_cand, top_k, d_ids,
+    return flat_rerank_device_call({"dpq_flat_rerank", dpq::kFlatIP, dpq::kFlatI8, true}, f, d_queries, nq, d_cand_ids, n_cand, top_k, d_ids,
                                    d_scores, hip_stream);
     });
 }

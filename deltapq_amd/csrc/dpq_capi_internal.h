@@ -150,20 +150,16 @@ inline uint64_t next_flat_serial() {
     return next++;
 }
 
-// Raw vectors resident on one GPU (exact search).  An fp32 handle (dpq_flat.hip) stores rows padded to Dp floats; a byte
-// handle (dpq_flat_u8.hip) stores them biased to int8 and padded to Dp bytes, with an int32 norm per row.
-enum { kFlatKindF32 = 0, kFlatKindU8 = 1, kFlatKindI8 = 2 };  // dpq_flat::kind; a half handle is kFlatKindF32 with `half` set
-
+// Raw vectors resident on one GPU (exact search): rows of `format` padded to Dp values (dpq_flat.h: fp32, fp16 / bf16, or
+// bytes stored as int8 with an int32 norm per row).  A handle takes the calls whose queries are of
+// dpq::flat_query_format(format).
 struct dpq_flat {
     int device = 0;
     int64_t n = 0, id_offset = 0;
     int D = 0, Dp = 0;
-    int kind = kFlatKindF32;      // what the open call stored: fp32 or half rows, bytes (dpq_flat_open_u8), int8 (_i8)
-    int half = 0;                 // opened by dpq_flat_open_half / _narrowed: DPQ_HALF_F16 or DPQ_HALF_BF16
-    DevBuf<float> base;           // [n][Dp]
-    DevBuf<uint16_t> base16;      // [n][Dp] (half handle)
-    DevBuf<int8_t> base8;         // [n][Dp] (byte handle)
-    DevBuf<int32_t> norm8;        // [n rounded up to 4]
+    int format = dpq::kFlatF32;   // what the open call stored: dpq::kFlatF32 .. kFlatI8
+    DevBuf<uint8_t> rows;         // [n][Dp] values of `format`
+    DevBuf<int32_t> norm8;        // [n rounded up to 4] a byte handle's row norms
     DevBuf<int32_t> rsum8;        // [n rounded up to 4] a u8 handle's row terms of the inner product: made by its first
                                   // inner-product search or range call, kept until dpq_flat_close
     DevBuf<uint32_t> map;         // DFS position -> row (dpq_flat_set_id_map)

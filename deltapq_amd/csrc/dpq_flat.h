@@ -1,14 +1,13 @@
-// dpq_flat.h -- exact search over raw vectors on the GPU, by squared L2 or by inner product: fp32 (dpq_flat.hip),
-// fp16 / bf16 widened exactly to fp32 (dpq_flat_half.hip) and bytes, unsigned or signed, on the int8 matrix cores
-// (dpq_flat_u8.hip); top-k over a whole base or over the rows a filter lists, range search, re-ranking over a candidate
-// list per query.  The arithmetic is the reference's brute force (main.cpp:150-156), restated in include/deltapq_amd.h
-// and DESIGN.md 5.10.  Each element type has one distance kernel template <LIST, MODE> in its own file; one stripe
-// driver (launch_flat_search) and one range pass (launch_flat_range_pass) serve every type, with and without a filter.
-// What the kernels of the three files share -- the modes, the key sink, the padding key, and for the fp32-query kernels
-// the step of the sum and the key -- is defined here, once.
-// The metric is a compile-time parameter of every distance kernel beside <LIST, MODE>; it reaches them through
-// FlatBase::metric and the metric argument of launch_flat_rerank*, so the drivers stay one of each kind.  The byte
-// kernels take the signedness of the rows the same way (FlatBase::i8_signed).
+// dpq_flat.h -- exact search over raw vectors on the GPU, by squared L2 or by inner product: fp32 rows and fp16 / bf16
+// rows widened exactly to fp32, both under fp32 queries (dpq_flat.hip), and bytes, unsigned or signed, on the int8 matrix
+// cores (dpq_flat_u8.hip); top-k over a whole base or over the rows a filter lists, range search, re-ranking over a
+// candidate list per query.  The arithmetic is the reference's brute force (main.cpp:150-156), restated in
+// include/deltapq_amd.h and DESIGN.md 5.10.  A base says what its rows are once, in FlatBase::format.  The fp32-query
+// formats share one distance kernel template <LIST, MODE, METRIC, FORMAT> and one re-rank kernel <METRIC, FORMAT>; the
+// bytes have their own pair.  One stripe driver (launch_flat_search), one range pass (launch_flat_range_pass) and one
+// re-rank launcher (launch_flat_rerank) serve every format, with and without a filter; the metric reaches the kernels
+// through FlatBase::metric.  What the kernels of the two files share -- the modes, the key sink, the padding key, the
+// row a candidate names, and for the fp32-query kernels the step of the sum and the key -- is defined here, once.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -23,6 +22,10 @@ constexpr int kFlatMaxD = 2048;
 // The metric of a kernel.  kFlatL2: the key's high word is the bits of the (non-negative) distance.  kFlatIP: the
 // score's bits mapped so that ascending keys are descending scores (flat_ip_word below).
 enum { kFlatL2 = 0, kFlatIP = 1 };
+// What the rows of a base are stored as.  kFlatF16 / kFlatBF16 are DPQ_HALF_F16 / DPQ_HALF_BF16.
+enum { kFlatF32 = 0, kFlatF16 = 1, kFlatBF16 = 2, kFlatU8 = 3, kFlatI8 = 4 };
+// The format of the queries a base of this format takes: fp32 for fp32 and half rows, the rows' own for bytes.
+inline int flat_query_format(int format) { return format == kFlatF16 || format == kFlatBF16 ? kFlatF32 : format; }
 // Score bits <-> high word of an inner-product key; the map is its own inverse.  -0.0 is read as +0.0 first.  A
 // non-negative score u becomes ~u & 0x7fffffff (larger scores, smaller words), a negative one keeps its bits (sign set,
 // larger magnitudes later): +inf 0x007fffff < 1.0 < +0.0 0x7fffffff < -1e-40 < -1.0 < -inf 0xff800000 < kFlatNoKey's.
@@ -52,6 +55,25 @@ __device__ __forceinline__ void accumulate(double& acc, float v, float q) {
         acc += (double)s;
     }
 }
+
+// The row a re-rank candidate c names, or -1.  A negative candidate is padding.  With a map (n_map entries) c is a DFS
+// position and the row map[c]; without one the row is c - id_offset.  *flag is set when c >= 0 names no row of the n.
+__device__ __forceinline__ int flat_candidate_row(int32_t c, int64_t n, int64_t id_offset, const uint32_t* map, int64_t n_map,
+                                                  uint32_t* flag) {
+    int row = -1;
+    if (c >= 0) {
+        if (map) {
+            int64_t p = c;
+            if ((n_map & 1) == 0 && p == n_map) p = n_map - 1;  // the even-N id of the last DFS node
+            if (p < n_map && (int64_t)map[p] < n) row = (int)map[p];
+        } else {
+            const int64_t r = (int64_t)c - id_offset;
+            if (r >= 0 && r < n) row = (int)r;
+        }
+        if (row < 0) *flag = 1;
+    }
+    return row;
+}
 #endif
 
 // Per-query selection state of a search.  overflow: an append fell outside the key buffer (the launcher's striping
@@ -69,25 +91,24 @@ int flat_key_capacity(int top_k);
 // Queries one search pass takes (their key buffers together stay within 64 MB).
 int flat_query_batch(int top_k);
 
-// ---- what a search or a range pass runs over ---------------------------------------------------------------------------
-// A prepared base: fp32 rows [n][Dp] padded with zeros (f32), or biased int8 rows [n][Dp] with their int32 norms (i8,
-// norm; see "byte vectors" below) -- exactly one of f32 / i8 is set.  The entries a pass visits are rows
-// 0 .. n_entries - 1, or, with `filtered`, rows list[0 .. n_entries - 1] (ascending).  `filtered`, not the list pointer,
-// says which: an empty filter has n_entries == 0 and may have a NULL list.  Reported id = row + id_offset.
+// ---- what a search, a range pass or a re-rank runs over ----------------------------------------------------------------
+// A prepared base: rows [n][Dp] of `format`, padded with zeros -- fp32 to a multiple of four values, halves to a multiple
+// of eight, bytes (biased int8 for kFlatU8, see "byte vectors" below) to the K step of the MFMA, with their int32 norms.
+// The entries a pass visits are rows 0 .. n_entries - 1, or, with `filtered`, rows list[0 .. n_entries - 1] (ascending).
+// `filtered`, not the list pointer, says which: an empty filter has n_entries == 0 and may have a NULL list.
+// Reported id = row + id_offset.
 struct FlatBase {
-    const float* f32;
-    const int8_t* i8;
-    const int32_t* norm;
-    int Dp;
-    int64_t id_offset;
-    bool filtered;
-    const uint32_t* list;
-    int64_t n_entries;
+    int format = kFlatF32;
+    const void* rows = nullptr;
+    int64_t n = 0;
+    int D = 0, Dp = 0;
+    int64_t id_offset = 0;
     int metric = kFlatL2;
-    const uint16_t* h16 = nullptr;  // a half base (dpq_flat_half.hip): 16-bit rows [n][Dp], Dp a multiple of 8; f32 and
-    int half_format = 0;            // i8 are then NULL.  kFlatF16 or kFlatBF16.  Its queries are fp32, padded to its Dp.
-    bool i8_signed = false;         // a byte base: the rows are the caller's int8 values, not bytes biased by 128
-    const int32_t* rsum = nullptr;  // an unsigned byte base under kFlatIP: the rows' correction terms, padded as norm is
+    const int32_t* norm = nullptr;  // a byte base: the rows' norms, allocated rounded up to four rows
+    const int32_t* rsum = nullptr;  // a kFlatU8 base under kFlatIP: the rows' correction terms, padded as norm is
+    bool filtered = false;
+    const uint32_t* list = nullptr;
+    int64_t n_entries = 0;
 };
 // Prepared queries of the base's kind: [nq][Dp] padded rows, with norms for bytes (and, for the inner product over an
 // unsigned byte base, the queries' correction terms).
@@ -122,15 +143,26 @@ __device__ __forceinline__ uint64_t* flat_sink_of(uint64_t* keys, int cap, const
 hipError_t launch_flat_search(const FlatBase& b, const FlatQueries& q, int top_k, uint64_t* d_keys, FlatQueryState* d_state,
                               int32_t* d_ids, float* d_dists, hipStream_t stream);
 
-// Exact distances of cand[nq][n_cand] only, best top_k by (distance, reported id).  d_map (may be NULL) [n_map]: a
-// candidate is a DFS position, row = map[c], with the even-N rule; without it row = c - id_offset.  d_queries [nq][D]
-// unpadded.  d_keys [nq][n_cand rounded up to a power of two].  *d_flag is set when a candidate names no row.
-// metric kFlatIP: exact scores, best top_k by (score descending, reported id).
-hipError_t launch_flat_rerank(int metric, const float* d_base, int64_t n, int D, int Dp, const float* d_queries, int nq,
-                              const int32_t* d_cand, int n_cand, int top_k, int64_t id_offset, const uint32_t* d_map,
-                              int64_t n_map, uint64_t* d_keys, uint32_t* d_flag, int32_t* d_ids, float* d_dists,
-                              hipStream_t stream);
-size_t flat_rerank_keys(int n_cand);  // keys per query launch_flat_rerank needs
+// A re-rank: exact distances of cand[nq][n_cand] only, best top_k by (distance, reported id), all device pointers.
+// queries: the caller's [nq][D], unpadded, of flat_query_format(the base's format).  map (may be NULL) [n_map]: a
+// candidate is a DFS position, row = map[c], with the even-N rule; without it row = c - id_offset.
+// keys [nq][flat_rerank_keys(n_cand)].  *flag is set when a candidate names no row.  kFlatIP: exact scores, best top_k by
+// (score descending, reported id).
+struct FlatRerank {
+    const void* queries = nullptr;
+    int nq = 0;
+    const int32_t* cand = nullptr;
+    int n_cand = 0;
+    int top_k = 0;
+    const uint32_t* map = nullptr;
+    int64_t n_map = 0;
+    uint64_t* keys = nullptr;
+    uint32_t* flag = nullptr;
+    int32_t* ids = nullptr;
+    float* dists = nullptr;
+};
+hipError_t launch_flat_rerank(const FlatBase& b, const FlatRerank& r, hipStream_t stream);
+size_t flat_rerank_keys(int n_cand);  // keys per query launch_flat_rerank needs: n_cand rounded up to a power of two
 
 // [rows][D] -> [rows][Dp] with zero padding, on the device.
 hipError_t launch_flat_pad_rows(const float* d_in, int64_t rows, int D, int Dp, float* d_out, hipStream_t stream);
@@ -154,21 +186,19 @@ hipError_t launch_flat_u8_prepare(const uint8_t* d_in, int64_t rows, int D, int 
 // d_sums[r] = 128 * (the sum of prepared row r) + add: the rows' terms with add = 16384 * D, the queries' with add = 0.
 hipError_t launch_flat_u8_sums(const int8_t* d_rows8, int64_t rows, int Dp, int add, int32_t* d_sums, hipStream_t stream);
 // The distance stage of launch_flat_search / launch_flat_range_pass on a byte base: one launch of the byte kernel's
-// (b.filtered, mode, b.metric, b.i8_signed) instantiation over entries e0 .. e0 + rows - 1.  keys / cap / offs: the mode's
+// (b.filtered, mode, b.metric, signed rows) instantiation over entries e0 .. e0 + rows - 1.  keys / cap / offs: the mode's
 // sink, as above.  kFlatIP on an unsigned base needs b.rsum and q.sum.
 hipError_t launch_flat_dist_u8(int mode, const FlatBase& b, int64_t e0, int rows, const FlatQueries& q, uint64_t* keys,
                                int cap, const int64_t* offs, FlatQueryState* state, hipStream_t stream);
-// launch_flat_rerank over a prepared base; d_queries are the caller's bytes [nq][D] (int8 values when is_signed), unpadded.
-hipError_t launch_flat_rerank_u8(int metric, bool is_signed, const int8_t* d_base, int64_t n, int D, int Dp,
-                                 const uint8_t* d_queries, int nq, const int32_t* d_cand, int n_cand, int top_k,
-                                 int64_t id_offset, const uint32_t* d_map, int64_t n_map, uint64_t* d_keys, uint32_t* d_flag,
-                                 int32_t* d_ids, float* d_dists, hipStream_t stream);
+// The distance stage of launch_flat_rerank on a byte base: one launch of the byte re-rank kernel's (b.metric, signed)
+// instantiation over r.nq <= 65535 queries (the grid's y extent); r.queries are the caller's bytes (int8 values on a
+// kFlatI8 base).  n_pad: flat_rerank_keys(r.n_cand), the stride of r.keys.
+void launch_flat_rerank_chunk_u8(const FlatBase& b, const FlatRerank& r, int n_pad, hipStream_t stream);
 
-// ---- half-precision vectors, fp16 and bf16 (dpq_flat_half.hip) -------------------------------------------------------
+// ---- half-precision vectors, fp16 and bf16 (dpq_flat.hip: the fp32 kernels' FORMAT) ----------------------------------
 // Rows are stored as they are given, 16 bits per value, padded with zeros to a multiple of eight values (16-byte loads).
-// The kernels widen a value to fp32, which is exact, and from there on are the fp32 kernels: an answer over a half base
-// is, bit for bit, the answer of the fp32 code over the widened rows.  Queries are fp32 throughout.
-enum { kFlatF16 = 1, kFlatBF16 = 2 };  // DPQ_HALF_F16, DPQ_HALF_BF16
+// The kernels widen a value to fp32 as they stage it, which is exact, and are the fp32 kernels in everything else: an
+// answer over a half base is, bit for bit, the answer over the widened rows.  Queries are fp32 throughout.
 inline int flat_half_padded_d(int D) { return (D + 7) & ~7; }
 
 // fp32 bits -> 16 bits, round to nearest, ties to even, in integer arithmetic: the same bits on the host and on the
@@ -207,16 +237,6 @@ __host__ __device__ inline uint32_t flat_half_widen(uint16_t h, int format) {
 hipError_t launch_flat_half_prepare(const uint16_t* d_in, int64_t rows, int D, int Dp, uint16_t* d_out, hipStream_t stream);
 hipError_t launch_flat_half_narrow(const float* d_in, int64_t rows, int D, int Dp, int format, uint16_t* d_out,
                                    hipStream_t stream);
-// The distance stage of launch_flat_search / launch_flat_range_pass on a half base (b.h16, b.half_format, b.metric): one
-// launch of the half kernel's instantiation over entries e0 .. e0 + rows - 1.  keys / cap / offs: the mode's sink.
-hipError_t launch_flat_dist_half(int mode, const FlatBase& b, int64_t e0, int rows, const FlatQueries& q, uint64_t* keys,
-                                 int cap, const int64_t* offs, FlatQueryState* state, hipStream_t stream);
-// launch_flat_rerank over a half base; d_queries are the caller's fp32 [nq][D], unpadded.
-hipError_t launch_flat_rerank_half(int metric, int format, const uint16_t* d_base, int64_t n, int D, int Dp,
-                                   const float* d_queries, int nq, const int32_t* d_cand, int n_cand, int top_k,
-                                   int64_t id_offset, const uint32_t* d_map, int64_t n_map, uint64_t* d_keys, uint32_t* d_flag,
-                                   int32_t* d_ids, float* d_dists, hipStream_t stream);
-
 // ---- filters and range search (dpq_flat_filter.hip: the row list, the range state, the sort; no distance code) -----
 // A filter is the ascending list of a handle's eligible rows.  d_words [n_words]: bit b of word w = row 32 w + b.
 // flat_filter_count fills d_cnt / d_off [n_words] (popcounts and their exclusive prefix sum) and waits for n_allowed;

@@ -1,5 +1,5 @@
-// dpq_flat.hip -- exact L2 distances, or inner products, between fp32 queries and fp32 base vectors on gfx950
-// (DESIGN.md 5.10, 5.10.3).
+// dpq_flat.hip -- exact L2 distances, or inner products, between fp32 queries and fp32, fp16 or bf16 base vectors on gfx950
+// (DESIGN.md 5.10, 5.10.3, 5.10.4).
 //
 // The arithmetic (include/deltapq_amd.h, "exact search"): per dimension, in ascending order, t = v[d] - q[d] and
 // s = t * t in fp32, each rounded on its own (the build passes -ffp-contract=off), then acc += (double)s on an fp64
@@ -9,9 +9,9 @@
 // step, and the score's bits go through flat_ip_word into the key, so that ascending keys are descending scores; the
 // kernels below are otherwise the same source.
 //
-//   flat_dist_kernel<LIST, MODE, METRIC>
-//                         the one fp32 distance kernel, for every search.  A workgroup takes 64 queries x 64 entries of
-//                         a stripe; both tiles go through LDS in slices of 32 dimensions, transposed so that a lane
+//   flat_dist_kernel<LIST, MODE, METRIC, FORMAT>
+//                         the one fp32-query distance kernel, for every search.  A workgroup takes 64 queries x 64 entries
+//                         of a stripe; both tiles go through LDS in slices of 32 dimensions, transposed so that a lane
 //                         reads its four queries and four vectors as two 16-byte LDS loads; 16 fp64 accumulators per
 //                         lane.  LIST: entry e is row l0 + e (false: every row, or a range search without a filter), or
 //                         row list[l0 + e] (true: a filter's row list), the tile's row numbers staged in LDS.  MODE,
@@ -21,22 +21,32 @@
 //                           kFlatEmit   key <  the radius key: appended to the query's list in the pool, whose length
 //                                       the count pass gave
 //                         Every append checks its position against the capacity of its buffer and raises
-//                         FlatQueryState::overflow instead of storing outside it.
+//                         FlatQueryState::overflow instead of storing outside it.  FORMAT: the rows are fp32, or fp16 /
+//                         bf16 at half the bytes, widened as the base tile is staged -- a lane loads
+//                         16 bytes, eight halves, widens them in registers and writes fp32 to LDS; the staging is the
+//                         only code the formats do not share.  Widening is exact, so every answer over a half base
+//                         equals, bit for bit, the answer over the widened rows.  No matrix instruction: the f16 / bf16
+//                         MFMAs accumulate in fp32 and in an order of their own, which the contract does not allow.
 //   flat_select_kernel    when a buffer is filling up: radix select of the top_k-th key, compaction in place, the
 //                         threshold lowered to that key.
 //   flat_sort_emit_kernel<METRIC>
 //                         bitonic sort of a query's keys in LDS, duplicates dropped, ids and distances (scores) written.
-//   flat_rerank_kernel<METRIC>
+//   flat_rerank_kernel<METRIC, FORMAT>
 //                         a lane per candidate; a wavefront fetches its 64 rows with 16-byte loads into LDS, 32
-//                         dimensions at a time, and every lane then walks its own row in order.
+//                         dimensions at a time (halves widened on the way), and every lane then walks its own row in
+//                         order.
+//   flat_pad_rows_kernel, flat_half_prepare_kernel, flat_half_narrow_kernel
+//                         pad fp32 rows / pad 16-bit rows / narrow fp32 rows to padded 16-bit rows, when a base is opened
 // launch_flat_search is the one stripe driver (state, then per stripe a select and a distance launch, then the last
-// select and the sort) and launch_flat_range_pass the one range pass, for every element type, with and without a list;
-// the byte kernel of dpq_flat_u8.hip comes in through launch_flat_dist_u8, the half kernel of dpq_flat_half.hip through
-// launch_flat_dist_half.  make_key<METRIC> and accumulate<METRIC> live in dpq_flat.h, shared with the half kernels.
+// select and the sort), launch_flat_range_pass the one range pass and launch_flat_rerank the one re-rank launcher (the
+// chunks of the grid's y extent, then the sort), for every format, with and without a list; the byte kernels of
+// dpq_flat_u8.hip come in through launch_flat_dist_u8 and launch_flat_rerank_chunk_u8.  make_key<METRIC>,
+// accumulate<METRIC> and flat_candidate_row live in dpq_flat.h.
 #include "dpq_flat.h"
 
 #include <algorithm>
 #include <atomic>
+#include <type_traits>
 
 namespace dpq {
 namespace {
@@ -63,15 +73,43 @@ __global__ void flat_pad_rows_kernel(const float* in, int64_t rows, int D, int D
     out[i] = d < D ? in[r * D + d] : 0.0f;
 }
 
+// The stored type of a row's values, and eight halves as they lie in memory -> eight fp32 values (exact: bf16 widens
+// with a shift, fp16 with v_cvt_f32_f16, which under the build's 16-bit denormal mode keeps subnormals).
+template <int FORMAT> using flat_row_t = std::conditional_t<FORMAT == kFlatF32, float, uint16_t>;
+
+template <int FORMAT>
+__device__ __forceinline__ void widen8(const uint4& raw, float* out) {
+    const uint32_t w[4] = {raw.x, raw.y, raw.z, raw.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        if constexpr (FORMAT == kFlatBF16) {
+            out[2 * i] = __uint_as_float(w[i] << 16);
+            out[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
+        } else {
+            union { uint16_t u; _Float16 h; } lo, hi;
+            lo.u = (uint16_t)(w[i] & 0xffffu);
+            hi.u = (uint16_t)(w[i] >> 16);
+            out[2 * i] = (float)lo.h;
+            out[2 * i + 1] = (float)hi.h;
+        }
+    }
+}
+
 // grid (tiles of the stripe's `rows` entries, query tiles), 256 threads: thread (tx, ty) owns queries ty*4.. x entries
 // tx*4.. of the tile.  Entry e of the stripe is row l0 + e, computed where it is needed (LIST false: no row numbers in
 // LDS, no barrier before the first slice), or row list[l0 + e], staged once per tile in lrow.  Every instantiation is
 // the straight-line kernel of its case; nothing is picked at run time.
-template <bool LIST, int MODE, int METRIC>
-__global__ __launch_bounds__(256) void flat_dist_kernel(const float* __restrict__ base, const uint32_t* __restrict__ list,
+// FORMAT decides one thing, how a slice of the base tile, 64 rows x 32 dimensions, gets into vs.  fp32: thread t loads
+// 16 bytes of rows sr and sr + 32, as it does for the queries.  Halves: the slice is 256 loads of 16 bytes, one per
+// thread; thread t takes row vr = (t & 15) | (t >> 6) << 4 and dimensions vj = ((t >> 4) & 3) * 8 .. + 7, so that the 32
+// lanes of a half wavefront write 16 consecutive rows of two slice rows that lie 8 * LD floats apart: two addresses per
+// LDS bank of a ds_write_b32, which costs nothing extra.
+template <bool LIST, int MODE, int METRIC, int FORMAT>
+__global__ __launch_bounds__(256) void flat_dist_kernel(const void* __restrict__ base_rows, const uint32_t* __restrict__ list,
                                                         int64_t l0, int rows, int Dp, const float* __restrict__ queries,
                                                         int nq, int64_t id_offset, uint64_t* __restrict__ keys, int cap,
                                                         const int64_t* __restrict__ offs, FlatQueryState* state) {
+    const auto* base = static_cast<const flat_row_t<FORMAT>*>(base_rows);
     __shared__ float qs[DC][LD];
     __shared__ float vs[DC][LD];
     __shared__ uint32_t lrow[TV];  // LIST only
@@ -81,6 +119,7 @@ __global__ __launch_bounds__(256) void flat_dist_kernel(const float* __restrict_
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
     const int v0 = blockIdx.x * TV, q0 = blockIdx.y * TQ;
     const int sr = tid >> 3, sj = (tid & 7) * 4;  // staging: row sr (and sr + 32), dimensions sj .. sj + 3 of the slice
+    const int vr = (tid & 15) | ((tid >> 6) << 4), vj = ((tid >> 4) & 3) * 8;  // halves: row vr, eight dimensions
     if constexpr (LIST) {
         if (tid < TV) lrow[tid] = v0 + tid < rows ? list[l0 + v0 + tid] : 0;  // past the stripe: row 0, masked below
         __syncthreads();
@@ -98,13 +137,25 @@ __global__ __launch_bounds__(256) void flat_dist_kernel(const float* __restrict_
         for (int j = 0; j < 4; ++j) acc[i][j] = 0.0;
 
     for (int d0 = 0; d0 < Dp; d0 += DC) {
+        if constexpr (FORMAT != kFlatF32) {
+            uint4 raw = make_uint4(0u, 0u, 0u, 0u);  // the bits of eight zeros in either format
+            if (v0 + vr < rows && d0 + vj < Dp) raw = *reinterpret_cast<const uint4*>(base + (size_t)row_of(vr) * Dp + d0 + vj);
+            float v[8];
+            widen8<FORMAT>(raw, v);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) vs[vj + k][vr] = v[k];
+        }
+        // the queries, and beside them the fp32 base tile: both loads ahead of both sets of LDS writes
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             const int r = sr + 32 * h, d = d0 + sj;
             float4 v = make_float4(0.f, 0.f, 0.f, 0.f), q = v;
-            if (v0 + r < rows && d < Dp) v = *reinterpret_cast<const float4*>(base + (size_t)row_of(r) * Dp + d);
+            if constexpr (FORMAT == kFlatF32)
+                if (v0 + r < rows && d < Dp) v = *reinterpret_cast<const float4*>(base + (size_t)row_of(r) * Dp + d);
             if (q0 + r < nq && d < Dp) q = *reinterpret_cast<const float4*>(queries + (size_t)(q0 + r) * Dp + d);
-            vs[sj + 0][r] = v.x; vs[sj + 1][r] = v.y; vs[sj + 2][r] = v.z; vs[sj + 3][r] = v.w;
+            if constexpr (FORMAT == kFlatF32) {
+                vs[sj + 0][r] = v.x; vs[sj + 1][r] = v.y; vs[sj + 2][r] = v.z; vs[sj + 3][r] = v.w;
+            }
             qs[sj + 0][r] = q.x; qs[sj + 1][r] = q.y; qs[sj + 2][r] = q.z; qs[sj + 3][r] = q.w;
         }
         __syncthreads();
@@ -287,44 +338,48 @@ __global__ __launch_bounds__(kSelThreads) void flat_sort_emit_kernel(const uint6
     }
 }
 
-// grid (candidate groups of 256, queries), 256 threads: lane = candidate.
-template <int METRIC>
-__global__ __launch_bounds__(256) void flat_rerank_kernel(const float* __restrict__ base, int64_t n, int D, int Dp,
+// grid (candidate groups of 256, queries), 256 threads: lane = candidate.  FORMAT decides how a wavefront fetches the
+// 32-dimension slice of its 64 rows into its tile: eight rounds of 8 rows, eight lanes of 16 bytes (four floats) per row,
+// or, for halves, four rounds of 16 rows, four lanes of 16 bytes (eight halves, widened) per row.
+template <int METRIC, int FORMAT>
+__global__ __launch_bounds__(256) void flat_rerank_kernel(const void* __restrict__ base_rows, int64_t n, int D, int Dp,
                                                           const float* __restrict__ queries,
                                                           const int32_t* __restrict__ cand, int n_cand, int n_pad,
                                                           int64_t id_offset, const uint32_t* __restrict__ map,
                                                           int64_t n_map, uint64_t* __restrict__ keys, uint32_t* flag) {
+    const auto* base = static_cast<const flat_row_t<FORMAT>*>(base_rows);
     __shared__ float qv[kFlatMaxD];
     __shared__ float tile[4][64][DC + 1];
     const int q = blockIdx.y, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     for (int d = tid; d < Dp; d += 256) qv[d] = d < D ? queries[(size_t)q * D + d] : 0.0f;
     const int ci = blockIdx.x * 256 + tid;
     int row = -1;
-    if (ci < n_cand) {
-        const int32_t c = cand[(size_t)q * n_cand + ci];
-        if (c >= 0) {  // a negative candidate is padding
-            if (map) {
-                int64_t p = c;
-                if ((n_map & 1) == 0 && p == n_map) p = n_map - 1;  // the even-N id of the last DFS node
-                if (p < n_map && (int64_t)map[p] < n) row = (int)map[p];
-            } else {
-                const int64_t r = (int64_t)c - id_offset;
-                if (r >= 0 && r < n) row = (int)r;
-            }
-            if (row < 0) *flag = 1;  // names no row
-        }
-    }
+    if (ci < n_cand) row = flat_candidate_row(cand[(size_t)q * n_cand + ci], n, id_offset, map, n_map, flag);
     __syncthreads();
     double acc = 0.0;
-    const int lj = (lane & 7) * 4;
+    const int lj = FORMAT == kFlatF32 ? (lane & 7) * 4 : (lane & 3) * 8;  // the lane's first dimension of a fetched slice
     for (int d0 = 0; d0 < Dp; d0 += DC) {
+        if constexpr (FORMAT == kFlatF32) {
 #pragma unroll
-        for (int it = 0; it < 8; ++it) {
-            const int cc = it * 8 + (lane >> 3);
-            const int rr = __shfl(row, cc);
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (rr >= 0 && d0 + lj < Dp) v = *reinterpret_cast<const float4*>(base + (size_t)rr * Dp + d0 + lj);
-            tile[w][cc][lj + 0] = v.x; tile[w][cc][lj + 1] = v.y; tile[w][cc][lj + 2] = v.z; tile[w][cc][lj + 3] = v.w;
+            for (int it = 0; it < 8; ++it) {
+                const int cc = it * 8 + (lane >> 3);
+                const int rr = __shfl(row, cc);
+                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (rr >= 0 && d0 + lj < Dp) v = *reinterpret_cast<const float4*>(base + (size_t)rr * Dp + d0 + lj);
+                tile[w][cc][lj + 0] = v.x; tile[w][cc][lj + 1] = v.y; tile[w][cc][lj + 2] = v.z; tile[w][cc][lj + 3] = v.w;
+            }
+        } else {
+#pragma unroll
+            for (int it = 0; it < 4; ++it) {
+                const int cc = it * 16 + (lane >> 2);
+                const int rr = __shfl(row, cc);
+                uint4 raw = make_uint4(0u, 0u, 0u, 0u);
+                if (rr >= 0 && d0 + lj < Dp) raw = *reinterpret_cast<const uint4*>(base + (size_t)rr * Dp + d0 + lj);
+                float v[8];
+                widen8<FORMAT>(raw, v);
+#pragma unroll
+                for (int k = 0; k < 8; ++k) tile[w][cc][lj + k] = v[k];
+            }
         }
         __syncthreads();
         const int dc = min(DC, Dp - d0);
@@ -335,6 +390,29 @@ __global__ __launch_bounds__(256) void flat_rerank_kernel(const float* __restric
     if (ci < n_pad)
         keys[(size_t)q * n_pad + ci] = row >= 0 ? make_key<METRIC>(acc, (uint32_t)((int64_t)row + id_offset)) : kFlatNoKey;
 }
+
+// The two kernels that make a half base's rows.  Grid-stride over the rows * Dp values of the output.
+__global__ __launch_bounds__(256) void flat_half_prepare_kernel(const uint16_t* __restrict__ in, int64_t rows, int D, int Dp,
+                                                                uint16_t* __restrict__ out) {
+    const int64_t total = rows * Dp, step = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += step) {
+        const int64_t r = i / Dp;
+        const int d = (int)(i - r * Dp);
+        out[i] = d < D ? in[r * D + d] : (uint16_t)0;
+    }
+}
+
+__global__ __launch_bounds__(256) void flat_half_narrow_kernel(const float* __restrict__ in, int64_t rows, int D, int Dp,
+                                                               int format, uint16_t* __restrict__ out) {
+    const int64_t total = rows * Dp, step = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += step) {
+        const int64_t r = i / Dp;
+        const int d = (int)(i - r * Dp);
+        out[i] = d < D ? flat_half_narrow(__float_as_uint(in[r * D + d]), format) : (uint16_t)0;
+    }
+}
+
+unsigned grid_for(int64_t total) { return (unsigned)std::min<int64_t>((total + 255) / 256, 8192); }
 
 int pow2_at_least(int v) {
     int p = 1;
@@ -374,23 +452,44 @@ hipError_t launch_flat_pad_rows(const float* d_in, int64_t rows, int D, int Dp, 
     return hipGetLastError();
 }
 
-namespace {
-
-template <bool LIST, int MODE, int METRIC>
-void dist_fp32(const FlatBase& b, int64_t e0, int rows, const FlatQueries& q, uint64_t* keys, int cap, const int64_t* offs,
-               FlatQueryState* state, hipStream_t stream) {
-    flat_dist_kernel<LIST, MODE, METRIC><<<dim3((rows + TV - 1) / TV, (q.nq + TQ - 1) / TQ), dim3(256), 0, stream>>>(
-        b.f32, b.list, e0, rows, b.Dp, q.f32, q.nq, b.id_offset, keys, cap, offs, state);
+hipError_t launch_flat_half_prepare(const uint16_t* d_in, int64_t rows, int D, int Dp, uint16_t* d_out, hipStream_t stream) {
+    const int64_t total = rows * Dp;
+    if (total <= 0) return hipSuccess;
+    flat_half_prepare_kernel<<<dim3(grid_for(total)), dim3(256), 0, stream>>>(d_in, rows, D, Dp, d_out);
+    return hipGetLastError();
 }
 
-template <int METRIC>
-auto* pick_dist_fp32(bool filtered, int mode) {
-    return filtered ? (mode == kFlatTopK    ? dist_fp32<true, kFlatTopK, METRIC>
-                       : mode == kFlatCount ? dist_fp32<true, kFlatCount, METRIC>
-                                            : dist_fp32<true, kFlatEmit, METRIC>)
-                    : (mode == kFlatTopK    ? dist_fp32<false, kFlatTopK, METRIC>
-                       : mode == kFlatCount ? dist_fp32<false, kFlatCount, METRIC>
-                                            : dist_fp32<false, kFlatEmit, METRIC>);
+hipError_t launch_flat_half_narrow(const float* d_in, int64_t rows, int D, int Dp, int format, uint16_t* d_out,
+                                   hipStream_t stream) {
+    const int64_t total = rows * Dp;
+    if (total <= 0) return hipSuccess;
+    flat_half_narrow_kernel<<<dim3(grid_for(total)), dim3(256), 0, stream>>>(d_in, rows, D, Dp, format, d_out);
+    return hipGetLastError();
+}
+
+namespace {
+
+template <bool LIST, int MODE, int METRIC, int FORMAT>
+void dist(const FlatBase& b, int64_t e0, int rows, const FlatQueries& q, uint64_t* keys, int cap, const int64_t* offs,
+          FlatQueryState* state, hipStream_t stream) {
+    flat_dist_kernel<LIST, MODE, METRIC, FORMAT><<<dim3((rows + TV - 1) / TV, (q.nq + TQ - 1) / TQ), dim3(256), 0, stream>>>(
+        b.rows, b.list, e0, rows, b.Dp, q.f32, q.nq, b.id_offset, keys, cap, offs, state);
+}
+
+// The launch of an fp32-query base's instantiation: format x metric x row source x mode.
+template <int METRIC, int FORMAT>
+auto* pick_dist(bool filtered, int mode) {
+    return filtered ? (mode == kFlatTopK    ? dist<true, kFlatTopK, METRIC, FORMAT>
+                       : mode == kFlatCount ? dist<true, kFlatCount, METRIC, FORMAT>
+                                            : dist<true, kFlatEmit, METRIC, FORMAT>)
+                    : (mode == kFlatTopK    ? dist<false, kFlatTopK, METRIC, FORMAT>
+                       : mode == kFlatCount ? dist<false, kFlatCount, METRIC, FORMAT>
+                                            : dist<false, kFlatEmit, METRIC, FORMAT>);
+}
+
+template <int FORMAT>
+auto* pick_dist(int metric, bool filtered, int mode) {
+    return metric == kFlatIP ? pick_dist<kFlatIP, FORMAT>(filtered, mode) : pick_dist<kFlatL2, FORMAT>(filtered, mode);
 }
 
 // The sort stage of a search or a re-rank, by metric.
@@ -401,14 +500,25 @@ void sort_emit(int metric, const uint64_t* d_keys, size_t stride, const FlatQuer
                                                                                      top_k, d_ids, d_dists);
 }
 
-// One distance launch over entries e0 .. e0 + rows - 1 of the base, by element type, metric, row source and mode.
+// One distance launch over entries e0 .. e0 + rows - 1 of the base, by format, metric, row source and mode.
 hipError_t launch_flat_dist(int mode, const FlatBase& b, int64_t e0, int rows, const FlatQueries& q, uint64_t* keys, int cap,
                             const int64_t* offs, FlatQueryState* state, hipStream_t stream) {
-    if (b.i8) return launch_flat_dist_u8(mode, b, e0, rows, q, keys, cap, offs, state, stream);
-    if (b.h16) return launch_flat_dist_half(mode, b, e0, rows, q, keys, cap, offs, state, stream);
-    auto* launch = b.metric == kFlatIP ? pick_dist_fp32<kFlatIP>(b.filtered, mode) : pick_dist_fp32<kFlatL2>(b.filtered, mode);
-    launch(b, e0, rows, q, keys, cap, offs, state, stream);
+    switch (b.format) {
+        case kFlatU8:
+        case kFlatI8: return launch_flat_dist_u8(mode, b, e0, rows, q, keys, cap, offs, state, stream);
+        case kFlatF16: pick_dist<kFlatF16>(b.metric, b.filtered, mode)(b, e0, rows, q, keys, cap, offs, state, stream); break;
+        case kFlatBF16: pick_dist<kFlatBF16>(b.metric, b.filtered, mode)(b, e0, rows, q, keys, cap, offs, state, stream); break;
+        default: pick_dist<kFlatF32>(b.metric, b.filtered, mode)(b, e0, rows, q, keys, cap, offs, state, stream);
+    }
     return hipGetLastError();
+}
+
+template <int FORMAT>
+void rerank_chunk(const FlatBase& b, const FlatRerank& r, int n_pad, hipStream_t stream) {
+    auto* kernel = b.metric == kFlatIP ? flat_rerank_kernel<kFlatIP, FORMAT> : flat_rerank_kernel<kFlatL2, FORMAT>;
+    kernel<<<dim3((n_pad + 255) / 256, r.nq), dim3(256), 0, stream>>>(
+        b.rows, b.n, b.D, b.Dp, static_cast<const float*>(r.queries), r.cand, r.n_cand, n_pad, b.id_offset, r.map, r.n_map,
+        r.keys, r.flag);
 }
 
 }  // namespace
@@ -444,22 +554,27 @@ hipError_t launch_flat_range_pass(const FlatBase& b, const FlatQueries& q, uint6
                             d_state, stream);
 }
 
-hipError_t launch_flat_rerank(int metric, const float* d_base, int64_t n, int D, int Dp, const float* d_queries, int nq,
-                              const int32_t* d_cand, int n_cand, int top_k, int64_t id_offset, const uint32_t* d_map,
-                              int64_t n_map, uint64_t* d_keys, uint32_t* d_flag, int32_t* d_ids, float* d_dists,
-                              hipStream_t stream) {
-    if (nq <= 0) return hipSuccess;
+hipError_t launch_flat_rerank(const FlatBase& b, const FlatRerank& r, hipStream_t stream) {
+    if (r.nq <= 0) return hipSuccess;
     hipError_t e = ensure_sort_lds();
     if (e != hipSuccess) return e;
-    const int n_pad = pow2_at_least(n_cand);
-    for (int q0 = 0; q0 < nq; q0 += 65535) {  // the grid's y extent
-        const int m = std::min(65535, nq - q0);
-        auto* kernel = metric == kFlatIP ? flat_rerank_kernel<kFlatIP> : flat_rerank_kernel<kFlatL2>;
-        kernel<<<dim3((n_pad + 255) / 256, m), dim3(256), 0, stream>>>(
-            d_base, n, D, Dp, d_queries + (size_t)q0 * D, d_cand + (size_t)q0 * n_cand, n_cand, n_pad, id_offset, d_map,
-            n_map, d_keys + (size_t)q0 * n_pad, d_flag);
+    const int n_pad = pow2_at_least(r.n_cand);
+    const size_t q_bytes = (size_t)b.D * (flat_query_format(b.format) == kFlatF32 ? sizeof(float) : 1);  // of one query
+    for (int q0 = 0; q0 < r.nq; q0 += 65535) {  // the grid's y extent
+        FlatRerank c = r;
+        c.queries = static_cast<const char*>(r.queries) + (size_t)q0 * q_bytes;
+        c.nq = std::min(65535, r.nq - q0);
+        c.cand = r.cand + (size_t)q0 * r.n_cand;
+        c.keys = r.keys + (size_t)q0 * n_pad;
+        switch (b.format) {
+            case kFlatU8:
+            case kFlatI8: launch_flat_rerank_chunk_u8(b, c, n_pad, stream); break;
+            case kFlatF16: rerank_chunk<kFlatF16>(b, c, n_pad, stream); break;
+            case kFlatBF16: rerank_chunk<kFlatBF16>(b, c, n_pad, stream); break;
+            default: rerank_chunk<kFlatF32>(b, c, n_pad, stream);
+        }
     }
-    sort_emit(metric, d_keys, (size_t)n_pad, nullptr, nq, n_pad, n_pad, top_k, d_ids, d_dists, stream);
+    sort_emit(b.metric, r.keys, (size_t)n_pad, nullptr, r.nq, n_pad, n_pad, r.top_k, r.ids, r.dists, stream);
     return hipGetLastError();
 }
 

@@ -35,10 +35,9 @@
 //   flat_rerank_u8_kernel<METRIC, SIGNED>
 //                              a lane per candidate; a wavefront fetches its 64 rows with 16-byte loads into LDS, 128
 //                              bytes of a row at a time, and every lane then sums its own row in int32.
-// State, selection, the final sort and the stripe driver are dpq_flat.hip's; launch_flat_dist_u8 is the one way in.
+// State, selection, the final sort, the stripe driver and the re-rank launcher are dpq_flat.hip's; launch_flat_dist_u8 and
+// launch_flat_rerank_chunk_u8 are the two ways in.
 #include "dpq_flat.h"
-
-#include <algorithm>
 
 namespace dpq {
 namespace {
@@ -329,20 +328,7 @@ __global__ __launch_bounds__(256) void flat_rerank_u8_kernel(const int8_t* __res
     for (int d = tid; d < Dp; d += 256) qv[d] = d < D ? (int8_t)(queries[(size_t)q * D + d] ^ flip) : qpad;
     const int ci = blockIdx.x * 256 + tid;
     int row = -1;
-    if (ci < n_cand) {
-        const int32_t c = cand[(size_t)q * n_cand + ci];
-        if (c >= 0) {  // a negative candidate is padding
-            if (map) {
-                int64_t p = c;
-                if ((n_map & 1) == 0 && p == n_map) p = n_map - 1;  // the even-N id of the last DFS node
-                if (p < n_map && (int64_t)map[p] < n) row = (int)map[p];
-            } else {
-                const int64_t rr = (int64_t)c - id_offset;
-                if (rr >= 0 && rr < n) row = (int)rr;
-            }
-            if (row < 0) *flag = 1;  // names no row
-        }
-    }
+    if (ci < n_cand) row = flat_candidate_row(cand[(size_t)q * n_cand + ci], n, id_offset, map, n_map, flag);
     __syncthreads();
     int acc = 0;
     const int lj = (lane & 7) * 16;
@@ -398,7 +384,7 @@ void dist_u8(const FlatBase& b, int64_t e0, int rows, const FlatQueries& q, uint
     const int32_t* vterm = METRIC == kFlatL2 ? b.norm : CORR ? b.rsum : nullptr;
     const int32_t* qterm = METRIC == kFlatL2 ? q.norm : CORR ? q.sum : nullptr;
     flat_dist_u8_kernel<LIST, MODE, METRIC, CORR><<<dim3((rows + UV - 1) / UV, (q.nq + UQ - 1) / UQ), dim3(256), 0, stream>>>(
-        b.i8, vterm, b.list, e0, rows, b.Dp, q.i8, qterm, q.nq, b.id_offset, keys, cap, offs, state);
+        static_cast<const int8_t*>(b.rows), vterm, b.list, e0, rows, b.Dp, q.i8, qterm, q.nq, b.id_offset, keys, cap, offs, state);
 }
 
 template <int METRIC, bool CORR>
@@ -415,28 +401,20 @@ auto pick_dist_u8(bool filtered, int mode) {
 
 hipError_t launch_flat_dist_u8(int mode, const FlatBase& b, int64_t e0, int rows, const FlatQueries& q, uint64_t* keys,
                                int cap, const int64_t* offs, FlatQueryState* state, hipStream_t stream) {
-    auto* launch = b.metric != kFlatIP ? pick_dist_u8<kFlatL2, true>(b.filtered, mode)
-                   : b.i8_signed       ? pick_dist_u8<kFlatIP, false>(b.filtered, mode)
-                                       : pick_dist_u8<kFlatIP, true>(b.filtered, mode);
+    auto* launch = b.metric != kFlatIP   ? pick_dist_u8<kFlatL2, true>(b.filtered, mode)
+                   : b.format == kFlatI8 ? pick_dist_u8<kFlatIP, false>(b.filtered, mode)
+                                         : pick_dist_u8<kFlatIP, true>(b.filtered, mode);
     launch(b, e0, rows, q, keys, cap, offs, state, stream);
     return hipGetLastError();
 }
 
-hipError_t launch_flat_rerank_u8(int metric, bool is_signed, const int8_t* d_base, int64_t n, int D, int Dp,
-                                 const uint8_t* d_queries, int nq, const int32_t* d_cand, int n_cand, int top_k,
-                                 int64_t id_offset, const uint32_t* d_map, int64_t n_map, uint64_t* d_keys, uint32_t* d_flag,
-                                 int32_t* d_ids, float* d_dists, hipStream_t stream) {
-    if (nq <= 0) return hipSuccess;
-    const int n_pad = (int)flat_rerank_keys(n_cand);
-    auto* kernel = metric == kFlatIP ? (is_signed ? flat_rerank_u8_kernel<kFlatIP, true> : flat_rerank_u8_kernel<kFlatIP, false>)
-                                     : (is_signed ? flat_rerank_u8_kernel<kFlatL2, true> : flat_rerank_u8_kernel<kFlatL2, false>);
-    for (int q0 = 0; q0 < nq; q0 += 65535) {  // the grid's y extent
-        const int m = std::min(65535, nq - q0);
-        kernel<<<dim3((n_pad + 255) / 256, m), dim3(256), 0, stream>>>(
-            d_base, n, D, Dp, d_queries + (size_t)q0 * D, d_cand + (size_t)q0 * n_cand, n_cand, n_pad, id_offset, d_map,
-            n_map, d_keys + (size_t)q0 * n_pad, d_flag);
-    }
-    return launch_flat_sort_emit(d_keys, (size_t)n_pad, nullptr, nq, n_pad, top_k, d_ids, d_dists, stream, metric);
+void launch_flat_rerank_chunk_u8(const FlatBase& b, const FlatRerank& r, int n_pad, hipStream_t stream) {
+    const bool is_signed = b.format == kFlatI8;
+    auto* kernel = b.metric == kFlatIP ? (is_signed ? flat_rerank_u8_kernel<kFlatIP, true> : flat_rerank_u8_kernel<kFlatIP, false>)
+                                       : (is_signed ? flat_rerank_u8_kernel<kFlatL2, true> : flat_rerank_u8_kernel<kFlatL2, false>);
+    kernel<<<dim3((n_pad + 255) / 256, r.nq), dim3(256), 0, stream>>>(
+        static_cast<const int8_t*>(b.rows), b.n, b.D, b.Dp, static_cast<const uint8_t*>(r.queries), r.cand, r.n_cand, n_pad,
+        b.id_offset, r.map, r.n_map, r.keys, r.flag);
 }
 
 }  // namespace dpq
