@@ -1376,6 +1376,122 @@ class FlatIndexHalf(FlatIndex):
         self._h = h
 
 
+SQ_BITS = (8, 4)   # DPQ_SQ_8BIT, DPQ_SQ_4BIT
+
+
+def _sq_bits(bits):
+    if bits not in SQ_BITS:
+        raise ValueError("bits must be 8 or 4")
+    return int(bits)
+
+
+def _sq_quantiser(lo, step, D):
+    """lo, step as contiguous float32 [D]; anything that would need a conversion is refused."""
+    out = []
+    for name, a in (("lo", lo), ("step", step)):
+        a = np.asarray(a)
+        if a.dtype != np.float32:
+            raise TypeError("%s must be float32 (got %s)" % (name, a.dtype))
+        if a.shape != (D,):
+            raise ValueError("%s must be [%d]" % (name, D))
+        out.append(np.ascontiguousarray(a))
+    return out
+
+
+def _sq_rows(vectors):
+    v = np.asarray(vectors)
+    if v.dtype != np.float32:
+        raise TypeError("vectors must be float32 (got %s)" % v.dtype)
+    if v.ndim != 2:
+        raise ValueError("vectors must be [n][D]")
+    return np.ascontiguousarray(v)
+
+
+def _sq_codes(codes, D, bits):
+    c = np.asarray(codes)
+    if c.dtype != np.uint8:
+        raise TypeError("codes must be uint8 (got %s)" % c.dtype)
+    if c.ndim != 2 or c.shape[1] != (D if bits == 8 else (D + 1) // 2):
+        raise ValueError("codes must be [n][D] at 8 bits, [n][(D + 1) / 2] at 4 bits")
+    return np.ascontiguousarray(c)
+
+
+def sq_train(vectors, bits=8, device=0):
+    """A scalar quantiser trained on float32 vectors [n][D]: (lo, step), float32 [D] each -- the minimum of every
+    dimension and (max - min) / (2^bits - 1) (dpq_sq_train; the reduction runs on the GPU)."""
+    v, bits = _sq_rows(vectors), _sq_bits(bits)
+    lo, step = np.empty(v.shape[1], dtype=np.float32), np.empty(v.shape[1], dtype=np.float32)
+    check(_lib.load().dpq_sq_train(_np_ptr(v), v.shape[0], v.shape[1], bits, device, _np_ptr(lo), _np_ptr(step)), "dpq_sq_train")
+    return lo, step
+
+
+def sq_encode(vectors, lo, step, bits=8, device=0):
+    """float32 vectors [n][D] -> uint8 codes [n][D] (8 bits) or [n][(D + 1) / 2] (4 bits: dimension 2j in the low nibble
+    of byte j), round to nearest, ties to even, saturating (dpq_sq_encode; on the GPU)."""
+    v, bits = _sq_rows(vectors), _sq_bits(bits)
+    lo, step = _sq_quantiser(lo, step, v.shape[1])
+    out = np.empty((v.shape[0], v.shape[1] if bits == 8 else (v.shape[1] + 1) // 2), dtype=np.uint8)
+    check(_lib.load().dpq_sq_encode(_np_ptr(v), v.shape[0], v.shape[1], bits, _np_ptr(lo), _np_ptr(step), device, _np_ptr(out)),
+          "dpq_sq_encode")
+    return out
+
+
+def sq_decode(codes, lo, step, bits=8):
+    """uint8 codes as sq_encode writes them -> the float32 values [n][D] they stand for, lo + code * step with both
+    roundings (dpq_sq_decode; host only)."""
+    bits = _sq_bits(bits)
+    D = int(np.asarray(lo).shape[0]) if np.asarray(lo).ndim == 1 else -1
+    lo, step = _sq_quantiser(lo, step, D)
+    c = _sq_codes(codes, D, bits)
+    out = np.empty((c.shape[0], D), dtype=np.float32)
+    check(_lib.load().dpq_sq_decode(_np_ptr(c), c.shape[0], D, bits, _np_ptr(lo), _np_ptr(step), _np_ptr(out)), "dpq_sq_decode")
+    return out
+
+
+class FlatIndexSQ(FlatIndex):
+    """Scalar-quantised vectors [n][D] on one GPU, a byte (bits=8) or a nibble (bits=4) per dimension: every method of
+    FlatIndex, with fp32 queries, and bit for bit FlatIndex's answers over sq_decode of the codes.  The constructor takes
+    codes the caller already has with their quantiser (dpq_flat_open_sq); from_float quantises float32 rows on the GPU
+    (dpq_flat_open_quantised)."""
+
+    def __init__(self, codes, lo, step, bits=8, device=0, id_offset=0):
+        self._h = None
+        bits = _sq_bits(bits)
+        D = int(np.asarray(lo).shape[0]) if np.asarray(lo).ndim == 1 else -1
+        lo, step = _sq_quantiser(lo, step, D)
+        c = _sq_codes(codes, D, bits)
+        self._open("dpq_flat_open_sq", c, c.shape[0], D, bits, lo, step, device, id_offset)
+
+    @classmethod
+    def from_float(cls, vectors, bits=8, lo=None, step=None, device=0, id_offset=0):
+        """float32 vectors [n][D], quantised on the GPU under (lo, step), or, with neither, under the quantiser trained on
+        these very rows."""
+        v, bits = _sq_rows(vectors), _sq_bits(bits)
+        if (lo is None) != (step is None):
+            raise ValueError("lo and step are both given or both left out")
+        if lo is not None:
+            lo, step = _sq_quantiser(lo, step, v.shape[1])
+        self = cls.__new__(cls)
+        self._h = None
+        self._open("dpq_flat_open_quantised", v, v.shape[0], v.shape[1], bits, lo, step, device, id_offset)
+        return self
+
+    def _open(self, name, data, n, D, bits, lo, step, device, id_offset):
+        self._lib = _lib.load()
+        self.n, self.D, self.bits, self.id_offset = int(n), int(D), bits, int(id_offset)
+        h = ctypes.c_void_p()
+        check(getattr(self._lib, name)(_np_ptr(data), self.n, self.D, bits, None if lo is None else _np_ptr(lo),
+                                       None if step is None else _np_ptr(step), device, id_offset, ctypes.byref(h)), name)
+        self._h = h
+
+    def quantiser(self):
+        """(lo, step, bits) of the handle (dpq_flat_sq_get)."""
+        bits = ctypes.c_int()
+        lo, step = np.empty(self.D, dtype=np.float32), np.empty(self.D, dtype=np.float32)
+        check(self._lib.dpq_flat_sq_get(self._h, ctypes.byref(bits), _np_ptr(lo), _np_ptr(step)), "dpq_flat_sq_get")
+        return lo, step, bits.value
+
+
 class FlatIndexU8(_FlatIndexBase):
     """Byte vectors [n][D] on one GPU (dpq_flat_open_u8): FlatIndex's answers -- the same ids and the same distance bits as
     on the bytes widened to fp32 -- from the int8 matrix cores, at a quarter of the device memory.  The *_ip methods are

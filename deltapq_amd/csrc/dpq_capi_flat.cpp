@@ -6,7 +6,7 @@
 namespace {
 
 // The format of queries of type Q.  A call takes the handles whose rows go with it (dpq::flat_query_format): float -- an
-// fp32 or a half handle, uint8_t -- a handle of dpq_flat_open_u8, int8_t -- a handle of dpq_flat_open_i8.
+// fp32, a half or a quantised handle, uint8_t -- a handle of dpq_flat_open_u8, int8_t -- a handle of dpq_flat_open_i8.
 template <class Q> constexpr int format_of = dpq::kFlatF32;
 template <> constexpr int format_of<uint8_t> = dpq::kFlatU8;
 template <> constexpr int format_of<int8_t> = dpq::kFlatI8;
@@ -29,7 +29,7 @@ struct FlatCall {
 dpq::FlatBase flat_base(const dpq_flat* f, const dpq_flat_filter* ff, int metric) {
     dpq::FlatBase b;
     b.format = f->format;
-    b.rows = f->rows.get();
+    b.rows = f->rows.get() + f->rows_at;
     b.n = f->n;
     b.D = f->D;
     b.Dp = f->Dp;
@@ -37,6 +37,7 @@ dpq::FlatBase flat_base(const dpq_flat* f, const dpq_flat_filter* ff, int metric
     b.metric = metric;
     b.norm = f->norm8;
     b.rsum = f->rsum8;
+    if (f->rows_at) b.quant = reinterpret_cast<const float2*>(f->rows.get());
     b.filtered = ff != nullptr;
     b.list = ff ? ff->list.get() : nullptr;
     b.n_entries = ff ? ff->n_allowed : f->n;
@@ -76,9 +77,9 @@ int flat_rerank_on_device(const char* fn, int metric, dpq_flat* f, const Q* d_qu
     return DPQ_OK;
 }
 
-// A handle takes the calls of its own kind only: the fp32-query functions an fp32 or a half handle, the _u8 functions a
-// handle of dpq_flat_open_u8, the _i8 functions one of dpq_flat_open_i8.  The message names the call of the same shape
-// that the handle does take.
+// A handle takes the calls of its own kind only: the fp32-query functions an fp32, a half or a quantised handle, the
+// _u8 functions a handle of dpq_flat_open_u8, the _i8 functions one of dpq_flat_open_i8.  The message names the call of
+// the same shape that the handle does take.
 int flat_kind(const dpq_flat* f, const FlatCall& c) {
     const int kind = dpq::flat_query_format(f->format);
     if (kind == c.kind) return DPQ_OK;
@@ -88,6 +89,10 @@ int flat_kind(const dpq_flat* f, const FlatCall& c) {
         case dpq::kFlatBF16:
             return fail(DPQ_ERR_ARG, fn + ": the handle holds half-precision vectors (dpq_flat_open_half, "
                                           "dpq_flat_open_narrowed), searched with fp32 queries; call " + right);
+        case dpq::kFlatSQ8:
+        case dpq::kFlatSQ4:
+            return fail(DPQ_ERR_ARG, fn + ": the handle holds scalar-quantised vectors (dpq_flat_open_sq, "
+                                          "dpq_flat_open_quantised), searched with fp32 queries; call " + right);
         case dpq::kFlatF32: return fail(DPQ_ERR_ARG, fn + ": the handle holds fp32 vectors (dpq_flat_open); call " + right);
         case dpq::kFlatI8:
             return fail(DPQ_ERR_ARG, fn + ": the handle holds signed byte vectors (dpq_flat_open_i8); call " + right);
@@ -107,6 +112,16 @@ int flat_rerank_args(const FlatCall& c, const dpq_flat* f, const void* queries, 
     return DPQ_OK;
 }
 
+// After the arguments: the device a call works on.
+int flat_use_device(int device) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail(DPQ_ERR_NO_DEVICE, "no HIP device visible; this library has no CPU fallback");
+    if (device < 0 || device >= ndev) return fail(DPQ_ERR_NO_DEVICE, "device ordinal out of range");
+    DPQ_HIP(hipSetDevice(device));
+    return DPQ_OK;
+}
+
 // The checks of every dpq_flat_open*: the arguments (the half format too, where there is one) before any device call,
 // then the device.
 int flat_open_args(const char* fn, const void* vectors, int64_t n, int D, int device, int64_t id_offset, dpq_flat** out,
@@ -120,12 +135,7 @@ int flat_open_args(const char* fn, const void* vectors, int64_t n, int D, int de
         return fail(DPQ_ERR_ARG, who + ": id_offset < 0 or n + id_offset >= 2^31 (ids are int32)");
     if (half_format && *half_format != DPQ_HALF_F16 && *half_format != DPQ_HALF_BF16)
         return fail(DPQ_ERR_ARG, who + ": format is neither DPQ_HALF_F16 nor DPQ_HALF_BF16");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(DPQ_ERR_NO_DEVICE, "no HIP device visible; this library has no CPU fallback");
-    if (device < 0 || device >= ndev) return fail(DPQ_ERR_NO_DEVICE, "device ordinal out of range");
-    DPQ_HIP(hipSetDevice(device));
-    return DPQ_OK;
+    return flat_use_device(device);
 }
 
 // Every dpq_flat_open*: n rows of D values, fp32 (from_fp32: dpq_flat_open, and dpq_flat_open_narrowed, which narrows
@@ -178,6 +188,103 @@ int flat_open(const char* fn, int format, bool from_fp32, bool callers_format, c
         }
     }
     *out = f.release();
+    return DPQ_OK;
+}
+
+// ---- scalar-quantised vectors: the quantiser's calls and the two ways of opening a quantised handle -----------------
+
+// The arguments every dpq_sq_* / dpq_flat_open_sq / dpq_flat_open_quantised call checks, in the header's order, before
+// any device call.  null_arg: one of the call's required pointers is NULL.  id_offset: of the open calls only.  lo and
+// step are checked where both are given; `optional` (dpq_flat_open_quantised) allows both to be NULL, never one.
+int sq_args(const std::string& who, bool null_arg, int64_t n, int D, int bits, const int64_t* id_offset, const float* lo,
+            const float* step, bool optional = false) {
+    if (null_arg || (!optional && (!lo || !step))) return fail(DPQ_ERR_ARG, who + ": NULL argument");
+    if (n < 1) return fail(DPQ_ERR_ARG, who + ": n < 1");
+    if (D < 1 || D > dpq::kFlatMaxD) return fail(DPQ_ERR_ARG, who + ": D outside 1..2048");
+    if (bits != DPQ_SQ_8BIT && bits != DPQ_SQ_4BIT) return fail(DPQ_ERR_ARG, who + ": bits is neither DPQ_SQ_8BIT nor DPQ_SQ_4BIT");
+    if (id_offset && (*id_offset < 0 || n + *id_offset >= ((int64_t)1 << 31)))
+        return fail(DPQ_ERR_ARG, who + ": id_offset < 0 or n + id_offset >= 2^31 (ids are int32)");
+    if (lo && step) {
+        for (int d = 0; d < D; ++d) {
+            if (!std::isfinite(lo[d])) return fail(DPQ_ERR_ARG, who + ": lo of dimension " + std::to_string(d) + " is not finite");
+            if (!(step[d] >= 0.0f) || std::isinf(step[d]))
+                return fail(DPQ_ERR_ARG, who + ": step of dimension " + std::to_string(d) + " is negative, NaN or infinite");
+        }
+    } else if (lo || step) {
+        return fail(DPQ_ERR_ARG, who + ": lo and step are both NULL (train on these rows) or both given");
+    }
+    return DPQ_OK;
+}
+
+// Host rows [n][row_bytes] go up in slices of at most 128 MB through one staging buffer; use(d_slice, r0, m) works on
+// rows r0 .. r0 + m - 1 and the device is idle when it returns.
+template <class F>
+int sq_slices(const void* host, int64_t n, size_t row_bytes, F&& use) {
+    const int64_t tile = std::max<int64_t>(1, ((int64_t)128 << 20) / (int64_t)row_bytes);
+    DevBuf<uint8_t> tmp;
+    if (int rc = tmp.alloc((size_t)std::min(n, tile) * row_bytes)) return rc;
+    for (int64_t r0 = 0; r0 < n; r0 += tile) {
+        const int64_t m = std::min(tile, n - r0);
+        DPQ_HIP(hipMemcpy(tmp, static_cast<const uint8_t*>(host) + (size_t)r0 * row_bytes, (size_t)m * row_bytes, hipMemcpyHostToDevice));
+        if (int rc = use(tmp.get(), r0, m)) return rc;
+        DPQ_HIP(hipDeviceSynchronize());
+    }
+    return DPQ_OK;
+}
+
+// dpq_sq_train once the arguments are checked and the device is chosen.
+int sq_train(const float* vectors, int64_t n, int D, int bits, float* lo_out, float* step_out) {
+    std::vector<uint32_t> mm((size_t)2 * D, 0u);
+    std::fill(mm.begin(), mm.begin() + D, 0xffffffffu);
+    DevBuf<uint32_t> d_mm;
+    if (int rc = d_mm.alloc(mm.size())) return rc;
+    DPQ_HIP(hipMemcpy(d_mm, mm.data(), mm.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    int rc = sq_slices(vectors, n, (size_t)D * sizeof(float), [&](const uint8_t* d_slice, int64_t, int64_t m) -> int {
+        DPQ_HIP(dpq::launch_flat_sq_minmax(reinterpret_cast<const float*>(d_slice), m, D, d_mm, d_mm.get() + D, nullptr));
+        return DPQ_OK;
+    });
+    if (rc) return rc;
+    DPQ_HIP(hipMemcpy(mm.data(), d_mm, mm.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    const double levels = bits == DPQ_SQ_8BIT ? 255.0 : 15.0;
+    for (int d = 0; d < D; ++d) {
+        const uint32_t lb = dpq::flat_order_bits(mm[(size_t)d]), hb = dpq::flat_order_bits(mm[(size_t)D + d]);
+        float lo, hi;
+        memcpy(&lo, &lb, sizeof lo);
+        memcpy(&hi, &hb, sizeof hi);
+        if (lo == 0.0f) lo = 0.0f;  // -0.0 is stored as +0.0
+        if (hi == 0.0f) hi = 0.0f;
+        lo_out[d] = lo;
+        step_out[d] = (float)(((double)hi - (double)lo) / levels);
+    }
+    return DPQ_OK;
+}
+
+// (lo, step) [D] -> the device array the kernels read, len >= D entries, (+0, +0) beyond D.
+int sq_upload_quant(const float* lo, const float* step, int D, int len, float2* d_quant) {
+    std::vector<float2> q((size_t)len, make_float2(0.0f, 0.0f));
+    for (int d = 0; d < D; ++d) q[(size_t)d] = make_float2(lo[d], step[d]);
+    DPQ_HIP(hipMemcpy(d_quant, q.data(), q.size() * sizeof(float2), hipMemcpyHostToDevice));
+    return DPQ_OK;
+}
+
+// A quantised handle with its quantiser in place and its rows allocated, not yet filled.
+int sq_new_handle(const char* fn, int64_t n, int D, int bits, const float* lo, const float* step, int device, int64_t id_offset,
+                  std::unique_ptr<dpq_flat>* out) {
+    std::unique_ptr<dpq_flat> f(new dpq_flat);
+    f->device = device;
+    f->n = n;
+    f->id_offset = id_offset;
+    f->D = D;
+    f->Dp = dpq::flat_sq_padded_d(D, bits);
+    f->format = bits == DPQ_SQ_8BIT ? dpq::kFlatSQ8 : dpq::kFlatSQ4;
+    f->sq_lo.assign(lo, lo + D);
+    f->sq_step.assign(step, step + D);
+    const int qlen = dpq::flat_sq_quant_len(f->Dp);
+    f->rows_at = (size_t)qlen * sizeof(float2);
+    if (int rc = f->rows.alloc(f->rows_at + (size_t)n * dpq::flat_sq_row_bytes(f->Dp, bits)))
+        return fail(rc, std::string(fn) + ": the vectors do not fit into device memory (" + dpq_last_error() + ")");
+    if (int rc = sq_upload_quant(lo, step, D, qlen, reinterpret_cast<float2*>(f->rows.get()))) return rc;
+    *out = std::move(f);
     return DPQ_OK;
 }
 
@@ -345,6 +452,118 @@ int dpq_flat_open_half(const uint16_t* vectors, int64_t n, int D, int format, in
 int dpq_flat_open_narrowed(const float* vectors, int64_t n, int D, int format, int device, int64_t id_offset, dpq_flat** out) {
     return guarded([&]() -> int {
     return flat_open("dpq_flat_open_narrowed", format, true, true, vectors, n, D, device, id_offset, out);
+    });
+}
+
+int dpq_sq_train(const float* vectors, int64_t n, int D, int bits, int device, float* lo_out, float* step_out) {
+    return guarded([&]() -> int {
+    if (int rc = sq_args("dpq_sq_train", !vectors || !lo_out || !step_out, n, D, bits, nullptr, nullptr, nullptr, true)) return rc;
+    if (int rc = flat_use_device(device)) return rc;
+    return sq_train(vectors, n, D, bits, lo_out, step_out);
+    });
+}
+
+int dpq_sq_encode(const float* vectors, int64_t n, int D, int bits, const float* lo, const float* step, int device,
+                  uint8_t* codes_out) {
+    return guarded([&]() -> int {
+    if (int rc = sq_args("dpq_sq_encode", !vectors || !codes_out, n, D, bits, nullptr, lo, step)) return rc;
+    if (int rc = flat_use_device(device)) return rc;
+    const int stride = dpq::flat_sq_row_bytes(D, bits);
+    const int64_t tile = std::max<int64_t>(1, ((int64_t)128 << 20) / ((int64_t)D * (int64_t)sizeof(float)));
+    DevBuf<float2> d_quant;
+    DevBuf<uint8_t> d_codes;
+    int rc = d_quant.alloc((size_t)D);
+    if (!rc) rc = d_codes.alloc((size_t)std::min(n, tile) * stride);
+    if (!rc) rc = sq_upload_quant(lo, step, D, D, d_quant);
+    if (rc) return rc;
+    return sq_slices(vectors, n, (size_t)D * sizeof(float), [&](const uint8_t* d_slice, int64_t r0, int64_t m) -> int {
+        DPQ_HIP(dpq::launch_flat_sq_encode(reinterpret_cast<const float*>(d_slice), m, D, bits, d_quant, d_codes, stride, nullptr));
+        DPQ_HIP(hipMemcpy(codes_out + (size_t)r0 * stride, d_codes, (size_t)m * stride, hipMemcpyDeviceToHost));
+        return DPQ_OK;
+    });
+    });
+}
+
+int dpq_sq_decode(const uint8_t* codes, int64_t n, int D, int bits, const float* lo, const float* step, float* out) {
+    return guarded([&]() -> int {
+    if (int rc = sq_args("dpq_sq_decode", !codes || !out, n, D, bits, nullptr, lo, step)) return rc;
+    const size_t stride = (size_t)dpq::flat_sq_row_bytes(D, bits);
+    for (int64_t r = 0; r < n; ++r)
+        for (int d = 0; d < D; ++d) {
+            const uint8_t b = codes[(size_t)r * stride + (bits == DPQ_SQ_8BIT ? d : d >> 1)];
+            const uint32_t c = bits == DPQ_SQ_8BIT ? b : (d & 1) ? b >> 4 : b & 15u;
+            const float scaled = (float)c * step[d];  // the product and the sum each rounded: the build passes -ffp-contract=off
+            out[(size_t)r * D + d] = lo[d] + scaled;
+        }
+    return DPQ_OK;
+    });
+}
+
+int dpq_flat_open_sq(const uint8_t* codes, int64_t n, int D, int bits, const float* lo, const float* step, int device,
+                     int64_t id_offset, dpq_flat** out) {
+    return guarded([&]() -> int {
+    const char* fn = "dpq_flat_open_sq";
+    if (out) *out = nullptr;
+    if (int rc = sq_args(fn, !codes || !out, n, D, bits, &id_offset, lo, step)) return rc;
+    if (int rc = flat_use_device(device)) return rc;
+    std::unique_ptr<dpq_flat> f;
+    if (int rc = sq_new_handle(fn, n, D, bits, lo, step, device, id_offset, &f)) return rc;
+    const int in_stride = dpq::flat_sq_row_bytes(D, bits), stride = dpq::flat_sq_row_bytes(f->Dp, bits);
+    uint8_t* rows = f->rows.get() + f->rows_at;
+    if (f->Dp == D) {
+        DPQ_HIP(hipMemcpy(rows, codes, (size_t)n * stride, hipMemcpyHostToDevice));
+    } else {
+        int rc = sq_slices(codes, n, (size_t)in_stride, [&](const uint8_t* d_slice, int64_t r0, int64_t m) -> int {
+            DPQ_HIP(dpq::launch_flat_sq_prepare(d_slice, m, D, bits, rows + (size_t)r0 * stride, stride, nullptr));
+            return DPQ_OK;
+        });
+        if (rc) return rc;
+    }
+    *out = f.release();
+    return DPQ_OK;
+    });
+}
+
+int dpq_flat_open_quantised(const float* vectors, int64_t n, int D, int bits, const float* lo, const float* step, int device,
+                            int64_t id_offset, dpq_flat** out) {
+    return guarded([&]() -> int {
+    const char* fn = "dpq_flat_open_quantised";
+    if (out) *out = nullptr;
+    if (int rc = sq_args(fn, !vectors || !out, n, D, bits, &id_offset, lo, step, true)) return rc;
+    if (int rc = flat_use_device(device)) return rc;
+    std::vector<float> trained;
+    if (!lo) {  // dpq_sq_train on these very rows
+        trained.resize((size_t)2 * D);
+        if (int rc = sq_train(vectors, n, D, bits, trained.data(), trained.data() + D)) return rc;
+        lo = trained.data();
+        step = trained.data() + D;
+    }
+    std::unique_ptr<dpq_flat> f;
+    if (int rc = sq_new_handle(fn, n, D, bits, lo, step, device, id_offset, &f)) return rc;
+    const int stride = dpq::flat_sq_row_bytes(f->Dp, bits);
+    uint8_t* rows = f->rows.get() + f->rows_at;
+    const float2* d_quant = reinterpret_cast<const float2*>(f->rows.get());
+    int rc = sq_slices(vectors, n, (size_t)D * sizeof(float), [&](const uint8_t* d_slice, int64_t r0, int64_t m) -> int {
+        DPQ_HIP(dpq::launch_flat_sq_encode(reinterpret_cast<const float*>(d_slice), m, D, bits, d_quant, rows + (size_t)r0 * stride,
+                                           stride, nullptr));
+        return DPQ_OK;
+    });
+    if (rc) return rc;
+    *out = f.release();
+    return DPQ_OK;
+    });
+}
+
+int dpq_flat_sq_get(const dpq_flat* f, int* bits, float* lo_out, float* step_out) {
+    return guarded([&]() -> int {
+    if (!f || !bits || !lo_out || !step_out) return fail(DPQ_ERR_ARG, "dpq_flat_sq_get: NULL argument");
+    if (f->format != dpq::kFlatSQ8 && f->format != dpq::kFlatSQ4)
+        return fail(DPQ_ERR_ARG, "dpq_flat_sq_get: the handle holds no scalar-quantised vectors (dpq_flat_open_sq, "
+                                 "dpq_flat_open_quantised)");
+    *bits = f->format == dpq::kFlatSQ8 ? DPQ_SQ_8BIT : DPQ_SQ_4BIT;
+    memcpy(lo_out, f->sq_lo.data(), (size_t)f->D * sizeof(float));
+    memcpy(step_out, f->sq_step.data(), (size_t)f->D * sizeof(float));
+    return DPQ_OK;
     });
 }
 

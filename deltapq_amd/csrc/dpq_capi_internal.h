@@ -157,8 +157,10 @@ struct dpq_flat {
     int device = 0;
     int64_t n = 0, id_offset = 0;
     int D = 0, Dp = 0;
-    int format = dpq::kFlatF32;   // what the open call stored: dpq::kFlatF32 .. kFlatI8
-    DevBuf<uint8_t> rows;         // [n][Dp] values of `format`
+    int format = dpq::kFlatF32;   // what the open call stored: dpq::kFlatF32 .. kFlatSQ4
+    DevBuf<uint8_t> rows;         // [n][Dp] values of `format`; a quantised handle: its quantiser in front of them, (lo, step)
+    size_t rows_at = 0;           // [flat_sq_quant_len(Dp)], and the byte at which the rows start
+    std::vector<float> sq_lo, sq_step;  // a quantised handle's quantiser [D], as dpq_flat_sq_get returns it
     DevBuf<int32_t> norm8;        // [n rounded up to 4] a byte handle's row norms
     DevBuf<int32_t> rsum8;        // [n rounded up to 4] a u8 handle's row terms of the inner product: made by its first
                                   // inner-product search or range call, kept until dpq_flat_close

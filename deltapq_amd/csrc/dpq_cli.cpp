@@ -26,7 +26,8 @@
 // reference) decodes the DTC index on the GPU back into the codes.bin.plain record layout.  -metric l2|ip (default l2)
 // switches groundtruth and recall to the inner product: dpq_flat_search_ip and its kin for the truth and the re-rank,
 // dpq_query_batch_ip for the PQ answer; the truth file is then groundtruth/N{N}Top{k}.ip.txt.  -store f16|bf16 runs
-// recall's re-rank a second time from the base narrowed to that format (dpq_flat_open_narrowed).
+// recall's re-rank a second time from the base narrowed to that format (dpq_flat_open_narrowed), -store sq8|sq4 from the
+// base scalar-quantised under the quantiser trained on it (dpq_flat_open_quantised).
 #include <sys/stat.h>
 
 #include <algorithm>
@@ -146,10 +147,12 @@ int main(int argc, char* argv[]) {
         return 2;
     }
 
-    if (!store.empty() && ((store != "f16" && store != "bf16") || task != "recall" || rerank == 0)) {
-        std::cout << "usage: -store f16|bf16 serves -task recall with -rerank R (also with -metric ip): the re-rank is run a "
-                     "second time from the base narrowed to that format (dpq_flat_open_narrowed) and its recall printed beside "
-                     "the fp32 line" << std::endl;
+    const bool store_sq = store == "sq8" || store == "sq4";
+    if (!store.empty() && ((store != "f16" && store != "bf16" && !store_sq) || task != "recall" || rerank == 0)) {
+        std::cout << "usage: -store f16|bf16|sq8|sq4 serves -task recall with -rerank R (also with -metric ip): the re-rank is "
+                     "run a second time from the base narrowed to that format (dpq_flat_open_narrowed), or scalar-quantised to 8 "
+                     "or 4 bits per dimension under the quantiser trained on the base itself (dpq_flat_open_quantised), and its "
+                     "recall printed beside the fp32 line" << std::endl;
         return 2;
     }
 
@@ -590,9 +593,9 @@ int main(int argc, char* argv[]) {
         // against base.{ext} (main.cpp:898-939) and reports the recall of that answer too.
         if (PQ_M <= 0 || PQ_K <= 0 || dataset.empty() || N < 1 || !topk_given || top_k < 1 || query_size < 1) {
             std::cout << "usage: deltapq -dataset DIR -task recall -m M -k K -N N -query_size Q -topk K [-gt_topk G] [-rerank R]"
-                         " [-store f16|bf16] [-ext fvecs|bvecs] [-filter FILE] [-opq] [-refine R [-m2 M2] [-k2 K2]] [-metric l2|ip]   (-refine: the"
+                         " [-store f16|bf16|sq8|sq4] [-ext fvecs|bvecs] [-filter FILE] [-opq] [-refine R [-m2 M2] [-k2 K2]] [-metric l2|ip]   (-refine: the"
                          " level of -task refine, M <= 8; -metric ip: dpq_query_batch_ip against the .ip.txt truth, not with -refine;"
-                         " -store: the re-rank once more from the base narrowed to fp16 / bf16)" << std::endl;
+                         " -store: the re-rank once more from the base narrowed to fp16 / bf16, or scalar-quantised to 8 / 4 bits)" << std::endl;
             return 2;
         }
         if (gt_topk < 0) gt_topk = top_k;
@@ -810,13 +813,16 @@ int main(int argc, char* argv[]) {
             if (rc) return die("dpq_recall", rc);
             snprintf(line, sizeof line, "reranked recall@%d = %.6f", top_k, rec);
             std::cout << line << std::endl;
-            if (!store.empty()) {  // the same re-rank from the base narrowed to 16 bits per value; the truth stays fp32
+            if (!store.empty()) {  // the same re-rank from the base narrowed or quantised; the truth stays fp32
                 std::vector<float> base((size_t)N * D);
                 rc = dpq_read_vecs_range(base_path.c_str(), bvecs, 0, N, &Db, base.data());
                 if (rc) return die("ItrReader", rc);
                 const float* q32 = queries.data();  // fp32, a .bvecs file widened
-                rc = dpq_flat_open_narrowed(base.data(), N, D, store == "f16" ? DPQ_HALF_F16 : DPQ_HALF_BF16, 0, 0, &f);
-                if (rc) return die("dpq_flat_open_narrowed", rc);
+                if (store_sq)
+                    rc = dpq_flat_open_quantised(base.data(), N, D, store == "sq8" ? DPQ_SQ_8BIT : DPQ_SQ_4BIT, nullptr, nullptr, 0, 0, &f);
+                else
+                    rc = dpq_flat_open_narrowed(base.data(), N, D, store == "f16" ? DPQ_HALF_F16 : DPQ_HALF_BF16, 0, 0, &f);
+                if (rc) return die(store_sq ? "dpq_flat_open_quantised" : "dpq_flat_open_narrowed", rc);
                 rc = dpq_flat_set_id_map(f, vec_id.data(), N);
                 if (rc) return die("dpq_flat_set_id_map", rc);
                 const double t2 = Elapsed();

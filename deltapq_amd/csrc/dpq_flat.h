@@ -1,7 +1,7 @@
-// dpq_flat.h -- exact search over raw vectors on the GPU, by squared L2 or by inner product: fp32 rows and fp16 / bf16
-// rows widened exactly to fp32, both under fp32 queries (dpq_flat.hip), and bytes, unsigned or signed, on the int8 matrix
-// cores (dpq_flat_u8.hip); top-k over a whole base or over the rows a filter lists, range search, re-ranking over a
-// candidate list per query.  The arithmetic is the reference's brute force (main.cpp:150-156), restated in
+// dpq_flat.h -- exact search over raw vectors on the GPU, by squared L2 or by inner product: fp32 rows, fp16 / bf16
+// rows widened exactly to fp32 and 8-bit / 4-bit scalar-quantised rows decoded to fp32, all under fp32 queries
+// (dpq_flat.hip), and bytes, unsigned or signed, on the int8 matrix cores (dpq_flat_u8.hip); top-k over a whole base or
+// over the rows a filter lists, range search, re-ranking over a candidate list per query.  The arithmetic is the reference's brute force (main.cpp:150-156), restated in
 // include/deltapq_amd.h and DESIGN.md 5.10.  A base says what its rows are once, in FlatBase::format.  The fp32-query
 // formats share one distance kernel template <LIST, MODE, METRIC, FORMAT> and one re-rank kernel <METRIC, FORMAT>; the
 // bytes have their own pair.  One stripe driver (launch_flat_search), one range pass (launch_flat_range_pass) and one
@@ -23,9 +23,10 @@ constexpr int kFlatMaxD = 2048;
 // score's bits mapped so that ascending keys are descending scores (flat_ip_word below).
 enum { kFlatL2 = 0, kFlatIP = 1 };
 // What the rows of a base are stored as.  kFlatF16 / kFlatBF16 are DPQ_HALF_F16 / DPQ_HALF_BF16.
-enum { kFlatF32 = 0, kFlatF16 = 1, kFlatBF16 = 2, kFlatU8 = 3, kFlatI8 = 4 };
-// The format of the queries a base of this format takes: fp32 for fp32 and half rows, the rows' own for bytes.
-inline int flat_query_format(int format) { return format == kFlatF16 || format == kFlatBF16 ? kFlatF32 : format; }
+// kFlatSQ8 / kFlatSQ4: codes of a scalar quantiser, DPQ_SQ_8BIT / DPQ_SQ_4BIT ("scalar-quantised vectors" below).
+enum { kFlatF32 = 0, kFlatF16 = 1, kFlatBF16 = 2, kFlatU8 = 3, kFlatI8 = 4, kFlatSQ8 = 5, kFlatSQ4 = 6 };
+// The format of the queries a base of this format takes: fp32 for fp32, half and quantised rows, the rows' own for bytes.
+inline int flat_query_format(int format) { return format == kFlatU8 || format == kFlatI8 ? format : kFlatF32; }
 // Score bits <-> high word of an inner-product key; the map is its own inverse.  -0.0 is read as +0.0 first.  A
 // non-negative score u becomes ~u & 0x7fffffff (larger scores, smaller words), a negative one keeps its bits (sign set,
 // larger magnitudes later): +inf 0x007fffff < 1.0 < +0.0 0x7fffffff < -1e-40 < -1.0 < -inf 0xff800000 < kFlatNoKey's.
@@ -93,7 +94,8 @@ int flat_query_batch(int top_k);
 
 // ---- what a search, a range pass or a re-rank runs over ----------------------------------------------------------------
 // A prepared base: rows [n][Dp] of `format`, padded with zeros -- fp32 to a multiple of four values, halves to a multiple
-// of eight, bytes (biased int8 for kFlatU8, see "byte vectors" below) to the K step of the MFMA, with their int32 norms.
+// of eight, bytes (biased int8 for kFlatU8, see "byte vectors" below) to the K step of the MFMA, with their int32 norms,
+// codes of a scalar quantiser to 16 (kFlatSQ8) or 32 (kFlatSQ4, two to a byte) with code 0, beside their quantiser.
 // The entries a pass visits are rows 0 .. n_entries - 1, or, with `filtered`, rows list[0 .. n_entries - 1] (ascending).
 // `filtered`, not the list pointer, says which: an empty filter has n_entries == 0 and may have a NULL list.
 // Reported id = row + id_offset.
@@ -106,6 +108,9 @@ struct FlatBase {
     int metric = kFlatL2;
     const int32_t* norm = nullptr;  // a byte base: the rows' norms, allocated rounded up to four rows
     const int32_t* rsum = nullptr;  // a kFlatU8 base under kFlatIP: the rows' correction terms, padded as norm is
+    // a kFlatSQ8 / kFlatSQ4 base: (lo, step) per padded dimension, (+0, +0) in the padding.  It lies in the rows' own
+    // allocation, directly in front of them (flat_sq_quant_of), where the kernels find it without an argument of its own
+    const float2* quant = nullptr;
     bool filtered = false;
     const uint32_t* list = nullptr;
     int64_t n_entries = 0;
@@ -237,6 +242,46 @@ __host__ __device__ inline uint32_t flat_half_widen(uint16_t h, int format) {
 hipError_t launch_flat_half_prepare(const uint16_t* d_in, int64_t rows, int D, int Dp, uint16_t* d_out, hipStream_t stream);
 hipError_t launch_flat_half_narrow(const float* d_in, int64_t rows, int D, int Dp, int format, uint16_t* d_out,
                                    hipStream_t stream);
+
+// ---- scalar-quantised vectors, 8 and 4 bits per dimension (dpq_flat.hip: the fp32 kernels' FORMAT) -------------------
+// A quantiser over D dimensions is (lo[d], step[d]); a code c of `bits` bits stands for lo[d] + (float)c * step[d], the
+// product and the sum each rounded in fp32 (include/deltapq_amd.h, "scalar-quantised vectors").  A base keeps one byte
+// per dimension (kFlatSQ8), rows padded to a multiple of 16 dimensions, or one nibble (kFlatSQ4: dimension 2j in the low
+// nibble of byte j), rows padded to a multiple of 32: a row is whole 16-byte loads.  The padding is code 0 under
+// (lo, step) = (+0, +0), which decodes to +0.0.  The kernels decode a value as they stage it and are the fp32 kernels in
+// everything else: an answer over a quantised base is, bit for bit, the answer over the decoded rows.
+inline int flat_sq_padded_d(int D, int bits) { return bits == 8 ? (D + 15) & ~15 : (D + 31) & ~31; }
+__host__ __device__ inline int flat_sq_row_bytes(int d, int bits) { return bits == 8 ? d : (d + 1) / 2; }  // of d dimensions' codes
+// The quantiser array of a base: (lo, step) per dimension, allocated and zeroed up to a multiple of 32 dimensions (256
+// bytes), and placed so that it ends where the rows begin: the distance and re-rank kernels keep one argument list for
+// every format and reach a quantised base's quantiser from its rows.
+__host__ __device__ inline int flat_sq_quant_len(int Dp) { return (Dp + 31) & ~31; }
+__host__ __device__ inline const float2* flat_sq_quant_of(const void* rows, int Dp) {
+    return static_cast<const float2*>(rows) - flat_sq_quant_len(Dp);
+}
+
+#ifdef __HIPCC__
+// The value of code c.  Two roundings: the build passes -ffp-contract=off, and the intrinsics say it once more.
+__device__ __forceinline__ float flat_sq_decode(uint32_t c, float2 q) { return __fadd_rn(q.x, __fmul_rn((float)c, q.y)); }
+#endif
+
+// Float bits <-> a word whose unsigned order is the order of the values (-0.0 below +0.0); the minima and maxima of
+// launch_flat_sq_minmax are such words.
+__host__ __device__ inline uint32_t flat_order_word(uint32_t u) { return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
+__host__ __device__ inline uint32_t flat_order_bits(uint32_t w) { return (w & 0x80000000u) ? (w & 0x7fffffffu) : ~w; }
+
+// d_mn / d_mx [D] order words: lowered / raised to the minimum / maximum of every column of d_in [rows][D].  The caller
+// starts them at 0xffffffff / 0.
+hipError_t launch_flat_sq_minmax(const float* d_in, int64_t rows, int D, uint32_t* d_mn, uint32_t* d_mx, hipStream_t stream);
+// fp32 rows [rows][D] -> codes, out_stride bytes per row: the codes of dimensions 0 .. D - 1 under d_quant [D], then
+// code 0 (out_stride = flat_sq_row_bytes(D, bits): the caller's layout; flat_sq_row_bytes(Dp, bits): a base's rows).
+hipError_t launch_flat_sq_encode(const float* d_in, int64_t rows, int D, int bits, const float2* d_quant, uint8_t* d_out,
+                                 int out_stride, hipStream_t stream);
+// The caller's codes [rows][flat_sq_row_bytes(D, bits)] -> a base's rows [rows][out_stride]; the spare nibble of an odd
+// D and the padding become code 0.
+hipError_t launch_flat_sq_prepare(const uint8_t* d_in, int64_t rows, int D, int bits, uint8_t* d_out, int out_stride,
+                                  hipStream_t stream);
+
 // ---- filters and range search (dpq_flat_filter.hip: the row list, the range state, the sort; no distance code) -----
 // A filter is the ascending list of a handle's eligible rows.  d_words [n_words]: bit b of word w = row 32 w + b.
 // flat_filter_count fills d_cnt / d_off [n_words] (popcounts and their exclusive prefix sum) and waits for n_allowed;

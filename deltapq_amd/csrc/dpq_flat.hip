@@ -1,5 +1,5 @@
-// dpq_flat.hip -- exact L2 distances, or inner products, between fp32 queries and fp32, fp16 or bf16 base vectors on gfx950
-// (DESIGN.md 5.10, 5.10.3, 5.10.4).
+// dpq_flat.hip -- exact L2 distances, or inner products, between fp32 queries and fp32, fp16, bf16 or scalar-quantised
+// (8-bit, 4-bit) base vectors on gfx950.
 //
 // The arithmetic (include/deltapq_amd.h, "exact search"): per dimension, in ascending order, t = v[d] - q[d] and
 // s = t * t in fp32, each rounded on its own (the build passes -ffp-contract=off), then acc += (double)s on an fp64
@@ -27,16 +27,22 @@
 //                         only code the formats do not share.  Widening is exact, so every answer over a half base
 //                         equals, bit for bit, the answer over the widened rows.  No matrix instruction: the f16 / bf16
 //                         MFMAs accumulate in fp32 and in an order of their own, which the contract does not allow.
+//                         kFlatSQ8 / kFlatSQ4: the rows are codes of a scalar quantiser, a byte or a
+//                         nibble per dimension; a lane loads 16 bytes of one row, decodes them with the slice's
+//                         (lo, step), read once per slice through scalar loads, and writes fp32 to LDS.
 //   flat_select_kernel    when a buffer is filling up: radix select of the top_k-th key, compaction in place, the
 //                         threshold lowered to that key.
 //   flat_sort_emit_kernel<METRIC>
 //                         bitonic sort of a query's keys in LDS, duplicates dropped, ids and distances (scores) written.
 //   flat_rerank_kernel<METRIC, FORMAT>
 //                         a lane per candidate; a wavefront fetches its 64 rows with 16-byte loads into LDS, 32
-//                         dimensions at a time (halves widened on the way), and every lane then walks its own row in
-//                         order.
+//                         dimensions at a time (halves widened, codes decoded on the way), and every lane then walks
+//                         its own row in order.
 //   flat_pad_rows_kernel, flat_half_prepare_kernel, flat_half_narrow_kernel
 //                         pad fp32 rows / pad 16-bit rows / narrow fp32 rows to padded 16-bit rows, when a base is opened
+//   flat_sq_minmax_kernel, flat_sq_encode_kernel, flat_sq_prepare_kernel
+//                         a scalar quantiser's training reduction (per-dimension minima and maxima, integer atomics on
+//                         order-mapped float bits), fp32 rows to codes, a caller's codes to a base's padded rows
 // launch_flat_search is the one stripe driver (state, then per stripe a select and a distance launch, then the last
 // select and the sort), launch_flat_range_pass the one range pass and launch_flat_rerank the one re-rank launcher (the
 // chunks of the grid's y extent, then the sort), for every format, with and without a list; the byte kernels of
@@ -75,7 +81,35 @@ __global__ void flat_pad_rows_kernel(const float* in, int64_t rows, int D, int D
 
 // The stored type of a row's values, and eight halves as they lie in memory -> eight fp32 values (exact: bf16 widens
 // with a shift, fp16 with v_cvt_f32_f16, which under the build's 16-bit denormal mode keeps subnormals).
-template <int FORMAT> using flat_row_t = std::conditional_t<FORMAT == kFlatF32, float, uint16_t>;
+template <int FORMAT> using flat_row_t =
+    std::conditional_t<FORMAT == kFlatF32, float, std::conditional_t<FORMAT == kFlatSQ8 || FORMAT == kFlatSQ4, uint8_t, uint16_t>>;
+template <int FORMAT> constexpr bool flat_is_sq = FORMAT == kFlatSQ8 || FORMAT == kFlatSQ4;
+// Dimensions that 16 bytes of a quantised row hold, and the byte at which dimension d (a multiple of that) of a row starts.
+template <int FORMAT> constexpr int flat_sq_dims16 = FORMAT == kFlatSQ8 ? 16 : 32;
+template <int FORMAT>
+__device__ __forceinline__ size_t flat_sq_offset(int64_t row, int Dp, int d) {
+    return FORMAT == kFlatSQ8 ? (size_t)row * Dp + d : ((size_t)row * Dp + d) >> 1;
+}
+
+// 16 bytes of a quantised row as they lie in memory -> the 16 (kFlatSQ8) or 32 (kFlatSQ4: low nibble first) fp32 values
+// of their dimensions; q: those dimensions' (lo, step), the same for every lane.
+template <int FORMAT>
+__device__ __forceinline__ void decode16(const uint4& raw, const float2* __restrict__ q, float* out) {
+    const uint32_t w[4] = {raw.x, raw.y, raw.z, raw.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const uint32_t byte = (w[i] >> (8 * b)) & 0xffu;
+            const int j = 4 * i + b;
+            if constexpr (FORMAT == kFlatSQ8) {
+                out[j] = flat_sq_decode(byte, q[j]);
+            } else {
+                out[2 * j] = flat_sq_decode(byte & 15u, q[2 * j]);
+                out[2 * j + 1] = flat_sq_decode(byte >> 4, q[2 * j + 1]);
+            }
+        }
+}
 
 template <int FORMAT>
 __device__ __forceinline__ void widen8(const uint4& raw, float* out) {
@@ -103,13 +137,19 @@ __device__ __forceinline__ void widen8(const uint4& raw, float* out) {
 // 16 bytes of rows sr and sr + 32, as it does for the queries.  Halves: the slice is 256 loads of 16 bytes, one per
 // thread; thread t takes row vr = (t & 15) | (t >> 6) << 4 and dimensions vj = ((t >> 4) & 3) * 8 .. + 7, so that the 32
 // lanes of a half wavefront write 16 consecutive rows of two slice rows that lie 8 * LD floats apart: two addresses per
-// LDS bank of a ds_write_b32, which costs nothing extra.
+// LDS bank of a ds_write_b32, which costs nothing extra.  Quantised rows: the slice is 2 KB (kFlatSQ8) or 1 KB (kFlatSQ4),
+// 128 or 64 loads of 16 bytes; thread t takes row t & 63 and, at 8 bits, dimensions (t >> 6) * 16 .. + 15 of the slice,
+// at 4 bits all 32.  A wavefront's lanes so hold 64 consecutive rows of the same dimensions: every ds_write_b32 puts the
+// 32 lanes of a half wavefront on 32 consecutive words, one address per bank, and the dimensions' (lo, step) are the
+// same for the whole wavefront, fetched once per slice by scalar loads.  The quantiser lies in front of the rows
+// (flat_sq_quant_of), so the kernel's arguments are those of every other format.
 template <bool LIST, int MODE, int METRIC, int FORMAT>
 __global__ __launch_bounds__(256) void flat_dist_kernel(const void* __restrict__ base_rows, const uint32_t* __restrict__ list,
                                                         int64_t l0, int rows, int Dp, const float* __restrict__ queries,
                                                         int nq, int64_t id_offset, uint64_t* __restrict__ keys, int cap,
                                                         const int64_t* __restrict__ offs, FlatQueryState* state) {
     const auto* base = static_cast<const flat_row_t<FORMAT>*>(base_rows);
+    [[maybe_unused]] const float2* quant = flat_sq_quant_of(base_rows, Dp);  // quantised rows only
     __shared__ float qs[DC][LD];
     __shared__ float vs[DC][LD];
     __shared__ uint32_t lrow[TV];  // LIST only
@@ -137,7 +177,20 @@ __global__ __launch_bounds__(256) void flat_dist_kernel(const void* __restrict__
         for (int j = 0; j < 4; ++j) acc[i][j] = 0.0;
 
     for (int d0 = 0; d0 < Dp; d0 += DC) {
-        if constexpr (FORMAT != kFlatF32) {
+        if constexpr (flat_is_sq<FORMAT>) {
+            constexpr int N16 = flat_sq_dims16<FORMAT>;
+            const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);  // the wavefront: DC / N16 of the four stage
+            const int cj = wv * N16;                                  // its first dimension of the slice
+            if (wv < DC / N16 && d0 + cj < Dp) {                      // Dp is a multiple of N16
+                const int cr = tid & 63;
+                uint4 raw = make_uint4(0u, 0u, 0u, 0u);  // past the stripe: code 0, masked below
+                if (v0 + cr < rows) raw = *reinterpret_cast<const uint4*>(base + flat_sq_offset<FORMAT>(row_of(cr), Dp, d0 + cj));
+                float v[N16];
+                decode16<FORMAT>(raw, quant + d0 + cj, v);
+#pragma unroll
+                for (int k = 0; k < N16; ++k) vs[cj + k][cr] = v[k];
+            }
+        } else if constexpr (FORMAT != kFlatF32) {
             uint4 raw = make_uint4(0u, 0u, 0u, 0u);  // the bits of eight zeros in either format
             if (v0 + vr < rows && d0 + vj < Dp) raw = *reinterpret_cast<const uint4*>(base + (size_t)row_of(vr) * Dp + d0 + vj);
             float v[8];
@@ -340,7 +393,9 @@ __global__ __launch_bounds__(kSelThreads) void flat_sort_emit_kernel(const uint6
 
 // grid (candidate groups of 256, queries), 256 threads: lane = candidate.  FORMAT decides how a wavefront fetches the
 // 32-dimension slice of its 64 rows into its tile: eight rounds of 8 rows, eight lanes of 16 bytes (four floats) per row,
-// or, for halves, four rounds of 16 rows, four lanes of 16 bytes (eight halves, widened) per row.
+// or, for halves, four rounds of 16 rows, four lanes of 16 bytes (eight halves, widened) per row.  Quantised rows: a lane
+// per row, 16 bytes of it per round -- two rounds of 16 dimensions at 8 bits, one of 32 at 4 -- so that a round's
+// (lo, step) are the same for every lane (scalar loads) and a lane decodes into its own row of the tile.
 template <int METRIC, int FORMAT>
 __global__ __launch_bounds__(256) void flat_rerank_kernel(const void* __restrict__ base_rows, int64_t n, int D, int Dp,
                                                           const float* __restrict__ queries,
@@ -348,6 +403,7 @@ __global__ __launch_bounds__(256) void flat_rerank_kernel(const void* __restrict
                                                           int64_t id_offset, const uint32_t* __restrict__ map,
                                                           int64_t n_map, uint64_t* __restrict__ keys, uint32_t* flag) {
     const auto* base = static_cast<const flat_row_t<FORMAT>*>(base_rows);
+    [[maybe_unused]] const float2* quant = flat_sq_quant_of(base_rows, Dp);  // quantised rows only
     __shared__ float qv[kFlatMaxD];
     __shared__ float tile[4][64][DC + 1];
     const int q = blockIdx.y, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -359,7 +415,19 @@ __global__ __launch_bounds__(256) void flat_rerank_kernel(const void* __restrict
     double acc = 0.0;
     const int lj = FORMAT == kFlatF32 ? (lane & 7) * 4 : (lane & 3) * 8;  // the lane's first dimension of a fetched slice
     for (int d0 = 0; d0 < Dp; d0 += DC) {
-        if constexpr (FORMAT == kFlatF32) {
+        if constexpr (flat_is_sq<FORMAT>) {
+            constexpr int N16 = flat_sq_dims16<FORMAT>;
+#pragma unroll
+            for (int cj = 0; cj < DC; cj += N16) {
+                if (d0 + cj >= Dp) break;  // Dp is a multiple of N16
+                uint4 raw = make_uint4(0u, 0u, 0u, 0u);
+                if (row >= 0) raw = *reinterpret_cast<const uint4*>(base + flat_sq_offset<FORMAT>(row, Dp, d0 + cj));
+                float v[N16];
+                decode16<FORMAT>(raw, quant + d0 + cj, v);
+#pragma unroll
+                for (int k = 0; k < N16; ++k) tile[w][lane][cj + k] = v[k];
+            }
+        } else if constexpr (FORMAT == kFlatF32) {
 #pragma unroll
             for (int it = 0; it < 8; ++it) {
                 const int cc = it * 8 + (lane >> 3);
@@ -409,6 +477,64 @@ __global__ __launch_bounds__(256) void flat_half_narrow_kernel(const float* __re
         const int64_t r = i / Dp;
         const int d = (int)(i - r * Dp);
         out[i] = d < D ? flat_half_narrow(__float_as_uint(in[r * D + d]), format) : (uint16_t)0;
+    }
+}
+
+// The kernels of a scalar quantiser.  Min / max: block (64, 4), thread (x, y) walks column blockIdx.y * 64 + x over rows
+// y, y + 4, .. of the block's kSqRows and folds its minimum and maximum into the column's order words.
+constexpr int kSqRows = 1024;
+__global__ __launch_bounds__(256) void flat_sq_minmax_kernel(const float* __restrict__ in, int64_t rows, int D,
+                                                             uint32_t* __restrict__ mn, uint32_t* __restrict__ mx) {
+    const int d = blockIdx.y * 64 + threadIdx.x;
+    const int64_t r0 = (int64_t)blockIdx.x * kSqRows, r1 = min(rows, r0 + kSqRows);
+    if (d >= D || r0 + threadIdx.y >= r1) return;
+    uint32_t lo = 0xffffffffu, hi = 0u;
+    for (int64_t r = r0 + threadIdx.y; r < r1; r += 4) {
+        const uint32_t w = flat_order_word(__float_as_uint(in[r * D + d]));
+        lo = min(lo, w);
+        hi = max(hi, w);
+    }
+    atomicMin(&mn[d], lo);
+    atomicMax(&mx[d], hi);
+}
+
+// The code of v (include/deltapq_amd.h, "scalar-quantised vectors"): fp64 subtract, fp64 divide, ties to even, clamp.
+__device__ __forceinline__ uint32_t flat_sq_code(float v, float2 q, double top) {
+    if (q.y == 0.0f) return 0u;
+    const double u = ((double)v - (double)q.x) / (double)q.y;
+    return (uint32_t)(int)fmin(fmax(rint(u), 0.0), top);
+}
+
+// One byte of the output per step of the grid-stride loop.
+__global__ __launch_bounds__(256) void flat_sq_encode_kernel(const float* __restrict__ in, int64_t rows, int D, int bits,
+                                                             const float2* __restrict__ quant, uint8_t* __restrict__ out,
+                                                             int out_stride) {
+    const int64_t total = rows * out_stride, step = (int64_t)gridDim.x * blockDim.x;
+    const double top = bits == 8 ? 255.0 : 15.0;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += step) {
+        const int64_t r = i / out_stride;
+        const int j = (int)(i - r * out_stride);
+        uint32_t c = 0;
+        if (bits == 8) {
+            if (j < D) c = flat_sq_code(in[r * D + j], quant[j], top);
+        } else {
+            if (2 * j < D) c = flat_sq_code(in[r * D + 2 * j], quant[2 * j], top);
+            if (2 * j + 1 < D) c |= flat_sq_code(in[r * D + 2 * j + 1], quant[2 * j + 1], top) << 4;
+        }
+        out[i] = (uint8_t)c;
+    }
+}
+
+__global__ __launch_bounds__(256) void flat_sq_prepare_kernel(const uint8_t* __restrict__ in, int64_t rows, int D, int bits,
+                                                              uint8_t* __restrict__ out, int out_stride) {
+    const int64_t total = rows * out_stride, step = (int64_t)gridDim.x * blockDim.x;
+    const int in_stride = flat_sq_row_bytes(D, bits);
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += step) {
+        const int64_t r = i / out_stride;
+        const int j = (int)(i - r * out_stride);
+        uint8_t c = j < in_stride ? in[r * in_stride + j] : (uint8_t)0;
+        if (bits == 4 && 2 * j + 1 >= D) c &= 15u;  // the spare nibble of an odd D
+        out[i] = c;
     }
 }
 
@@ -467,6 +593,29 @@ hipError_t launch_flat_half_narrow(const float* d_in, int64_t rows, int D, int D
     return hipGetLastError();
 }
 
+hipError_t launch_flat_sq_minmax(const float* d_in, int64_t rows, int D, uint32_t* d_mn, uint32_t* d_mx, hipStream_t stream) {
+    if (rows <= 0) return hipSuccess;
+    flat_sq_minmax_kernel<<<dim3((unsigned)((rows + kSqRows - 1) / kSqRows), (D + 63) / 64), dim3(64, 4), 0, stream>>>(
+        d_in, rows, D, d_mn, d_mx);
+    return hipGetLastError();
+}
+
+hipError_t launch_flat_sq_encode(const float* d_in, int64_t rows, int D, int bits, const float2* d_quant, uint8_t* d_out,
+                                 int out_stride, hipStream_t stream) {
+    const int64_t total = rows * out_stride;
+    if (total <= 0) return hipSuccess;
+    flat_sq_encode_kernel<<<dim3(grid_for(total)), dim3(256), 0, stream>>>(d_in, rows, D, bits, d_quant, d_out, out_stride);
+    return hipGetLastError();
+}
+
+hipError_t launch_flat_sq_prepare(const uint8_t* d_in, int64_t rows, int D, int bits, uint8_t* d_out, int out_stride,
+                                  hipStream_t stream) {
+    const int64_t total = rows * out_stride;
+    if (total <= 0) return hipSuccess;
+    flat_sq_prepare_kernel<<<dim3(grid_for(total)), dim3(256), 0, stream>>>(d_in, rows, D, bits, d_out, out_stride);
+    return hipGetLastError();
+}
+
 namespace {
 
 template <bool LIST, int MODE, int METRIC, int FORMAT>
@@ -500,14 +649,22 @@ void sort_emit(int metric, const uint64_t* d_keys, size_t stride, const FlatQuer
                                                                                      top_k, d_ids, d_dists);
 }
 
+// A quantised base keeps its quantiser where the kernels look for it.
+bool sq_layout_ok(const FlatBase& b) {
+    return (b.format != kFlatSQ8 && b.format != kFlatSQ4) || (b.quant && b.quant == flat_sq_quant_of(b.rows, b.Dp));
+}
+
 // One distance launch over entries e0 .. e0 + rows - 1 of the base, by format, metric, row source and mode.
 hipError_t launch_flat_dist(int mode, const FlatBase& b, int64_t e0, int rows, const FlatQueries& q, uint64_t* keys, int cap,
                             const int64_t* offs, FlatQueryState* state, hipStream_t stream) {
+    if (!sq_layout_ok(b)) return hipErrorInvalidValue;
     switch (b.format) {
         case kFlatU8:
         case kFlatI8: return launch_flat_dist_u8(mode, b, e0, rows, q, keys, cap, offs, state, stream);
         case kFlatF16: pick_dist<kFlatF16>(b.metric, b.filtered, mode)(b, e0, rows, q, keys, cap, offs, state, stream); break;
         case kFlatBF16: pick_dist<kFlatBF16>(b.metric, b.filtered, mode)(b, e0, rows, q, keys, cap, offs, state, stream); break;
+        case kFlatSQ8: pick_dist<kFlatSQ8>(b.metric, b.filtered, mode)(b, e0, rows, q, keys, cap, offs, state, stream); break;
+        case kFlatSQ4: pick_dist<kFlatSQ4>(b.metric, b.filtered, mode)(b, e0, rows, q, keys, cap, offs, state, stream); break;
         default: pick_dist<kFlatF32>(b.metric, b.filtered, mode)(b, e0, rows, q, keys, cap, offs, state, stream);
     }
     return hipGetLastError();
@@ -556,6 +713,7 @@ hipError_t launch_flat_range_pass(const FlatBase& b, const FlatQueries& q, uint6
 
 hipError_t launch_flat_rerank(const FlatBase& b, const FlatRerank& r, hipStream_t stream) {
     if (r.nq <= 0) return hipSuccess;
+    if (!sq_layout_ok(b)) return hipErrorInvalidValue;
     hipError_t e = ensure_sort_lds();
     if (e != hipSuccess) return e;
     const int n_pad = pow2_at_least(r.n_cand);
@@ -571,6 +729,8 @@ hipError_t launch_flat_rerank(const FlatBase& b, const FlatRerank& r, hipStream_
             case kFlatI8: launch_flat_rerank_chunk_u8(b, c, n_pad, stream); break;
             case kFlatF16: rerank_chunk<kFlatF16>(b, c, n_pad, stream); break;
             case kFlatBF16: rerank_chunk<kFlatBF16>(b, c, n_pad, stream); break;
+            case kFlatSQ8: rerank_chunk<kFlatSQ8>(b, c, n_pad, stream); break;
+            case kFlatSQ4: rerank_chunk<kFlatSQ4>(b, c, n_pad, stream); break;
             default: rerank_chunk<kFlatF32>(b, c, n_pad, stream);
         }
     }

@@ -54,6 +54,9 @@
  *   (none: FAISS's IndexScalarQuantizer fp16 /  dpq_flat_open_half / dpq_flat_open_narrowed, then every fp32-query
  *     bf16 under IndexFlat's calls, and           dpq_flat_* call; dpq_half_from_float / dpq_half_to_float
  *     IndexRefineFlat over it)
+ *   (none: FAISS's IndexScalarQuantizer         dpq_sq_train / dpq_sq_encode / dpq_sq_decode, dpq_flat_open_sq /
+ *     QT_8bit / QT_4bit under IndexFlat's         dpq_flat_open_quantised, dpq_flat_sq_get, then every fp32-query
+ *     calls, IndexRefine over it)                 dpq_flat_* call
  *
  * Conventions: plain pointers and sizes only; the caller owns every host
  * buffer it passes, the library owns device memory.  Every function returns a
@@ -848,7 +851,7 @@ int dpq_merge_topk_ip_host(const int32_t* ids, const float* scores, int n_lists,
  * dpq_flat_filter_count work on an i8 handle), dpq_flat_set_id_map with the even-n_map rule, negative candidates as
  * padding, a row named twice counting once, the flag word of the device forms, dpq_flat_close, dpq_merge_topk_host (L2)
  * and dpq_merge_topk_ip_host (scores).
- * Handle kinds do not mix: fp32 (and half), u8 and i8 handles each take the calls of their own kind; any other is
+ * Handle kinds do not mix: fp32 (and half, and scalar-quantised), u8 and i8 handles each take the calls of their own kind; any other is
  * DPQ_ERR_ARG with a message that names the function to call instead.  fp32 queries against byte rows are out of scope. */
 int dpq_flat_open_i8(const int8_t* vectors, int64_t n, int D, int device, int64_t id_offset, dpq_flat** out);
 int dpq_flat_search_ip_u8(dpq_flat* f, const uint8_t* queries, int nq, int top_k, int32_t* ids, float* scores);
@@ -917,6 +920,61 @@ int dpq_flat_open_half(const uint16_t* vectors /* [n][D], host */, int64_t n, in
  * slices of at most 128 MB: indistinguishable from dpq_flat_open_half over dpq_half_from_float of the same rows. */
 int dpq_flat_open_narrowed(const float* vectors /* [n][D], host */, int64_t n, int D, int format, int device,
                            int64_t id_offset, dpq_flat** out);
+
+/* ---- exact search over scalar-quantised vectors: 8 and 4 bits per dimension ---
+ * Between a PQ code (8 B per 128-d vector, 16 B with a refine level) and a half handle (256 B) sits a scalar quantiser:
+ * one byte (128 B) or one nibble (64 B) per dimension, with a trained offset and step per dimension, under fp32 queries.
+ * FAISS's IndexScalarQuantizer(QT_8bit / QT_4bit) under IndexFlat's calls, and IndexRefine over it.  The rules below
+ * are this library's own; tests/_sq_restatement.py restates them in numpy and the GPU meets them bit for bit.
+ * bits is DPQ_SQ_8BIT or DPQ_SQ_4BIT and L = 2^bits - 1.  A quantiser over D dimensions is two fp32 arrays, lo[D] and
+ * step[D].
+ * Train (dpq_sq_train).  Per dimension lo[d] is the minimum and hi[d] the maximum of the training values; a result of
+ * -0.0 is stored as +0.0.  step[d] = (float)(((double)hi[d] - (double)lo[d]) / (double)L): one fp64 subtract, one fp64
+ * divide, one rounding to fp32.  A constant column gives step = +0.0.  Non-finite inputs, and a range whose step is not
+ * finite, are out of scope.  lo = 0.1f (0x3dcccccd), hi = 0.7f (0x3f333333): the 8-bit step is 0x3b1a33cd, the 4-bit
+ * step 0x3d23d70a.
+ * Encode.  step[d] == 0 gives code 0.  Otherwise u = ((double)v - (double)lo[d]) / (double)step[d], one fp64 subtract and
+ * one fp64 divide; c = rint(u), ties to even, clamped to [0, L] before the conversion to an integer: values outside the
+ * trained range saturate.  With lo = 0, step = 1 and 8 bits, 0.5, 1.5, 2.5, 254.5, 255.5, 300 and -3 encode to 0, 2, 2,
+ * 254, 255, 255 and 0.  Under the quantiser above 0.4f encodes to 128 at 8 bits and to 8 at 4 bits.
+ * Decode.  x = lo[d] + (float)c * step[d] in fp32, the product and the sum each rounded on its own; no fused
+ * multiply-add.  Under the quantiser above code 128 decodes to 0x3ecd6700 at 8 bits, code 8 to 0x3ed70a3d at 4 bits;
+ * lo = 0x3eb0f069, step = 0x3b82a8a7, c = 111 decodes to 0x3f49c676 (a fused decode would give 0x3f49c675).
+ * Storage.  8 bits: one byte per dimension, D bytes per row.  4 bits: dimension 2j in the low nibble and 2j + 1 in the
+ * high nibble of byte j, (D + 1) / 2 bytes per row; the spare nibble of an odd D is written as 0 and ignored when read.
+ * Search.  There are no new search calls: a quantised handle takes every fp32-query call the half section lists.  Queries
+ * are fp32 and never quantised.  Every such call on a quantised handle gives ids, float bits and lims equal, bit for bit,
+ * to the same call on a dpq_flat_open handle over dpq_sq_decode of the codes.  The L2 and the inner-product rule, the key
+ * order and the padding rows, DPQ_ERR_TOPK, the id map with its even-n_map rule, the flag word of the device forms and
+ * the order of the argument checks all carry over unchanged.  A _u8 or _i8 call on a quantised handle is DPQ_ERR_ARG
+ * with a message that names the fp32 function.
+ * Argument errors, DPQ_ERR_ARG, in this order and before any device call: a NULL pointer; n < 1; D outside 1..2048; bits
+ * outside {4, 8}; id_offset as in dpq_flat_open; a lo that is not finite; a step that is negative, NaN or infinite;
+ * exactly one of lo / step given to dpq_flat_open_quantised.  Then the device: DPQ_ERR_NO_DEVICE without one.
+ * Device memory of a handle: n * Dp bytes at 8 bits (Dp = D rounded up to a multiple of 16), n * Dp / 2 bytes at 4 bits
+ * (Dp = D rounded up to a multiple of 32), 8 bytes per padded dimension (rounded up to 32 dimensions), and the
+ * workspaces of an fp32 handle; while a call runs that uploads in slices, a buffer of at most 128 MB on top of that. */
+#define DPQ_SQ_8BIT 8
+#define DPQ_SQ_4BIT 4
+/* vectors[n][D], host memory -> lo_out[D], step_out[D].  The minima and maxima are reduced on the GPU, over upload
+ * slices of at most 128 MB. */
+int dpq_sq_train(const float* vectors, int64_t n, int D, int bits, int device, float* lo_out, float* step_out);
+/* vectors[n][D], host memory -> codes_out[n][D] (8 bits) or [n][(D + 1) / 2] (4 bits), encoded on the GPU in the same
+ * slices. */
+int dpq_sq_encode(const float* vectors, int64_t n, int D, int bits, const float* lo, const float* step, int device,
+                  uint8_t* codes_out);
+/* Host only, no device: codes as dpq_sq_encode writes them -> out[n][D]. */
+int dpq_sq_decode(const uint8_t* codes, int64_t n, int D, int bits, const float* lo, const float* step, float* out);
+/* A handle over codes the caller already has, uploaded as they are and padded on the GPU. */
+int dpq_flat_open_sq(const uint8_t* codes, int64_t n, int D, int bits, const float* lo, const float* step, int device,
+                     int64_t id_offset, dpq_flat** out);
+/* The same handle from fp32 rows, quantised on the GPU in upload slices of at most 128 MB.  lo and step are both given,
+ * or both NULL: the quantiser is then trained on these very rows.  Indistinguishable from dpq_sq_train (when NULL), then
+ * dpq_sq_encode, then dpq_flat_open_sq. */
+int dpq_flat_open_quantised(const float* vectors /* [n][D], host */, int64_t n, int D, int bits, const float* lo,
+                            const float* step, int device, int64_t id_offset, dpq_flat** out);
+/* The quantiser of a quantised handle: *bits, lo_out[D], step_out[D].  DPQ_ERR_ARG on a handle of any other kind. */
+int dpq_flat_sq_get(const dpq_flat* f, int* bits, float* lo_out, float* step_out);
 
 /* ---- residual re-ranking: a second PQ level refines a shortlist ---------------
  * Every answer of dpq_query_batch is a coarse PQ approximation, and dpq_flat_rerank needs the raw vectors on the GPU
