@@ -133,6 +133,25 @@ __global__ __launch_bounds__(kAssignThreads) void train_assign_kernel(
                 best_k[j] = k;
             }
     }
+    // Nothing was below FLT_MAX (every distance +inf, or FLT_MAX itself): the label stays 0, dpq_encode_pq's, and the
+    // winning distance is the computed distance to that codeword, not the FLT_MAX the search started from.  Off
+    // the hot loop: the sub-vector is still in registers, so this is one more codeword for the rare thread.
+#pragma unroll
+    for (int j = 0; j < V; ++j)
+        if (!(best[j] < FLT_MAX)) {
+            float d0 = 0.0f;
+#pragma unroll
+            for (int q = 0; q < Q; ++q) {
+                const float4 c = cw[q];
+                const float ce[4] = {c.x, c.y, c.z, c.w};
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float diff = __fsub_rn(x[j][4 * q + e], ce[e]);
+                    d0 = __fadd_rn(d0, __fmul_rn(diff, diff));
+                }
+            }
+            best[j] = d0;
+        }
     double ds = 0.0;
     uint32_t ch = 0;
 #pragma unroll

@@ -335,7 +335,11 @@ int dpq_encode_pq(const float* vectors, int64_t n, int D, const float* codewords
  *           the largest, converged is 1 only if every run converged, distortion[] is run 0's trace.
  *   Assign  dpq_encode_pq's arithmetic: per codeword `diff = v - c; dist += diff * diff` in fp32, subtract, multiply
  *           and add rounded separately, dimensions in order, strict `<` (the lowest k wins a tie).  The labels of a
- *           round are dpq_encode_pq(vectors, the codebook entering that round).
+ *           round are dpq_encode_pq(vectors, the codebook entering that round): the search starts at FLT_MAX, so the
+ *           label is 0 when no distance is below FLT_MAX.  The winning distance is the computed distance to the
+ *           reported label, never the FLT_MAX the search starts from: it is +inf when every distance overflows (and
+ *           the potential, the distortion and the restart comparison are +inf with it: runs that tie there keep the
+ *           lowest r).  NaN inputs are unspecified.
  *   Stop    a sub-space stops right after an assignment (not the first) that changes no label and leaves no cluster
  *           empty: its codebook already is the mean of those labels.  It is not touched again.  Otherwise after
  *           max_iters rounds.
@@ -349,7 +353,8 @@ int dpq_encode_pq(const float* vectors, int64_t n, int D, const float* codewords
  * The same input gives the same bytes, run to run.  opts == NULL: device 0, 25 rounds, seed 0.  DPQ_ERR_ARG, before
  * any device call: a NULL pointer, D < 1, M < 1 or > 256, K outside 2..256, K > n, n * M >= 2^31, max_iters
  * outside 1..64, init outside 0..1, restarts outside 0..16, init == 1 together with use_initial != 0, a sub-space
- * whose codewords need more than 160 KB of LDS (Ds > 160, or K * Ds close to 40960).
+ * whose codewords need more than 160 KB of LDS (Ds > 160, or 4 * K * W + 1072 > 163840 bytes with W = Ds rounded up to
+ * 4, 8, 12, 16, 24, 32, 64, 96, 128 or 160: K <= 254 at Ds 129..160, every K at Ds <= 128).
  * Without a GPU: DPQ_ERR_NO_DEVICE.  Device memory: about 4 * n * M * (Ds rounded up to 4..160) + 16 * n * M bytes. */
 typedef struct dpq_train_opts {
     int32_t device;

@@ -7,7 +7,9 @@ with this file bit for bit.
   start    the caller's codebook, or K rows drawn by the splitmix64 partial shuffle below, the same rows for
            every sub-space
   assign   oracle/pq_encode_oracle.py's arithmetic (fp32, separately rounded subtract / multiply / add,
-           dimensions in order, first minimum wins), keeping the winning distance
+           dimensions in order) and its selection (start at FLT_MAX, strict `<`: the first minimum wins, and the label
+           is 0 when no distance is below FLT_MAX); the winning distance is the computed distance to that label,
+           +inf when every distance overflows
   stop     after an assignment (not the first) that changes no label and leaves no cluster empty
   update   fp64 sum, starting from +0.0, of the members' fp32 values in ascending vector index, one add after the
            other (a cumulative sum over the members in that order), / float64(count), rounded once to fp32
@@ -15,6 +17,8 @@ with this file bit for bit.
            vector index ascending); the donor stays in its old cluster's mean of this round
 """
 import numpy as np
+
+from oracle import pq_encode_oracle as E     # the encoder's selection rule: one statement of it, not two
 
 _MASK = (1 << 64) - 1
 
@@ -44,13 +48,16 @@ def split(vectors, M):
 
 
 def assign(sub, c):
-    """labels int64 [n], winning distances float32 [n]."""
+    """labels int64 [n], winning distances float32 [n].  The label is the encoder's own selection
+    (oracle/pq_encode_oracle.py: start at FLT_MAX, strict `<`, so 0 when nothing is below FLT_MAX), and the winning
+    distance is the computed distance to that label: +inf when every distance overflows."""
     n, Ds = sub.shape
     dist = np.zeros((n, len(c)), dtype=np.float32)
-    for d in range(Ds):
-        diff = (sub[:, d:d + 1] - c[:, d][None, :]).astype(np.float32)
-        dist = (dist + (diff * diff).astype(np.float32)).astype(np.float32)
-    lab = dist.argmin(1)                      # argmin returns the first minimum
+    with np.errstate(over="ignore", invalid="ignore", under="ignore"):
+        for d in range(Ds):
+            diff = (sub[:, d:d + 1] - c[:, d][None, :]).astype(np.float32)
+            dist = (dist + (diff * diff).astype(np.float32)).astype(np.float32)
+    lab = E.select(dist)
     return lab, dist[np.arange(n), lab]
 
 
@@ -78,8 +85,9 @@ def update(sub, lab, win, c):
 
 
 def train(vectors, M, K, max_iters=25, seed=0, init=None):
-    """(codebook float32 [M][K][Ds], stats) -- stats also carries the codebook entering the last round and that
-    round's labels per sub-space."""
+    """(codebook float32 [M][K][Ds], stats) -- stats also carries the last round's labels per sub-space, and per
+    round the winning distances its distortion sums (`wins`, float32 [M][n]) and the sub-spaces still active after
+    its stop rule (`active`)."""
     subs = split(vectors, M)
     n, Ds = subs[0].shape
     if init is None:
@@ -89,9 +97,11 @@ def train(vectors, M, K, max_iters=25, seed=0, init=None):
         cb = np.array(init, dtype=np.float32)
         assert cb.shape == (M, K, Ds)
     labels = [None] * M
+    wins = [None] * M
     sums = [0.0] * M
     active = [True] * M
     distortion, reseeded, iters_run, converged = [], 0, 0, False
+    win_trace, active_trace = [], []
     for r in range(max_iters):
         iters_run = r + 1
         todo = []
@@ -102,12 +112,15 @@ def train(vectors, M, K, max_iters=25, seed=0, init=None):
             changed = n if labels[m] is None else int((lab != labels[m]).sum())
             n_empty = K - len(np.unique(lab))
             labels[m] = lab
+            wins[m] = win
             sums[m] = float(win.astype(np.float64).sum())
             if r > 0 and changed == 0 and n_empty == 0:
                 active[m] = False
             else:
                 todo.append((m, lab, win))
         distortion.append(float(sum(sums)))
+        win_trace.append(np.stack(wins))
+        active_trace.append(list(active))
         if not any(active):
             converged = True
             break
@@ -115,4 +128,4 @@ def train(vectors, M, K, max_iters=25, seed=0, init=None):
             cb[m], e = update(subs[m], lab, win, cb[m])
             reseeded += e
     return cb, dict(iters_run=iters_run, converged=int(converged), reseeded=reseeded, distortion=distortion,
-                    labels=np.stack(labels, axis=1))
+                    labels=np.stack(labels, axis=1), wins=win_trace, active=active_trace)
