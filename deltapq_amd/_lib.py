@@ -211,6 +211,14 @@ SYMBOLS = [
     ("dpq_flat_open_sq", ctypes.c_int, [_VP, c_i64, ctypes.c_int, ctypes.c_int, _VP, _VP, ctypes.c_int, c_i64, P(_VP)]),
     ("dpq_flat_open_quantised", ctypes.c_int, [_VP, c_i64, ctypes.c_int, ctypes.c_int, _VP, _VP, ctypes.c_int, c_i64, P(_VP)]),
     ("dpq_flat_sq_get", ctypes.c_int, [_VP, P(ctypes.c_int), _VP, _VP]),
+    ("dpq_flat_open_bits", ctypes.c_int, [_VP, c_i64, ctypes.c_int, ctypes.c_int, c_i64, P(_VP)]),
+    ("dpq_bits_from_float", ctypes.c_int, [_VP, c_i64, ctypes.c_int, _VP, ctypes.c_int, _VP]),
+    ("dpq_flat_open_binarised", ctypes.c_int, [_VP, c_i64, ctypes.c_int, _VP, ctypes.c_int, c_i64, P(_VP)]),
+    ("dpq_flat_search_bits", ctypes.c_int, [_VP, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP]),
+    ("dpq_flat_search_filtered_bits", ctypes.c_int, [_VP, _VP, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP]),
+    ("dpq_flat_range_search_bits", ctypes.c_int, [_VP, _VP, _VP, ctypes.c_int, _VP, P(_VP)]),
+    ("dpq_flat_rerank_bits", ctypes.c_int, [_VP, _VP, ctypes.c_int, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP]),
+    ("dpq_flat_rerank_bits_device", ctypes.c_int, [_VP, _VP, ctypes.c_int, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP]),
     ("dpq_range_recall", ctypes.c_int, [ctypes.c_int, _VP, _VP, _VP, _VP, P(ctypes.c_double), P(ctypes.c_double)]),
     ("dpq_bitmap_to_dfs", ctypes.c_int, [_VP, c_i64, _VP, c_i64, _VP]),
     ("dpq_write_bitmap", ctypes.c_int, [ctypes.c_char_p, _VP, c_i64]),

@@ -1070,7 +1070,7 @@ class IdFilter:
 
 
 class FlatIdFilter:
-    """A filter of FlatIndex / FlatIndexU8 / FlatIndexI8 .search_filtered and .range_search (dpq_flat_filter): the set of reported ids
+    """A filter of FlatIndex / FlatIndexU8 / FlatIndexI8 / FlatIndexBits .search_filtered and .range_search (dpq_flat_filter): the set of reported ids
     (row + id_offset) a search may return, compacted once on the index's device into a list of eligible rows.  The bitmap
     convention is IdFilter's; ids at or beyond n_bits are not allowed."""
 
@@ -1156,10 +1156,15 @@ class _FlatIndexBase:
 
     _l2, _ip = "", "_ip"
 
+    @property
+    def _qcols(self):
+        """Elements of one query: D, or the bytes of D bits."""
+        return self.D
+
     def _queries(self, queries):
         q = self._as_queries(queries)
-        if q.ndim != 2 or q.shape[1] != self.D:
-            raise ValueError("queries must be [nq][%d]" % self.D)
+        if q.ndim != 2 or q.shape[1] != self._qcols:
+            raise ValueError("queries must be [nq][%d]" % self._qcols)
         return q
 
     def _search(self, name, queries, top_k, *id_filter):
@@ -1238,7 +1243,7 @@ class _FlatIndexBase:
     def _rerank_torch(self, name, queries, cand_ids, top_k, out_ids, out_dists):
         import torch
         self._check_tensor(queries)
-        assert queries.is_cuda and queries.is_contiguous() and queries.shape[1] == self.D
+        assert queries.is_cuda and queries.is_contiguous() and queries.shape[1] == self._qcols
         assert cand_ids.is_cuda and cand_ids.dtype == torch.int32 and cand_ids.is_contiguous()
         assert cand_ids.shape[0] == queries.shape[0]
         nq = queries.shape[0]
@@ -1539,6 +1544,80 @@ class FlatIndexI8(FlatIndexU8):
         if not isinstance(a, np.ndarray) or a.dtype != np.int8 or not a.flags.c_contiguous:
             raise TypeError("%s must be a C-contiguous int8 array (FlatIndexU8 takes uint8, FlatIndex fp32)" % what)
         return a
+
+
+def _bits_thresholds(thresholds, D):
+    if thresholds is None:
+        return None
+    t = np.asarray(thresholds)
+    if t.dtype != np.float32:
+        raise TypeError("thresholds must be float32 (got %s)" % t.dtype)
+    if t.shape != (D,):
+        raise ValueError("thresholds must be [%d]" % D)
+    return np.ascontiguousarray(t)
+
+
+def bits_from_float(vectors, thresholds=None, device=0):
+    """float32 vectors [n][D] -> uint8 [n][(D + 7) // 8] packed bits, bit d = vectors[:, d] > thresholds[d] (> 0 without
+    thresholds), dimension d in bit d & 7 of byte d >> 3, spare bits 0 (dpq_bits_from_float; on the GPU)."""
+    v = _sq_rows(vectors)
+    t = _bits_thresholds(thresholds, v.shape[1])
+    out = np.empty((v.shape[0], (v.shape[1] + 7) // 8), dtype=np.uint8)
+    check(_lib.load().dpq_bits_from_float(_np_ptr(v), v.shape[0], v.shape[1], None if t is None else _np_ptr(t), device,
+                                          _np_ptr(out)), "dpq_bits_from_float")
+    return out
+
+
+class FlatIndexBits(FlatIndexU8):
+    """Binary vectors on one GPU, one bit per dimension (dpq_flat_open_bits): `bits` is a uint8 array [n][(D + 7) // 8],
+    dimension d in bit d & 7 of byte d >> 3 (np.packbits(..., bitorder="little")); the spare bits of the last byte are
+    ignored.  search, search_filtered, range_search, rerank and rerank_torch answer by Hamming distance, reported as a
+    float32, in the order and with the padding of the L2 calls (dpq_flat_*_bits); queries are packed the same way.  There
+    is no inner product over bits: the *_ip methods raise the library's DpqError.  from_float binarises float32 rows on
+    the GPU (dpq_flat_open_binarised).  Takes uint8 arrays and tensors only."""
+
+    _l2, _ip = "_bits", "_ip_u8"
+
+    def __init__(self, bits, D, device=0, id_offset=0):
+        self._h = None
+        b = self._rows(bits, D, "bits")
+        self._lib = _lib.load()
+        self.n, self.D, self.id_offset = int(b.shape[0]), int(D), int(id_offset)
+        h = ctypes.c_void_p()
+        check(self._lib.dpq_flat_open_bits(_np_ptr(b), self.n, self.D, device, id_offset, ctypes.byref(h)), "dpq_flat_open_bits")
+        self._h = h
+
+    @classmethod
+    def from_float(cls, vectors, thresholds=None, device=0, id_offset=0):
+        """float32 vectors [n][D], binarised on the GPU: bit d = vectors[:, d] > thresholds[d] (> 0 without thresholds)."""
+        v = _sq_rows(vectors)
+        t = _bits_thresholds(thresholds, v.shape[1])
+        self = cls.__new__(cls)
+        self._h = None
+        self._lib = _lib.load()
+        self.n, self.D, self.id_offset = int(v.shape[0]), int(v.shape[1]), int(id_offset)
+        h = ctypes.c_void_p()
+        check(self._lib.dpq_flat_open_binarised(_np_ptr(v), self.n, self.D, None if t is None else _np_ptr(t), device, id_offset,
+                                                ctypes.byref(h)), "dpq_flat_open_binarised")
+        self._h = h
+        return self
+
+    @classmethod
+    def _rows(cls, a, D, what):
+        a = cls._bytes(a, what)
+        if a.ndim != 2 or a.shape[1] != (int(D) + 7) // 8:
+            raise ValueError("%s must be [n][(D + 7) // 8] = [n][%d]" % (what, (int(D) + 7) // 8))
+        return a
+
+    @classmethod
+    def _bytes(cls, a, what):
+        if not isinstance(a, np.ndarray) or a.dtype != np.uint8:
+            raise TypeError("%s must be a uint8 array of packed bits, eight dimensions to a byte" % what)
+        return np.ascontiguousarray(a)
+
+    @property
+    def _qcols(self):
+        return (self.D + 7) // 8
 
 
 class RefineLevel:

@@ -7,9 +7,18 @@ namespace {
 
 // The format of queries of type Q.  A call takes the handles whose rows go with it (dpq::flat_query_format): float -- an
 // fp32, a half or a quantised handle, uint8_t -- a handle of dpq_flat_open_u8, int8_t -- a handle of dpq_flat_open_i8.
+// The _bits calls take uint8_t as well, eight dimensions to a byte: their entry points hand the bytes on as bits_t.
+enum class bits_t : uint8_t {};
 template <class Q> constexpr int format_of = dpq::kFlatF32;
 template <> constexpr int format_of<uint8_t> = dpq::kFlatU8;
 template <> constexpr int format_of<int8_t> = dpq::kFlatI8;
+template <> constexpr int format_of<bits_t> = dpq::kFlatBits;
+const bits_t* as_bits(const uint8_t* p) { return reinterpret_cast<const bits_t*>(p); }
+
+// Elements of type Q in one query as the caller holds it: D values, or the (D + 7) / 8 bytes of D bits.
+size_t flat_query_elems(const dpq_flat* f) {
+    return f->format == dpq::kFlatBits ? (size_t)dpq::flat_bits_bytes(f->D) : (size_t)f->D;
+}
 
 // A search call's name: its shape ("dpq_flat_search", "dpq_flat_rerank", ...), its metric, the format of its queries
 // (`kind`), the device form.  The same pieces name the call of the same shape for queries of any other format.
@@ -19,6 +28,7 @@ struct FlatCall {
     int kind;
     bool device = false;
     std::string name(int k) const {
+        if (k == dpq::kFlatBits) return std::string(stem) + "_bits" + (device ? "_device" : "");  // no inner product over bits
         return std::string(stem) + (metric == dpq::kFlatIP ? "_ip" : "") + (k == dpq::kFlatU8 ? "_u8" : k == dpq::kFlatI8 ? "_i8" : "") +
                (device ? "_device" : "");
     }
@@ -63,7 +73,7 @@ int flat_rerank_on_device(const char* fn, int metric, dpq_flat* f, const Q* d_qu
     r.keys = f->keys;
     r.flag = f->flag;
     for (int q0 = 0; q0 < nq; q0 += per) {
-        r.queries = d_queries + (size_t)q0 * f->D;
+        r.queries = d_queries + (size_t)q0 * flat_query_elems(f);
         r.nq = std::min(per, nq - q0);
         r.cand = d_cand + (size_t)q0 * n_cand;
         r.ids = d_ids + (size_t)q0 * top_k;
@@ -78,8 +88,8 @@ int flat_rerank_on_device(const char* fn, int metric, dpq_flat* f, const Q* d_qu
 }
 
 // A handle takes the calls of its own kind only: the fp32-query functions an fp32, a half or a quantised handle, the
-// _u8 functions a handle of dpq_flat_open_u8, the _i8 functions one of dpq_flat_open_i8.  The message names the call of
-// the same shape that the handle does take.
+// _u8 functions a handle of dpq_flat_open_u8, the _i8 functions one of dpq_flat_open_i8, the _bits functions one of
+// dpq_flat_open_bits / dpq_flat_open_binarised.  The message names the call of the same shape that the handle does take.
 int flat_kind(const dpq_flat* f, const FlatCall& c) {
     const int kind = dpq::flat_query_format(f->format);
     if (kind == c.kind) return DPQ_OK;
@@ -96,6 +106,9 @@ int flat_kind(const dpq_flat* f, const FlatCall& c) {
         case dpq::kFlatF32: return fail(DPQ_ERR_ARG, fn + ": the handle holds fp32 vectors (dpq_flat_open); call " + right);
         case dpq::kFlatI8:
             return fail(DPQ_ERR_ARG, fn + ": the handle holds signed byte vectors (dpq_flat_open_i8); call " + right);
+        case dpq::kFlatBits:
+            return fail(DPQ_ERR_ARG, fn + ": the handle holds binary vectors (dpq_flat_open_bits, dpq_flat_open_binarised), "
+                                          "compared by Hamming distance only; call " + right);
     }
     if (c.kind == dpq::kFlatF32 && c.metric == dpq::kFlatIP)
         return fail(DPQ_ERR_ARG, fn + ": the handle holds byte vectors (dpq_flat_open_u8), which have no inner-product search "
@@ -125,12 +138,12 @@ int flat_use_device(int device) {
 // The checks of every dpq_flat_open*: the arguments (the half format too, where there is one) before any device call,
 // then the device.
 int flat_open_args(const char* fn, const void* vectors, int64_t n, int D, int device, int64_t id_offset, dpq_flat** out,
-                   const int* half_format = nullptr) {
+                   const int* half_format = nullptr, int max_d = dpq::kFlatMaxD) {
     const std::string who(fn);
     if (out) *out = nullptr;
     if (!vectors || !out) return fail(DPQ_ERR_ARG, who + ": NULL argument");
     if (n < 1) return fail(DPQ_ERR_ARG, who + ": n < 1");
-    if (D < 1 || D > dpq::kFlatMaxD) return fail(DPQ_ERR_ARG, who + ": D outside 1..2048");
+    if (D < 1 || D > max_d) return fail(DPQ_ERR_ARG, who + ": D outside 1.." + std::to_string(max_d));
     if (id_offset < 0 || n + id_offset >= ((int64_t)1 << 31))
         return fail(DPQ_ERR_ARG, who + ": id_offset < 0 or n + id_offset >= 2^31 (ids are int32)");
     if (half_format && *half_format != DPQ_HALF_F16 && *half_format != DPQ_HALF_BF16)
@@ -288,6 +301,29 @@ int sq_new_handle(const char* fn, int64_t n, int D, int bits, const float* lo, c
     return DPQ_OK;
 }
 
+// ---- binary vectors: a handle with its rows allocated, not yet filled ------------------------------------------------
+int bits_new_handle(const char* fn, int64_t n, int D, int device, int64_t id_offset, std::unique_ptr<dpq_flat>* out) {
+    std::unique_ptr<dpq_flat> f(new dpq_flat);
+    f->device = device;
+    f->n = n;
+    f->id_offset = id_offset;
+    f->D = D;
+    f->Dp = dpq::flat_bits_row_bytes(D);  // bytes of a stored row
+    f->format = dpq::kFlatBits;
+    if (int rc = f->rows.alloc((size_t)n * f->Dp))
+        return fail(rc, std::string(fn) + ": the vectors do not fit into device memory (" + dpq_last_error() + ")");
+    *out = std::move(f);
+    return DPQ_OK;
+}
+
+// thresholds [D] on the device, or nothing for NULL
+int bits_upload_thresholds(const float* thresholds, int D, DevBuf<float>* d_thr) {
+    if (!thresholds) return DPQ_OK;
+    if (int rc = d_thr->alloc((size_t)D)) return rc;
+    DPQ_HIP(hipMemcpy(*d_thr, thresholds, (size_t)D * sizeof(float), hipMemcpyHostToDevice));
+    return DPQ_OK;
+}
+
 int grow_outputs(dpq_flat* f, size_t want) {
     if (f->out_n >= want) return DPQ_OK;
     f->out_n = 0;
@@ -302,7 +338,10 @@ int grow_outputs(dpq_flat* f, size_t want) {
 template <class Q>
 int flat_stage_queries(dpq_flat* f, int metric, const Q* src, int m, std::vector<float>* padded) {
     const int D = f->D, Dp = f->Dp;
-    if constexpr (format_of<Q> != dpq::kFlatF32) {
+    if constexpr (format_of<Q> == dpq::kFlatBits) {
+        DPQ_HIP(hipMemcpy(f->q_raw, src, (size_t)m * flat_query_elems(f), hipMemcpyHostToDevice));
+        DPQ_HIP(dpq::launch_flat_bits_prepare(f->q_raw, m, D, reinterpret_cast<uint8_t*>(f->q8.get()), Dp, nullptr));
+    } else if constexpr (format_of<Q> != dpq::kFlatF32) {
         DPQ_HIP(hipMemcpy(f->q_raw, src, (size_t)m * D, hipMemcpyHostToDevice));
         DPQ_HIP(dpq::launch_flat_u8_prepare(f->q_raw, m, D, Dp, f->q8, f->qnorm, nullptr, format_of<Q> == dpq::kFlatI8));
         if (format_of<Q> == dpq::kFlatU8 && metric == dpq::kFlatIP)
@@ -322,7 +361,12 @@ int flat_stage_queries(dpq_flat* f, int metric, const Q* src, int m, std::vector
 // correction terms, in one pass over the stored rows: 4 * n bytes, kept until dpq_flat_close.
 template <class Q>
 int flat_grow_queries(dpq_flat* f, int metric, size_t qb) {
-    if constexpr (format_of<Q> != dpq::kFlatF32) {
+    if constexpr (format_of<Q> == dpq::kFlatBits) {
+        // the distance kernel reads whole tiles of up to 64 queries from wherever a sub-batch starts, and masks the rest
+        int rc = grow(f->q_raw, &f->q_raw_n, qb * flat_query_elems(f));
+        if (!rc) rc = grow(f->q8, &f->q8_n, (qb + 64) * f->Dp);
+        return rc;
+    } else if constexpr (format_of<Q> != dpq::kFlatF32) {
         int rc = grow(f->q_raw, &f->q_raw_n, qb * f->D);
         if (!rc) rc = grow(f->q8, &f->q8_n, qb * f->Dp);
         if (!rc) rc = grow(f->qnorm, &f->qnorm_n, qb);
@@ -346,6 +390,8 @@ int flat_grow_queries(dpq_flat* f, int metric, size_t qb) {
 
 // Queries [a, a + m) of the staged batch, as the launchers of dpq_flat.h take them.
 dpq::FlatQueries flat_queries(const dpq_flat* f, int a, int m) {
+    if (f->format == dpq::kFlatBits)
+        return {nullptr, nullptr, nullptr, m, nullptr, reinterpret_cast<const uint8_t*>(f->q8.get()) + (size_t)a * f->Dp};
     if (dpq::flat_query_format(f->format) != dpq::kFlatF32)
         return {nullptr, f->q8.get() + (size_t)a * f->Dp, f->qnorm.get() + a, m, f->qsum.get() ? f->qsum.get() + a : nullptr};
     return {f->d_q.get() + (size_t)a * f->Dp, nullptr, nullptr, m};
@@ -371,7 +417,7 @@ int flat_search_run(const std::string& who, int metric, dpq_flat* f, const dpq_f
     std::vector<dpq::FlatQueryState> st((size_t)qb);
     for (int q0 = 0; q0 < nq; q0 += qb) {
         const int m = std::min(qb, nq - q0);
-        if ((rc = flat_stage_queries(f, metric, queries + (size_t)q0 * f->D, m, &padded))) return rc;
+        if ((rc = flat_stage_queries(f, metric, queries + (size_t)q0 * flat_query_elems(f), m, &padded))) return rc;
         DPQ_HIP(dpq::launch_flat_search(base, flat_queries(f, 0, m), top_k, f->keys, f->state, f->d_ids, f->d_dists, nullptr));
         DPQ_HIP(hipMemcpy(ids + (size_t)q0 * top_k, f->d_ids, (size_t)m * top_k * sizeof(int32_t), hipMemcpyDeviceToHost));
         DPQ_HIP(hipMemcpy(dists + (size_t)q0 * top_k, f->d_dists, (size_t)m * top_k * sizeof(float), hipMemcpyDeviceToHost));
@@ -567,6 +613,64 @@ int dpq_flat_sq_get(const dpq_flat* f, int* bits, float* lo_out, float* step_out
     });
 }
 
+int dpq_flat_open_bits(const uint8_t* rows, int64_t n, int D, int device, int64_t id_offset, dpq_flat** out) {
+    return guarded([&]() -> int {
+    const char* fn = "dpq_flat_open_bits";
+    if (int rc = flat_open_args(fn, rows, n, D, device, id_offset, out, nullptr, DPQ_FLAT_BITS_MAX_D)) return rc;
+    std::unique_ptr<dpq_flat> f;
+    if (int rc = bits_new_handle(fn, n, D, device, id_offset, &f)) return rc;
+    int rc = sq_slices(rows, n, (size_t)dpq::flat_bits_bytes(D), [&](const uint8_t* d_slice, int64_t r0, int64_t m) -> int {
+        DPQ_HIP(dpq::launch_flat_bits_prepare(d_slice, m, D, f->rows.get() + (size_t)r0 * f->Dp, f->Dp, nullptr));
+        return DPQ_OK;
+    });
+    if (rc) return rc;
+    *out = f.release();
+    return DPQ_OK;
+    });
+}
+
+int dpq_bits_from_float(const float* vectors, int64_t n, int D, const float* thresholds, int device, uint8_t* bits_out) {
+    return guarded([&]() -> int {
+    const std::string who("dpq_bits_from_float");
+    if (!vectors || !bits_out) return fail(DPQ_ERR_ARG, who + ": NULL argument");
+    if (n < 1) return fail(DPQ_ERR_ARG, who + ": n < 1");
+    if (D < 1 || D > DPQ_FLAT_BITS_MAX_D) return fail(DPQ_ERR_ARG, who + ": D outside 1.." + std::to_string(DPQ_FLAT_BITS_MAX_D));
+    if (int rc = flat_use_device(device)) return rc;
+    const int stride = dpq::flat_bits_bytes(D);
+    const int64_t tile = std::max<int64_t>(1, ((int64_t)128 << 20) / ((int64_t)D * (int64_t)sizeof(float)));
+    DevBuf<float> d_thr;
+    DevBuf<uint8_t> d_bits;
+    int rc = bits_upload_thresholds(thresholds, D, &d_thr);
+    if (!rc) rc = d_bits.alloc((size_t)std::min(n, tile) * stride);
+    if (rc) return rc;
+    return sq_slices(vectors, n, (size_t)D * sizeof(float), [&](const uint8_t* d_slice, int64_t r0, int64_t m) -> int {
+        DPQ_HIP(dpq::launch_flat_bits_from_float(reinterpret_cast<const float*>(d_slice), m, D, d_thr.get(), d_bits, stride, nullptr));
+        DPQ_HIP(hipMemcpy(bits_out + (size_t)r0 * stride, d_bits, (size_t)m * stride, hipMemcpyDeviceToHost));
+        return DPQ_OK;
+    });
+    });
+}
+
+int dpq_flat_open_binarised(const float* vectors, int64_t n, int D, const float* thresholds, int device, int64_t id_offset,
+                            dpq_flat** out) {
+    return guarded([&]() -> int {
+    const char* fn = "dpq_flat_open_binarised";
+    if (int rc = flat_open_args(fn, vectors, n, D, device, id_offset, out, nullptr, DPQ_FLAT_BITS_MAX_D)) return rc;
+    std::unique_ptr<dpq_flat> f;
+    if (int rc = bits_new_handle(fn, n, D, device, id_offset, &f)) return rc;
+    DevBuf<float> d_thr;
+    if (int rc = bits_upload_thresholds(thresholds, D, &d_thr)) return rc;
+    int rc = sq_slices(vectors, n, (size_t)D * sizeof(float), [&](const uint8_t* d_slice, int64_t r0, int64_t m) -> int {
+        DPQ_HIP(dpq::launch_flat_bits_from_float(reinterpret_cast<const float*>(d_slice), m, D, d_thr.get(),
+                                                 f->rows.get() + (size_t)r0 * f->Dp, f->Dp, nullptr));
+        return DPQ_OK;
+    });
+    if (rc) return rc;
+    *out = f.release();
+    return DPQ_OK;
+    });
+}
+
 int dpq_flat_close(dpq_flat* f) {
     return guarded([&]() -> int {
     if (!f) return DPQ_OK;
@@ -609,6 +713,12 @@ int dpq_flat_search_i8(dpq_flat* f, const int8_t* queries, int nq, int top_k, in
 int dpq_flat_search_ip_i8(dpq_flat* f, const int8_t* queries, int nq, int top_k, int32_t* ids, float* scores) {
     return guarded([&]() -> int {
     return flat_search_call({"dpq_flat_search", dpq::kFlatIP, dpq::kFlatI8}, f, queries, nq, top_k, ids, scores);
+    });
+}
+
+int dpq_flat_search_bits(dpq_flat* f, const uint8_t* queries, int nq, int top_k, int32_t* ids, float* dists) {
+    return guarded([&]() -> int {
+    return flat_search_call({"dpq_flat_search", dpq::kFlatL2, dpq::kFlatBits}, f, as_bits(queries), nq, top_k, ids, dists);
     });
 }
 
@@ -727,7 +837,7 @@ int flat_range_call(const FlatCall& c, dpq_flat* f, const dpq_flat_filter* ff, c
     std::vector<int64_t> offs;
     for (int q0 = 0; q0 < nq && !rc; q0 += qb) {
         const int m = std::min(qb, nq - q0);
-        if ((rc = flat_stage_queries(f, metric, queries + (size_t)q0 * f->D, m, &padded))) break;
+        if ((rc = flat_stage_queries(f, metric, queries + (size_t)q0 * flat_query_elems(f), m, &padded))) break;
         for (int q = 0; q < m; ++q) {  // d < r on non-negative floats is bits(d) < bits(r); key 0 lets nothing pass
             const float r = radii[q0 + q];
             uint32_t bits = 0;
@@ -866,6 +976,21 @@ int dpq_flat_search_filtered_i8(dpq_flat* f, const dpq_flat_filter* ff, const in
     });
 }
 
+int dpq_flat_search_filtered_bits(dpq_flat* f, const dpq_flat_filter* ff, const uint8_t* queries, int nq, int top_k,
+                                  int32_t* ids, float* dists) {
+    return guarded([&]() -> int {
+    return flat_search_filtered_call({"dpq_flat_search_filtered", dpq::kFlatL2, dpq::kFlatBits}, f, ff, as_bits(queries), nq, top_k, ids,
+                                     dists);
+    });
+}
+
+int dpq_flat_range_search_bits(dpq_flat* f, const dpq_flat_filter* ff, const uint8_t* queries, int nq, const float* radii,
+                               dpq_range_result** out) {
+    return guarded([&]() -> int {
+    return flat_range_call({"dpq_flat_range_search", dpq::kFlatL2, dpq::kFlatBits}, f, ff, as_bits(queries), nq, radii, out);
+    });
+}
+
 int dpq_flat_search_filtered_ip(dpq_flat* f, const dpq_flat_filter* ff, const float* queries, int nq, int top_k, int32_t* ids,
                                 float* scores) {
     return guarded([&]() -> int {
@@ -968,7 +1093,7 @@ int flat_rerank_host_call(const FlatCall& c, dpq_flat* f, const Q* queries, int 
     DPQ_HIP(hipSetDevice(f->device));
     Q* d_q;
     if constexpr (bytes) {
-        rc = grow(f->q_raw, &f->q_raw_n, (size_t)nq * f->D);
+        rc = grow(f->q_raw, &f->q_raw_n, (size_t)nq * flat_query_elems(f));
         d_q = reinterpret_cast<Q*>(f->q_raw.get());
     } else {
         rc = grow(f->d_q, &f->q_n, (size_t)nq * f->D);
@@ -977,7 +1102,7 @@ int flat_rerank_host_call(const FlatCall& c, dpq_flat* f, const Q* queries, int 
     if (!rc) rc = grow(f->d_cand, &f->cand_n, (size_t)nq * n_cand);
     if (!rc) rc = grow_outputs(f, (size_t)nq * top_k);
     if (rc) return rc;
-    DPQ_HIP(hipMemcpy(d_q, queries, (size_t)nq * f->D * sizeof(Q), hipMemcpyHostToDevice));
+    DPQ_HIP(hipMemcpy(d_q, queries, (size_t)nq * flat_query_elems(f) * sizeof(Q), hipMemcpyHostToDevice));
     DPQ_HIP(hipMemcpy(f->d_cand, cand_ids, (size_t)nq * n_cand * sizeof(int32_t), hipMemcpyHostToDevice));
     rc = flat_rerank_on_device(fn, c.metric, f, d_q, nq, f->d_cand, n_cand, top_k, f->d_ids, f->d_dists, nullptr);
     if (rc) return rc;
@@ -1032,6 +1157,22 @@ int dpq_flat_rerank_i8_device(dpq_flat* f, const int8_t* d_queries, int nq, cons
     return guarded([&]() -> int {
     return flat_rerank_device_call({"dpq_flat_rerank", dpq::kFlatL2, dpq::kFlatI8, true}, f, d_queries, nq, d_cand_ids, n_cand, top_k, d_ids,
                                    d_dists, hip_stream);
+    });
+}
+
+int dpq_flat_rerank_bits(dpq_flat* f, const uint8_t* queries, int nq, const int32_t* cand_ids, int n_cand, int top_k,
+                         int32_t* ids, float* dists) {
+    return guarded([&]() -> int {
+    return flat_rerank_host_call({"dpq_flat_rerank", dpq::kFlatL2, dpq::kFlatBits}, f, as_bits(queries), nq, cand_ids, n_cand, top_k, ids,
+                                 dists);
+    });
+}
+
+int dpq_flat_rerank_bits_device(dpq_flat* f, const uint8_t* d_queries, int nq, const int32_t* d_cand_ids, int n_cand,
+                                int top_k, int32_t* d_ids, float* d_dists, void* hip_stream) {
+    return guarded([&]() -> int {
+    return flat_rerank_device_call({"dpq_flat_rerank", dpq::kFlatL2, dpq::kFlatBits, true}, f, as_bits(d_queries), nq, d_cand_ids, n_cand,
+                                   top_k, d_ids, d_dists, hip_stream);
     });
 }
 

@@ -140,9 +140,17 @@ int main(int argc, char* argv[]) {
         return 2;
     }
 
+    // -metric hamming: exact Hamming distances over packed bits, eight dimensions to a byte of a .bvecs file
+    const bool hamming = metric == "hamming";
+    if (hamming && (task != "groundtruth" || ext != "bvecs")) {
+        std::cout << "usage: -metric hamming serves -task groundtruth -ext bvecs [-filter FILE]: base.bvecs and query.bvecs hold "
+                     "packed bits, every byte eight dimensions (dimension d in bit d & 7 of byte d >> 3); a .fvecs file has no bits"
+                  << std::endl;
+        return 2;
+    }
     const bool ip = metric == "ip";
-    if ((!ip && metric != "l2") || (ip && (refine_r != 0 || gpus > 1 || (task != "groundtruth" && task != "recall")))) {
-        std::cout << "usage: -metric l2|ip (default l2); -metric ip serves -task groundtruth and -task recall [-rerank R] "
+    if ((!ip && !hamming && metric != "l2") || (ip && (refine_r != 0 || gpus > 1 || (task != "groundtruth" && task != "recall")))) {
+        std::cout << "usage: -metric l2|ip|hamming (default l2); -metric hamming serves -task groundtruth -ext bvecs; -metric ip serves -task groundtruth and -task recall [-rerank R] "
                      "[-filter FILE] [-opq], and cannot be combined with -refine R or -gpus above 1" << std::endl;
         return 2;
     }
@@ -376,9 +384,10 @@ int main(int argc, char* argv[]) {
         // With -ext bvecs the bytes stay bytes (dpq_flat_open_u8 / dpq_flat_search[_ip]_u8): the same bits, the same file.
         if (dataset.empty() || !topk_given || top_k < 1 || query_size < 1) {
             std::cout << "usage: deltapq -dataset DIR -task groundtruth -topk K -query_size Q [-N N] [-ext fvecs|bvecs] [-filter FILE]"
-                         " [-metric l2|ip]" << std::endl;
+                         " [-metric l2|ip|hamming]" << std::endl;
             return 2;
         }
+        // -metric hamming: the bytes are packed bits, D = 8 x the file's dimension (dpq_flat_open_bits / dpq_flat_search_bits)
         // -metric ip: exact inner products (dpq_flat_search_ip; over a .bvecs base dpq_flat_search_ip_u8, the bytes kept)
         const bool file_bvecs = ext == "bvecs", bvecs = file_bvecs;
         const std::string q_path = dataset + "/query." + ext, base_path = dataset + "/base." + ext;
@@ -419,6 +428,10 @@ int main(int argc, char* argv[]) {
             std::cout << "-topk " << top_k << " outside 1.." << std::min<int64_t>(n, DPQ_FLAT_MAX_TOPK) << std::endl;
             return 1;
         }
+        if (hamming && D > DPQ_FLAT_BITS_MAX_D / 8) {
+            std::cout << "-metric hamming: " << D << " bytes a row exceed " << DPQ_FLAT_BITS_MAX_D << " bits" << std::endl;
+            return 1;
+        }
         if (dpq_device_count() < 1) {
             std::cout << "no GPU visible: this build has no CPU search path" << std::endl;
             return 1;
@@ -445,14 +458,14 @@ int main(int argc, char* argv[]) {
                 part8.resize((size_t)rows * D);
                 rc = dpq_read_bvecs_range(base_path.c_str(), r0, rows, &Db, part8.data());
                 if (rc) return die("ItrReader", rc);
-                rc = dpq_flat_open_u8(part8.data(), rows, D, 0, r0, &f);
+                rc = hamming ? dpq_flat_open_bits(part8.data(), rows, 8 * D, 0, r0, &f) : dpq_flat_open_u8(part8.data(), rows, D, 0, r0, &f);
             } else {
                 part.resize((size_t)rows * D);
                 rc = dpq_read_vecs_range(base_path.c_str(), file_bvecs, r0, rows, &Db, part.data());
                 if (rc) return die("ItrReader", rc);
                 rc = dpq_flat_open(part.data(), rows, D, 0, r0, &f);
             }
-            if (rc) return die(bvecs ? "dpq_flat_open_u8" : "dpq_flat_open", rc);
+            if (rc) return die(hamming ? "dpq_flat_open_bits" : bvecs ? "dpq_flat_open_u8" : "dpq_flat_open", rc);
             // a short last part gives a short list, padded; a filtered search pads its own rows
             const int kk = filtered ? top_k : (int)std::min<int64_t>(top_k, rows);
             p_ids.resize((size_t)nq * kk);
@@ -461,22 +474,26 @@ int main(int argc, char* argv[]) {
                 dpq_flat_filter* ff = nullptr;
                 rc = dpq_flat_filter_create(f, f_words.data(), f_bits, &ff);
                 if (rc) return die("dpq_flat_filter_create", rc);
-                rc = bvecs ? (ip ? dpq_flat_search_filtered_ip_u8(f, ff, queries8.data(), nq, kk, p_ids.data(), p_dists.data())
+                rc = hamming ? dpq_flat_search_filtered_bits(f, ff, queries8.data(), nq, kk, p_ids.data(), p_dists.data())
+                     : bvecs ? (ip ? dpq_flat_search_filtered_ip_u8(f, ff, queries8.data(), nq, kk, p_ids.data(), p_dists.data())
                                  : dpq_flat_search_filtered_u8(f, ff, queries8.data(), nq, kk, p_ids.data(), p_dists.data()))
                      : ip  ? dpq_flat_search_filtered_ip(f, ff, queries.data(), nq, kk, p_ids.data(), p_dists.data())
                            : dpq_flat_search_filtered(f, ff, queries.data(), nq, kk, p_ids.data(), p_dists.data());
                 if (rc)
-                    return die(bvecs ? (ip ? "dpq_flat_search_filtered_ip_u8" : "dpq_flat_search_filtered_u8")
+                    return die(hamming ? "dpq_flat_search_filtered_bits"
+                               : bvecs ? (ip ? "dpq_flat_search_filtered_ip_u8" : "dpq_flat_search_filtered_u8")
                                : ip  ? "dpq_flat_search_filtered_ip"
                                      : "dpq_flat_search_filtered", rc);
                 dpq_flat_filter_free(ff);
             } else {
-                rc = bvecs ? (ip ? dpq_flat_search_ip_u8(f, queries8.data(), nq, kk, p_ids.data(), p_dists.data())
+                rc = hamming ? dpq_flat_search_bits(f, queries8.data(), nq, kk, p_ids.data(), p_dists.data())
+                     : bvecs ? (ip ? dpq_flat_search_ip_u8(f, queries8.data(), nq, kk, p_ids.data(), p_dists.data())
                                  : dpq_flat_search_u8(f, queries8.data(), nq, kk, p_ids.data(), p_dists.data()))
                      : ip  ? dpq_flat_search_ip(f, queries.data(), nq, kk, p_ids.data(), p_dists.data())
                            : dpq_flat_search(f, queries.data(), nq, kk, p_ids.data(), p_dists.data());
                 if (rc)
-                    return die(bvecs ? (ip ? "dpq_flat_search_ip_u8" : "dpq_flat_search_u8") : ip ? "dpq_flat_search_ip" : "dpq_flat_search",
+                    return die(hamming ? "dpq_flat_search_bits"
+                               : bvecs ? (ip ? "dpq_flat_search_ip_u8" : "dpq_flat_search_u8") : ip ? "dpq_flat_search_ip" : "dpq_flat_search",
                                rc);
             }
             dpq_flat_close(f);
@@ -497,7 +514,7 @@ int main(int argc, char* argv[]) {
         const std::string gt_dir = dataset + "/groundtruth";
         mkdir(gt_dir.c_str(), 0777);  // (exists already: fine)
         const std::string gt_path = gt_dir + "/N" + std::to_string(n) + "Top" + std::to_string(top_k) +
-                                    (ip ? ".ip" : "") + (filtered ? ".filtered.txt" : ".txt");  // main.cpp:663-667
+                                    (ip ? ".ip" : hamming ? ".hamming" : "") + (filtered ? ".filtered.txt" : ".txt");  // main.cpp:663-667
         rc = dpq_write_groundtruth(gt_path.c_str(), out_ids.data(), out_dists.data(), nq, top_k);
         if (rc) return die("write_groundtruth", rc);
         std::cout << gt_path << std::endl;

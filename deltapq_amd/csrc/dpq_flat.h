@@ -18,15 +18,20 @@ namespace dpq {
 
 constexpr int kFlatMaxTopK = 16384;  // DPQ_FLAT_MAX_TOPK, and the most candidates a re-rank takes per query
 constexpr int kFlatMaxD = 2048;
+constexpr int kFlatBitsMaxD = 4096;  // DPQ_FLAT_BITS_MAX_D: the most dimensions of a binary row
 
 // The metric of a kernel.  kFlatL2: the key's high word is the bits of the (non-negative) distance.  kFlatIP: the
 // score's bits mapped so that ascending keys are descending scores (flat_ip_word below).
 enum { kFlatL2 = 0, kFlatIP = 1 };
 // What the rows of a base are stored as.  kFlatF16 / kFlatBF16 are DPQ_HALF_F16 / DPQ_HALF_BF16.
 // kFlatSQ8 / kFlatSQ4: codes of a scalar quantiser, DPQ_SQ_8BIT / DPQ_SQ_4BIT ("scalar-quantised vectors" below).
-enum { kFlatF32 = 0, kFlatF16 = 1, kFlatBF16 = 2, kFlatU8 = 3, kFlatI8 = 4, kFlatSQ8 = 5, kFlatSQ4 = 6 };
-// The format of the queries a base of this format takes: fp32 for fp32, half and quantised rows, the rows' own for bytes.
-inline int flat_query_format(int format) { return format == kFlatU8 || format == kFlatI8 ? format : kFlatF32; }
+// kFlatBits: one bit per dimension, compared by Hamming distance ("binary vectors" below).
+enum { kFlatF32 = 0, kFlatF16 = 1, kFlatBF16 = 2, kFlatU8 = 3, kFlatI8 = 4, kFlatSQ8 = 5, kFlatSQ4 = 6, kFlatBits = 7 };
+// The format of the queries a base of this format takes: fp32 for fp32, half and quantised rows, the rows' own for bytes
+// and for bits.
+inline int flat_query_format(int format) {
+    return format == kFlatU8 || format == kFlatI8 || format == kFlatBits ? format : kFlatF32;
+}
 // Score bits <-> high word of an inner-product key; the map is its own inverse.  -0.0 is read as +0.0 first.  A
 // non-negative score u becomes ~u & 0x7fffffff (larger scores, smaller words), a negative one keeps its bits (sign set,
 // larger magnitudes later): +inf 0x007fffff < 1.0 < +0.0 0x7fffffff < -1e-40 < -1.0 < -inf 0xff800000 < kFlatNoKey's.
@@ -96,6 +101,7 @@ int flat_query_batch(int top_k);
 // A prepared base: rows [n][Dp] of `format`, padded with zeros -- fp32 to a multiple of four values, halves to a multiple
 // of eight, bytes (biased int8 for kFlatU8, see "byte vectors" below) to the K step of the MFMA, with their int32 norms,
 // codes of a scalar quantiser to 16 (kFlatSQ8) or 32 (kFlatSQ4, two to a byte) with code 0, beside their quantiser.
+// A kFlatBits base: D is the number of bits and Dp the bytes of a stored row (flat_bits_row_bytes), no norms.
 // The entries a pass visits are rows 0 .. n_entries - 1, or, with `filtered`, rows list[0 .. n_entries - 1] (ascending).
 // `filtered`, not the list pointer, says which: an empty filter has n_entries == 0 and may have a NULL list.
 // Reported id = row + id_offset.
@@ -123,6 +129,7 @@ struct FlatQueries {
     const int32_t* norm;
     int nq;
     const int32_t* sum = nullptr;
+    const uint8_t* bits = nullptr;  // a kFlatBits base: [nq][Dp] prepared as the rows are
 };
 
 // What a distance kernel does with a key (its MODE): at or below the query's threshold it is appended to the query's
@@ -149,7 +156,7 @@ hipError_t launch_flat_search(const FlatBase& b, const FlatQueries& q, int top_k
                               int32_t* d_ids, float* d_dists, hipStream_t stream);
 
 // A re-rank: exact distances of cand[nq][n_cand] only, best top_k by (distance, reported id), all device pointers.
-// queries: the caller's [nq][D], unpadded, of flat_query_format(the base's format).  map (may be NULL) [n_map]: a
+// queries: the caller's [nq][D] (a bits base: [nq][(D + 7) / 8] bytes), unpadded, of flat_query_format(the base's format).  map (may be NULL) [n_map]: a
 // candidate is a DFS position, row = map[c], with the even-N rule; without it row = c - id_offset.
 // keys [nq][flat_rerank_keys(n_cand)].  *flag is set when a candidate names no row.  kFlatIP: exact scores, best top_k by
 // (score descending, reported id).
@@ -281,6 +288,28 @@ hipError_t launch_flat_sq_encode(const float* d_in, int64_t rows, int D, int bit
 // D and the padding become code 0.
 hipError_t launch_flat_sq_prepare(const uint8_t* d_in, int64_t rows, int D, int bits, uint8_t* d_out, int out_stride,
                                   hipStream_t stream);
+
+// ---- binary vectors, one bit per dimension, by Hamming distance (dpq_flat_bits.hip) ----------------------------------
+// A row is D bits in (D + 7) / 8 bytes, dimension d in bit d & 7 of byte d >> 3.  A base (and a staged query batch) keeps
+// the spare bits of the last byte cleared and pads a row with zero bytes to a multiple of 16 (16-byte loads); zero against
+// zero XORs to zero, so the padding adds nothing to a distance.  FlatBase::D is the number of bits, FlatBase::Dp the bytes
+// of a stored row; the metric stays kFlatL2: the key word is the fp32 bits of the integer distance.
+inline int flat_bits_bytes(int D) { return (D + 7) / 8; }                         // of a row as the caller holds it
+inline int flat_bits_row_bytes(int D) { return (flat_bits_bytes(D) + 15) & ~15; }  // of a stored row
+// The caller's bytes [rows][flat_bits_bytes(D)] -> stored rows [rows][out_stride = flat_bits_row_bytes(D)]; a query batch
+// takes the same path.
+hipError_t launch_flat_bits_prepare(const uint8_t* d_in, int64_t rows, int D, uint8_t* d_out, int out_stride,
+                                    hipStream_t stream);
+// fp32 rows [rows][D] -> packed bits, bit d = in[d] > d_thr[d] in fp32 (d_thr NULL: > 0), out_stride bytes per row, zero
+// from the row's last dimension on (out_stride = flat_bits_bytes(D): the caller's layout; flat_bits_row_bytes(D): a base's).
+hipError_t launch_flat_bits_from_float(const float* d_in, int64_t rows, int D, const float* d_thr, uint8_t* d_out,
+                                       int out_stride, hipStream_t stream);
+// The distance stage of launch_flat_search / launch_flat_range_pass on a bits base (q.bits), as launch_flat_dist_u8 is
+// the byte bases'.
+hipError_t launch_flat_dist_bits(int mode, const FlatBase& b, int64_t e0, int rows, const FlatQueries& q, uint64_t* keys,
+                                 int cap, const int64_t* offs, FlatQueryState* state, hipStream_t stream);
+// The distance stage of launch_flat_rerank on a bits base; r.queries are the caller's bytes [nq][flat_bits_bytes(D)].
+void launch_flat_rerank_chunk_bits(const FlatBase& b, const FlatRerank& r, int n_pad, hipStream_t stream);
 
 // ---- filters and range search (dpq_flat_filter.hip: the row list, the range state, the sort; no distance code) -----
 // A filter is the ascending list of a handle's eligible rows.  d_words [n_words]: bit b of word w = row 32 w + b.

@@ -46,7 +46,8 @@
 // launch_flat_search is the one stripe driver (state, then per stripe a select and a distance launch, then the last
 // select and the sort), launch_flat_range_pass the one range pass and launch_flat_rerank the one re-rank launcher (the
 // chunks of the grid's y extent, then the sort), for every format, with and without a list; the byte kernels of
-// dpq_flat_u8.hip come in through launch_flat_dist_u8 and launch_flat_rerank_chunk_u8.  make_key<METRIC>,
+// dpq_flat_u8.hip come in through launch_flat_dist_u8 and launch_flat_rerank_chunk_u8, the Hamming kernels of
+// dpq_flat_bits.hip through launch_flat_dist_bits and launch_flat_rerank_chunk_bits.  make_key<METRIC>,
 // accumulate<METRIC> and flat_candidate_row live in dpq_flat.h.
 #include "dpq_flat.h"
 
@@ -661,6 +662,7 @@ hipError_t launch_flat_dist(int mode, const FlatBase& b, int64_t e0, int rows, c
     switch (b.format) {
         case kFlatU8:
         case kFlatI8: return launch_flat_dist_u8(mode, b, e0, rows, q, keys, cap, offs, state, stream);
+        case kFlatBits: return launch_flat_dist_bits(mode, b, e0, rows, q, keys, cap, offs, state, stream);
         case kFlatF16: pick_dist<kFlatF16>(b.metric, b.filtered, mode)(b, e0, rows, q, keys, cap, offs, state, stream); break;
         case kFlatBF16: pick_dist<kFlatBF16>(b.metric, b.filtered, mode)(b, e0, rows, q, keys, cap, offs, state, stream); break;
         case kFlatSQ8: pick_dist<kFlatSQ8>(b.metric, b.filtered, mode)(b, e0, rows, q, keys, cap, offs, state, stream); break;
@@ -717,7 +719,8 @@ hipError_t launch_flat_rerank(const FlatBase& b, const FlatRerank& r, hipStream_
     hipError_t e = ensure_sort_lds();
     if (e != hipSuccess) return e;
     const int n_pad = pow2_at_least(r.n_cand);
-    const size_t q_bytes = (size_t)b.D * (flat_query_format(b.format) == kFlatF32 ? sizeof(float) : 1);  // of one query
+    const size_t q_bytes = b.format == kFlatBits ? (size_t)flat_bits_bytes(b.D)  // of one query
+                                                 : (size_t)b.D * (flat_query_format(b.format) == kFlatF32 ? sizeof(float) : 1);
     for (int q0 = 0; q0 < r.nq; q0 += 65535) {  // the grid's y extent
         FlatRerank c = r;
         c.queries = static_cast<const char*>(r.queries) + (size_t)q0 * q_bytes;
@@ -727,6 +730,7 @@ hipError_t launch_flat_rerank(const FlatBase& b, const FlatRerank& r, hipStream_
         switch (b.format) {
             case kFlatU8:
             case kFlatI8: launch_flat_rerank_chunk_u8(b, c, n_pad, stream); break;
+            case kFlatBits: launch_flat_rerank_chunk_bits(b, c, n_pad, stream); break;
             case kFlatF16: rerank_chunk<kFlatF16>(b, c, n_pad, stream); break;
             case kFlatBF16: rerank_chunk<kFlatBF16>(b, c, n_pad, stream); break;
             case kFlatSQ8: rerank_chunk<kFlatSQ8>(b, c, n_pad, stream); break;

@@ -57,6 +57,9 @@
  *   (none: FAISS's IndexScalarQuantizer         dpq_sq_train / dpq_sq_encode / dpq_sq_decode, dpq_flat_open_sq /
  *     QT_8bit / QT_4bit under IndexFlat's         dpq_flat_open_quantised, dpq_flat_sq_get, then every fp32-query
  *     calls, IndexRefine over it)                 dpq_flat_* call
+ *   (none: FAISS's IndexBinaryFlat: Hamming     dpq_flat_open_bits / dpq_flat_open_binarised / dpq_bits_from_float,
+ *     search, range search, an IDSelector,        dpq_flat_search_bits / dpq_flat_search_filtered_bits /
+ *     re-ranking over packed bits)                dpq_flat_range_search_bits / dpq_flat_rerank_bits[_device]
  *
  * Conventions: plain pointers and sizes only; the caller owns every host
  * buffer it passes, the library owns device memory.  Every function returns a
@@ -980,6 +983,54 @@ int dpq_flat_open_quantised(const float* vectors /* [n][D], host */, int64_t n, 
                             const float* step, int device, int64_t id_offset, dpq_flat** out);
 /* The quantiser of a quantised handle: *bits, lo_out[D], step_out[D].  DPQ_ERR_ARG on a handle of any other kind. */
 int dpq_flat_sq_get(const dpq_flat* f, int* bits, float* lo_out, float* step_out);
+
+/* ---- exact search over binary vectors: one bit per dimension, by Hamming distance ---
+ * The bottom of the storage ladder: sign-binarised embeddings, perceptual hashes and LSH sketches, 1 bit per dimension
+ * (128 B for 1024 dimensions), compared by the number of differing dimensions.  FAISS's IndexBinaryFlat.  The rules below
+ * are this library's own; tests/_exact_bits_restatement.py restates them in numpy and the GPU meets them bit for bit.
+ * Row layout.  A row is D bits in (D + 7) / 8 bytes; dimension d is bit d & 7 of byte d >> 3 (numpy's
+ * packbits(..., bitorder="little"), and the convention of this library's bitmaps).  1 <= D <= DPQ_FLAT_BITS_MAX_D.  The
+ * spare high bits of a row's last byte are ignored, whatever they hold, in base rows and in queries alike.
+ * Distance.  The distance of a query and a row is the number of dimensions in which they differ, reported as (float) of
+ * that integer, which is exact.  Keys, order and padding are those of the L2 calls: rows ascend by (distance, reported
+ * id), reported id = row + id_offset, a list shorter than top_k is padded with -1 / +inf; top_k outside
+ * 1..DPQ_FLAT_MAX_TOPK is DPQ_ERR_ARG and top_k > n DPQ_ERR_TOPK (not for the filtered call).  Range search is strict
+ * (d < r); every query's list is sorted by (distance, id); the result is a dpq_range_result.  Re-ranking follows
+ * dpq_flat_rerank's rules: negative candidates are padding, a row named twice counts once, the id map with its even-n_map
+ * rule, 1 <= top_k <= n_cand <= 16384, a candidate that names no row is DPQ_ERR_ARG (the device form raises a flag word
+ * that is read back at the end).
+ * Call kinds.  A bits handle takes the _bits calls only: every other dpq_flat_* search, range or re-rank call on it is
+ * DPQ_ERR_ARG with a message that names the _bits call of the same shape (there is no inner product over bits), and a
+ * _bits call on a handle of any other kind is refused the same way.  dpq_flat_set_id_map, dpq_flat_filter_create,
+ * dpq_flat_close and dpq_merge_topk_host work on a bits handle unchanged.
+ * Binarising.  bit d = (v[d] > t[d]), the comparison in fp32, with t the caller's thresholds[D] or all zeros when
+ * thresholds is NULL: NaN and -0.0 > 0 give 0.  There is no training step, so nothing depends on a reduction order.
+ * Argument errors, DPQ_ERR_ARG, in this order and before any device call: a NULL pointer; n < 1; D outside
+ * 1..DPQ_FLAT_BITS_MAX_D; id_offset as in dpq_flat_open.  Then the device: DPQ_ERR_NO_DEVICE without one.
+ * Device memory of a handle: n * Rp bytes, Rp = (D + 7) / 8 rounded up to a multiple of 16, and the workspaces of a byte
+ * handle; while a call runs that uploads in slices, a buffer of at most 128 MB on top of that. */
+#define DPQ_FLAT_BITS_MAX_D 4096
+/* A handle over packed rows the caller already has, uploaded as they are; masked and padded on the GPU. */
+int dpq_flat_open_bits(const uint8_t* rows /* [n][(D+7)/8], host */, int64_t n, int D /* bits */, int device,
+                       int64_t id_offset, dpq_flat** out);
+/* vectors[n][D], host memory -> bits_out[n][(D+7)/8], spare bits 0; binarised on the GPU in upload slices of at most
+ * 128 MB. */
+int dpq_bits_from_float(const float* vectors /* [n][D], host */, int64_t n, int D, const float* thresholds /* [D] or NULL */,
+                        int device, uint8_t* bits_out /* [n][(D+7)/8], spare bits 0 */);
+/* The same handle from fp32 rows, binarised on the device slice by slice, as dpq_flat_open_quantised encodes:
+ * indistinguishable from dpq_bits_from_float, then dpq_flat_open_bits. */
+int dpq_flat_open_binarised(const float* vectors, int64_t n, int D, const float* thresholds, int device, int64_t id_offset,
+                            dpq_flat** out);
+/* queries [nq][(D+7)/8] throughout; otherwise the argument lists and rules of the _u8 call of the same shape. */
+int dpq_flat_search_bits(dpq_flat* f, const uint8_t* queries, int nq, int top_k, int32_t* ids, float* dists);
+int dpq_flat_search_filtered_bits(dpq_flat* f, const dpq_flat_filter* ff, const uint8_t* queries, int nq, int top_k,
+                                  int32_t* ids, float* dists);
+int dpq_flat_range_search_bits(dpq_flat* f, const dpq_flat_filter* ff /* may be NULL */, const uint8_t* queries, int nq,
+                               const float* radii, dpq_range_result** out);
+int dpq_flat_rerank_bits(dpq_flat* f, const uint8_t* queries, int nq, const int32_t* cand_ids, int n_cand, int top_k,
+                         int32_t* ids, float* dists);
+int dpq_flat_rerank_bits_device(dpq_flat* f, const uint8_t* d_queries, int nq, const int32_t* d_cand_ids, int n_cand,
+                                int top_k, int32_t* d_ids, float* d_dists, void* hip_stream);
 
 /* ---- residual re-ranking: a second PQ level refines a shortlist ---------------
  * Every answer of dpq_query_batch is a coarse PQ approximation, and dpq_flat_rerank needs the raw vectors on the GPU
