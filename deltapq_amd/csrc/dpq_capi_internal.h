@@ -439,6 +439,7 @@ int query_device_src(dpq_index* x, const dpq_filter* filt, const TableSource& sr
                      float* d_dists, void* hip_stream);                                                         // dpq_capi.cpp
 int range_search_src(dpq_index* x, const TableSource& src, int nq, const float* radii, dpq_range_result** out);  // dpq_capi.cpp
 int ensure_out_stage(dpq_index* x, size_t elems);  // d_ids_stage / d_dists_stage                                  dpq_capi.cpp
+int splits_for(int n_seg_pass, int n_groups);  // scan workgroups per query group                                dpq_capi.cpp
 int flat_device_present(const std::string& who);                                                                // dpq_capi_flat.cpp
 bool lookup_id_ok(const dpq_index* x, int64_t id);                                                              // dpq_capi_lookup.cpp
 int lookup_on_device(dpq_index* x, const int32_t* d_ids, int64_t n, uint8_t* d_codes, float* d_vecs, hipStream_t stream,

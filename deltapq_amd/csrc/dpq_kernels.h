@@ -6,6 +6,12 @@
 
 #include "dpq_format.h"  // layout constants of the images (kChunk, kRunLen, kStripNodes, kPhaseLen)
 
+// s_setprio level of the kernels that run UNDER the previous pipelined batch's scan (lut_build_kernel, where the reason
+// is written; decode_list_kernel; tables_ingest_kernel)
+#ifndef DPQ_UNDER_SCAN_PRIO
+#define DPQ_UNDER_SCAN_PRIO 3
+#endif
+
 namespace dpq {
 
 constexpr int kScanThreads = 1024;  // 16 wavefronts, one workgroup per CU (LDS-bound residency)

@@ -112,9 +112,6 @@ __global__ __launch_bounds__(256) void lut_build_kernel(const float* __restrict_
     // CU take instruction issue by age, and what is left made a 15 us table build take 85 us (kernel-trace timeline,
     // profiles/r04_timeline_default.txt) -- on the critical path of the lane's next bootstrap.  Raised wave priority gives
     // these few wavefronts the issue slots they ask for; the scan loses as much as they use, no more.
-#ifndef DPQ_UNDER_SCAN_PRIO
-#define DPQ_UNDER_SCAN_PRIO 3
-#endif
     __builtin_amdgcn_s_setprio(DPQ_UNDER_SCAN_PRIO);
     const int q0 = blockIdx.x * kLutQueries, m = blockIdx.y, k = threadIdx.x;
     if (m == 0 && k < kLutQueries && q0 + k < n_slots) {
@@ -551,13 +548,8 @@ __global__ __launch_bounds__(64) void saturation_debug_kernel(const ScanArgs a, 
     if (sub == 0) *reinterpret_cast<uint64_t*>(out + (size_t)slot * 16 + 8) = key;
 }
 
-// Read window of the scan's ADC gathers at M = 8 (ds_read_b128 in flight before the first pair is summed; 0 = leave
-// the order to the compiler).  See scan_kernel.
 #ifndef DPQ_TIGHT_SLEEP
 #define DPQ_TIGHT_SLEEP 32  // s_sleep units of 64 cycles between two looks of the helper wavefront (16 / 32 / 64: the same scan, scripts/gpu_tight_sleep.sh)
-#endif
-#ifndef DPQ_GATHER_PIPE
-#define DPQ_GATHER_PIPE 0
 #endif
 
 // LDS map of the scan workgroup
@@ -1047,55 +1039,9 @@ __global__ __launch_bounds__(kScanThreads, (PLAIN && !STAMPS && (MF & ~kFiltered
             // ---- ADC lower bound: M LDS gathers per 4 * F queries; the fields of a dword are
             // summed with 3-input integer adds (no carry can cross a field) ----
             uint32_t acc[NA];
-            uint32_t fold_h[MD] = {};  // R == 1 with the pipelined gathers: the fold below is done as the groups complete
-            if constexpr (C::R == 1 && DPQ_GATHER_PIPE > 0) {
-                // The NG * 8 gathers of a wave step as ONE rolling window over the LDS queue: DPQ_GATHER_PIPE reads are
-                // issued up front, then every pair of reads that is summed into its accumulators is replaced by the next
-                // pair, so the queue never drains inside the step (the compiler's own order issued 16 + 8 + 8 reads with
-                // an s_waitcnt lgkmcnt(0) behind each group: three full drains per step at four wavefronts per SIMD).
-                // The scheduling fences pin the program order; the waits are the compiler's counted lgkmcnt(N).  The
-                // reject-bit fold of a group's four accumulators follows the group's last pair, under the later reads.
-                static_assert(NG * 8 == 32 && (DPQ_GATHER_PIPE % 2) == 0 && DPQ_GATHER_PIPE >= 2 && DPQ_GATHER_PIPE <= 14, "window of read pairs");
-                uint32_t off[8];
-#pragma unroll
-                for (int m = 0; m < 8; ++m) off[m] = (code[m >> 2] >> (8 * (m & 3))) & 0xffu;
-                uint4 gv[32];
-#define DPQ_RD(r) gv[r] = lut[(((r) >> 3) * M + ((r) & 7)) * 256 + off[(r) & 7]]
-#pragma unroll
-                for (int r = 0; r < DPQ_GATHER_PIPE; r += 2) {
-                    DPQ_RD(r);
-                    DPQ_RD(r + 1);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-#pragma unroll
-                for (int p = 0; p < 16; ++p) {  // pair p = reads 2p, 2p + 1 = sub-spaces 2 (p & 3), + 1 of group p >> 2
-                    if (2 * p + DPQ_GATHER_PIPE < 32) {
-                        DPQ_RD(2 * p + DPQ_GATHER_PIPE);
-                        DPQ_RD(2 * p + DPQ_GATHER_PIPE + 1);
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                    const int g = p >> 2;
-                    const uint4 x = gv[2 * p], y = gv[2 * p + 1];
-                    if ((p & 3) == 0) {
-                        acc[4 * g + 0] = x.x + y.x;
-                        acc[4 * g + 1] = x.y + y.y;
-                        acc[4 * g + 2] = x.z + y.z;
-                        acc[4 * g + 3] = x.w + y.w;
-                    } else {
-                        acc[4 * g + 0] += x.x + y.x;
-                        acc[4 * g + 1] += x.y + y.y;
-                        acc[4 * g + 2] += x.z + y.z;
-                        acc[4 * g + 3] += x.w + y.w;
-                    }
-                    if ((p & 3) == 3) {
-#pragma unroll
-                        for (int j = 4 * g; j < 4 * g + 4; ++j)
-                            fold_h[j / EB] = and_or(acc[j], C::LOW << (EB - 1), fold_h[j / EB] >> 1);
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-#undef DPQ_RD
-            } else
+            // (Tried at R == 1: the NG * 8 gathers as one rolling window of 8 / 12 / 14 reads pinned with sched_barrier, so the
+            // LDS queue never drains inside a step: 86.9 against 86.1 / 86.9 / 85.7 us on the filter alone, nothing -- the other
+            // wavefronts cover a wavefront's drain.  Removed; last present in d613e05.)
 #pragma unroll
             for (int g = 0; g < NG; ++g) {
                 if constexpr (C::R == 1) {
@@ -1162,12 +1108,8 @@ __global__ __launch_bounds__(kScanThreads, (PLAIN && !STAMPS && (MF & ~kFiltered
 #pragma unroll
             for (int h = 0; h < MD; ++h) {
                 uint32_t fail = 0;
-                if constexpr (C::R == 1 && DPQ_GATHER_PIPE > 0) {
-                    fail = fold_h[h];
-                } else {
 #pragma unroll
-                    for (int j = 0; j < C::J; ++j) fail = and_or(acc[EB * h + j], C::LOW << (EB - 1), fail >> 1);
-                }
+                for (int j = 0; j < C::J; ++j) fail = and_or(acc[EB * h + j], C::LOW << (EB - 1), fail >> 1);
                 fail >>= EB - C::J;
                 pend |= (uint64_t)(valid ? (~fail & live) : 0u) << (32 * h);
             }
@@ -1653,9 +1595,9 @@ __global__ __launch_bounds__(kStrandThreads, Q >= 4 ? 2 : Q == 2 ? 3 : 4) void s
 //    (c << 8 | (lane mod 32) << 2) + offset:(half << 7 | m & 3) hits its own bank whatever c is (a 4-byte-class DS access
 //    serves 32 lanes per pass: SQ_LDS_BANK_CONFLICT 14 cycles per launch); the address is one v_perm_b32 (the code byte
 //    lands on bits 8..15), the eight bytes are added with v_add3_u32.  A lane owns its accumulator (no saturation tricks,
-//    QT = 250 units instead of the batched scan's 64).  (DPQ_S1_U8 = 0 keeps the round's first shape: 8-byte rows per
-//    bank pair read whole with ds_read_b64, the wanted byte added with v_dot4 against a one-hot constant: 2 VALU
-//    instructions per node more, 8 VGPRs more, 2 % slower.)
+//    QT = 250 units instead of the batched scan's 64).  (Tried first: 8-byte rows per bank pair read whole with
+//    ds_read_b64, the wanted byte added with v_dot4 against a one-hot constant: 2 VALU instructions per node more,
+//    8 VGPRs more, 2 % slower.  Removed; last present in d613e05.)
 //  * the changed bytes never touch LDS: a lane loads the <= 8 bytes of each of its next four nodes with FOUR unaligned
 //    8-byte global loads at exactly the node's byte offset (the wave prefix sum of the masks' popcounts gives a lane's
 //    offset in the phase, the popcounts of its own earlier masks the rest), a phase ahead.  No row parking, no
@@ -1678,15 +1620,10 @@ __global__ __launch_bounds__(kStrandThreads, Q >= 4 ? 2 : Q == 2 ? 3 : 4) void s
 #ifndef DPQ_S1_QT
 #define DPQ_S1_QT 250  // units of the bound table that span (tau' - sum of minima); entries saturate at 255
 #endif
-#ifndef DPQ_S1_SKIP
-#define DPQ_S1_SKIP 0  // (timing experiments only, wrong results: 1 no ADC, 2 no stack / selector traffic, 4 no changed-byte loads, 8 one of the four, 16 the four from a cache-resident 64 KB)
-#endif
-#ifndef DPQ_S1_U8
-#define DPQ_S1_U8 1  // bound rows as two words per code value and bank, entries read with ds_read_u8 and added; 0: round 4's first shape, 8-byte rows + v_dot4
-#endif
-#ifndef DPQ_S1_PAIR
-#define DPQ_S1_PAIR 2  // two changed-byte loads per phase serve the four nodes where a pair's bytes fit one window: 1 = 8-byte windows, 2 = 12, 3 = 16 (always); 0: four loads
-#endif
+// (Tried for timing only, with wrong results: builds that left out the ADC, the stack / selector traffic or the
+// changed-byte loads -- 218.7 us complete, 206.2 / 213.7 / 175.0 us without each, 104.2 us without all three -- and builds
+// with per-step instructions that do nothing: eight more v_perm_b32 / eight s_mov_b32 / four more ds_read_u8 cost
+// 222.7 -> 229.0 / 221.6 / 225.0 us (profiles/r04_strand1_experiments.md).  Removed; last present in d613e05.)
 #ifndef DPQ_S1_DEPTH
 #define DPQ_S1_DEPTH 1  // phases the changed bytes are fetched ahead of their decode, 1 .. 3 (headers: four ahead; 2: 215 against 217 us)
 #endif
@@ -1701,7 +1638,7 @@ constexpr int kS1Buckets = 64;  // histogram words: bucket b = candidates under 
 static_assert((DPQ_S1_QT >> 2) < kS1Buckets && DPQ_S1_QT <= 253, "a lane per bucket; 8 entries of 255 must reject");
 
 struct S1Lds {
-    static constexpr size_t kTq = 0;                                          // [256][2][32] x 4 B bound words ([256][32] x 8 B rows without DPQ_S1_U8)
+    static constexpr size_t kTq = 0;                                          // [256][2][32] x 4 B bound words
     static constexpr size_t kSel = kTq + 256 * 32 * 8;                        // [16][32] x 4 B nibble selectors
     static constexpr size_t kStack = kSel + 16 * 32 * 4;                      // [waves][8][64] x 8 B ancestor stacks
     static constexpr size_t kT32 = kStack + (size_t)kS1Waves * 8 * 64 * 8;    // [8][256] f32 exact table
@@ -1714,7 +1651,7 @@ struct S1Lds {
 static_assert(S1Lds::kBytes <= 160 * 1024 && S1Lds::kTq == 0, "one workgroup per CU; the bound rows sit at LDS offset 0");
 
 // LDS accesses by BYTE OFFSET (this kernel has no static LDS: its dynamic LDS starts at offset 0, checked in the
-// prologue): the bound rows' addresses are built with v_perm_b32 and must reach ds_read_b64 as they are
+// prologue): the bound rows' addresses are built with v_perm_b32 and must reach ds_read_u8 as they are
 #define DPQ_LDS __attribute__((address_space(3)))
 __device__ __forceinline__ uint2 lds_ld64(uint32_t off) {
     const uint64_t v = *(const DPQ_LDS uint64_t*)(uintptr_t)off;
@@ -1722,13 +1659,7 @@ __device__ __forceinline__ uint2 lds_ld64(uint32_t off) {
 }
 __device__ __forceinline__ uint32_t lds_ld32(uint32_t off) { return *(const DPQ_LDS uint32_t*)(uintptr_t)off; }
 __device__ __forceinline__ void lds_st64(uint32_t off, uint2 v) { *(DPQ_LDS uint64_t*)(uintptr_t)off = ((uint64_t)v.y << 32) | v.x; }
-// a whole 8-byte row although one half is used: a ds_read_b64 of 32 lanes covers all 64 banks with (lane mod 32) * 8;
-// narrowed to ds_read_b32 the same addresses would meet two to a bank
 __device__ __forceinline__ uint32_t lds_ld8(uint32_t off) { return *(const DPQ_LDS uint8_t*)(uintptr_t)off; }
-__device__ __forceinline__ uint2 lds_ld64_whole(uint32_t off) {
-    const uint64_t v = *(const volatile DPQ_LDS uint64_t*)(uintptr_t)off;
-    return make_uint2((uint32_t)v, (uint32_t)(v >> 32));
-}
 
 // v_perm_b32 selector of a mask nibble: byte i = rank of bit i among the set bits (take the i-th changed byte) where the
 // bit is set, 4 + i (keep the parent's byte) elsewhere.  perm(parent, raw, sel).
@@ -1827,16 +1758,11 @@ __global__ __launch_bounds__(kS1Threads) void strand1_kernel(const ScanArgs a) {
             qtmp[tid] = make_uint2(lo, hi);
         }
         __syncthreads();
-        uint2* Tq = reinterpret_cast<uint2*>(smem + S1Lds::kTq);
-        if constexpr (DPQ_S1_U8) {
-            // word (c, half, bank) at c << 8 | half << 7 | bank << 2: sub-spaces 4 half .. 4 half + 3 of code value c
-            uint32_t* Tw = reinterpret_cast<uint32_t*>(smem + S1Lds::kTq);
-            for (int w = tid; w < 256 * 64; w += kS1Threads) {
-                const uint2 row = qtmp[w >> 6];
-                Tw[w] = ((w >> 5) & 1) ? row.y : row.x;
-            }
-        } else {
-            for (int w = tid; w < 256 * 32; w += kS1Threads) Tq[w] = qtmp[w >> 5];
+        // word (c, half, bank) at c << 8 | half << 7 | bank << 2: sub-spaces 4 half .. 4 half + 3 of code value c
+        uint32_t* Tw = reinterpret_cast<uint32_t*>(smem + S1Lds::kTq);
+        for (int w = tid; w < 256 * 64; w += kS1Threads) {
+            const uint2 row = qtmp[w >> 6];
+            Tw[w] = ((w >> 5) & 1) ? row.y : row.x;
         }
         if (tid == 0) {
             *reinterpret_cast<uint32_t*>(smem + S1Lds::kShare) = (uint32_t)QT;
@@ -1850,7 +1776,7 @@ __global__ __launch_bounds__(kS1Threads) void strand1_kernel(const ScanArgs a) {
 
     stamp();
     // LDS byte offsets a lane uses all along
-    const uint32_t lane8 = (uint32_t)(lane & 31) * (DPQ_S1_U8 ? 4u : 8u);                          // its copy of a bound row
+    const uint32_t lane8 = (uint32_t)(lane & 31) * 4u;                                            // its copy of a bound word
     const uint32_t lane_sel = (uint32_t)S1Lds::kSel + (uint32_t)(lane & 31) * 4u;                  // ... of a selector
     // row -1 of its stack column: depth 0 (the root, mask 0xFF: every byte replaced) reads a parent that does not matter
     // from the 512 bytes in front of the stack -- the previous wavefront's row 7 or the end of the selectors: valid LDS
@@ -1943,7 +1869,7 @@ __global__ __launch_bounds__(kS1Threads) void strand1_kernel(const ScanArgs a) {
         };
         struct Bytes {
             uint2 w[kPhaseLen];  // the (up to) eight changed bytes of each of them, from the node's first byte on
-            uint32_t x[4];       // (DPQ_S1_PAIR >= 2: the third (and fourth) dwords of the 12- (16-) byte windows of nodes 0 and 2)
+            uint32_t x[2];       // the third dwords of the 12-byte windows of nodes 0 and 2
         };
         auto load_hdr = [&](int g) -> Hdr {
             const int gc = min(g, GROUPS - 1);  // (past the strip: the last phase again, never used)
@@ -1958,56 +1884,18 @@ __global__ __launch_bounds__(kS1Threads) void strand1_kernel(const ScanArgs a) {
             const unsigned char* base = a.img.st_delta + (size_t)(uint32_t)__builtin_amdgcn_readlane((int)pb, gc) * 16;
             const uint32_t o1 = off + (uint32_t)__popc(h.masks & 0xffu), o2 = off + (uint32_t)__popc(h.masks & 0xffffu),
                            o3 = off + (uint32_t)__popc(h.masks & 0xffffffu);
-            if constexpr ((DPQ_S1_SKIP & 4) != 0) {
-                r.w[0] = make_uint2(off, o1), r.w[1] = make_uint2(o1, o2), r.w[2] = make_uint2(o2, o3), r.w[3] = make_uint2(o3, (uint32_t)(uintptr_t)base);
-                return r;
-            }
-            if constexpr ((DPQ_S1_SKIP & 8) != 0) {  // one of the four loads (the others' registers: copies)
-                __builtin_memcpy(&r.w[0], base + off, 8);
-                r.w[1] = make_uint2(r.w[0].x + o1, r.w[0].y), r.w[2] = make_uint2(r.w[0].x + o2, r.w[0].y), r.w[3] = make_uint2(r.w[0].x + o3, r.w[0].y);
-                return r;
-            }
-            if constexpr ((DPQ_S1_SKIP & 16) != 0) {  // the four loads, from the image's first 64 KB (cache-resident)
-                const unsigned char* b0 = a.img.st_delta + (((size_t)(uint32_t)__builtin_amdgcn_readlane((int)pb, gc) * 16) & 0xf000u);
-                __builtin_memcpy(&r.w[0], b0 + off, 8);
-                __builtin_memcpy(&r.w[1], b0 + o1, 8);
-                __builtin_memcpy(&r.w[2], b0 + o2, 8);
-                __builtin_memcpy(&r.w[3], b0 + o3, 8);
-                return r;
-            }
-            if constexpr (DPQ_S1_PAIR == 3) {  // 16-byte windows: a pair always fits
-                uint32_t a4[4], c4[4];
-                __builtin_memcpy(a4, base + off, 16);
-                __builtin_memcpy(c4, base + o2, 16);
-                r.w[0] = make_uint2(a4[0], a4[1]), r.x[0] = a4[2], r.x[2] = a4[3], r.w[2] = make_uint2(c4[0], c4[1]), r.x[1] = c4[2], r.x[3] = c4[3];
-                return r;
-            }
-            if constexpr (DPQ_S1_PAIR == 2) {
-                // As below with 12-byte windows: a pair runs past one in 0.3 % of the lanes, so the second node's own load is
-                // skipped by most wavefronts altogether (the branch around it is wave-uniform) instead of issued for a few lanes.
-                uint32_t a3[3], c3[3];
-                __builtin_memcpy(a3, base + off, 12);
-                __builtin_memcpy(c3, base + o2, 12);
-                r.w[0] = make_uint2(a3[0], a3[1]), r.x[0] = a3[2], r.w[2] = make_uint2(c3[0], c3[1]), r.x[1] = c3[2];
-                asm volatile("" : "=v"(r.w[1].x), "=v"(r.w[1].y), "=v"(r.w[3].x), "=v"(r.w[3].y));
-                if (o2 - off > 12u) __builtin_memcpy(&r.w[1], base + o1, 8);
-                if (off + mine - o2 > 12u) __builtin_memcpy(&r.w[3], base + o3, 8);
-                return r;
-            }
-            if constexpr (DPQ_S1_PAIR) {
-                // Two loads serve the four nodes wherever a pair's bytes fit one 8-byte window (the second node's are the first
-                // load's, shifted: below); only the lanes whose pair runs past it load the second node's bytes themselves.
-                __builtin_memcpy(&r.w[0], base + off, 8);
-                __builtin_memcpy(&r.w[2], base + o2, 8);
-                asm volatile("" : "=v"(r.w[1].x), "=v"(r.w[1].y), "=v"(r.w[3].x), "=v"(r.w[3].y));  // (whatever they hold: read only where loaded)
-                if (o2 - off > 8u) __builtin_memcpy(&r.w[1], base + o1, 8);
-                if (off + mine - o2 > 8u) __builtin_memcpy(&r.w[3], base + o3, 8);
-                return r;
-            }
-            __builtin_memcpy(&r.w[0], base + off, 8);  // byte addresses: unaligned 8-byte loads
-            __builtin_memcpy(&r.w[1], base + o1, 8);
-            __builtin_memcpy(&r.w[2], base + o2, 8);
-            __builtin_memcpy(&r.w[3], base + o3, 8);
+            // Two loads of 12 bytes serve the four nodes wherever a pair's bytes fit one window (the second node's are the first
+            // load's, shifted: below); a pair runs past it in 0.3 % of the lanes, so the second node's own load is skipped by
+            // most wavefronts altogether (the branch around it is wave-uniform) instead of issued for a few lanes.
+            // (Tried: four unaligned 8-byte loads per phase, the first shape; two 8-byte windows, - 2.5 %; these 12-byte ones,
+            // - 3.3 % more; 16-byte windows without the branch, + 9 %.  Removed; last present in d613e05.)
+            uint32_t a3[3], c3[3];
+            __builtin_memcpy(a3, base + off, 12);  // byte addresses: unaligned loads
+            __builtin_memcpy(c3, base + o2, 12);
+            r.w[0] = make_uint2(a3[0], a3[1]), r.x[0] = a3[2], r.w[2] = make_uint2(c3[0], c3[1]), r.x[1] = c3[2];
+            asm volatile("" : "=v"(r.w[1].x), "=v"(r.w[1].y), "=v"(r.w[3].x), "=v"(r.w[3].y));  // (whatever they hold: read only where loaded)
+            if (o2 - off > 12u) __builtin_memcpy(&r.w[1], base + o1, 8);
+            if (off + mine - o2 > 12u) __builtin_memcpy(&r.w[3], base + o3, 8);
             return r;
         };
         // Headers and bytes wait in RINGS of R slots with compile-time indices -- the phase loop is unrolled R times -- so that
@@ -2040,9 +1928,6 @@ __global__ __launch_bounds__(kS1Threads) void strand1_kernel(const ScanArgs a) {
             bq[(u + D) % R] = load_bytes(g + D, hq[(u + D) % R]);
             const Bytes& cur = bq[u];
             uint32_t codes[kPhaseLen][2], sum[kPhaseLen];
-#if defined(DPQ_S1_PAD_VALU) || defined(DPQ_S1_PAD_SALU) || defined(DPQ_S1_PAD_LDS)
-            uint32_t pad_v[4] = {1u, 2u, 3u, 4u}, pad_s = 5u, pad_l[4] = {0u, 0u, 0u, 0u};
-#endif
             // The four steps as a software pipeline over the LDS round trips: step s + 1's parent and selectors are read
             // behind step s's eight bound-row gathers and before their sums -- one round trip per step instead of two.
             struct Dec {
@@ -2057,10 +1942,6 @@ __global__ __launch_bounds__(kS1Threads) void strand1_kernel(const ScanArgs a) {
                 const uint32_t hi = (hdr.masks >> (8 * st + 4)) & 0xfu;
                 d.lo = (hdr.masks >> (8 * st)) & 0xfu;
                 d.paddr = (depth << 9) + lane_stk;
-                if constexpr ((DPQ_S1_SKIP & 2) != 0) {
-                    d.parent = make_uint2(d.paddr, hi), d.sel_lo = d.lo * 0x01010101u, d.sel_hi = hi * 0x01010101u;
-                    return d;
-                }
                 d.parent = lds_ld64(d.paddr);
                 d.sel_lo = lds_ld32((d.lo << 7) + lane_sel);
                 d.sel_hi = lds_ld32((hi << 7) + lane_sel);
@@ -2070,87 +1951,28 @@ __global__ __launch_bounds__(kS1Threads) void strand1_kernel(const ScanArgs a) {
 #pragma unroll
             for (int st = 0; st < kPhaseLen; ++st) {
                 uint2 raw = cur.w[st];
-                if constexpr (DPQ_S1_PAIR == 3) {
-                    if (st & 1) {  // bytes [pa, pa + 8) of the first node's 16-byte window
-                        const uint32_t pa = (uint32_t)__popc((hdr.masks >> (8 * (st - 1))) & 0xffu);
-                        const uint32_t w0 = cur.w[st - 1].x, w1 = cur.w[st - 1].y, w2 = cur.x[st >> 1], w3 = cur.x[2 + (st >> 1)];
-                        const bool s1 = pa >= 4u, s2 = pa >= 8u;
-                        const uint32_t d0 = s2 ? w2 : s1 ? w1 : w0, d1 = s2 ? w3 : s1 ? w2 : w1, d2 = s2 ? 0u : s1 ? w3 : w2;
-                        raw = make_uint2(__builtin_amdgcn_alignbyte(d1, d0, pa & 3u), __builtin_amdgcn_alignbyte(d2, d1, pa & 3u));
-                    }
-                } else if constexpr (DPQ_S1_PAIR == 2) {
-                    if (st & 1) {  // bytes [pa, pa + 8) of the first node's 12-byte window, unless the pair ran past it
-                        const uint32_t pa = (uint32_t)__popc((hdr.masks >> (8 * (st - 1))) & 0xffu), pn = (uint32_t)__popc((hdr.masks >> (8 * st)) & 0xffu);
-                        const uint32_t w0 = cur.w[st - 1].x, w1 = cur.w[st - 1].y, w2 = cur.x[st >> 1];
-                        const bool s1 = pa >= 4u, s2 = pa >= 8u;
-                        const uint32_t d0 = s2 ? w2 : s1 ? w1 : w0, d1 = s2 ? 0u : s1 ? w2 : w1, d2 = s1 ? 0u : w2;
-                        if (pa + pn <= 12u) raw = make_uint2(__builtin_amdgcn_alignbyte(d1, d0, pa & 3u), __builtin_amdgcn_alignbyte(d2, d1, pa & 3u));
-                    }
-                } else if constexpr (DPQ_S1_PAIR) {
-                    if (st & 1) {  // a pair's second node: its own load where the pair ran past 8 bytes, else the first node's window shifted
-                        const uint32_t pa = (uint32_t)__popc((hdr.masks >> (8 * (st - 1))) & 0xffu), pn = (uint32_t)__popc((hdr.masks >> (8 * st)) & 0xffu);
-                        const uint2 fst = cur.w[st - 1];
-                        const uint64_t sh = ((((uint64_t)fst.y << 32) | fst.x) >> ((8u * pa) & 63u));
-                        if (pa + pn <= 8u) raw = make_uint2((uint32_t)sh, (uint32_t)(sh >> 32));
-                    }
+                if (st & 1) {  // bytes [pa, pa + 8) of the first node's 12-byte window, unless the pair ran past it
+                    const uint32_t pa = (uint32_t)__popc((hdr.masks >> (8 * (st - 1))) & 0xffu), pn = (uint32_t)__popc((hdr.masks >> (8 * st)) & 0xffu);
+                    const uint32_t w0 = cur.w[st - 1].x, w1 = cur.w[st - 1].y, w2 = cur.x[st >> 1];
+                    const bool s1 = pa >= 4u, s2 = pa >= 8u;
+                    const uint32_t d0 = s2 ? w2 : s1 ? w1 : w0, d1 = s2 ? 0u : s1 ? w2 : w1, d2 = s1 ? 0u : w2;
+                    if (pa + pn <= 12u) raw = make_uint2(__builtin_amdgcn_alignbyte(d1, d0, pa & 3u), __builtin_amdgcn_alignbyte(d2, d1, pa & 3u));
                 }
                 const uint32_t raw_hi = (uint32_t)((((uint64_t)raw.y << 32) | raw.x) >> (8 * __popc(dc.lo)));
                 uint32_t* code = codes[st];
                 code[0] = __builtin_amdgcn_perm(dc.parent.x, raw.x, dc.sel_lo);
                 code[1] = __builtin_amdgcn_perm(dc.parent.y, raw_hi, dc.sel_hi);
-                if constexpr ((DPQ_S1_SKIP & 2) == 0) lds_st64(dc.paddr + 512u, make_uint2(code[0], code[1]));  // stack[depth] = code
-                // ADC, lower bound: sum of the eight entries; row of code byte c at c << 8, the lane's copy at lane8
-                if constexpr ((DPQ_S1_SKIP & 1) != 0) {
-                    if (st + 1 < kPhaseLen) dc = dec_reads(st + 1);
-                    sum[st] = 300u + (code[0] ^ code[1]);
-                    continue;
-                }
+                lds_st64(dc.paddr + 512u, make_uint2(code[0], code[1]));  // stack[depth] = code
+                // ADC, lower bound: sum of the eight entries; word of code byte c at c << 8, the lane's copy at lane8
                 uint32_t row[M];
 #pragma unroll
                 for (int m = 0; m < M; ++m) row[m] = __builtin_amdgcn_perm(code[m >> 2], lane8, 0x0c0c0400u + ((uint32_t)(m & 3) << 8));
-                if constexpr (DPQ_S1_U8) {
-                    uint32_t e[M];
+                uint32_t e[M];
 #pragma unroll
-                    for (int m = 0; m < M; ++m) e[m] = lds_ld8(row[m] + (uint32_t)(((m >> 2) << 7) | (m & 3)));
-                    if (st + 1 < kPhaseLen) dc = dec_reads(st + 1);
-                    sum[st] = ((e[0] + e[1] + e[2]) + (e[3] + e[4])) + (e[5] + e[6] + e[7]);
-#if defined(DPQ_S1_PAD_VALU) || defined(DPQ_S1_PAD_SALU) || defined(DPQ_S1_PAD_LDS)
-                    {  // (timing experiments: instructions that do nothing, per step)
-#ifdef DPQ_S1_PAD_VALU
-#pragma unroll
-                        for (int i = 0; i < DPQ_S1_PAD_VALU; ++i) asm volatile("v_perm_b32 %0, %0, %1, %2" : "+v"(pad_v[i & 3]) : "v"(lane8), "v"(code[0]));
-#endif
-#ifdef DPQ_S1_PAD_SALU
-#pragma unroll
-                        for (int i = 0; i < DPQ_S1_PAD_SALU; ++i) asm volatile("s_mov_b32 %0, %0" : "+s"(pad_s));
-#endif
-#ifdef DPQ_S1_PAD_LDS
-#pragma unroll
-                        for (int i = 0; i < DPQ_S1_PAD_LDS; ++i) {
-                            uint32_t t;
-                            asm volatile("ds_read_u8 %0, %1 offset:%2" : "=v"(t) : "v"(row[i & 7]), "n"(4 * (i & 7)));
-                            pad_l[i & 3] = t;
-                        }
-#endif
-                    }
-#endif
-                    continue;
-                }
-                uint2 e[M];
-#pragma unroll
-                for (int m = 0; m < M; ++m) e[m] = lds_ld64_whole(row[m]);
+                for (int m = 0; m < M; ++m) e[m] = lds_ld8(row[m] + (uint32_t)(((m >> 2) << 7) | (m & 3)));
                 if (st + 1 < kPhaseLen) dc = dec_reads(st + 1);
-                uint32_t acc0 = 0, acc1 = 0;  // two chains
-#pragma unroll
-                for (int m = 0; m < 4; ++m) {
-                    acc0 = __builtin_amdgcn_udot4(e[m].x, 1u << (8 * m), acc0, false);
-                    acc1 = __builtin_amdgcn_udot4(e[m + 4].y, 1u << (8 * m), acc1, false);
-                }
-                sum[st] = acc0 + acc1;
+                sum[st] = ((e[0] + e[1] + e[2]) + (e[3] + e[4])) + (e[5] + e[6] + e[7]);
             }
-#if defined(DPQ_S1_PAD_VALU) || defined(DPQ_S1_PAD_SALU) || defined(DPQ_S1_PAD_LDS)
-            asm volatile("" ::"v"(pad_v[0]), "v"(pad_v[1]), "v"(pad_v[2]), "v"(pad_v[3]), "s"(pad_s), "v"(pad_l[0]), "v"(pad_l[1]), "v"(pad_l[2]), "v"(pad_l[3]));
-#endif
             // what the bound lets through: the reference's distance and the whole (distance, id) key
             const uint32_t cutp = (uint32_t)cut + 1u;
             if (__ballot(min(min(sum[0], sum[1]), min(sum[2], sum[3])) <= cutp) && !(dbg & 1)) {

@@ -16,10 +16,6 @@
 
 namespace dpq {
 
-#ifndef DPQ_UNDER_SCAN_PRIO
-#define DPQ_UNDER_SCAN_PRIO 3
-#endif
-
 // grid = (n_slots, M), block = 256: one thread per entry of the [slot][m][256] table.
 __global__ __launch_bounds__(256) void tables_ingest_kernel(const float* __restrict__ tables, int nq, int n_slots, int M,
                                                              int K, float* __restrict__ lut, float* __restrict__ lut_min,

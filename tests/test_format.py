@@ -392,7 +392,7 @@ def test_strand1_decode_rules(lib, n):
 
 
 def test_strand1_bound_table_address_map():
-    """strand1_kernel's bound table in LDS (dpq_kernels.hip, DPQ_S1_U8): the eight entries of code value c as two words
+    """strand1_kernel's bound table in LDS (dpq_kernels.hip, S1Lds::kTq): the eight entries of code value c as two words
     (sub-spaces 0..3, 4..7), each stored once per bank -- word (c, half, bank) at c << 8 | half << 7 | bank << 2.  The fill
     loop and the read address (one v_perm_b32: code byte to bits 8..15, (lane mod 32) << 2 below it, sub-space in the
     ds_read_u8 offset field) restated in numpy: every lane reads entry[m][c] and the 32 lanes of a pass hit 32 banks."""
@@ -418,7 +418,7 @@ def test_strand1_bound_table_address_map():
 
 
 def test_strand1_pair_window_extraction():
-    """strand1_kernel (DPQ_S1_PAIR = 2): the second node of a pair takes bytes [p, p + 8) of the first node's 12-byte window
+    """strand1_kernel (its two changed-byte loads per phase): the second node of a pair takes bytes [p, p + 8) of the first node's 12-byte window
     -- a dword select on p >= 4 / p >= 8 and two v_alignbyte_b32 -- instead of a load of its own.  The rule restated in numpy
     for every p in 0..8: what it yields equals the window's bytes from p on (zeros behind the twelfth), so whenever the pair's
     bytes fit the window (p + the second node's count <= 12) the node reads exactly the bytes at its own offset."""
