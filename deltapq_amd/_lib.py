@@ -256,6 +256,13 @@ SYMBOLS = [
     ("dpq_query_batch_ip", ctypes.c_int, [_VP, _VP, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP, _VP]),
     ("dpq_query_batch_device_ip", ctypes.c_int, [_VP, _VP, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP, _VP, _VP]),
     ("dpq_ip_scores", ctypes.c_int, [_VP, _VP, _VP, ctypes.c_int, ctypes.c_int, _VP]),
+    ("dpq_candidate_search", ctypes.c_int, [_VP, _VP, ctypes.c_int, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP]),
+    ("dpq_candidate_search_device", ctypes.c_int, [_VP, _VP, ctypes.c_int, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP]),
+    ("dpq_candidate_search_tables", ctypes.c_int, [_VP, _VP, ctypes.c_int, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP]),
+    ("dpq_candidate_search_device_tables", ctypes.c_int,
+     [_VP, _VP, ctypes.c_int, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP]),
+    ("dpq_candidate_distances", ctypes.c_int, [_VP, _VP, ctypes.c_int, _VP, ctypes.c_int, _VP]),
+    ("dpq_candidate_distances_device", ctypes.c_int, [_VP, _VP, ctypes.c_int, _VP, ctypes.c_int, _VP, _VP]),
     ("dpq_profile_enable", ctypes.c_int, [_VP, ctypes.c_int]),
     ("dpq_profile_reset", ctypes.c_int, [_VP]),
     ("dpq_profile_read", ctypes.c_int, [_VP, P(Profile)]),

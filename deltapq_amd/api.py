@@ -665,6 +665,96 @@ class DeltaPQIndex:
               "dpq_query_batch_device_ip")
         return out_ids, out_scores
 
+    # ---- candidate search: PQ distances and top-k over each query's own ids (include/deltapq_amd.h) ----
+
+    @staticmethod
+    def _cand(cand_ids, nq):
+        """int32 [nq][n_cand], C-contiguous; ragged lists come padded with -1."""
+        c = np.ascontiguousarray(cand_ids, dtype=np.int32)
+        if c.ndim == 1:
+            c = c[None, :]
+        assert c.ndim == 2 and c.shape[0] == nq, "cand_ids must be [nq][n_cand]"
+        return c
+
+    def _candidate_search(self, fn, name, rows, cand_ids, top_k):
+        c = self._cand(cand_ids, rows.shape[0])
+        nq = rows.shape[0]
+        ids = np.empty((nq, top_k), dtype=np.int32)
+        dists = np.empty((nq, top_k), dtype=np.float32)
+        check(fn(self._h, _np_ptr(rows), nq, _np_ptr(c), c.shape[1], top_k, _np_ptr(ids), _np_ptr(dists)), name)
+        return ids, dists
+
+    def candidate_search(self, queries, cand_ids, top_k):
+        """The best top_k of each query's own candidates by PQ distance (dpq_candidate_search): cand_ids int32
+        [nq][n_cand] of reported ids, -1 = padding, another shard's ids are skipped.  Returns (ids int32 [nq][k], dists
+        float32 [nq][k]), the distances query_batch reports for those ids, padded with -1 / +inf."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        return self._candidate_search(self._lib.dpq_candidate_search, "dpq_candidate_search", q, cand_ids, top_k)
+
+    def candidate_search_tables(self, tables, cand_ids, top_k):
+        """candidate_search with the caller's distance tables [nq][M][K] (dpq_candidate_search_tables); needs no
+        codebook."""
+        return self._candidate_search(self._lib.dpq_candidate_search_tables, "dpq_candidate_search_tables",
+                                      self._tables(tables), cand_ids, top_k)
+
+    def candidate_distances(self, queries, cand_ids):
+        """float32 [nq][n_cand]: the PQ distance of cand_ids[q][j] to query q, in place (dpq_candidate_distances); NaN
+        where the entry is padding or another shard's id."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        c = self._cand(cand_ids, q.shape[0])
+        dists = np.empty(c.shape, dtype=np.float32)
+        check(self._lib.dpq_candidate_distances(self._h, _np_ptr(q), q.shape[0], _np_ptr(c), c.shape[1], _np_ptr(dists)),
+              "dpq_candidate_distances")
+        return dists
+
+    def _candidate_search_torch(self, fn, name, rows, cand_ids, top_k, out_ids, out_dists):
+        import torch
+        assert rows.is_cuda and rows.dtype == torch.float32 and rows.is_contiguous()
+        assert cand_ids.is_cuda and cand_ids.dtype == torch.int32 and cand_ids.is_contiguous() and cand_ids.dim() == 2
+        nq = rows.shape[0]
+        assert cand_ids.shape[0] == nq
+        if out_ids is None:
+            out_ids = torch.empty((nq, top_k), dtype=torch.int32, device=rows.device)
+        if out_dists is None:
+            out_dists = torch.empty((nq, top_k), dtype=torch.float32, device=rows.device)
+        stream = torch.cuda.current_stream(rows.device).cuda_stream
+        check(fn(self._h, ctypes.c_void_p(rows.data_ptr()), nq, ctypes.c_void_p(cand_ids.data_ptr()), cand_ids.shape[1], top_k,
+                 ctypes.c_void_p(out_ids.data_ptr()), ctypes.c_void_p(out_dists.data_ptr()), ctypes.c_void_p(stream)), name)
+        return out_ids, out_dists
+
+    def candidate_search_torch(self, queries, cand_ids, top_k, out_ids=None, out_dists=None):
+        """candidate_search on device tensors, synchronous on torch's current stream (dpq_candidate_search_device)."""
+        return self._candidate_search_torch(self._lib.dpq_candidate_search_device, "dpq_candidate_search_device", queries,
+                                            cand_ids, top_k, out_ids, out_dists)
+
+    def candidate_search_tables_torch(self, tables, cand_ids, top_k, out_ids=None, out_dists=None):
+        """candidate_search_tables on device tensors ([nq][M][K] float32), synchronous on torch's current stream
+        (dpq_candidate_search_device_tables)."""
+        assert tables.dim() == 3
+        return self._candidate_search_torch(self._lib.dpq_candidate_search_device_tables,
+                                            "dpq_candidate_search_device_tables", tables, cand_ids, top_k, out_ids, out_dists)
+
+    def candidate_distances_torch(self, queries, cand_ids, out=None):
+        """candidate_distances on device tensors, synchronous on torch's current stream
+        (dpq_candidate_distances_device)."""
+        import torch
+        assert queries.is_cuda and queries.dtype == torch.float32 and queries.is_contiguous()
+        assert cand_ids.is_cuda and cand_ids.dtype == torch.int32 and cand_ids.is_contiguous() and cand_ids.dim() == 2
+        nq = queries.shape[0]
+        assert cand_ids.shape[0] == nq
+        if out is None:
+            out = torch.empty(tuple(cand_ids.shape), dtype=torch.float32, device=queries.device)
+        stream = torch.cuda.current_stream(queries.device).cuda_stream
+        check(self._lib.dpq_candidate_distances_device(self._h, ctypes.c_void_p(queries.data_ptr()), nq,
+                                                       ctypes.c_void_p(cand_ids.data_ptr()), cand_ids.shape[1],
+                                                       ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(stream)),
+              "dpq_candidate_distances_device")
+        return out
+
     def set_vec_ids(self, vec_id):
         """The original vector id of every node this handle holds (dpq_set_vec_ids): `vec_id` is the handle's local
         slice, uint32 [node_hi - node_lo], of the builder's DFS position -> vector id array.  Kept on the device for
@@ -849,6 +939,18 @@ class RotatedIndex:
     def query_batch_ip(self, queries, top_k, id_filter=None):
         """An orthogonal rotation leaves inner products alone: rotate the queries, then the index's own call."""
         return self.index.query_batch_ip(self._rotated_host(queries), top_k, id_filter=id_filter)
+
+    def candidate_search(self, queries, cand_ids, top_k):
+        return self.index.candidate_search(self._rotated_host(queries), cand_ids, top_k)
+
+    def candidate_distances(self, queries, cand_ids):
+        return self.index.candidate_distances(self._rotated_host(queries), cand_ids)
+
+    def candidate_search_torch(self, queries, cand_ids, top_k, **kw):
+        return self.index.candidate_search_torch(self._rotated(queries), cand_ids, top_k, **kw)
+
+    def candidate_distances_torch(self, queries, cand_ids, **kw):
+        return self.index.candidate_distances_torch(self._rotated(queries), cand_ids, **kw)
 
     def __getattr__(self, name):
         if name == "index":      # (not set yet: __init__ failed early)

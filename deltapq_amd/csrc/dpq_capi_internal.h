@@ -22,6 +22,7 @@
 
 #include "../../include/deltapq_amd.h"
 #include "dpq_build.h"
+#include "dpq_candidates.h"
 #include "dpq_filter.h"
 #include "dpq_flat.h"
 #include "dpq_format.h"
@@ -241,6 +242,21 @@ struct LookupWs {
     size_t ids_n = 0, codes_n = 0, vecs_n = 0, tile_n = 0, tile_segs_n = 0;
 };
 
+// The device buffers of the candidate search (dpq_candidate_search* / dpq_candidate_distances*), apart from every search
+// lane's workspace, its tables included.  The work buffers hold one slice (at most 2^20 candidates of at most 2048
+// queries); the staging buffers of the host forms hold a whole call.
+struct CandWs {
+    DevBuf<float> lut32;      // [slice queries][M][256] exact tables
+    DevBuf<float> lut_min;    // [slice queries][M][4] the table build writes its partial minima unconditionally
+    DevBuf<int32_t> local;    // [slice] the candidates with everything that is not a node of this handle as -1
+    DevBuf<uint8_t> codes;    // [slice][M] their level-1 codes
+    DevBuf<uint64_t> keys;    // [slice queries][cand_keys(n_cand)]
+    DevBuf<uint32_t> flag;    // [2] a candidate names no node of the index; a table entry is no distance
+    DevBuf<float> d_in, d_dists;    // host forms: queries or tables, and the distances
+    DevBuf<int32_t> d_cand, d_ids;  // ... the candidates and the ids
+    size_t lut_n = 0, min_n = 0, local_n = 0, codes_n = 0, keys_n = 0, in_n = 0, dists_n = 0, cand_n = 0, ids_n = 0;
+};
+
 // Where a batch's exact tables come from: queries against the handle's codebook (lut_build_kernel), or the caller's own
 // tables[nq][M][K] (tables_ingest_kernel), which raises *d_bad when an entry is not a distance.
 struct TableSource {
@@ -373,6 +389,7 @@ struct dpq_index {
     std::vector<int> level_off, level_cnt;
     RangeWs range;                   // dpq_range_search
     LookupWs lookup;                 // dpq_get_codes / dpq_reconstruct / dpq_decode_range
+    CandWs cand;                     // dpq_candidate_search* / dpq_candidate_distances*
     DevBuf<uint32_t> d_vec_id;       // [n_local] local node -> original vector id (dpq_set_vec_ids; the _vec filter constructors)
     bool vec_ids_set = false;
     DevBuf<unsigned long long> d_filter_count;  // [1] the set bits of the filter being built (dpq_filter_create_* on the device)

@@ -46,6 +46,9 @@
  *     PQ codes)
  *   (none: a caller's own distance tables:      dpq_query_batch_tables / dpq_range_search_tables
  *     weights, masks, residual queries)
+ *   (none: FAISS's IndexPQ distance computer    dpq_candidate_search[_device][_tables] / dpq_candidate_distances[_device]
+ *     over ids; search with a per-query           (PQ distances and top-k over each query's own id list)
+ *     IDSelectorArray)
  *   (none: FAISS's IndexFlatIP: search, an      dpq_flat_search_ip / dpq_flat_search_filtered_ip /
  *     IDSelector, range_search; re-ranking by     dpq_flat_range_search_ip / dpq_flat_rerank_ip[_device],
  *     inner product)                              dpq_merge_topk_ip_host
@@ -1275,6 +1278,58 @@ int dpq_query_batch_device_ip(dpq_index* idx, const dpq_filter* filter, const fl
                               int32_t* d_ids, float* d_scores, float* d_gaps, float* d_bias, void* hip_stream);
 /* Host only, no device: scores from merged gaps (shards).  A negative id gives -inf. */
 int dpq_ip_scores(const float* bias, const float* gaps, const int32_t* ids, int nq, int top_k, float* scores_out);
+
+/* ---- candidate search: PQ distances and top-k over each query's own ids ---------
+ * Every search above runs over the whole handle, or over one filter shared by the whole batch.  These calls take, per
+ * query, the list of ids that matter for THAT query -- what a graph or inverted-list traversal hands over, the allowed
+ * rows of one tenant of a mixed batch, the hits of a text retriever, the lists of dpq_range_search or of another handle
+ * -- and answer with their PQ distances (the _distances forms) or the best top_k of them (the _search forms).  Beside
+ * dpq_flat_rerank* (raw rows) and dpq_refine_rerank* (two-level reconstructions) this is the plain one-level ranker: it
+ * needs nothing but the index.  cand_ids is [nq][n_cand], row-major; ragged lists are padded to n_cand with -1.
+ *   Distance   of candidate c for query q: to the bit what dpq_query_batch reports for id c on this handle.  With T the
+ *           query's exact table (the L2 rule of every search, or the caller's tables[q] under the rules of "search by
+ *           distance tables": M and K the handle's, columns K .. 255 at +inf) and code the node's M bytes: on a DTC
+ *           handle (float) of the fp64 sum, m ascending, of the fp32 entries T[m][code[m]]; on a dpq_open_plain_* handle
+ *           `float dist += T[m][code[m]]`, m ascending, M roundings.  +inf is an ordinary value; NaN inputs are out of
+ *           scope.  tests/_candidates_restatement.py restates the rules in numpy; the GPU meets them bit for bit.
+ *   Ids     A candidate is a reported id, exactly as dpq_query_batch reports it: a global DFS position, with the even-N
+ *           rule (on a DTC index of even N the id N names position N - 1).  A negative candidate is padding.  A
+ *           candidate that names a node of the index but not of this handle -- another shard's: its position lies in
+ *           [0, n_codes_total) outside [node_lo, node_hi) -- is skipped like padding, so every shard can be handed the
+ *           same lists and the partial answers merge with dpq_merge_topk_* unchanged.  A candidate that names no node of
+ *           the whole index (beyond N; N - 1 on an even-N DTC index; N on a plain one) is DPQ_ERR_ARG: the host forms
+ *           check on the host before any device work, the device forms raise a flag word that is read back once at the
+ *           end of the call (their outputs are then unspecified).
+ *   Search  The best top_k valid candidates by key `distance bits << 32 | id`, ascending; the reported id is the
+ *           candidate itself; a node named twice by one query counts once; rows are padded with -1 / +inf when fewer
+ *           than top_k candidates are valid.  1 <= top_k <= n_cand <= 16384 (else DPQ_ERR_ARG).
+ *   Distances   dists[q][j] is the distance of cand_ids[q][j], in place; padding and skipped entries get a quiet NaN.
+ *           1 <= n_cand <= 16384.
+ *   Tables  A table entry that is negative, -inf or a NaN is DPQ_ERR_ARG, as in dpq_query_batch_tables: checked on the
+ *           host by the host form, by a flag word in the device form.  The _tables forms work before dpq_set_codebook;
+ *           the query forms are DPQ_ERR_STATE there.  Inner product composes: dpq_ip_tables, then
+ *           dpq_candidate_search_tables (the distances are gaps), then dpq_ip_scores.
+ *   State   Handles of M = 8 and M = 16 (what the code lookup decodes).  nq == 0 is DPQ_OK and writes nothing.  All
+ *           forms are synchronous and finish pending asynchronous batches first; the device forms enqueue on
+ *           `hip_stream` (NULL = default stream) and return with the results complete (dpq_refine_rerank_device's
+ *           conventions).  The calls work in buffers of their own, kept with the handle until dpq_close -- one slice of
+ *           at most 2^20 candidates of at most 2048 queries: their tables (M KB a query), M bytes of code and 8 bytes
+ *           of key a candidate -- and never write into a search lane's workspace: dpq_query_batch before and after
+ *           gives the same answer.  The host forms also keep their staging of a whole call.  Argument checks that need
+ *           no device come first. */
+int dpq_candidate_search(dpq_index* idx, const float* queries, int nq, const int32_t* cand_ids, int n_cand, int top_k,
+                         int32_t* ids, float* dists);
+int dpq_candidate_search_device(dpq_index* idx, const float* d_queries, int nq, const int32_t* d_cand_ids, int n_cand,
+                                int top_k, int32_t* d_ids, float* d_dists, void* hip_stream);
+/* tables[nq][M][K] standing where the queries' L2 tables stand. */
+int dpq_candidate_search_tables(dpq_index* idx, const float* tables, int nq, const int32_t* cand_ids, int n_cand, int top_k,
+                                int32_t* ids, float* dists);
+int dpq_candidate_search_device_tables(dpq_index* idx, const float* d_tables, int nq, const int32_t* d_cand_ids, int n_cand,
+                                       int top_k, int32_t* d_ids, float* d_dists, void* hip_stream);
+/* dists[nq][n_cand]. */
+int dpq_candidate_distances(dpq_index* idx, const float* queries, int nq, const int32_t* cand_ids, int n_cand, float* dists);
+int dpq_candidate_distances_device(dpq_index* idx, const float* d_queries, int nq, const int32_t* d_cand_ids, int n_cand,
+                                   float* d_dists, void* hip_stream);
 
 /* ---- measurement -------------------------------------------------------- */
 int dpq_profile_enable(dpq_index* idx, int on);  /* 0 off, 1 every kernel, 2 scan launches only (less event overhead) */
