@@ -81,6 +81,14 @@ class OpqStats(ctypes.Structure):
                 ("rotate_ms", ctypes.c_double), ("cross_ms", ctypes.c_double), ("procrustes_ms", ctypes.c_double)]
 
 
+class IvfStats(ctypes.Structure):
+    _fields_ = [("n_assigned", c_i64), ("n_unassigned", c_i64), ("max_list_len", c_i64), ("device_bytes", c_i64),
+                ("nlist", c_i32), ("has_centroids", c_i32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 # every symbol include/deltapq_amd.h declares: (name, restype, argtypes)
 _VP = ctypes.c_void_p
 SYMBOLS = [
@@ -263,6 +271,19 @@ SYMBOLS = [
      [_VP, _VP, ctypes.c_int, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP]),
     ("dpq_candidate_distances", ctypes.c_int, [_VP, _VP, ctypes.c_int, _VP, ctypes.c_int, _VP]),
     ("dpq_candidate_distances_device", ctypes.c_int, [_VP, _VP, ctypes.c_int, _VP, ctypes.c_int, _VP, _VP]),
+    ("dpq_ivf_create", ctypes.c_int, [_VP, _VP, c_i64, ctypes.c_int, P(_VP)]),
+    ("dpq_ivf_create_device", ctypes.c_int, [_VP, _VP, c_i64, ctypes.c_int, _VP, P(_VP)]),
+    ("dpq_ivf_build", ctypes.c_int, [_VP, _VP, ctypes.c_int, P(_VP)]),
+    ("dpq_ivf_set_centroids", ctypes.c_int, [_VP, _VP, ctypes.c_int]),
+    ("dpq_ivf_free", None, [_VP]),
+    ("dpq_ivf_get_info", ctypes.c_int, [_VP, P(IvfStats)]),
+    ("dpq_ivf_get", ctypes.c_int, [_VP, _VP, _VP]),
+    ("dpq_ivf_search_probes", ctypes.c_int, [_VP, _VP, ctypes.c_int, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP]),
+    ("dpq_ivf_search_probes_device", ctypes.c_int,
+     [_VP, _VP, ctypes.c_int, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP]),
+    ("dpq_ivf_probe", ctypes.c_int, [_VP, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP]),
+    ("dpq_ivf_search", ctypes.c_int, [_VP, _VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, _VP, _VP]),
+    ("dpq_ivf_search_device", ctypes.c_int, [_VP, _VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP]),
     ("dpq_profile_enable", ctypes.c_int, [_VP, ctypes.c_int]),
     ("dpq_profile_reset", ctypes.c_int, [_VP]),
     ("dpq_profile_read", ctypes.c_int, [_VP, P(Profile)]),

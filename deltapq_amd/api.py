@@ -1171,6 +1171,151 @@ class IdFilter:
         self.close()
 
 
+class IVF:
+    """Inverted lists over the nodes of one DeltaPQIndex (dpq_ivf, include/deltapq_amd.h "IVF search"): a query scans only
+    the lists it probes.  Keeps its index alive; close it (or leave its `with` block) before the index is closed."""
+
+    def __init__(self, index, handle):
+        self._lib = index._lib
+        self._index = index
+        self._h = handle
+
+    @classmethod
+    def build(cls, index, centroids):
+        """Lists by the nearest centroid of every node's reconstruction (dpq_ivf_build); centroids float32
+        [nlist][M * Ds], kept for probe() and search()."""
+        c = np.ascontiguousarray(centroids, dtype=np.float32)
+        assert c.ndim == 2, "centroids must be [nlist][M * Ds]"
+        h = ctypes.c_void_p()
+        check(index._lib.dpq_ivf_build(index._h, _np_ptr(c), c.shape[0], h), "dpq_ivf_build")
+        return cls(index, h)
+
+    @classmethod
+    def from_labels(cls, index, labels, nlist, centroids=None):
+        """Lists from labels (dpq_ivf_create; a CUDA int32 tensor: dpq_ivf_create_device on torch's current stream):
+        labels[l] is the list of the index's local node l, -1 puts it in no list.  `centroids`: see set_centroids."""
+        h = ctypes.c_void_p()
+        if isinstance(labels, np.ndarray) or not hasattr(labels, "data_ptr"):
+            a = np.ascontiguousarray(np.asarray(labels, dtype=np.int32).ravel())
+            check(index._lib.dpq_ivf_create(index._h, _np_ptr(a), a.size, int(nlist), h), "dpq_ivf_create")
+        else:
+            import torch
+            assert labels.is_cuda and labels.dtype == torch.int32 and labels.is_contiguous()
+            stream = ctypes.c_void_p(torch.cuda.current_stream(labels.device).cuda_stream)
+            check(index._lib.dpq_ivf_create_device(index._h, ctypes.c_void_p(labels.data_ptr()), labels.numel(), int(nlist),
+                                                   stream, h), "dpq_ivf_create_device")
+        ivf = cls(index, h)
+        if centroids is not None:
+            ivf.set_centroids(centroids)
+        return ivf
+
+    def set_centroids(self, centroids):
+        """Attaches centroids float32 [nlist][M * Ds] to lists made from labels (dpq_ivf_set_centroids)."""
+        c = np.ascontiguousarray(centroids, dtype=np.float32)
+        assert c.ndim == 2, "centroids must be [nlist][M * Ds]"
+        check(self._lib.dpq_ivf_set_centroids(self._h, _np_ptr(c), c.shape[0]), "dpq_ivf_set_centroids")
+        return self
+
+    def info(self):
+        s = _lib.IvfStats()
+        check(self._lib.dpq_ivf_get_info(self._h, s), "dpq_ivf_get_info")
+        return s.as_dict()
+
+    def lists(self):
+        """(offsets int64 [nlist + 1], ids int32 [n_assigned]): list l holds ids[offsets[l]:offsets[l + 1]], the reported
+        ids of its nodes, ascending (dpq_ivf_get)."""
+        inf = self.info()
+        offsets = np.empty(inf["nlist"] + 1, dtype=np.int64)
+        ids = np.empty(inf["n_assigned"], dtype=np.int32)
+        check(self._lib.dpq_ivf_get(self._h, _np_ptr(offsets), _np_ptr(ids) if ids.size else None), "dpq_ivf_get")
+        return offsets, ids
+
+    @staticmethod
+    def _queries(queries):
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        return q[None, :] if q.ndim == 1 else q
+
+    def probe(self, queries, nprobe):
+        """(lists int32 [nq][nprobe], dists float32 [nq][nprobe]): each query's nprobe nearest centroids by (exact L2
+        distance, list number) (dpq_ivf_probe)."""
+        q = self._queries(queries)
+        lists = np.empty((q.shape[0], nprobe), dtype=np.int32)
+        dists = np.empty((q.shape[0], nprobe), dtype=np.float32)
+        check(self._lib.dpq_ivf_probe(self._h, _np_ptr(q), q.shape[0], nprobe, _np_ptr(lists), _np_ptr(dists)), "dpq_ivf_probe")
+        return lists, dists
+
+    def search(self, queries, nprobe, top_k):
+        """The top_k nearest codes of the nprobe lists nearest to each query (dpq_ivf_search).  Returns (ids int32
+        [nq][k], dists float32 [nq][k]), the distances query_batch reports for those ids, padded with -1 / +inf."""
+        q = self._queries(queries)
+        ids = np.empty((q.shape[0], top_k), dtype=np.int32)
+        dists = np.empty((q.shape[0], top_k), dtype=np.float32)
+        check(self._lib.dpq_ivf_search(self._h, _np_ptr(q), q.shape[0], nprobe, top_k, _np_ptr(ids), _np_ptr(dists)),
+              "dpq_ivf_search")
+        return ids, dists
+
+    def search_probes(self, queries, probes, top_k):
+        """search over the caller's own lists: probes int32 [nq][nprobe], -1 = padding (dpq_ivf_search_probes)."""
+        q = self._queries(queries)
+        p = np.ascontiguousarray(probes, dtype=np.int32)
+        if p.ndim == 1:
+            p = p[None, :]
+        assert p.ndim == 2 and p.shape[0] == q.shape[0], "probes must be [nq][nprobe]"
+        ids = np.empty((q.shape[0], top_k), dtype=np.int32)
+        dists = np.empty((q.shape[0], top_k), dtype=np.float32)
+        check(self._lib.dpq_ivf_search_probes(self._h, _np_ptr(q), q.shape[0], _np_ptr(p), p.shape[1], top_k, _np_ptr(ids),
+                                              _np_ptr(dists)), "dpq_ivf_search_probes")
+        return ids, dists
+
+    @staticmethod
+    def _torch_out(queries, top_k, out_ids, out_dists):
+        import torch
+        assert queries.is_cuda and queries.dtype == torch.float32 and queries.is_contiguous() and queries.dim() == 2
+        nq = queries.shape[0]
+        if out_ids is None:
+            out_ids = torch.empty((nq, top_k), dtype=torch.int32, device=queries.device)
+        if out_dists is None:
+            out_dists = torch.empty((nq, top_k), dtype=torch.float32, device=queries.device)
+        return nq, out_ids, out_dists, ctypes.c_void_p(torch.cuda.current_stream(queries.device).cuda_stream)
+
+    def search_torch(self, queries, nprobe, top_k, out_ids=None, out_dists=None):
+        """search on device tensors, synchronous on torch's current stream (dpq_ivf_search_device)."""
+        nq, out_ids, out_dists, stream = self._torch_out(queries, top_k, out_ids, out_dists)
+        check(self._lib.dpq_ivf_search_device(self._h, ctypes.c_void_p(queries.data_ptr()), nq, nprobe, top_k,
+                                              ctypes.c_void_p(out_ids.data_ptr()), ctypes.c_void_p(out_dists.data_ptr()), stream),
+              "dpq_ivf_search_device")
+        return out_ids, out_dists
+
+    def search_probes_torch(self, queries, probes, top_k, out_ids=None, out_dists=None):
+        """search_probes on device tensors, synchronous on torch's current stream (dpq_ivf_search_probes_device)."""
+        import torch
+        nq, out_ids, out_dists, stream = self._torch_out(queries, top_k, out_ids, out_dists)
+        assert probes.is_cuda and probes.dtype == torch.int32 and probes.is_contiguous() and probes.dim() == 2
+        assert probes.shape[0] == nq
+        check(self._lib.dpq_ivf_search_probes_device(self._h, ctypes.c_void_p(queries.data_ptr()), nq,
+                                                     ctypes.c_void_p(probes.data_ptr()), probes.shape[1], top_k,
+                                                     ctypes.c_void_p(out_ids.data_ptr()), ctypes.c_void_p(out_dists.data_ptr()),
+                                                     stream), "dpq_ivf_search_probes_device")
+        return out_ids, out_dists
+
+    def close(self):
+        if self._h is not None:
+            self._lib.dpq_ivf_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 class FlatIdFilter:
     """A filter of FlatIndex / FlatIndexU8 / FlatIndexI8 / FlatIndexBits .search_filtered and .range_search (dpq_flat_filter): the set of reported ids
     (row + id_offset) a search may return, compacted once on the index's device into a list of eligible rows.  The bitmap

@@ -26,6 +26,7 @@
 #include "dpq_filter.h"
 #include "dpq_flat.h"
 #include "dpq_format.h"
+#include "dpq_ivf.h"
 #include "dpq_kernels.h"
 #include "dpq_lookup.h"
 #include "dpq_opq.h"
@@ -190,6 +191,33 @@ struct dpq_flat_filter {
     int device = 0;
     DevBuf<uint32_t> list;   // [n_allowed]
     int64_t n_allowed = 0;
+};
+
+// An inverted file over one handle's nodes (dpq_ivf_*, dpq_capi_ivf.cpp): the lists in device memory of their own, and
+// the workspace every search on it works in -- apart from every search lane's workspace, tables included.
+struct dpq_ivf {
+    dpq_index* idx = nullptr;       // the handle it was made on; freed before dpq_close
+    int device = 0;
+    int nlist = 0, M = 0, D = 0;      // D = M * Ds of the centroids (0: none set)
+    int64_t n_assigned = 0, n_unassigned = 0, max_list_len = 0;
+    std::vector<int64_t> h_offsets; // [nlist + 1] host copy (dpq_ivf_get, dpq_ivf_get_info)
+    DevBuf<int64_t> offsets;        // [nlist + 1]
+    DevBuf<int32_t> ids;            // [n_assigned] reported ids, ascending inside a list
+    DevBuf<uint8_t> codes;          // [n_assigned][M] plain code values in list order
+    DevBuf<float> centroids;        // [nlist][D] (launch_flat_search's rows: D is a multiple of 8); NULL: none set
+    int64_t device_bytes = 0;       // of the four above
+    // workspace, grown on demand and kept until dpq_ivf_free
+    DevBuf<float> lut32, lut_min;          // [slice queries][M][256] exact tables, [slice queries][M][4]
+    DevBuf<int32_t> probes;                // [slice queries][nprobe] the pre-pass's rows
+    DevBuf<int32_t> part_ids, tmp_ids;     // [nprobe][slice queries][top_k] the lists' answers; [slice queries][top_k] a
+    DevBuf<float> part_dists, tmp_dists;   // merge round's
+    DevBuf<uint32_t> flag;                 // [1] a probe names no list
+    DevBuf<uint64_t> keys;                 // coarse step: a batch's key buffers and states
+    DevBuf<dpq::FlatQueryState> state;
+    DevBuf<float> d_in, d_dists, d_cdists; // host forms: queries, distances; the coarse step's distances
+    DevBuf<int32_t> d_probes, d_ids;       // ... probes, ids
+    size_t lut_n = 0, min_n = 0, probes_n = 0, part_ids_n = 0, part_dists_n = 0, tmp_ids_n = 0, tmp_dists_n = 0,
+           keys_n = 0, state_n = 0, in_n = 0, dists_n = 0, cdists_n = 0, dprobes_n = 0, ids_n = 0;
 };
 
 uint64_t next_index_serial();  // dpq_capi.cpp: one counter for the process

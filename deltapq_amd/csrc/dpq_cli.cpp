@@ -98,6 +98,8 @@ int main(int argc, char* argv[]) {
     long long train_size = 0;
     bool opq = false;
     int opq_outer = 0, opq_init_iters = 25, opq_inner_iters = 4;
+    std::string ivf_path;
+    int nprobe = 1;
     for (int i = 0; i < argc; i++) {  // main:26-70: hand-rolled scan, no validation
         std::string arg = argv[i];
         const char* nx = i + 1 < argc ? argv[i + 1] : "";
@@ -132,6 +134,8 @@ int main(int argc, char* argv[]) {
         if (arg == "-opq") opq = true, opq_outer = atoi(nx);  // learn: -opq T outer steps; elsewhere a bare flag
         if (arg == "-opq_init_iters") opq_init_iters = atoi(nx);
         if (arg == "-opq_inner_iters") opq_inner_iters = atoi(nx);
+        if (arg == "-ivf") ivf_path = nx;
+        if (arg == "-nprobe") nprobe = atoi(nx);
     }
     (void)diff_argument; (void)method; (void)queryset;
     if (opq && (task == "refine" || (task == "recall" && refine_r != 0))) {
@@ -610,7 +614,7 @@ int main(int argc, char* argv[]) {
         // against base.{ext} (main.cpp:898-939) and reports the recall of that answer too.
         if (PQ_M <= 0 || PQ_K <= 0 || dataset.empty() || N < 1 || !topk_given || top_k < 1 || query_size < 1) {
             std::cout << "usage: deltapq -dataset DIR -task recall -m M -k K -N N -query_size Q -topk K [-gt_topk G] [-rerank R]"
-                         " [-store f16|bf16|sq8|sq4] [-ext fvecs|bvecs] [-filter FILE] [-opq] [-refine R [-m2 M2] [-k2 K2]] [-metric l2|ip]   (-refine: the"
+                         " [-store f16|bf16|sq8|sq4] [-ext fvecs|bvecs] [-filter FILE] [-opq] [-refine R [-m2 M2] [-k2 K2]] [-metric l2|ip] [-ivf CENTROIDS.fvecs -nprobe P]   (-refine: the"
                          " level of -task refine, M <= 8; -metric ip: dpq_query_batch_ip against the .ip.txt truth, not with -refine;"
                          " -store: the re-rank once more from the base narrowed to fp16 / bf16, or scalar-quantised to 8 / 4 bits)" << std::endl;
             return 2;
@@ -632,6 +636,14 @@ int main(int argc, char* argv[]) {
         }
         if (refine_r != 0 && (refine_r < top_k || refine_r > 2048 || filtered || PQ_M > 8)) {
             std::cout << "-refine " << refine_r << " outside " << top_k << "..2048, or combined with -filter, or M > 8" << std::endl;
+            return 1;
+        }
+        // -ivf CENTROIDS.fvecs -nprobe P: inverted lists built from the centroids file over the opened index
+        // (dpq_ivf_build); the recall of dpq_ivf_search is printed beside the exhaustive line
+        const bool with_ivf = !ivf_path.empty();
+        if (with_ivf && (refine_r != 0 || filtered || gpus > 1 || ip || opq || nprobe < 1 || nprobe > 1024 || top_k > 2048)) {
+            std::cout << "-ivf FILE -nprobe P (1..1024, -topk up to 2048) cannot be combined with -refine, -filter, -metric ip, -opq "
+                         "(the centroids would have to be in the rotated space) or -gpus above 1" << std::endl;
             return 1;
         }
         const bool bvecs = ext == "bvecs";
@@ -662,6 +674,21 @@ int main(int argc, char* argv[]) {
         if (D != PQ_M * cDs) {
             std::cout << "query dimension " << D << " != M*Ds = " << PQ_M * cDs << std::endl;
             return 1;
+        }
+        std::vector<float> ivf_centroids;
+        int64_t nlist = 0;
+        if (with_ivf) {
+            int32_t Dc = 0;
+            rc = dpq_read_vecs(ivf_path.c_str(), 0, &nlist, &Dc, nullptr, 0);
+            if (rc) return die("read -ivf centroids", rc);
+            if (Dc != D || nlist < 1 || nlist > 65536 || nprobe > nlist) {
+                std::cout << ivf_path << " holds " << nlist << " x " << Dc << ": needs 1..65536 centroids of dimension " << D
+                          << " and -nprobe " << nprobe << " at most their number" << std::endl;
+                return 1;
+            }
+            ivf_centroids.resize((size_t)nlist * Dc);
+            rc = dpq_read_vecs(ivf_path.c_str(), 0, &nlist, &Dc, ivf_centroids.data(), nlist);
+            if (rc) return die("read -ivf centroids", rc);
         }
         // -opq: the PQ query sees rotated queries; ground truth and the exact re-rank keep the raw ones
         std::vector<float> pq_queries_store;
@@ -759,6 +786,25 @@ int main(int argc, char* argv[]) {
             std::cout << "refined query " << (Elapsed() - t1) / (double)nq * 1000 << " [msec/query] " << std::endl;
             dpq_refine_free(lvl);
         }
+        std::vector<int32_t> ivf_pos;
+        if (with_ivf) {
+            dpq_ivf* ivf = nullptr;
+            const double t1 = Elapsed();
+            rc = dpq_ivf_build(idx, ivf_centroids.data(), (int)nlist, &ivf);
+            if (rc) return die("dpq_ivf_build", rc);
+            dpq_ivf_stats st;
+            rc = dpq_ivf_get_info(ivf, &st);
+            if (rc) return die("dpq_ivf_get_info", rc);
+            std::cout << "ivf: " << st.nlist << " lists over " << st.n_assigned << " codes, longest " << st.max_list_len << ", "
+                      << st.device_bytes << " bytes, built in " << (Elapsed() - t1) * 1000 << " [msec]" << std::endl;
+            ivf_pos.resize((size_t)nq * top_k);
+            std::vector<float> ivf_d((size_t)nq * top_k);
+            const double t2 = Elapsed();
+            rc = dpq_ivf_search(ivf, pq_queries.data(), nq, nprobe, top_k, ivf_pos.data(), ivf_d.data());
+            if (rc) return die("dpq_ivf_search", rc);
+            std::cout << "ivf query " << (Elapsed() - t2) / (double)nq * 1000 << " [msec/query] " << std::endl;
+            dpq_ivf_free(ivf);
+        }
         dpq_close(idx);
         for (size_t i = 0; i < found.size(); ++i) {
             int64_t p = pos[i];
@@ -771,6 +817,19 @@ int main(int argc, char* argv[]) {
         char line[128];
         snprintf(line, sizeof line, filtered ? "filtered recall@%d = %.6f" : "recall@%d = %.6f", top_k, rec);
         std::cout << line << std::endl;
+        if (with_ivf) {
+            std::vector<int32_t> ivf_found(ivf_pos.size());
+            for (size_t i = 0; i < ivf_found.size(); ++i) {
+                int64_t p = ivf_pos[i];
+                if (p == N && N % 2 == 0) p = N - 1;
+                ivf_found[i] = p < 0 || p >= N ? -1 : (int32_t)vec_id[(size_t)p];
+            }
+            double ivf_rec = 0;
+            rc = dpq_recall(ivf_found.data(), top_k, top_k, truth.data(), g_k, top_k, nq, &ivf_rec);
+            if (rc) return die("dpq_recall", rc);
+            snprintf(line, sizeof line, "ivf recall@%d = %.6f (nlist %d, nprobe %d)", top_k, ivf_rec, (int)nlist, nprobe);
+            std::cout << line << std::endl;
+        }
         if (refine_r) {
             std::vector<int32_t> ref_found(ref_pos.size());
             for (size_t i = 0; i < ref_found.size(); ++i) {

@@ -49,6 +49,9 @@
  *   (none: FAISS's IndexPQ distance computer    dpq_candidate_search[_device][_tables] / dpq_candidate_distances[_device]
  *     over ids; search with a per-query           (PQ distances and top-k over each query's own id list)
  *     IDSelectorArray)
+ *   (none: FAISS's IndexIVFPQ with              dpq_ivf_create[_device] / dpq_ivf_build / dpq_ivf_set_centroids,
+ *     by_residual = false: inverted lists,        dpq_ivf_probe / dpq_ivf_search[_device] / dpq_ivf_search_probes[_device]
+ *     nprobe)                                     (lists over the index's nodes, probed per query)
  *   (none: FAISS's IndexFlatIP: search, an      dpq_flat_search_ip / dpq_flat_search_filtered_ip /
  *     IDSelector, range_search; re-ranking by     dpq_flat_range_search_ip / dpq_flat_rerank_ip[_device],
  *     inner product)                              dpq_merge_topk_ip_host
@@ -1330,6 +1333,74 @@ int dpq_candidate_search_device_tables(dpq_index* idx, const float* d_tables, in
 int dpq_candidate_distances(dpq_index* idx, const float* queries, int nq, const int32_t* cand_ids, int n_cand, float* dists);
 int dpq_candidate_distances_device(dpq_index* idx, const float* d_queries, int nq, const int32_t* d_cand_ids, int n_cand,
                                    float* d_dists, void* hip_stream);
+
+/* ---- IVF search: inverted lists over the index, probed per query -----------------
+ * FAISS's IndexIVFPQ with by_residual = false.  NO REFERENCE COUNTERPART.  A dpq_ivf holds nlist lists over the nodes of
+ * ONE dpq_index; a query scans only the lists it probes, so it touches a fraction of the handle.  The answer is a
+ * shortlist like any other: dpq_refine_rerank*, dpq_flat_rerank* and dpq_candidate_search* re-rank it unchanged.
+ *   Ownership  The structure is bound to the handle it was made on, is freed (dpq_ivf_free) BEFORE dpq_close of that
+ *           handle, and is used from the handle's thread.  Handles of M = 8 and M = 16, DTC and dpq_open_plain_*.
+ *   Memory  Device memory of its own: offsets[nlist + 1] int64; ids[n_assigned] int32, the REPORTED ids of the listed
+ *           nodes -- global DFS positions (shards, parts with global_offset, num_codes prefixes), the even-N rule applied
+ *           -- ascending inside a list; codes[n_assigned][M], the same nodes' plain code values in list order; and,
+ *           where set, centroids[nlist][M * Ds].  M + 4 bytes per listed node beside the compressed image.
+ *   Labels  dpq_ivf_create[_device]: labels[l] is the list of LOCAL node l (position node_lo + l), n must be node_hi -
+ *           node_lo, a negative label puts the node in no list, empty lists are legal, 1 <= nlist <= 65536.  A label >=
+ *           nlist is DPQ_ERR_ARG: the host form checks before any device work, the device form raises one flag word read
+ *           back at the end (dpq_get_codes_device's convention).  The lists are made on the device: a count per list, an
+ *           exclusive scan, a stable sort of (label, position), a gather of the codes from the bulk decode in tiles of at
+ *           most 4 Mi nodes.
+ *   Centroids  dpq_ivf_build: centroids[nlist][M * Ds] in host memory; a codebook must be set (else DPQ_ERR_STATE); M *
+ *           Ds > 2048 is DPQ_ERR_ARG.  The label of a node is the centroid nearest to its RECONSTRUCTION (dpq_reconstruct's
+ *           row) under the exact search's arithmetic: per dimension the fp32 difference and its fp32 square, each rounded,
+ *           summed in fp64 in dimension order and rounded to fp32; the lowest list wins a tie.  Non-finite rows are
+ *           unspecified.  The centroids are kept.  dpq_ivf_set_centroids attaches centroids[nlist][M * Ds] to a structure
+ *           made from labels -- for callers who assign by their ORIGINAL vectors (through vec_id), as FAISS does.
+ *   Probes  dpq_ivf_search_probes[_device]: probes[nq][nprobe] are list numbers of the caller's choice; a negative entry
+ *           is padding; a list named twice by one query counts once; an entry >= nlist is DPQ_ERR_ARG (host form: checked
+ *           on the host; device form: a flag word, the outputs then unspecified, the next call works).  dpq_ivf_probe:
+ *           the nprobe nearest centroids of each query, ordered by (exact L2 distance, list number) under the arithmetic
+ *           above; empty lists are probed like any other; dists_out may be NULL.  dpq_ivf_search[_device] is dpq_ivf_probe
+ *           followed by dpq_ivf_search_probes.  Without centroids dpq_ivf_probe and dpq_ivf_search* are DPQ_ERR_STATE.
+ *   Answer  For query q: the unfiltered search applied to the union of the probed lists.  Distances are to the bit what
+ *           dpq_query_batch reports for the same id on the same handle ("candidate search" above: the fp64 sum rounded
+ *           once on a DTC handle, fp32 accumulation on a plain one).  Results ascend by key `distance bits << 32 | id`,
+ *           the lowest ids win at the k-th boundary, a real id at +inf comes before padding, rows are padded with -1 /
+ *           +inf.  On shards every rank takes the same centroids or probes and its own labels; the partial answers merge
+ *           with dpq_merge_topk_* unchanged.
+ *   Limits  1 <= top_k <= 2048, 1 <= nprobe <= min(nlist, 1024), else DPQ_ERR_ARG; nq == 0 is DPQ_OK.  Argument errors
+ *           that need no device come before any device call.
+ *   State   Calls are synchronous (the device forms enqueue on `hip_stream`, NULL = default stream, and return with the
+ *           results complete) and finish pending asynchronous batches first.  They work in a workspace owned by the
+ *           dpq_ivf -- per slice of at most 2048 queries their tables and the partial answers [nprobe][queries][top_k],
+ *           at most 256 MB -- and never write a search lane's workspace, tables included.
+ * tests/_ivf_restatement.py restates the rules in numpy; the GPU meets them bit for bit. */
+typedef struct dpq_ivf dpq_ivf;
+typedef struct dpq_ivf_stats {
+    int64_t n_assigned;    /* nodes in a list */
+    int64_t n_unassigned;  /* nodes with a negative label */
+    int64_t max_list_len;
+    int64_t device_bytes;  /* offsets, ids, codes and centroids (the workspace of the searches is not counted) */
+    int32_t nlist;
+    int32_t has_centroids;
+} dpq_ivf_stats;
+int dpq_ivf_create(dpq_index* idx, const int32_t* labels, int64_t n, int nlist, dpq_ivf** out);
+int dpq_ivf_create_device(dpq_index* idx, const int32_t* d_labels, int64_t n, int nlist, void* hip_stream, dpq_ivf** out);
+int dpq_ivf_build(dpq_index* idx, const float* centroids, int nlist, dpq_ivf** out);
+int dpq_ivf_set_centroids(dpq_ivf* ivf, const float* centroids, int nlist);
+void dpq_ivf_free(dpq_ivf* ivf); /* NULL: nothing happens */
+int dpq_ivf_get_info(const dpq_ivf* ivf, dpq_ivf_stats* out);
+/* offsets_out[nlist + 1], ids_out[n_assigned] (may be NULL: the offsets only). */
+int dpq_ivf_get(const dpq_ivf* ivf, int64_t* offsets_out, int32_t* ids_out);
+int dpq_ivf_search_probes(dpq_ivf* ivf, const float* queries, int nq, const int32_t* probes, int nprobe, int top_k,
+                          int32_t* ids, float* dists);
+int dpq_ivf_search_probes_device(dpq_ivf* ivf, const float* d_queries, int nq, const int32_t* d_probes, int nprobe, int top_k,
+                                 int32_t* d_ids, float* d_dists, void* hip_stream);
+/* lists_out[nq][nprobe], dists_out[nq][nprobe]. */
+int dpq_ivf_probe(dpq_ivf* ivf, const float* queries, int nq, int nprobe, int32_t* lists_out, float* dists_out);
+int dpq_ivf_search(dpq_ivf* ivf, const float* queries, int nq, int nprobe, int top_k, int32_t* ids, float* dists);
+int dpq_ivf_search_device(dpq_ivf* ivf, const float* d_queries, int nq, int nprobe, int top_k, int32_t* d_ids, float* d_dists,
+                          void* hip_stream);
 
 /* ---- measurement -------------------------------------------------------- */
 int dpq_profile_enable(dpq_index* idx, int on);  /* 0 off, 1 every kernel, 2 scan launches only (less event overhead) */
