@@ -6,6 +6,7 @@ the restatement of tests/_ivf_restatement.py, and against query_batch on the sam
 of 256, the threshold refresh of the scan's buffer, the merge rounds, padding, the flag words, ids on shards, parts, even-N
 and prefix handles, the build from centroids, the state a call leaves behind, the CLI.  CPU: the symbols, the hand case,
 the probe rule, the argument checks.  Nothing is skipped and no case is exempt.
+Every open option: tests/test_matrix_ivf.py; slices, merge rounds, long probe rows, the sort width: tests/test_ivf_edges.py.
 """
 import ctypes
 import os
