@@ -89,6 +89,15 @@ class IvfStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class IvfTrainOpts(ctypes.Structure):
+    _fields_ = [("device", c_i32), ("max_iters", c_i32), ("seed", ctypes.c_uint64), ("use_initial", c_i32),
+                ("reserved", c_i32 * 3)]
+
+
+class IvfTrainStats(ctypes.Structure):
+    _fields_ = TrainStats._fields_
+
+
 # every symbol include/deltapq_amd.h declares: (name, restype, argtypes)
 _VP = ctypes.c_void_p
 SYMBOLS = [
@@ -284,6 +293,10 @@ SYMBOLS = [
     ("dpq_ivf_probe", ctypes.c_int, [_VP, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP]),
     ("dpq_ivf_search", ctypes.c_int, [_VP, _VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, _VP, _VP]),
     ("dpq_ivf_search_device", ctypes.c_int, [_VP, _VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP]),
+    ("dpq_ivf_train", ctypes.c_int, [_VP, c_i64, ctypes.c_int, ctypes.c_int, P(IvfTrainOpts), _VP, P(IvfTrainStats)]),
+    ("dpq_ivf_assign", ctypes.c_int, [_VP, ctypes.c_int, ctypes.c_int, _VP, c_i64, ctypes.c_int, _VP, _VP]),
+    ("dpq_ivf_assign_device", ctypes.c_int, [_VP, ctypes.c_int, ctypes.c_int, _VP, c_i64, _VP, _VP, _VP]),
+    ("dpq_write_vecs", ctypes.c_int, [ctypes.c_char_p, _VP, c_i64, ctypes.c_int]),
     ("dpq_profile_enable", ctypes.c_int, [_VP, ctypes.c_int]),
     ("dpq_profile_reset", ctypes.c_int, [_VP]),
     ("dpq_profile_read", ctypes.c_int, [_VP, P(Profile)]),

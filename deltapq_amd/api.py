@@ -1171,6 +1171,68 @@ class IdFilter:
         self.close()
 
 
+def train_ivf_centroids(vectors, nlist, max_iters=25, seed=0, init=None, device=0):
+    """The coarse quantiser of an IVF, learned on the GPU (dpq_ivf_train, include/deltapq_amd.h "IVF training"): Lloyd's
+    rounds over whole vectors under the exact search's arithmetic.  init: a start [nlist][D] instead of the seeded rows.
+    Returns (centroids float32 [nlist][D], stats dict)."""
+    lib = _lib.load()
+    v = np.ascontiguousarray(vectors, dtype=np.float32)
+    assert v.ndim == 2
+    n, D = v.shape
+    opts = _lib.IvfTrainOpts(device=device, max_iters=max_iters, seed=seed, use_initial=int(init is not None))
+    if init is None:
+        c = np.zeros((max(int(nlist), 1), D), dtype=np.float32)
+    else:
+        c = np.array(init, dtype=np.float32, order="C")
+        assert c.shape == (nlist, D), "init must be [nlist][D]"
+    st = _lib.IvfTrainStats()
+    check(lib.dpq_ivf_train(_np_ptr(v), n, D, int(nlist), opts, _np_ptr(c), st), "dpq_ivf_train")
+    stats = {k: getattr(st, k) for k, _ in st._fields_ if k != "distortion"}
+    stats["distortion"] = [st.distortion[i] for i in range(st.iters_run)]
+    return c, stats
+
+
+def ivf_assign(centroids, vectors, device=0):
+    """The nearest centroid of every vector, the lowest list at a tie (dpq_ivf_assign): (labels int32 [n], dists float32
+    [n]), host arrays."""
+    c = np.ascontiguousarray(centroids, dtype=np.float32)
+    v = np.ascontiguousarray(vectors, dtype=np.float32)
+    assert c.ndim == 2 and v.ndim == 2 and c.shape[1] == v.shape[1], "centroids [nlist][D], vectors [n][D]"
+    labels = np.empty(v.shape[0], dtype=np.int32)
+    dists = np.empty(v.shape[0], dtype=np.float32)
+    check(_lib.load().dpq_ivf_assign(_np_ptr(c), c.shape[0], c.shape[1], _np_ptr(v), v.shape[0], device, _np_ptr(labels),
+                                     _np_ptr(dists)), "dpq_ivf_assign")
+    return labels, dists
+
+
+def ivf_assign_torch(centroids, vectors, out_labels=None, out_dists=None):
+    """ivf_assign on device tensors (dpq_ivf_assign_device): enqueued on torch's current stream, no allocation by the
+    library, no host round trip.  D must be a multiple of 4."""
+    import torch
+    for t in (centroids, vectors):
+        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 2
+    n, D = vectors.shape
+    assert centroids.shape[1] == D and centroids.device == vectors.device
+    if out_labels is None:
+        out_labels = torch.empty(n, dtype=torch.int32, device=vectors.device)
+    if out_dists is None:
+        out_dists = torch.empty(n, dtype=torch.float32, device=vectors.device)
+    with torch.cuda.device(vectors.device):
+        stream = torch.cuda.current_stream(vectors.device).cuda_stream
+        check(_lib.load().dpq_ivf_assign_device(ctypes.c_void_p(centroids.data_ptr()), centroids.shape[0], D,
+                                                ctypes.c_void_p(vectors.data_ptr()), n, ctypes.c_void_p(out_labels.data_ptr()),
+                                                ctypes.c_void_p(out_dists.data_ptr()), ctypes.c_void_p(stream)),
+              "dpq_ivf_assign_device")
+    return out_labels, out_dists
+
+
+def write_vecs(path, vectors):
+    """float32 [n][D] as an .fvecs file (dpq_write_vecs): read_vecs gives the same bits."""
+    v = np.ascontiguousarray(vectors, dtype=np.float32)
+    assert v.ndim == 2
+    check(_lib.load().dpq_write_vecs(path.encode(), _np_ptr(v), v.shape[0], v.shape[1]), "dpq_write_vecs")
+
+
 class IVF:
     """Inverted lists over the nodes of one DeltaPQIndex (dpq_ivf, include/deltapq_amd.h "IVF search"): a query scans only
     the lists it probes.  Keeps its index alive; close it (or leave its `with` block) before the index is closed."""
@@ -1208,6 +1270,16 @@ class IVF:
         if centroids is not None:
             ivf.set_centroids(centroids)
         return ivf
+
+    @classmethod
+    def train(cls, index, vectors, vec_id, nlist, **opts):
+        """End to end, as FAISS trains and fills an IndexIVF: train_ivf_centroids on the original `vectors` (**opts:
+        max_iters, seed, init, device), ivf_assign of the same vectors, local node l into the list of its vector
+        vec_id[l] (what set_vec_ids takes), the centroids kept for probe() and search()."""
+        centroids, _ = train_ivf_centroids(vectors, nlist, **opts)
+        vec_labels, _ = ivf_assign(centroids, vectors, device=opts.get("device", 0))
+        labels = vec_labels[np.asarray(vec_id, dtype=np.int64)]
+        return cls.from_labels(index, labels, nlist, centroids=centroids)
 
     def set_centroids(self, centroids):
         """Attaches centroids float32 [nlist][M * Ds] to lists made from labels (dpq_ivf_set_centroids)."""

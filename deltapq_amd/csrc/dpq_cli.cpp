@@ -99,7 +99,7 @@ int main(int argc, char* argv[]) {
     bool opq = false;
     int opq_outer = 0, opq_init_iters = 25, opq_inner_iters = 4;
     std::string ivf_path;
-    int nprobe = 1;
+    int nprobe = 1, learn_nlist = 0, iters = 25;
     for (int i = 0; i < argc; i++) {  // main:26-70: hand-rolled scan, no validation
         std::string arg = argv[i];
         const char* nx = i + 1 < argc ? argv[i + 1] : "";
@@ -136,6 +136,8 @@ int main(int argc, char* argv[]) {
         if (arg == "-opq_inner_iters") opq_inner_iters = atoi(nx);
         if (arg == "-ivf") ivf_path = nx;
         if (arg == "-nprobe") nprobe = atoi(nx);
+        if (arg == "-nlist") learn_nlist = atoi(nx);
+        if (arg == "-iters") iters = atoi(nx);
     }
     (void)diff_argument; (void)method; (void)queryset;
     if (opq && (task == "refine" || (task == "recall" && refine_r != 0))) {
@@ -232,6 +234,41 @@ int main(int argc, char* argv[]) {
         std::cout << "learned M = " << PQ_M << " K = " << PQ_K << " Ds = " << Ds << " from " << n << " vectors in " << st.iters_run
                   << " rounds" << (st.converged ? " (converged)" : "") << ", " << st.reseeded << " empty clusters reseeded, "
                   << st.wall_ms / 1000 << " [sec] -> " << cw_path << std::endl;
+        return 0;
+    }
+    if (task == "ivf_learn") {
+        // No reference counterpart: learn.fvecs -> IVF{L}centroids.fvecs, the coarse quantiser `-task recall -ivf FILE` takes
+        // (dpq_ivf_train: Lloyd's rounds over whole vectors, the seeded-rows start).  -N takes the first T vectors.
+        if (learn_nlist <= 0 || dataset.empty()) {
+            std::cout << "usage: deltapq -dataset DIR -task ivf_learn -nlist L [-N TRAIN_SIZE] [-iters I] [-seed S]" << std::endl;
+            return 2;
+        }
+        const std::string learn_path = dataset + "/learn.fvecs";
+        int64_t n_file = 0;
+        int32_t D = 0;
+        int rc = dpq_read_vecs(learn_path.c_str(), 0, &n_file, &D, nullptr, 0);
+        if (rc) return die("ReadTopN", rc);
+        int64_t n = n_file;
+        if (N != -1 && N < n) n = N;
+        std::vector<float> learn((size_t)n * D);
+        rc = dpq_read_vecs(learn_path.c_str(), 0, &n_file, &D, learn.data(), n);
+        if (rc) return die("ReadTopN", rc);
+        std::vector<float> centroids((size_t)learn_nlist * D);
+        dpq_ivf_train_opts io = {};
+        io.max_iters = iters;
+        io.seed = seed;
+        dpq_ivf_train_stats st;
+        rc = dpq_ivf_train(learn.data(), n, D, learn_nlist, &io, centroids.data(), &st);
+        if (rc) return die("ivf_learn", rc);
+        for (int r = 0; r < st.iters_run; ++r) std::cout << "round " << r + 1 << " distortion " << st.distortion[r] << std::endl;
+        const std::string out = dataset + "/IVF" + std::to_string(learn_nlist) + "centroids.fvecs";
+        rc = dpq_write_vecs(out.c_str(), centroids.data(), learn_nlist, D);
+        if (rc) return die("dpq_write_vecs", rc);
+        std::cout << "assign " << st.assign_ms << " [ms] update " << st.update_ms << " [ms] repair " << st.repair_ms
+                  << " [ms] rounds " << st.rounds_ms << " [ms]" << std::endl;
+        std::cout << "learned nlist = " << learn_nlist << " D = " << D << " from " << n << " vectors in " << st.iters_run << " rounds"
+                  << (st.converged ? " (converged)" : "") << ", " << st.reseeded << " empty lists reseeded, " << st.wall_ms / 1000
+                  << " [sec] -> " << out << std::endl;
         return 0;
     }
     if (task == "encode") {
@@ -927,7 +964,7 @@ int main(int argc, char* argv[]) {
         task = "query";
     }
     if (task != "query" && task != "query_im" && !pqscan) {
-        std::cout << "deltapq (MI355X build): -task query, query_im, pqscan, approx_tree, encode, learn, decompress, groundtruth and recall are implemented (batch_query = "
+        std::cout << "deltapq (MI355X build): -task query, query_im, pqscan, approx_tree, encode, learn, ivf_learn, decompress, groundtruth and recall are implemented (batch_query = "
                      "alias of query); got '" << task
                   << "'" << std::endl;
         return 2;

@@ -52,6 +52,8 @@
  *   (none: FAISS's IndexIVFPQ with              dpq_ivf_create[_device] / dpq_ivf_build / dpq_ivf_set_centroids,
  *     by_residual = false: inverted lists,        dpq_ivf_probe / dpq_ivf_search[_device] / dpq_ivf_search_probes[_device]
  *     nprobe)                                     (lists over the index's nodes, probed per query)
+ *   (none: FAISS's IndexIVF::train,             dpq_ivf_train / dpq_ivf_assign[_device], dpq_write_vecs
+ *     quantizer->assign)                          (the coarse quantiser's centroids, learned and applied on the GPU)
  *   (none: FAISS's IndexFlatIP: search, an      dpq_flat_search_ip / dpq_flat_search_filtered_ip /
  *     IDSelector, range_search; re-ranking by     dpq_flat_range_search_ip / dpq_flat_rerank_ip[_device],
  *     inner product)                              dpq_merge_topk_ip_host
@@ -1401,6 +1403,69 @@ int dpq_ivf_probe(dpq_ivf* ivf, const float* queries, int nq, int nprobe, int32_
 int dpq_ivf_search(dpq_ivf* ivf, const float* queries, int nq, int nprobe, int top_k, int32_t* ids, float* dists);
 int dpq_ivf_search_device(dpq_ivf* ivf, const float* d_queries, int nq, int nprobe, int top_k, int32_t* d_ids, float* d_dists,
                           void* hip_stream);
+
+/* ---- IVF training: the coarse quantiser's centroids, learned and applied on the GPU ---
+ * FAISS's IndexIVF::train and quantizer->assign.  NO REFERENCE COUNTERPART.  One codebook over the WHOLE vector, nlist up
+ * to 65536: what dpq_ivf_build and dpq_ivf_set_centroids take, and what dpq_train_codebook (a codebook per sub-space,
+ * K <= 256) cannot give.  With vectors v[n][D] and centroids c[nlist][D], both fp32:
+ *   Distance  the exact search's arithmetic, which dpq_ivf_build and dpq_ivf_probe use, so a trained set is consistent
+ *           with the labels and probes an IVF makes from it: an fp64 acc starts at +0.0; for d ascending t = c[d] - v[d]
+ *           in fp32, s = t * t in fp32, each rounded on its own, acc += (double)s; the distance is (float)acc.  This is
+ *           NOT dpq_train_codebook's fp32 accumulation.
+ *   Assign  the label of a vector is the list with the smallest key `distance bits << 32 | list`: the lowest list wins a
+ *           tie.  The winning distance is the distance to that list.  +inf is an ordinary value: if every distance is
+ *           +inf the label is 0.  NaN inputs are unspecified.
+ *   Start   use_initial != 0: the caller's centroids.  Otherwise dpq_train_codebook's "rows" start with K = nlist (the
+ *           splitmix64 partial shuffle of "codebook learning" above): centroid i is vector p[i].
+ *   Stop    right after an assignment (not the first) that changes no label and leaves no list empty: the centroids
+ *           already are the means of those labels.  Otherwise after max_iters rounds.
+ *   Update  list with members: per dimension the fp64 sum, starting from +0.0, of the members' fp32 values in ascending
+ *           vector index, one add after the other, divided in fp64 by (double)count, rounded once to fp32.
+ *   Empty   with E empty lists after an assignment, the vectors are ranked by (winning distance descending, vector index
+ *           ascending); the j-th empty list in ascending order takes the j-th ranked vector.  The donor stays in its old
+ *           list's mean of this round.
+ *   Distortion  per round the fp64 sum of the winning fp32 distances; the order of that sum is not part of the contract,
+ *           but the same input gives the same bits run to run.
+ * The same input gives the same centroid bytes, run to run.  tests/_ivf_train_restatement.py restates the rules in
+ * numpy; the GPU meets them bit for bit.  opts == NULL: device 0, 25 rounds, seed 0.
+ *   Limits  DPQ_ERR_ARG, before any device call: a NULL pointer (stats and dists_out may be NULL), D outside 1..2048,
+ *           nlist outside 1..65536, n outside 1..2^31 - 1 (dpq_ivf_assign*: n == 0 is DPQ_OK), and for dpq_ivf_train
+ *           nlist > n, max_iters outside 1..64, a non-zero reserved word.  Without a GPU: DPQ_ERR_NO_DEVICE.
+ *   Memory  dpq_ivf_train holds on the device 4 * n * Dp bytes of rows (Dp = D rounded up to 4), 24 * n bytes of labels,
+ *           winning distances and sort arrays, 4 * nlist * Dp of centroids and the sorts' scratch; dpq_ivf_assign works in
+ *           tiles of at most 256 MB of rows.  A failed allocation is DPQ_ERR_NOMEM; everything is freed before the call
+ *           returns.  dpq_ivf_assign_device allocates nothing. */
+typedef struct dpq_ivf_train_opts {
+    int32_t device;
+    int32_t max_iters;   /* 1..64 */
+    uint64_t seed;       /* of the seeded start */
+    int32_t use_initial; /* != 0: `centroids` holds the start on entry */
+    int32_t reserved[3]; /* 0 */
+} dpq_ivf_train_opts;
+
+typedef struct dpq_ivf_train_stats {
+    int32_t iters_run;     /* rounds run = entries of distortion[] */
+    int32_t converged;     /* 1: stopped by the rule */
+    int64_t reseeded;      /* empty lists repaired, all rounds */
+    double distortion[64]; /* per round */
+    double gpu_ms;         /* assign_ms + update_ms + repair_ms (device events) */
+    double wall_ms;        /* the whole call, upload included */
+    double rounds_ms;      /* host clock around the rounds; minus gpu_ms = the host round trips */
+    double assign_ms, update_ms, repair_ms; /* assign: the arg-min; update: lists, distortion and means */
+} dpq_ivf_train_stats;
+
+/* vectors [n][D] host; centroids [nlist][D] host, in (use_initial) and out.  stats may be NULL. */
+int dpq_ivf_train(const float* vectors, int64_t n, int D, int nlist, const dpq_ivf_train_opts* opts, float* centroids,
+                  dpq_ivf_train_stats* stats);
+/* Assign alone: labels_out [n] int32, dists_out [n] float (may be NULL); host buffers. */
+int dpq_ivf_assign(const float* centroids, int nlist, int D, const float* vectors, int64_t n, int device, int32_t* labels_out,
+                   float* dists_out);
+/* Device pointers on the current device, enqueue only: no allocation, no synchronisation (dpq_rotate_device's
+ * convention); d_dists may be NULL.  Needs D % 4 == 0 and 16-byte aligned rows, else DPQ_ERR_ARG. */
+int dpq_ivf_assign_device(const float* d_centroids, int nlist, int D, const float* d_vectors, int64_t n, int32_t* d_labels,
+                          float* d_dists, void* hip_stream);
+/* Host only: n rows of (int32 D, D floats), the .fvecs layout dpq_read_vecs reads. */
+int dpq_write_vecs(const char* path, const float* vectors, int64_t n, int D);
 
 /* ---- measurement -------------------------------------------------------- */
 int dpq_profile_enable(dpq_index* idx, int on);  /* 0 off, 1 every kernel, 2 scan launches only (less event overhead) */
