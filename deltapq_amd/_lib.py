@@ -293,6 +293,25 @@ SYMBOLS = [
     ("dpq_ivf_probe", ctypes.c_int, [_VP, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP]),
     ("dpq_ivf_search", ctypes.c_int, [_VP, _VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, _VP, _VP]),
     ("dpq_ivf_search_device", ctypes.c_int, [_VP, _VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP]),
+    ("dpq_ivf_search_filtered", ctypes.c_int, [_VP, _VP, _VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, _VP, _VP]),
+    ("dpq_ivf_search_device_filtered", ctypes.c_int, [_VP, _VP, _VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP]),
+    ("dpq_ivf_search_probes_filtered", ctypes.c_int,
+     [_VP, _VP, _VP, ctypes.c_int, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP]),
+    ("dpq_ivf_search_probes_device_filtered", ctypes.c_int,
+     [_VP, _VP, _VP, ctypes.c_int, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP]),
+    ("dpq_ivf_search_probes_tables", ctypes.c_int, [_VP, _VP, _VP, ctypes.c_int, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP]),
+    ("dpq_ivf_search_probes_device_tables", ctypes.c_int,
+     [_VP, _VP, _VP, ctypes.c_int, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP]),
+    ("dpq_ivf_probe_ip", ctypes.c_int, [_VP, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP]),
+    ("dpq_ivf_search_ip", ctypes.c_int, [_VP, _VP, _VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP, _VP]),
+    ("dpq_ivf_search_device_ip", ctypes.c_int,
+     [_VP, _VP, _VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP, _VP, _VP]),
+    ("dpq_ivf_search_probes_ip", ctypes.c_int,
+     [_VP, _VP, _VP, ctypes.c_int, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP, _VP]),
+    ("dpq_ivf_search_probes_device_ip", ctypes.c_int,
+     [_VP, _VP, _VP, ctypes.c_int, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP, _VP, _VP]),
+    ("dpq_ivf_range_search", ctypes.c_int, [_VP, _VP, _VP, ctypes.c_int, ctypes.c_int, _VP, P(_VP)]),
+    ("dpq_ivf_range_search_probes", ctypes.c_int, [_VP, _VP, _VP, ctypes.c_int, _VP, ctypes.c_int, _VP, P(_VP)]),
     ("dpq_ivf_train", ctypes.c_int, [_VP, c_i64, ctypes.c_int, ctypes.c_int, P(IvfTrainOpts), _VP, P(IvfTrainStats)]),
     ("dpq_ivf_assign", ctypes.c_int, [_VP, ctypes.c_int, ctypes.c_int, _VP, c_i64, ctypes.c_int, _VP, _VP]),
     ("dpq_ivf_assign_device", ctypes.c_int, [_VP, ctypes.c_int, ctypes.c_int, _VP, c_i64, _VP, _VP, _VP]),

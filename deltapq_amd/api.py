@@ -1316,33 +1316,123 @@ class IVF:
         check(self._lib.dpq_ivf_probe(self._h, _np_ptr(q), q.shape[0], nprobe, _np_ptr(lists), _np_ptr(dists)), "dpq_ivf_probe")
         return lists, dists
 
-    def search(self, queries, nprobe, top_k):
-        """The top_k nearest codes of the nprobe lists nearest to each query (dpq_ivf_search).  Returns (ids int32
-        [nq][k], dists float32 [nq][k]), the distances query_batch reports for those ids, padded with -1 / +inf."""
-        q = self._queries(queries)
-        ids = np.empty((q.shape[0], top_k), dtype=np.int32)
-        dists = np.empty((q.shape[0], top_k), dtype=np.float32)
-        check(self._lib.dpq_ivf_search(self._h, _np_ptr(q), q.shape[0], nprobe, top_k, _np_ptr(ids), _np_ptr(dists)),
-              "dpq_ivf_search")
-        return ids, dists
-
-    def search_probes(self, queries, probes, top_k):
-        """search over the caller's own lists: probes int32 [nq][nprobe], -1 = padding (dpq_ivf_search_probes)."""
-        q = self._queries(queries)
+    @staticmethod
+    def _probes(probes, nq):
         p = np.ascontiguousarray(probes, dtype=np.int32)
         if p.ndim == 1:
             p = p[None, :]
-        assert p.ndim == 2 and p.shape[0] == q.shape[0], "probes must be [nq][nprobe]"
+        assert p.ndim == 2 and p.shape[0] == nq, "probes must be [nq][nprobe]"
+        return p
+
+    @staticmethod
+    def _filter(id_filter):
+        return IdFilter._handle(id_filter) if id_filter is not None else None
+
+    def search(self, queries, nprobe, top_k, id_filter=None):
+        """The top_k nearest codes of the nprobe lists nearest to each query (dpq_ivf_search).  Returns (ids int32
+        [nq][k], dists float32 [nq][k]), the distances query_batch reports for those ids, padded with -1 / +inf.
+        `id_filter` (an IdFilter made on this IVF's index): only the codes it allows (dpq_ivf_search_filtered)."""
+        q = self._queries(queries)
         ids = np.empty((q.shape[0], top_k), dtype=np.int32)
         dists = np.empty((q.shape[0], top_k), dtype=np.float32)
-        check(self._lib.dpq_ivf_search_probes(self._h, _np_ptr(q), q.shape[0], _np_ptr(p), p.shape[1], top_k, _np_ptr(ids),
-                                              _np_ptr(dists)), "dpq_ivf_search_probes")
+        if id_filter is None:
+            check(self._lib.dpq_ivf_search(self._h, _np_ptr(q), q.shape[0], nprobe, top_k, _np_ptr(ids), _np_ptr(dists)),
+                  "dpq_ivf_search")
+        else:
+            check(self._lib.dpq_ivf_search_filtered(self._h, IdFilter._handle(id_filter), _np_ptr(q), q.shape[0], nprobe, top_k,
+                                                    _np_ptr(ids), _np_ptr(dists)), "dpq_ivf_search_filtered")
         return ids, dists
+
+    def search_probes(self, queries, probes, top_k, id_filter=None):
+        """search over the caller's own lists: probes int32 [nq][nprobe], -1 = padding (dpq_ivf_search_probes; with
+        `id_filter`, dpq_ivf_search_probes_filtered)."""
+        q = self._queries(queries)
+        p = self._probes(probes, q.shape[0])
+        ids = np.empty((q.shape[0], top_k), dtype=np.int32)
+        dists = np.empty((q.shape[0], top_k), dtype=np.float32)
+        if id_filter is None:
+            check(self._lib.dpq_ivf_search_probes(self._h, _np_ptr(q), q.shape[0], _np_ptr(p), p.shape[1], top_k, _np_ptr(ids),
+                                                  _np_ptr(dists)), "dpq_ivf_search_probes")
+        else:
+            check(self._lib.dpq_ivf_search_probes_filtered(self._h, IdFilter._handle(id_filter), _np_ptr(q), q.shape[0],
+                                                           _np_ptr(p), p.shape[1], top_k, _np_ptr(ids), _np_ptr(dists)),
+                  "dpq_ivf_search_probes_filtered")
+        return ids, dists
+
+    def search_probes_tables(self, tables, probes, top_k, id_filter=None):
+        """search_probes with the caller's distance tables [nq][M][K] standing where the L2 tables of the queries stand
+        (dpq_ivf_search_probes_tables); needs no codebook.  Entries: finite >= 0 or +inf."""
+        t = self._index._tables(tables)
+        p = self._probes(probes, t.shape[0])
+        ids = np.empty((t.shape[0], top_k), dtype=np.int32)
+        dists = np.empty((t.shape[0], top_k), dtype=np.float32)
+        check(self._lib.dpq_ivf_search_probes_tables(self._h, self._filter(id_filter), _np_ptr(t), t.shape[0], _np_ptr(p),
+                                                     p.shape[1], top_k, _np_ptr(ids), _np_ptr(dists)),
+              "dpq_ivf_search_probes_tables")
+        return ids, dists
+
+    def probe_ip(self, queries, nprobe):
+        """(lists int32 [nq][nprobe], scores float32 [nq][nprobe]): each query's nprobe centroids of largest exact inner
+        product, by (score descending, list number) (dpq_ivf_probe_ip)."""
+        q = self._queries(queries)
+        lists = np.empty((q.shape[0], nprobe), dtype=np.int32)
+        scores = np.empty((q.shape[0], nprobe), dtype=np.float32)
+        check(self._lib.dpq_ivf_probe_ip(self._h, _np_ptr(q), q.shape[0], nprobe, _np_ptr(lists), _np_ptr(scores)),
+              "dpq_ivf_probe_ip")
+        return lists, scores
+
+    def _ip_out(self, nq, top_k):
+        return (np.empty((nq, top_k), dtype=np.int32), np.empty((nq, top_k), dtype=np.float32),
+                np.empty((nq, top_k), dtype=np.float32), np.empty(nq, dtype=np.float32))
+
+    def search_ip(self, queries, nprobe, top_k, id_filter=None):
+        """The top_k codes of the largest approximate inner product among the nprobe lists whose centroids have the
+        largest exact inner product with each query (dpq_ivf_search_ip).  Returns (ids, scores descending, gaps, bias) as
+        query_batch_ip does; padding is -1 / -inf / +inf."""
+        q = self._queries(queries)
+        ids, scores, gaps, bias = self._ip_out(q.shape[0], top_k)
+        check(self._lib.dpq_ivf_search_ip(self._h, self._filter(id_filter), _np_ptr(q), q.shape[0], nprobe, top_k, _np_ptr(ids),
+                                          _np_ptr(scores), _np_ptr(gaps), _np_ptr(bias)), "dpq_ivf_search_ip")
+        return ids, scores, gaps, bias
+
+    def search_probes_ip(self, queries, probes, top_k, id_filter=None):
+        """search_ip over the caller's own lists (dpq_ivf_search_probes_ip)."""
+        q = self._queries(queries)
+        p = self._probes(probes, q.shape[0])
+        ids, scores, gaps, bias = self._ip_out(q.shape[0], top_k)
+        check(self._lib.dpq_ivf_search_probes_ip(self._h, self._filter(id_filter), _np_ptr(q), q.shape[0], _np_ptr(p), p.shape[1],
+                                                 top_k, _np_ptr(ids), _np_ptr(scores), _np_ptr(gaps), _np_ptr(bias)),
+              "dpq_ivf_search_probes_ip")
+        return ids, scores, gaps, bias
+
+    def _radii(self, radius, nq):
+        return np.ascontiguousarray(np.broadcast_to(np.asarray(radius, dtype=np.float32), (nq,)))
+
+    def range_search(self, queries, nprobe, radius, id_filter=None):
+        """Every code of the nprobe nearest lists within `radius` of each query, d < radius strictly
+        (dpq_ivf_range_search).  `radius`: a scalar or one value per query.  Returns what DeltaPQIndex.range_search
+        returns: (lims int64 [nq + 1], ids int32, dists float32), each list ascending by (distance, id)."""
+        q = self._queries(queries)
+        r = self._radii(radius, q.shape[0])
+        res = ctypes.c_void_p()
+        check(self._lib.dpq_ivf_range_search(self._h, self._filter(id_filter), _np_ptr(q), q.shape[0], nprobe, _np_ptr(r), res),
+              "dpq_ivf_range_search")
+        return _range_result(self._lib, res)
+
+    def range_search_probes(self, queries, probes, radius, id_filter=None):
+        """range_search over the caller's own lists (dpq_ivf_range_search_probes)."""
+        q = self._queries(queries)
+        p = self._probes(probes, q.shape[0])
+        r = self._radii(radius, q.shape[0])
+        res = ctypes.c_void_p()
+        check(self._lib.dpq_ivf_range_search_probes(self._h, self._filter(id_filter), _np_ptr(q), q.shape[0], _np_ptr(p),
+                                                    p.shape[1], _np_ptr(r), res), "dpq_ivf_range_search_probes")
+        return _range_result(self._lib, res)
 
     @staticmethod
     def _torch_out(queries, top_k, out_ids, out_dists):
         import torch
-        assert queries.is_cuda and queries.dtype == torch.float32 and queries.is_contiguous() and queries.dim() == 2
+        assert queries.is_cuda and queries.dtype == torch.float32 and queries.is_contiguous() and queries.dim() in (2, 3)
         nq = queries.shape[0]
         if out_ids is None:
             out_ids = torch.empty((nq, top_k), dtype=torch.int32, device=queries.device)
@@ -1350,25 +1440,82 @@ class IVF:
             out_dists = torch.empty((nq, top_k), dtype=torch.float32, device=queries.device)
         return nq, out_ids, out_dists, ctypes.c_void_p(torch.cuda.current_stream(queries.device).cuda_stream)
 
-    def search_torch(self, queries, nprobe, top_k, out_ids=None, out_dists=None):
-        """search on device tensors, synchronous on torch's current stream (dpq_ivf_search_device)."""
-        nq, out_ids, out_dists, stream = self._torch_out(queries, top_k, out_ids, out_dists)
-        check(self._lib.dpq_ivf_search_device(self._h, ctypes.c_void_p(queries.data_ptr()), nq, nprobe, top_k,
-                                              ctypes.c_void_p(out_ids.data_ptr()), ctypes.c_void_p(out_dists.data_ptr()), stream),
-              "dpq_ivf_search_device")
-        return out_ids, out_dists
-
-    def search_probes_torch(self, queries, probes, top_k, out_ids=None, out_dists=None):
-        """search_probes on device tensors, synchronous on torch's current stream (dpq_ivf_search_probes_device)."""
+    @staticmethod
+    def _torch_probes(probes, nq):
         import torch
-        nq, out_ids, out_dists, stream = self._torch_out(queries, top_k, out_ids, out_dists)
         assert probes.is_cuda and probes.dtype == torch.int32 and probes.is_contiguous() and probes.dim() == 2
         assert probes.shape[0] == nq
-        check(self._lib.dpq_ivf_search_probes_device(self._h, ctypes.c_void_p(queries.data_ptr()), nq,
-                                                     ctypes.c_void_p(probes.data_ptr()), probes.shape[1], top_k,
-                                                     ctypes.c_void_p(out_ids.data_ptr()), ctypes.c_void_p(out_dists.data_ptr()),
-                                                     stream), "dpq_ivf_search_probes_device")
+        return ctypes.c_void_p(probes.data_ptr()), probes.shape[1]
+
+    def search_torch(self, queries, nprobe, top_k, out_ids=None, out_dists=None, id_filter=None):
+        """search on device tensors, synchronous on torch's current stream (dpq_ivf_search_device[_filtered])."""
+        nq, out_ids, out_dists, stream = self._torch_out(queries, top_k, out_ids, out_dists)
+        assert queries.dim() == 2
+        if id_filter is None:
+            check(self._lib.dpq_ivf_search_device(self._h, ctypes.c_void_p(queries.data_ptr()), nq, nprobe, top_k,
+                                                  ctypes.c_void_p(out_ids.data_ptr()), ctypes.c_void_p(out_dists.data_ptr()), stream),
+                  "dpq_ivf_search_device")
+        else:
+            check(self._lib.dpq_ivf_search_device_filtered(self._h, IdFilter._handle(id_filter), ctypes.c_void_p(queries.data_ptr()),
+                                                           nq, nprobe, top_k, ctypes.c_void_p(out_ids.data_ptr()),
+                                                           ctypes.c_void_p(out_dists.data_ptr()), stream),
+                  "dpq_ivf_search_device_filtered")
         return out_ids, out_dists
+
+    def search_probes_torch(self, queries, probes, top_k, out_ids=None, out_dists=None, id_filter=None):
+        """search_probes on device tensors, synchronous on torch's current stream
+        (dpq_ivf_search_probes_device[_filtered])."""
+        nq, out_ids, out_dists, stream = self._torch_out(queries, top_k, out_ids, out_dists)
+        assert queries.dim() == 2
+        pp, nprobe = self._torch_probes(probes, nq)
+        if id_filter is None:
+            check(self._lib.dpq_ivf_search_probes_device(self._h, ctypes.c_void_p(queries.data_ptr()), nq, pp, nprobe, top_k,
+                                                         ctypes.c_void_p(out_ids.data_ptr()), ctypes.c_void_p(out_dists.data_ptr()),
+                                                         stream), "dpq_ivf_search_probes_device")
+        else:
+            check(self._lib.dpq_ivf_search_probes_device_filtered(self._h, IdFilter._handle(id_filter),
+                                                                  ctypes.c_void_p(queries.data_ptr()), nq, pp, nprobe, top_k,
+                                                                  ctypes.c_void_p(out_ids.data_ptr()),
+                                                                  ctypes.c_void_p(out_dists.data_ptr()), stream),
+                  "dpq_ivf_search_probes_device_filtered")
+        return out_ids, out_dists
+
+    def search_probes_tables_torch(self, tables, probes, top_k, id_filter=None, out_ids=None, out_dists=None):
+        """search_probes_tables on device tensors ([nq][M][K] float32, contiguous), synchronous on torch's current
+        stream (dpq_ivf_search_probes_device_tables)."""
+        nq, out_ids, out_dists, stream = self._torch_out(tables, top_k, out_ids, out_dists)
+        assert tables.dim() == 3
+        pp, nprobe = self._torch_probes(probes, nq)
+        check(self._lib.dpq_ivf_search_probes_device_tables(self._h, self._filter(id_filter), ctypes.c_void_p(tables.data_ptr()),
+                                                            nq, pp, nprobe, top_k, ctypes.c_void_p(out_ids.data_ptr()),
+                                                            ctypes.c_void_p(out_dists.data_ptr()), stream),
+              "dpq_ivf_search_probes_device_tables")
+        return out_ids, out_dists
+
+    def search_ip_torch(self, queries, nprobe, top_k, id_filter=None, out_ids=None, out_scores=None, out_gaps=None,
+                        out_bias=None):
+        """search_ip on device tensors, synchronous on torch's current stream (dpq_ivf_search_device_ip).  Returns
+        (ids, scores); gaps and bias are written where out_gaps / out_bias are given."""
+        nq, out_ids, out_scores, stream = self._torch_out(queries, top_k, out_ids, out_scores)
+        assert queries.dim() == 2
+        opt = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        check(self._lib.dpq_ivf_search_device_ip(self._h, self._filter(id_filter), ctypes.c_void_p(queries.data_ptr()), nq, nprobe,
+                                                 top_k, ctypes.c_void_p(out_ids.data_ptr()), ctypes.c_void_p(out_scores.data_ptr()),
+                                                 opt(out_gaps), opt(out_bias), stream), "dpq_ivf_search_device_ip")
+        return out_ids, out_scores
+
+    def search_probes_ip_torch(self, queries, probes, top_k, id_filter=None, out_ids=None, out_scores=None, out_gaps=None,
+                               out_bias=None):
+        """search_probes_ip on device tensors, synchronous on torch's current stream (dpq_ivf_search_probes_device_ip)."""
+        nq, out_ids, out_scores, stream = self._torch_out(queries, top_k, out_ids, out_scores)
+        assert queries.dim() == 2
+        pp, nprobe = self._torch_probes(probes, nq)
+        opt = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        check(self._lib.dpq_ivf_search_probes_device_ip(self._h, self._filter(id_filter), ctypes.c_void_p(queries.data_ptr()), nq,
+                                                        pp, nprobe, top_k, ctypes.c_void_p(out_ids.data_ptr()),
+                                                        ctypes.c_void_p(out_scores.data_ptr()), opt(out_gaps), opt(out_bias),
+                                                        stream), "dpq_ivf_search_probes_device_ip")
+        return out_ids, out_scores
 
     def close(self):
         if self._h is not None:

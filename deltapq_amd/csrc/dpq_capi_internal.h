@@ -211,13 +211,22 @@ struct dpq_ivf {
     DevBuf<int32_t> probes;                // [slice queries][nprobe] the pre-pass's rows
     DevBuf<int32_t> part_ids, tmp_ids;     // [nprobe][slice queries][top_k] the lists' answers; [slice queries][top_k] a
     DevBuf<float> part_dists, tmp_dists;   // merge round's
-    DevBuf<uint32_t> flag;                 // [1] a probe names no list
+    DevBuf<uint32_t> flag;                 // [2] a probe names no list; a table entry is no distance
     DevBuf<uint64_t> keys;                 // coarse step: a batch's key buffers and states
     DevBuf<dpq::FlatQueryState> state;
     DevBuf<float> d_in, d_dists, d_cdists; // host forms: queries, distances; the coarse step's distances
     DevBuf<int32_t> d_probes, d_ids;       // ... probes, ids
     size_t lut_n = 0, min_n = 0, probes_n = 0, part_ids_n = 0, part_dists_n = 0, tmp_ids_n = 0, tmp_dists_n = 0,
            keys_n = 0, state_n = 0, in_n = 0, dists_n = 0, cdists_n = 0, dprobes_n = 0, ids_n = 0;
+    // inner product (dpq_ivf_search*_ip): a slice's tables [slice queries][M][K]; gaps and bias where the caller passes none
+    DevBuf<float> tab, d_gaps, d_bias;
+    size_t tab_n = 0, gaps_n = 0, bias_n = 0;
+    // range search (dpq_ivf_range_search*): the radius keys of the call; a slice's counts and their exclusive scan
+    // [slice queries][nprobe] + 1; a group's list starts [queries + 1]; the pool of a group's keys, unsorted and sorted
+    // (at most dpq::kIvfRangePoolKeys each: a longer single list works in buffers of the call)
+    DevBuf<uint64_t> r_thr, r_pool, r_sorted;
+    DevBuf<int64_t> r_counts, r_offs, r_qoffs;
+    size_t r_thr_n = 0, r_pool_n = 0, r_sorted_n = 0, r_counts_n = 0, r_offs_n = 0, r_qoffs_n = 0;
 };
 
 uint64_t next_index_serial();  // dpq_capi.cpp: one counter for the process

@@ -157,7 +157,7 @@ int main(int argc, char* argv[]) {
     const bool ip = metric == "ip";
     if ((!ip && !hamming && metric != "l2") || (ip && (refine_r != 0 || gpus > 1 || (task != "groundtruth" && task != "recall")))) {
         std::cout << "usage: -metric l2|ip|hamming (default l2); -metric hamming serves -task groundtruth -ext bvecs; -metric ip serves -task groundtruth and -task recall [-rerank R] "
-                     "[-filter FILE] [-opq], and cannot be combined with -refine R or -gpus above 1" << std::endl;
+                     "[-filter FILE] [-opq] [-ivf FILE -nprobe P], and cannot be combined with -refine R or -gpus above 1" << std::endl;
         return 2;
     }
 
@@ -653,6 +653,7 @@ int main(int argc, char* argv[]) {
             std::cout << "usage: deltapq -dataset DIR -task recall -m M -k K -N N -query_size Q -topk K [-gt_topk G] [-rerank R]"
                          " [-store f16|bf16|sq8|sq4] [-ext fvecs|bvecs] [-filter FILE] [-opq] [-refine R [-m2 M2] [-k2 K2]] [-metric l2|ip] [-ivf CENTROIDS.fvecs -nprobe P]   (-refine: the"
                          " level of -task refine, M <= 8; -metric ip: dpq_query_batch_ip against the .ip.txt truth, not with -refine;"
+                         " -ivf: the lists' recall beside the exhaustive line under the same -filter and -metric, not with -refine, -opq or -gpus above 1;"
                          " -store: the re-rank once more from the base narrowed to fp16 / bf16, or scalar-quantised to 8 / 4 bits)" << std::endl;
             return 2;
         }
@@ -676,10 +677,12 @@ int main(int argc, char* argv[]) {
             return 1;
         }
         // -ivf CENTROIDS.fvecs -nprobe P: inverted lists built from the centroids file over the opened index
-        // (dpq_ivf_build); the recall of dpq_ivf_search is printed beside the exhaustive line
+        // (dpq_ivf_build); the recall of dpq_ivf_search is printed beside the exhaustive line, against the same truth file.
+        // With -filter FILE the lists are searched under the same filter (dpq_ivf_search_filtered), with -metric ip by
+        // inner product, coarse step included (dpq_ivf_search_ip, which takes the filter too)
         const bool with_ivf = !ivf_path.empty();
-        if (with_ivf && (refine_r != 0 || filtered || gpus > 1 || ip || opq || nprobe < 1 || nprobe > 1024 || top_k > 2048)) {
-            std::cout << "-ivf FILE -nprobe P (1..1024, -topk up to 2048) cannot be combined with -refine, -filter, -metric ip, -opq "
+        if (with_ivf && (refine_r != 0 || gpus > 1 || opq || nprobe < 1 || nprobe > 1024 || top_k > 2048)) {
+            std::cout << "-ivf FILE -nprobe P (1..1024, -topk up to 2048) cannot be combined with -refine, -opq "
                          "(the centroids would have to be in the rotated space) or -gpus above 1" << std::endl;
             return 1;
         }
@@ -792,7 +795,6 @@ int main(int argc, char* argv[]) {
             if (rc) return die(ip ? "dpq_query_batch_ip" : filtered ? "dpq_query_batch_filtered" : "dpq_query_batch", rc);
         }
         std::cout << (Elapsed() - t0) / (double)nq * 1000 << " [msec/query] " << std::endl;
-        dpq_filter_free(filt);
         std::vector<int32_t> ref_pos;
         if (refine_r) {  // the level -task refine wrote: the PQ top-R refined to top_k on the device
             const int M2 = refine_m2 ? refine_m2 : PQ_M, K2 = refine_k2 ? refine_k2 : 256;
@@ -837,11 +839,15 @@ int main(int argc, char* argv[]) {
             ivf_pos.resize((size_t)nq * top_k);
             std::vector<float> ivf_d((size_t)nq * top_k);
             const double t2 = Elapsed();
-            rc = dpq_ivf_search(ivf, pq_queries.data(), nq, nprobe, top_k, ivf_pos.data(), ivf_d.data());
-            if (rc) return die("dpq_ivf_search", rc);
+            rc = ip         ? dpq_ivf_search_ip(ivf, filt, pq_queries.data(), nq, nprobe, top_k, ivf_pos.data(), ivf_d.data(), nullptr,
+                                                nullptr)  // filt may be NULL
+                 : filtered ? dpq_ivf_search_filtered(ivf, filt, pq_queries.data(), nq, nprobe, top_k, ivf_pos.data(), ivf_d.data())
+                            : dpq_ivf_search(ivf, pq_queries.data(), nq, nprobe, top_k, ivf_pos.data(), ivf_d.data());
+            if (rc) return die(ip ? "dpq_ivf_search_ip" : filtered ? "dpq_ivf_search_filtered" : "dpq_ivf_search", rc);
             std::cout << "ivf query " << (Elapsed() - t2) / (double)nq * 1000 << " [msec/query] " << std::endl;
             dpq_ivf_free(ivf);
         }
+        dpq_filter_free(filt);
         dpq_close(idx);
         for (size_t i = 0; i < found.size(); ++i) {
             int64_t p = pos[i];

@@ -62,4 +62,36 @@ hipError_t launch_ivf_scan(const float* d_lut32, int nq, const int32_t* d_probes
                            const int32_t* d_ids, const uint8_t* d_codes, int M, bool plain_rule, int top_k,
                            int32_t* d_part_ids, float* d_part_dists, hipStream_t stream);
 
+// ---- filters and range search over lists --------------------------------------------------------------
+constexpr int64_t kIvfRangePoolKeys = (int64_t)8 << 20;  // keys of a range slice: 64 MB unsorted beside 64 MB sorted
+
+// A dpq_filter as the list scans read it: bit l of `bits` is local node l of the handle (what dpq_filter::bits holds);
+// an entry's reported id goes back to its node by undoing the even-N renaming (`even`: id N is position N - 1) and
+// subtracting `base` (id_base).  bits == NULL: no filter (launch_ivf_range only).
+struct IvfFilter {
+    const uint32_t* bits = nullptr;
+    int64_t base = 0, n_local = 0, N = 0;
+    int32_t even = 0;
+};
+
+// launch_ivf_scan over the entries the filter allows: an entry it refuses forms no key (its bit is tested before its
+// code is loaded).  A list without an eligible entry gives a row of padding.
+hipError_t launch_ivf_scan_filtered(const float* d_lut32, int nq, const int32_t* d_probes, int nprobe, const int64_t* d_offsets,
+                                    const int32_t* d_ids, const uint8_t* d_codes, int M, bool plain_rule, const IvfFilter& filter,
+                                    int top_k, int32_t* d_part_ids, float* d_part_dists, hipStream_t stream);
+
+// The range scan, the same grid and table load.  d_thr[nq]: the radius keys -- distance bits << 32; 0 passes nothing
+// (r <= 0), ~0 passes every entry (r = +inf).  d_pool == NULL, the count pass: d_counts[q][p] = the eligible entries of
+// probe p's list with key < d_thr[q] (0 for padding, a repeat, an empty list).  Else the emit pass: those keys to
+// d_pool[d_offs[q][p] - pool_base ..), in list order (d_offs: the exclusive scan of the counts; pool_base: the offset of
+// the first query of this launch); nothing is written at or past pool_n.
+hipError_t launch_ivf_range(const float* d_lut32, int nq, const int32_t* d_probes, int nprobe, const int64_t* d_offsets,
+                            const int32_t* d_ids, const uint8_t* d_codes, int M, bool plain_rule, const IvfFilter& filter,
+                            const uint64_t* d_thr, int64_t* d_counts, const int64_t* d_offs, int64_t pool_base, uint64_t* d_pool,
+                            int64_t pool_n, hipStream_t stream);
+
+// hipCUB's two-call protocol (d_temp NULL: *temp_bytes only): d_offs[n] = the exclusive prefix sum of d_counts[n].
+hipError_t ivf_range_offsets(void* d_temp, size_t* temp_bytes, const int64_t* d_counts, int64_t* d_offs, int64_t n,
+                             hipStream_t stream);
+
 }  // namespace dpq

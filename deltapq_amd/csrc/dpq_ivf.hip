@@ -17,11 +17,16 @@
 //                          wavefront, one barrier per stride, no atomics.  When the buffer cannot take another stride a bitonic sort in LDS keeps the best
 //                          top_k and the threshold becomes the k-th key; ids are unique inside a list, so the strict
 //                          comparison loses nothing.  A last sort emits the list's top_k.
+//   ivf_scan_filtered_kernel  the same scan over the entries a dpq_filter allows: the entry's bit is
+//                          tested before its code is loaded.
+//   ivf_range_kernel       the same grid and table load for a radius: a count pass, then an emit pass that writes every
+//                          passing key at its rank inside the region the count reserved.
 #include "dpq_ivf.h"
 
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "dpq_flat.h"
 
@@ -210,6 +215,172 @@ __global__ __launch_bounds__(256) void ivf_scan_kernel(const float* __restrict__
     }
 }
 
+// ---- the list scans of DESIGN.md 5.18: a filter, a radius ----------------------------------------------------------------
+
+// The key of list entry `at` under the table in LDS: ivf_scan_kernel's arithmetic, to the bit.
+template <int M, bool PLAIN_RULE>
+__device__ __forceinline__ uint64_t ivf_entry_key(const float* T, const uint8_t* __restrict__ codes, int64_t at, int32_t id) {
+    uint32_t w[M / 4];
+    if constexpr (M == 8) {
+        const uint2 v = reinterpret_cast<const uint2*>(codes)[at];
+        w[0] = v.x; w[1] = v.y;
+    } else {
+        const uint4 v = reinterpret_cast<const uint4*>(codes)[at];
+        w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+    }
+    [[maybe_unused]] double acc64 = 0.0;
+    [[maybe_unused]] float acc32 = 0.0f;
+#pragma unroll
+    for (int m = 0; m < M; ++m) {
+        const float e = T[m * 256 + ((w[m >> 2] >> (8 * (m & 3))) & 0xffu)];
+        if constexpr (PLAIN_RULE)
+            acc32 = __fadd_rn(acc32, e);
+        else
+            acc64 = __dadd_rn(acc64, (double)e);
+    }
+    const float d = PLAIN_RULE ? acc32 : (float)acc64;
+    return ((uint64_t)__float_as_uint(d) << 32) | (uint32_t)id;
+}
+
+// Whether the filter lets the entry of reported id `id` pass: the id back to its local node (the even-N renaming undone,
+// id_base subtracted), then that node's bit.  A list holds ids of the handle's own nodes only; the range test keeps a
+// foreign id from reading past the bitmap all the same.
+__device__ __forceinline__ bool ivf_eligible(const IvfFilter& f, int32_t id) {
+    const int64_t pos = (f.even && (int64_t)id == f.N) ? f.N - 1 : (int64_t)id;
+    const int64_t l = pos - f.base;
+    if (l < 0 || l >= f.n_local) return false;
+    return (f.bits[l >> 5] >> (l & 31)) & 1u;
+}
+
+// ivf_scan_kernel with an eligibility test per entry, made before the code load and the M gathers: an entry the filter
+// refuses forms no key.  Everything else -- the register count, the parity words, the uniform branches -- is the scan's.
+template <int M, bool PLAIN_RULE>
+__global__ __launch_bounds__(256) void ivf_scan_filtered_kernel(const float* __restrict__ lut32,
+                                                                const int32_t* __restrict__ probes, int nprobe,
+                                                                const int64_t* __restrict__ offsets,
+                                                                const int32_t* __restrict__ ids,
+                                                                const uint8_t* __restrict__ codes, const IvfFilter filt,
+                                                                int top_k, int cap, int32_t* __restrict__ part_ids,
+                                                                float* __restrict__ part_dists) {
+    __shared__ __attribute__((aligned(16))) float T[M * 256];
+    __shared__ uint32_t s_wcnt[2][4];
+    extern __shared__ __attribute__((aligned(16))) unsigned char ivf_smem[];
+    uint64_t* buf = reinterpret_cast<uint64_t*>(ivf_smem);  // [cap = 2 P]
+    const int p = blockIdx.x, q = blockIdx.y, nq = gridDim.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int32_t* out_i = part_ids + ((size_t)p * nq + q) * top_k;
+    float* out_d = part_dists + ((size_t)p * nq + q) * top_k;
+    const int32_t list = probes[(size_t)q * nprobe + p];
+    int64_t lo = 0, hi = 0;
+    if (list >= 0) {
+        lo = offsets[list];
+        hi = offsets[list + 1];
+    }
+    if (hi <= lo) {  // padding, a repeat or an empty list (uniform over the workgroup)
+        for (int r = tid; r < top_k; r += 256) {
+            out_i[r] = -1;
+            out_d[r] = INFINITY;
+        }
+        return;
+    }
+    const float4* src = reinterpret_cast<const float4*>(lut32 + (size_t)q * M * 256);
+#pragma unroll
+    for (int i = 0; i < M / 4; ++i) reinterpret_cast<float4*>(T)[i * 256 + tid] = src[i * 256 + tid];
+    __syncthreads();
+    uint32_t cnt = 0u;  // uniform over the workgroup, as in ivf_scan_kernel
+    int par = 0;
+    uint64_t thr = kFlatNoKey;
+    for (int64_t base = lo; base < hi; base += 256, par ^= 1) {
+        const int64_t at = base + tid;
+        uint64_t key = kFlatNoKey;
+        if (at < hi) {
+            const int32_t id = ids[at];
+            if (ivf_eligible(filt, id)) key = ivf_entry_key<M, PLAIN_RULE>(T, codes, at, id);
+        }
+        const bool pass = key < thr;
+        const unsigned long long mask = __ballot(pass);
+        if (lane == 0) s_wcnt[par][wave] = (uint32_t)__popcll(mask);
+        __syncthreads();
+        const uint32_t c0 = s_wcnt[par][0], c1 = s_wcnt[par][1], c2 = s_wcnt[par][2], c3 = s_wcnt[par][3];
+        const uint32_t wbase = cnt + (wave > 0 ? c0 : 0u) + (wave > 1 ? c1 : 0u) + (wave > 2 ? c2 : 0u);
+        if (pass) buf[wbase + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull))] = key;  // < cap: the stride had room
+        cnt += c0 + c1 + c2 + c3;
+        if (cnt + 256u > (uint32_t)cap && base + 256 < hi) {
+            ivf_sort_keys(buf, cnt, tid);
+            if (cnt >= (uint32_t)top_k) thr = buf[top_k - 1];
+            cnt = min(cnt, (uint32_t)top_k);
+        }
+    }
+    ivf_sort_keys(buf, cnt, tid);
+    for (int r = tid; r < top_k; r += 256) {
+        const uint64_t key = (uint32_t)r < cnt ? buf[r] : kFlatNoKey;
+        out_i[r] = key != kFlatNoKey ? (int32_t)(key & 0xffffffffu) : -1;
+        out_d[r] = key != kFlatNoKey ? __uint_as_float((uint32_t)(key >> 32)) : INFINITY;
+    }
+}
+
+// The range scan, grid (probes, queries), 256 threads.  EMIT false: counts[q][p] = the eligible entries of the list whose
+// key lies below thr[q].  EMIT true: the same walk again, every such key to pool[offs[q][p] - pool_base + its rank]; the
+// rank of an entry is the number of passing entries before it in the list, from the ballot prefix of its wavefront, the
+// counts of the wavefronts before it in the stride, and the running count of the strides before (a register, uniform
+// over the workgroup, fed through the parity words exactly as the top-k scan's).  No atomics; both passes visit the same
+// entries in the same order, so the ranks fill the region the count reserved.  A write at or past pool_n is dropped.
+template <int M, bool PLAIN_RULE, bool EMIT>
+__global__ __launch_bounds__(256) void ivf_range_kernel(const float* __restrict__ lut32, const int32_t* __restrict__ probes,
+                                                        int nprobe, const int64_t* __restrict__ offsets,
+                                                        const int32_t* __restrict__ ids, const uint8_t* __restrict__ codes,
+                                                        const IvfFilter filt, const uint64_t* __restrict__ thr_key,
+                                                        int64_t* __restrict__ counts, const int64_t* __restrict__ offs,
+                                                        int64_t pool_base, uint64_t* __restrict__ pool, int64_t pool_n) {
+    __shared__ __attribute__((aligned(16))) float T[M * 256];
+    __shared__ uint32_t s_wcnt[2][4];
+    const int p = blockIdx.x, q = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const size_t slot = (size_t)q * nprobe + p;
+    const int32_t list = probes[slot];
+    const uint64_t thr = thr_key[q];
+    int64_t lo = 0, hi = 0;
+    if (list >= 0 && thr != 0ull) {
+        lo = offsets[list];
+        hi = offsets[list + 1];
+    }
+    if (hi <= lo) {  // padding, a repeat, an empty list or a radius <= 0 (uniform over the workgroup)
+        if (!EMIT && tid == 0) counts[slot] = 0;
+        return;
+    }
+    const float4* src = reinterpret_cast<const float4*>(lut32 + (size_t)q * M * 256);
+#pragma unroll
+    for (int i = 0; i < M / 4; ++i) reinterpret_cast<float4*>(T)[i * 256 + tid] = src[i * 256 + tid];
+    __syncthreads();
+    [[maybe_unused]] const int64_t out0 = EMIT ? offs[slot] - pool_base : 0;
+    uint32_t cnt = 0u;  // EMIT: uniform over the workgroup; else the wavefront's own total
+    int par = 0;
+    for (int64_t base = lo; base < hi; base += 256, par ^= 1) {
+        const int64_t at = base + tid;
+        uint64_t key = kFlatNoKey;
+        if (at < hi) {
+            const int32_t id = ids[at];
+            if (!filt.bits || ivf_eligible(filt, id)) key = ivf_entry_key<M, PLAIN_RULE>(T, codes, at, id);
+        }
+        const bool pass = key < thr;  // (thr = kFlatNoKey, the radius +inf, passes every key and no padding)
+        const unsigned long long mask = __ballot(pass);
+        if constexpr (!EMIT) {
+            cnt += (uint32_t)__popcll(mask);
+        } else {
+            if (lane == 0) s_wcnt[par][wave] = (uint32_t)__popcll(mask);
+            __syncthreads();
+            const uint32_t c0 = s_wcnt[par][0], c1 = s_wcnt[par][1], c2 = s_wcnt[par][2], c3 = s_wcnt[par][3];
+            const uint32_t wbase = cnt + (wave > 0 ? c0 : 0u) + (wave > 1 ? c1 : 0u) + (wave > 2 ? c2 : 0u);
+            const int64_t to = out0 + wbase + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
+            if (pass && to >= 0 && to < pool_n) pool[to] = key;
+            cnt += c0 + c1 + c2 + c3;
+        }
+    }
+    if constexpr (!EMIT) {
+        if (lane == 0) s_wcnt[0][wave] = cnt;
+        __syncthreads();
+        if (tid == 0) counts[slot] = (int64_t)s_wcnt[0][0] + s_wcnt[0][1] + s_wcnt[0][2] + s_wcnt[0][3];
+    }
+}
+
 int pow2_at_least(int v) {
     int p = 1;
     while (p < v) p <<= 1;
@@ -320,6 +491,71 @@ hipError_t launch_ivf_scan(const float* d_lut32, int nq, const int32_t* d_probes
                                                                      top_k, cap, d_part_ids, d_part_dists);
     }
     return hipGetLastError();
+}
+
+namespace {
+bool ivf_filter_ok(const IvfFilter& f, bool required) {
+    if (!f.bits) return !required;
+    return f.n_local >= 0 && f.base >= 0 && f.N >= 0;
+}
+}  // namespace
+
+hipError_t launch_ivf_scan_filtered(const float* d_lut32, int nq, const int32_t* d_probes, int nprobe, const int64_t* d_offsets,
+                                    const int32_t* d_ids, const uint8_t* d_codes, int M, bool plain_rule, const IvfFilter& filter,
+                                    int top_k, int32_t* d_part_ids, float* d_part_dists, hipStream_t stream) {
+    if (nq <= 0) return hipSuccess;
+    if (!d_lut32 || !d_probes || !d_offsets || !d_ids || !d_codes || !d_part_ids || !d_part_dists || (M != 8 && M != 16) ||
+        nprobe < 1 || nprobe > kIvfMaxProbe || top_k < 1 || top_k > kIvfMaxTopK || nq > 65535 || !ivf_filter_ok(filter, true) ||
+        (reinterpret_cast<uintptr_t>(d_codes) & (uintptr_t)(M - 1)) || (reinterpret_cast<uintptr_t>(d_lut32) & 15u))
+        return hipErrorInvalidValue;
+    const int cap = 2 * pow2_at_least(std::max(top_k, 256));
+    const size_t lds = (size_t)cap * sizeof(uint64_t);
+    const dim3 grid((unsigned)nprobe, (unsigned)nq), block(256);
+    auto* kernel = M == 8 ? (plain_rule ? ivf_scan_filtered_kernel<8, true> : ivf_scan_filtered_kernel<8, false>)
+                          : (plain_rule ? ivf_scan_filtered_kernel<16, true> : ivf_scan_filtered_kernel<16, false>);
+    kernel<<<grid, block, lds, stream>>>(d_lut32, d_probes, nprobe, d_offsets, d_ids, d_codes, filter, top_k, cap, d_part_ids,
+                                         d_part_dists);
+    return hipGetLastError();
+}
+
+hipError_t launch_ivf_range(const float* d_lut32, int nq, const int32_t* d_probes, int nprobe, const int64_t* d_offsets,
+                            const int32_t* d_ids, const uint8_t* d_codes, int M, bool plain_rule, const IvfFilter& filter,
+                            const uint64_t* d_thr, int64_t* d_counts, const int64_t* d_offs, int64_t pool_base, uint64_t* d_pool,
+                            int64_t pool_n, hipStream_t stream) {
+    if (nq <= 0) return hipSuccess;
+    const bool emit = d_pool != nullptr;
+    if (!d_lut32 || !d_probes || !d_offsets || !d_ids || !d_codes || !d_thr || (M != 8 && M != 16) || nprobe < 1 ||
+        nprobe > kIvfMaxProbe || nq > 65535 || !ivf_filter_ok(filter, false) || (emit ? (!d_offs || pool_n < 0) : !d_counts) ||
+        (reinterpret_cast<uintptr_t>(d_codes) & (uintptr_t)(M - 1)) || (reinterpret_cast<uintptr_t>(d_lut32) & 15u))
+        return hipErrorInvalidValue;
+    const dim3 grid((unsigned)nprobe, (unsigned)nq), block(256);
+    auto pick = [&](auto m, auto plain) {
+        constexpr int MM = decltype(m)::value;
+        constexpr bool PL = decltype(plain)::value;
+        if (emit)
+            ivf_range_kernel<MM, PL, true><<<grid, block, 0, stream>>>(d_lut32, d_probes, nprobe, d_offsets, d_ids, d_codes, filter,
+                                                                       d_thr, d_counts, d_offs, pool_base, d_pool, pool_n);
+        else
+            ivf_range_kernel<MM, PL, false><<<grid, block, 0, stream>>>(d_lut32, d_probes, nprobe, d_offsets, d_ids, d_codes, filter,
+                                                                        d_thr, d_counts, d_offs, pool_base, d_pool, pool_n);
+    };
+    if (M == 8) {
+        if (plain_rule) pick(std::integral_constant<int, 8>{}, std::true_type{});
+        else pick(std::integral_constant<int, 8>{}, std::false_type{});
+    } else {
+        if (plain_rule) pick(std::integral_constant<int, 16>{}, std::true_type{});
+        else pick(std::integral_constant<int, 16>{}, std::false_type{});
+    }
+    return hipGetLastError();
+}
+
+hipError_t ivf_range_offsets(void* d_temp, size_t* temp_bytes, const int64_t* d_counts, int64_t* d_offs, int64_t n,
+                             hipStream_t stream) {
+    if (n < 1 || n > 0x7fffffff) return hipErrorInvalidValue;
+    size_t tb = d_temp ? *temp_bytes : 0;
+    const hipError_t e = hipcub::DeviceScan::ExclusiveSum(d_temp, tb, d_counts, d_offs, (int)n, stream);
+    if (!d_temp) *temp_bytes = tb;
+    return e;
 }
 
 }  // namespace dpq

@@ -1404,6 +1404,73 @@ int dpq_ivf_search(dpq_ivf* ivf, const float* queries, int nq, int nprobe, int t
 int dpq_ivf_search_device(dpq_ivf* ivf, const float* d_queries, int nq, int nprobe, int top_k, int32_t* d_ids, float* d_dists,
                           void* hip_stream);
 
+/* ---- IVF search: filters, caller tables, inner product and range search ----------
+ * FAISS's IDSelector, METRIC_INNER_PRODUCT and range_search on an IndexIVFPQ.  NO REFERENCE COUNTERPART.  For a query q
+ * let U(q) be the set of nodes in the lists it probes (probe handling is dpq_ivf_search_probes' rule: negative entries
+ * are padding, a list named twice counts once, an entry >= nlist is DPQ_ERR_ARG).  Every call below is an existing
+ * exhaustive call applied to U(q) instead of to the whole handle.
+ *   Filter  A node of U(q) is eligible iff dpq_query_batch_filtered would find it eligible under the same dpq_filter:
+ *           by REPORTED id r, r < n_bits and bit r set; the even-N rule applies (bit N governs the last node of an even-N
+ *           DTC index, bit N - 1 governs nothing); global ids on shards, parts and prefixes.  The answer is the IVF answer
+ *           over the eligible nodes: the same distance bits, order by key `distance bits << 32 | id`, padding -1 / +inf.
+ *           No eligible node gives an all-padding row and is no error.  One filter per call.  A NULL filter in the
+ *           _filtered forms, or a filter whose owner is not the IVF's handle, is DPQ_ERR_ARG before any device work; in
+ *           the tables, inner-product and range forms `filter` may be NULL.
+ *   Tables  tables[nq][M][K] stand where the L2 tables stand, under dpq_candidate_search_tables' entry rules: negative,
+ *           -inf or NaN is DPQ_ERR_ARG (host check in the host form, a flag word read back at the end in the device form,
+ *           the outputs then unspecified, the next call works); -0.0 is read as +0.0; columns K .. 255 are +inf.  The forms
+ *           work before dpq_set_codebook.  The distance is the candidate search's: the fp64 sum in ascending m rounded
+ *           once on a DTC handle, fp32 accumulation on a plain one.  There are no queries, hence no coarse step: these
+ *           forms take the caller's probes only.
+ *   Inner product  dpq_ip_tables, then the tables form, then dpq_ip_scores: ids, scores descending, optional gaps and
+ *           bias as dpq_query_batch_ip gives them (gaps / bias may be NULL); padding is -1, gap +inf, score -inf.
+ *           dpq_ivf_probe_ip: the nprobe centroids of largest EXACT inner product with each query under
+ *           dpq_flat_search_ip's arithmetic and order -- score descending, list number ascending -- and their scores
+ *           (scores_out may be NULL); what FAISS does with an inner-product quantiser.  dpq_ivf_search[_device]_ip is
+ *           dpq_ivf_probe_ip followed by dpq_ivf_search_probes[_device]_ip; a caller who wants the L2 coarse step calls
+ *           dpq_ivf_probe and passes its rows.
+ *   Range   radii[nq] follow dpq_range_search's rules to the letter: d < r strictly; r <= 0 gives an empty list; r = +inf
+ *           gives every eligible node of U(q), those at +inf included; a NaN radius is DPQ_ERR_ARG before any device
+ *           work.  The answer is a dpq_range_result (host-owned; dpq_range_result_get, dpq_range_result_free); each list
+ *           ascends by (distance bits, id).  Host forms only, as dpq_range_search is.  Two passes over the probed lists,
+ *           count then emit, per slice of at most 2048 queries; the keys of a group of queries are laid out, sorted and
+ *           brought down through a pool of at most 2 x 64 MB kept with the dpq_ivf; one query whose list alone exceeds
+ *           the pool works in buffers of the call, released before it returns.
+ *   Everything else -- the limits of top_k and nprobe, nq == 0, synchronous calls that finish pending asynchronous
+ *           batches, the workspace owned by the dpq_ivf, never writing a search lane's workspace, argument checks that
+ *           need no device first -- is as in "IVF search" above.  Partial answers of shards merge with dpq_merge_topk_*
+ *           (inner product: the _ip merges); range lists of shards merge on the host by (distance, id).
+ * tests/_ivf_modes_restatement.py restates the rules in numpy; the GPU meets them bit for bit. */
+int dpq_ivf_search_filtered(dpq_ivf* ivf, const dpq_filter* filter, const float* queries, int nq, int nprobe, int top_k,
+                            int32_t* ids, float* dists);
+int dpq_ivf_search_device_filtered(dpq_ivf* ivf, const dpq_filter* filter, const float* d_queries, int nq, int nprobe,
+                                   int top_k, int32_t* d_ids, float* d_dists, void* hip_stream);
+int dpq_ivf_search_probes_filtered(dpq_ivf* ivf, const dpq_filter* filter, const float* queries, int nq,
+                                   const int32_t* probes, int nprobe, int top_k, int32_t* ids, float* dists);
+int dpq_ivf_search_probes_device_filtered(dpq_ivf* ivf, const dpq_filter* filter, const float* d_queries, int nq,
+                                          const int32_t* d_probes, int nprobe, int top_k, int32_t* d_ids, float* d_dists,
+                                          void* hip_stream);
+int dpq_ivf_search_probes_tables(dpq_ivf* ivf, const dpq_filter* filter, const float* tables, int nq, const int32_t* probes,
+                                 int nprobe, int top_k, int32_t* ids, float* dists);
+int dpq_ivf_search_probes_device_tables(dpq_ivf* ivf, const dpq_filter* filter, const float* d_tables, int nq,
+                                        const int32_t* d_probes, int nprobe, int top_k, int32_t* d_ids, float* d_dists,
+                                        void* hip_stream);
+/* lists_out[nq][nprobe], scores_out[nq][nprobe] (may be NULL). */
+int dpq_ivf_probe_ip(dpq_ivf* ivf, const float* queries, int nq, int nprobe, int32_t* lists_out, float* scores_out);
+int dpq_ivf_search_ip(dpq_ivf* ivf, const dpq_filter* filter, const float* queries, int nq, int nprobe, int top_k,
+                      int32_t* ids, float* scores, float* gaps_out, float* bias_out);
+int dpq_ivf_search_device_ip(dpq_ivf* ivf, const dpq_filter* filter, const float* d_queries, int nq, int nprobe, int top_k,
+                             int32_t* d_ids, float* d_scores, float* d_gaps, float* d_bias, void* hip_stream);
+int dpq_ivf_search_probes_ip(dpq_ivf* ivf, const dpq_filter* filter, const float* queries, int nq, const int32_t* probes,
+                             int nprobe, int top_k, int32_t* ids, float* scores, float* gaps_out, float* bias_out);
+int dpq_ivf_search_probes_device_ip(dpq_ivf* ivf, const dpq_filter* filter, const float* d_queries, int nq,
+                                    const int32_t* d_probes, int nprobe, int top_k, int32_t* d_ids, float* d_scores,
+                                    float* d_gaps, float* d_bias, void* hip_stream);
+int dpq_ivf_range_search(dpq_ivf* ivf, const dpq_filter* filter, const float* queries, int nq, int nprobe,
+                         const float* radii, dpq_range_result** out);
+int dpq_ivf_range_search_probes(dpq_ivf* ivf, const dpq_filter* filter, const float* queries, int nq, const int32_t* probes,
+                                int nprobe, const float* radii, dpq_range_result** out);
+
 /* ---- IVF training: the coarse quantiser's centroids, learned and applied on the GPU ---
  * FAISS's IndexIVF::train and quantizer->assign.  NO REFERENCE COUNTERPART.  One codebook over the WHOLE vector, nlist up
  * to 65536: what dpq_ivf_build and dpq_ivf_set_centroids take, and what dpq_train_codebook (a codebook per sub-space,
