@@ -157,6 +157,8 @@ SYMBOLS = [
     ("dpq_query_batch_host_async", ctypes.c_int, [_VP, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP]),
     ("dpq_pin_host", ctypes.c_int, [_VP, c_i64]),
     ("dpq_unpin_host", ctypes.c_int, [_VP]),
+    ("dpq_alloc_host", ctypes.c_int, [P(_VP), c_i64]),
+    ("dpq_free_host", ctypes.c_int, [_VP]),
     ("dpq_range_search", ctypes.c_int, [_VP, _VP, ctypes.c_int, _VP, P(_VP)]),
     ("dpq_range_result_get", ctypes.c_int, [_VP, P(c_i32), P(_VP), P(_VP), P(_VP)]),
     ("dpq_range_result_free", None, [_VP]),

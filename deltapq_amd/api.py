@@ -4,6 +4,7 @@ library does the work.  Names of the two convenience functions at the bottom
 mirror the reference's entry points (deltapq_create_approx_tree.h:2805, 3731).
 """
 import ctypes
+import weakref
 
 import numpy as np
 
@@ -829,7 +830,7 @@ class DeltaPQIndex:
     def query_batch_host_async(self, queries, top_k, ids, dists):
         """dpq_query_batch_host_async: host arrays in and out, enqueued only -- up to four batches in flight, queries up and
         results down beside the kernels.  `queries` (float32 [nq][D], C-contiguous), `ids` (int32 [nq][k]) and `dists`
-        (float32 [nq][k]) belong to the library until finish(); pin them (pin_host) for the copies to overlap."""
+        (float32 [nq][k]) belong to the library until finish(); page-locked arrays (what pin_host returns, alloc_host) let the copies overlap."""
         assert queries.dtype == np.float32 and queries.flags.c_contiguous and ids.dtype == np.int32 and dists.dtype == np.float32
         assert ids.flags.c_contiguous and dists.flags.c_contiguous and ids.shape == dists.shape == (queries.shape[0], top_k)
         check(self._lib.dpq_query_batch_host_async(self._h, _np_ptr(queries), queries.shape[0], top_k, _np_ptr(ids), _np_ptr(dists)),
@@ -2330,14 +2331,51 @@ def read_bitmap(path):
     return words, n.value
 
 
-def pin_host(arr):
-    """Page-lock a numpy array's memory (hipHostRegister through the library): host-to-host batches then overlap their copies."""
-    check(_lib.load().dpq_pin_host(_np_ptr(arr), arr.nbytes), "dpq_pin_host")
+class _HostBlock:
+    """Page-locked memory of the library's (dpq_alloc_host), given back when the last array over it is gone."""
+
+    def __init__(self, nbytes):
+        lib = _lib.load()
+        p = ctypes.c_void_p()
+        check(lib.dpq_alloc_host(ctypes.byref(p), nbytes), "dpq_alloc_host")
+        self.__array_interface__ = {"shape": (nbytes,), "typestr": "|u1", "data": (p.value, False), "version": 3}
+        weakref.finalize(self, lib.dpq_free_host, p).atexit = False   # (at exit the runtime takes everything down itself)
+
+
+def _host_block_of(arr):
+    while arr is not None and not isinstance(arr, _HostBlock):
+        arr = getattr(arr, "base", None)
     return arr
 
 
+def alloc_host(shape, dtype):
+    """A numpy array in page-locked memory (hipHostMalloc through the library), contents undefined.  The memory lives as
+    long as an array over it does."""
+    dtype = np.dtype(dtype)
+    n = int(np.prod(shape, dtype=np.int64))
+    if n <= 0:
+        raise ValueError("alloc_host needs at least one element")
+    return np.asarray(_HostBlock(n * dtype.itemsize)).view(dtype).reshape(shape)
+
+
+def pin_host(arr):
+    """-> the array in page-locked memory: host-to-host batches then overlap their copies.  This is `arr` itself where
+    the runtime page-locks memory the process already has (hipHostRegister through the library); where it refuses, as
+    with a GPU passed through to a virtual machine, a page-locked copy (alloc_host).  Use what is returned."""
+    status = _lib.load().dpq_pin_host(_np_ptr(arr), arr.nbytes)
+    if status == 0:
+        return arr
+    if status != -5:   # DPQ_ERR_HIP: the runtime's refusal; anything else is the caller's mistake
+        check(status, "dpq_pin_host")
+    out = alloc_host(arr.shape, arr.dtype)
+    out[...] = arr
+    return out
+
+
 def unpin_host(arr):
-    check(_lib.load().dpq_unpin_host(_np_ptr(arr)), "dpq_unpin_host")
+    """Undo pin_host on the array it returned (a page-locked copy is released with its last reference instead)."""
+    if _host_block_of(arr) is None:
+        check(_lib.load().dpq_unpin_host(_np_ptr(arr)), "dpq_unpin_host")
 
 
 def merge_topk_host(ids, dists):

@@ -2035,11 +2035,17 @@ int dpq_query_batch_host_async(dpq_index* x, const float* queries, int nq, int t
 }
 
 // Page-locks / releases caller memory (hipHostRegister) so that dpq_query_batch_host_async's copies run beside the kernels;
-// for callers that do not link the HIP runtime themselves.
+// for callers that do not link the HIP runtime themselves.  Not every system registers memory a process already has
+// (a GPU passed through to a virtual machine may refuse): the refusal is this call's answer alone, so the error the
+// runtime keeps for the next launch check is taken off.  dpq_alloc_host is the page-locked memory that every system has.
 int dpq_pin_host(void* ptr, int64_t bytes) {
     return guarded([&]() -> int {
     if (!ptr || bytes <= 0) return fail(DPQ_ERR_ARG, "NULL pointer or no bytes");
-    DPQ_HIP(hipHostRegister(ptr, (size_t)bytes, hipHostRegisterDefault));
+    const hipError_t e = hipHostRegister(ptr, (size_t)bytes, hipHostRegisterDefault);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(DPQ_ERR_HIP, std::string("hipHostRegister: ") + hipGetErrorString(e));
+    }
     return DPQ_OK;
     });
 }
@@ -2047,7 +2053,36 @@ int dpq_pin_host(void* ptr, int64_t bytes) {
 int dpq_unpin_host(void* ptr) {
     return guarded([&]() -> int {
     if (!ptr) return fail(DPQ_ERR_ARG, "NULL pointer");
-    DPQ_HIP(hipHostUnregister(ptr));
+    const hipError_t e = hipHostUnregister(ptr);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(DPQ_ERR_HIP, std::string("hipHostUnregister: ") + hipGetErrorString(e));
+    }
+    return DPQ_OK;
+    });
+}
+
+// Page-locked host memory of the library's own (hipHostMalloc: mapped into the device's address space, usable from every
+// device), for the buffers of dpq_query_batch_host_async where dpq_pin_host is refused.
+int dpq_alloc_host(void** ptr, int64_t bytes) {
+    return guarded([&]() -> int {
+    if (!ptr) return fail(DPQ_ERR_ARG, "ptr is NULL");
+    *ptr = nullptr;
+    if (bytes <= 0) return fail(DPQ_ERR_ARG, "no bytes");
+    const hipError_t e = hipHostMalloc(ptr, (size_t)bytes, hipHostMallocPortable | hipHostMallocMapped);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        *ptr = nullptr;
+        return fail(e == hipErrorOutOfMemory ? DPQ_ERR_NOMEM : DPQ_ERR_HIP, std::string("hipHostMalloc: ") + hipGetErrorString(e));
+    }
+    return DPQ_OK;
+    });
+}
+
+int dpq_free_host(void* ptr) {
+    return guarded([&]() -> int {
+    if (!ptr) return DPQ_OK;
+    DPQ_HIP(hipHostFree(ptr));
     return DPQ_OK;
     });
 }

@@ -455,10 +455,16 @@ int dpq_finish(dpq_index* idx);
  * settles the earlier ones first); `queries`, `ids` and `dists` belong to the library until dpq_finish(idx) returns.  Page-locked
  * buffers (dpq_pin_host / dpq_unpin_host = hipHostRegister, for callers that do not link the HIP runtime) make it a
  * pipeline: the queries go up on a copy stream and the result lists are written by the select kernel straight into the
- * mapped buffers; pageable memory works through staging copies, without the overlap. */
+ * mapped buffers; pageable memory works through staging copies, without the overlap.
+ * Not every system page-locks memory the process already has (a GPU passed through to a virtual machine may refuse):
+ * dpq_pin_host then returns DPQ_ERR_HIP and changes nothing, the buffer stays usable as pageable memory, and later calls
+ * are not affected.  dpq_alloc_host / dpq_free_host (hipHostMalloc / hipHostFree) give page-locked, mapped memory on every
+ * system, usable from every device; dpq_free_host(NULL) is DPQ_OK. */
 int dpq_query_batch_host_async(dpq_index* idx, const float* queries, int nq, int top_k, int32_t* ids, float* dists);
 int dpq_pin_host(void* ptr, int64_t bytes);
 int dpq_unpin_host(void* ptr);
+int dpq_alloc_host(void** ptr, int64_t bytes);
+int dpq_free_host(void* ptr);
 /* ---- range search ---------------------------------------------------------
  * Every code within a radius of each query (FAISS's range_search).  For query q the list holds every code whose
  * distance d is STRICTLY below radii[q] (d < r, FAISS's L2 convention), d being exactly the distance dpq_query_batch

@@ -196,9 +196,9 @@ def test_host_to_host_batches_in_flight(gpu, oracle, codebook):
             q_in = [np.ascontiguousarray(qs[lo:hi]) for lo, hi in cuts]
             out_i = [np.full((hi - lo, k), -7, dtype=np.int32) for lo, hi in cuts]
             out_d = [np.full((hi - lo, k), -7.0, dtype=np.float32) for lo, hi in cuts]
-            if pinned:
-                for a in q_in + out_i + out_d:
-                    gpu.pin_host(a)
+            if pinned:   # (what pin_host returns is page-locked: the array itself, or a copy where the runtime registers none)
+                q_in, out_i, out_d = ([gpu.pin_host(a) for a in arrs] for arrs in (q_in, out_i, out_d))
+                assert all(np.all(a == -7) for a in out_i + out_d)
             for q, oi, od in zip(q_in, out_i, out_d):
                 idx.query_batch_host_async(q, k, oi, od)
             reruns = idx.finish()
@@ -217,6 +217,33 @@ def test_host_to_host_batches_in_flight(gpu, oracle, codebook):
         assert np.array_equal(got_i, want_i) and np.array_equal(got_d.view(np.uint32), want_d.view(np.uint32)), (pinned, kw)
     pick = [0, 300, 702, 1499]
     assert_parity(want_i[pick], want_d[pick], oracle_topk(oracle, payload, n, codebook, qs[pick], k), n)
+
+
+def test_page_locked_arrays(gpu, codebook):
+    """alloc_host gives a writable array of the shape and type asked for that outlives unpin_host; pin_host returns the
+    array's contents page-locked whether or not the runtime registers caller memory; and a dpq_pin_host that the runtime
+    refuses is that call's error alone: the batch after it (its launches check the runtime's last error) answers."""
+    from deltapq_amd import _lib, synth
+    a = gpu.alloc_host((3, 5), np.int32)
+    assert a.shape == (3, 5) and a.dtype == np.int32 and a.flags.c_contiguous and a.flags.writeable
+    a[...] = np.arange(15, dtype=np.int32).reshape(3, 5)
+    src = np.arange(7, dtype=np.float32)
+    p = gpu.pin_host(src)
+    assert p.dtype == src.dtype and np.array_equal(p, src)
+    gpu.unpin_host(p)
+    gpu.unpin_host(a)
+    assert np.array_equal(a.ravel(), np.arange(15)) and np.array_equal(p, src)
+    n, k = 5000, 10
+    tree, payload, _ = make_case(n, seed=421)
+    q = synth.make_queries(9, 128, seed=422)
+    with gpu.DeltaPQIndex.open_memory(payload, n, 8, 256) as idx:
+        idx.set_codebook(codebook)
+        want = idx.query_batch(q, k)
+        raw = np.empty(1 << 16, dtype=np.uint8)
+        if _lib.load().dpq_pin_host(raw.ctypes.data, raw.nbytes) == 0:
+            _lib.check(_lib.load().dpq_unpin_host(raw.ctypes.data), "dpq_unpin_host")
+        got = idx.query_batch(q, k)
+        assert np.array_equal(got[0], want[0]) and np.array_equal(got[1].view(np.uint32), want[1].view(np.uint32))
 
 
 def test_stream_ordered_batches_feed_device_consumers(gpu, oracle, codebook):
