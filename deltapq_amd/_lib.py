@@ -314,6 +314,14 @@ SYMBOLS = [
      [_VP, _VP, _VP, ctypes.c_int, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP, _VP, _VP]),
     ("dpq_ivf_range_search", ctypes.c_int, [_VP, _VP, _VP, ctypes.c_int, ctypes.c_int, _VP, P(_VP)]),
     ("dpq_ivf_range_search_probes", ctypes.c_int, [_VP, _VP, _VP, ctypes.c_int, _VP, ctypes.c_int, _VP, P(_VP)]),
+    ("dpq_ivf_residuals", ctypes.c_int, [_VP, ctypes.c_int, ctypes.c_int, _VP, c_i64, _VP, ctypes.c_int, _VP]),
+    ("dpq_ivf_residuals_device", ctypes.c_int, [_VP, ctypes.c_int, ctypes.c_int, _VP, c_i64, _VP, _VP, _VP]),
+    ("dpq_ivf_search_residual", ctypes.c_int, [_VP, _VP, _VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, _VP, _VP]),
+    ("dpq_ivf_search_residual_device", ctypes.c_int, [_VP, _VP, _VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP]),
+    ("dpq_ivf_search_probes_residual", ctypes.c_int,
+     [_VP, _VP, _VP, ctypes.c_int, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP]),
+    ("dpq_ivf_search_probes_residual_device", ctypes.c_int,
+     [_VP, _VP, _VP, ctypes.c_int, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP]),
     ("dpq_ivf_train", ctypes.c_int, [_VP, c_i64, ctypes.c_int, ctypes.c_int, P(IvfTrainOpts), _VP, P(IvfTrainStats)]),
     ("dpq_ivf_assign", ctypes.c_int, [_VP, ctypes.c_int, ctypes.c_int, _VP, c_i64, ctypes.c_int, _VP, _VP]),
     ("dpq_ivf_assign_device", ctypes.c_int, [_VP, ctypes.c_int, ctypes.c_int, _VP, c_i64, _VP, _VP, _VP]),

@@ -1227,6 +1227,40 @@ def ivf_assign_torch(centroids, vectors, out_labels=None, out_dists=None):
     return out_labels, out_dists
 
 
+def ivf_residuals(centroids, vectors, labels, device=0):
+    """float32 [n][D]: vectors[i] - centroids[labels[i]], one fp32 subtraction per float (dpq_ivf_residuals) -- the rows a
+    residual index trains its codebook on and encodes, and the rounding IVF.search_residual undoes."""
+    c = np.ascontiguousarray(centroids, dtype=np.float32)
+    v = np.ascontiguousarray(vectors, dtype=np.float32)
+    l = np.ascontiguousarray(labels, dtype=np.int32).ravel()
+    assert c.ndim == 2 and v.ndim == 2 and c.shape[1] == v.shape[1] and l.size == v.shape[0], \
+        "centroids [nlist][D], vectors [n][D], labels [n]"
+    out = np.empty_like(v)
+    check(_lib.load().dpq_ivf_residuals(_np_ptr(c), c.shape[0], c.shape[1], _np_ptr(v), v.shape[0], _np_ptr(l), device,
+                                        _np_ptr(out)), "dpq_ivf_residuals")
+    return out
+
+
+def ivf_residuals_torch(centroids, vectors, labels, out=None):
+    """ivf_residuals on device tensors (dpq_ivf_residuals_device), synchronous on torch's current stream; `out` may be
+    `vectors`."""
+    import torch
+    for t in (centroids, vectors):
+        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 2
+    n, D = vectors.shape
+    assert centroids.shape[1] == D and centroids.device == vectors.device
+    assert labels.is_cuda and labels.dtype == torch.int32 and labels.is_contiguous() and labels.numel() == n
+    if out is None:
+        out = torch.empty_like(vectors)
+    with torch.cuda.device(vectors.device):
+        stream = torch.cuda.current_stream(vectors.device).cuda_stream
+        check(_lib.load().dpq_ivf_residuals_device(ctypes.c_void_p(centroids.data_ptr()), centroids.shape[0], D,
+                                                   ctypes.c_void_p(vectors.data_ptr()), n, ctypes.c_void_p(labels.data_ptr()),
+                                                   ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(stream)),
+              "dpq_ivf_residuals_device")
+    return out
+
+
 def write_vecs(path, vectors):
     """float32 [n][D] as an .fvecs file (dpq_write_vecs): read_vecs gives the same bits."""
     v = np.ascontiguousarray(vectors, dtype=np.float32)
@@ -1360,6 +1394,27 @@ class IVF:
                   "dpq_ivf_search_probes_filtered")
         return ids, dists
 
+    def search_residual(self, queries, nprobe, top_k, id_filter=None):
+        """search over an index of RESIDUAL codes -- every node's code encodes x - c_list (ivf_residuals) -- with the table
+        of (query, probed list) made inside the list scan (dpq_ivf_search_residual).  Needs centroids."""
+        q = self._queries(queries)
+        ids = np.empty((q.shape[0], top_k), dtype=np.int32)
+        dists = np.empty((q.shape[0], top_k), dtype=np.float32)
+        check(self._lib.dpq_ivf_search_residual(self._h, self._filter(id_filter), _np_ptr(q), q.shape[0], nprobe, top_k,
+                                                _np_ptr(ids), _np_ptr(dists)), "dpq_ivf_search_residual")
+        return ids, dists
+
+    def search_probes_residual(self, queries, probes, top_k, id_filter=None):
+        """search_residual over the caller's own lists (dpq_ivf_search_probes_residual); needs centroids all the same."""
+        q = self._queries(queries)
+        p = self._probes(probes, q.shape[0])
+        ids = np.empty((q.shape[0], top_k), dtype=np.int32)
+        dists = np.empty((q.shape[0], top_k), dtype=np.float32)
+        check(self._lib.dpq_ivf_search_probes_residual(self._h, self._filter(id_filter), _np_ptr(q), q.shape[0], _np_ptr(p),
+                                                       p.shape[1], top_k, _np_ptr(ids), _np_ptr(dists)),
+              "dpq_ivf_search_probes_residual")
+        return ids, dists
+
     def search_probes_tables(self, tables, probes, top_k, id_filter=None):
         """search_probes with the caller's distance tables [nq][M][K] standing where the L2 tables of the queries stand
         (dpq_ivf_search_probes_tables); needs no codebook.  Entries: finite >= 0 or +inf."""
@@ -1479,6 +1534,28 @@ class IVF:
                                                                   ctypes.c_void_p(out_ids.data_ptr()),
                                                                   ctypes.c_void_p(out_dists.data_ptr()), stream),
                   "dpq_ivf_search_probes_device_filtered")
+        return out_ids, out_dists
+
+    def search_residual_torch(self, queries, nprobe, top_k, out_ids=None, out_dists=None, id_filter=None):
+        """search_residual on device tensors, synchronous on torch's current stream (dpq_ivf_search_residual_device)."""
+        nq, out_ids, out_dists, stream = self._torch_out(queries, top_k, out_ids, out_dists)
+        assert queries.dim() == 2
+        check(self._lib.dpq_ivf_search_residual_device(self._h, self._filter(id_filter), ctypes.c_void_p(queries.data_ptr()), nq,
+                                                       nprobe, top_k, ctypes.c_void_p(out_ids.data_ptr()),
+                                                       ctypes.c_void_p(out_dists.data_ptr()), stream),
+              "dpq_ivf_search_residual_device")
+        return out_ids, out_dists
+
+    def search_probes_residual_torch(self, queries, probes, top_k, out_ids=None, out_dists=None, id_filter=None):
+        """search_probes_residual on device tensors, synchronous on torch's current stream
+        (dpq_ivf_search_probes_residual_device)."""
+        nq, out_ids, out_dists, stream = self._torch_out(queries, top_k, out_ids, out_dists)
+        assert queries.dim() == 2
+        pp, nprobe = self._torch_probes(probes, nq)
+        check(self._lib.dpq_ivf_search_probes_residual_device(self._h, self._filter(id_filter), ctypes.c_void_p(queries.data_ptr()),
+                                                              nq, pp, nprobe, top_k, ctypes.c_void_p(out_ids.data_ptr()),
+                                                              ctypes.c_void_p(out_dists.data_ptr()), stream),
+              "dpq_ivf_search_probes_residual_device")
         return out_ids, out_dists
 
     def search_probes_tables_torch(self, tables, probes, top_k, id_filter=None, out_ids=None, out_dists=None):

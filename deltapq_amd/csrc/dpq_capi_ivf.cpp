@@ -181,6 +181,15 @@ int ivf_assign(dpq_index* x, const float* d_centroids, int nlist, int D, int32_t
     return DPQ_OK;
 }
 
+// dpq_ivf_residuals[_device]: the shapes dpq_ivf_assign takes.
+constexpr int64_t kIvfResidualTileBytes = (int64_t)256 << 20;  // rows dpq_ivf_residuals holds on the device at a time
+int ivf_residual_shape(const std::string& who, int D, int nlist, int64_t n) {
+    if (D < 1 || D > dpq::kFlatMaxD) return fail(DPQ_ERR_ARG, who + ": needs 1 <= D <= 2048");
+    if (int rc = ivf_nlist_ok(who, nlist)) return rc;
+    if (n < 0 || n >= ((int64_t)1 << 31)) return fail(DPQ_ERR_ARG, who + ": needs 0 <= n < 2^31");
+    return DPQ_OK;
+}
+
 // ---- search ----------------------------------------------------------------------------------------------------------
 
 int ivf_search_args(const std::string& who, const void* ivf, const void* queries, int nq, bool with_probes, const void* probes,
@@ -225,10 +234,11 @@ int ivf_probe_on_device(dpq_ivf* v, const float* d_queries, int nq, int nprobe, 
 }
 
 // Where a slice's exact tables come from, and who may be scanned.
-enum { kIvfQueries = 0, kIvfTables = 1, kIvfIp = 2 };
+// kIvfResidual: no tables at all -- the index holds residual codes, and the scan makes the table of (query, list) in LDS
+enum { kIvfQueries = 0, kIvfTables = 1, kIvfIp = 2, kIvfResidual = 3 };
 struct IvfSource {
     int kind = kIvfQueries;
-    const float* d_in = nullptr;         // queries [nq][M * Ds] (kIvfQueries, kIvfIp) or tables [nq][M][K] (kIvfTables)
+    const float* d_in = nullptr;         // queries [nq][M * Ds] (kIvfQueries, kIvfIp, kIvfResidual) or tables [nq][M][K] (kIvfTables)
     const dpq_filter* filter = nullptr;  // NULL: every entry of a list
     float* d_bias = nullptr;             // kIvfIp: [nq] dpq_ip_tables' bias, and d_scores[nq][top_k] the scores made of
     float* d_scores = nullptr;           // it and the gaps (the search's distances) behind the last slice
@@ -243,6 +253,14 @@ dpq::IvfFilter ivf_filter_of(const dpq_filter* f) {
     g.N = f->N;
     g.even = (!f->plain && (f->N & 1) == 0) ? 1 : 0;
     return g;
+}
+
+// Probe columns a workgroup of the residual scan takes.
+int ivf_residual_group_cfg() {
+    int group = dpq::kIvfResidualGroup;
+    if (dev_mode())
+        if (const char* e = getenv("DPQ_IVF_RESIDUAL_GROUP")) group = std::max(1, atoi(e));  // tests and the probe script: 1, 2, 4
+    return group;
 }
 
 // The exact tables of queries q0 .. q0 + m - 1 into v->lut32: from the queries and the codebook, from the caller's tables,
@@ -287,8 +305,10 @@ int ivf_search_on_device(dpq_ivf* v, const std::string& who, const IvfSource& sr
     const size_t row = (size_t)nprobe * top_k;
     const int per = (int)std::max<size_t>(1, std::min<size_t>(std::min(nq, dpq::kIvfSliceQueries), dpq::kIvfPartialBytes / (row * 8)));
     const int round = dpq::kIvfMergeKeys / top_k;  // lists one merge takes: at least 8
-    int rc = grow(v->lut32, &v->lut_n, (size_t)per * M * 256);
-    if (!rc) rc = grow(v->lut_min, &v->min_n, (size_t)per * M * dpq::kLutMinParts);
+    const bool residual = src.kind == kIvfResidual;  // no tables in memory: none are grown
+    int rc = DPQ_OK;
+    if (!residual) rc = grow(v->lut32, &v->lut_n, (size_t)per * M * 256);
+    if (!rc && !residual) rc = grow(v->lut_min, &v->min_n, (size_t)per * M * dpq::kLutMinParts);
     if (!rc) rc = grow(v->probes, &v->probes_n, (size_t)per * nprobe);
     if (!rc) rc = grow(v->part_ids, &v->part_ids_n, (size_t)per * row);
     if (!rc) rc = grow(v->part_dists, &v->part_dists_n, (size_t)per * row);
@@ -301,9 +321,13 @@ int ivf_search_on_device(dpq_ivf* v, const std::string& who, const IvfSource& sr
     for (int q0 = 0; q0 < nq; q0 += per) {
         const int m = std::min(per, nq - q0);
         const size_t list = (size_t)m * top_k;  // elements of one list's answers for the slice
-        if ((rc = ivf_slice_tables(v, src, q0, m, stream))) return rc;
+        if (!residual && (rc = ivf_slice_tables(v, src, q0, m, stream))) return rc;
         DPQ_HIP(dpq::launch_ivf_probes(d_probes + (size_t)q0 * nprobe, m, nprobe, v->nlist, v->probes, v->flag, stream));
-        if (filt.bits)
+        if (residual)
+            DPQ_HIP(dpq::launch_ivf_scan_residual(x->d_codebook, K, x->Ds, src.d_in + (size_t)q0 * M * x->Ds, v->centroids, m, v->probes,
+                                                  nprobe, v->offsets, v->ids, v->codes, M, x->plain, filt, top_k,
+                                                  ivf_residual_group_cfg(), v->part_ids, v->part_dists, stream));
+        else if (filt.bits)
             DPQ_HIP(dpq::launch_ivf_scan_filtered(v->lut32, m, v->probes, nprobe, v->offsets, v->ids, v->codes, M, x->plain, filt,
                                                   top_k, v->part_ids, v->part_dists, stream));
         else
@@ -354,7 +378,7 @@ int ivf_results_down(dpq_ivf* v, int nq, int top_k, int32_t* ids, float* dists) 
 // One top-k call of the forms that came after the unfiltered L2 search.  `in`: queries, or tables (kIvfTables).
 struct IvfCall {
     const char* fn;
-    int kind;          // kIvfQueries / kIvfTables / kIvfIp
+    int kind;          // kIvfQueries / kIvfTables / kIvfIp / kIvfResidual (needs centroids whoever chose the probes)
     bool need_filter;  // the _filtered forms: a NULL filter is an error
     bool coarse;       // the probes come from the centroids (kIvfIp: by inner product)
     bool device;       // device pointers, results complete on return
@@ -397,7 +421,7 @@ int ivf_call(dpq_ivf* v, const IvfCall& c) {
             for (size_t i = 0; i < n_in; ++i)
                 if (!(c.in[i] >= 0.0f)) return fail(DPQ_ERR_ARG, who + ": table entry " + std::to_string(i) + " is negative or a NaN");
     }
-    if (int rc = ivf_enter(who, v, c.nprobe, c.coarse, !tables)) return rc;
+    if (int rc = ivf_enter(who, v, c.nprobe, c.coarse || c.kind == kIvfResidual, !tables)) return rc;
     if (c.nq == 0) return DPQ_OK;
     const bool ip = c.kind == kIvfIp;
     IvfSource src;
@@ -885,6 +909,102 @@ int dpq_ivf_search_probes_device_ip(dpq_ivf* v, const dpq_filter* filter, const 
     return guarded([&]() -> int {
     return ivf_call(v, IvfCall{"dpq_ivf_search_probes_device_ip", kIvfIp, false, false, true, filter, d_queries, nq, d_probes,
                                nprobe, top_k, d_ids, d_scores, d_gaps, d_bias, (hipStream_t)hip_stream});
+    });
+}
+
+// ---- an index of residual codes ----
+
+int dpq_ivf_search_residual(dpq_ivf* v, const dpq_filter* filter, const float* queries, int nq, int nprobe, int top_k,
+                            int32_t* ids, float* dists) {
+    return guarded([&]() -> int {
+    return ivf_call(v, IvfCall{"dpq_ivf_search_residual", kIvfResidual, false, true, false, filter, queries, nq, nullptr, nprobe,
+                               top_k, ids, dists, nullptr, nullptr, nullptr});
+    });
+}
+
+int dpq_ivf_search_residual_device(dpq_ivf* v, const dpq_filter* filter, const float* d_queries, int nq, int nprobe, int top_k,
+                                   int32_t* d_ids, float* d_dists, void* hip_stream) {
+    return guarded([&]() -> int {
+    return ivf_call(v, IvfCall{"dpq_ivf_search_residual_device", kIvfResidual, false, true, true, filter, d_queries, nq, nullptr,
+                               nprobe, top_k, d_ids, d_dists, nullptr, nullptr, (hipStream_t)hip_stream});
+    });
+}
+
+int dpq_ivf_search_probes_residual(dpq_ivf* v, const dpq_filter* filter, const float* queries, int nq, const int32_t* probes,
+                                   int nprobe, int top_k, int32_t* ids, float* dists) {
+    return guarded([&]() -> int {
+    return ivf_call(v, IvfCall{"dpq_ivf_search_probes_residual", kIvfResidual, false, false, false, filter, queries, nq, probes,
+                               nprobe, top_k, ids, dists, nullptr, nullptr, nullptr});
+    });
+}
+
+int dpq_ivf_search_probes_residual_device(dpq_ivf* v, const dpq_filter* filter, const float* d_queries, int nq,
+                                          const int32_t* d_probes, int nprobe, int top_k, int32_t* d_ids, float* d_dists,
+                                          void* hip_stream) {
+    return guarded([&]() -> int {
+    return ivf_call(v, IvfCall{"dpq_ivf_search_probes_residual_device", kIvfResidual, false, false, true, filter, d_queries, nq,
+                               d_probes, nprobe, top_k, d_ids, d_dists, nullptr, nullptr, (hipStream_t)hip_stream});
+    });
+}
+
+int dpq_ivf_residuals_device(const float* d_centroids, int nlist, int D, const float* d_vectors, int64_t n, const int32_t* d_labels,
+                             float* d_out, void* hip_stream) {
+    return guarded([&]() -> int {
+    const std::string who = "dpq_ivf_residuals_device";
+    if (!d_centroids || !d_vectors || !d_labels || !d_out) return fail(DPQ_ERR_ARG, who + ": NULL argument");
+    if (int rc = ivf_residual_shape(who, D, nlist, n)) return rc;
+    if (int rc = flat_device_present(who)) return rc;
+    if (n == 0) return DPQ_OK;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    DevBuf<uint32_t> flag;
+    if (int rc = flag.alloc(1)) return rc;
+    uint32_t bad = 0;
+    DPQ_HIP(hipMemsetAsync(flag, 0, sizeof(uint32_t), stream));
+    DPQ_HIP(dpq::launch_ivf_residuals(d_vectors, d_labels, n, D, d_centroids, nlist, d_out, flag, stream));
+    DPQ_HIP(hipMemcpyAsync(&bad, flag, sizeof bad, hipMemcpyDeviceToHost, stream));
+    DPQ_HIP(hipStreamSynchronize(stream));
+    if (bad) return fail(DPQ_ERR_ARG, who + ": a label is outside 0 .. nlist - 1; the rows are unspecified");
+    return DPQ_OK;
+    });
+}
+
+int dpq_ivf_residuals(const float* centroids, int nlist, int D, const float* vectors, int64_t n, const int32_t* labels, int device,
+                      float* out) {
+    return guarded([&]() -> int {
+    const std::string who = "dpq_ivf_residuals";
+    if (!centroids || !vectors || !labels || !out) return fail(DPQ_ERR_ARG, who + ": NULL argument");
+    if (int rc = ivf_residual_shape(who, D, nlist, n)) return rc;
+    for (int64_t i = 0; i < n; ++i)
+        if (labels[i] < 0 || labels[i] >= nlist) {
+            char msg[96];
+            snprintf(msg, sizeof msg, ": labels[%lld] = %d is outside 0 .. nlist - 1", (long long)i, (int)labels[i]);
+            return fail(DPQ_ERR_ARG, who + msg);
+        }
+    if (int rc = flat_device_present(who)) return rc;
+    int ndev = 0;
+    hipGetDeviceCount(&ndev);
+    if (device < 0 || device >= ndev) return fail(DPQ_ERR_NO_DEVICE, who + ": device ordinal out of range");
+    DPQ_HIP(hipSetDevice(device));
+    if (n == 0) return DPQ_OK;
+    const int64_t tile = std::max<int64_t>(1, std::min(n, kIvfResidualTileBytes / ((int64_t)D * 4)));
+    DevBuf<float> d_cent, d_rows;
+    DevBuf<int32_t> d_labels;
+    DevBuf<uint32_t> flag;
+    int rc = d_cent.alloc((size_t)nlist * D);
+    if (!rc) rc = d_rows.alloc((size_t)tile * D);
+    if (!rc) rc = d_labels.alloc((size_t)tile);
+    if (!rc) rc = flag.alloc(1);
+    if (rc) return rc;
+    DPQ_HIP(hipMemcpy(d_cent, centroids, (size_t)nlist * D * sizeof(float), hipMemcpyHostToDevice));
+    DPQ_HIP(hipMemset(flag, 0, sizeof(uint32_t)));
+    for (int64_t r0 = 0; r0 < n; r0 += tile) {  // the rows are subtracted in place on the device
+        const int64_t m = std::min(tile, n - r0);
+        DPQ_HIP(hipMemcpy(d_rows, vectors + (size_t)r0 * D, (size_t)m * D * sizeof(float), hipMemcpyHostToDevice));
+        DPQ_HIP(hipMemcpy(d_labels, labels + r0, (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice));
+        DPQ_HIP(dpq::launch_ivf_residuals(d_rows, d_labels, m, D, d_cent, nlist, d_rows, flag, nullptr));
+        DPQ_HIP(hipMemcpy(out + (size_t)r0 * D, d_rows, (size_t)m * D * sizeof(float), hipMemcpyDeviceToHost));
+    }
+    return DPQ_OK;
     });
 }
 

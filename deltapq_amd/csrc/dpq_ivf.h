@@ -80,6 +80,31 @@ hipError_t launch_ivf_scan_filtered(const float* d_lut32, int nq, const int32_t*
                                     const int32_t* d_ids, const uint8_t* d_codes, int M, bool plain_rule, const IvfFilter& filter,
                                     int top_k, int32_t* d_part_ids, float* d_part_dists, hipStream_t stream);
 
+// ---- an index of residual codes (dpq_ivf_residual.hip) ---------------------------------------------------
+constexpr int kIvfResidualGroupMax = 4;  // probe columns one workgroup takes: 1, 2 or 4
+constexpr int kIvfResidualGroup = 2;     // ... and the shipped choice: the fastest measured at nprobe 16
+
+// The group the residual scan runs with: the largest of 4, 2, 1 that is at most `group` and whose LDS -- group * M KB of
+// tables beside the 2 P2 keys -- fits a workgroup.
+int ivf_residual_group(int M, int top_k, int group);
+
+// launch_ivf_scan[_filtered] (filter.bits NULL: no filter) over an index whose codes are PQ codes of x - c_list: the table
+// of (query q, probed list l) is lut_build_kernel's table of the residual query r[d] = q[d] - c_l[d] (fp32, round to
+// nearest; d_queries [nq][M * Ds], d_centroids [nlist][M * Ds], d_codebook [M][K][Ds], 16-byte aligned where Ds % 4 ==
+// 0), made in LDS by the workgroup that scans the list; entries k >= K are +inf.  A workgroup takes one query and `group`
+// consecutive probe columns (see ivf_residual_group) and reads the codebook once for them; the answer does not depend on
+// the group.  Output as launch_ivf_scan's.
+hipError_t launch_ivf_scan_residual(const float* d_codebook, int K, int Ds, const float* d_queries, const float* d_centroids,
+                                    int nq, const int32_t* d_probes, int nprobe, const int64_t* d_offsets, const int32_t* d_ids,
+                                    const uint8_t* d_codes, int M, bool plain_rule, const IvfFilter& filter, int top_k, int group,
+                                    int32_t* d_part_ids, float* d_part_dists, hipStream_t stream);
+
+// d_out[i][d] = d_vectors[i][d] - d_centroids[d_labels[i]][d], i < n: ONE fp32 subtraction, round to nearest -- the
+// rounding the residual scan undoes when it forms q[d] - c_l[d].  A label outside 0 .. nlist - 1 raises *d_flag and
+// leaves its row unspecified.
+hipError_t launch_ivf_residuals(const float* d_vectors, const int32_t* d_labels, int64_t n, int D, const float* d_centroids,
+                                int nlist, float* d_out, uint32_t* d_flag, hipStream_t stream);
+
 // The range scan, the same grid and table load.  d_thr[nq]: the radius keys -- distance bits << 32; 0 passes nothing
 // (r <= 0), ~0 passes every entry (r = +inf).  d_pool == NULL, the count pass: d_counts[q][p] = the eligible entries of
 // probe p's list with key < d_thr[q] (0 for padding, a repeat, an empty list).  Else the emit pass: those keys to

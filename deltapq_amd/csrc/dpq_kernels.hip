@@ -61,6 +61,7 @@
 // threshold, rounded down, saturated), so it never drops a node the exact rule
 // would keep.
 #include "dpq_kernels.h"
+#include "dpq_lut_step.h"
 #include "dpq_wave_decoder.h"
 
 #include <atomic>
@@ -130,12 +131,7 @@ __global__ __launch_bounds__(256) void lut_build_kernel(const float* __restrict_
         const float* c = codebook + ((size_t)m * K + k) * Ds;
         const float* qv = queries + (size_t)q0 * M * Ds + (size_t)m * Ds;  // query j: qv + j * M * Ds (clamped to nq - 1)
         const size_t qstride = (size_t)M * Ds;
-        // h:2845-2846: `float += pow(float - float, 2)`, d ascending
-        auto step = [&](float& a, float cv, float qd) {
-            const float diff = __fsub_rn(cv, qd);                      // fp32 subtract
-            const double sq = __dmul_rn((double)diff, (double)diff);   // pow(.,2): exact in fp64
-            a = (float)__dadd_rn((double)a, sq);                       // float += double
-        };
+        // one dimension of an entry: lut_step (dpq_lut_step.h), shared with the residual list scan
         if ((Ds & 3) == 0) {  // rows are 16-byte aligned: one dwordx4 load per 4 dimensions
             const float4* c4 = reinterpret_cast<const float4*>(c);
             for (int d = 0; d < Ds; d += 4) {
@@ -143,17 +139,17 @@ __global__ __launch_bounds__(256) void lut_build_kernel(const float* __restrict_
 #pragma unroll
                 for (int j = 0; j < kLutQueries; ++j) {
                     const float* qj = qv + (size_t)min(j, nq - 1 - q0) * qstride + d;
-                    step(acc[j], v.x, qj[0]);
-                    step(acc[j], v.y, qj[1]);
-                    step(acc[j], v.z, qj[2]);
-                    step(acc[j], v.w, qj[3]);
+                    lut_step(acc[j], v.x, qj[0]);
+                    lut_step(acc[j], v.y, qj[1]);
+                    lut_step(acc[j], v.z, qj[2]);
+                    lut_step(acc[j], v.w, qj[3]);
                 }
             }
         } else {
             for (int d = 0; d < Ds; ++d) {
                 const float cv = c[d];
 #pragma unroll
-                for (int j = 0; j < kLutQueries; ++j) step(acc[j], cv, qv[(size_t)min(j, nq - 1 - q0) * qstride + d]);
+                for (int j = 0; j < kLutQueries; ++j) lut_step(acc[j], cv, qv[(size_t)min(j, nq - 1 - q0) * qstride + d]);
             }
         }
     } else {

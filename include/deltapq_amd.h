@@ -52,6 +52,9 @@
  *   (none: FAISS's IndexIVFPQ with              dpq_ivf_create[_device] / dpq_ivf_build / dpq_ivf_set_centroids,
  *     by_residual = false: inverted lists,        dpq_ivf_probe / dpq_ivf_search[_device] / dpq_ivf_search_probes[_device]
  *     nprobe)                                     (lists over the index's nodes, probed per query)
+ *   (none: FAISS's IndexIVFPQ with              dpq_ivf_residuals[_device], dpq_ivf_search_residual[_device] /
+ *     by_residual = true)                         dpq_ivf_search_probes_residual[_device]
+ *                                                 (codes of x - c_list; the table of (query, list) made inside the scan)
  *   (none: FAISS's IndexIVF::train,             dpq_ivf_train / dpq_ivf_assign[_device], dpq_write_vecs
  *     quantizer->assign)                          (the coarse quantiser's centroids, learned and applied on the GPU)
  *   (none: FAISS's IndexFlatIP: search, an      dpq_flat_search_ip / dpq_flat_search_filtered_ip /
@@ -1476,6 +1479,50 @@ int dpq_ivf_range_search(dpq_ivf* ivf, const dpq_filter* filter, const float* qu
                          const float* radii, dpq_range_result** out);
 int dpq_ivf_range_search_probes(dpq_ivf* ivf, const dpq_filter* filter, const float* queries, int nq, const int32_t* probes,
                                 int nprobe, const float* radii, dpq_range_result** out);
+
+/* ---- IVF search by residual: an index whose codes encode x - c_list -----------------
+ * FAISS's IndexIVFPQ with by_residual = true, the form people deploy: every vector is encoded as the PQ code of its
+ * residual against the centroid of its list, so the codebook spends its words on the spread inside a cell.  NO
+ * REFERENCE COUNTERPART.
+ *   The index  is made by the caller from calls this library already has: dpq_ivf_train (centroids), dpq_ivf_assign
+ *           (labels), dpq_ivf_residuals (rows x - c_label), dpq_train_codebook and dpq_encode over those rows, the
+ *           DeltaTree builder over the codes, dpq_ivf_create with the nodes' labels, dpq_ivf_set_centroids.  A dpq_ivf
+ *           does NOT record which encoding its codes use: the calls below are meaningful only over an index of residual
+ *           codes, and dpq_ivf_build -- which assigns nodes by the reconstruction of their codes -- is not meaningful over
+ *           one.
+ *   Residuals  dpq_ivf_residuals[_device]: out[i][d] = vectors[i][d] - centroids[labels[i]][d], ONE fp32 subtraction rounded
+ *           to nearest (FAISS's compute_residual_n).  It is the rounding the search undoes.  A label outside 0 .. nlist - 1
+ *           is DPQ_ERR_ARG (host form: before any device work; device form: a flag word read at the end, the rows then
+ *           unspecified).  Shapes, errors and memory follow dpq_ivf_assign[_device]: D <= 2048, n < 2^31, the host form
+ *           works in tiles of 256 MB; the device form allocates one word and is complete on return; `out` may be
+ *           `vectors`.
+ *   Distance  For query q and probed list l: r[d] = q[d] - c_l[d] (fp32, round to nearest); the table T[m][k] of r by the
+ *           rule of dpq_query_batch's tables (fp32 subtract cb - r, the square in fp64, `float += double`, d ascending;
+ *           k >= K: +inf); the distance of an entry is the IVF search's sum of its M table entries (a plain handle: M fp32
+ *           additions in ascending m; else the fp64 sum, rounded once).  The partial answer of (q, l) is, bit for bit, what
+ *           dpq_ivf_search_probes returns for the query q - c_l and the probe row {l}; the answer of q is the top_k of its
+ *           lists' partial answers by (distance bits, id).  The tables are never in memory: the workgroup that scans a
+ *           list makes its table in LDS.
+ *   Calls   dpq_ivf_search_probes_residual[_device] take probe rows by dpq_ivf_search_probes' rules (padding, repeats,
+ *           an entry >= nlist); dpq_ivf_search_residual[_device] is dpq_ivf_probe (L2 to the centroids) followed by them.
+ *           `filter` may be NULL; otherwise only the codes it allows are scanned (dpq_ivf_search_filtered's rules).
+ *           Arguments and state are checked as in the calls above, with one addition: EVERY residual form needs
+ *           centroids, the probes forms included (DPQ_ERR_STATE without).  The device forms are complete on return.
+ *   Out of scope  inner product (there q . c_l is a constant per list and the table does not depend on it), range search
+ *           and caller tables by residual; FAISS's precomputed per-list tables, which change the arithmetic. */
+int dpq_ivf_residuals(const float* centroids, int nlist, int D, const float* vectors, int64_t n, const int32_t* labels,
+                      int device, float* out);
+int dpq_ivf_residuals_device(const float* d_centroids, int nlist, int D, const float* d_vectors, int64_t n,
+                             const int32_t* d_labels, float* d_out, void* hip_stream);
+int dpq_ivf_search_residual(dpq_ivf* ivf, const dpq_filter* filter, const float* queries, int nq, int nprobe, int top_k,
+                            int32_t* ids, float* dists);
+int dpq_ivf_search_residual_device(dpq_ivf* ivf, const dpq_filter* filter, const float* d_queries, int nq, int nprobe,
+                                   int top_k, int32_t* d_ids, float* d_dists, void* hip_stream);
+int dpq_ivf_search_probes_residual(dpq_ivf* ivf, const dpq_filter* filter, const float* queries, int nq,
+                                   const int32_t* probes, int nprobe, int top_k, int32_t* ids, float* dists);
+int dpq_ivf_search_probes_residual_device(dpq_ivf* ivf, const dpq_filter* filter, const float* d_queries, int nq,
+                                          const int32_t* d_probes, int nprobe, int top_k, int32_t* d_ids, float* d_dists,
+                                          void* hip_stream);
 
 /* ---- IVF training: the coarse quantiser's centroids, learned and applied on the GPU ---
  * FAISS's IndexIVF::train and quantizer->assign.  NO REFERENCE COUNTERPART.  One codebook over the WHOLE vector, nlist up
