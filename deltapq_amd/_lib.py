@@ -295,6 +295,19 @@ SYMBOLS = [
     ("dpq_ivf_probe", ctypes.c_int, [_VP, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP]),
     ("dpq_ivf_search", ctypes.c_int, [_VP, _VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, _VP, _VP]),
     ("dpq_ivf_search_device", ctypes.c_int, [_VP, _VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP]),
+    ("dpq_flat_ivf_create", ctypes.c_int, [_VP, _VP, c_i64, ctypes.c_int, P(_VP)]),
+    ("dpq_flat_ivf_create_device", ctypes.c_int, [_VP, _VP, c_i64, ctypes.c_int, _VP, P(_VP)]),
+    ("dpq_flat_ivf_build", ctypes.c_int, [_VP, _VP, ctypes.c_int, P(_VP)]),
+    ("dpq_flat_ivf_set_centroids", ctypes.c_int, [_VP, _VP, ctypes.c_int]),
+    ("dpq_flat_ivf_free", None, [_VP]),
+    ("dpq_flat_ivf_get_info", ctypes.c_int, [_VP, P(IvfStats)]),
+    ("dpq_flat_ivf_get", ctypes.c_int, [_VP, _VP, _VP]),
+    ("dpq_flat_ivf_probe", ctypes.c_int, [_VP, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP]),
+    ("dpq_flat_ivf_search_probes", ctypes.c_int, [_VP, _VP, ctypes.c_int, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP]),
+    ("dpq_flat_ivf_search_probes_device", ctypes.c_int,
+     [_VP, _VP, ctypes.c_int, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP]),
+    ("dpq_flat_ivf_search", ctypes.c_int, [_VP, _VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, _VP, _VP]),
+    ("dpq_flat_ivf_search_device", ctypes.c_int, [_VP, _VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP]),
     ("dpq_ivf_search_filtered", ctypes.c_int, [_VP, _VP, _VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, _VP, _VP]),
     ("dpq_ivf_search_device_filtered", ctypes.c_int, [_VP, _VP, _VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP]),
     ("dpq_ivf_search_probes_filtered", ctypes.c_int,

@@ -1855,6 +1855,144 @@ class FlatIndex(_FlatIndexBase):
         assert queries.dtype == torch.float32
 
 
+class FlatIVF:
+    """Inverted lists over the rows of one FlatIndex (dpq_flat_ivf, include/deltapq_amd.h "IVF search over raw vectors"):
+    exact distances to the rows of the lists a query probes, FAISS's IndexIVFFlat.  fp32 rows and squared L2 only.  Keeps
+    its index alive; close it (or leave its `with` block) before the index is closed."""
+
+    def __init__(self, flat_index, handle):
+        self._lib = flat_index._lib
+        self._index = flat_index
+        self._h = handle
+
+    @staticmethod
+    def _centroids(centroids):
+        c = np.ascontiguousarray(centroids, dtype=np.float32)
+        assert c.ndim == 2, "centroids must be [nlist][D]"
+        return c
+
+    @classmethod
+    def build(cls, flat_index, centroids):
+        """Lists by the nearest centroid of every row, ivf_assign's labels (dpq_flat_ivf_build); centroids float32
+        [nlist][D], kept for probe() and search()."""
+        c = cls._centroids(centroids)
+        assert c.shape[1] == flat_index.D
+        h = ctypes.c_void_p()
+        check(flat_index._lib.dpq_flat_ivf_build(flat_index._h, _np_ptr(c), c.shape[0], h), "dpq_flat_ivf_build")
+        return cls(flat_index, h)
+
+    @classmethod
+    def from_labels(cls, flat_index, labels, nlist, centroids=None):
+        """Lists from labels (dpq_flat_ivf_create; a CUDA int32 tensor: dpq_flat_ivf_create_device on torch's current
+        stream): labels[r] is the list of row r, -1 puts it in no list.  `centroids`: see set_centroids."""
+        h = ctypes.c_void_p()
+        lib = flat_index._lib
+        if isinstance(labels, np.ndarray) or not hasattr(labels, "data_ptr"):
+            a = np.ascontiguousarray(np.asarray(labels, dtype=np.int32).ravel())
+            check(lib.dpq_flat_ivf_create(flat_index._h, _np_ptr(a), a.size, int(nlist), h), "dpq_flat_ivf_create")
+        else:
+            import torch
+            assert labels.is_cuda and labels.dtype == torch.int32 and labels.is_contiguous()
+            stream = ctypes.c_void_p(torch.cuda.current_stream(labels.device).cuda_stream)
+            check(lib.dpq_flat_ivf_create_device(flat_index._h, ctypes.c_void_p(labels.data_ptr()), labels.numel(), int(nlist),
+                                                 stream, h), "dpq_flat_ivf_create_device")
+        ivf = cls(flat_index, h)
+        if centroids is not None:
+            ivf.set_centroids(centroids)
+        return ivf
+
+    def set_centroids(self, centroids):
+        """Attaches centroids float32 [nlist][D] to lists made from labels (dpq_flat_ivf_set_centroids)."""
+        c = self._centroids(centroids)
+        assert c.shape[1] == self._index.D
+        check(self._lib.dpq_flat_ivf_set_centroids(self._h, _np_ptr(c), c.shape[0]), "dpq_flat_ivf_set_centroids")
+        return self
+
+    def info(self):
+        s = _lib.IvfStats()
+        check(self._lib.dpq_flat_ivf_get_info(self._h, s), "dpq_flat_ivf_get_info")
+        return s.as_dict()
+
+    def lists(self):
+        """(offsets int64 [nlist + 1], ids int32 [n_assigned]): list l holds ids[offsets[l]:offsets[l + 1]], the reported
+        ids of its rows, ascending (dpq_flat_ivf_get)."""
+        inf = self.info()
+        offsets = np.empty(inf["nlist"] + 1, dtype=np.int64)
+        ids = np.empty(inf["n_assigned"], dtype=np.int32)
+        check(self._lib.dpq_flat_ivf_get(self._h, _np_ptr(offsets), _np_ptr(ids) if ids.size else None), "dpq_flat_ivf_get")
+        return offsets, ids
+
+    def _out(self, nq, cols):
+        return np.empty((nq, cols), dtype=np.int32), np.empty((nq, cols), dtype=np.float32)
+
+    def probe(self, queries, nprobe):
+        """(lists int32 [nq][nprobe], dists float32 [nq][nprobe]): each query's nprobe nearest centroids by (exact L2
+        distance, list number) (dpq_flat_ivf_probe)."""
+        q = self._index._queries(queries)
+        lists, dists = self._out(q.shape[0], nprobe)
+        check(self._lib.dpq_flat_ivf_probe(self._h, _np_ptr(q), q.shape[0], nprobe, _np_ptr(lists), _np_ptr(dists)),
+              "dpq_flat_ivf_probe")
+        return lists, dists
+
+    def search(self, queries, nprobe, top_k):
+        """The top_k nearest rows of the nprobe lists nearest to each query, by exact distance (dpq_flat_ivf_search).
+        Returns (ids int32 [nq][k], dists float32 [nq][k]): what search_filtered gives under a filter of those lists'
+        rows, padded with -1 / +inf."""
+        q = self._index._queries(queries)
+        ids, dists = self._out(q.shape[0], top_k)
+        check(self._lib.dpq_flat_ivf_search(self._h, _np_ptr(q), q.shape[0], nprobe, top_k, _np_ptr(ids), _np_ptr(dists)),
+              "dpq_flat_ivf_search")
+        return ids, dists
+
+    def search_probes(self, queries, probes, top_k):
+        """search over the caller's own lists: probes int32 [nq][nprobe], -1 = padding (dpq_flat_ivf_search_probes)."""
+        q = self._index._queries(queries)
+        p = IVF._probes(probes, q.shape[0])
+        ids, dists = self._out(q.shape[0], top_k)
+        check(self._lib.dpq_flat_ivf_search_probes(self._h, _np_ptr(q), q.shape[0], _np_ptr(p), p.shape[1], top_k, _np_ptr(ids),
+                                                   _np_ptr(dists)), "dpq_flat_ivf_search_probes")
+        return ids, dists
+
+    def _torch_out(self, queries, top_k, out_ids, out_dists):
+        assert queries.dim() == 2 and queries.shape[1] == self._index.D
+        return IVF._torch_out(queries, top_k, out_ids, out_dists)
+
+    def search_torch(self, queries, nprobe, top_k, out_ids=None, out_dists=None):
+        """search on device tensors, synchronous on torch's current stream (dpq_flat_ivf_search_device)."""
+        nq, out_ids, out_dists, stream = self._torch_out(queries, top_k, out_ids, out_dists)
+        check(self._lib.dpq_flat_ivf_search_device(self._h, ctypes.c_void_p(queries.data_ptr()), nq, nprobe, top_k,
+                                                   ctypes.c_void_p(out_ids.data_ptr()), ctypes.c_void_p(out_dists.data_ptr()),
+                                                   stream), "dpq_flat_ivf_search_device")
+        return out_ids, out_dists
+
+    def search_probes_torch(self, queries, probes, top_k, out_ids=None, out_dists=None):
+        """search_probes on device tensors, synchronous on torch's current stream (dpq_flat_ivf_search_probes_device)."""
+        nq, out_ids, out_dists, stream = self._torch_out(queries, top_k, out_ids, out_dists)
+        pp, nprobe = IVF._torch_probes(probes, nq)
+        check(self._lib.dpq_flat_ivf_search_probes_device(self._h, ctypes.c_void_p(queries.data_ptr()), nq, pp, nprobe, top_k,
+                                                          ctypes.c_void_p(out_ids.data_ptr()),
+                                                          ctypes.c_void_p(out_dists.data_ptr()), stream),
+              "dpq_flat_ivf_search_probes_device")
+        return out_ids, out_dists
+
+    def close(self):
+        if self._h is not None:
+            self._lib.dpq_flat_ivf_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 HALF_FORMATS = {"f16": 1, "bf16": 2}   # DPQ_HALF_F16, DPQ_HALF_BF16
 
 

@@ -1,0 +1,441 @@
+// dpq_capi_flat_ivf.cpp -- the dpq_flat_ivf_* entry points of include/deltapq_amd.h (kernels in dpq_flat_ivf.hip): inverted
+// lists over the rows of an fp32 dpq_flat handle, built on the device from labels or from centroids, and the search that
+// forms exact distances to the rows of the lists a query probes.
+#include "dpq_capi_internal.h"
+#include "dpq_ivf_train.h"
+
+namespace {
+
+int fivf_nlist_ok(const std::string& who, int nlist) {
+    if (nlist < 1 || nlist > dpq::kIvfMaxLists) return fail(DPQ_ERR_ARG, who + ": needs 1 <= nlist <= 65536");
+    return DPQ_OK;
+}
+
+// An fp32 handle on a present device.  (The launchers that make the lists take at most 2^31 - 1 rows.)
+int fivf_enter_flat(const std::string& who, dpq_flat* f) {
+    if (f->format != dpq::kFlatF32)
+        return fail(DPQ_ERR_ARG, who + ": needs a handle of fp32 rows (dpq_flat_open); half, byte, quantised and binary handles are not supported");
+    if (f->map.get()) return fail(DPQ_ERR_ARG, who + ": a handle with an id map (dpq_flat_set_id_map) is not supported");
+    if (f->n > 0x7fffffff) return fail(DPQ_ERR_ARG, who + ": the handle has too many rows");
+    if (int rc = flat_device_present(who)) return rc;
+    DPQ_HIP(hipSetDevice(f->device));
+    return DPQ_OK;
+}
+
+// The lists of d_labels[n] (n = the handle's rows), all on `stream`; *out is a structure without centroids.
+int fivf_from_device_labels(const std::string& who, dpq_flat* f, const int32_t* d_labels, int64_t n, int nlist,
+                            hipStream_t stream, std::unique_ptr<dpq_flat_ivf>* out) {
+    if (n != f->n) return fail(DPQ_ERR_ARG, who + ": n must be the handle's row count");
+    std::unique_ptr<dpq_flat_ivf> v(new dpq_flat_ivf());
+    v->flat = f;
+    v->device = f->device;
+    v->nlist = nlist;
+    DevBuf<uint32_t> keys, pos, keys_out, flag;
+    DevBuf<unsigned long long> counts;
+    DevBuf<uint8_t> temp;
+    int rc = keys.alloc((size_t)n);
+    if (!rc) rc = pos.alloc((size_t)n);
+    if (!rc) rc = keys_out.alloc((size_t)n);
+    if (!rc) rc = v->rows.alloc((size_t)n);  // the sorted positions ARE the lists: rows [0, n_assigned), then the unassigned
+    if (!rc) rc = counts.alloc((size_t)nlist + 1);
+    if (!rc) rc = flag.alloc(1);
+    if (!rc) rc = v->offsets.alloc((size_t)nlist + 1);
+    if (rc) return rc;
+    DPQ_HIP(hipMemsetAsync(counts, 0, ((size_t)nlist + 1) * sizeof(unsigned long long), stream));
+    DPQ_HIP(hipMemsetAsync(flag, 0, sizeof(uint32_t), stream));
+    DPQ_HIP(dpq::launch_ivf_label_keys(d_labels, n, nlist, keys, pos, counts, flag, stream));
+    size_t temp_bytes = 0;
+    DPQ_HIP(dpq::ivf_scan_and_sort(nullptr, &temp_bytes, counts, v->offsets, nlist, keys, keys_out, pos, v->rows, n, stream));
+    if ((rc = temp.alloc(temp_bytes))) return rc;
+    DPQ_HIP(dpq::ivf_scan_and_sort(temp, &temp_bytes, counts, v->offsets, nlist, keys, keys_out, pos, v->rows, n, stream));
+    v->h_offsets.resize((size_t)nlist + 1);
+    uint32_t bad = 0;
+    DPQ_HIP(hipMemcpyAsync(v->h_offsets.data(), v->offsets, ((size_t)nlist + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+    DPQ_HIP(hipMemcpyAsync(&bad, flag, sizeof bad, hipMemcpyDeviceToHost, stream));
+    DPQ_HIP(hipStreamSynchronize(stream));
+    if (bad) return fail(DPQ_ERR_ARG, who + ": a label is >= nlist");
+    v->n_assigned = v->h_offsets[(size_t)nlist];
+    v->n_unassigned = n - v->n_assigned;
+    if (v->h_offsets[0] != 0 || v->n_assigned < 0 || v->n_assigned > n)
+        return fail(DPQ_ERR_STATE, who + ": internal error: the list offsets do not add up");
+    for (int l = 0; l < nlist; ++l) {
+        const int64_t len = v->h_offsets[(size_t)l + 1] - v->h_offsets[(size_t)l];
+        if (len < 0) return fail(DPQ_ERR_STATE, who + ": internal error: the list offsets do not ascend");
+        v->max_list_len = std::max(v->max_list_len, len);
+    }
+    v->device_bytes = ((int64_t)nlist + 1) * 8 + n * 4;
+    *out = std::move(v);
+    return DPQ_OK;
+}
+
+// centroids[nlist][D] in host memory -> the device, padded with zeros to the handle's Dp.
+int fivf_upload_centroids(const dpq_flat* f, const float* centroids, int nlist, DevBuf<float>* d_out) {
+    const int D = f->D, Dp = f->Dp;
+    if (int rc = d_out->alloc((size_t)nlist * Dp)) return rc;
+    if (D == Dp) {
+        DPQ_HIP(hipMemcpy(d_out->get(), centroids, (size_t)nlist * D * sizeof(float), hipMemcpyHostToDevice));
+        return DPQ_OK;
+    }
+    std::vector<float> padded((size_t)nlist * Dp, 0.0f);
+    for (int l = 0; l < nlist; ++l) memcpy(&padded[(size_t)l * Dp], centroids + (size_t)l * D, (size_t)D * sizeof(float));
+    DPQ_HIP(hipMemcpy(d_out->get(), padded.data(), padded.size() * sizeof(float), hipMemcpyHostToDevice));
+    return DPQ_OK;
+}
+
+void fivf_keep_centroids(dpq_flat_ivf* v, DevBuf<float>&& d_cent) {
+    const int64_t bytes = (int64_t)v->nlist * v->flat->Dp * 4;
+    if (v->centroids.get()) v->device_bytes -= bytes;
+    v->centroids = std::move(d_cent);
+    v->device_bytes += bytes;
+}
+
+int fivf_search_args(const std::string& who, const void* ivf, const void* queries, int nq, bool with_probes, const void* probes,
+                     int nprobe, int top_k, const void* ids, const void* dists) {
+    if (!ivf || !queries || (with_probes && !probes) || !ids || !dists || nq < 0)
+        return fail(DPQ_ERR_ARG, who + ": NULL argument or nq < 0");
+    if (top_k < 1 || top_k > dpq::kIvfMaxTopK) return fail(DPQ_ERR_ARG, who + ": needs 1 <= top_k <= 2048");
+    if (nprobe < 1 || nprobe > dpq::kIvfMaxProbe) return fail(DPQ_ERR_ARG, who + ": needs 1 <= nprobe <= min(nlist, 1024)");
+    return DPQ_OK;
+}
+
+// What needs the structure's fields; then a device.
+int fivf_enter(const std::string& who, dpq_flat_ivf* v, int nprobe, bool coarse) {
+    if (nprobe > v->nlist) return fail(DPQ_ERR_ARG, who + ": needs 1 <= nprobe <= min(nlist, 1024)");
+    if (coarse && !v->centroids.get())
+        return fail(DPQ_ERR_STATE, who + ": the structure has no centroids (dpq_flat_ivf_build / dpq_flat_ivf_set_centroids)");
+    if (int rc = flat_device_present(who)) return rc;
+    DPQ_HIP(hipSetDevice(v->device));
+    return DPQ_OK;
+}
+
+int fivf_probe_rows_ok(const std::string& who, const dpq_flat_ivf* v, const int32_t* probes, int nq, int nprobe) {
+    for (size_t i = 0; i < (size_t)nq * nprobe; ++i)
+        if (probes[i] >= v->nlist) {
+            char msg[96];
+            snprintf(msg, sizeof msg, ": entry %lld = %d names no list", (long long)i, (int)probes[i]);
+            return fail(DPQ_ERR_ARG, who + msg);
+        }
+    return DPQ_OK;
+}
+
+// Queries as the kernels read them, [nq][Dp] with zero padding.  Host form: into v->d_q.  Device form: the caller's
+// rows where they already are that (D a multiple of four, 16-byte aligned), else padded into v->d_q on `stream`.
+int fivf_queries(dpq_flat_ivf* v, const float* queries, int nq, bool device, hipStream_t stream, const float** out) {
+    const int D = v->flat->D, Dp = v->flat->Dp;
+    if (device && D == Dp && (reinterpret_cast<uintptr_t>(queries) & 15u) == 0) {
+        *out = queries;
+        return DPQ_OK;
+    }
+    if (int rc = grow(v->d_q, &v->q_n, (size_t)nq * Dp)) return rc;
+    if (device) {
+        DPQ_HIP(dpq::launch_flat_pad_rows(queries, nq, D, Dp, v->d_q, stream));
+    } else if (D == Dp) {
+        DPQ_HIP(hipMemcpy(v->d_q, queries, (size_t)nq * D * sizeof(float), hipMemcpyHostToDevice));
+    } else {
+        std::vector<float> padded((size_t)nq * Dp, 0.0f);
+        for (int q = 0; q < nq; ++q) memcpy(&padded[(size_t)q * Dp], queries + (size_t)q * D, (size_t)D * sizeof(float));
+        DPQ_HIP(hipMemcpy(v->d_q, padded.data(), padded.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
+    *out = v->d_q;
+    return DPQ_OK;
+}
+
+// Room for the host forms' probes and results on the device.
+int fivf_stage(dpq_flat_ivf* v, int nq, int nprobe, int top_k) {
+    int rc = grow(v->d_probes, &v->dprobes_n, (size_t)nq * nprobe);
+    if (!rc) rc = grow(v->d_cdists, &v->cdists_n, (size_t)nq * nprobe);
+    if (!rc && top_k > 0) rc = grow(v->d_ids, &v->ids_n, (size_t)nq * top_k);
+    if (!rc && top_k > 0) rc = grow(v->d_dists, &v->dists_n, (size_t)nq * top_k);
+    return rc;
+}
+
+// The coarse step, all device pointers: d_lists[nq][nprobe] the nearest centroids by (distance, list number),
+// d_cdists[nq][nprobe] their distances: the exact search over the centroids as a base.  Enqueues on `stream`.
+int fivf_probe_on_device(dpq_flat_ivf* v, const float* d_q, int nq, int nprobe, int32_t* d_lists, float* d_cdists,
+                         hipStream_t stream) {
+    const int qb = std::min(nq, dpq::flat_query_batch(nprobe));
+    int rc = grow(v->keys, &v->keys_n, (size_t)qb * dpq::flat_key_capacity(nprobe));
+    if (!rc) rc = grow(v->state, &v->state_n, (size_t)qb);
+    if (rc) return rc;
+    dpq::FlatBase base;
+    base.format = dpq::kFlatF32;
+    base.rows = v->centroids.get();
+    base.n = v->nlist;
+    base.D = v->flat->D;
+    base.Dp = v->flat->Dp;
+    base.n_entries = v->nlist;
+    for (int q0 = 0; q0 < nq; q0 += qb) {
+        const int m = std::min(qb, nq - q0);
+        const dpq::FlatQueries q{d_q + (size_t)q0 * base.Dp, nullptr, nullptr, m};
+        DPQ_HIP(dpq::launch_flat_search(base, q, nprobe, v->keys, v->state, d_lists + (size_t)q0 * nprobe,
+                                        d_cdists + (size_t)q0 * nprobe, stream));
+    }
+    return DPQ_OK;
+}
+
+// Pairs a workgroup of the scan takes.
+int fivf_group_cfg() {
+    int group = dpq::kFlatIvfGroup;
+    if (dev_mode())
+        if (const char* e = getenv("DPQ_FLAT_IVF_GROUP")) group = std::max(1, atoi(e));  // tests and the probe script: a cap on G
+    return group;
+}
+
+// The search behind its checks, all device pointers; d_q [nq][Dp].  Slices of queries: per slice the probe pre-pass, the
+// pairs sorted by list, the list scan, the merge of the pairs' answers in rounds.  Ends with the flag word read back.
+int fivf_search_on_device(dpq_flat_ivf* v, const std::string& who, const float* d_q, int nq, const int32_t* d_probes, int nprobe,
+                          int top_k, int32_t* d_ids, float* d_dists, hipStream_t stream) {
+    const dpq_flat* f = v->flat;
+    const size_t row = (size_t)nprobe * top_k;
+    const int per = (int)std::max<size_t>(1, std::min<size_t>(std::min(nq, dpq::kIvfSliceQueries), dpq::kIvfPartialBytes / (row * 8)));
+    const int round = dpq::kIvfMergeKeys / top_k;
+    const size_t pairs = (size_t)per * nprobe;
+    size_t sort_bytes = 0, last_bytes = 0;  // of a full slice's sort, and of the last slice's
+    DPQ_HIP(dpq::flat_ivf_sort_pairs(nullptr, &sort_bytes, nullptr, nullptr, nullptr, nullptr, (int64_t)pairs, v->nlist, stream));
+    if (nq % per)
+        DPQ_HIP(dpq::flat_ivf_sort_pairs(nullptr, &last_bytes, nullptr, nullptr, nullptr, nullptr, (int64_t)(nq % per) * nprobe,
+                                         v->nlist, stream));
+    sort_bytes = std::max(sort_bytes, last_bytes);
+    int rc = grow(v->probes, &v->probes_n, pairs);
+    if (!rc && v->pairs_n < pairs) {
+        v->pairs_n = 0;
+        rc = v->pkeys.alloc(pairs);
+        if (!rc) rc = v->pvals.alloc(pairs);
+        if (!rc) rc = v->skeys.alloc(pairs);
+        if (!rc) rc = v->svals.alloc(pairs);
+        if (!rc) v->pairs_n = pairs;
+    }
+    if (!rc) rc = grow(v->sort_temp, &v->sort_n, sort_bytes);
+    if (!rc) rc = grow(v->part_ids, &v->part_ids_n, (size_t)per * row);
+    if (!rc) rc = grow(v->part_dists, &v->part_dists_n, (size_t)per * row);
+    if (!rc && nprobe > round) rc = grow(v->tmp_ids, &v->tmp_ids_n, (size_t)per * top_k);
+    if (!rc && nprobe > round) rc = grow(v->tmp_dists, &v->tmp_dists_n, (size_t)per * top_k);
+    if (!rc && !v->flag.get()) rc = v->flag.alloc(1);
+    if (rc) return rc;
+    dpq::FlatIvfLists lists;
+    lists.rows = reinterpret_cast<const float*>(f->rows.get() + f->rows_at);
+    lists.Dp = f->Dp;
+    lists.id_offset = f->id_offset;
+    lists.offsets = v->offsets;
+    lists.list_rows = v->rows;
+    lists.nlist = v->nlist;
+    const int group = fivf_group_cfg();
+    DPQ_HIP(hipMemsetAsync(v->flag, 0, sizeof(uint32_t), stream));
+    for (int q0 = 0; q0 < nq; q0 += per) {
+        const int m = std::min(per, nq - q0);
+        const int64_t n_pairs = (int64_t)m * nprobe;
+        DPQ_HIP(dpq::launch_ivf_probes(d_probes + (size_t)q0 * nprobe, m, nprobe, v->nlist, v->probes, v->flag, stream));
+        DPQ_HIP(dpq::launch_flat_ivf_pairs(v->probes, n_pairs, v->nlist, v->pkeys, v->pvals, stream));
+        size_t tb = v->sort_n;
+        DPQ_HIP(dpq::flat_ivf_sort_pairs(v->sort_temp, &tb, v->pkeys, v->skeys, v->pvals, v->svals, n_pairs, v->nlist, stream));
+        DPQ_HIP(dpq::launch_flat_ivf_scan(lists, d_q + (size_t)q0 * f->Dp, m, nprobe, v->skeys, v->svals, top_k, group, v->part_ids,
+                                          v->part_dists, stream));
+        if ((rc = ivf_merge_rounds(v->part_ids, v->part_dists, v->tmp_ids, v->tmp_dists, nprobe, m, top_k,
+                                   d_ids + (size_t)q0 * top_k, d_dists + (size_t)q0 * top_k, stream)))
+            return rc;
+    }
+    uint32_t bad = 0;
+    DPQ_HIP(hipMemcpyAsync(&bad, v->flag, sizeof bad, hipMemcpyDeviceToHost, stream));
+    DPQ_HIP(hipStreamSynchronize(stream));
+    if (bad) return fail(DPQ_ERR_ARG, who + ": a probe names no list (an entry >= nlist)");
+    return DPQ_OK;
+}
+
+int fivf_results_down(dpq_flat_ivf* v, int nq, int top_k, int32_t* ids, float* dists) {
+    DPQ_HIP(hipMemcpy(ids, v->d_ids, (size_t)nq * top_k * sizeof(int32_t), hipMemcpyDeviceToHost));
+    DPQ_HIP(hipMemcpy(dists, v->d_dists, (size_t)nq * top_k * sizeof(float), hipMemcpyDeviceToHost));
+    return DPQ_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dpq_flat_ivf_create_device(dpq_flat* f, const int32_t* d_labels, int64_t n, int nlist, void* hip_stream, dpq_flat_ivf** out) {
+    return guarded([&]() -> int {
+    const std::string who = "dpq_flat_ivf_create_device";
+    if (out) *out = nullptr;
+    if (!f || !d_labels || !out || n < 0) return fail(DPQ_ERR_ARG, who + ": NULL argument or n < 0");
+    if (int rc = fivf_nlist_ok(who, nlist)) return rc;
+    if (int rc = fivf_enter_flat(who, f)) return rc;
+    std::unique_ptr<dpq_flat_ivf> v;
+    if (int rc = fivf_from_device_labels(who, f, d_labels, n, nlist, (hipStream_t)hip_stream, &v)) return rc;
+    *out = v.release();
+    return DPQ_OK;
+    });
+}
+
+int dpq_flat_ivf_create(dpq_flat* f, const int32_t* labels, int64_t n, int nlist, dpq_flat_ivf** out) {
+    return guarded([&]() -> int {
+    const std::string who = "dpq_flat_ivf_create";
+    if (out) *out = nullptr;
+    if (!f || !labels || !out || n < 0) return fail(DPQ_ERR_ARG, who + ": NULL argument or n < 0");
+    if (int rc = fivf_nlist_ok(who, nlist)) return rc;
+    if (n != f->n) return fail(DPQ_ERR_ARG, who + ": n must be the handle's row count");
+    for (int64_t i = 0; i < n; ++i)
+        if (labels[i] >= nlist) {
+            char msg[96];
+            snprintf(msg, sizeof msg, ": labels[%lld] = %d is >= nlist", (long long)i, (int)labels[i]);
+            return fail(DPQ_ERR_ARG, who + msg);
+        }
+    if (int rc = fivf_enter_flat(who, f)) return rc;
+    DevBuf<int32_t> d_labels;
+    if (int rc = d_labels.alloc((size_t)n)) return rc;
+    DPQ_HIP(hipMemcpy(d_labels, labels, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
+    std::unique_ptr<dpq_flat_ivf> v;
+    if (int rc = fivf_from_device_labels(who, f, d_labels, n, nlist, nullptr, &v)) return rc;
+    *out = v.release();
+    return DPQ_OK;
+    });
+}
+
+int dpq_flat_ivf_build(dpq_flat* f, const float* centroids, int nlist, dpq_flat_ivf** out) {
+    return guarded([&]() -> int {
+    const std::string who = "dpq_flat_ivf_build";
+    if (out) *out = nullptr;
+    if (!f || !centroids || !out) return fail(DPQ_ERR_ARG, who + ": NULL argument");
+    if (int rc = fivf_nlist_ok(who, nlist)) return rc;
+    if (int rc = fivf_enter_flat(who, f)) return rc;
+    DevBuf<float> d_cent;
+    if (int rc = fivf_upload_centroids(f, centroids, nlist, &d_cent)) return rc;
+    // dpq_ivf_assign's arg-min over the handle's own padded rows: the zero padding adds +0.0 to every distance
+    DevBuf<int32_t> d_labels;
+    if (int rc = d_labels.alloc((size_t)f->n)) return rc;
+    DPQ_HIP(dpq::launch_ivf_argmin(reinterpret_cast<const float*>(f->rows.get() + f->rows_at), f->n, f->Dp, d_cent, nlist, nullptr,
+                                   d_labels, nullptr, nullptr, nullptr));
+    std::unique_ptr<dpq_flat_ivf> v;
+    if (int rc = fivf_from_device_labels(who, f, d_labels, f->n, nlist, nullptr, &v)) return rc;
+    fivf_keep_centroids(v.get(), std::move(d_cent));
+    *out = v.release();
+    return DPQ_OK;
+    });
+}
+
+int dpq_flat_ivf_set_centroids(dpq_flat_ivf* v, const float* centroids, int nlist) {
+    return guarded([&]() -> int {
+    const std::string who = "dpq_flat_ivf_set_centroids";
+    if (!v || !centroids) return fail(DPQ_ERR_ARG, who + ": NULL argument");
+    if (nlist != v->nlist) return fail(DPQ_ERR_ARG, who + ": nlist is not the structure's");
+    if (int rc = flat_device_present(who)) return rc;
+    DPQ_HIP(hipSetDevice(v->device));
+    DevBuf<float> d_cent;
+    if (int rc = fivf_upload_centroids(v->flat, centroids, nlist, &d_cent)) return rc;
+    fivf_keep_centroids(v, std::move(d_cent));
+    return DPQ_OK;
+    });
+}
+
+void dpq_flat_ivf_free(dpq_flat_ivf* v) {
+    if (!v) return;
+    hipSetDevice(v->device);
+    delete v;
+}
+
+int dpq_flat_ivf_get_info(const dpq_flat_ivf* v, dpq_ivf_stats* out) {
+    return guarded([&]() -> int {
+    if (!v || !out) return fail(DPQ_ERR_ARG, "dpq_flat_ivf_get_info: NULL argument");
+    out->n_assigned = v->n_assigned;
+    out->n_unassigned = v->n_unassigned;
+    out->max_list_len = v->max_list_len;
+    out->device_bytes = v->device_bytes;
+    out->nlist = v->nlist;
+    out->has_centroids = v->centroids.get() ? 1 : 0;
+    return DPQ_OK;
+    });
+}
+
+int dpq_flat_ivf_get(const dpq_flat_ivf* v, int64_t* offsets_out, int32_t* ids_out) {
+    return guarded([&]() -> int {
+    if (!v || !offsets_out) return fail(DPQ_ERR_ARG, "dpq_flat_ivf_get: NULL argument");
+    std::copy(v->h_offsets.begin(), v->h_offsets.end(), offsets_out);
+    if (ids_out && v->n_assigned > 0) {
+        DPQ_HIP(hipSetDevice(v->device));
+        std::vector<uint32_t> rows((size_t)v->n_assigned);
+        DPQ_HIP(hipMemcpy(rows.data(), v->rows, rows.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < rows.size(); ++i) ids_out[i] = (int32_t)(uint32_t)((int64_t)rows[i] + v->flat->id_offset);
+    }
+    return DPQ_OK;
+    });
+}
+
+int dpq_flat_ivf_probe(dpq_flat_ivf* v, const float* queries, int nq, int nprobe, int32_t* lists_out, float* dists_out) {
+    return guarded([&]() -> int {
+    const std::string who = "dpq_flat_ivf_probe";
+    if (!v || !queries || !lists_out || nq < 0) return fail(DPQ_ERR_ARG, who + ": NULL argument or nq < 0");
+    if (nprobe < 1 || nprobe > dpq::kIvfMaxProbe) return fail(DPQ_ERR_ARG, who + ": needs 1 <= nprobe <= min(nlist, 1024)");
+    if (int rc = fivf_enter(who, v, nprobe, true)) return rc;
+    if (nq == 0) return DPQ_OK;
+    const float* d_q = nullptr;
+    if (int rc = fivf_queries(v, queries, nq, false, nullptr, &d_q)) return rc;
+    if (int rc = fivf_stage(v, nq, nprobe, 0)) return rc;
+    if (int rc = fivf_probe_on_device(v, d_q, nq, nprobe, v->d_probes, v->d_cdists, nullptr)) return rc;
+    DPQ_HIP(hipMemcpy(lists_out, v->d_probes, (size_t)nq * nprobe * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (dists_out) DPQ_HIP(hipMemcpy(dists_out, v->d_cdists, (size_t)nq * nprobe * sizeof(float), hipMemcpyDeviceToHost));
+    return DPQ_OK;
+    });
+}
+
+int dpq_flat_ivf_search_probes_device(dpq_flat_ivf* v, const float* d_queries, int nq, const int32_t* d_probes, int nprobe,
+                                      int top_k, int32_t* d_ids, float* d_dists, void* hip_stream) {
+    return guarded([&]() -> int {
+    const std::string who = "dpq_flat_ivf_search_probes_device";
+    if (int rc = fivf_search_args(who, v, d_queries, nq, true, d_probes, nprobe, top_k, d_ids, d_dists)) return rc;
+    if (int rc = fivf_enter(who, v, nprobe, false)) return rc;
+    if (nq == 0) return DPQ_OK;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    const float* d_q = nullptr;
+    if (int rc = fivf_queries(v, d_queries, nq, true, stream, &d_q)) return rc;
+    return fivf_search_on_device(v, who, d_q, nq, d_probes, nprobe, top_k, d_ids, d_dists, stream);
+    });
+}
+
+int dpq_flat_ivf_search_probes(dpq_flat_ivf* v, const float* queries, int nq, const int32_t* probes, int nprobe, int top_k,
+                               int32_t* ids, float* dists) {
+    return guarded([&]() -> int {
+    const std::string who = "dpq_flat_ivf_search_probes";
+    if (int rc = fivf_search_args(who, v, queries, nq, true, probes, nprobe, top_k, ids, dists)) return rc;
+    if (nprobe > v->nlist) return fail(DPQ_ERR_ARG, who + ": needs 1 <= nprobe <= min(nlist, 1024)");
+    if (int rc = fivf_probe_rows_ok(who, v, probes, nq, nprobe)) return rc;
+    if (int rc = fivf_enter(who, v, nprobe, false)) return rc;
+    if (nq == 0) return DPQ_OK;
+    const float* d_q = nullptr;
+    if (int rc = fivf_queries(v, queries, nq, false, nullptr, &d_q)) return rc;
+    if (int rc = fivf_stage(v, nq, nprobe, top_k)) return rc;
+    DPQ_HIP(hipMemcpy(v->d_probes, probes, (size_t)nq * nprobe * sizeof(int32_t), hipMemcpyHostToDevice));
+    if (int rc = fivf_search_on_device(v, who, d_q, nq, v->d_probes, nprobe, top_k, v->d_ids, v->d_dists, nullptr)) return rc;
+    return fivf_results_down(v, nq, top_k, ids, dists);
+    });
+}
+
+int dpq_flat_ivf_search_device(dpq_flat_ivf* v, const float* d_queries, int nq, int nprobe, int top_k, int32_t* d_ids,
+                               float* d_dists, void* hip_stream) {
+    return guarded([&]() -> int {
+    const std::string who = "dpq_flat_ivf_search_device";
+    if (int rc = fivf_search_args(who, v, d_queries, nq, false, nullptr, nprobe, top_k, d_ids, d_dists)) return rc;
+    if (int rc = fivf_enter(who, v, nprobe, true)) return rc;
+    if (nq == 0) return DPQ_OK;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    const float* d_q = nullptr;
+    if (int rc = fivf_queries(v, d_queries, nq, true, stream, &d_q)) return rc;
+    if (int rc = fivf_stage(v, nq, nprobe, 0)) return rc;
+    if (int rc = fivf_probe_on_device(v, d_q, nq, nprobe, v->d_probes, v->d_cdists, stream)) return rc;
+    return fivf_search_on_device(v, who, d_q, nq, v->d_probes, nprobe, top_k, d_ids, d_dists, stream);
+    });
+}
+
+int dpq_flat_ivf_search(dpq_flat_ivf* v, const float* queries, int nq, int nprobe, int top_k, int32_t* ids, float* dists) {
+    return guarded([&]() -> int {
+    const std::string who = "dpq_flat_ivf_search";
+    if (int rc = fivf_search_args(who, v, queries, nq, false, nullptr, nprobe, top_k, ids, dists)) return rc;
+    if (int rc = fivf_enter(who, v, nprobe, true)) return rc;
+    if (nq == 0) return DPQ_OK;
+    const float* d_q = nullptr;
+    if (int rc = fivf_queries(v, queries, nq, false, nullptr, &d_q)) return rc;
+    if (int rc = fivf_stage(v, nq, nprobe, top_k)) return rc;
+    if (int rc = fivf_probe_on_device(v, d_q, nq, nprobe, v->d_probes, v->d_cdists, nullptr)) return rc;
+    if (int rc = fivf_search_on_device(v, who, d_q, nq, v->d_probes, nprobe, top_k, v->d_ids, v->d_dists, nullptr)) return rc;
+    return fivf_results_down(v, nq, top_k, ids, dists);
+    });
+}
+
+}  // extern "C"

@@ -25,6 +25,7 @@
 #include "dpq_candidates.h"
 #include "dpq_filter.h"
 #include "dpq_flat.h"
+#include "dpq_flat_ivf.h"
 #include "dpq_format.h"
 #include "dpq_ivf.h"
 #include "dpq_kernels.h"
@@ -227,6 +228,33 @@ struct dpq_ivf {
     DevBuf<uint64_t> r_thr, r_pool, r_sorted;
     DevBuf<int64_t> r_counts, r_offs, r_qoffs;
     size_t r_thr_n = 0, r_pool_n = 0, r_sorted_n = 0, r_counts_n = 0, r_offs_n = 0, r_qoffs_n = 0;
+};
+
+// Inverted lists over the rows of one fp32 dpq_flat handle (dpq_flat_ivf_*, dpq_capi_flat_ivf.cpp): row numbers into the
+// handle's own rows, and the workspace every search on it works in.
+struct dpq_flat_ivf {
+    dpq_flat* flat = nullptr;       // the handle it was made on; freed before dpq_flat_close
+    int device = 0;
+    int nlist = 0;
+    int64_t n_assigned = 0, n_unassigned = 0, max_list_len = 0;
+    std::vector<int64_t> h_offsets; // [nlist + 1] host copy (dpq_flat_ivf_get, dpq_flat_ivf_get_info)
+    DevBuf<int64_t> offsets;        // [nlist + 1]
+    DevBuf<uint32_t> rows;          // [n_assigned] row numbers, ascending inside a list
+    DevBuf<float> centroids;        // [nlist][Dp] padded as the handle's rows are; NULL: none set
+    int64_t device_bytes = 0;       // of the three above
+    // workspace, grown on demand and kept until dpq_flat_ivf_free
+    DevBuf<int32_t> probes;                  // [slice queries][nprobe] the pre-pass's rows
+    DevBuf<uint32_t> pkeys, pvals, skeys, svals;  // [slice queries * nprobe] the pairs, as formed and sorted by list
+    DevBuf<uint8_t> sort_temp;               // the pair sort's scratch
+    DevBuf<int32_t> part_ids, tmp_ids;       // [nprobe][slice queries][top_k] the lists' answers; [slice queries][top_k] a
+    DevBuf<float> part_dists, tmp_dists;     // merge round's
+    DevBuf<uint32_t> flag;                   // [1] a probe names no list
+    DevBuf<uint64_t> keys;                   // coarse step: a batch's key buffers and states
+    DevBuf<dpq::FlatQueryState> state;
+    DevBuf<float> d_q, d_dists, d_cdists;    // queries padded to Dp; host forms: distances; the coarse step's distances
+    DevBuf<int32_t> d_probes, d_ids;         // ... probes, ids
+    size_t probes_n = 0, pairs_n = 0, sort_n = 0, part_ids_n = 0, part_dists_n = 0, tmp_ids_n = 0, tmp_dists_n = 0, keys_n = 0,
+           state_n = 0, q_n = 0, dists_n = 0, cdists_n = 0, dprobes_n = 0, ids_n = 0;
 };
 
 uint64_t next_index_serial();  // dpq_capi.cpp: one counter for the process
@@ -499,5 +527,7 @@ bool lookup_id_ok(const dpq_index* x, int64_t id);                              
 int lookup_on_device(dpq_index* x, const int32_t* d_ids, int64_t n, uint8_t* d_codes, float* d_vecs, hipStream_t stream,
                      const char* who);                                                                          // dpq_capi_lookup.cpp
 int opq_check_dim(const std::string& who, int D);                                                               // dpq_capi_train.cpp
+int ivf_merge_rounds(int32_t* part_ids, float* part_dists, int32_t* tmp_ids, float* tmp_dists, int nprobe, int m, int top_k,
+                     int32_t* out_i, float* out_d, hipStream_t stream);                                         // dpq_capi_ivf.cpp
 
 #pragma GCC visibility pop

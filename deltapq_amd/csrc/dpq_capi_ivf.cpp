@@ -2,6 +2,26 @@
 // handle's nodes, built on the device from labels or from centroids, and the search that scans the lists a query probes.
 #include "dpq_capi_internal.h"
 
+// The lists' answers of a slice, part [nprobe][m][top_k], merged into out [m][top_k] in rounds of what one merge holds.
+// The lists are disjoint and the merge keeps every key, so a merge of merges is the merge of all: a round's answer
+// (tmp [m][top_k], needed where nprobe exceeds a round) takes the place of the last list it consumed and opens the next.
+int ivf_merge_rounds(int32_t* part_ids, float* part_dists, int32_t* tmp_ids, float* tmp_dists, int nprobe, int m, int top_k,
+                     int32_t* out_i, float* out_d, hipStream_t stream) {
+    const int round = dpq::kIvfMergeKeys / top_k;  // lists one merge takes: at least 8
+    const size_t list = (size_t)m * top_k;         // elements of one list's answers for the slice
+    for (int l0 = 0;;) {
+        const int l1 = std::min(l0 + round, nprobe);
+        const bool last = l1 == nprobe;
+        DPQ_HIP(dpq::launch_merge(part_ids + (size_t)l0 * list, part_dists + (size_t)l0 * list, l1 - l0, m, top_k, top_k,
+                                  last ? out_i : tmp_ids, last ? out_d : tmp_dists, stream));
+        if (last) break;
+        l0 = l1 - 1;
+        DPQ_HIP(hipMemcpyAsync(part_ids + (size_t)l0 * list, tmp_ids, list * sizeof(int32_t), hipMemcpyDeviceToDevice, stream));
+        DPQ_HIP(hipMemcpyAsync(part_dists + (size_t)l0 * list, tmp_dists, list * sizeof(float), hipMemcpyDeviceToDevice, stream));
+    }
+    return DPQ_OK;
+}
+
 namespace {
 
 constexpr int64_t kIvfTileNodes = (int64_t)4 << 20;      // nodes decoded per tile (dpq_decode_range's bound)
@@ -320,7 +340,6 @@ int ivf_search_on_device(dpq_ivf* v, const std::string& who, const IvfSource& sr
     DPQ_HIP(hipMemsetAsync(v->flag, 0, 2 * sizeof(uint32_t), stream));
     for (int q0 = 0; q0 < nq; q0 += per) {
         const int m = std::min(per, nq - q0);
-        const size_t list = (size_t)m * top_k;  // elements of one list's answers for the slice
         if (!residual && (rc = ivf_slice_tables(v, src, q0, m, stream))) return rc;
         DPQ_HIP(dpq::launch_ivf_probes(d_probes + (size_t)q0 * nprobe, m, nprobe, v->nlist, v->probes, v->flag, stream));
         if (residual)
@@ -333,22 +352,9 @@ int ivf_search_on_device(dpq_ivf* v, const std::string& who, const IvfSource& sr
         else
             DPQ_HIP(dpq::launch_ivf_scan(v->lut32, m, v->probes, nprobe, v->offsets, v->ids, v->codes, M, x->plain, top_k,
                                          v->part_ids, v->part_dists, stream));
-        int32_t* out_i = d_ids + (size_t)q0 * top_k;
-        float* out_d = d_dists + (size_t)q0 * top_k;
-        // the lists are disjoint and the merge keeps every key, so a merge of merges is the merge of all: a round's
-        // answer takes the place of the last list it consumed and opens the next round
-        for (int l0 = 0;;) {
-            const int l1 = std::min(l0 + round, nprobe);
-            const bool last = l1 == nprobe;
-            DPQ_HIP(dpq::launch_merge(v->part_ids.get() + (size_t)l0 * list, v->part_dists.get() + (size_t)l0 * list, l1 - l0, m,
-                                      top_k, top_k, last ? out_i : v->tmp_ids.get(), last ? out_d : v->tmp_dists.get(), stream));
-            if (last) break;
-            l0 = l1 - 1;
-            DPQ_HIP(hipMemcpyAsync(v->part_ids.get() + (size_t)l0 * list, v->tmp_ids, list * sizeof(int32_t),
-                                   hipMemcpyDeviceToDevice, stream));
-            DPQ_HIP(hipMemcpyAsync(v->part_dists.get() + (size_t)l0 * list, v->tmp_dists, list * sizeof(float),
-                                   hipMemcpyDeviceToDevice, stream));
-        }
+        if ((rc = ivf_merge_rounds(v->part_ids, v->part_dists, v->tmp_ids, v->tmp_dists, nprobe, m, top_k,
+                                   d_ids + (size_t)q0 * top_k, d_dists + (size_t)q0 * top_k, stream)))
+            return rc;
     }
     if (src.d_scores) DPQ_HIP(dpq::launch_ip_scores(src.d_bias, d_dists, d_ids, nq, top_k, src.d_scores, stream));
     return ivf_read_flags(v, who, src.kind, stream);

@@ -1,0 +1,345 @@
+// dpq_flat_ivf.hip -- the inverted-list scan over raw fp32 rows on gfx950: exact distances of the
+// queries to the rows of the lists they probe.  The arithmetic is the exact search's (dpq_flat.h): per dimension in
+// ascending order t = v[d] - q[d] and s = t * t, each rounded in fp32, summed on one lane's fp64 accumulator from +0.0,
+// rounded once.  The build passes -ffp-contract=off and keeps clear of the packed fp32 instructions.
+//
+//   flat_ivf_pairs_kernel  a thread per (query, probe): the pair's sort key, its list or nlist for padding.
+//   flat_ivf_scan_kernel   a workgroup of 256 per run of G consecutive SORTED pairs.  The pairs of a list are neighbours, so
+//                          a run is a few stretches of equal list; the workgroup takes them in turn and reads a list's rows
+//                          once for all the queries of its stretch.  Per tile of 256 rows: the row numbers go to LDS
+//                          once; then, in slices of 32 dimensions, the rows (gathered through the row numbers, eight
+//                          lanes to a row's 128 bytes) and the stretch's queries go to LDS transposed -- Rs[d][row]
+//                          with a stride of 260, Qs[d][query] -- while the next slice's rows are already on their way
+//                          in registers.  Lane (tx, ty) owns rows 4 tx .. 4 tx + 3 and queries QPL ty .. QPL ty + QPL - 1
+//                          (QPL = 4 at G = 16): its rows come as one 16-byte LDS read per dimension, its queries as a
+//                          broadcast, and each of its 4 QPL fp64 accumulators runs from the first dimension to the
+//                          last.  Behind the last slice a key below its pair's threshold is appended to the pair's
+//                          buffer of 2 P2 keys by an LDS atomic on the pair's count.  When a buffer could overflow on
+//                          the next tile, the buffers of the stretch are sorted side by side (one bitonic network, the
+//                          same barriers for all), cut to top_k, and the thresholds become the k-th keys.
+#include "dpq_flat_ivf.h"
+
+#include <hipcub/hipcub.hpp>
+
+#include <algorithm>
+#include <atomic>
+
+#include "dpq_flat.h"
+#include "dpq_ivf.h"
+
+namespace dpq {
+namespace {
+
+constexpr int TR = kFlatIvfTileRows, SD = kFlatIvfSliceDims, GM = kFlatIvfGroupMax;
+constexpr int RS = TR + 4;  // floats between two dimensions of the row tile: 16-byte reads stay aligned, and the eight
+                            // 4-dimension columns a wavefront stores at once start 16 banks apart
+constexpr size_t kTileBytes = (size_t)SD * RS * 4 + (size_t)SD * GM * 4 + (size_t)TR * 4;  // rows, queries, row numbers
+constexpr size_t kLdsBytes = 160 * 1024;
+constexpr size_t kStaticBytes = 512;  // the run's words below, rounded up
+constexpr uint32_t kNoRow = 0xffffffffu;
+
+__global__ __launch_bounds__(256) void flat_ivf_pairs_kernel(const int32_t* __restrict__ probes, int64_t n, int nlist,
+                                                             uint32_t* __restrict__ keys, uint32_t* __restrict__ vals) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int32_t l = probes[i];
+    keys[i] = (l >= 0 && l < nlist) ? (uint32_t)l : (uint32_t)nlist;
+    vals[i] = (uint32_t)i;
+}
+
+// Sorts nb buffers of n keys each (n a power of two >= 2), `stride` keys apart, ascending: ivf_bitonic's network over
+// every buffer at once.  Every thread of the workgroup calls it.  Ends behind a barrier.
+__device__ __forceinline__ void sort_buffers(uint64_t* buf, int nb, int n, int stride, int tid) {
+    const int half = n >> 1, hs = __ffs(half) - 1, total = nb * half;
+    for (int k = 2; k <= n; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int t = tid; t < total; t += 256) {
+                const int u = t & (half - 1);
+                uint64_t* b = buf + (size_t)(t >> hs) * stride;
+                const int i = ((u & ~(j - 1)) << 1) | (u & (j - 1));
+                const int l = i | j;
+                const uint64_t x = b[i], y = b[l];
+                const bool up = (i & k) == 0;
+                if ((x > y) == up) {
+                    b[i] = y;
+                    b[l] = x;
+                }
+            }
+            __syncthreads();
+        }
+}
+
+// The rows' part of slice d0 for this thread: float4 c of row r = idx >> 3, idx = tid + 256 i.  A row beyond the list's
+// end and a column beyond the last dimension give zeros (neither is read by the sum).
+__device__ __forceinline__ void load_slice(float4 (&pre)[8], const float* __restrict__ rows, int Dp, const uint32_t* s_rows,
+                                           int d0, int tid) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const int idx = tid + 256 * i, r = idx >> 3, c = idx & 7;
+        const uint32_t row = s_rows[r];
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (row != kNoRow && d0 + 4 * c < Dp) v = *reinterpret_cast<const float4*>(rows + (size_t)row * Dp + d0 + 4 * c);
+        pre[i] = v;
+    }
+}
+
+// grid: the runs; 256 threads; dynamic LDS: the tiles, then G buffers of cap = 2 P2 keys.
+template <int QPL>
+__global__ __launch_bounds__(256) void flat_ivf_scan_kernel(const float* __restrict__ rows, int Dp, int64_t id_offset,
+                                                            const int64_t* __restrict__ offsets,
+                                                            const uint32_t* __restrict__ list_rows, int nlist,
+                                                            const float* __restrict__ queries, int nq, int nprobe,
+                                                            const uint32_t* __restrict__ skeys,
+                                                            const uint32_t* __restrict__ svals, int64_t n_pairs, int G,
+                                                            int top_k, int cap, int32_t* __restrict__ part_ids,
+                                                            float* __restrict__ part_dists) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char flat_ivf_smem[];
+    float* Rs = reinterpret_cast<float*>(flat_ivf_smem);          // [SD][RS]
+    float* Qs = Rs + SD * RS;                                     // [SD][GM]
+    uint32_t* s_rows = reinterpret_cast<uint32_t*>(Qs + SD * GM);  // [TR]
+    uint64_t* buf = reinterpret_cast<uint64_t*>(s_rows + TR);      // [G][cap]
+    __shared__ uint32_t s_key[GM], s_val[GM], s_q[GM], s_cnt[GM];
+    __shared__ uint64_t s_thr[GM];
+    const int tid = threadIdx.x, tx = tid & 63, ty = tid >> 6;
+    const int64_t p0 = (int64_t)blockIdx.x * G;
+    const int np = (int)min((int64_t)G, n_pairs - p0);
+    if (tid < GM) {
+        const uint32_t val = tid < np ? svals[p0 + tid] : 0u;
+        s_key[tid] = tid < np ? skeys[p0 + tid] : (uint32_t)nlist;
+        s_val[tid] = val;
+        s_q[tid] = val / (uint32_t)nprobe;
+    }
+    __syncthreads();
+    // Everything the workgroup branches on below is read from LDS behind a barrier, or from one global address: the
+    // stretches, the list bounds and the buffer counts are the same in every thread.
+    for (int s = 0; s < np;) {
+        const uint32_t list = s_key[s];
+        int e = s + 1;
+        while (e < np && s_key[e] == list) ++e;
+        const int nqs = e - s;  // queries of the stretch: pairs s .. e - 1
+        int64_t lo = 0, hi = 0;
+        if (list < (uint32_t)nlist) {
+            lo = offsets[list];
+            hi = offsets[list + 1];
+        }
+        if (tid < nqs) {
+            s_cnt[tid] = 0u;
+            s_thr[tid] = kFlatNoKey;
+        }
+        const bool active = QPL * ty < nqs;  // (a wavefront's lanes share ty)
+        for (int64_t base = lo; base < hi; base += TR) {
+            __syncthreads();  // the tile before is done with s_rows; the first tile: the counts above are in place
+            s_rows[tid] = base + tid < hi ? list_rows[base + tid] : kNoRow;
+            __syncthreads();
+            double acc[QPL][4];
+#pragma unroll
+            for (int i = 0; i < QPL; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc[i][j] = 0.0;
+            float4 pre[8];
+            load_slice(pre, rows, Dp, s_rows, 0, tid);
+            for (int d0 = 0; d0 < Dp; d0 += SD) {
+                const int dlen = min(SD, Dp - d0);  // a multiple of four
+#pragma unroll
+                for (int i = 0; i < 8; ++i) {
+                    const int idx = tid + 256 * i, r = idx >> 3, c = idx & 7;
+                    if (4 * c < dlen) {
+                        Rs[(4 * c + 0) * RS + r] = pre[i].x;
+                        Rs[(4 * c + 1) * RS + r] = pre[i].y;
+                        Rs[(4 * c + 2) * RS + r] = pre[i].z;
+                        Rs[(4 * c + 3) * RS + r] = pre[i].w;
+                    }
+                }
+#pragma unroll
+                for (int i = 0; i < SD * GM / 256; ++i) {
+                    const int idx = tid + 256 * i, qs = idx >> 5, d = idx & 31;
+                    float v = 0.f;
+                    if (qs < nqs && d < dlen) v = queries[(size_t)s_q[s + qs] * Dp + d0 + d];
+                    Qs[d * GM + qs] = v;
+                }
+                __syncthreads();
+                if (d0 + SD < Dp) load_slice(pre, rows, Dp, s_rows, d0 + SD, tid);  // in flight under the sums below
+                if (active) {
+#pragma unroll 4
+                    for (int d = 0; d < dlen; ++d) {
+                        const float4 v = *reinterpret_cast<const float4*>(&Rs[d * RS + 4 * tx]);
+                        float q[QPL];
+                        if constexpr (QPL == 4) {
+                            const float4 w = *reinterpret_cast<const float4*>(&Qs[d * GM + 4 * ty]);
+                            q[0] = w.x; q[1] = w.y; q[2] = w.z; q[3] = w.w;
+                        } else if constexpr (QPL == 2) {
+                            const float2 w = *reinterpret_cast<const float2*>(&Qs[d * GM + 2 * ty]);
+                            q[0] = w.x; q[1] = w.y;
+                        } else {
+                            q[0] = Qs[d * GM + ty];
+                        }
+#pragma unroll
+                        for (int i = 0; i < QPL; ++i) {
+                            accumulate<kFlatL2>(acc[i][0], v.x, q[i]);
+                            accumulate<kFlatL2>(acc[i][1], v.y, q[i]);
+                            accumulate<kFlatL2>(acc[i][2], v.z, q[i]);
+                            accumulate<kFlatL2>(acc[i][3], v.w, q[i]);
+                        }
+                    }
+                }
+                __syncthreads();
+            }
+            if (active) {
+#pragma unroll
+                for (int i = 0; i < QPL; ++i) {
+                    const int qs = QPL * ty + i;
+                    if (qs >= nqs) continue;
+                    const uint64_t thr = s_thr[qs];
+                    uint64_t* b = buf + (size_t)qs * cap;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const uint32_t row = s_rows[4 * tx + j];
+                        if (row == kNoRow) continue;
+                        const uint64_t key = make_key<kFlatL2>(acc[i][j], (uint32_t)(id_offset + (int64_t)row));
+                        if (key < thr) b[atomicAdd(&s_cnt[qs], 1u)] = key;  // < cap: the tile had room for its 256 rows
+                    }
+                }
+            }
+            __syncthreads();
+            if (base + TR < hi) {
+                uint32_t mx = 0u;
+                for (int p = 0; p < nqs; ++p) mx = max(mx, s_cnt[p]);
+                if (mx + TR > (uint32_t)cap) {  // a buffer has no room for the next tile: sort, keep top_k, lower the thresholds
+                    int n = 2;
+                    while ((uint32_t)n < mx) n <<= 1;
+                    for (int p = 0; p < nqs; ++p)
+                        for (int i = (int)s_cnt[p] + tid; i < n; i += 256) buf[(size_t)p * cap + i] = kFlatNoKey;
+                    __syncthreads();
+                    sort_buffers(buf, nqs, n, cap, tid);
+                    if (tid < nqs) {
+                        const uint32_t c = s_cnt[tid];
+                        if (c >= (uint32_t)top_k) s_thr[tid] = buf[(size_t)tid * cap + top_k - 1];  // ids are unique in a list: the
+                        s_cnt[tid] = min(c, (uint32_t)top_k);                                      // strict test loses nothing
+                    }
+                }
+            }
+        }
+        if (hi > lo) {
+            uint32_t mx = 0u;
+            for (int p = 0; p < nqs; ++p) mx = max(mx, s_cnt[p]);  // (behind the last tile's closing barrier)
+            int n = 2;
+            while ((uint32_t)n < mx) n <<= 1;
+            for (int p = 0; p < nqs; ++p)
+                for (int i = (int)s_cnt[p] + tid; i < n; i += 256) buf[(size_t)p * cap + i] = kFlatNoKey;
+            __syncthreads();
+            sort_buffers(buf, nqs, n, cap, tid);
+        }
+        // the stretch's answers: pair i = q * nprobe + j goes to row j * nq + q.  A padding pair, or an empty list: padding
+        for (int p = 0; p < nqs; ++p) {
+            const uint32_t q = s_q[s + p], j = s_val[s + p] - q * (uint32_t)nprobe;
+            int32_t* out_i = part_ids + ((size_t)j * nq + q) * top_k;
+            float* out_d = part_dists + ((size_t)j * nq + q) * top_k;
+            const uint32_t cnt = hi > lo ? s_cnt[p] : 0u;
+            for (int r = tid; r < top_k; r += 256) {
+                const uint64_t key = (uint32_t)r < cnt ? buf[(size_t)p * cap + r] : kFlatNoKey;
+                out_i[r] = key != kFlatNoKey ? (int32_t)(key & 0xffffffffu) : -1;
+                out_d[r] = key != kFlatNoKey ? __uint_as_float((uint32_t)(key >> 32)) : INFINITY;
+            }
+        }
+        __syncthreads();  // the next stretch starts the counts and the buffers over
+        s = e;
+    }
+}
+
+int pow2_at_least(int v) {
+    int p = 1;
+    while (p < v) p <<= 1;
+    return p;
+}
+
+int scan_cap(int top_k) { return 2 * pow2_at_least(std::max(top_k, 256)); }
+
+// hipFuncSetAttribute is per device
+template <int QPL>
+hipError_t ensure_scan_lds() {
+    static std::atomic<bool> done[64];
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    if (dev < 0 || dev >= 64 || !done[dev].load(std::memory_order_acquire)) {
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&flat_ivf_scan_kernel<QPL>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kLdsBytes - kStaticBytes));
+        if (e != hipSuccess) return e;
+        if (dev >= 0 && dev < 64) done[dev].store(true, std::memory_order_release);
+    }
+    return hipSuccess;
+}
+
+template <int QPL>
+hipError_t launch_scan(const FlatIvfLists& L, const float* d_queries, int nq, int nprobe, const uint32_t* d_skeys,
+                       const uint32_t* d_svals, int64_t n_pairs, int G, int top_k, int cap, int32_t* d_part_ids,
+                       float* d_part_dists, hipStream_t stream) {
+    if (hipError_t e = ensure_scan_lds<QPL>()) return e;
+    const size_t lds = kTileBytes + (size_t)G * cap * sizeof(uint64_t);
+    const dim3 grid((unsigned)((n_pairs + G - 1) / G)), block(256);
+    flat_ivf_scan_kernel<QPL><<<grid, block, lds, stream>>>(L.rows, L.Dp, L.id_offset, L.offsets, L.list_rows, L.nlist, d_queries,
+                                                            nq, nprobe, d_skeys, d_svals, n_pairs, G, top_k, cap, d_part_ids,
+                                                            d_part_dists);
+    return hipGetLastError();
+}
+
+int key_bits(int nlist) {
+    int bits = 1;  // keys are 0 .. nlist
+    while ((1u << bits) <= (uint32_t)nlist) ++bits;
+    return bits;
+}
+
+}  // namespace
+
+int flat_ivf_group(int top_k, int group) {
+    const size_t per = (size_t)scan_cap(top_k) * sizeof(uint64_t);
+    int g = GM;
+    while (g > 1 && (g > group || kTileBytes + (size_t)g * per + kStaticBytes > kLdsBytes)) g >>= 1;
+    return g;
+}
+
+hipError_t launch_flat_ivf_pairs(const int32_t* d_probes, int64_t n_pairs, int nlist, uint32_t* d_keys, uint32_t* d_vals,
+                                 hipStream_t stream) {
+    if (n_pairs <= 0) return hipSuccess;
+    if (!d_probes || !d_keys || !d_vals || nlist < 1 || nlist > kIvfMaxLists || n_pairs > 0x7fffffff) return hipErrorInvalidValue;
+    flat_ivf_pairs_kernel<<<dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, stream>>>(d_probes, n_pairs, nlist, d_keys,
+                                                                                               d_vals);
+    return hipGetLastError();
+}
+
+hipError_t flat_ivf_sort_pairs(void* d_temp, size_t* temp_bytes, const uint32_t* d_keys, uint32_t* d_keys_out,
+                               const uint32_t* d_vals, uint32_t* d_vals_out, int64_t n_pairs, int nlist, hipStream_t stream) {
+    if (!temp_bytes || nlist < 1 || nlist > kIvfMaxLists || n_pairs < 1 || n_pairs > 0x7fffffff) return hipErrorInvalidValue;
+    size_t need = 0;
+    hipError_t e = hipcub::DeviceRadixSort::SortPairs(nullptr, need, d_keys, d_keys_out, d_vals, d_vals_out, (int)n_pairs, 0,
+                                                      key_bits(nlist), stream);
+    if (e != hipSuccess) return e;
+    if (!d_temp) {
+        *temp_bytes = need;
+        return hipSuccess;
+    }
+    if (*temp_bytes < need) return hipErrorInvalidValue;
+    size_t tb = *temp_bytes;
+    return hipcub::DeviceRadixSort::SortPairs(d_temp, tb, d_keys, d_keys_out, d_vals, d_vals_out, (int)n_pairs, 0, key_bits(nlist),
+                                              stream);
+}
+
+hipError_t launch_flat_ivf_scan(const FlatIvfLists& L, const float* d_queries, int nq, int nprobe, const uint32_t* d_skeys,
+                                const uint32_t* d_svals, int top_k, int group, int32_t* d_part_ids, float* d_part_dists,
+                                hipStream_t stream) {
+    if (nq <= 0) return hipSuccess;
+    if (!L.rows || !L.offsets || !L.list_rows || !d_queries || !d_skeys || !d_svals || !d_part_ids || !d_part_dists ||
+        L.Dp < 4 || L.Dp % 4 != 0 || L.Dp > kFlatMaxD || L.nlist < 1 || L.nlist > kIvfMaxLists || nprobe < 1 ||
+        nprobe > kIvfMaxProbe || top_k < 1 || top_k > kIvfMaxTopK || group < 1 || (int64_t)nq * nprobe > 0x7fffffff ||
+        ((reinterpret_cast<uintptr_t>(L.rows) | reinterpret_cast<uintptr_t>(d_queries)) & 15u))
+        return hipErrorInvalidValue;
+    const int cap = scan_cap(top_k), G = flat_ivf_group(top_k, group);
+    const int64_t n_pairs = (int64_t)nq * nprobe;
+    if (G == 16)
+        return launch_scan<4>(L, d_queries, nq, nprobe, d_skeys, d_svals, n_pairs, G, top_k, cap, d_part_ids, d_part_dists, stream);
+    if (G == 8)
+        return launch_scan<2>(L, d_queries, nq, nprobe, d_skeys, d_svals, n_pairs, G, top_k, cap, d_part_ids, d_part_dists, stream);
+    return launch_scan<1>(L, d_queries, nq, nprobe, d_skeys, d_svals, n_pairs, G, top_k, cap, d_part_ids, d_part_dists, stream);
+}
+
+}  // namespace dpq

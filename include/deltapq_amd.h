@@ -57,6 +57,9 @@
  *                                                 (codes of x - c_list; the table of (query, list) made inside the scan)
  *   (none: FAISS's IndexIVF::train,             dpq_ivf_train / dpq_ivf_assign[_device], dpq_write_vecs
  *     quantizer->assign)                          (the coarse quantiser's centroids, learned and applied on the GPU)
+ *   (none: FAISS's IndexIVFFlat)                dpq_flat_ivf_create[_device] / dpq_flat_ivf_build, dpq_flat_ivf_probe /
+ *                                                 dpq_flat_ivf_search[_device] / dpq_flat_ivf_search_probes[_device]
+ *                                                 (lists over a dpq_flat handle's rows, exact distances in the probed lists)
  *   (none: FAISS's IndexFlatIP: search, an      dpq_flat_search_ip / dpq_flat_search_filtered_ip /
  *     IDSelector, range_search; re-ranking by     dpq_flat_range_search_ip / dpq_flat_rerank_ip[_device],
  *     inner product)                              dpq_merge_topk_ip_host
@@ -1586,6 +1589,60 @@ int dpq_ivf_assign_device(const float* d_centroids, int nlist, int D, const floa
                           float* d_dists, void* hip_stream);
 /* Host only: n rows of (int32 D, D floats), the .fvecs layout dpq_read_vecs reads. */
 int dpq_write_vecs(const char* path, const float* vectors, int64_t n, int D);
+
+/* ---- IVF search over raw vectors: exact distances in the probed lists ------------
+ * FAISS's IndexIVFFlat.  NO REFERENCE COUNTERPART.  A dpq_flat_ivf holds nlist inverted lists over the rows of ONE open
+ * dpq_flat handle; a query forms exact distances to the rows of the lists it probes only.
+ *   Formats    fp32 rows (dpq_flat_open) only.  Half, byte, quantised and binary handles, and a handle with an id map, are
+ *           DPQ_ERR_ARG.  Squared L2 only: no inner product, no filter, no range search, no shards and no CLI task yet.
+ *   Ownership  The structure is bound to the handle it was made on and is freed (dpq_flat_ivf_free) BEFORE
+ *           dpq_flat_close of that handle; both are used from one thread.
+ *   Memory  No row is copied: a list is the ascending ROW NUMBERS of its members in the handle's own padded rows.
+ *           offsets[nlist + 1] int64 and 4 bytes per row of the handle, beside, where set, centroids[nlist][D padded to a
+ *           multiple of four].
+ *   Labels  dpq_flat_ivf_create[_device]: labels[r] is the list of row r, n must be the handle's row count (fewer than
+ *           2^31), a negative label puts the row in no list, empty lists are legal, 1 <= nlist <= 65536.  A label >= nlist
+ *           is DPQ_ERR_ARG (host form: checked before any device work; device form: one flag word read back at the end).
+ *   Centroids  dpq_flat_ivf_build: centroids[nlist][D] in host memory; the label of a row is what dpq_ivf_assign gives it
+ *           -- the nearest centroid under the exact search's arithmetic, the lower list number at a tie -- computed on
+ *           the device over the handle's rows.  The centroids are kept.  dpq_flat_ivf_set_centroids attaches
+ *           centroids[nlist][D] to a structure made from labels.
+ *   Probes  dpq_flat_ivf_search_probes[_device]: probes[nq][nprobe] by dpq_ivf_search_probes' rules -- a negative entry
+ *           is padding, a list named twice counts once, an entry >= nlist is DPQ_ERR_ARG (host form: checked on the host;
+ *           device form: a flag word, the outputs then unspecified, the next call works).  dpq_flat_ivf_probe: the nprobe
+ *           nearest centroids of each query by (exact L2 distance, list number); dists_out may be NULL.
+ *           dpq_flat_ivf_search[_device] is dpq_flat_ivf_probe followed by dpq_flat_ivf_search_probes.  Without centroids
+ *           dpq_flat_ivf_probe and dpq_flat_ivf_search* are DPQ_ERR_STATE.
+ *   Answer  For query q exactly what dpq_flat_search_filtered returns under a filter that allows the union of the probed
+ *           lists: the same distance bits (per dimension in ascending order t = v[d] - q[d] and s = t * t, each rounded in
+ *           fp32, summed in fp64 from +0.0 and rounded once), reported id = row + id_offset, order by (distance, id), rows
+ *           padded with -1 / +inf where the union holds fewer than top_k rows.
+ *   Limits  1 <= top_k <= 2048, 1 <= nprobe <= min(nlist, 1024), else DPQ_ERR_ARG; nq == 0 is DPQ_OK; queries are
+ *           [nq][D] fp32.  Argument errors that need no device come before any device call.
+ *   State   Calls are synchronous (the device forms enqueue on `hip_stream`, NULL = default stream, and return with the
+ *           results complete).  They work in a workspace owned by the dpq_flat_ivf -- per slice of at most 2048 queries the
+ *           (query, list) pairs sorted by list and the partial answers [nprobe][queries][top_k], at most 256 MB -- and
+ *           never write the dpq_flat handle's own workspace. */
+typedef struct dpq_flat_ivf dpq_flat_ivf;
+int dpq_flat_ivf_create(dpq_flat* flat, const int32_t* labels, int64_t n, int nlist, dpq_flat_ivf** out);
+int dpq_flat_ivf_create_device(dpq_flat* flat, const int32_t* d_labels, int64_t n, int nlist, void* hip_stream,
+                               dpq_flat_ivf** out);
+int dpq_flat_ivf_build(dpq_flat* flat, const float* centroids, int nlist, dpq_flat_ivf** out);
+int dpq_flat_ivf_set_centroids(dpq_flat_ivf* ivf, const float* centroids, int nlist);
+void dpq_flat_ivf_free(dpq_flat_ivf* ivf); /* NULL: nothing happens */
+/* dpq_ivf_stats with rows for nodes; device_bytes: offsets, row numbers and centroids. */
+int dpq_flat_ivf_get_info(const dpq_flat_ivf* ivf, dpq_ivf_stats* out);
+/* offsets_out[nlist + 1], ids_out[n_assigned] the reported ids (may be NULL: the offsets only). */
+int dpq_flat_ivf_get(const dpq_flat_ivf* ivf, int64_t* offsets_out, int32_t* ids_out);
+/* lists_out[nq][nprobe], dists_out[nq][nprobe]. */
+int dpq_flat_ivf_probe(dpq_flat_ivf* ivf, const float* queries, int nq, int nprobe, int32_t* lists_out, float* dists_out);
+int dpq_flat_ivf_search_probes(dpq_flat_ivf* ivf, const float* queries, int nq, const int32_t* probes, int nprobe, int top_k,
+                               int32_t* ids, float* dists);
+int dpq_flat_ivf_search_probes_device(dpq_flat_ivf* ivf, const float* d_queries, int nq, const int32_t* d_probes, int nprobe,
+                                      int top_k, int32_t* d_ids, float* d_dists, void* hip_stream);
+int dpq_flat_ivf_search(dpq_flat_ivf* ivf, const float* queries, int nq, int nprobe, int top_k, int32_t* ids, float* dists);
+int dpq_flat_ivf_search_device(dpq_flat_ivf* ivf, const float* d_queries, int nq, int nprobe, int top_k, int32_t* d_ids,
+                               float* d_dists, void* hip_stream);
 
 /* ---- measurement -------------------------------------------------------- */
 int dpq_profile_enable(dpq_index* idx, int on);  /* 0 off, 1 every kernel, 2 scan launches only (less event overhead) */
