@@ -308,6 +308,15 @@ SYMBOLS = [
      [_VP, _VP, ctypes.c_int, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP]),
     ("dpq_flat_ivf_search", ctypes.c_int, [_VP, _VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, _VP, _VP]),
     ("dpq_flat_ivf_search_device", ctypes.c_int, [_VP, _VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP]),
+    ("dpq_flat_ivf_create_bytes", ctypes.c_int, [_VP, _VP, c_i64, ctypes.c_int, P(_VP)]),
+    ("dpq_flat_ivf_create_bytes_device", ctypes.c_int, [_VP, _VP, c_i64, ctypes.c_int, _VP, P(_VP)]),
+    ("dpq_flat_ivf_build_bytes", ctypes.c_int, [_VP, _VP, ctypes.c_int, P(_VP)]),
+    ("dpq_flat_ivf_probe_bytes", ctypes.c_int, [_VP, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP]),
+    ("dpq_flat_ivf_search_probes_bytes", ctypes.c_int, [_VP, _VP, ctypes.c_int, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP]),
+    ("dpq_flat_ivf_search_probes_bytes_device", ctypes.c_int,
+     [_VP, _VP, ctypes.c_int, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP]),
+    ("dpq_flat_ivf_search_bytes", ctypes.c_int, [_VP, _VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, _VP, _VP]),
+    ("dpq_flat_ivf_search_bytes_device", ctypes.c_int, [_VP, _VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP]),
     ("dpq_ivf_search_filtered", ctypes.c_int, [_VP, _VP, _VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, _VP, _VP]),
     ("dpq_ivf_search_device_filtered", ctypes.c_int, [_VP, _VP, _VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP]),
     ("dpq_ivf_search_probes_filtered", ctypes.c_int,

@@ -1993,6 +1993,96 @@ class FlatIVF:
         self.close()
 
 
+class FlatIVFBytes(FlatIVF):
+    """FlatIVF over a FlatIndexU8 / FlatIndexI8 (include/deltapq_amd.h "IVF search over byte vectors"), FAISS's
+    IndexIVFScalarQuantizer with QT_8bit_direct: the probed lists are scanned on the int8 matrix cores, and an answer is,
+    bit for bit, the byte index's search_filtered under a filter of the probed lists' rows.  Queries are the index's own
+    kind of bytes (anything else is a TypeError); centroids stay float32 in the caller's units.  Squared L2 only."""
+
+    @classmethod
+    def build(cls, flat_index, centroids):
+        """Lists by the nearest centroid of every row widened to fp32, ivf_assign's labels (dpq_flat_ivf_build_bytes)."""
+        c = cls._centroids(centroids)
+        assert c.shape[1] == flat_index.D
+        h = ctypes.c_void_p()
+        check(flat_index._lib.dpq_flat_ivf_build_bytes(flat_index._h, _np_ptr(c), c.shape[0], h), "dpq_flat_ivf_build_bytes")
+        return cls(flat_index, h)
+
+    @classmethod
+    def from_labels(cls, flat_index, labels, nlist, centroids=None):
+        """FlatIVF.from_labels over a byte index (dpq_flat_ivf_create_bytes[_device])."""
+        h = ctypes.c_void_p()
+        lib = flat_index._lib
+        if isinstance(labels, np.ndarray) or not hasattr(labels, "data_ptr"):
+            a = np.ascontiguousarray(np.asarray(labels, dtype=np.int32).ravel())
+            check(lib.dpq_flat_ivf_create_bytes(flat_index._h, _np_ptr(a), a.size, int(nlist), h), "dpq_flat_ivf_create_bytes")
+        else:
+            import torch
+            assert labels.is_cuda and labels.dtype == torch.int32 and labels.is_contiguous()
+            stream = ctypes.c_void_p(torch.cuda.current_stream(labels.device).cuda_stream)
+            check(lib.dpq_flat_ivf_create_bytes_device(flat_index._h, ctypes.c_void_p(labels.data_ptr()), labels.numel(),
+                                                       int(nlist), stream, h), "dpq_flat_ivf_create_bytes_device")
+        ivf = cls(flat_index, h)
+        if centroids is not None:
+            ivf.set_centroids(centroids)
+        return ivf
+
+    def probe(self, queries, nprobe):
+        """FlatIVF.probe of the queries widened exactly to fp32 (dpq_flat_ivf_probe_bytes)."""
+        q = self._index._queries(queries)
+        lists, dists = self._out(q.shape[0], nprobe)
+        check(self._lib.dpq_flat_ivf_probe_bytes(self._h, _np_ptr(q), q.shape[0], nprobe, _np_ptr(lists), _np_ptr(dists)),
+              "dpq_flat_ivf_probe_bytes")
+        return lists, dists
+
+    def search(self, queries, nprobe, top_k):
+        """(ids int32 [nq][k], dists float32 [nq][k]) over the nprobe lists nearest to each query (dpq_flat_ivf_search_bytes)."""
+        q = self._index._queries(queries)
+        ids, dists = self._out(q.shape[0], top_k)
+        check(self._lib.dpq_flat_ivf_search_bytes(self._h, _np_ptr(q), q.shape[0], nprobe, top_k, _np_ptr(ids), _np_ptr(dists)),
+              "dpq_flat_ivf_search_bytes")
+        return ids, dists
+
+    def search_probes(self, queries, probes, top_k):
+        """search over the caller's own lists: probes int32 [nq][nprobe], -1 = padding (dpq_flat_ivf_search_probes_bytes)."""
+        q = self._index._queries(queries)
+        p = IVF._probes(probes, q.shape[0])
+        ids, dists = self._out(q.shape[0], top_k)
+        check(self._lib.dpq_flat_ivf_search_probes_bytes(self._h, _np_ptr(q), q.shape[0], _np_ptr(p), p.shape[1], top_k,
+                                                         _np_ptr(ids), _np_ptr(dists)), "dpq_flat_ivf_search_probes_bytes")
+        return ids, dists
+
+    def _torch_out(self, queries, top_k, out_ids, out_dists):
+        import torch
+        self._index._check_tensor(queries)
+        assert queries.is_cuda and queries.is_contiguous() and queries.dim() == 2 and queries.shape[1] == self._index.D
+        nq = queries.shape[0]
+        if out_ids is None:
+            out_ids = torch.empty((nq, top_k), dtype=torch.int32, device=queries.device)
+        if out_dists is None:
+            out_dists = torch.empty((nq, top_k), dtype=torch.float32, device=queries.device)
+        return nq, out_ids, out_dists, ctypes.c_void_p(torch.cuda.current_stream(queries.device).cuda_stream)
+
+    def search_torch(self, queries, nprobe, top_k, out_ids=None, out_dists=None):
+        """search on device tensors, synchronous on torch's current stream (dpq_flat_ivf_search_bytes_device)."""
+        nq, out_ids, out_dists, stream = self._torch_out(queries, top_k, out_ids, out_dists)
+        check(self._lib.dpq_flat_ivf_search_bytes_device(self._h, ctypes.c_void_p(queries.data_ptr()), nq, nprobe, top_k,
+                                                         ctypes.c_void_p(out_ids.data_ptr()),
+                                                         ctypes.c_void_p(out_dists.data_ptr()), stream),
+              "dpq_flat_ivf_search_bytes_device")
+        return out_ids, out_dists
+
+    def search_probes_torch(self, queries, probes, top_k, out_ids=None, out_dists=None):
+        """search_probes on device tensors (dpq_flat_ivf_search_probes_bytes_device)."""
+        nq, out_ids, out_dists, stream = self._torch_out(queries, top_k, out_ids, out_dists)
+        pp, nprobe = IVF._torch_probes(probes, nq)
+        check(self._lib.dpq_flat_ivf_search_probes_bytes_device(self._h, ctypes.c_void_p(queries.data_ptr()), nq, pp, nprobe,
+                                                                top_k, ctypes.c_void_p(out_ids.data_ptr()),
+                                                                ctypes.c_void_p(out_dists.data_ptr()), stream),
+              "dpq_flat_ivf_search_probes_bytes_device")
+        return out_ids, out_dists
+
+
 HALF_FORMATS = {"f16": 1, "bf16": 2}   # DPQ_HALF_F16, DPQ_HALF_BF16
 
 

@@ -1,6 +1,7 @@
-// dpq_capi_flat_ivf.cpp -- the dpq_flat_ivf_* entry points of include/deltapq_amd.h (kernels in dpq_flat_ivf.hip): inverted
-// lists over the rows of an fp32 dpq_flat handle, built on the device from labels or from centroids, and the search that
-// forms exact distances to the rows of the lists a query probes.
+// dpq_capi_flat_ivf.cpp -- the dpq_flat_ivf_* entry points of include/deltapq_amd.h (kernels in dpq_flat_ivf.hip and
+// dpq_flat_ivf_u8.hip): inverted lists over the rows of an fp32 or a byte dpq_flat handle, built on the device from labels
+// or from centroids, and the search that forms exact distances to the rows of the lists a query probes.  The fp32 entry
+// points and the *_bytes ones run the same code; `bytes` says which kind of handle and of queries a call is about.
 #include "dpq_capi_internal.h"
 #include "dpq_ivf_train.h"
 
@@ -11,9 +12,11 @@ int fivf_nlist_ok(const std::string& who, int nlist) {
     return DPQ_OK;
 }
 
-// An fp32 handle on a present device.  (The launchers that make the lists take at most 2^31 - 1 rows.)
-int fivf_enter_flat(const std::string& who, dpq_flat* f) {
-    if (f->format != dpq::kFlatF32)
+// A handle of the call's kind on a present device.  (The launchers that make the lists take at most 2^31 - 1 rows.)
+int fivf_enter_flat(const std::string& who, dpq_flat* f, bool bytes) {
+    if (bytes && f->format != dpq::kFlatU8 && f->format != dpq::kFlatI8)
+        return fail(DPQ_ERR_ARG, who + ": needs a handle of byte rows (dpq_flat_open_u8 / dpq_flat_open_i8)");
+    if (!bytes && f->format != dpq::kFlatF32)
         return fail(DPQ_ERR_ARG, who + ": needs a handle of fp32 rows (dpq_flat_open); half, byte, quantised and binary handles are not supported");
     if (f->map.get()) return fail(DPQ_ERR_ARG, who + ": a handle with an id map (dpq_flat_set_id_map) is not supported");
     if (f->n > 0x7fffffff) return fail(DPQ_ERR_ARG, who + ": the handle has too many rows");
@@ -28,6 +31,7 @@ int fivf_from_device_labels(const std::string& who, dpq_flat* f, const int32_t* 
     if (n != f->n) return fail(DPQ_ERR_ARG, who + ": n must be the handle's row count");
     std::unique_ptr<dpq_flat_ivf> v(new dpq_flat_ivf());
     v->flat = f;
+    v->bytes = f->format != dpq::kFlatF32;
     v->device = f->device;
     v->nlist = nlist;
     DevBuf<uint32_t> keys, pos, keys_out, flag;
@@ -99,7 +103,10 @@ int fivf_search_args(const std::string& who, const void* ivf, const void* querie
 }
 
 // What needs the structure's fields; then a device.
-int fivf_enter(const std::string& who, dpq_flat_ivf* v, int nprobe, bool coarse) {
+int fivf_enter(const std::string& who, dpq_flat_ivf* v, bool bytes, int nprobe, bool coarse) {
+    if (v->bytes != bytes)
+        return fail(DPQ_ERR_ARG, who + (bytes ? ": the structure is over fp32 rows: its calls are the ones without _bytes"
+                                              : ": the structure is over byte rows: its calls are the *_bytes ones"));
     if (nprobe > v->nlist) return fail(DPQ_ERR_ARG, who + ": needs 1 <= nprobe <= min(nlist, 1024)");
     if (coarse && !v->centroids.get())
         return fail(DPQ_ERR_STATE, who + ": the structure has no centroids (dpq_flat_ivf_build / dpq_flat_ivf_set_centroids)");
@@ -118,9 +125,47 @@ int fivf_probe_rows_ok(const std::string& who, const dpq_flat_ivf* v, const int3
     return DPQ_OK;
 }
 
-// Queries as the kernels read them, [nq][Dp] with zero padding.  Host form: into v->d_q.  Device form: the caller's
-// rows where they already are that (D a multiple of four, 16-byte aligned), else padded into v->d_q on `stream`.
-int fivf_queries(dpq_flat_ivf* v, const float* queries, int nq, bool device, hipStream_t stream, const float** out) {
+// A call's queries as the kernels read them.  f32 [nq][Dp] with zero padding: what the coarse step ranks the centroids by,
+// and what the fp32 scan reads.  A byte structure: i8 [nq][Dp] and norm [nq], the queries as the handle stores rows.
+struct FivfQueries {
+    const float* f32 = nullptr;
+    const int8_t* i8 = nullptr;
+    const int32_t* norm = nullptr;
+};
+
+// Byte queries [nq][D] of the handle's kind: prepared as the rows are (launch_flat_u8_prepare over the batch) and, for a
+// call with a coarse step, widened exactly to fp32 -- the caller's values, not the biased storage.  Host form: through
+// v->q_raw.
+int fivf_queries_bytes(dpq_flat_ivf* v, const void* queries, int nq, bool device, bool coarse, hipStream_t stream,
+                       FivfQueries* out) {
+    const int D = v->flat->D, Dp = v->flat->Dp;
+    const bool is_signed = v->flat->format == dpq::kFlatI8;
+    const uint8_t* raw = static_cast<const uint8_t*>(queries);
+    int rc = grow(v->q8, &v->q8_n, (size_t)nq * Dp);
+    if (!rc) rc = grow(v->qnorm, &v->qnorm_n, (size_t)nq);
+    if (!rc && !device) rc = grow(v->q_raw, &v->q_raw_n, (size_t)nq * D);
+    if (!rc && coarse) rc = grow(v->d_q, &v->q_n, (size_t)nq * Dp);
+    if (rc) return rc;
+    if (!device) {
+        DPQ_HIP(hipMemcpy(v->q_raw, queries, (size_t)nq * D, hipMemcpyHostToDevice));
+        raw = v->q_raw;
+    }
+    DPQ_HIP(dpq::launch_flat_u8_prepare(raw, nq, D, Dp, v->q8, v->qnorm, stream, is_signed));
+    if (coarse) {
+        DPQ_HIP(dpq::launch_flat_ivf_widen(raw, nq, D, D, Dp, false, is_signed, v->d_q, stream));
+        out->f32 = v->d_q;
+    }
+    out->i8 = v->q8;
+    out->norm = v->qnorm;
+    return DPQ_OK;
+}
+
+// fp32 queries [nq][D].  Host form: into v->d_q.  Device form: the caller's rows where they already are [nq][Dp] (D a
+// multiple of four, 16-byte aligned), else padded into v->d_q on `stream`.
+int fivf_queries(dpq_flat_ivf* v, const void* queries_, int nq, bool device, bool coarse, hipStream_t stream, FivfQueries* q) {
+    if (v->bytes) return fivf_queries_bytes(v, queries_, nq, device, coarse, stream, q);
+    const float* queries = static_cast<const float*>(queries_);
+    const float** out = &q->f32;
     const int D = v->flat->D, Dp = v->flat->Dp;
     if (device && D == Dp && (reinterpret_cast<uintptr_t>(queries) & 15u) == 0) {
         *out = queries;
@@ -173,18 +218,19 @@ int fivf_probe_on_device(dpq_flat_ivf* v, const float* d_q, int nq, int nprobe, 
     return DPQ_OK;
 }
 
-// Pairs a workgroup of the scan takes (DESIGN.md 5.20).
-int fivf_group_cfg() {
-    int group = dpq::kFlatIvfGroup;
+// Pairs a workgroup of the scan takes (DESIGN.md 5.20, 5.21).
+int fivf_group_cfg(bool bytes) {
+    int group = bytes ? dpq::kFlatIvfGroupU8 : dpq::kFlatIvfGroup;
     if (dev_mode())
         if (const char* e = getenv("DPQ_FLAT_IVF_GROUP")) group = std::max(1, atoi(e));  // tests and the probe script: a cap on G
     return group;
 }
 
-// The search behind its checks, all device pointers; d_q [nq][Dp].  Slices of queries: per slice the probe pre-pass, the
-// pairs sorted by list, the list scan, the merge of the pairs' answers in rounds.  Ends with the flag word read back.
-int fivf_search_on_device(dpq_flat_ivf* v, const std::string& who, const float* d_q, int nq, const int32_t* d_probes, int nprobe,
-                          int top_k, int32_t* d_ids, float* d_dists, hipStream_t stream) {
+// The search behind its checks, all device pointers; qs: the prepared queries.  Slices of queries: per slice the probe
+// pre-pass, the pairs sorted by list, the list scan of the structure's kind, the merge of the pairs' answers in rounds.
+// Ends with the flag word read back.
+int fivf_search_on_device(dpq_flat_ivf* v, const std::string& who, const FivfQueries& qs, int nq, const int32_t* d_probes,
+                          int nprobe, int top_k, int32_t* d_ids, float* d_dists, hipStream_t stream) {
     const dpq_flat* f = v->flat;
     const size_t row = (size_t)nprobe * top_k;
     const int per = (int)std::max<size_t>(1, std::min<size_t>(std::min(nq, dpq::kIvfSliceQueries), dpq::kIvfPartialBytes / (row * 8)));
@@ -219,7 +265,15 @@ int fivf_search_on_device(dpq_flat_ivf* v, const std::string& who, const float* 
     lists.offsets = v->offsets;
     lists.list_rows = v->rows;
     lists.nlist = v->nlist;
-    const int group = fivf_group_cfg();
+    dpq::FlatIvfListsU8 lists8;
+    lists8.rows = reinterpret_cast<const int8_t*>(f->rows.get() + f->rows_at);
+    lists8.norm = f->norm8;
+    lists8.Dp = f->Dp;
+    lists8.id_offset = f->id_offset;
+    lists8.offsets = v->offsets;
+    lists8.list_rows = v->rows;
+    lists8.nlist = v->nlist;
+    const int group = fivf_group_cfg(v->bytes);
     DPQ_HIP(hipMemsetAsync(v->flag, 0, sizeof(uint32_t), stream));
     for (int q0 = 0; q0 < nq; q0 += per) {
         const int m = std::min(per, nq - q0);
@@ -228,8 +282,12 @@ int fivf_search_on_device(dpq_flat_ivf* v, const std::string& who, const float* 
         DPQ_HIP(dpq::launch_flat_ivf_pairs(v->probes, n_pairs, v->nlist, v->pkeys, v->pvals, stream));
         size_t tb = v->sort_n;
         DPQ_HIP(dpq::flat_ivf_sort_pairs(v->sort_temp, &tb, v->pkeys, v->skeys, v->pvals, v->svals, n_pairs, v->nlist, stream));
-        DPQ_HIP(dpq::launch_flat_ivf_scan(lists, d_q + (size_t)q0 * f->Dp, m, nprobe, v->skeys, v->svals, top_k, group, v->part_ids,
-                                          v->part_dists, stream));
+        if (v->bytes)
+            DPQ_HIP(dpq::launch_flat_ivf_scan_u8(lists8, qs.i8 + (size_t)q0 * f->Dp, qs.norm + q0, m, nprobe, v->skeys, v->svals,
+                                                 top_k, group, v->part_ids, v->part_dists, stream));
+        else
+            DPQ_HIP(dpq::launch_flat_ivf_scan(lists, qs.f32 + (size_t)q0 * f->Dp, m, nprobe, v->skeys, v->svals, top_k, group,
+                                              v->part_ids, v->part_dists, stream));
         if ((rc = ivf_merge_rounds(v->part_ids, v->part_dists, v->tmp_ids, v->tmp_dists, nprobe, m, top_k,
                                    d_ids + (size_t)q0 * top_k, d_dists + (size_t)q0 * top_k, stream)))
             return rc;
@@ -247,27 +305,21 @@ int fivf_results_down(dpq_flat_ivf* v, int nq, int top_k, int32_t* ids, float* d
     return DPQ_OK;
 }
 
-}  // namespace
+// ---- the entry points' bodies, for either kind of handle ----------------------------------------------------------------
 
-extern "C" {
-
-int dpq_flat_ivf_create_device(dpq_flat* f, const int32_t* d_labels, int64_t n, int nlist, void* hip_stream, dpq_flat_ivf** out) {
-    return guarded([&]() -> int {
-    const std::string who = "dpq_flat_ivf_create_device";
+int fivf_create_device(const std::string& who, bool bytes, dpq_flat* f, const int32_t* d_labels, int64_t n, int nlist,
+                       void* hip_stream, dpq_flat_ivf** out) {
     if (out) *out = nullptr;
     if (!f || !d_labels || !out || n < 0) return fail(DPQ_ERR_ARG, who + ": NULL argument or n < 0");
     if (int rc = fivf_nlist_ok(who, nlist)) return rc;
-    if (int rc = fivf_enter_flat(who, f)) return rc;
+    if (int rc = fivf_enter_flat(who, f, bytes)) return rc;
     std::unique_ptr<dpq_flat_ivf> v;
     if (int rc = fivf_from_device_labels(who, f, d_labels, n, nlist, (hipStream_t)hip_stream, &v)) return rc;
     *out = v.release();
     return DPQ_OK;
-    });
 }
 
-int dpq_flat_ivf_create(dpq_flat* f, const int32_t* labels, int64_t n, int nlist, dpq_flat_ivf** out) {
-    return guarded([&]() -> int {
-    const std::string who = "dpq_flat_ivf_create";
+int fivf_create(const std::string& who, bool bytes, dpq_flat* f, const int32_t* labels, int64_t n, int nlist, dpq_flat_ivf** out) {
     if (out) *out = nullptr;
     if (!f || !labels || !out || n < 0) return fail(DPQ_ERR_ARG, who + ": NULL argument or n < 0");
     if (int rc = fivf_nlist_ok(who, nlist)) return rc;
@@ -278,7 +330,7 @@ int dpq_flat_ivf_create(dpq_flat* f, const int32_t* labels, int64_t n, int nlist
             snprintf(msg, sizeof msg, ": labels[%lld] = %d is >= nlist", (long long)i, (int)labels[i]);
             return fail(DPQ_ERR_ARG, who + msg);
         }
-    if (int rc = fivf_enter_flat(who, f)) return rc;
+    if (int rc = fivf_enter_flat(who, f, bytes)) return rc;
     DevBuf<int32_t> d_labels;
     if (int rc = d_labels.alloc((size_t)n)) return rc;
     DPQ_HIP(hipMemcpy(d_labels, labels, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
@@ -286,29 +338,140 @@ int dpq_flat_ivf_create(dpq_flat* f, const int32_t* labels, int64_t n, int nlist
     if (int rc = fivf_from_device_labels(who, f, d_labels, n, nlist, nullptr, &v)) return rc;
     *out = v.release();
     return DPQ_OK;
-    });
 }
 
-int dpq_flat_ivf_build(dpq_flat* f, const float* centroids, int nlist, dpq_flat_ivf** out) {
-    return guarded([&]() -> int {
-    const std::string who = "dpq_flat_ivf_build";
+// dpq_ivf_assign's arg-min over the handle's rows.  fp32: over its own padded rows, whose zero padding adds +0.0 to every
+// distance.  Bytes: over its rows widened to fp32 (the bias of unsigned rows undone) a chunk at a time, the scratch
+// bounded at 256 MB.
+int fivf_labels_by_centroids(dpq_flat* f, const float* d_cent, int nlist, int32_t* d_labels) {
+    if (f->format == dpq::kFlatF32) {
+        DPQ_HIP(dpq::launch_ivf_argmin(reinterpret_cast<const float*>(f->rows.get() + f->rows_at), f->n, f->Dp, d_cent, nlist, nullptr,
+                                       d_labels, nullptr, nullptr, nullptr));
+        return DPQ_OK;
+    }
+    const int64_t chunk = std::max<int64_t>(1, ((int64_t)256 << 20) / ((int64_t)f->Dp * (int64_t)sizeof(float)));
+    DevBuf<float> wide;
+    if (int rc = wide.alloc((size_t)std::min(chunk, f->n) * f->Dp)) return rc;
+    for (int64_t r0 = 0; r0 < f->n; r0 += chunk) {
+        const int64_t m = std::min(chunk, f->n - r0);
+        DPQ_HIP(dpq::launch_flat_ivf_widen(f->rows.get() + (size_t)r0 * f->Dp, m, f->D, f->Dp, f->Dp, true,
+                                           f->format == dpq::kFlatI8, wide, nullptr));
+        DPQ_HIP(dpq::launch_ivf_argmin(wide, m, f->Dp, d_cent, nlist, nullptr, d_labels + r0, nullptr, nullptr, nullptr));
+    }
+    DPQ_HIP(hipDeviceSynchronize());  // `wide` is freed on return
+    return DPQ_OK;
+}
+
+int fivf_build(const std::string& who, bool bytes, dpq_flat* f, const float* centroids, int nlist, dpq_flat_ivf** out) {
     if (out) *out = nullptr;
     if (!f || !centroids || !out) return fail(DPQ_ERR_ARG, who + ": NULL argument");
     if (int rc = fivf_nlist_ok(who, nlist)) return rc;
-    if (int rc = fivf_enter_flat(who, f)) return rc;
+    if (int rc = fivf_enter_flat(who, f, bytes)) return rc;
     DevBuf<float> d_cent;
     if (int rc = fivf_upload_centroids(f, centroids, nlist, &d_cent)) return rc;
-    // dpq_ivf_assign's arg-min over the handle's own padded rows: the zero padding adds +0.0 to every distance
     DevBuf<int32_t> d_labels;
     if (int rc = d_labels.alloc((size_t)f->n)) return rc;
-    DPQ_HIP(dpq::launch_ivf_argmin(reinterpret_cast<const float*>(f->rows.get() + f->rows_at), f->n, f->Dp, d_cent, nlist, nullptr,
-                                   d_labels, nullptr, nullptr, nullptr));
+    if (int rc = fivf_labels_by_centroids(f, d_cent, nlist, d_labels)) return rc;
     std::unique_ptr<dpq_flat_ivf> v;
     if (int rc = fivf_from_device_labels(who, f, d_labels, f->n, nlist, nullptr, &v)) return rc;
     fivf_keep_centroids(v.get(), std::move(d_cent));
     *out = v.release();
     return DPQ_OK;
-    });
+}
+
+int fivf_probe(const std::string& who, bool bytes, dpq_flat_ivf* v, const void* queries, int nq, int nprobe, int32_t* lists_out,
+               float* dists_out) {
+    if (!v || !queries || !lists_out || nq < 0) return fail(DPQ_ERR_ARG, who + ": NULL argument or nq < 0");
+    if (nprobe < 1 || nprobe > dpq::kIvfMaxProbe) return fail(DPQ_ERR_ARG, who + ": needs 1 <= nprobe <= min(nlist, 1024)");
+    if (int rc = fivf_enter(who, v, bytes, nprobe, true)) return rc;
+    if (nq == 0) return DPQ_OK;
+    FivfQueries q;
+    if (int rc = fivf_queries(v, queries, nq, false, true, nullptr, &q)) return rc;
+    if (int rc = fivf_stage(v, nq, nprobe, 0)) return rc;
+    if (int rc = fivf_probe_on_device(v, q.f32, nq, nprobe, v->d_probes, v->d_cdists, nullptr)) return rc;
+    DPQ_HIP(hipMemcpy(lists_out, v->d_probes, (size_t)nq * nprobe * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (dists_out) DPQ_HIP(hipMemcpy(dists_out, v->d_cdists, (size_t)nq * nprobe * sizeof(float), hipMemcpyDeviceToHost));
+    return DPQ_OK;
+}
+
+int fivf_search_probes_device(const std::string& who, bool bytes, dpq_flat_ivf* v, const void* d_queries, int nq,
+                              const int32_t* d_probes, int nprobe, int top_k, int32_t* d_ids, float* d_dists, void* hip_stream) {
+    if (int rc = fivf_search_args(who, v, d_queries, nq, true, d_probes, nprobe, top_k, d_ids, d_dists)) return rc;
+    if (int rc = fivf_enter(who, v, bytes, nprobe, false)) return rc;
+    if (nq == 0) return DPQ_OK;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    FivfQueries q;
+    if (int rc = fivf_queries(v, d_queries, nq, true, false, stream, &q)) return rc;
+    return fivf_search_on_device(v, who, q, nq, d_probes, nprobe, top_k, d_ids, d_dists, stream);
+}
+
+int fivf_search_probes(const std::string& who, bool bytes, dpq_flat_ivf* v, const void* queries, int nq, const int32_t* probes,
+                       int nprobe, int top_k, int32_t* ids, float* dists) {
+    if (int rc = fivf_search_args(who, v, queries, nq, true, probes, nprobe, top_k, ids, dists)) return rc;
+    if (nprobe > v->nlist) return fail(DPQ_ERR_ARG, who + ": needs 1 <= nprobe <= min(nlist, 1024)");
+    if (int rc = fivf_probe_rows_ok(who, v, probes, nq, nprobe)) return rc;
+    if (int rc = fivf_enter(who, v, bytes, nprobe, false)) return rc;
+    if (nq == 0) return DPQ_OK;
+    FivfQueries q;
+    if (int rc = fivf_queries(v, queries, nq, false, false, nullptr, &q)) return rc;
+    if (int rc = fivf_stage(v, nq, nprobe, top_k)) return rc;
+    DPQ_HIP(hipMemcpy(v->d_probes, probes, (size_t)nq * nprobe * sizeof(int32_t), hipMemcpyHostToDevice));
+    if (int rc = fivf_search_on_device(v, who, q, nq, v->d_probes, nprobe, top_k, v->d_ids, v->d_dists, nullptr)) return rc;
+    return fivf_results_down(v, nq, top_k, ids, dists);
+}
+
+int fivf_search_device(const std::string& who, bool bytes, dpq_flat_ivf* v, const void* d_queries, int nq, int nprobe, int top_k,
+                       int32_t* d_ids, float* d_dists, void* hip_stream) {
+    if (int rc = fivf_search_args(who, v, d_queries, nq, false, nullptr, nprobe, top_k, d_ids, d_dists)) return rc;
+    if (int rc = fivf_enter(who, v, bytes, nprobe, true)) return rc;
+    if (nq == 0) return DPQ_OK;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    FivfQueries q;
+    if (int rc = fivf_queries(v, d_queries, nq, true, true, stream, &q)) return rc;
+    if (int rc = fivf_stage(v, nq, nprobe, 0)) return rc;
+    if (int rc = fivf_probe_on_device(v, q.f32, nq, nprobe, v->d_probes, v->d_cdists, stream)) return rc;
+    return fivf_search_on_device(v, who, q, nq, v->d_probes, nprobe, top_k, d_ids, d_dists, stream);
+}
+
+int fivf_search(const std::string& who, bool bytes, dpq_flat_ivf* v, const void* queries, int nq, int nprobe, int top_k,
+                int32_t* ids, float* dists) {
+    if (int rc = fivf_search_args(who, v, queries, nq, false, nullptr, nprobe, top_k, ids, dists)) return rc;
+    if (int rc = fivf_enter(who, v, bytes, nprobe, true)) return rc;
+    if (nq == 0) return DPQ_OK;
+    FivfQueries q;
+    if (int rc = fivf_queries(v, queries, nq, false, true, nullptr, &q)) return rc;
+    if (int rc = fivf_stage(v, nq, nprobe, top_k)) return rc;
+    if (int rc = fivf_probe_on_device(v, q.f32, nq, nprobe, v->d_probes, v->d_cdists, nullptr)) return rc;
+    if (int rc = fivf_search_on_device(v, who, q, nq, v->d_probes, nprobe, top_k, v->d_ids, v->d_dists, nullptr)) return rc;
+    return fivf_results_down(v, nq, top_k, ids, dists);
+}
+
+}  // namespace
+
+extern "C" {
+
+int dpq_flat_ivf_create_device(dpq_flat* f, const int32_t* d_labels, int64_t n, int nlist, void* hip_stream, dpq_flat_ivf** out) {
+    return guarded([&]() -> int { return fivf_create_device("dpq_flat_ivf_create_device", false, f, d_labels, n, nlist, hip_stream, out); });
+}
+
+int dpq_flat_ivf_create_bytes_device(dpq_flat* f, const int32_t* d_labels, int64_t n, int nlist, void* hip_stream, dpq_flat_ivf** out) {
+    return guarded([&]() -> int { return fivf_create_device("dpq_flat_ivf_create_bytes_device", true, f, d_labels, n, nlist, hip_stream, out); });
+}
+
+int dpq_flat_ivf_create(dpq_flat* f, const int32_t* labels, int64_t n, int nlist, dpq_flat_ivf** out) {
+    return guarded([&]() -> int { return fivf_create("dpq_flat_ivf_create", false, f, labels, n, nlist, out); });
+}
+
+int dpq_flat_ivf_create_bytes(dpq_flat* f, const int32_t* labels, int64_t n, int nlist, dpq_flat_ivf** out) {
+    return guarded([&]() -> int { return fivf_create("dpq_flat_ivf_create_bytes", true, f, labels, n, nlist, out); });
+}
+
+int dpq_flat_ivf_build(dpq_flat* f, const float* centroids, int nlist, dpq_flat_ivf** out) {
+    return guarded([&]() -> int { return fivf_build("dpq_flat_ivf_build", false, f, centroids, nlist, out); });
+}
+
+int dpq_flat_ivf_build_bytes(dpq_flat* f, const float* centroids, int nlist, dpq_flat_ivf** out) {
+    return guarded([&]() -> int { return fivf_build("dpq_flat_ivf_build_bytes", true, f, centroids, nlist, out); });
 }
 
 int dpq_flat_ivf_set_centroids(dpq_flat_ivf* v, const float* centroids, int nlist) {
@@ -359,83 +522,49 @@ int dpq_flat_ivf_get(const dpq_flat_ivf* v, int64_t* offsets_out, int32_t* ids_o
 }
 
 int dpq_flat_ivf_probe(dpq_flat_ivf* v, const float* queries, int nq, int nprobe, int32_t* lists_out, float* dists_out) {
-    return guarded([&]() -> int {
-    const std::string who = "dpq_flat_ivf_probe";
-    if (!v || !queries || !lists_out || nq < 0) return fail(DPQ_ERR_ARG, who + ": NULL argument or nq < 0");
-    if (nprobe < 1 || nprobe > dpq::kIvfMaxProbe) return fail(DPQ_ERR_ARG, who + ": needs 1 <= nprobe <= min(nlist, 1024)");
-    if (int rc = fivf_enter(who, v, nprobe, true)) return rc;
-    if (nq == 0) return DPQ_OK;
-    const float* d_q = nullptr;
-    if (int rc = fivf_queries(v, queries, nq, false, nullptr, &d_q)) return rc;
-    if (int rc = fivf_stage(v, nq, nprobe, 0)) return rc;
-    if (int rc = fivf_probe_on_device(v, d_q, nq, nprobe, v->d_probes, v->d_cdists, nullptr)) return rc;
-    DPQ_HIP(hipMemcpy(lists_out, v->d_probes, (size_t)nq * nprobe * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (dists_out) DPQ_HIP(hipMemcpy(dists_out, v->d_cdists, (size_t)nq * nprobe * sizeof(float), hipMemcpyDeviceToHost));
-    return DPQ_OK;
-    });
+    return guarded([&]() -> int { return fivf_probe("dpq_flat_ivf_probe", false, v, queries, nq, nprobe, lists_out, dists_out); });
 }
 
-int dpq_flat_ivf_search_probes_device(dpq_flat_ivf* v, const float* d_queries, int nq, const int32_t* d_probes, int nprobe,
-                                      int top_k, int32_t* d_ids, float* d_dists, void* hip_stream) {
-    return guarded([&]() -> int {
-    const std::string who = "dpq_flat_ivf_search_probes_device";
-    if (int rc = fivf_search_args(who, v, d_queries, nq, true, d_probes, nprobe, top_k, d_ids, d_dists)) return rc;
-    if (int rc = fivf_enter(who, v, nprobe, false)) return rc;
-    if (nq == 0) return DPQ_OK;
-    hipStream_t stream = (hipStream_t)hip_stream;
-    const float* d_q = nullptr;
-    if (int rc = fivf_queries(v, d_queries, nq, true, stream, &d_q)) return rc;
-    return fivf_search_on_device(v, who, d_q, nq, d_probes, nprobe, top_k, d_ids, d_dists, stream);
-    });
+int dpq_flat_ivf_probe_bytes(dpq_flat_ivf* v, const void* queries, int nq, int nprobe, int32_t* lists_out, float* dists_out) {
+    return guarded([&]() -> int { return fivf_probe("dpq_flat_ivf_probe_bytes", true, v, queries, nq, nprobe, lists_out, dists_out); });
 }
 
-int dpq_flat_ivf_search_probes(dpq_flat_ivf* v, const float* queries, int nq, const int32_t* probes, int nprobe, int top_k,
-                               int32_t* ids, float* dists) {
-    return guarded([&]() -> int {
-    const std::string who = "dpq_flat_ivf_search_probes";
-    if (int rc = fivf_search_args(who, v, queries, nq, true, probes, nprobe, top_k, ids, dists)) return rc;
-    if (nprobe > v->nlist) return fail(DPQ_ERR_ARG, who + ": needs 1 <= nprobe <= min(nlist, 1024)");
-    if (int rc = fivf_probe_rows_ok(who, v, probes, nq, nprobe)) return rc;
-    if (int rc = fivf_enter(who, v, nprobe, false)) return rc;
-    if (nq == 0) return DPQ_OK;
-    const float* d_q = nullptr;
-    if (int rc = fivf_queries(v, queries, nq, false, nullptr, &d_q)) return rc;
-    if (int rc = fivf_stage(v, nq, nprobe, top_k)) return rc;
-    DPQ_HIP(hipMemcpy(v->d_probes, probes, (size_t)nq * nprobe * sizeof(int32_t), hipMemcpyHostToDevice));
-    if (int rc = fivf_search_on_device(v, who, d_q, nq, v->d_probes, nprobe, top_k, v->d_ids, v->d_dists, nullptr)) return rc;
-    return fivf_results_down(v, nq, top_k, ids, dists);
-    });
+int dpq_flat_ivf_search_probes_device(dpq_flat_ivf* v, const float* d_queries, int nq, const int32_t* d_probes, int nprobe, int top_k, int32_t* d_ids,
+        float* d_dists, void* hip_stream) {
+    return guarded([&]() -> int { return fivf_search_probes_device("dpq_flat_ivf_search_probes_device", false, v, d_queries, nq, d_probes, nprobe, top_k, d_ids, d_dists, hip_stream); });
 }
 
-int dpq_flat_ivf_search_device(dpq_flat_ivf* v, const float* d_queries, int nq, int nprobe, int top_k, int32_t* d_ids,
-                               float* d_dists, void* hip_stream) {
-    return guarded([&]() -> int {
-    const std::string who = "dpq_flat_ivf_search_device";
-    if (int rc = fivf_search_args(who, v, d_queries, nq, false, nullptr, nprobe, top_k, d_ids, d_dists)) return rc;
-    if (int rc = fivf_enter(who, v, nprobe, true)) return rc;
-    if (nq == 0) return DPQ_OK;
-    hipStream_t stream = (hipStream_t)hip_stream;
-    const float* d_q = nullptr;
-    if (int rc = fivf_queries(v, d_queries, nq, true, stream, &d_q)) return rc;
-    if (int rc = fivf_stage(v, nq, nprobe, 0)) return rc;
-    if (int rc = fivf_probe_on_device(v, d_q, nq, nprobe, v->d_probes, v->d_cdists, stream)) return rc;
-    return fivf_search_on_device(v, who, d_q, nq, v->d_probes, nprobe, top_k, d_ids, d_dists, stream);
-    });
+int dpq_flat_ivf_search_probes_bytes_device(dpq_flat_ivf* v, const void* d_queries, int nq, const int32_t* d_probes, int nprobe, int top_k, int32_t* d_ids,
+        float* d_dists, void* hip_stream) {
+    return guarded([&]() -> int { return fivf_search_probes_device("dpq_flat_ivf_search_probes_bytes_device", true, v, d_queries, nq, d_probes, nprobe, top_k, d_ids, d_dists, hip_stream); });
+}
+
+int dpq_flat_ivf_search_probes(dpq_flat_ivf* v, const float* queries, int nq, const int32_t* probes, int nprobe, int top_k, int32_t* ids,
+        float* dists) {
+    return guarded([&]() -> int { return fivf_search_probes("dpq_flat_ivf_search_probes", false, v, queries, nq, probes, nprobe, top_k, ids, dists); });
+}
+
+int dpq_flat_ivf_search_probes_bytes(dpq_flat_ivf* v, const void* queries, int nq, const int32_t* probes, int nprobe, int top_k, int32_t* ids,
+        float* dists) {
+    return guarded([&]() -> int { return fivf_search_probes("dpq_flat_ivf_search_probes_bytes", true, v, queries, nq, probes, nprobe, top_k, ids, dists); });
+}
+
+int dpq_flat_ivf_search_device(dpq_flat_ivf* v, const float* d_queries, int nq, int nprobe, int top_k, int32_t* d_ids, float* d_dists,
+        void* hip_stream) {
+    return guarded([&]() -> int { return fivf_search_device("dpq_flat_ivf_search_device", false, v, d_queries, nq, nprobe, top_k, d_ids, d_dists, hip_stream); });
+}
+
+int dpq_flat_ivf_search_bytes_device(dpq_flat_ivf* v, const void* d_queries, int nq, int nprobe, int top_k, int32_t* d_ids, float* d_dists,
+        void* hip_stream) {
+    return guarded([&]() -> int { return fivf_search_device("dpq_flat_ivf_search_bytes_device", true, v, d_queries, nq, nprobe, top_k, d_ids, d_dists, hip_stream); });
 }
 
 int dpq_flat_ivf_search(dpq_flat_ivf* v, const float* queries, int nq, int nprobe, int top_k, int32_t* ids, float* dists) {
-    return guarded([&]() -> int {
-    const std::string who = "dpq_flat_ivf_search";
-    if (int rc = fivf_search_args(who, v, queries, nq, false, nullptr, nprobe, top_k, ids, dists)) return rc;
-    if (int rc = fivf_enter(who, v, nprobe, true)) return rc;
-    if (nq == 0) return DPQ_OK;
-    const float* d_q = nullptr;
-    if (int rc = fivf_queries(v, queries, nq, false, nullptr, &d_q)) return rc;
-    if (int rc = fivf_stage(v, nq, nprobe, top_k)) return rc;
-    if (int rc = fivf_probe_on_device(v, d_q, nq, nprobe, v->d_probes, v->d_cdists, nullptr)) return rc;
-    if (int rc = fivf_search_on_device(v, who, d_q, nq, v->d_probes, nprobe, top_k, v->d_ids, v->d_dists, nullptr)) return rc;
-    return fivf_results_down(v, nq, top_k, ids, dists);
-    });
+    return guarded([&]() -> int { return fivf_search("dpq_flat_ivf_search", false, v, queries, nq, nprobe, top_k, ids, dists); });
+}
+
+int dpq_flat_ivf_search_bytes(dpq_flat_ivf* v, const void* queries, int nq, int nprobe, int top_k, int32_t* ids, float* dists) {
+    return guarded([&]() -> int { return fivf_search("dpq_flat_ivf_search_bytes", true, v, queries, nq, nprobe, top_k, ids, dists); });
 }
 
 }  // extern "C"

@@ -230,7 +230,7 @@ struct dpq_ivf {
     size_t r_thr_n = 0, r_pool_n = 0, r_sorted_n = 0, r_counts_n = 0, r_offs_n = 0, r_qoffs_n = 0;
 };
 
-// Inverted lists over the rows of one fp32 dpq_flat handle (dpq_flat_ivf_*, dpq_capi_flat_ivf.cpp): row numbers into the
+// Inverted lists over the rows of one fp32 or byte dpq_flat handle (dpq_flat_ivf_*, dpq_capi_flat_ivf.cpp): row numbers into the
 // handle's own rows, and the workspace every search on it works in.
 struct dpq_flat_ivf {
     dpq_flat* flat = nullptr;       // the handle it was made on; freed before dpq_flat_close
@@ -255,6 +255,13 @@ struct dpq_flat_ivf {
     DevBuf<int32_t> d_probes, d_ids;         // ... probes, ids
     size_t probes_n = 0, pairs_n = 0, sort_n = 0, part_ids_n = 0, part_dists_n = 0, tmp_ids_n = 0, tmp_dists_n = 0, keys_n = 0,
            state_n = 0, q_n = 0, dists_n = 0, cdists_n = 0, dprobes_n = 0, ids_n = 0;
+    // a structure over a byte handle (dpq_flat_ivf_*_bytes): the host forms' queries as given; a call's queries as the
+    // handle stores rows, [nq][Dp] int8 with their norms (d_q then holds them widened to fp32, for the coarse step)
+    bool bytes = false;
+    DevBuf<uint8_t> q_raw;
+    DevBuf<int8_t> q8;
+    DevBuf<int32_t> qnorm;
+    size_t q_raw_n = 0, q8_n = 0, qnorm_n = 0;
 };
 
 uint64_t next_index_serial();  // dpq_capi.cpp: one counter for the process

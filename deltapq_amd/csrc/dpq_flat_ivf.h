@@ -1,6 +1,7 @@
 // dpq_flat_ivf.h -- launch interface of the inverted-list scan over raw fp32 rows (dpq_flat_ivf.hip): exact distances of
 // the queries to the rows of the lists they probe, a running top-k per (query, probed list) (include/deltapq_amd.h "IVF
-// search over raw vectors").  The lists are row numbers into a dpq_flat handle's own padded rows; they
+// search over raw vectors"), and of its sibling over byte rows on the int8 matrix cores
+// (dpq_flat_ivf_u8.hip, "IVF search over byte vectors").  The lists are row numbers into a dpq_flat handle's own padded rows; they
 // come from dpq_ivf.h's launch_ivf_label_keys and ivf_scan_and_sort, the probe rows from its launch_ivf_probes.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -50,5 +51,38 @@ struct FlatIvfLists {
 hipError_t launch_flat_ivf_scan(const FlatIvfLists& lists, const float* d_queries, int nq, int nprobe, const uint32_t* d_skeys,
                                 const uint32_t* d_svals, int top_k, int group, int32_t* d_part_ids, float* d_part_dists,
                                 hipStream_t stream);
+
+// ---- byte rows (dpq_flat_ivf_u8.hip) -------------------------------------------------------------------------------
+constexpr int kFlatIvfGroupU8 = 8;  // the byte scan's shipped group: the fastest measured at nprobe 16
+
+// flat_ivf_group for the byte scan, whose LDS beside the buffers is the stretch's queries [16][Dp + 16] bytes and the
+// row numbers.
+int flat_ivf_group_u8(int top_k, int Dp, int group);
+
+// What the byte scan runs over: a byte base's rows [n][Dp] int8 (dpq_flat.h "byte vectors": biased where the data are
+// unsigned, padded with zeros, Dp % 32 == 0, 16-byte aligned) and their int32 norms [n]; the lists as in FlatIvfLists.
+struct FlatIvfListsU8 {
+    const int8_t* rows = nullptr;
+    const int32_t* norm = nullptr;
+    int Dp = 0;
+    int64_t id_offset = 0;
+    const int64_t* offsets = nullptr;
+    const uint32_t* list_rows = nullptr;
+    int nlist = 0;
+};
+
+// launch_flat_ivf_scan over byte rows.  d_queries [nq][Dp] int8 and d_qnorm [nq]: the queries as the rows are stored,
+// launch_flat_u8_prepare's output.  The distance of (row, query) is norm[row] + qnorm[query] - 2 * (their int8 dot
+// product) in int32 -- the exact sum of (v[d] - q[d])^2 -- converted once to fp32, round to nearest even.  The same pairs,
+// the same output rows, the same order and padding; the answer does not depend on the group.
+hipError_t launch_flat_ivf_scan_u8(const FlatIvfListsU8& lists, const int8_t* d_queries, const int32_t* d_qnorm, int nq,
+                                   int nprobe, const uint32_t* d_skeys, const uint32_t* d_svals, int top_k, int group,
+                                   int32_t* d_part_ids, float* d_part_dists, hipStream_t stream);
+
+// Bytes -> the fp32 values they stand for, d_out [rows][Dp] padded with zeros.  d_in [rows][in_stride] bytes, the first D
+// of a row read.  is_signed: int8 values.  stored: a byte base's rows, whose unsigned values are biased (undone here);
+// otherwise the caller's bytes as they are.
+hipError_t launch_flat_ivf_widen(const void* d_in, int64_t rows, int D, int in_stride, int Dp, bool stored, bool is_signed,
+                                 float* d_out, hipStream_t stream);
 
 }  // namespace dpq

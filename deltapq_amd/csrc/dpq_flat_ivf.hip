@@ -16,7 +16,8 @@
 //                          last.  Behind the last slice a key below its pair's threshold is appended to the pair's
 //                          buffer of 2 P2 keys by an LDS atomic on the pair's count.  When a buffer could overflow on
 //                          the next tile, the buffers of the stretch are sorted side by side (one bitonic network, the
-//                          same barriers for all), cut to top_k, and the thresholds become the k-th keys.
+//                          same barriers for all), cut to top_k, and the thresholds become the k-th keys
+//                          (dpq_flat_ivf_device.h: the sink is shared with the byte scan, dpq_flat_ivf_u8.hip).
 #include "dpq_flat_ivf.h"
 
 #include <hipcub/hipcub.hpp>
@@ -25,6 +26,7 @@
 #include <atomic>
 
 #include "dpq_flat.h"
+#include "dpq_flat_ivf_device.h"
 #include "dpq_ivf.h"
 
 namespace dpq {
@@ -36,7 +38,6 @@ constexpr int RS = TR + 4;  // floats between two dimensions of the row tile: 16
 constexpr size_t kTileBytes = (size_t)SD * RS * 4 + (size_t)SD * GM * 4 + (size_t)TR * 4;  // rows, queries, row numbers
 constexpr size_t kLdsBytes = 160 * 1024;
 constexpr size_t kStaticBytes = 512;  // the run's words below, rounded up
-constexpr uint32_t kNoRow = 0xffffffffu;
 
 __global__ __launch_bounds__(256) void flat_ivf_pairs_kernel(const int32_t* __restrict__ probes, int64_t n, int nlist,
                                                              uint32_t* __restrict__ keys, uint32_t* __restrict__ vals) {
@@ -45,28 +46,6 @@ __global__ __launch_bounds__(256) void flat_ivf_pairs_kernel(const int32_t* __re
     const int32_t l = probes[i];
     keys[i] = (l >= 0 && l < nlist) ? (uint32_t)l : (uint32_t)nlist;
     vals[i] = (uint32_t)i;
-}
-
-// Sorts nb buffers of n keys each (n a power of two >= 2), `stride` keys apart, ascending: ivf_bitonic's network over
-// every buffer at once.  Every thread of the workgroup calls it.  Ends behind a barrier.
-__device__ __forceinline__ void sort_buffers(uint64_t* buf, int nb, int n, int stride, int tid) {
-    const int half = n >> 1, hs = __ffs(half) - 1, total = nb * half;
-    for (int k = 2; k <= n; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int t = tid; t < total; t += 256) {
-                const int u = t & (half - 1);
-                uint64_t* b = buf + (size_t)(t >> hs) * stride;
-                const int i = ((u & ~(j - 1)) << 1) | (u & (j - 1));
-                const int l = i | j;
-                const uint64_t x = b[i], y = b[l];
-                const bool up = (i & k) == 0;
-                if ((x > y) == up) {
-                    b[i] = y;
-                    b[l] = x;
-                }
-            }
-            __syncthreads();
-        }
 }
 
 // The rows' part of slice d0 for this thread: float4 c of row r = idx >> 3, idx = tid + 256 i.  A row beyond the list's
@@ -201,58 +180,20 @@ __global__ __launch_bounds__(256) void flat_ivf_scan_kernel(const float* __restr
                 }
             }
             __syncthreads();
-            if (base + TR < hi) {
-                uint32_t mx = 0u;
-                for (int p = 0; p < nqs; ++p) mx = max(mx, s_cnt[p]);
-                if (mx + TR > (uint32_t)cap) {  // a buffer has no room for the next tile: sort, keep top_k, lower the thresholds
-                    int n = 2;
-                    while ((uint32_t)n < mx) n <<= 1;
-                    for (int p = 0; p < nqs; ++p)
-                        for (int i = (int)s_cnt[p] + tid; i < n; i += 256) buf[(size_t)p * cap + i] = kFlatNoKey;
-                    __syncthreads();
-                    sort_buffers(buf, nqs, n, cap, tid);
-                    if (tid < nqs) {
-                        const uint32_t c = s_cnt[tid];
-                        if (c >= (uint32_t)top_k) s_thr[tid] = buf[(size_t)tid * cap + top_k - 1];  // ids are unique in a list: the
-                        s_cnt[tid] = min(c, (uint32_t)top_k);                                      // strict test loses nothing
-                    }
-                }
-            }
+            if (base + TR < hi) sink_make_room(buf, s_cnt, s_thr, nqs, cap, top_k, tid);
         }
-        if (hi > lo) {
-            uint32_t mx = 0u;
-            for (int p = 0; p < nqs; ++p) mx = max(mx, s_cnt[p]);  // (behind the last tile's closing barrier)
-            int n = 2;
-            while ((uint32_t)n < mx) n <<= 1;
-            for (int p = 0; p < nqs; ++p)
-                for (int i = (int)s_cnt[p] + tid; i < n; i += 256) buf[(size_t)p * cap + i] = kFlatNoKey;
-            __syncthreads();
-            sort_buffers(buf, nqs, n, cap, tid);
-        }
+        if (hi > lo) sink_sort(buf, s_cnt, nqs, cap, tid);  // (behind the last tile's closing barrier)
         // the stretch's answers: pair i = q * nprobe + j goes to row j * nq + q.  A padding pair, or an empty list: padding
         for (int p = 0; p < nqs; ++p) {
             const uint32_t q = s_q[s + p], j = s_val[s + p] - q * (uint32_t)nprobe;
             int32_t* out_i = part_ids + ((size_t)j * nq + q) * top_k;
             float* out_d = part_dists + ((size_t)j * nq + q) * top_k;
-            const uint32_t cnt = hi > lo ? s_cnt[p] : 0u;
-            for (int r = tid; r < top_k; r += 256) {
-                const uint64_t key = (uint32_t)r < cnt ? buf[(size_t)p * cap + r] : kFlatNoKey;
-                out_i[r] = key != kFlatNoKey ? (int32_t)(key & 0xffffffffu) : -1;
-                out_d[r] = key != kFlatNoKey ? __uint_as_float((uint32_t)(key >> 32)) : INFINITY;
-            }
+            sink_emit(buf + (size_t)p * cap, hi > lo ? s_cnt[p] : 0u, top_k, out_i, out_d, tid);
         }
         __syncthreads();  // the next stretch starts the counts and the buffers over
         s = e;
     }
 }
-
-int pow2_at_least(int v) {
-    int p = 1;
-    while (p < v) p <<= 1;
-    return p;
-}
-
-int scan_cap(int top_k) { return 2 * pow2_at_least(std::max(top_k, 256)); }
 
 // hipFuncSetAttribute is per device
 template <int QPL>

@@ -60,6 +60,10 @@
  *   (none: FAISS's IndexIVFFlat)                dpq_flat_ivf_create[_device] / dpq_flat_ivf_build, dpq_flat_ivf_probe /
  *                                                 dpq_flat_ivf_search[_device] / dpq_flat_ivf_search_probes[_device]
  *                                                 (lists over a dpq_flat handle's rows, exact distances in the probed lists)
+ *   (none: FAISS's IndexIVFScalarQuantizer      dpq_flat_ivf_create_bytes[_device] / dpq_flat_ivf_build_bytes,
+ *     with QT_8bit_direct)                        dpq_flat_ivf_probe_bytes / dpq_flat_ivf_search_bytes[_device] /
+ *                                                 dpq_flat_ivf_search_probes_bytes[_device]
+ *                                                 (the same over a byte handle; the list scan on the int8 matrix cores)
  *   (none: FAISS's IndexFlatIP: search, an      dpq_flat_search_ip / dpq_flat_search_filtered_ip /
  *     IDSelector, range_search; re-ranking by     dpq_flat_range_search_ip / dpq_flat_rerank_ip[_device],
  *     inner product)                              dpq_merge_topk_ip_host
@@ -1594,7 +1598,7 @@ int dpq_write_vecs(const char* path, const float* vectors, int64_t n, int D);
  * FAISS's IndexIVFFlat.  NO REFERENCE COUNTERPART.  A dpq_flat_ivf holds nlist inverted lists over the rows of ONE open
  * dpq_flat handle; a query forms exact distances to the rows of the lists it probes only.
  *   Formats    fp32 rows (dpq_flat_open) only.  Half, byte, quantised and binary handles, and a handle with an id map, are
- *           DPQ_ERR_ARG.  Squared L2 only: no inner product, no filter, no range search, no shards and no CLI task yet.
+ *           DPQ_ERR_ARG (byte handles have calls of their own: "IVF search over byte vectors" below).  Squared L2 only: no inner product, no filter, no range search, no shards and no CLI task yet.
  *   Ownership  The structure is bound to the handle it was made on and is freed (dpq_flat_ivf_free) BEFORE
  *           dpq_flat_close of that handle; both are used from one thread.
  *   Memory  No row is copied: a list is the ascending ROW NUMBERS of its members in the handle's own padded rows.
@@ -1643,6 +1647,41 @@ int dpq_flat_ivf_search_probes_device(dpq_flat_ivf* ivf, const float* d_queries,
 int dpq_flat_ivf_search(dpq_flat_ivf* ivf, const float* queries, int nq, int nprobe, int top_k, int32_t* ids, float* dists);
 int dpq_flat_ivf_search_device(dpq_flat_ivf* ivf, const float* d_queries, int nq, int nprobe, int top_k, int32_t* d_ids,
                                float* d_dists, void* hip_stream);
+
+/* ---- IVF search over byte vectors: the list scan on the int8 matrix cores ----------
+ * FAISS's IndexIVFScalarQuantizer with QT_8bit_direct.  NO REFERENCE COUNTERPART.  The structure above over a BYTE handle
+ * (dpq_flat_open_u8 / dpq_flat_open_i8): the same lists of row numbers, no row copied, a quarter of the fp32 handle's
+ * device memory; the scan of the probed lists runs on v_mfma_i32_16x16x64_i8.
+ *   Entry points  dpq_flat_ivf_create / _create_device / _build keep refusing every handle that is not fp32; a byte handle
+ *           has the *_bytes calls below, and they accept byte handles ONLY: an fp32, half, quantised or binary handle, or
+ *           a handle with an id map, is DPQ_ERR_ARG.  There is ONE set for both kinds of bytes, not a _u8 and an _i8 copy
+ *           of each: `queries` are [nq][D] bytes OF THE HANDLE'S KIND -- uint8 on a dpq_flat_open_u8 handle, int8 on a
+ *           dpq_flat_open_i8 one -- which the structure knows from its handle.
+ *           dpq_flat_ivf_set_centroids, _get_info, _get and _free serve both kinds of structure unchanged.  The searches do
+ *           not: a *_bytes search or probe on a structure over fp32 rows, and an fp32 one on a structure over byte rows, is
+ *           DPQ_ERR_ARG, never a read of the wrong type.
+ *   Centroids  fp32 [nlist][D] in the caller's units (0..255, or -128..127), as above.  dpq_flat_ivf_build_bytes labels a row
+ *           as dpq_ivf_assign labels it widened exactly to fp32; dpq_flat_ivf_probe_bytes ranks the centroids by
+ *           dpq_flat_ivf_probe's rule over the queries widened exactly to fp32 -- the caller's values, not the stored ones.
+ *   Answer  For query q exactly what dpq_flat_search_filtered_u8 / _i8 returns under a filter that allows the union of the
+ *           probed lists, bit for bit: distance = (float)(int32) sum (v[d] - q[d])^2, one round-to-nearest-even
+ *           conversion; reported id = row + id_offset; order by (distance bits, id); padding -1 / +inf; a repeated probe
+ *           counts once, a negative probe is padding, an entry >= nlist is DPQ_ERR_ARG as above.
+ *   Limits  The byte handle's (D <= 2048) and the structure's above (nlist <= 65536, nprobe <= min(nlist, 1024),
+ *           top_k <= 2048, fewer than 2^31 rows).  Squared L2 only: no inner product, no filter, no range search, no
+ *           shards, no CLI task.  State and ownership as above. */
+int dpq_flat_ivf_create_bytes(dpq_flat* flat, const int32_t* labels, int64_t n, int nlist, dpq_flat_ivf** out);
+int dpq_flat_ivf_create_bytes_device(dpq_flat* flat, const int32_t* d_labels, int64_t n, int nlist, void* hip_stream,
+                                     dpq_flat_ivf** out);
+int dpq_flat_ivf_build_bytes(dpq_flat* flat, const float* centroids, int nlist, dpq_flat_ivf** out);
+int dpq_flat_ivf_probe_bytes(dpq_flat_ivf* ivf, const void* queries, int nq, int nprobe, int32_t* lists_out, float* dists_out);
+int dpq_flat_ivf_search_probes_bytes(dpq_flat_ivf* ivf, const void* queries, int nq, const int32_t* probes, int nprobe,
+                                     int top_k, int32_t* ids, float* dists);
+int dpq_flat_ivf_search_probes_bytes_device(dpq_flat_ivf* ivf, const void* d_queries, int nq, const int32_t* d_probes,
+                                            int nprobe, int top_k, int32_t* d_ids, float* d_dists, void* hip_stream);
+int dpq_flat_ivf_search_bytes(dpq_flat_ivf* ivf, const void* queries, int nq, int nprobe, int top_k, int32_t* ids, float* dists);
+int dpq_flat_ivf_search_bytes_device(dpq_flat_ivf* ivf, const void* d_queries, int nq, int nprobe, int top_k, int32_t* d_ids,
+                                     float* d_dists, void* hip_stream);
 
 /* ---- measurement -------------------------------------------------------- */
 int dpq_profile_enable(dpq_index* idx, int on);  /* 0 off, 1 every kernel, 2 scan launches only (less event overhead) */
