@@ -1,6 +1,6 @@
 """IVF search over raw vectors (include/deltapq_amd.h "IVF search over raw vectors").  The reference is the numpy
-restatement below -- fp32 subtract and square, a float64 sum in dimension order, one cast -- restricted to the union of
-the probed lists.  The GPU meets it bit for bit, for every group size G of the scan."""
+restatement of tests/_flat_ivf_restatement.py -- fp32 subtract and square, a float64 sum in dimension order, one cast --
+restricted to the union of the probed lists.  The GPU meets it bit for bit, for every group size G of the scan."""
 import ctypes
 import os
 import re
@@ -8,6 +8,8 @@ import subprocess
 
 import numpy as np
 import pytest
+
+from _flat_ivf_restatement import distances, lists_from_labels, same, search
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ERR_ARG, ERR_STATE = -1, -7
@@ -18,43 +20,6 @@ F32, F64 = np.float32, np.float64
 # lists 0 .. 11: the row-tile edge; 5 is long with its nearest rows last; 6 .. 8 are short and far; row 0 is in no list
 LENGTHS = (0, 1, 255, 256, 257, 1500, 40, 30, 20, 300, 300, 300)
 NLIST, NQ = len(LENGTHS), 50
-
-
-def distances(rows, q):
-    """float32 [n]: t = v[d] - q[d] and s = t * t rounded in fp32, summed in float64 in ascending d, cast once."""
-    t = (rows - q).astype(F32)
-    s = (t * t).astype(F32)
-    acc = np.zeros(len(rows), dtype=F64)
-    for d in range(rows.shape[1]):
-        acc += s[:, d]
-    return acc.astype(F32)
-
-
-def lists_from_labels(labels, nlist):
-    """(offsets int64 [nlist + 1], rows int64 [n_assigned]): the rows of a list ascend."""
-    key = np.where(labels < 0, nlist, labels)
-    rows = np.argsort(key, kind="stable")[:int((labels >= 0).sum())]
-    return np.concatenate([[0], np.cumsum(np.bincount(key, minlength=nlist + 1)[:nlist])]).astype(np.int64), rows
-
-
-def search(c, qs, probes, top_k, id_offset=0):
-    """(ids int32 [nq][top_k], dists float32 [nq][top_k]) by key (distance bits, id), padded with -1 / +inf."""
-    ids = np.full((len(qs), top_k), -1, dtype=np.int32)
-    dists = np.full((len(qs), top_k), np.inf, dtype=F32)
-    for i, (q, row) in enumerate(zip(qs, probes)):
-        keys = [np.zeros(0, dtype=np.uint64)]
-        for l in dict.fromkeys(int(p) for p in row if p >= 0):                     # padding skipped, a repeat counts once
-            r = c["rows"][c["offsets"][l]:c["offsets"][l + 1]]
-            d = distances(c["base"][r], q)
-            keys.append((d.view(np.uint32).astype(np.uint64) << np.uint64(32)) | (r + id_offset).astype(np.uint64))
-        keys = np.sort(np.concatenate(keys))[:top_k]
-        ids[i, :len(keys)] = (keys & np.uint64(0xffffffff)).astype(np.int32)
-        dists[i, :len(keys)] = (keys >> np.uint64(32)).astype(np.uint32).view(F32)
-    return ids, dists
-
-
-def same(got, want):
-    return np.array_equal(got[0], want[0]) and np.array_equal(got[1].view(np.uint32), want[1].view(np.uint32))
 
 
 _cases = {}

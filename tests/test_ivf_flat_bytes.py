@@ -1,6 +1,7 @@
 """IVF search over byte vectors (include/deltapq_amd.h "IVF search over byte vectors").  The reference is
-the numpy restatement below -- the int64 sum of (v - q)^2 over the rows of the probed lists, cast once to float32, the
-keys sorted.  It is exact, so there is no tolerance: ids and distance bits are equal, for every group size G."""
+the numpy restatement of tests/_flat_ivf_restatement.py -- the int64 sum of (v - q)^2 over the rows of the probed lists,
+cast once to float32, the keys sorted.  It is exact, so there is no tolerance: ids and distance bits are equal, for every
+group size G."""
 import ctypes
 import os
 import re
@@ -8,6 +9,8 @@ import subprocess
 
 import numpy as np
 import pytest
+
+from _flat_ivf_restatement import lists_from_labels, same, search
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ERR_ARG, ERR_STATE = -1, -7
@@ -20,33 +23,6 @@ F32 = np.float32
 LENGTHS = (0, 1, 15, 16, 17, 63, 64, 65, 255, 256, 257, 1500, 40, 30, 20)
 NLIST, NQ, LONG = len(LENGTHS), 50, 11
 KINDS = {"u8": (np.uint8, 0), "i8": (np.int8, 128)}                                # dtype, what the values 0 .. 255 are lowered by
-
-
-def lists_from_labels(labels, nlist):
-    """(offsets int64 [nlist + 1], rows int64 [n_assigned]): the rows of a list ascend."""
-    key = np.where(labels < 0, nlist, labels)
-    rows = np.argsort(key, kind="stable")[:int((labels >= 0).sum())]
-    return np.concatenate([[0], np.cumsum(np.bincount(key, minlength=nlist + 1)[:nlist])]).astype(np.int64), rows
-
-
-def search(c, qs, probes, top_k, id_offset=0):
-    """(ids int32 [nq][top_k], dists float32 [nq][top_k]) by key (distance bits, id), padded with -1 / +inf."""
-    ids = np.full((len(qs), top_k), -1, dtype=np.int32)
-    dists = np.full((len(qs), top_k), np.inf, dtype=F32)
-    for i, (q, row) in enumerate(zip(qs.astype(np.int64), probes)):
-        keys = [np.zeros(0, dtype=np.uint64)]
-        for l in dict.fromkeys(int(p) for p in row if p >= 0):                     # padding skipped, a repeat counts once
-            r = c["rows"][c["offsets"][l]:c["offsets"][l + 1]]
-            d = ((c["base"][r].astype(np.int64) - q) ** 2).sum(axis=1).astype(F32)
-            keys.append((d.view(np.uint32).astype(np.uint64) << np.uint64(32)) | (r + id_offset).astype(np.uint64))
-        keys = np.sort(np.concatenate(keys))[:top_k]
-        ids[i, :len(keys)] = (keys & np.uint64(0xffffffff)).astype(np.int32)
-        dists[i, :len(keys)] = (keys >> np.uint64(32)).astype(np.uint32).view(F32)
-    return ids, dists
-
-
-def same(got, want):
-    return np.array_equal(got[0], want[0]) and np.array_equal(got[1].view(np.uint32), want[1].view(np.uint32))
 
 
 _cases = {}

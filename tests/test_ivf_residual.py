@@ -1,6 +1,7 @@
 """IVF search over an index of residual codes (include/deltapq_amd.h "IVF search by residual").  The reference is the numpy
-restatement below: r = q - c_l in fp32, the table by the table build's rule, then the fp64 sum rounded once (a DTC
-handle) or M fp32 additions (a plain handle).  The GPU meets it bit for bit, for every group size P of the scan."""
+restatement of tests/_ivf_residual_restatement.py: r = q - c_l in fp32, the table by the table build's rule, then the fp64
+sum rounded once (a DTC handle) or M fp32 additions (a plain handle).  The GPU meets it bit for bit, for every group size
+P of the scan."""
 import ctypes
 import os
 import re
@@ -11,55 +12,13 @@ import pytest
 
 import _ivf_restatement as R
 import _numeric_edges as ne
+from _ivf_residual_restatement import distances, same, search, table
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ERR_ARG, ERR_STATE = -1, -7
 SYMBOLS = ("dpq_ivf_residuals", "dpq_ivf_residuals_device", "dpq_ivf_search_residual", "dpq_ivf_search_residual_device",
            "dpq_ivf_search_probes_residual", "dpq_ivf_search_probes_residual_device")
 F32, F64 = np.float32, np.float64
-
-
-def table(cb, r):
-    """float32 [M][256]: the exact table of the (residual) query r under codebook cb [M][K][Ds]; k >= K: +inf."""
-    M, K, Ds = cb.shape
-    acc = np.zeros((M, K), dtype=F32)
-    for d in range(Ds):
-        diff = (cb[:, :, d] - r.reshape(M, Ds)[:, d, None]).astype(F32)            # fp32 subtract
-        acc = (acc.astype(F64) + diff.astype(F64) * diff.astype(F64)).astype(F32)  # the square in fp64; float += double
-    T = np.full((M, 256), np.inf, dtype=F32)
-    T[:, :K] = acc
-    return T
-
-
-def distances(T, codes, plain):
-    """float32 [n]: codes uint8 [n][M] under table T, m ascending."""
-    e = T[np.arange(T.shape[0]), codes]
-    acc = np.zeros(len(codes), dtype=F32 if plain else F64)
-    for m in range(T.shape[0]):
-        acc = (acc + e[:, m]).astype(acc.dtype)                                    # (f64 + f32 is an f64 addition)
-    return acc.astype(F32)
-
-
-def search(c, qs, probes, top_k, allowed=None):
-    """(ids int32 [nq][top_k], dists float32 [nq][top_k]) by key (distance bits, id), padded with -1 / +inf."""
-    ids = np.full((len(qs), top_k), -1, dtype=np.int32)
-    dists = np.full((len(qs), top_k), np.inf, dtype=F32)
-    for i, (q, row) in enumerate(zip(qs, probes)):
-        keys = [np.zeros(0, dtype=np.uint64)]
-        for l in dict.fromkeys(int(p) for p in row if p >= 0):                     # padding skipped, a repeat counts once
-            ent = slice(c["offsets"][l], c["offsets"][l + 1])
-            eid = c["ids"][ent].astype(np.int64)
-            d = distances(table(c["cb"], (q - c["cents"][l]).astype(F32)), c["entry_codes"][ent], c["plain"])
-            keep = np.ones(len(eid), dtype=bool) if allowed is None else allowed[eid]
-            keys.append((d[keep].view(np.uint32).astype(np.uint64) << np.uint64(32)) | eid[keep].astype(np.uint64))
-        keys = np.sort(np.concatenate(keys))[:top_k]
-        ids[i, :len(keys)] = (keys & np.uint64(0xffffffff)).astype(np.int32)
-        dists[i, :len(keys)] = (keys >> np.uint64(32)).astype(np.uint32).view(F32)
-    return ids, dists
-
-
-def same(got, want):
-    return np.array_equal(got[0], want[0]) and np.array_equal(got[1].view(np.uint32), want[1].view(np.uint32))
 
 
 LENGTHS = (0, 1, 255, 256, 257, 600)  # lists 0 .. 5; list 6 takes the rest
