@@ -317,6 +317,16 @@ SYMBOLS = [
      [_VP, _VP, ctypes.c_int, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP]),
     ("dpq_flat_ivf_search_bytes", ctypes.c_int, [_VP, _VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, _VP, _VP]),
     ("dpq_flat_ivf_search_bytes_device", ctypes.c_int, [_VP, _VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP]),
+    ("dpq_flat_ivf_create_bits", ctypes.c_int, [_VP, _VP, c_i64, ctypes.c_int, P(_VP)]),
+    ("dpq_flat_ivf_create_bits_device", ctypes.c_int, [_VP, _VP, c_i64, ctypes.c_int, _VP, P(_VP)]),
+    ("dpq_flat_ivf_build_bits", ctypes.c_int, [_VP, _VP, ctypes.c_int, P(_VP)]),
+    ("dpq_flat_ivf_set_centroids_bits", ctypes.c_int, [_VP, _VP, ctypes.c_int]),
+    ("dpq_flat_ivf_probe_bits", ctypes.c_int, [_VP, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP]),
+    ("dpq_flat_ivf_search_probes_bits", ctypes.c_int, [_VP, _VP, ctypes.c_int, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP]),
+    ("dpq_flat_ivf_search_probes_bits_device", ctypes.c_int,
+     [_VP, _VP, ctypes.c_int, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP]),
+    ("dpq_flat_ivf_search_bits", ctypes.c_int, [_VP, _VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, _VP, _VP]),
+    ("dpq_flat_ivf_search_bits_device", ctypes.c_int, [_VP, _VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP]),
     ("dpq_ivf_search_filtered", ctypes.c_int, [_VP, _VP, _VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, _VP, _VP]),
     ("dpq_ivf_search_device_filtered", ctypes.c_int, [_VP, _VP, _VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP]),
     ("dpq_ivf_search_probes_filtered", ctypes.c_int,

@@ -2392,6 +2392,105 @@ class FlatIndexBits(FlatIndexU8):
         return (self.D + 7) // 8
 
 
+class FlatIVFBits(FlatIVF):
+    """FlatIVF over a FlatIndexBits (include/deltapq_amd.h "IVF search over binary vectors"), FAISS's IndexBinaryIVF: the
+    probed lists are scanned by Hamming distance, and an answer is, bit for bit, the binary index's search_filtered under
+    a filter of the probed lists' rows.  Queries AND centroids are uint8 arrays of packed rows [.][(D + 7) // 8], checked
+    as FlatIndexBits checks its queries (anything else is a TypeError); the centroids are ranked by Hamming distance,
+    ties to the lower list number.  There is no trainer for binary centroids: binarise train_ivf_centroids' output with
+    bits_from_float (and the rows' thresholds), or take rows of the base."""
+
+    @classmethod
+    def build(cls, flat_index, centroids):
+        """Lists by the nearest centroid of every row by (Hamming distance, list number) (dpq_flat_ivf_build_bits);
+        centroids uint8 [nlist][(D + 7) // 8], kept for probe() and search()."""
+        c = flat_index._rows(centroids, flat_index.D, "centroids")
+        h = ctypes.c_void_p()
+        check(flat_index._lib.dpq_flat_ivf_build_bits(flat_index._h, _np_ptr(c), c.shape[0], h), "dpq_flat_ivf_build_bits")
+        return cls(flat_index, h)
+
+    @classmethod
+    def from_labels(cls, flat_index, labels, nlist, centroids=None):
+        """FlatIVF.from_labels over a binary index (dpq_flat_ivf_create_bits[_device])."""
+        h = ctypes.c_void_p()
+        lib = flat_index._lib
+        if isinstance(labels, np.ndarray) or not hasattr(labels, "data_ptr"):
+            a = np.ascontiguousarray(np.asarray(labels, dtype=np.int32).ravel())
+            check(lib.dpq_flat_ivf_create_bits(flat_index._h, _np_ptr(a), a.size, int(nlist), h), "dpq_flat_ivf_create_bits")
+        else:
+            import torch
+            assert labels.is_cuda and labels.dtype == torch.int32 and labels.is_contiguous()
+            stream = ctypes.c_void_p(torch.cuda.current_stream(labels.device).cuda_stream)
+            check(lib.dpq_flat_ivf_create_bits_device(flat_index._h, ctypes.c_void_p(labels.data_ptr()), labels.numel(),
+                                                      int(nlist), stream, h), "dpq_flat_ivf_create_bits_device")
+        ivf = cls(flat_index, h)
+        if centroids is not None:
+            ivf.set_centroids(centroids)
+        return ivf
+
+    def set_centroids(self, centroids):
+        """Attaches packed centroids uint8 [nlist][(D + 7) // 8] to lists made from labels (dpq_flat_ivf_set_centroids_bits)."""
+        c = self._index._rows(centroids, self._index.D, "centroids")
+        check(self._lib.dpq_flat_ivf_set_centroids_bits(self._h, _np_ptr(c), c.shape[0]), "dpq_flat_ivf_set_centroids_bits")
+        return self
+
+    def probe(self, queries, nprobe):
+        """(lists int32 [nq][nprobe], dists float32 [nq][nprobe]): each query's nprobe nearest centroids by (Hamming
+        distance, list number) (dpq_flat_ivf_probe_bits)."""
+        q = self._index._queries(queries)
+        lists, dists = self._out(q.shape[0], nprobe)
+        check(self._lib.dpq_flat_ivf_probe_bits(self._h, _np_ptr(q), q.shape[0], nprobe, _np_ptr(lists), _np_ptr(dists)),
+              "dpq_flat_ivf_probe_bits")
+        return lists, dists
+
+    def search(self, queries, nprobe, top_k):
+        """(ids int32 [nq][k], dists float32 [nq][k]) over the nprobe lists nearest to each query (dpq_flat_ivf_search_bits)."""
+        q = self._index._queries(queries)
+        ids, dists = self._out(q.shape[0], top_k)
+        check(self._lib.dpq_flat_ivf_search_bits(self._h, _np_ptr(q), q.shape[0], nprobe, top_k, _np_ptr(ids), _np_ptr(dists)),
+              "dpq_flat_ivf_search_bits")
+        return ids, dists
+
+    def search_probes(self, queries, probes, top_k):
+        """search over the caller's own lists: probes int32 [nq][nprobe], -1 = padding (dpq_flat_ivf_search_probes_bits)."""
+        q = self._index._queries(queries)
+        p = IVF._probes(probes, q.shape[0])
+        ids, dists = self._out(q.shape[0], top_k)
+        check(self._lib.dpq_flat_ivf_search_probes_bits(self._h, _np_ptr(q), q.shape[0], _np_ptr(p), p.shape[1], top_k,
+                                                        _np_ptr(ids), _np_ptr(dists)), "dpq_flat_ivf_search_probes_bits")
+        return ids, dists
+
+    def _torch_out(self, queries, top_k, out_ids, out_dists):
+        import torch
+        self._index._check_tensor(queries)
+        assert queries.is_cuda and queries.is_contiguous() and queries.dim() == 2 and queries.shape[1] == self._index._qcols
+        nq = queries.shape[0]
+        if out_ids is None:
+            out_ids = torch.empty((nq, top_k), dtype=torch.int32, device=queries.device)
+        if out_dists is None:
+            out_dists = torch.empty((nq, top_k), dtype=torch.float32, device=queries.device)
+        return nq, out_ids, out_dists, ctypes.c_void_p(torch.cuda.current_stream(queries.device).cuda_stream)
+
+    def search_torch(self, queries, nprobe, top_k, out_ids=None, out_dists=None):
+        """search on device tensors, synchronous on torch's current stream (dpq_flat_ivf_search_bits_device)."""
+        nq, out_ids, out_dists, stream = self._torch_out(queries, top_k, out_ids, out_dists)
+        check(self._lib.dpq_flat_ivf_search_bits_device(self._h, ctypes.c_void_p(queries.data_ptr()), nq, nprobe, top_k,
+                                                        ctypes.c_void_p(out_ids.data_ptr()),
+                                                        ctypes.c_void_p(out_dists.data_ptr()), stream),
+              "dpq_flat_ivf_search_bits_device")
+        return out_ids, out_dists
+
+    def search_probes_torch(self, queries, probes, top_k, out_ids=None, out_dists=None):
+        """search_probes on device tensors (dpq_flat_ivf_search_probes_bits_device)."""
+        nq, out_ids, out_dists, stream = self._torch_out(queries, top_k, out_ids, out_dists)
+        pp, nprobe = IVF._torch_probes(probes, nq)
+        check(self._lib.dpq_flat_ivf_search_probes_bits_device(self._h, ctypes.c_void_p(queries.data_ptr()), nq, pp, nprobe,
+                                                               top_k, ctypes.c_void_p(out_ids.data_ptr()),
+                                                               ctypes.c_void_p(out_dists.data_ptr()), stream),
+              "dpq_flat_ivf_search_probes_bits_device")
+        return out_ids, out_dists
+
+
 class RefineLevel:
     """A second PQ level over the residuals of an index's nodes (dpq_refine): M2 more bytes per node, and a PQ
     shortlist is re-ranked by the distance to the two-level reconstruction -- no raw vectors on the GPU.  Made on one

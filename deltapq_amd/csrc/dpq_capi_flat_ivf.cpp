@@ -1,7 +1,8 @@
-// dpq_capi_flat_ivf.cpp -- the dpq_flat_ivf_* entry points of include/deltapq_amd.h (kernels in dpq_flat_ivf.hip and
-// dpq_flat_ivf_u8.hip): inverted lists over the rows of an fp32 or a byte dpq_flat handle, built on the device from labels
-// or from centroids, and the search that forms exact distances to the rows of the lists a query probes.  The fp32 entry
-// points and the *_bytes ones run the same code; `bytes` says which kind of handle and of queries a call is about.
+// dpq_capi_flat_ivf.cpp -- the dpq_flat_ivf_* entry points of include/deltapq_amd.h (kernels in dpq_flat_ivf.hip,
+// dpq_flat_ivf_u8.hip and dpq_flat_ivf_bits.hip): inverted lists over the rows of an fp32, a byte or a binary dpq_flat handle,
+// built on the device from labels or from centroids, and the search that forms exact distances to the rows of the lists a
+// query probes.  The fp32 entry points, the *_bytes and the *_bits ones run the same code; `kind` (kFivfF32, kFivfBytes,
+// kFivfBits) says which kind of handle, of queries and of centroids a call is about.
 #include "dpq_capi_internal.h"
 #include "dpq_ivf_train.h"
 
@@ -13,11 +14,13 @@ int fivf_nlist_ok(const std::string& who, int nlist) {
 }
 
 // A handle of the call's kind on a present device.  (The launchers that make the lists take at most 2^31 - 1 rows.)
-int fivf_enter_flat(const std::string& who, dpq_flat* f, bool bytes) {
-    if (bytes && f->format != dpq::kFlatU8 && f->format != dpq::kFlatI8)
+int fivf_enter_flat(const std::string& who, dpq_flat* f, int kind) {
+    if (kind == kFivfBits && f->format != dpq::kFlatBits)
+        return fail(DPQ_ERR_ARG, who + ": needs a handle of binary rows (dpq_flat_open_bits / dpq_flat_open_binarised)");
+    if (kind == kFivfBytes && f->format != dpq::kFlatU8 && f->format != dpq::kFlatI8)
         return fail(DPQ_ERR_ARG, who + ": needs a handle of byte rows (dpq_flat_open_u8 / dpq_flat_open_i8)");
-    if (!bytes && f->format != dpq::kFlatF32)
-        return fail(DPQ_ERR_ARG, who + ": needs a handle of fp32 rows (dpq_flat_open); half, byte, quantised and binary handles are not supported");
+    if (kind == kFivfF32 && f->format != dpq::kFlatF32)
+        return fail(DPQ_ERR_ARG, who + ": needs a handle of fp32 rows (dpq_flat_open); byte handles have the *_bytes calls, binary handles the *_bits calls; half and quantised handles are not supported");
     if (f->map.get()) return fail(DPQ_ERR_ARG, who + ": a handle with an id map (dpq_flat_set_id_map) is not supported");
     if (f->n > 0x7fffffff) return fail(DPQ_ERR_ARG, who + ": the handle has too many rows");
     if (int rc = flat_device_present(who)) return rc;
@@ -31,7 +34,7 @@ int fivf_from_device_labels(const std::string& who, dpq_flat* f, const int32_t* 
     if (n != f->n) return fail(DPQ_ERR_ARG, who + ": n must be the handle's row count");
     std::unique_ptr<dpq_flat_ivf> v(new dpq_flat_ivf());
     v->flat = f;
-    v->bytes = f->format != dpq::kFlatF32;
+    v->kind = f->format == dpq::kFlatBits ? kFivfBits : f->format != dpq::kFlatF32 ? kFivfBytes : kFivfF32;
     v->device = f->device;
     v->nlist = nlist;
     DevBuf<uint32_t> keys, pos, keys_out, flag;
@@ -102,14 +105,23 @@ int fivf_search_args(const std::string& who, const void* ivf, const void* querie
     return DPQ_OK;
 }
 
+// A call of one kind on a structure of another names the structure's own set.
+int fivf_kind_ok(const std::string& who, const dpq_flat_ivf* v, int kind) {
+    if (v->kind == kind) return DPQ_OK;
+    static const char* const sets[] = {": the structure is over fp32 rows: its calls are the ones without _bytes or _bits",
+                                       ": the structure is over byte rows: its calls are the *_bytes ones",
+                                       ": the structure is over binary rows: its calls are the *_bits ones"};
+    return fail(DPQ_ERR_ARG, who + sets[v->kind]);
+}
+
 // What needs the structure's fields; then a device.
-int fivf_enter(const std::string& who, dpq_flat_ivf* v, bool bytes, int nprobe, bool coarse) {
-    if (v->bytes != bytes)
-        return fail(DPQ_ERR_ARG, who + (bytes ? ": the structure is over fp32 rows: its calls are the ones without _bytes"
-                                              : ": the structure is over byte rows: its calls are the *_bytes ones"));
+int fivf_enter(const std::string& who, dpq_flat_ivf* v, int kind, int nprobe, bool coarse) {
+    if (int rc = fivf_kind_ok(who, v, kind)) return rc;
     if (nprobe > v->nlist) return fail(DPQ_ERR_ARG, who + ": needs 1 <= nprobe <= min(nlist, 1024)");
-    if (coarse && !v->centroids.get())
-        return fail(DPQ_ERR_STATE, who + ": the structure has no centroids (dpq_flat_ivf_build / dpq_flat_ivf_set_centroids)");
+    if (coarse && !(kind == kFivfBits ? (const void*)v->bcent.get() : (const void*)v->centroids.get()))
+        return fail(DPQ_ERR_STATE, who + (kind == kFivfBits
+                                              ? ": the structure has no centroids (dpq_flat_ivf_build_bits / dpq_flat_ivf_set_centroids_bits)"
+                                              : ": the structure has no centroids (dpq_flat_ivf_build / dpq_flat_ivf_set_centroids)"));
     if (int rc = flat_device_present(who)) return rc;
     DPQ_HIP(hipSetDevice(v->device));
     return DPQ_OK;
@@ -127,11 +139,33 @@ int fivf_probe_rows_ok(const std::string& who, const dpq_flat_ivf* v, const int3
 
 // A call's queries as the kernels read them.  f32 [nq][Dp] with zero padding: what the coarse step ranks the centroids by,
 // and what the fp32 scan reads.  A byte structure: i8 [nq][Dp] and norm [nq], the queries as the handle stores rows.
+// A binary structure: bits [nq][Dp] bytes, the queries as the handle stores rows, for the coarse step and the scan alike.
 struct FivfQueries {
     const float* f32 = nullptr;
     const int8_t* i8 = nullptr;
     const int32_t* norm = nullptr;
+    const uint8_t* bits = nullptr;
 };
+
+// Packed binary queries [nq][(D + 7) / 8] in the caller's layout: prepared as dpq_flat_search_bits prepares them
+// (launch_flat_bits_prepare over the batch).  Host form: through v->q_raw.  The buffer has room for 64 more queries: the
+// Hamming kernel of the coarse step reads whole query tiles and masks what lies past nq.
+int fivf_queries_bits(dpq_flat_ivf* v, const void* queries, int nq, bool device, hipStream_t stream, FivfQueries* out) {
+    const int D = v->flat->D, Dp = v->flat->Dp;
+    const size_t nb = (size_t)dpq::flat_bits_bytes(D);
+    const uint8_t* raw = static_cast<const uint8_t*>(queries);
+    int rc = grow(v->q8, &v->q8_n, ((size_t)nq + 64) * Dp);
+    if (!rc && !device) rc = grow(v->q_raw, &v->q_raw_n, (size_t)nq * nb);
+    if (rc) return rc;
+    if (!device) {
+        DPQ_HIP(hipMemcpy(v->q_raw, queries, (size_t)nq * nb, hipMemcpyHostToDevice));
+        raw = v->q_raw;
+    }
+    uint8_t* q = reinterpret_cast<uint8_t*>(v->q8.get());
+    DPQ_HIP(dpq::launch_flat_bits_prepare(raw, nq, D, q, Dp, stream));
+    out->bits = q;
+    return DPQ_OK;
+}
 
 // Byte queries [nq][D] of the handle's kind: prepared as the rows are (launch_flat_u8_prepare over the batch) and, for a
 // call with a coarse step, widened exactly to fp32 -- the caller's values, not the biased storage.  Host form: through
@@ -163,7 +197,8 @@ int fivf_queries_bytes(dpq_flat_ivf* v, const void* queries, int nq, bool device
 // fp32 queries [nq][D].  Host form: into v->d_q.  Device form: the caller's rows where they already are [nq][Dp] (D a
 // multiple of four, 16-byte aligned), else padded into v->d_q on `stream`.
 int fivf_queries(dpq_flat_ivf* v, const void* queries_, int nq, bool device, bool coarse, hipStream_t stream, FivfQueries* q) {
-    if (v->bytes) return fivf_queries_bytes(v, queries_, nq, device, coarse, stream, q);
+    if (v->kind == kFivfBits) return fivf_queries_bits(v, queries_, nq, device, stream, q);
+    if (v->kind == kFivfBytes) return fivf_queries_bytes(v, queries_, nq, device, coarse, stream, q);
     const float* queries = static_cast<const float*>(queries_);
     const float** out = &q->f32;
     const int D = v->flat->D, Dp = v->flat->Dp;
@@ -196,31 +231,35 @@ int fivf_stage(dpq_flat_ivf* v, int nq, int nprobe, int top_k) {
 
 // The coarse step, all device pointers: d_lists[nq][nprobe] the nearest centroids by (distance, list number),
 // d_cdists[nq][nprobe] their distances: the exact search over the centroids as a base.  Enqueues on `stream`.
-int fivf_probe_on_device(dpq_flat_ivf* v, const float* d_q, int nq, int nprobe, int32_t* d_lists, float* d_cdists,
+// A binary structure: the centroids are a kFlatBits base and the distance is Hamming's, so ties are the rule and the key
+// order settles them.  The query pointer of a batch may stand anywhere in a buffer with 64 spare rows behind its last.
+int fivf_probe_on_device(dpq_flat_ivf* v, const FivfQueries& qs, int nq, int nprobe, int32_t* d_lists, float* d_cdists,
                          hipStream_t stream) {
     const int qb = std::min(nq, dpq::flat_query_batch(nprobe));
     int rc = grow(v->keys, &v->keys_n, (size_t)qb * dpq::flat_key_capacity(nprobe));
     if (!rc) rc = grow(v->state, &v->state_n, (size_t)qb);
     if (rc) return rc;
+    const bool bits = v->kind == kFivfBits;
     dpq::FlatBase base;
-    base.format = dpq::kFlatF32;
-    base.rows = v->centroids.get();
+    base.format = bits ? dpq::kFlatBits : dpq::kFlatF32;
+    base.rows = bits ? (const void*)v->bcent.get() : (const void*)v->centroids.get();
     base.n = v->nlist;
     base.D = v->flat->D;
     base.Dp = v->flat->Dp;
     base.n_entries = v->nlist;
     for (int q0 = 0; q0 < nq; q0 += qb) {
         const int m = std::min(qb, nq - q0);
-        const dpq::FlatQueries q{d_q + (size_t)q0 * base.Dp, nullptr, nullptr, m};
+        const dpq::FlatQueries q{bits ? nullptr : qs.f32 + (size_t)q0 * base.Dp, nullptr, nullptr, m, nullptr,
+                                 bits ? qs.bits + (size_t)q0 * base.Dp : nullptr};
         DPQ_HIP(dpq::launch_flat_search(base, q, nprobe, v->keys, v->state, d_lists + (size_t)q0 * nprobe,
                                         d_cdists + (size_t)q0 * nprobe, stream));
     }
     return DPQ_OK;
 }
 
-// Pairs a workgroup of the scan takes (DESIGN.md 5.20, 5.21).
-int fivf_group_cfg(bool bytes) {
-    int group = bytes ? dpq::kFlatIvfGroupU8 : dpq::kFlatIvfGroup;
+// Pairs a workgroup of the scan takes (DESIGN.md 5.20, 5.21, 5.22).
+int fivf_group_cfg(int kind) {
+    int group = kind == kFivfBits ? dpq::kFlatIvfGroupBits : kind == kFivfBytes ? dpq::kFlatIvfGroupU8 : dpq::kFlatIvfGroup;
     if (dev_mode())
         if (const char* e = getenv("DPQ_FLAT_IVF_GROUP")) group = std::max(1, atoi(e));  // tests and the probe script: a cap on G
     return group;
@@ -273,7 +312,14 @@ int fivf_search_on_device(dpq_flat_ivf* v, const std::string& who, const FivfQue
     lists8.offsets = v->offsets;
     lists8.list_rows = v->rows;
     lists8.nlist = v->nlist;
-    const int group = fivf_group_cfg(v->bytes);
+    dpq::FlatIvfListsBits listsb;
+    listsb.rows = reinterpret_cast<const uint32_t*>(f->rows.get() + f->rows_at);
+    listsb.Wp = f->Dp >> 2;
+    listsb.id_offset = f->id_offset;
+    listsb.offsets = v->offsets;
+    listsb.list_rows = v->rows;
+    listsb.nlist = v->nlist;
+    const int group = fivf_group_cfg(v->kind);
     DPQ_HIP(hipMemsetAsync(v->flag, 0, sizeof(uint32_t), stream));
     for (int q0 = 0; q0 < nq; q0 += per) {
         const int m = std::min(per, nq - q0);
@@ -282,7 +328,10 @@ int fivf_search_on_device(dpq_flat_ivf* v, const std::string& who, const FivfQue
         DPQ_HIP(dpq::launch_flat_ivf_pairs(v->probes, n_pairs, v->nlist, v->pkeys, v->pvals, stream));
         size_t tb = v->sort_n;
         DPQ_HIP(dpq::flat_ivf_sort_pairs(v->sort_temp, &tb, v->pkeys, v->skeys, v->pvals, v->svals, n_pairs, v->nlist, stream));
-        if (v->bytes)
+        if (v->kind == kFivfBits)
+            DPQ_HIP(dpq::launch_flat_ivf_scan_bits(listsb, reinterpret_cast<const uint32_t*>(qs.bits + (size_t)q0 * f->Dp), m, nprobe,
+                                                   v->skeys, v->svals, top_k, group, v->part_ids, v->part_dists, stream));
+        else if (v->kind == kFivfBytes)
             DPQ_HIP(dpq::launch_flat_ivf_scan_u8(lists8, qs.i8 + (size_t)q0 * f->Dp, qs.norm + q0, m, nprobe, v->skeys, v->svals,
                                                  top_k, group, v->part_ids, v->part_dists, stream));
         else
@@ -307,19 +356,19 @@ int fivf_results_down(dpq_flat_ivf* v, int nq, int top_k, int32_t* ids, float* d
 
 // ---- the entry points' bodies, for either kind of handle ----------------------------------------------------------------
 
-int fivf_create_device(const std::string& who, bool bytes, dpq_flat* f, const int32_t* d_labels, int64_t n, int nlist,
+int fivf_create_device(const std::string& who, int kind, dpq_flat* f, const int32_t* d_labels, int64_t n, int nlist,
                        void* hip_stream, dpq_flat_ivf** out) {
     if (out) *out = nullptr;
     if (!f || !d_labels || !out || n < 0) return fail(DPQ_ERR_ARG, who + ": NULL argument or n < 0");
     if (int rc = fivf_nlist_ok(who, nlist)) return rc;
-    if (int rc = fivf_enter_flat(who, f, bytes)) return rc;
+    if (int rc = fivf_enter_flat(who, f, kind)) return rc;
     std::unique_ptr<dpq_flat_ivf> v;
     if (int rc = fivf_from_device_labels(who, f, d_labels, n, nlist, (hipStream_t)hip_stream, &v)) return rc;
     *out = v.release();
     return DPQ_OK;
 }
 
-int fivf_create(const std::string& who, bool bytes, dpq_flat* f, const int32_t* labels, int64_t n, int nlist, dpq_flat_ivf** out) {
+int fivf_create(const std::string& who, int kind, dpq_flat* f, const int32_t* labels, int64_t n, int nlist, dpq_flat_ivf** out) {
     if (out) *out = nullptr;
     if (!f || !labels || !out || n < 0) return fail(DPQ_ERR_ARG, who + ": NULL argument or n < 0");
     if (int rc = fivf_nlist_ok(who, nlist)) return rc;
@@ -330,7 +379,7 @@ int fivf_create(const std::string& who, bool bytes, dpq_flat* f, const int32_t* 
             snprintf(msg, sizeof msg, ": labels[%lld] = %d is >= nlist", (long long)i, (int)labels[i]);
             return fail(DPQ_ERR_ARG, who + msg);
         }
-    if (int rc = fivf_enter_flat(who, f, bytes)) return rc;
+    if (int rc = fivf_enter_flat(who, f, kind)) return rc;
     DevBuf<int32_t> d_labels;
     if (int rc = d_labels.alloc((size_t)n)) return rc;
     DPQ_HIP(hipMemcpy(d_labels, labels, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
@@ -362,11 +411,11 @@ int fivf_labels_by_centroids(dpq_flat* f, const float* d_cent, int nlist, int32_
     return DPQ_OK;
 }
 
-int fivf_build(const std::string& who, bool bytes, dpq_flat* f, const float* centroids, int nlist, dpq_flat_ivf** out) {
+int fivf_build(const std::string& who, int kind, dpq_flat* f, const float* centroids, int nlist, dpq_flat_ivf** out) {
     if (out) *out = nullptr;
     if (!f || !centroids || !out) return fail(DPQ_ERR_ARG, who + ": NULL argument");
     if (int rc = fivf_nlist_ok(who, nlist)) return rc;
-    if (int rc = fivf_enter_flat(who, f, bytes)) return rc;
+    if (int rc = fivf_enter_flat(who, f, kind)) return rc;
     DevBuf<float> d_cent;
     if (int rc = fivf_upload_centroids(f, centroids, nlist, &d_cent)) return rc;
     DevBuf<int32_t> d_labels;
@@ -379,25 +428,101 @@ int fivf_build(const std::string& who, bool bytes, dpq_flat* f, const float* cen
     return DPQ_OK;
 }
 
-int fivf_probe(const std::string& who, bool bytes, dpq_flat_ivf* v, const void* queries, int nq, int nprobe, int32_t* lists_out,
+// ---- binary centroids: packed rows [nlist][(D + 7) / 8] in the caller's layout, ranked by Hamming distance ------------------
+
+// ... in host memory -> the device, prepared as the handle's rows are (spare bits cleared, padded to Dp bytes).
+int fivf_upload_centroids_bits(const dpq_flat* f, const uint8_t* centroids, int nlist, DevBuf<uint8_t>* d_out) {
+    const size_t nb = (size_t)dpq::flat_bits_bytes(f->D);
+    DevBuf<uint8_t> raw;
+    if (int rc = raw.alloc((size_t)nlist * nb)) return rc;
+    if (int rc = d_out->alloc((size_t)nlist * f->Dp)) return rc;
+    DPQ_HIP(hipMemcpy(raw, centroids, (size_t)nlist * nb, hipMemcpyHostToDevice));
+    DPQ_HIP(dpq::launch_flat_bits_prepare(raw, nlist, f->D, d_out->get(), f->Dp, nullptr));
+    DPQ_HIP(hipDeviceSynchronize());  // `raw` is freed on return
+    return DPQ_OK;
+}
+
+void fivf_keep_centroids_bits(dpq_flat_ivf* v, DevBuf<uint8_t>&& d_cent) {
+    const int64_t bytes = (int64_t)v->nlist * v->flat->Dp;
+    if (v->bcent.get()) v->device_bytes -= bytes;
+    v->bcent = std::move(d_cent);
+    v->device_bytes += bytes;
+}
+
+// The label of a row is its nearest centroid by (Hamming distance, list number): the exact top-1 search over the
+// centroids as a kFlatBits base with the handle's own stored rows -- which have the prepared-query layout -- as the
+// queries, a batch at a time.  The Hamming kernel reads whole tiles of up to 64 queries and masks those past the batch:
+// the last batch of a handle whose row count is no multiple of 64 is searched from a copy with room behind it.
+int fivf_labels_by_centroids_bits(dpq_flat* f, const uint8_t* d_cent, int nlist, int32_t* d_labels) {
+    if (f->n == 0) return DPQ_OK;
+    const int qb = (int)std::min<int64_t>(f->n, dpq::flat_query_batch(1));
+    DevBuf<uint64_t> keys;
+    DevBuf<dpq::FlatQueryState> state;
+    DevBuf<float> dists;
+    DevBuf<uint8_t> tail;
+    int rc = keys.alloc((size_t)qb * dpq::flat_key_capacity(1));
+    if (!rc) rc = state.alloc((size_t)qb);
+    if (!rc) rc = dists.alloc((size_t)qb);
+    if (rc) return rc;
+    dpq::FlatBase base;
+    base.format = dpq::kFlatBits;
+    base.rows = d_cent;
+    base.n = nlist;
+    base.D = f->D;
+    base.Dp = f->Dp;
+    base.n_entries = nlist;
+    const uint8_t* rows = f->rows.get() + f->rows_at;
+    for (int64_t r0 = 0; r0 < f->n; r0 += qb) {
+        const int m = (int)std::min<int64_t>(qb, f->n - r0);
+        const uint8_t* q = rows + (size_t)r0 * f->Dp;
+        if (r0 + m == f->n && f->n % 64 != 0) {
+            if ((rc = tail.alloc(((size_t)m + 64) * f->Dp))) return rc;
+            DPQ_HIP(hipMemcpyAsync(tail, q, (size_t)m * f->Dp, hipMemcpyDeviceToDevice, nullptr));
+            q = tail;
+        }
+        DPQ_HIP(dpq::launch_flat_search(base, dpq::FlatQueries{nullptr, nullptr, nullptr, m, nullptr, q}, 1, keys, state,
+                                        d_labels + r0, dists, nullptr));
+    }
+    DPQ_HIP(hipDeviceSynchronize());  // the scratch is freed on return
+    return DPQ_OK;
+}
+
+int fivf_build_bits(const std::string& who, dpq_flat* f, const uint8_t* centroids, int nlist, dpq_flat_ivf** out) {
+    if (out) *out = nullptr;
+    if (!f || !centroids || !out) return fail(DPQ_ERR_ARG, who + ": NULL argument");
+    if (int rc = fivf_nlist_ok(who, nlist)) return rc;
+    if (int rc = fivf_enter_flat(who, f, kFivfBits)) return rc;
+    DevBuf<uint8_t> d_cent;
+    if (int rc = fivf_upload_centroids_bits(f, centroids, nlist, &d_cent)) return rc;
+    DevBuf<int32_t> d_labels;
+    if (int rc = d_labels.alloc((size_t)f->n)) return rc;
+    if (int rc = fivf_labels_by_centroids_bits(f, d_cent, nlist, d_labels)) return rc;
+    std::unique_ptr<dpq_flat_ivf> v;
+    if (int rc = fivf_from_device_labels(who, f, d_labels, f->n, nlist, nullptr, &v)) return rc;
+    fivf_keep_centroids_bits(v.get(), std::move(d_cent));
+    *out = v.release();
+    return DPQ_OK;
+}
+
+int fivf_probe(const std::string& who, int kind, dpq_flat_ivf* v, const void* queries, int nq, int nprobe, int32_t* lists_out,
                float* dists_out) {
     if (!v || !queries || !lists_out || nq < 0) return fail(DPQ_ERR_ARG, who + ": NULL argument or nq < 0");
     if (nprobe < 1 || nprobe > dpq::kIvfMaxProbe) return fail(DPQ_ERR_ARG, who + ": needs 1 <= nprobe <= min(nlist, 1024)");
-    if (int rc = fivf_enter(who, v, bytes, nprobe, true)) return rc;
+    if (int rc = fivf_enter(who, v, kind, nprobe, true)) return rc;
     if (nq == 0) return DPQ_OK;
     FivfQueries q;
     if (int rc = fivf_queries(v, queries, nq, false, true, nullptr, &q)) return rc;
     if (int rc = fivf_stage(v, nq, nprobe, 0)) return rc;
-    if (int rc = fivf_probe_on_device(v, q.f32, nq, nprobe, v->d_probes, v->d_cdists, nullptr)) return rc;
+    if (int rc = fivf_probe_on_device(v, q, nq, nprobe, v->d_probes, v->d_cdists, nullptr)) return rc;
     DPQ_HIP(hipMemcpy(lists_out, v->d_probes, (size_t)nq * nprobe * sizeof(int32_t), hipMemcpyDeviceToHost));
     if (dists_out) DPQ_HIP(hipMemcpy(dists_out, v->d_cdists, (size_t)nq * nprobe * sizeof(float), hipMemcpyDeviceToHost));
     return DPQ_OK;
 }
 
-int fivf_search_probes_device(const std::string& who, bool bytes, dpq_flat_ivf* v, const void* d_queries, int nq,
+int fivf_search_probes_device(const std::string& who, int kind, dpq_flat_ivf* v, const void* d_queries, int nq,
                               const int32_t* d_probes, int nprobe, int top_k, int32_t* d_ids, float* d_dists, void* hip_stream) {
     if (int rc = fivf_search_args(who, v, d_queries, nq, true, d_probes, nprobe, top_k, d_ids, d_dists)) return rc;
-    if (int rc = fivf_enter(who, v, bytes, nprobe, false)) return rc;
+    if (int rc = fivf_enter(who, v, kind, nprobe, false)) return rc;
     if (nq == 0) return DPQ_OK;
     hipStream_t stream = (hipStream_t)hip_stream;
     FivfQueries q;
@@ -405,12 +530,12 @@ int fivf_search_probes_device(const std::string& who, bool bytes, dpq_flat_ivf* 
     return fivf_search_on_device(v, who, q, nq, d_probes, nprobe, top_k, d_ids, d_dists, stream);
 }
 
-int fivf_search_probes(const std::string& who, bool bytes, dpq_flat_ivf* v, const void* queries, int nq, const int32_t* probes,
+int fivf_search_probes(const std::string& who, int kind, dpq_flat_ivf* v, const void* queries, int nq, const int32_t* probes,
                        int nprobe, int top_k, int32_t* ids, float* dists) {
     if (int rc = fivf_search_args(who, v, queries, nq, true, probes, nprobe, top_k, ids, dists)) return rc;
     if (nprobe > v->nlist) return fail(DPQ_ERR_ARG, who + ": needs 1 <= nprobe <= min(nlist, 1024)");
     if (int rc = fivf_probe_rows_ok(who, v, probes, nq, nprobe)) return rc;
-    if (int rc = fivf_enter(who, v, bytes, nprobe, false)) return rc;
+    if (int rc = fivf_enter(who, v, kind, nprobe, false)) return rc;
     if (nq == 0) return DPQ_OK;
     FivfQueries q;
     if (int rc = fivf_queries(v, queries, nq, false, false, nullptr, &q)) return rc;
@@ -420,28 +545,28 @@ int fivf_search_probes(const std::string& who, bool bytes, dpq_flat_ivf* v, cons
     return fivf_results_down(v, nq, top_k, ids, dists);
 }
 
-int fivf_search_device(const std::string& who, bool bytes, dpq_flat_ivf* v, const void* d_queries, int nq, int nprobe, int top_k,
+int fivf_search_device(const std::string& who, int kind, dpq_flat_ivf* v, const void* d_queries, int nq, int nprobe, int top_k,
                        int32_t* d_ids, float* d_dists, void* hip_stream) {
     if (int rc = fivf_search_args(who, v, d_queries, nq, false, nullptr, nprobe, top_k, d_ids, d_dists)) return rc;
-    if (int rc = fivf_enter(who, v, bytes, nprobe, true)) return rc;
+    if (int rc = fivf_enter(who, v, kind, nprobe, true)) return rc;
     if (nq == 0) return DPQ_OK;
     hipStream_t stream = (hipStream_t)hip_stream;
     FivfQueries q;
     if (int rc = fivf_queries(v, d_queries, nq, true, true, stream, &q)) return rc;
     if (int rc = fivf_stage(v, nq, nprobe, 0)) return rc;
-    if (int rc = fivf_probe_on_device(v, q.f32, nq, nprobe, v->d_probes, v->d_cdists, stream)) return rc;
+    if (int rc = fivf_probe_on_device(v, q, nq, nprobe, v->d_probes, v->d_cdists, stream)) return rc;
     return fivf_search_on_device(v, who, q, nq, v->d_probes, nprobe, top_k, d_ids, d_dists, stream);
 }
 
-int fivf_search(const std::string& who, bool bytes, dpq_flat_ivf* v, const void* queries, int nq, int nprobe, int top_k,
+int fivf_search(const std::string& who, int kind, dpq_flat_ivf* v, const void* queries, int nq, int nprobe, int top_k,
                 int32_t* ids, float* dists) {
     if (int rc = fivf_search_args(who, v, queries, nq, false, nullptr, nprobe, top_k, ids, dists)) return rc;
-    if (int rc = fivf_enter(who, v, bytes, nprobe, true)) return rc;
+    if (int rc = fivf_enter(who, v, kind, nprobe, true)) return rc;
     if (nq == 0) return DPQ_OK;
     FivfQueries q;
     if (int rc = fivf_queries(v, queries, nq, false, true, nullptr, &q)) return rc;
     if (int rc = fivf_stage(v, nq, nprobe, top_k)) return rc;
-    if (int rc = fivf_probe_on_device(v, q.f32, nq, nprobe, v->d_probes, v->d_cdists, nullptr)) return rc;
+    if (int rc = fivf_probe_on_device(v, q, nq, nprobe, v->d_probes, v->d_cdists, nullptr)) return rc;
     if (int rc = fivf_search_on_device(v, who, q, nq, v->d_probes, nprobe, top_k, v->d_ids, v->d_dists, nullptr)) return rc;
     return fivf_results_down(v, nq, top_k, ids, dists);
 }
@@ -451,33 +576,35 @@ int fivf_search(const std::string& who, bool bytes, dpq_flat_ivf* v, const void*
 extern "C" {
 
 int dpq_flat_ivf_create_device(dpq_flat* f, const int32_t* d_labels, int64_t n, int nlist, void* hip_stream, dpq_flat_ivf** out) {
-    return guarded([&]() -> int { return fivf_create_device("dpq_flat_ivf_create_device", false, f, d_labels, n, nlist, hip_stream, out); });
+    return guarded([&]() -> int { return fivf_create_device("dpq_flat_ivf_create_device", kFivfF32, f, d_labels, n, nlist, hip_stream, out); });
 }
 
 int dpq_flat_ivf_create_bytes_device(dpq_flat* f, const int32_t* d_labels, int64_t n, int nlist, void* hip_stream, dpq_flat_ivf** out) {
-    return guarded([&]() -> int { return fivf_create_device("dpq_flat_ivf_create_bytes_device", true, f, d_labels, n, nlist, hip_stream, out); });
+    return guarded([&]() -> int { return fivf_create_device("dpq_flat_ivf_create_bytes_device", kFivfBytes, f, d_labels, n, nlist, hip_stream, out); });
 }
 
 int dpq_flat_ivf_create(dpq_flat* f, const int32_t* labels, int64_t n, int nlist, dpq_flat_ivf** out) {
-    return guarded([&]() -> int { return fivf_create("dpq_flat_ivf_create", false, f, labels, n, nlist, out); });
+    return guarded([&]() -> int { return fivf_create("dpq_flat_ivf_create", kFivfF32, f, labels, n, nlist, out); });
 }
 
 int dpq_flat_ivf_create_bytes(dpq_flat* f, const int32_t* labels, int64_t n, int nlist, dpq_flat_ivf** out) {
-    return guarded([&]() -> int { return fivf_create("dpq_flat_ivf_create_bytes", true, f, labels, n, nlist, out); });
+    return guarded([&]() -> int { return fivf_create("dpq_flat_ivf_create_bytes", kFivfBytes, f, labels, n, nlist, out); });
 }
 
 int dpq_flat_ivf_build(dpq_flat* f, const float* centroids, int nlist, dpq_flat_ivf** out) {
-    return guarded([&]() -> int { return fivf_build("dpq_flat_ivf_build", false, f, centroids, nlist, out); });
+    return guarded([&]() -> int { return fivf_build("dpq_flat_ivf_build", kFivfF32, f, centroids, nlist, out); });
 }
 
 int dpq_flat_ivf_build_bytes(dpq_flat* f, const float* centroids, int nlist, dpq_flat_ivf** out) {
-    return guarded([&]() -> int { return fivf_build("dpq_flat_ivf_build_bytes", true, f, centroids, nlist, out); });
+    return guarded([&]() -> int { return fivf_build("dpq_flat_ivf_build_bytes", kFivfBytes, f, centroids, nlist, out); });
 }
 
 int dpq_flat_ivf_set_centroids(dpq_flat_ivf* v, const float* centroids, int nlist) {
     return guarded([&]() -> int {
     const std::string who = "dpq_flat_ivf_set_centroids";
     if (!v || !centroids) return fail(DPQ_ERR_ARG, who + ": NULL argument");
+    if (v->kind == kFivfBits)
+        return fail(DPQ_ERR_ARG, who + ": the structure is over binary rows: its centroids are packed bits (dpq_flat_ivf_set_centroids_bits)");
     if (nlist != v->nlist) return fail(DPQ_ERR_ARG, who + ": nlist is not the structure's");
     if (int rc = flat_device_present(who)) return rc;
     DPQ_HIP(hipSetDevice(v->device));
@@ -486,6 +613,58 @@ int dpq_flat_ivf_set_centroids(dpq_flat_ivf* v, const float* centroids, int nlis
     fivf_keep_centroids(v, std::move(d_cent));
     return DPQ_OK;
     });
+}
+
+int dpq_flat_ivf_set_centroids_bits(dpq_flat_ivf* v, const uint8_t* centroids, int nlist) {
+    return guarded([&]() -> int {
+    const std::string who = "dpq_flat_ivf_set_centroids_bits";
+    if (!v || !centroids) return fail(DPQ_ERR_ARG, who + ": NULL argument");
+    if (int rc = fivf_kind_ok(who, v, kFivfBits)) return rc;
+    if (nlist != v->nlist) return fail(DPQ_ERR_ARG, who + ": nlist is not the structure's");
+    if (int rc = flat_device_present(who)) return rc;
+    DPQ_HIP(hipSetDevice(v->device));
+    DevBuf<uint8_t> d_cent;
+    if (int rc = fivf_upload_centroids_bits(v->flat, centroids, nlist, &d_cent)) return rc;
+    fivf_keep_centroids_bits(v, std::move(d_cent));
+    return DPQ_OK;
+    });
+}
+
+// ---- the *_bits set: a dpq_flat_open_bits handle, packed queries [nq][(D + 7) / 8] -----------------------------------------
+
+int dpq_flat_ivf_create_bits(dpq_flat* f, const int32_t* labels, int64_t n, int nlist, dpq_flat_ivf** out) {
+    return guarded([&]() -> int { return fivf_create("dpq_flat_ivf_create_bits", kFivfBits, f, labels, n, nlist, out); });
+}
+
+int dpq_flat_ivf_create_bits_device(dpq_flat* f, const int32_t* d_labels, int64_t n, int nlist, void* hip_stream, dpq_flat_ivf** out) {
+    return guarded([&]() -> int { return fivf_create_device("dpq_flat_ivf_create_bits_device", kFivfBits, f, d_labels, n, nlist, hip_stream, out); });
+}
+
+int dpq_flat_ivf_build_bits(dpq_flat* f, const uint8_t* centroids, int nlist, dpq_flat_ivf** out) {
+    return guarded([&]() -> int { return fivf_build_bits("dpq_flat_ivf_build_bits", f, centroids, nlist, out); });
+}
+
+int dpq_flat_ivf_probe_bits(dpq_flat_ivf* v, const uint8_t* queries, int nq, int nprobe, int32_t* lists_out, float* dists_out) {
+    return guarded([&]() -> int { return fivf_probe("dpq_flat_ivf_probe_bits", kFivfBits, v, queries, nq, nprobe, lists_out, dists_out); });
+}
+
+int dpq_flat_ivf_search_probes_bits_device(dpq_flat_ivf* v, const uint8_t* d_queries, int nq, const int32_t* d_probes, int nprobe, int top_k,
+        int32_t* d_ids, float* d_dists, void* hip_stream) {
+    return guarded([&]() -> int { return fivf_search_probes_device("dpq_flat_ivf_search_probes_bits_device", kFivfBits, v, d_queries, nq, d_probes, nprobe, top_k, d_ids, d_dists, hip_stream); });
+}
+
+int dpq_flat_ivf_search_probes_bits(dpq_flat_ivf* v, const uint8_t* queries, int nq, const int32_t* probes, int nprobe, int top_k, int32_t* ids,
+        float* dists) {
+    return guarded([&]() -> int { return fivf_search_probes("dpq_flat_ivf_search_probes_bits", kFivfBits, v, queries, nq, probes, nprobe, top_k, ids, dists); });
+}
+
+int dpq_flat_ivf_search_bits_device(dpq_flat_ivf* v, const uint8_t* d_queries, int nq, int nprobe, int top_k, int32_t* d_ids, float* d_dists,
+        void* hip_stream) {
+    return guarded([&]() -> int { return fivf_search_device("dpq_flat_ivf_search_bits_device", kFivfBits, v, d_queries, nq, nprobe, top_k, d_ids, d_dists, hip_stream); });
+}
+
+int dpq_flat_ivf_search_bits(dpq_flat_ivf* v, const uint8_t* queries, int nq, int nprobe, int top_k, int32_t* ids, float* dists) {
+    return guarded([&]() -> int { return fivf_search("dpq_flat_ivf_search_bits", kFivfBits, v, queries, nq, nprobe, top_k, ids, dists); });
 }
 
 void dpq_flat_ivf_free(dpq_flat_ivf* v) {
@@ -502,7 +681,7 @@ int dpq_flat_ivf_get_info(const dpq_flat_ivf* v, dpq_ivf_stats* out) {
     out->max_list_len = v->max_list_len;
     out->device_bytes = v->device_bytes;
     out->nlist = v->nlist;
-    out->has_centroids = v->centroids.get() ? 1 : 0;
+    out->has_centroids = v->centroids.get() || v->bcent.get() ? 1 : 0;
     return DPQ_OK;
     });
 }
@@ -522,49 +701,49 @@ int dpq_flat_ivf_get(const dpq_flat_ivf* v, int64_t* offsets_out, int32_t* ids_o
 }
 
 int dpq_flat_ivf_probe(dpq_flat_ivf* v, const float* queries, int nq, int nprobe, int32_t* lists_out, float* dists_out) {
-    return guarded([&]() -> int { return fivf_probe("dpq_flat_ivf_probe", false, v, queries, nq, nprobe, lists_out, dists_out); });
+    return guarded([&]() -> int { return fivf_probe("dpq_flat_ivf_probe", kFivfF32, v, queries, nq, nprobe, lists_out, dists_out); });
 }
 
 int dpq_flat_ivf_probe_bytes(dpq_flat_ivf* v, const void* queries, int nq, int nprobe, int32_t* lists_out, float* dists_out) {
-    return guarded([&]() -> int { return fivf_probe("dpq_flat_ivf_probe_bytes", true, v, queries, nq, nprobe, lists_out, dists_out); });
+    return guarded([&]() -> int { return fivf_probe("dpq_flat_ivf_probe_bytes", kFivfBytes, v, queries, nq, nprobe, lists_out, dists_out); });
 }
 
 int dpq_flat_ivf_search_probes_device(dpq_flat_ivf* v, const float* d_queries, int nq, const int32_t* d_probes, int nprobe, int top_k, int32_t* d_ids,
         float* d_dists, void* hip_stream) {
-    return guarded([&]() -> int { return fivf_search_probes_device("dpq_flat_ivf_search_probes_device", false, v, d_queries, nq, d_probes, nprobe, top_k, d_ids, d_dists, hip_stream); });
+    return guarded([&]() -> int { return fivf_search_probes_device("dpq_flat_ivf_search_probes_device", kFivfF32, v, d_queries, nq, d_probes, nprobe, top_k, d_ids, d_dists, hip_stream); });
 }
 
 int dpq_flat_ivf_search_probes_bytes_device(dpq_flat_ivf* v, const void* d_queries, int nq, const int32_t* d_probes, int nprobe, int top_k, int32_t* d_ids,
         float* d_dists, void* hip_stream) {
-    return guarded([&]() -> int { return fivf_search_probes_device("dpq_flat_ivf_search_probes_bytes_device", true, v, d_queries, nq, d_probes, nprobe, top_k, d_ids, d_dists, hip_stream); });
+    return guarded([&]() -> int { return fivf_search_probes_device("dpq_flat_ivf_search_probes_bytes_device", kFivfBytes, v, d_queries, nq, d_probes, nprobe, top_k, d_ids, d_dists, hip_stream); });
 }
 
 int dpq_flat_ivf_search_probes(dpq_flat_ivf* v, const float* queries, int nq, const int32_t* probes, int nprobe, int top_k, int32_t* ids,
         float* dists) {
-    return guarded([&]() -> int { return fivf_search_probes("dpq_flat_ivf_search_probes", false, v, queries, nq, probes, nprobe, top_k, ids, dists); });
+    return guarded([&]() -> int { return fivf_search_probes("dpq_flat_ivf_search_probes", kFivfF32, v, queries, nq, probes, nprobe, top_k, ids, dists); });
 }
 
 int dpq_flat_ivf_search_probes_bytes(dpq_flat_ivf* v, const void* queries, int nq, const int32_t* probes, int nprobe, int top_k, int32_t* ids,
         float* dists) {
-    return guarded([&]() -> int { return fivf_search_probes("dpq_flat_ivf_search_probes_bytes", true, v, queries, nq, probes, nprobe, top_k, ids, dists); });
+    return guarded([&]() -> int { return fivf_search_probes("dpq_flat_ivf_search_probes_bytes", kFivfBytes, v, queries, nq, probes, nprobe, top_k, ids, dists); });
 }
 
 int dpq_flat_ivf_search_device(dpq_flat_ivf* v, const float* d_queries, int nq, int nprobe, int top_k, int32_t* d_ids, float* d_dists,
         void* hip_stream) {
-    return guarded([&]() -> int { return fivf_search_device("dpq_flat_ivf_search_device", false, v, d_queries, nq, nprobe, top_k, d_ids, d_dists, hip_stream); });
+    return guarded([&]() -> int { return fivf_search_device("dpq_flat_ivf_search_device", kFivfF32, v, d_queries, nq, nprobe, top_k, d_ids, d_dists, hip_stream); });
 }
 
 int dpq_flat_ivf_search_bytes_device(dpq_flat_ivf* v, const void* d_queries, int nq, int nprobe, int top_k, int32_t* d_ids, float* d_dists,
         void* hip_stream) {
-    return guarded([&]() -> int { return fivf_search_device("dpq_flat_ivf_search_bytes_device", true, v, d_queries, nq, nprobe, top_k, d_ids, d_dists, hip_stream); });
+    return guarded([&]() -> int { return fivf_search_device("dpq_flat_ivf_search_bytes_device", kFivfBytes, v, d_queries, nq, nprobe, top_k, d_ids, d_dists, hip_stream); });
 }
 
 int dpq_flat_ivf_search(dpq_flat_ivf* v, const float* queries, int nq, int nprobe, int top_k, int32_t* ids, float* dists) {
-    return guarded([&]() -> int { return fivf_search("dpq_flat_ivf_search", false, v, queries, nq, nprobe, top_k, ids, dists); });
+    return guarded([&]() -> int { return fivf_search("dpq_flat_ivf_search", kFivfF32, v, queries, nq, nprobe, top_k, ids, dists); });
 }
 
 int dpq_flat_ivf_search_bytes(dpq_flat_ivf* v, const void* queries, int nq, int nprobe, int top_k, int32_t* ids, float* dists) {
-    return guarded([&]() -> int { return fivf_search("dpq_flat_ivf_search_bytes", true, v, queries, nq, nprobe, top_k, ids, dists); });
+    return guarded([&]() -> int { return fivf_search("dpq_flat_ivf_search_bytes", kFivfBytes, v, queries, nq, nprobe, top_k, ids, dists); });
 }
 
 }  // extern "C"

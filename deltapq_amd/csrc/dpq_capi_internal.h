@@ -232,6 +232,10 @@ struct dpq_ivf {
 
 // Inverted lists over the rows of one fp32 or byte dpq_flat handle (dpq_flat_ivf_*, dpq_capi_flat_ivf.cpp): row numbers into the
 // handle's own rows, and the workspace every search on it works in.
+// What a dpq_flat_ivf is over, and so which set of entry points serves it: fp32 rows (no suffix), byte rows (_bytes),
+// binary rows (_bits).
+enum { kFivfF32 = 0, kFivfBytes = 1, kFivfBits = 2 };
+
 struct dpq_flat_ivf {
     dpq_flat* flat = nullptr;       // the handle it was made on; freed before dpq_flat_close
     int device = 0;
@@ -256,8 +260,11 @@ struct dpq_flat_ivf {
     size_t probes_n = 0, pairs_n = 0, sort_n = 0, part_ids_n = 0, part_dists_n = 0, tmp_ids_n = 0, tmp_dists_n = 0, keys_n = 0,
            state_n = 0, q_n = 0, dists_n = 0, cdists_n = 0, dprobes_n = 0, ids_n = 0;
     // a structure over a byte handle (dpq_flat_ivf_*_bytes): the host forms' queries as given; a call's queries as the
-    // handle stores rows, [nq][Dp] int8 with their norms (d_q then holds them widened to fp32, for the coarse step)
-    bool bytes = false;
+    // handle stores rows, [nq][Dp] int8 with their norms (d_q then holds them widened to fp32, for the coarse step).
+    // Over a binary handle (dpq_flat_ivf_*_bits): q_raw likewise, q8 the queries as the handle stores rows, [nq + 64][Dp]
+    // bytes (the Hamming kernel of the coarse step reads whole query tiles), and the centroids are bcent, not `centroids`
+    int kind = kFivfF32;
+    DevBuf<uint8_t> bcent;          // [nlist][Dp] packed centroids, prepared as the handle's rows are; NULL: none set
     DevBuf<uint8_t> q_raw;
     DevBuf<int8_t> q8;
     DevBuf<int32_t> qnorm;

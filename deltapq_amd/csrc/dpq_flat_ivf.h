@@ -1,7 +1,8 @@
 // dpq_flat_ivf.h -- launch interface of the inverted-list scan over raw fp32 rows (dpq_flat_ivf.hip): exact distances of
 // the queries to the rows of the lists they probe, a running top-k per (query, probed list) (include/deltapq_amd.h "IVF
 // search over raw vectors"), and of its sibling over byte rows on the int8 matrix cores
-// (dpq_flat_ivf_u8.hip, "IVF search over byte vectors").  The lists are row numbers into a dpq_flat handle's own padded rows; they
+// (dpq_flat_ivf_u8.hip, "IVF search over byte vectors") and over binary rows by Hamming distance
+// (dpq_flat_ivf_bits.hip, "IVF search over binary vectors").  The lists are row numbers into a dpq_flat handle's own padded rows; they
 // come from dpq_ivf.h's launch_ivf_label_keys and ivf_scan_and_sort, the probe rows from its launch_ivf_probes.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -84,5 +85,31 @@ hipError_t launch_flat_ivf_scan_u8(const FlatIvfListsU8& lists, const int8_t* d_
 // otherwise the caller's bytes as they are.
 hipError_t launch_flat_ivf_widen(const void* d_in, int64_t rows, int D, int in_stride, int Dp, bool stored, bool is_signed,
                                  float* d_out, hipStream_t stream);
+
+// ---- binary rows (dpq_flat_ivf_bits.hip) -----------------------------------------------------------------------------
+constexpr int kFlatIvfGroupBits = 4;  // the binary scan's shipped group: the fastest measured at nprobe 16
+
+// flat_ivf_group for the binary scan, whose LDS is the buffers alone: a lane keeps its row number in a register and the
+// queries are read as scalars (Wp, the words of a row, is part of the rule for a form that stages them).
+int flat_ivf_group_bits(int top_k, int Wp, int group);
+
+// What the binary scan runs over: a kFlatBits base's rows [n][Wp] uint32 (dpq_flat.h "binary vectors": Wp * 4 =
+// flat_bits_row_bytes(D), spare bits and padding zero, 16-byte aligned); the lists as in FlatIvfLists.
+struct FlatIvfListsBits {
+    const uint32_t* rows = nullptr;
+    int Wp = 0;
+    int64_t id_offset = 0;
+    const int64_t* offsets = nullptr;
+    const uint32_t* list_rows = nullptr;
+    int nlist = 0;
+};
+
+// launch_flat_ivf_scan over binary rows.  d_queries [nq][Wp]: the queries as the rows are stored,
+// launch_flat_bits_prepare's output.  The distance of (row, query) is the population count of their XOR, an integer,
+// converted to fp32 exactly; the key is flat_dist_bits_kernel's.  The same pairs, the same output rows, the same order and
+// padding; the answer does not depend on the group.
+hipError_t launch_flat_ivf_scan_bits(const FlatIvfListsBits& lists, const uint32_t* d_queries, int nq, int nprobe,
+                                     const uint32_t* d_skeys, const uint32_t* d_svals, int top_k, int group, int32_t* d_part_ids,
+                                     float* d_part_dists, hipStream_t stream);
 
 }  // namespace dpq

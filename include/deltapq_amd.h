@@ -64,6 +64,10 @@
  *     with QT_8bit_direct)                        dpq_flat_ivf_probe_bytes / dpq_flat_ivf_search_bytes[_device] /
  *                                                 dpq_flat_ivf_search_probes_bytes[_device]
  *                                                 (the same over a byte handle; the list scan on the int8 matrix cores)
+ *   (none: FAISS's IndexBinaryIVF)              dpq_flat_ivf_create_bits[_device] / dpq_flat_ivf_build_bits /
+ *                                                 dpq_flat_ivf_set_centroids_bits, dpq_flat_ivf_probe_bits /
+ *                                                 dpq_flat_ivf_search_bits[_device] / dpq_flat_ivf_search_probes_bits[_device]
+ *                                                 (the same over a binary handle; centroids are packed bits, Hamming distance)
  *   (none: FAISS's IndexFlatIP: search, an      dpq_flat_search_ip / dpq_flat_search_filtered_ip /
  *     IDSelector, range_search; re-ranking by     dpq_flat_range_search_ip / dpq_flat_rerank_ip[_device],
  *     inner product)                              dpq_merge_topk_ip_host
@@ -1598,7 +1602,8 @@ int dpq_write_vecs(const char* path, const float* vectors, int64_t n, int D);
  * FAISS's IndexIVFFlat.  NO REFERENCE COUNTERPART.  A dpq_flat_ivf holds nlist inverted lists over the rows of ONE open
  * dpq_flat handle; a query forms exact distances to the rows of the lists it probes only.
  *   Formats    fp32 rows (dpq_flat_open) only.  Half, byte, quantised and binary handles, and a handle with an id map, are
- *           DPQ_ERR_ARG (byte handles have calls of their own: "IVF search over byte vectors" below).  Squared L2 only: no inner product, no filter, no range search, no shards and no CLI task yet.
+ *           DPQ_ERR_ARG (byte and binary handles have calls of their own: "IVF search over byte vectors" and "IVF search
+ *           over binary vectors" below).  Squared L2 only: no inner product, no filter, no range search, no shards and no CLI task yet.
  *   Ownership  The structure is bound to the handle it was made on and is freed (dpq_flat_ivf_free) BEFORE
  *           dpq_flat_close of that handle; both are used from one thread.
  *   Memory  No row is copied: a list is the ascending ROW NUMBERS of its members in the handle's own padded rows.
@@ -1682,6 +1687,46 @@ int dpq_flat_ivf_search_probes_bytes_device(dpq_flat_ivf* ivf, const void* d_que
 int dpq_flat_ivf_search_bytes(dpq_flat_ivf* ivf, const void* queries, int nq, int nprobe, int top_k, int32_t* ids, float* dists);
 int dpq_flat_ivf_search_bytes_device(dpq_flat_ivf* ivf, const void* d_queries, int nq, int nprobe, int top_k, int32_t* d_ids,
                                      float* d_dists, void* hip_stream);
+
+/* ---- IVF search over binary vectors: the Hamming list scan ----------
+ * FAISS's IndexBinaryIVF.  NO REFERENCE COUNTERPART.  The structure above over a BINARY handle (dpq_flat_open_bits /
+ * dpq_flat_open_binarised): the same lists of row numbers, no row copied; the scan of the probed lists is a kernel of its
+ * own -- a lane per row, the row's words in registers, the queries as scalar operands of XOR and population count
+ * (DESIGN.md 5.22).
+ *   Entry points  The *_bits calls below accept binary handles ONLY: an fp32, half, byte or quantised handle, or a handle
+ *           with an id map, is DPQ_ERR_ARG; the fp32 and *_bytes calls keep refusing a binary handle.  `queries` are packed
+ *           bits [nq][(D + 7) / 8] in dpq_flat_search_bits' layout (dimension d in bit d & 7 of byte d >> 3; the spare bits
+ *           of the last byte are ignored).  dpq_flat_ivf_get_info, _get and _free serve every kind of structure.  A call of
+ *           one kind on a structure of another -- a search, a probe, dpq_flat_ivf_set_centroids[_bits] -- is DPQ_ERR_ARG
+ *           with a message that names the structure's own set, never a read of the wrong type.
+ *   Centroids  PACKED BITS [nlist][(D + 7) / 8] in the rows' layout, ranked by Hamming distance, as FAISS's binary
+ *           quantiser ranks them.  This library does not train binary centroids: take dpq_bits_from_float of
+ *           dpq_ivf_train's centroids (with the thresholds the rows were binarised with), or any rows of the base.
+ *           dpq_flat_ivf_build_bits labels a row with its nearest centroid by (Hamming distance, list number) -- ties are
+ *           common, the lower list number wins -- and keeps the centroids; dpq_flat_ivf_set_centroids_bits attaches them to
+ *           lists made from labels; dpq_flat_ivf_probe_bits gives each query's nprobe nearest centroids by the same order,
+ *           dists_out (may be NULL) their Hamming distances as fp32.  device_bytes counts the centroids as stored, nlist
+ *           rows of (D + 7) / 8 bytes padded to a multiple of 16.
+ *   Answer  For query q exactly what dpq_flat_search_filtered_bits returns under a filter that allows the union of the
+ *           probed lists, bit for bit: distance = the Hamming distance, an integer, as fp32; reported id = row + id_offset;
+ *           order by (distance bits, id); padding -1 / +inf; a repeated probe counts once, a negative probe is padding, an
+ *           entry >= nlist is DPQ_ERR_ARG as above.
+ *   Limits  The binary handle's (D <= DPQ_FLAT_BITS_MAX_D) and the structure's above (nlist <= 65536, nprobe <=
+ *           min(nlist, 1024), top_k <= 2048, fewer than 2^31 rows).  No filter, no range search, no id map, no shards and
+ *           no CLI task yet.  State and ownership as above. */
+int dpq_flat_ivf_create_bits(dpq_flat* flat, const int32_t* labels, int64_t n, int nlist, dpq_flat_ivf** out);
+int dpq_flat_ivf_create_bits_device(dpq_flat* flat, const int32_t* d_labels, int64_t n, int nlist, void* hip_stream,
+                                    dpq_flat_ivf** out);
+int dpq_flat_ivf_build_bits(dpq_flat* flat, const uint8_t* centroids, int nlist, dpq_flat_ivf** out);
+int dpq_flat_ivf_set_centroids_bits(dpq_flat_ivf* ivf, const uint8_t* centroids, int nlist);
+int dpq_flat_ivf_probe_bits(dpq_flat_ivf* ivf, const uint8_t* queries, int nq, int nprobe, int32_t* lists_out, float* dists_out);
+int dpq_flat_ivf_search_probes_bits(dpq_flat_ivf* ivf, const uint8_t* queries, int nq, const int32_t* probes, int nprobe,
+                                    int top_k, int32_t* ids, float* dists);
+int dpq_flat_ivf_search_probes_bits_device(dpq_flat_ivf* ivf, const uint8_t* d_queries, int nq, const int32_t* d_probes,
+                                           int nprobe, int top_k, int32_t* d_ids, float* d_dists, void* hip_stream);
+int dpq_flat_ivf_search_bits(dpq_flat_ivf* ivf, const uint8_t* queries, int nq, int nprobe, int top_k, int32_t* ids, float* dists);
+int dpq_flat_ivf_search_bits_device(dpq_flat_ivf* ivf, const uint8_t* d_queries, int nq, int nprobe, int top_k, int32_t* d_ids,
+                                    float* d_dists, void* hip_stream);
 
 /* ---- measurement -------------------------------------------------------- */
 int dpq_profile_enable(dpq_index* idx, int on);  /* 0 off, 1 every kernel, 2 scan launches only (less event overhead) */
