@@ -1857,7 +1857,9 @@ class FlatIndex(_FlatIndexBase):
 
 class FlatIVF:
     """Inverted lists over the rows of one FlatIndex (dpq_flat_ivf, include/deltapq_amd.h "IVF search over raw vectors"):
-    exact distances to the rows of the lists a query probes, FAISS's IndexIVFFlat.  fp32 rows and squared L2 only.  Keeps
+    exact distances to the rows of the lists a query probes, FAISS's IndexIVFFlat -- and, over a FlatIndexHalf or a
+    FlatIndexSQ, its IndexIVFScalarQuantizer with QT_fp16 / QT_bf16 / QT_8bit / QT_4bit: the same methods, fp32 queries and
+    centroids, and bit for bit the answers of a FlatIVF over the rows widened or decoded to fp32.  Squared L2 only.  Keeps
     its index alive; close it (or leave its `with` block) before the index is closed."""
 
     def __init__(self, flat_index, handle):

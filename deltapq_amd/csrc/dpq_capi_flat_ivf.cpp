@@ -1,5 +1,6 @@
 // dpq_capi_flat_ivf.cpp -- the dpq_flat_ivf_* entry points of include/deltapq_amd.h (kernels in dpq_flat_ivf.hip,
-// dpq_flat_ivf_u8.hip and dpq_flat_ivf_bits.hip): inverted lists over the rows of an fp32, a byte or a binary dpq_flat handle,
+// dpq_flat_ivf_narrow.hip, dpq_flat_ivf_u8.hip and dpq_flat_ivf_bits.hip): inverted lists over the rows of an fp32 (or half, or
+// scalar-quantised: the formats that take fp32 queries, one kind), a byte or a binary dpq_flat handle,
 // built on the device from labels or from centroids, and the search that forms exact distances to the rows of the lists a
 // query probes.  The fp32 entry points, the *_bytes and the *_bits ones run the same code; `kind` (kFivfF32, kFivfBytes,
 // kFivfBits) says which kind of handle, of queries and of centroids a call is about.
@@ -19,8 +20,8 @@ int fivf_enter_flat(const std::string& who, dpq_flat* f, int kind) {
         return fail(DPQ_ERR_ARG, who + ": needs a handle of binary rows (dpq_flat_open_bits / dpq_flat_open_binarised)");
     if (kind == kFivfBytes && f->format != dpq::kFlatU8 && f->format != dpq::kFlatI8)
         return fail(DPQ_ERR_ARG, who + ": needs a handle of byte rows (dpq_flat_open_u8 / dpq_flat_open_i8)");
-    if (kind == kFivfF32 && f->format != dpq::kFlatF32)
-        return fail(DPQ_ERR_ARG, who + ": needs a handle of fp32 rows (dpq_flat_open); byte handles have the *_bytes calls, binary handles the *_bits calls; half and quantised handles are not supported");
+    if (kind == kFivfF32 && dpq::flat_query_format(f->format) != dpq::kFlatF32)
+        return fail(DPQ_ERR_ARG, who + ": needs a handle that takes fp32 queries (fp32, half or scalar-quantised rows); byte handles have the *_bytes calls, binary handles the *_bits calls");
     if (f->map.get()) return fail(DPQ_ERR_ARG, who + ": a handle with an id map (dpq_flat_set_id_map) is not supported");
     if (f->n > 0x7fffffff) return fail(DPQ_ERR_ARG, who + ": the handle has too many rows");
     if (int rc = flat_device_present(who)) return rc;
@@ -34,7 +35,7 @@ int fivf_from_device_labels(const std::string& who, dpq_flat* f, const int32_t* 
     if (n != f->n) return fail(DPQ_ERR_ARG, who + ": n must be the handle's row count");
     std::unique_ptr<dpq_flat_ivf> v(new dpq_flat_ivf());
     v->flat = f;
-    v->kind = f->format == dpq::kFlatBits ? kFivfBits : f->format != dpq::kFlatF32 ? kFivfBytes : kFivfF32;
+    v->kind = f->format == dpq::kFlatBits ? kFivfBits : f->format == dpq::kFlatU8 || f->format == dpq::kFlatI8 ? kFivfBytes : kFivfF32;
     v->device = f->device;
     v->nlist = nlist;
     DevBuf<uint32_t> keys, pos, keys_out, flag;
@@ -257,9 +258,10 @@ int fivf_probe_on_device(dpq_flat_ivf* v, const FivfQueries& qs, int nq, int npr
     return DPQ_OK;
 }
 
-// Pairs a workgroup of the scan takes (DESIGN.md 5.20, 5.21, 5.22).
-int fivf_group_cfg(int kind) {
-    int group = kind == kFivfBits ? dpq::kFlatIvfGroupBits : kind == kFivfBytes ? dpq::kFlatIvfGroupU8 : dpq::kFlatIvfGroup;
+// Pairs a workgroup of the scan takes (DESIGN.md 5.20, 5.21, 5.22, 5.23).
+int fivf_group_cfg(int kind, int format) {
+    int group = kind == kFivfBits ? dpq::kFlatIvfGroupBits : kind == kFivfBytes ? dpq::kFlatIvfGroupU8
+              : format != dpq::kFlatF32 ? dpq::kFlatIvfGroupNarrow : dpq::kFlatIvfGroup;
     if (dev_mode())
         if (const char* e = getenv("DPQ_FLAT_IVF_GROUP")) group = std::max(1, atoi(e));  // tests and the probe script: a cap on G
     return group;
@@ -319,7 +321,15 @@ int fivf_search_on_device(dpq_flat_ivf* v, const std::string& who, const FivfQue
     listsb.offsets = v->offsets;
     listsb.list_rows = v->rows;
     listsb.nlist = v->nlist;
-    const int group = fivf_group_cfg(v->kind);
+    dpq::FlatIvfListsNarrow listsn;  // a half or a quantised handle
+    listsn.format = f->format;
+    listsn.rows = f->rows.get() + f->rows_at;
+    listsn.Dp = f->Dp;
+    listsn.id_offset = f->id_offset;
+    listsn.offsets = v->offsets;
+    listsn.list_rows = v->rows;
+    listsn.nlist = v->nlist;
+    const int group = fivf_group_cfg(v->kind, f->format);
     DPQ_HIP(hipMemsetAsync(v->flag, 0, sizeof(uint32_t), stream));
     for (int q0 = 0; q0 < nq; q0 += per) {
         const int m = std::min(per, nq - q0);
@@ -334,6 +344,9 @@ int fivf_search_on_device(dpq_flat_ivf* v, const std::string& who, const FivfQue
         else if (v->kind == kFivfBytes)
             DPQ_HIP(dpq::launch_flat_ivf_scan_u8(lists8, qs.i8 + (size_t)q0 * f->Dp, qs.norm + q0, m, nprobe, v->skeys, v->svals,
                                                  top_k, group, v->part_ids, v->part_dists, stream));
+        else if (f->format != dpq::kFlatF32)
+            DPQ_HIP(dpq::launch_flat_ivf_scan_narrow(listsn, qs.f32 + (size_t)q0 * f->Dp, m, nprobe, v->skeys, v->svals, top_k,
+                                                     group, v->part_ids, v->part_dists, stream));
         else
             DPQ_HIP(dpq::launch_flat_ivf_scan(lists, qs.f32 + (size_t)q0 * f->Dp, m, nprobe, v->skeys, v->svals, top_k, group,
                                               v->part_ids, v->part_dists, stream));
@@ -391,7 +404,7 @@ int fivf_create(const std::string& who, int kind, dpq_flat* f, const int32_t* la
 
 // dpq_ivf_assign's arg-min over the handle's rows.  fp32: over its own padded rows, whose zero padding adds +0.0 to every
 // distance.  Bytes: over its rows widened to fp32 (the bias of unsigned rows undone) a chunk at a time, the scratch
-// bounded at 256 MB.
+// bounded at 256 MB.  Half and quantised rows: likewise, widened or decoded by launch_flat_ivf_narrow_widen.
 int fivf_labels_by_centroids(dpq_flat* f, const float* d_cent, int nlist, int32_t* d_labels) {
     if (f->format == dpq::kFlatF32) {
         DPQ_HIP(dpq::launch_ivf_argmin(reinterpret_cast<const float*>(f->rows.get() + f->rows_at), f->n, f->Dp, d_cent, nlist, nullptr,
@@ -401,10 +414,14 @@ int fivf_labels_by_centroids(dpq_flat* f, const float* d_cent, int nlist, int32_
     const int64_t chunk = std::max<int64_t>(1, ((int64_t)256 << 20) / ((int64_t)f->Dp * (int64_t)sizeof(float)));
     DevBuf<float> wide;
     if (int rc = wide.alloc((size_t)std::min(chunk, f->n) * f->Dp)) return rc;
+    const bool bytes = f->format == dpq::kFlatU8 || f->format == dpq::kFlatI8;
     for (int64_t r0 = 0; r0 < f->n; r0 += chunk) {
         const int64_t m = std::min(chunk, f->n - r0);
-        DPQ_HIP(dpq::launch_flat_ivf_widen(f->rows.get() + (size_t)r0 * f->Dp, m, f->D, f->Dp, f->Dp, true,
-                                           f->format == dpq::kFlatI8, wide, nullptr));
+        if (bytes)
+            DPQ_HIP(dpq::launch_flat_ivf_widen(f->rows.get() + (size_t)r0 * f->Dp, m, f->D, f->Dp, f->Dp, true,
+                                               f->format == dpq::kFlatI8, wide, nullptr));
+        else
+            DPQ_HIP(dpq::launch_flat_ivf_narrow_widen(f->format, f->rows.get() + f->rows_at, f->Dp, r0, m, wide, nullptr));
         DPQ_HIP(dpq::launch_ivf_argmin(wide, m, f->Dp, d_cent, nlist, nullptr, d_labels + r0, nullptr, nullptr, nullptr));
     }
     DPQ_HIP(hipDeviceSynchronize());  // `wide` is freed on return

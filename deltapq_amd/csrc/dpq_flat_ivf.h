@@ -2,7 +2,8 @@
 // the queries to the rows of the lists they probe, a running top-k per (query, probed list) (include/deltapq_amd.h "IVF
 // search over raw vectors"), and of its sibling over byte rows on the int8 matrix cores
 // (dpq_flat_ivf_u8.hip, "IVF search over byte vectors") and over binary rows by Hamming distance
-// (dpq_flat_ivf_bits.hip, "IVF search over binary vectors").  The lists are row numbers into a dpq_flat handle's own padded rows; they
+// (dpq_flat_ivf_bits.hip, "IVF search over binary vectors"), and of the fp32 scan's form for half and
+// scalar-quantised rows (dpq_flat_ivf_narrow.hip).  The lists are row numbers into a dpq_flat handle's own padded rows; they
 // come from dpq_ivf.h's launch_ivf_label_keys and ivf_scan_and_sort, the probe rows from its launch_ivf_probes.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -111,5 +112,38 @@ struct FlatIvfListsBits {
 hipError_t launch_flat_ivf_scan_bits(const FlatIvfListsBits& lists, const uint32_t* d_queries, int nq, int nprobe,
                                      const uint32_t* d_skeys, const uint32_t* d_svals, int top_k, int group, int32_t* d_part_ids,
                                      float* d_part_dists, hipStream_t stream);
+
+// ---- narrow rows: fp16, bf16, 8-bit and 4-bit scalar-quantised (dpq_flat_ivf_narrow.hip) ----------------------------------
+constexpr int kFlatIvfGroupNarrow = 4;  // the narrow scan's shipped group, every format: the fastest measured at nprobe 16
+constexpr int kFlatIvfNarrowSliceWords = 16;  // 4-byte words of a stored row that are in LDS at a time: 32 / 64 / 128 dimensions
+
+// flat_ivf_group for the narrow scan of `format`, whose LDS beside the buffers is the narrow row tile, a slice of the
+// stretch's queries, a quantised format's (lo, step) of the slice, and the row numbers.
+int flat_ivf_group_narrow(int format, int top_k, int group);
+
+// What the narrow scan runs over: a kFlatF16 / kFlatBF16 / kFlatSQ8 / kFlatSQ4 base's rows [n][Dp] as dpq_flat.h stores
+// them (Dp dimensions, a multiple of 8 / 8 / 16 / 32: a row is whole 16-byte loads; 16-byte aligned; a quantised base's
+// quantiser in front of the rows, flat_sq_quant_of); the lists as in FlatIvfLists.
+struct FlatIvfListsNarrow {
+    int format = 0;  // dpq_flat.h's kFlatF16, kFlatBF16, kFlatSQ8 or kFlatSQ4
+    const void* rows = nullptr;
+    int Dp = 0;
+    int64_t id_offset = 0;
+    const int64_t* offsets = nullptr;
+    const uint32_t* list_rows = nullptr;
+    int nlist = 0;
+};
+
+// launch_flat_ivf_scan over narrow rows.  d_queries [nq][Dp] fp32, padded with zeros.  The distance of (row, query) is
+// launch_flat_ivf_scan's over the row widened (flat_half_widen) or decoded (flat_sq_decode) to fp32, bit for bit.  The
+// same pairs, the same output rows, the same order and padding; the answer does not depend on the group.
+hipError_t launch_flat_ivf_scan_narrow(const FlatIvfListsNarrow& lists, const float* d_queries, int nq, int nprobe,
+                                       const uint32_t* d_skeys, const uint32_t* d_svals, int top_k, int group, int32_t* d_part_ids,
+                                       float* d_part_dists, hipStream_t stream);
+
+// Rows r0 .. r0 + rows - 1 of a narrow base (d_rows: the base's first row) -> the fp32 values they stand for,
+// d_out [rows][Dp]; the padding comes out as +0.0.
+hipError_t launch_flat_ivf_narrow_widen(int format, const void* d_rows, int Dp, int64_t r0, int64_t rows, float* d_out,
+                                        hipStream_t stream);
 
 }  // namespace dpq

@@ -1601,9 +1601,17 @@ int dpq_write_vecs(const char* path, const float* vectors, int64_t n, int D);
 /* ---- IVF search over raw vectors: exact distances in the probed lists ------------
  * FAISS's IndexIVFFlat.  NO REFERENCE COUNTERPART.  A dpq_flat_ivf holds nlist inverted lists over the rows of ONE open
  * dpq_flat handle; a query forms exact distances to the rows of the lists it probes only.
- *   Formats    fp32 rows (dpq_flat_open) only.  Half, byte, quantised and binary handles, and a handle with an id map, are
- *           DPQ_ERR_ARG (byte and binary handles have calls of their own: "IVF search over byte vectors" and "IVF search
- *           over binary vectors" below).  Squared L2 only: no inner product, no filter, no range search, no shards and no CLI task yet.
+ *   Formats    Every handle that takes fp32 queries: fp32 rows (dpq_flat_open), fp16 and bf16 rows (dpq_flat_open_half /
+ *           _narrowed) and 8-bit and 4-bit scalar-quantised rows (dpq_flat_open_sq / _quantised) -- FAISS's
+ *           IndexIVFScalarQuantizer with QT_fp16, QT_bf16, QT_8bit, QT_4bit.  There are no calls of their own: over a half
+ *           or a quantised handle every call below answers, bit for bit, as it would over a dpq_flat_open handle of the rows
+ *           widened (dpq_half_to_float) or decoded (dpq_sq_decode) to fp32; queries and centroids are fp32 in the caller's
+ *           units, never narrowed or quantised, and dpq_flat_ivf_build labels the widened or decoded rows.  The centroids
+ *           are padded to the handle's own row padding (8, 16 or 32 dimensions for half, 8-bit, 4-bit rows).  Byte and
+ *           binary handles, and a handle with an id map, are DPQ_ERR_ARG (byte and binary handles have calls of their own:
+ *           "IVF search over byte vectors" and "IVF search over binary vectors" below).  Squared L2 only: no inner
+ *           product, no filter, no range search, no id maps, no shards, no CLI task and no training of the quantiser or of
+ *           the centroids here (dpq_sq_train, dpq_ivf_train and dpq_ivf_assign exist).
  *   Ownership  The structure is bound to the handle it was made on and is freed (dpq_flat_ivf_free) BEFORE
  *           dpq_flat_close of that handle; both are used from one thread.
  *   Memory  No row is copied: a list is the ascending ROW NUMBERS of its members in the handle's own padded rows.
