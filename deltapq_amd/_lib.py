@@ -327,6 +327,19 @@ SYMBOLS = [
      [_VP, _VP, ctypes.c_int, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP]),
     ("dpq_flat_ivf_search_bits", ctypes.c_int, [_VP, _VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, _VP, _VP]),
     ("dpq_flat_ivf_search_bits_device", ctypes.c_int, [_VP, _VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP]),
+    # inner product, plain and _bytes: the searches take a trailing dpq_flat_filter (NULL: none)
+    *[(name % kind, ctypes.c_int, args) for kind in ("", "_bytes") for name, args in (
+        ("dpq_flat_ivf_probe_ip%s", [_VP, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP]),
+        ("dpq_flat_ivf_search_probes_ip%s", [_VP, _VP, ctypes.c_int, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP]),
+        ("dpq_flat_ivf_search_probes_ip%s_device", [_VP, _VP, ctypes.c_int, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP, _VP]),
+        ("dpq_flat_ivf_search_ip%s", [_VP, _VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP]),
+        ("dpq_flat_ivf_search_ip%s_device", [_VP, _VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP, _VP]))],
+    # the *_filtered forms of the twelve searches above: the same arguments and a trailing dpq_flat_filter (NULL: none)
+    *[(name % kind, ctypes.c_int, args + [_VP]) for kind in ("", "_bytes", "_bits") for name, args in (
+        ("dpq_flat_ivf_search_probes_filtered%s", [_VP, _VP, ctypes.c_int, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP]),
+        ("dpq_flat_ivf_search_probes_filtered%s_device", [_VP, _VP, ctypes.c_int, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP]),
+        ("dpq_flat_ivf_search_filtered%s", [_VP, _VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, _VP, _VP]),
+        ("dpq_flat_ivf_search_filtered%s_device", [_VP, _VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP]))],
     ("dpq_ivf_search_filtered", ctypes.c_int, [_VP, _VP, _VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, _VP, _VP]),
     ("dpq_ivf_search_device_filtered", ctypes.c_int, [_VP, _VP, _VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP]),
     ("dpq_ivf_search_probes_filtered", ctypes.c_int,

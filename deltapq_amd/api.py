@@ -1859,8 +1859,11 @@ class FlatIVF:
     """Inverted lists over the rows of one FlatIndex (dpq_flat_ivf, include/deltapq_amd.h "IVF search over raw vectors"):
     exact distances to the rows of the lists a query probes, FAISS's IndexIVFFlat -- and, over a FlatIndexHalf or a
     FlatIndexSQ, its IndexIVFScalarQuantizer with QT_fp16 / QT_bf16 / QT_8bit / QT_4bit: the same methods, fp32 queries and
-    centroids, and bit for bit the answers of a FlatIVF over the rows widened or decoded to fp32.  Squared L2 only.  Keeps
-    its index alive; close it (or leave its `with` block) before the index is closed."""
+    centroids, and bit for bit the answers of a FlatIVF over the rows widened or decoded to fp32.  Squared L2, or the exact inner product
+    (probe_ip, search_ip, search_probes_ip and their _torch forms: scores in the second output, padding -inf).  Every
+    search* takes id_filter=, a FlatIdFilter of the same index (FAISS's IDSelector): only the rows it allows are scanned, and
+    the answer is the unfiltered one over lists cut to those rows; probe() does not see it.  Keeps its index alive; close
+    it (or leave its `with` block) before the index is closed."""
 
     def __init__(self, flat_index, handle):
         self._lib = flat_index._lib
@@ -1927,6 +1930,77 @@ class FlatIVF:
     def _out(self, nq, cols):
         return np.empty((nq, cols), dtype=np.int32), np.empty((nq, cols), dtype=np.float32)
 
+    # a search entry point -> its form under an id filter, which takes the filter as a trailing argument
+    _FILTERED = {
+        "dpq_flat_ivf_search": "dpq_flat_ivf_search_filtered",
+        "dpq_flat_ivf_search_device": "dpq_flat_ivf_search_filtered_device",
+        "dpq_flat_ivf_search_probes": "dpq_flat_ivf_search_probes_filtered",
+        "dpq_flat_ivf_search_probes_device": "dpq_flat_ivf_search_probes_filtered_device",
+        "dpq_flat_ivf_search_bytes": "dpq_flat_ivf_search_filtered_bytes",
+        "dpq_flat_ivf_search_bytes_device": "dpq_flat_ivf_search_filtered_bytes_device",
+        "dpq_flat_ivf_search_probes_bytes": "dpq_flat_ivf_search_probes_filtered_bytes",
+        "dpq_flat_ivf_search_probes_bytes_device": "dpq_flat_ivf_search_probes_filtered_bytes_device",
+        "dpq_flat_ivf_search_bits": "dpq_flat_ivf_search_filtered_bits",
+        "dpq_flat_ivf_search_bits_device": "dpq_flat_ivf_search_filtered_bits_device",
+        "dpq_flat_ivf_search_probes_bits": "dpq_flat_ivf_search_probes_filtered_bits",
+        "dpq_flat_ivf_search_probes_bits_device": "dpq_flat_ivf_search_probes_filtered_bits_device",
+    }
+    # the inner-product entry points of this kind of structure (FlatIVFBits keeps these: the library refuses them on it)
+    _IP = dict(probe="dpq_flat_ivf_probe_ip", search="dpq_flat_ivf_search_ip", search_device="dpq_flat_ivf_search_ip_device",
+               probes="dpq_flat_ivf_search_probes_ip", probes_device="dpq_flat_ivf_search_probes_ip_device")
+
+    def _search_call(self, name, id_filter, *args):
+        """The search entry point `name` on this structure; under id_filter (a FlatIdFilter of the same flat index: only
+        the ids it allows are scanned and reported) its *_filtered form."""
+        if id_filter is not None:
+            name, args = self._FILTERED[name], args + (FlatIdFilter._handle(id_filter),)
+        check(getattr(self._lib, name)(self._h, *args), name)
+
+    def _ip_call(self, which, id_filter, *args):
+        name = self._IP[which]
+        check(getattr(self._lib, name)(self._h, *args, FlatIdFilter._handle(id_filter, optional=True)), name)
+
+    def probe_ip(self, queries, nprobe):
+        """(lists int32 [nq][nprobe], scores float32 [nq][nprobe]): each query's nprobe centroids of largest exact inner
+        product, by (score descending, list number) (dpq_flat_ivf_probe_ip[_bytes])."""
+        q = self._index._queries(queries)
+        lists, scores = self._out(q.shape[0], nprobe)
+        name = self._IP["probe"]
+        check(getattr(self._lib, name)(self._h, _np_ptr(q), q.shape[0], nprobe, _np_ptr(lists), _np_ptr(scores)), name)
+        return lists, scores
+
+    def search_ip(self, queries, nprobe, top_k, id_filter=None):
+        """The top_k rows of largest exact inner product among the nprobe lists probe_ip names (dpq_flat_ivf_search_ip[_bytes]).
+        Returns (ids int32 [nq][k], scores float32 [nq][k]) by (score descending, id), padded with -1 / -inf: what
+        search_filtered_ip gives under a filter of those lists' rows."""
+        q = self._index._queries(queries)
+        ids, scores = self._out(q.shape[0], top_k)
+        self._ip_call("search", id_filter, _np_ptr(q), q.shape[0], nprobe, top_k, _np_ptr(ids), _np_ptr(scores))
+        return ids, scores
+
+    def search_probes_ip(self, queries, probes, top_k, id_filter=None):
+        """search_ip over the caller's own lists: probes int32 [nq][nprobe], -1 = padding (dpq_flat_ivf_search_probes_ip[_bytes])."""
+        q = self._index._queries(queries)
+        p = IVF._probes(probes, q.shape[0])
+        ids, scores = self._out(q.shape[0], top_k)
+        self._ip_call("probes", id_filter, _np_ptr(q), q.shape[0], _np_ptr(p), p.shape[1], top_k, _np_ptr(ids), _np_ptr(scores))
+        return ids, scores
+
+    def search_ip_torch(self, queries, nprobe, top_k, out_ids=None, out_scores=None, id_filter=None):
+        """search_ip on device tensors, synchronous on torch's current stream (dpq_flat_ivf_search_ip[_bytes]_device)."""
+        nq, out_ids, out_scores, stream = self._torch_out(queries, top_k, out_ids, out_scores)
+        self._ip_call("search_device", id_filter, ctypes.c_void_p(queries.data_ptr()), nq, nprobe, top_k,
+                      ctypes.c_void_p(out_ids.data_ptr()), ctypes.c_void_p(out_scores.data_ptr()), stream)
+        return out_ids, out_scores
+
+    def search_probes_ip_torch(self, queries, probes, top_k, out_ids=None, out_scores=None, id_filter=None):
+        """search_probes_ip on device tensors (dpq_flat_ivf_search_probes_ip[_bytes]_device)."""
+        nq, out_ids, out_scores, stream = self._torch_out(queries, top_k, out_ids, out_scores)
+        pp, nprobe = IVF._torch_probes(probes, nq)
+        self._ip_call("probes_device", id_filter, ctypes.c_void_p(queries.data_ptr()), nq, pp, nprobe, top_k,
+                      ctypes.c_void_p(out_ids.data_ptr()), ctypes.c_void_p(out_scores.data_ptr()), stream)
+        return out_ids, out_scores
+
     def probe(self, queries, nprobe):
         """(lists int32 [nq][nprobe], dists float32 [nq][nprobe]): each query's nprobe nearest centroids by (exact L2
         distance, list number) (dpq_flat_ivf_probe)."""
@@ -1936,45 +2010,42 @@ class FlatIVF:
               "dpq_flat_ivf_probe")
         return lists, dists
 
-    def search(self, queries, nprobe, top_k):
+    def search(self, queries, nprobe, top_k, id_filter=None):
         """The top_k nearest rows of the nprobe lists nearest to each query, by exact distance (dpq_flat_ivf_search).
         Returns (ids int32 [nq][k], dists float32 [nq][k]): what search_filtered gives under a filter of those lists'
         rows, padded with -1 / +inf."""
         q = self._index._queries(queries)
         ids, dists = self._out(q.shape[0], top_k)
-        check(self._lib.dpq_flat_ivf_search(self._h, _np_ptr(q), q.shape[0], nprobe, top_k, _np_ptr(ids), _np_ptr(dists)),
-              "dpq_flat_ivf_search")
+        self._search_call("dpq_flat_ivf_search", id_filter, _np_ptr(q), q.shape[0], nprobe, top_k, _np_ptr(ids),
+                          _np_ptr(dists))
         return ids, dists
 
-    def search_probes(self, queries, probes, top_k):
+    def search_probes(self, queries, probes, top_k, id_filter=None):
         """search over the caller's own lists: probes int32 [nq][nprobe], -1 = padding (dpq_flat_ivf_search_probes)."""
         q = self._index._queries(queries)
         p = IVF._probes(probes, q.shape[0])
         ids, dists = self._out(q.shape[0], top_k)
-        check(self._lib.dpq_flat_ivf_search_probes(self._h, _np_ptr(q), q.shape[0], _np_ptr(p), p.shape[1], top_k, _np_ptr(ids),
-                                                   _np_ptr(dists)), "dpq_flat_ivf_search_probes")
+        self._search_call("dpq_flat_ivf_search_probes", id_filter, _np_ptr(q), q.shape[0], _np_ptr(p), p.shape[1], top_k,
+                          _np_ptr(ids), _np_ptr(dists))
         return ids, dists
 
     def _torch_out(self, queries, top_k, out_ids, out_dists):
         assert queries.dim() == 2 and queries.shape[1] == self._index.D
         return IVF._torch_out(queries, top_k, out_ids, out_dists)
 
-    def search_torch(self, queries, nprobe, top_k, out_ids=None, out_dists=None):
+    def search_torch(self, queries, nprobe, top_k, out_ids=None, out_dists=None, id_filter=None):
         """search on device tensors, synchronous on torch's current stream (dpq_flat_ivf_search_device)."""
         nq, out_ids, out_dists, stream = self._torch_out(queries, top_k, out_ids, out_dists)
-        check(self._lib.dpq_flat_ivf_search_device(self._h, ctypes.c_void_p(queries.data_ptr()), nq, nprobe, top_k,
-                                                   ctypes.c_void_p(out_ids.data_ptr()), ctypes.c_void_p(out_dists.data_ptr()),
-                                                   stream), "dpq_flat_ivf_search_device")
+        self._search_call("dpq_flat_ivf_search_device", id_filter, ctypes.c_void_p(queries.data_ptr()), nq, nprobe, top_k,
+                          ctypes.c_void_p(out_ids.data_ptr()), ctypes.c_void_p(out_dists.data_ptr()), stream)
         return out_ids, out_dists
 
-    def search_probes_torch(self, queries, probes, top_k, out_ids=None, out_dists=None):
+    def search_probes_torch(self, queries, probes, top_k, out_ids=None, out_dists=None, id_filter=None):
         """search_probes on device tensors, synchronous on torch's current stream (dpq_flat_ivf_search_probes_device)."""
         nq, out_ids, out_dists, stream = self._torch_out(queries, top_k, out_ids, out_dists)
         pp, nprobe = IVF._torch_probes(probes, nq)
-        check(self._lib.dpq_flat_ivf_search_probes_device(self._h, ctypes.c_void_p(queries.data_ptr()), nq, pp, nprobe, top_k,
-                                                          ctypes.c_void_p(out_ids.data_ptr()),
-                                                          ctypes.c_void_p(out_dists.data_ptr()), stream),
-              "dpq_flat_ivf_search_probes_device")
+        self._search_call("dpq_flat_ivf_search_probes_device", id_filter, ctypes.c_void_p(queries.data_ptr()), nq, pp,
+                          nprobe, top_k, ctypes.c_void_p(out_ids.data_ptr()), ctypes.c_void_p(out_dists.data_ptr()), stream)
         return out_ids, out_dists
 
     def close(self):
@@ -1999,7 +2070,12 @@ class FlatIVFBytes(FlatIVF):
     """FlatIVF over a FlatIndexU8 / FlatIndexI8 (include/deltapq_amd.h "IVF search over byte vectors"), FAISS's
     IndexIVFScalarQuantizer with QT_8bit_direct: the probed lists are scanned on the int8 matrix cores, and an answer is,
     bit for bit, the byte index's search_filtered under a filter of the probed lists' rows.  Queries are the index's own
-    kind of bytes (anything else is a TypeError); centroids stay float32 in the caller's units.  Squared L2 only."""
+    kind of bytes (anything else is a TypeError); centroids stay float32 in the caller's units.  Squared L2, or the exact
+    integer inner product (FlatIVF's probe_ip, search_ip, search_probes_ip and _torch forms); id_filter= as in FlatIVF."""
+
+    _IP = dict(probe="dpq_flat_ivf_probe_ip_bytes", search="dpq_flat_ivf_search_ip_bytes",
+               search_device="dpq_flat_ivf_search_ip_bytes_device", probes="dpq_flat_ivf_search_probes_ip_bytes",
+               probes_device="dpq_flat_ivf_search_probes_ip_bytes_device")
 
     @classmethod
     def build(cls, flat_index, centroids):
@@ -2037,21 +2113,21 @@ class FlatIVFBytes(FlatIVF):
               "dpq_flat_ivf_probe_bytes")
         return lists, dists
 
-    def search(self, queries, nprobe, top_k):
+    def search(self, queries, nprobe, top_k, id_filter=None):
         """(ids int32 [nq][k], dists float32 [nq][k]) over the nprobe lists nearest to each query (dpq_flat_ivf_search_bytes)."""
         q = self._index._queries(queries)
         ids, dists = self._out(q.shape[0], top_k)
-        check(self._lib.dpq_flat_ivf_search_bytes(self._h, _np_ptr(q), q.shape[0], nprobe, top_k, _np_ptr(ids), _np_ptr(dists)),
-              "dpq_flat_ivf_search_bytes")
+        self._search_call("dpq_flat_ivf_search_bytes", id_filter, _np_ptr(q), q.shape[0], nprobe, top_k, _np_ptr(ids),
+                          _np_ptr(dists))
         return ids, dists
 
-    def search_probes(self, queries, probes, top_k):
+    def search_probes(self, queries, probes, top_k, id_filter=None):
         """search over the caller's own lists: probes int32 [nq][nprobe], -1 = padding (dpq_flat_ivf_search_probes_bytes)."""
         q = self._index._queries(queries)
         p = IVF._probes(probes, q.shape[0])
         ids, dists = self._out(q.shape[0], top_k)
-        check(self._lib.dpq_flat_ivf_search_probes_bytes(self._h, _np_ptr(q), q.shape[0], _np_ptr(p), p.shape[1], top_k,
-                                                         _np_ptr(ids), _np_ptr(dists)), "dpq_flat_ivf_search_probes_bytes")
+        self._search_call("dpq_flat_ivf_search_probes_bytes", id_filter, _np_ptr(q), q.shape[0], _np_ptr(p), p.shape[1],
+                          top_k, _np_ptr(ids), _np_ptr(dists))
         return ids, dists
 
     def _torch_out(self, queries, top_k, out_ids, out_dists):
@@ -2065,23 +2141,19 @@ class FlatIVFBytes(FlatIVF):
             out_dists = torch.empty((nq, top_k), dtype=torch.float32, device=queries.device)
         return nq, out_ids, out_dists, ctypes.c_void_p(torch.cuda.current_stream(queries.device).cuda_stream)
 
-    def search_torch(self, queries, nprobe, top_k, out_ids=None, out_dists=None):
+    def search_torch(self, queries, nprobe, top_k, out_ids=None, out_dists=None, id_filter=None):
         """search on device tensors, synchronous on torch's current stream (dpq_flat_ivf_search_bytes_device)."""
         nq, out_ids, out_dists, stream = self._torch_out(queries, top_k, out_ids, out_dists)
-        check(self._lib.dpq_flat_ivf_search_bytes_device(self._h, ctypes.c_void_p(queries.data_ptr()), nq, nprobe, top_k,
-                                                         ctypes.c_void_p(out_ids.data_ptr()),
-                                                         ctypes.c_void_p(out_dists.data_ptr()), stream),
-              "dpq_flat_ivf_search_bytes_device")
+        self._search_call("dpq_flat_ivf_search_bytes_device", id_filter, ctypes.c_void_p(queries.data_ptr()), nq, nprobe,
+                          top_k, ctypes.c_void_p(out_ids.data_ptr()), ctypes.c_void_p(out_dists.data_ptr()), stream)
         return out_ids, out_dists
 
-    def search_probes_torch(self, queries, probes, top_k, out_ids=None, out_dists=None):
+    def search_probes_torch(self, queries, probes, top_k, out_ids=None, out_dists=None, id_filter=None):
         """search_probes on device tensors (dpq_flat_ivf_search_probes_bytes_device)."""
         nq, out_ids, out_dists, stream = self._torch_out(queries, top_k, out_ids, out_dists)
         pp, nprobe = IVF._torch_probes(probes, nq)
-        check(self._lib.dpq_flat_ivf_search_probes_bytes_device(self._h, ctypes.c_void_p(queries.data_ptr()), nq, pp, nprobe,
-                                                                top_k, ctypes.c_void_p(out_ids.data_ptr()),
-                                                                ctypes.c_void_p(out_dists.data_ptr()), stream),
-              "dpq_flat_ivf_search_probes_bytes_device")
+        self._search_call("dpq_flat_ivf_search_probes_bytes_device", id_filter, ctypes.c_void_p(queries.data_ptr()), nq, pp,
+                          nprobe, top_k, ctypes.c_void_p(out_ids.data_ptr()), ctypes.c_void_p(out_dists.data_ptr()), stream)
         return out_ids, out_dists
 
 
@@ -2445,21 +2517,21 @@ class FlatIVFBits(FlatIVF):
               "dpq_flat_ivf_probe_bits")
         return lists, dists
 
-    def search(self, queries, nprobe, top_k):
+    def search(self, queries, nprobe, top_k, id_filter=None):
         """(ids int32 [nq][k], dists float32 [nq][k]) over the nprobe lists nearest to each query (dpq_flat_ivf_search_bits)."""
         q = self._index._queries(queries)
         ids, dists = self._out(q.shape[0], top_k)
-        check(self._lib.dpq_flat_ivf_search_bits(self._h, _np_ptr(q), q.shape[0], nprobe, top_k, _np_ptr(ids), _np_ptr(dists)),
-              "dpq_flat_ivf_search_bits")
+        self._search_call("dpq_flat_ivf_search_bits", id_filter, _np_ptr(q), q.shape[0], nprobe, top_k, _np_ptr(ids),
+                          _np_ptr(dists))
         return ids, dists
 
-    def search_probes(self, queries, probes, top_k):
+    def search_probes(self, queries, probes, top_k, id_filter=None):
         """search over the caller's own lists: probes int32 [nq][nprobe], -1 = padding (dpq_flat_ivf_search_probes_bits)."""
         q = self._index._queries(queries)
         p = IVF._probes(probes, q.shape[0])
         ids, dists = self._out(q.shape[0], top_k)
-        check(self._lib.dpq_flat_ivf_search_probes_bits(self._h, _np_ptr(q), q.shape[0], _np_ptr(p), p.shape[1], top_k,
-                                                        _np_ptr(ids), _np_ptr(dists)), "dpq_flat_ivf_search_probes_bits")
+        self._search_call("dpq_flat_ivf_search_probes_bits", id_filter, _np_ptr(q), q.shape[0], _np_ptr(p), p.shape[1],
+                          top_k, _np_ptr(ids), _np_ptr(dists))
         return ids, dists
 
     def _torch_out(self, queries, top_k, out_ids, out_dists):
@@ -2473,23 +2545,19 @@ class FlatIVFBits(FlatIVF):
             out_dists = torch.empty((nq, top_k), dtype=torch.float32, device=queries.device)
         return nq, out_ids, out_dists, ctypes.c_void_p(torch.cuda.current_stream(queries.device).cuda_stream)
 
-    def search_torch(self, queries, nprobe, top_k, out_ids=None, out_dists=None):
+    def search_torch(self, queries, nprobe, top_k, out_ids=None, out_dists=None, id_filter=None):
         """search on device tensors, synchronous on torch's current stream (dpq_flat_ivf_search_bits_device)."""
         nq, out_ids, out_dists, stream = self._torch_out(queries, top_k, out_ids, out_dists)
-        check(self._lib.dpq_flat_ivf_search_bits_device(self._h, ctypes.c_void_p(queries.data_ptr()), nq, nprobe, top_k,
-                                                        ctypes.c_void_p(out_ids.data_ptr()),
-                                                        ctypes.c_void_p(out_dists.data_ptr()), stream),
-              "dpq_flat_ivf_search_bits_device")
+        self._search_call("dpq_flat_ivf_search_bits_device", id_filter, ctypes.c_void_p(queries.data_ptr()), nq, nprobe,
+                          top_k, ctypes.c_void_p(out_ids.data_ptr()), ctypes.c_void_p(out_dists.data_ptr()), stream)
         return out_ids, out_dists
 
-    def search_probes_torch(self, queries, probes, top_k, out_ids=None, out_dists=None):
+    def search_probes_torch(self, queries, probes, top_k, out_ids=None, out_dists=None, id_filter=None):
         """search_probes on device tensors (dpq_flat_ivf_search_probes_bits_device)."""
         nq, out_ids, out_dists, stream = self._torch_out(queries, top_k, out_ids, out_dists)
         pp, nprobe = IVF._torch_probes(probes, nq)
-        check(self._lib.dpq_flat_ivf_search_probes_bits_device(self._h, ctypes.c_void_p(queries.data_ptr()), nq, pp, nprobe,
-                                                               top_k, ctypes.c_void_p(out_ids.data_ptr()),
-                                                               ctypes.c_void_p(out_dists.data_ptr()), stream),
-              "dpq_flat_ivf_search_probes_bits_device")
+        self._search_call("dpq_flat_ivf_search_probes_bits_device", id_filter, ctypes.c_void_p(queries.data_ptr()), nq, pp,
+                          nprobe, top_k, ctypes.c_void_p(out_ids.data_ptr()), ctypes.c_void_p(out_dists.data_ptr()), stream)
         return out_ids, out_dists
 
 

@@ -372,15 +372,7 @@ int flat_grow_queries(dpq_flat* f, int metric, size_t qb) {
         if (!rc) rc = grow(f->qnorm, &f->qnorm_n, qb);
         if (format_of<Q> == dpq::kFlatU8 && metric == dpq::kFlatIP) {
             if (!rc) rc = grow(f->qsum, &f->qsum_n, qb);
-            if (!rc && !f->rsum8.get()) {
-                DevBuf<int32_t> sums;
-                if ((rc = sums.alloc((size_t)((f->n + 3) & ~(int64_t)3)))) return rc;
-                // the padding is read by the last stripe's 16-byte loads (and masked afterwards): keep it defined
-                DPQ_HIP(hipMemset(sums.get() + ((f->n - 1) & ~(int64_t)3), 0, 4 * sizeof(int32_t)));
-                DPQ_HIP(dpq::launch_flat_u8_sums(reinterpret_cast<const int8_t*>(f->rows.get()), f->n, f->Dp, 16384 * f->D, sums, nullptr));
-                DPQ_HIP(hipDeviceSynchronize());
-                f->rsum8 = std::move(sums);
-            }
+            if (!rc) rc = flat_ensure_rsum(f);
         }
         return rc;
     } else {
@@ -760,6 +752,19 @@ uint32_t bitmap_bits32(const uint32_t* words, int64_t n_bits, int64_t start) {
 
 }  // namespace
 
+// A u8 handle's row terms of the inner product (dpq_flat_u8.hip's rs), made on first use and kept until dpq_flat_close.
+int flat_ensure_rsum(dpq_flat* f) {
+    if (f->rsum8.get()) return DPQ_OK;
+    DevBuf<int32_t> sums;
+    if (int rc = sums.alloc((size_t)((f->n + 3) & ~(int64_t)3))) return rc;
+    // the padding is read by the last stripe's 16-byte loads (and masked afterwards): keep it defined
+    if (f->n > 0) DPQ_HIP(hipMemset(sums.get() + ((f->n - 1) & ~(int64_t)3), 0, 4 * sizeof(int32_t)));
+    DPQ_HIP(dpq::launch_flat_u8_sums(reinterpret_cast<const int8_t*>(f->rows.get()), f->n, f->Dp, 16384 * f->D, sums, nullptr));
+    DPQ_HIP(hipDeviceSynchronize());
+    f->rsum8 = std::move(sums);
+    return DPQ_OK;
+}
+
 // After the arguments that need no handle, before the handle is read.
 int flat_device_present(const std::string& who) {
     int ndev = 0;
@@ -938,6 +943,7 @@ int dpq_flat_filter_create(dpq_flat* f, const uint32_t* words, int64_t n_bits, d
     uint32_t bad = 0;
     DPQ_HIP(hipMemcpy(&bad, d_flag, sizeof bad, hipMemcpyDeviceToHost));
     if (bad) return fail(DPQ_ERR_STATE, who + ": internal error: the row list overflowed");
+    ff->words = std::move(d_words);  // the list scans of dpq_flat_ivf_search*_filtered* test a row's bit: n / 8 bytes
     *out = ff.release();
     return DPQ_OK;
     });

@@ -115,6 +115,16 @@ int fivf_kind_ok(const std::string& who, const dpq_flat_ivf* v, int kind) {
     return fail(DPQ_ERR_ARG, who + sets[v->kind]);
 }
 
+// A filter of the *_filtered calls (NULL: none) was made for the structure's own handle, which puts it on its device:
+// dpq_flat_search_filtered's checks.
+int fivf_filter_ok(const std::string& who, const dpq_flat_ivf* v, const dpq_flat_filter* ff) {
+    if (!ff) return DPQ_OK;
+    if (ff->owner != v->flat->serial) return fail(DPQ_ERR_ARG, who + ": the filter was made for another handle");
+    if (ff->device != v->device)  // defensive: a filter of the structure's handle lives on the handle's device
+        return fail(DPQ_ERR_ARG, who + ": the filter is on another device");
+    return DPQ_OK;
+}
+
 // What needs the structure's fields; then a device.
 int fivf_enter(const std::string& who, dpq_flat_ivf* v, int kind, int nprobe, bool coarse) {
     if (int rc = fivf_kind_ok(who, v, kind)) return rc;
@@ -171,8 +181,10 @@ int fivf_queries_bits(dpq_flat_ivf* v, const void* queries, int nq, bool device,
 // Byte queries [nq][D] of the handle's kind: prepared as the rows are (launch_flat_u8_prepare over the batch) and, for a
 // call with a coarse step, widened exactly to fp32 -- the caller's values, not the biased storage.  Host form: through
 // v->q_raw.
+// metric kFlatIP: out->norm is, in the place of the norms, the queries' terms qs of the unsigned inner product
+// (launch_flat_u8_sums, add = 0), or NULL on a signed handle, whose score is the int8 dot product alone.
 int fivf_queries_bytes(dpq_flat_ivf* v, const void* queries, int nq, bool device, bool coarse, hipStream_t stream,
-                       FivfQueries* out) {
+                       FivfQueries* out, int metric) {
     const int D = v->flat->D, Dp = v->flat->Dp;
     const bool is_signed = v->flat->format == dpq::kFlatI8;
     const uint8_t* raw = static_cast<const uint8_t*>(queries);
@@ -192,14 +204,19 @@ int fivf_queries_bytes(dpq_flat_ivf* v, const void* queries, int nq, bool device
     }
     out->i8 = v->q8;
     out->norm = v->qnorm;
+    if (metric == dpq::kFlatIP) {
+        if (is_signed) out->norm = nullptr;
+        else DPQ_HIP(dpq::launch_flat_u8_sums(v->q8, nq, Dp, 0, v->qnorm, stream));
+    }
     return DPQ_OK;
 }
 
 // fp32 queries [nq][D].  Host form: into v->d_q.  Device form: the caller's rows where they already are [nq][Dp] (D a
 // multiple of four, 16-byte aligned), else padded into v->d_q on `stream`.
-int fivf_queries(dpq_flat_ivf* v, const void* queries_, int nq, bool device, bool coarse, hipStream_t stream, FivfQueries* q) {
+int fivf_queries(dpq_flat_ivf* v, const void* queries_, int nq, bool device, bool coarse, hipStream_t stream, FivfQueries* q,
+                 int metric = dpq::kFlatL2) {
     if (v->kind == kFivfBits) return fivf_queries_bits(v, queries_, nq, device, stream, q);
-    if (v->kind == kFivfBytes) return fivf_queries_bytes(v, queries_, nq, device, coarse, stream, q);
+    if (v->kind == kFivfBytes) return fivf_queries_bytes(v, queries_, nq, device, coarse, stream, q, metric);
     const float* queries = static_cast<const float*>(queries_);
     const float** out = &q->f32;
     const int D = v->flat->D, Dp = v->flat->Dp;
@@ -234,8 +251,10 @@ int fivf_stage(dpq_flat_ivf* v, int nq, int nprobe, int top_k) {
 // d_cdists[nq][nprobe] their distances: the exact search over the centroids as a base.  Enqueues on `stream`.
 // A binary structure: the centroids are a kFlatBits base and the distance is Hamming's, so ties are the rule and the key
 // order settles them.  The query pointer of a batch may stand anywhere in a buffer with 64 spare rows behind its last.
+// metric kFlatIP (fp32 centroids only): the nprobe centroids of largest exact inner product, ties to the lower list number,
+// d_cdists their scores.
 int fivf_probe_on_device(dpq_flat_ivf* v, const FivfQueries& qs, int nq, int nprobe, int32_t* d_lists, float* d_cdists,
-                         hipStream_t stream) {
+                         hipStream_t stream, int metric = dpq::kFlatL2) {
     const int qb = std::min(nq, dpq::flat_query_batch(nprobe));
     int rc = grow(v->keys, &v->keys_n, (size_t)qb * dpq::flat_key_capacity(nprobe));
     if (!rc) rc = grow(v->state, &v->state_n, (size_t)qb);
@@ -248,6 +267,7 @@ int fivf_probe_on_device(dpq_flat_ivf* v, const FivfQueries& qs, int nq, int npr
     base.D = v->flat->D;
     base.Dp = v->flat->Dp;
     base.n_entries = v->nlist;
+    base.metric = metric;
     for (int q0 = 0; q0 < nq; q0 += qb) {
         const int m = std::min(qb, nq - q0);
         const dpq::FlatQueries q{bits ? nullptr : qs.f32 + (size_t)q0 * base.Dp, nullptr, nullptr, m, nullptr,
@@ -269,9 +289,10 @@ int fivf_group_cfg(int kind, int format) {
 
 // The search behind its checks, all device pointers; qs: the prepared queries.  Slices of queries: per slice the probe
 // pre-pass, the pairs sorted by list, the list scan of the structure's kind, the merge of the pairs' answers in rounds.
-// Ends with the flag word read back.
+// Ends with the flag word read back.  ff (NULL: none): the scans take the rows its bitmap allows only.
 int fivf_search_on_device(dpq_flat_ivf* v, const std::string& who, const FivfQueries& qs, int nq, const int32_t* d_probes,
-                          int nprobe, int top_k, int32_t* d_ids, float* d_dists, hipStream_t stream) {
+                          int nprobe, int top_k, int32_t* d_ids, float* d_dists, hipStream_t stream, const dpq_flat_filter* ff,
+                          int metric = dpq::kFlatL2) {
     const dpq_flat* f = v->flat;
     const size_t row = (size_t)nprobe * top_k;
     const int per = (int)std::max<size_t>(1, std::min<size_t>(std::min(nq, dpq::kIvfSliceQueries), dpq::kIvfPartialBytes / (row * 8)));
@@ -329,6 +350,13 @@ int fivf_search_on_device(dpq_flat_ivf* v, const std::string& who, const FivfQue
     listsn.offsets = v->offsets;
     listsn.list_rows = v->rows;
     listsn.nlist = v->nlist;
+    lists.filter = lists8.filter = listsb.filter = listsn.filter = ff ? ff->words.get() : nullptr;
+    lists.metric = lists8.metric = listsn.metric = metric;
+    if (metric == dpq::kFlatIP && v->kind == kFivfBytes) {  // the rows' terms in the place of the norms; none for signed rows
+        if (f->format == dpq::kFlatU8)
+            if (int rc2 = flat_ensure_rsum(v->flat)) return rc2;
+        lists8.norm = f->format == dpq::kFlatU8 ? f->rsum8.get() : nullptr;
+    }
     const int group = fivf_group_cfg(v->kind, f->format);
     DPQ_HIP(hipMemsetAsync(v->flag, 0, sizeof(uint32_t), stream));
     for (int q0 = 0; q0 < nq; q0 += per) {
@@ -342,7 +370,7 @@ int fivf_search_on_device(dpq_flat_ivf* v, const std::string& who, const FivfQue
             DPQ_HIP(dpq::launch_flat_ivf_scan_bits(listsb, reinterpret_cast<const uint32_t*>(qs.bits + (size_t)q0 * f->Dp), m, nprobe,
                                                    v->skeys, v->svals, top_k, group, v->part_ids, v->part_dists, stream));
         else if (v->kind == kFivfBytes)
-            DPQ_HIP(dpq::launch_flat_ivf_scan_u8(lists8, qs.i8 + (size_t)q0 * f->Dp, qs.norm + q0, m, nprobe, v->skeys, v->svals,
+            DPQ_HIP(dpq::launch_flat_ivf_scan_u8(lists8, qs.i8 + (size_t)q0 * f->Dp, qs.norm ? qs.norm + q0 : nullptr, m, nprobe, v->skeys, v->svals,
                                                  top_k, group, v->part_ids, v->part_dists, stream));
         else if (f->format != dpq::kFlatF32)
             DPQ_HIP(dpq::launch_flat_ivf_scan_narrow(listsn, qs.f32 + (size_t)q0 * f->Dp, m, nprobe, v->skeys, v->svals, top_k,
@@ -353,6 +381,8 @@ int fivf_search_on_device(dpq_flat_ivf* v, const std::string& who, const FivfQue
         if ((rc = ivf_merge_rounds(v->part_ids, v->part_dists, v->tmp_ids, v->tmp_dists, nprobe, m, top_k,
                                    d_ids + (size_t)q0 * top_k, d_dists + (size_t)q0 * top_k, stream)))
             return rc;
+        if (metric == dpq::kFlatIP)  // the merge ordered key words: now the scores, and -inf for padding
+            DPQ_HIP(dpq::launch_flat_ivf_ip_scores(d_ids + (size_t)q0 * top_k, d_dists + (size_t)q0 * top_k, (int64_t)m * top_k, stream));
     }
     uint32_t bad = 0;
     DPQ_HIP(hipMemcpyAsync(&bad, v->flag, sizeof bad, hipMemcpyDeviceToHost, stream));
@@ -522,69 +552,74 @@ int fivf_build_bits(const std::string& who, dpq_flat* f, const uint8_t* centroid
 }
 
 int fivf_probe(const std::string& who, int kind, dpq_flat_ivf* v, const void* queries, int nq, int nprobe, int32_t* lists_out,
-               float* dists_out) {
+               float* dists_out, int metric = dpq::kFlatL2) {
     if (!v || !queries || !lists_out || nq < 0) return fail(DPQ_ERR_ARG, who + ": NULL argument or nq < 0");
     if (nprobe < 1 || nprobe > dpq::kIvfMaxProbe) return fail(DPQ_ERR_ARG, who + ": needs 1 <= nprobe <= min(nlist, 1024)");
     if (int rc = fivf_enter(who, v, kind, nprobe, true)) return rc;
     if (nq == 0) return DPQ_OK;
     FivfQueries q;
-    if (int rc = fivf_queries(v, queries, nq, false, true, nullptr, &q)) return rc;
+    if (int rc = fivf_queries(v, queries, nq, false, true, nullptr, &q)) return rc;  // (the coarse step reads no query terms)
     if (int rc = fivf_stage(v, nq, nprobe, 0)) return rc;
-    if (int rc = fivf_probe_on_device(v, q, nq, nprobe, v->d_probes, v->d_cdists, nullptr)) return rc;
+    if (int rc = fivf_probe_on_device(v, q, nq, nprobe, v->d_probes, v->d_cdists, nullptr, metric)) return rc;
     DPQ_HIP(hipMemcpy(lists_out, v->d_probes, (size_t)nq * nprobe * sizeof(int32_t), hipMemcpyDeviceToHost));
     if (dists_out) DPQ_HIP(hipMemcpy(dists_out, v->d_cdists, (size_t)nq * nprobe * sizeof(float), hipMemcpyDeviceToHost));
     return DPQ_OK;
 }
 
 int fivf_search_probes_device(const std::string& who, int kind, dpq_flat_ivf* v, const void* d_queries, int nq,
-                              const int32_t* d_probes, int nprobe, int top_k, int32_t* d_ids, float* d_dists, void* hip_stream) {
+                              const int32_t* d_probes, int nprobe, int top_k, int32_t* d_ids, float* d_dists, void* hip_stream,
+                              const dpq_flat_filter* ff = nullptr, int metric = dpq::kFlatL2) {
     if (int rc = fivf_search_args(who, v, d_queries, nq, true, d_probes, nprobe, top_k, d_ids, d_dists)) return rc;
+    if (int rc = fivf_filter_ok(who, v, ff)) return rc;
     if (int rc = fivf_enter(who, v, kind, nprobe, false)) return rc;
     if (nq == 0) return DPQ_OK;
     hipStream_t stream = (hipStream_t)hip_stream;
     FivfQueries q;
-    if (int rc = fivf_queries(v, d_queries, nq, true, false, stream, &q)) return rc;
-    return fivf_search_on_device(v, who, q, nq, d_probes, nprobe, top_k, d_ids, d_dists, stream);
+    if (int rc = fivf_queries(v, d_queries, nq, true, false, stream, &q, metric)) return rc;
+    return fivf_search_on_device(v, who, q, nq, d_probes, nprobe, top_k, d_ids, d_dists, stream, ff, metric);
 }
 
 int fivf_search_probes(const std::string& who, int kind, dpq_flat_ivf* v, const void* queries, int nq, const int32_t* probes,
-                       int nprobe, int top_k, int32_t* ids, float* dists) {
+                       int nprobe, int top_k, int32_t* ids, float* dists, const dpq_flat_filter* ff = nullptr, int metric = dpq::kFlatL2) {
     if (int rc = fivf_search_args(who, v, queries, nq, true, probes, nprobe, top_k, ids, dists)) return rc;
+    if (int rc = fivf_filter_ok(who, v, ff)) return rc;
     if (nprobe > v->nlist) return fail(DPQ_ERR_ARG, who + ": needs 1 <= nprobe <= min(nlist, 1024)");
     if (int rc = fivf_probe_rows_ok(who, v, probes, nq, nprobe)) return rc;
     if (int rc = fivf_enter(who, v, kind, nprobe, false)) return rc;
     if (nq == 0) return DPQ_OK;
     FivfQueries q;
-    if (int rc = fivf_queries(v, queries, nq, false, false, nullptr, &q)) return rc;
+    if (int rc = fivf_queries(v, queries, nq, false, false, nullptr, &q, metric)) return rc;
     if (int rc = fivf_stage(v, nq, nprobe, top_k)) return rc;
     DPQ_HIP(hipMemcpy(v->d_probes, probes, (size_t)nq * nprobe * sizeof(int32_t), hipMemcpyHostToDevice));
-    if (int rc = fivf_search_on_device(v, who, q, nq, v->d_probes, nprobe, top_k, v->d_ids, v->d_dists, nullptr)) return rc;
+    if (int rc = fivf_search_on_device(v, who, q, nq, v->d_probes, nprobe, top_k, v->d_ids, v->d_dists, nullptr, ff, metric)) return rc;
     return fivf_results_down(v, nq, top_k, ids, dists);
 }
 
 int fivf_search_device(const std::string& who, int kind, dpq_flat_ivf* v, const void* d_queries, int nq, int nprobe, int top_k,
-                       int32_t* d_ids, float* d_dists, void* hip_stream) {
+                       int32_t* d_ids, float* d_dists, void* hip_stream, const dpq_flat_filter* ff = nullptr, int metric = dpq::kFlatL2) {
     if (int rc = fivf_search_args(who, v, d_queries, nq, false, nullptr, nprobe, top_k, d_ids, d_dists)) return rc;
+    if (int rc = fivf_filter_ok(who, v, ff)) return rc;
     if (int rc = fivf_enter(who, v, kind, nprobe, true)) return rc;
     if (nq == 0) return DPQ_OK;
     hipStream_t stream = (hipStream_t)hip_stream;
     FivfQueries q;
-    if (int rc = fivf_queries(v, d_queries, nq, true, true, stream, &q)) return rc;
+    if (int rc = fivf_queries(v, d_queries, nq, true, true, stream, &q, metric)) return rc;
     if (int rc = fivf_stage(v, nq, nprobe, 0)) return rc;
-    if (int rc = fivf_probe_on_device(v, q, nq, nprobe, v->d_probes, v->d_cdists, stream)) return rc;
-    return fivf_search_on_device(v, who, q, nq, v->d_probes, nprobe, top_k, d_ids, d_dists, stream);
+    if (int rc = fivf_probe_on_device(v, q, nq, nprobe, v->d_probes, v->d_cdists, stream, metric)) return rc;
+    return fivf_search_on_device(v, who, q, nq, v->d_probes, nprobe, top_k, d_ids, d_dists, stream, ff, metric);
 }
 
 int fivf_search(const std::string& who, int kind, dpq_flat_ivf* v, const void* queries, int nq, int nprobe, int top_k,
-                int32_t* ids, float* dists) {
+                int32_t* ids, float* dists, const dpq_flat_filter* ff = nullptr, int metric = dpq::kFlatL2) {
     if (int rc = fivf_search_args(who, v, queries, nq, false, nullptr, nprobe, top_k, ids, dists)) return rc;
+    if (int rc = fivf_filter_ok(who, v, ff)) return rc;
     if (int rc = fivf_enter(who, v, kind, nprobe, true)) return rc;
     if (nq == 0) return DPQ_OK;
     FivfQueries q;
-    if (int rc = fivf_queries(v, queries, nq, false, true, nullptr, &q)) return rc;
+    if (int rc = fivf_queries(v, queries, nq, false, true, nullptr, &q, metric)) return rc;
     if (int rc = fivf_stage(v, nq, nprobe, top_k)) return rc;
-    if (int rc = fivf_probe_on_device(v, q, nq, nprobe, v->d_probes, v->d_cdists, nullptr)) return rc;
-    if (int rc = fivf_search_on_device(v, who, q, nq, v->d_probes, nprobe, top_k, v->d_ids, v->d_dists, nullptr)) return rc;
+    if (int rc = fivf_probe_on_device(v, q, nq, nprobe, v->d_probes, v->d_cdists, nullptr, metric)) return rc;
+    if (int rc = fivf_search_on_device(v, who, q, nq, v->d_probes, nprobe, top_k, v->d_ids, v->d_dists, nullptr, ff, metric)) return rc;
     return fivf_results_down(v, nq, top_k, ids, dists);
 }
 
@@ -761,6 +796,118 @@ int dpq_flat_ivf_search(dpq_flat_ivf* v, const float* queries, int nq, int nprob
 
 int dpq_flat_ivf_search_bytes(dpq_flat_ivf* v, const void* queries, int nq, int nprobe, int top_k, int32_t* ids, float* dists) {
     return guarded([&]() -> int { return fivf_search("dpq_flat_ivf_search_bytes", kFivfBytes, v, queries, nq, nprobe, top_k, ids, dists); });
+}
+
+// ---- the *_filtered set: the search of each kind under a dpq_flat_filter of the structure's handle (NULL: no filter) ----------
+
+int dpq_flat_ivf_search_probes_filtered_device(dpq_flat_ivf* v, const float* d_queries, int nq, const int32_t* d_probes, int nprobe, int top_k,
+        int32_t* d_ids, float* d_dists, void* hip_stream, const dpq_flat_filter* filter) {
+    return guarded([&]() -> int { return fivf_search_probes_device("dpq_flat_ivf_search_probes_filtered_device", kFivfF32, v, d_queries, nq, d_probes, nprobe, top_k, d_ids, d_dists, hip_stream, filter); });
+}
+
+int dpq_flat_ivf_search_probes_filtered(dpq_flat_ivf* v, const float* queries, int nq, const int32_t* probes, int nprobe, int top_k, int32_t* ids,
+        float* dists, const dpq_flat_filter* filter) {
+    return guarded([&]() -> int { return fivf_search_probes("dpq_flat_ivf_search_probes_filtered", kFivfF32, v, queries, nq, probes, nprobe, top_k, ids, dists, filter); });
+}
+
+int dpq_flat_ivf_search_filtered_device(dpq_flat_ivf* v, const float* d_queries, int nq, int nprobe, int top_k, int32_t* d_ids, float* d_dists,
+        void* hip_stream, const dpq_flat_filter* filter) {
+    return guarded([&]() -> int { return fivf_search_device("dpq_flat_ivf_search_filtered_device", kFivfF32, v, d_queries, nq, nprobe, top_k, d_ids, d_dists, hip_stream, filter); });
+}
+
+int dpq_flat_ivf_search_filtered(dpq_flat_ivf* v, const float* queries, int nq, int nprobe, int top_k, int32_t* ids, float* dists,
+        const dpq_flat_filter* filter) {
+    return guarded([&]() -> int { return fivf_search("dpq_flat_ivf_search_filtered", kFivfF32, v, queries, nq, nprobe, top_k, ids, dists, filter); });
+}
+
+int dpq_flat_ivf_search_probes_filtered_bytes_device(dpq_flat_ivf* v, const void* d_queries, int nq, const int32_t* d_probes, int nprobe, int top_k,
+        int32_t* d_ids, float* d_dists, void* hip_stream, const dpq_flat_filter* filter) {
+    return guarded([&]() -> int { return fivf_search_probes_device("dpq_flat_ivf_search_probes_filtered_bytes_device", kFivfBytes, v, d_queries, nq, d_probes, nprobe, top_k, d_ids, d_dists, hip_stream, filter); });
+}
+
+int dpq_flat_ivf_search_probes_filtered_bytes(dpq_flat_ivf* v, const void* queries, int nq, const int32_t* probes, int nprobe, int top_k, int32_t* ids,
+        float* dists, const dpq_flat_filter* filter) {
+    return guarded([&]() -> int { return fivf_search_probes("dpq_flat_ivf_search_probes_filtered_bytes", kFivfBytes, v, queries, nq, probes, nprobe, top_k, ids, dists, filter); });
+}
+
+int dpq_flat_ivf_search_filtered_bytes_device(dpq_flat_ivf* v, const void* d_queries, int nq, int nprobe, int top_k, int32_t* d_ids, float* d_dists,
+        void* hip_stream, const dpq_flat_filter* filter) {
+    return guarded([&]() -> int { return fivf_search_device("dpq_flat_ivf_search_filtered_bytes_device", kFivfBytes, v, d_queries, nq, nprobe, top_k, d_ids, d_dists, hip_stream, filter); });
+}
+
+int dpq_flat_ivf_search_filtered_bytes(dpq_flat_ivf* v, const void* queries, int nq, int nprobe, int top_k, int32_t* ids, float* dists,
+        const dpq_flat_filter* filter) {
+    return guarded([&]() -> int { return fivf_search("dpq_flat_ivf_search_filtered_bytes", kFivfBytes, v, queries, nq, nprobe, top_k, ids, dists, filter); });
+}
+
+int dpq_flat_ivf_search_probes_filtered_bits_device(dpq_flat_ivf* v, const uint8_t* d_queries, int nq, const int32_t* d_probes, int nprobe, int top_k,
+        int32_t* d_ids, float* d_dists, void* hip_stream, const dpq_flat_filter* filter) {
+    return guarded([&]() -> int { return fivf_search_probes_device("dpq_flat_ivf_search_probes_filtered_bits_device", kFivfBits, v, d_queries, nq, d_probes, nprobe, top_k, d_ids, d_dists, hip_stream, filter); });
+}
+
+int dpq_flat_ivf_search_probes_filtered_bits(dpq_flat_ivf* v, const uint8_t* queries, int nq, const int32_t* probes, int nprobe, int top_k, int32_t* ids,
+        float* dists, const dpq_flat_filter* filter) {
+    return guarded([&]() -> int { return fivf_search_probes("dpq_flat_ivf_search_probes_filtered_bits", kFivfBits, v, queries, nq, probes, nprobe, top_k, ids, dists, filter); });
+}
+
+int dpq_flat_ivf_search_filtered_bits_device(dpq_flat_ivf* v, const uint8_t* d_queries, int nq, int nprobe, int top_k, int32_t* d_ids, float* d_dists,
+        void* hip_stream, const dpq_flat_filter* filter) {
+    return guarded([&]() -> int { return fivf_search_device("dpq_flat_ivf_search_filtered_bits_device", kFivfBits, v, d_queries, nq, nprobe, top_k, d_ids, d_dists, hip_stream, filter); });
+}
+
+int dpq_flat_ivf_search_filtered_bits(dpq_flat_ivf* v, const uint8_t* queries, int nq, int nprobe, int top_k, int32_t* ids, float* dists,
+        const dpq_flat_filter* filter) {
+    return guarded([&]() -> int { return fivf_search("dpq_flat_ivf_search_filtered_bits", kFivfBits, v, queries, nq, nprobe, top_k, ids, dists, filter); });
+}
+
+// ---- inner product: the plain and the *_bytes set (a structure over binary rows is refused by its kind) --------------------
+
+int dpq_flat_ivf_probe_ip(dpq_flat_ivf* v, const float* queries, int nq, int nprobe, int32_t* lists_out, float* scores_out) {
+    return guarded([&]() -> int { return fivf_probe("dpq_flat_ivf_probe_ip", kFivfF32, v, queries, nq, nprobe, lists_out, scores_out, dpq::kFlatIP); });
+}
+
+int dpq_flat_ivf_search_probes_ip_device(dpq_flat_ivf* v, const float* d_queries, int nq, const int32_t* d_probes, int nprobe, int top_k,
+        int32_t* d_ids, float* d_scores, void* hip_stream, const dpq_flat_filter* filter) {
+    return guarded([&]() -> int { return fivf_search_probes_device("dpq_flat_ivf_search_probes_ip_device", kFivfF32, v, d_queries, nq, d_probes, nprobe, top_k, d_ids, d_scores, hip_stream, filter, dpq::kFlatIP); });
+}
+
+int dpq_flat_ivf_search_probes_ip(dpq_flat_ivf* v, const float* queries, int nq, const int32_t* probes, int nprobe, int top_k, int32_t* ids,
+        float* scores, const dpq_flat_filter* filter) {
+    return guarded([&]() -> int { return fivf_search_probes("dpq_flat_ivf_search_probes_ip", kFivfF32, v, queries, nq, probes, nprobe, top_k, ids, scores, filter, dpq::kFlatIP); });
+}
+
+int dpq_flat_ivf_search_ip_device(dpq_flat_ivf* v, const float* d_queries, int nq, int nprobe, int top_k, int32_t* d_ids, float* d_scores,
+        void* hip_stream, const dpq_flat_filter* filter) {
+    return guarded([&]() -> int { return fivf_search_device("dpq_flat_ivf_search_ip_device", kFivfF32, v, d_queries, nq, nprobe, top_k, d_ids, d_scores, hip_stream, filter, dpq::kFlatIP); });
+}
+
+int dpq_flat_ivf_search_ip(dpq_flat_ivf* v, const float* queries, int nq, int nprobe, int top_k, int32_t* ids, float* scores,
+        const dpq_flat_filter* filter) {
+    return guarded([&]() -> int { return fivf_search("dpq_flat_ivf_search_ip", kFivfF32, v, queries, nq, nprobe, top_k, ids, scores, filter, dpq::kFlatIP); });
+}
+
+int dpq_flat_ivf_probe_ip_bytes(dpq_flat_ivf* v, const void* queries, int nq, int nprobe, int32_t* lists_out, float* scores_out) {
+    return guarded([&]() -> int { return fivf_probe("dpq_flat_ivf_probe_ip_bytes", kFivfBytes, v, queries, nq, nprobe, lists_out, scores_out, dpq::kFlatIP); });
+}
+
+int dpq_flat_ivf_search_probes_ip_bytes_device(dpq_flat_ivf* v, const void* d_queries, int nq, const int32_t* d_probes, int nprobe, int top_k,
+        int32_t* d_ids, float* d_scores, void* hip_stream, const dpq_flat_filter* filter) {
+    return guarded([&]() -> int { return fivf_search_probes_device("dpq_flat_ivf_search_probes_ip_bytes_device", kFivfBytes, v, d_queries, nq, d_probes, nprobe, top_k, d_ids, d_scores, hip_stream, filter, dpq::kFlatIP); });
+}
+
+int dpq_flat_ivf_search_probes_ip_bytes(dpq_flat_ivf* v, const void* queries, int nq, const int32_t* probes, int nprobe, int top_k, int32_t* ids,
+        float* scores, const dpq_flat_filter* filter) {
+    return guarded([&]() -> int { return fivf_search_probes("dpq_flat_ivf_search_probes_ip_bytes", kFivfBytes, v, queries, nq, probes, nprobe, top_k, ids, scores, filter, dpq::kFlatIP); });
+}
+
+int dpq_flat_ivf_search_ip_bytes_device(dpq_flat_ivf* v, const void* d_queries, int nq, int nprobe, int top_k, int32_t* d_ids, float* d_scores,
+        void* hip_stream, const dpq_flat_filter* filter) {
+    return guarded([&]() -> int { return fivf_search_device("dpq_flat_ivf_search_ip_bytes_device", kFivfBytes, v, d_queries, nq, nprobe, top_k, d_ids, d_scores, hip_stream, filter, dpq::kFlatIP); });
+}
+
+int dpq_flat_ivf_search_ip_bytes(dpq_flat_ivf* v, const void* queries, int nq, int nprobe, int top_k, int32_t* ids, float* scores,
+        const dpq_flat_filter* filter) {
+    return guarded([&]() -> int { return fivf_search("dpq_flat_ivf_search_ip_bytes", kFivfBytes, v, queries, nq, nprobe, top_k, ids, scores, filter, dpq::kFlatIP); });
 }
 
 }  // extern "C"

@@ -186,11 +186,13 @@ struct dpq_flat {
     size_t r_thr_n = 0, r_pool_n = 0, r_sorted_n = 0, r_offs_n = 0;
 };
 
-// A filter of dpq_flat_search_filtered* / dpq_flat_range_search*: the ascending list of the handle's eligible rows.
+// A filter of dpq_flat_search_filtered* / dpq_flat_range_search*: the ascending list of the handle's eligible rows; and of
+// dpq_flat_ivf_search*_filtered*: the bitmap over the handle's rows the list was made from.
 struct dpq_flat_filter {
     uint64_t owner = 0;      // dpq_flat::serial
     int device = 0;
     DevBuf<uint32_t> list;   // [n_allowed]
+    DevBuf<uint32_t> words;  // [(n + 31) / 32] bit r & 31 of word r >> 5: row r is eligible; the bits beyond n are zero
     int64_t n_allowed = 0;
 };
 
@@ -536,6 +538,7 @@ int query_device_src(dpq_index* x, const dpq_filter* filt, const TableSource& sr
 int range_search_src(dpq_index* x, const TableSource& src, int nq, const float* radii, dpq_range_result** out);  // dpq_capi.cpp
 int ensure_out_stage(dpq_index* x, size_t elems);  // d_ids_stage / d_dists_stage                                  dpq_capi.cpp
 int splits_for(int n_seg_pass, int n_groups);  // scan workgroups per query group                                dpq_capi.cpp
+int flat_ensure_rsum(dpq_flat* f);  // a u8 handle's row terms of the inner product, made on first use (dpq_capi_flat.cpp)
 int flat_device_present(const std::string& who);                                                                // dpq_capi_flat.cpp
 bool lookup_id_ok(const dpq_index* x, int64_t id);                                                              // dpq_capi_lookup.cpp
 int lookup_on_device(dpq_index* x, const int32_t* d_ids, int64_t n, uint8_t* d_codes, float* d_vecs, hipStream_t stream,

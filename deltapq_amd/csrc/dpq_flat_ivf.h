@@ -41,6 +41,11 @@ struct FlatIvfLists {
     const int64_t* offsets = nullptr;
     const uint32_t* list_rows = nullptr;
     int nlist = 0;
+    const uint32_t* filter = nullptr;  // NULL, or a bitmap over the rows, [(n + 31) / 32] words, bit r & 31 of word r >> 5:
+                                       // only the rows whose bit is set are scanned (dpq_flat_ivf_device.h's fill_tile)
+    int metric = 0;  // dpq_flat.h's kFlatL2, or kFlatIP: the scan forms scores and d_part_dists holds their KEY WORDS
+                     // (flat_ip_word of the score's bits; padding -1 / +inf as ever), which launch_merge orders as it orders
+                     // distance bits: score descending, id ascending.  launch_flat_ivf_ip_scores turns the merged answer back
 };
 
 // The list scan.  d_skeys / d_svals [n_pairs = nq * nprobe]: the sorted pairs.  A workgroup takes `group` consecutive
@@ -53,6 +58,10 @@ struct FlatIvfLists {
 hipError_t launch_flat_ivf_scan(const FlatIvfLists& lists, const float* d_queries, int nq, int nprobe, const uint32_t* d_skeys,
                                 const uint32_t* d_svals, int top_k, int group, int32_t* d_part_ids, float* d_part_dists,
                                 hipStream_t stream);
+
+// After the last merge round of an inner-product search: d_vals[i], a key word, becomes the score's bits; an entry whose
+// d_ids[i] is negative becomes -inf.  n entries.
+hipError_t launch_flat_ivf_ip_scores(const int32_t* d_ids, float* d_vals, int64_t n, hipStream_t stream);
 
 // ---- byte rows (dpq_flat_ivf_u8.hip) -------------------------------------------------------------------------------
 constexpr int kFlatIvfGroupU8 = 8;  // the byte scan's shipped group: the fastest measured at nprobe 16
@@ -71,12 +80,17 @@ struct FlatIvfListsU8 {
     const int64_t* offsets = nullptr;
     const uint32_t* list_rows = nullptr;
     int nlist = 0;
+    const uint32_t* filter = nullptr;  // see FlatIvfLists
+    int metric = 0;                    // see FlatIvfLists
 };
 
 // launch_flat_ivf_scan over byte rows.  d_queries [nq][Dp] int8 and d_qnorm [nq]: the queries as the rows are stored,
 // launch_flat_u8_prepare's output.  The distance of (row, query) is norm[row] + qnorm[query] - 2 * (their int8 dot
 // product) in int32 -- the exact sum of (v[d] - q[d])^2 -- converted once to fp32, round to nearest even.  The same pairs,
-// the same output rows, the same order and padding; the answer does not depend on the group.
+// the same output rows, the same order and padding; the answer does not depend on the group.  lists.metric kFlatIP: the score
+// is the int32 S of dpq_flat_u8.hip's header, converted once: signed rows, the int8 dot product, lists.norm and d_qnorm both
+// NULL; unsigned rows, dot + rs[row] + qs[query] with rs in lists.norm (launch_flat_u8_sums, add = 16384 D) and qs in
+// d_qnorm (add = 0).
 hipError_t launch_flat_ivf_scan_u8(const FlatIvfListsU8& lists, const int8_t* d_queries, const int32_t* d_qnorm, int nq,
                                    int nprobe, const uint32_t* d_skeys, const uint32_t* d_svals, int top_k, int group,
                                    int32_t* d_part_ids, float* d_part_dists, hipStream_t stream);
@@ -103,6 +117,7 @@ struct FlatIvfListsBits {
     const int64_t* offsets = nullptr;
     const uint32_t* list_rows = nullptr;
     int nlist = 0;
+    const uint32_t* filter = nullptr;  // see FlatIvfLists
 };
 
 // launch_flat_ivf_scan over binary rows.  d_queries [nq][Wp]: the queries as the rows are stored,
@@ -132,6 +147,8 @@ struct FlatIvfListsNarrow {
     const int64_t* offsets = nullptr;
     const uint32_t* list_rows = nullptr;
     int nlist = 0;
+    const uint32_t* filter = nullptr;  // see FlatIvfLists
+    int metric = 0;                    // see FlatIvfLists
 };
 
 // launch_flat_ivf_scan over narrow rows.  d_queries [nq][Dp] fp32, padded with zeros.  The distance of (row, query) is

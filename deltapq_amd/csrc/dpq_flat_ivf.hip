@@ -63,7 +63,7 @@ __device__ __forceinline__ void load_slice(float4 (&pre)[8], const float* __rest
 }
 
 // grid: the runs; 256 threads; dynamic LDS: the tiles, then G buffers of cap = 2 P2 keys.
-template <int QPL>
+template <int QPL, bool FILTERED, int METRIC>
 __global__ __launch_bounds__(256) void flat_ivf_scan_kernel(const float* __restrict__ rows, int Dp, int64_t id_offset,
                                                             const int64_t* __restrict__ offsets,
                                                             const uint32_t* __restrict__ list_rows, int nlist,
@@ -71,7 +71,8 @@ __global__ __launch_bounds__(256) void flat_ivf_scan_kernel(const float* __restr
                                                             const uint32_t* __restrict__ skeys,
                                                             const uint32_t* __restrict__ svals, int64_t n_pairs, int G,
                                                             int top_k, int cap, int32_t* __restrict__ part_ids,
-                                                            float* __restrict__ part_dists) {
+                                                            float* __restrict__ part_dists,
+                                                            const uint32_t* __restrict__ fbits) {
     extern __shared__ __attribute__((aligned(16))) unsigned char flat_ivf_smem[];
     float* Rs = reinterpret_cast<float*>(flat_ivf_smem);          // [SD][RS]
     float* Qs = Rs + SD * RS;                                     // [SD][GM]
@@ -106,10 +107,14 @@ __global__ __launch_bounds__(256) void flat_ivf_scan_kernel(const float* __restr
             s_thr[tid] = kFlatNoKey;
         }
         const bool active = QPL * ty < nqs;  // (a wavefront's lanes share ty)
-        for (int64_t base = lo; base < hi; base += TR) {
+        for (int64_t base = lo; base < hi; base += FILTERED ? 0 : TR) {
             __syncthreads();  // the tile before is done with s_rows; the first tile: the counts above are in place
-            s_rows[tid] = base + tid < hi ? list_rows[base + tid] : kNoRow;
-            __syncthreads();
+            if constexpr (FILTERED) {  // the next up to 256 eligible rows; base moves to where the next tile starts
+                if (fill_tile(s_rows, list_rows, base, hi, fbits, tid) == 0) break;  // the list ended on no eligible row
+            } else {
+                s_rows[tid] = base + tid < hi ? list_rows[base + tid] : kNoRow;
+                __syncthreads();
+            }
             double acc[QPL][4];
 #pragma unroll
             for (int i = 0; i < QPL; ++i)
@@ -154,10 +159,10 @@ __global__ __launch_bounds__(256) void flat_ivf_scan_kernel(const float* __restr
                         }
 #pragma unroll
                         for (int i = 0; i < QPL; ++i) {
-                            accumulate<kFlatL2>(acc[i][0], v.x, q[i]);
-                            accumulate<kFlatL2>(acc[i][1], v.y, q[i]);
-                            accumulate<kFlatL2>(acc[i][2], v.z, q[i]);
-                            accumulate<kFlatL2>(acc[i][3], v.w, q[i]);
+                            accumulate<METRIC>(acc[i][0], v.x, q[i]);
+                            accumulate<METRIC>(acc[i][1], v.y, q[i]);
+                            accumulate<METRIC>(acc[i][2], v.z, q[i]);
+                            accumulate<METRIC>(acc[i][3], v.w, q[i]);
                         }
                     }
                 }
@@ -174,13 +179,13 @@ __global__ __launch_bounds__(256) void flat_ivf_scan_kernel(const float* __restr
                     for (int j = 0; j < 4; ++j) {
                         const uint32_t row = s_rows[4 * tx + j];
                         if (row == kNoRow) continue;
-                        const uint64_t key = make_key<kFlatL2>(acc[i][j], (uint32_t)(id_offset + (int64_t)row));
+                        const uint64_t key = make_key<METRIC>(acc[i][j], (uint32_t)(id_offset + (int64_t)row));
                         if (key < thr) b[atomicAdd(&s_cnt[qs], 1u)] = key;  // < cap: the tile had room for its 256 rows
                     }
                 }
             }
             __syncthreads();
-            if (base + TR < hi) sink_make_room(buf, s_cnt, s_thr, nqs, cap, top_k, tid);
+            if (base + (FILTERED ? 0 : TR) < hi) sink_make_room(buf, s_cnt, s_thr, nqs, cap, top_k, tid);
         }
         if (hi > lo) sink_sort(buf, s_cnt, nqs, cap, tid);  // (behind the last tile's closing barrier)
         // the stretch's answers: pair i = q * nprobe + j goes to row j * nq + q.  A padding pair, or an empty list: padding
@@ -196,14 +201,14 @@ __global__ __launch_bounds__(256) void flat_ivf_scan_kernel(const float* __restr
 }
 
 // hipFuncSetAttribute is per device
-template <int QPL>
+template <int QPL, bool FILTERED, int METRIC>
 hipError_t ensure_scan_lds() {
     static std::atomic<bool> done[64];
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
     if (dev < 0 || dev >= 64 || !done[dev].load(std::memory_order_acquire)) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&flat_ivf_scan_kernel<QPL>),
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&flat_ivf_scan_kernel<QPL, FILTERED, METRIC>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kLdsBytes - kStaticBytes));
         if (e != hipSuccess) return e;
         if (dev >= 0 && dev < 64) done[dev].store(true, std::memory_order_release);
@@ -211,17 +216,24 @@ hipError_t ensure_scan_lds() {
     return hipSuccess;
 }
 
-template <int QPL>
+template <int QPL, bool FILTERED, int METRIC>
 hipError_t launch_scan(const FlatIvfLists& L, const float* d_queries, int nq, int nprobe, const uint32_t* d_skeys,
                        const uint32_t* d_svals, int64_t n_pairs, int G, int top_k, int cap, int32_t* d_part_ids,
                        float* d_part_dists, hipStream_t stream) {
-    if (hipError_t e = ensure_scan_lds<QPL>()) return e;
+    if (hipError_t e = ensure_scan_lds<QPL, FILTERED, METRIC>()) return e;
     const size_t lds = kTileBytes + (size_t)G * cap * sizeof(uint64_t);
     const dim3 grid((unsigned)((n_pairs + G - 1) / G)), block(256);
-    flat_ivf_scan_kernel<QPL><<<grid, block, lds, stream>>>(L.rows, L.Dp, L.id_offset, L.offsets, L.list_rows, L.nlist, d_queries,
-                                                            nq, nprobe, d_skeys, d_svals, n_pairs, G, top_k, cap, d_part_ids,
-                                                            d_part_dists);
+    flat_ivf_scan_kernel<QPL, FILTERED, METRIC><<<grid, block, lds, stream>>>(L.rows, L.Dp, L.id_offset, L.offsets, L.list_rows, L.nlist,
+                                                                      d_queries, nq, nprobe, d_skeys, d_svals, n_pairs, G, top_k,
+                                                                      cap, d_part_ids, d_part_dists, L.filter);
     return hipGetLastError();
+}
+
+// a thread per entry of the merged answer: the key word back to the score's bits, padding to -inf
+__global__ __launch_bounds__(256) void flat_ivf_ip_scores_kernel(const int32_t* __restrict__ ids, float* __restrict__ vals, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    vals[i] = ids[i] < 0 ? -INFINITY : __uint_as_float(flat_ip_word(__float_as_uint(vals[i])));
 }
 
 int key_bits(int nlist) {
@@ -265,6 +277,13 @@ hipError_t flat_ivf_sort_pairs(void* d_temp, size_t* temp_bytes, const uint32_t*
                                               stream);
 }
 
+hipError_t launch_flat_ivf_ip_scores(const int32_t* d_ids, float* d_vals, int64_t n, hipStream_t stream) {
+    if (n <= 0) return hipSuccess;
+    if (!d_ids || !d_vals) return hipErrorInvalidValue;
+    flat_ivf_ip_scores_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream>>>(d_ids, d_vals, n);
+    return hipGetLastError();
+}
+
 hipError_t launch_flat_ivf_scan(const FlatIvfLists& L, const float* d_queries, int nq, int nprobe, const uint32_t* d_skeys,
                                 const uint32_t* d_svals, int top_k, int group, int32_t* d_part_ids, float* d_part_dists,
                                 hipStream_t stream) {
@@ -276,11 +295,13 @@ hipError_t launch_flat_ivf_scan(const FlatIvfLists& L, const float* d_queries, i
         return hipErrorInvalidValue;
     const int cap = scan_cap(top_k), G = flat_ivf_group(top_k, group);
     const int64_t n_pairs = (int64_t)nq * nprobe;
-    if (G == 16)
-        return launch_scan<4>(L, d_queries, nq, nprobe, d_skeys, d_svals, n_pairs, G, top_k, cap, d_part_ids, d_part_dists, stream);
-    if (G == 8)
-        return launch_scan<2>(L, d_queries, nq, nprobe, d_skeys, d_svals, n_pairs, G, top_k, cap, d_part_ids, d_part_dists, stream);
-    return launch_scan<1>(L, d_queries, nq, nprobe, d_skeys, d_svals, n_pairs, G, top_k, cap, d_part_ids, d_part_dists, stream);
+    auto* launch = G == 16 ? launch_scan<4, false, kFlatL2> : G == 8 ? launch_scan<2, false, kFlatL2> : launch_scan<1, false, kFlatL2>;
+    if (L.filter) launch = G == 16 ? launch_scan<4, true, kFlatL2> : G == 8 ? launch_scan<2, true, kFlatL2> : launch_scan<1, true, kFlatL2>;
+    if (L.metric == kFlatIP) {
+        launch = G == 16 ? launch_scan<4, false, kFlatIP> : G == 8 ? launch_scan<2, false, kFlatIP> : launch_scan<1, false, kFlatIP>;
+        if (L.filter) launch = G == 16 ? launch_scan<4, true, kFlatIP> : G == 8 ? launch_scan<2, true, kFlatIP> : launch_scan<1, true, kFlatIP>;
+    }
+    return launch(L, d_queries, nq, nprobe, d_skeys, d_svals, n_pairs, G, top_k, cap, d_part_ids, d_part_dists, stream);
 }
 
 }  // namespace dpq

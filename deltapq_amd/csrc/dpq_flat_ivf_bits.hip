@@ -69,7 +69,9 @@ __device__ __forceinline__ void bits_tile(const uint32_t* __restrict__ rp, bool 
 
 // grid: the runs; 256 threads; dynamic LDS: G buffers of cap = 2 P2 keys.  Wp: words of a stored row and of a prepared
 // query, a multiple of CW.  nq * Wp < 2^32 (a slice holds at most kIvfSliceQueries queries of at most 128 words).
-template <int CW>
+// FILTERED (fbits: the filter's bitmap over the rows): a tile is the next up to 256 eligible rows, compacted into 256
+// row-number slots in front of the buffers (dpq_flat_ivf_device.h's fill_tile); a lane takes its row number from its slot.
+template <int CW, bool FILTERED>
 __global__ __launch_bounds__(256) void flat_ivf_scan_bits_kernel(const uint32_t* __restrict__ rows, int Wp, int64_t id_offset,
                                                                  const int64_t* __restrict__ offsets,
                                                                  const uint32_t* __restrict__ list_rows, int nlist,
@@ -77,9 +79,11 @@ __global__ __launch_bounds__(256) void flat_ivf_scan_bits_kernel(const uint32_t*
                                                                  const uint32_t* __restrict__ skeys,
                                                                  const uint32_t* __restrict__ svals, int64_t n_pairs, int G,
                                                                  int top_k, int cap, int32_t* __restrict__ part_ids,
-                                                                 float* __restrict__ part_dists) {
+                                                                 float* __restrict__ part_dists,
+                                                                 const uint32_t* __restrict__ fbits) {
     extern __shared__ __attribute__((aligned(16))) unsigned char flat_ivf_bits_smem[];
-    uint64_t* buf = reinterpret_cast<uint64_t*>(flat_ivf_bits_smem);  // [G][cap]
+    [[maybe_unused]] uint32_t* s_rows = reinterpret_cast<uint32_t*>(flat_ivf_bits_smem);           // [TR], FILTERED only
+    uint64_t* buf = reinterpret_cast<uint64_t*>(flat_ivf_bits_smem + (FILTERED ? TR * 4 : 0));  // [G][cap]
     __shared__ uint32_t s_key[GM], s_val[GM], s_q[GM], s_cnt[GM];
     __shared__ uint64_t s_thr[GM];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -113,10 +117,19 @@ __global__ __launch_bounds__(256) void flat_ivf_scan_bits_kernel(const uint32_t*
 #pragma unroll
         for (int j = 0; j < GM; ++j)
             qoff[j] = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_q[s + min(j, nqs - 1)]) * (uint32_t)Wp;
-        for (int64_t base = lo; base < hi; base += TR) {
+        for (int64_t base = lo; base < hi; base += FILTERED ? 0 : TR) {
             __syncthreads();  // the counts and thresholds: the stretch's first, or what sink_make_room left
-            const bool ok = base + tid < hi;
-            const uint32_t row = ok ? list_rows[base + tid] : 0u;
+            bool ok;
+            uint32_t row;
+            if constexpr (FILTERED) {  // base moves to where the next tile starts; every lane has read its slot before
+                const int got = fill_tile(s_rows, list_rows, base, hi, fbits, tid);  // the tile's closing barrier
+                if (got == 0) break;  // the list ended on no eligible row
+                ok = tid < got;
+                row = ok ? s_rows[tid] : 0u;
+            } else {
+                ok = base + tid < hi;
+                row = ok ? list_rows[base + tid] : 0u;
+            }
             const uint32_t* rp = rows + (size_t)row * Wp;
             uint32_t acc[GM];
 #pragma unroll
@@ -139,7 +152,7 @@ __global__ __launch_bounds__(256) void flat_ivf_scan_bits_kernel(const uint32_t*
                 }
             }
             __syncthreads();
-            if (base + TR < hi) sink_make_room(buf, s_cnt, s_thr, nqs, cap, top_k, tid);
+            if (base + (FILTERED ? 0 : TR) < hi) sink_make_room(buf, s_cnt, s_thr, nqs, cap, top_k, tid);
         }
         if (hi > lo) sink_sort(buf, s_cnt, nqs, cap, tid);  // (behind the last tile's closing barrier)
         // the stretch's answers: pair i = q * nprobe + j goes to row j * nq + q.  A padding pair, or an empty list: padding
@@ -161,8 +174,10 @@ hipError_t ensure_scan_lds() {
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
     if (dev < 0 || dev >= 64 || !done[dev].load(std::memory_order_acquire)) {
-        for (const void* k : {reinterpret_cast<const void*>(&flat_ivf_scan_bits_kernel<32>),
-                              reinterpret_cast<const void*>(&flat_ivf_scan_bits_kernel<4>)}) {
+        for (const void* k : {reinterpret_cast<const void*>(&flat_ivf_scan_bits_kernel<32, false>),
+                              reinterpret_cast<const void*>(&flat_ivf_scan_bits_kernel<4, false>),
+                              reinterpret_cast<const void*>(&flat_ivf_scan_bits_kernel<32, true>),
+                              reinterpret_cast<const void*>(&flat_ivf_scan_bits_kernel<4, true>)}) {
             e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kLdsBytes - kStaticBytes));
             if (e != hipSuccess) return e;
         }
@@ -193,11 +208,15 @@ hipError_t launch_flat_ivf_scan_bits(const FlatIvfListsBits& L, const uint32_t* 
     if (hipError_t e = ensure_scan_lds()) return e;
     const int cap = scan_cap(top_k), G = flat_ivf_group_bits(top_k, L.Wp, group);
     const int64_t n_pairs = (int64_t)nq * nprobe;
-    const size_t lds = (size_t)G * cap * sizeof(uint64_t);
-    auto* kernel = L.Wp % 32 == 0 ? flat_ivf_scan_bits_kernel<32> : flat_ivf_scan_bits_kernel<4>;
+    // the filtered scan's 256 row-number slots never cost a pair: a group's buffers are a power of two of at most 128 KB
+    const size_t lds = (L.filter ? (size_t)TR * 4 : 0) + (size_t)G * cap * sizeof(uint64_t);
+    if (lds + kStaticBytes > kLdsBytes) return hipErrorInvalidValue;
+    auto* kernel = L.Wp % 32 == 0 ? flat_ivf_scan_bits_kernel<32, false> : flat_ivf_scan_bits_kernel<4, false>;
+    if (L.filter) kernel = L.Wp % 32 == 0 ? flat_ivf_scan_bits_kernel<32, true> : flat_ivf_scan_bits_kernel<4, true>;
     kernel<<<dim3((unsigned)((n_pairs + G - 1) / G)), dim3(256), lds, stream>>>(L.rows, L.Wp, L.id_offset, L.offsets, L.list_rows,
                                                                                  L.nlist, d_queries, nq, nprobe, d_skeys, d_svals,
-                                                                                 n_pairs, G, top_k, cap, d_part_ids, d_part_dists);
+                                                                                 n_pairs, G, top_k, cap, d_part_ids, d_part_dists,
+                                                                                 L.filter);
     return hipGetLastError();
 }
 

@@ -3,8 +3,9 @@
 // power of two >= max(top_k, 256); a count and a threshold per pair.  A key below its pair's threshold is appended by an
 // LDS atomic on the count; when a buffer could overflow on the next tile of kFlatIvfTileRows rows, the buffers of the
 // stretch are sorted side by side (one bitonic network, the same barriers for all), cut to top_k, and the thresholds
-// become the k-th keys.  Included by the two .hip files only; every function is called by all 256 threads of a workgroup
-// with arguments that are the same in every thread.
+// become the k-th keys.  Below it, fill_tile: the tile of a scan under an id filter.  Included by the
+// scans' .hip files only; every function is called by all 256 threads of a workgroup with arguments that are the same in
+// every thread.
 #pragma once
 #include "dpq_flat.h"
 #include "dpq_flat_ivf.h"
@@ -85,6 +86,51 @@ __device__ __forceinline__ void sink_emit(const uint64_t* b, uint32_t cnt, int t
         out_i[r] = key != kFlatNoKey ? (int32_t)(key & 0xffffffffu) : -1;
         out_d[r] = key != kFlatNoKey ? __uint_as_float((uint32_t)(key >> 32)) : INFINITY;
     }
+}
+
+// ---- the filled tile of a scan under an id filter -------------------------------------------------------
+// A tile of a filtered scan is the next up to kFlatIvfTileRows ELIGIBLE rows of the list, not its next 256 row numbers.
+// From list position `pos` on the workgroup reads row numbers in chunks of 256, a thread to a row number, and tests the
+// row's bit in `fbits` (bit r & 31 of word r >> 5: the filter's bitmap over the handle's rows; every row number of a list is
+// below the handle's row count, which the bitmap covers).  The survivors of a chunk are compacted in list order: a
+// wavefront ballot gives a lane its place among its wavefront's survivors, the four wavefronts' counts -- through LDS --
+// its wavefront's place in the chunk, and `fill` the chunk's place in the tile.  What fits goes to s_rows[place]; of what
+// does not fit, the first survivor's thread leaves its offset in the chunk, and THERE the next tile's fill starts again:
+// the carry is a list position, not a second row-number buffer, and costs the next tile at most one chunk read twice.
+// Stops at a full tile or at the list's end; the slots behind the last row are kNoRow.  Returns the rows of the tile and
+// moves pos to where the next tile starts; both are read from LDS behind a barrier, the same in every thread.
+// Called by all 256 threads behind a barrier after which nobody reads s_rows; ends behind a barrier.  The words of two
+// consecutive chunks alternate between two sets, so a chunk costs two barriers.
+__device__ __forceinline__ int fill_tile(uint32_t* s_rows, const uint32_t* __restrict__ list_rows, int64_t& pos, int64_t hi,
+                                         const uint32_t* __restrict__ fbits, int tid) {
+    __shared__ uint32_t s_wcnt[2][4], s_stop[2];
+    const int lane = tid & 63, w = tid >> 6;
+    const uint64_t below = ((uint64_t)1 << lane) - 1;
+    s_rows[tid] = kNoRow;
+    uint32_t fill = 0u;
+    for (int it = 0; fill < (uint32_t)kFlatIvfTileRows && pos < hi; it ^= 1) {
+        const bool in = pos + tid < hi;
+        const uint32_t row = in ? list_rows[pos + tid] : 0u;
+        const bool ok = in && ((fbits[row >> 5] >> (row & 31u)) & 1u) != 0u;
+        const uint64_t m = __ballot(ok);
+        if (lane == 0) s_wcnt[it][w] = (uint32_t)__popcll(m);
+        if (tid == 0) s_stop[it] = (uint32_t)kFlatIvfTileRows;  // the whole chunk, unless a survivor does not fit
+        __syncthreads();  // also: s_rows is cleared before the first chunk's survivors land
+        uint32_t before = 0u, total = 0u;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const uint32_t c = s_wcnt[it][i];
+            before += i < w ? c : 0u;
+            total += c;
+        }
+        const uint32_t slot = fill + before + (uint32_t)__popcll(m & below);
+        if (ok && slot < (uint32_t)kFlatIvfTileRows) s_rows[slot] = row;
+        if (ok && slot == (uint32_t)kFlatIvfTileRows) s_stop[it] = (uint32_t)tid;  // one thread at most
+        __syncthreads();
+        pos += s_stop[it];
+        fill = min(fill + total, (uint32_t)kFlatIvfTileRows);
+    }
+    return (int)fill;
 }
 
 }  // namespace

@@ -114,7 +114,7 @@ __device__ __forceinline__ void load_slice(uint4 (&pre)[4], const uint32_t* __re
 
 // grid: the runs; 256 threads; dynamic LDS: the tiles, then G buffers of cap = 2 P2 keys.  Wr: the words of a stored row,
 // a multiple of four.
-template <int FORMAT, int QPL>
+template <int FORMAT, int QPL, bool FILTERED, int METRIC>
 __global__ __launch_bounds__(256) void flat_ivf_scan_narrow_kernel(const uint32_t* __restrict__ rows, int Wr, int64_t id_offset,
                                                                    const int64_t* __restrict__ offsets,
                                                                    const uint32_t* __restrict__ list_rows, int nlist,
@@ -122,7 +122,8 @@ __global__ __launch_bounds__(256) void flat_ivf_scan_narrow_kernel(const uint32_
                                                                    const uint32_t* __restrict__ skeys,
                                                                    const uint32_t* __restrict__ svals, int64_t n_pairs, int G,
                                                                    int top_k, int cap, int32_t* __restrict__ part_ids,
-                                                                   float* __restrict__ part_dists) {
+                                                                   float* __restrict__ part_dists,
+                                                                   const uint32_t* __restrict__ fbits) {
     constexpr int DW = word_dims<FORMAT>, SD = SW * DW;  // dimensions of a word and of a slice
     constexpr int UNR = 8 / DW;                          // words the sum is unrolled by: eight dimensions
     extern __shared__ __attribute__((aligned(16))) unsigned char flat_ivf_narrow_smem[];
@@ -162,10 +163,14 @@ __global__ __launch_bounds__(256) void flat_ivf_scan_narrow_kernel(const uint32_
             s_thr[tid] = kFlatNoKey;
         }
         const bool active = QPL * ty < nqs;  // (a wavefront's lanes share ty)
-        for (int64_t base = lo; base < hi; base += TR) {
+        for (int64_t base = lo; base < hi; base += FILTERED ? 0 : TR) {
             __syncthreads();  // the tile before is done with s_rows; the first tile: the counts above are in place
-            s_rows[tid] = base + tid < hi ? list_rows[base + tid] : kNoRow;
-            __syncthreads();
+            if constexpr (FILTERED) {  // the next up to 256 eligible rows; base moves to where the next tile starts
+                if (fill_tile(s_rows, list_rows, base, hi, fbits, tid) == 0) break;  // the list ended on no eligible row
+            } else {
+                s_rows[tid] = base + tid < hi ? list_rows[base + tid] : kNoRow;
+                __syncthreads();
+            }
             double acc[QPL][4];
 #pragma unroll
             for (int i = 0; i < QPL; ++i)
@@ -219,10 +224,10 @@ __global__ __launch_bounds__(256) void flat_ivf_scan_narrow_kernel(const uint32_
                             }
 #pragma unroll
                             for (int i = 0; i < QPL; ++i) {
-                                accumulate<kFlatL2>(acc[i][0], v[0][k], q[i]);
-                                accumulate<kFlatL2>(acc[i][1], v[1][k], q[i]);
-                                accumulate<kFlatL2>(acc[i][2], v[2][k], q[i]);
-                                accumulate<kFlatL2>(acc[i][3], v[3][k], q[i]);
+                                accumulate<METRIC>(acc[i][0], v[0][k], q[i]);
+                                accumulate<METRIC>(acc[i][1], v[1][k], q[i]);
+                                accumulate<METRIC>(acc[i][2], v[2][k], q[i]);
+                                accumulate<METRIC>(acc[i][3], v[3][k], q[i]);
                             }
                         }
                     }
@@ -240,13 +245,13 @@ __global__ __launch_bounds__(256) void flat_ivf_scan_narrow_kernel(const uint32_
                     for (int j = 0; j < 4; ++j) {
                         const uint32_t row = s_rows[4 * tx + j];
                         if (row == kNoRow) continue;
-                        const uint64_t key = make_key<kFlatL2>(acc[i][j], (uint32_t)(id_offset + (int64_t)row));
+                        const uint64_t key = make_key<METRIC>(acc[i][j], (uint32_t)(id_offset + (int64_t)row));
                         if (key < thr) b[atomicAdd(&s_cnt[qs], 1u)] = key;  // < cap: the tile had room for its 256 rows
                     }
                 }
             }
             __syncthreads();
-            if (base + TR < hi) sink_make_room(buf, s_cnt, s_thr, nqs, cap, top_k, tid);
+            if (base + (FILTERED ? 0 : TR) < hi) sink_make_room(buf, s_cnt, s_thr, nqs, cap, top_k, tid);
         }
         if (hi > lo) sink_sort(buf, s_cnt, nqs, cap, tid);  // (behind the last tile's closing barrier)
         // the stretch's answers: pair i = q * nprobe + j goes to row j * nq + q.  A padding pair, or an empty list: padding
@@ -262,14 +267,14 @@ __global__ __launch_bounds__(256) void flat_ivf_scan_narrow_kernel(const uint32_
 }
 
 // hipFuncSetAttribute is per device
-template <int FORMAT, int QPL>
+template <int FORMAT, int QPL, bool FILTERED, int METRIC>
 hipError_t ensure_scan_lds() {
     static std::atomic<bool> done[64];
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
     if (dev < 0 || dev >= 64 || !done[dev].load(std::memory_order_acquire)) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&flat_ivf_scan_narrow_kernel<FORMAT, QPL>),
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&flat_ivf_scan_narrow_kernel<FORMAT, QPL, FILTERED, METRIC>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kLdsBytes - kStaticBytes));
         if (e != hipSuccess) return e;
         if (dev >= 0 && dev < 64) done[dev].store(true, std::memory_order_release);
@@ -287,24 +292,31 @@ struct ScanArgs {
     hipStream_t stream;
 };
 
-template <int FORMAT, int QPL>
+template <int FORMAT, int QPL, bool FILTERED, int METRIC>
 hipError_t launch_scan(const FlatIvfListsNarrow& L, const ScanArgs& a) {
-    if (hipError_t e = ensure_scan_lds<FORMAT, QPL>()) return e;
+    if (hipError_t e = ensure_scan_lds<FORMAT, QPL, FILTERED, METRIC>()) return e;
     const int cap = scan_cap(a.top_k);
     const int64_t n_pairs = (int64_t)a.nq * a.nprobe;
     const size_t lds = tile_bytes(FORMAT) + (size_t)a.G * cap * sizeof(uint64_t);
     const dim3 grid((unsigned)((n_pairs + a.G - 1) / a.G)), block(256);
-    flat_ivf_scan_narrow_kernel<FORMAT, QPL><<<grid, block, lds, a.stream>>>(
+    flat_ivf_scan_narrow_kernel<FORMAT, QPL, FILTERED, METRIC><<<grid, block, lds, a.stream>>>(
         static_cast<const uint32_t*>(L.rows), L.Dp / word_dims<FORMAT>, L.id_offset, L.offsets, L.list_rows, L.nlist, a.queries,
-        a.nq, a.nprobe, a.skeys, a.svals, n_pairs, a.G, a.top_k, cap, a.part_ids, a.part_dists);
+        a.nq, a.nprobe, a.skeys, a.svals, n_pairs, a.G, a.top_k, cap, a.part_ids, a.part_dists, L.filter);
     return hipGetLastError();
+}
+
+template <int FORMAT, int METRIC>
+hipError_t launch_scan_by(const FlatIvfListsNarrow& L, const ScanArgs& a) {
+    if (L.filter) return a.G == 16 ? launch_scan<FORMAT, 4, true, METRIC>(L, a) : a.G == 8 ? launch_scan<FORMAT, 2, true, METRIC>(L, a)
+                                                                                          : launch_scan<FORMAT, 1, true, METRIC>(L, a);
+    if (a.G == 16) return launch_scan<FORMAT, 4, false, METRIC>(L, a);
+    if (a.G == 8) return launch_scan<FORMAT, 2, false, METRIC>(L, a);
+    return launch_scan<FORMAT, 1, false, METRIC>(L, a);
 }
 
 template <int FORMAT>
 hipError_t launch_scan_of(const FlatIvfListsNarrow& L, const ScanArgs& a) {
-    if (a.G == 16) return launch_scan<FORMAT, 4>(L, a);
-    if (a.G == 8) return launch_scan<FORMAT, 2>(L, a);
-    return launch_scan<FORMAT, 1>(L, a);
+    return L.metric == kFlatIP ? launch_scan_by<FORMAT, kFlatIP>(L, a) : launch_scan_by<FORMAT, kFlatL2>(L, a);
 }
 
 bool is_narrow(int format) { return format == kFlatF16 || format == kFlatBF16 || format == kFlatSQ8 || format == kFlatSQ4; }

@@ -65,6 +65,10 @@ __global__ __launch_bounds__(256) void flat_ivf_widen_kernel(const uint8_t* __re
 }
 
 // grid: the runs; 256 threads; dynamic LDS: the queries, the row numbers, then G buffers of cap = 2 P2 keys.
+// METRIC kFlatIP: the score is the int32 S of dpq_flat_u8.hip's header -- the int8 dot product, plus, for unsigned rows (CORR),
+// rs[row] + qs[query], which come in the place of the norms (vnorm, qnorm); without CORR neither array is read.  The key
+// word is flat_ip_word of the converted score's bits.  kFlatL2 always has CORR: its norms.
+template <bool FILTERED, int METRIC, bool CORR>
 __global__ __launch_bounds__(256) void flat_ivf_scan_u8_kernel(const int8_t* __restrict__ rows, const int32_t* __restrict__ vnorm,
                                                                int Dp, int64_t id_offset, const int64_t* __restrict__ offsets,
                                                                const uint32_t* __restrict__ list_rows, int nlist,
@@ -73,7 +77,8 @@ __global__ __launch_bounds__(256) void flat_ivf_scan_u8_kernel(const int8_t* __r
                                                                const uint32_t* __restrict__ skeys,
                                                                const uint32_t* __restrict__ svals, int64_t n_pairs, int G,
                                                                int top_k, int cap, int32_t* __restrict__ part_ids,
-                                                               float* __restrict__ part_dists) {
+                                                               float* __restrict__ part_dists,
+                                                               const uint32_t* __restrict__ fbits) {
     extern __shared__ __attribute__((aligned(16))) unsigned char flat_ivf_u8_smem[];
     const int QS = Dp + QPAD;                                                          // bytes between two query rows
     int8_t* Qs = reinterpret_cast<int8_t*>(flat_ivf_u8_smem);                          // [GM][QS]
@@ -109,7 +114,7 @@ __global__ __launch_bounds__(256) void flat_ivf_scan_u8_kernel(const int8_t* __r
         if (tid < nqs) {
             s_cnt[tid] = 0u;
             s_thr[tid] = kFlatNoKey;
-            s_qn[tid] = qnorm[s_q[s + tid]];
+            s_qn[tid] = CORR ? qnorm[s_q[s + tid]] : 0;
         }
         if (hi > lo)  // the stretch's queries, once for all its tiles (the first tile's barriers publish them)
             for (int idx = tid; idx < GM * cpr; idx += 256) {
@@ -118,10 +123,14 @@ __global__ __launch_bounds__(256) void flat_ivf_scan_u8_kernel(const int8_t* __r
                 if (slot < nqs) v = *reinterpret_cast<const i32x4*>(queries + (size_t)s_q[s + slot] * Dp + 16 * c);
                 *reinterpret_cast<i32x4*>(Qs + slot * QS + 16 * c) = v;
             }
-        for (int64_t base = lo; base < hi; base += TR) {
+        for (int64_t base = lo; base < hi; base += FILTERED ? 0 : TR) {
             __syncthreads();  // the tile before is done with s_rows; the first tile: the counts and queries above are in place
-            s_rows[tid] = base + tid < hi ? list_rows[base + tid] : kNoRow;
-            __syncthreads();
+            if constexpr (FILTERED) {  // the next up to 256 eligible rows; base moves to where the next tile starts
+                if (fill_tile(s_rows, list_rows, base, hi, fbits, tid) == 0) break;  // the list ended on no eligible row
+            } else {
+                s_rows[tid] = base + tid < hi ? list_rows[base + tid] : kNoRow;
+                __syncthreads();
+            }
             const int8_t* ap[4];
             bool aok[4];
 #pragma unroll
@@ -137,7 +146,7 @@ __global__ __launch_bounds__(256) void flat_ivf_scan_u8_kernel(const int8_t* __r
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
                     const uint32_t row = s_rows[64 * w + 16 * i + 4 * h + c];
-                    vn[i][c] = row != kNoRow ? vnorm[row] : 0;
+                    vn[i][c] = CORR && row != kNoRow ? vnorm[row] : 0;
                 }
             const int8_t* bp = Qs + r * QS + 16 * h;
             i32x4 acc[4], nxt[4];
@@ -167,13 +176,14 @@ __global__ __launch_bounds__(256) void flat_ivf_scan_u8_kernel(const int8_t* __r
                     for (int c = 0; c < 4; ++c) {
                         const uint32_t row = s_rows[64 * w + 16 * i + 4 * h + c];
                         if (row == kNoRow) continue;
-                        const int d = vn[i][c] + qn - 2 * acc[i][c];
-                        const uint64_t key = ((uint64_t)__float_as_uint(__int2float_rn(d)) << 32) | (uint32_t)(id_offset + (int64_t)row);
+                        const int d = METRIC == kFlatIP ? acc[i][c] + vn[i][c] + qn : vn[i][c] + qn - 2 * acc[i][c];
+                        const uint32_t u = __float_as_uint(__int2float_rn(d));
+                        const uint64_t key = ((uint64_t)(METRIC == kFlatIP ? flat_ip_word(u) : u) << 32) | (uint32_t)(id_offset + (int64_t)row);
                         if (key < thr) b[atomicAdd(&s_cnt[r], 1u)] = key;  // < cap: the tile had room for its 256 rows
                     }
             }
             __syncthreads();
-            if (base + TR < hi) sink_make_room(buf, s_cnt, s_thr, nqs, cap, top_k, tid);
+            if (base + (FILTERED ? 0 : TR) < hi) sink_make_room(buf, s_cnt, s_thr, nqs, cap, top_k, tid);
         }
         if (hi > lo) sink_sort(buf, s_cnt, nqs, cap, tid);  // (behind the last tile's closing barrier)
         // the stretch's answers: pair i = q * nprobe + j goes to row j * nq + q.  A padding pair, or an empty list: padding
@@ -189,18 +199,42 @@ __global__ __launch_bounds__(256) void flat_ivf_scan_u8_kernel(const int8_t* __r
 }
 
 // hipFuncSetAttribute is per device
+template <bool FILTERED, int METRIC, bool CORR>
 hipError_t ensure_scan_lds() {
     static std::atomic<bool> done[64];
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
     if (dev < 0 || dev >= 64 || !done[dev].load(std::memory_order_acquire)) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&flat_ivf_scan_u8_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)(kLdsBytes - kStaticBytes));
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&flat_ivf_scan_u8_kernel<FILTERED, METRIC, CORR>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kLdsBytes - kStaticBytes));
         if (e != hipSuccess) return e;
         if (dev >= 0 && dev < 64) done[dev].store(true, std::memory_order_release);
     }
     return hipSuccess;
+}
+
+struct ScanArgs {
+    const int8_t* queries;
+    const int32_t* qterm;
+    int nq, nprobe;
+    const uint32_t *skeys, *svals;
+    int G, top_k;
+    int32_t* part_ids;
+    float* part_dists;
+    hipStream_t stream;
+};
+
+template <bool FILTERED, int METRIC, bool CORR>
+hipError_t launch_scan(const FlatIvfListsU8& L, const ScanArgs& a) {
+    if (hipError_t e = ensure_scan_lds<FILTERED, METRIC, CORR>()) return e;
+    const int cap = scan_cap(a.top_k);
+    const int64_t n_pairs = (int64_t)a.nq * a.nprobe;
+    const size_t lds = tile_bytes(L.Dp) + (size_t)a.G * cap * sizeof(uint64_t);
+    flat_ivf_scan_u8_kernel<FILTERED, METRIC, CORR><<<dim3((unsigned)((n_pairs + a.G - 1) / a.G)), dim3(256), lds, a.stream>>>(
+        L.rows, L.norm, L.Dp, L.id_offset, L.offsets, L.list_rows, L.nlist, a.queries, a.qterm, a.nq, a.nprobe, a.skeys, a.svals,
+        n_pairs, a.G, a.top_k, cap, a.part_ids, a.part_dists, L.filter);
+    return hipGetLastError();
 }
 
 }  // namespace
@@ -226,20 +260,21 @@ hipError_t launch_flat_ivf_scan_u8(const FlatIvfListsU8& L, const int8_t* d_quer
                                    const uint32_t* d_skeys, const uint32_t* d_svals, int top_k, int group, int32_t* d_part_ids,
                                    float* d_part_dists, hipStream_t stream) {
     if (nq <= 0) return hipSuccess;
-    if (!L.rows || !L.norm || !L.offsets || !L.list_rows || !d_queries || !d_qnorm || !d_skeys || !d_svals || !d_part_ids ||
+    const bool terms = L.metric != kFlatIP || L.norm || d_qnorm;  // signed rows under kFlatIP take neither array
+    if (L.metric != kFlatL2 && L.metric != kFlatIP) return hipErrorInvalidValue;
+    if (!L.rows || (terms && (!L.norm || !d_qnorm)) || !L.offsets || !L.list_rows || !d_queries || !d_skeys || !d_svals || !d_part_ids ||
         !d_part_dists || L.Dp < kFlatU8KStep || L.Dp % kFlatU8KStep != 0 || L.Dp > kFlatMaxD || L.nlist < 1 ||
         L.nlist > kIvfMaxLists || nprobe < 1 || nprobe > kIvfMaxProbe || top_k < 1 || top_k > kIvfMaxTopK || group < 1 ||
         (int64_t)nq * nprobe > 0x7fffffff ||
         ((reinterpret_cast<uintptr_t>(L.rows) | reinterpret_cast<uintptr_t>(d_queries)) & 15u))
         return hipErrorInvalidValue;
-    if (hipError_t e = ensure_scan_lds()) return e;
-    const int cap = scan_cap(top_k), G = flat_ivf_group_u8(top_k, L.Dp, group);
-    const int64_t n_pairs = (int64_t)nq * nprobe;
-    const size_t lds = tile_bytes(L.Dp) + (size_t)G * cap * sizeof(uint64_t);
-    flat_ivf_scan_u8_kernel<<<dim3((unsigned)((n_pairs + G - 1) / G)), dim3(256), lds, stream>>>(
-        L.rows, L.norm, L.Dp, L.id_offset, L.offsets, L.list_rows, L.nlist, d_queries, d_qnorm, nq, nprobe, d_skeys, d_svals,
-        n_pairs, G, top_k, cap, d_part_ids, d_part_dists);
-    return hipGetLastError();
+    const ScanArgs a{d_queries, d_qnorm, nq, nprobe, d_skeys, d_svals, flat_ivf_group_u8(top_k, L.Dp, group), top_k, d_part_ids,
+                     d_part_dists, stream};
+    if (L.metric == kFlatIP) {
+        if (L.norm) return L.filter ? launch_scan<true, kFlatIP, true>(L, a) : launch_scan<false, kFlatIP, true>(L, a);
+        return L.filter ? launch_scan<true, kFlatIP, false>(L, a) : launch_scan<false, kFlatIP, false>(L, a);
+    }
+    return L.filter ? launch_scan<true, kFlatL2, true>(L, a) : launch_scan<false, kFlatL2, true>(L, a);
 }
 
 }  // namespace dpq

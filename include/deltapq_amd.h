@@ -1609,8 +1609,8 @@ int dpq_write_vecs(const char* path, const float* vectors, int64_t n, int D);
  *           units, never narrowed or quantised, and dpq_flat_ivf_build labels the widened or decoded rows.  The centroids
  *           are padded to the handle's own row padding (8, 16 or 32 dimensions for half, 8-bit, 4-bit rows).  Byte and
  *           binary handles, and a handle with an id map, are DPQ_ERR_ARG (byte and binary handles have calls of their own:
- *           "IVF search over byte vectors" and "IVF search over binary vectors" below).  Squared L2 only: no inner
- *           product, no filter, no range search, no id maps, no shards, no CLI task and no training of the quantiser or of
+ *           "IVF search over byte vectors" and "IVF search over binary vectors" below).  Squared L2 here (inner product: the *_ip calls below;
+ *           an id filter: the *_filtered calls below): no range search, no id maps, no shards, no CLI task and no training of the quantiser or of
  *           the centroids here (dpq_sq_train, dpq_ivf_train and dpq_ivf_assign exist).
  *   Ownership  The structure is bound to the handle it was made on and is freed (dpq_flat_ivf_free) BEFORE
  *           dpq_flat_close of that handle; both are used from one thread.
@@ -1681,8 +1681,8 @@ int dpq_flat_ivf_search_device(dpq_flat_ivf* ivf, const float* d_queries, int nq
  *           conversion; reported id = row + id_offset; order by (distance bits, id); padding -1 / +inf; a repeated probe
  *           counts once, a negative probe is padding, an entry >= nlist is DPQ_ERR_ARG as above.
  *   Limits  The byte handle's (D <= 2048) and the structure's above (nlist <= 65536, nprobe <= min(nlist, 1024),
- *           top_k <= 2048, fewer than 2^31 rows).  Squared L2 only: no inner product, no filter, no range search, no
- *           shards, no CLI task.  State and ownership as above. */
+ *           top_k <= 2048, fewer than 2^31 rows).  Squared L2 here (inner product: the *_ip_bytes calls below; an id filter: the
+ *           *_filtered calls below): no range search, no shards, no CLI task.  State and ownership as above. */
 int dpq_flat_ivf_create_bytes(dpq_flat* flat, const int32_t* labels, int64_t n, int nlist, dpq_flat_ivf** out);
 int dpq_flat_ivf_create_bytes_device(dpq_flat* flat, const int32_t* d_labels, int64_t n, int nlist, void* hip_stream,
                                      dpq_flat_ivf** out);
@@ -1720,8 +1720,8 @@ int dpq_flat_ivf_search_bytes_device(dpq_flat_ivf* ivf, const void* d_queries, i
  *           order by (distance bits, id); padding -1 / +inf; a repeated probe counts once, a negative probe is padding, an
  *           entry >= nlist is DPQ_ERR_ARG as above.
  *   Limits  The binary handle's (D <= DPQ_FLAT_BITS_MAX_D) and the structure's above (nlist <= 65536, nprobe <=
- *           min(nlist, 1024), top_k <= 2048, fewer than 2^31 rows).  No filter, no range search, no id map, no shards and
- *           no CLI task yet.  State and ownership as above. */
+ *           min(nlist, 1024), top_k <= 2048, fewer than 2^31 rows).  No range search, no id map, no shards and
+ *           no CLI task yet (an id filter: the *_filtered calls below).  State and ownership as above. */
 int dpq_flat_ivf_create_bits(dpq_flat* flat, const int32_t* labels, int64_t n, int nlist, dpq_flat_ivf** out);
 int dpq_flat_ivf_create_bits_device(dpq_flat* flat, const int32_t* d_labels, int64_t n, int nlist, void* hip_stream,
                                     dpq_flat_ivf** out);
@@ -1735,6 +1735,94 @@ int dpq_flat_ivf_search_probes_bits_device(dpq_flat_ivf* ivf, const uint8_t* d_q
 int dpq_flat_ivf_search_bits(dpq_flat_ivf* ivf, const uint8_t* queries, int nq, int nprobe, int top_k, int32_t* ids, float* dists);
 int dpq_flat_ivf_search_bits_device(dpq_flat_ivf* ivf, const uint8_t* d_queries, int nq, int nprobe, int top_k, int32_t* d_ids,
                                     float* d_dists, void* hip_stream);
+
+/* ---- IVF search over raw vectors under an id filter: only eligible rows are scanned ----------
+ * FAISS's IDSelector in SearchParametersIVF.  NO REFERENCE COUNTERPART.  Every dpq_flat_ivf_search* call above has a
+ * *_filtered form with the same arguments and a trailing `filter`: a dpq_flat_filter made by dpq_flat_filter_create for
+ * the handle the structure was made on (fp32, half, quantised, byte or binary), or NULL, which is the unfiltered call.
+ *   Answer  For query q exactly what the unfiltered call returns over lists from which the rows the filter does not allow
+ *           were taken out -- and so what dpq_flat_search_filtered* returns under the intersection of the filter with the
+ *           union of the probed lists: the same distance bits (the arithmetic restated above for each kind of rows), reported
+ *           id = row + id_offset, order by (distance bits, id), padding -1 / +inf.  A filter that allows nothing, and a
+ *           probed list without an eligible row, give padding; ids at or beyond the bitmap's n_bits are not eligible.  The
+ *           coarse step (dpq_flat_ivf_probe*) does not see the filter: the lists probed are the unfiltered call's.
+ *   Cost    The filter keeps its bitmap on the device, one bit per row of the handle.  A scan reads a list's row numbers
+ *           and their bits, compacts the eligible ones, and gathers rows and forms distances in full tiles of eligible
+ *           rows only: a filter that allows few rows costs row-number reads, not row reads.
+ *   Errors  A filter made for another handle (which covers a filter on another device) is DPQ_ERR_ARG, before any
+ *           device call; the structure's next call works.  Everything else as in the unfiltered call of the same kind.
+ *           Squared L2 and Hamming here; inner product: the *_ip calls below, which take the same filter.  No range search, no id
+ *           maps, no shards, no CLI task yet. */
+int dpq_flat_ivf_search_probes_filtered(dpq_flat_ivf* ivf, const float* queries, int nq, const int32_t* probes, int nprobe,
+                                        int top_k, int32_t* ids, float* dists, const dpq_flat_filter* filter);
+int dpq_flat_ivf_search_probes_filtered_device(dpq_flat_ivf* ivf, const float* d_queries, int nq, const int32_t* d_probes,
+                                               int nprobe, int top_k, int32_t* d_ids, float* d_dists, void* hip_stream,
+                                               const dpq_flat_filter* filter);
+int dpq_flat_ivf_search_filtered(dpq_flat_ivf* ivf, const float* queries, int nq, int nprobe, int top_k, int32_t* ids,
+                                 float* dists, const dpq_flat_filter* filter);
+int dpq_flat_ivf_search_filtered_device(dpq_flat_ivf* ivf, const float* d_queries, int nq, int nprobe, int top_k,
+                                        int32_t* d_ids, float* d_dists, void* hip_stream, const dpq_flat_filter* filter);
+int dpq_flat_ivf_search_probes_filtered_bytes(dpq_flat_ivf* ivf, const void* queries, int nq, const int32_t* probes, int nprobe,
+                                              int top_k, int32_t* ids, float* dists, const dpq_flat_filter* filter);
+int dpq_flat_ivf_search_probes_filtered_bytes_device(dpq_flat_ivf* ivf, const void* d_queries, int nq, const int32_t* d_probes,
+                                                     int nprobe, int top_k, int32_t* d_ids, float* d_dists, void* hip_stream,
+                                                     const dpq_flat_filter* filter);
+int dpq_flat_ivf_search_filtered_bytes(dpq_flat_ivf* ivf, const void* queries, int nq, int nprobe, int top_k, int32_t* ids,
+                                       float* dists, const dpq_flat_filter* filter);
+int dpq_flat_ivf_search_filtered_bytes_device(dpq_flat_ivf* ivf, const void* d_queries, int nq, int nprobe, int top_k,
+                                              int32_t* d_ids, float* d_dists, void* hip_stream, const dpq_flat_filter* filter);
+int dpq_flat_ivf_search_probes_filtered_bits(dpq_flat_ivf* ivf, const uint8_t* queries, int nq, const int32_t* probes, int nprobe,
+                                             int top_k, int32_t* ids, float* dists, const dpq_flat_filter* filter);
+int dpq_flat_ivf_search_probes_filtered_bits_device(dpq_flat_ivf* ivf, const uint8_t* d_queries, int nq, const int32_t* d_probes,
+                                                    int nprobe, int top_k, int32_t* d_ids, float* d_dists, void* hip_stream,
+                                                    const dpq_flat_filter* filter);
+int dpq_flat_ivf_search_filtered_bits(dpq_flat_ivf* ivf, const uint8_t* queries, int nq, int nprobe, int top_k, int32_t* ids,
+                                      float* dists, const dpq_flat_filter* filter);
+int dpq_flat_ivf_search_filtered_bits_device(dpq_flat_ivf* ivf, const uint8_t* d_queries, int nq, int nprobe, int top_k,
+                                             int32_t* d_ids, float* d_dists, void* hip_stream, const dpq_flat_filter* filter);
+
+/* ---- IVF search over raw vectors by inner product ----------
+ * FAISS's IndexIVFFlat and IndexIVFScalarQuantizer with METRIC_INNER_PRODUCT.  NO REFERENCE COUNTERPART.  The probe and the
+ * searches above by the exact inner product instead of the squared L2 distance, for the plain set (fp32, half and
+ * scalar-quantised rows under fp32 queries) and the *_bytes set.  The searches take a trailing `filter` as the *_filtered
+ * calls do (NULL: none).  A structure over binary rows has no inner product: every call below is DPQ_ERR_ARG on it.
+ *   Score   fp32, half and quantised rows (widened or decoded exactly as for L2): acc is fp64 and starts at +0.0; for d
+ *           ascending acc = fma((double)v[d], (double)q[d], acc) -- the product of two fp32 values is exact in fp64, so a step
+ *           is one rounding; the score is (float)acc, and -0.0 is reported and ordered as +0.0: dpq_flat_search_ip's.
+ *           Byte rows: the int32 sum of v[d] * q[d] over the caller's values, exact whatever the order, converted once,
+ *           round to nearest even: dpq_flat_search_ip_u8 / _i8's.  Unsigned rows are stored biased by 128, so the kernel forms
+ *           v'.q' + rs[row] + qs[query] with rs = 128 sum v' + 16384 D and qs = 128 sum q' -- the same integer; the handle's
+ *           rs are made on first use, as dpq_flat_search_ip_u8 makes them, and kept.
+ *   Answer  For query q exactly what dpq_flat_search_filtered_ip* returns under a filter that allows the union of the probed
+ *           lists (intersected with `filter`): order by (score descending, id ascending), `scores` in the place of the
+ *           distances, padding -1 / -inf -- which sorts behind every score, negative ones included.
+ *   Probes  dpq_flat_ivf_probe_ip*: the nprobe centroids of LARGEST exact inner product with each query, by (score
+ *           descending, list number ascending), scores_out (may be NULL) their scores: dpq_flat_search_ip over the centroids
+ *           as a base.  Byte structures rank their fp32 centroids by the queries widened exactly, as for L2.
+ *           dpq_flat_ivf_search_ip* is dpq_flat_ivf_probe_ip* followed by dpq_flat_ivf_search_probes_ip*.  The lists
+ *           themselves are what dpq_flat_ivf_build* or the labels made them: dpq_flat_ivf_build keeps assigning by L2.
+ *   Errors, limits, state  As in the L2 call of the same kind and the *_filtered calls.  No range search, no id maps, no
+ *           shards, no CLI task yet. */
+int dpq_flat_ivf_probe_ip(dpq_flat_ivf* ivf, const float* queries, int nq, int nprobe, int32_t* lists_out, float* scores_out);
+int dpq_flat_ivf_search_probes_ip(dpq_flat_ivf* ivf, const float* queries, int nq, const int32_t* probes, int nprobe, int top_k,
+                                  int32_t* ids, float* scores, const dpq_flat_filter* filter);
+int dpq_flat_ivf_search_probes_ip_device(dpq_flat_ivf* ivf, const float* d_queries, int nq, const int32_t* d_probes, int nprobe,
+                                         int top_k, int32_t* d_ids, float* d_scores, void* hip_stream,
+                                         const dpq_flat_filter* filter);
+int dpq_flat_ivf_search_ip(dpq_flat_ivf* ivf, const float* queries, int nq, int nprobe, int top_k, int32_t* ids, float* scores,
+                           const dpq_flat_filter* filter);
+int dpq_flat_ivf_search_ip_device(dpq_flat_ivf* ivf, const float* d_queries, int nq, int nprobe, int top_k, int32_t* d_ids,
+                                  float* d_scores, void* hip_stream, const dpq_flat_filter* filter);
+int dpq_flat_ivf_probe_ip_bytes(dpq_flat_ivf* ivf, const void* queries, int nq, int nprobe, int32_t* lists_out, float* scores_out);
+int dpq_flat_ivf_search_probes_ip_bytes(dpq_flat_ivf* ivf, const void* queries, int nq, const int32_t* probes, int nprobe,
+                                        int top_k, int32_t* ids, float* scores, const dpq_flat_filter* filter);
+int dpq_flat_ivf_search_probes_ip_bytes_device(dpq_flat_ivf* ivf, const void* d_queries, int nq, const int32_t* d_probes,
+                                               int nprobe, int top_k, int32_t* d_ids, float* d_scores, void* hip_stream,
+                                               const dpq_flat_filter* filter);
+int dpq_flat_ivf_search_ip_bytes(dpq_flat_ivf* ivf, const void* queries, int nq, int nprobe, int top_k, int32_t* ids,
+                                 float* scores, const dpq_flat_filter* filter);
+int dpq_flat_ivf_search_ip_bytes_device(dpq_flat_ivf* ivf, const void* d_queries, int nq, int nprobe, int top_k, int32_t* d_ids,
+                                        float* d_scores, void* hip_stream, const dpq_flat_filter* filter);
 
 /* ---- measurement -------------------------------------------------------- */
 int dpq_profile_enable(dpq_index* idx, int on);  /* 0 off, 1 every kernel, 2 scan launches only (less event overhead) */
