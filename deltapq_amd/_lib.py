@@ -334,6 +334,10 @@ SYMBOLS = [
         ("dpq_flat_ivf_search_probes_ip%s_device", [_VP, _VP, ctypes.c_int, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP, _VP]),
         ("dpq_flat_ivf_search_ip%s", [_VP, _VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP]),
         ("dpq_flat_ivf_search_ip%s_device", [_VP, _VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP, _VP]))],
+    # range search over the probed lists: (ivf, filter or NULL, queries, nq, [probes,] nprobe, radii or thresholds, &result)
+    *[(name % kind, ctypes.c_int, args) for kind in ("", "_ip", "_bytes", "_ip_bytes", "_bits") for name, args in (
+        ("dpq_flat_ivf_range_search%s", [_VP, _VP, _VP, ctypes.c_int, ctypes.c_int, _VP, P(_VP)]),
+        ("dpq_flat_ivf_range_search_probes%s", [_VP, _VP, _VP, ctypes.c_int, _VP, ctypes.c_int, _VP, P(_VP)]))],
     # the *_filtered forms of the twelve searches above: the same arguments and a trailing dpq_flat_filter (NULL: none)
     *[(name % kind, ctypes.c_int, args + [_VP]) for kind in ("", "_bytes", "_bits") for name, args in (
         ("dpq_flat_ivf_search_probes_filtered%s", [_VP, _VP, ctypes.c_int, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP]),

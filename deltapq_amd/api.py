@@ -2029,6 +2029,44 @@ class FlatIVF:
                           _np_ptr(ids), _np_ptr(dists))
         return ids, dists
 
+    # the suffixes of this kind's range entry points, by L2 / Hamming and by inner product (FlatIVFBits keeps the plain
+    # _ip names: the library refuses them on it)
+    _RANGE = ("", "_ip")
+
+    def _range_call(self, ip, queries, probes, nprobe, radius, id_filter):
+        q = self._index._queries(queries)
+        r = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, dtype=np.float32), (q.shape[0],)))
+        args = (nprobe,)
+        if probes is not None:
+            p = IVF._probes(probes, q.shape[0])
+            args = (_np_ptr(p), p.shape[1])
+        name = "dpq_flat_ivf_range_search" + ("_probes" if probes is not None else "") + self._RANGE[ip]
+        res = ctypes.c_void_p()
+        check(getattr(self._lib, name)(self._h, FlatIdFilter._handle(id_filter, optional=True), _np_ptr(q), q.shape[0], *args,
+                                       _np_ptr(r), res), name)
+        return _range_result(self._lib, res)
+
+    def range_search(self, queries, nprobe, radius, id_filter=None):
+        """Every row of the nprobe lists probe() names within `radius` of each query, d < radius strictly
+        (dpq_flat_ivf_range_search[_bytes | _bits]).  `radius`: a scalar or one value per query.  Returns (lims int64
+        [nq + 1], ids int32, dists float32), each list ascending by (distance, id): what the flat index's range_search gives
+        under a filter of those lists' rows."""
+        return self._range_call(0, queries, None, nprobe, radius, id_filter)
+
+    def range_search_probes(self, queries, probes, radius, id_filter=None):
+        """range_search over the caller's own lists: probes int32 [nq][nprobe], -1 = padding
+        (dpq_flat_ivf_range_search_probes[_bytes | _bits])."""
+        return self._range_call(0, queries, probes, 0, radius, id_filter)
+
+    def range_search_ip(self, queries, nprobe, threshold, id_filter=None):
+        """Every row of the nprobe lists probe_ip() names whose exact inner product is above `threshold`, strictly
+        (dpq_flat_ivf_range_search_ip[_bytes]); each list by (score descending, id)."""
+        return self._range_call(1, queries, None, nprobe, threshold, id_filter)
+
+    def range_search_probes_ip(self, queries, probes, threshold, id_filter=None):
+        """range_search_ip over the caller's own lists (dpq_flat_ivf_range_search_probes_ip[_bytes])."""
+        return self._range_call(1, queries, probes, 0, threshold, id_filter)
+
     def _torch_out(self, queries, top_k, out_ids, out_dists):
         assert queries.dim() == 2 and queries.shape[1] == self._index.D
         return IVF._torch_out(queries, top_k, out_ids, out_dists)
@@ -2076,6 +2114,7 @@ class FlatIVFBytes(FlatIVF):
     _IP = dict(probe="dpq_flat_ivf_probe_ip_bytes", search="dpq_flat_ivf_search_ip_bytes",
                search_device="dpq_flat_ivf_search_ip_bytes_device", probes="dpq_flat_ivf_search_probes_ip_bytes",
                probes_device="dpq_flat_ivf_search_probes_ip_bytes_device")
+    _RANGE = ("_bytes", "_ip_bytes")
 
     @classmethod
     def build(cls, flat_index, centroids):
@@ -2473,6 +2512,8 @@ class FlatIVFBits(FlatIVF):
     as FlatIndexBits checks its queries (anything else is a TypeError); the centroids are ranked by Hamming distance,
     ties to the lower list number.  There is no trainer for binary centroids: binarise train_ivf_centroids' output with
     bits_from_float (and the rows' thresholds), or take rows of the base."""
+
+    _RANGE = ("_bits", "_ip")
 
     @classmethod
     def build(cls, flat_index, centroids):

@@ -287,6 +287,53 @@ int fivf_group_cfg(int kind, int format) {
     return group;
 }
 
+// What the scans of the four row formats run over: the handle's rows and the structure's lists, under a filter's bitmap
+// (ff NULL: none) and a metric.  The scan of the structure's kind and the handle's format reads its own member.
+struct FivfLists {
+    dpq::FlatIvfLists f32;
+    dpq::FlatIvfListsU8 u8;
+    dpq::FlatIvfListsBits bits;
+    dpq::FlatIvfListsNarrow narrow;  // a half or a quantised handle
+};
+
+int fivf_lists(dpq_flat_ivf* v, const dpq_flat_filter* ff, int metric, FivfLists* L) {
+    const dpq_flat* f = v->flat;
+    L->f32.rows = reinterpret_cast<const float*>(f->rows.get() + f->rows_at);
+    L->f32.Dp = f->Dp;
+    L->f32.id_offset = f->id_offset;
+    L->f32.offsets = v->offsets;
+    L->f32.list_rows = v->rows;
+    L->f32.nlist = v->nlist;
+    L->u8.rows = reinterpret_cast<const int8_t*>(f->rows.get() + f->rows_at);
+    L->u8.norm = f->norm8;
+    L->u8.Dp = f->Dp;
+    L->u8.id_offset = f->id_offset;
+    L->u8.offsets = v->offsets;
+    L->u8.list_rows = v->rows;
+    L->u8.nlist = v->nlist;
+    L->bits.rows = reinterpret_cast<const uint32_t*>(f->rows.get() + f->rows_at);
+    L->bits.Wp = f->Dp >> 2;
+    L->bits.id_offset = f->id_offset;
+    L->bits.offsets = v->offsets;
+    L->bits.list_rows = v->rows;
+    L->bits.nlist = v->nlist;
+    L->narrow.format = f->format;
+    L->narrow.rows = f->rows.get() + f->rows_at;
+    L->narrow.Dp = f->Dp;
+    L->narrow.id_offset = f->id_offset;
+    L->narrow.offsets = v->offsets;
+    L->narrow.list_rows = v->rows;
+    L->narrow.nlist = v->nlist;
+    L->f32.filter = L->u8.filter = L->bits.filter = L->narrow.filter = ff ? ff->words.get() : nullptr;
+    L->f32.metric = L->u8.metric = L->narrow.metric = metric;
+    if (metric == dpq::kFlatIP && v->kind == kFivfBytes) {  // the rows' terms in the place of the norms; none for signed rows
+        if (f->format == dpq::kFlatU8)
+            if (int rc = flat_ensure_rsum(v->flat)) return rc;
+        L->u8.norm = f->format == dpq::kFlatU8 ? f->rsum8.get() : nullptr;
+    }
+    return DPQ_OK;
+}
+
 // The search behind its checks, all device pointers; qs: the prepared queries.  Slices of queries: per slice the probe
 // pre-pass, the pairs sorted by list, the list scan of the structure's kind, the merge of the pairs' answers in rounds.
 // Ends with the flag word read back.  ff (NULL: none): the scans take the rows its bitmap allows only.
@@ -320,43 +367,12 @@ int fivf_search_on_device(dpq_flat_ivf* v, const std::string& who, const FivfQue
     if (!rc && nprobe > round) rc = grow(v->tmp_dists, &v->tmp_dists_n, (size_t)per * top_k);
     if (!rc && !v->flag.get()) rc = v->flag.alloc(1);
     if (rc) return rc;
-    dpq::FlatIvfLists lists;
-    lists.rows = reinterpret_cast<const float*>(f->rows.get() + f->rows_at);
-    lists.Dp = f->Dp;
-    lists.id_offset = f->id_offset;
-    lists.offsets = v->offsets;
-    lists.list_rows = v->rows;
-    lists.nlist = v->nlist;
-    dpq::FlatIvfListsU8 lists8;
-    lists8.rows = reinterpret_cast<const int8_t*>(f->rows.get() + f->rows_at);
-    lists8.norm = f->norm8;
-    lists8.Dp = f->Dp;
-    lists8.id_offset = f->id_offset;
-    lists8.offsets = v->offsets;
-    lists8.list_rows = v->rows;
-    lists8.nlist = v->nlist;
-    dpq::FlatIvfListsBits listsb;
-    listsb.rows = reinterpret_cast<const uint32_t*>(f->rows.get() + f->rows_at);
-    listsb.Wp = f->Dp >> 2;
-    listsb.id_offset = f->id_offset;
-    listsb.offsets = v->offsets;
-    listsb.list_rows = v->rows;
-    listsb.nlist = v->nlist;
-    dpq::FlatIvfListsNarrow listsn;  // a half or a quantised handle
-    listsn.format = f->format;
-    listsn.rows = f->rows.get() + f->rows_at;
-    listsn.Dp = f->Dp;
-    listsn.id_offset = f->id_offset;
-    listsn.offsets = v->offsets;
-    listsn.list_rows = v->rows;
-    listsn.nlist = v->nlist;
-    lists.filter = lists8.filter = listsb.filter = listsn.filter = ff ? ff->words.get() : nullptr;
-    lists.metric = lists8.metric = listsn.metric = metric;
-    if (metric == dpq::kFlatIP && v->kind == kFivfBytes) {  // the rows' terms in the place of the norms; none for signed rows
-        if (f->format == dpq::kFlatU8)
-            if (int rc2 = flat_ensure_rsum(v->flat)) return rc2;
-        lists8.norm = f->format == dpq::kFlatU8 ? f->rsum8.get() : nullptr;
-    }
+    FivfLists L;
+    if ((rc = fivf_lists(v, ff, metric, &L))) return rc;
+    const dpq::FlatIvfLists& lists = L.f32;
+    const dpq::FlatIvfListsU8& lists8 = L.u8;
+    const dpq::FlatIvfListsBits& listsb = L.bits;
+    const dpq::FlatIvfListsNarrow& listsn = L.narrow;
     const int group = fivf_group_cfg(v->kind, f->format);
     DPQ_HIP(hipMemsetAsync(v->flag, 0, sizeof(uint32_t), stream));
     for (int q0 = 0; q0 < nq; q0 += per) {
@@ -621,6 +637,185 @@ int fivf_search(const std::string& who, int kind, dpq_flat_ivf* v, const void* q
     if (int rc = fivf_probe_on_device(v, q, nq, nprobe, v->d_probes, v->d_cdists, nullptr, metric)) return rc;
     if (int rc = fivf_search_on_device(v, who, q, nq, v->d_probes, nprobe, top_k, v->d_ids, v->d_dists, nullptr, ff, metric)) return rc;
     return fivf_results_down(v, nq, top_k, ids, dists);
+}
+
+// ---- range search over the probed lists ------------------------------------------------------------------
+
+// One pass of the range scan of the structure's kind over queries q0 .. q0 + m - 1 and their sorted pairs: counting
+// (r.pool NULL) or emitting.
+int fivf_range_pass(dpq_flat_ivf* v, const FivfLists& L, const FivfQueries& qs, int q0, int m, int nprobe, int group,
+                    const dpq::FlatIvfRange& r) {
+    const dpq_flat* f = v->flat;
+    if (v->kind == kFivfBits)
+        DPQ_HIP(dpq::launch_flat_ivf_range_bits(L.bits, reinterpret_cast<const uint32_t*>(qs.bits + (size_t)q0 * f->Dp), m, nprobe,
+                                                v->skeys, v->svals, group, r, nullptr));
+    else if (v->kind == kFivfBytes)
+        DPQ_HIP(dpq::launch_flat_ivf_range_u8(L.u8, qs.i8 + (size_t)q0 * f->Dp, qs.norm ? qs.norm + q0 : nullptr, m, nprobe, v->skeys,
+                                              v->svals, group, r, nullptr));
+    else if (f->format != dpq::kFlatF32)
+        DPQ_HIP(dpq::launch_flat_ivf_range_narrow(L.narrow, qs.f32 + (size_t)q0 * f->Dp, m, nprobe, v->skeys, v->svals, group, r, nullptr));
+    else
+        DPQ_HIP(dpq::launch_flat_ivf_range(L.f32, qs.f32 + (size_t)q0 * f->Dp, m, nprobe, v->skeys, v->svals, group, r, nullptr));
+    return DPQ_OK;
+}
+
+// dpq_flat_ivf_range_search[_probes][_ip][_bytes | _bits].  probes == NULL: the coarse step.  Slices of at most 2048
+// queries: the probe pre-pass, the pairs sorted by list, the count pass and its exclusive scan, and ONE host round trip for
+// the queries' totals; then sub-batches of queries whose lists fit the pool: the emit pass, the segmented sort, the keys
+// down and split on the host (inner product: the key words back to scores).
+int fivf_range_call(const char* fn, int kind, int metric, dpq_flat_ivf* v, const dpq_flat_filter* ff, const void* queries, int nq,
+                    const int32_t* probes, bool coarse, int nprobe, const float* radii, dpq_range_result** out) {
+    const std::string who = fn;
+    const bool ip = metric == dpq::kFlatIP;
+    if (!out) return fail(DPQ_ERR_ARG, who + ": out is NULL");
+    *out = nullptr;
+    if (!v || nq < 0 || (nq > 0 && (!queries || !radii || (!coarse && !probes))))
+        return fail(DPQ_ERR_ARG, who + ": NULL argument or nq < 0");
+    if (nprobe < 1 || nprobe > dpq::kIvfMaxProbe) return fail(DPQ_ERR_ARG, who + ": needs 1 <= nprobe <= min(nlist, 1024)");
+    for (int q = 0; q < nq; ++q)
+        if (std::isnan(radii[q]))
+            return fail(DPQ_ERR_ARG, who + (ip ? ": threshold of query " : ": radius of query ") + std::to_string(q) + " is NaN");
+    if (int rc = fivf_filter_ok(who, v, ff)) return rc;
+    if (nprobe > v->nlist) return fail(DPQ_ERR_ARG, who + ": needs 1 <= nprobe <= min(nlist, 1024)");
+    if (!coarse)
+        if (int rc = fivf_probe_rows_ok(who, v, probes, nq, nprobe)) return rc;
+    if (int rc = fivf_enter(who, v, kind, nprobe, coarse)) return rc;
+    std::unique_ptr<dpq_range_result> res(new dpq_range_result());
+    res->nq = nq;
+    res->lims.assign((size_t)nq + 1, 0);
+    if (nq == 0) {
+        *out = res.release();
+        return DPQ_OK;
+    }
+    FivfQueries qs;
+    if (int rc = fivf_queries(v, queries, nq, false, coarse, nullptr, &qs, metric)) return rc;
+    const int per = std::min(nq, dpq::kIvfSliceQueries);
+    const size_t pairs = (size_t)per * nprobe, slots = pairs + 1;
+    const int64_t budget = ivf_range_pool_keys();
+    size_t sort_bytes = 0, last_bytes = 0, scan_bytes = 0;  // of a full slice's pair sort, of the last slice's, of the offsets' scan
+    DPQ_HIP(dpq::flat_ivf_sort_pairs(nullptr, &sort_bytes, nullptr, nullptr, nullptr, nullptr, (int64_t)pairs, v->nlist, nullptr));
+    if (nq % per)
+        DPQ_HIP(dpq::flat_ivf_sort_pairs(nullptr, &last_bytes, nullptr, nullptr, nullptr, nullptr, (int64_t)(nq % per) * nprobe,
+                                         v->nlist, nullptr));
+    sort_bytes = std::max(sort_bytes, last_bytes);
+    int rc = fivf_stage(v, nq, nprobe, 0);
+    if (!rc) rc = grow(v->probes, &v->probes_n, pairs);
+    if (!rc && v->pairs_n < pairs) {
+        v->pairs_n = 0;
+        rc = v->pkeys.alloc(pairs);
+        if (!rc) rc = v->pvals.alloc(pairs);
+        if (!rc) rc = v->skeys.alloc(pairs);
+        if (!rc) rc = v->svals.alloc(pairs);
+        if (!rc) v->pairs_n = pairs;
+    }
+    if (!rc) rc = grow(v->sort_temp, &v->sort_n, sort_bytes);
+    if (!rc) rc = grow(v->r_thr, &v->r_thr_n, (size_t)nq);
+    if (!rc) rc = grow(v->r_counts, &v->r_counts_n, slots);
+    if (!rc) rc = grow(v->r_offs, &v->r_offs_n, slots);
+    if (!rc) rc = grow(v->r_qoffs, &v->r_qoffs_n, (size_t)per + 1);
+    if (!rc) rc = grow(v->r_pool, &v->r_pool_n, (size_t)budget);
+    if (!rc) rc = grow(v->r_sorted, &v->r_sorted_n, (size_t)budget);
+    if (!rc && !v->flag.get()) rc = v->flag.alloc(1);
+    if (rc) return rc;
+    std::vector<uint64_t> thr((size_t)nq), sorted;
+    for (int q = 0; q < nq; ++q) {
+        const float r = radii[q];
+        uint32_t bits = 0;
+        if (ip) {  // s > t is word(s) < word(t): dpq_flat_range_search_ip's rule
+            memcpy(&bits, &r, sizeof bits);
+            thr[(size_t)q] = (uint64_t)dpq::flat_ip_word(bits) << 32;
+        } else {  // d < r on non-negative floats is bits(d) < bits(r); key 0 lets nothing pass, ~0 everything
+            if (r > 0.0f) memcpy(&bits, &r, sizeof bits);
+            thr[(size_t)q] = std::isinf(r) && r > 0.0f ? dpq::kFlatNoKey : (uint64_t)bits << 32;
+        }
+    }
+    DPQ_HIP(hipMemcpy(v->r_thr, thr.data(), (size_t)nq * sizeof(uint64_t), hipMemcpyHostToDevice));
+    if (coarse) {
+        if ((rc = fivf_probe_on_device(v, qs, nq, nprobe, v->d_probes, v->d_cdists, nullptr, metric))) return rc;
+    } else {
+        DPQ_HIP(hipMemcpy(v->d_probes, probes, (size_t)nq * nprobe * sizeof(int32_t), hipMemcpyHostToDevice));
+    }
+    FivfLists L;
+    if ((rc = fivf_lists(v, ff, metric, &L))) return rc;
+    const int group = fivf_group_cfg(v->kind, v->flat->format);
+    DPQ_HIP(hipMemsetAsync(v->flag, 0, sizeof(uint32_t), nullptr));
+    DPQ_HIP(dpq::ivf_range_offsets(nullptr, &scan_bytes, v->r_counts, v->r_offs, (int64_t)slots, nullptr));
+    DevBuf<uint8_t> scan_temp;
+    if ((rc = scan_temp.alloc(scan_bytes))) return rc;
+    std::vector<int64_t> tot((size_t)per + 1), qoffs, offs_h;
+    for (int q0 = 0; q0 < nq; q0 += per) {
+        const int m = std::min(per, nq - q0);
+        const int64_t n_pairs = (int64_t)m * nprobe;
+        DPQ_HIP(dpq::launch_ivf_probes(v->d_probes.get() + (size_t)q0 * nprobe, m, nprobe, v->nlist, v->probes, v->flag, nullptr));
+        DPQ_HIP(dpq::launch_flat_ivf_pairs(v->probes, n_pairs, v->nlist, v->pkeys, v->pvals, nullptr));
+        size_t tb = v->sort_n;
+        DPQ_HIP(dpq::flat_ivf_sort_pairs(v->sort_temp, &tb, v->pkeys, v->skeys, v->pvals, v->svals, n_pairs, v->nlist, nullptr));
+        DPQ_HIP(hipMemsetAsync(v->r_counts.get() + n_pairs, 0, sizeof(int64_t), nullptr));  // the slot behind the last pair
+        dpq::FlatIvfRange r;
+        r.thr = v->r_thr.get() + q0;
+        r.counts = v->r_counts;
+        if ((rc = fivf_range_pass(v, L, qs, q0, m, nprobe, group, r))) return rc;
+        tb = scan_bytes;
+        DPQ_HIP(dpq::ivf_range_offsets(scan_temp, &tb, v->r_counts, v->r_offs, n_pairs + 1, nullptr));
+        // the queries' list starts: every nprobe-th offset, and the slice's total behind them (one contiguous copy: a
+        // strided one to pageable memory goes row by row)
+        offs_h.resize((size_t)n_pairs + 1);
+        DPQ_HIP(hipMemcpy(offs_h.data(), v->r_offs, offs_h.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
+        for (int q = 0; q <= m; ++q) tot[(size_t)q] = offs_h[(size_t)q * nprobe];
+        const int64_t at0 = res->lims[(size_t)q0];
+        for (int q = 0; q <= m; ++q) {
+            if (tot[(size_t)q] < 0 || (q > 0 && tot[(size_t)q] < tot[(size_t)q - 1]))
+                return fail(DPQ_ERR_STATE, who + ": internal error: the list offsets do not ascend");
+            res->lims[(size_t)q0 + q] = at0 + tot[(size_t)q];
+        }
+        res->ids.resize((size_t)res->lims[(size_t)q0 + m]);
+        res->dists.resize((size_t)res->lims[(size_t)q0 + m]);
+        for (int a = 0; a < m;) {
+            int b = a + 1;
+            while (b < m && tot[(size_t)b + 1] - tot[(size_t)a] <= budget) ++b;
+            const int64_t sum = tot[(size_t)b] - tot[(size_t)a];
+            if (sum > 0) {
+                DevBuf<uint64_t> own_pool, own_sorted;  // one query's list beyond the pool: buffers of this call
+                uint64_t *pool = v->r_pool, *spool = v->r_sorted;
+                if (sum > budget) {
+                    if ((rc = own_pool.alloc((size_t)sum))) return rc;
+                    if ((rc = own_sorted.alloc((size_t)sum))) return rc;
+                    pool = own_pool;
+                    spool = own_sorted;
+                }
+                qoffs.assign((size_t)(b - a) + 1, 0);
+                for (int q = a; q <= b; ++q) qoffs[(size_t)(q - a)] = tot[(size_t)q] - tot[(size_t)a];
+                DPQ_HIP(hipMemcpy(v->r_qoffs, qoffs.data(), qoffs.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+                r.offs = v->r_offs;
+                r.pool_base = tot[(size_t)a];
+                r.pool = pool;
+                r.pool_n = sum;
+                r.qa = a;
+                r.qb = b;
+                if ((rc = fivf_range_pass(v, L, qs, q0, m, nprobe, group, r))) return rc;
+                size_t sb = 0;
+                DPQ_HIP(dpq::flat_range_sort(nullptr, &sb, pool, spool, sum, b - a, v->r_qoffs, nullptr));
+                DevBuf<uint8_t> temp;  // the segmented sort's workspace
+                if ((rc = temp.alloc(sb))) return rc;
+                DPQ_HIP(dpq::flat_range_sort(temp, &sb, pool, spool, sum, b - a, v->r_qoffs, nullptr));
+                sorted.resize((size_t)sum);
+                DPQ_HIP(hipMemcpy(sorted.data(), spool, (size_t)sum * sizeof(uint64_t), hipMemcpyDeviceToHost));
+                const size_t at = (size_t)(at0 + tot[(size_t)a]);
+                for (size_t i = 0; i < (size_t)sum; ++i) {
+                    uint32_t bits = (uint32_t)(sorted[i] >> 32);
+                    if (ip) bits = dpq::flat_ip_word(bits);
+                    res->ids[at + i] = (int32_t)(uint32_t)sorted[i];
+                    memcpy(&res->dists[at + i], &bits, sizeof bits);
+                }
+            }
+            a = b;
+        }
+    }
+    uint32_t bad = 0;
+    DPQ_HIP(hipMemcpy(&bad, v->flag, sizeof bad, hipMemcpyDeviceToHost));
+    if (bad) return fail(DPQ_ERR_ARG, who + ": a probe names no list (an entry >= nlist)");
+    *out = res.release();
+    return DPQ_OK;
 }
 
 }  // namespace
@@ -908,6 +1103,58 @@ int dpq_flat_ivf_search_ip_bytes_device(dpq_flat_ivf* v, const void* d_queries, 
 int dpq_flat_ivf_search_ip_bytes(dpq_flat_ivf* v, const void* queries, int nq, int nprobe, int top_k, int32_t* ids, float* scores,
         const dpq_flat_filter* filter) {
     return guarded([&]() -> int { return fivf_search("dpq_flat_ivf_search_ip_bytes", kFivfBytes, v, queries, nq, nprobe, top_k, ids, scores, filter, dpq::kFlatIP); });
+}
+
+// ---- range search: host forms; the answer is freed by dpq_range_result_free ------------------------------------------------
+
+int dpq_flat_ivf_range_search(dpq_flat_ivf* v, const dpq_flat_filter* filter, const float* queries, int nq, int nprobe, const float* radii,
+        dpq_range_result** out) {
+    return guarded([&]() -> int { return fivf_range_call("dpq_flat_ivf_range_search", kFivfF32, dpq::kFlatL2, v, filter, queries, nq, nullptr, true, nprobe, radii, out); });
+}
+
+int dpq_flat_ivf_range_search_probes(dpq_flat_ivf* v, const dpq_flat_filter* filter, const float* queries, int nq, const int32_t* probes,
+        int nprobe, const float* radii, dpq_range_result** out) {
+    return guarded([&]() -> int { return fivf_range_call("dpq_flat_ivf_range_search_probes", kFivfF32, dpq::kFlatL2, v, filter, queries, nq, probes, false, nprobe, radii, out); });
+}
+
+int dpq_flat_ivf_range_search_ip(dpq_flat_ivf* v, const dpq_flat_filter* filter, const float* queries, int nq, int nprobe,
+        const float* thresholds, dpq_range_result** out) {
+    return guarded([&]() -> int { return fivf_range_call("dpq_flat_ivf_range_search_ip", kFivfF32, dpq::kFlatIP, v, filter, queries, nq, nullptr, true, nprobe, thresholds, out); });
+}
+
+int dpq_flat_ivf_range_search_probes_ip(dpq_flat_ivf* v, const dpq_flat_filter* filter, const float* queries, int nq, const int32_t* probes,
+        int nprobe, const float* thresholds, dpq_range_result** out) {
+    return guarded([&]() -> int { return fivf_range_call("dpq_flat_ivf_range_search_probes_ip", kFivfF32, dpq::kFlatIP, v, filter, queries, nq, probes, false, nprobe, thresholds, out); });
+}
+
+int dpq_flat_ivf_range_search_bytes(dpq_flat_ivf* v, const dpq_flat_filter* filter, const void* queries, int nq, int nprobe, const float* radii,
+        dpq_range_result** out) {
+    return guarded([&]() -> int { return fivf_range_call("dpq_flat_ivf_range_search_bytes", kFivfBytes, dpq::kFlatL2, v, filter, queries, nq, nullptr, true, nprobe, radii, out); });
+}
+
+int dpq_flat_ivf_range_search_probes_bytes(dpq_flat_ivf* v, const dpq_flat_filter* filter, const void* queries, int nq, const int32_t* probes,
+        int nprobe, const float* radii, dpq_range_result** out) {
+    return guarded([&]() -> int { return fivf_range_call("dpq_flat_ivf_range_search_probes_bytes", kFivfBytes, dpq::kFlatL2, v, filter, queries, nq, probes, false, nprobe, radii, out); });
+}
+
+int dpq_flat_ivf_range_search_ip_bytes(dpq_flat_ivf* v, const dpq_flat_filter* filter, const void* queries, int nq, int nprobe,
+        const float* thresholds, dpq_range_result** out) {
+    return guarded([&]() -> int { return fivf_range_call("dpq_flat_ivf_range_search_ip_bytes", kFivfBytes, dpq::kFlatIP, v, filter, queries, nq, nullptr, true, nprobe, thresholds, out); });
+}
+
+int dpq_flat_ivf_range_search_probes_ip_bytes(dpq_flat_ivf* v, const dpq_flat_filter* filter, const void* queries, int nq, const int32_t* probes,
+        int nprobe, const float* thresholds, dpq_range_result** out) {
+    return guarded([&]() -> int { return fivf_range_call("dpq_flat_ivf_range_search_probes_ip_bytes", kFivfBytes, dpq::kFlatIP, v, filter, queries, nq, probes, false, nprobe, thresholds, out); });
+}
+
+int dpq_flat_ivf_range_search_bits(dpq_flat_ivf* v, const dpq_flat_filter* filter, const uint8_t* queries, int nq, int nprobe, const float* radii,
+        dpq_range_result** out) {
+    return guarded([&]() -> int { return fivf_range_call("dpq_flat_ivf_range_search_bits", kFivfBits, dpq::kFlatL2, v, filter, queries, nq, nullptr, true, nprobe, radii, out); });
+}
+
+int dpq_flat_ivf_range_search_probes_bits(dpq_flat_ivf* v, const dpq_flat_filter* filter, const uint8_t* queries, int nq, const int32_t* probes,
+        int nprobe, const float* radii, dpq_range_result** out) {
+    return guarded([&]() -> int { return fivf_range_call("dpq_flat_ivf_range_search_probes_bits", kFivfBits, dpq::kFlatL2, v, filter, queries, nq, probes, false, nprobe, radii, out); });
 }
 
 }  // extern "C"

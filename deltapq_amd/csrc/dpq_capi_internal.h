@@ -271,6 +271,12 @@ struct dpq_flat_ivf {
     DevBuf<int8_t> q8;
     DevBuf<int32_t> qnorm;
     size_t q_raw_n = 0, q8_n = 0, qnorm_n = 0;
+    // range search (dpq_flat_ivf_range_search*): the threshold keys of the call; a slice's counts per pair and their
+    // exclusive scan; a sub-batch's list starts; the unsorted and the sorted key pool (at most dpq::kIvfRangePoolKeys each:
+    // a longer single list works in buffers of the call)
+    DevBuf<uint64_t> r_thr, r_pool, r_sorted;
+    DevBuf<int64_t> r_counts, r_offs, r_qoffs;
+    size_t r_thr_n = 0, r_pool_n = 0, r_sorted_n = 0, r_counts_n = 0, r_offs_n = 0, r_qoffs_n = 0;
 };
 
 uint64_t next_index_serial();  // dpq_capi.cpp: one counter for the process
@@ -538,6 +544,7 @@ int query_device_src(dpq_index* x, const dpq_filter* filt, const TableSource& sr
 int range_search_src(dpq_index* x, const TableSource& src, int nq, const float* radii, dpq_range_result** out);  // dpq_capi.cpp
 int ensure_out_stage(dpq_index* x, size_t elems);  // d_ids_stage / d_dists_stage                                  dpq_capi.cpp
 int splits_for(int n_seg_pass, int n_groups);  // scan workgroups per query group                                dpq_capi.cpp
+int64_t ivf_range_pool_keys();  // the range pool of dpq_ivf and dpq_flat_ivf, in keys (dpq_capi_ivf.cpp)
 int flat_ensure_rsum(dpq_flat* f);  // a u8 handle's row terms of the inner product, made on first use (dpq_capi_flat.cpp)
 int flat_device_present(const std::string& who);                                                                // dpq_capi_flat.cpp
 bool lookup_id_ok(const dpq_index* x, int64_t id);                                                              // dpq_capi_lookup.cpp

@@ -490,6 +490,8 @@ int ivf_call(dpq_ivf* v, const IvfCall& c) {
 
 // ---- range search over lists ---------------------------------------------------------------------------------------
 
+}  // namespace
+
 // Keys a group of queries may lay out in the structure's pool (a longer single list works in buffers of the call).
 int64_t ivf_range_pool_keys() {
     int64_t keys = dpq::kIvfRangePoolKeys;
@@ -498,6 +500,8 @@ int64_t ivf_range_pool_keys() {
             keys = std::min(keys, std::max<int64_t>(1, atoll(e)));
     return keys;
 }
+
+namespace {
 
 // dpq_ivf_range_search[_probes].  probes == NULL: the coarse step.  Slices of at most 2048 queries: their tables, the probe
 // pre-pass, the count pass and its exclusive scan, and ONE host round trip for the queries' totals; then groups of queries

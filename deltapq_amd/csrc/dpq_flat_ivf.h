@@ -163,4 +163,38 @@ hipError_t launch_flat_ivf_scan_narrow(const FlatIvfListsNarrow& lists, const fl
 hipError_t launch_flat_ivf_narrow_widen(int format, const void* d_rows, int Dp, int64_t r0, int64_t rows, float* d_out,
                                         hipStream_t stream);
 
+// ---- range search: every row of the probed lists below a threshold ----------------------------------------
+// The four scans above with a second sink in the place of the running top-k.  thr [nq]: a query's threshold as a key --
+// distance bits << 32 (0 passes nothing, kFlatNoKey everything), or flat_ip_word of a score threshold << 32; a key passes
+// when key < thr.  pool == NULL, the count pass: counts[q * nprobe + j] = the eligible rows of pair (q, j)'s list that pass
+// (0 for padding, a repeat, an empty list); one workgroup writes a pair's count, once.  Else the emit pass: the pairs whose
+// count is 0 or whose query lies outside [qa, qb) are dropped before anything of their list is read, the stretch's
+// surviving queries are compacted, and the passing keys of pair i go to pool[offs[i] - pool_base ..) in no particular
+// order (offs: ivf_range_offsets of the counts); nothing is written at or past pool_n.  No key buffers in LDS: the group
+// is the largest of 16, 8, 4, 2, 1 that is at most `group`, whatever the format.
+struct FlatIvfRange {
+    const uint64_t* thr = nullptr;
+    int64_t* counts = nullptr;  // written by the count pass, read by the emit pass
+    const int64_t* offs = nullptr;
+    int64_t pool_base = 0;
+    uint64_t* pool = nullptr;
+    int64_t pool_n = 0;
+    int qa = 0, qb = 0;
+};
+
+int flat_ivf_range_group(int group);
+
+// The arguments are those of the scan of the same row format; d_qnorm as in launch_flat_ivf_scan_u8.
+hipError_t launch_flat_ivf_range(const FlatIvfLists& lists, const float* d_queries, int nq, int nprobe, const uint32_t* d_skeys,
+                                 const uint32_t* d_svals, int group, const FlatIvfRange& range, hipStream_t stream);
+hipError_t launch_flat_ivf_range_narrow(const FlatIvfListsNarrow& lists, const float* d_queries, int nq, int nprobe,
+                                        const uint32_t* d_skeys, const uint32_t* d_svals, int group, const FlatIvfRange& range,
+                                        hipStream_t stream);
+hipError_t launch_flat_ivf_range_u8(const FlatIvfListsU8& lists, const int8_t* d_queries, const int32_t* d_qnorm, int nq, int nprobe,
+                                    const uint32_t* d_skeys, const uint32_t* d_svals, int group, const FlatIvfRange& range,
+                                    hipStream_t stream);
+hipError_t launch_flat_ivf_range_bits(const FlatIvfListsBits& lists, const uint32_t* d_queries, int nq, int nprobe,
+                                      const uint32_t* d_skeys, const uint32_t* d_svals, int group, const FlatIvfRange& range,
+                                      hipStream_t stream);
+
 }  // namespace dpq

@@ -63,7 +63,9 @@ __device__ __forceinline__ void load_slice(float4 (&pre)[8], const float* __rest
 }
 
 // grid: the runs; 256 threads; dynamic LDS: the tiles, then G buffers of cap = 2 P2 keys.
-template <int QPL, bool FILTERED, int METRIC>
+// SINK (dpq_flat_ivf_device.h): kSinkTopK as described above; kSinkCount / kSinkEmit, the passes of a range search, take
+// `sink.r`, keep no buffers (top_k, cap and the outputs are unused) and share every line of the distance loop.
+template <int QPL, bool FILTERED, int METRIC, int SINK>
 __global__ __launch_bounds__(256) void flat_ivf_scan_kernel(const float* __restrict__ rows, int Dp, int64_t id_offset,
                                                             const int64_t* __restrict__ offsets,
                                                             const uint32_t* __restrict__ list_rows, int nlist,
@@ -72,7 +74,8 @@ __global__ __launch_bounds__(256) void flat_ivf_scan_kernel(const float* __restr
                                                             const uint32_t* __restrict__ svals, int64_t n_pairs, int G,
                                                             int top_k, int cap, int32_t* __restrict__ part_ids,
                                                             float* __restrict__ part_dists,
-                                                            const uint32_t* __restrict__ fbits) {
+                                                            const uint32_t* __restrict__ fbits,
+                                                            [[maybe_unused]] SinkArgs<SINK> sink) {
     extern __shared__ __attribute__((aligned(16))) unsigned char flat_ivf_smem[];
     float* Rs = reinterpret_cast<float*>(flat_ivf_smem);          // [SD][RS]
     float* Qs = Rs + SD * RS;                                     // [SD][GM]
@@ -81,6 +84,7 @@ __global__ __launch_bounds__(256) void flat_ivf_scan_kernel(const float* __restr
     __shared__ uint32_t s_key[GM], s_val[GM], s_q[GM], s_cnt[GM];
     __shared__ uint64_t s_thr[GM];
     const int tid = threadIdx.x, tx = tid & 63, ty = tid >> 6;
+    [[maybe_unused]] RangeLds* rl = nullptr;
     const int64_t p0 = (int64_t)blockIdx.x * G;
     const int np = (int)min((int64_t)G, n_pairs - p0);
     if (tid < GM) {
@@ -96,16 +100,29 @@ __global__ __launch_bounds__(256) void flat_ivf_scan_kernel(const float* __restr
         const uint32_t list = s_key[s];
         int e = s + 1;
         while (e < np && s_key[e] == list) ++e;
-        const int nqs = e - s;  // queries of the stretch: pairs s .. e - 1
+        int nqs = e - s;  // queries of the stretch: pairs s .. e - 1
+        if constexpr (SINK != kSinkTopK) {  // the thresholds; emit: only the pairs with hits stay, compacted
+            __shared__ RangeLds s_range;
+            rl = &s_range;
+            nqs = range_begin<SINK>(sink.r, s_val, s_q, s_cnt, s_thr, s_range, s, nqs, tid);
+            if (nqs == 0) {  // (emit only) nothing of the list is read
+                s = e;
+                continue;
+            }
+        }
         int64_t lo = 0, hi = 0;
         if (list < (uint32_t)nlist) {
             lo = offsets[list];
             hi = offsets[list + 1];
         }
-        if (tid < nqs) {
-            s_cnt[tid] = 0u;
-            s_thr[tid] = kFlatNoKey;
-        }
+        if constexpr (SINK == kSinkTopK)
+            if (tid < nqs) {
+                s_cnt[tid] = 0u;
+                s_thr[tid] = kFlatNoKey;
+            }
+        [[maybe_unused]] uint32_t hits[QPL];  // count: this lane's passing keys per query it owns, over the stretch
+#pragma unroll
+        for (int i = 0; i < QPL; ++i) hits[i] = 0u;
         const bool active = QPL * ty < nqs;  // (a wavefront's lanes share ty)
         for (int64_t base = lo; base < hi; base += FILTERED ? 0 : TR) {
             __syncthreads();  // the tile before is done with s_rows; the first tile: the counts above are in place
@@ -180,12 +197,31 @@ __global__ __launch_bounds__(256) void flat_ivf_scan_kernel(const float* __restr
                         const uint32_t row = s_rows[4 * tx + j];
                         if (row == kNoRow) continue;
                         const uint64_t key = make_key<METRIC>(acc[i][j], (uint32_t)(id_offset + (int64_t)row));
-                        if (key < thr) b[atomicAdd(&s_cnt[qs], 1u)] = key;  // < cap: the tile had room for its 256 rows
+                        if (key >= thr) continue;
+                        if constexpr (SINK == kSinkTopK) b[atomicAdd(&s_cnt[qs], 1u)] = key;  // < cap: the tile had room for its 256 rows
+                        else if constexpr (SINK == kSinkCount) ++hits[i];
+                        else range_put(sink.r, *rl, s_cnt, qs, key);
                     }
                 }
             }
-            __syncthreads();
-            if (base + (FILTERED ? 0 : TR) < hi) sink_make_room(buf, s_cnt, s_thr, nqs, cap, top_k, tid);
+            if constexpr (SINK == kSinkTopK) {  // (the range sinks need no barrier of their own between two tiles)
+                __syncthreads();
+                if (base + (FILTERED ? 0 : TR) < hi) sink_make_room(buf, s_cnt, s_thr, nqs, cap, top_k, tid);
+            }
+        }
+        if constexpr (SINK != kSinkTopK) {
+            if constexpr (SINK == kSinkCount) {
+                if (active && hi > lo)  // (a wavefront's lanes share their queries)
+#pragma unroll
+                    for (int i = 0; i < QPL; ++i) {
+                        const uint32_t c = wave_sum(hits[i]);
+                        if (tx == 0 && QPL * ty + i < nqs) atomicAdd(&s_cnt[QPL * ty + i], c);
+                    }
+                range_counts_out(sink.r, s_val, s_cnt, s, nqs, hi > lo, tid);
+            }
+            __syncthreads();  // the next stretch starts the counts over
+            s = e;
+            continue;
         }
         if (hi > lo) sink_sort(buf, s_cnt, nqs, cap, tid);  // (behind the last tile's closing barrier)
         // the stretch's answers: pair i = q * nprobe + j goes to row j * nq + q.  A padding pair, or an empty list: padding
@@ -201,14 +237,15 @@ __global__ __launch_bounds__(256) void flat_ivf_scan_kernel(const float* __restr
 }
 
 // hipFuncSetAttribute is per device
-template <int QPL, bool FILTERED, int METRIC>
+template <int QPL, bool FILTERED, int METRIC, int SINK>
 hipError_t ensure_scan_lds() {
+    if constexpr (SINK != kSinkTopK) return hipSuccess;  // the range sinks' tiles fit the default 64 KB
     static std::atomic<bool> done[64];
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
     if (dev < 0 || dev >= 64 || !done[dev].load(std::memory_order_acquire)) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&flat_ivf_scan_kernel<QPL, FILTERED, METRIC>),
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&flat_ivf_scan_kernel<QPL, FILTERED, METRIC, SINK>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kLdsBytes - kStaticBytes));
         if (e != hipSuccess) return e;
         if (dev >= 0 && dev < 64) done[dev].store(true, std::memory_order_release);
@@ -216,17 +253,34 @@ hipError_t ensure_scan_lds() {
     return hipSuccess;
 }
 
-template <int QPL, bool FILTERED, int METRIC>
+// The range sinks (sink.r) take no buffers: top_k, cap and the outputs are 0 / NULL.
+template <int QPL, bool FILTERED, int METRIC, int SINK>
 hipError_t launch_scan(const FlatIvfLists& L, const float* d_queries, int nq, int nprobe, const uint32_t* d_skeys,
                        const uint32_t* d_svals, int64_t n_pairs, int G, int top_k, int cap, int32_t* d_part_ids,
-                       float* d_part_dists, hipStream_t stream) {
-    if (hipError_t e = ensure_scan_lds<QPL, FILTERED, METRIC>()) return e;
-    const size_t lds = kTileBytes + (size_t)G * cap * sizeof(uint64_t);
+                       float* d_part_dists, const SinkArgs<SINK>& sink, hipStream_t stream) {
+    if (hipError_t e = ensure_scan_lds<QPL, FILTERED, METRIC, SINK>()) return e;
+    const size_t lds = kTileBytes + (SINK == kSinkTopK ? (size_t)G * cap * sizeof(uint64_t) : 0);
     const dim3 grid((unsigned)((n_pairs + G - 1) / G)), block(256);
-    flat_ivf_scan_kernel<QPL, FILTERED, METRIC><<<grid, block, lds, stream>>>(L.rows, L.Dp, L.id_offset, L.offsets, L.list_rows, L.nlist,
-                                                                      d_queries, nq, nprobe, d_skeys, d_svals, n_pairs, G, top_k,
-                                                                      cap, d_part_ids, d_part_dists, L.filter);
+    flat_ivf_scan_kernel<QPL, FILTERED, METRIC, SINK><<<grid, block, lds, stream>>>(
+        L.rows, L.Dp, L.id_offset, L.offsets, L.list_rows, L.nlist, d_queries, nq, nprobe, d_skeys, d_svals, n_pairs, G, top_k, cap,
+        d_part_ids, d_part_dists, L.filter, sink);
     return hipGetLastError();
+}
+
+// The instantiation for a group, a filter and a metric.
+template <int SINK>
+auto* scan_of(const FlatIvfLists& L, int G) {
+    auto* launch = G == 16 ? launch_scan<4, false, kFlatL2, SINK> : G == 8 ? launch_scan<2, false, kFlatL2, SINK> : launch_scan<1, false, kFlatL2, SINK>;
+    if (L.filter) launch = G == 16 ? launch_scan<4, true, kFlatL2, SINK> : G == 8 ? launch_scan<2, true, kFlatL2, SINK> : launch_scan<1, true, kFlatL2, SINK>;
+    if (L.metric == kFlatIP) {
+        launch = G == 16 ? launch_scan<4, false, kFlatIP, SINK> : G == 8 ? launch_scan<2, false, kFlatIP, SINK> : launch_scan<1, false, kFlatIP, SINK>;
+        if (L.filter) launch = G == 16 ? launch_scan<4, true, kFlatIP, SINK> : G == 8 ? launch_scan<2, true, kFlatIP, SINK> : launch_scan<1, true, kFlatIP, SINK>;
+    }
+    return launch;
+}
+
+bool range_ok(const FlatIvfRange& r, int nq) {
+    return r.thr && r.counts && (!r.pool || (r.offs && r.pool_n > 0 && r.qa >= 0 && r.qa < r.qb && r.qb <= nq));
 }
 
 // a thread per entry of the merged answer: the key word back to the score's bits, padding to -inf
@@ -295,13 +349,29 @@ hipError_t launch_flat_ivf_scan(const FlatIvfLists& L, const float* d_queries, i
         return hipErrorInvalidValue;
     const int cap = scan_cap(top_k), G = flat_ivf_group(top_k, group);
     const int64_t n_pairs = (int64_t)nq * nprobe;
-    auto* launch = G == 16 ? launch_scan<4, false, kFlatL2> : G == 8 ? launch_scan<2, false, kFlatL2> : launch_scan<1, false, kFlatL2>;
-    if (L.filter) launch = G == 16 ? launch_scan<4, true, kFlatL2> : G == 8 ? launch_scan<2, true, kFlatL2> : launch_scan<1, true, kFlatL2>;
-    if (L.metric == kFlatIP) {
-        launch = G == 16 ? launch_scan<4, false, kFlatIP> : G == 8 ? launch_scan<2, false, kFlatIP> : launch_scan<1, false, kFlatIP>;
-        if (L.filter) launch = G == 16 ? launch_scan<4, true, kFlatIP> : G == 8 ? launch_scan<2, true, kFlatIP> : launch_scan<1, true, kFlatIP>;
-    }
-    return launch(L, d_queries, nq, nprobe, d_skeys, d_svals, n_pairs, G, top_k, cap, d_part_ids, d_part_dists, stream);
+    return scan_of<kSinkTopK>(L, G)(L, d_queries, nq, nprobe, d_skeys, d_svals, n_pairs, G, top_k, cap, d_part_ids, d_part_dists, {},
+                                    stream);
+}
+
+int flat_ivf_range_group(int group) {
+    int g = GM;
+    while (g > 1 && g > group) g >>= 1;
+    return g;
+}
+
+hipError_t launch_flat_ivf_range(const FlatIvfLists& L, const float* d_queries, int nq, int nprobe, const uint32_t* d_skeys,
+                                 const uint32_t* d_svals, int group, const FlatIvfRange& range, hipStream_t stream) {
+    if (nq <= 0) return hipSuccess;
+    if (!L.rows || !L.offsets || !L.list_rows || !d_queries || !d_skeys || !d_svals || !range_ok(range, nq) || L.Dp < 4 ||
+        L.Dp % 4 != 0 || L.Dp > kFlatMaxD || L.nlist < 1 || L.nlist > kIvfMaxLists || nprobe < 1 || nprobe > kIvfMaxProbe ||
+        group < 1 || (int64_t)nq * nprobe > 0x7fffffff ||
+        ((reinterpret_cast<uintptr_t>(L.rows) | reinterpret_cast<uintptr_t>(d_queries)) & 15u))
+        return hipErrorInvalidValue;
+    const int G = flat_ivf_range_group(group);
+    const int64_t n_pairs = (int64_t)nq * nprobe;
+    if (!range.pool)
+        return scan_of<kSinkCount>(L, G)(L, d_queries, nq, nprobe, d_skeys, d_svals, n_pairs, G, 0, 0, nullptr, nullptr, {range}, stream);
+    return scan_of<kSinkEmit>(L, G)(L, d_queries, nq, nprobe, d_skeys, d_svals, n_pairs, G, 0, 0, nullptr, nullptr, {range}, stream);
 }
 
 }  // namespace dpq

@@ -71,7 +71,7 @@ __device__ __forceinline__ void bits_tile(const uint32_t* __restrict__ rp, bool 
 // query, a multiple of CW.  nq * Wp < 2^32 (a slice holds at most kIvfSliceQueries queries of at most 128 words).
 // FILTERED (fbits: the filter's bitmap over the rows): a tile is the next up to 256 eligible rows, compacted into 256
 // row-number slots in front of the buffers (dpq_flat_ivf_device.h's fill_tile); a lane takes its row number from its slot.
-template <int CW, bool FILTERED>
+template <int CW, bool FILTERED, int SINK>
 __global__ __launch_bounds__(256) void flat_ivf_scan_bits_kernel(const uint32_t* __restrict__ rows, int Wp, int64_t id_offset,
                                                                  const int64_t* __restrict__ offsets,
                                                                  const uint32_t* __restrict__ list_rows, int nlist,
@@ -80,7 +80,8 @@ __global__ __launch_bounds__(256) void flat_ivf_scan_bits_kernel(const uint32_t*
                                                                  const uint32_t* __restrict__ svals, int64_t n_pairs, int G,
                                                                  int top_k, int cap, int32_t* __restrict__ part_ids,
                                                                  float* __restrict__ part_dists,
-                                                                 const uint32_t* __restrict__ fbits) {
+                                                                 const uint32_t* __restrict__ fbits,
+                                                                 [[maybe_unused]] SinkArgs<SINK> sink) {
     extern __shared__ __attribute__((aligned(16))) unsigned char flat_ivf_bits_smem[];
     [[maybe_unused]] uint32_t* s_rows = reinterpret_cast<uint32_t*>(flat_ivf_bits_smem);           // [TR], FILTERED only
     uint64_t* buf = reinterpret_cast<uint64_t*>(flat_ivf_bits_smem + (FILTERED ? TR * 4 : 0));  // [G][cap]
@@ -88,6 +89,7 @@ __global__ __launch_bounds__(256) void flat_ivf_scan_bits_kernel(const uint32_t*
     __shared__ uint64_t s_thr[GM];
     const int tid = threadIdx.x, lane = tid & 63;
     const uint64_t below = ((uint64_t)1 << lane) - 1;
+    [[maybe_unused]] RangeLds* rl = nullptr;
     const int64_t p0 = (int64_t)blockIdx.x * G;
     const int np = (int)min((int64_t)G, n_pairs - p0);
     if (tid < GM) {
@@ -103,16 +105,29 @@ __global__ __launch_bounds__(256) void flat_ivf_scan_bits_kernel(const uint32_t*
         const uint32_t list = s_key[s];
         int e = s + 1;
         while (e < np && s_key[e] == list) ++e;
-        const int nqs = e - s;  // queries of the stretch: pairs s .. e - 1, at most GM
+        int nqs = e - s;  // queries of the stretch: pairs s .. e - 1, at most GM
+        if constexpr (SINK != kSinkTopK) {  // the thresholds; emit: only the pairs with hits stay -- maybe a smaller form
+            __shared__ RangeLds s_range;
+            rl = &s_range;
+            nqs = range_begin<SINK>(sink.r, s_val, s_q, s_cnt, s_thr, s_range, s, nqs, tid);
+            if (nqs == 0) {  // (emit only) nothing of the list is read
+                s = e;
+                continue;
+            }
+        }
         int64_t lo = 0, hi = 0;
         if (list < (uint32_t)nlist) {
             lo = offsets[list];
             hi = offsets[list + 1];
         }
-        if (tid < nqs) {
-            s_cnt[tid] = 0u;
-            s_thr[tid] = kFlatNoKey;
-        }
+        if constexpr (SINK == kSinkTopK)
+            if (tid < nqs) {
+                s_cnt[tid] = 0u;
+                s_thr[tid] = kFlatNoKey;
+            }
+        [[maybe_unused]] uint32_t hits[GM];  // count: this lane's passing keys per query, over the stretch
+#pragma unroll
+        for (int j = 0; j < GM; ++j) hits[j] = 0u;
         uint32_t qoff[GM];  // SGPRs: slots beyond the stretch repeat its last query
 #pragma unroll
         for (int j = 0; j < GM; ++j)
@@ -142,17 +157,42 @@ __global__ __launch_bounds__(256) void flat_ivf_scan_bits_kernel(const uint32_t*
             for (int j = 0; j < GM; ++j) {
                 const uint64_t key = ((uint64_t)__float_as_uint(__int2float_rn((int)acc[j])) << 32) | id;
                 const bool p = j < nqs && ok && key < s_thr[j];
+                if constexpr (SINK == kSinkCount) {
+                    hits[j] += p ? 1u : 0u;
+                    continue;
+                }
                 const uint64_t m = __ballot(p);
                 if (m != 0) {
                     const int first = __ffsll((unsigned long long)m) - 1;
                     uint32_t at = 0u;
                     if (lane == first) at = atomicAdd(&s_cnt[j], (uint32_t)__popcll(m));
-                    at = (uint32_t)__shfl((int)at, first);
-                    if (p) buf[(size_t)j * cap + at + (uint32_t)__popcll(m & below)] = key;  // < cap: the tile had room for its 256 rows
+                    at = (uint32_t)__shfl((int)at, first) + (uint32_t)__popcll(m & below);
+                    if constexpr (SINK == kSinkTopK) {
+                        if (p) buf[(size_t)j * cap + at] = key;  // < cap: the tile had room for its 256 rows
+                    } else {
+                        const int64_t to = rl->off[j] + (int64_t)at;
+                        if (p && to >= 0 && to < sink.r.pool_n) sink.r.pool[to] = key;
+                    }
                 }
             }
-            __syncthreads();
-            if (base + (FILTERED ? 0 : TR) < hi) sink_make_room(buf, s_cnt, s_thr, nqs, cap, top_k, tid);
+            if constexpr (SINK == kSinkTopK) {  // (the range sinks need no barrier of their own between two tiles)
+                __syncthreads();
+                if (base + (FILTERED ? 0 : TR) < hi) sink_make_room(buf, s_cnt, s_thr, nqs, cap, top_k, tid);
+            }
+        }
+        if constexpr (SINK != kSinkTopK) {
+            if constexpr (SINK == kSinkCount) {
+                if (hi > lo)
+#pragma unroll
+                    for (int j = 0; j < GM; ++j) {
+                        const uint32_t c = wave_sum(hits[j]);
+                        if (lane == 0 && j < nqs) atomicAdd(&s_cnt[j], c);
+                    }
+                range_counts_out(sink.r, s_val, s_cnt, s, nqs, hi > lo, tid);
+            }
+            __syncthreads();  // the next stretch starts the counts over
+            s = e;
+            continue;
         }
         if (hi > lo) sink_sort(buf, s_cnt, nqs, cap, tid);  // (behind the last tile's closing barrier)
         // the stretch's answers: pair i = q * nprobe + j goes to row j * nq + q.  A padding pair, or an empty list: padding
@@ -174,10 +214,10 @@ hipError_t ensure_scan_lds() {
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
     if (dev < 0 || dev >= 64 || !done[dev].load(std::memory_order_acquire)) {
-        for (const void* k : {reinterpret_cast<const void*>(&flat_ivf_scan_bits_kernel<32, false>),
-                              reinterpret_cast<const void*>(&flat_ivf_scan_bits_kernel<4, false>),
-                              reinterpret_cast<const void*>(&flat_ivf_scan_bits_kernel<32, true>),
-                              reinterpret_cast<const void*>(&flat_ivf_scan_bits_kernel<4, true>)}) {
+        for (const void* k : {reinterpret_cast<const void*>(&flat_ivf_scan_bits_kernel<32, false, kSinkTopK>),
+                              reinterpret_cast<const void*>(&flat_ivf_scan_bits_kernel<4, false, kSinkTopK>),
+                              reinterpret_cast<const void*>(&flat_ivf_scan_bits_kernel<32, true, kSinkTopK>),
+                              reinterpret_cast<const void*>(&flat_ivf_scan_bits_kernel<4, true, kSinkTopK>)}) {
             e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kLdsBytes - kStaticBytes));
             if (e != hipSuccess) return e;
         }
@@ -211,13 +251,41 @@ hipError_t launch_flat_ivf_scan_bits(const FlatIvfListsBits& L, const uint32_t* 
     // the filtered scan's 256 row-number slots never cost a pair: a group's buffers are a power of two of at most 128 KB
     const size_t lds = (L.filter ? (size_t)TR * 4 : 0) + (size_t)G * cap * sizeof(uint64_t);
     if (lds + kStaticBytes > kLdsBytes) return hipErrorInvalidValue;
-    auto* kernel = L.Wp % 32 == 0 ? flat_ivf_scan_bits_kernel<32, false> : flat_ivf_scan_bits_kernel<4, false>;
-    if (L.filter) kernel = L.Wp % 32 == 0 ? flat_ivf_scan_bits_kernel<32, true> : flat_ivf_scan_bits_kernel<4, true>;
+    auto* kernel = L.Wp % 32 == 0 ? flat_ivf_scan_bits_kernel<32, false, kSinkTopK> : flat_ivf_scan_bits_kernel<4, false, kSinkTopK>;
+    if (L.filter) kernel = L.Wp % 32 == 0 ? flat_ivf_scan_bits_kernel<32, true, kSinkTopK> : flat_ivf_scan_bits_kernel<4, true, kSinkTopK>;
     kernel<<<dim3((unsigned)((n_pairs + G - 1) / G)), dim3(256), lds, stream>>>(L.rows, L.Wp, L.id_offset, L.offsets, L.list_rows,
                                                                                  L.nlist, d_queries, nq, nprobe, d_skeys, d_svals,
                                                                                  n_pairs, G, top_k, cap, d_part_ids, d_part_dists,
-                                                                                 L.filter);
+                                                                                 L.filter, {});
     return hipGetLastError();
+}
+
+// The range sinks: the only dynamic LDS is a filtered scan's 256 row-number slots.
+template <int SINK>
+hipError_t launch_range(const FlatIvfListsBits& L, const uint32_t* d_queries, int nq, int nprobe, const uint32_t* d_skeys,
+                        const uint32_t* d_svals, int G, const FlatIvfRange& r, hipStream_t stream) {
+    const int64_t n_pairs = (int64_t)nq * nprobe;
+    auto* kernel = L.Wp % 32 == 0 ? flat_ivf_scan_bits_kernel<32, false, SINK> : flat_ivf_scan_bits_kernel<4, false, SINK>;
+    if (L.filter) kernel = L.Wp % 32 == 0 ? flat_ivf_scan_bits_kernel<32, true, SINK> : flat_ivf_scan_bits_kernel<4, true, SINK>;
+    kernel<<<dim3((unsigned)((n_pairs + G - 1) / G)), dim3(256), L.filter ? (size_t)TR * 4 : 0, stream>>>(
+        L.rows, L.Wp, L.id_offset, L.offsets, L.list_rows, L.nlist, d_queries, nq, nprobe, d_skeys, d_svals, n_pairs, G, 0, 0, nullptr,
+        nullptr, L.filter, {r});
+    return hipGetLastError();
+}
+
+hipError_t launch_flat_ivf_range_bits(const FlatIvfListsBits& L, const uint32_t* d_queries, int nq, int nprobe,
+                                      const uint32_t* d_skeys, const uint32_t* d_svals, int group, const FlatIvfRange& r,
+                                      hipStream_t stream) {
+    if (nq <= 0) return hipSuccess;
+    if (!L.rows || !L.offsets || !L.list_rows || !d_queries || !d_skeys || !d_svals || !r.thr || !r.counts ||
+        (r.pool && (!r.offs || r.pool_n < 1 || r.qa < 0 || r.qa >= r.qb || r.qb > nq)) || L.Wp < 4 || L.Wp % 4 != 0 ||
+        L.Wp * 4 > flat_bits_row_bytes(kFlatBitsMaxD) || L.nlist < 1 || L.nlist > kIvfMaxLists || nprobe < 1 ||
+        nprobe > kIvfMaxProbe || group < 1 || (int64_t)nq * nprobe > 0x7fffffff || (int64_t)nq * L.Wp > 0xffffffffll ||
+        ((reinterpret_cast<uintptr_t>(L.rows) | reinterpret_cast<uintptr_t>(d_queries)) & 15u))
+        return hipErrorInvalidValue;
+    const int G = flat_ivf_range_group(group);
+    return r.pool ? launch_range<kSinkEmit>(L, d_queries, nq, nprobe, d_skeys, d_svals, G, r, stream)
+                  : launch_range<kSinkCount>(L, d_queries, nq, nprobe, d_skeys, d_svals, G, r, stream);
 }
 
 }  // namespace dpq

@@ -88,6 +88,87 @@ __device__ __forceinline__ void sink_emit(const uint64_t* b, uint32_t cnt, int t
     }
 }
 
+// ---- the range sink --------------------------------------------------------------------------------------
+// A scan kernel's last template argument says where its keys go: kSinkTopK, the buffers above; kSinkCount and kSinkEmit,
+// the two passes of a range search (dpq_flat_ivf.h's FlatIvfRange), which keep NO key buffers in LDS.  Both take a pair's
+// threshold from the caller, once per stretch, and never lower it.  Count: a lane counts its passing keys in registers
+// over all tiles of the stretch; at the stretch's end one wavefront reduction and one LDS atomic per wavefront and query,
+// and the sum goes out under the pair's value word.  Emit: range_begin drops the pairs without hits and compacts the
+// rest in place, so everything behind it -- the staged queries, the active wavefronts, the MFMA's N side, the binary
+// scan's 4 / 8 / 16-query form -- sees a shorter stretch; a passing key takes its slot from an LDS atomic on its pair's
+// counter and goes to the pool with an ordinary store.
+constexpr int kSinkTopK = 0, kSinkCount = 1, kSinkEmit = 2;
+
+// The kernels' last argument: nothing for the top-k sink.
+template <int SINK> struct SinkArgs { FlatIvfRange r; };
+template <> struct SinkArgs<kSinkTopK> {};
+
+// The pair-offset words of the range modes; the top-k kernels declare none.
+struct RangeLds {
+    int64_t off[kFlatIvfGroupMax];  // emit: where a surviving pair's region starts in the pool
+    uint32_t nk;                    // emit: the stretch's surviving pairs
+};
+
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o);
+    return v;
+}
+
+// The start of a stretch -- pairs s .. s + nqs - 1 of the run, nqs <= 16 -- in a range mode; every thread calls it behind
+// a barrier that published s_val / s_q.  Returns the queries the stretch goes on with, the same in every thread: all of
+// them when counting (the counts and thresholds are in place behind the caller's next barrier); when emitting, the pairs
+// that have hits and whose query is of the launch's sub-batch, moved to the front of s_val / s_q in order, their counters,
+// thresholds and pool offsets set, behind a barrier.  One wavefront compacts: its reads of a slot come before its writes.
+template <int SINK>
+__device__ __forceinline__ int range_begin(const FlatIvfRange& R, uint32_t* s_val, uint32_t* s_q, uint32_t* s_cnt, uint64_t* s_thr,
+                                           RangeLds& rl, int s, int nqs, int tid) {
+    if constexpr (SINK == kSinkCount) {
+        if (tid < nqs) {
+            s_cnt[tid] = 0u;
+            s_thr[tid] = R.thr[s_q[s + tid]];
+        }
+        return nqs;
+    } else {
+        if (tid < 64) {
+            uint32_t val = 0u, q = 0u;
+            bool keep = false;
+            if (tid < nqs) {
+                val = s_val[s + tid];
+                q = s_q[s + tid];
+                keep = (int)q >= R.qa && (int)q < R.qb && R.counts[val] > 0;
+            }
+            const uint64_t m = __ballot(keep);
+            if (keep) {
+                const int slot = __popcll(m & (((uint64_t)1 << tid) - 1));
+                s_val[s + slot] = val;
+                s_q[s + slot] = q;
+                s_cnt[slot] = 0u;
+                s_thr[slot] = R.thr[q];
+                rl.off[slot] = R.offs[val] - R.pool_base;
+            }
+            if (tid == 0) rl.nk = (uint32_t)__popcll(m);
+        }
+        __syncthreads();
+        const int nk = (int)rl.nk;
+        __syncthreads();  // a stretch without pairs is left at once: the next one's count must not overtake this read
+        return nk;
+    }
+}
+
+// Emit: the key of surviving pair qs to its next slot.
+__device__ __forceinline__ void range_put(const FlatIvfRange& R, const RangeLds& rl, uint32_t* s_cnt, int qs, uint64_t key) {
+    const int64_t at = rl.off[qs] + (int64_t)atomicAdd(&s_cnt[qs], 1u);
+    if (at >= 0 && at < R.pool_n) R.pool[at] = key;
+}
+
+// Count: the end of a stretch, behind the atomics that added the wavefronts' sums to s_cnt.  list_read: the stretch had rows.
+__device__ __forceinline__ void range_counts_out(const FlatIvfRange& R, const uint32_t* s_val, const uint32_t* s_cnt, int s, int nqs,
+                                                 bool list_read, int tid) {
+    __syncthreads();
+    if (tid < nqs) R.counts[s_val[s + tid]] = list_read ? (int64_t)s_cnt[tid] : 0;
+}
+
 // ---- the filled tile of a scan under an id filter -------------------------------------------------------
 // A tile of a filtered scan is the next up to kFlatIvfTileRows ELIGIBLE rows of the list, not its next 256 row numbers.
 // From list position `pos` on the workgroup reads row numbers in chunks of 256, a thread to a row number, and tests the

@@ -114,7 +114,7 @@ __device__ __forceinline__ void load_slice(uint4 (&pre)[4], const uint32_t* __re
 
 // grid: the runs; 256 threads; dynamic LDS: the tiles, then G buffers of cap = 2 P2 keys.  Wr: the words of a stored row,
 // a multiple of four.
-template <int FORMAT, int QPL, bool FILTERED, int METRIC>
+template <int FORMAT, int QPL, bool FILTERED, int METRIC, int SINK>
 __global__ __launch_bounds__(256) void flat_ivf_scan_narrow_kernel(const uint32_t* __restrict__ rows, int Wr, int64_t id_offset,
                                                                    const int64_t* __restrict__ offsets,
                                                                    const uint32_t* __restrict__ list_rows, int nlist,
@@ -123,7 +123,8 @@ __global__ __launch_bounds__(256) void flat_ivf_scan_narrow_kernel(const uint32_
                                                                    const uint32_t* __restrict__ svals, int64_t n_pairs, int G,
                                                                    int top_k, int cap, int32_t* __restrict__ part_ids,
                                                                    float* __restrict__ part_dists,
-                                                                   const uint32_t* __restrict__ fbits) {
+                                                                   const uint32_t* __restrict__ fbits,
+                                                                   [[maybe_unused]] SinkArgs<SINK> sink) {
     constexpr int DW = word_dims<FORMAT>, SD = SW * DW;  // dimensions of a word and of a slice
     constexpr int UNR = 8 / DW;                          // words the sum is unrolled by: eight dimensions
     extern __shared__ __attribute__((aligned(16))) unsigned char flat_ivf_narrow_smem[];
@@ -137,6 +138,7 @@ __global__ __launch_bounds__(256) void flat_ivf_scan_narrow_kernel(const uint32_
     const int Dp = Wr * DW;
     [[maybe_unused]] const float2* quant = flat_sq_quant_of(rows, Dp);  // quantised rows only
     const int tid = threadIdx.x, tx = tid & 63, ty = tid >> 6;
+    [[maybe_unused]] RangeLds* rl = nullptr;
     const int64_t p0 = (int64_t)blockIdx.x * G;
     const int np = (int)min((int64_t)G, n_pairs - p0);
     if (tid < GM) {
@@ -152,16 +154,29 @@ __global__ __launch_bounds__(256) void flat_ivf_scan_narrow_kernel(const uint32_
         const uint32_t list = s_key[s];
         int e = s + 1;
         while (e < np && s_key[e] == list) ++e;
-        const int nqs = e - s;  // queries of the stretch: pairs s .. e - 1
+        int nqs = e - s;  // queries of the stretch: pairs s .. e - 1
+        if constexpr (SINK != kSinkTopK) {  // the thresholds; emit: only the pairs with hits stay, compacted
+            __shared__ RangeLds s_range;
+            rl = &s_range;
+            nqs = range_begin<SINK>(sink.r, s_val, s_q, s_cnt, s_thr, s_range, s, nqs, tid);
+            if (nqs == 0) {  // (emit only) nothing of the list is read
+                s = e;
+                continue;
+            }
+        }
         int64_t lo = 0, hi = 0;
         if (list < (uint32_t)nlist) {
             lo = offsets[list];
             hi = offsets[list + 1];
         }
-        if (tid < nqs) {
-            s_cnt[tid] = 0u;
-            s_thr[tid] = kFlatNoKey;
-        }
+        if constexpr (SINK == kSinkTopK)
+            if (tid < nqs) {
+                s_cnt[tid] = 0u;
+                s_thr[tid] = kFlatNoKey;
+            }
+        [[maybe_unused]] uint32_t hits[QPL];  // count: this lane's passing keys per query it owns, over the stretch
+#pragma unroll
+        for (int i = 0; i < QPL; ++i) hits[i] = 0u;
         const bool active = QPL * ty < nqs;  // (a wavefront's lanes share ty)
         for (int64_t base = lo; base < hi; base += FILTERED ? 0 : TR) {
             __syncthreads();  // the tile before is done with s_rows; the first tile: the counts above are in place
@@ -246,12 +261,31 @@ __global__ __launch_bounds__(256) void flat_ivf_scan_narrow_kernel(const uint32_
                         const uint32_t row = s_rows[4 * tx + j];
                         if (row == kNoRow) continue;
                         const uint64_t key = make_key<METRIC>(acc[i][j], (uint32_t)(id_offset + (int64_t)row));
-                        if (key < thr) b[atomicAdd(&s_cnt[qs], 1u)] = key;  // < cap: the tile had room for its 256 rows
+                        if (key >= thr) continue;
+                        if constexpr (SINK == kSinkTopK) b[atomicAdd(&s_cnt[qs], 1u)] = key;  // < cap: the tile had room for its 256 rows
+                        else if constexpr (SINK == kSinkCount) ++hits[i];
+                        else range_put(sink.r, *rl, s_cnt, qs, key);
                     }
                 }
             }
-            __syncthreads();
-            if (base + (FILTERED ? 0 : TR) < hi) sink_make_room(buf, s_cnt, s_thr, nqs, cap, top_k, tid);
+            if constexpr (SINK == kSinkTopK) {  // (the range sinks need no barrier of their own between two tiles)
+                __syncthreads();
+                if (base + (FILTERED ? 0 : TR) < hi) sink_make_room(buf, s_cnt, s_thr, nqs, cap, top_k, tid);
+            }
+        }
+        if constexpr (SINK != kSinkTopK) {
+            if constexpr (SINK == kSinkCount) {
+                if (active && hi > lo)  // (a wavefront's lanes share their queries)
+#pragma unroll
+                    for (int i = 0; i < QPL; ++i) {
+                        const uint32_t c = wave_sum(hits[i]);
+                        if (tx == 0 && QPL * ty + i < nqs) atomicAdd(&s_cnt[QPL * ty + i], c);
+                    }
+                range_counts_out(sink.r, s_val, s_cnt, s, nqs, hi > lo, tid);
+            }
+            __syncthreads();  // the next stretch starts the counts over
+            s = e;
+            continue;
         }
         if (hi > lo) sink_sort(buf, s_cnt, nqs, cap, tid);  // (behind the last tile's closing barrier)
         // the stretch's answers: pair i = q * nprobe + j goes to row j * nq + q.  A padding pair, or an empty list: padding
@@ -267,14 +301,15 @@ __global__ __launch_bounds__(256) void flat_ivf_scan_narrow_kernel(const uint32_
 }
 
 // hipFuncSetAttribute is per device
-template <int FORMAT, int QPL, bool FILTERED, int METRIC>
+template <int FORMAT, int QPL, bool FILTERED, int METRIC, int SINK>
 hipError_t ensure_scan_lds() {
+    if constexpr (SINK != kSinkTopK) return hipSuccess;  // the range sinks' tiles fit the default 64 KB
     static std::atomic<bool> done[64];
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
     if (dev < 0 || dev >= 64 || !done[dev].load(std::memory_order_acquire)) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&flat_ivf_scan_narrow_kernel<FORMAT, QPL, FILTERED, METRIC>),
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&flat_ivf_scan_narrow_kernel<FORMAT, QPL, FILTERED, METRIC, SINK>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kLdsBytes - kStaticBytes));
         if (e != hipSuccess) return e;
         if (dev >= 0 && dev < 64) done[dev].store(true, std::memory_order_release);
@@ -290,33 +325,44 @@ struct ScanArgs {
     int32_t* part_ids;
     float* part_dists;
     hipStream_t stream;
+    const FlatIvfRange* range = nullptr;  // the range sinks: top_k 0, no outputs
 };
 
-template <int FORMAT, int QPL, bool FILTERED, int METRIC>
+template <int FORMAT, int QPL, bool FILTERED, int METRIC, int SINK>
 hipError_t launch_scan(const FlatIvfListsNarrow& L, const ScanArgs& a) {
-    if (hipError_t e = ensure_scan_lds<FORMAT, QPL, FILTERED, METRIC>()) return e;
-    const int cap = scan_cap(a.top_k);
+    if (hipError_t e = ensure_scan_lds<FORMAT, QPL, FILTERED, METRIC, SINK>()) return e;
+    const int cap = SINK == kSinkTopK ? scan_cap(a.top_k) : 0;
     const int64_t n_pairs = (int64_t)a.nq * a.nprobe;
     const size_t lds = tile_bytes(FORMAT) + (size_t)a.G * cap * sizeof(uint64_t);
     const dim3 grid((unsigned)((n_pairs + a.G - 1) / a.G)), block(256);
-    flat_ivf_scan_narrow_kernel<FORMAT, QPL, FILTERED, METRIC><<<grid, block, lds, a.stream>>>(
+    SinkArgs<SINK> sink;
+    if constexpr (SINK != kSinkTopK) sink.r = *a.range;
+    flat_ivf_scan_narrow_kernel<FORMAT, QPL, FILTERED, METRIC, SINK><<<grid, block, lds, a.stream>>>(
         static_cast<const uint32_t*>(L.rows), L.Dp / word_dims<FORMAT>, L.id_offset, L.offsets, L.list_rows, L.nlist, a.queries,
-        a.nq, a.nprobe, a.skeys, a.svals, n_pairs, a.G, a.top_k, cap, a.part_ids, a.part_dists, L.filter);
+        a.nq, a.nprobe, a.skeys, a.svals, n_pairs, a.G, a.top_k, cap, a.part_ids, a.part_dists, L.filter, sink);
     return hipGetLastError();
 }
 
-template <int FORMAT, int METRIC>
+template <int FORMAT, int METRIC, int SINK>
 hipError_t launch_scan_by(const FlatIvfListsNarrow& L, const ScanArgs& a) {
-    if (L.filter) return a.G == 16 ? launch_scan<FORMAT, 4, true, METRIC>(L, a) : a.G == 8 ? launch_scan<FORMAT, 2, true, METRIC>(L, a)
-                                                                                          : launch_scan<FORMAT, 1, true, METRIC>(L, a);
-    if (a.G == 16) return launch_scan<FORMAT, 4, false, METRIC>(L, a);
-    if (a.G == 8) return launch_scan<FORMAT, 2, false, METRIC>(L, a);
-    return launch_scan<FORMAT, 1, false, METRIC>(L, a);
+    if (L.filter) return a.G == 16 ? launch_scan<FORMAT, 4, true, METRIC, SINK>(L, a) : a.G == 8 ? launch_scan<FORMAT, 2, true, METRIC, SINK>(L, a)
+                                                                                                : launch_scan<FORMAT, 1, true, METRIC, SINK>(L, a);
+    if (a.G == 16) return launch_scan<FORMAT, 4, false, METRIC, SINK>(L, a);
+    if (a.G == 8) return launch_scan<FORMAT, 2, false, METRIC, SINK>(L, a);
+    return launch_scan<FORMAT, 1, false, METRIC, SINK>(L, a);
 }
 
-template <int FORMAT>
+template <int FORMAT, int SINK>
 hipError_t launch_scan_of(const FlatIvfListsNarrow& L, const ScanArgs& a) {
-    return L.metric == kFlatIP ? launch_scan_by<FORMAT, kFlatIP>(L, a) : launch_scan_by<FORMAT, kFlatL2>(L, a);
+    return L.metric == kFlatIP ? launch_scan_by<FORMAT, kFlatIP, SINK>(L, a) : launch_scan_by<FORMAT, kFlatL2, SINK>(L, a);
+}
+
+template <int SINK>
+hipError_t launch_scan_format(const FlatIvfListsNarrow& L, const ScanArgs& a) {
+    if (L.format == kFlatF16) return launch_scan_of<kFlatF16, SINK>(L, a);
+    if (L.format == kFlatBF16) return launch_scan_of<kFlatBF16, SINK>(L, a);
+    if (L.format == kFlatSQ8) return launch_scan_of<kFlatSQ8, SINK>(L, a);
+    return launch_scan_of<kFlatSQ4, SINK>(L, a);
 }
 
 bool is_narrow(int format) { return format == kFlatF16 || format == kFlatBF16 || format == kFlatSQ8 || format == kFlatSQ4; }
@@ -360,10 +406,21 @@ hipError_t launch_flat_ivf_scan_narrow(const FlatIvfListsNarrow& L, const float*
         return hipErrorInvalidValue;
     const ScanArgs a{d_queries, nq, nprobe, d_skeys, d_svals, flat_ivf_group_narrow(L.format, top_k, group), top_k, d_part_ids,
                      d_part_dists, stream};
-    if (L.format == kFlatF16) return launch_scan_of<kFlatF16>(L, a);
-    if (L.format == kFlatBF16) return launch_scan_of<kFlatBF16>(L, a);
-    if (L.format == kFlatSQ8) return launch_scan_of<kFlatSQ8>(L, a);
-    return launch_scan_of<kFlatSQ4>(L, a);
+    return launch_scan_format<kSinkTopK>(L, a);
+}
+
+hipError_t launch_flat_ivf_range_narrow(const FlatIvfListsNarrow& L, const float* d_queries, int nq, int nprobe,
+                                        const uint32_t* d_skeys, const uint32_t* d_svals, int group, const FlatIvfRange& r,
+                                        hipStream_t stream) {
+    if (nq <= 0) return hipSuccess;
+    if (!is_narrow(L.format) || !L.rows || !L.offsets || !L.list_rows || !d_queries || !d_skeys || !d_svals || !r.thr || !r.counts ||
+        (r.pool && (!r.offs || r.pool_n < 1 || r.qa < 0 || r.qa >= r.qb || r.qb > nq)) || L.Dp < pad_of(L.format) ||
+        L.Dp % pad_of(L.format) != 0 || L.Dp > kFlatMaxD || L.nlist < 1 || L.nlist > kIvfMaxLists || nprobe < 1 ||
+        nprobe > kIvfMaxProbe || group < 1 || (int64_t)nq * nprobe > 0x7fffffff ||
+        ((reinterpret_cast<uintptr_t>(L.rows) | reinterpret_cast<uintptr_t>(d_queries)) & 15u))
+        return hipErrorInvalidValue;
+    const ScanArgs a{d_queries, nq, nprobe, d_skeys, d_svals, flat_ivf_range_group(group), 0, nullptr, nullptr, stream, &r};
+    return r.pool ? launch_scan_format<kSinkEmit>(L, a) : launch_scan_format<kSinkCount>(L, a);
 }
 
 }  // namespace dpq

@@ -68,7 +68,7 @@ __global__ __launch_bounds__(256) void flat_ivf_widen_kernel(const uint8_t* __re
 // METRIC kFlatIP: the score is the int32 S of dpq_flat_u8.hip's header -- the int8 dot product, plus, for unsigned rows (CORR),
 // rs[row] + qs[query], which come in the place of the norms (vnorm, qnorm); without CORR neither array is read.  The key
 // word is flat_ip_word of the converted score's bits.  kFlatL2 always has CORR: its norms.
-template <bool FILTERED, int METRIC, bool CORR>
+template <bool FILTERED, int METRIC, bool CORR, int SINK>
 __global__ __launch_bounds__(256) void flat_ivf_scan_u8_kernel(const int8_t* __restrict__ rows, const int32_t* __restrict__ vnorm,
                                                                int Dp, int64_t id_offset, const int64_t* __restrict__ offsets,
                                                                const uint32_t* __restrict__ list_rows, int nlist,
@@ -78,7 +78,8 @@ __global__ __launch_bounds__(256) void flat_ivf_scan_u8_kernel(const int8_t* __r
                                                                const uint32_t* __restrict__ svals, int64_t n_pairs, int G,
                                                                int top_k, int cap, int32_t* __restrict__ part_ids,
                                                                float* __restrict__ part_dists,
-                                                               const uint32_t* __restrict__ fbits) {
+                                                               const uint32_t* __restrict__ fbits,
+                                                               [[maybe_unused]] SinkArgs<SINK> sink) {
     extern __shared__ __attribute__((aligned(16))) unsigned char flat_ivf_u8_smem[];
     const int QS = Dp + QPAD;                                                          // bytes between two query rows
     int8_t* Qs = reinterpret_cast<int8_t*>(flat_ivf_u8_smem);                          // [GM][QS]
@@ -88,6 +89,7 @@ __global__ __launch_bounds__(256) void flat_ivf_scan_u8_kernel(const int8_t* __r
     __shared__ int32_t s_qn[GM];
     __shared__ uint64_t s_thr[GM];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r = lane & 15, h = lane >> 4;
+    [[maybe_unused]] RangeLds* rl = nullptr;
     const int64_t p0 = (int64_t)blockIdx.x * G;
     const int np = (int)min((int64_t)G, n_pairs - p0);
     if (tid < GM) {
@@ -105,17 +107,29 @@ __global__ __launch_bounds__(256) void flat_ivf_scan_u8_kernel(const int8_t* __r
         const uint32_t list = s_key[s];
         int e = s + 1;
         while (e < np && s_key[e] == list) ++e;
-        const int nqs = e - s;  // queries of the stretch: pairs s .. e - 1, at most GM
+        int nqs = e - s;  // queries of the stretch: pairs s .. e - 1, at most GM
+        if constexpr (SINK != kSinkTopK) {  // the thresholds; emit: only the pairs with hits stay -- a shorter N side
+            __shared__ RangeLds s_range;
+            rl = &s_range;
+            nqs = range_begin<SINK>(sink.r, s_val, s_q, s_cnt, s_thr, s_range, s, nqs, tid);
+            if (nqs == 0) {  // (emit only) nothing of the list is read
+                s = e;
+                continue;
+            }
+        }
         int64_t lo = 0, hi = 0;
         if (list < (uint32_t)nlist) {
             lo = offsets[list];
             hi = offsets[list + 1];
         }
         if (tid < nqs) {
-            s_cnt[tid] = 0u;
-            s_thr[tid] = kFlatNoKey;
+            if constexpr (SINK == kSinkTopK) {
+                s_cnt[tid] = 0u;
+                s_thr[tid] = kFlatNoKey;
+            }
             s_qn[tid] = CORR ? qnorm[s_q[s + tid]] : 0;
         }
+        [[maybe_unused]] uint32_t hits = 0u;  // count: this lane's passing keys for query r, over the stretch
         if (hi > lo)  // the stretch's queries, once for all its tiles (the first tile's barriers publish them)
             for (int idx = tid; idx < GM * cpr; idx += 256) {
                 const int slot = idx / cpr, c = idx - slot * cpr;
@@ -179,11 +193,28 @@ __global__ __launch_bounds__(256) void flat_ivf_scan_u8_kernel(const int8_t* __r
                         const int d = METRIC == kFlatIP ? acc[i][c] + vn[i][c] + qn : vn[i][c] + qn - 2 * acc[i][c];
                         const uint32_t u = __float_as_uint(__int2float_rn(d));
                         const uint64_t key = ((uint64_t)(METRIC == kFlatIP ? flat_ip_word(u) : u) << 32) | (uint32_t)(id_offset + (int64_t)row);
-                        if (key < thr) b[atomicAdd(&s_cnt[r], 1u)] = key;  // < cap: the tile had room for its 256 rows
+                        if (key >= thr) continue;
+                        if constexpr (SINK == kSinkTopK) b[atomicAdd(&s_cnt[r], 1u)] = key;  // < cap: the tile had room for its 256 rows
+                        else if constexpr (SINK == kSinkCount) ++hits;
+                        else range_put(sink.r, *rl, s_cnt, r, key);
                     }
             }
-            __syncthreads();
-            if (base + (FILTERED ? 0 : TR) < hi) sink_make_room(buf, s_cnt, s_thr, nqs, cap, top_k, tid);
+            if constexpr (SINK == kSinkTopK) {  // (the range sinks need no barrier of their own between two tiles)
+                __syncthreads();
+                if (base + (FILTERED ? 0 : TR) < hi) sink_make_room(buf, s_cnt, s_thr, nqs, cap, top_k, tid);
+            }
+        }
+        if constexpr (SINK != kSinkTopK) {
+            if constexpr (SINK == kSinkCount) {  // the four lanes of a wavefront that share query r, then one atomic
+                uint32_t c = hits;
+                c += (uint32_t)__shfl_xor((int)c, 16);
+                c += (uint32_t)__shfl_xor((int)c, 32);
+                if (h == 0 && r < nqs && hi > lo) atomicAdd(&s_cnt[r], c);
+                range_counts_out(sink.r, s_val, s_cnt, s, nqs, hi > lo, tid);
+            }
+            __syncthreads();  // the next stretch starts the counts and the queries over
+            s = e;
+            continue;
         }
         if (hi > lo) sink_sort(buf, s_cnt, nqs, cap, tid);  // (behind the last tile's closing barrier)
         // the stretch's answers: pair i = q * nprobe + j goes to row j * nq + q.  A padding pair, or an empty list: padding
@@ -199,14 +230,15 @@ __global__ __launch_bounds__(256) void flat_ivf_scan_u8_kernel(const int8_t* __r
 }
 
 // hipFuncSetAttribute is per device
-template <bool FILTERED, int METRIC, bool CORR>
+template <bool FILTERED, int METRIC, bool CORR, int SINK>
 hipError_t ensure_scan_lds() {
+    if constexpr (SINK != kSinkTopK) return hipSuccess;  // the range sinks' tiles fit the default 64 KB
     static std::atomic<bool> done[64];
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
     if (dev < 0 || dev >= 64 || !done[dev].load(std::memory_order_acquire)) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&flat_ivf_scan_u8_kernel<FILTERED, METRIC, CORR>),
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&flat_ivf_scan_u8_kernel<FILTERED, METRIC, CORR, SINK>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kLdsBytes - kStaticBytes));
         if (e != hipSuccess) return e;
         if (dev >= 0 && dev < 64) done[dev].store(true, std::memory_order_release);
@@ -223,18 +255,30 @@ struct ScanArgs {
     int32_t* part_ids;
     float* part_dists;
     hipStream_t stream;
+    const FlatIvfRange* range = nullptr;  // the range sinks: top_k 0, no outputs
 };
 
-template <bool FILTERED, int METRIC, bool CORR>
+template <bool FILTERED, int METRIC, bool CORR, int SINK>
 hipError_t launch_scan(const FlatIvfListsU8& L, const ScanArgs& a) {
-    if (hipError_t e = ensure_scan_lds<FILTERED, METRIC, CORR>()) return e;
-    const int cap = scan_cap(a.top_k);
+    if (hipError_t e = ensure_scan_lds<FILTERED, METRIC, CORR, SINK>()) return e;
+    const int cap = SINK == kSinkTopK ? scan_cap(a.top_k) : 0;
     const int64_t n_pairs = (int64_t)a.nq * a.nprobe;
     const size_t lds = tile_bytes(L.Dp) + (size_t)a.G * cap * sizeof(uint64_t);
-    flat_ivf_scan_u8_kernel<FILTERED, METRIC, CORR><<<dim3((unsigned)((n_pairs + a.G - 1) / a.G)), dim3(256), lds, a.stream>>>(
+    SinkArgs<SINK> sink;
+    if constexpr (SINK != kSinkTopK) sink.r = *a.range;
+    flat_ivf_scan_u8_kernel<FILTERED, METRIC, CORR, SINK><<<dim3((unsigned)((n_pairs + a.G - 1) / a.G)), dim3(256), lds, a.stream>>>(
         L.rows, L.norm, L.Dp, L.id_offset, L.offsets, L.list_rows, L.nlist, a.queries, a.qterm, a.nq, a.nprobe, a.skeys, a.svals,
-        n_pairs, a.G, a.top_k, cap, a.part_ids, a.part_dists, L.filter);
+        n_pairs, a.G, a.top_k, cap, a.part_ids, a.part_dists, L.filter, sink);
     return hipGetLastError();
+}
+
+template <int SINK>
+hipError_t launch_scan_of(const FlatIvfListsU8& L, const ScanArgs& a) {
+    if (L.metric == kFlatIP) {
+        if (L.norm) return L.filter ? launch_scan<true, kFlatIP, true, SINK>(L, a) : launch_scan<false, kFlatIP, true, SINK>(L, a);
+        return L.filter ? launch_scan<true, kFlatIP, false, SINK>(L, a) : launch_scan<false, kFlatIP, false, SINK>(L, a);
+    }
+    return L.filter ? launch_scan<true, kFlatL2, true, SINK>(L, a) : launch_scan<false, kFlatL2, true, SINK>(L, a);
 }
 
 }  // namespace
@@ -270,11 +314,23 @@ hipError_t launch_flat_ivf_scan_u8(const FlatIvfListsU8& L, const int8_t* d_quer
         return hipErrorInvalidValue;
     const ScanArgs a{d_queries, d_qnorm, nq, nprobe, d_skeys, d_svals, flat_ivf_group_u8(top_k, L.Dp, group), top_k, d_part_ids,
                      d_part_dists, stream};
-    if (L.metric == kFlatIP) {
-        if (L.norm) return L.filter ? launch_scan<true, kFlatIP, true>(L, a) : launch_scan<false, kFlatIP, true>(L, a);
-        return L.filter ? launch_scan<true, kFlatIP, false>(L, a) : launch_scan<false, kFlatIP, false>(L, a);
-    }
-    return L.filter ? launch_scan<true, kFlatL2, true>(L, a) : launch_scan<false, kFlatL2, true>(L, a);
+    return launch_scan_of<kSinkTopK>(L, a);
+}
+
+hipError_t launch_flat_ivf_range_u8(const FlatIvfListsU8& L, const int8_t* d_queries, const int32_t* d_qnorm, int nq, int nprobe,
+                                    const uint32_t* d_skeys, const uint32_t* d_svals, int group, const FlatIvfRange& r,
+                                    hipStream_t stream) {
+    if (nq <= 0) return hipSuccess;
+    const bool terms = L.metric != kFlatIP || L.norm || d_qnorm;  // signed rows under kFlatIP take neither array
+    if (L.metric != kFlatL2 && L.metric != kFlatIP) return hipErrorInvalidValue;
+    if (!L.rows || (terms && (!L.norm || !d_qnorm)) || !L.offsets || !L.list_rows || !d_queries || !d_skeys || !d_svals || !r.thr ||
+        !r.counts || (r.pool && (!r.offs || r.pool_n < 1 || r.qa < 0 || r.qa >= r.qb || r.qb > nq)) || L.Dp < kFlatU8KStep ||
+        L.Dp % kFlatU8KStep != 0 || L.Dp > kFlatMaxD || L.nlist < 1 || L.nlist > kIvfMaxLists || nprobe < 1 ||
+        nprobe > kIvfMaxProbe || group < 1 || (int64_t)nq * nprobe > 0x7fffffff ||
+        ((reinterpret_cast<uintptr_t>(L.rows) | reinterpret_cast<uintptr_t>(d_queries)) & 15u))
+        return hipErrorInvalidValue;
+    const ScanArgs a{d_queries, d_qnorm, nq, nprobe, d_skeys, d_svals, flat_ivf_range_group(group), 0, nullptr, nullptr, stream, &r};
+    return r.pool ? launch_scan_of<kSinkEmit>(L, a) : launch_scan_of<kSinkCount>(L, a);
 }
 
 }  // namespace dpq

@@ -1610,7 +1610,7 @@ int dpq_write_vecs(const char* path, const float* vectors, int64_t n, int D);
  *           are padded to the handle's own row padding (8, 16 or 32 dimensions for half, 8-bit, 4-bit rows).  Byte and
  *           binary handles, and a handle with an id map, are DPQ_ERR_ARG (byte and binary handles have calls of their own:
  *           "IVF search over byte vectors" and "IVF search over binary vectors" below).  Squared L2 here (inner product: the *_ip calls below;
- *           an id filter: the *_filtered calls below): no range search, no id maps, no shards, no CLI task and no training of the quantiser or of
+ *           an id filter: the *_filtered calls below; range search: "IVF range search over raw vectors"): no id maps, no shards, no CLI task and no training of the quantiser or of
  *           the centroids here (dpq_sq_train, dpq_ivf_train and dpq_ivf_assign exist).
  *   Ownership  The structure is bound to the handle it was made on and is freed (dpq_flat_ivf_free) BEFORE
  *           dpq_flat_close of that handle; both are used from one thread.
@@ -1682,7 +1682,7 @@ int dpq_flat_ivf_search_device(dpq_flat_ivf* ivf, const float* d_queries, int nq
  *           counts once, a negative probe is padding, an entry >= nlist is DPQ_ERR_ARG as above.
  *   Limits  The byte handle's (D <= 2048) and the structure's above (nlist <= 65536, nprobe <= min(nlist, 1024),
  *           top_k <= 2048, fewer than 2^31 rows).  Squared L2 here (inner product: the *_ip_bytes calls below; an id filter: the
- *           *_filtered calls below): no range search, no shards, no CLI task.  State and ownership as above. */
+ *           *_filtered calls below; range search: the *_range_search*_bytes calls below): no shards, no CLI task.  State and ownership as above. */
 int dpq_flat_ivf_create_bytes(dpq_flat* flat, const int32_t* labels, int64_t n, int nlist, dpq_flat_ivf** out);
 int dpq_flat_ivf_create_bytes_device(dpq_flat* flat, const int32_t* d_labels, int64_t n, int nlist, void* hip_stream,
                                      dpq_flat_ivf** out);
@@ -1720,8 +1720,8 @@ int dpq_flat_ivf_search_bytes_device(dpq_flat_ivf* ivf, const void* d_queries, i
  *           order by (distance bits, id); padding -1 / +inf; a repeated probe counts once, a negative probe is padding, an
  *           entry >= nlist is DPQ_ERR_ARG as above.
  *   Limits  The binary handle's (D <= DPQ_FLAT_BITS_MAX_D) and the structure's above (nlist <= 65536, nprobe <=
- *           min(nlist, 1024), top_k <= 2048, fewer than 2^31 rows).  No range search, no id map, no shards and
- *           no CLI task yet (an id filter: the *_filtered calls below).  State and ownership as above. */
+ *           min(nlist, 1024), top_k <= 2048, fewer than 2^31 rows).  No id map, no shards and
+ *           no CLI task yet (an id filter: the *_filtered calls below; range search: the *_range_search*_bits calls below).  State and ownership as above. */
 int dpq_flat_ivf_create_bits(dpq_flat* flat, const int32_t* labels, int64_t n, int nlist, dpq_flat_ivf** out);
 int dpq_flat_ivf_create_bits_device(dpq_flat* flat, const int32_t* d_labels, int64_t n, int nlist, void* hip_stream,
                                     dpq_flat_ivf** out);
@@ -1751,8 +1751,8 @@ int dpq_flat_ivf_search_bits_device(dpq_flat_ivf* ivf, const uint8_t* d_queries,
  *           rows only: a filter that allows few rows costs row-number reads, not row reads.
  *   Errors  A filter made for another handle (which covers a filter on another device) is DPQ_ERR_ARG, before any
  *           device call; the structure's next call works.  Everything else as in the unfiltered call of the same kind.
- *           Squared L2 and Hamming here; inner product: the *_ip calls below, which take the same filter.  No range search, no id
- *           maps, no shards, no CLI task yet. */
+ *           Squared L2 and Hamming here; inner product: the *_ip calls below, which take the same filter; range search: the
+ *           *_range_search* calls below, which take it too.  No id maps, no shards, no CLI task yet. */
 int dpq_flat_ivf_search_probes_filtered(dpq_flat_ivf* ivf, const float* queries, int nq, const int32_t* probes, int nprobe,
                                         int top_k, int32_t* ids, float* dists, const dpq_flat_filter* filter);
 int dpq_flat_ivf_search_probes_filtered_device(dpq_flat_ivf* ivf, const float* d_queries, int nq, const int32_t* d_probes,
@@ -1801,7 +1801,7 @@ int dpq_flat_ivf_search_filtered_bits_device(dpq_flat_ivf* ivf, const uint8_t* d
  *           as a base.  Byte structures rank their fp32 centroids by the queries widened exactly, as for L2.
  *           dpq_flat_ivf_search_ip* is dpq_flat_ivf_probe_ip* followed by dpq_flat_ivf_search_probes_ip*.  The lists
  *           themselves are what dpq_flat_ivf_build* or the labels made them: dpq_flat_ivf_build keeps assigning by L2.
- *   Errors, limits, state  As in the L2 call of the same kind and the *_filtered calls.  No range search, no id maps, no
+ *   Errors, limits, state  As in the L2 call of the same kind and the *_filtered calls.  Range search: the section below.  No id maps, no
  *           shards, no CLI task yet. */
 int dpq_flat_ivf_probe_ip(dpq_flat_ivf* ivf, const float* queries, int nq, int nprobe, int32_t* lists_out, float* scores_out);
 int dpq_flat_ivf_search_probes_ip(dpq_flat_ivf* ivf, const float* queries, int nq, const int32_t* probes, int nprobe, int top_k,
@@ -1823,6 +1823,50 @@ int dpq_flat_ivf_search_ip_bytes(dpq_flat_ivf* ivf, const void* queries, int nq,
                                  float* scores, const dpq_flat_filter* filter);
 int dpq_flat_ivf_search_ip_bytes_device(dpq_flat_ivf* ivf, const void* d_queries, int nq, int nprobe, int top_k, int32_t* d_ids,
                                         float* d_scores, void* hip_stream, const dpq_flat_filter* filter);
+
+/* ---- IVF range search over raw vectors ----------
+ * FAISS's IndexIVFFlat::range_search (and IndexBinaryIVF's, IndexIVFScalarQuantizer's).  NO REFERENCE COUNTERPART.  Every
+ * row of the lists a query probes within a radius, for every row format a dpq_flat_ivf takes: squared L2 (Hamming for binary
+ * rows), or, in the *_ip calls, every row whose inner product is above a threshold.  `filter` may be NULL (every row).  Host
+ * forms only, as every range call of the library; *out is freed by dpq_range_result_free.
+ *   Answer  For query q, bit for bit, what the handle's own dpq_flat_range_search* / dpq_flat_range_search_ip* returns under a
+ *           filter that allows exactly the rows of the probed lists, intersected with `filter`: the distance or score of the
+ *           search of the same kind, the STRICT rule d < radii[q] (s > thresholds[q]), a query's list ordered by (distance,
+ *           id) or (score descending, id).  A radius <= 0 gives an empty list and +inf every eligible row of the probed
+ *           lists; a threshold of +inf gives an empty list, -inf every eligible row.  Probe rows as in the searches: -1 pads, a
+ *           repeated list counts once.  dpq_flat_ivf_range_search* is dpq_flat_ivf_probe* (by the call's metric) followed by
+ *           dpq_flat_ivf_range_search_probes*.
+ *   How     The list scans of the searches with a second sink: a count pass per slice of 2048 queries, one
+ *           exclusive scan, then per sub-batch of queries whose lists fit a pool of 8 M keys an emit pass that forms
+ *           distances again only for the (query, list) pairs that had hits, a segmented sort, and the keys brought down.  A
+ *           single query with more keys than the pool works in buffers of the call.
+ *   Errors, limits, state  Checked in this order: out NULL, a NULL argument or nq < 0, nprobe outside 1 .. 1024, a NaN radius
+ *           or threshold (before any device work), a filter of another handle, nprobe > nlist, a probe entry >= nlist, a call
+ *           of another kind than the structure's (the *_ip calls on a binary structure included): all DPQ_ERR_ARG; the
+ *           coarse-step forms on a structure without centroids DPQ_ERR_STATE.  nq == 0 gives an empty result.  The pool and
+ *           its sorted twin (64 MB each) belong to the structure and live until dpq_flat_ivf_free.  One call at a time per
+ *           structure.  No id maps, no shards, no CLI task, no device-output forms yet. */
+int dpq_flat_ivf_range_search(dpq_flat_ivf* ivf, const dpq_flat_filter* filter, const float* queries, int nq, int nprobe,
+                              const float* radii, dpq_range_result** out);
+int dpq_flat_ivf_range_search_probes(dpq_flat_ivf* ivf, const dpq_flat_filter* filter, const float* queries, int nq,
+                                     const int32_t* probes, int nprobe, const float* radii, dpq_range_result** out);
+int dpq_flat_ivf_range_search_ip(dpq_flat_ivf* ivf, const dpq_flat_filter* filter, const float* queries, int nq, int nprobe,
+                                 const float* thresholds, dpq_range_result** out);
+int dpq_flat_ivf_range_search_probes_ip(dpq_flat_ivf* ivf, const dpq_flat_filter* filter, const float* queries, int nq,
+                                        const int32_t* probes, int nprobe, const float* thresholds, dpq_range_result** out);
+int dpq_flat_ivf_range_search_bytes(dpq_flat_ivf* ivf, const dpq_flat_filter* filter, const void* queries, int nq, int nprobe,
+                                    const float* radii, dpq_range_result** out);
+int dpq_flat_ivf_range_search_probes_bytes(dpq_flat_ivf* ivf, const dpq_flat_filter* filter, const void* queries, int nq,
+                                           const int32_t* probes, int nprobe, const float* radii, dpq_range_result** out);
+int dpq_flat_ivf_range_search_ip_bytes(dpq_flat_ivf* ivf, const dpq_flat_filter* filter, const void* queries, int nq, int nprobe,
+                                       const float* thresholds, dpq_range_result** out);
+int dpq_flat_ivf_range_search_probes_ip_bytes(dpq_flat_ivf* ivf, const dpq_flat_filter* filter, const void* queries, int nq,
+                                              const int32_t* probes, int nprobe, const float* thresholds,
+                                              dpq_range_result** out);
+int dpq_flat_ivf_range_search_bits(dpq_flat_ivf* ivf, const dpq_flat_filter* filter, const uint8_t* queries, int nq, int nprobe,
+                                   const float* radii, dpq_range_result** out);
+int dpq_flat_ivf_range_search_probes_bits(dpq_flat_ivf* ivf, const dpq_flat_filter* filter, const uint8_t* queries, int nq,
+                                          const int32_t* probes, int nprobe, const float* radii, dpq_range_result** out);
 
 /* ---- measurement -------------------------------------------------------- */
 int dpq_profile_enable(dpq_index* idx, int on);  /* 0 off, 1 every kernel, 2 scan launches only (less event overhead) */
